@@ -12,6 +12,13 @@ rides on another's tail (round-4 verdict).  The same passes driven as a stream o
 second HIP stream under the optimiser's last round: a directory of .npz files through the CLI) are `extras.streamed`
 (`--streamed` makes that the timed mode).  Inputs are resident in HBM when the timed region starts; weights are seeded
 random (the trained checkpoint and ModelNet40 are downloads).  Prints ONE JSON line on rank 0.
+
+A plain run does only what the headline needs: set up, W warm-up passes, K timed passes, the line (its `roofline` object
+comes from the events of the timed passes).  `--full` adds everything measured beside it, each in runs of its own: the
+CPU baseline, `extras` (streamed driving, reference-style GPU baseline, trained-like field, K = 2048, ONet-Opt, ONet-Mesh,
+split precision), `f32_equivalent`, and for N > 1 weak scaling the strong-scaling figure.  `--dump-outputs DIR` writes
+the restored clouds of the last timed pass as DIR/restored_points.npy (float32; inputs and weights are seeded, so two
+builds can be compared output for output).
 """
 import argparse
 import json
@@ -121,6 +128,33 @@ def subsample_like(clouds, k=256, seed=1234):
     return np.stack([c[np.sort(rng.choice(len(c), k, replace=False))] for c in clouds]).astype(np.float32)
 
 
+def usable_cpus():
+    """CPUs this process may run on: its affinity mask, bounded by OMP_NUM_THREADS where that is set (a shared host's budget
+    per job; os.cpu_count() is the whole host's, and threads or workers sized by it only slow each other down)."""
+    n = len(os.sched_getaffinity(0)) if hasattr(os, "sched_getaffinity") else (os.cpu_count() or 1)
+    env = os.environ.get("OMP_NUM_THREADS", "")
+    if env.isdigit() and int(env) > 0:
+        n = min(n, int(env))
+    return max(1, n)
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(d, points):
+    """--dump-outputs: what the timed path returned in its last pass, the restored clouds [clouds, 1024, 3], as d/restored_points.npy
+    (float32).  Above 64 MB (weak scaling over many ranks) an evenly spaced fixed subset of the clouds, whose global indices go to
+    d/restored_points_cloud_index.npy (float64)."""
+    os.makedirs(d, exist_ok=True)
+    a = points.detach().cpu().numpy().astype(np.float32, copy=False)
+    per_cloud = a[0].nbytes + 8
+    if len(a) * per_cloud > DUMP_LIMIT_BYTES:
+        idx = np.arange(0, len(a), -(-len(a) // (DUMP_LIMIT_BYTES // per_cloud)))
+        a = a[idx]
+        np.save(os.path.join(d, "restored_points_cloud_index.npy"), idx.astype(np.float64))
+    np.save(os.path.join(d, "restored_points.npy"), np.ascontiguousarray(a))
+
+
 def host_cpu_model():
     try:
         for line in open("/proc/cpuinfo"):
@@ -175,7 +209,7 @@ def cpu_baseline(clouds, n_sample=16, budget_s=15.0, onet=False, full_run_clouds
     Threads are capped at 16: with one thread per core of a 256-core host the small ops of this loop run
     ~100x slower (measured: 22 s per step), which would say nothing about the CPU path."""
     from oracle import convonet_oracle as O
-    threads = min(os.cpu_count() or 1, 16)
+    threads = min(usable_cpus(), 16)
     torch.set_num_threads(threads)
     if onet:
         from oracle import onet_oracle as OO
@@ -250,7 +284,7 @@ def _cpu_worker_cold(job):
 
 
 def cpu_baseline_pick(base):
-    """ONE `cpu_baseline.value` (round-5 verdict): the WHOLE HOST - cores // 16 oracle processes of 16 threads side by side, the
+    """ONE `cpu_baseline.value` (round-5 verdict): every CPU the run may use - usable_cpus() // 16 oracle processes of 16 threads side by side, the
     sampling in which the reference's loop uses the box best - with the once-per-cloud pre-processing of the single-process sample
     added; the other samplings (one 16-thread process; 4 clouds unscaled; one B = 192 batch on all threads) stay beside it."""
     sat = base.get("host_saturating", {}).get("workers_x16_threads", {})
@@ -268,17 +302,18 @@ def cpu_baseline_pick(base):
                                "batch192_all_threads": base["host_saturating"].get("batch192_all_threads")}
     base.pop("host_saturating", None)
     base.update({"value": round(v, 4), "cores": sat["cores"], "sample": sat["sample"] + "; + SOR / preprocess / encoder once per cloud from the "
-                 "one-process sample", "definition": "THE cpu_baseline: the whole host, %d oracle processes x 16 threads (other_samplings: "
+                 "one-process sample", "definition": "THE cpu_baseline: every CPU the run may use, %d oracle processes x 16 threads (other_samplings: "
                  "smaller or differently batched samples of the same loop - they differ by up to 30 %% and are not the baseline)" % sat.get("workers", 0)})
     return base
 
 
 def cpu_baseline_saturating(base, budget_s=20.0):
     """Two host-SATURATING figures next to the 16-thread one (round-4 verdict): (i) floor(cores / 16) concurrent 16-thread workers on
-    disjoint 16-cloud batches, (ii) the reference's own batch of 192 clouds in ONE process at os.cpu_count() threads (BASELINE.md
-    section 3's setting).  Optimiser loop only (96 % of the path's CPU time), a few steps each, scaled to 501; bounded."""
+    disjoint 16-cloud batches, (ii) the reference's own batch of 192 clouds in ONE process at one thread per core (BASELINE.md
+    section 3's setting).  Optimiser loop only (96 % of the path's CPU time), a few steps each, scaled to 501; bounded.  cores =
+    usable_cpus(), the CPUs this run may use; at most 15 workers, so that with this process no more than 16 hold the GPU open."""
     import multiprocessing as mp
-    cores = os.cpu_count() or 1
+    cores = usable_cpus()
     out = {}
     per_step_16 = None
     try:
@@ -287,7 +322,7 @@ def cpu_baseline_saturating(base, budget_s=20.0):
     except Exception:      # noqa: BLE001
         pass
     try:
-        workers = max(1, cores // 16)
+        workers = max(1, min(15, cores // 16))
         steps = 3 if per_step_16 is None else int(max(2, min(10, budget_s / (3.0 * per_step_16))))
         with mp.get_context("spawn").Pool(workers) as pool:
             t0 = time.perf_counter()
@@ -410,7 +445,7 @@ def trained_like_full(dev, n=N_CLOUDS, n_files=2):
 
 
 def extras(dev):
-    """Bounded side measurements carried in the N = 1 line (a few seconds each; none of them is the headline):
+    """Bounded side measurements carried in the N = 1 --full line (a few seconds each; none of them is the headline):
     the reference's op sequence run unfused by PyTorch-ROCm on the same GPU, and the two ONet rows of SURVEY 8f."""
     import ifdefense_amd as I
     out = {}
@@ -619,6 +654,11 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=10)      # ~1 s per step; the first timed pass has nothing to hide its
     ap.add_argument("--warmup", type=int, default=2)      # pre-processing under, so short runs read ~1.5 % low
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beside the headline, in runs of its own: CPU baseline, extras, f32_equivalent, and "
+                         "the strong-scaling figure of an N > 1 weak-scaling run (--no-cpu-baseline / --no-extras drop parts of it)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the restored clouds of the last timed pass to DIR/restored_points.npy (float32)")
     ap.add_argument("--clouds", type=int, default=N_CLOUDS, help="clouds per GPU per step (default: MN40 test size)")
     ap.add_argument("--scaling", choices=("weak", "strong"), default="weak",
                     help="weak (default): every rank restores its own --clouds clouds; strong: ONE array of --clouds clouds is "
@@ -629,7 +669,7 @@ def main():
                          "optimiser tail) instead of one file at a time with a synchronisation after each (the default: BASELINE configs[1])")
     ap.add_argument("--no-overlap", action="store_true", help="(kept for scripts: the default since round 5) one file at a time")
     ap.add_argument("--no-extras", action="store_true", help="skip the bounded side measurements (reference-style unfused "
-                    "GPU baseline, ONet-Opt, ONet-Mesh) that ride along in the N = 1 line")
+                    "GPU baseline, ONet-Opt, ONet-Mesh) that ride along in the N = 1 --full line")
     ap.add_argument("--dry-run", action="store_true",
                     help="no GPU work: initialise the process group (gloo on a CPU host), shard the clouds, push a placeholder "
                          "of every rank's shard through the real gather, print the JSON line with value null - checks the launch "
@@ -644,6 +684,8 @@ def main():
                     help="PROFILING ONLY (scripts/pmc_bench.sh): run the timed passes in a split-precision mode; the line is then labelled "
                          "as such in metric / dtype / config.arith and is not the BASELINE metric")
     a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
     a.no_overlap = not a.streamed
     onet = a.workload == "onet-opt"
     if onet and a.clouds == N_CLOUDS:
@@ -746,6 +788,8 @@ def main():
     barrier()
     dt = reduce_max(time.perf_counter() - t0)
     assert out.shape == (total, K_POINTS, 3) and bool(torch.isfinite(out).all())
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, out)
 
     kern_ms = [e0.elapsed_time(e1) for e0, e1, _ in ev]
     kern_clouds = [n for _, _, n in ev]
@@ -753,7 +797,7 @@ def main():
     # BASELINE configs #3 / #5 are ONE file over the GPUs of a node (strong scaling).  A weak-scaling run with more than one rank
     # therefore times that too, right behind the headline passes: ONE array of --clouds clouds sharded over the ranks (round-5 verdict)
     strong = None
-    if world > 1 and a.scaling == "weak" and not onet:
+    if a.full and world > 1 and a.scaling == "weak" and not onet:
         s_lo, s_hi, s_per = D.shard_range(a.clouds, rank, world)
         xs = x[:max(0, s_hi - s_lo)]
 
@@ -831,7 +875,7 @@ def main():
             res["roofline"]["note"] = "achieved is in f32-EQUIVALENT FLOP against the f32-MFMA peak; the matrix core executes %dx as many bf16 FLOP" % \
                 (6 if a.profile_precision == "bf16x6" else 3)
         streamed = None
-        if world == 1 and not onet and not a.no_extras and a.no_overlap:
+        if a.full and world == 1 and not onet and not a.no_extras and a.no_overlap:
             # the same passes as a stream of files (what a directory of .npz files through the CLI does): five passes, driver-timed
             torch.cuda.synchronize()
             t1 = time.perf_counter()
@@ -842,12 +886,12 @@ def main():
             streamed = {"value": round(total / dt1, 2), "unit": "clouds/s", "ms_per_file": round(dt1 * 1e3, 2),
                         "what": "the same workload driven as a stream of 8 files: pre-processing of file n+1 on a second HIP stream under "
                                 "file n's last optimiser round (a directory input of the CLI); the first file has nothing to hide under"}
-        if world == 1 and not a.no_cpu_baseline:
+        if a.full and world == 1 and not a.no_cpu_baseline:
             res["cpu_baseline"] = cpu_baseline(my_clouds, onet=onet, full_run_clouds=0 if onet else 4)
             if not onet:
                 res["cpu_baseline"]["host_saturating"] = cpu_baseline_saturating(res["cpu_baseline"])
                 res["cpu_baseline"] = cpu_baseline_pick(res["cpu_baseline"])
-        if world == 1 and not onet and not a.no_extras:
+        if a.full and world == 1 and not onet and not a.no_extras:
             res["extras"] = extras(dev)
             if streamed is not None:
                 res["extras"]["streamed"] = streamed

@@ -136,20 +136,9 @@ def test_marching_cubes_table_is_the_reference_polygonisation():
         assert (tri[cfg, 3 * ntri[cfg]:] == -1).all()
 
 
-def test_marching_cubes_single_cubes_against_live_reference_library():
-    """Every sign configuration x random corner values through (ifd_mc_table + the iso-crossing interpolation) and through
-    the reference's own libmcubes (oracle/_ref): identical vertex coordinates in identical triangle order - the surface
-    is the reference's triangle for triangle, so triangle count, area and orientation (signed volume) agree exactly."""
-    import os
-    import sys
-    import numpy as np
-    import pytest
-    d = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "oracle", "_ref")
-    if not os.path.isdir(d) or not any(f.startswith("mcubes") for f in os.listdir(d)):
-        pytest.skip("oracle/_ref not built (python oracle/build_ref.py needs /root/reference)")
-    sys.path.insert(0, d)
-    import mcubes
-    tri, ntri = _mc_table()
+def _single_cube_cases():
+    """(cfg_eff, val, grid) of every single-cube case: each sign configuration x three seeded draws of corner values, the third
+    with a corner exactly on the iso-value."""
     rng = np.random.default_rng(7)
     corner = np.array(_CORNER, float)
     for cfg in range(256):
@@ -163,18 +152,49 @@ def test_marching_cubes_single_cubes_against_live_reference_library():
             grid = np.empty((2, 2, 2))
             for m in range(8):
                 grid[tuple(corner[m].astype(int))] = val[m]
-            v, t = mcubes.marching_cubes(grid, 0.0)
-            v = v - 0.5                                                          # mcubes.pyx's cell-centre shift
-            ours = []
-            for k in range(ntri[cfg_eff]):
-                for e in tri[cfg_eff, 3 * k:3 * k + 3]:
-                    a, b = _EC[e]
-                    w = 0.5 if val[b] == val[a] else (0.0 - val[a]) / (val[b] - val[a])     # marchingcubes.cpp:290-297
-                    ours.append(corner[a] + (corner[b] - corner[a]) * w)
-            ours = np.array(ours).reshape(-1, 3, 3)
-            theirs = v[t.astype(int)] if len(t) else np.zeros((0, 3, 3))
-            assert ours.shape == theirs.shape, (cfg, rep)
-            np.testing.assert_allclose(ours, theirs, rtol=0, atol=1e-12, err_msg=str((cfg, rep)))
+            yield cfg_eff, val, grid
+
+
+def _ref_single_cube_triangles(mcubes, grid):
+    """The reference libmcubes' triangles [n, 3, 3] of one 2 x 2 x 2 grid at iso-value 0."""
+    v, t = mcubes.marching_cubes(grid, 0.0)
+    v = v - 0.5                                                          # mcubes.pyx's cell-centre shift
+    return v[t.astype(int)] if len(t) else np.zeros((0, 3, 3))
+
+
+def test_marching_cubes_single_cubes_against_live_reference_library():
+    """Every sign configuration x random corner values through (ifd_mc_table + the iso-crossing interpolation) and through
+    the reference's own libmcubes: identical vertex coordinates in identical triangle order - the surface is the reference's
+    triangle for triangle, so triangle count, area and orientation (signed volume) agree exactly.  The reference's triangles
+    for these inputs are stored in tests/golden/mc_single_cubes_ref.npz (tests/golden/make_mc_single_cubes.py); where
+    oracle/_ref is built the live library is asked again and must reproduce them bit for bit."""
+    import sys
+    ref = dict(np.load(os.path.join(ROOT, "tests", "golden", "mc_single_cubes_ref.npz")))
+    starts = np.concatenate([[0], np.cumsum(ref["ntri"])])
+    mcubes = None
+    d = os.path.join(ROOT, "oracle", "_ref")
+    if os.path.isdir(d) and any(f.startswith("mcubes") for f in os.listdir(d)):
+        sys.path.insert(0, d)
+        import mcubes
+    tri, ntri = _mc_table()
+    corner = np.array(_CORNER, float)
+    n_cases = 0
+    for i, (cfg_eff, val, grid) in enumerate(_single_cube_cases()):
+        np.testing.assert_array_equal(val, ref["val"][i])
+        theirs = ref["tris"][starts[i]:starts[i + 1]]
+        if mcubes is not None:
+            np.testing.assert_array_equal(_ref_single_cube_triangles(mcubes, grid), theirs, err_msg=str(i))
+        ours = []
+        for k in range(ntri[cfg_eff]):
+            for e in tri[cfg_eff, 3 * k:3 * k + 3]:
+                a, b = _EC[e]
+                w = 0.5 if val[b] == val[a] else (0.0 - val[a]) / (val[b] - val[a])     # marchingcubes.cpp:290-297
+                ours.append(corner[a] + (corner[b] - corner[a]) * w)
+        ours = np.array(ours).reshape(-1, 3, 3)
+        assert ours.shape == theirs.shape, (i, cfg_eff)
+        np.testing.assert_allclose(ours, theirs, rtol=0, atol=1e-12, err_msg=str((i, cfg_eff)))
+        n_cases += 1
+    assert n_cases == len(ref["ntri"]) == 768
 
 
 def _gfx950_code_objects(path):

@@ -2061,11 +2061,16 @@ def test_rccl_path_under_torchrun(tmp_path):
     r0.close()
     assert np.array_equal(np.load(tmp_path / "out.npy"), want)
 
-    r = launch(["bench.py", "--gpus", "1", "--clouds", "64", "--steps", "1", "--warmup", "1", "--no-cpu-baseline"])
+    r = launch(["bench.py", "--gpus", "1", "--clouds", "64", "--steps", "1", "--warmup", "1", "--no-cpu-baseline",
+                "--dump-outputs", str(tmp_path / "dump")])
     assert r.returncode == 0, r.stdout + r.stderr
     line = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
     assert line["n_gpus"] == 1 and line["value"] > 0 and line["config"]["parallelism"] == "shard1+allgather"
     assert 0.05 < line["roofline"]["frac"] < 1.0
+    assert "extras" not in line and "f32_equivalent" not in line          # a plain run measures the headline only (--full: the rest)
+    pts = np.load(tmp_path / "dump" / "restored_points.npy")              # the last timed pass's restored clouds, unit-sphere normalised
+    assert pts.shape == (64, 1024, 3) and pts.dtype == np.float32
+    np.testing.assert_allclose(np.linalg.norm(pts, axis=-1).max(axis=1), 1.0, rtol=1e-5)
     # --scaling strong (BASELINE configs #3 / #5: ONE array over the ranks) through the same launch line
     r = launch(["bench.py", "--gpus", "1", "--clouds", "70", "--steps", "1", "--warmup", "1", "--no-cpu-baseline", "--no-extras",
                 "--scaling", "strong"])

@@ -105,8 +105,8 @@ def test_bench_line_with_two_ranks_on_one_gpu(tmp_path):
         port = s.getsockname()[1]
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0", IFD_SPLIT="1")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
-           "--master-port", str(port), "bench.py", "--gpus", "2", "--clouds", "40", "--steps", "2", "--warmup", "1", "--no-cpu-baseline",
-           "--no-extras", "--backend", "gloo", "--device", "cuda:0"]
+           "--master-port", str(port), "bench.py", "--gpus", "2", "--clouds", "40", "--steps", "2", "--warmup", "1", "--full",
+           "--no-cpu-baseline", "--no-extras", "--backend", "gloo", "--device", "cuda:0"]
     r = subprocess.run(cmd, capture_output=True, text=True, cwd=ROOT, timeout=900, env=env)
     assert r.returncode == 0, r.stdout + r.stderr
     line = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])

@@ -377,6 +377,26 @@ def test_bench_launch_line_dry_run_for_2_4_8_ranks(scaling):
             assert c["clouds_total"] == 2468 and c["clouds_per_gpu"] == per and c["shard_of_rank0"] == [0, per]
 
 
+def test_bench_dump_outputs_stays_within_64_mb(tmp_path):
+    """bench.py --dump-outputs: the restored clouds as float32, whole up to 64 MB (one GPU's 2468 clouds), beyond that a fixed
+    evenly spaced subset with its global cloud indices - the same subset on every run."""
+    sys.path.insert(0, ROOT)
+    import bench
+    small = torch.arange(2468 * 1024 * 3, dtype=torch.float32).reshape(2468, 1024, 3)
+    bench.dump_outputs(str(tmp_path / "a"), small)
+    assert sorted(os.listdir(tmp_path / "a")) == ["restored_points.npy"]
+    got = np.load(tmp_path / "a" / "restored_points.npy")
+    assert got.dtype == np.float32 and np.array_equal(got, small.numpy())
+    big = torch.arange(8 * 2468, dtype=torch.float32)[:, None, None].expand(8 * 2468, 1024, 3)
+    for d in ("b", "c"):
+        bench.dump_outputs(str(tmp_path / d), big)
+    idx = np.load(tmp_path / "b" / "restored_points_cloud_index.npy")
+    pts = np.load(tmp_path / "b" / "restored_points.npy")
+    assert idx.dtype == np.float64 and pts.dtype == np.float32 and len(idx) == len(pts) > 2468
+    assert sum(os.path.getsize(tmp_path / "b" / f) for f in os.listdir(tmp_path / "b")) <= 64 << 20
+    assert np.array_equal(pts[:, 0, 0], idx) and np.array_equal(idx, np.load(tmp_path / "c" / "restored_points_cloud_index.npy"))
+
+
 def test_init_from_env_rejects_a_local_rank_without_a_gpu(monkeypatch):
     """One process per GPU: a rank whose LOCAL_RANK has no device behind it (more ranks than visible GPUs) must say so, not
     die inside torch.cuda.set_device / the RCCL communicator."""
