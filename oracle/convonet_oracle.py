@@ -171,10 +171,20 @@ def scatter_mean_plane(c: torch.Tensor, index: torch.Tensor, reso: int = PLANE_R
     return mean.permute(0, 2, 1).reshape(B, C, reso, reso)
 
 
-def pointnet_features(w: Weights, p: torch.Tensor, return_stages: bool = False):
-    """Point-wise part of LocalPoolPointnet.forward (pointnet.py:124-156): [B,T,3] -> c [B,T,32]."""
-    coords = {pl: normalize_coordinate(p, pl) for pl in PLANES}
-    index = {pl: coordinate2index(coords[pl]) for pl in PLANES}
+def plane_index(p: torch.Tensor) -> Dict[str, torch.Tensor]:
+    """The cell of every point in each plane (pointnet.py:127-137): {'xz','xy','yz': [B,T] int64}."""
+    return {pl: coordinate2index(normalize_coordinate(p, pl)) for pl in PLANES}
+
+
+def pointnet_features(w: Weights, p: torch.Tensor, return_stages: bool = False,
+                      index: Optional[Dict[str, torch.Tensor]] = None):
+    """Point-wise part of LocalPoolPointnet.forward (pointnet.py:124-156): [B,T,3] -> c [B,T,32].
+
+    ``index`` (a ``plane_index`` result) overrides the cells computed from ``p``: a float64 restatement passes the
+    cells of the float32 points, the discrete decisions the reference makes, and computes only the features in float64.
+    """
+    if index is None:
+        index = plane_index(p)
     stages: List[torch.Tensor] = []
     pooled_stages: List[torch.Tensor] = []
     net = F.linear(p, w["encoder.fc_pos.weight"], w["encoder.fc_pos.bias"])
@@ -214,12 +224,13 @@ def unet_forward(w: Weights, x: torch.Tensor, prefix: str = "encoder.unet") -> t
     return conv("conv_final", x, 0)
 
 
-def encode_inputs(w: Weights, sel: torch.Tensor, return_pre_unet: bool = False):
+def encode_inputs(w: Weights, sel: torch.Tensor, return_pre_unet: bool = False,
+                  index: Optional[Dict[str, torch.Tensor]] = None):
     """``generator.model.encode_inputs`` (models/__init__.py:52 -> pointnet.py:124-168).
 
-    sel [B,T,3] -> {'xz','xy','yz': [B,32,64,64]}.
+    sel [B,T,3] -> {'xz','xy','yz': [B,32,64,64]}.  ``index``: as in ``pointnet_features``.
     """
-    c, index = pointnet_features(w, sel)
+    c, index = pointnet_features(w, sel, index=index)
     pre = {pl: scatter_mean_plane(c, index[pl]) for pl in PLANES}
     out = {pl: unet_forward(w, pre[pl]) for pl in PLANES}
     if return_pre_unet:

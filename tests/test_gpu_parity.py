@@ -781,7 +781,7 @@ def test_encoder_planes_match_reference(restorer, golden):
     planes = I.planes_from_channel_last(restorer.encode_inputs(sel))
     for i, pl in enumerate(PL):
         ref = golden["planes01"][:, i]
-        assert _rel(planes[pl][:2].cpu().numpy(), ref) < 2e-4, pl
+        assert _rel(planes[pl][:2].cpu().numpy(), ref) < 3e-6, pl             # measured 5.7e-7 ... 6.4e-7 (~4x)
         for b in range(4):
             assert abs(float(planes[pl][b].abs().mean()) - golden["planes_stats"][b, i, 1]) < 1e-4
 
@@ -1230,7 +1230,7 @@ def test_unet_matches_reference_and_is_batch_invariant(restorer, golden):
     pre = torch.from_numpy(golden["enc_pre_xz0"]).permute(1, 2, 0)[None, None].repeat(1, 3, 1, 1, 1).contiguous()
     out = restorer.unet(pre)                                                    # [1,3,64,64,32]
     got = out[0, 0].permute(2, 0, 1).cpu().numpy()
-    assert _rel(got, golden["planes01"][0, 0]) < 2e-5
+    assert _rel(got, golden["planes01"][0, 0]) < 3e-6                          # measured 6.9e-7 (~4x)
     big = restorer.unet(torch.cat([torch.randn(2, 3, 64, 64, 32), pre, torch.randn(3, 3, 64, 64, 32)]))
     assert torch.equal(big[2], out[0])                                          # fixed summation order: batch-size independent
 

@@ -5,6 +5,8 @@ tests/golden/make_golden.py, which imports /root/reference/ConvONet on CPU.
 Tolerances are float32 round-off: both sides run torch CPU kernels, but op
 ordering (e.g. torch.where vs masked assignment, scatter order) may differ.
 """
+import os
+
 import numpy as np
 import torch
 
@@ -66,6 +68,44 @@ def test_encoder_planes(golden, oracle_weights):
         np.testing.assert_allclose(planes[pl][:2].numpy(), ref, rtol=1e-3, atol=2e-5 * np.abs(ref).max())
         for b in range(4):
             assert abs(float(planes[pl][b].abs().mean()) - golden["planes_stats"][b, i, 1]) < 1e-5
+
+
+def test_float64_encoder_with_float32_cells_reproduces_the_fixtures(golden, oracle_weights):
+    """The float64 encoder the GPU encoder tests hold the kernels to (tests/test_gpu_encoder_f64.py): weights cast to
+    double, the cells computed from the float32 points (what the reference does) and injected through ``index``.  It
+    must be the reference's function: every fixture - point features, pre-U-Net plane, planes, ONet latent code - lies
+    no further from it than the float32 oracle does (one float32 rounding floor; the oracle reproduces the first and the
+    last fixture to the bit).  Measured: the fixtures 3.4e-7 ... 5.9e-7 of each tensor's maximum from float64, the
+    float32 oracle 3.4e-7 ... 8.4e-7."""
+    from oracle import onet_oracle as OO
+
+    def err(x, ref):
+        x, ref = np.asarray(x, np.float64), np.asarray(ref, np.float64)
+        return float(np.abs(x - ref).max() / np.abs(ref).max())
+
+    w64 = {k: v.double() for k, v in oracle_weights.items()}
+    proc = _proc(golden)
+    sel = torch.from_numpy(np.stack([proc[b][golden["sel_idx"][b]] for b in range(4)]))
+    index = O.plane_index(sel)
+    assert np.array_equal(np.stack([index[pl].numpy() for pl in PL], 1), golden["enc_index"])
+    c32, _ = O.pointnet_features(oracle_weights, sel)
+    c64, _ = O.pointnet_features(w64, sel.double(), index=index)
+    pre32, pre64 = O.scatter_mean_plane(c32, index["xz"])[0], O.scatter_mean_plane(c64, index["xz"])[0]
+    out32 = O.encode_inputs(oracle_weights, sel[:2])
+    out64 = O.encode_inputs(w64, sel[:2].double(), index={pl: v[:2] for pl, v in index.items()})
+    pairs = [("enc_c", golden["enc_c"], c32, c64), ("enc_pre_xz0", golden["enc_pre_xz0"], pre32, pre64)]
+    pairs += [("planes01 %s %d" % (pl, b), golden["planes01"][b, i], out32[pl][b], out64[pl][b])
+              for i, pl in enumerate(PL) for b in range(2)]
+    ow = OO.to_torch(OO.make_random_weights(0))
+    og = np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "onet_golden.npz"))
+    oc32 = OO.encode_latent(ow, torch.from_numpy(og["sel"]))
+    oc64 = OO.encode_latent({k: v.double() if v.is_floating_point() else v for k, v in ow.items()},
+                            torch.from_numpy(og["sel"]).double())
+    pairs += [("onet c %d" % b, og["c"][b], oc32[b], oc64[b]) for b in range(4)]
+    for name, fixture, f32, f64 in pairs:
+        e_fix, e_f32 = err(fixture, f64.numpy()), err(f32.numpy(), f64.numpy())
+        print("%-16s fixture vs float64 %.2e, float32 oracle vs float64 %.2e" % (name, e_fix, e_f32))
+        assert e_fix <= e_f32 * (1 + 1e-9) and e_fix < 1e-6, name
 
 
 def test_decoder_logits_and_grad(golden, oracle_weights):
