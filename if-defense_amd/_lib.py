@@ -85,6 +85,26 @@ SIGNATURES = {
     "ifd_mc_table": (C.c_int, [C.c_void_p, C.c_void_p]),
 }
 
+# include/ifd_dup.h (the baseline defenses: SRS, DUP fill, PU-Net), versioned on its own
+DUP_ABI_VERSION = 1
+
+
+class IfdPunetAux(C.Structure):
+    _fields_ = [("fps_idx", C.c_void_p), ("ball_idx", C.c_void_p), ("knn_idx", C.c_void_p)]
+
+
+DUP_SIGNATURES = {
+    "ifd_dup_abi_version": (C.c_int, []),
+    "ifd_punet_weight_count": (C.c_size_t, []),
+    "ifd_dup_create": (C.c_void_p, [C.c_void_p, C.c_size_t, C.c_int]),
+    "ifd_srs": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_uint64, C.c_int64, C.c_void_p, C.c_void_p,
+                          C.c_void_p]),
+    "ifd_dup_fill": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_uint64, C.c_int64, C.c_void_p,
+                               C.c_void_p, C.c_void_p, C.c_void_p]),
+    "ifd_punet_forward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_uint64, C.c_int64,
+                                    C.c_void_p, C.POINTER(IfdPunetAux), C.c_void_p]),
+}
+
 _lib = None
 
 
@@ -99,10 +119,12 @@ def load() -> C.CDLL:
             "there is no CPU or PyTorch fallback for the restoration path." % LIB_PATH)
     import torch  # noqa: F401  (loads libamdhip64.so.7 first; libifd binds to the same runtime)
     lib = C.CDLL(LIB_PATH, mode=C.RTLD_GLOBAL)
-    for name, (res, args) in SIGNATURES.items():
+    for name, (res, args) in list(SIGNATURES.items()) + list(DUP_SIGNATURES.items()):
         fn = getattr(lib, name)          # AttributeError if the library lacks a declared symbol
         fn.restype, fn.argtypes = res, args
     if lib.ifd_abi_version() != ABI_VERSION:
         raise ImportError("libifd.so ABI %d != binding ABI %d; rebuild" % (lib.ifd_abi_version(), ABI_VERSION))
+    if lib.ifd_dup_abi_version() != DUP_ABI_VERSION:
+        raise ImportError("libifd.so DUP ABI %d != binding DUP ABI %d; rebuild" % (lib.ifd_dup_abi_version(), DUP_ABI_VERSION))
     _lib = lib
     return lib

@@ -32,6 +32,7 @@ def sources():
 def _deps():
     hdr = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h")]
     hdr.append(os.path.join(os.path.dirname(HERE), "include", "ifd.h"))
+    hdr.append(os.path.join(os.path.dirname(HERE), "include", "ifd_dup.h"))
     return hdr
 
 

@@ -5,6 +5,7 @@
 // host waits on an event per round - one round BEHIND what it has enqueued - only to learn when the queues have run empty), and any call that needs MORE context workspace than every
 // earlier call on that context (the old buffer is freed after a device synchronisation; steady-state calls never do).
 #include "../../include/ifd.h"
+#include "../../include/ifd_dup.h"
 
 #include <hip/hip_runtime.h>
 
@@ -133,6 +134,11 @@ struct ifd_ctx {
     hipEvent_t large_fork = nullptr, large_join[LARGE_MAX_GROUPS - 1] = {};
     int test_no_morton = 0;        // measurement hook: ifd_prepare leaves the optimised points in draw order (the locality A/B through the whole pipeline)
     unsigned long long* d_status_out = nullptr;   // ifd_optimize_status: the status words as taken (atomic exchange) by status_take_kernel
+    // baseline defenses (ifd_dup_create): the PU-Net tile image (punet.hip) and its per-chunk scratch
+    float* d_punet = nullptr;
+    PunetImage pimg{};
+    void* ws_dup = nullptr;
+    size_t ws_dup_bytes = 0;
     std::string err;
 };
 
@@ -597,6 +603,8 @@ void ifd_destroy(ifd_ctx* ctx) {
     for (hipStream_t st : ctx->large_side) if (st) (void)hipStreamDestroy(st);
     for (hipEvent_t ev : ctx->large_join) if (ev) (void)hipEventDestroy(ev);
     if (ctx->large_fork) (void)hipEventDestroy(ctx->large_fork);
+    if (ctx->d_punet) (void)hipFree(ctx->d_punet);
+    if (ctx->ws_dup) (void)hipFree(ctx->ws_dup);
     delete ctx;
 }
 
@@ -1209,3 +1217,173 @@ int ifd_onet_mesh_sample(ifd_ctx* ctx, const float* c, int B, const ifd_mesh_par
 }
 
 }  // extern "C"
+
+// ---- baseline defenses (include/ifd_dup.h) ---------------------------------------------------------------------------
+namespace {
+
+// one 1x1 conv of the canonical PU-Net order: [out][in] weight, then bias
+struct PunetTensor { int out, in; };
+constexpr PunetTensor PUNET_LAYERS[] = {
+    {32, 3}, {32, 32}, {64, 32}, {64, 67}, {64, 64}, {128, 64}, {128, 131}, {128, 128}, {256, 128}, {256, 259}, {256, 256}, {512, 256},
+    {64, 128}, {64, 256}, {64, 512},
+    {256, 259}, {128, 256}, {256, 259}, {128, 256}, {256, 259}, {128, 256}, {256, 259}, {128, 256},
+    {64, 128}, {3, 64}};
+constexpr int PUNET_NL = (int)(sizeof(PUNET_LAYERS) / sizeof(PUNET_LAYERS[0]));
+constexpr int PUNET_CHUNK = 512;             // clouds per chunk of ifd_punet_forward
+
+size_t punet_count() {
+    size_t n = 0;
+    for (const PunetTensor& t : PUNET_LAYERS) n += (size_t)t.out * t.in + t.out;
+    return n;
+}
+
+// Tile image of every layer (punet.hip header comment).  Column maps: the first layer of SA level v takes
+// [features (C), dx, dy, dz] (reference order [dx, dy, dz, features]), the expansion layers take
+// [l_feats[1], up0, up1, up2, x, y, z] (reference order [x, y, z, l_feats[1], up0, up1, up2]).
+std::vector<float> build_punet_image(const float* w, PunetImage& I) {
+    std::vector<float> img;
+    size_t src = 0;
+    auto round16 = [](int n) { return (n + 15) / 16 * 16; };
+    auto put = [&](const PunetTensor& t, int feat_c) {    // feat_c >= 0: permuted input [feat (feat_c), 3 coordinates]
+        const int Kp = feat_c >= 0 ? round16(feat_c + 3) : t.in, Np = round16(t.out), SG = Kp / 16;
+        const float* W = w + src;
+        const float* bsrc = W + (size_t)t.out * t.in;
+        src += (size_t)t.out * t.in + t.out;
+        PunetLayer L;
+        L.w = (int)img.size();
+        img.resize(img.size() + (size_t)Np * Kp, 0.f);
+        for (int m = 0; m < Np / 16; ++m)
+            for (int g = 0; g < SG; ++g)
+                for (int l = 0; l < 64; ++l)
+                    for (int j = 0; j < 4; ++j) {
+                        const int o = 16 * m + (l & 15), c = 16 * g + 4 * (l >> 4) + j;
+                        int col = c;
+                        if (feat_c >= 0) col = c < feat_c ? 3 + c : (c < feat_c + 3 ? c - feat_c : -1);
+                        if (o < t.out && col >= 0 && col < t.in)
+                            img[L.w + ((size_t)(m * SG + g) * 64 + l) * 4 + j] = W[(size_t)o * t.in + col];
+                    }
+        L.b = (int)img.size();
+        img.resize(img.size() + Np, 0.f);
+        for (int o = 0; o < t.out; ++o) img[L.b + o] = bsrc[o];
+        return L;
+    };
+    const int sa_c[4] = {0, 64, 128, 256};
+    int k = 0;
+    for (int v = 0; v < 4; ++v)
+        for (int j = 0; j < 3; ++j, ++k) I.sa[v][j] = put(PUNET_LAYERS[k], j == 0 ? sa_c[v] : -1);
+    for (int f = 0; f < 3; ++f, ++k) I.head.fp[f] = put(PUNET_LAYERS[k], -1);
+    for (int b = 0; b < 4; ++b) {
+        I.head.fc0[b] = put(PUNET_LAYERS[k++], 256);
+        I.head.fc1[b] = put(PUNET_LAYERS[k++], -1);
+    }
+    I.head.pcd0 = put(PUNET_LAYERS[k++], -1);
+    I.head.pcd1 = put(PUNET_LAYERS[k++], -1);
+    I.total = (int)img.size();
+    return img;
+}
+
+size_t punet_ws_bytes(int B) {
+    return (size_t)B * (DUP_NS * 3 * 4 + DUP_NS * 4 + (size_t)DUP_NS * DUP_NSAMPLE * 4 + (size_t)DUP_FEAT_FLOATS * 4 +
+                        2 * (size_t)3 * DUP_NP * 3 * 4);
+}
+
+DupDraws dup_draws(uint64_t seed, int64_t base) {
+    return DupDraws{(uint32_t)base, (uint32_t)seed, (uint32_t)(seed >> 32)};
+}
+
+}  // namespace
+
+int ifd_dup_abi_version(void) { return IFD_DUP_ABI_VERSION; }
+
+size_t ifd_punet_weight_count(void) { return punet_count(); }
+
+ifd_ctx* ifd_dup_create(const float* weights_host, size_t n_weights, int device) {
+    g_create_error.clear();
+    if (weights_host ? n_weights != punet_count() : n_weights != 0) {
+        g_create_error = "ifd_dup_create: expected " + std::to_string(punet_count()) + " weights (or NULL and 0), got " +
+                         std::to_string(n_weights);
+        return nullptr;
+    }
+    ifd_ctx* ctx = new (std::nothrow) ifd_ctx();
+    if (!ctx) { g_create_error = "ifd_dup_create: out of host memory"; return nullptr; }
+    ctx->device = device;
+    ctx->model = IFD_MODEL_DUP;
+    hipError_t e = hipSetDevice(device);
+    if (e == hipSuccess && weights_host) {
+        std::vector<float> img = build_punet_image(weights_host, ctx->pimg);
+        e = hipMalloc(reinterpret_cast<void**>(&ctx->d_punet), img.size() * sizeof(float));
+        if (e == hipSuccess) e = hipMemcpy(ctx->d_punet, img.data(), img.size() * sizeof(float), hipMemcpyHostToDevice);
+    }
+    if (e == hipSuccess) e = configure_prep_kernels();
+    if (e == hipSuccess) e = configure_punet_kernels();
+    if (e != hipSuccess) {
+        g_create_error = std::string("ifd_dup_create: ") + hipGetErrorString(e);
+        ifd_destroy(ctx);
+        return nullptr;
+    }
+    return ctx;
+}
+
+int ifd_srs(ifd_ctx* ctx, const float* pc, int B, int K, int drop_num, uint64_t seed, int64_t cloud_index_base,
+            const int32_t* idx, float* out, void* stream) {
+    if (!ctx) return IFD_ERR_ARG;
+    IFD_ON_CTX_DEVICE(ctx);
+    if (!pc || !out || B < 1 || K < 1 || K > PREP_MAXK || drop_num < 0 || K - drop_num < 1)
+        return fail(ctx, IFD_ERR_ARG, "ifd_srs: bad argument (1 <= K - drop_num, drop_num >= 0, K <= 10000)");
+    hipError_t e = launch_srs(pc, B, K, K - drop_num, idx, dup_draws(seed, cloud_index_base), out, static_cast<hipStream_t>(stream));
+    return e == hipSuccess ? IFD_OK : fail(ctx, IFD_ERR_HIP, "ifd_srs launch", e);
+}
+
+int ifd_dup_fill(ifd_ctx* ctx, const float* pc, const uint8_t* keep_mask, int B, int K, int npoint, uint64_t seed,
+                 int64_t cloud_index_base, const int32_t* draws, float* out, int32_t* n_kept, void* stream) {
+    if (!ctx) return IFD_ERR_ARG;
+    IFD_ON_CTX_DEVICE(ctx);
+    if (npoint != DUP_NP) return fail(ctx, IFD_ERR_UNSUPPORTED, "ifd_dup_fill: only npoint = 1024 is built");
+    if (!pc || !keep_mask || !out || B < 1 || K < 1 || K > PREP_MAXK)
+        return fail(ctx, IFD_ERR_ARG, "ifd_dup_fill: bad argument (1 <= K <= 10000)");
+    hipError_t e = launch_dup_fill(pc, keep_mask, B, K, draws, dup_draws(seed, cloud_index_base), out, n_kept,
+                                   static_cast<hipStream_t>(stream));
+    return e == hipSuccess ? IFD_OK : fail(ctx, IFD_ERR_HIP, "ifd_dup_fill launch", e);
+}
+
+int ifd_punet_forward(ifd_ctx* ctx, const float* xyz, int B, int npoint, int up_ratio, const int32_t* fps_start,
+                      uint64_t seed, int64_t cloud_index_base, float* out, const ifd_punet_aux* aux, void* stream) {
+    if (!ctx) return IFD_ERR_ARG;
+    IFD_ON_CTX_DEVICE(ctx);
+    if (npoint != DUP_NP || up_ratio != 4)
+        return fail(ctx, IFD_ERR_UNSUPPORTED, "ifd_punet_forward: only npoint = 1024, up_ratio = 4 is built");
+    if (!ctx->d_punet) return fail(ctx, IFD_ERR_ARG, "ifd_punet_forward: the context holds no PU-Net weights");
+    if (!xyz || !out || B < 1) return fail(ctx, IFD_ERR_ARG, "ifd_punet_forward: bad argument");
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const int chunk = std::min(B, PUNET_CHUNK);
+    const size_t need = punet_ws_bytes(chunk);
+    if (need > ctx->ws_dup_bytes) {
+        hipError_t e = hipDeviceSynchronize();
+        if (ctx->ws_dup) { (void)hipFree(ctx->ws_dup); ctx->ws_dup = nullptr; ctx->ws_dup_bytes = 0; }
+        if (e == hipSuccess) e = hipMalloc(&ctx->ws_dup, need);
+        if (e != hipSuccess) { ctx->ws_dup = nullptr; return fail(ctx, IFD_ERR_NOMEM, "ifd_punet_forward: workspace", e); }
+        ctx->ws_dup_bytes = need;
+    }
+    for (int c0 = 0; c0 < B; c0 += chunk) {
+        const int n = std::min(chunk, B - c0);
+        char* p = static_cast<char*>(ctx->ws_dup);
+        PunetWs w;
+        w.nxyz = reinterpret_cast<float*>(p); p += (size_t)n * DUP_NS * 3 * 4;
+        w.fidx = reinterpret_cast<int32_t*>(p); p += (size_t)n * DUP_NS * 4;
+        w.bidx = reinterpret_cast<int32_t*>(p); p += (size_t)n * DUP_NS * DUP_NSAMPLE * 4;
+        w.feat = reinterpret_cast<float*>(p); p += (size_t)n * DUP_FEAT_FLOATS * 4;
+        w.kidx = reinterpret_cast<int32_t*>(p); p += (size_t)n * 3 * DUP_NP * 3 * 4;
+        w.kw = reinterpret_cast<float*>(p);
+        hipError_t e = launch_punet(ctx->d_punet, ctx->pimg, xyz + (size_t)c0 * DUP_NP * 3, n, fps_start ? fps_start + (size_t)c0 * 4 : nullptr,
+                                    dup_draws(seed, cloud_index_base + c0), w, out + (size_t)c0 * DUP_NP * 4 * 3, s);
+        if (e == hipSuccess && aux && aux->fps_idx)
+            e = hipMemcpyAsync(aux->fps_idx + (size_t)c0 * DUP_NS, w.fidx, (size_t)n * DUP_NS * 4, hipMemcpyDeviceToDevice, s);
+        if (e == hipSuccess && aux && aux->ball_idx)
+            e = hipMemcpyAsync(aux->ball_idx + (size_t)c0 * DUP_NS * DUP_NSAMPLE, w.bidx, (size_t)n * DUP_NS * DUP_NSAMPLE * 4,
+                               hipMemcpyDeviceToDevice, s);
+        if (e == hipSuccess && aux && aux->knn_idx)
+            e = hipMemcpyAsync(aux->knn_idx + (size_t)c0 * 3 * DUP_NP * 3, w.kidx, (size_t)n * 3 * DUP_NP * 3 * 4, hipMemcpyDeviceToDevice, s);
+        if (e != hipSuccess) return fail(ctx, IFD_ERR_HIP, "ifd_punet_forward launch", e);
+    }
+    return IFD_OK;
+}

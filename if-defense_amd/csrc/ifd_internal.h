@@ -173,4 +173,35 @@ hipError_t launch_marching_cubes(const float* val, int B, int P, double iso, flo
 hipError_t launch_sample_surface(const float* tris, const double* cum_area, const int* ntri_total, int B, int cap, int n,
                                  uint64_t seed, int cloud_base, float* out, hipStream_t s);
 
+// ---- baseline defenses: SRS, DUP-Net fill, PU-Net (punet.hip; C ABI in include/ifd_dup.h) ----------------------------
+constexpr int DUP_NP = 1024;            // PU-Net input points (npoint)
+constexpr int DUP_NS = 1920;            // centroids of the four SA levels per cloud (1024 + 512 + 256 + 128)
+constexpr int DUP_NSAMPLE = 32;         // ball-query samples
+constexpr int DUP_FEAT_FLOATS = 4 * 65536;   // SA outputs per cloud: [1024][64] | [512][128] | [256][256] | [128][512]
+constexpr uint32_t DUP_STAGE_SRS = 16, DUP_STAGE_FILL = 17, DUP_STAGE_FPS = 18;   // Philox counter word 2 (FPS: + level)
+__host__ __device__ constexpr int dup_level_off(int v) { return v == 0 ? 0 : (v == 1 ? 1024 : (v == 2 ? 1536 : 1792)); }
+__host__ __device__ constexpr size_t dup_feat_off(int v) { return (size_t)v * 65536; }
+// radius ** 2 of the reference (a Python double), compared against the float32 distances in float32
+__host__ __device__ constexpr float dup_radius2(int v) {
+    return v == 0 ? (float)(0.05 * 0.05) : (v == 1 ? (float)(0.1 * 0.1) : (v == 2 ? (float)(0.2 * 0.2) : (float)(0.3 * 0.3)));
+}
+struct DupDraws { uint32_t cloud_base, seed_lo, seed_hi; };
+struct PunetLayer { int w, b; };        // float offsets of a layer's tile image and padded bias inside the PU-Net image
+struct PunetHead { PunetLayer fp[3], fc0[4], fc1[4], pcd0, pcd1; };
+struct PunetImage { PunetLayer sa[4][3]; PunetHead head; int total; };
+struct PunetWs {                        // per-chunk scratch of launch_punet (api.cpp punet_ws_bytes)
+    float* nxyz;     // [B][1920][3]  centroids of the four levels
+    int32_t* fidx;   // [B][1920]     FPS indices (into the level's input)
+    int32_t* bidx;   // [B][1920][32] ball-query indices
+    float* feat;     // [B][DUP_FEAT_FLOATS]
+    int32_t* kidx;   // [B][3][1024][3]  3-NN of the FP modules
+    float* kw;       // [B][3][1024][3]  normalised weights
+};
+hipError_t configure_punet_kernels();
+hipError_t launch_srs(const float* pc, int B, int K, int m, const int32_t* idx, DupDraws d, float* out, hipStream_t s);
+hipError_t launch_dup_fill(const float* pc, const uint8_t* keep, int B, int K, const int32_t* draws, DupDraws d, float* out,
+                           int32_t* n_kept, hipStream_t s);
+hipError_t launch_punet(const float* img, const PunetImage& I, const float* xyz, int B, const int32_t* fps_start, DupDraws d,
+                        const PunetWs& w, float* out, hipStream_t s);
+
 }  // namespace ifd

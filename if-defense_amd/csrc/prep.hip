@@ -24,20 +24,7 @@ __host__ __device__ inline int prep_nkey(int K, int n_opt_sorted) {
     return n_opt_sorted > K ? n_opt_sorted + ((3 * K + n_opt_sorted) & 1) : K;
 }
 
-// ---- Philox-4x32-10 (Salmon et al., SC'11) ---------------------------------------------------------
-struct U4 { uint32_t x, y, z, w; };
-__device__ __forceinline__ U4 philox(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1) {
-#pragma unroll
-    for (int r = 0; r < 10; ++r) {
-        const uint64_t p0 = (uint64_t)0xD2511F53u * c0, p1 = (uint64_t)0xCD9E8D57u * c2;
-        const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c1 ^ k0, n1 = (uint32_t)p1;
-        const uint32_t n2 = (uint32_t)(p0 >> 32) ^ c3 ^ k1, n3 = (uint32_t)p0;
-        c0 = n0; c1 = n1; c2 = n2; c3 = n3;
-        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
-    }
-    return U4{c0, c1, c2, c3};
-}
-__device__ __forceinline__ float u01(uint32_t r) { return ((float)(r >> 8) + 0.5f) * (1.0f / 16777216.0f); }   // (0,1)
+// Philox-4x32-10 and u01: ifd_device.h
 
 // deterministic block reductions (fixed order), doubles
 __device__ __forceinline__ double block_sum_d(double v, double* scratch) {

@@ -439,3 +439,146 @@ class OnetRestorer(Restorer):
         raise IfdError("encode_points / unet belong to the ConvONet model")
 
     unet = encode_points
+
+
+class DupNet:
+    """The reference's baseline defenses on one GPU (include/ifd_dup.h): SRSDefense, SORDefense and DUPNet
+    (baselines/defense/drop_points/SRS.py, SOR.py, DUP_Net/DUP_Net.py) behind their call seams.
+
+    ``weights``: the packed PU-Net checkpoint (``weights.load_checkpoint(path, "punet")``), or None for SRS / SOR only.
+    Draws are the library's, keyed by ``seed`` and the global cloud index (``cloud_index_base`` + row), so a file gives the
+    same result however it is batched; every method also takes explicit draws.  Batches are processed in chunks of
+    ``chunk`` clouds, which bounds the context workspace (PU-Net: 1.4 MB per cloud of a chunk)."""
+
+    NPOINT = 1024
+    UP_RATIO = 4
+
+    def __init__(self, weights: Optional[np.ndarray] = None, device=None, seed: int = 0, chunk: int = 512):
+        self.lib = _lib.load()
+        if not torch.cuda.is_available():
+            raise IfdError("no GPU visible: the baseline defenses only run on an MI355X (no CPU fallback)")
+        self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+        self.seed, self.chunk = int(seed), int(chunk)
+        w = None if weights is None else np.ascontiguousarray(weights, dtype=np.float32)
+        if w is not None and w.size != self.lib.ifd_punet_weight_count():
+            raise IfdError("expected %d PU-Net weights, got %d" % (self.lib.ifd_punet_weight_count(), w.size))
+        with torch.cuda.device(self.device):
+            self.ctx = self.lib.ifd_dup_create(None if w is None else w.ctypes.data, 0 if w is None else w.size,
+                                               self.device.index or 0)
+        if not self.ctx:
+            raise IfdError((self.lib.ifd_last_error(None) or b"ifd_dup_create failed").decode())
+        self.has_punet = w is not None
+
+    def close(self):
+        if getattr(self, "ctx", None):
+            self.lib.ifd_destroy(self.ctx)
+            self.ctx = None
+
+    __del__ = close
+
+    def _stream(self) -> int:
+        return torch.cuda.current_stream(self.device).cuda_stream
+
+    def _check(self, rc: int):
+        if rc != _lib.IFD_OK:
+            raise IfdError("libifd error %d: %s" % (rc, (self.lib.ifd_last_error(self.ctx) or b"").decode()))
+
+    def _i32(self, t, shape) -> Optional[torch.Tensor]:
+        if t is None:
+            return None
+        t = torch.as_tensor(t).to(device=self.device, dtype=torch.int32).contiguous()
+        if tuple(t.shape) != tuple(shape):
+            raise IfdError("explicit draws must have shape %s, got %s" % (tuple(shape), tuple(t.shape)))
+        return t
+
+    def _chunks(self, B: int):
+        for c0 in range(0, B, self.chunk):
+            yield c0, min(B, c0 + self.chunk)
+
+    # ------------------------------------------------------------------ SRS
+    def srs(self, pc: torch.Tensor, drop_num: int = 500, idx=None, cloud_index_base: int = 0) -> torch.Tensor:
+        """SRSDefense(drop_num).random_drop: [B,K,3] -> [B,K-drop_num,3], rows in draw order.  idx: [B,K-drop_num]."""
+        pc = _f32(pc, self.device)
+        B, K = pc.shape[:2]
+        m = K - int(drop_num)
+        if m < 1 or drop_num < 0:
+            raise IfdError("SRS: drop_num must leave at least one point (K=%d, drop_num=%d)" % (K, drop_num))
+        idx = self._i32(idx, (B, m))
+        out = torch.empty(B, m, 3, device=self.device, dtype=torch.float32)
+        with torch.cuda.device(self.device):
+            for a, b in self._chunks(B):
+                self._check(self.lib.ifd_srs(self.ctx, pc[a:b].data_ptr(), b - a, K, int(drop_num), self.seed,
+                                             int(cloud_index_base) + a, None if idx is None else idx[a:b].data_ptr(),
+                                             out[a:b].data_ptr(), self._stream()))
+        return out
+
+    # ------------------------------------------------------------------ SOR
+    def sor_mask(self, pc: torch.Tensor, k: int = 2, alpha: float = 1.1) -> torch.Tensor:
+        """SORDefense(k, alpha) keep mask [B,K] uint8 (ifd_sor)."""
+        pc = _f32(pc, self.device)
+        B, K = pc.shape[:2]
+        keep = torch.empty(B, K, device=self.device, dtype=torch.uint8)
+        with torch.cuda.device(self.device):
+            for a, b in self._chunks(B):
+                self._check(self.lib.ifd_sor(self.ctx, pc[a:b].data_ptr(), b - a, K, int(k), float(alpha),
+                                             keep[a:b].data_ptr(), None, self._stream()))
+        return keep
+
+    def sor(self, pc: torch.Tensor, k: int = 2, alpha: float = 1.1):
+        """SORDefense.forward: a list of [N_i,3] tensors, the kept points in their original order."""
+        pc = _f32(pc, self.device)
+        keep = self.sor_mask(pc, k, alpha).bool()
+        return [pc[i][keep[i]] for i in range(pc.shape[0])]
+
+    # ------------------------------------------------------------------ DUP-Net
+    def process_data(self, pc: torch.Tensor, keep: torch.Tensor, draws=None, cloud_index_base: int = 0):
+        """DUPNet.process_data on SOR's output given as (pc [B,K,3], keep mask [B,K]) -> ([B,1024,3], n_kept [B]).
+        draws: [B,1024] explicit choices into each cloud's kept rows."""
+        pc = _f32(pc, self.device)
+        B, K = pc.shape[:2]
+        keep = keep.to(device=self.device, dtype=torch.uint8).contiguous()
+        draws = self._i32(draws, (B, self.NPOINT))
+        out = torch.empty(B, self.NPOINT, 3, device=self.device, dtype=torch.float32)
+        n = torch.empty(B, device=self.device, dtype=torch.int32)
+        with torch.cuda.device(self.device):
+            for a, b in self._chunks(B):
+                self._check(self.lib.ifd_dup_fill(self.ctx, pc[a:b].data_ptr(), keep[a:b].data_ptr(), b - a, K, self.NPOINT,
+                                                  self.seed, int(cloud_index_base) + a,
+                                                  None if draws is None else draws[a:b].data_ptr(), out[a:b].data_ptr(),
+                                                  n[a:b].data_ptr(), self._stream()))
+        return out, n
+
+    def pu_net(self, x: torch.Tensor, fps_start=None, cloud_index_base: int = 0, want_aux: bool = False):
+        """PUNet(npoint=1024, up_ratio=4).forward: [B,1024,3] -> [B,4096,3] (row k*1024+i = branch k, point i).
+        fps_start: [B,4] start index of each level's FPS.  want_aux: also return the discrete decisions
+        {"fps_idx" [B,1920], "ball_idx" [B,1920,32], "knn_idx" [B,3,1024,3]}."""
+        if not self.has_punet:
+            raise IfdError("this DupNet was made without PU-Net weights")
+        x = _f32(x, self.device)
+        B = x.shape[0]
+        if tuple(x.shape[1:]) != (self.NPOINT, 3):
+            raise IfdError("PU-Net input must be [B,1024,3], got %s" % (tuple(x.shape),))
+        fps_start = self._i32(fps_start, (B, 4))
+        out = torch.empty(B, self.NPOINT * self.UP_RATIO, 3, device=self.device, dtype=torch.float32)
+        aux = None
+        if want_aux:
+            aux = {"fps_idx": torch.empty(B, 1920, device=self.device, dtype=torch.int32),
+                   "ball_idx": torch.empty(B, 1920, 32, device=self.device, dtype=torch.int32),
+                   "knn_idx": torch.empty(B, 3, self.NPOINT, 3, device=self.device, dtype=torch.int32)}
+        with torch.cuda.device(self.device):
+            for a, b in self._chunks(B):
+                st = None if aux is None else C.byref(_lib.IfdPunetAux(aux["fps_idx"][a:b].data_ptr(),
+                                                                       aux["ball_idx"][a:b].data_ptr(),
+                                                                       aux["knn_idx"][a:b].data_ptr()))
+                self._check(self.lib.ifd_punet_forward(self.ctx, x[a:b].data_ptr(), b - a, self.NPOINT, self.UP_RATIO,
+                                                       None if fps_start is None else fps_start[a:b].data_ptr(), self.seed,
+                                                       int(cloud_index_base) + a, out[a:b].data_ptr(), st, self._stream()))
+        return (out, aux) if want_aux else out
+
+    def dup(self, pc: torch.Tensor, k: int = 2, alpha: float = 1.1, fill_draws=None, fps_start=None,
+            cloud_index_base: int = 0) -> torch.Tensor:
+        """DUPNet.forward: SOR, process_data, PU-Net -> [B,4096,3]."""
+        pc = _f32(pc, self.device)
+        keep = self.sor_mask(pc, k, alpha)
+        x, _ = self.process_data(pc, keep, fill_draws, cloud_index_base)
+        return self.pu_net(x, fps_start, cloud_index_base)

@@ -69,11 +69,39 @@ def onet_canonical_keys() -> List[Tuple[str, Tuple[int, ...]]]:
     return k
 
 
+def punet_canonical_keys() -> List[Tuple[str, Tuple[int, ...]]]:
+    """PU-Net of DUP-Net (baselines/defense/DUP_Net/pu_net.py, npoint 1024, up_ratio 4, no BN): the state_dict order of
+    pu-in_1024-up_4.pth (include/ifd_dup.h).  1x1 Conv2d kernels keep their trailing [1, 1]."""
+    k: List[Tuple[str, Tuple[int, ...]]] = []
+
+    def conv(pre, co, ci):
+        return [(pre + ".conv.weight", (co, ci, 1, 1)), (pre + ".conv.bias", (co,))]
+
+    sa = [[3, 32, 32, 64], [67, 64, 64, 128], [131, 128, 128, 256], [259, 256, 256, 512]]
+    for i, m in enumerate(sa):
+        for j in range(3):
+            k += conv(f"SA_modules.{i}.mlps.0.layer{j}", m[j + 1], m[j])
+    for i, c in enumerate([128, 256, 512]):
+        k += conv(f"FP_Modules.{i}.mlp.layer0", 64, c)
+    for i in range(4):
+        k += conv(f"FC_Modules.{i}.layer0", 256, 259) + conv(f"FC_Modules.{i}.layer1", 128, 256)
+    k += conv("pcd_layer.0.layer0", 64, 128) + conv("pcd_layer.1.layer0", 3, 64)
+    return k
+
+
+def _keys(model: str):
+    if model == "onet":
+        return onet_canonical_keys()
+    if model == "punet":
+        return punet_canonical_keys()
+    return canonical_keys()
+
+
 def pack_state_dict(state: Dict[str, object], model: str = "convonet") -> np.ndarray:
     """Flatten a state_dict (torch tensors or numpy arrays) into one float32 vector.  Missing or
     mis-shaped tensors raise KeyError / ValueError, like ``load_state_dict(strict=True)``."""
     parts = []
-    for name, shape in (onet_canonical_keys() if model == "onet" else canonical_keys()):
+    for name, shape in _keys(model):
         if name not in state:
             raise KeyError("checkpoint lacks %r" % name)
         t = state[name]
@@ -87,6 +115,13 @@ def pack_state_dict(state: Dict[str, object], model: str = "convonet") -> np.nda
 def load_checkpoint(path: str, model: str = "convonet") -> np.ndarray:
     """``torch.load`` a reference checkpoint (ConvONet/opt_defense.py:65) and pack it.  Accepts a bare
     state_dict or the training checkpoints' {'model': state_dict, ...} wrapper."""
+    if model == "punet":
+        # pu-in_1024-up_4.pth (baselines/config.py PU_NET_WEIGHT) or an .npz of the same arrays
+        if path.endswith(".npz"):
+            with np.load(path, allow_pickle=False) as z:
+                return pack_state_dict({n: z[n] for n in z.files}, model)
+        import torch
+        return pack_state_dict(torch.load(path, map_location="cpu", weights_only=True), model)
     import torch
     sd = torch.load(path, map_location="cpu")
     if isinstance(sd, dict) and "model" in sd and "decoder.fc_p.weight" not in sd:
