@@ -105,6 +105,24 @@ DUP_SIGNATURES = {
                                     C.c_void_p, C.POINTER(IfdPunetAux), C.c_void_p]),
 }
 
+# include/ifd_cls.h (the victim classifier: PointNet), versioned on its own
+CLS_ABI_VERSION = 1
+CLS_POINTNET, CLS_POINTNET2, CLS_DGCNN, CLS_POINTCONV = 0, 1, 2, 3
+CLS_MAX_POINTS = 10000
+
+
+class IfdClsAux(C.Structure):
+    _fields_ = [("trans", C.c_void_p), ("trans_feat", C.c_void_p), ("global_feat", C.c_void_p), ("pred", C.c_void_p)]
+
+
+CLS_SIGNATURES = {
+    "ifd_cls_abi_version": (C.c_int, []),
+    "ifd_cls_weight_count": (C.c_size_t, [C.c_int, C.c_int]),
+    "ifd_cls_create": (C.c_void_p, [C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_int]),
+    "ifd_cls_forward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.POINTER(IfdClsAux),
+                                  C.c_void_p]),
+}
+
 _lib = None
 
 
@@ -119,12 +137,14 @@ def load() -> C.CDLL:
             "there is no CPU or PyTorch fallback for the restoration path." % LIB_PATH)
     import torch  # noqa: F401  (loads libamdhip64.so.7 first; libifd binds to the same runtime)
     lib = C.CDLL(LIB_PATH, mode=C.RTLD_GLOBAL)
-    for name, (res, args) in list(SIGNATURES.items()) + list(DUP_SIGNATURES.items()):
+    for name, (res, args) in list(SIGNATURES.items()) + list(DUP_SIGNATURES.items()) + list(CLS_SIGNATURES.items()):
         fn = getattr(lib, name)          # AttributeError if the library lacks a declared symbol
         fn.restype, fn.argtypes = res, args
     if lib.ifd_abi_version() != ABI_VERSION:
         raise ImportError("libifd.so ABI %d != binding ABI %d; rebuild" % (lib.ifd_abi_version(), ABI_VERSION))
     if lib.ifd_dup_abi_version() != DUP_ABI_VERSION:
         raise ImportError("libifd.so DUP ABI %d != binding DUP ABI %d; rebuild" % (lib.ifd_dup_abi_version(), DUP_ABI_VERSION))
+    if lib.ifd_cls_abi_version() != CLS_ABI_VERSION:
+        raise ImportError("libifd.so CLS ABI %d != binding CLS ABI %d; rebuild" % (lib.ifd_cls_abi_version(), CLS_ABI_VERSION))
     _lib = lib
     return lib

@@ -33,6 +33,7 @@ def _deps():
     hdr = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h")]
     hdr.append(os.path.join(os.path.dirname(HERE), "include", "ifd.h"))
     hdr.append(os.path.join(os.path.dirname(HERE), "include", "ifd_dup.h"))
+    hdr.append(os.path.join(os.path.dirname(HERE), "include", "ifd_cls.h"))
     return hdr
 
 

@@ -6,6 +6,7 @@
 // earlier call on that context (the old buffer is freed after a device synchronisation; steady-state calls never do).
 #include "../../include/ifd.h"
 #include "../../include/ifd_dup.h"
+#include "../../include/ifd_cls.h"
 
 #include <hip/hip_runtime.h>
 
@@ -139,6 +140,10 @@ struct ifd_ctx {
     PunetImage pimg{};
     void* ws_dup = nullptr;
     size_t ws_dup_bytes = 0;
+    // victim classifier (ifd_cls_create): the PointNet weight image (pointnet.hip); its scratch is `ws`
+    float* d_cls = nullptr;
+    ClsImage cimg{};
+    int cls_feature_transform = 0, cls_classes = 0;
     std::string err;
 };
 
@@ -605,6 +610,7 @@ void ifd_destroy(ifd_ctx* ctx) {
     if (ctx->large_fork) (void)hipEventDestroy(ctx->large_fork);
     if (ctx->d_punet) (void)hipFree(ctx->d_punet);
     if (ctx->ws_dup) (void)hipFree(ctx->ws_dup);
+    if (ctx->d_cls) (void)hipFree(ctx->d_cls);
     delete ctx;
 }
 
@@ -1387,3 +1393,195 @@ int ifd_punet_forward(ifd_ctx* ctx, const float* xyz, int B, int npoint, int up_
     }
     return IFD_OK;
 }
+
+// ---- victim classifier (include/ifd_cls.h) ---------------------------------------------------------------------------
+namespace {
+
+constexpr int CLS_CLASSES = 40;
+constexpr int CLS_CHUNK = 4096;              // most clouds per chunk of ifd_cls_forward
+
+// one layer of the canonical order: [out][in] weight, then bias
+struct ClsTensor { int out, in; };
+std::vector<ClsTensor> cls_layers(bool ft) {
+    std::vector<ClsTensor> k = {{64, 3}, {128, 64}, {1024, 128}, {512, 1024}, {256, 512}, {9, 256}, {64, 3}};
+    if (ft) for (const ClsTensor& t : {ClsTensor{64, 64}, {128, 64}, {1024, 128}, {512, 1024}, {256, 512}, {4096, 256}}) k.push_back(t);
+    for (const ClsTensor& t : {ClsTensor{128, 64}, {1024, 128}, {512, 1024}, {256, 512}, {CLS_CLASSES, 256}}) k.push_back(t);
+    return k;
+}
+
+size_t cls_count(bool ft) {
+    size_t n = 0;
+    for (const ClsTensor& t : cls_layers(ft)) n += (size_t)t.out * t.in + t.out;
+    return n;
+}
+
+// The device image: 3-input layers as [64][4] = {w0, w1, w2, bias}, every other layer as MFMA tiles (pointnet.hip header
+// comment) followed by its bias, both zero-padded to whole 16-row tiles.
+std::vector<float> build_cls_image(const float* w, bool ft, ClsImage& I) {
+    std::vector<float> img;
+    size_t src = 0;
+    auto first = [&]() {
+        const float* W = w + src;
+        src += 64 * 3 + 64;
+        const int o0 = (int)img.size();
+        img.resize(img.size() + 64 * 4);
+        for (int o = 0; o < 64; ++o) {
+            for (int a = 0; a < 3; ++a) img[o0 + o * 4 + a] = W[o * 3 + a];
+            img[o0 + o * 4 + 3] = W[64 * 3 + o];
+        }
+        return o0;
+    };
+    auto put = [&](const ClsTensor& t) {
+        const int Np = (t.out + 15) / 16 * 16, SG = t.in / 16;
+        const float* W = w + src;
+        const float* bsrc = W + (size_t)t.out * t.in;
+        src += (size_t)t.out * t.in + t.out;
+        ClsFc L;
+        L.n_out = t.out; L.n_in = t.in;
+        L.w = (int)img.size();
+        img.resize(img.size() + (size_t)Np * t.in, 0.f);
+        for (int m = 0; m < Np / 16; ++m)
+            for (int g = 0; g < SG; ++g)
+                for (int l = 0; l < 64; ++l)
+                    for (int j = 0; j < 4; ++j) {
+                        const int o = 16 * m + (l & 15), c = 16 * g + 4 * (l >> 4) + j;
+                        if (o < t.out) img[L.w + ((size_t)(m * SG + g) * 64 + l) * 4 + j] = W[(size_t)o * t.in + c];
+                    }
+        L.b = (int)img.size();
+        img.resize(img.size() + Np, 0.f);
+        for (int o = 0; o < t.out; ++o) img[L.b + o] = bsrc[o];
+        return L;
+    };
+    const std::vector<ClsTensor> K = cls_layers(ft);
+    int k = 0;
+    auto stack_tail = [&](ClsStack& S) {
+        const ClsFc a = put(K[k++]), b = put(K[k++]);
+        S.w2 = a.w; S.b2 = a.b; S.w3 = b.w; S.b3 = b.b;
+    };
+    I.stn.first = first(); ++k;
+    I.stn.mid_w = I.stn.mid_b = 0;
+    stack_tail(I.stn);
+    for (int j = 0; j < 3; ++j) I.stn_fc[j] = put(K[k++]);
+    I.trunk.first = first(); ++k;
+    I.trunk.mid_w = I.trunk.mid_b = 0;
+    I.fstn = ClsStack{};
+    if (ft) {
+        I.fstn.first = I.trunk.first;
+        const ClsFc mid = put(K[k++]);
+        I.fstn.mid_w = mid.w; I.fstn.mid_b = mid.b;
+        stack_tail(I.fstn);
+        for (int j = 0; j < 3; ++j) I.fstn_fc[j] = put(K[k++]);
+    }
+    stack_tail(I.trunk);
+    for (int j = 0; j < 3; ++j) I.head_fc[j] = put(K[k++]);
+    I.total = (int)img.size();
+    return img;
+}
+
+size_t cls_bytes_per_cloud(int stride, bool ft) {
+    const size_t T = (size_t)(stride + CLS_TILE - 1) / CLS_TILE;
+    return 4096 * T + 4096 + 2048 + 1024 + 64 + (ft ? 16384 : 0);
+}
+
+}  // namespace
+
+extern "C" {
+
+int ifd_cls_abi_version(void) { return IFD_CLS_ABI_VERSION; }
+
+size_t ifd_cls_weight_count(int model, int feature_transform) {
+    return model == IFD_CLS_POINTNET ? cls_count(feature_transform != 0) : 0;
+}
+
+ifd_ctx* ifd_cls_create(const float* weights_host, size_t n_weights, int model, int feature_transform, int n_classes, int device) {
+    g_create_error.clear();
+    if (model < IFD_CLS_POINTNET || model > IFD_CLS_POINTCONV) {
+        g_create_error = "ifd_cls_create: unknown model id " + std::to_string(model);
+        return nullptr;
+    }
+    if (model != IFD_CLS_POINTNET) {
+        g_create_error = "ifd_cls_create: only PointNet (IFD_CLS_POINTNET) is built; PointNet++, DGCNN and PointConv are not";
+        return nullptr;
+    }
+    if (n_classes != CLS_CLASSES) {
+        g_create_error = "ifd_cls_create: only n_classes = 40 (ModelNet40) is built, got " + std::to_string(n_classes);
+        return nullptr;
+    }
+    const bool ft = feature_transform != 0;
+    if (!weights_host || n_weights != cls_count(ft)) {
+        g_create_error = "ifd_cls_create: expected " + std::to_string(cls_count(ft)) + " weights, got " +
+                         (weights_host ? std::to_string(n_weights) : std::string("NULL"));
+        return nullptr;
+    }
+    ifd_ctx* ctx = new (std::nothrow) ifd_ctx();
+    if (!ctx) { g_create_error = "ifd_cls_create: out of host memory"; return nullptr; }
+    ctx->device = device;
+    ctx->model = IFD_MODEL_CLS;
+    ctx->cls_feature_transform = ft ? 1 : 0;
+    ctx->cls_classes = n_classes;
+    hipError_t e = hipSetDevice(device);
+    if (e == hipSuccess) {
+        std::vector<float> img = build_cls_image(weights_host, ft, ctx->cimg);
+        e = hipMalloc(reinterpret_cast<void**>(&ctx->d_cls), img.size() * sizeof(float));
+        if (e == hipSuccess) e = hipMemcpy(ctx->d_cls, img.data(), img.size() * sizeof(float), hipMemcpyHostToDevice);
+    }
+    if (e != hipSuccess) {
+        g_create_error = std::string("ifd_cls_create: ") + hipGetErrorString(e);
+        ifd_destroy(ctx);
+        return nullptr;
+    }
+    return ctx;
+}
+
+int ifd_cls_forward(ifd_ctx* ctx, const float* pc, const int32_t* n_points, int B, int stride, float* logits,
+                    const ifd_cls_aux* aux, void* stream) {
+    if (!ctx) return IFD_ERR_ARG;
+    if (ctx->model != IFD_MODEL_CLS || !ctx->d_cls) return fail(ctx, IFD_ERR_ARG, "ifd_cls_forward: not a classifier context");
+    if (!pc || !logits || B < 1 || stride < 1 || stride > IFD_CLS_MAX_POINTS)
+        return fail(ctx, IFD_ERR_ARG, "ifd_cls_forward: bad argument (B >= 1, 1 <= stride <= 10000)");
+    const bool ft = ctx->cls_feature_transform != 0;
+    if (aux && aux->trans_feat && !ft)
+        return fail(ctx, IFD_ERR_ARG, "ifd_cls_forward: trans_feat asked of a model without feature_transform");
+    IFD_ON_CTX_DEVICE(ctx);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const int n_chunks = (B + CLS_CHUNK - 1) / CLS_CHUNK, chunk = (B + n_chunks - 1) / n_chunks;
+    const size_t per = cls_bytes_per_cloud(stride, ft);
+    hipError_t e = ensure_ws(ctx, 256 + per * chunk);
+    if (e != hipSuccess) return fail(ctx, IFD_ERR_NOMEM, "ifd_cls_forward: workspace", e);
+    char* base = static_cast<char*>(ctx->ws);
+    if (n_points) {                       // the one blocking step: the counts are device memory
+        int32_t bad = 0;
+        e = launch_cls_check(n_points, B, stride, reinterpret_cast<int32_t*>(base), s);
+        if (e == hipSuccess) e = hipMemcpyAsync(&bad, base, sizeof(bad), hipMemcpyDeviceToHost, s);
+        if (e == hipSuccess) e = hipStreamSynchronize(s);
+        if (e != hipSuccess) return fail(ctx, IFD_ERR_HIP, "ifd_cls_forward: checking n_points", e);
+        if (bad != 0) {
+            const std::string msg = "ifd_cls_forward: " + std::to_string(bad) + " cloud(s) with n_points outside [1, stride]";
+            return fail(ctx, IFD_ERR_ARG, msg.c_str());
+        }
+    }
+    const int T = (stride + CLS_TILE - 1) / CLS_TILE, nc = ctx->cls_classes;
+    for (int c0 = 0; c0 < B; c0 += chunk) {
+        const int n = std::min(chunk, B - c0);
+        char* p = base + 256;
+        ClsWs w;
+        w.part = reinterpret_cast<float*>(p); p += (size_t)n * T * CLS_FEAT * 4;
+        w.gmax = reinterpret_cast<float*>(p); p += (size_t)n * CLS_FEAT * 4;
+        w.f1 = reinterpret_cast<float*>(p); p += (size_t)n * 512 * 4;
+        w.f2 = reinterpret_cast<float*>(p); p += (size_t)n * 256 * 4;
+        w.trans = reinterpret_cast<float*>(p); p += (size_t)n * 16 * 4;
+        w.tfeat = ft ? reinterpret_cast<float*>(p) : nullptr;
+        e = launch_cls(ctx->d_cls, ctx->cimg, ft, pc + (size_t)c0 * stride * 3, n_points ? n_points + c0 : nullptr, n, stride, w,
+                       logits + (size_t)c0 * nc, nc, aux && aux->pred ? aux->pred + c0 : nullptr, s);
+        if (e == hipSuccess && aux && aux->trans)
+            e = hipMemcpy2DAsync(aux->trans + (size_t)c0 * 9, 36, w.trans, 64, 36, (size_t)n, hipMemcpyDeviceToDevice, s);
+        if (e == hipSuccess && aux && aux->trans_feat)
+            e = hipMemcpyAsync(aux->trans_feat + (size_t)c0 * 4096, w.tfeat, (size_t)n * 4096 * 4, hipMemcpyDeviceToDevice, s);
+        if (e == hipSuccess && aux && aux->global_feat)
+            e = hipMemcpyAsync(aux->global_feat + (size_t)c0 * CLS_FEAT, w.gmax, (size_t)n * CLS_FEAT * 4, hipMemcpyDeviceToDevice, s);
+        if (e != hipSuccess) return fail(ctx, IFD_ERR_HIP, "ifd_cls_forward launch", e);
+    }
+    return IFD_OK;
+}
+
+}  // extern "C"

@@ -204,4 +204,28 @@ hipError_t launch_dup_fill(const float* pc, const uint8_t* keep, int B, int K, c
 hipError_t launch_punet(const float* img, const PunetImage& I, const float* xyz, int B, const int32_t* fps_start, DupDraws d,
                         const PunetWs& w, float* out, hipStream_t s);
 
+// ---- victim classifier: PointNet (pointnet.hip; C ABI in include/ifd_cls.h) ------------------------------------------
+constexpr int CLS_TILE = 256;           // points of one workgroup of the fused point-MLP + max kernel
+constexpr int CLS_FEAT = 1024;          // width of the max-pooled feature
+struct ClsFc { int w, b, n_out, n_in; };    // float offsets of a layer's tile image (punet.hip layout) and padded bias
+// One per-point stack ending in the max over points: [3 -> 64] (plain FMAs), optionally [64 -> 64], [64 -> 128], [128 -> 1024].
+struct ClsStack { int first, mid_w, mid_b, w2, b2, w3, b3; };      // first: [64][4] = {w0, w1, w2, bias} per output channel
+struct ClsImage {
+    ClsStack stn, fstn, trunk;          // fstn.first == trunk.first (the STNkd runs on the trunk's conv1 output)
+    ClsFc stn_fc[3], fstn_fc[3], head_fc[3];
+    int total;
+};
+struct ClsWs {                          // per-chunk scratch of launch_cls (api.cpp cls_ws_bytes)
+    float* part;     // [B][T][1024]  maxima of the 256-point tiles, T = ceil(stride / 256)
+    float* gmax;     // [B][1024]
+    float* f1;       // [B][512]
+    float* f2;       // [B][256]
+    float* trans;    // [B][16]      (9 used)
+    float* tfeat;    // [B][4096]    (feature_transform only)
+};
+// bad[0] = number of clouds with n_points outside [1, stride]
+hipError_t launch_cls_check(const int32_t* n_points, int B, int stride, int32_t* bad, hipStream_t s);
+hipError_t launch_cls(const float* img, const ClsImage& I, bool feature_transform, const float* pc, const int32_t* n_points, int B,
+                      int stride, const ClsWs& w, float* logits, int n_classes, int32_t* pred, hipStream_t s);
+
 }  // namespace ifd

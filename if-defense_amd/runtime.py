@@ -582,3 +582,107 @@ class DupNet:
         keep = self.sor_mask(pc, k, alpha)
         x, _ = self.process_data(pc, keep, fill_draws, cloud_index_base)
         return self.pu_net(x, fps_start, cloud_index_base)
+
+
+class Classifier:
+    """A victim classifier of the reference on one GPU (include/ifd_cls.h): PointNetCls(k=40, feature_transform, use_bn) in
+    eval mode, what baselines/inference.py runs on a restored cloud file.
+
+    ``weights``: the BN-folded canonical vector (``weights.load_checkpoint(path, "pointnet")`` or
+    ``weights.pack_state_dict(state_dict, "pointnet")``).  Clouds go in point-major, [B,N,3] - the layout of the .npz files -
+    not the [B,3,N] the reference's model takes.  A cloud's logits do not depend on how it is batched or padded."""
+
+    N_CLASSES = 40
+    MODELS = {"pointnet": _lib.CLS_POINTNET, "pointnet2": _lib.CLS_POINTNET2, "dgcnn": _lib.CLS_DGCNN,
+              "pointconv": _lib.CLS_POINTCONV}
+
+    def __init__(self, weights: np.ndarray, model: str = "pointnet", feature_transform: bool = False, device=None):
+        if model not in self.MODELS:
+            raise IfdError("unknown victim model %r" % (model,))
+        self.lib = _lib.load()
+        self.feature_transform = bool(feature_transform)
+        w = np.ascontiguousarray(weights, dtype=np.float32)
+        want = self.lib.ifd_cls_weight_count(self.MODELS[model], int(self.feature_transform))
+        if want == 0:
+            raise IfdError("victim model %r is not built (only pointnet is)" % model)
+        if w.size != want:
+            raise IfdError("expected %d %s weights (feature_transform=%s), got %d" % (want, model, self.feature_transform, w.size))
+        if not torch.cuda.is_available():
+            raise IfdError("no GPU visible: the classifier only runs on an MI355X (no CPU fallback)")
+        self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+        with torch.cuda.device(self.device):
+            self.ctx = self.lib.ifd_cls_create(w.ctypes.data, w.size, self.MODELS[model], int(self.feature_transform),
+                                               self.N_CLASSES, self.device.index or 0)
+        if not self.ctx:
+            raise IfdError((self.lib.ifd_last_error(None) or b"ifd_cls_create failed").decode())
+
+    def close(self):
+        if getattr(self, "ctx", None):
+            self.lib.ifd_destroy(self.ctx)
+            self.ctx = None
+
+    __del__ = close
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
+
+    def _check(self, rc: int):
+        if rc != _lib.IFD_OK:
+            raise IfdError("libifd error %d: %s" % (rc, (self.lib.ifd_last_error(self.ctx) or b"").decode()))
+
+    def _batch(self, pc, n_points):
+        """-> (pc [B,stride,3] f32 on the device, n_points [B] int32 on the device or None)."""
+        if isinstance(pc, (list, tuple)) or (isinstance(pc, np.ndarray) and pc.dtype == object):
+            if n_points is not None:
+                raise IfdError("n_points comes from the clouds themselves when a list of clouds is passed")
+            clouds = [np.asarray(c.detach().cpu() if hasattr(c, "detach") else c, dtype=np.float32)[:, :3] for c in pc]
+            if not clouds:
+                raise IfdError("no clouds")
+            counts = np.array([len(c) for c in clouds], dtype=np.int32)
+            if len(set(counts.tolist())) == 1:
+                return torch.from_numpy(np.ascontiguousarray(np.stack(clouds))).to(self.device), None
+            padded = np.zeros((len(clouds), max(int(counts.max()), 1), 3), np.float32)
+            for i, c in enumerate(clouds):
+                padded[i, :len(c)] = c
+            return torch.from_numpy(padded).to(self.device), torch.from_numpy(counts).to(self.device)
+        pc = _f32(torch.as_tensor(pc), self.device)
+        if pc.dim() != 3 or pc.shape[2] != 3:
+            raise IfdError("clouds must be [B,N,3] (point-major), got %s" % (tuple(pc.shape),))
+        if n_points is not None:
+            n_points = torch.as_tensor(n_points).to(device=self.device, dtype=torch.int32).contiguous()
+            if tuple(n_points.shape) != (pc.shape[0],):
+                raise IfdError("n_points must be [B]")
+        return pc, n_points
+
+    def logits(self, pc, n_points=None, want_aux: bool = False, want_pred: bool = False):
+        """pc: [B,N,3] tensor / array, or a list (or object array) of ragged [K_i,3] clouds, which are padded into one strided
+        batch.  n_points: [B] valid rows of each cloud of a [B,N,3] batch.  Returns logits [B,40]; with want_aux also
+        {"trans" [B,3,3], "trans_feat" [B,64,64] (feature_transform only), "global_feat" [B,1024], "pred" [B] int32}."""
+        pc, n_points = self._batch(pc, n_points)
+        B, stride = int(pc.shape[0]), int(pc.shape[1])
+        if B < 1 or stride < 1:
+            raise IfdError("empty batch")
+        out = torch.empty(B, self.N_CLASSES, device=self.device, dtype=torch.float32)
+        aux, st = None, None
+        if want_aux or want_pred:
+            aux = {"pred": torch.empty(B, device=self.device, dtype=torch.int32)}
+            if want_aux:
+                aux["trans"] = torch.empty(B, 3, 3, device=self.device, dtype=torch.float32)
+                aux["global_feat"] = torch.empty(B, 1024, device=self.device, dtype=torch.float32)
+                if self.feature_transform:
+                    aux["trans_feat"] = torch.empty(B, 64, 64, device=self.device, dtype=torch.float32)
+            ptr = lambda k: aux[k].data_ptr() if k in aux else None        # noqa: E731
+            st = C.byref(_lib.IfdClsAux(ptr("trans"), ptr("trans_feat"), ptr("global_feat"), ptr("pred")))
+        with torch.cuda.device(self.device):
+            self._check(self.lib.ifd_cls_forward(self.ctx, pc.data_ptr(), None if n_points is None else n_points.data_ptr(),
+                                                 B, stride, out.data_ptr(), st, torch.cuda.current_stream(self.device).cuda_stream))
+        return (out, aux) if aux is not None else out
+
+    def predict(self, pc, n_points=None) -> torch.Tensor:
+        """argmax of the logits, [B] int64 (the lowest class among equal logits, as torch.argmax on the CPU)."""
+        _, aux = self.logits(pc, n_points, want_pred=True)
+        return aux["pred"].long()

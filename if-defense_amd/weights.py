@@ -89,7 +89,89 @@ def punet_canonical_keys() -> List[Tuple[str, Tuple[int, ...]]]:
     return k
 
 
+BN_EPS = 1e-5
+
+
+def pointnet_layers(feature_transform: bool = False) -> List[Tuple[str, object, Tuple[int, int], bool]]:
+    """The conv / linear layers of PointNetCls(k=40, use_bn=True) (baselines/model/pointnet.py) in network order, which is
+    the canonical order of include/ifd_cls.h: (layer key, its BatchNorm's key or None, (out, in), is a Conv1d).  The
+    Sequential members are ``.0`` (conv / linear) and ``.1`` (BatchNorm); STNkd names its layers conv1..3 / fc1..3 / bn1..5."""
+    def seq(pre, dims, conv):
+        return [(pre + ".0", pre + ".1", dims, conv)]
+
+    k = (seq("feat.stn.conv1", (64, 3), True) + seq("feat.stn.conv2", (128, 64), True) + seq("feat.stn.conv3", (1024, 128), True)
+         + seq("feat.stn.fc1", (512, 1024), False) + seq("feat.stn.fc2", (256, 512), False)
+         + [("feat.stn.fc3", None, (9, 256), False)] + seq("feat.conv1", (64, 3), True))
+    if feature_transform:
+        f = "feat.fstn."
+        k += [(f + "conv1", f + "bn1", (64, 64), True), (f + "conv2", f + "bn2", (128, 64), True),
+              (f + "conv3", f + "bn3", (1024, 128), True), (f + "fc1", f + "bn4", (512, 1024), False),
+              (f + "fc2", f + "bn5", (256, 512), False), (f + "fc3", None, (4096, 256), False)]
+    k += seq("feat.conv2", (128, 64), True) + seq("feat.conv3", (1024, 128), True) + seq("fc1", (512, 1024), False)
+    k += [("fc2", "bn2", (256, 512), False), ("fc3", None, (40, 256), False)]
+    return k
+
+
+def pointnet_canonical_keys(feature_transform: bool = False) -> List[Tuple[str, Tuple[int, ...]]]:
+    """(name, shape) of the BN-folded tensors ifd_cls_create expects, in order (include/ifd_cls.h)."""
+    k: List[Tuple[str, Tuple[int, ...]]] = []
+    for lin, _, (co, ci), _ in pointnet_layers(feature_transform):
+        k += [(lin + ".weight", (co, ci)), (lin + ".bias", (co,))]
+    return k
+
+
+def pointnet_state_keys(feature_transform: bool = False) -> List[Tuple[str, Tuple[int, ...]]]:
+    """(name, shape) of the un-folded state_dict tensors the packer reads (no ``module.`` prefix, no num_batches_tracked)."""
+    k: List[Tuple[str, Tuple[int, ...]]] = []
+    for lin, bn, (co, ci), conv in pointnet_layers(feature_transform):
+        k += [(lin + ".weight", (co, ci, 1) if conv else (co, ci)), (lin + ".bias", (co,))]
+        if bn:
+            k += [(bn + "." + n, (co,)) for n in ("weight", "bias", "running_mean", "running_var")]
+    return k
+
+
+def strip_module_prefix(state: Dict[str, object]) -> Dict[str, object]:
+    """Keys of a state_dict saved from nn.DataParallel carry ``module.``; accept both forms."""
+    return {(k[len("module."):] if k.startswith("module.") else k): v for k, v in state.items()}
+
+
+def fold_pointnet(state: Dict[str, object], feature_transform=None) -> List[Tuple[str, np.ndarray]]:
+    """Fold every eval-mode BatchNorm into its layer in float64: w' = w g / sqrt(var + eps), b' = (b - mean) g / sqrt(var +
+    eps) + beta.  -> [(canonical name, float64 array)] in canonical order.  feature_transform None: judged from the keys."""
+    state = strip_module_prefix(state)
+    if feature_transform is None:
+        feature_transform = "feat.fstn.conv1.weight" in state
+
+    def get(name, shape):
+        if name not in state:
+            raise KeyError("checkpoint lacks %r" % name)
+        t = state[name]
+        a = t.detach().cpu().numpy() if hasattr(t, "detach") else np.asarray(t)
+        if tuple(a.shape) != tuple(shape):
+            raise ValueError("%s: expected shape %s, got %s" % (name, shape, tuple(a.shape)))
+        return a.astype(np.float64)
+
+    out: List[Tuple[str, np.ndarray]] = []
+    for lin, bn, (co, ci), conv in pointnet_layers(bool(feature_transform)):
+        w = get(lin + ".weight", (co, ci, 1) if conv else (co, ci)).reshape(co, ci)
+        b = get(lin + ".bias", (co,))
+        if bn:
+            g, beta = get(bn + ".weight", (co,)), get(bn + ".bias", (co,))
+            mean, var = get(bn + ".running_mean", (co,)), get(bn + ".running_var", (co,))
+            sc = g / np.sqrt(var + BN_EPS)
+            w, b = w * sc[:, None], (b - mean) * sc + beta
+        out += [(lin + ".weight", w), (lin + ".bias", b)]
+    return out
+
+
+def pack_pointnet(state: Dict[str, object], feature_transform=None) -> np.ndarray:
+    """fold_pointnet, rounded to float32 and flattened in canonical order (num_batches_tracked is ignored)."""
+    return np.concatenate([a.astype(np.float32).reshape(-1) for _, a in fold_pointnet(state, feature_transform)])
+
+
 def _keys(model: str):
+    if model == "pointnet":
+        return pointnet_canonical_keys(False)
     if model == "onet":
         return onet_canonical_keys()
     if model == "punet":
@@ -97,9 +179,12 @@ def _keys(model: str):
     return canonical_keys()
 
 
-def pack_state_dict(state: Dict[str, object], model: str = "convonet") -> np.ndarray:
+def pack_state_dict(state: Dict[str, object], model: str = "convonet", feature_transform=None) -> np.ndarray:
     """Flatten a state_dict (torch tensors or numpy arrays) into one float32 vector.  Missing or
-    mis-shaped tensors raise KeyError / ValueError, like ``load_state_dict(strict=True)``."""
+    mis-shaped tensors raise KeyError / ValueError, like ``load_state_dict(strict=True)``.  "pointnet": BatchNorm is
+    folded on the way (pack_pointnet); feature_transform None means judged from the keys."""
+    if model == "pointnet":
+        return pack_pointnet(state, feature_transform)
     parts = []
     for name, shape in _keys(model):
         if name not in state:
@@ -112,9 +197,16 @@ def pack_state_dict(state: Dict[str, object], model: str = "convonet") -> np.nda
     return np.concatenate(parts)
 
 
-def load_checkpoint(path: str, model: str = "convonet") -> np.ndarray:
+def load_checkpoint(path: str, model: str = "convonet", feature_transform=None) -> np.ndarray:
     """``torch.load`` a reference checkpoint (ConvONet/opt_defense.py:65) and pack it.  Accepts a bare
     state_dict or the training checkpoints' {'model': state_dict, ...} wrapper."""
+    if model == "pointnet":
+        # pretrain/<dataset>/pointnet.pth (baselines/config.py BEST_WEIGHTS; saved from nn.DataParallel) or an .npz of its arrays
+        if path.endswith(".npz"):
+            with np.load(path, allow_pickle=False) as z:
+                return pack_pointnet({n: z[n] for n in z.files}, feature_transform)
+        import torch
+        return pack_pointnet(torch.load(path, map_location="cpu", weights_only=True), feature_transform)
     if model == "punet":
         # pu-in_1024-up_4.pth (baselines/config.py PU_NET_WEIGHT) or an .npz of the same arrays
         if path.endswith(".npz"):
@@ -215,4 +307,23 @@ def onet_random_state_dict(seed: int = 0) -> Dict[str, np.ndarray]:
         lin(f"decoder.block{i}.fc_1", 256, 256, conv=True)
     cbn("decoder.bn")
     lin("decoder.fc_out", 1, 256, conv=True)
+    return w
+
+
+def pointnet_random_state_dict(seed: int = 0, feature_transform: bool = False) -> Dict[str, np.ndarray]:
+    """Seeded random un-folded PointNet weights for smoke / benchmark runs (no victim checkpoint ships: pretrain/mn40/
+    pointnet.pth is a download).  Per layer in network order: weight and bias U(+-1/sqrt(fan_in)); each BatchNorm after
+    its layer: gamma 1 + U(+-0.2), beta U(+-0.1), running_mean N(0, 0.1), running_var U(0.5, 1.25) - never the init
+    values.  The recipe (and so the numbers) is that of tests/pointnet_oracle.py make_weights."""
+    rng = np.random.default_rng(seed + 9001)
+    w: Dict[str, np.ndarray] = {}
+    for lin, bn, (co, ci), conv in pointnet_layers(feature_transform):
+        b = 1.0 / np.sqrt(ci)
+        w[lin + ".weight"] = rng.uniform(-b, b, size=(co, ci, 1) if conv else (co, ci)).astype(np.float32)
+        w[lin + ".bias"] = rng.uniform(-b, b, size=(co,)).astype(np.float32)
+        if bn:
+            w[bn + ".weight"] = (1.0 + rng.uniform(-0.2, 0.2, co)).astype(np.float32)
+            w[bn + ".bias"] = rng.uniform(-0.1, 0.1, co).astype(np.float32)
+            w[bn + ".running_mean"] = rng.normal(0.0, 0.1, co).astype(np.float32)
+            w[bn + ".running_var"] = rng.uniform(0.5, 1.25, co).astype(np.float32)
     return w

@@ -1,0 +1,104 @@
+"""PointNetCls(k=40, feature_transform, use_bn=True) in eval mode restated in torch functional ops, the test oracle of the
+victim classifier (include/ifd_cls.h).  It follows baselines/model/pointnet.py op for op (conv1d -> batch_norm -> relu,
+torch.max over points, linear, bmm) so that in float32 it repeats the reference's rounding, and runs in float64 as the
+yardstick of the GPU's arithmetic.
+
+Weights: ``make_weights(seed, feature_transform)`` draws the un-folded state_dict from numpy's default_rng(seed + 9001).
+Layers in network order (ifdefense_amd.weights.pointnet_layers); per layer: weight then bias U(+-1/sqrt(fan_in)); then, where
+the layer has a BatchNorm: gamma 1 + U(+-0.2), beta U(+-0.1), running_mean N(0, 0.1), running_var U(0.5, 1.25).  Nothing
+needs committing.  A dict WITHOUT BatchNorm keys (weights.fold_pointnet's output) runs the same network with the
+BatchNorms left out."""
+import numpy as np
+import torch
+import torch.nn.functional as F
+
+from ifdefense_amd.weights import BN_EPS, pointnet_layers
+
+
+def make_weights(seed=0, feature_transform=False):
+    rng = np.random.default_rng(seed + 9001)
+    w = {}
+    for lin, bn, (co, ci), conv in pointnet_layers(feature_transform):
+        b = 1.0 / np.sqrt(ci)
+        w[lin + ".weight"] = rng.uniform(-b, b, size=(co, ci, 1) if conv else (co, ci)).astype(np.float32)
+        w[lin + ".bias"] = rng.uniform(-b, b, size=(co,)).astype(np.float32)
+        if bn:
+            w[bn + ".weight"] = (1.0 + rng.uniform(-0.2, 0.2, co)).astype(np.float32)
+            w[bn + ".bias"] = rng.uniform(-0.1, 0.1, co).astype(np.float32)
+            w[bn + ".running_mean"] = rng.normal(0.0, 0.1, co).astype(np.float32)
+            w[bn + ".running_var"] = rng.uniform(0.5, 1.25, co).astype(np.float32)
+    return w
+
+
+def reference_state_dict(w):
+    """make_weights' dict as nn.DataParallel saves it: torch tensors, ``module.`` prefix, num_batches_tracked counters."""
+    sd = {}
+    for k, v in w.items():
+        sd["module." + k] = torch.from_numpy(np.asarray(v))
+        if k.endswith(".running_var"):
+            sd["module." + k[:-len("running_var")] + "num_batches_tracked"] = torch.tensor(0, dtype=torch.long)
+    return sd
+
+
+def to_torch(w, dtype=torch.float32):
+    return {k: torch.as_tensor(np.asarray(v)).to(dtype) for k, v in w.items()}
+
+
+def has_feature_transform(W):
+    return "feat.fstn.conv1.weight" in W
+
+
+def _layer(W, x, lin, bn, conv, relu):
+    w = W[lin + ".weight"]
+    if conv:
+        x = F.conv1d(x, w if w.dim() == 3 else w[:, :, None], W[lin + ".bias"])
+    else:
+        x = F.linear(x, w, W[lin + ".bias"])
+    if bn and (bn + ".running_var") in W:
+        x = F.batch_norm(x, W[bn + ".running_mean"], W[bn + ".running_var"], W[bn + ".weight"], W[bn + ".bias"], False, 0.0, BN_EPS)
+    return F.relu(x) if relu else x
+
+
+def _stn(W, x, layers, k):
+    """layers: the six (lin, bn, dims, conv) entries of one STN; x [B,C,N] -> [B,k,k]."""
+    for i, (lin, bn, _, conv) in enumerate(layers):
+        if i == 3:
+            x = torch.max(x, 2, keepdim=True)[0].view(-1, 1024)
+        x = _layer(W, x, lin, bn, conv, relu=i < 5)
+    return (x + torch.eye(k, dtype=x.dtype, device=x.device).flatten()[None]).view(-1, k, k)
+
+
+def _forward_batch(W, x):
+    """x [B,3,N] -> logits, trans, trans_feat | None, global feature."""
+    ft = has_feature_transform(W)
+    L = pointnet_layers(ft)
+    trans = _stn(W, x, L[0:6], 3)
+    x = torch.bmm(x.transpose(2, 1), trans).transpose(2, 1)
+    x = _layer(W, x, *L[6][:2], True, True)
+    k = 7
+    trans_feat = None
+    if ft:
+        trans_feat = _stn(W, x, L[7:13], 64)
+        x = torch.bmm(x.transpose(2, 1), trans_feat).transpose(2, 1)
+        k = 13
+    x = _layer(W, x, *L[k][:2], True, True)
+    x = _layer(W, x, *L[k + 1][:2], True, False)
+    g = torch.max(x, 2, keepdim=True)[0].view(-1, 1024)
+    x = _layer(W, g, *L[k + 2][:2], False, True)
+    x = _layer(W, x, *L[k + 3][:2], False, True)
+    x = _layer(W, x, *L[k + 4][:2], False, False)
+    return x, trans, trans_feat, g
+
+
+def forward(W, x, n_points=None, dtype=torch.float32):
+    """x: [B,N,3] (point-major, as the .npz files hold clouds) or a list of [K_i,3]; n_points: [B] valid rows of each cloud.
+    -> (logits [B,40], trans [B,3,3], trans_feat [B,64,64] | None, global feature [B,1024]) in ``dtype`` (W must be in it)."""
+    with torch.no_grad():
+        if isinstance(x, (list, tuple)) or n_points is not None:
+            clouds = [c if torch.is_tensor(c) else torch.as_tensor(np.asarray(c)) for c in x]
+            if n_points is not None:
+                clouds = [c[:int(n)] for c, n in zip(clouds, n_points)]
+            outs = [_forward_batch(W, c.to(dtype)[None, :, :3].transpose(1, 2).contiguous()) for c in clouds]
+            return tuple(None if outs[0][j] is None else torch.cat([o[j] for o in outs]) for j in range(4))
+        x = (x if torch.is_tensor(x) else torch.as_tensor(np.asarray(x))).to(dtype)
+        return _forward_batch(W, x[:, :, :3].transpose(1, 2).contiguous())
