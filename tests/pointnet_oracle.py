@@ -7,7 +7,22 @@ Weights: ``make_weights(seed, feature_transform)`` draws the un-folded state_dic
 Layers in network order (ifdefense_amd.weights.pointnet_layers); per layer: weight then bias U(+-1/sqrt(fan_in)); then, where
 the layer has a BatchNorm: gamma 1 + U(+-0.2), beta U(+-0.1), running_mean N(0, 0.1), running_var U(0.5, 1.25).  Nothing
 needs committing.  A dict WITHOUT BatchNorm keys (weights.fold_pointnet's output) runs the same network with the
-BatchNorms left out."""
+BatchNorms left out.
+
+A second weight set: ``make_calibrated_weights(seed, feature_transform)``.  Under make_weights the head is bias-dominated (the
+logits' spread across clouds is 0.0024 inside +-0.2), so every cloud lands in one class (two with feature_transform) and a test of
+the *prediction* checks nothing.  The calibrated set is make_weights with fc3 alone replaced, so trans, trans_feat and the global
+feature are the same numbers.  With h [140,256] the float64 oracle's post-ReLU fc2 output on bench.synth_clouds(140, seed=31) (20
+clouds of each shape family), mu = h.mean(0), s = h.std(0) (population), live = s > 1e-6 max(s):
+    fc3.weight <- fc3.weight * where(live, 1/s, 0)[None,:] * sqrt(3 * 256 / live.sum()),   fc3.bias <- -(fc3.weight @ mu),
+both rounded to float32: every live feature is whitened, the logits are centred on the calibration clouds and have a standard
+deviation of about 1.  Measured on bench.synth_clouds(512, seed=23) for (seed, mode) = (0, plain), (0, ft), (1, plain), (1, ft):
+live features 146 / 142 / 135 / 119 of 256, classes predicted 22 / 25 / 25 / 23, largest class share 0.188 / 0.207 / 0.145 /
+0.205, largest |fc3.weight| 658 / 286 / 4143 / 3539 (a nearly dead feature divided by a tiny std; every bar is relative to an e_32
+recomputed under these weights, so the recipe stands).  tests/test_cls_varied_cpu.py asserts the variety.
+``make_tied_weights`` copies fc3's rows 0..19 onto 20..39: 20 exact ties in every cloud's logits."""
+import functools
+
 import numpy as np
 import torch
 import torch.nn.functional as F
@@ -27,6 +42,45 @@ def make_weights(seed=0, feature_transform=False):
             w[bn + ".bias"] = rng.uniform(-0.1, 0.1, co).astype(np.float32)
             w[bn + ".running_mean"] = rng.normal(0.0, 0.1, co).astype(np.float32)
             w[bn + ".running_var"] = rng.uniform(0.5, 1.25, co).astype(np.float32)
+    return w
+
+
+CALIBRATION_CLOUDS, CALIBRATION_SEED = 140, 31
+
+
+@functools.lru_cache(maxsize=None)
+def _calibrated_fc3(seed, feature_transform):
+    import bench
+    w = make_weights(seed, feature_transform)
+    W = to_torch(w, torch.float64)
+    L = pointnet_layers(feature_transform)
+    k = 13 if feature_transform else 7
+    with torch.no_grad():
+        x = bench.synth_clouds(CALIBRATION_CLOUDS, seed=CALIBRATION_SEED)                                # 20 per shape family
+        g = torch.cat([forward(W, x[a:a + 28], dtype=torch.float64)[3] for a in range(0, len(x), 28)])
+        h =_layer(W, _layer(W, g, *L[k + 2][:2], False, True), *L[k + 3][:2], False, True).numpy()     # post-ReLU fc2, [140, 256]
+    mu, s = h.mean(0), h.std(0)
+    live = s > 1e-6 * s.max()
+    inv = np.where(live, 1.0 / np.where(live, s, 1.0), 0.0)
+    w3 = w["fc3.weight"].astype(np.float64) * inv[None, :] * np.sqrt(3.0 * 256 / live.sum())
+    return w3.astype(np.float32), (-(w3 @ mu)).astype(np.float32), int(live.sum())
+
+
+def make_calibrated_weights(seed=0, feature_transform=False):
+    """make_weights(seed, feature_transform) with fc3 rescaled so that the predicted class varies from cloud to cloud (see the
+    module docstring).  Deterministic; the calibration pass is computed once per (seed, mode) and cached."""
+    w = make_weights(seed, feature_transform)
+    w3, b3, _ = _calibrated_fc3(int(seed), bool(feature_transform))
+    w["fc3.weight"], w["fc3.bias"] = w3.copy(), b3.copy()
+    return w
+
+
+def make_tied_weights(w):
+    """A copy of ``w`` in which classes 20..39 are bit-identical twins of classes 0..19 (fc3 rows and biases copied), so that
+    every cloud's logits hold 20 exact ties and the argmax rule (the lowest class among equals) decides every prediction."""
+    w = {k: np.array(v, copy=True) for k, v in w.items()}
+    w["fc3.weight"][20:40] = w["fc3.weight"][0:20]
+    w["fc3.bias"][20:40] = w["fc3.bias"][0:20]
     return w
 
 
