@@ -10,6 +10,7 @@ from .runtime import Classifier, DupNet, IfdError, OnetRestorer, Restorer, plane
 from .pipeline import (DefenseArgs, defend_npz_test_data, defend_npz_train_test_data, defend_point_cloud,   # noqa: F401
                        defend_stream, get_save_name, remesh_point_cloud)
 from .inference import evaluate_npz   # noqa: F401
+from . import attack   # noqa: F401
 
 __all__ = ["Restorer", "DupNet", "Classifier", "evaluate_npz", "OnetRestorer", "IfdError", "weights", "load_library", "LIB_PATH", "planes_to_channel_last",
            "planes_from_channel_last", "DefenseArgs", "defend_point_cloud", "defend_npz_test_data",

@@ -123,6 +123,32 @@ CLS_SIGNATURES = {
                                   C.c_void_p]),
 }
 
+# include/ifd_atk.h (input gradients of the PointNet victim and the FGM family), versioned on its own
+ATK_ABI_VERSION = 1
+ATK_LOSS_LOGITS, ATK_LOSS_CE = 0, 1
+FGM_FGM, FGM_IFGM, FGM_MIFGM, FGM_PGD = 0, 1, 2, 3
+
+
+class IfdAtkOut(C.Structure):
+    _fields_ = [("logits", C.c_void_p), ("loss", C.c_void_p), ("pred", C.c_void_p), ("win_feat", C.c_void_p),
+                ("win_stn", C.c_void_p), ("global_feat", C.c_void_p)]
+
+
+class IfdFgmParams(C.Structure):
+    _fields_ = [("struct_size", C.c_int32), ("kind", C.c_int32), ("loss_kind", C.c_int32), ("num_iter", C.c_int32),
+                ("kappa", C.c_float), ("scale", C.c_float), ("step_size", C.c_float), ("budget", C.c_float), ("mu", C.c_float)]
+
+
+ATK_SIGNATURES = {
+    "ifd_atk_abi_version": (C.c_int, []),
+    "ifd_cls_input_grad": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_float, C.c_float,
+                                     C.c_void_p, C.POINTER(IfdAtkOut), C.c_void_p]),
+    "ifd_fgm_update": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_float, C.c_float,
+                                 C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
+    "ifd_fgm_attack": (C.c_int, [C.c_void_p, C.POINTER(IfdFgmParams), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p,
+                                 C.c_void_p, C.c_void_p]),
+}
+
 _lib = None
 
 
@@ -137,7 +163,8 @@ def load() -> C.CDLL:
             "there is no CPU or PyTorch fallback for the restoration path." % LIB_PATH)
     import torch  # noqa: F401  (loads libamdhip64.so.7 first; libifd binds to the same runtime)
     lib = C.CDLL(LIB_PATH, mode=C.RTLD_GLOBAL)
-    for name, (res, args) in list(SIGNATURES.items()) + list(DUP_SIGNATURES.items()) + list(CLS_SIGNATURES.items()):
+    for name, (res, args) in list(SIGNATURES.items()) + list(DUP_SIGNATURES.items()) + list(CLS_SIGNATURES.items()) + \
+            list(ATK_SIGNATURES.items()):
         fn = getattr(lib, name)          # AttributeError if the library lacks a declared symbol
         fn.restype, fn.argtypes = res, args
     if lib.ifd_abi_version() != ABI_VERSION:
@@ -146,5 +173,7 @@ def load() -> C.CDLL:
         raise ImportError("libifd.so DUP ABI %d != binding DUP ABI %d; rebuild" % (lib.ifd_dup_abi_version(), DUP_ABI_VERSION))
     if lib.ifd_cls_abi_version() != CLS_ABI_VERSION:
         raise ImportError("libifd.so CLS ABI %d != binding CLS ABI %d; rebuild" % (lib.ifd_cls_abi_version(), CLS_ABI_VERSION))
+    if lib.ifd_atk_abi_version() != ATK_ABI_VERSION:
+        raise ImportError("libifd.so ATK ABI %d != binding ATK ABI %d; rebuild" % (lib.ifd_atk_abi_version(), ATK_ABI_VERSION))
     _lib = lib
     return lib

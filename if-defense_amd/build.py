@@ -34,6 +34,7 @@ def _deps():
     hdr.append(os.path.join(os.path.dirname(HERE), "include", "ifd.h"))
     hdr.append(os.path.join(os.path.dirname(HERE), "include", "ifd_dup.h"))
     hdr.append(os.path.join(os.path.dirname(HERE), "include", "ifd_cls.h"))
+    hdr.append(os.path.join(os.path.dirname(HERE), "include", "ifd_atk.h"))
     return hdr
 
 

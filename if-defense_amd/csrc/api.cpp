@@ -7,6 +7,7 @@
 #include "../../include/ifd.h"
 #include "../../include/ifd_dup.h"
 #include "../../include/ifd_cls.h"
+#include "../../include/ifd_atk.h"
 
 #include <hip/hip_runtime.h>
 
@@ -144,6 +145,9 @@ struct ifd_ctx {
     float* d_cls = nullptr;
     ClsImage cimg{};
     int cls_feature_transform = 0, cls_classes = 0;
+    // ... and the backward pass's weight image (include/ifd_atk.h; contexts without feature_transform only)
+    float* d_cls_grad = nullptr;
+    ClsGradImage gimg{};
     std::string err;
 };
 
@@ -611,6 +615,7 @@ void ifd_destroy(ifd_ctx* ctx) {
     if (ctx->d_punet) (void)hipFree(ctx->d_punet);
     if (ctx->ws_dup) (void)hipFree(ctx->ws_dup);
     if (ctx->d_cls) (void)hipFree(ctx->d_cls);
+    if (ctx->d_cls_grad) (void)hipFree(ctx->d_cls_grad);
     delete ctx;
 }
 
@@ -1483,6 +1488,55 @@ size_t cls_bytes_per_cloud(int stride, bool ft) {
     return 4096 * T + 4096 + 2048 + 1024 + 64 + (ft ? 16384 : 0);
 }
 
+// The backward pass's image (ifd_internal.h ClsGradImage) from the canonical vector of a model without feature_transform.
+std::vector<float> build_cls_grad_image(const float* w, const ClsImage& F, ClsGradImage& G) {
+    const std::vector<ClsTensor> K = cls_layers(false);
+    std::vector<size_t> at(K.size());
+    size_t src = 0;
+    for (size_t k = 0; k < K.size(); ++k) { at[k] = src; src += (size_t)K[k].out * K[k].in + K[k].out; }
+    std::vector<float> img;
+    auto plain = [&](const float* p, size_t n) {
+        const int o = (int)img.size();
+        img.insert(img.end(), p, p + n);
+        img.resize((img.size() + 3) / 4 * 4, 0.f);
+        return o;
+    };
+    auto stack = [&](int k2, int k3, int first) {                      // k2: the [128][64] layer, k3: the [1024][128] layer
+        ClsGradStack S;
+        S.w1 = first;
+        S.w2 = plain(w + at[k2], 128 * 64);
+        S.b2 = plain(w + at[k2] + 128 * 64, 128);
+        S.w3 = plain(w + at[k3], 1024 * 128);
+        return S;
+    };
+    auto transposed = [&](int k) {                                     // layer [out][in] -> tiles of the layer [in][out padded to 64]
+        const int n_out = K[k].in, n_in = (K[k].out + 63) / 64 * 64, SG = n_in / 16;
+        const float* W = w + at[k];
+        ClsFc L;
+        L.n_out = n_out; L.n_in = n_in;
+        L.w = L.b = (int)img.size();
+        img.resize(img.size() + (size_t)n_out * n_in, 0.f);
+        for (int m = 0; m < n_out / 16; ++m)
+            for (int g = 0; g < SG; ++g)
+                for (int l = 0; l < 64; ++l)
+                    for (int j = 0; j < 4; ++j) {
+                        const int o = 16 * m + (l & 15), c = 16 * g + 4 * (l >> 4) + j;
+                        if (c < K[k].out) img[L.w + ((size_t)(m * SG + g) * 64 + l) * 4 + j] = W[(size_t)c * K[k].in + o];
+                    }
+        return L;
+    };
+    G.stn = stack(1, 2, F.stn.first);
+    G.trunk = stack(7, 8, F.trunk.first);
+    for (int j = 0; j < 3; ++j) { G.stn_fct[j] = transposed(3 + j); G.head_fct[j] = transposed(9 + j); }
+    G.total = (int)img.size();
+    return img;
+}
+
+size_t cls_grad_bytes_per_cloud(int stride) {
+    const size_t T = (size_t)(stride + CLS_TILE - 1) / CLS_TILE;
+    return 8192 * T + 2 * 4096 + 2 * 4096 + 2 * 2048 + 2 * 1024 + 64 + 160 + 256 + 1024 + 2048 + 4096 + 8;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1524,6 +1578,11 @@ ifd_ctx* ifd_cls_create(const float* weights_host, size_t n_weights, int model, 
         std::vector<float> img = build_cls_image(weights_host, ft, ctx->cimg);
         e = hipMalloc(reinterpret_cast<void**>(&ctx->d_cls), img.size() * sizeof(float));
         if (e == hipSuccess) e = hipMemcpy(ctx->d_cls, img.data(), img.size() * sizeof(float), hipMemcpyHostToDevice);
+        if (e == hipSuccess && !ft) {
+            std::vector<float> gimg = build_cls_grad_image(weights_host, ctx->cimg, ctx->gimg);
+            e = hipMalloc(reinterpret_cast<void**>(&ctx->d_cls_grad), gimg.size() * sizeof(float));
+            if (e == hipSuccess) e = hipMemcpy(ctx->d_cls_grad, gimg.data(), gimg.size() * sizeof(float), hipMemcpyHostToDevice);
+        }
     }
     if (e != hipSuccess) {
         g_create_error = std::string("ifd_cls_create: ") + hipGetErrorString(e);
@@ -1533,8 +1592,14 @@ ifd_ctx* ifd_cls_create(const float* weights_host, size_t n_weights, int model, 
     return ctx;
 }
 
-int ifd_cls_forward(ifd_ctx* ctx, const float* pc, const int32_t* n_points, int B, int stride, float* logits,
-                    const ifd_cls_aux* aux, void* stream) {
+}  // extern "C"
+
+namespace {
+
+// ifd_cls_forward.  check_counts = false: the caller has checked n_points already (nothing blocks); ws_off: bytes in front of the
+// workspace that belong to the caller (ifd_fgm_attack's loop state)
+int cls_forward_impl(ifd_ctx* ctx, const float* pc, const int32_t* n_points, int B, int stride, float* logits, const ifd_cls_aux* aux,
+                     void* stream, bool check_counts, size_t ws_off) {
     if (!ctx) return IFD_ERR_ARG;
     if (ctx->model != IFD_MODEL_CLS || !ctx->d_cls) return fail(ctx, IFD_ERR_ARG, "ifd_cls_forward: not a classifier context");
     if (!pc || !logits || B < 1 || stride < 1 || stride > IFD_CLS_MAX_POINTS)
@@ -1546,10 +1611,10 @@ int ifd_cls_forward(ifd_ctx* ctx, const float* pc, const int32_t* n_points, int 
     hipStream_t s = static_cast<hipStream_t>(stream);
     const int n_chunks = (B + CLS_CHUNK - 1) / CLS_CHUNK, chunk = (B + n_chunks - 1) / n_chunks;
     const size_t per = cls_bytes_per_cloud(stride, ft);
-    hipError_t e = ensure_ws(ctx, 256 + per * chunk);
+    hipError_t e = ensure_ws(ctx, ws_off + 256 + per * chunk);
     if (e != hipSuccess) return fail(ctx, IFD_ERR_NOMEM, "ifd_cls_forward: workspace", e);
-    char* base = static_cast<char*>(ctx->ws);
-    if (n_points) {                       // the one blocking step: the counts are device memory
+    char* base = static_cast<char*>(ctx->ws) + ws_off;
+    if (n_points && check_counts) {       // the one blocking step: the counts are device memory
         int32_t bad = 0;
         e = launch_cls_check(n_points, B, stride, reinterpret_cast<int32_t*>(base), s);
         if (e == hipSuccess) e = hipMemcpyAsync(&bad, base, sizeof(bad), hipMemcpyDeviceToHost, s);
@@ -1581,6 +1646,179 @@ int ifd_cls_forward(ifd_ctx* ctx, const float* pc, const int32_t* n_points, int 
             e = hipMemcpyAsync(aux->global_feat + (size_t)c0 * CLS_FEAT, w.gmax, (size_t)n * CLS_FEAT * 4, hipMemcpyDeviceToDevice, s);
         if (e != hipSuccess) return fail(ctx, IFD_ERR_HIP, "ifd_cls_forward launch", e);
     }
+    return IFD_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int ifd_cls_forward(ifd_ctx* ctx, const float* pc, const int32_t* n_points, int B, int stride, float* logits,
+                    const ifd_cls_aux* aux, void* stream) {
+    return cls_forward_impl(ctx, pc, n_points, B, stride, logits, aux, stream, true, 0);
+}
+
+}  // extern "C"
+
+// ---- attacks on the victim classifier (include/ifd_atk.h) ------------------------------------------------------------
+namespace {
+
+int atk_context_ok(ifd_ctx* ctx, const char* who) {
+    if (ctx->model != IFD_MODEL_CLS || !ctx->d_cls) return fail(ctx, IFD_ERR_ARG, (std::string(who) + ": not a classifier context").c_str());
+    if (ctx->cls_feature_transform || !ctx->d_cls_grad)
+        return fail(ctx, IFD_ERR_ARG, (std::string(who) + ": input gradients are not built for a model with feature_transform").c_str());
+    return IFD_OK;
+}
+
+// the one blocking step of the attack calls: counts and targets live on the device.  Uses the first 8 bytes of the workspace.
+int atk_check(ifd_ctx* ctx, const char* who, const int32_t* n_points, const int32_t* target, int B, int stride, hipStream_t s) {
+    int32_t bad[2] = {0, 0};
+    hipError_t e = launch_atk_check(n_points, target, B, stride, ctx->cls_classes, static_cast<int32_t*>(ctx->ws), s);
+    if (e == hipSuccess) e = hipMemcpyAsync(bad, ctx->ws, sizeof(bad), hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    if (e != hipSuccess) return fail(ctx, IFD_ERR_HIP, (std::string(who) + ": checking n_points and target").c_str(), e);
+    if (bad[0] != 0)
+        return fail(ctx, IFD_ERR_ARG, (std::string(who) + ": " + std::to_string(bad[0]) + " cloud(s) with n_points outside [1, stride]").c_str());
+    if (bad[1] != 0)
+        return fail(ctx, IFD_ERR_ARG, (std::string(who) + ": " + std::to_string(bad[1]) + " target(s) outside [0, 40)").c_str());
+    return IFD_OK;
+}
+
+int atk_chunk(int B) {
+    const int n_chunks = (B + CLS_CHUNK - 1) / CLS_CHUNK;
+    return (B + n_chunks - 1) / n_chunks;
+}
+size_t atk_grad_ws_bytes(int B, int stride) { return 256 + cls_grad_bytes_per_cloud(stride) * (size_t)atk_chunk(B); }
+
+// ifd_cls_input_grad on workspace that is already large enough (ws_off: bytes in front that belong to the caller), unchecked
+int input_grad_impl(ifd_ctx* ctx, size_t ws_off, const float* pc, const int32_t* n_points, int B, int stride, const int32_t* target,
+                    int loss_kind, float kappa, float scale, float* grad, const ifd_atk_out* out, hipStream_t s) {
+    const int chunk = atk_chunk(B), T = (stride + CLS_TILE - 1) / CLS_TILE, nc = ctx->cls_classes;
+    char* base = static_cast<char*>(ctx->ws) + ws_off + 256;
+    for (int c0 = 0; c0 < B; c0 += chunk) {
+        const size_t n = (size_t)std::min(chunk, B - c0);
+        char* p = base;
+        auto take = [&](size_t bytes_per_cloud) { char* q = p; p += n * bytes_per_cloud; return q; };
+        ClsGradWs w;
+        w.part = reinterpret_cast<float*>(take((size_t)T * 4096));
+        w.part_idx = reinterpret_cast<int32_t*>(take((size_t)T * 4096));
+        w.gmax_stn = reinterpret_cast<float*>(take(4096));
+        w.gmax = reinterpret_cast<float*>(take(4096));
+        w.win_stn = reinterpret_cast<int32_t*>(take(4096));
+        w.win = reinterpret_cast<int32_t*>(take(4096));
+        w.f1_stn = reinterpret_cast<float*>(take(2048));
+        w.f1 = reinterpret_cast<float*>(take(2048));
+        w.f2_stn = reinterpret_cast<float*>(take(1024));
+        w.f2 = reinterpret_cast<float*>(take(1024));
+        w.trans = reinterpret_cast<float*>(take(64));
+        w.logits = reinterpret_cast<float*>(take(160));
+        w.d_out = reinterpret_cast<float*>(take(256));
+        w.d2 = reinterpret_cast<float*>(take(1024));
+        w.d1 = reinterpret_cast<float*>(take(2048));
+        w.g = reinterpret_cast<float*>(take(4096));
+        w.pred = reinterpret_cast<int32_t*>(take(4));
+        w.loss = reinterpret_cast<float*>(take(4));
+        const float* pcc = pc + (size_t)c0 * stride * 3;
+        const int32_t* npc = n_points ? n_points + c0 : nullptr;
+        hipError_t e = launch_cls_win(ctx->d_cls, ctx->cimg, pcc, npc, (int)n, stride, w, nc, s);
+        if (e == hipSuccess)
+            e = launch_cls_backward(ctx->d_cls, ctx->cimg, ctx->d_cls_grad, ctx->gimg, pcc, npc, (int)n, stride, target + c0, loss_kind, kappa,
+                                    scale, w, nc, grad + (size_t)c0 * stride * 3, s);
+        auto copy = [&](void* dst, size_t dst_off, const void* src, size_t bytes_per_cloud) {
+            if (e == hipSuccess && dst)
+                e = hipMemcpyAsync(static_cast<char*>(dst) + dst_off * bytes_per_cloud, src, n * bytes_per_cloud, hipMemcpyDeviceToDevice, s);
+        };
+        if (out) {
+            copy(out->logits, c0, w.logits, 160);
+            copy(out->loss, c0, w.loss, 4);
+            copy(out->pred, c0, w.pred, 4);
+            copy(out->win_feat, c0, w.win, 4096);
+            copy(out->win_stn, c0, w.win_stn, 4096);
+            copy(out->global_feat, c0, w.gmax, 4096);
+        }
+        if (e != hipSuccess) return fail(ctx, IFD_ERR_HIP, "ifd_cls_input_grad launch", e);
+    }
+    return IFD_OK;
+}
+
+bool atk_loss_ok(int k) { return k == IFD_ATK_LOSS_LOGITS || k == IFD_ATK_LOSS_CE; }
+bool atk_kind_ok(int k) { return k >= IFD_FGM_FGM && k <= IFD_FGM_PGD; }
+
+}  // namespace
+
+extern "C" {
+
+int ifd_atk_abi_version(void) { return IFD_ATK_ABI_VERSION; }
+
+int ifd_cls_input_grad(ifd_ctx* ctx, const float* pc, const int32_t* n_points, int B, int stride, const int32_t* target, int loss_kind,
+                       float kappa, float scale, float* grad, const ifd_atk_out* out, void* stream) {
+    if (!ctx) return IFD_ERR_ARG;
+    if (int rc = atk_context_ok(ctx, "ifd_cls_input_grad")) return rc;
+    if (!pc || !target || !grad || B < 1 || stride < 1 || stride > IFD_CLS_MAX_POINTS)
+        return fail(ctx, IFD_ERR_ARG, "ifd_cls_input_grad: bad argument (pc, target, grad; B >= 1, 1 <= stride <= 10000)");
+    if (!atk_loss_ok(loss_kind)) return fail(ctx, IFD_ERR_ARG, "ifd_cls_input_grad: unknown loss_kind");
+    IFD_ON_CTX_DEVICE(ctx);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    hipError_t e = ensure_ws(ctx, atk_grad_ws_bytes(B, stride));
+    if (e != hipSuccess) return fail(ctx, IFD_ERR_NOMEM, "ifd_cls_input_grad: workspace", e);
+    if (int rc = atk_check(ctx, "ifd_cls_input_grad", n_points, target, B, stride, s)) return rc;
+    return input_grad_impl(ctx, 0, pc, n_points, B, stride, target, loss_kind, kappa, scale, grad, out, s);
+}
+
+int ifd_fgm_update(ifd_ctx* ctx, int kind, const float* grad, float* pc, const float* ori_pc, float* momentum, float step_size,
+                   float budget, float mu, const int32_t* n_points, int B, int stride, void* stream) {
+    if (!ctx) return IFD_ERR_ARG;
+    if (int rc = atk_context_ok(ctx, "ifd_fgm_update")) return rc;
+    if (!atk_kind_ok(kind)) return fail(ctx, IFD_ERR_ARG, "ifd_fgm_update: unknown kind");
+    if (!grad || !pc || B < 1 || stride < 1 || stride > IFD_CLS_MAX_POINTS || (kind != IFD_FGM_FGM && !ori_pc) ||
+        (kind == IFD_FGM_MIFGM && !momentum))
+        return fail(ctx, IFD_ERR_ARG, "ifd_fgm_update: bad argument (grad, pc; ori_pc unless FGM; momentum for MIFGM; 1 <= stride <= 10000)");
+    IFD_ON_CTX_DEVICE(ctx);
+    hipError_t e = launch_fgm_update(kind, grad, pc, ori_pc, momentum, step_size, budget, mu, n_points, B, stride,
+                                     static_cast<hipStream_t>(stream));
+    if (e != hipSuccess) return fail(ctx, IFD_ERR_HIP, "ifd_fgm_update launch", e);
+    return IFD_OK;
+}
+
+int ifd_fgm_attack(ifd_ctx* ctx, const ifd_fgm_params* params, const float* pc_in, const int32_t* n_points, const int32_t* target, int B,
+                   int stride, float* pc_out, int32_t* success, void* stream) {
+    if (!ctx) return IFD_ERR_ARG;
+    if (int rc = atk_context_ok(ctx, "ifd_fgm_attack")) return rc;
+    if (!params || params->struct_size != (int32_t)sizeof(ifd_fgm_params))
+        return fail(ctx, IFD_ERR_ARG, "ifd_fgm_attack: params missing or of another struct_size");
+    if (!atk_kind_ok(params->kind) || !atk_loss_ok(params->loss_kind) || params->num_iter < 1)
+        return fail(ctx, IFD_ERR_ARG, "ifd_fgm_attack: unknown kind or loss_kind, or num_iter < 1");
+    if (!pc_in || !target || !pc_out || !success || pc_in == pc_out || B < 1 || stride < 1 || stride > IFD_CLS_MAX_POINTS)
+        return fail(ctx, IFD_ERR_ARG, "ifd_fgm_attack: bad argument (pc_in, target, pc_out, success; B >= 1, 1 <= stride <= 10000)");
+    IFD_ON_CTX_DEVICE(ctx);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const size_t cloud = (size_t)stride * 12, state = (((size_t)B * (2 * cloud + 160 + 4)) + 255) / 256 * 256;
+    const size_t fwd = 256 + cls_bytes_per_cloud(stride, false) * (size_t)atk_chunk(B);
+    hipError_t e = ensure_ws(ctx, state + std::max(atk_grad_ws_bytes(B, stride), fwd));
+    if (e != hipSuccess) return fail(ctx, IFD_ERR_NOMEM, "ifd_fgm_attack: workspace", e);
+    if (int rc = atk_check(ctx, "ifd_fgm_attack", n_points, target, B, stride, s)) return rc;
+    // the loop's own state in front of the workspace of the calls it makes
+    char* base = static_cast<char*>(ctx->ws);
+    float* grad = reinterpret_cast<float*>(base);
+    float* mom = reinterpret_cast<float*>(base + (size_t)B * cloud);
+    float* logits = reinterpret_cast<float*>(base + (size_t)B * 2 * cloud);
+    int32_t* pred = reinterpret_cast<int32_t*>(base + (size_t)B * (2 * cloud + 160));
+    e = hipMemcpyAsync(pc_out, pc_in, (size_t)B * cloud, hipMemcpyDeviceToDevice, s);
+    if (e == hipSuccess && params->kind == IFD_FGM_MIFGM) e = hipMemsetAsync(mom, 0, (size_t)B * cloud, s);
+    if (e != hipSuccess) return fail(ctx, IFD_ERR_HIP, "ifd_fgm_attack: start", e);
+    const int iters = params->kind == IFD_FGM_FGM ? 1 : params->num_iter;
+    for (int it = 0; it < iters; ++it) {
+        if (int rc = input_grad_impl(ctx, state, pc_out, n_points, B, stride, target, params->loss_kind, params->kappa, params->scale, grad,
+                                     nullptr, s))
+            return rc;
+        e = launch_fgm_update(params->kind, grad, pc_out, pc_in, mom, params->step_size, params->budget, params->mu, n_points, B, stride, s);
+        if (e != hipSuccess) return fail(ctx, IFD_ERR_HIP, "ifd_fgm_attack: update", e);
+    }
+    // the final forward behind the loop's state; the counts were checked above, so it does not block
+    ifd_cls_aux aux{nullptr, nullptr, nullptr, pred};
+    if (int rc = cls_forward_impl(ctx, pc_out, n_points, B, stride, logits, &aux, stream, false, state)) return rc;
+    e = launch_atk_success(pred, target, B, success, s);
+    if (e != hipSuccess) return fail(ctx, IFD_ERR_HIP, "ifd_fgm_attack: success", e);
     return IFD_OK;
 }
 

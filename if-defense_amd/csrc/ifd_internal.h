@@ -228,4 +228,42 @@ hipError_t launch_cls_check(const int32_t* n_points, int B, int stride, int32_t*
 hipError_t launch_cls(const float* img, const ClsImage& I, bool feature_transform, const float* pc, const int32_t* n_points, int B,
                       int stride, const ClsWs& w, float* logits, int n_classes, int32_t* pred, hipStream_t s);
 
+
+// ---- PointNet input gradients and the FGM updates (pointnet_grad.hip; C ABI in include/ifd_atk.h) -------------------
+// The backward pass's own weight image (api.cpp build_cls_grad_image): the FC layers transposed in the MFMA tile layout
+// (a layer [out][in] becomes the layer [in][out padded to 64], zero bias), the point stacks' layers row-major.
+struct ClsGradStack { int w1, w2, b2, w3; };     // w1: the forward's [64][4] = {w0, w1, w2, bias}; w2 [128][64]; b2 [128]; w3 [1024][128]
+struct ClsGradImage {
+    ClsGradStack stn, trunk;
+    ClsFc stn_fct[3], head_fct[3];              // fc1^T, fc2^T, fc3^T
+    int total;
+};
+struct ClsGradWs {                              // per-chunk scratch of ifd_cls_input_grad (api.cpp cls_grad_bytes_per_cloud)
+    float* part;        // [B][T][1024]
+    int32_t* part_idx;  // [B][T][1024]
+    float *gmax_stn, *gmax;          // [B][1024]
+    int32_t *win_stn, *win;          // [B][1024]
+    float *f1_stn, *f1;              // [B][512]
+    float *f2_stn, *f2;              // [B][256]
+    float* trans;       // [B][16]
+    float* logits;      // [B][40]
+    int32_t* pred;      // [B]
+    float* loss;        // [B]
+    float* d_out;       // [B][64]   d loss / d logits (40 used), later d loss / d trans (9 used); the rest zero
+    float* d2;          // [B][256]
+    float* d1;          // [B][512]
+    float* g;           // [B][1024] d loss / d (max-pooled feature) of the stack being differentiated
+};
+hipError_t launch_cls_win(const float* img, const ClsImage& I, const float* pc, const int32_t* n_points, int B, int stride,
+                          const ClsGradWs& w, int n_classes, hipStream_t s);
+// bad[0] = clouds with n_points outside [1, stride] (n_points may be null), bad[1] = targets outside [0, n_classes)
+hipError_t launch_atk_check(const int32_t* n_points, const int32_t* target, int B, int stride, int n_classes, int32_t* bad, hipStream_t s);
+// after launch_cls_win: loss, its gradient through the head, the trunk, the STN head and the STN stack -> grad [B][stride][3]
+hipError_t launch_cls_backward(const float* img, const ClsImage& I, const float* gimg, const ClsGradImage& G, const float* pc,
+                               const int32_t* n_points, int B, int stride, const int32_t* target, int loss_kind, float kappa, float scale,
+                               const ClsGradWs& w, int n_classes, float* grad, hipStream_t s);
+hipError_t launch_fgm_update(int kind, const float* grad, float* pc, const float* ori_pc, float* momentum, float step_size, float budget,
+                             float mu, const int32_t* n_points, int B, int stride, hipStream_t s);
+hipError_t launch_atk_success(const int32_t* pred, const int32_t* target, int B, int32_t* success, hipStream_t s);
+
 }  // namespace ifd

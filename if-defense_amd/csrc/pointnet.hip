@@ -29,6 +29,8 @@ namespace ifd {
 
 namespace {
 
+typedef int32_t i32x4 __attribute__((ext_vector_type(4)));
+
 __device__ __forceinline__ f32x4 mfma4(const f32x4 a, const f32x4 b, f32x4 c) {
     c = __builtin_amdgcn_mfma_f32_16x16x4f32(a[0], b[0], c, 0, 0, 0);
     c = __builtin_amdgcn_mfma_f32_16x16x4f32(a[1], b[1], c, 0, 0, 0);
@@ -75,12 +77,16 @@ __device__ __forceinline__ void dense(Wt wt, const float* __restrict__ bias, con
 
 // trans: [B][16] (the 3 x 3 transform in the first 9), tfeat: [B][64][64]; either may be null.  part: [B][T][1024].
 // KD: the STNkd stack (one more 64 -> 64 layer).  RELU_LAST: ReLU after the 1024-wide layer (the STNs; not the trunk).
-template <bool KD, bool RELU_LAST>
+// WIN (the input-gradient path, include/ifd_atk.h): also part_idx [B][T][1024], the point each maximum was taken from - the
+// lowest index among equal values.  The maxima are computed exactly as without WIN; the index is found afterwards, by
+// comparing against the finished maximum.
+template <bool KD, bool RELU_LAST, bool WIN = false>
 __global__ __launch_bounds__(256, 2) void point_stack_kernel(const float* __restrict__ img, ClsStack S, const float* __restrict__ pc,
                                                              const int32_t* __restrict__ n_points, int stride,
                                                              const float* __restrict__ trans, const float* __restrict__ tfeat,
-                                                             float* __restrict__ part, int T) {
+                                                             float* __restrict__ part, int T, int32_t* __restrict__ part_idx = nullptr) {
     __shared__ __attribute__((aligned(16))) float red[4][CLS_FEAT];
+    __shared__ __attribute__((aligned(16))) int32_t redi[WIN ? 4 : 1][WIN ? CLS_FEAT : 4];
     const int b = blockIdx.y, tile = blockIdx.x;
     int n = n_points ? n_points[b] : stride;
     n = min(max(n, 0), stride);
@@ -88,7 +94,10 @@ __global__ __launch_bounds__(256, 2) void point_stack_kernel(const float* __rest
     const int wv = threadIdx.x >> 6, l = threadIdx.x & 63, q = l >> 4, p = l & 15;
     const int base = tile * CLS_TILE + wv * 64;
     if (base >= n) {                                                   // the whole wave
-        for (int c = l; c < CLS_FEAT; c += 64) red[wv][c] = -INFINITY;
+        for (int c = l; c < CLS_FEAT; c += 64) {
+            red[wv][c] = -INFINITY;
+            if (WIN) redi[wv][c] = INT32_MAX;
+        }
     } else {
         const float* P = pc + (size_t)b * stride * 3;
         bool valid[PT];
@@ -183,6 +192,24 @@ __global__ __launch_bounds__(256, 2) void point_stack_kernel(const float* __rest
                 r[k] = x;
             }
             if (p == 0) *reinterpret_cast<f32x4*>(&red[wv][16 * m + 4 * q]) = r;
+            if (WIN) {                                                 // the lowest point of this wave that holds the maximum
+                i32x4 wi = i32x4{INT32_MAX, INT32_MAX, INT32_MAX, INT32_MAX};
+#pragma unroll
+                for (int t = PT - 1; t >= 0; --t) {
+                    const f32x4 v = RELU_LAST ? relu4(acc[t]) : acc[t];
+#pragma unroll
+                    for (int k = 0; k < 4; ++k)
+                        if (valid[t] && v[k] == r[k]) wi[k] = base + 16 * t + p;
+                }
+#pragma unroll
+                for (int k = 0; k < 4; ++k) {
+                    int x = wi[k];
+                    x = min(x, __shfl_xor(x, 1)); x = min(x, __shfl_xor(x, 2));
+                    x = min(x, __shfl_xor(x, 4)); x = min(x, __shfl_xor(x, 8));
+                    wi[k] = x;
+                }
+                if (p == 0) *reinterpret_cast<i32x4*>(&redi[wv][16 * m + 4 * q]) = wi;
+            }
 #pragma unroll
             for (int g = 0; g < 8; ++g) cur[g] = nxt[g];
         }
@@ -192,6 +219,18 @@ __global__ __launch_bounds__(256, 2) void point_stack_kernel(const float* __rest
     const f32x4 r = max4(max4(*reinterpret_cast<const f32x4*>(&red[0][c]), *reinterpret_cast<const f32x4*>(&red[1][c])),
                          max4(*reinterpret_cast<const f32x4*>(&red[2][c]), *reinterpret_cast<const f32x4*>(&red[3][c])));
     *reinterpret_cast<f32x4*>(part + ((size_t)b * T + tile) * CLS_FEAT + c) = r;
+    if (WIN) {                                                         // waves own ascending point ranges: the first wave that holds it
+        i32x4 wi;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            int x = INT32_MAX;
+#pragma unroll
+            for (int w = 3; w >= 0; --w)
+                if (red[w][c + k] == r[k]) x = redi[w][c + k];
+            wi[k] = x;
+        }
+        *reinterpret_cast<i32x4*>(part_idx + ((size_t)b * T + tile) * CLS_FEAT + c) = wi;
+    }
 }
 
 __global__ __launch_bounds__(256) void tile_max_kernel(const float* __restrict__ part, const int32_t* __restrict__ n_points, int stride,
@@ -204,6 +243,33 @@ __global__ __launch_bounds__(256) void tile_max_kernel(const float* __restrict__
     f32x4 r = *reinterpret_cast<const f32x4*>(Pp);
     for (int t = 1; t < tiles; ++t) r = max4(r, *reinterpret_cast<const f32x4*>(Pp + (size_t)t * CLS_FEAT));
     *reinterpret_cast<f32x4*>(gmax + (size_t)b * CLS_FEAT + c) = r;
+}
+
+// tile_max_kernel and the winners: the first tile (tiles own ascending point ranges) that holds the maximum.  The index is
+// clamped into the cloud, so that whatever the values were (NaN input) it can be used as a row number.
+__global__ __launch_bounds__(256) void tile_max_win_kernel(const float* __restrict__ part, const int32_t* __restrict__ part_idx,
+                                                           const int32_t* __restrict__ n_points, int stride, int T,
+                                                           float* __restrict__ gmax, int32_t* __restrict__ win) {
+    const int b = blockIdx.x, c = threadIdx.x * 4;
+    int n = n_points ? n_points[b] : stride;
+    n = min(max(n, 1), stride);
+    const int tiles = (n + CLS_TILE - 1) / CLS_TILE;
+    const float* Pp = part + (size_t)b * T * CLS_FEAT + c;
+    const int32_t* Pi = part_idx + (size_t)b * T * CLS_FEAT + c;
+    f32x4 r = *reinterpret_cast<const f32x4*>(Pp);
+    for (int t = 1; t < tiles; ++t) r = max4(r, *reinterpret_cast<const f32x4*>(Pp + (size_t)t * CLS_FEAT));
+    i32x4 wi = i32x4{INT32_MAX, INT32_MAX, INT32_MAX, INT32_MAX};
+    for (int t = tiles - 1; t >= 0; --t) {
+        const f32x4 v = *reinterpret_cast<const f32x4*>(Pp + (size_t)t * CLS_FEAT);
+        const i32x4 vi = *reinterpret_cast<const i32x4*>(Pi + (size_t)t * CLS_FEAT);
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+            if (v[k] == r[k]) wi[k] = vi[k];
+    }
+#pragma unroll
+    for (int k = 0; k < 4; ++k) wi[k] = min(max(wi[k], 0), n - 1);
+    *reinterpret_cast<f32x4*>(gmax + (size_t)b * CLS_FEAT + c) = r;
+    *reinterpret_cast<i32x4*>(win + (size_t)b * CLS_FEAT + c) = wi;
 }
 
 // out[b][o] = act(bias[o] + sum_k W[o][k] x[b][k]) (+ 1 where o is a diagonal element of an eye x eye matrix).  x: [B][L.n_in]
@@ -301,6 +367,28 @@ hipError_t launch_cls(const float* img, const ClsImage& I, bool feature_transfor
     hipLaunchKernelGGL(tile_max_kernel, dim3(B), block, 0, s, (const float*)w.part, n_points, stride, T, w.gmax);
     launch_fc_stack(img, I.head_fc, B, w, 0, logits, n_classes, s);
     if (pred) hipLaunchKernelGGL(argmax_kernel, dim3((B + 255) / 256), block, 0, s, (const float*)logits, B, n_classes, pred);
+    return hipGetLastError();
+}
+
+// launch_cls without feature_transform, keeping what the backward pass needs (ClsGradWs): both stacks' maxima and winners and
+// both FC stacks' activations.  The same kernels in the same order on the same arithmetic: logits, pred and the global
+// feature are launch_cls's, bit for bit.
+hipError_t launch_cls_win(const float* img, const ClsImage& I, const float* pc, const int32_t* n_points, int B, int stride,
+                          const ClsGradWs& w, int n_classes, hipStream_t s) {
+    const int T = (stride + CLS_TILE - 1) / CLS_TILE;
+    const dim3 grid(T, B), block(256);
+    ClsWs a{w.part, w.gmax_stn, w.f1_stn, w.f2_stn, w.trans, nullptr}, h{w.part, w.gmax, w.f1, w.f2, w.trans, nullptr};
+    hipLaunchKernelGGL((point_stack_kernel<false, true, true>), grid, block, 0, s, img, I.stn, pc, n_points, stride, (const float*)nullptr,
+                       (const float*)nullptr, w.part, T, w.part_idx);
+    hipLaunchKernelGGL(tile_max_win_kernel, dim3(B), block, 0, s, (const float*)w.part, (const int32_t*)w.part_idx, n_points, stride, T,
+                       w.gmax_stn, w.win_stn);
+    launch_fc_stack(img, I.stn_fc, B, a, 3, w.trans, 16, s);
+    hipLaunchKernelGGL((point_stack_kernel<false, false, true>), grid, block, 0, s, img, I.trunk, pc, n_points, stride, (const float*)w.trans,
+                       (const float*)nullptr, w.part, T, w.part_idx);
+    hipLaunchKernelGGL(tile_max_win_kernel, dim3(B), block, 0, s, (const float*)w.part, (const int32_t*)w.part_idx, n_points, stride, T,
+                       w.gmax, w.win);
+    launch_fc_stack(img, I.head_fc, B, h, 0, w.logits, n_classes, s);
+    hipLaunchKernelGGL(argmax_kernel, dim3((B + 255) / 256), block, 0, s, (const float*)w.logits, B, n_classes, w.pred);
     return hipGetLastError();
 }
 

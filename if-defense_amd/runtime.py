@@ -686,3 +686,83 @@ class Classifier:
         """argmax of the logits, [B] int64 (the lowest class among equal logits, as torch.argmax on the CPU)."""
         _, aux = self.logits(pc, n_points, want_pred=True)
         return aux["pred"].long()
+
+    # ---- include/ifd_atk.h: input gradients and the FGM family (models without feature_transform) ----
+    LOSSES = {"logits": _lib.ATK_LOSS_LOGITS, "cross_entropy": _lib.ATK_LOSS_CE, "ce": _lib.ATK_LOSS_CE}
+    FGM_KINDS = {"fgm": _lib.FGM_FGM, "ifgm": _lib.FGM_IFGM, "mifgm": _lib.FGM_MIFGM, "pgd": _lib.FGM_PGD}
+
+    def _loss_kind(self, loss):
+        if loss not in self.LOSSES:
+            raise IfdError("unknown adversarial loss %r (logits | cross_entropy)" % (loss,))
+        return self.LOSSES[loss]
+
+    def _target(self, target, B):
+        t = torch.as_tensor(target).to(device=self.device, dtype=torch.int32).contiguous()
+        if tuple(t.shape) != (B,):
+            raise IfdError("target must be [B]")
+        return t
+
+    def _stream(self):
+        return torch.cuda.current_stream(self.device).cuda_stream
+
+    def input_grad(self, pc, target, loss="logits", kappa=0., scale=1., n_points=None, want_aux: bool = False):
+        """scale * d loss_b / d pc[b] of an adversarial loss on the logits (FGM.get_gradient without its normalisation):
+        grad [B,N,3], zeros in the rows beyond a cloud's points.  pc: as ``logits`` takes it, ragged lists included; target [B].
+        loss: "logits" (LogitsAdvLoss(kappa)) or "cross_entropy".  With want_aux also {"logits" [B,40], "loss" [B], "pred" [B],
+        "win_feat" / "win_stn" [B,1024] int32 (the point each max-pool channel came from), "global_feat" [B,1024]}."""
+        kind = self._loss_kind(loss)
+        pc, n_points = self._batch(pc, n_points)
+        B, stride = int(pc.shape[0]), int(pc.shape[1])
+        if B < 1 or stride < 1:
+            raise IfdError("empty batch")
+        target = self._target(target, B)
+        grad = torch.empty(B, stride, 3, device=self.device, dtype=torch.float32)
+        aux, st = None, None
+        if want_aux:
+            f, i = torch.float32, torch.int32
+            aux = {"logits": torch.empty(B, self.N_CLASSES, device=self.device, dtype=f), "loss": torch.empty(B, device=self.device, dtype=f),
+                   "pred": torch.empty(B, device=self.device, dtype=i), "win_feat": torch.empty(B, 1024, device=self.device, dtype=i),
+                   "win_stn": torch.empty(B, 1024, device=self.device, dtype=i),
+                   "global_feat": torch.empty(B, 1024, device=self.device, dtype=f)}
+            st = C.byref(_lib.IfdAtkOut(*[aux[k].data_ptr() for k in ("logits", "loss", "pred", "win_feat", "win_stn", "global_feat")]))
+        with torch.cuda.device(self.device):
+            self._check(self.lib.ifd_cls_input_grad(self.ctx, pc.data_ptr(), None if n_points is None else n_points.data_ptr(), B, stride,
+                                                    target.data_ptr(), kind, float(kappa), float(scale), grad.data_ptr(), st,
+                                                    self._stream()))
+        return (grad, aux) if want_aux else grad
+
+    def fgm_update(self, kind, grad, pc, ori_pc=None, momentum=None, step_size=0., budget=0., mu=1., n_points=None):
+        """One update of FGM.py IN PLACE on ``pc`` (and ``momentum``): contiguous float32 [B,N,3] tensors on the device."""
+        if kind not in self.FGM_KINDS:
+            raise IfdError("unknown attack %r (fgm | ifgm | mifgm | pgd)" % (kind,))
+        B, stride = int(pc.shape[0]), int(pc.shape[1])
+        for t in (grad, pc, ori_pc, momentum):
+            if t is not None and not (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and tuple(t.shape) == (B, stride, 3)):
+                raise IfdError("fgm_update works in place on contiguous float32 [B,N,3] device tensors")
+        if n_points is not None:
+            n_points = torch.as_tensor(n_points).to(device=self.device, dtype=torch.int32).contiguous()
+        ptr = lambda t: None if t is None else t.data_ptr()        # noqa: E731
+        with torch.cuda.device(self.device):
+            self._check(self.lib.ifd_fgm_update(self.ctx, self.FGM_KINDS[kind], ptr(grad), ptr(pc), ptr(ori_pc), ptr(momentum),
+                                                float(step_size), float(budget), float(mu), ptr(n_points), B, stride, self._stream()))
+        return pc
+
+    def fgm_attack(self, kind, pc, target, budget, step_size, num_iter=1, mu=1., loss="logits", kappa=0., scale=1., n_points=None):
+        """The whole loop on the device (ifd_fgm_attack): -> (adversarial clouds [B,N,3], success [B] bool).  ``pc`` is the
+        start AND the centre of the clip: pass it with the start noise already added."""
+        if kind not in self.FGM_KINDS:
+            raise IfdError("unknown attack %r (fgm | ifgm | mifgm | pgd)" % (kind,))
+        loss_kind = self._loss_kind(loss)
+        pc, n_points = self._batch(pc, n_points)
+        B, stride = int(pc.shape[0]), int(pc.shape[1])
+        if B < 1 or stride < 1:
+            raise IfdError("empty batch")
+        target = self._target(target, B)
+        out = torch.empty_like(pc)
+        success = torch.empty(B, device=self.device, dtype=torch.int32)
+        P = _lib.IfdFgmParams(C.sizeof(_lib.IfdFgmParams), self.FGM_KINDS[kind], loss_kind, int(num_iter), float(kappa), float(scale),
+                              float(step_size), float(budget), float(mu))
+        with torch.cuda.device(self.device):
+            self._check(self.lib.ifd_fgm_attack(self.ctx, C.byref(P), pc.data_ptr(), None if n_points is None else n_points.data_ptr(),
+                                                target.data_ptr(), B, stride, out.data_ptr(), success.data_ptr(), self._stream()))
+        return out, success.bool()
