@@ -149,6 +149,31 @@ ATK_SIGNATURES = {
                                  C.c_void_p, C.c_void_p]),
 }
 
+# include/ifd_cw.h (the CW point-perturbation attack on the PointNet victim), versioned on its own
+CW_ABI_VERSION = 1
+
+
+class IfdCwState(C.Structure):
+    _fields_ = [("m", C.c_void_p), ("v", C.c_void_p), ("bestdist", C.c_void_p), ("bestscore", C.c_void_p), ("o_bestdist", C.c_void_p),
+                ("o_bestscore", C.c_void_p), ("o_bestattack", C.c_void_p), ("weight", C.c_void_p), ("lower", C.c_void_p),
+                ("upper", C.c_void_p)]
+
+
+class IfdCwParams(C.Structure):
+    _fields_ = [("struct_size", C.c_int32), ("loss_kind", C.c_int32), ("binary_step", C.c_int32), ("num_iter", C.c_int32),
+                ("kappa", C.c_float), ("scale", C.c_float), ("attack_lr", C.c_float), ("init_weight", C.c_float),
+                ("max_weight", C.c_float)]
+
+
+CW_SIGNATURES = {
+    "ifd_cw_abi_version": (C.c_int, []),
+    "ifd_cw_step": (C.c_int, [C.c_void_p, C.POINTER(IfdCwState), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                              C.c_void_p, C.c_void_p, C.c_int, C.c_float, C.c_float, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
+    "ifd_cw_adjust": (C.c_int, [C.c_void_p, C.POINTER(IfdCwState), C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
+    "ifd_cw_perturb_attack": (C.c_int, [C.c_void_p, C.POINTER(IfdCwParams), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
+                                        C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+}
+
 _lib = None
 
 
@@ -164,7 +189,7 @@ def load() -> C.CDLL:
     import torch  # noqa: F401  (loads libamdhip64.so.7 first; libifd binds to the same runtime)
     lib = C.CDLL(LIB_PATH, mode=C.RTLD_GLOBAL)
     for name, (res, args) in list(SIGNATURES.items()) + list(DUP_SIGNATURES.items()) + list(CLS_SIGNATURES.items()) + \
-            list(ATK_SIGNATURES.items()):
+            list(ATK_SIGNATURES.items()) + list(CW_SIGNATURES.items()):
         fn = getattr(lib, name)          # AttributeError if the library lacks a declared symbol
         fn.restype, fn.argtypes = res, args
     if lib.ifd_abi_version() != ABI_VERSION:
@@ -175,5 +200,7 @@ def load() -> C.CDLL:
         raise ImportError("libifd.so CLS ABI %d != binding CLS ABI %d; rebuild" % (lib.ifd_cls_abi_version(), CLS_ABI_VERSION))
     if lib.ifd_atk_abi_version() != ATK_ABI_VERSION:
         raise ImportError("libifd.so ATK ABI %d != binding ATK ABI %d; rebuild" % (lib.ifd_atk_abi_version(), ATK_ABI_VERSION))
+    if lib.ifd_cw_abi_version() != CW_ABI_VERSION:
+        raise ImportError("libifd.so CW ABI %d != binding CW ABI %d; rebuild" % (lib.ifd_cw_abi_version(), CW_ABI_VERSION))
     _lib = lib
     return lib

@@ -15,6 +15,9 @@ distribution only, not number for number.
 
 The reference's loss is a mean over the batch it was called with; pass that batch size as ``ref_batch`` (scale = 1 / ref_batch) to
 reproduce how its ``+ 1e-9`` terms weigh against the gradient's norm.  The default is the batch passed to ``attack``.
+
+``CWPerturb`` is the reference's Carlini-Wagner point-perturbation attack (baselines/attack/CW/Perturb.py, include/ifd_cw.h), on the
+same two loop forms; it is not one of ``ATTACKS``, which names the FGM family for the fgm_attack CLI.
 """
 from __future__ import annotations
 
@@ -104,3 +107,79 @@ class PGD(IFGM):
 
 
 ATTACKS = {"fgm": FGM, "ifgm": IFGM, "mifgm": MIFGM, "pgd": PGD}
+
+
+class CWPerturb:
+    """CW attack by perturbing points (Perturb.py CWPerturb): ``binary_step`` search steps on the weight of the L2 distance term,
+    ``num_iter`` Adam iterations each.  ``model`` is a ``runtime.Classifier`` (anything with its ``input_grad``, ``cw_state``,
+    ``cw_step``, ``cw_adjust`` and ``cw_perturb_attack``), ``adv_func`` the loss by name ("logits": LogitsAdvLoss(kappa), or
+    "cross_entropy"), ``dist_func`` "l2" (L2Dist, the only one built).  ``attack(data [B,K,3], target [B])`` returns the reference's
+    triple (o_bestdist [B], o_bestattack [B,K,3], success_num) as numpy arrays and prints its progress lines without the wall-clock
+    ones.  ``verbose=True`` drives the loop from the host, one ``input_grad`` and one ``cw_step`` an iteration, with the reference's
+    lines every num_iter // 5 iterations (the two losses are the batch means of the previous iteration, zero at iteration 0, as in
+    the reference); ``verbose=False`` is one library call and prints the last line only.  Both give the same bits.
+
+    Every search step starts from data + randn * 1e-7, drawn here once per search step from a seeded HOST torch.Generator: the
+    reference draws on the GPU from the global CUDA stream, which cannot be reproduced, so clouds agree with a reference run in
+    distribution only, not number for number.  ``ref_batch``: the batch the reference's losses are a mean over (scale =
+    1 / ref_batch); the default is the batch passed to ``attack``."""
+
+    def __init__(self, model, adv_func="logits", dist_func="l2", attack_lr=1e-2, init_weight=10., max_weight=80., binary_step=10,
+                 num_iter=500, kappa=0., seed=1, ref_batch=None, verbose=True):
+        if str(dist_func).lower() != "l2":
+            raise ValueError("only the l2 distance of the reference's script is built")
+        if int(binary_step) < 1 or int(num_iter) < 1:
+            raise ValueError("binary_step and num_iter must be at least 1")
+        self.model, self.adv_func, self.kappa = model, adv_func, float(kappa)
+        self.attack_lr, self.init_weight, self.max_weight = float(attack_lr), float(init_weight), float(max_weight)
+        self.binary_step, self.num_iter = int(binary_step), int(num_iter)
+        self.ref_batch, self.verbose = ref_batch, verbose
+        self.generator = torch.Generator().manual_seed(int(seed))
+
+    def noise(self, data: torch.Tensor) -> torch.Tensor:
+        """[binary_step,B,K,3]: the start noise, one draw per search step."""
+        return torch.stack([torch.randn(data.shape, generator=self.generator) * 1e-7 for _ in range(self.binary_step)])
+
+    def _scale(self, B):
+        return 1.0 / float(self.ref_batch or B)
+
+    def _loop(self, data, target, noise):
+        """Perturb.py:69-175 from the host: the kernels of ifd_cw_perturb_attack on the same numbers."""
+        net = self.model
+        dev = net.device
+        B, K = int(data.shape[0]), int(data.shape[1])
+        ori = data.to(dev).contiguous()
+        tgt = target.to(dev)
+        state = net.cw_state(B, K, self.init_weight, self.max_weight)
+        last = torch.empty_like(ori)
+        every = max(self.num_iter // 5, 1)
+        for step in range(self.binary_step):
+            adv = ori + noise[step].to(dev)
+            info = None
+            for it in range(self.num_iter):
+                grad, aux = net.input_grad(adv, tgt, self.adv_func, self.kappa, self._scale(B), want_aux=True)
+                if it % every == 0:
+                    adv_loss, dist_loss = (0., 0.) if info is None else (float(info[:, 0].mean()), float(info[:, 1].mean()))
+                    print('Step {}, iteration {}, success {}/{}\nadv_loss: {:.4f}, dist_loss: {:.4f}'.format(
+                        step, it, int((aux["pred"].long() == tgt.long()).sum()), B, adv_loss, dist_loss))
+                final = step == self.binary_step - 1 and it == self.num_iter - 1
+                info = net.cw_step(state, grad, aux["pred"], tgt, adv, ori, it + 1, self.attack_lr, self._scale(B), loss=aux["loss"],
+                                   last_input=last if final else None, want_info=it % every == every - 1)
+            net.cw_adjust(state, tgt)
+        ok = state["lower"] > 0
+        out = torch.where(ok[:, None, None], state["o_bestattack"], last)
+        return out, state["o_bestdist"], ok
+
+    def attack(self, data, target):
+        data = torch.as_tensor(np.asarray(data) if not torch.is_tensor(data) else data).float().cpu()
+        target = torch.as_tensor(np.asarray(target) if not torch.is_tensor(target) else target).long().cpu()
+        B = int(data.shape[0])
+        noise = self.noise(data)
+        if self.verbose:
+            adv, dist, ok = self._loop(data, target, noise)
+        else:
+            adv, dist, ok = self.model.cw_perturb_attack(data, target, noise, self.adv_func, self.kappa, self._scale(B), self.attack_lr,
+                                                         self.init_weight, self.max_weight, self.binary_step, self.num_iter)
+        success_num = int(ok.sum())
+        print('Successfully attack {}/{}'.format(success_num, B))
+        return dist.cpu().numpy().astype(np.float64), adv.cpu().numpy(), success_num

@@ -35,6 +35,7 @@ def _deps():
     hdr.append(os.path.join(os.path.dirname(HERE), "include", "ifd_dup.h"))
     hdr.append(os.path.join(os.path.dirname(HERE), "include", "ifd_cls.h"))
     hdr.append(os.path.join(os.path.dirname(HERE), "include", "ifd_atk.h"))
+    hdr.append(os.path.join(os.path.dirname(HERE), "include", "ifd_cw.h"))
     return hdr
 
 

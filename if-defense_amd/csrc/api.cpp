@@ -8,6 +8,7 @@
 #include "../../include/ifd_dup.h"
 #include "../../include/ifd_cls.h"
 #include "../../include/ifd_atk.h"
+#include "../../include/ifd_cw.h"
 
 #include <hip/hip_runtime.h>
 
@@ -1819,6 +1820,120 @@ int ifd_fgm_attack(ifd_ctx* ctx, const ifd_fgm_params* params, const float* pc_i
     if (int rc = cls_forward_impl(ctx, pc_out, n_points, B, stride, logits, &aux, stream, false, state)) return rc;
     e = launch_atk_success(pred, target, B, success, s);
     if (e != hipSuccess) return fail(ctx, IFD_ERR_HIP, "ifd_fgm_attack: success", e);
+    return IFD_OK;
+}
+
+}  // extern "C"
+
+// ---- the CW point-perturbation attack (include/ifd_cw.h) --------------------------------------------------------------
+namespace {
+
+CwState cw_state(const ifd_cw_state* st) {
+    return CwState{st->m, st->v, st->bestdist, st->bestscore, st->o_bestdist, st->o_bestscore, st->o_bestattack, st->weight, st->lower, st->upper};
+}
+
+}  // namespace
+
+extern "C" {
+
+int ifd_cw_abi_version(void) { return IFD_CW_ABI_VERSION; }
+
+int ifd_cw_step(ifd_ctx* ctx, const ifd_cw_state* state, const float* grad, const int32_t* pred, const float* loss, const int32_t* target,
+                float* adv, const float* ori, float* last_input, float* info, int t, float lr, float scale, const int32_t* n_points, int B,
+                int stride, void* stream) {
+    if (!ctx) return IFD_ERR_ARG;
+    if (int rc = atk_context_ok(ctx, "ifd_cw_step")) return rc;
+    if (!state || !state->m || !state->v || !state->bestdist || !state->bestscore || !state->o_bestdist || !state->o_bestscore ||
+        !state->o_bestattack || !state->weight)
+        return fail(ctx, IFD_ERR_ARG, "ifd_cw_step: state missing (m, v, bestdist, bestscore, o_bestdist, o_bestscore, o_bestattack, weight)");
+    if (!grad || !pred || !target || !adv || !ori || t < 1 || B < 1 || stride < 1 || stride > IFD_CLS_MAX_POINTS)
+        return fail(ctx, IFD_ERR_ARG, "ifd_cw_step: bad argument (grad, pred, target, adv, ori; t >= 1, B >= 1, 1 <= stride <= 10000)");
+    IFD_ON_CTX_DEVICE(ctx);
+    hipError_t e = launch_cw_step(cw_state(state), grad, pred, loss, target, adv, ori, last_input, info, t, lr, scale, n_points, B, stride,
+                                  static_cast<hipStream_t>(stream));
+    if (e != hipSuccess) return fail(ctx, IFD_ERR_HIP, "ifd_cw_step launch", e);
+    return IFD_OK;
+}
+
+int ifd_cw_adjust(ifd_ctx* ctx, const ifd_cw_state* state, const int32_t* target, const int32_t* n_points, int B, int stride, void* stream) {
+    if (!ctx) return IFD_ERR_ARG;
+    if (int rc = atk_context_ok(ctx, "ifd_cw_adjust")) return rc;
+    if (!state || !state->bestdist || !state->bestscore || !state->o_bestdist || !state->weight || !state->lower || !state->upper)
+        return fail(ctx, IFD_ERR_ARG, "ifd_cw_adjust: state missing (bestdist, bestscore, o_bestdist, weight, lower, upper)");
+    if (!target || B < 1 || stride < 1 || stride > IFD_CLS_MAX_POINTS)
+        return fail(ctx, IFD_ERR_ARG, "ifd_cw_adjust: bad argument (target; B >= 1, 1 <= stride <= 10000)");
+    IFD_ON_CTX_DEVICE(ctx);
+    hipError_t e = launch_cw_adjust(cw_state(state), target, n_points, B, stride, static_cast<hipStream_t>(stream));
+    if (e != hipSuccess) return fail(ctx, IFD_ERR_HIP, "ifd_cw_adjust launch", e);
+    return IFD_OK;
+}
+
+int ifd_cw_perturb_attack(ifd_ctx* ctx, const ifd_cw_params* params, const float* pc_in, const int32_t* n_points, const int32_t* target,
+                          const float* noise, int B, int stride, float* pc_out, float* best_dist, int32_t* success, double* bounds,
+                          void* stream) {
+    if (!ctx) return IFD_ERR_ARG;
+    if (int rc = atk_context_ok(ctx, "ifd_cw_perturb_attack")) return rc;
+    if (!params || params->struct_size != (int32_t)sizeof(ifd_cw_params))
+        return fail(ctx, IFD_ERR_ARG, "ifd_cw_perturb_attack: params missing or of another struct_size");
+    if (params->binary_step < 1) return fail(ctx, IFD_ERR_ARG, "ifd_cw_perturb_attack: binary_step < 1");
+    if (params->num_iter < 1) return fail(ctx, IFD_ERR_ARG, "ifd_cw_perturb_attack: num_iter < 1");
+    if (!atk_loss_ok(params->loss_kind)) return fail(ctx, IFD_ERR_ARG, "ifd_cw_perturb_attack: unknown loss_kind");
+    if (B < 1) return fail(ctx, IFD_ERR_ARG, "ifd_cw_perturb_attack: B >= 1 is needed");
+    if (stride < 1 || stride > IFD_CLS_MAX_POINTS) return fail(ctx, IFD_ERR_ARG, "ifd_cw_perturb_attack: stride outside [1, 10000]");
+    if (!pc_in || !target || !pc_out || !best_dist || !success)
+        return fail(ctx, IFD_ERR_ARG, "ifd_cw_perturb_attack: missing pointer (pc_in, target, pc_out, best_dist, success)");
+    const size_t cloud = (size_t)stride * 12, all = (size_t)B * cloud;
+    {
+        const char *a = reinterpret_cast<const char*>(pc_in), *b = reinterpret_cast<const char*>(pc_out);
+        if (a < b + all && b < a + all) return fail(ctx, IFD_ERR_ARG, "ifd_cw_perturb_attack: pc_out overlaps pc_in");
+    }
+    IFD_ON_CTX_DEVICE(ctx);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const size_t state = ((size_t)B * (5 * cloud + 64) + 255) / 256 * 256;
+    hipError_t e = ensure_ws(ctx, state + atk_grad_ws_bytes(B, stride));
+    if (e != hipSuccess) return fail(ctx, IFD_ERR_NOMEM, "ifd_cw_perturb_attack: workspace", e);
+    if (int rc = atk_check(ctx, "ifd_cw_perturb_attack", n_points, target, B, stride, s)) return rc;
+    // the loop's own state in front of the workspace of ifd_cls_input_grad: the float64 weights first (alignment)
+    char* p = static_cast<char*>(ctx->ws);
+    auto take = [&](size_t bytes) { char* q = p; p += bytes; return q; };
+    CwState S;
+    S.weight = reinterpret_cast<double*>(take((size_t)B * 8));
+    S.lower = reinterpret_cast<double*>(take((size_t)B * 8));
+    S.upper = reinterpret_cast<double*>(take((size_t)B * 8));
+    S.bestdist = reinterpret_cast<float*>(take((size_t)B * 4));
+    S.bestscore = reinterpret_cast<int32_t*>(take((size_t)B * 4));
+    S.o_bestscore = reinterpret_cast<int32_t*>(take((size_t)B * 4));
+    int32_t* pred = reinterpret_cast<int32_t*>(take((size_t)B * 4));
+    float* loss = reinterpret_cast<float*>(take((size_t)B * 4));
+    float* grad = reinterpret_cast<float*>(take(all));
+    float* adv = reinterpret_cast<float*>(take(all));
+    S.m = reinterpret_cast<float*>(take(all));
+    S.v = reinterpret_cast<float*>(take(all));
+    float* last = reinterpret_cast<float*>(take(all));
+    S.o_bestdist = best_dist;
+    S.o_bestattack = pc_out;
+    e = launch_cw_init(S, B, params->init_weight, params->max_weight, s);
+    if (e == hipSuccess) e = hipMemsetAsync(S.m, 0, 2 * all, s);       // m and v lie side by side
+    if (e != hipSuccess) return fail(ctx, IFD_ERR_HIP, "ifd_cw_perturb_attack: start", e);
+    const ifd_atk_out out{nullptr, loss, pred, nullptr, nullptr, nullptr};
+    for (int step = 0; step < params->binary_step; ++step) {
+        e = launch_cw_start(pc_in, noise ? noise + (size_t)step * B * stride * 3 : nullptr, adv, n_points, B, stride, s);
+        if (e != hipSuccess) return fail(ctx, IFD_ERR_HIP, "ifd_cw_perturb_attack: search step start", e);
+        for (int it = 0; it < params->num_iter; ++it) {
+            if (int rc = input_grad_impl(ctx, state, adv, n_points, B, stride, target, params->loss_kind, params->kappa, params->scale, grad,
+                                         &out, s))
+                return rc;
+            // the reference's input_val is read once, behind its loops: only the last iteration's copy is ever seen
+            const bool final_it = step == params->binary_step - 1 && it == params->num_iter - 1;
+            e = launch_cw_step(S, grad, pred, loss, target, adv, pc_in, final_it ? last : nullptr, nullptr, it + 1, params->attack_lr,
+                               params->scale, n_points, B, stride, s);
+            if (e != hipSuccess) return fail(ctx, IFD_ERR_HIP, "ifd_cw_perturb_attack: step", e);
+        }
+        e = launch_cw_adjust(S, target, n_points, B, stride, s);
+        if (e != hipSuccess) return fail(ctx, IFD_ERR_HIP, "ifd_cw_perturb_attack: adjust", e);
+    }
+    e = launch_cw_finish(S, last, pc_out, success, bounds, n_points, B, stride, s);
+    if (e != hipSuccess) return fail(ctx, IFD_ERR_HIP, "ifd_cw_perturb_attack: finish", e);
     return IFD_OK;
 }
 

@@ -266,4 +266,23 @@ hipError_t launch_fgm_update(int kind, const float* grad, float* pc, const float
                              float mu, const int32_t* n_points, int B, int stride, hipStream_t s);
 hipError_t launch_atk_success(const int32_t* pred, const int32_t* target, int B, int32_t* success, hipStream_t s);
 
+// ---- the CW point-perturbation attack (pointnet_cw.hip, include/ifd_cw.h) ----
+struct CwState {                                // ifd_cw_state, member for member
+    float *m, *v;                               // [B][stride][3]
+    float* bestdist;                            // [B]
+    int32_t* bestscore;
+    float* o_bestdist;
+    int32_t* o_bestscore;
+    float* o_bestattack;                        // [B][stride][3]
+    double *weight, *lower, *upper;             // [B]
+};
+hipError_t launch_cw_start(const float* pc_in, const float* noise, float* adv, const int32_t* n_points, int B, int stride, hipStream_t s);
+hipError_t launch_cw_init(const CwState& S, int B, float init_weight, float max_weight, hipStream_t s);
+hipError_t launch_cw_step(const CwState& S, const float* grad, const int32_t* pred, const float* loss, const int32_t* target, float* adv,
+                          const float* ori, float* last_input, float* info, int t, float lr, float scale, const int32_t* n_points, int B,
+                          int stride, hipStream_t s);
+hipError_t launch_cw_adjust(const CwState& S, const int32_t* target, const int32_t* n_points, int B, int stride, hipStream_t s);
+hipError_t launch_cw_finish(const CwState& S, const float* last_input, float* pc_out, int32_t* success, double* bounds,
+                            const int32_t* n_points, int B, int stride, hipStream_t s);
+
 }  // namespace ifd

@@ -766,3 +766,100 @@ class Classifier:
             self._check(self.lib.ifd_fgm_attack(self.ctx, C.byref(P), pc.data_ptr(), None if n_points is None else n_points.data_ptr(),
                                                 target.data_ptr(), B, stride, out.data_ptr(), success.data_ptr(), self._stream()))
         return out, success.bool()
+
+    # ---- include/ifd_cw.h: the CW point-perturbation attack (models without feature_transform) ----
+    CW_STATE = (("m", torch.float32, 3), ("v", torch.float32, 3), ("bestdist", torch.float32, 1), ("bestscore", torch.int32, 1),
+                ("o_bestdist", torch.float32, 1), ("o_bestscore", torch.int32, 1), ("o_bestattack", torch.float32, 3),
+                ("weight", torch.float64, 1), ("lower", torch.float64, 1), ("upper", torch.float64, 1))
+
+    def cw_state(self, B, stride, init_weight=10., max_weight=80.):
+        """The state of a fresh attack (ifd_cw_state) as a dict of device tensors: Perturb.py:59-66, 74-76."""
+        f = lambda shape, v, dt: torch.full(shape, v, device=self.device, dtype=dt)      # noqa: E731
+        return {"m": f((B, stride, 3), 0., torch.float32), "v": f((B, stride, 3), 0., torch.float32),
+                "bestdist": f((B,), 1e10, torch.float32), "bestscore": f((B,), -1, torch.int32),
+                "o_bestdist": f((B,), 1e10, torch.float32), "o_bestscore": f((B,), -1, torch.int32),
+                "o_bestattack": f((B, stride, 3), 0., torch.float32), "weight": f((B,), float(init_weight), torch.float64),
+                "lower": f((B,), 0., torch.float64), "upper": f((B,), float(max_weight), torch.float64)}
+
+    def _cw_struct(self, state, B, stride):
+        ptrs = []
+        for key, dt, rank in self.CW_STATE:
+            t = state.get(key)
+            want = (B, stride, 3) if rank == 3 else (B,)
+            if t is None or not (t.is_cuda and t.dtype == dt and t.is_contiguous() and tuple(t.shape) == want):
+                raise IfdError("cw state %r must be a contiguous %s device tensor of shape %s" % (key, dt, want))
+            ptrs.append(t.data_ptr())
+        return _lib.IfdCwState(*ptrs)
+
+    def _cw_cloud(self, t, B, stride, what):
+        if t is not None and not (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and tuple(t.shape) == (B, stride, 3)):
+            raise IfdError("%s must be a contiguous float32 [B,N,3] device tensor" % what)
+        return None if t is None else t.data_ptr()
+
+    def cw_step(self, state, grad, pred, target, adv, ori, t, lr, scale=1., loss=None, last_input=None, n_points=None,
+                want_info: bool = False):
+        """One iteration of the CW attack behind ``input_grad`` (ifd_cw_step), IN PLACE on ``adv`` and ``state`` (a dict as
+        ``cw_state`` makes it).  grad, pred, loss: as ``input_grad`` returned them for ``adv``.  With want_info returns
+        [B,3] = (adversarial loss, dist * weight, dist) per cloud."""
+        B, stride = int(adv.shape[0]), int(adv.shape[1])
+        st = self._cw_struct(state, B, stride)
+        ptrs = [self._cw_cloud(x, B, stride, n) for x, n in ((grad, "grad"), (adv, "adv"), (ori, "ori"), (last_input, "last_input"))]
+        pred = torch.as_tensor(pred).to(device=self.device, dtype=torch.int32).contiguous()
+        target = self._target(target, B)
+        if tuple(pred.shape) != (B,):
+            raise IfdError("pred must be [B]")
+        if loss is not None:
+            loss = _f32(torch.as_tensor(loss), self.device)
+            if tuple(loss.shape) != (B,):
+                raise IfdError("loss must be [B]")
+        if n_points is not None:
+            n_points = torch.as_tensor(n_points).to(device=self.device, dtype=torch.int32).contiguous()
+        info = torch.empty(B, 3, device=self.device, dtype=torch.float32) if want_info else None
+        ptr = lambda x: None if x is None else x.data_ptr()        # noqa: E731
+        with torch.cuda.device(self.device):
+            self._check(self.lib.ifd_cw_step(self.ctx, C.byref(st), ptrs[0], pred.data_ptr(), ptr(loss), target.data_ptr(), ptrs[1], ptrs[2],
+                                             ptrs[3], ptr(info), int(t), float(lr), float(scale), ptr(n_points), B, stride, self._stream()))
+        return info
+
+    def cw_adjust(self, state, target, n_points=None):
+        """The end of a search step (ifd_cw_adjust), IN PLACE on ``state``: the weight's binary search, then the reset of
+        bestdist, bestscore, m and v."""
+        B, stride = int(state["m"].shape[0]), int(state["m"].shape[1])
+        st = self._cw_struct(state, B, stride)
+        target = self._target(target, B)
+        if n_points is not None:
+            n_points = torch.as_tensor(n_points).to(device=self.device, dtype=torch.int32).contiguous()
+        with torch.cuda.device(self.device):
+            self._check(self.lib.ifd_cw_adjust(self.ctx, C.byref(st), target.data_ptr(), None if n_points is None else n_points.data_ptr(),
+                                               B, stride, self._stream()))
+        return state
+
+    def cw_perturb_attack(self, pc, target, noise=None, loss="logits", kappa=0., scale=1., attack_lr=1e-2, init_weight=10.,
+                          max_weight=80., binary_step=10, num_iter=500, n_points=None, want_bounds: bool = False):
+        """The whole CW point-perturbation attack on the device (ifd_cw_perturb_attack): -> (adversarial clouds [B,N,3],
+        best_dist [B] (1e10 where no iteration reached the target), success [B] bool) and with want_bounds also
+        {"weight", "lower", "upper"} [B] float64.  noise: [binary_step,B,N,3], the start noise of every search step, or None."""
+        loss_kind = self._loss_kind(loss)
+        pc, n_points = self._batch(pc, n_points)
+        B, stride = int(pc.shape[0]), int(pc.shape[1])
+        if B < 1 or stride < 1:
+            raise IfdError("empty batch")
+        target = self._target(target, B)
+        if noise is not None:
+            noise = _f32(torch.as_tensor(noise), self.device)
+            if tuple(noise.shape) != (int(binary_step), B, stride, 3):
+                raise IfdError("noise must be [binary_step,B,N,3]")
+        out = torch.empty_like(pc)
+        best = torch.empty(B, device=self.device, dtype=torch.float32)
+        success = torch.empty(B, device=self.device, dtype=torch.int32)
+        bounds = torch.empty(3, B, device=self.device, dtype=torch.float64) if want_bounds else None
+        P = _lib.IfdCwParams(C.sizeof(_lib.IfdCwParams), loss_kind, int(binary_step), int(num_iter), float(kappa), float(scale),
+                             float(attack_lr), float(init_weight), float(max_weight))
+        with torch.cuda.device(self.device):
+            self._check(self.lib.ifd_cw_perturb_attack(self.ctx, C.byref(P), pc.data_ptr(), None if n_points is None else n_points.data_ptr(),
+                                                       target.data_ptr(), None if noise is None else noise.data_ptr(), B, stride,
+                                                       out.data_ptr(), best.data_ptr(), success.data_ptr(),
+                                                       None if bounds is None else bounds.data_ptr(), self._stream()))
+        if want_bounds:
+            return out, best, success.bool(), {"weight": bounds[0], "lower": bounds[1], "upper": bounds[2]}
+        return out, best, success.bool()
