@@ -174,6 +174,30 @@ CW_SIGNATURES = {
                                         C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
 }
 
+# include/ifd_knn.h (the kNN attack on the PointNet victim), versioned on its own
+KNN_ABI_VERSION = 1
+KNN_MIN_POINTS, KNN_MAX_POINTS = 6, 2048
+
+
+class IfdKnnParams(C.Structure):
+    _fields_ = [("struct_size", C.c_int32), ("loss_kind", C.c_int32), ("num_iter", C.c_int32), ("kappa", C.c_float), ("scale", C.c_float),
+                ("attack_lr", C.c_float), ("chamfer_weight", C.c_float), ("knn_weight", C.c_float), ("alpha", C.c_float),
+                ("budget", C.c_float)]
+
+
+class IfdKnnDiag(C.Structure):
+    _fields_ = [("info", C.c_void_p), ("dist_grad", C.c_void_p), ("nn_ori", C.c_void_p), ("nn5", C.c_void_p), ("mask", C.c_void_p)]
+
+
+KNN_SIGNATURES = {
+    "ifd_knn_abi_version": (C.c_int, []),
+    "ifd_knn_step": (C.c_int, [C.c_void_p, C.POINTER(IfdKnnParams), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                               C.c_void_p, C.c_int, C.c_float, C.c_float, C.POINTER(IfdKnnDiag), C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
+    "ifd_knn_project_clip": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
+    "ifd_knn_attack": (C.c_int, [C.c_void_p, C.POINTER(IfdKnnParams), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
+                                 C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+}
+
 _lib = None
 
 
@@ -189,7 +213,7 @@ def load() -> C.CDLL:
     import torch  # noqa: F401  (loads libamdhip64.so.7 first; libifd binds to the same runtime)
     lib = C.CDLL(LIB_PATH, mode=C.RTLD_GLOBAL)
     for name, (res, args) in list(SIGNATURES.items()) + list(DUP_SIGNATURES.items()) + list(CLS_SIGNATURES.items()) + \
-            list(ATK_SIGNATURES.items()) + list(CW_SIGNATURES.items()):
+            list(ATK_SIGNATURES.items()) + list(CW_SIGNATURES.items()) + list(KNN_SIGNATURES.items()):
         fn = getattr(lib, name)          # AttributeError if the library lacks a declared symbol
         fn.restype, fn.argtypes = res, args
     if lib.ifd_abi_version() != ABI_VERSION:
@@ -202,5 +226,7 @@ def load() -> C.CDLL:
         raise ImportError("libifd.so ATK ABI %d != binding ATK ABI %d; rebuild" % (lib.ifd_atk_abi_version(), ATK_ABI_VERSION))
     if lib.ifd_cw_abi_version() != CW_ABI_VERSION:
         raise ImportError("libifd.so CW ABI %d != binding CW ABI %d; rebuild" % (lib.ifd_cw_abi_version(), CW_ABI_VERSION))
+    if lib.ifd_knn_abi_version() != KNN_ABI_VERSION:
+        raise ImportError("libifd.so KNN ABI %d != binding KNN ABI %d; rebuild" % (lib.ifd_knn_abi_version(), KNN_ABI_VERSION))
     _lib = lib
     return lib

@@ -17,7 +17,8 @@ The reference's loss is a mean over the batch it was called with; pass that batc
 reproduce how its ``+ 1e-9`` terms weigh against the gradient's norm.  The default is the batch passed to ``attack``.
 
 ``CWPerturb`` is the reference's Carlini-Wagner point-perturbation attack (baselines/attack/CW/Perturb.py, include/ifd_cw.h), on the
-same two loop forms; it is not one of ``ATTACKS``, which names the FGM family for the fgm_attack CLI.
+same two loop forms; it is not one of ``ATTACKS``, which names the FGM family for the fgm_attack CLI.  ``CWKNN`` is the reference's
+kNN attack (baselines/attack/CW/kNN.py, include/ifd_knn.h), likewise.
 """
 from __future__ import annotations
 
@@ -183,3 +184,85 @@ class CWPerturb:
         success_num = int(ok.sum())
         print('Successfully attack {}/{}'.format(success_num, B))
         return dist.cpu().numpy().astype(np.float64), adv.cpu().numpy(), success_num
+
+
+class CWKNN:
+    """The kNN attack (kNN.py CWKNN): ``num_iter`` Adam iterations on the adversarial loss plus ChamferkNNDist('adv2ori', 5, 1.05, 5.,
+    3.), each followed by ProjectInnerClipLinf(0.1); no binary search, no records.  ``model`` is a ``runtime.Classifier`` (anything
+    with its ``input_grad``, ``knn_step``, ``knn_attack`` and ``predict``), ``adv_func`` the loss by name ("logits":
+    LogitsAdvLoss(kappa), or "cross_entropy"); ``dist_func`` "chamfer_knn" and ``clip_func`` "project_inner_clip_linf" are the only
+    ones built.  ``attack(data, target [B])`` takes data [B,K,6] (points and normals) or [B,K,3] (no projection, the clip alone, as
+    the reference does without normals) and returns the reference's pair (adversarial clouds [B,K,3] as a numpy array,
+    success_num).  ``verbose=True`` drives the loop from the host, one ``input_grad`` and one ``knn_step`` an iteration, with the
+    reference's two lines every num_iter // 5 iterations (every iteration when num_iter < 5; the two losses are the batch means of the
+    previous iteration, zero at iteration 0) but not its wall-clock lines; ``verbose=False`` is one library call and prints the last
+    line only.  Both give the same bits.
+
+    The start is data + randn * 1e-7, drawn here from a seeded HOST torch.Generator: agreement with a reference run in distribution
+    only.  ``ref_batch``: the batch the reference's losses are a mean over (scale = 1 / ref_batch); default: the batch passed."""
+
+    CHAMFER_WEIGHT, KNN_WEIGHT, ALPHA, BUDGET = 5., 3., 1.05, 0.1
+
+    def __init__(self, model, adv_func="logits", dist_func="chamfer_knn", clip_func="project_inner_clip_linf", attack_lr=1e-3,
+                 num_iter=2500, kappa=15., seed=1, ref_batch=None, verbose=True):
+        if str(dist_func).lower() != "chamfer_knn":
+            raise ValueError("only the chamfer_knn distance of the reference's script is built")
+        if str(clip_func).lower() != "project_inner_clip_linf":
+            raise ValueError("only the project_inner_clip_linf clip of the reference's script is built")
+        if int(num_iter) < 1:
+            raise ValueError("num_iter must be at least 1")
+        self.model, self.adv_func, self.kappa = model, adv_func, float(kappa)
+        self.attack_lr, self.num_iter = float(attack_lr), int(num_iter)
+        self.ref_batch, self.verbose = ref_batch, verbose
+        self.generator = torch.Generator().manual_seed(int(seed))
+
+    def noise(self, data: torch.Tensor) -> torch.Tensor:
+        """[B,K,3]: the start noise, one draw."""
+        return torch.randn((int(data.shape[0]), int(data.shape[1]), 3), generator=self.generator) * 1e-7
+
+    def _scale(self, B):
+        return 1.0 / float(self.ref_batch or B)
+
+    def _hyper(self):
+        return dict(chamfer_weight=self.CHAMFER_WEIGHT, knn_weight=self.KNN_WEIGHT, alpha=self.ALPHA, budget=self.BUDGET)
+
+    def _loop(self, pts, normal, target, noise):
+        """kNN.py:77-140 from the host: the kernels of ifd_knn_attack on the same numbers."""
+        net = self.model
+        dev = net.device
+        B = int(pts.shape[0])
+        ori = pts.to(dev).contiguous()
+        nrm = None if normal is None else normal.to(dev).contiguous()
+        tgt = target.to(dev)
+        adv = ori + noise.to(dev)
+        m, v = torch.zeros_like(ori), torch.zeros_like(ori)
+        every = max(self.num_iter // 5, 1)
+        info = None
+        for it in range(self.num_iter):
+            grad, aux = net.input_grad(adv, tgt, self.adv_func, self.kappa, self._scale(B), want_aux=True)
+            if it % every == 0:
+                adv_loss, dist_loss = (0., 0.) if info is None else (float(info[:, 0].mean()), float(info[:, 3].mean()))
+                print('Iteration {}/{}, success {}/{}\nadv_loss: {:.4f}, dist_loss: {:.4f}'.format(
+                    it, self.num_iter, int((aux["pred"].long() == tgt.long()).sum()), B, adv_loss, dist_loss))
+            want = ("info",) if it % every == every - 1 else ()
+            info = net.knn_step(grad, adv, ori, m, v, it + 1, self.attack_lr, self._scale(B), normal=nrm, loss=aux["loss"], want=want,
+                                **self._hyper()).get("info")
+        return adv, net.predict(adv).to(tgt.device) == tgt
+
+    def attack(self, data, target):
+        data = torch.as_tensor(np.asarray(data) if not torch.is_tensor(data) else data).float().cpu()
+        target = torch.as_tensor(np.asarray(target) if not torch.is_tensor(target) else target).long().cpu()
+        if data.dim() != 3 or int(data.shape[2]) not in (3, 6):
+            raise ValueError("data must be [B,K,6] (points and normals) or [B,K,3]")
+        B = int(data.shape[0])
+        pts = data[:, :, :3].contiguous()
+        normal = data[:, :, 3:].contiguous() if int(data.shape[2]) == 6 else None
+        noise = self.noise(data)
+        if self.verbose:
+            adv, ok = self._loop(pts, normal, target, noise)
+        else:
+            adv, _, ok = self.model.knn_attack(pts, target, normal, noise, self.adv_func, self.kappa, self._scale(B), self.attack_lr,
+                                               self.num_iter, **self._hyper())
+        success_num = int(ok.sum())
+        print('Successfully attack {}/{}'.format(success_num, B))
+        return adv.cpu().numpy(), success_num

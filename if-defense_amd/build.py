@@ -36,6 +36,7 @@ def _deps():
     hdr.append(os.path.join(os.path.dirname(HERE), "include", "ifd_cls.h"))
     hdr.append(os.path.join(os.path.dirname(HERE), "include", "ifd_atk.h"))
     hdr.append(os.path.join(os.path.dirname(HERE), "include", "ifd_cw.h"))
+    hdr.append(os.path.join(os.path.dirname(HERE), "include", "ifd_knn.h"))
     return hdr
 
 

@@ -9,6 +9,7 @@
 #include "../../include/ifd_cls.h"
 #include "../../include/ifd_atk.h"
 #include "../../include/ifd_cw.h"
+#include "../../include/ifd_knn.h"
 
 #include <hip/hip_runtime.h>
 
@@ -1934,6 +1935,109 @@ int ifd_cw_perturb_attack(ifd_ctx* ctx, const ifd_cw_params* params, const float
     }
     e = launch_cw_finish(S, last, pc_out, success, bounds, n_points, B, stride, s);
     if (e != hipSuccess) return fail(ctx, IFD_ERR_HIP, "ifd_cw_perturb_attack: finish", e);
+    return IFD_OK;
+}
+
+}  // extern "C"
+
+// ---- the kNN attack (include/ifd_knn.h) ----------------------------------------------------------------------------------
+static_assert(IFD_KNN_MAX_POINTS == ifd::KNN_MAX_POINTS, "the header's limit is the kernel's");
+
+extern "C" {
+
+int ifd_knn_abi_version(void) { return IFD_KNN_ABI_VERSION; }
+
+int ifd_knn_step(ifd_ctx* ctx, const ifd_knn_params* params, const float* grad, const float* loss, float* adv, const float* ori,
+                 const float* normal, float* m, float* v, int t, float lr, float scale, const ifd_knn_diag* diag, const int32_t* n_points,
+                 int B, int stride, void* stream) {
+    if (!ctx) return IFD_ERR_ARG;
+    if (int rc = atk_context_ok(ctx, "ifd_knn_step")) return rc;
+    if (!params || params->struct_size != (int32_t)sizeof(ifd_knn_params))
+        return fail(ctx, IFD_ERR_ARG, "ifd_knn_step: params missing or of another struct_size");
+    if (B < 1) return fail(ctx, IFD_ERR_ARG, "ifd_knn_step: B >= 1 is needed");
+    if (stride < IFD_KNN_MIN_POINTS || stride > IFD_KNN_MAX_POINTS) return fail(ctx, IFD_ERR_ARG, "ifd_knn_step: stride outside [6, 2048]");
+    if (!grad || !adv || !ori || !m || !v || t < 1) return fail(ctx, IFD_ERR_ARG, "ifd_knn_step: missing pointer (grad, adv, ori, m, v) or t < 1");
+    IFD_ON_CTX_DEVICE(ctx);
+    const KnnDiag D = diag ? KnnDiag{diag->info, diag->dist_grad, diag->nn_ori, diag->nn5, diag->mask} : KnnDiag{};
+    hipError_t e = launch_knn_step(grad, loss, adv, ori, normal, m, v, D, params->chamfer_weight, params->knn_weight, params->alpha,
+                                   params->budget, t, lr, scale, n_points, B, stride, static_cast<hipStream_t>(stream));
+    if (e != hipSuccess) return fail(ctx, IFD_ERR_HIP, "ifd_knn_step launch", e);
+    return IFD_OK;
+}
+
+int ifd_knn_project_clip(ifd_ctx* ctx, float* adv, const float* ori, const float* normal, float budget, const int32_t* n_points, int B,
+                         int stride, void* stream) {
+    if (!ctx) return IFD_ERR_ARG;
+    if (int rc = atk_context_ok(ctx, "ifd_knn_project_clip")) return rc;
+    if (B < 1) return fail(ctx, IFD_ERR_ARG, "ifd_knn_project_clip: B >= 1 is needed");
+    if (stride < 1 || stride > IFD_CLS_MAX_POINTS) return fail(ctx, IFD_ERR_ARG, "ifd_knn_project_clip: stride outside [1, 10000]");
+    if (!adv || !ori) return fail(ctx, IFD_ERR_ARG, "ifd_knn_project_clip: missing pointer (adv, ori)");
+    IFD_ON_CTX_DEVICE(ctx);
+    hipError_t e = launch_knn_clip(adv, ori, normal, budget, n_points, B, stride, static_cast<hipStream_t>(stream));
+    if (e != hipSuccess) return fail(ctx, IFD_ERR_HIP, "ifd_knn_project_clip launch", e);
+    return IFD_OK;
+}
+
+int ifd_knn_attack(ifd_ctx* ctx, const ifd_knn_params* params, const float* pc_in, const float* normal, const int32_t* n_points,
+                   const int32_t* target, const float* noise, int B, int stride, float* pc_out, int32_t* pred, int32_t* success,
+                   void* stream) {
+    if (!ctx) return IFD_ERR_ARG;
+    if (int rc = atk_context_ok(ctx, "ifd_knn_attack")) return rc;
+    if (!params || params->struct_size != (int32_t)sizeof(ifd_knn_params))
+        return fail(ctx, IFD_ERR_ARG, "ifd_knn_attack: params missing or of another struct_size");
+    if (params->num_iter < 1) return fail(ctx, IFD_ERR_ARG, "ifd_knn_attack: num_iter < 1");
+    if (!atk_loss_ok(params->loss_kind)) return fail(ctx, IFD_ERR_ARG, "ifd_knn_attack: unknown loss_kind");
+    if (B < 1) return fail(ctx, IFD_ERR_ARG, "ifd_knn_attack: B >= 1 is needed");
+    if (stride < IFD_KNN_MIN_POINTS || stride > IFD_KNN_MAX_POINTS) return fail(ctx, IFD_ERR_ARG, "ifd_knn_attack: stride outside [6, 2048]");
+    if (!pc_in || !target || !pc_out || !pred || !success)
+        return fail(ctx, IFD_ERR_ARG, "ifd_knn_attack: missing pointer (pc_in, target, pc_out, pred, success)");
+    const size_t cloud = (size_t)stride * 12, all = (size_t)B * cloud;
+    {
+        const char *a = reinterpret_cast<const char*>(pc_in), *b = reinterpret_cast<const char*>(pc_out);
+        if (a < b + all && b < a + all) return fail(ctx, IFD_ERR_ARG, "ifd_knn_attack: pc_out overlaps pc_in");
+    }
+    IFD_ON_CTX_DEVICE(ctx);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const size_t state = ((size_t)B * (3 * cloud + 160 + 8) + 255) / 256 * 256;
+    const size_t fwd = 256 + cls_bytes_per_cloud(stride, false) * (size_t)atk_chunk(B);
+    hipError_t e = ensure_ws(ctx, state + std::max(atk_grad_ws_bytes(B, stride), fwd));
+    if (e != hipSuccess) return fail(ctx, IFD_ERR_NOMEM, "ifd_knn_attack: workspace", e);
+    {   // the one blocking step: counts (a cloud below 6 points has no five neighbours) and targets
+        int32_t bad[2] = {0, 0};
+        e = launch_knn_check(n_points, target, B, stride, ctx->cls_classes, static_cast<int32_t*>(ctx->ws), s);
+        if (e == hipSuccess) e = hipMemcpyAsync(bad, ctx->ws, sizeof(bad), hipMemcpyDeviceToHost, s);
+        if (e == hipSuccess) e = hipStreamSynchronize(s);
+        if (e != hipSuccess) return fail(ctx, IFD_ERR_HIP, "ifd_knn_attack: checking n_points and target", e);
+        if (bad[0] != 0)
+            return fail(ctx, IFD_ERR_ARG, ("ifd_knn_attack: " + std::to_string(bad[0]) + " cloud(s) with n_points outside [6, stride]").c_str());
+        if (bad[1] != 0)
+            return fail(ctx, IFD_ERR_ARG, ("ifd_knn_attack: " + std::to_string(bad[1]) + " target(s) outside [0, 40)").c_str());
+    }
+    // the loop's own state in front of the workspace of the calls it makes; adv is pc_out itself
+    char* p = static_cast<char*>(ctx->ws);
+    auto take = [&](size_t bytes) { char* q = p; p += bytes; return q; };
+    float* grad = reinterpret_cast<float*>(take(all));
+    float* m = reinterpret_cast<float*>(take(all));
+    float* v = reinterpret_cast<float*>(take(all));
+    float* logits = reinterpret_cast<float*>(take((size_t)B * 160));
+    float* loss = reinterpret_cast<float*>(take((size_t)B * 4));
+    e = launch_cw_start(pc_in, noise, pc_out, n_points, B, stride, s);
+    if (e == hipSuccess) e = hipMemsetAsync(m, 0, 2 * all, s);         // m and v lie side by side
+    if (e != hipSuccess) return fail(ctx, IFD_ERR_HIP, "ifd_knn_attack: start", e);
+    const ifd_atk_out out{nullptr, loss, nullptr, nullptr, nullptr, nullptr};
+    for (int it = 0; it < params->num_iter; ++it) {
+        if (int rc = input_grad_impl(ctx, state, pc_out, n_points, B, stride, target, params->loss_kind, params->kappa, params->scale, grad,
+                                     &out, s))
+            return rc;
+        e = launch_knn_step(grad, loss, pc_out, pc_in, normal, m, v, KnnDiag{}, params->chamfer_weight, params->knn_weight, params->alpha,
+                            params->budget, it + 1, params->attack_lr, params->scale, n_points, B, stride, s);
+        if (e != hipSuccess) return fail(ctx, IFD_ERR_HIP, "ifd_knn_attack: step", e);
+    }
+    // the final forward behind the loop's state; the counts were checked above, so it does not block
+    ifd_cls_aux aux{nullptr, nullptr, nullptr, pred};
+    if (int rc = cls_forward_impl(ctx, pc_out, n_points, B, stride, logits, &aux, stream, false, state)) return rc;
+    e = launch_atk_success(pred, target, B, success, s);
+    if (e != hipSuccess) return fail(ctx, IFD_ERR_HIP, "ifd_knn_attack: success", e);
     return IFD_OK;
 }
 

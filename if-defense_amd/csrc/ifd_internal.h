@@ -285,4 +285,22 @@ hipError_t launch_cw_adjust(const CwState& S, const int32_t* target, const int32
 hipError_t launch_cw_finish(const CwState& S, const float* last_input, float* pc_out, int32_t* success, double* bounds,
                             const int32_t* n_points, int B, int stride, hipStream_t s);
 
+// ---- the kNN attack (pointnet_knn.hip, include/ifd_knn.h) ----
+constexpr int KNN_MAX_POINTS = 2048;            // IFD_KNN_MAX_POINTS: adv and ori of one cloud in a workgroup's static LDS
+struct KnnDiag {                                // ifd_knn_diag, member for member; every pointer may be null
+    float* info;                                // [B][4]
+    float* dist_grad;                           // [B][stride][3]
+    int32_t* nn_ori;                            // [B][stride]
+    int32_t* nn5;                               // [B][stride][5]
+    int32_t* mask;                              // [B][stride]
+};
+// one iteration behind ifd_cls_input_grad, a workgroup a cloud; 6 <= stride <= KNN_MAX_POINTS is the caller's to check
+hipError_t launch_knn_step(const float* grad, const float* loss, float* adv, const float* ori, const float* normal, float* m, float* v,
+                           const KnnDiag& D, float chamfer_weight, float knn_weight, float alpha, float budget, int t, float lr, float scale,
+                           const int32_t* n_points, int B, int stride, hipStream_t s);
+hipError_t launch_knn_clip(float* adv, const float* ori, const float* normal, float budget, const int32_t* n_points, int B, int stride,
+                           hipStream_t s);
+// bad[0] = clouds with n_points outside [6, stride], bad[1] = targets outside [0, n_classes)
+hipError_t launch_knn_check(const int32_t* n_points, const int32_t* target, int B, int stride, int n_classes, int32_t* bad, hipStream_t s);
+
 }  // namespace ifd

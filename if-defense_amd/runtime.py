@@ -863,3 +863,97 @@ class Classifier:
         if want_bounds:
             return out, best, success.bool(), {"weight": bounds[0], "lower": bounds[1], "upper": bounds[2]}
         return out, best, success.bool()
+
+    # ---- include/ifd_knn.h: the kNN attack (models without feature_transform) ----
+    def _knn_params(self, loss_kind=_lib.ATK_LOSS_LOGITS, num_iter=1, kappa=0., scale=1., attack_lr=1e-3, chamfer_weight=5., knn_weight=3.,
+                    alpha=1.05, budget=0.1):
+        return _lib.IfdKnnParams(C.sizeof(_lib.IfdKnnParams), int(loss_kind), int(num_iter), float(kappa), float(scale), float(attack_lr),
+                                 float(chamfer_weight), float(knn_weight), float(alpha), float(budget))
+
+    def _knn_counts(self, n_points, B):
+        if n_points is None:
+            return None
+        n_points = torch.as_tensor(n_points).to(device=self.device, dtype=torch.int32).contiguous()
+        if tuple(n_points.shape) != (B,):
+            raise IfdError("n_points must be [B]")
+        return n_points
+
+    def knn_step(self, grad, adv, ori, m, v, t, lr, scale=1., normal=None, loss=None, n_points=None, chamfer_weight=5., knn_weight=3.,
+                 alpha=1.05, budget=0.1, want=()):
+        """One iteration of the kNN attack behind ``input_grad`` (ifd_knn_step), IN PLACE on ``adv``, ``m`` and ``v``: contiguous
+        float32 [B,N,3] device tensors, 6 <= N <= 2048.  grad, loss: as ``input_grad`` returned them for ``adv``; normal [B,N,3] or
+        None (then the clip alone follows Adam).  ``want``: names of diagnostics to return as a dict - "info" [B,4] (adversarial
+        loss, cd, knn, n (w1 cd + w2 knn)), "dist_grad" [B,N,3], "nn_ori" [B,N], "nn5" [B,N,5], "mask" [B,N] (int32; rows beyond a
+        cloud's count, and clouds below 6 points, are left as they were allocated: -1 / NaN)."""
+        if not torch.is_tensor(adv) or adv.dim() != 3:
+            raise IfdError("adv must be a contiguous float32 [B,N,3] device tensor")
+        B, stride = int(adv.shape[0]), int(adv.shape[1])
+        names = (("grad", grad), ("adv", adv), ("ori", ori), ("m", m), ("v", v), ("normal", normal))
+        for name, x in names:
+            if x is None and name != "normal":
+                raise IfdError("%s is missing" % name)
+        ptrs = {name: self._cw_cloud(x, B, stride, name) for name, x in names}
+        if loss is not None:
+            loss = _f32(torch.as_tensor(loss), self.device)
+            if tuple(loss.shape) != (B,):
+                raise IfdError("loss must be [B]")
+        n_points = self._knn_counts(n_points, B)
+        shapes = {"info": ((B, 4), torch.float32), "dist_grad": ((B, stride, 3), torch.float32), "nn_ori": ((B, stride), torch.int32),
+                  "nn5": ((B, stride, 5), torch.int32), "mask": ((B, stride), torch.int32)}
+        out = {}
+        for k in want:
+            if k not in shapes:
+                raise IfdError("unknown diagnostic %r (info | dist_grad | nn_ori | nn5 | mask)" % (k,))
+            shape, dt = shapes[k]
+            out[k] = torch.full(shape, float("nan") if dt == torch.float32 else -1, device=self.device, dtype=dt)
+        ptr = lambda x: None if x is None else x.data_ptr()        # noqa: E731
+        diag = _lib.IfdKnnDiag(*[ptr(out.get(k)) for k in ("info", "dist_grad", "nn_ori", "nn5", "mask")])
+        P = self._knn_params(chamfer_weight=chamfer_weight, knn_weight=knn_weight, alpha=alpha, budget=budget)
+        with torch.cuda.device(self.device):
+            self._check(self.lib.ifd_knn_step(self.ctx, C.byref(P), ptrs["grad"], ptr(loss), ptrs["adv"], ptrs["ori"], ptrs["normal"],
+                                              ptrs["m"], ptrs["v"], int(t), float(lr), float(scale), C.byref(diag) if out else None,
+                                              ptr(n_points), B, stride, self._stream()))
+        return out
+
+    def knn_project_clip(self, adv, ori, normal=None, budget=0.1, n_points=None):
+        """ProjectInnerClipLinf(budget) IN PLACE on ``adv`` (ifd_knn_project_clip): contiguous float32 [B,N,3] device tensors;
+        normal None: the clip alone."""
+        if not torch.is_tensor(adv) or adv.dim() != 3:
+            raise IfdError("adv must be a contiguous float32 [B,N,3] device tensor")
+        B, stride = int(adv.shape[0]), int(adv.shape[1])
+        if ori is None:
+            raise IfdError("ori is missing")
+        ptrs = [self._cw_cloud(x, B, stride, name) for name, x in (("adv", adv), ("ori", ori), ("normal", normal))]
+        n_points = self._knn_counts(n_points, B)
+        with torch.cuda.device(self.device):
+            self._check(self.lib.ifd_knn_project_clip(self.ctx, ptrs[0], ptrs[1], ptrs[2], float(budget),
+                                                      None if n_points is None else n_points.data_ptr(), B, stride, self._stream()))
+        return adv
+
+    def knn_attack(self, pc, target, normal=None, noise=None, loss="logits", kappa=15., scale=1., attack_lr=1e-3, num_iter=2500,
+                   n_points=None, chamfer_weight=5., knn_weight=3., alpha=1.05, budget=0.1):
+        """The whole kNN attack on the device (ifd_knn_attack): -> (adversarial clouds [B,N,3], pred [B] int64, success [B] bool).
+        pc [B,N,3]; normal [B,N,3] or None (the clip alone); noise [B,N,3], the start noise, or None."""
+        loss_kind = self._loss_kind(loss)
+        pc, n_points = self._batch(pc, n_points)
+        B, stride = int(pc.shape[0]), int(pc.shape[1])
+        if B < 1 or stride < 1:
+            raise IfdError("empty batch")
+        target = self._target(target, B)
+        extra = {}
+        for name, x in (("normal", normal), ("noise", noise)):
+            if x is not None:
+                x = _f32(torch.as_tensor(x), self.device)
+                if tuple(x.shape) != (B, stride, 3):
+                    raise IfdError("%s must be [B,N,3]" % name)
+            extra[name] = x
+        out = torch.empty_like(pc)
+        pred = torch.empty(B, device=self.device, dtype=torch.int32)
+        success = torch.empty(B, device=self.device, dtype=torch.int32)
+        P = self._knn_params(loss_kind, num_iter, kappa, scale, attack_lr, chamfer_weight, knn_weight, alpha, budget)
+        ptr = lambda x: None if x is None else x.data_ptr()        # noqa: E731
+        with torch.cuda.device(self.device):
+            self._check(self.lib.ifd_knn_attack(self.ctx, C.byref(P), pc.data_ptr(), ptr(extra["normal"]), ptr(n_points), target.data_ptr(),
+                                                ptr(extra["noise"]), B, stride, out.data_ptr(), pred.data_ptr(), success.data_ptr(),
+                                                self._stream()))
+        return out, pred.long(), success.bool()
