@@ -83,6 +83,10 @@ SIGNATURES = {
     "ifd_onet_mesh_sample": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(IfdMeshParams), C.c_void_p, C.c_void_p,
                                        C.c_void_p, C.c_void_p, C.c_void_p]),
     "ifd_mc_table": (C.c_int, [C.c_void_p, C.c_void_p]),
+    # validation seams of the mesh path
+    "ifd_mesh_from_grid": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_float, C.c_int, C.c_int, C.c_uint64,
+                                     C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "ifd_mise_from_field": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_void_p, C.c_void_p]),
 }
 
 # include/ifd_dup.h (the baseline defenses: SRS, DUP fill, PU-Net), versioned on its own

@@ -1110,6 +1110,135 @@ int ifd_mc_table(int8_t* tri, uint8_t* ntri) {
     return IFD_OK;
 }
 
+}  // extern "C"
+
+namespace {
+// Scratch of one pass of the mesh path over `chunk` clouds: the MISE arrays (g), the per-cube counts / offsets and the triangle soup.
+struct MeshWork {
+    MiseGrid g;
+    int chunk;
+    int* cube_offs;
+    float* tris;
+    double* area;
+    int* ntri;
+};
+
+// Lays the context's mesh workspace out for clouds of a res0 << depth grid with capT triangle slots each (grown on demand), and
+// makes sure the pinned landing slots of the queue lengths and their events exist.  `who` names the entry point in error texts.
+int mesh_work(ifd_ctx* ctx, const std::string& who, int res0, int depth, double threshold, int B, int capT, MeshWork& w) {
+    MiseGrid& g = w.g;
+    g = MiseGrid{};
+    g.res0 = res0; g.depth = depth; g.P = (res0 << depth) + 1; g.P3 = g.P * g.P * g.P;
+    g.cap = g.P3;                                   // every grid point can be queued once
+    g.pend_stride = ((size_t)g.P3 + 3) & ~(size_t)3;
+    g.sub_total = 0;
+    for (int l = 0; l < 4; ++l) {
+        g.sub_off[l] = g.sub_total;
+        if (l < depth) { const int nv = res0 << l; g.sub_total += nv * nv * nv; }
+    }
+    g.sub_total = (g.sub_total + 3) & ~3;
+    if (g.sub_total == 0) g.sub_total = 4;
+    g.threshold = threshold;
+    const int NC = g.P + 1, ncube = NC * NC * NC;
+    // per-cloud scratch layout (bytes, every block 16-byte aligned)
+    auto al = [](size_t n) { return (n + 15) & ~(size_t)15; };
+    const size_t o_val = 0, o_known = o_val + al((size_t)g.P3 * 4), o_pend = o_known + al(g.P3), o_sub = o_pend + al(g.pend_stride),
+                 o_mix = o_sub + al(g.sub_total), o_list = o_mix + al(g.sub_total), o_cube = o_list + al((size_t)g.cap * 4),
+                 o_tris = o_cube + al((size_t)ncube * 4), o_area = o_tris + al((size_t)capT * 36), per = o_area + al((size_t)capT * 8);
+    const size_t fit = ((size_t)6 << 30) / per;                 // ~6 GB of scratch per pass
+    const int chunk = fit < 1 ? 1 : fit > (size_t)B ? B : (int)fit;
+    w.chunk = chunk;
+    // layout: arrays are [chunk][stride] each (struct-of-arrays), plus count / ntri / ab folded separately
+    const size_t total = per * chunk + al((size_t)chunk * 4) * 3 + al((size_t)(chunk + 1) * 4);
+    hipError_t e = ensure_buf(&ctx->ws_mesh, &ctx->ws_mesh_bytes, total);
+    if (e != hipSuccess) return fail(ctx, IFD_ERR_NOMEM, (who + " workspace").c_str(), e);
+    if (ctx->h_mesh_counts_n < (size_t)chunk) {          // pinned landing slots of the queue lengths + their events (kept by the context)
+        if (ctx->h_mesh_counts) (void)hipHostFree(ctx->h_mesh_counts);
+        ctx->h_mesh_counts = nullptr;
+        ctx->h_mesh_counts_n = 0;
+        e = hipHostMalloc(reinterpret_cast<void**>(&ctx->h_mesh_counts), (size_t)2 * chunk * sizeof(int), hipHostMallocDefault);
+        if (e != hipSuccess) return fail(ctx, IFD_ERR_NOMEM, (who + " pinned counts").c_str(), e);
+        ctx->h_mesh_counts_n = (size_t)chunk;
+    }
+    for (hipEvent_t& ev : ctx->mesh_ev)
+        if (!ev && (e = hipEventCreateWithFlags(&ev, hipEventDisableTiming)) != hipSuccess)
+            return fail(ctx, IFD_ERR_HIP, (who + " events").c_str(), e);
+    char* base = static_cast<char*>(ctx->ws_mesh);
+    auto blk = [&](size_t off_per_cloud) { return base + off_per_cloud * chunk; };
+    g.val = reinterpret_cast<float*>(blk(o_val));
+    g.known = reinterpret_cast<uint8_t*>(blk(o_known));
+    g.pend = reinterpret_cast<uint8_t*>(blk(o_pend));
+    g.sub = reinterpret_cast<uint8_t*>(blk(o_sub));
+    g.mix = reinterpret_cast<uint8_t*>(blk(o_mix));
+    g.list = reinterpret_cast<int*>(blk(o_list));
+    w.cube_offs = reinterpret_cast<int*>(blk(o_cube));
+    w.tris = reinterpret_cast<float*>(blk(o_tris));
+    w.area = reinterpret_cast<double*>(blk(o_area));
+    g.count = reinterpret_cast<int*>(base + per * chunk);
+    w.ntri = reinterpret_cast<int*>(base + per * chunk + al((size_t)chunk * 4));
+    g.prev = reinterpret_cast<int*>(base + per * chunk + al((size_t)chunk * 4) * 2);
+    g.plan = reinterpret_cast<int*>(base + per * chunk + al((size_t)chunk * 4) * 3);
+    return IFD_OK;
+}
+
+// The MISE loop of one pass of nb clouds: init, the eval / update / count-copy / event rounds, the overflow check, termination and
+// to_dense's fill; g.val holds the dense grids afterwards.  `eval(g, nb, s)` enqueues the evaluation of every cloud's queued points
+// (list[0 .. min(count, cap)): val and known written) - the decoder in ifd_onet_mesh_sample, a gather from a caller's field in
+// ifd_mise_from_field.  Adds to ctx->mesh_points / mesh_rounds.
+template <class Eval>
+int mise_rounds(ifd_ctx* ctx, const std::string& who, const MiseGrid& g, int nb, hipStream_t s, Eval&& eval) {
+    hipError_t e = launch_mise_init(g, nb, s);
+    if (e != hipSuccess) return fail(ctx, IFD_ERR_HIP, (who + " init").c_str(), e);
+    // The MISE loop is driven from the device: queue lengths, the split of a round's decoder passes over the CUs and the
+    // clouds that are finished are all decided there (onet.hip grid_plan_kernel / onet_grid_eval_kernel, mesh.hip
+    // mise_begin_kernel).  The host only has to learn WHEN every queue has run empty, and it does so one round late: round r
+    // is enqueued before the queue lengths round r - 1 produced have been looked at (pinned copy + event per round, two
+    // slots), so the GPU never waits for the host; the one round enqueued past the end finds empty queues and is a handful of
+    // empty launches.
+    const int n0 = (g.res0 + 1) * (g.res0 + 1) * (g.res0 + 1);
+    ctx->mesh_points += (unsigned long long)n0 * nb;
+    bool done = false;
+    int round = 0;
+    for (; round < 64 && !done; ++round) {
+        int* slot = ctx->h_mesh_counts + (size_t)(round & 1) * ctx->h_mesh_counts_n;
+        e = eval(g, nb, s);
+        if (e == hipSuccess) e = launch_mise_update(g, nb, s);
+        if (e == hipSuccess) e = hipMemcpyAsync(slot, g.count, (size_t)nb * sizeof(int), hipMemcpyDeviceToHost, s);
+        if (e == hipSuccess) e = hipEventRecord(ctx->mesh_ev[round & 1], s);
+        if (e == hipSuccess && round >= 1) {
+            e = hipEventSynchronize(ctx->mesh_ev[(round - 1) & 1]);
+            const int* c_prev = ctx->h_mesh_counts + (size_t)((round - 1) & 1) * ctx->h_mesh_counts_n;   // queued BY round - 1 = evaluated IN this round
+            int max_count = 0;
+            for (int b = 0; b < nb; ++b) { max_count = c_prev[b] > max_count ? c_prev[b] : max_count; ctx->mesh_points += c_prev[b]; }
+            if (max_count > g.cap) return fail(ctx, IFD_ERR_HIP, (who + ": point queue overflow").c_str());
+            if (max_count == 0) done = true;           // this round (already enqueued) had nothing to do: the grid is complete
+            else ++ctx->mesh_rounds;
+        } else if (e == hipSuccess) {
+            ++ctx->mesh_rounds;                        // round 0 always has the coarse lattice to evaluate
+        }
+        if (e != hipSuccess) return fail(ctx, IFD_ERR_HIP, (who + " round").c_str(), e);
+    }
+    // the last enqueued round's copy must have landed before its slot is reused by the next chunk
+    e = hipEventSynchronize(ctx->mesh_ev[(round - 1) & 1]);
+    if (e != hipSuccess) return fail(ctx, IFD_ERR_HIP, (who + " round").c_str(), e);
+    e = launch_mise_fill(g, nb, s);
+    return e == hipSuccess ? IFD_OK : fail(ctx, IFD_ERR_HIP, (who + " fill").c_str(), e);
+}
+
+// Marching cubes of nb dense grids val [nb][P^3] and the surface samples, into the caller's arrays (already offset to this pass's
+// first cloud; triangles / cum_area optional: their first min(n_triangles, capT) rows are written, nothing else).
+hipError_t mesh_extract(const MeshWork& w, const float* val, int nb, int P, double iso, float box, int capT, int n_sample, uint64_t seed,
+                        int cloud_base, float* points, int32_t* n_triangles, float* triangles, double* cum_area, hipStream_t s) {
+    hipError_t e = launch_marching_cubes(val, nb, P, iso, box, w.cube_offs, w.ntri, capT, w.tris, w.area, s);
+    if (e == hipSuccess) e = launch_sample_surface(w.tris, w.area, w.ntri, nb, capT, n_sample, seed, cloud_base, points, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(n_triangles, w.ntri, (size_t)nb * sizeof(int), hipMemcpyDeviceToDevice, s);
+    if (e == hipSuccess && (triangles || cum_area)) e = launch_copy_triangles(w.tris, w.area, w.ntri, nb, capT, triangles, cum_area, s);
+    return e;
+}
+}  // namespace
+
+extern "C" {
+
 int ifd_onet_mesh_sample(ifd_ctx* ctx, const float* c, int B, const ifd_mesh_params* prm, float* points,
                          int32_t* n_triangles, float* grid, float* triangles, void* stream) {
     if (!ctx) return IFD_ERR_ARG;
@@ -1122,109 +1251,85 @@ int ifd_onet_mesh_sample(ifd_ctx* ctx, const float* c, int B, const ifd_mesh_par
         !(prm->threshold > 0.0 && prm->threshold < 1.0) || prm->precision < 0 || prm->precision > 2)
         return fail(ctx, IFD_ERR_ARG, "ifd_onet_mesh_sample: resolution0 << upsampling_steps <= 128, steps <= 2, 0 < threshold < 1, precision 0 ... 2");
     hipStream_t s = static_cast<hipStream_t>(stream);
-    MiseGrid g{};
-    g.res0 = res0; g.depth = depth; g.P = (res0 << depth) + 1; g.P3 = g.P * g.P * g.P;
-    g.cap = g.P3;                                   // every grid point can be queued once
-    g.pend_stride = ((size_t)g.P3 + 3) & ~(size_t)3;
-    g.sub_total = 0;
-    for (int l = 0; l < 4; ++l) {
-        g.sub_off[l] = g.sub_total;
-        if (l < depth) { const int nv = res0 << l; g.sub_total += nv * nv * nv; }
-    }
-    g.sub_total = (g.sub_total + 3) & ~3;
-    if (g.sub_total == 0) g.sub_total = 4;
-    g.threshold = std::log(prm->threshold) - std::log(1.0 - prm->threshold);        // generation.py:97
+    const std::string who = "ifd_onet_mesh_sample";
     const float box = 1.0f + prm->padding;
-    const int NC = g.P + 1, ncube = NC * NC * NC, capT = prm->max_triangles;
-    // per-cloud scratch layout (bytes, every block 16-byte aligned)
-    auto al = [](size_t n) { return (n + 15) & ~(size_t)15; };
-    const size_t o_val = 0, o_known = o_val + al((size_t)g.P3 * 4), o_pend = o_known + al(g.P3), o_sub = o_pend + al(g.pend_stride),
-                 o_mix = o_sub + al(g.sub_total), o_list = o_mix + al(g.sub_total), o_cube = o_list + al((size_t)g.cap * 4),
-                 o_tris = o_cube + al((size_t)ncube * 4), o_area = o_tris + al((size_t)capT * 36), per = o_area + al((size_t)capT * 8);
-    const size_t fit = ((size_t)6 << 30) / per;                 // ~6 GB of scratch per pass
-    const int chunk = fit < 1 ? 1 : fit > (size_t)B ? B : (int)fit;
-    // layout: arrays are [chunk][stride] each (struct-of-arrays), plus count / ntri / ab folded separately
-    const size_t total = per * chunk + al((size_t)chunk * 4) * 3 + al((size_t)(chunk + 1) * 4);
-    hipError_t e = ensure_buf(&ctx->ws_mesh, &ctx->ws_mesh_bytes, total);
-    if (e != hipSuccess) return fail(ctx, IFD_ERR_NOMEM, "ifd_onet_mesh_sample workspace", e);
-    if (ctx->h_mesh_counts_n < (size_t)chunk) {          // pinned landing slots of the queue lengths + their events (kept by the context)
-        if (ctx->h_mesh_counts) (void)hipHostFree(ctx->h_mesh_counts);
-        ctx->h_mesh_counts = nullptr;
-        ctx->h_mesh_counts_n = 0;
-        e = hipHostMalloc(reinterpret_cast<void**>(&ctx->h_mesh_counts), (size_t)2 * chunk * sizeof(int), hipHostMallocDefault);
-        if (e != hipSuccess) return fail(ctx, IFD_ERR_NOMEM, "ifd_onet_mesh_sample pinned counts", e);
-        ctx->h_mesh_counts_n = (size_t)chunk;
-    }
-    for (hipEvent_t& ev : ctx->mesh_ev)
-        if (!ev && (e = hipEventCreateWithFlags(&ev, hipEventDisableTiming)) != hipSuccess)
-            return fail(ctx, IFD_ERR_HIP, "ifd_onet_mesh_sample events", e);
-    char* base = static_cast<char*>(ctx->ws_mesh);
-    auto blk = [&](size_t off_per_cloud) { return base + off_per_cloud * chunk; };
-    g.val = reinterpret_cast<float*>(blk(o_val));
-    g.known = reinterpret_cast<uint8_t*>(blk(o_known));
-    g.pend = reinterpret_cast<uint8_t*>(blk(o_pend));
-    g.sub = reinterpret_cast<uint8_t*>(blk(o_sub));
-    g.mix = reinterpret_cast<uint8_t*>(blk(o_mix));
-    g.list = reinterpret_cast<int*>(blk(o_list));
-    int* cube_offs = reinterpret_cast<int*>(blk(o_cube));
-    float* tris = reinterpret_cast<float*>(blk(o_tris));
-    double* area = reinterpret_cast<double*>(blk(o_area));
-    g.count = reinterpret_cast<int*>(base + per * chunk);
-    int* ntri = reinterpret_cast<int*>(base + per * chunk + al((size_t)chunk * 4));
-    g.prev = reinterpret_cast<int*>(base + per * chunk + al((size_t)chunk * 4) * 2);
-    g.plan = reinterpret_cast<int*>(base + per * chunk + al((size_t)chunk * 4) * 3);
+    const int capT = prm->max_triangles;
+    MeshWork w;
+    const int st = mesh_work(ctx, who, res0, depth, std::log(prm->threshold) - std::log(1.0 - prm->threshold) /* generation.py:97 */, B, capT, w);
+    if (st != IFD_OK) return st;
+    const MiseGrid& g = w.g;
     ctx->mesh_points = 0;
     ctx->mesh_rounds = 0;
-    for (int b0 = 0; b0 < B; b0 += chunk) {
-        const int nb = B - b0 < chunk ? B - b0 : chunk;
+    for (int b0 = 0; b0 < B; b0 += w.chunk) {
+        const int nb = B - b0 < w.chunk ? B - b0 : w.chunk;
         float* ab = nullptr;
-        e = onet_fold(ctx, c + (size_t)b0 * ONET_C, nb, s, &ab);
-        if (e == hipSuccess) e = launch_mise_init(g, nb, s);
+        hipError_t e = onet_fold(ctx, c + (size_t)b0 * ONET_C, nb, s, &ab);
         if (e != hipSuccess) return fail(ctx, IFD_ERR_HIP, "ifd_onet_mesh_sample init", e);
-        // The MISE loop is driven from the device: queue lengths, the split of a round's decoder passes over the CUs and the
-        // clouds that are finished are all decided there (onet.hip grid_plan_kernel / onet_grid_eval_kernel, mesh.hip
-        // mise_begin_kernel).  The host only has to learn WHEN every queue has run empty, and it does so one round late: round r
-        // is enqueued before the queue lengths round r - 1 produced have been looked at (pinned copy + event per round, two
-        // slots), so the GPU never waits for the host; the one round enqueued past the end finds empty queues and is a handful of
-        // empty launches.
-        const int n0 = (res0 + 1) * (res0 + 1) * (res0 + 1);
-        ctx->mesh_points += (unsigned long long)n0 * nb;
-        bool done = false;
-        int round = 0;
-        for (; round < 64 && !done; ++round) {
-            int* slot = ctx->h_mesh_counts + (size_t)(round & 1) * ctx->h_mesh_counts_n;
-            e = prm->precision != 0 ? launch_onet_grid_eval_bf(prm->precision, ctx->d_onet_img_bf, ctx->d_onet_small, ab, g, nb, ctx->n_cu, box, s)
-                                    : launch_onet_grid_eval(ctx->d_onet_img, ctx->d_onet_small, ab, g, nb, ctx->n_cu, box, s);
-            if (e == hipSuccess) e = launch_mise_update(g, nb, s);
-            if (e == hipSuccess) e = hipMemcpyAsync(slot, g.count, (size_t)nb * sizeof(int), hipMemcpyDeviceToHost, s);
-            if (e == hipSuccess) e = hipEventRecord(ctx->mesh_ev[round & 1], s);
-            if (e == hipSuccess && round >= 1) {
-                e = hipEventSynchronize(ctx->mesh_ev[(round - 1) & 1]);
-                const int* c_prev = ctx->h_mesh_counts + (size_t)((round - 1) & 1) * ctx->h_mesh_counts_n;   // queued BY round - 1 = evaluated IN this round
-                int max_count = 0;
-                for (int b = 0; b < nb; ++b) { max_count = c_prev[b] > max_count ? c_prev[b] : max_count; ctx->mesh_points += c_prev[b]; }
-                if (max_count > g.cap) return fail(ctx, IFD_ERR_HIP, "ifd_onet_mesh_sample: point queue overflow");
-                if (max_count == 0) done = true;           // this round (already enqueued) had nothing to do: the grid is complete
-                else ++ctx->mesh_rounds;
-            } else if (e == hipSuccess) {
-                ++ctx->mesh_rounds;                        // round 0 always has the coarse lattice to evaluate
-            }
-            if (e != hipSuccess) return fail(ctx, IFD_ERR_HIP, "ifd_onet_mesh_sample round", e);
-        }
-        // the last enqueued round's copy must have landed before its slot is reused by the next chunk
-        e = hipEventSynchronize(ctx->mesh_ev[(round - 1) & 1]);
-        if (e != hipSuccess) return fail(ctx, IFD_ERR_HIP, "ifd_onet_mesh_sample round", e);
-        e = launch_mise_fill(g, nb, s);
-        if (e == hipSuccess && grid)
+        const int r = mise_rounds(ctx, who, g, nb, s, [&](const MiseGrid& gg, int n, hipStream_t ss) {
+            return prm->precision != 0 ? launch_onet_grid_eval_bf(prm->precision, ctx->d_onet_img_bf, ctx->d_onet_small, ab, gg, n, ctx->n_cu, box, ss)
+                                       : launch_onet_grid_eval(ctx->d_onet_img, ctx->d_onet_small, ab, gg, n, ctx->n_cu, box, ss);
+        });
+        if (r != IFD_OK) return r;
+        if (grid)
             e = hipMemcpyAsync(grid + (size_t)b0 * g.P3, g.val, (size_t)nb * g.P3 * sizeof(float), hipMemcpyDeviceToDevice, s);
-        if (e == hipSuccess) e = launch_marching_cubes(g.val, nb, g.P, g.threshold, box, cube_offs, ntri, capT, tris, area, s);
         if (e == hipSuccess)
-            e = launch_sample_surface(tris, area, ntri, nb, capT, prm->n_sample, prm->seed, (int)(prm->cloud_index_base + b0),
-                                      points + (size_t)b0 * prm->n_sample * 3, s);
-        if (e == hipSuccess) e = hipMemcpyAsync(n_triangles + b0, ntri, (size_t)nb * sizeof(int), hipMemcpyDeviceToDevice, s);
-        if (e == hipSuccess && triangles)
-            e = hipMemcpyAsync(triangles + (size_t)b0 * capT * 9, tris, (size_t)nb * capT * 9 * sizeof(float), hipMemcpyDeviceToDevice, s);
+            e = mesh_extract(w, g.val, nb, g.P, g.threshold, box, capT, prm->n_sample, prm->seed, (int)(prm->cloud_index_base + b0),
+                             points + (size_t)b0 * prm->n_sample * 3, n_triangles + b0, triangles ? triangles + (size_t)b0 * capT * 9 : nullptr,
+                             nullptr, s);
         if (e != hipSuccess) return fail(ctx, IFD_ERR_HIP, "ifd_onet_mesh_sample", e);
+    }
+    return IFD_OK;
+}
+
+int ifd_mesh_from_grid(ifd_ctx* ctx, const float* grid, int B, int P, double iso, float padding, int max_triangles, int n_sample,
+                       uint64_t seed, int64_t cloud_index_base, float* points, int32_t* n_triangles, float* triangles,
+                       double* cum_area, void* stream) {
+    if (!ctx) return IFD_ERR_ARG;
+    IFD_ON_CTX_DEVICE(ctx);
+    if (ctx->model != IFD_MODEL_ONET) return fail(ctx, IFD_ERR_ARG, "ifd_mesh_from_grid: not an ONet context");
+    if (!grid || !points || !n_triangles || B < 1 || n_sample < 1)
+        return fail(ctx, IFD_ERR_ARG, "ifd_mesh_from_grid: bad argument");
+    if (P < 2 || P > 129 || max_triangles < 1) return fail(ctx, IFD_ERR_ARG, "ifd_mesh_from_grid: 2 <= P <= 129, max_triangles >= 1");
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    MeshWork w;
+    const int st = mesh_work(ctx, "ifd_mesh_from_grid", P - 1, 0, iso, B, max_triangles, w);   // (the MISE arrays stay unused)
+    if (st != IFD_OK) return st;
+    const size_t P3 = (size_t)P * P * P;
+    for (int b0 = 0; b0 < B; b0 += w.chunk) {
+        const int nb = B - b0 < w.chunk ? B - b0 : w.chunk;
+        const hipError_t e = mesh_extract(w, grid + (size_t)b0 * P3, nb, P, iso, 1.0f + padding, max_triangles, n_sample, seed,
+                                          (int)(cloud_index_base + b0), points + (size_t)b0 * n_sample * 3, n_triangles + b0,
+                                          triangles ? triangles + (size_t)b0 * max_triangles * 9 : nullptr,
+                                          cum_area ? cum_area + (size_t)b0 * max_triangles : nullptr, s);
+        if (e != hipSuccess) return fail(ctx, IFD_ERR_HIP, "ifd_mesh_from_grid", e);
+    }
+    return IFD_OK;
+}
+
+int ifd_mise_from_field(ifd_ctx* ctx, const float* field, int B, int P, int resolution0, int upsampling_steps, double threshold,
+                        float* grid, void* stream) {
+    if (!ctx) return IFD_ERR_ARG;
+    IFD_ON_CTX_DEVICE(ctx);
+    if (ctx->model != IFD_MODEL_ONET) return fail(ctx, IFD_ERR_ARG, "ifd_mise_from_field: not an ONet context");
+    if (!field || !grid || B < 1) return fail(ctx, IFD_ERR_ARG, "ifd_mise_from_field: bad argument");
+    const int depth = upsampling_steps, res0 = resolution0;
+    if (depth < 0 || depth > 2 || res0 < 2 || (res0 << depth) > 128 || P != (res0 << depth) + 1)
+        return fail(ctx, IFD_ERR_ARG, "ifd_mise_from_field: resolution0 >= 2, steps <= 2, resolution0 << upsampling_steps <= 128 and == P - 1");
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const std::string who = "ifd_mise_from_field";
+    MeshWork w;
+    const int st = mesh_work(ctx, who, res0, depth, threshold, B, 1, w);
+    if (st != IFD_OK) return st;
+    const MiseGrid& g = w.g;
+    ctx->mesh_points = 0;
+    ctx->mesh_rounds = 0;
+    for (int b0 = 0; b0 < B; b0 += w.chunk) {
+        const int nb = B - b0 < w.chunk ? B - b0 : w.chunk;
+        const float* f = field + (size_t)b0 * g.P3;
+        const int r = mise_rounds(ctx, who, g, nb, s, [&](const MiseGrid& gg, int n, hipStream_t ss) { return launch_mise_gather(gg, f, n, ss); });
+        if (r != IFD_OK) return r;
+        const hipError_t e = hipMemcpyAsync(grid + (size_t)b0 * g.P3, g.val, (size_t)nb * g.P3 * sizeof(float), hipMemcpyDeviceToDevice, s);
+        if (e != hipSuccess) return fail(ctx, IFD_ERR_HIP, "ifd_mise_from_field", e);
     }
     return IFD_OK;
 }

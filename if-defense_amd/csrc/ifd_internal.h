@@ -162,6 +162,7 @@ struct MiseGrid {
 hipError_t launch_mise_init(const MiseGrid& g, int B, hipStream_t s);
 hipError_t launch_mise_update(const MiseGrid& g, int B, hipStream_t s);
 hipError_t launch_mise_fill(const MiseGrid& g, int B, hipStream_t s);
+hipError_t launch_mise_gather(const MiseGrid& g, const float* field, int B, hipStream_t s);
 hipError_t launch_onet_grid_eval(const float* img, const float* small, const float* ab, const MiseGrid& g, int B,
                                  int n_blocks, float box, hipStream_t s);
 hipError_t launch_onet_grid_eval_bf(int precision, const float* img_bf, const float* small, const float* ab, const MiseGrid& g, int B,
@@ -170,6 +171,8 @@ hipError_t mc_upload_table();
 void mc_host_table(int8_t (*tri)[16], uint8_t* ntri);
 hipError_t launch_marching_cubes(const float* val, int B, int P, double iso, float box, int* cube_offs, int* ntri_total,
                                  int cap, float* tris, double* area, hipStream_t s);
+hipError_t launch_copy_triangles(const float* tris, const double* area, const int* ntri_total, int B, int cap, float* out_tris,
+                                 double* out_area, hipStream_t s);
 hipError_t launch_sample_surface(const float* tris, const double* cum_area, const int* ntri_total, int B, int cap, int n,
                                  uint64_t seed, int cloud_base, float* out, hipStream_t s);
 

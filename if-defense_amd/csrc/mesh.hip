@@ -175,6 +175,26 @@ __global__ __launch_bounds__(256) void mise_fill_z_kernel(MiseGrid g) {
     for (int i = threadIdx.x; i < nlines * P; i += 256) { val[i] = fz[i]; known[i] = kz[i]; }
 }
 
+// Validation seam (ifd_mise_from_field): the evaluation step of a round with the decoder replaced by a look-up in a caller's dense
+// field [B][P^3] - every queued point list[0 .. min(count, cap)) of every cloud takes its value from the field and becomes known,
+// which is all onet_grid_eval_kernel does to the MISE state.
+__global__ void mise_gather_kernel(MiseGrid g, const float* __restrict__ field) {
+    const int cloud = blockIdx.y;
+    const int n = min(g.count[cloud], g.cap);
+    const int* list = g.list + (size_t)cloud * g.cap;
+    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
+        const int idx = list[i];
+        g.val[(size_t)cloud * g.P3 + idx] = field[(size_t)cloud * g.P3 + idx];
+        g.known[(size_t)cloud * g.P3 + idx] = 1;
+    }
+}
+
+hipError_t launch_mise_gather(const MiseGrid& g, const float* field, int B, hipStream_t s) {
+    const int need = (g.cap + 255) / 256, blocks = need < 256 ? need : 256;
+    hipLaunchKernelGGL(mise_gather_kernel, dim3(blocks, B), dim3(256), 0, s, g, field);
+    return hipGetLastError();
+}
+
 hipError_t launch_mise_init(const MiseGrid& g, int B, hipStream_t s) {
     hipError_t e = hipMemsetAsync(g.known, 0, (size_t)B * g.P3, s);
     if (e == hipSuccess) e = hipMemsetAsync(g.pend, 0, (size_t)B * g.pend_stride, s);
@@ -368,6 +388,19 @@ __global__ __launch_bounds__(256) void mc_chunk_apply_kernel(int* __restrict__ n
     for (int j = 0; j < 8; ++j) { if (i0 + j < n) a[i0 + j] = run; run += v[j]; }
 }
 
+// Area of the triangle with the DOUBLE vertices p, every operation rounded on its own.  With the compiler free to contract, the edge
+// vectors came out as fma(box, t1, -p0) - the difference of an unrounded product and a rounded one - so the area was that of vertices
+// an ulp away from the ones emitted: 5e-9 of the area for the 1e-7-sized triangles the -1e6 padding cuts off the box corners, and a
+// function of the compiler's fusing choices.  Now it is a function of p alone (tests/test_gpu_mesh_grid.py holds cum_area to the
+// float64 running sum of the plain reference's areas).
+__device__ __forceinline__ double triangle_area(const double (&p)[3][3]) {
+#pragma clang fp contract(off)
+    const double ux = p[1][0] - p[0][0], uy = p[1][1] - p[0][1], uz = p[1][2] - p[0][2];
+    const double vx = p[2][0] - p[0][0], vy = p[2][1] - p[0][1], vz = p[2][2] - p[0][2];
+    const double cx = uy * vz - uz * vy, cy = uz * vx - ux * vz, cz = ux * vy - uy * vx;
+    return 0.5 * sqrt(cx * cx + cy * cy + cz * cz);
+}
+
 // pass 2: emit the triangles (vertex coordinates in the decoder's frame, generation.py:171-176) and their areas.  One thread per
 // TRIANGLE (round 5; one thread per cube left 95 % of every wave idle behind the two or three lanes whose cube is cut by the
 // surface): triangle `at` of a cloud belongs to the last cube whose offset is <= at (cubes without triangles share their
@@ -405,10 +438,7 @@ __global__ void mc_emit_kernel(const float* __restrict__ val, int P, double iso,
     float* o = tris + ((size_t)cloud * cap + at) * 9;
 #pragma unroll
     for (int k = 0; k < 3; ++k) { o[3 * k] = (float)p[k][0]; o[3 * k + 1] = (float)p[k][1]; o[3 * k + 2] = (float)p[k][2]; }
-    const double ux = p[1][0] - p[0][0], uy = p[1][1] - p[0][1], uz = p[1][2] - p[0][2];
-    const double vx = p[2][0] - p[0][0], vy = p[2][1] - p[0][1], vz = p[2][2] - p[0][2];
-    const double cx = uy * vz - uz * vy, cy = uz * vx - ux * vz, cz = ux * vy - uy * vx;
-    area[(size_t)cloud * cap + at] = 0.5 * sqrt(cx * cx + cy * cy + cz * cz);
+    area[(size_t)cloud * cap + at] = triangle_area(p);
 }
 
 // inclusive scan of the triangle areas (double), one block per cloud
@@ -432,7 +462,9 @@ __global__ __launch_bounds__(1024) void area_scan_kernel(double* __restrict__ ar
             part[threadIdx.x] += t;
             __syncthreads();
         }
-        double run = carry + part[threadIdx.x] - sum;
+        // the exclusive prefix is the previous thread's inclusive one - not `part - sum`: behind the 1e-15-sized triangles at a box
+        // corner that difference cancels, and the running sum came out 1e-11 off (relative) where the summation order allows 1e-15
+        double run = carry + (threadIdx.x > 0 ? part[threadIdx.x - 1] : 0.0);
 #pragma unroll
         for (int j = 0; j < 8; ++j) { run += v[j]; if (i0 + j < n) a[i0 + j] = run; }
         __syncthreads();
@@ -496,6 +528,28 @@ hipError_t launch_marching_cubes(const float* val, int B, int P, double iso, flo
     }
     hipLaunchKernelGGL(mc_emit_kernel, dim3((cap + 255) / 256, B), dim3(256), 0, s, val, P, iso, box, cube_offs, ntri_total, cap, tris, area);
     hipLaunchKernelGGL(area_scan_kernel, dim3(B), dim3(1024), 0, s, area, ntri_total, cap);
+    return hipGetLastError();
+}
+
+// the optional outputs: the valid rows (the first min(total, cap)) of the triangle soup and of the cumulative areas; rows past them
+// stay as the caller left them
+__global__ void copy_triangles_kernel(const float* __restrict__ tris, const double* __restrict__ area, const int* __restrict__ ntri_total,
+                                      int cap, float* __restrict__ out_tris, double* __restrict__ out_area) {
+    const int cloud = blockIdx.y;
+    const int n = min(ntri_total[cloud], cap);
+    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
+        const size_t at = (size_t)cloud * cap + i;
+        if (out_tris)
+#pragma unroll
+            for (int k = 0; k < 9; ++k) out_tris[at * 9 + k] = tris[at * 9 + k];
+        if (out_area) out_area[at] = area[at];
+    }
+}
+
+hipError_t launch_copy_triangles(const float* tris, const double* area, const int* ntri_total, int B, int cap, float* out_tris,
+                                 double* out_area, hipStream_t s) {
+    const int need = (cap + 255) / 256, blocks = need < 1024 ? need : 1024;
+    hipLaunchKernelGGL(copy_triangles_kernel, dim3(blocks, B), dim3(256), 0, s, tris, area, ntri_total, cap, out_tris, out_area);
     return hipGetLastError();
 }
 

@@ -35,6 +35,8 @@ class DefenseArgs:
                                     # does not change results)
     printing: bool = False          # optimize_points(..., printing=True) of the reference (opt_defense.py:229-236)
     precision: str = "f32"          # extension (opt-in): "bf16x6" (f32-equivalent) / "bf16x3" (reduced) decoder layers, ifd_opt_params.precision
+    max_triangles: int = 400000     # extension (remesh_point_cloud): triangle slots per cloud of a mesh pass (memory knob, 44 bytes each;
+                                    # does not change results: a cloud whose surface has more is meshed again with room for all of them)
 
 
 def _prepare_unit(r: Restorer, xb: torch.Tensor, args: DefenseArgs, base: int, total: int):
@@ -204,10 +206,23 @@ def remesh_point_cloud(r, pc, args: "DefenseArgs", cloud_index_base: int = 0, re
         prep = r.prepare(xb, keep, n_sel=args.input_npoint, n_opt=n, padding_scale=args.padding_scale,
                          init_sigma=args.init_sigma, seed=args.seed, cloud_index_base=cloud_index_base + lo)
         c = r.encode_inputs(prep["sel"], prep["t_per_cloud"])
-        res = r.mesh_sample(c, n_sample=n, seed=args.seed, cloud_index_base=cloud_index_base + lo,
-                            precision=getattr(args, "precision", "f32") or "f32")
+        cap = int(getattr(args, "max_triangles", 400000))
+        precision = getattr(args, "precision", "f32") or "f32"
+        res = r.mesh_sample(c, n_sample=n, seed=args.seed, cloud_index_base=cloud_index_base + lo, precision=precision,
+                            max_triangles=cap)
         pts = res["points"]
-        empty = (res["n_triangles"] == 0).nonzero().flatten().tolist()
+        ntri = res["n_triangles"].cpu()
+        for b in (ntri > cap).nonzero().flatten().tolist():
+            # n_triangles is the uncapped total, the samples cover the first `cap` triangles only (the lowest-x slabs of the
+            # surface): mesh this cloud again with room for all of them - same seed, same global index, so the same samples as a
+            # pass whose capacity sufficed from the start
+            again = r.mesh_sample(c[b:b + 1], n_sample=n, seed=args.seed, cloud_index_base=cloud_index_base + lo + b,
+                                  precision=precision, max_triangles=int(ntri[b]))
+            if int(again["n_triangles"][0]) != int(ntri[b]):
+                raise RuntimeError("remesh_point_cloud: cloud %d has %d triangles in one pass and %d in the next"
+                                   % (cloud_index_base + lo + b, int(ntri[b]), int(again["n_triangles"][0])))
+            pts[b] = again["points"][0]
+        empty = (ntri == 0).nonzero().flatten().tolist()
         for b in empty:                                          # rare: reconstruction failed
             ori = xb[b][keep[b].bool()] if keep is not None else xb[b]
             fb = torch.zeros(n, 3, device=r.device)

@@ -413,7 +413,9 @@ class OnetRestorer(Restorer):
                     want_grid: bool = False, want_triangles: bool = False, threshold: Optional[float] = None, precision=None):
         """reconstruct_mesh + trimesh.sample.sample_surface (ONet/remesh_defense.py:128-157) for a batch of latent codes:
         c [B,512] -> dict(points [B,n_sample,3] (not normalised), n_triangles [B] int32, optionally grid [B,P,P,P] and
-        triangles [B,max_triangles,9]).  ``precision``: arithmetic of the grid evaluation's decoder layers (ifd_mesh_params.precision,
+        triangles [B,max_triangles,9]).  ``n_triangles`` is the uncapped total of a cloud's surface: the valid rows of
+        ``triangles`` are the first min(n_triangles, max_triangles), and where n_triangles > max_triangles the samples cover
+        those triangles only (the lowest-x slabs) - call again with a larger ``max_triangles``.  ``precision``: arithmetic of the grid evaluation's decoder layers (ifd_mesh_params.precision,
         "f32" default / "bf16x6" / "bf16x3")."""
         c = self._cond(c)
         B = c.shape[0]
@@ -434,6 +436,49 @@ class OnetRestorer(Restorer):
         if want_triangles:
             out["triangles"] = tris
         return out
+
+    def mesh_from_grid(self, grid: torch.Tensor, iso: float = 0.0, padding: float = 0.1, max_triangles: int = 400000,
+                       n_sample: int = 1024, seed: int = 0, cloud_index_base: int = 0, points: Optional[torch.Tensor] = None,
+                       triangles: Optional[torch.Tensor] = None, cum_area: Optional[torch.Tensor] = None):
+        """Validation seam (ifd_mesh_from_grid): marching cubes + surface sampling of caller-supplied grids [B,P,P,P] at the
+        iso-value ``iso`` (used as is), by the production code.  Returns dict(points, n_triangles); ``points`` [B,n_sample,3],
+        ``triangles`` [B,max_triangles,9] float32 and ``cum_area`` [B,max_triangles] float64 may be passed in - the library writes
+        the valid rows only - and are returned under their names."""
+        grid = _f32(grid, self.device)
+        if grid.dim() != 4 or not (grid.shape[1] == grid.shape[2] == grid.shape[3]):
+            raise IfdError("mesh_from_grid takes grids [B,P,P,P]")
+        B, P = int(grid.shape[0]), int(grid.shape[1])
+        pts = torch.zeros(B, n_sample, 3, device=self.device, dtype=torch.float32) if points is None else points
+        ntri = torch.zeros(B, device=self.device, dtype=torch.int32)
+        for t, shape, dt in ((pts, (B, n_sample, 3), torch.float32), (triangles, (B, max_triangles, 9), torch.float32),
+                             (cum_area, (B, max_triangles), torch.float64)):
+            if t is not None and (tuple(t.shape) != shape or t.dtype != dt or t.device != self.device or not t.is_contiguous()):
+                raise IfdError("mesh_from_grid: an output tensor must be contiguous %s %s on %s" % (shape, dt, self.device))
+        with torch.cuda.device(self.device):
+            self._check(self.lib.ifd_mesh_from_grid(self.ctx, grid.data_ptr(), B, P, float(iso), float(padding), int(max_triangles),
+                                                    int(n_sample), int(seed), int(cloud_index_base), pts.data_ptr(), ntri.data_ptr(),
+                                                    self._ptr(triangles), self._ptr(cum_area), self._stream()))
+        out = {"points": pts, "n_triangles": ntri}
+        if triangles is not None:
+            out["triangles"] = triangles
+        if cum_area is not None:
+            out["cum_area"] = cum_area
+        return out
+
+    def mise_from_field(self, field: torch.Tensor, resolution0: int, upsampling_steps: int, threshold: float = 0.0):
+        """Validation seam (ifd_mise_from_field): the production MISE loop on caller-supplied fields [B,P,P,P]
+        (P = (resolution0 << upsampling_steps) + 1) in place of the decoder, ``threshold`` compared as is.  Returns
+        dict(grid [B,P,P,P] (to_dense), rounds, points): the rounds of the call and the grid points it evaluated."""
+        field = _f32(field, self.device)
+        if field.dim() != 4 or not (field.shape[1] == field.shape[2] == field.shape[3]):
+            raise IfdError("mise_from_field takes fields [B,P,P,P]")
+        B, P = int(field.shape[0]), int(field.shape[1])
+        grid = torch.empty_like(field)
+        with torch.cuda.device(self.device):
+            self._check(self.lib.ifd_mise_from_field(self.ctx, field.data_ptr(), B, P, int(resolution0), int(upsampling_steps),
+                                                     float(threshold), grid.data_ptr(), self._stream()))
+        cnt = self.counters()
+        return {"grid": grid, "rounds": cnt["mesh_rounds"], "points": cnt["mesh_points"]}
 
     def encode_points(self, *a, **k):
         raise IfdError("encode_points / unet belong to the ConvONet model")

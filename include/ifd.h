@@ -247,7 +247,7 @@ int ifd_optimize(ifd_ctx* ctx, const float* planes, float* p, int B, int K,
  * radii + re-passes for overflowed balls), [3] shader-clock cycles cloud 0 spent in the optimiser kernel
  * (effective clock = cycles / kernel time), [4] wave-steps that had to evaluate the back ring of the lists,
  * [5] wave-steps with a near-tie settled by an exact per-point query (and the loss-reporting step), [6] wave-steps with individual
- * list refreshes, [7] lists built in total; of the most recent ifd_onet_mesh_sample: [8] grid points evaluated,
+ * list refreshes, [7] lists built in total; of the most recent ifd_onet_mesh_sample / ifd_mise_from_field: [8] grid points evaluated,
  * [9] MISE rounds (summed over chunks).  n <= IFD_N_COUNTERS (slots beyond it exist only for the wave trace of
  * diagnostic -DIFD_TRACE builds). */
 #define IFD_N_COUNTERS 16
@@ -324,9 +324,12 @@ int ifd_onet_optimize(ifd_ctx* ctx, const float* c, float* p, int B, int K, cons
  *   c [B,512] -> points [B,n_sample,3] (NOT yet normalised: call ifd_normalize_unit_sphere, remesh_defense.py:262),
  *   n_triangles [B] (device int32; 0 = empty mesh: the cloud's rows of `points` are left untouched and the caller
  *   applies the reference's fallback, remesh_defense.py:160-170).
+ *   n_triangles[b] is the UNCAPPED total of the cloud's surface.  The triangle buffer holds, and the samples are drawn from, the first
+ *   min(n_triangles[b], max_triangles) triangles only - in cube order, i.e. the lowest-x slabs: a caller that finds
+ *   n_triangles[b] > max_triangles must call again with a capacity of at least n_triangles[b] (pipeline.remesh_point_cloud does).
  * Optional outputs for inspection / tests: grid [B,P,P,P] float32 (P = resolution0 * 2^upsampling_steps + 1; MISE's
  * to_dense()), triangles [B,max_triangles,9] float32 (three xyz vertices per triangle in the decoder's frame; the
- * first n_triangles[b] rows are valid).  The surface samples use the counter-based generator of ifd_prepare, keyed by
+ * first min(n_triangles[b], max_triangles) rows are valid, the rows behind them are left untouched).  The surface samples use the counter-based generator of ifd_prepare, keyed by
  * (seed, cloud_index_base + b, sample index) - the reference's are unseeded numpy draws.
  * The MISE loop is driven from the device (queue lengths, the split of a round's decoder passes over the CUs, finished clouds);
  * the host enqueues round r before it has looked at what round r - 1 queued and waits on one event per round only to learn when
@@ -337,7 +340,7 @@ typedef struct ifd_mesh_params {
     int32_t upsampling_steps;  /* cfg generation.upsampling_steps (2); 0..2, resolution0 << steps <= 128 */
     int32_t n_sample;          /* args.sample_npoint (1024) */
     int32_t max_triangles;     /* capacity per cloud of the triangle buffer (e.g. 400000) */
-    float padding;             /* Generator3D padding (0.1): box_size = 1 + padding */
+    float padding;             /* Generator3D padding (0.1): box_size = 1 + padding, formed in float32 */
     double threshold;          /* cfg test.threshold (0.2), as a probability; the iso-value is its logit */
     uint64_t seed;
     int64_t cloud_index_base;
@@ -356,6 +359,28 @@ int ifd_onet_mesh_sample(ifd_ctx* ctx, const float* c, int B, const ifd_mesh_par
  * (scripts/probe_mc_table.py; fixture tests/golden/mc_table_ref.npz; it is the classic Lorensen-Cline table in libmcubes'
  * numbering).  Nothing is generated at start-up.  Corner / edge numbering as in libmcubes (marchingcubes.h:44-64). */
 int ifd_mc_table(int8_t* tri, uint8_t* ntri);
+
+/* Validation seams (no reference counterpart; they add no entry to the versioned drop-in surface above, IFD_ABI_VERSION stays): the two
+ * halves of ifd_onet_mesh_sample on CALLER-SUPPLIED arrays, so that tests can drive the kernels of csrc/mesh.hip with inputs no decoder
+ * produces - all 256 cube configurations, values exactly on the threshold, activation cascades, tiny triangle capacities.  Both run
+ * the production code (the same workspace layout, round loop, launches and kernels as ifd_onet_mesh_sample), on an ONet context.
+ *
+ * ifd_mesh_from_grid: marching cubes + surface sampling of dense grids.  grid [B,P,P,P] float32 (device), 2 <= P <= 129; iso is the
+ * iso-value in the grid's own units (a logit in production), used as is; padding, max_triangles (>= 1), n_sample, seed,
+ * cloud_index_base, points [B,n_sample,3] and n_triangles [B] as in ifd_mesh_params / ifd_onet_mesh_sample (n_triangles uncapped;
+ * empty meshes leave their rows of points untouched).  Optional: triangles [B,max_triangles,9] float32, cum_area [B,max_triangles]
+ * float64 (the running sum of the triangle areas the sampler searches); of both the first min(n_triangles[b], max_triangles) rows
+ * are written and nothing else. */
+int ifd_mesh_from_grid(ifd_ctx* ctx, const float* grid, int B, int P, double iso, float padding, int max_triangles, int n_sample,
+                       uint64_t seed, int64_t cloud_index_base, float* points, int32_t* n_triangles, float* triangles,
+                       double* cum_area, void* stream);
+
+/* ifd_mise_from_field: the MISE loop of ifd_onet_mesh_sample with the decoder evaluation of a round replaced by a look-up in a dense
+ * field: field [B,P,P,P] float32 (device), P == (resolution0 << upsampling_steps) + 1 (resolution0 >= 2, 0 <= upsampling_steps <= 2,
+ * P <= 129); threshold is compared as is (a logit in production).  grid [B,P,P,P] float32 = MISE's to_dense().  The rounds and the
+ * points evaluated are the context's tallies, ifd_get_counters [9] and [8].  Waits on one event per round like ifd_onet_mesh_sample. */
+int ifd_mise_from_field(ifd_ctx* ctx, const float* field, int B, int P, int resolution0, int upsampling_steps, double threshold,
+                        float* grid, void* stream);
 
 #ifdef __cplusplus
 }

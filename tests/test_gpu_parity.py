@@ -1906,16 +1906,7 @@ def test_onet_decode_seam_in_split_precision(onet, og, golden, mode):
         assert got.shape == (2, K) and _rel(got, og["dec_logits"][:, :K]) < tl, K
 
 
-def _philox4x32_10(k0, k1, c0, c1, c2, c3):
-    """Philox-4x32-10 (Salmon et al. 2011) on uint32 numpy arrays - the generator of prep.hip / mesh.hip."""
-    k0, k1 = np.uint64(k0), np.uint64(k1)
-    c = [np.asarray(x, np.uint64) for x in np.broadcast_arrays(c0, c1, c2, c3)]
-    M = np.uint64(0xffffffff)
-    for _ in range(10):
-        p0, p1 = np.uint64(0xD2511F53) * c[0], np.uint64(0xCD9E8D57) * c[2]
-        c = [((p1 >> np.uint64(32)) ^ c[1] ^ k0) & M, p1 & M, ((p0 >> np.uint64(32)) ^ c[3] ^ k1) & M, p0 & M]
-        k0, k1 = (k0 + np.uint64(0x9E3779B9)) & M, (k1 + np.uint64(0xBB67AE85)) & M
-    return c
+from mesh_plain import _philox4x32_10  # noqa: E402  (the generator of prep.hip / mesh.hip, restated in tests/mesh_plain.py)
 
 
 def test_onet_mesh_sampler_is_the_documented_algorithm_on_its_own_uniforms(onet, og):
