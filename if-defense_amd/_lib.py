@@ -202,6 +202,35 @@ KNN_SIGNATURES = {
                                  C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
 }
 
+# include/ifd_add.h (the CW point-adding attack on the PointNet victim), versioned on its own
+ADD_ABI_VERSION = 1
+ADD_CHAMFER, ADD_HAUSDORFF = 0, 1
+ADD_MAX_ADD, ADD_MAX_ORI = 1024, 2048
+
+
+class IfdAddDiag(C.Structure):
+    _fields_ = [("dist_grad", C.c_void_p), ("nn_ori", C.c_void_p), ("far", C.c_void_p)]
+
+
+class IfdAddParams(C.Structure):
+    _fields_ = [("struct_size", C.c_int32), ("kind", C.c_int32), ("loss_kind", C.c_int32), ("binary_step", C.c_int32),
+                ("num_iter", C.c_int32), ("num_add", C.c_int32), ("kappa", C.c_float), ("scale", C.c_float), ("attack_lr", C.c_float),
+                ("init_weight", C.c_float), ("max_weight", C.c_float)]
+
+
+ADD_SIGNATURES = {
+    "ifd_add_abi_version": (C.c_int, []),
+    "ifd_add_select": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+                                 C.c_void_p]),
+    "ifd_add_critical_points": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_float,
+                                          C.c_void_p, C.c_void_p, C.c_void_p]),
+    "ifd_add_step": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(IfdCwState), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                               C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(IfdAddDiag), C.c_int, C.c_float, C.c_float, C.c_int, C.c_int,
+                               C.c_int, C.c_void_p]),
+    "ifd_add_attack": (C.c_int, [C.c_void_p, C.POINTER(IfdAddParams), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int,
+                                 C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+}
+
 _lib = None
 
 
@@ -217,7 +246,7 @@ def load() -> C.CDLL:
     import torch  # noqa: F401  (loads libamdhip64.so.7 first; libifd binds to the same runtime)
     lib = C.CDLL(LIB_PATH, mode=C.RTLD_GLOBAL)
     for name, (res, args) in list(SIGNATURES.items()) + list(DUP_SIGNATURES.items()) + list(CLS_SIGNATURES.items()) + \
-            list(ATK_SIGNATURES.items()) + list(CW_SIGNATURES.items()) + list(KNN_SIGNATURES.items()):
+            list(ATK_SIGNATURES.items()) + list(CW_SIGNATURES.items()) + list(KNN_SIGNATURES.items()) + list(ADD_SIGNATURES.items()):
         fn = getattr(lib, name)          # AttributeError if the library lacks a declared symbol
         fn.restype, fn.argtypes = res, args
     if lib.ifd_abi_version() != ABI_VERSION:
@@ -232,5 +261,7 @@ def load() -> C.CDLL:
         raise ImportError("libifd.so CW ABI %d != binding CW ABI %d; rebuild" % (lib.ifd_cw_abi_version(), CW_ABI_VERSION))
     if lib.ifd_knn_abi_version() != KNN_ABI_VERSION:
         raise ImportError("libifd.so KNN ABI %d != binding KNN ABI %d; rebuild" % (lib.ifd_knn_abi_version(), KNN_ABI_VERSION))
+    if lib.ifd_add_abi_version() != ADD_ABI_VERSION:
+        raise ImportError("libifd.so ADD ABI %d != binding ADD ABI %d; rebuild" % (lib.ifd_add_abi_version(), ADD_ABI_VERSION))
     _lib = lib
     return lib

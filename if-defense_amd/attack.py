@@ -18,7 +18,8 @@ reproduce how its ``+ 1e-9`` terms weigh against the gradient's norm.  The defau
 
 ``CWPerturb`` is the reference's Carlini-Wagner point-perturbation attack (baselines/attack/CW/Perturb.py, include/ifd_cw.h), on the
 same two loop forms; it is not one of ``ATTACKS``, which names the FGM family for the fgm_attack CLI.  ``CWKNN`` is the reference's
-kNN attack (baselines/attack/CW/kNN.py, include/ifd_knn.h), likewise.
+kNN attack (baselines/attack/CW/kNN.py, include/ifd_knn.h), likewise, and ``CWAdd`` its point-adding attack
+(baselines/attack/CW/Add.py, include/ifd_add.h), whose clouds come back larger than they went in.
 """
 from __future__ import annotations
 
@@ -266,3 +267,93 @@ class CWKNN:
         success_num = int(ok.sum())
         print('Successfully attack {}/{}'.format(success_num, B))
         return adv.cpu().numpy(), success_num
+
+
+class CWAdd:
+    """CW attack by adding points (Add.py CWAdd): ``num_add`` points start on the cloud's critical points - the rows with the largest
+    gradient of cross_entropy(logits, target) - and are optimised by ``binary_step`` search steps on the weight of the set distance,
+    ``num_iter`` Adam iterations each, while the victim sees the original cloud with the added points behind it.  ``model`` is a
+    ``runtime.Classifier`` (anything with its ``input_grad``, ``add_critical_points``, ``cw_state``, ``add_step``, ``cw_adjust`` and
+    ``add_attack``), ``adv_func`` the loss by name ("logits": LogitsAdvLoss(kappa), or "cross_entropy"), ``dist_func`` "chamfer"
+    (ChamferDist('adv2ori')) or "hausdorff" (HausdorffDist('adv2ori')).  ``attack(data [B,K,3], target [B])`` returns the reference's
+    triple (o_bestdist [B], clouds [B,K+num_add,3]: the originals, then the best added points, or the last forwarded ones where the
+    search never succeeded; success_num) as numpy arrays.  ``verbose=True`` drives the loop from the host, one ``input_grad`` and
+    one ``add_step`` an iteration, with the reference's progress lines every num_iter // 5 iterations (the two losses are the batch
+    means of the previous iteration, zero at iteration 0, as in the reference) - its wall-clock lines ("total time: ...") are left
+    out; ``verbose=False`` is one library call and prints the last line only.  Both give the same bits.
+
+    Every search step starts from critical points + randn * 1e-7, drawn here once per search step from a seeded HOST
+    torch.Generator: agreement with a reference run in distribution only.  Where torch.topk leaves the order among equal scores
+    open, the library's selection takes the lowest index first (include/ifd_add.h).  ``ref_batch``: the batch the reference's losses
+    are a mean over (scale = 1 / ref_batch); the default is the batch passed to ``attack``."""
+
+    def __init__(self, model, adv_func="logits", dist_func="chamfer", attack_lr=1e-2, init_weight=5e3, max_weight=4e4, binary_step=10,
+                 num_iter=500, num_add=512, kappa=0., seed=1, ref_batch=None, verbose=True):
+        self.dist_func = str(dist_func).lower()
+        if self.dist_func not in ("chamfer", "hausdorff"):
+            raise ValueError("dist_func must be chamfer or hausdorff")
+        if int(binary_step) < 1 or int(num_iter) < 1:
+            raise ValueError("binary_step and num_iter must be at least 1")
+        if not 1 <= int(num_add) <= 1024:
+            raise ValueError("num_add must be in [1, 1024]")
+        self.model, self.adv_func, self.kappa = model, adv_func, float(kappa)
+        self.attack_lr, self.init_weight, self.max_weight = float(attack_lr), float(init_weight), float(max_weight)
+        self.binary_step, self.num_iter, self.num_add = int(binary_step), int(num_iter), int(num_add)
+        self.ref_batch, self.verbose = ref_batch, verbose
+        self.generator = torch.Generator().manual_seed(int(seed))
+
+    def noise(self, data: torch.Tensor) -> torch.Tensor:
+        """[binary_step,B,num_add,3]: the start noise, one draw per search step."""
+        shape = (int(data.shape[0]), self.num_add, 3)
+        return torch.stack([torch.randn(shape, generator=self.generator) * 1e-7 for _ in range(self.binary_step)])
+
+    def _scale(self, B):
+        return 1.0 / float(self.ref_batch or B)
+
+    def _loop(self, data, target, noise):
+        """Add.py:85-220 from the host: the kernels of ifd_add_attack on the same numbers."""
+        net = self.model
+        dev = net.device
+        B, K, A = int(data.shape[0]), int(data.shape[1]), self.num_add
+        ori = data.to(dev).contiguous()
+        tgt = target.to(dev)
+        cri = net.add_critical_points(ori, tgt, A, self._scale(B))
+        state = net.cw_state(B, A, self.init_weight, self.max_weight)
+        cat = torch.cat([ori, cri], dim=1).contiguous()
+        last = torch.empty_like(cri)
+        every = max(self.num_iter // 5, 1)
+        for step in range(self.binary_step):
+            cat[:, K:] = cri + noise[step].to(dev)
+            info = None
+            for it in range(self.num_iter):
+                grad, aux = net.input_grad(cat, tgt, self.adv_func, self.kappa, self._scale(B), want_aux=True)
+                if it % every == 0:
+                    adv_loss, dist_loss = (0., 0.) if info is None else (float(info[:, 0].mean()), float(info[:, 1].mean()))
+                    print('Step {}, iteration {}, success {}/{}\nadv_loss: {:.4f}, dist_loss: {:.4f}'.format(
+                        step, it, int((aux["pred"].long() == tgt.long()).sum()), B, adv_loss, dist_loss))
+                final = step == self.binary_step - 1 and it == self.num_iter - 1
+                info = net.add_step(self.dist_func, state, grad, aux["pred"], tgt, cat, A, it + 1, self.attack_lr, self._scale(B),
+                                    loss=aux["loss"], last_input=last if final else None, want_info=it % every == every - 1).get("info")
+            net.cw_adjust(state, tgt)
+        ok = state["lower"] > 0
+        added = torch.where(ok[:, None, None], state["o_bestattack"], last)
+        return torch.cat([ori, added], dim=1), state["o_bestdist"], ok
+
+    def attack(self, data, target):
+        data = torch.as_tensor(np.asarray(data) if not torch.is_tensor(data) else data).float().cpu()
+        target = torch.as_tensor(np.asarray(target) if not torch.is_tensor(target) else target).long().cpu()
+        if data.dim() != 3 or int(data.shape[2]) != 3:
+            raise ValueError("data must be [B,K,3]")
+        if not self.num_add <= int(data.shape[1]) <= 2048:
+            raise ValueError("clouds must have between num_add and 2048 points")
+        B = int(data.shape[0])
+        noise = self.noise(data)
+        if self.verbose:
+            adv, dist, ok = self._loop(data, target, noise)
+        else:
+            adv, dist, ok = self.model.add_attack(self.dist_func, data, target, self.num_add, noise, self.adv_func, self.kappa,
+                                                  self._scale(B), self.attack_lr, self.init_weight, self.max_weight, self.binary_step,
+                                                  self.num_iter)
+        success_num = int(ok.sum())
+        print('Successfully attack {}/{}'.format(success_num, B))
+        return dist.cpu().numpy().astype(np.float64), adv.cpu().numpy(), success_num

@@ -37,6 +37,7 @@ def _deps():
     hdr.append(os.path.join(os.path.dirname(HERE), "include", "ifd_atk.h"))
     hdr.append(os.path.join(os.path.dirname(HERE), "include", "ifd_cw.h"))
     hdr.append(os.path.join(os.path.dirname(HERE), "include", "ifd_knn.h"))
+    hdr.append(os.path.join(os.path.dirname(HERE), "include", "ifd_add.h"))
     return hdr
 
 

@@ -10,6 +10,7 @@
 #include "../../include/ifd_atk.h"
 #include "../../include/ifd_cw.h"
 #include "../../include/ifd_knn.h"
+#include "../../include/ifd_add.h"
 
 #include <hip/hip_runtime.h>
 
@@ -2143,6 +2144,183 @@ int ifd_knn_attack(ifd_ctx* ctx, const ifd_knn_params* params, const float* pc_i
     if (int rc = cls_forward_impl(ctx, pc_out, n_points, B, stride, logits, &aux, stream, false, state)) return rc;
     e = launch_atk_success(pred, target, B, success, s);
     if (e != hipSuccess) return fail(ctx, IFD_ERR_HIP, "ifd_knn_attack: success", e);
+    return IFD_OK;
+}
+
+}  // extern "C"
+
+// ---- the CW point-adding attack (include/ifd_add.h) --------------------------------------------------------------------
+static_assert(IFD_ADD_MAX_ADD == ifd::ADD_MAX_ADD && IFD_ADD_MAX_ORI == ifd::ADD_MAX_ORI, "the header's limits are the kernel's");
+static_assert(IFD_ADD_CHAMFER == ifd::ADD_CHAMFER && IFD_ADD_HAUSDORFF == ifd::ADD_HAUSDORFF, "the header's kinds are the kernel's");
+
+namespace {
+
+bool add_kind_ok(int k) { return k == IFD_ADD_CHAMFER || k == IFD_ADD_HAUSDORFF; }
+
+// the blocking check of the point-adding calls: n_points in [lo, hi], targets in range.  Uses the first 8 bytes of the workspace.
+int add_check(ifd_ctx* ctx, const char* who, const int32_t* n_points, const int32_t* target, int B, int lo, int hi, hipStream_t s) {
+    int32_t bad[2] = {0, 0};
+    hipError_t e = launch_add_check(n_points, target, B, lo, hi, ctx->cls_classes, static_cast<int32_t*>(ctx->ws), s);
+    if (e == hipSuccess) e = hipMemcpyAsync(bad, ctx->ws, sizeof(bad), hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    if (e != hipSuccess) return fail(ctx, IFD_ERR_HIP, (std::string(who) + ": checking n_points and target").c_str(), e);
+    if (bad[0] != 0)
+        return fail(ctx, IFD_ERR_ARG, (std::string(who) + ": " + std::to_string(bad[0]) + " cloud(s) with n_points outside [" +
+                                       std::to_string(lo) + ", " + std::to_string(hi) + "]").c_str());
+    if (bad[1] != 0)
+        return fail(ctx, IFD_ERR_ARG, (std::string(who) + ": " + std::to_string(bad[1]) + " target(s) outside [0, 40)").c_str());
+    return IFD_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int ifd_add_abi_version(void) { return IFD_ADD_ABI_VERSION; }
+
+int ifd_add_select(ifd_ctx* ctx, const float* grad, const float* pc, const int32_t* n_points, int B, int stride, int num_add, float* cri,
+                   int32_t* idx, void* stream) {
+    if (!ctx) return IFD_ERR_ARG;
+    if (int rc = atk_context_ok(ctx, "ifd_add_select")) return rc;
+    if (!grad || !pc || !cri || B < 1) return fail(ctx, IFD_ERR_ARG, "ifd_add_select: bad argument (grad, pc, cri; B >= 1)");
+    if (num_add < 1 || num_add > IFD_ADD_MAX_ADD) return fail(ctx, IFD_ERR_ARG, "ifd_add_select: num_add outside [1, 1024]");
+    if (stride < 1 || stride > IFD_CLS_MAX_POINTS) return fail(ctx, IFD_ERR_ARG, "ifd_add_select: stride outside [1, 10000]");
+    if (!n_points && (stride < num_add || stride > IFD_ADD_MAX_ORI))
+        return fail(ctx, IFD_ERR_ARG, "ifd_add_select: without n_points, stride outside [num_add, 2048]");
+    IFD_ON_CTX_DEVICE(ctx);
+    hipError_t e = launch_add_select(grad, pc, n_points, B, stride, num_add, cri, idx, static_cast<hipStream_t>(stream));
+    if (e != hipSuccess) return fail(ctx, IFD_ERR_HIP, "ifd_add_select launch", e);
+    return IFD_OK;
+}
+
+int ifd_add_critical_points(ifd_ctx* ctx, const float* pc, const int32_t* n_points, const int32_t* target, int B, int stride, int num_add,
+                            float scale, float* cri, int32_t* idx, void* stream) {
+    if (!ctx) return IFD_ERR_ARG;
+    if (int rc = atk_context_ok(ctx, "ifd_add_critical_points")) return rc;
+    if (!pc || !target || !cri || B < 1) return fail(ctx, IFD_ERR_ARG, "ifd_add_critical_points: bad argument (pc, target, cri; B >= 1)");
+    if (num_add < 1 || num_add > IFD_ADD_MAX_ADD) return fail(ctx, IFD_ERR_ARG, "ifd_add_critical_points: num_add outside [1, 1024]");
+    if (stride < 1 || stride > IFD_CLS_MAX_POINTS) return fail(ctx, IFD_ERR_ARG, "ifd_add_critical_points: stride outside [1, 10000]");
+    if (!n_points && (stride < num_add || stride > IFD_ADD_MAX_ORI))
+        return fail(ctx, IFD_ERR_ARG, "ifd_add_critical_points: without n_points, stride outside [num_add, 2048]");
+    IFD_ON_CTX_DEVICE(ctx);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const size_t state = ((size_t)B * stride * 12 + 255) / 256 * 256;
+    hipError_t e = ensure_ws(ctx, state + atk_grad_ws_bytes(B, stride));
+    if (e != hipSuccess) return fail(ctx, IFD_ERR_NOMEM, "ifd_add_critical_points: workspace", e);
+    if (int rc = add_check(ctx, "ifd_add_critical_points", n_points, target, B, num_add, std::min(stride, IFD_ADD_MAX_ORI), s)) return rc;
+    float* grad = static_cast<float*>(ctx->ws);
+    if (int rc = input_grad_impl(ctx, state, pc, n_points, B, stride, target, IFD_ATK_LOSS_CE, 0.f, scale, grad, nullptr, s)) return rc;
+    e = launch_add_select(grad, pc, n_points, B, stride, num_add, cri, idx, s);
+    if (e != hipSuccess) return fail(ctx, IFD_ERR_HIP, "ifd_add_critical_points: select", e);
+    return IFD_OK;
+}
+
+int ifd_add_step(ifd_ctx* ctx, int kind, const ifd_cw_state* state, const float* grad, const int32_t* pred, const float* loss,
+                 const int32_t* target, float* cat, const int32_t* n_ori, float* last_input, float* info, const ifd_add_diag* diag, int t,
+                 float lr, float scale, int B, int cat_stride, int num_add, void* stream) {
+    if (!ctx) return IFD_ERR_ARG;
+    if (int rc = atk_context_ok(ctx, "ifd_add_step")) return rc;
+    if (!add_kind_ok(kind)) return fail(ctx, IFD_ERR_ARG, "ifd_add_step: unknown kind");
+    if (!state || !state->m || !state->v || !state->bestdist || !state->bestscore || !state->o_bestdist || !state->o_bestscore ||
+        !state->o_bestattack || !state->weight)
+        return fail(ctx, IFD_ERR_ARG, "ifd_add_step: state missing (m, v, bestdist, bestscore, o_bestdist, o_bestscore, o_bestattack, weight)");
+    if (!grad || !pred || !target || !cat || t < 1 || B < 1)
+        return fail(ctx, IFD_ERR_ARG, "ifd_add_step: bad argument (grad, pred, target, cat; t >= 1, B >= 1)");
+    if (num_add < 1 || num_add > IFD_ADD_MAX_ADD) return fail(ctx, IFD_ERR_ARG, "ifd_add_step: num_add outside [1, 1024]");
+    if (cat_stride > IFD_CLS_MAX_POINTS || cat_stride < 2 * num_add)
+        return fail(ctx, IFD_ERR_ARG, "ifd_add_step: cat_stride outside [2 num_add, 10000]");
+    if (!n_ori && cat_stride - num_add > IFD_ADD_MAX_ORI)
+        return fail(ctx, IFD_ERR_ARG, "ifd_add_step: without n_ori, cat_stride - num_add > 2048 original rows");
+    IFD_ON_CTX_DEVICE(ctx);
+    const AddDiag D = diag ? AddDiag{diag->dist_grad, diag->nn_ori, diag->far} : AddDiag{};
+    hipError_t e = launch_add_step(kind, cw_state(state), grad, pred, loss, target, cat, n_ori, last_input, info, D, t, lr, scale, B,
+                                   cat_stride, num_add, static_cast<hipStream_t>(stream));
+    if (e != hipSuccess) return fail(ctx, IFD_ERR_HIP, "ifd_add_step launch", e);
+    return IFD_OK;
+}
+
+int ifd_add_attack(ifd_ctx* ctx, const ifd_add_params* params, const float* pc_in, const int32_t* n_points, const int32_t* target,
+                   const float* noise, int B, int stride, int out_stride, float* pc_out, float* best_dist, int32_t* success,
+                   double* bounds, void* stream) {
+    if (!ctx) return IFD_ERR_ARG;
+    if (int rc = atk_context_ok(ctx, "ifd_add_attack")) return rc;
+    if (!params || params->struct_size != (int32_t)sizeof(ifd_add_params))
+        return fail(ctx, IFD_ERR_ARG, "ifd_add_attack: params missing or of another struct_size");
+    if (!add_kind_ok(params->kind)) return fail(ctx, IFD_ERR_ARG, "ifd_add_attack: unknown kind");
+    if (!atk_loss_ok(params->loss_kind)) return fail(ctx, IFD_ERR_ARG, "ifd_add_attack: unknown loss_kind");
+    if (params->binary_step < 1) return fail(ctx, IFD_ERR_ARG, "ifd_add_attack: binary_step < 1");
+    if (params->num_iter < 1) return fail(ctx, IFD_ERR_ARG, "ifd_add_attack: num_iter < 1");
+    const int num_add = params->num_add;
+    if (num_add < 1 || num_add > IFD_ADD_MAX_ADD) return fail(ctx, IFD_ERR_ARG, "ifd_add_attack: num_add outside [1, 1024]");
+    if (B < 1) return fail(ctx, IFD_ERR_ARG, "ifd_add_attack: B >= 1 is needed");
+    if (stride < 1 || stride > IFD_CLS_MAX_POINTS) return fail(ctx, IFD_ERR_ARG, "ifd_add_attack: stride outside [1, 10000]");
+    if (out_stride < 1 || out_stride > IFD_CLS_MAX_POINTS) return fail(ctx, IFD_ERR_ARG, "ifd_add_attack: out_stride outside [1, 10000]");
+    if (!pc_in || !target || !pc_out || !best_dist || !success)
+        return fail(ctx, IFD_ERR_ARG, "ifd_add_attack: missing pointer (pc_in, target, pc_out, best_dist, success)");
+    const int hi = std::min(std::min(stride, IFD_ADD_MAX_ORI), out_stride - num_add);
+    if (!n_points && (stride < num_add || stride > hi))
+        return fail(ctx, IFD_ERR_ARG, "ifd_add_attack: without n_points, stride outside [num_add, min(2048, out_stride - num_add)]");
+    {
+        const char *a = reinterpret_cast<const char*>(pc_in), *b = reinterpret_cast<const char*>(pc_out);
+        if (a < b + (size_t)B * out_stride * 12 && b < a + (size_t)B * stride * 12)
+            return fail(ctx, IFD_ERR_ARG, "ifd_add_attack: pc_out overlaps pc_in");
+    }
+    IFD_ON_CTX_DEVICE(ctx);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const int G = std::max(stride, out_stride);
+    const size_t added = (size_t)B * num_add * 12;
+    const size_t state = ((size_t)B * (12 * (size_t)G + 60 * (size_t)num_add + 52) + 255) / 256 * 256;
+    hipError_t e = ensure_ws(ctx, state + atk_grad_ws_bytes(B, G));
+    if (e != hipSuccess) return fail(ctx, IFD_ERR_NOMEM, "ifd_add_attack: workspace", e);
+    if (int rc = add_check(ctx, "ifd_add_attack", n_points, target, B, num_add, hi, s)) return rc;
+    // the loop's own state in front of the workspace of ifd_cls_input_grad: the float64 weights first (alignment)
+    char* p = static_cast<char*>(ctx->ws);
+    auto take = [&](size_t bytes) { char* q = p; p += bytes; return q; };
+    CwState S;
+    S.weight = reinterpret_cast<double*>(take((size_t)B * 8));
+    S.lower = reinterpret_cast<double*>(take((size_t)B * 8));
+    S.upper = reinterpret_cast<double*>(take((size_t)B * 8));
+    S.bestdist = reinterpret_cast<float*>(take((size_t)B * 4));
+    S.bestscore = reinterpret_cast<int32_t*>(take((size_t)B * 4));
+    S.o_bestscore = reinterpret_cast<int32_t*>(take((size_t)B * 4));
+    int32_t* pred = reinterpret_cast<int32_t*>(take((size_t)B * 4));
+    float* loss = reinterpret_cast<float*>(take((size_t)B * 4));
+    int32_t* n_cat = reinterpret_cast<int32_t*>(take((size_t)B * 4));
+    int32_t* n_ori = reinterpret_cast<int32_t*>(take((size_t)B * 4));
+    float* grad = reinterpret_cast<float*>(take((size_t)B * G * 12));
+    float* cri = reinterpret_cast<float*>(take(added));
+    S.m = reinterpret_cast<float*>(take(added));
+    S.v = reinterpret_cast<float*>(take(added));
+    S.o_bestattack = reinterpret_cast<float*>(take(added));
+    float* last = reinterpret_cast<float*>(take(added));
+    S.o_bestdist = best_dist;
+    // the critical points (Add.py:14-42): cross-entropy towards the target, whatever the loop's loss
+    if (int rc = input_grad_impl(ctx, state, pc_in, n_points, B, stride, target, IFD_ATK_LOSS_CE, 0.f, params->scale, grad, nullptr, s))
+        return rc;
+    e = launch_add_select(grad, pc_in, n_points, B, stride, num_add, cri, nullptr, s);
+    if (e == hipSuccess) e = launch_add_begin(pc_in, n_points, B, stride, out_stride, num_add, pc_out, n_ori, n_cat, s);
+    if (e == hipSuccess) e = launch_cw_init(S, B, params->init_weight, params->max_weight, s);
+    if (e == hipSuccess) e = hipMemsetAsync(S.m, 0, 3 * added, s);     // m, v and o_bestattack lie side by side
+    if (e != hipSuccess) return fail(ctx, IFD_ERR_HIP, "ifd_add_attack: start", e);
+    const ifd_atk_out out{nullptr, loss, pred, nullptr, nullptr, nullptr};
+    for (int step = 0; step < params->binary_step; ++step) {
+        e = launch_add_start(cri, noise ? noise + (size_t)step * B * num_add * 3 : nullptr, n_cat, B, out_stride, num_add, pc_out, s);
+        if (e != hipSuccess) return fail(ctx, IFD_ERR_HIP, "ifd_add_attack: search step start", e);
+        for (int it = 0; it < params->num_iter; ++it) {
+            if (int rc = input_grad_impl(ctx, state, pc_out, n_cat, B, out_stride, target, params->loss_kind, params->kappa, params->scale,
+                                         grad, &out, s))
+                return rc;
+            // the reference's input_val is read once, behind its loops: only the last iteration's copy is ever seen
+            const bool final_it = step == params->binary_step - 1 && it == params->num_iter - 1;
+            e = launch_add_step(params->kind, S, grad, pred, loss, target, pc_out, n_ori, final_it ? last : nullptr, nullptr, AddDiag{},
+                                it + 1, params->attack_lr, params->scale, B, out_stride, num_add, s);
+            if (e != hipSuccess) return fail(ctx, IFD_ERR_HIP, "ifd_add_attack: step", e);
+        }
+        e = launch_cw_adjust(S, target, nullptr, B, num_add, s);
+        if (e != hipSuccess) return fail(ctx, IFD_ERR_HIP, "ifd_add_attack: adjust", e);
+    }
+    e = launch_add_finish(S, last, n_cat, B, out_stride, num_add, pc_out, success, bounds, s);
+    if (e != hipSuccess) return fail(ctx, IFD_ERR_HIP, "ifd_add_attack: finish", e);
     return IFD_OK;
 }
 

@@ -306,4 +306,31 @@ hipError_t launch_knn_clip(float* adv, const float* ori, const float* normal, fl
 // bad[0] = clouds with n_points outside [6, stride], bad[1] = targets outside [0, n_classes)
 hipError_t launch_knn_check(const int32_t* n_points, const int32_t* target, int B, int stride, int n_classes, int32_t* bad, hipStream_t s);
 
+// ---- the CW point-adding attack (pointnet_add.hip, include/ifd_add.h) ----
+constexpr int ADD_MAX_ADD = 1024;               // IFD_ADD_MAX_ADD, IFD_ADD_MAX_ORI: the added points and the originals of one cloud
+constexpr int ADD_MAX_ORI = 2048;               // in a workgroup's static LDS
+constexpr int ADD_CHAMFER = 0, ADD_HAUSDORFF = 1;        // IFD_ADD_CHAMFER, IFD_ADD_HAUSDORFF
+struct AddDiag {                                // ifd_add_diag, member for member; every pointer may be null
+    float* dist_grad;                           // [B][num_add][3]
+    int32_t* nn_ori;                            // [B][num_add]
+    int32_t* far;                               // [B]
+};
+// the limits on stride, num_add and (where n_points is null) the counts are the caller's to check
+hipError_t launch_add_select(const float* grad, const float* pc, const int32_t* n_points, int B, int stride, int num_add, float* cri,
+                             int32_t* idx, hipStream_t s);
+// one iteration behind ifd_cls_input_grad on the concatenated cloud, a workgroup a cloud; S has stride num_add
+hipError_t launch_add_step(int kind, const CwState& S, const float* grad, const int32_t* pred, const float* loss, const int32_t* target,
+                           float* cat, const int32_t* n_ori, float* last_input, float* info, const AddDiag& D, int t, float lr, float scale,
+                           int B, int cat_stride, int num_add, hipStream_t s);
+// pc_out[b][0 .. n) = pc_in[b][0 .. n), n_ori[b] = n, n_cat[b] = n + num_add
+hipError_t launch_add_begin(const float* pc_in, const int32_t* n_points, int B, int stride, int out_stride, int num_add, float* pc_out,
+                            int32_t* n_ori, int32_t* n_cat, hipStream_t s);
+hipError_t launch_add_start(const float* cri, const float* noise, const int32_t* n_cat, int B, int out_stride, int num_add, float* pc_out,
+                            hipStream_t s);
+hipError_t launch_add_finish(const CwState& S, const float* last_input, const int32_t* n_cat, int B, int out_stride, int num_add,
+                             float* pc_out, int32_t* success, double* bounds, hipStream_t s);
+// bad[0] = clouds with n_points outside [lo, hi] (n_points may be null), bad[1] = targets outside [0, n_classes)
+hipError_t launch_add_check(const int32_t* n_points, const int32_t* target, int B, int lo, int hi, int n_classes, int32_t* bad,
+                            hipStream_t s);
+
 }  // namespace ifd

@@ -1002,3 +1002,131 @@ class Classifier:
                                                 ptr(extra["noise"]), B, stride, out.data_ptr(), pred.data_ptr(), success.data_ptr(),
                                                 self._stream()))
         return out, pred.long(), success.bool()
+
+    # ---- include/ifd_add.h: the CW point-adding attack (models without feature_transform) ----
+    ADD_KINDS = {"chamfer": _lib.ADD_CHAMFER, "hausdorff": _lib.ADD_HAUSDORFF}
+
+    def _add_kind(self, kind):
+        if kind not in self.ADD_KINDS:
+            raise IfdError("unknown set distance %r (chamfer | hausdorff)" % (kind,))
+        return self.ADD_KINDS[kind]
+
+    def _add_num(self, num_add):
+        num_add = int(num_add)
+        if not 1 <= num_add <= _lib.ADD_MAX_ADD:
+            raise IfdError("num_add must be in [1, %d]" % _lib.ADD_MAX_ADD)
+        return num_add
+
+    def add_select(self, grad, pc, num_add, n_points=None, want_idx: bool = False):
+        """The num_add rows of ``pc`` [B,N,3] with the largest gradient norm (ifd_add_select), in descending order of the score
+        (gx*gx + gy*gy) + gz*gz, the lowest index first among equal scores: -> cri [B,num_add,3], with want_idx also idx
+        [B,num_add] int32.  grad [B,N,3] as ``input_grad`` returns it; num_add <= n <= 2048 rows per cloud."""
+        num_add = self._add_num(num_add)
+        pc, n_points = self._batch(pc, n_points)
+        B, stride = int(pc.shape[0]), int(pc.shape[1])
+        grad = _f32(torch.as_tensor(grad), self.device)
+        if tuple(grad.shape) != (B, stride, 3):
+            raise IfdError("grad must have the clouds' shape [B,N,3]")
+        cri = torch.empty(B, num_add, 3, device=self.device, dtype=torch.float32)
+        idx = torch.empty(B, num_add, device=self.device, dtype=torch.int32) if want_idx else None
+        with torch.cuda.device(self.device):
+            self._check(self.lib.ifd_add_select(self.ctx, grad.data_ptr(), pc.data_ptr(), None if n_points is None else n_points.data_ptr(),
+                                                B, stride, num_add, cri.data_ptr(), None if idx is None else idx.data_ptr(),
+                                                self._stream()))
+        return (cri, idx) if want_idx else cri
+
+    def add_critical_points(self, pc, target, num_add, scale=1., n_points=None, want_idx: bool = False):
+        """Add.py get_critical_points (ifd_add_critical_points): ``add_select`` on the gradient of scale * cross_entropy(logits,
+        target) -> cri [B,num_add,3], with want_idx also idx [B,num_add] int32."""
+        num_add = self._add_num(num_add)
+        pc, n_points = self._batch(pc, n_points)
+        B, stride = int(pc.shape[0]), int(pc.shape[1])
+        target = self._target(target, B)
+        cri = torch.empty(B, num_add, 3, device=self.device, dtype=torch.float32)
+        idx = torch.empty(B, num_add, device=self.device, dtype=torch.int32) if want_idx else None
+        with torch.cuda.device(self.device):
+            self._check(self.lib.ifd_add_critical_points(self.ctx, pc.data_ptr(), None if n_points is None else n_points.data_ptr(),
+                                                         target.data_ptr(), B, stride, num_add, float(scale), cri.data_ptr(),
+                                                         None if idx is None else idx.data_ptr(), self._stream()))
+        return (cri, idx) if want_idx else cri
+
+    def add_step(self, kind, state, grad, pred, target, cat, num_add, t, lr, scale=1., loss=None, last_input=None, n_ori=None,
+                 want_info: bool = False, want=()):
+        """One iteration of the point-adding attack behind ``input_grad`` on the concatenated clouds (ifd_add_step), IN PLACE on
+        the added rows of ``cat`` [B,N,3] (cloud b: n_ori[b] originals, then num_add added rows; n_ori None: N - num_add) and on
+        ``state`` (``cw_state(B, num_add, ...)``).  grad [B,N,3], pred, loss: as ``input_grad`` returned them for ``cat`` with
+        n_points = n_ori + num_add; last_input [B,num_add,3] or None.  Returns a dict: with want_info "info" [B,3] (adversarial loss,
+        dist * weight, dist), and the diagnostics named in ``want``: "dist_grad" [B,num_add,3], "nn_ori" [B,num_add] int32, "far" [B]
+        int32 (clouds outside the limits are left as allocated: NaN / -1)."""
+        kind = self._add_kind(kind)
+        num_add = self._add_num(num_add)
+        if not torch.is_tensor(cat) or cat.dim() != 3:
+            raise IfdError("cat must be a contiguous float32 [B,N,3] device tensor")
+        B, stride = int(cat.shape[0]), int(cat.shape[1])
+        st = self._cw_struct(state, B, num_add)
+        ptrs = [self._cw_cloud(x, B, stride, n) for x, n in ((grad, "grad"), (cat, "cat"))]
+        if grad is None:
+            raise IfdError("grad is missing")
+        li = self._cw_cloud(last_input, B, num_add, "last_input")
+        pred = torch.as_tensor(pred).to(device=self.device, dtype=torch.int32).contiguous()
+        target = self._target(target, B)
+        if tuple(pred.shape) != (B,):
+            raise IfdError("pred must be [B]")
+        if loss is not None:
+            loss = _f32(torch.as_tensor(loss), self.device)
+            if tuple(loss.shape) != (B,):
+                raise IfdError("loss must be [B]")
+        n_ori = self._knn_counts(n_ori, B)
+        shapes = {"dist_grad": ((B, num_add, 3), torch.float32), "nn_ori": ((B, num_add), torch.int32), "far": ((B,), torch.int32)}
+        out = {}
+        for k in want:
+            if k not in shapes:
+                raise IfdError("unknown diagnostic %r (dist_grad | nn_ori | far)" % (k,))
+            shape, dt = shapes[k]
+            out[k] = torch.full(shape, float("nan") if dt == torch.float32 else -1, device=self.device, dtype=dt)
+        ptr = lambda x: None if x is None else x.data_ptr()        # noqa: E731
+        diag = _lib.IfdAddDiag(*[ptr(out.get(k)) for k in ("dist_grad", "nn_ori", "far")])
+        info = torch.empty(B, 3, device=self.device, dtype=torch.float32) if want_info else None
+        with torch.cuda.device(self.device):
+            self._check(self.lib.ifd_add_step(self.ctx, kind, C.byref(st), ptrs[0], pred.data_ptr(), ptr(loss), target.data_ptr(), ptrs[1],
+                                              ptr(n_ori), li, ptr(info), C.byref(diag) if out else None, int(t), float(lr), float(scale),
+                                              B, stride, num_add, self._stream()))
+        if want_info:
+            out["info"] = info
+        return out
+
+    def add_attack(self, kind, pc, target, num_add, noise=None, loss="logits", kappa=0., scale=1., attack_lr=1e-2, init_weight=5e3,
+                   max_weight=4e4, binary_step=10, num_iter=500, n_points=None, out_stride=None, want_bounds: bool = False):
+        """The whole CW point-adding attack on the device (ifd_add_attack): -> (clouds [B,out_stride,3]: each cloud's originals bit
+        for bit, then its num_add added points; best_dist [B] (1e10 where no iteration reached the target); success [B] bool) and
+        with want_bounds also {"weight", "lower", "upper"} [B] float64.  noise: [binary_step,B,num_add,3], the start noise of every
+        search step, or None.  out_stride: rows of the output, default N + num_add (rows beyond a cloud's n + num_add are zero)."""
+        kind = self._add_kind(kind)
+        num_add = self._add_num(num_add)
+        loss_kind = self._loss_kind(loss)
+        pc, n_points = self._batch(pc, n_points)
+        B, stride = int(pc.shape[0]), int(pc.shape[1])
+        if B < 1 or stride < 1:
+            raise IfdError("empty batch")
+        target = self._target(target, B)
+        if noise is not None:
+            noise = _f32(torch.as_tensor(noise), self.device)
+            if tuple(noise.shape) != (int(binary_step), B, num_add, 3):
+                raise IfdError("noise must be [binary_step,B,num_add,3]")
+        out_stride = stride + num_add if out_stride is None else int(out_stride)
+        if out_stride < 1:
+            raise IfdError("out_stride must be positive")
+        out = torch.zeros(B, out_stride, 3, device=self.device, dtype=torch.float32)
+        best = torch.empty(B, device=self.device, dtype=torch.float32)
+        success = torch.empty(B, device=self.device, dtype=torch.int32)
+        bounds = torch.empty(3, B, device=self.device, dtype=torch.float64) if want_bounds else None
+        P = _lib.IfdAddParams(C.sizeof(_lib.IfdAddParams), kind, loss_kind, int(binary_step), int(num_iter), num_add, float(kappa),
+                              float(scale), float(attack_lr), float(init_weight), float(max_weight))
+        with torch.cuda.device(self.device):
+            self._check(self.lib.ifd_add_attack(self.ctx, C.byref(P), pc.data_ptr(), None if n_points is None else n_points.data_ptr(),
+                                                target.data_ptr(), None if noise is None else noise.data_ptr(), B, stride, out_stride,
+                                                out.data_ptr(), best.data_ptr(), success.data_ptr(),
+                                                None if bounds is None else bounds.data_ptr(), self._stream()))
+        if want_bounds:
+            return out, best, success.bool(), {"weight": bounds[0], "lower": bounds[1], "upper": bounds[2]}
+        return out, best, success.bool()
