@@ -19,39 +19,22 @@ from the host; default: the whole loop in one library call).
 """
 from __future__ import annotations
 
-import argparse
 import os
 import sys
 
 import numpy as np
 
-from .inference import DATASETS, default_weight_path, normalize_points_np, str2bool
+from . import attack_cli as C
 
 
 def build_parser():
-    parser = argparse.ArgumentParser(description='Point Cloud Recognition')
-    parser.add_argument('--data_root', type=str, default='data/attack_data.npz')
-    parser.add_argument('--model', type=str, default='pointnet', metavar='N', choices=['pointnet', 'pointnet2', 'dgcnn', 'pointconv'])
-    parser.add_argument('--feature_transform', type=str2bool, default=False)
-    parser.add_argument('--dataset', type=str, default='mn40', metavar='N', choices=list(DATASETS))
-    parser.add_argument('--batch_size', type=int, default=-1, metavar='BS', help="the reference's batch (loss mean); -1: the whole file")
-    parser.add_argument('--num_points', type=int, default=1024)
-    parser.add_argument('--emb_dims', type=int, default=1024, help='unused by PointNet')
-    parser.add_argument('--k', type=int, default=20, help='unused by PointNet')
-    parser.add_argument('--adv_func', type=str, default='logits', choices=['logits', 'cross_entropy'])
-    parser.add_argument('--kappa', type=float, default=0.)
+    parser = C.parser_head()
     parser.add_argument('--dist_func', type=str, default='chamfer', choices=['chamfer', 'hausdorff'])
     parser.add_argument('--num_add', type=int, default=512, metavar='N')
     parser.add_argument('--attack_lr', type=float, default=1e-2)
     parser.add_argument('--binary_step', type=int, default=10, metavar='N')
     parser.add_argument('--num_iter', type=int, default=500, metavar='N')
-    parser.add_argument('--local_rank', default=-1, type=int, help='accepted; only names the output file')
-    parser.add_argument('--model_path', type=str, default='')
-    parser.add_argument('--seed', type=int, default=1)
-    parser.add_argument('--device', type=str, default='cuda:0')
-    parser.add_argument('--out_dir', type=str, default='.')
-    parser.add_argument('--verbose', type=str2bool, default=False)
-    return parser
+    return C.parser_tail(parser)
 
 
 WEIGHTS = {'chamfer': (5e3, 4e4), 'hausdorff': (2e2, 9e2)}        # targeted_add_attack.py:143-150: init_weight, max_weight
@@ -68,12 +51,7 @@ def save_path(out_dir, dataset, num_points, dist_func, model, adv_func, kappa, s
 def main(argv=None, make_classifier=None) -> int:
     from .attack import CWAdd
     args = build_parser().parse_args(argv)
-    if args.model.lower() != 'pointnet':
-        print("add_attack: the {} victim is not built here (only pointnet is)".format(args.model), file=sys.stderr)
-        return 2
-    if args.feature_transform:
-        print("add_attack: input gradients through the feature transform are not built here (--feature_transform false only)",
-              file=sys.stderr)
+    if C.refuse_unbuilt('add_attack', args):
         return 2
     if args.binary_step < 1 or args.num_iter < 1:
         print("add_attack: --binary_step and --num_iter must be at least 1", file=sys.stderr)
@@ -83,36 +61,21 @@ def main(argv=None, make_classifier=None) -> int:
         return 2
     print(args)
     npz = np.load(args.data_root)
-    data = np.stack([normalize_points_np(np.asarray(c, dtype=np.float32)[:args.num_points, :3]) for c in npz['test_pc']])
-    label, target = np.asarray(npz['test_label']).reshape(-1), np.asarray(npz['target_label']).reshape(-1)
-    if make_classifier is None:
-        def make_classifier(model, feature_transform, model_path):
-            from .runtime import Classifier
-            from .weights import load_checkpoint
-            return Classifier(load_checkpoint(model_path, model, feature_transform), model, feature_transform, device=args.device)
-    model_path = args.model_path or default_weight_path(args.dataset, args.model)
-    print('Loading weight {}'.format(model_path))
-    classifier = make_classifier(args.model, False, model_path)
+    data = C.load_points(npz, args.num_points)
+    label, target = C.load_labels(npz)
+    classifier = C.open_classifier(args, make_classifier)
     try:
         init_w, upper_w = WEIGHTS[args.dist_func]
         attacker = CWAdd(classifier, args.adv_func, args.dist_func, attack_lr=args.attack_lr, init_weight=init_w, max_weight=upper_w,
                          binary_step=args.binary_step, num_iter=args.num_iter, num_add=args.num_add, kappa=args.kappa, seed=args.seed,
                          verbose=args.verbose)
-        bs = len(data) if args.batch_size < 1 else args.batch_size
-        adv, num = [], 0
-        for a in range(0, len(data), bs):
-            _, pc, n_ok = attacker.attack(data[a:a + bs], target[a:a + bs].astype(np.int64))
-            adv.append(pc)
-            num += n_ok
+        adv, num = C.run_batches(attacker, data, target, args.batch_size)
     finally:
-        if hasattr(classifier, "close"):
-            classifier.close()
-    adv = np.concatenate(adv, axis=0)
+        C.close_classifier(classifier)
     rate = float(num) / float(len(data))
     d, name = save_path(args.out_dir, args.dataset, args.num_points, args.dist_func, args.model, args.adv_func, args.kappa, rate,
                         0 if args.local_rank < 0 else args.local_rank)
-    os.makedirs(d, exist_ok=True)
-    np.savez(os.path.join(d, name), test_pc=adv.astype(np.float32), test_label=label.astype(np.uint8), target_label=target.astype(np.uint8))
+    C.save_npz(d, name, adv, label, target)
     return 0
 
 

@@ -27,7 +27,41 @@ import numpy as np
 import torch
 
 
-class FGM:
+class _Attack:
+    """What the attack classes share: the seeded host generator, the loss scale, the coercion of attack()'s arguments and the
+    reference's progress and closing lines."""
+
+    STEP_LINES = 'Step {}, iteration {}, success {}/{}\nadv_loss: {:.4f}, dist_loss: {:.4f}'
+
+    def _common(self, seed, ref_batch, verbose):
+        self.ref_batch, self.verbose = ref_batch, verbose
+        self.generator = torch.Generator().manual_seed(int(seed))
+
+    def _scale(self, B):
+        return 1.0 / float(self.ref_batch or B)
+
+    @staticmethod
+    def _tensors(data, target):
+        """(data, target) as CPU float / long tensors."""
+        data = torch.as_tensor(np.asarray(data) if not torch.is_tensor(data) else data).float().cpu()
+        target = torch.as_tensor(np.asarray(target) if not torch.is_tensor(target) else target).long().cpu()
+        return data, target
+
+    @staticmethod
+    def _progress(fmt, a, b, pred, tgt, info, dist_col):
+        """The reference's two lines: fmt filled with (a, b, hits, B, adv_loss, dist_loss), the two losses the batch means of
+        info[:, 0] and info[:, dist_col] of the previous iteration, zero without one."""
+        adv_loss, dist_loss = (0., 0.) if info is None else (float(info[:, 0].mean()), float(info[:, dist_col].mean()))
+        print(fmt.format(a, b, int((pred.long() == tgt.long()).sum()), int(tgt.shape[0]), adv_loss, dist_loss))
+
+    @staticmethod
+    def _finish(ok, B, fmt='Successfully attack {}/{}'):
+        success_num = int(ok.sum())
+        print(fmt.format(success_num, B))
+        return success_num
+
+
+class FGM(_Attack):
     KIND = "fgm"
 
     def __init__(self, model, adv_func="logits", budget=0.08, dist_metric="l2", kappa=0., seed=1, ref_batch=None, verbose=True):
@@ -35,15 +69,11 @@ class FGM:
             raise ValueError("only the l2 constraint of the reference's script is built")
         self.model, self.adv_func, self.kappa = model, adv_func, float(kappa)
         self.budget, self.step_size, self.num_iter, self.mu = float(budget), float(budget), 1, 1.0
-        self.ref_batch, self.verbose = ref_batch, verbose
-        self.generator = torch.Generator().manual_seed(int(seed))
+        self._common(seed, ref_batch, verbose)
 
     def start(self, data: torch.Tensor) -> torch.Tensor:
         """The cloud the loop starts from and clips against (plain FGM: the data themselves)."""
         return data
-
-    def _scale(self, B):
-        return 1.0 / float(self.ref_batch or B)
 
     def _loop(self, pc, target):
         """The reference's loop from the host, one ifd_cls_input_grad and one ifd_fgm_update an iteration: the same kernels as
@@ -62,8 +92,7 @@ class FGM:
         return cur, self.model.predict(cur).to(tgt.device) == tgt
 
     def attack(self, data, target):
-        data = torch.as_tensor(np.asarray(data) if not torch.is_tensor(data) else data).float().cpu()
-        target = torch.as_tensor(np.asarray(target) if not torch.is_tensor(target) else target).long().cpu()
+        data, target = self._tensors(data, target)
         B = int(data.shape[0])
         pc = self.start(data)
         if self.KIND != "fgm" and self.verbose:
@@ -71,11 +100,7 @@ class FGM:
         else:
             adv, ok = self.model.fgm_attack(self.KIND, pc, target, self.budget, self.step_size, self.num_iter, self.mu, self.adv_func,
                                             self.kappa, self._scale(B))
-        success_num = int(ok.sum())
-        if self.KIND == "fgm":
-            print('Successfully attack {}/{}'.format(success_num, B))
-        else:
-            print('Final success: {}/{}'.format(success_num, B))
+        success_num = self._finish(ok, B) if self.KIND == "fgm" else self._finish(ok, B, 'Final success: {}/{}')
         return adv.cpu().numpy(), success_num
 
 
@@ -111,7 +136,7 @@ class PGD(IFGM):
 ATTACKS = {"fgm": FGM, "ifgm": IFGM, "mifgm": MIFGM, "pgd": PGD}
 
 
-class CWPerturb:
+class CWPerturb(_Attack):
     """CW attack by perturbing points (Perturb.py CWPerturb): ``binary_step`` search steps on the weight of the L2 distance term,
     ``num_iter`` Adam iterations each.  ``model`` is a ``runtime.Classifier`` (anything with its ``input_grad``, ``cw_state``,
     ``cw_step``, ``cw_adjust`` and ``cw_perturb_attack``), ``adv_func`` the loss by name ("logits": LogitsAdvLoss(kappa), or
@@ -135,15 +160,11 @@ class CWPerturb:
         self.model, self.adv_func, self.kappa = model, adv_func, float(kappa)
         self.attack_lr, self.init_weight, self.max_weight = float(attack_lr), float(init_weight), float(max_weight)
         self.binary_step, self.num_iter = int(binary_step), int(num_iter)
-        self.ref_batch, self.verbose = ref_batch, verbose
-        self.generator = torch.Generator().manual_seed(int(seed))
+        self._common(seed, ref_batch, verbose)
 
     def noise(self, data: torch.Tensor) -> torch.Tensor:
         """[binary_step,B,K,3]: the start noise, one draw per search step."""
         return torch.stack([torch.randn(data.shape, generator=self.generator) * 1e-7 for _ in range(self.binary_step)])
-
-    def _scale(self, B):
-        return 1.0 / float(self.ref_batch or B)
 
     def _loop(self, data, target, noise):
         """Perturb.py:69-175 from the host: the kernels of ifd_cw_perturb_attack on the same numbers."""
@@ -161,9 +182,7 @@ class CWPerturb:
             for it in range(self.num_iter):
                 grad, aux = net.input_grad(adv, tgt, self.adv_func, self.kappa, self._scale(B), want_aux=True)
                 if it % every == 0:
-                    adv_loss, dist_loss = (0., 0.) if info is None else (float(info[:, 0].mean()), float(info[:, 1].mean()))
-                    print('Step {}, iteration {}, success {}/{}\nadv_loss: {:.4f}, dist_loss: {:.4f}'.format(
-                        step, it, int((aux["pred"].long() == tgt.long()).sum()), B, adv_loss, dist_loss))
+                    self._progress(self.STEP_LINES, step, it, aux["pred"], tgt, info, 1)
                 final = step == self.binary_step - 1 and it == self.num_iter - 1
                 info = net.cw_step(state, grad, aux["pred"], tgt, adv, ori, it + 1, self.attack_lr, self._scale(B), loss=aux["loss"],
                                    last_input=last if final else None, want_info=it % every == every - 1)
@@ -173,8 +192,7 @@ class CWPerturb:
         return out, state["o_bestdist"], ok
 
     def attack(self, data, target):
-        data = torch.as_tensor(np.asarray(data) if not torch.is_tensor(data) else data).float().cpu()
-        target = torch.as_tensor(np.asarray(target) if not torch.is_tensor(target) else target).long().cpu()
+        data, target = self._tensors(data, target)
         B = int(data.shape[0])
         noise = self.noise(data)
         if self.verbose:
@@ -182,12 +200,10 @@ class CWPerturb:
         else:
             adv, dist, ok = self.model.cw_perturb_attack(data, target, noise, self.adv_func, self.kappa, self._scale(B), self.attack_lr,
                                                          self.init_weight, self.max_weight, self.binary_step, self.num_iter)
-        success_num = int(ok.sum())
-        print('Successfully attack {}/{}'.format(success_num, B))
-        return dist.cpu().numpy().astype(np.float64), adv.cpu().numpy(), success_num
+        return dist.cpu().numpy().astype(np.float64), adv.cpu().numpy(), self._finish(ok, B)
 
 
-class CWKNN:
+class CWKNN(_Attack):
     """The kNN attack (kNN.py CWKNN): ``num_iter`` Adam iterations on the adversarial loss plus ChamferkNNDist('adv2ori', 5, 1.05, 5.,
     3.), each followed by ProjectInnerClipLinf(0.1); no binary search, no records.  ``model`` is a ``runtime.Classifier`` (anything
     with its ``input_grad``, ``knn_step``, ``knn_attack`` and ``predict``), ``adv_func`` the loss by name ("logits":
@@ -214,15 +230,11 @@ class CWKNN:
             raise ValueError("num_iter must be at least 1")
         self.model, self.adv_func, self.kappa = model, adv_func, float(kappa)
         self.attack_lr, self.num_iter = float(attack_lr), int(num_iter)
-        self.ref_batch, self.verbose = ref_batch, verbose
-        self.generator = torch.Generator().manual_seed(int(seed))
+        self._common(seed, ref_batch, verbose)
 
     def noise(self, data: torch.Tensor) -> torch.Tensor:
         """[B,K,3]: the start noise, one draw."""
         return torch.randn((int(data.shape[0]), int(data.shape[1]), 3), generator=self.generator) * 1e-7
-
-    def _scale(self, B):
-        return 1.0 / float(self.ref_batch or B)
 
     def _hyper(self):
         return dict(chamfer_weight=self.CHAMFER_WEIGHT, knn_weight=self.KNN_WEIGHT, alpha=self.ALPHA, budget=self.BUDGET)
@@ -242,17 +254,15 @@ class CWKNN:
         for it in range(self.num_iter):
             grad, aux = net.input_grad(adv, tgt, self.adv_func, self.kappa, self._scale(B), want_aux=True)
             if it % every == 0:
-                adv_loss, dist_loss = (0., 0.) if info is None else (float(info[:, 0].mean()), float(info[:, 3].mean()))
-                print('Iteration {}/{}, success {}/{}\nadv_loss: {:.4f}, dist_loss: {:.4f}'.format(
-                    it, self.num_iter, int((aux["pred"].long() == tgt.long()).sum()), B, adv_loss, dist_loss))
+                self._progress('Iteration {}/{}, success {}/{}\nadv_loss: {:.4f}, dist_loss: {:.4f}', it, self.num_iter, aux["pred"], tgt,
+                               info, 3)
             want = ("info",) if it % every == every - 1 else ()
             info = net.knn_step(grad, adv, ori, m, v, it + 1, self.attack_lr, self._scale(B), normal=nrm, loss=aux["loss"], want=want,
                                 **self._hyper()).get("info")
         return adv, net.predict(adv).to(tgt.device) == tgt
 
     def attack(self, data, target):
-        data = torch.as_tensor(np.asarray(data) if not torch.is_tensor(data) else data).float().cpu()
-        target = torch.as_tensor(np.asarray(target) if not torch.is_tensor(target) else target).long().cpu()
+        data, target = self._tensors(data, target)
         if data.dim() != 3 or int(data.shape[2]) not in (3, 6):
             raise ValueError("data must be [B,K,6] (points and normals) or [B,K,3]")
         B = int(data.shape[0])
@@ -264,12 +274,10 @@ class CWKNN:
         else:
             adv, _, ok = self.model.knn_attack(pts, target, normal, noise, self.adv_func, self.kappa, self._scale(B), self.attack_lr,
                                                self.num_iter, **self._hyper())
-        success_num = int(ok.sum())
-        print('Successfully attack {}/{}'.format(success_num, B))
-        return adv.cpu().numpy(), success_num
+        return adv.cpu().numpy(), self._finish(ok, B)
 
 
-class CWAdd:
+class CWAdd(_Attack):
     """CW attack by adding points (Add.py CWAdd): ``num_add`` points start on the cloud's critical points - the rows with the largest
     gradient of cross_entropy(logits, target) - and are optimised by ``binary_step`` search steps on the weight of the set distance,
     ``num_iter`` Adam iterations each, while the victim sees the original cloud with the added points behind it.  ``model`` is a
@@ -299,16 +307,12 @@ class CWAdd:
         self.model, self.adv_func, self.kappa = model, adv_func, float(kappa)
         self.attack_lr, self.init_weight, self.max_weight = float(attack_lr), float(init_weight), float(max_weight)
         self.binary_step, self.num_iter, self.num_add = int(binary_step), int(num_iter), int(num_add)
-        self.ref_batch, self.verbose = ref_batch, verbose
-        self.generator = torch.Generator().manual_seed(int(seed))
+        self._common(seed, ref_batch, verbose)
 
     def noise(self, data: torch.Tensor) -> torch.Tensor:
         """[binary_step,B,num_add,3]: the start noise, one draw per search step."""
         shape = (int(data.shape[0]), self.num_add, 3)
         return torch.stack([torch.randn(shape, generator=self.generator) * 1e-7 for _ in range(self.binary_step)])
-
-    def _scale(self, B):
-        return 1.0 / float(self.ref_batch or B)
 
     def _loop(self, data, target, noise):
         """Add.py:85-220 from the host: the kernels of ifd_add_attack on the same numbers."""
@@ -328,9 +332,7 @@ class CWAdd:
             for it in range(self.num_iter):
                 grad, aux = net.input_grad(cat, tgt, self.adv_func, self.kappa, self._scale(B), want_aux=True)
                 if it % every == 0:
-                    adv_loss, dist_loss = (0., 0.) if info is None else (float(info[:, 0].mean()), float(info[:, 1].mean()))
-                    print('Step {}, iteration {}, success {}/{}\nadv_loss: {:.4f}, dist_loss: {:.4f}'.format(
-                        step, it, int((aux["pred"].long() == tgt.long()).sum()), B, adv_loss, dist_loss))
+                    self._progress(self.STEP_LINES, step, it, aux["pred"], tgt, info, 1)
                 final = step == self.binary_step - 1 and it == self.num_iter - 1
                 info = net.add_step(self.dist_func, state, grad, aux["pred"], tgt, cat, A, it + 1, self.attack_lr, self._scale(B),
                                     loss=aux["loss"], last_input=last if final else None, want_info=it % every == every - 1).get("info")
@@ -340,8 +342,7 @@ class CWAdd:
         return torch.cat([ori, added], dim=1), state["o_bestdist"], ok
 
     def attack(self, data, target):
-        data = torch.as_tensor(np.asarray(data) if not torch.is_tensor(data) else data).float().cpu()
-        target = torch.as_tensor(np.asarray(target) if not torch.is_tensor(target) else target).long().cpu()
+        data, target = self._tensors(data, target)
         if data.dim() != 3 or int(data.shape[2]) != 3:
             raise ValueError("data must be [B,K,3]")
         if not self.num_add <= int(data.shape[1]) <= 2048:
@@ -354,6 +355,4 @@ class CWAdd:
             adv, dist, ok = self.model.add_attack(self.dist_func, data, target, self.num_add, noise, self.adv_func, self.kappa,
                                                   self._scale(B), self.attack_lr, self.init_weight, self.max_weight, self.binary_step,
                                                   self.num_iter)
-        success_num = int(ok.sum())
-        print('Successfully attack {}/{}'.format(success_num, B))
-        return dist.cpu().numpy().astype(np.float64), adv.cpu().numpy(), success_num
+        return dist.cpu().numpy().astype(np.float64), adv.cpu().numpy(), self._finish(ok, B)

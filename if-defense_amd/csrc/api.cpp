@@ -1778,18 +1778,27 @@ int atk_context_ok(ifd_ctx* ctx, const char* who) {
     return IFD_OK;
 }
 
-// the one blocking step of the attack calls: counts and targets live on the device.  Uses the first 8 bytes of the workspace.
-int atk_check(ifd_ctx* ctx, const char* who, const int32_t* n_points, const int32_t* target, int B, int stride, hipStream_t s) {
+// the one blocking step of the attack calls: counts (n_points in [lo, hi], range_text in the message) and targets live on the
+// device.  Uses the first 8 bytes of the workspace.
+int atk_check(ifd_ctx* ctx, const char* who, const int32_t* n_points, const int32_t* target, int B, int lo, int hi,
+              const std::string& range_text, hipStream_t s) {
     int32_t bad[2] = {0, 0};
-    hipError_t e = launch_atk_check(n_points, target, B, stride, ctx->cls_classes, static_cast<int32_t*>(ctx->ws), s);
+    hipError_t e = launch_atk_check(n_points, target, B, lo, hi, ctx->cls_classes, static_cast<int32_t*>(ctx->ws), s);
     if (e == hipSuccess) e = hipMemcpyAsync(bad, ctx->ws, sizeof(bad), hipMemcpyDeviceToHost, s);
     if (e == hipSuccess) e = hipStreamSynchronize(s);
     if (e != hipSuccess) return fail(ctx, IFD_ERR_HIP, (std::string(who) + ": checking n_points and target").c_str(), e);
     if (bad[0] != 0)
-        return fail(ctx, IFD_ERR_ARG, (std::string(who) + ": " + std::to_string(bad[0]) + " cloud(s) with n_points outside [1, stride]").c_str());
+        return fail(ctx, IFD_ERR_ARG, (std::string(who) + ": " + std::to_string(bad[0]) + " cloud(s) with n_points outside " + range_text).c_str());
     if (bad[1] != 0)
         return fail(ctx, IFD_ERR_ARG, (std::string(who) + ": " + std::to_string(bad[1]) + " target(s) outside [0, 40)").c_str());
     return IFD_OK;
+}
+// the numeric range_text of the point-adding calls
+std::string numeric_range(int lo, int hi) { return "[" + std::to_string(lo) + ", " + std::to_string(hi) + "]"; }
+
+bool clouds_overlap(const void* a, size_t bytes_a, const void* b, size_t bytes_b) {
+    const char *p = static_cast<const char*>(a), *q = static_cast<const char*>(b);
+    return p < q + bytes_b && q < p + bytes_a;
 }
 
 int atk_chunk(int B) {
@@ -1852,6 +1861,61 @@ int input_grad_impl(ifd_ctx* ctx, size_t ws_off, const float* pc, const int32_t*
 bool atk_loss_ok(int k) { return k == IFD_ATK_LOSS_LOGITS || k == IFD_ATK_LOSS_CE; }
 bool atk_kind_ok(int k) { return k >= IFD_FGM_FGM && k <= IFD_FGM_PGD; }
 
+// workspace of an attack loop: its own state in front of ifd_cls_input_grad's and, with_forward, of the final forward's
+size_t atk_loop_ws_bytes(int B, int stride, size_t state_bytes, bool with_forward) {
+    const size_t fwd = with_forward ? 256 + cls_bytes_per_cloud(stride, false) * (size_t)atk_chunk(B) : 0;
+    return state_bytes + std::max(atk_grad_ws_bytes(B, stride), fwd);
+}
+
+// the final forward behind the loop's state (the counts were checked before the loop, so it does not block), success = pred == target
+int atk_final_success(ifd_ctx* ctx, const char* who, const float* pc_out, const int32_t* n_points, int B, int stride, float* logits,
+                      int32_t* pred, const int32_t* target, int32_t* success, size_t state_bytes, hipStream_t s) {
+    ifd_cls_aux aux{nullptr, nullptr, nullptr, pred};
+    if (int rc = cls_forward_impl(ctx, pc_out, n_points, B, stride, logits, &aux, s, false, state_bytes)) return rc;
+    hipError_t e = launch_atk_success(pred, target, B, success, s);
+    if (e != hipSuccess) return fail(ctx, IFD_ERR_HIP, (std::string(who) + ": success").c_str(), e);
+    return IFD_OK;
+}
+
+// ---- shared by the two Carlini-Wagner searches (ifd_cw_perturb_attack, ifd_add_attack) ----
+CwState cw_state(const ifd_cw_state* st) {
+    return CwState{st->m, st->v, st->bestdist, st->bestscore, st->o_bestdist, st->o_bestscore, st->o_bestattack, st->weight, st->lower, st->upper};
+}
+
+// what a step call needs of the caller's state; need_bounds: lower and upper as well (the adjust call) instead of the moments and records
+bool cw_state_ok(const ifd_cw_state* st, bool need_bounds) {
+    if (!st || !st->bestdist || !st->bestscore || !st->o_bestdist || !st->weight) return false;
+    return need_bounds ? st->lower && st->upper : st->m && st->v && st->o_bestscore && st->o_bestattack;
+}
+
+// the common front of the two loops' state in the workspace: the float64 weights first (alignment), then the [B] records, pred and loss
+template <class Take>
+void cw_carve_front(Take& take, int B, CwState& S, int32_t*& pred, float*& loss) {
+    S.weight = reinterpret_cast<double*>(take((size_t)B * 8));
+    S.lower = reinterpret_cast<double*>(take((size_t)B * 8));
+    S.upper = reinterpret_cast<double*>(take((size_t)B * 8));
+    S.bestdist = reinterpret_cast<float*>(take((size_t)B * 4));
+    S.bestscore = reinterpret_cast<int32_t*>(take((size_t)B * 4));
+    S.o_bestscore = reinterpret_cast<int32_t*>(take((size_t)B * 4));
+    pred = reinterpret_cast<int32_t*>(take((size_t)B * 4));
+    loss = reinterpret_cast<float*>(take((size_t)B * 4));
+}
+
+// the binary search on the weight around the Adam iterations; the callbacks return a status, the first non-zero one ends the search
+template <class Start, class Iterate, class Adjust>
+int cw_search(int binary_step, int num_iter, Start start, Iterate iterate, Adjust adjust) {
+    for (int step = 0; step < binary_step; ++step) {
+        if (int rc = start(step)) return rc;
+        for (int it = 0; it < num_iter; ++it) {
+            // the reference's input_val is read once, behind its loops: only the last iteration's copy is ever seen
+            const bool final_it = step == binary_step - 1 && it == num_iter - 1;
+            if (int rc = iterate(step, it, final_it)) return rc;
+        }
+        if (int rc = adjust(step)) return rc;
+    }
+    return IFD_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1869,7 +1933,7 @@ int ifd_cls_input_grad(ifd_ctx* ctx, const float* pc, const int32_t* n_points, i
     hipStream_t s = static_cast<hipStream_t>(stream);
     hipError_t e = ensure_ws(ctx, atk_grad_ws_bytes(B, stride));
     if (e != hipSuccess) return fail(ctx, IFD_ERR_NOMEM, "ifd_cls_input_grad: workspace", e);
-    if (int rc = atk_check(ctx, "ifd_cls_input_grad", n_points, target, B, stride, s)) return rc;
+    if (int rc = atk_check(ctx, "ifd_cls_input_grad", n_points, target, B, 1, stride, "[1, stride]", s)) return rc;
     return input_grad_impl(ctx, 0, pc, n_points, B, stride, target, loss_kind, kappa, scale, grad, out, s);
 }
 
@@ -1901,10 +1965,9 @@ int ifd_fgm_attack(ifd_ctx* ctx, const ifd_fgm_params* params, const float* pc_i
     IFD_ON_CTX_DEVICE(ctx);
     hipStream_t s = static_cast<hipStream_t>(stream);
     const size_t cloud = (size_t)stride * 12, state = (((size_t)B * (2 * cloud + 160 + 4)) + 255) / 256 * 256;
-    const size_t fwd = 256 + cls_bytes_per_cloud(stride, false) * (size_t)atk_chunk(B);
-    hipError_t e = ensure_ws(ctx, state + std::max(atk_grad_ws_bytes(B, stride), fwd));
+    hipError_t e = ensure_ws(ctx, atk_loop_ws_bytes(B, stride, state, true));
     if (e != hipSuccess) return fail(ctx, IFD_ERR_NOMEM, "ifd_fgm_attack: workspace", e);
-    if (int rc = atk_check(ctx, "ifd_fgm_attack", n_points, target, B, stride, s)) return rc;
+    if (int rc = atk_check(ctx, "ifd_fgm_attack", n_points, target, B, 1, stride, "[1, stride]", s)) return rc;
     // the loop's own state in front of the workspace of the calls it makes
     char* base = static_cast<char*>(ctx->ws);
     float* grad = reinterpret_cast<float*>(base);
@@ -1922,25 +1985,12 @@ int ifd_fgm_attack(ifd_ctx* ctx, const ifd_fgm_params* params, const float* pc_i
         e = launch_fgm_update(params->kind, grad, pc_out, pc_in, mom, params->step_size, params->budget, params->mu, n_points, B, stride, s);
         if (e != hipSuccess) return fail(ctx, IFD_ERR_HIP, "ifd_fgm_attack: update", e);
     }
-    // the final forward behind the loop's state; the counts were checked above, so it does not block
-    ifd_cls_aux aux{nullptr, nullptr, nullptr, pred};
-    if (int rc = cls_forward_impl(ctx, pc_out, n_points, B, stride, logits, &aux, stream, false, state)) return rc;
-    e = launch_atk_success(pred, target, B, success, s);
-    if (e != hipSuccess) return fail(ctx, IFD_ERR_HIP, "ifd_fgm_attack: success", e);
-    return IFD_OK;
+    return atk_final_success(ctx, "ifd_fgm_attack", pc_out, n_points, B, stride, logits, pred, target, success, state, s);
 }
 
 }  // extern "C"
 
 // ---- the CW point-perturbation attack (include/ifd_cw.h) --------------------------------------------------------------
-namespace {
-
-CwState cw_state(const ifd_cw_state* st) {
-    return CwState{st->m, st->v, st->bestdist, st->bestscore, st->o_bestdist, st->o_bestscore, st->o_bestattack, st->weight, st->lower, st->upper};
-}
-
-}  // namespace
-
 extern "C" {
 
 int ifd_cw_abi_version(void) { return IFD_CW_ABI_VERSION; }
@@ -1950,8 +2000,7 @@ int ifd_cw_step(ifd_ctx* ctx, const ifd_cw_state* state, const float* grad, cons
                 int stride, void* stream) {
     if (!ctx) return IFD_ERR_ARG;
     if (int rc = atk_context_ok(ctx, "ifd_cw_step")) return rc;
-    if (!state || !state->m || !state->v || !state->bestdist || !state->bestscore || !state->o_bestdist || !state->o_bestscore ||
-        !state->o_bestattack || !state->weight)
+    if (!cw_state_ok(state, false))
         return fail(ctx, IFD_ERR_ARG, "ifd_cw_step: state missing (m, v, bestdist, bestscore, o_bestdist, o_bestscore, o_bestattack, weight)");
     if (!grad || !pred || !target || !adv || !ori || t < 1 || B < 1 || stride < 1 || stride > IFD_CLS_MAX_POINTS)
         return fail(ctx, IFD_ERR_ARG, "ifd_cw_step: bad argument (grad, pred, target, adv, ori; t >= 1, B >= 1, 1 <= stride <= 10000)");
@@ -1965,7 +2014,7 @@ int ifd_cw_step(ifd_ctx* ctx, const ifd_cw_state* state, const float* grad, cons
 int ifd_cw_adjust(ifd_ctx* ctx, const ifd_cw_state* state, const int32_t* target, const int32_t* n_points, int B, int stride, void* stream) {
     if (!ctx) return IFD_ERR_ARG;
     if (int rc = atk_context_ok(ctx, "ifd_cw_adjust")) return rc;
-    if (!state || !state->bestdist || !state->bestscore || !state->o_bestdist || !state->weight || !state->lower || !state->upper)
+    if (!cw_state_ok(state, true))
         return fail(ctx, IFD_ERR_ARG, "ifd_cw_adjust: state missing (bestdist, bestscore, o_bestdist, weight, lower, upper)");
     if (!target || B < 1 || stride < 1 || stride > IFD_CLS_MAX_POINTS)
         return fail(ctx, IFD_ERR_ARG, "ifd_cw_adjust: bad argument (target; B >= 1, 1 <= stride <= 10000)");
@@ -1990,28 +2039,20 @@ int ifd_cw_perturb_attack(ifd_ctx* ctx, const ifd_cw_params* params, const float
     if (!pc_in || !target || !pc_out || !best_dist || !success)
         return fail(ctx, IFD_ERR_ARG, "ifd_cw_perturb_attack: missing pointer (pc_in, target, pc_out, best_dist, success)");
     const size_t cloud = (size_t)stride * 12, all = (size_t)B * cloud;
-    {
-        const char *a = reinterpret_cast<const char*>(pc_in), *b = reinterpret_cast<const char*>(pc_out);
-        if (a < b + all && b < a + all) return fail(ctx, IFD_ERR_ARG, "ifd_cw_perturb_attack: pc_out overlaps pc_in");
-    }
+    if (clouds_overlap(pc_in, all, pc_out, all)) return fail(ctx, IFD_ERR_ARG, "ifd_cw_perturb_attack: pc_out overlaps pc_in");
     IFD_ON_CTX_DEVICE(ctx);
     hipStream_t s = static_cast<hipStream_t>(stream);
     const size_t state = ((size_t)B * (5 * cloud + 64) + 255) / 256 * 256;
-    hipError_t e = ensure_ws(ctx, state + atk_grad_ws_bytes(B, stride));
+    hipError_t e = ensure_ws(ctx, atk_loop_ws_bytes(B, stride, state, false));
     if (e != hipSuccess) return fail(ctx, IFD_ERR_NOMEM, "ifd_cw_perturb_attack: workspace", e);
-    if (int rc = atk_check(ctx, "ifd_cw_perturb_attack", n_points, target, B, stride, s)) return rc;
+    if (int rc = atk_check(ctx, "ifd_cw_perturb_attack", n_points, target, B, 1, stride, "[1, stride]", s)) return rc;
     // the loop's own state in front of the workspace of ifd_cls_input_grad: the float64 weights first (alignment)
     char* p = static_cast<char*>(ctx->ws);
     auto take = [&](size_t bytes) { char* q = p; p += bytes; return q; };
     CwState S;
-    S.weight = reinterpret_cast<double*>(take((size_t)B * 8));
-    S.lower = reinterpret_cast<double*>(take((size_t)B * 8));
-    S.upper = reinterpret_cast<double*>(take((size_t)B * 8));
-    S.bestdist = reinterpret_cast<float*>(take((size_t)B * 4));
-    S.bestscore = reinterpret_cast<int32_t*>(take((size_t)B * 4));
-    S.o_bestscore = reinterpret_cast<int32_t*>(take((size_t)B * 4));
-    int32_t* pred = reinterpret_cast<int32_t*>(take((size_t)B * 4));
-    float* loss = reinterpret_cast<float*>(take((size_t)B * 4));
+    int32_t* pred;
+    float* loss;
+    cw_carve_front(take, B, S, pred, loss);
     float* grad = reinterpret_cast<float*>(take(all));
     float* adv = reinterpret_cast<float*>(take(all));
     S.m = reinterpret_cast<float*>(take(all));
@@ -2023,22 +2064,25 @@ int ifd_cw_perturb_attack(ifd_ctx* ctx, const ifd_cw_params* params, const float
     if (e == hipSuccess) e = hipMemsetAsync(S.m, 0, 2 * all, s);       // m and v lie side by side
     if (e != hipSuccess) return fail(ctx, IFD_ERR_HIP, "ifd_cw_perturb_attack: start", e);
     const ifd_atk_out out{nullptr, loss, pred, nullptr, nullptr, nullptr};
-    for (int step = 0; step < params->binary_step; ++step) {
-        e = launch_cw_start(pc_in, noise ? noise + (size_t)step * B * stride * 3 : nullptr, adv, n_points, B, stride, s);
-        if (e != hipSuccess) return fail(ctx, IFD_ERR_HIP, "ifd_cw_perturb_attack: search step start", e);
-        for (int it = 0; it < params->num_iter; ++it) {
+    if (int rc = cw_search(
+        params->binary_step, params->num_iter,
+        [&](int step) {
+            hipError_t e = launch_cw_start(pc_in, noise ? noise + (size_t)step * B * stride * 3 : nullptr, adv, n_points, B, stride, s);
+            return e == hipSuccess ? IFD_OK : fail(ctx, IFD_ERR_HIP, "ifd_cw_perturb_attack: search step start", e);
+        },
+        [&](int, int it, bool final_it) {
             if (int rc = input_grad_impl(ctx, state, adv, n_points, B, stride, target, params->loss_kind, params->kappa, params->scale, grad,
                                          &out, s))
                 return rc;
-            // the reference's input_val is read once, behind its loops: only the last iteration's copy is ever seen
-            const bool final_it = step == params->binary_step - 1 && it == params->num_iter - 1;
-            e = launch_cw_step(S, grad, pred, loss, target, adv, pc_in, final_it ? last : nullptr, nullptr, it + 1, params->attack_lr,
-                               params->scale, n_points, B, stride, s);
-            if (e != hipSuccess) return fail(ctx, IFD_ERR_HIP, "ifd_cw_perturb_attack: step", e);
-        }
-        e = launch_cw_adjust(S, target, n_points, B, stride, s);
-        if (e != hipSuccess) return fail(ctx, IFD_ERR_HIP, "ifd_cw_perturb_attack: adjust", e);
-    }
+            hipError_t e = launch_cw_step(S, grad, pred, loss, target, adv, pc_in, final_it ? last : nullptr, nullptr, it + 1,
+                                          params->attack_lr, params->scale, n_points, B, stride, s);
+            return e == hipSuccess ? IFD_OK : fail(ctx, IFD_ERR_HIP, "ifd_cw_perturb_attack: step", e);
+        },
+        [&](int) {
+            hipError_t e = launch_cw_adjust(S, target, n_points, B, stride, s);
+            return e == hipSuccess ? IFD_OK : fail(ctx, IFD_ERR_HIP, "ifd_cw_perturb_attack: adjust", e);
+        }))
+        return rc;
     e = launch_cw_finish(S, last, pc_out, success, bounds, n_points, B, stride, s);
     if (e != hipSuccess) return fail(ctx, IFD_ERR_HIP, "ifd_cw_perturb_attack: finish", e);
     return IFD_OK;
@@ -2098,27 +2142,14 @@ int ifd_knn_attack(ifd_ctx* ctx, const ifd_knn_params* params, const float* pc_i
     if (!pc_in || !target || !pc_out || !pred || !success)
         return fail(ctx, IFD_ERR_ARG, "ifd_knn_attack: missing pointer (pc_in, target, pc_out, pred, success)");
     const size_t cloud = (size_t)stride * 12, all = (size_t)B * cloud;
-    {
-        const char *a = reinterpret_cast<const char*>(pc_in), *b = reinterpret_cast<const char*>(pc_out);
-        if (a < b + all && b < a + all) return fail(ctx, IFD_ERR_ARG, "ifd_knn_attack: pc_out overlaps pc_in");
-    }
+    if (clouds_overlap(pc_in, all, pc_out, all)) return fail(ctx, IFD_ERR_ARG, "ifd_knn_attack: pc_out overlaps pc_in");
     IFD_ON_CTX_DEVICE(ctx);
     hipStream_t s = static_cast<hipStream_t>(stream);
     const size_t state = ((size_t)B * (3 * cloud + 160 + 8) + 255) / 256 * 256;
-    const size_t fwd = 256 + cls_bytes_per_cloud(stride, false) * (size_t)atk_chunk(B);
-    hipError_t e = ensure_ws(ctx, state + std::max(atk_grad_ws_bytes(B, stride), fwd));
+    hipError_t e = ensure_ws(ctx, atk_loop_ws_bytes(B, stride, state, true));
     if (e != hipSuccess) return fail(ctx, IFD_ERR_NOMEM, "ifd_knn_attack: workspace", e);
-    {   // the one blocking step: counts (a cloud below 6 points has no five neighbours) and targets
-        int32_t bad[2] = {0, 0};
-        e = launch_knn_check(n_points, target, B, stride, ctx->cls_classes, static_cast<int32_t*>(ctx->ws), s);
-        if (e == hipSuccess) e = hipMemcpyAsync(bad, ctx->ws, sizeof(bad), hipMemcpyDeviceToHost, s);
-        if (e == hipSuccess) e = hipStreamSynchronize(s);
-        if (e != hipSuccess) return fail(ctx, IFD_ERR_HIP, "ifd_knn_attack: checking n_points and target", e);
-        if (bad[0] != 0)
-            return fail(ctx, IFD_ERR_ARG, ("ifd_knn_attack: " + std::to_string(bad[0]) + " cloud(s) with n_points outside [6, stride]").c_str());
-        if (bad[1] != 0)
-            return fail(ctx, IFD_ERR_ARG, ("ifd_knn_attack: " + std::to_string(bad[1]) + " target(s) outside [0, 40)").c_str());
-    }
+    // a cloud below 6 points has no five neighbours
+    if (int rc = atk_check(ctx, "ifd_knn_attack", n_points, target, B, IFD_KNN_MIN_POINTS, stride, "[6, stride]", s)) return rc;
     // the loop's own state in front of the workspace of the calls it makes; adv is pc_out itself
     char* p = static_cast<char*>(ctx->ws);
     auto take = [&](size_t bytes) { char* q = p; p += bytes; return q; };
@@ -2139,12 +2170,7 @@ int ifd_knn_attack(ifd_ctx* ctx, const ifd_knn_params* params, const float* pc_i
                             params->budget, it + 1, params->attack_lr, params->scale, n_points, B, stride, s);
         if (e != hipSuccess) return fail(ctx, IFD_ERR_HIP, "ifd_knn_attack: step", e);
     }
-    // the final forward behind the loop's state; the counts were checked above, so it does not block
-    ifd_cls_aux aux{nullptr, nullptr, nullptr, pred};
-    if (int rc = cls_forward_impl(ctx, pc_out, n_points, B, stride, logits, &aux, stream, false, state)) return rc;
-    e = launch_atk_success(pred, target, B, success, s);
-    if (e != hipSuccess) return fail(ctx, IFD_ERR_HIP, "ifd_knn_attack: success", e);
-    return IFD_OK;
+    return atk_final_success(ctx, "ifd_knn_attack", pc_out, n_points, B, stride, logits, pred, target, success, state, s);
 }
 
 }  // extern "C"
@@ -2156,21 +2182,6 @@ static_assert(IFD_ADD_CHAMFER == ifd::ADD_CHAMFER && IFD_ADD_HAUSDORFF == ifd::A
 namespace {
 
 bool add_kind_ok(int k) { return k == IFD_ADD_CHAMFER || k == IFD_ADD_HAUSDORFF; }
-
-// the blocking check of the point-adding calls: n_points in [lo, hi], targets in range.  Uses the first 8 bytes of the workspace.
-int add_check(ifd_ctx* ctx, const char* who, const int32_t* n_points, const int32_t* target, int B, int lo, int hi, hipStream_t s) {
-    int32_t bad[2] = {0, 0};
-    hipError_t e = launch_add_check(n_points, target, B, lo, hi, ctx->cls_classes, static_cast<int32_t*>(ctx->ws), s);
-    if (e == hipSuccess) e = hipMemcpyAsync(bad, ctx->ws, sizeof(bad), hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
-    if (e != hipSuccess) return fail(ctx, IFD_ERR_HIP, (std::string(who) + ": checking n_points and target").c_str(), e);
-    if (bad[0] != 0)
-        return fail(ctx, IFD_ERR_ARG, (std::string(who) + ": " + std::to_string(bad[0]) + " cloud(s) with n_points outside [" +
-                                       std::to_string(lo) + ", " + std::to_string(hi) + "]").c_str());
-    if (bad[1] != 0)
-        return fail(ctx, IFD_ERR_ARG, (std::string(who) + ": " + std::to_string(bad[1]) + " target(s) outside [0, 40)").c_str());
-    return IFD_OK;
-}
 
 }  // namespace
 
@@ -2207,7 +2218,8 @@ int ifd_add_critical_points(ifd_ctx* ctx, const float* pc, const int32_t* n_poin
     const size_t state = ((size_t)B * stride * 12 + 255) / 256 * 256;
     hipError_t e = ensure_ws(ctx, state + atk_grad_ws_bytes(B, stride));
     if (e != hipSuccess) return fail(ctx, IFD_ERR_NOMEM, "ifd_add_critical_points: workspace", e);
-    if (int rc = add_check(ctx, "ifd_add_critical_points", n_points, target, B, num_add, std::min(stride, IFD_ADD_MAX_ORI), s)) return rc;
+    const int hi = std::min(stride, IFD_ADD_MAX_ORI);
+    if (int rc = atk_check(ctx, "ifd_add_critical_points", n_points, target, B, num_add, hi, numeric_range(num_add, hi), s)) return rc;
     float* grad = static_cast<float*>(ctx->ws);
     if (int rc = input_grad_impl(ctx, state, pc, n_points, B, stride, target, IFD_ATK_LOSS_CE, 0.f, scale, grad, nullptr, s)) return rc;
     e = launch_add_select(grad, pc, n_points, B, stride, num_add, cri, idx, s);
@@ -2221,8 +2233,7 @@ int ifd_add_step(ifd_ctx* ctx, int kind, const ifd_cw_state* state, const float*
     if (!ctx) return IFD_ERR_ARG;
     if (int rc = atk_context_ok(ctx, "ifd_add_step")) return rc;
     if (!add_kind_ok(kind)) return fail(ctx, IFD_ERR_ARG, "ifd_add_step: unknown kind");
-    if (!state || !state->m || !state->v || !state->bestdist || !state->bestscore || !state->o_bestdist || !state->o_bestscore ||
-        !state->o_bestattack || !state->weight)
+    if (!cw_state_ok(state, false))
         return fail(ctx, IFD_ERR_ARG, "ifd_add_step: state missing (m, v, bestdist, bestscore, o_bestdist, o_bestscore, o_bestattack, weight)");
     if (!grad || !pred || !target || !cat || t < 1 || B < 1)
         return fail(ctx, IFD_ERR_ARG, "ifd_add_step: bad argument (grad, pred, target, cat; t >= 1, B >= 1)");
@@ -2260,31 +2271,23 @@ int ifd_add_attack(ifd_ctx* ctx, const ifd_add_params* params, const float* pc_i
     const int hi = std::min(std::min(stride, IFD_ADD_MAX_ORI), out_stride - num_add);
     if (!n_points && (stride < num_add || stride > hi))
         return fail(ctx, IFD_ERR_ARG, "ifd_add_attack: without n_points, stride outside [num_add, min(2048, out_stride - num_add)]");
-    {
-        const char *a = reinterpret_cast<const char*>(pc_in), *b = reinterpret_cast<const char*>(pc_out);
-        if (a < b + (size_t)B * out_stride * 12 && b < a + (size_t)B * stride * 12)
-            return fail(ctx, IFD_ERR_ARG, "ifd_add_attack: pc_out overlaps pc_in");
-    }
+    if (clouds_overlap(pc_in, (size_t)B * stride * 12, pc_out, (size_t)B * out_stride * 12))
+        return fail(ctx, IFD_ERR_ARG, "ifd_add_attack: pc_out overlaps pc_in");
     IFD_ON_CTX_DEVICE(ctx);
     hipStream_t s = static_cast<hipStream_t>(stream);
     const int G = std::max(stride, out_stride);
     const size_t added = (size_t)B * num_add * 12;
     const size_t state = ((size_t)B * (12 * (size_t)G + 60 * (size_t)num_add + 52) + 255) / 256 * 256;
-    hipError_t e = ensure_ws(ctx, state + atk_grad_ws_bytes(B, G));
+    hipError_t e = ensure_ws(ctx, atk_loop_ws_bytes(B, G, state, false));
     if (e != hipSuccess) return fail(ctx, IFD_ERR_NOMEM, "ifd_add_attack: workspace", e);
-    if (int rc = add_check(ctx, "ifd_add_attack", n_points, target, B, num_add, hi, s)) return rc;
+    if (int rc = atk_check(ctx, "ifd_add_attack", n_points, target, B, num_add, hi, numeric_range(num_add, hi), s)) return rc;
     // the loop's own state in front of the workspace of ifd_cls_input_grad: the float64 weights first (alignment)
     char* p = static_cast<char*>(ctx->ws);
     auto take = [&](size_t bytes) { char* q = p; p += bytes; return q; };
     CwState S;
-    S.weight = reinterpret_cast<double*>(take((size_t)B * 8));
-    S.lower = reinterpret_cast<double*>(take((size_t)B * 8));
-    S.upper = reinterpret_cast<double*>(take((size_t)B * 8));
-    S.bestdist = reinterpret_cast<float*>(take((size_t)B * 4));
-    S.bestscore = reinterpret_cast<int32_t*>(take((size_t)B * 4));
-    S.o_bestscore = reinterpret_cast<int32_t*>(take((size_t)B * 4));
-    int32_t* pred = reinterpret_cast<int32_t*>(take((size_t)B * 4));
-    float* loss = reinterpret_cast<float*>(take((size_t)B * 4));
+    int32_t* pred;
+    float* loss;
+    cw_carve_front(take, B, S, pred, loss);
     int32_t* n_cat = reinterpret_cast<int32_t*>(take((size_t)B * 4));
     int32_t* n_ori = reinterpret_cast<int32_t*>(take((size_t)B * 4));
     float* grad = reinterpret_cast<float*>(take((size_t)B * G * 12));
@@ -2303,22 +2306,26 @@ int ifd_add_attack(ifd_ctx* ctx, const ifd_add_params* params, const float* pc_i
     if (e == hipSuccess) e = hipMemsetAsync(S.m, 0, 3 * added, s);     // m, v and o_bestattack lie side by side
     if (e != hipSuccess) return fail(ctx, IFD_ERR_HIP, "ifd_add_attack: start", e);
     const ifd_atk_out out{nullptr, loss, pred, nullptr, nullptr, nullptr};
-    for (int step = 0; step < params->binary_step; ++step) {
-        e = launch_add_start(cri, noise ? noise + (size_t)step * B * num_add * 3 : nullptr, n_cat, B, out_stride, num_add, pc_out, s);
-        if (e != hipSuccess) return fail(ctx, IFD_ERR_HIP, "ifd_add_attack: search step start", e);
-        for (int it = 0; it < params->num_iter; ++it) {
+    if (int rc = cw_search(
+        params->binary_step, params->num_iter,
+        [&](int step) {
+            hipError_t e = launch_add_start(cri, noise ? noise + (size_t)step * B * num_add * 3 : nullptr, n_cat, B, out_stride, num_add,
+                                            pc_out, s);
+            return e == hipSuccess ? IFD_OK : fail(ctx, IFD_ERR_HIP, "ifd_add_attack: search step start", e);
+        },
+        [&](int, int it, bool final_it) {
             if (int rc = input_grad_impl(ctx, state, pc_out, n_cat, B, out_stride, target, params->loss_kind, params->kappa, params->scale,
                                          grad, &out, s))
                 return rc;
-            // the reference's input_val is read once, behind its loops: only the last iteration's copy is ever seen
-            const bool final_it = step == params->binary_step - 1 && it == params->num_iter - 1;
-            e = launch_add_step(params->kind, S, grad, pred, loss, target, pc_out, n_ori, final_it ? last : nullptr, nullptr, AddDiag{},
-                                it + 1, params->attack_lr, params->scale, B, out_stride, num_add, s);
-            if (e != hipSuccess) return fail(ctx, IFD_ERR_HIP, "ifd_add_attack: step", e);
-        }
-        e = launch_cw_adjust(S, target, nullptr, B, num_add, s);
-        if (e != hipSuccess) return fail(ctx, IFD_ERR_HIP, "ifd_add_attack: adjust", e);
-    }
+            hipError_t e = launch_add_step(params->kind, S, grad, pred, loss, target, pc_out, n_ori, final_it ? last : nullptr, nullptr,
+                                           AddDiag{}, it + 1, params->attack_lr, params->scale, B, out_stride, num_add, s);
+            return e == hipSuccess ? IFD_OK : fail(ctx, IFD_ERR_HIP, "ifd_add_attack: step", e);
+        },
+        [&](int) {
+            hipError_t e = launch_cw_adjust(S, target, nullptr, B, num_add, s);
+            return e == hipSuccess ? IFD_OK : fail(ctx, IFD_ERR_HIP, "ifd_add_attack: adjust", e);
+        }))
+        return rc;
     e = launch_add_finish(S, last, n_cat, B, out_stride, num_add, pc_out, success, bounds, s);
     if (e != hipSuccess) return fail(ctx, IFD_ERR_HIP, "ifd_add_attack: finish", e);
     return IFD_OK;

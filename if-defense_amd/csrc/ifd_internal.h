@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <cmath>
 #include "ifd_device.h"
 
 namespace ifd {
@@ -259,8 +260,10 @@ struct ClsGradWs {                              // per-chunk scratch of ifd_cls_
 };
 hipError_t launch_cls_win(const float* img, const ClsImage& I, const float* pc, const int32_t* n_points, int B, int stride,
                           const ClsGradWs& w, int n_classes, hipStream_t s);
-// bad[0] = clouds with n_points outside [1, stride] (n_points may be null), bad[1] = targets outside [0, n_classes)
-hipError_t launch_atk_check(const int32_t* n_points, const int32_t* target, int B, int stride, int n_classes, int32_t* bad, hipStream_t s);
+// the one check of every attack call: bad[0] = clouds with n_points outside [lo, hi] (n_points may be null), bad[1] = targets
+// outside [0, n_classes)
+hipError_t launch_atk_check(const int32_t* n_points, const int32_t* target, int B, int lo, int hi, int n_classes, int32_t* bad,
+                            hipStream_t s);
 // after launch_cls_win: loss, its gradient through the head, the trunk, the STN head and the STN stack -> grad [B][stride][3]
 hipError_t launch_cls_backward(const float* img, const ClsImage& I, const float* gimg, const ClsGradImage& G, const float* pc,
                                const int32_t* n_points, int B, int stride, const int32_t* target, int loss_kind, float kappa, float scale,
@@ -268,6 +271,15 @@ hipError_t launch_cls_backward(const float* img, const ClsImage& I, const float*
 hipError_t launch_fgm_update(int kind, const float* grad, float* pc, const float* ori_pc, float* momentum, float step_size, float budget,
                              float mu, const int32_t* n_points, int B, int stride, hipStream_t s);
 hipError_t launch_atk_success(const int32_t* pred, const int32_t* target, int B, int32_t* success, hipStream_t s);
+
+// torch.optim.Adam's scalars of step t for the attacks' step kernels (atk_device.h atk_adam): step_size = lr / (1 - b1^t),
+// bc2 = sqrt(1 - b2^t), omb1 = 1 - b1, omb2 = 1 - b2.  torch/optim/adam.py: Python doubles, rounded to float where they meet the
+// float tensors (optimize.hip adam_table_kernel)
+struct AdamStep { float step_size, bc2, omb1, omb2; };
+inline AdamStep adam_step_consts(int t, float lr) {
+    return AdamStep{(float)((double)lr / (1.0 - std::pow(0.9, (double)t))), (float)std::sqrt(1.0 - std::pow(0.999, (double)t)),
+                    (float)(1.0 - 0.9), (float)(1.0 - 0.999)};
+}
 
 // ---- the CW point-perturbation attack (pointnet_cw.hip, include/ifd_cw.h) ----
 struct CwState {                                // ifd_cw_state, member for member
@@ -303,8 +315,6 @@ hipError_t launch_knn_step(const float* grad, const float* loss, float* adv, con
                            const int32_t* n_points, int B, int stride, hipStream_t s);
 hipError_t launch_knn_clip(float* adv, const float* ori, const float* normal, float budget, const int32_t* n_points, int B, int stride,
                            hipStream_t s);
-// bad[0] = clouds with n_points outside [6, stride], bad[1] = targets outside [0, n_classes)
-hipError_t launch_knn_check(const int32_t* n_points, const int32_t* target, int B, int stride, int n_classes, int32_t* bad, hipStream_t s);
 
 // ---- the CW point-adding attack (pointnet_add.hip, include/ifd_add.h) ----
 constexpr int ADD_MAX_ADD = 1024;               // IFD_ADD_MAX_ADD, IFD_ADD_MAX_ORI: the added points and the originals of one cloud
@@ -329,8 +339,5 @@ hipError_t launch_add_start(const float* cri, const float* noise, const int32_t*
                             hipStream_t s);
 hipError_t launch_add_finish(const CwState& S, const float* last_input, const int32_t* n_cat, int B, int out_stride, int num_add,
                              float* pc_out, int32_t* success, double* bounds, hipStream_t s);
-// bad[0] = clouds with n_points outside [lo, hi] (n_points may be null), bad[1] = targets outside [0, n_classes)
-hipError_t launch_add_check(const int32_t* n_points, const int32_t* target, int B, int lo, int hi, int n_classes, int32_t* bad,
-                            hipStream_t s);
 
 }  // namespace ifd

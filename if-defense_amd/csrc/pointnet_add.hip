@@ -14,15 +14,9 @@
 //   add_begin_kernel    the originals into the concatenated cloud, n_ori and n_ori + num_add (the counts the victim sees).
 //   add_start_kernel    added rows = critical points + noise of a search step.
 //   add_finish_kernel   the best added rows or, where lower == 0, the last forwarded ones; success = lower > 0.
-//   add_check_kernel    counts and targets of the one blocking check.
-//
-// Adam is cw_step_kernel's arithmetic (pointnet_cw.hip) restated term for term, not shared, as pointnet_knn.hip does: moving it into
-// a header would change how that file is compiled.
 #include <climits>
-#include <cmath>
 
-#include "ifd_device.h"
-#include "ifd_internal.h"
+#include "atk_device.h"
 
 namespace ifd {
 
@@ -32,19 +26,6 @@ constexpr int ADD_PPT = ADD_MAX_ADD / 256;           // added points a thread ow
 constexpr int ADD_SPT = ADD_MAX_ORI / 256;           // scores a thread ranks at the most
 static_assert(ADD_MAX_ADD % 256 == 0 && ADD_MAX_ORI % 256 == 0, "whole rows of 256 threads");
 static_assert((ADD_MAX_ORI + ADD_MAX_ADD) * 12 + 256 * 8 <= 65536, "static LDS of add_step_kernel");
-
-// sum over the workgroup of v, every thread's contribution already summed in its own fixed order: a fixed tree
-__device__ __forceinline__ float add_block_sum(float v, float* sh) {
-    const int tid = threadIdx.x;
-    __syncthreads();
-    sh[tid] = v;
-    __syncthreads();
-    for (int w = 128; w > 0; w >>= 1) {
-        if (tid < w) sh[tid] += sh[tid + w];
-        __syncthreads();
-    }
-    return sh[0];
-}
 
 // the largest (value, index) pair of the workgroup, the lowest index among equal values: a fixed tree; -> sh[0], shi[0]
 __device__ __forceinline__ void add_block_argmax(float v, int i, float* sh, int* shi) {
@@ -111,7 +92,7 @@ __global__ __launch_bounds__(256) void add_select_kernel(const float* __restrict
     }
 }
 
-// step_size = lr / (1 - b1^t), bc2 = sqrt(1 - b2^t), omb1 = 1 - b1, omb2 = 1 - b2: doubles on the host, rounded to float
+// step_size, bc2, omb1, omb2: adam_step_consts (ifd_internal.h)
 __global__ __launch_bounds__(256) void add_step_kernel(int kind, CwState S, const float* __restrict__ grad, const int32_t* __restrict__ pred,
                                                        const float* __restrict__ loss, const int32_t* __restrict__ target,
                                                        float* __restrict__ cat, const int32_t* __restrict__ n_ori,
@@ -159,7 +140,7 @@ __global__ __launch_bounds__(256) void add_step_kernel(int kind, CwState S, cons
         float part = 0.f;
 #pragma unroll
         for (int r = 0; r < ADD_PPT; ++r) part += (r * 256 + tid < num_add) ? best[r] : 0.f;
-        dist = add_block_sum(part, sh) / (float)num_add;
+        dist = atk_block_sum(part, sh) / (float)num_add;
     } else {
         float mv = -INFINITY;
         int mi = INT_MAX;
@@ -209,12 +190,8 @@ __global__ __launch_bounds__(256) void add_step_kernel(int kind, CwState S, cons
             const float d = x - sO[3 * bi[r] + c];
             if (D.dist_grad) D.dist_grad[aoff + i] = active ? coef * d : 0.f;
             const float g = active ? __builtin_fmaf(coef, d, G[i]) : G[i];
-            // cw_step_kernel's Adam (torch/optim/adam.py _single_tensor_adam), term by term
             float mr = M[i], vr = V[i];
-            mr = __builtin_fmaf(g - mr, omb1, mr);
-            vr = __builtin_fmaf(omb2 * g, g, vr * 0.999f);
-            const float denom = sqrtf(vr) / bc2 + 1e-8f;
-            X[i] = __builtin_fmaf(-step_size, mr / denom, x);
+            X[i] = atk_adam(x, g, mr, vr, step_size, bc2, omb1, omb2);
             M[i] = mr;
             V[i] = vr;
         }
@@ -246,22 +223,7 @@ __global__ __launch_bounds__(256) void add_finish_kernel(CwState S, const float*
     const double lo = S.lower[b];
     const float* src = lo == 0.0 ? last_input : S.o_bestattack;
     for (int i = tid; i < num_add * 3; i += 256) pc_out[out + i] = src[a + i];
-    if (tid == 0) {
-        success[b] = lo > 0.0 ? 1 : 0;
-        if (bounds) {
-            bounds[b] = S.weight[b];
-            bounds[(size_t)B + b] = lo;
-            bounds[2 * (size_t)B + b] = S.upper[b];
-        }
-    }
-}
-
-__global__ __launch_bounds__(256) void add_check_kernel(const int32_t* __restrict__ n_points, const int32_t* __restrict__ target, int B,
-                                                        int lo, int hi, int n_classes, int32_t* __restrict__ bad) {
-    const int b = blockIdx.x * 256 + threadIdx.x;
-    if (b >= B) return;
-    if (n_points && (n_points[b] < lo || n_points[b] > hi)) atomicAdd(bad, 1);
-    if (target[b] < 0 || target[b] >= n_classes) atomicAdd(bad + 1, 1);
+    if (tid == 0) atk_cw_report(S, b, B, lo, success, bounds);
 }
 
 }  // namespace
@@ -275,11 +237,9 @@ hipError_t launch_add_select(const float* grad, const float* pc, const int32_t* 
 hipError_t launch_add_step(int kind, const CwState& S, const float* grad, const int32_t* pred, const float* loss, const int32_t* target,
                            float* cat, const int32_t* n_ori, float* last_input, float* info, const AddDiag& D, int t, float lr, float scale,
                            int B, int cat_stride, int num_add, hipStream_t s) {
-    // torch/optim/adam.py: Python doubles, rounded to float where they meet the float tensors (launch_cw_step)
-    const float step_size = (float)((double)lr / (1.0 - std::pow(0.9, (double)t)));
-    const float bc2 = (float)std::sqrt(1.0 - std::pow(0.999, (double)t));
+    const AdamStep a = adam_step_consts(t, lr);
     hipLaunchKernelGGL(add_step_kernel, dim3(B), dim3(256), 0, s, kind, S, grad, pred, loss, target, cat, n_ori, last_input, info, D,
-                       step_size, bc2, (float)(1.0 - 0.9), (float)(1.0 - 0.999), scale, cat_stride, num_add);
+                       a.step_size, a.bc2, a.omb1, a.omb2, scale, cat_stride, num_add);
     return hipGetLastError();
 }
 
@@ -298,14 +258,6 @@ hipError_t launch_add_start(const float* cri, const float* noise, const int32_t*
 hipError_t launch_add_finish(const CwState& S, const float* last_input, const int32_t* n_cat, int B, int out_stride, int num_add,
                              float* pc_out, int32_t* success, double* bounds, hipStream_t s) {
     hipLaunchKernelGGL(add_finish_kernel, dim3(B), dim3(256), 0, s, S, last_input, n_cat, out_stride, num_add, pc_out, success, bounds, B);
-    return hipGetLastError();
-}
-
-hipError_t launch_add_check(const int32_t* n_points, const int32_t* target, int B, int lo, int hi, int n_classes, int32_t* bad,
-                            hipStream_t s) {
-    hipError_t e = hipMemsetAsync(bad, 0, 2 * sizeof(int32_t), s);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(add_check_kernel, dim3((B + 255) / 256), dim3(256), 0, s, n_points, target, B, lo, hi, n_classes, bad);
     return hipGetLastError();
 }
 

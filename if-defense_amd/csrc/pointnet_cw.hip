@@ -10,41 +10,20 @@
 //   cw_finish_kernel   the fallback to the last forwarded cloud, success = lower > 0.
 //
 // The weights are float64 (the reference's numpy arrays): thread 0 alone touches them, nothing on the hot path is double.
-#include <cmath>
-
-#include "ifd_device.h"
-#include "ifd_internal.h"
+#include "atk_device.h"
 
 namespace ifd {
 
 namespace {
 
-// sum over the workgroup of v, every thread's contribution already summed in its own fixed order: a fixed tree
-__device__ __forceinline__ float cw_block_sum(float v, float* sh) {
-    const int tid = threadIdx.x;
-    __syncthreads();
-    sh[tid] = v;
-    __syncthreads();
-    for (int w = 128; w > 0; w >>= 1) {
-        if (tid < w) sh[tid] += sh[tid + w];
-        __syncthreads();
-    }
-    return sh[0];
-}
-
-__device__ __forceinline__ int cw_rows(const int32_t* n_points, int b, int stride) {
-    const int n = n_points ? n_points[b] : stride;
-    return min(max(n, 0), stride);
-}
-
 __global__ __launch_bounds__(256) void cw_start_kernel(const float* __restrict__ pc_in, const float* __restrict__ noise,
                                                        float* __restrict__ adv, const int32_t* __restrict__ n_points, int stride) {
-    const int b = blockIdx.x, E = cw_rows(n_points, b, stride) * 3;
+    const int b = blockIdx.x, E = atk_rows(n_points, b, stride) * 3;
     const size_t off = (size_t)b * stride * 3;
     for (int i = threadIdx.x; i < E; i += 256) adv[off + i] = noise ? pc_in[off + i] + noise[off + i] : pc_in[off + i];
 }
 
-// step_size = lr / (1 - b1^t), bc2 = sqrt(1 - b2^t), omb1 = 1 - b1, omb2 = 1 - b2: doubles on the host, rounded to float
+// step_size, bc2, omb1, omb2: adam_step_consts (ifd_internal.h)
 __global__ __launch_bounds__(256) void cw_step_kernel(CwState S, const float* __restrict__ grad, const int32_t* __restrict__ pred,
                                                       const float* __restrict__ loss, const int32_t* __restrict__ target,
                                                       float* __restrict__ adv, const float* __restrict__ ori,
@@ -53,7 +32,7 @@ __global__ __launch_bounds__(256) void cw_step_kernel(CwState S, const float* __
                                                       const int32_t* __restrict__ n_points, int stride) {
     __shared__ float sh[256];
     const int b = blockIdx.x, tid = threadIdx.x;
-    const int E = cw_rows(n_points, b, stride) * 3;
+    const int E = atk_rows(n_points, b, stride) * 3;
     const size_t off = (size_t)b * stride * 3;
     float* A = adv + off;
     const float* O = ori + off;
@@ -62,8 +41,7 @@ __global__ __launch_bounds__(256) void cw_step_kernel(CwState S, const float* __
     float* V = S.v + off;
     float a = 0.f;
     for (int i = tid; i < E; i += 256) { const float d = A[i] - O[i]; a = fmaf(d, d, a); }
-    const float dist = sqrtf(cw_block_sum(a, sh));
-    // the records: every thread reads the old values, thread 0 writes the new ones behind a barrier
+    const float dist = sqrtf(atk_block_sum(a, sh));
     const bool hit = pred[b] == target[b];
     const bool rec = hit && dist < S.bestdist[b], orec = hit && dist < S.o_bestdist[b];
     const float w = (float)S.weight[b];
@@ -85,12 +63,8 @@ __global__ __launch_bounds__(256) void cw_step_kernel(CwState S, const float* __
         if (orec) OB[i] = x;
         if (LI) LI[i] = x;
         const float g = G[i] + c * (x - O[i]);
-        // csrc/optimize.hip's Adam phase (torch/optim/adam.py _single_tensor_adam), term by term
         float mr = M[i], vr = V[i];
-        mr = __builtin_fmaf(g - mr, omb1, mr);
-        vr = __builtin_fmaf(omb2 * g, g, vr * 0.999f);
-        const float denom = sqrtf(vr) / bc2 + 1e-8f;
-        A[i] = __builtin_fmaf(-step_size, mr / denom, x);
+        A[i] = atk_adam(x, g, mr, vr, step_size, bc2, omb1, omb2);
         M[i] = mr;
         V[i] = vr;
     }
@@ -99,7 +73,7 @@ __global__ __launch_bounds__(256) void cw_step_kernel(CwState S, const float* __
 __global__ __launch_bounds__(256) void cw_adjust_kernel(CwState S, const int32_t* __restrict__ target,
                                                         const int32_t* __restrict__ n_points, int stride) {
     const int b = blockIdx.x, tid = threadIdx.x;
-    const int E = cw_rows(n_points, b, stride) * 3;
+    const int E = atk_rows(n_points, b, stride) * 3;
     const size_t off = (size_t)b * stride * 3;
     if (tid == 0) {
         const int bs = S.bestscore[b];
@@ -135,19 +109,12 @@ __global__ __launch_bounds__(256) void cw_finish_kernel(CwState S, const float* 
                                                         int32_t* __restrict__ success, double* __restrict__ bounds, int B,
                                                         const int32_t* __restrict__ n_points, int stride) {
     const int b = blockIdx.x, tid = threadIdx.x;
-    const int E = cw_rows(n_points, b, stride) * 3;
+    const int E = atk_rows(n_points, b, stride) * 3;
     const size_t off = (size_t)b * stride * 3;
     const double lo = S.lower[b];
     if (lo == 0.0)
         for (int i = tid; i < E; i += 256) pc_out[off + i] = last_input[off + i];
-    if (tid == 0) {
-        success[b] = lo > 0.0 ? 1 : 0;
-        if (bounds) {
-            bounds[b] = S.weight[b];
-            bounds[(size_t)B + b] = lo;
-            bounds[2 * (size_t)B + b] = S.upper[b];
-        }
-    }
+    if (tid == 0) atk_cw_report(S, b, B, lo, success, bounds);
 }
 
 }  // namespace
@@ -165,11 +132,9 @@ hipError_t launch_cw_init(const CwState& S, int B, float init_weight, float max_
 hipError_t launch_cw_step(const CwState& S, const float* grad, const int32_t* pred, const float* loss, const int32_t* target, float* adv,
                           const float* ori, float* last_input, float* info, int t, float lr, float scale, const int32_t* n_points, int B,
                           int stride, hipStream_t s) {
-    // torch/optim/adam.py: Python doubles, rounded to float where they meet the float tensors (optimize.hip adam_table_kernel)
-    const float step_size = (float)((double)lr / (1.0 - std::pow(0.9, (double)t)));
-    const float bc2 = (float)std::sqrt(1.0 - std::pow(0.999, (double)t));
-    hipLaunchKernelGGL(cw_step_kernel, dim3(B), dim3(256), 0, s, S, grad, pred, loss, target, adv, ori, last_input, info, step_size, bc2,
-                       (float)(1.0 - 0.9), (float)(1.0 - 0.999), scale, n_points, stride);
+    const AdamStep a = adam_step_consts(t, lr);
+    hipLaunchKernelGGL(cw_step_kernel, dim3(B), dim3(256), 0, s, S, grad, pred, loss, target, adv, ori, last_input, info, a.step_size, a.bc2,
+                       a.omb1, a.omb2, scale, n_points, stride);
     return hipGetLastError();
 }
 

@@ -16,11 +16,11 @@
 //                          Every sum has a fixed order and no atomics: a cloud's gradient is the same bits wherever it runs.
 //                          The trunk's pass writes grad (zeros where no gradient arrives), the STN's pass adds to it.
 //   fgm_update_kernel      one workgroup a cloud: two fixed-order reductions and an elementwise pass.
+//   atk_check_kernel       counts in [lo, hi] and targets of the one blocking check of every attack call (CW, kNN and Add too).
 //
 // The dense work here is small beside the forward's (at most 1024 points x 3 small layers, under 4 % of its FLOPs), so the
 // stack's backward is plain FMAs; the FC transposes are MFMA (v_mfma_f32_16x16x4_f32), like the forward's.
-#include "ifd_device.h"
-#include "ifd_internal.h"
+#include "atk_device.h"
 
 namespace ifd {
 
@@ -40,10 +40,10 @@ __device__ __forceinline__ f32x4 mfma4(const f32x4 a, const f32x4 b, f32x4 c) {
 }
 
 __global__ __launch_bounds__(256) void atk_check_kernel(const int32_t* __restrict__ n_points, const int32_t* __restrict__ target, int B,
-                                                        int stride, int n_classes, int32_t* __restrict__ bad) {
+                                                        int lo, int hi, int n_classes, int32_t* __restrict__ bad) {
     const int b = blockIdx.x * 256 + threadIdx.x;
     if (b >= B) return;
-    if (n_points && (n_points[b] < 1 || n_points[b] > stride)) atomicAdd(bad, 1);
+    if (n_points && (n_points[b] < lo || n_points[b] > hi)) atomicAdd(bad, 1);
     if (target[b] < 0 || target[b] >= n_classes) atomicAdd(bad + 1, 1);
 }
 
@@ -273,27 +273,12 @@ __global__ __launch_bounds__(256) void stack_backward_kernel(const float* __rest
     if (TRUNK && tid < 64) dtrans[(size_t)b * 64 + tid] = tid < 9 ? dt : 0.f;
 }
 
-// sum over the workgroup of v, every thread's contribution already summed in its own fixed order: a fixed tree
-__device__ __forceinline__ float block_sum(float v, float* sh) {
-    const int tid = threadIdx.x;
-    __syncthreads();
-    sh[tid] = v;
-    __syncthreads();
-    for (int w = 128; w > 0; w >>= 1) {
-        if (tid < w) sh[tid] += sh[tid + w];
-        __syncthreads();
-    }
-    return sh[0];
-}
-
 __global__ __launch_bounds__(256) void fgm_update_kernel(int kind, const float* __restrict__ grad, float* __restrict__ pc,
                                                          const float* __restrict__ ori_pc, float* __restrict__ momentum, float step,
                                                          float budget, float mu, const int32_t* __restrict__ n_points, int stride) {
     __shared__ float sh[256];
     const int b = blockIdx.x, tid = threadIdx.x;
-    int n = n_points ? n_points[b] : stride;
-    n = min(max(n, 0), stride);
-    const int E = n * 3;
+    const int E = atk_rows(n_points, b, stride) * 3;
     const size_t off = (size_t)b * stride * 3;
     const float* Gd = grad + off;
     float* P = pc + off;
@@ -302,20 +287,20 @@ __global__ __launch_bounds__(256) void fgm_update_kernel(int kind, const float* 
         float* M = momentum + off;
         float a = 0.f;
         for (int i = tid; i < E; i += 256) a += fabsf(Gd[i]);
-        const float l1 = block_sum(a, sh) + 1e-9f;
+        const float l1 = atk_block_sum(a, sh) + 1e-9f;
         for (int i = tid; i < E; i += 256) M[i] = mu * M[i] + Gd[i] / l1;
         D = M;                                                         // each thread reads back what it wrote itself
     }
     float a = 0.f;
     for (int i = tid; i < E; i += 256) a = fmaf(D[i], D[i], a);
-    const float norm = sqrtf(block_sum(a, sh)) + 1e-9f;
+    const float norm = sqrtf(atk_block_sum(a, sh)) + 1e-9f;
     for (int i = tid; i < E; i += 256) P[i] = P[i] - step * (D[i] / norm);
     if (kind == KIND_FGM) return;
     // ClipPointsL2 against ori_pc
     const float* O = ori_pc + off;
     a = 0.f;
     for (int i = tid; i < E; i += 256) { const float d = P[i] - O[i]; a = fmaf(d, d, a); }
-    const float sf = fminf(budget / (sqrtf(block_sum(a, sh)) + 1e-9f), 1.f);
+    const float sf = fminf(budget / (sqrtf(atk_block_sum(a, sh)) + 1e-9f), 1.f);
     for (int i = tid; i < E; i += 256) P[i] = O[i] + (P[i] - O[i]) * sf;
 }
 
@@ -331,10 +316,11 @@ void launch_fc_t(const float* gimg, const ClsFc& L, const float* x, int B, const
 
 }  // namespace
 
-hipError_t launch_atk_check(const int32_t* n_points, const int32_t* target, int B, int stride, int n_classes, int32_t* bad, hipStream_t s) {
+hipError_t launch_atk_check(const int32_t* n_points, const int32_t* target, int B, int lo, int hi, int n_classes, int32_t* bad,
+                            hipStream_t s) {
     hipError_t e = hipMemsetAsync(bad, 0, 2 * sizeof(int32_t), s);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(atk_check_kernel, dim3((B + 255) / 256), dim3(256), 0, s, n_points, target, B, stride, n_classes, bad);
+    hipLaunchKernelGGL(atk_check_kernel, dim3((B + 255) / 256), dim3(256), 0, s, n_points, target, B, lo, hi, n_classes, bad);
     return hipGetLastError();
 }
 

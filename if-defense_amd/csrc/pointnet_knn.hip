@@ -11,14 +11,7 @@
 //                       room for it is walked in chunks, in the same order.  No atomics, no float sum whose order could vary.
 //                       Work per cloud: 2 n^2 distances (8.4 M at 2048 points) - VALU-bound; global traffic is 8 arrays of 12 n bytes.
 //   knn_clip_kernel     the projection and the clip alone, the step's device function.
-//   knn_check_kernel    counts and targets of ifd_knn_attack's one blocking check.
-//
-// Adam is cw_step_kernel's arithmetic (pointnet_cw.hip) restated term for term, not shared: moving it into a header would change
-// how that file is compiled for no gain in a dozen lines.
-#include <cmath>
-
-#include "ifd_device.h"
-#include "ifd_internal.h"
+#include "atk_device.h"
 #include "knn_device.h"
 
 namespace ifd {
@@ -29,24 +22,6 @@ constexpr int KNN_PPT = KNN_MAX_POINTS / 256;        // points a thread owns at 
 constexpr int KNN_LIST_CAP = 1024;                   // masked points per chunk of the gather list (3 words each: 12 KB)
 static_assert(KNN_MAX_POINTS % 256 == 0 && KNN_MAX_POINTS <= 65536, "the gather list holds 16-bit indices");
 static_assert(2 * KNN_MAX_POINTS * 12 + KNN_LIST_CAP * 12 + 256 * 4 + KNN_PPT * 4 * 4 <= 65536, "static LDS of knn_step_kernel");
-
-// sum over the workgroup of v, every thread's contribution already summed in its own fixed order: a fixed tree
-__device__ __forceinline__ float knn_block_sum(float v, float* sh) {
-    const int tid = threadIdx.x;
-    __syncthreads();
-    sh[tid] = v;
-    __syncthreads();
-    for (int w = 128; w > 0; w >>= 1) {
-        if (tid < w) sh[tid] += sh[tid + w];
-        __syncthreads();
-    }
-    return sh[0];
-}
-
-__device__ __forceinline__ int knn_rows(const int32_t* n_points, int b, int stride) {
-    const int n = n_points ? n_points[b] : stride;
-    return min(max(n, 0), stride);
-}
 
 // ProjectInnerClipLinf on one point (clip_utils.py:83-112, 54-59): p the point, o its original, nrm its normal or nullptr
 __device__ __forceinline__ void knn_project_clip_point(float (&p)[3], const float (&o)[3], const float* __restrict__ nrm, float budget) {
@@ -77,7 +52,7 @@ struct KnnHyper {
     float w1, w2, alpha, budget;
 };
 
-// step_size = lr / (1 - b1^t), bc2 = sqrt(1 - b2^t), omb1 = 1 - b1, omb2 = 1 - b2: doubles on the host, rounded to float
+// step_size, bc2, omb1, omb2: adam_step_consts (ifd_internal.h)
 __global__ __launch_bounds__(256) void knn_step_kernel(const float* __restrict__ grad, const float* __restrict__ loss, float* __restrict__ adv,
                                                        const float* __restrict__ ori, const float* __restrict__ normal,
                                                        float* __restrict__ m, float* __restrict__ v, KnnDiag D, KnnHyper H, float step_size,
@@ -89,7 +64,7 @@ __global__ __launch_bounds__(256) void knn_step_kernel(const float* __restrict__
     __shared__ float sh[256];
     __shared__ int sCnt[KNN_PPT * 4];
     const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int n = knn_rows(n_points, b, stride);
+    const int n = atk_rows(n_points, b, stride);
     if (n < 6) return;                                          // the header: left untouched (block-uniform)
     const size_t off = (size_t)b * stride * 3;
     float* A = adv + off;
@@ -134,14 +109,14 @@ __global__ __launch_bounds__(256) void knn_step_kernel(const float* __restrict__
     float part = 0.f;
 #pragma unroll
     for (int r = 0; r < KNN_PPT; ++r) part += (r * 256 + tid < n) ? val[r] : 0.f;
-    const float mean = knn_block_sum(part, sh) / (float)n;
+    const float mean = atk_block_sum(part, sh) / (float)n;
     part = 0.f;
 #pragma unroll
     for (int r = 0; r < KNN_PPT; ++r) {
         const float c = val[r] - mean;
         part += (r * 256 + tid < n) ? c * c : 0.f;
     }
-    const float sd = sqrtf(knn_block_sum(part, sh) / (float)(n - 1));
+    const float sd = sqrtf(atk_block_sum(part, sh) / (float)(n - 1));
     const float thr = mean + H.alpha * sd;
     unsigned int mbits = 0u;
 #pragma unroll
@@ -154,8 +129,8 @@ __global__ __launch_bounds__(256) void knn_step_kernel(const float* __restrict__
             pc += (r * 256 + tid < n) ? cdm[r] : 0.f;
             pk += ((mbits >> r) & 1u) ? val[r] : 0.f;
         }
-        const float cd = knn_block_sum(pc, sh) / (float)n;
-        const float kn = knn_block_sum(pk, sh) / (float)n;
+        const float cd = atk_block_sum(pc, sh) / (float)n;
+        const float kn = atk_block_sum(pk, sh) / (float)n;
         if (tid == 0) {
             float* I = D.info + (size_t)b * 4;
             I[0] = loss ? loss[b] : 0.f;
@@ -254,7 +229,7 @@ __global__ __launch_bounds__(256) void knn_step_kernel(const float* __restrict__
         for (int c = 0; c < 3; ++c) {
             const int i = 3 * j + c;
             const float g = G[i] + gd[c];
-            // cw_step_kernel's Adam (torch/optim/adam.py _single_tensor_adam), term by term
+            // atk_adam (atk_device.h) term by term: calling it here compiles this kernel to other register numbers
             float mr = M[i], vr = V[i];
             mr = __builtin_fmaf(g - mr, omb1, mr);
             vr = __builtin_fmaf(omb2 * g, g, vr * 0.999f);
@@ -271,7 +246,7 @@ __global__ __launch_bounds__(256) void knn_step_kernel(const float* __restrict__
 
 __global__ __launch_bounds__(256) void knn_clip_kernel(float* __restrict__ adv, const float* __restrict__ ori, const float* __restrict__ normal,
                                                        float budget, const int32_t* __restrict__ n_points, int stride) {
-    const int b = blockIdx.x, n = knn_rows(n_points, b, stride);
+    const int b = blockIdx.x, n = atk_rows(n_points, b, stride);
     const size_t off = (size_t)b * stride * 3;
     for (int j = threadIdx.x; j < n; j += 256) {
         float x[3], o[3];
@@ -283,38 +258,21 @@ __global__ __launch_bounds__(256) void knn_clip_kernel(float* __restrict__ adv, 
     }
 }
 
-__global__ __launch_bounds__(256) void knn_check_kernel(const int32_t* __restrict__ n_points, const int32_t* __restrict__ target, int B,
-                                                        int stride, int n_classes, int32_t* __restrict__ bad) {
-    const int b = blockIdx.x * 256 + threadIdx.x;
-    if (b >= B) return;
-    if (n_points && (n_points[b] < 6 || n_points[b] > stride)) atomicAdd(bad, 1);
-    if (target[b] < 0 || target[b] >= n_classes) atomicAdd(bad + 1, 1);
-}
-
 }  // namespace
 
 hipError_t launch_knn_step(const float* grad, const float* loss, float* adv, const float* ori, const float* normal, float* m, float* v,
                            const KnnDiag& D, float chamfer_weight, float knn_weight, float alpha, float budget, int t, float lr, float scale,
                            const int32_t* n_points, int B, int stride, hipStream_t s) {
-    // torch/optim/adam.py: Python doubles, rounded to float where they meet the float tensors (launch_cw_step)
-    const float step_size = (float)((double)lr / (1.0 - std::pow(0.9, (double)t)));
-    const float bc2 = (float)std::sqrt(1.0 - std::pow(0.999, (double)t));
+    const AdamStep a = adam_step_consts(t, lr);
     const KnnHyper H{2.f * chamfer_weight, 2.f * knn_weight / 5.f, chamfer_weight, knn_weight, alpha, budget};
-    hipLaunchKernelGGL(knn_step_kernel, dim3(B), dim3(256), 0, s, grad, loss, adv, ori, normal, m, v, D, H, step_size, bc2,
-                       (float)(1.0 - 0.9), (float)(1.0 - 0.999), scale, n_points, stride);
+    hipLaunchKernelGGL(knn_step_kernel, dim3(B), dim3(256), 0, s, grad, loss, adv, ori, normal, m, v, D, H, a.step_size, a.bc2,
+                       a.omb1, a.omb2, scale, n_points, stride);
     return hipGetLastError();
 }
 
 hipError_t launch_knn_clip(float* adv, const float* ori, const float* normal, float budget, const int32_t* n_points, int B, int stride,
                            hipStream_t s) {
     hipLaunchKernelGGL(knn_clip_kernel, dim3(B), dim3(256), 0, s, adv, ori, normal, budget, n_points, stride);
-    return hipGetLastError();
-}
-
-hipError_t launch_knn_check(const int32_t* n_points, const int32_t* target, int B, int stride, int n_classes, int32_t* bad, hipStream_t s) {
-    hipError_t e = hipMemsetAsync(bad, 0, 2 * sizeof(int32_t), s);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(knn_check_kernel, dim3((B + 255) / 256), dim3(256), 0, s, n_points, target, B, stride, n_classes, bad);
     return hipGetLastError();
 }
 

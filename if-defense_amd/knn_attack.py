@@ -20,36 +20,20 @@ call).
 """
 from __future__ import annotations
 
-import argparse
 import os
 import sys
 
 import numpy as np
 
-from .inference import DATASETS, default_weight_path, normalize_points_np, str2bool
+from . import attack_cli as C
+from .inference import normalize_points_np
 
 
 def build_parser():
-    parser = argparse.ArgumentParser(description='Point Cloud Recognition')
-    parser.add_argument('--data_root', type=str, default='data/attack_data.npz')
-    parser.add_argument('--model', type=str, default='pointnet', metavar='N', choices=['pointnet', 'pointnet2', 'dgcnn', 'pointconv'])
-    parser.add_argument('--feature_transform', type=str2bool, default=False)
-    parser.add_argument('--dataset', type=str, default='mn40', metavar='N', choices=list(DATASETS))
-    parser.add_argument('--batch_size', type=int, default=-1, metavar='BS', help="the reference's batch (loss mean); -1: the whole file")
-    parser.add_argument('--num_points', type=int, default=1024)
-    parser.add_argument('--emb_dims', type=int, default=1024, help='unused by PointNet')
-    parser.add_argument('--k', type=int, default=20, help='unused by PointNet')
-    parser.add_argument('--adv_func', type=str, default='logits', choices=['logits', 'cross_entropy'])
-    parser.add_argument('--kappa', type=float, default=15.)
+    parser = C.parser_head(kappa=15.)
     parser.add_argument('--attack_lr', type=float, default=1e-3)
     parser.add_argument('--num_iter', type=int, default=2500, metavar='N')
-    parser.add_argument('--local_rank', default=-1, type=int, help='accepted; only names the output file')
-    parser.add_argument('--model_path', type=str, default='')
-    parser.add_argument('--seed', type=int, default=1)
-    parser.add_argument('--device', type=str, default='cuda:0')
-    parser.add_argument('--out_dir', type=str, default='.')
-    parser.add_argument('--verbose', type=str2bool, default=False)
-    return parser
+    return C.parser_tail(parser)
 
 
 def save_path(out_dir, dataset, num_points, model, adv_func, kappa, success_rate, local_rank):
@@ -72,12 +56,7 @@ def load_clouds(test_pc, num_points):
 def main(argv=None, make_classifier=None) -> int:
     from .attack import CWKNN
     args = build_parser().parse_args(argv)
-    if args.model.lower() != 'pointnet':
-        print("knn_attack: the {} victim is not built here (only pointnet is)".format(args.model), file=sys.stderr)
-        return 2
-    if args.feature_transform:
-        print("knn_attack: input gradients through the feature transform are not built here (--feature_transform false only)",
-              file=sys.stderr)
+    if C.refuse_unbuilt('knn_attack', args):
         return 2
     if args.num_iter < 1:
         print("knn_attack: --num_iter must be at least 1", file=sys.stderr)
@@ -90,33 +69,18 @@ def main(argv=None, make_classifier=None) -> int:
         return 2
     if data.shape[2] == 3:
         print("knn_attack: the clouds carry no normals: running without the projection of inner points, the clip alone")
-    label, target = np.asarray(npz['test_label']).reshape(-1), np.asarray(npz['target_label']).reshape(-1)
-    if make_classifier is None:
-        def make_classifier(model, feature_transform, model_path):
-            from .runtime import Classifier
-            from .weights import load_checkpoint
-            return Classifier(load_checkpoint(model_path, model, feature_transform), model, feature_transform, device=args.device)
-    model_path = args.model_path or default_weight_path(args.dataset, args.model)
-    print('Loading weight {}'.format(model_path))
-    classifier = make_classifier(args.model, False, model_path)
+    label, target = C.load_labels(npz)
+    classifier = C.open_classifier(args, make_classifier)
     try:
         attacker = CWKNN(classifier, args.adv_func, 'chamfer_knn', 'project_inner_clip_linf', attack_lr=args.attack_lr,
                          num_iter=args.num_iter, kappa=args.kappa, seed=args.seed, verbose=args.verbose)
-        bs = len(data) if args.batch_size < 1 else args.batch_size
-        adv, num = [], 0
-        for a in range(0, len(data), bs):
-            pc, n_ok = attacker.attack(data[a:a + bs], target[a:a + bs].astype(np.int64))
-            adv.append(pc)
-            num += n_ok
+        adv, num = C.run_batches(attacker, data, target, args.batch_size)
     finally:
-        if hasattr(classifier, "close"):
-            classifier.close()
-    adv = np.concatenate(adv, axis=0)
+        C.close_classifier(classifier)
     rate = float(num) / float(len(data))
     d, name = save_path(args.out_dir, args.dataset, args.num_points, args.model, args.adv_func, args.kappa, rate,
                         0 if args.local_rank < 0 else args.local_rank)
-    os.makedirs(d, exist_ok=True)
-    np.savez(os.path.join(d, name), test_pc=adv.astype(np.float32), test_label=label.astype(np.uint8), target_label=target.astype(np.uint8))
+    C.save_npz(d, name, adv, label, target)
     return 0
 
 

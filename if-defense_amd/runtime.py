@@ -697,11 +697,7 @@ class Classifier:
         pc = _f32(torch.as_tensor(pc), self.device)
         if pc.dim() != 3 or pc.shape[2] != 3:
             raise IfdError("clouds must be [B,N,3] (point-major), got %s" % (tuple(pc.shape),))
-        if n_points is not None:
-            n_points = torch.as_tensor(n_points).to(device=self.device, dtype=torch.int32).contiguous()
-            if tuple(n_points.shape) != (pc.shape[0],):
-                raise IfdError("n_points must be [B]")
-        return pc, n_points
+        return pc, self._counts(n_points, int(pc.shape[0]))
 
     def logits(self, pc, n_points=None, want_aux: bool = False, want_pred: bool = False):
         """pc: [B,N,3] tensor / array, or a list (or object array) of ragged [K_i,3] clouds, which are padded into one strided
@@ -747,6 +743,38 @@ class Classifier:
             raise IfdError("target must be [B]")
         return t
 
+    def _counts(self, n, B):
+        """n_points / n_ori as [B] int32 on the device, or None."""
+        if n is None:
+            return None
+        n = torch.as_tensor(n).to(device=self.device, dtype=torch.int32).contiguous()
+        if tuple(n.shape) != (B,):
+            raise IfdError("n_points must be [B]")
+        return n
+
+    def _vec(self, x, B, dtype, name):
+        """pred / loss as [B] of dtype on the device, or None."""
+        if x is None:
+            return None
+        x = torch.as_tensor(x).to(device=self.device, dtype=dtype).contiguous()
+        if tuple(x.shape) != (B,):
+            raise IfdError("%s must be [B]" % name)
+        return x
+
+    def _diag(self, want, shapes, names_text):
+        """The diagnostics named in ``want`` as a dict of device tensors, NaN / -1 where the library leaves them untouched."""
+        out = {}
+        for k in want:
+            if k not in shapes:
+                raise IfdError("unknown diagnostic %r (%s)" % (k, names_text))
+            shape, dt = shapes[k]
+            out[k] = torch.full(shape, float("nan") if dt == torch.float32 else -1, device=self.device, dtype=dt)
+        return out
+
+    @staticmethod
+    def _bounds(bounds):
+        return {"weight": bounds[0], "lower": bounds[1], "upper": bounds[2]}
+
     def _stream(self):
         return torch.cuda.current_stream(self.device).cuda_stream
 
@@ -784,8 +812,7 @@ class Classifier:
         for t in (grad, pc, ori_pc, momentum):
             if t is not None and not (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and tuple(t.shape) == (B, stride, 3)):
                 raise IfdError("fgm_update works in place on contiguous float32 [B,N,3] device tensors")
-        if n_points is not None:
-            n_points = torch.as_tensor(n_points).to(device=self.device, dtype=torch.int32).contiguous()
+        n_points = self._counts(n_points, B)
         ptr = lambda t: None if t is None else t.data_ptr()        # noqa: E731
         with torch.cuda.device(self.device):
             self._check(self.lib.ifd_fgm_update(self.ctx, self.FGM_KINDS[kind], ptr(grad), ptr(pc), ptr(ori_pc), ptr(momentum),
@@ -849,16 +876,10 @@ class Classifier:
         B, stride = int(adv.shape[0]), int(adv.shape[1])
         st = self._cw_struct(state, B, stride)
         ptrs = [self._cw_cloud(x, B, stride, n) for x, n in ((grad, "grad"), (adv, "adv"), (ori, "ori"), (last_input, "last_input"))]
-        pred = torch.as_tensor(pred).to(device=self.device, dtype=torch.int32).contiguous()
+        pred = self._vec(pred, B, torch.int32, "pred")
         target = self._target(target, B)
-        if tuple(pred.shape) != (B,):
-            raise IfdError("pred must be [B]")
-        if loss is not None:
-            loss = _f32(torch.as_tensor(loss), self.device)
-            if tuple(loss.shape) != (B,):
-                raise IfdError("loss must be [B]")
-        if n_points is not None:
-            n_points = torch.as_tensor(n_points).to(device=self.device, dtype=torch.int32).contiguous()
+        loss = self._vec(loss, B, torch.float32, "loss")
+        n_points = self._counts(n_points, B)
         info = torch.empty(B, 3, device=self.device, dtype=torch.float32) if want_info else None
         ptr = lambda x: None if x is None else x.data_ptr()        # noqa: E731
         with torch.cuda.device(self.device):
@@ -872,8 +893,7 @@ class Classifier:
         B, stride = int(state["m"].shape[0]), int(state["m"].shape[1])
         st = self._cw_struct(state, B, stride)
         target = self._target(target, B)
-        if n_points is not None:
-            n_points = torch.as_tensor(n_points).to(device=self.device, dtype=torch.int32).contiguous()
+        n_points = self._counts(n_points, B)
         with torch.cuda.device(self.device):
             self._check(self.lib.ifd_cw_adjust(self.ctx, C.byref(st), target.data_ptr(), None if n_points is None else n_points.data_ptr(),
                                                B, stride, self._stream()))
@@ -906,7 +926,7 @@ class Classifier:
                                                        out.data_ptr(), best.data_ptr(), success.data_ptr(),
                                                        None if bounds is None else bounds.data_ptr(), self._stream()))
         if want_bounds:
-            return out, best, success.bool(), {"weight": bounds[0], "lower": bounds[1], "upper": bounds[2]}
+            return out, best, success.bool(), self._bounds(bounds)
         return out, best, success.bool()
 
     # ---- include/ifd_knn.h: the kNN attack (models without feature_transform) ----
@@ -914,14 +934,6 @@ class Classifier:
                     alpha=1.05, budget=0.1):
         return _lib.IfdKnnParams(C.sizeof(_lib.IfdKnnParams), int(loss_kind), int(num_iter), float(kappa), float(scale), float(attack_lr),
                                  float(chamfer_weight), float(knn_weight), float(alpha), float(budget))
-
-    def _knn_counts(self, n_points, B):
-        if n_points is None:
-            return None
-        n_points = torch.as_tensor(n_points).to(device=self.device, dtype=torch.int32).contiguous()
-        if tuple(n_points.shape) != (B,):
-            raise IfdError("n_points must be [B]")
-        return n_points
 
     def knn_step(self, grad, adv, ori, m, v, t, lr, scale=1., normal=None, loss=None, n_points=None, chamfer_weight=5., knn_weight=3.,
                  alpha=1.05, budget=0.1, want=()):
@@ -938,19 +950,11 @@ class Classifier:
             if x is None and name != "normal":
                 raise IfdError("%s is missing" % name)
         ptrs = {name: self._cw_cloud(x, B, stride, name) for name, x in names}
-        if loss is not None:
-            loss = _f32(torch.as_tensor(loss), self.device)
-            if tuple(loss.shape) != (B,):
-                raise IfdError("loss must be [B]")
-        n_points = self._knn_counts(n_points, B)
+        loss = self._vec(loss, B, torch.float32, "loss")
+        n_points = self._counts(n_points, B)
         shapes = {"info": ((B, 4), torch.float32), "dist_grad": ((B, stride, 3), torch.float32), "nn_ori": ((B, stride), torch.int32),
                   "nn5": ((B, stride, 5), torch.int32), "mask": ((B, stride), torch.int32)}
-        out = {}
-        for k in want:
-            if k not in shapes:
-                raise IfdError("unknown diagnostic %r (info | dist_grad | nn_ori | nn5 | mask)" % (k,))
-            shape, dt = shapes[k]
-            out[k] = torch.full(shape, float("nan") if dt == torch.float32 else -1, device=self.device, dtype=dt)
+        out = self._diag(want, shapes, "info | dist_grad | nn_ori | nn5 | mask")
         ptr = lambda x: None if x is None else x.data_ptr()        # noqa: E731
         diag = _lib.IfdKnnDiag(*[ptr(out.get(k)) for k in ("info", "dist_grad", "nn_ori", "nn5", "mask")])
         P = self._knn_params(chamfer_weight=chamfer_weight, knn_weight=knn_weight, alpha=alpha, budget=budget)
@@ -969,7 +973,7 @@ class Classifier:
         if ori is None:
             raise IfdError("ori is missing")
         ptrs = [self._cw_cloud(x, B, stride, name) for name, x in (("adv", adv), ("ori", ori), ("normal", normal))]
-        n_points = self._knn_counts(n_points, B)
+        n_points = self._counts(n_points, B)
         with torch.cuda.device(self.device):
             self._check(self.lib.ifd_knn_project_clip(self.ctx, ptrs[0], ptrs[1], ptrs[2], float(budget),
                                                       None if n_points is None else n_points.data_ptr(), B, stride, self._stream()))
@@ -1068,22 +1072,12 @@ class Classifier:
         if grad is None:
             raise IfdError("grad is missing")
         li = self._cw_cloud(last_input, B, num_add, "last_input")
-        pred = torch.as_tensor(pred).to(device=self.device, dtype=torch.int32).contiguous()
+        pred = self._vec(pred, B, torch.int32, "pred")
         target = self._target(target, B)
-        if tuple(pred.shape) != (B,):
-            raise IfdError("pred must be [B]")
-        if loss is not None:
-            loss = _f32(torch.as_tensor(loss), self.device)
-            if tuple(loss.shape) != (B,):
-                raise IfdError("loss must be [B]")
-        n_ori = self._knn_counts(n_ori, B)
+        loss = self._vec(loss, B, torch.float32, "loss")
+        n_ori = self._counts(n_ori, B)
         shapes = {"dist_grad": ((B, num_add, 3), torch.float32), "nn_ori": ((B, num_add), torch.int32), "far": ((B,), torch.int32)}
-        out = {}
-        for k in want:
-            if k not in shapes:
-                raise IfdError("unknown diagnostic %r (dist_grad | nn_ori | far)" % (k,))
-            shape, dt = shapes[k]
-            out[k] = torch.full(shape, float("nan") if dt == torch.float32 else -1, device=self.device, dtype=dt)
+        out = self._diag(want, shapes, "dist_grad | nn_ori | far")
         ptr = lambda x: None if x is None else x.data_ptr()        # noqa: E731
         diag = _lib.IfdAddDiag(*[ptr(out.get(k)) for k in ("dist_grad", "nn_ori", "far")])
         info = torch.empty(B, 3, device=self.device, dtype=torch.float32) if want_info else None
@@ -1128,5 +1122,5 @@ class Classifier:
                                                 out.data_ptr(), best.data_ptr(), success.data_ptr(),
                                                 None if bounds is None else bounds.data_ptr(), self._stream()))
         if want_bounds:
-            return out, best, success.bool(), {"weight": bounds[0], "lower": bounds[1], "upper": bounds[2]}
+            return out, best, success.bool(), self._bounds(bounds)
         return out, best, success.bool()
