@@ -24,6 +24,7 @@
 #include <vector>
 
 #include "ifd_internal.h"
+#include "ifd_host.h"
 
 // device-side size of the counter buffer: the IFD_N_COUNTERS public slots + the per-wave time stamps of -DIFD_TRACE builds
 constexpr int N_COUNTERS_DEV = IFD_N_COUNTERS + 8 * 32;
@@ -50,36 +51,36 @@ struct WeightMap {
 WeightMap make_weight_map() {
     WeightMap m{};
     size_t o = 0;
-    auto take = [&](size_t n) { size_t r = o; o += n; return r; };
-    m.dec_fc_p_w = take(32 * 3); m.dec_fc_p_b = take(32);
-    for (int i = 0; i < 5; ++i) { m.dec_fc_c_w[i] = take(1024); m.dec_fc_c_b[i] = take(32); }
+    auto next = [&](size_t n) { size_t r = o; o += n; return r; };
+    m.dec_fc_p_w = next(32 * 3); m.dec_fc_p_b = next(32);
+    for (int i = 0; i < 5; ++i) { m.dec_fc_c_w[i] = next(1024); m.dec_fc_c_b[i] = next(32); }
     for (int i = 0; i < 5; ++i) {
-        m.dec_fc0_w[i] = take(1024); m.dec_fc0_b[i] = take(32);
-        m.dec_fc1_w[i] = take(1024); m.dec_fc1_b[i] = take(32);
+        m.dec_fc0_w[i] = next(1024); m.dec_fc0_b[i] = next(32);
+        m.dec_fc1_w[i] = next(1024); m.dec_fc1_b[i] = next(32);
     }
-    m.dec_out_w = take(32); m.dec_out_b = take(1);
-    m.enc_pos_w = take(64 * 3); m.enc_pos_b = take(64);
+    m.dec_out_w = next(32); m.dec_out_b = next(1);
+    m.enc_pos_w = next(64 * 3); m.enc_pos_b = next(64);
     for (int i = 0; i < 5; ++i) {
-        m.enc_fc0_w[i] = take(32 * 64); m.enc_fc0_b[i] = take(32);
-        m.enc_fc1_w[i] = take(32 * 32); m.enc_fc1_b[i] = take(32);
-        m.enc_sc_w[i] = take(32 * 64);
+        m.enc_fc0_w[i] = next(32 * 64); m.enc_fc0_b[i] = next(32);
+        m.enc_fc1_w[i] = next(32 * 32); m.enc_fc1_b[i] = next(32);
+        m.enc_sc_w[i] = next(32 * 64);
     }
-    m.enc_fcc_w = take(1024); m.enc_fcc_b = take(32);
+    m.enc_fcc_w = next(1024); m.enc_fcc_b = next(32);
     const int ch[4] = {32, 64, 128, 256};
     int cin = 32;
     for (int i = 0; i < 4; ++i) {
-        m.down_w[i][0] = take((size_t)ch[i] * cin * 9); m.down_b[i][0] = take(ch[i]);
-        m.down_w[i][1] = take((size_t)ch[i] * ch[i] * 9); m.down_b[i][1] = take(ch[i]);
+        m.down_w[i][0] = next((size_t)ch[i] * cin * 9); m.down_b[i][0] = next(ch[i]);
+        m.down_w[i][1] = next((size_t)ch[i] * ch[i] * 9); m.down_b[i][1] = next(ch[i]);
         cin = ch[i];
     }
     for (int i = 0; i < 3; ++i) {
         const int co = cin / 2;
-        m.up_t_w[i] = take((size_t)cin * co * 4); m.up_t_b[i] = take(co);
-        m.up_w[i][0] = take((size_t)co * 2 * co * 9); m.up_b[i][0] = take(co);
-        m.up_w[i][1] = take((size_t)co * co * 9); m.up_b[i][1] = take(co);
+        m.up_t_w[i] = next((size_t)cin * co * 4); m.up_t_b[i] = next(co);
+        m.up_w[i][0] = next((size_t)co * 2 * co * 9); m.up_b[i][0] = next(co);
+        m.up_w[i][1] = next((size_t)co * co * 9); m.up_b[i][1] = next(co);
         cin = co;
     }
-    m.fin_w = take(32 * 32); m.fin_b = take(32);
+    m.fin_w = next(32 * 32); m.fin_b = next(32);
     m.total = o;
     return m;
 }
@@ -93,65 +94,61 @@ const WeightMap& wmap() {
 
 constexpr int LARGE_MAX_GROUPS = 4;   // stream groups of the launch-per-step path (large_optimize_in_groups)
 
+// Every HIP resource of a context is a member that releases itself (ifd_host.h): deleting the context is the only release path.
 struct ifd_ctx {
     int device = 0;
     ifd_config cfg{};
     std::vector<float> w;          // host copy, canonical order
-    float* d_dec_img = nullptr;    // decoder parameter image (ifd_device.h layout)
-    float* d_dec_img_bf = nullptr; // ... and the bf16 piece image of the split-precision tiles (ifd_opt_params.precision 1 / 2)
-    float* d_dec_img_opt = nullptr;// ... the persistent optimiser's copy: fc_0 / fc_1 / fc_out scaled by 2^RELU_K (ifd_device.h)
-    float* d_w = nullptr;          // the whole canonical weight vector on the device (encoder kernels index it)
+    DeviceBuffer d_dec_img;        // decoder parameter image (ifd_device.h layout)
+    DeviceBuffer d_dec_img_bf;     // ... and the bf16 piece image of the split-precision tiles (ifd_opt_params.precision 1 / 2)
+    DeviceBuffer d_dec_img_opt;    // ... the persistent optimiser's copy: fc_0 / fc_1 / fc_out scaled by 2^RELU_K (ifd_device.h)
+    DeviceBuffer d_w;              // the whole canonical weight vector on the device (encoder kernels index it)
     EncPointOffsets eo{};
-    float* d_unet = nullptr;       // re-packed U-Net weights ([tap][Cin][Cout])
-    float* d_enc_img = nullptr;    // aligned copy of the point-net weights (encoder.hip build_enc_image)
+    DeviceBuffer d_unet;           // re-packed U-Net weights ([tap][Cin][Cout])
+    DeviceBuffer d_enc_img;        // aligned copy of the point-net weights (encoder.hip build_enc_image)
     UNetWeights uw{};
-    void* ws_enc = nullptr;        // encoder scratch (pre-U-Net planes + U-Net activations), grown on demand
-    size_t ws_enc_bytes = 0;
-    void* ws_fold = nullptr;       // ONet: folded CBN coefficients of the clouds of the current decode / optimise / mesh call (onet_fold) -
-    size_t ws_fold_bytes = 0;      // NOT the encoder scratch: the optimiser reads them for its whole launch while an encoder call may run beside it
+    DeviceBuffer ws_enc;           // encoder scratch (pre-U-Net planes + U-Net activations), grown on demand
+    DeviceBuffer ws_fold;          // ONet: folded CBN coefficients of the clouds of the current decode / optimise / mesh call (onet_fold) -
+                                   // NOT the encoder scratch: the optimiser reads them for its whole launch while an encoder call may run beside it
     DecConst dc{};
-    unsigned long long* d_counters = nullptr;   // IFD_N_COUNTERS diagnostic counters of the last ifd_optimize
+    DeviceBuffer d_counters;       // IFD_N_COUNTERS diagnostic counters of the last ifd_optimize (unsigned long long)
     int n_cu = 256;                // compute units of the device (rounds of the persistent optimiser)
-    void* ws = nullptr;            // context-owned scratch (kNN lists, encoder activations), grown on demand
-    size_t ws_bytes = 0;
-    void* adam_tab = nullptr;      // per-step Adam bias corrections of the current optimise call (launch_adam_table)
-    size_t adam_bytes = 0;
+    DeviceBuffer ws;               // context-owned scratch (kNN lists, encoder activations), grown on demand
+    DeviceBuffer adam_tab;         // per-step Adam bias corrections of the current optimise call (launch_adam_table)
     // ONet-Opt variant (ifd_onet_create): padded copy of the canonical weights, fragment-ordered decoder layer images
     // (10 forward + 10 transposed), the small decoder parameters, tensor offsets into d_w
     int model = IFD_MODEL_CONVONET;
-    float* d_onet_img = nullptr;
-    float* d_onet_img_bf = nullptr; // ... the same layers as bf16 pieces (split precision, onet_fragment_image_bf)
-    float* d_onet_small = nullptr;
+    DeviceBuffer d_onet_img;
+    DeviceBuffer d_onet_img_bf;    // ... the same layers as bf16 pieces (split precision, onet_fragment_image_bf)
+    DeviceBuffer d_onet_small;
     OnetEncOffsets oe{};
     OnetDecOffsets od{};
-    void* ws_mesh = nullptr;       // ONet-Mesh scratch (MISE arrays, triangle soup)
+    DeviceBuffer ws_mesh;          // ONet-Mesh scratch (MISE arrays, triangle soup)
     unsigned long long mesh_points = 0, mesh_rounds = 0;   // grid points evaluated / MISE rounds of the last mesh call
-    size_t ws_mesh_bytes = 0;
-    int* h_mesh_counts = nullptr;  // pinned: the queue lengths of the last two MISE rounds (ifd_onet_mesh_sample reads them one round late)
-    size_t h_mesh_counts_n = 0;    // ints per slot
-    hipEvent_t mesh_ev[2] = {nullptr, nullptr};
+    PinnedBuffer h_mesh_counts;    // two slots of ints: the queue lengths of the last two MISE rounds (ifd_onet_mesh_sample reads them one round late)
+    Event mesh_ev[2];
     // read from the environment once, at creation (read_opt_env): bound of the cross-CU waits of split clouds, test hook
     unsigned int coop_timeout_ticks = 3000000000u;
     int test_drop_member = -1;
     int test_large_groups = 0;     // measurement hook: stream groups of the launch-per-step path (0 = automatic; large_groups_of)
     // clouds of more than 1024 points: side streams + fork / join events of the stream groups (run_large_in_groups), created on first use
-    hipStream_t large_side[LARGE_MAX_GROUPS - 1] = {};
-    hipEvent_t large_fork = nullptr, large_join[LARGE_MAX_GROUPS - 1] = {};
+    Stream large_side[LARGE_MAX_GROUPS - 1];
+    Event large_fork, large_join[LARGE_MAX_GROUPS - 1];
     int test_no_morton = 0;        // measurement hook: ifd_prepare leaves the optimised points in draw order (the locality A/B through the whole pipeline)
-    unsigned long long* d_status_out = nullptr;   // ifd_optimize_status: the status words as taken (atomic exchange) by status_take_kernel
+    DeviceBuffer d_status_out;     // ifd_optimize_status: the status words as taken (atomic exchange) by status_take_kernel
     // baseline defenses (ifd_dup_create): the PU-Net tile image (punet.hip) and its per-chunk scratch
-    float* d_punet = nullptr;
+    DeviceBuffer d_punet;
     PunetImage pimg{};
-    void* ws_dup = nullptr;
-    size_t ws_dup_bytes = 0;
+    DeviceBuffer ws_dup;
     // victim classifier (ifd_cls_create): the PointNet weight image (pointnet.hip); its scratch is `ws`
-    float* d_cls = nullptr;
+    DeviceBuffer d_cls;
     ClsImage cimg{};
     int cls_feature_transform = 0, cls_classes = 0;
     // ... and the backward pass's weight image (include/ifd_atk.h; contexts without feature_transform only)
-    float* d_cls_grad = nullptr;
+    DeviceBuffer d_cls_grad;
     ClsGradImage gimg{};
     std::string err;
+    unsigned long long* counters() const { return d_counters.get<unsigned long long>(); }
 };
 
 namespace {
@@ -304,22 +301,9 @@ OptEnv read_opt_env() {
     return o;
 }
 
-// Grow the context workspace.  Growing synchronises the device (hipFree), which only happens when a call
-// needs more scratch than any earlier call on this context.
-hipError_t ensure_buf(void** buf, size_t* have, size_t bytes) {
-    if (bytes <= *have) return hipSuccess;
-    if (*buf) {
-        hipError_t e = hipDeviceSynchronize();
-        if (e != hipSuccess) return e;
-        (void)hipFree(*buf);
-        *buf = nullptr;
-        *have = 0;
-    }
-    hipError_t e = hipMalloc(buf, bytes);
-    if (e == hipSuccess) *have = bytes;
-    return e;
-}
-hipError_t ensure_ws(ifd_ctx* ctx, size_t bytes) { return ensure_buf(&ctx->ws, &ctx->ws_bytes, bytes); }
+// the size of a workspace: its layout function run on a null base (ifd_host.h Carve)
+template <class Layout>
+size_t carved_bytes(Layout&& layout) { Carve c(nullptr); layout(c); return c.bytes(); }
 
 // Re-pack the U-Net convolutions to [tap][Cin][Cout] (Conv2d weight [Cout][Cin][kh][kw]; ConvTranspose2d weight
 // [Cin][Cout][kh][kw]) and record where each tensor starts.
@@ -409,33 +393,33 @@ struct OnetMap {
 OnetMap make_onet_map() {
     OnetMap m{};
     size_t ho = 0, dv = 0;
-    auto take = [&](size_t n) {
+    auto next = [&](size_t n) {
         OnetTensor t{ho, dv, n};
         ho += n;
         dv += (n + 3) & ~(size_t)3;          // device copy: every tensor starts on a 16-byte boundary
         return t;
     };
     auto cbn = [&](int i) {
-        m.cbn[i][0] = take((size_t)ONET_H * ONET_C); m.cbn[i][1] = take(ONET_H);
-        m.cbn[i][2] = take((size_t)ONET_H * ONET_C); m.cbn[i][3] = take(ONET_H);
-        m.cbn[i][4] = take(ONET_H); m.cbn[i][5] = take(ONET_H);
+        m.cbn[i][0] = next((size_t)ONET_H * ONET_C); m.cbn[i][1] = next(ONET_H);
+        m.cbn[i][2] = next((size_t)ONET_H * ONET_C); m.cbn[i][3] = next(ONET_H);
+        m.cbn[i][4] = next(ONET_H); m.cbn[i][5] = next(ONET_H);
     };
-    m.fc_p_w = take(ONET_H * 3); m.fc_p_b = take(ONET_H);
+    m.fc_p_w = next(ONET_H * 3); m.fc_p_b = next(ONET_H);
     for (int i = 0; i < 5; ++i) {
         cbn(2 * i); cbn(2 * i + 1);
-        m.fc0_w[i] = take((size_t)ONET_H * ONET_H); m.fc0_b[i] = take(ONET_H);
-        m.fc1_w[i] = take((size_t)ONET_H * ONET_H); m.fc1_b[i] = take(ONET_H);
+        m.fc0_w[i] = next((size_t)ONET_H * ONET_H); m.fc0_b[i] = next(ONET_H);
+        m.fc1_w[i] = next((size_t)ONET_H * ONET_H); m.fc1_b[i] = next(ONET_H);
     }
     cbn(10);
-    m.out_w = take(ONET_H); m.out_b = take(1);
+    m.out_w = next(ONET_H); m.out_b = next(1);
     const size_t H = ONET_ENC_H;
-    m.pos_w = take(2 * H * 3); m.pos_b = take(2 * H);
+    m.pos_w = next(2 * H * 3); m.pos_b = next(2 * H);
     for (int i = 0; i < 5; ++i) {
-        m.e_fc0_w[i] = take(H * 2 * H); m.e_fc0_b[i] = take(H);
-        m.e_fc1_w[i] = take(H * H); m.e_fc1_b[i] = take(H);
-        m.e_sc_w[i] = take(H * 2 * H);
+        m.e_fc0_w[i] = next(H * 2 * H); m.e_fc0_b[i] = next(H);
+        m.e_fc1_w[i] = next(H * H); m.e_fc1_b[i] = next(H);
+        m.e_sc_w[i] = next(H * 2 * H);
     }
-    m.fcc_w = take((size_t)ONET_C * H); m.fcc_b = take(ONET_C);
+    m.fcc_w = next((size_t)ONET_C * H); m.fcc_b = next(ONET_C);
     m.host_total = ho; m.dev_total = dv;
     return m;
 }
@@ -484,6 +468,44 @@ void onet_fragment_image_bf(const float* W, bool transposed, bool half_major, ui
         }
 }
 
+// The one way a context comes into being, behind the argument checks of the four ifd_*_create functions: the device is made
+// current, n_cu and the environment are read (for every kind of context), then `build` allocates and uploads what its kind needs.
+// A failed build deletes the half-built context, which releases whatever it had got.
+template <class Build>
+ifd_ctx* create_ctx(const char* who, int model, int device, Build&& build) {
+    g_create_error.clear();
+    ifd_ctx* ctx = new (std::nothrow) ifd_ctx();
+    if (!ctx) { g_create_error = std::string(who) + ": out of host memory"; return nullptr; }
+    ctx->device = device;
+    ctx->model = model;
+    hipError_t e = hipSetDevice(device);
+    if (e == hipSuccess) {
+        int n_cu = 0;
+        if (hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, device) == hipSuccess && n_cu > 0) ctx->n_cu = n_cu;
+        const OptEnv env = read_opt_env();
+        ctx->coop_timeout_ticks = env.coop_timeout_ticks; ctx->test_drop_member = env.test_drop_member;
+        ctx->test_no_morton = env.test_no_morton; ctx->test_large_groups = env.test_large_groups;
+        e = build(ctx);
+    }
+    if (e != hipSuccess) {
+        g_create_error = std::string(who) + ": " + hipGetErrorString(e);
+        delete ctx;
+        return nullptr;
+    }
+    return ctx;
+}
+
+template <class T>
+hipError_t upload(DeviceBuffer& dst, const std::vector<T>& src) { return dst.upload(src.data(), src.size() * sizeof(T)); }
+
+// the counter buffer (zeroed) and the landing words of ifd_optimize_status
+hipError_t alloc_counters(ifd_ctx* ctx) {
+    hipError_t e = ctx->d_counters.alloc(N_COUNTERS_ALLOC * sizeof(unsigned long long));
+    if (e == hipSuccess) e = hipMemset(ctx->d_counters.get(), 0, N_COUNTERS_ALLOC * sizeof(unsigned long long));
+    if (e == hipSuccess) e = ctx->d_status_out.alloc(2 * sizeof(unsigned long long));
+    return e;
+}
+
 }  // namespace
 
 extern "C" {
@@ -495,7 +517,6 @@ size_t ifd_weight_count(void) { return wmap().total; }
 const char* ifd_last_error(const ifd_ctx* ctx) { return ctx ? ctx->err.c_str() : g_create_error.c_str(); }
 
 ifd_ctx* ifd_create(const float* weights_host, size_t n_weights, const ifd_config* cfg, int device) {
-    g_create_error.clear();
     if (!weights_host || !cfg) { g_create_error = "ifd_create: NULL argument"; return nullptr; }
     if (n_weights != wmap().total) {
         g_create_error = "ifd_create: expected " + std::to_string(wmap().total) + " weights, got " +
@@ -508,40 +529,17 @@ ifd_ctx* ifd_create(const float* weights_host, size_t n_weights, const ifd_confi
                          "U-Net depth 4 / 32 filters) is supported";
         return nullptr;
     }
-    ifd_ctx* ctx = new (std::nothrow) ifd_ctx();
-    if (!ctx) { g_create_error = "ifd_create: out of host memory"; return nullptr; }
-    ctx->device = device;
-    ctx->cfg = *cfg;
-    ctx->w.assign(weights_host, weights_host + n_weights);
-    ctx->dc.sdiv = (float)(1.0 + (double)cfg->padding + 10e-6);
-    ctx->dc.uclamp = (float)(1.0 - 10e-6);
-    hipError_t e = hipSetDevice(device);
-    if (e == hipSuccess) {
-        int n_cu = 0;
-        if (hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, device) == hipSuccess && n_cu > 0) ctx->n_cu = n_cu;
-    }
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&ctx->d_dec_img), DEC_FLOATS * sizeof(float));
-    if (e == hipSuccess) {
-        std::vector<float> img = build_dec_image(ctx->w.data());
-        e = hipMemcpy(ctx->d_dec_img, img.data(), DEC_FLOATS * sizeof(float), hipMemcpyHostToDevice);
-        if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&ctx->d_dec_img_opt), DEC_FLOATS * sizeof(float));
-        if (e == hipSuccess) {
-            std::vector<float> img2 = build_dec_image(ctx->w.data(), true);
-            e = hipMemcpy(ctx->d_dec_img_opt, img2.data(), DEC_FLOATS * sizeof(float), hipMemcpyHostToDevice);
-        }
-        if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&ctx->d_dec_img_bf), BF_IMG_BYTES);
-        if (e == hipSuccess) {
-            std::vector<unsigned char> img3 = build_dec_image_bf(ctx->w.data());
-            e = hipMemcpy(ctx->d_dec_img_bf, img3.data(), BF_IMG_BYTES, hipMemcpyHostToDevice);
-        }
-    }
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&ctx->d_counters), N_COUNTERS_ALLOC * sizeof(unsigned long long));
-    if (e == hipSuccess) e = hipMemset(ctx->d_counters, 0, N_COUNTERS_ALLOC * sizeof(unsigned long long));
-    if (e == hipSuccess && !ctx->d_status_out) e = hipMalloc(reinterpret_cast<void**>(&ctx->d_status_out), 2 * sizeof(unsigned long long));
-    { const OptEnv oe = read_opt_env(); ctx->coop_timeout_ticks = oe.coop_timeout_ticks; ctx->test_drop_member = oe.test_drop_member; ctx->test_no_morton = oe.test_no_morton; ctx->test_large_groups = oe.test_large_groups; }
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&ctx->d_w), n_weights * sizeof(float));
-    if (e == hipSuccess) e = hipMemcpy(ctx->d_w, ctx->w.data(), n_weights * sizeof(float), hipMemcpyHostToDevice);
-    {
+    return create_ctx("ifd_create", IFD_MODEL_CONVONET, device, [&](ifd_ctx* ctx) {
+        ctx->cfg = *cfg;
+        ctx->w.assign(weights_host, weights_host + n_weights);
+        ctx->dc.sdiv = (float)(1.0 + (double)cfg->padding + 10e-6);
+        ctx->dc.uclamp = (float)(1.0 - 10e-6);
+        const float* w = ctx->w.data();
+        hipError_t e = upload(ctx->d_dec_img, build_dec_image(w));
+        if (e == hipSuccess) e = upload(ctx->d_dec_img_opt, build_dec_image(w, true));
+        if (e == hipSuccess) e = upload(ctx->d_dec_img_bf, build_dec_image_bf(w));
+        if (e == hipSuccess) e = alloc_counters(ctx);
+        if (e == hipSuccess) e = upload(ctx->d_w, ctx->w);
         const WeightMap& m = wmap();
         EncPointOffsets& o = ctx->eo;
         o.pos_w = (int)m.enc_pos_w; o.pos_b = (int)m.enc_pos_b; o.fcc_w = (int)m.enc_fcc_w; o.fcc_b = (int)m.enc_fcc_b;
@@ -550,75 +548,36 @@ ifd_ctx* ifd_create(const float* weights_host, size_t n_weights, const ifd_confi
             o.fc1_w[i] = (int)m.enc_fc1_w[i]; o.fc1_b[i] = (int)m.enc_fc1_b[i];
             o.sc_w[i] = (int)m.enc_sc_w[i];
         }
-    }
-    if (e == hipSuccess) {
-        UNetPack P = pack_unet(ctx->w.data());
-        e = hipMalloc(reinterpret_cast<void**>(&ctx->d_unet), P.data.size() * sizeof(float));
-        if (e == hipSuccess) e = hipMemcpy(ctx->d_unet, P.data.data(), P.data.size() * sizeof(float), hipMemcpyHostToDevice);
-        const float* d = ctx->d_unet;
-        UNetWeights& u = ctx->uw;
-        for (int i = 0; i < 4; ++i)
-            for (int j = 0; j < 2; ++j) { u.down_w[i][j] = d + P.down_w[i][j]; u.down_b[i][j] = d + P.down_b[i][j]; u.down_u[i][j] = d + P.down_u[i][j]; }
-        for (int i = 0; i < 3; ++i) {
-            u.up_t_w[i] = d + P.up_t_w[i]; u.up_t_b[i] = d + P.up_t_b[i];
-            for (int j = 0; j < 2; ++j) { u.up_w[i][j] = d + P.up_w[i][j]; u.up_b[i][j] = d + P.up_b[i][j]; u.up_u[i][j] = d + P.up_u[i][j]; }
+        if (e == hipSuccess) {
+            UNetPack P = pack_unet(w);
+            e = upload(ctx->d_unet, P.data);
+            const float* d = ctx->d_unet.get<float>();
+            UNetWeights& u = ctx->uw;
+            for (int i = 0; i < 4; ++i)
+                for (int j = 0; j < 2; ++j) { u.down_w[i][j] = d + P.down_w[i][j]; u.down_b[i][j] = d + P.down_b[i][j]; u.down_u[i][j] = d + P.down_u[i][j]; }
+            for (int i = 0; i < 3; ++i) {
+                u.up_t_w[i] = d + P.up_t_w[i]; u.up_t_b[i] = d + P.up_t_b[i];
+                for (int j = 0; j < 2; ++j) { u.up_w[i][j] = d + P.up_w[i][j]; u.up_b[i][j] = d + P.up_b[i][j]; u.up_u[i][j] = d + P.up_u[i][j]; }
+            }
+            u.fin_w = d + P.fin_w; u.fin_b = d + P.fin_b;
         }
-        u.fin_w = d + P.fin_w; u.fin_b = d + P.fin_b;
-    }
-    if (e == hipSuccess) {
-        std::vector<float> img((size_t)enc_image_floats());
-        build_enc_image(ctx->w.data(), ctx->eo, img.data());
-        e = hipMalloc(reinterpret_cast<void**>(&ctx->d_enc_img), img.size() * sizeof(float));
-        if (e == hipSuccess) e = hipMemcpy(ctx->d_enc_img, img.data(), img.size() * sizeof(float), hipMemcpyHostToDevice);
-    }
-    if (e == hipSuccess) e = configure_encoder_kernels();
-    if (e == hipSuccess) e = configure_unet_kernels();
-    if (e == hipSuccess) e = configure_prep_kernels();
-    if (e == hipSuccess) e = configure_optimize_kernels();
-    if (e == hipSuccess) e = configure_decode_bf_kernels();
-    if (e != hipSuccess) {
-        g_create_error = std::string("ifd_create: ") + hipGetErrorString(e);
-        if (ctx->d_dec_img) (void)hipFree(ctx->d_dec_img);
-        if (ctx->d_dec_img_opt) (void)hipFree(ctx->d_dec_img_opt);
-        if (ctx->d_dec_img_bf) (void)hipFree(ctx->d_dec_img_bf);
-        if (ctx->d_counters) (void)hipFree(ctx->d_counters);
-        if (ctx->d_w) (void)hipFree(ctx->d_w);
-        if (ctx->d_unet) (void)hipFree(ctx->d_unet);
-        if (ctx->d_enc_img) (void)hipFree(ctx->d_enc_img);
-        delete ctx;
-        return nullptr;
-    }
-    return ctx;
+        if (e == hipSuccess) {
+            std::vector<float> img((size_t)enc_image_floats());
+            build_enc_image(w, ctx->eo, img.data());
+            e = upload(ctx->d_enc_img, img);
+        }
+        if (e == hipSuccess) e = configure_encoder_kernels();
+        if (e == hipSuccess) e = configure_unet_kernels();
+        if (e == hipSuccess) e = configure_prep_kernels();
+        if (e == hipSuccess) e = configure_optimize_kernels();
+        if (e == hipSuccess) e = configure_decode_bf_kernels();
+        return e;
+    });
 }
 
 void ifd_destroy(ifd_ctx* ctx) {
     if (!ctx) return;
     DeviceGuard guard(ctx);
-    if (ctx->d_dec_img) (void)hipFree(ctx->d_dec_img);
-    if (ctx->d_dec_img_opt) (void)hipFree(ctx->d_dec_img_opt);
-    if (ctx->d_dec_img_bf) (void)hipFree(ctx->d_dec_img_bf);
-    if (ctx->ws) (void)hipFree(ctx->ws);
-    if (ctx->adam_tab) (void)hipFree(ctx->adam_tab);
-    if (ctx->d_counters) (void)hipFree(ctx->d_counters);
-    if (ctx->d_status_out) (void)hipFree(ctx->d_status_out);
-    if (ctx->d_w) (void)hipFree(ctx->d_w);
-    if (ctx->d_unet) (void)hipFree(ctx->d_unet);
-    if (ctx->d_enc_img) (void)hipFree(ctx->d_enc_img);
-    if (ctx->ws_enc) (void)hipFree(ctx->ws_enc);
-    if (ctx->ws_fold) (void)hipFree(ctx->ws_fold);
-    if (ctx->d_onet_img) (void)hipFree(ctx->d_onet_img);
-    if (ctx->d_onet_img_bf) (void)hipFree(ctx->d_onet_img_bf);
-    if (ctx->d_onet_small) (void)hipFree(ctx->d_onet_small);
-    if (ctx->ws_mesh) (void)hipFree(ctx->ws_mesh);
-    if (ctx->h_mesh_counts) (void)hipHostFree(ctx->h_mesh_counts);
-    for (hipEvent_t ev : ctx->mesh_ev) if (ev) (void)hipEventDestroy(ev);
-    for (hipStream_t st : ctx->large_side) if (st) (void)hipStreamDestroy(st);
-    for (hipEvent_t ev : ctx->large_join) if (ev) (void)hipEventDestroy(ev);
-    if (ctx->large_fork) (void)hipEventDestroy(ctx->large_fork);
-    if (ctx->d_punet) (void)hipFree(ctx->d_punet);
-    if (ctx->ws_dup) (void)hipFree(ctx->ws_dup);
-    if (ctx->d_cls) (void)hipFree(ctx->d_cls);
-    if (ctx->d_cls_grad) (void)hipFree(ctx->d_cls_grad);
     delete ctx;
 }
 
@@ -658,7 +617,7 @@ int ifd_encode_points(ifd_ctx* ctx, const float* sel, const int32_t* t_per_cloud
     if (!sel || !planes_pre || B < 1 || Tmax < 1 || Tmax > 1024)
         return fail(ctx, IFD_ERR_ARG, "ifd_encode_points: bad argument (1 <= Tmax <= 1024)");
     hipStream_t s = static_cast<hipStream_t>(stream);
-    hipError_t e = launch_encode_points(ctx->d_w, ctx->eo, ctx->d_enc_img, sel, t_per_cloud, B, Tmax, planes_pre, c_points, ctx->dc, s);
+    hipError_t e = launch_encode_points(ctx->d_w.get<float>(), ctx->eo, ctx->d_enc_img.get<float>(), sel, t_per_cloud, B, Tmax, planes_pre, c_points, ctx->dc, s);
     return e == hipSuccess ? IFD_OK : fail(ctx, IFD_ERR_HIP, "ifd_encode_points", e);
 }
 
@@ -667,9 +626,9 @@ int ifd_unet(ifd_ctx* ctx, const float* planes_pre, int B, float* planes, void* 
     IFD_ON_CTX_DEVICE(ctx);
     if (ctx->model != IFD_MODEL_CONVONET) return fail(ctx, IFD_ERR_ARG, "ifd_unet: not a ConvONet context");
     if (!planes_pre || !planes || B < 1) return fail(ctx, IFD_ERR_ARG, "ifd_unet: bad argument");
-    hipError_t e = ensure_buf(&ctx->ws_enc, &ctx->ws_enc_bytes, unet_workspace_floats(3 * B) * sizeof(float));
+    hipError_t e = ctx->ws_enc.grow(unet_workspace_floats(3 * B) * sizeof(float));
     if (e != hipSuccess) return fail(ctx, IFD_ERR_NOMEM, "ifd_unet workspace", e);
-    e = launch_unet(ctx->uw, planes_pre, planes, static_cast<float*>(ctx->ws_enc), 3 * B, static_cast<hipStream_t>(stream));
+    e = launch_unet(ctx->uw, planes_pre, planes, ctx->ws_enc.get<float>(), 3 * B, static_cast<hipStream_t>(stream));
     return e == hipSuccess ? IFD_OK : fail(ctx, IFD_ERR_HIP, "ifd_unet launch", e);
 }
 
@@ -682,11 +641,11 @@ int ifd_encode_planes(ifd_ctx* ctx, const float* sel, const int32_t* t_per_cloud
         return fail(ctx, IFD_ERR_ARG, "ifd_encode_planes: bad argument (1 <= Tmax <= 1024)");
     // scratch = [pre-U-Net planes | U-Net activations]
     const size_t pre_floats = (size_t)B * CLOUD_PLANE_FLOATS;
-    hipError_t e = ensure_buf(&ctx->ws_enc, &ctx->ws_enc_bytes, (pre_floats + unet_workspace_floats(3 * B)) * sizeof(float));
+    hipError_t e = ctx->ws_enc.grow((pre_floats + unet_workspace_floats(3 * B)) * sizeof(float));
     if (e != hipSuccess) return fail(ctx, IFD_ERR_NOMEM, "ifd_encode_planes workspace", e);
     hipStream_t s = static_cast<hipStream_t>(stream);
-    float* pre = static_cast<float*>(ctx->ws_enc);
-    e = launch_encode_points(ctx->d_w, ctx->eo, ctx->d_enc_img, sel, t_per_cloud, B, Tmax, pre, nullptr, ctx->dc, s);
+    float* pre = ctx->ws_enc.get<float>();
+    e = launch_encode_points(ctx->d_w.get<float>(), ctx->eo, ctx->d_enc_img.get<float>(), sel, t_per_cloud, B, Tmax, pre, nullptr, ctx->dc, s);
     if (e == hipSuccess) e = launch_unet(ctx->uw, pre, planes, pre + pre_floats, 3 * B, s);
     return e == hipSuccess ? IFD_OK : fail(ctx, IFD_ERR_HIP, "ifd_encode_planes", e);
 }
@@ -715,15 +674,15 @@ hipError_t large_optimize_in_groups(ifd_ctx* ctx, const float* dec_img, const fl
     const int G = large_groups_of(ctx, B, K <= LARGE_LDS_MAXK && a.knn_scan_every_step == 0);
     const int per = (B + G - 1) / G;
     const size_t slice = (large_ws_bytes(per, K, own) + 255) & ~(size_t)255;
-    hipError_t e = ensure_ws(ctx, slice * G);
+    hipError_t e = ctx->ws.grow(slice * G);
     if (e != hipSuccess) return e;
     if (G > 1) {
-        if (!ctx->large_fork && (e = hipEventCreateWithFlags(&ctx->large_fork, hipEventDisableTiming)) != hipSuccess) return e;
+        if ((e = ctx->large_fork.ensure()) != hipSuccess) return e;
         for (int g = 1; g < G; ++g) {
-            if (!ctx->large_side[g - 1] && (e = hipStreamCreateWithFlags(&ctx->large_side[g - 1], hipStreamNonBlocking)) != hipSuccess) return e;
-            if (!ctx->large_join[g - 1] && (e = hipEventCreateWithFlags(&ctx->large_join[g - 1], hipEventDisableTiming)) != hipSuccess) return e;
+            if ((e = ctx->large_side[g - 1].ensure()) != hipSuccess) return e;
+            if ((e = ctx->large_join[g - 1].ensure()) != hipSuccess) return e;
         }
-        if ((e = hipEventRecord(ctx->large_fork, s)) != hipSuccess) return e;
+        if ((e = hipEventRecord(ctx->large_fork.get(), s)) != hipSuccess) return e;
     }
     struct Group { int g0, Bg, parts; char* G; float *p, *m, *v, *loss; const int32_t* lb; const float* planes; void *f_ws, *list_ws; hipStream_t s; };
     Group gr[LARGE_MAX_GROUPS];
@@ -737,13 +696,13 @@ hipError_t large_optimize_in_groups(ifd_ctx* ctx, const float* dec_img, const fl
         if (q.Bg <= 0) break;
         ++n_groups;
         const size_t o3 = (size_t)q.g0 * K * 3;
-        q.s = g == 0 ? s : ctx->large_side[g - 1];
-        q.G = static_cast<char*>(ctx->ws) + slice * g;
+        q.s = g == 0 ? s : ctx->large_side[g - 1].get();
+        q.G = ctx->ws.get<char>() + slice * g;
         q.p = p + o3; q.planes = planes + (size_t)q.g0 * CLOUD_PLANE_FLOATS;
         q.loss = loss ? loss + 2 * (size_t)q.g0 : nullptr; q.lb = lbpc ? lbpc + q.g0 : nullptr;
         // one workgroup fills a CU; with fewer clouds than CUs a cloud's tiles are shared out over `parts` workgroups
         q.parts = q.Bg >= n_cu ? 1 : std::min((ntiles + 7) / 8, std::max(1, n_cu / q.Bg));
-        if (g > 0) note(hipStreamWaitEvent(q.s, ctx->large_fork, 0));
+        if (g > 0) note(hipStreamWaitEvent(q.s, ctx->large_fork.get(), 0));
         note(large_f_prepare(q.G, q.Bg, K, own, &q.f_ws, q.s));
         q.list_ws = large_list_ws(q.G, q.Bg, K, own);
         if (own) {                                        // own moments behind G (large_ws_bytes), zeroed
@@ -760,16 +719,16 @@ hipError_t large_optimize_in_groups(ifd_ctx* ctx, const float* dec_img, const fl
             Group& q = gr[g];
             note(launch_large_occupancy(a.precision, dec_img, q.planes, q.p, q.Bg, q.parts, K, q.lb, a.loss_batch, a.threshold,
                                         (last && q.loss != nullptr) ? 1 : 0, q.G, a.dc, q.s));
-            note(launch_large_step(q.p, q.m, q.v, q.G, q.Bg, K, static_cast<const float*>(ctx->adam_tab), step, q.lb, a, last ? q.loss : nullptr,
-                                   q.f_ws, q.list_ws, ctx->d_counters, q.s));
+            note(launch_large_step(q.p, q.m, q.v, q.G, q.Bg, K, ctx->adam_tab.get<float>(), step, q.lb, a, last ? q.loss : nullptr,
+                                   q.f_ws, q.list_ws, ctx->counters(), q.s));
         }
     }
     for (int g = 0; g < n_groups; ++g) {
         Group& q = gr[g];
         if (a.normalize && first == hipSuccess) note(launch_large_normalize(q.p, q.Bg, K, q.s));
         if (g > 0) {                                      // (joined even after a failed launch: the caller's stream must not run ahead of a side stream)
-            hipError_t x = hipEventRecord(ctx->large_join[g - 1], q.s);
-            if (x == hipSuccess) x = hipStreamWaitEvent(s, ctx->large_join[g - 1], 0);
+            hipError_t x = hipEventRecord(ctx->large_join[g - 1].get(), q.s);
+            if (x == hipSuccess) x = hipStreamWaitEvent(s, ctx->large_join[g - 1].get(), 0);
             note(x);
         }
     }
@@ -786,8 +745,8 @@ int ifd_decode_ex(ifd_ctx* ctx, const float* planes, const float* p, int B, int 
     if (!planes || !p || !logits || B < 1 || K < 1) return fail(ctx, IFD_ERR_ARG, "ifd_decode: bad argument");
     if (precision < 0 || precision > 2) return fail(ctx, IFD_ERR_ARG, "ifd_decode_ex: precision must be 0 (f32 MFMA), 1 (bf16x6) or 2 (bf16x3)");
     hipStream_t s = static_cast<hipStream_t>(stream);
-    hipError_t e = precision == 0 ? launch_decode(ctx->d_dec_img, planes, p, B, K, logits, dlogit_dp, ctx->dc, s)
-                                  : launch_decode_bf(precision, ctx->d_dec_img_bf, planes, p, B, K, logits, dlogit_dp, ctx->dc, ctx->n_cu, s);
+    hipError_t e = precision == 0 ? launch_decode(ctx->d_dec_img.get<float>(), planes, p, B, K, logits, dlogit_dp, ctx->dc, s)
+                                  : launch_decode_bf(precision, ctx->d_dec_img_bf.get<float>(), planes, p, B, K, logits, dlogit_dp, ctx->dc, ctx->n_cu, s);
     return e == hipSuccess ? IFD_OK : fail(ctx, IFD_ERR_HIP, "ifd_decode launch", e);
 }
 
@@ -805,9 +764,9 @@ int ifd_repulsion(ifd_ctx* ctx, const float* p, int B, int K, float* loss, float
     if (K <= MAXK) {
         e = launch_repulsion(p, B, K, loss, grad, knn_idx, 0.07f, 0.03f, 1e-12f, static_cast<hipStream_t>(stream));
     } else {
-        e = ensure_ws(ctx, large_f_bytes(B, K));          // (clouds beyond 4096 points: accumulators in the context's workspace)
+        e = ctx->ws.grow(large_f_bytes(B, K));          // (clouds beyond 4096 points: accumulators in the context's workspace)
         if (e == hipSuccess)
-            e = launch_large_repulsion(p, B, K, loss, grad, knn_idx, 0.07f, 0.03f, 1e-12f, large_f_bytes(B, K) ? ctx->ws : nullptr,
+            e = launch_large_repulsion(p, B, K, loss, grad, knn_idx, 0.07f, 0.03f, 1e-12f, large_f_bytes(B, K) ? ctx->ws.get() : nullptr,
                                        static_cast<hipStream_t>(stream));
     }
     return e == hipSuccess ? IFD_OK : fail(ctx, IFD_ERR_HIP, "ifd_repulsion launch", e);
@@ -840,20 +799,20 @@ int ifd_optimize(ifd_ctx* ctx, const float* planes, float* p, int B, int K, cons
         return fail(ctx, IFD_ERR_ARG, "ifd_optimize: precision must be 0 (f32 MFMA), 1 (bf16x6) or 2 (bf16x3)");
     a.precision = prm->precision;
     const bool large = K > MAXK;              // more points than one CU's LDS holds: two launches per step (optimize.hip)
-    hipError_t e = large ? hipSuccess : ensure_ws(ctx, optimize_ws_bytes(B));          // (large: per stream group, run_large_in_groups)
-    if (e == hipSuccess) e = ensure_buf(&ctx->adam_tab, &ctx->adam_bytes, (size_t)(prm->steps > 0 ? prm->steps : 1) * 2 * sizeof(float));
+    hipError_t e = large ? hipSuccess : ctx->ws.grow(optimize_ws_bytes(B));          // (large: per stream group, run_large_in_groups)
+    if (e == hipSuccess) e = ctx->adam_tab.grow((size_t)(prm->steps > 0 ? prm->steps : 1) * 2 * sizeof(float));
     if (e != hipSuccess) return fail(ctx, IFD_ERR_NOMEM, "ifd_optimize workspace", e);
-    e = hipMemsetAsync(ctx->d_counters, 0, N_COUNTERS_DEV * sizeof(unsigned long long), static_cast<hipStream_t>(stream));
-    if (e == hipSuccess) e = hipMemsetAsync(ctx->d_counters + STATUS_TIMEOUT_CUR, 0, sizeof(unsigned long long), static_cast<hipStream_t>(stream));
-    if (e == hipSuccess) e = launch_adam_table(static_cast<float*>(ctx->adam_tab), a.t0, a.steps, a.lr, static_cast<hipStream_t>(stream));
+    e = hipMemsetAsync(ctx->counters(), 0, N_COUNTERS_DEV * sizeof(unsigned long long), static_cast<hipStream_t>(stream));
+    if (e == hipSuccess) e = hipMemsetAsync(ctx->counters() + STATUS_TIMEOUT_CUR, 0, sizeof(unsigned long long), static_cast<hipStream_t>(stream));
+    if (e == hipSuccess) e = launch_adam_table(ctx->adam_tab.get<float>(), a.t0, a.steps, a.lr, static_cast<hipStream_t>(stream));
     if (e != hipSuccess) return fail(ctx, IFD_ERR_HIP, "ifd_optimize memset / Adam table", e);
     if (large) {
-        e = large_optimize_in_groups(ctx, a.precision != 0 ? ctx->d_dec_img_bf : ctx->d_dec_img_opt, planes, p, m, v, loss, loss_batch_per_cloud,
+        e = large_optimize_in_groups(ctx, a.precision != 0 ? ctx->d_dec_img_bf.get<float>() : ctx->d_dec_img_opt.get<float>(), planes, p, m, v, loss, loss_batch_per_cloud,
                                      B, K, a, static_cast<hipStream_t>(stream));
         return e == hipSuccess ? IFD_OK : fail(ctx, IFD_ERR_HIP, "ifd_optimize launch (large clouds)", e);
     }
-    e = launch_optimize(a.precision != 0 ? ctx->d_dec_img_bf : ctx->d_dec_img_opt, planes, p, m, v, loss, loss_batch_per_cloud, ctx->ws, ctx->d_counters,
-                        static_cast<const float*>(ctx->adam_tab), B, K, a, prm->split, ctx->n_cu, static_cast<hipStream_t>(stream));
+    e = launch_optimize(a.precision != 0 ? ctx->d_dec_img_bf.get<float>() : ctx->d_dec_img_opt.get<float>(), planes, p, m, v, loss, loss_batch_per_cloud, ctx->ws.get(), ctx->counters(),
+                        ctx->adam_tab.get<float>(), B, K, a, prm->split, ctx->n_cu, static_cast<hipStream_t>(stream));
     return e == hipSuccess ? IFD_OK : fail(ctx, IFD_ERR_HIP, "ifd_optimize launch", e);
 }
 
@@ -861,7 +820,7 @@ int ifd_get_counters(ifd_ctx* ctx, uint64_t* out_host, int n) {
     if (!ctx || !out_host || n < 1) return IFD_ERR_ARG;
     IFD_ON_CTX_DEVICE(ctx);
     unsigned long long tmp[N_COUNTERS_ALLOC] = {0};
-    hipError_t e = hipMemcpy(tmp, ctx->d_counters, sizeof(tmp), hipMemcpyDeviceToHost);   // synchronises
+    hipError_t e = hipMemcpy(tmp, ctx->counters(), sizeof(tmp), hipMemcpyDeviceToHost);   // synchronises
     if (e != hipSuccess) return fail(ctx, IFD_ERR_HIP, "ifd_get_counters", e);
     if (ctx->model == IFD_MODEL_ONET) {   // host-side tallies of the last ifd_onet_mesh_sample
         tmp[8] = ctx->mesh_points;
@@ -879,9 +838,9 @@ int ifd_optimize_status(ifd_ctx* ctx, void* stream) {
     // read-and-reset in one atomic exchange per word: an event raised by a launch on another stream between a copy and a
     // separate memset would have been cleared unreported (round-4 advisor)
     unsigned long long st[2] = {0, 0};
-    hipLaunchKernelGGL(status_take_kernel, dim3(1), dim3(64), 0, s, ctx->d_counters + STATUS_OVERFLOW, ctx->d_status_out);
+    hipLaunchKernelGGL(status_take_kernel, dim3(1), dim3(64), 0, s, ctx->counters() + STATUS_OVERFLOW, ctx->d_status_out.get<unsigned long long>());
     hipError_t e = hipGetLastError();
-    if (e == hipSuccess) e = hipMemcpyAsync(st, ctx->d_status_out, sizeof(st), hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(st, ctx->d_status_out.get<unsigned long long>(), sizeof(st), hipMemcpyDeviceToHost, s);
     if (e == hipSuccess) e = hipStreamSynchronize(s);
     if (e != hipSuccess) return fail(ctx, IFD_ERR_HIP, "ifd_optimize_status", e);
     if (st[0] == 0 && st[1] == 0) return IFD_OK;
@@ -911,99 +870,77 @@ int ifd_normalize_unit_sphere(ifd_ctx* ctx, float* p, int B, int K, void* stream
 size_t ifd_onet_weight_count(void) { return omap().host_total; }
 
 ifd_ctx* ifd_onet_create(const float* weights_host, size_t n_weights, int device) {
-    g_create_error.clear();
     const OnetMap& m = omap();
     if (!weights_host) { g_create_error = "ifd_onet_create: NULL argument"; return nullptr; }
     if (n_weights != m.host_total) {
         g_create_error = "ifd_onet_create: expected " + std::to_string(m.host_total) + " weights, got " + std::to_string(n_weights);
         return nullptr;
     }
-    ifd_ctx* ctx = new (std::nothrow) ifd_ctx();
-    if (!ctx) { g_create_error = "ifd_onet_create: out of host memory"; return nullptr; }
-    ctx->device = device;
-    {
-        int n_cu = 0;
-        if (hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, device) == hipSuccess && n_cu > 0) ctx->n_cu = n_cu;
-    }
-    ctx->model = IFD_MODEL_ONET;
-    ctx->w.assign(weights_host, weights_host + n_weights);
-    const float* w = ctx->w.data();
-    // padded device copy
-    std::vector<float> dev(m.dev_total, 0.f);
-    auto put = [&](const OnetTensor& t) { std::memcpy(dev.data() + t.dev_off, w + t.host_off, t.n * sizeof(float)); return (int)t.dev_off; };
-    put(m.fc_p_w); put(m.fc_p_b);
-    OnetDecOffsets& od = ctx->od;
-    for (int i = 0; i < 11; ++i) {
-        od.cbn_gamma_w[i] = put(m.cbn[i][0]); od.cbn_gamma_b[i] = put(m.cbn[i][1]);
-        od.cbn_beta_w[i] = put(m.cbn[i][2]); od.cbn_beta_b[i] = put(m.cbn[i][3]);
-        od.cbn_mean[i] = put(m.cbn[i][4]); od.cbn_var[i] = put(m.cbn[i][5]);
-    }
-    for (int i = 0; i < 5; ++i) { put(m.fc0_w[i]); od.fc0_b[i] = put(m.fc0_b[i]); put(m.fc1_w[i]); put(m.fc1_b[i]); }
-    put(m.out_w); put(m.out_b);
-    OnetEncOffsets& oe = ctx->oe;
-    oe.pos_w = put(m.pos_w); oe.pos_b = put(m.pos_b);
-    for (int i = 0; i < 5; ++i) {
-        oe.fc0_w[i] = put(m.e_fc0_w[i]); oe.fc0_b[i] = put(m.e_fc0_b[i]);
-        oe.fc1_w[i] = put(m.e_fc1_w[i]); oe.fc1_b[i] = put(m.e_fc1_b[i]);
-        oe.sc_w[i] = put(m.e_sc_w[i]);
-    }
-    oe.fcc_w = put(m.fcc_w); oe.fcc_b = put(m.fcc_b);
-    // decoder layer images: forward fc_0 / fc_1 of blocks 0..4, then the transposes in backward order
-    const size_t L = (size_t)ONET_H * ONET_H;
-    std::vector<float> img(20 * L);
-    for (int i = 0; i < 5; ++i) {
-        onet_fragment_image(w + m.fc0_w[i].host_off, false, img.data() + (size_t)(2 * i) * L);
-        onet_fragment_image(w + m.fc1_w[i].host_off, false, img.data() + (size_t)(2 * i + 1) * L);
-        onet_fragment_image(w + m.fc1_w[i].host_off, true, img.data() + (size_t)(10 + 2 * (4 - i)) * L);
-        onet_fragment_image(w + m.fc0_w[i].host_off, true, img.data() + (size_t)(11 + 2 * (4 - i)) * L);
-    }
-    // the bf16 piece images of the same twenty layers (W0^T output-half-major), packed into a float vector for the upload helper
-    const size_t LB = (size_t)16 * (8 * 3 * 64 * 8);              // uint16 per layer image
-    std::vector<float> img_bf(20 * LB / 2);
-    {
-        uint16_t* ib = reinterpret_cast<uint16_t*>(img_bf.data());
+    return create_ctx("ifd_onet_create", IFD_MODEL_ONET, device, [&](ifd_ctx* ctx) {
+        ctx->w.assign(weights_host, weights_host + n_weights);
+        const float* w = ctx->w.data();
+        // padded device copy
+        std::vector<float> dev(m.dev_total, 0.f);
+        auto put = [&](const OnetTensor& t) { std::memcpy(dev.data() + t.dev_off, w + t.host_off, t.n * sizeof(float)); return (int)t.dev_off; };
+        put(m.fc_p_w); put(m.fc_p_b);
+        OnetDecOffsets& od = ctx->od;
+        for (int i = 0; i < 11; ++i) {
+            od.cbn_gamma_w[i] = put(m.cbn[i][0]); od.cbn_gamma_b[i] = put(m.cbn[i][1]);
+            od.cbn_beta_w[i] = put(m.cbn[i][2]); od.cbn_beta_b[i] = put(m.cbn[i][3]);
+            od.cbn_mean[i] = put(m.cbn[i][4]); od.cbn_var[i] = put(m.cbn[i][5]);
+        }
+        for (int i = 0; i < 5; ++i) { put(m.fc0_w[i]); od.fc0_b[i] = put(m.fc0_b[i]); put(m.fc1_w[i]); put(m.fc1_b[i]); }
+        put(m.out_w); put(m.out_b);
+        OnetEncOffsets& oe = ctx->oe;
+        oe.pos_w = put(m.pos_w); oe.pos_b = put(m.pos_b);
         for (int i = 0; i < 5; ++i) {
+            oe.fc0_w[i] = put(m.e_fc0_w[i]); oe.fc0_b[i] = put(m.e_fc0_b[i]);
+            oe.fc1_w[i] = put(m.e_fc1_w[i]); oe.fc1_b[i] = put(m.e_fc1_b[i]);
+            oe.sc_w[i] = put(m.e_sc_w[i]);
+        }
+        oe.fcc_w = put(m.fcc_w); oe.fcc_b = put(m.fcc_b);
+        // decoder layer images: forward fc_0 / fc_1 of blocks 0..4, then the transposes in backward order
+        const size_t L = (size_t)ONET_H * ONET_H;
+        std::vector<float> img(20 * L);
+        for (int i = 0; i < 5; ++i) {
+            onet_fragment_image(w + m.fc0_w[i].host_off, false, img.data() + (size_t)(2 * i) * L);
+            onet_fragment_image(w + m.fc1_w[i].host_off, false, img.data() + (size_t)(2 * i + 1) * L);
+            onet_fragment_image(w + m.fc1_w[i].host_off, true, img.data() + (size_t)(10 + 2 * (4 - i)) * L);
+            onet_fragment_image(w + m.fc0_w[i].host_off, true, img.data() + (size_t)(11 + 2 * (4 - i)) * L);
+        }
+            // the bf16 piece images of the same twenty layers (W0^T output-half-major)
+        const size_t LB = (size_t)16 * (8 * 3 * 64 * 8);              // uint16 per layer image
+        std::vector<uint16_t> img_bf(20 * LB);
+        for (int i = 0; i < 5; ++i) {
+            uint16_t* ib = img_bf.data();
             onet_fragment_image_bf(w + m.fc0_w[i].host_off, false, false, ib + (size_t)(2 * i) * LB);
             onet_fragment_image_bf(w + m.fc1_w[i].host_off, false, false, ib + (size_t)(2 * i + 1) * LB);
             onet_fragment_image_bf(w + m.fc1_w[i].host_off, true, false, ib + (size_t)(10 + 2 * (4 - i)) * LB);
             onet_fragment_image_bf(w + m.fc0_w[i].host_off, true, true, ib + (size_t)(11 + 2 * (4 - i)) * LB);
         }
-    }
-    // small parameters, in the LDS order of onet.hip: fc_p [256][4] | fc_1 biases [5][256] | fc_out w [256] | b
-    std::vector<float> small((size_t)onet_small_floats(), 0.f);
-    for (int c = 0; c < ONET_H; ++c) {
-        for (int a = 0; a < 3; ++a) small[c * 4 + a] = w[m.fc_p_w.host_off + c * 3 + a];
-        small[c * 4 + 3] = w[m.fc_p_b.host_off + c];
-    }
-    for (int i = 0; i < 5; ++i)
-        for (int c = 0; c < ONET_H; ++c) small[ONET_H * 4 + i * ONET_H + c] = w[m.fc1_b[i].host_off + c];
-    for (int c = 0; c < ONET_H; ++c) small[ONET_H * 4 + 5 * ONET_H + c] = w[m.out_w.host_off + c];
-    small[ONET_H * 4 + 5 * ONET_H + ONET_H] = w[m.out_b.host_off];
+        // small parameters, in the LDS order of onet.hip: fc_p [256][4] | fc_1 biases [5][256] | fc_out w [256] | b
+        std::vector<float> small((size_t)onet_small_floats(), 0.f);
+        for (int c = 0; c < ONET_H; ++c) {
+            for (int a = 0; a < 3; ++a) small[c * 4 + a] = w[m.fc_p_w.host_off + c * 3 + a];
+            small[c * 4 + 3] = w[m.fc_p_b.host_off + c];
+        }
+        for (int i = 0; i < 5; ++i)
+            for (int c = 0; c < ONET_H; ++c) small[ONET_H * 4 + i * ONET_H + c] = w[m.fc1_b[i].host_off + c];
+        for (int c = 0; c < ONET_H; ++c) small[ONET_H * 4 + 5 * ONET_H + c] = w[m.out_w.host_off + c];
+        small[ONET_H * 4 + 5 * ONET_H + ONET_H] = w[m.out_b.host_off];
 
-    hipError_t e = hipSetDevice(device);
-    auto upload = [&](float** dst, const std::vector<float>& src) {
-        if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(dst), src.size() * sizeof(float));
-        if (e == hipSuccess) e = hipMemcpy(*dst, src.data(), src.size() * sizeof(float), hipMemcpyHostToDevice);
-    };
-    upload(&ctx->d_w, dev);
-    upload(&ctx->d_onet_img, img);
-    upload(&ctx->d_onet_img_bf, img_bf);
-    upload(&ctx->d_onet_small, small);
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&ctx->d_counters), N_COUNTERS_ALLOC * sizeof(unsigned long long));
-    if (e == hipSuccess) e = hipMemset(ctx->d_counters, 0, N_COUNTERS_ALLOC * sizeof(unsigned long long));
-    if (e == hipSuccess && !ctx->d_status_out) e = hipMalloc(reinterpret_cast<void**>(&ctx->d_status_out), 2 * sizeof(unsigned long long));
-    { const OptEnv oe = read_opt_env(); ctx->coop_timeout_ticks = oe.coop_timeout_ticks; ctx->test_drop_member = oe.test_drop_member; ctx->test_no_morton = oe.test_no_morton; }
-    if (e == hipSuccess) e = configure_prep_kernels();
-    if (e == hipSuccess) e = configure_optimize_kernels();
-    if (e == hipSuccess) e = configure_onet_kernels();
-    if (e == hipSuccess) e = configure_onet_bf_kernels();
-    if (e == hipSuccess) e = mc_upload_table();
-    if (e != hipSuccess) {
-        g_create_error = std::string("ifd_onet_create: ") + hipGetErrorString(e);
-        ifd_destroy(ctx);
-        return nullptr;
-    }
-    return ctx;
+        hipError_t e = upload(ctx->d_w, dev);
+        if (e == hipSuccess) e = upload(ctx->d_onet_img, img);
+        if (e == hipSuccess) e = upload(ctx->d_onet_img_bf, img_bf);
+        if (e == hipSuccess) e = upload(ctx->d_onet_small, small);
+        if (e == hipSuccess) e = alloc_counters(ctx);
+        if (e == hipSuccess) e = configure_prep_kernels();
+        if (e == hipSuccess) e = configure_optimize_kernels();
+        if (e == hipSuccess) e = configure_onet_kernels();
+        if (e == hipSuccess) e = configure_onet_bf_kernels();
+        if (e == hipSuccess) e = mc_upload_table();
+        return e;
+    });
 }
 
 int ifd_onet_encode(ifd_ctx* ctx, const float* sel, const int32_t* t_per_cloud, int B, int Tmax, float* c, void* stream) {
@@ -1013,12 +950,12 @@ int ifd_onet_encode(ifd_ctx* ctx, const float* sel, const int32_t* t_per_cloud, 
     if (!sel || !c || B < 1 || Tmax < 1 || Tmax > 1024) return fail(ctx, IFD_ERR_ARG, "ifd_onet_encode: bad argument (1 <= Tmax <= 1024)");
     hipStream_t s = static_cast<hipStream_t>(stream);
     const int chunk = 256;                                     // clouds per pass: ~0.8 GB of activations at T = 300
-    hipError_t e = ensure_buf(&ctx->ws_enc, &ctx->ws_enc_bytes, onet_encode_ws_floats(B < chunk ? B : chunk, Tmax) * sizeof(float));
+    hipError_t e = ctx->ws_enc.grow(onet_encode_ws_floats(B < chunk ? B : chunk, Tmax) * sizeof(float));
     if (e != hipSuccess) return fail(ctx, IFD_ERR_NOMEM, "ifd_onet_encode workspace", e);
     for (int b0 = 0; b0 < B && e == hipSuccess; b0 += chunk) {
         const int nb = B - b0 < chunk ? B - b0 : chunk;
-        e = launch_onet_encode(ctx->d_w, ctx->oe, sel + (size_t)b0 * Tmax * 3, t_per_cloud ? t_per_cloud + b0 : nullptr, nb, Tmax,
-                               static_cast<float*>(ctx->ws_enc), c + (size_t)b0 * ONET_C, s);
+        e = launch_onet_encode(ctx->d_w.get<float>(), ctx->oe, sel + (size_t)b0 * Tmax * 3, t_per_cloud ? t_per_cloud + b0 : nullptr, nb, Tmax,
+                               ctx->ws_enc.get<float>(), c + (size_t)b0 * ONET_C, s);
     }
     return e == hipSuccess ? IFD_OK : fail(ctx, IFD_ERR_HIP, "ifd_onet_encode", e);
 }
@@ -1030,12 +967,12 @@ namespace {
 // an optimiser launch still reads its coefficients (round-5 advisor: it used to live at offset 0 of the encoder scratch).
 hipError_t onet_fold(ifd_ctx* ctx, const float* c, int B, hipStream_t s, float** ab_out) {
     const size_t per = (size_t)2 * ONET_NCBN * ONET_H;
-    hipError_t e = ensure_buf(&ctx->ws_fold, &ctx->ws_fold_bytes, 2 * per * B * sizeof(float));
+    hipError_t e = ctx->ws_fold.grow(2 * per * B * sizeof(float));
     if (e != hipSuccess) return e;
-    float* gb = static_cast<float*>(ctx->ws_fold);
+    float* gb = ctx->ws_fold.get<float>();
     float* ab = gb + per * B;
     *ab_out = ab;
-    return launch_onet_cbn(ctx->d_w, ctx->od, c, B, gb, ab, s);
+    return launch_onet_cbn(ctx->d_w.get<float>(), ctx->od, c, B, gb, ab, s);
 }
 }  // namespace
 
@@ -1050,8 +987,8 @@ int ifd_onet_decode_ex(ifd_ctx* ctx, const float* c, const float* p, int B, int 
     float* ab = nullptr;
     hipError_t e = onet_fold(ctx, c, B, s, &ab);
     if (e == hipSuccess)
-        e = precision == 0 ? launch_onet_decode(ctx->d_onet_img, ctx->d_onet_small, ab, p, B, K, logits, dlogit_dp, s)
-                           : launch_onet_decode_bf(precision, ctx->d_onet_img_bf, ctx->d_onet_small, ab, p, B, K, logits, dlogit_dp, s);
+        e = precision == 0 ? launch_onet_decode(ctx->d_onet_img.get<float>(), ctx->d_onet_small.get<float>(), ab, p, B, K, logits, dlogit_dp, s)
+                           : launch_onet_decode_bf(precision, ctx->d_onet_img_bf.get<float>(), ctx->d_onet_small.get<float>(), ab, p, B, K, logits, dlogit_dp, s);
     return e == hipSuccess ? IFD_OK : fail(ctx, IFD_ERR_HIP, "ifd_onet_decode", e);
 }
 
@@ -1082,25 +1019,25 @@ int ifd_onet_optimize(ifd_ctx* ctx, const float* c, float* p, int B, int K, cons
     a.test_drop_member = ctx->test_drop_member;
     hipStream_t s = static_cast<hipStream_t>(stream);
     const bool large = K > MAXK;              // more points than one CU's LDS holds: two launches per step (onet.hip)
-    hipError_t e = ensure_ws(ctx, large ? large_ws_bytes(B, K, m == nullptr) : knn_list_bytes(B));
-    if (e == hipSuccess) e = ensure_buf(&ctx->adam_tab, &ctx->adam_bytes, (size_t)(prm->steps > 0 ? prm->steps : 1) * 2 * sizeof(float));
+    hipError_t e = ctx->ws.grow(large ? large_ws_bytes(B, K, m == nullptr) : knn_list_bytes(B));
+    if (e == hipSuccess) e = ctx->adam_tab.grow((size_t)(prm->steps > 0 ? prm->steps : 1) * 2 * sizeof(float));
     if (e != hipSuccess) return fail(ctx, IFD_ERR_NOMEM, "ifd_onet_optimize workspace", e);
     float* ab = nullptr;
     e = onet_fold(ctx, c, B, s, &ab);
-    if (e == hipSuccess) e = hipMemsetAsync(ctx->d_counters, 0, N_COUNTERS_DEV * sizeof(unsigned long long), s);
-    if (e == hipSuccess) e = hipMemsetAsync(ctx->d_counters + STATUS_TIMEOUT_CUR, 0, sizeof(unsigned long long), s);
-    if (e == hipSuccess) e = launch_adam_table(static_cast<float*>(ctx->adam_tab), a.t0, a.steps, a.lr, s);
+    if (e == hipSuccess) e = hipMemsetAsync(ctx->counters(), 0, N_COUNTERS_DEV * sizeof(unsigned long long), s);
+    if (e == hipSuccess) e = hipMemsetAsync(ctx->counters() + STATUS_TIMEOUT_CUR, 0, sizeof(unsigned long long), s);
+    if (e == hipSuccess) e = launch_adam_table(ctx->adam_tab.get<float>(), a.t0, a.steps, a.lr, s);
     a.precision = prm->precision;
     if (e == hipSuccess && large)
-        e = launch_onet_large_optimize(prm->precision != 0 ? ctx->d_onet_img_bf : ctx->d_onet_img, ctx->d_onet_small, ab, p, m, v, loss,
-                                       loss_batch_per_cloud, ctx->ws, ctx->d_counters, static_cast<const float*>(ctx->adam_tab), B, K, a, s);
+        e = launch_onet_large_optimize(prm->precision != 0 ? ctx->d_onet_img_bf.get<float>() : ctx->d_onet_img.get<float>(), ctx->d_onet_small.get<float>(), ab, p, m, v, loss,
+                                       loss_batch_per_cloud, ctx->ws.get(), ctx->counters(), ctx->adam_tab.get<float>(), B, K, a, s);
     else if (e == hipSuccess && prm->precision != 0)
-        e = launch_onet_optimize_bf(prm->precision, ctx->d_onet_img_bf, ctx->d_onet_small, ab, p, m, v, loss, loss_batch_per_cloud,
-                                    static_cast<uint16_t*>(ctx->ws), ctx->d_counters, static_cast<const float*>(ctx->adam_tab), B, K,
+        e = launch_onet_optimize_bf(prm->precision, ctx->d_onet_img_bf.get<float>(), ctx->d_onet_small.get<float>(), ab, p, m, v, loss, loss_batch_per_cloud,
+                                    ctx->ws.get<uint16_t>(), ctx->counters(), ctx->adam_tab.get<float>(), B, K,
                                     a, s);
     else if (e == hipSuccess)
-        e = launch_onet_optimize(ctx->d_onet_img, ctx->d_onet_small, ab, p, m, v, loss, loss_batch_per_cloud,
-                                 static_cast<uint16_t*>(ctx->ws), ctx->d_counters, static_cast<const float*>(ctx->adam_tab), B, K,
+        e = launch_onet_optimize(ctx->d_onet_img.get<float>(), ctx->d_onet_small.get<float>(), ab, p, m, v, loss, loss_batch_per_cloud,
+                                 ctx->ws.get<uint16_t>(), ctx->counters(), ctx->adam_tab.get<float>(), B, K,
                                  a, s);
     return e == hipSuccess ? IFD_OK : fail(ctx, IFD_ERR_HIP, "ifd_onet_optimize", e);
 }
@@ -1124,6 +1061,24 @@ struct MeshWork {
     int* ntri;
 };
 
+// The mesh scratch of `chunk` clouds whose grid and queue sizes w.g holds: the arrays are [chunk][stride] each (struct-of-arrays,
+// every per-cloud stride rounded up to 16 bytes), the count / ntri / prev / plan words behind them.  Returns the bytes of the
+// arrays alone (at chunk = 1: the scratch one more cloud costs).
+size_t mesh_carve(Carve& c, MeshWork& w, int capT, int chunk) {
+    MiseGrid& g = w.g;
+    const int NC = g.P + 1, ncube = NC * NC * NC;
+    auto al = [](size_t n) { return (n + 15) & ~(size_t)15; };
+    g.val = c.take<float>(al((size_t)g.P3 * 4) * chunk); g.known = c.take<uint8_t>(al(g.P3) * chunk);
+    g.pend = c.take<uint8_t>(al(g.pend_stride) * chunk);
+    g.sub = c.take<uint8_t>(al(g.sub_total) * chunk); g.mix = c.take<uint8_t>(al(g.sub_total) * chunk);
+    g.list = c.take<int>(al((size_t)g.cap * 4) * chunk); w.cube_offs = c.take<int>(al((size_t)ncube * 4) * chunk);
+    w.tris = c.take<float>(al((size_t)capT * 36) * chunk); w.area = c.take<double>(al((size_t)capT * 8) * chunk);
+    const size_t arrays = c.bytes();
+    g.count = c.take<int>(al((size_t)chunk * 4)); w.ntri = c.take<int>(al((size_t)chunk * 4));
+    g.prev = c.take<int>(al((size_t)chunk * 4)); g.plan = c.take<int>(al((size_t)(chunk + 1) * 4));
+    return arrays;
+}
+
 // Lays the context's mesh workspace out for clouds of a res0 << depth grid with capT triangle slots each (grown on demand), and
 // makes sure the pinned landing slots of the queue lengths and their events exist.  `who` names the entry point in error texts.
 int mesh_work(ifd_ctx* ctx, const std::string& who, int res0, int depth, double threshold, int B, int capT, MeshWork& w) {
@@ -1140,45 +1095,21 @@ int mesh_work(ifd_ctx* ctx, const std::string& who, int res0, int depth, double 
     g.sub_total = (g.sub_total + 3) & ~3;
     if (g.sub_total == 0) g.sub_total = 4;
     g.threshold = threshold;
-    const int NC = g.P + 1, ncube = NC * NC * NC;
-    // per-cloud scratch layout (bytes, every block 16-byte aligned)
-    auto al = [](size_t n) { return (n + 15) & ~(size_t)15; };
-    const size_t o_val = 0, o_known = o_val + al((size_t)g.P3 * 4), o_pend = o_known + al(g.P3), o_sub = o_pend + al(g.pend_stride),
-                 o_mix = o_sub + al(g.sub_total), o_list = o_mix + al(g.sub_total), o_cube = o_list + al((size_t)g.cap * 4),
-                 o_tris = o_cube + al((size_t)ncube * 4), o_area = o_tris + al((size_t)capT * 36), per = o_area + al((size_t)capT * 8);
+    Carve one(nullptr), all(nullptr);
+    const size_t per = mesh_carve(one, w, capT, 1);
     const size_t fit = ((size_t)6 << 30) / per;                 // ~6 GB of scratch per pass
     const int chunk = fit < 1 ? 1 : fit > (size_t)B ? B : (int)fit;
     w.chunk = chunk;
-    // layout: arrays are [chunk][stride] each (struct-of-arrays), plus count / ntri / ab folded separately
-    const size_t total = per * chunk + al((size_t)chunk * 4) * 3 + al((size_t)(chunk + 1) * 4);
-    hipError_t e = ensure_buf(&ctx->ws_mesh, &ctx->ws_mesh_bytes, total);
+    mesh_carve(all, w, capT, chunk);
+    hipError_t e = ctx->ws_mesh.grow(all.bytes());
     if (e != hipSuccess) return fail(ctx, IFD_ERR_NOMEM, (who + " workspace").c_str(), e);
-    if (ctx->h_mesh_counts_n < (size_t)chunk) {          // pinned landing slots of the queue lengths + their events (kept by the context)
-        if (ctx->h_mesh_counts) (void)hipHostFree(ctx->h_mesh_counts);
-        ctx->h_mesh_counts = nullptr;
-        ctx->h_mesh_counts_n = 0;
-        e = hipHostMalloc(reinterpret_cast<void**>(&ctx->h_mesh_counts), (size_t)2 * chunk * sizeof(int), hipHostMallocDefault);
-        if (e != hipSuccess) return fail(ctx, IFD_ERR_NOMEM, (who + " pinned counts").c_str(), e);
-        ctx->h_mesh_counts_n = (size_t)chunk;
-    }
-    for (hipEvent_t& ev : ctx->mesh_ev)
-        if (!ev && (e = hipEventCreateWithFlags(&ev, hipEventDisableTiming)) != hipSuccess)
-            return fail(ctx, IFD_ERR_HIP, (who + " events").c_str(), e);
-    char* base = static_cast<char*>(ctx->ws_mesh);
-    auto blk = [&](size_t off_per_cloud) { return base + off_per_cloud * chunk; };
-    g.val = reinterpret_cast<float*>(blk(o_val));
-    g.known = reinterpret_cast<uint8_t*>(blk(o_known));
-    g.pend = reinterpret_cast<uint8_t*>(blk(o_pend));
-    g.sub = reinterpret_cast<uint8_t*>(blk(o_sub));
-    g.mix = reinterpret_cast<uint8_t*>(blk(o_mix));
-    g.list = reinterpret_cast<int*>(blk(o_list));
-    w.cube_offs = reinterpret_cast<int*>(blk(o_cube));
-    w.tris = reinterpret_cast<float*>(blk(o_tris));
-    w.area = reinterpret_cast<double*>(blk(o_area));
-    g.count = reinterpret_cast<int*>(base + per * chunk);
-    w.ntri = reinterpret_cast<int*>(base + per * chunk + al((size_t)chunk * 4));
-    g.prev = reinterpret_cast<int*>(base + per * chunk + al((size_t)chunk * 4) * 2);
-    g.plan = reinterpret_cast<int*>(base + per * chunk + al((size_t)chunk * 4) * 3);
+    // pinned landing slots of the queue lengths + their events (kept by the context)
+    e = ctx->h_mesh_counts.grow((size_t)2 * chunk * sizeof(int));
+    if (e != hipSuccess) return fail(ctx, IFD_ERR_NOMEM, (who + " pinned counts").c_str(), e);
+    for (Event& ev : ctx->mesh_ev)
+        if ((e = ev.ensure()) != hipSuccess) return fail(ctx, IFD_ERR_HIP, (who + " events").c_str(), e);
+    Carve c(ctx->ws_mesh.get());
+    mesh_carve(c, w, capT, chunk);
     return IFD_OK;
 }
 
@@ -1198,17 +1129,18 @@ int mise_rounds(ifd_ctx* ctx, const std::string& who, const MiseGrid& g, int nb,
     // empty launches.
     const int n0 = (g.res0 + 1) * (g.res0 + 1) * (g.res0 + 1);
     ctx->mesh_points += (unsigned long long)n0 * nb;
+    const size_t slot_ints = ctx->h_mesh_counts.bytes() / (2 * sizeof(int));
     bool done = false;
     int round = 0;
     for (; round < 64 && !done; ++round) {
-        int* slot = ctx->h_mesh_counts + (size_t)(round & 1) * ctx->h_mesh_counts_n;
+        int* slot = ctx->h_mesh_counts.get<int>() + (size_t)(round & 1) * slot_ints;
         e = eval(g, nb, s);
         if (e == hipSuccess) e = launch_mise_update(g, nb, s);
         if (e == hipSuccess) e = hipMemcpyAsync(slot, g.count, (size_t)nb * sizeof(int), hipMemcpyDeviceToHost, s);
-        if (e == hipSuccess) e = hipEventRecord(ctx->mesh_ev[round & 1], s);
+        if (e == hipSuccess) e = hipEventRecord(ctx->mesh_ev[round & 1].get(), s);
         if (e == hipSuccess && round >= 1) {
-            e = hipEventSynchronize(ctx->mesh_ev[(round - 1) & 1]);
-            const int* c_prev = ctx->h_mesh_counts + (size_t)((round - 1) & 1) * ctx->h_mesh_counts_n;   // queued BY round - 1 = evaluated IN this round
+            e = hipEventSynchronize(ctx->mesh_ev[(round - 1) & 1].get());
+            const int* c_prev = ctx->h_mesh_counts.get<int>() + (size_t)((round - 1) & 1) * slot_ints;   // queued BY round - 1 = evaluated IN this round
             int max_count = 0;
             for (int b = 0; b < nb; ++b) { max_count = c_prev[b] > max_count ? c_prev[b] : max_count; ctx->mesh_points += c_prev[b]; }
             if (max_count > g.cap) return fail(ctx, IFD_ERR_HIP, (who + ": point queue overflow").c_str());
@@ -1220,7 +1152,7 @@ int mise_rounds(ifd_ctx* ctx, const std::string& who, const MiseGrid& g, int nb,
         if (e != hipSuccess) return fail(ctx, IFD_ERR_HIP, (who + " round").c_str(), e);
     }
     // the last enqueued round's copy must have landed before its slot is reused by the next chunk
-    e = hipEventSynchronize(ctx->mesh_ev[(round - 1) & 1]);
+    e = hipEventSynchronize(ctx->mesh_ev[(round - 1) & 1].get());
     if (e != hipSuccess) return fail(ctx, IFD_ERR_HIP, (who + " round").c_str(), e);
     e = launch_mise_fill(g, nb, s);
     return e == hipSuccess ? IFD_OK : fail(ctx, IFD_ERR_HIP, (who + " fill").c_str(), e);
@@ -1267,8 +1199,8 @@ int ifd_onet_mesh_sample(ifd_ctx* ctx, const float* c, int B, const ifd_mesh_par
         hipError_t e = onet_fold(ctx, c + (size_t)b0 * ONET_C, nb, s, &ab);
         if (e != hipSuccess) return fail(ctx, IFD_ERR_HIP, "ifd_onet_mesh_sample init", e);
         const int r = mise_rounds(ctx, who, g, nb, s, [&](const MiseGrid& gg, int n, hipStream_t ss) {
-            return prm->precision != 0 ? launch_onet_grid_eval_bf(prm->precision, ctx->d_onet_img_bf, ctx->d_onet_small, ab, gg, n, ctx->n_cu, box, ss)
-                                       : launch_onet_grid_eval(ctx->d_onet_img, ctx->d_onet_small, ab, gg, n, ctx->n_cu, box, ss);
+            return prm->precision != 0 ? launch_onet_grid_eval_bf(prm->precision, ctx->d_onet_img_bf.get<float>(), ctx->d_onet_small.get<float>(), ab, gg, n, ctx->n_cu, box, ss)
+                                       : launch_onet_grid_eval(ctx->d_onet_img.get<float>(), ctx->d_onet_small.get<float>(), ab, gg, n, ctx->n_cu, box, ss);
         });
         if (r != IFD_OK) return r;
         if (grid)
@@ -1401,10 +1333,15 @@ std::vector<float> build_punet_image(const float* w, PunetImage& I) {
     return img;
 }
 
-size_t punet_ws_bytes(int B) {
-    return (size_t)B * (DUP_NS * 3 * 4 + DUP_NS * 4 + (size_t)DUP_NS * DUP_NSAMPLE * 4 + (size_t)DUP_FEAT_FLOATS * 4 +
-                        2 * (size_t)3 * DUP_NP * 3 * 4);
+// the scratch of launch_punet over n clouds
+PunetWs punet_ws(Carve& c, size_t n) {
+    PunetWs w;
+    w.nxyz = c.take<float>(n * DUP_NS * 3 * 4); w.fidx = c.take<int32_t>(n * DUP_NS * 4);
+    w.bidx = c.take<int32_t>(n * DUP_NS * DUP_NSAMPLE * 4); w.feat = c.take<float>(n * DUP_FEAT_FLOATS * 4);
+    w.kidx = c.take<int32_t>(n * 3 * DUP_NP * 3 * 4); w.kw = c.take<float>(n * 3 * DUP_NP * 3 * 4);
+    return w;
 }
+size_t punet_ws_bytes(int B) { return carved_bytes([&](Carve& c) { punet_ws(c, (size_t)B); }); }
 
 DupDraws dup_draws(uint64_t seed, int64_t base) {
     return DupDraws{(uint32_t)base, (uint32_t)seed, (uint32_t)(seed >> 32)};
@@ -1417,30 +1354,17 @@ int ifd_dup_abi_version(void) { return IFD_DUP_ABI_VERSION; }
 size_t ifd_punet_weight_count(void) { return punet_count(); }
 
 ifd_ctx* ifd_dup_create(const float* weights_host, size_t n_weights, int device) {
-    g_create_error.clear();
     if (weights_host ? n_weights != punet_count() : n_weights != 0) {
         g_create_error = "ifd_dup_create: expected " + std::to_string(punet_count()) + " weights (or NULL and 0), got " +
                          std::to_string(n_weights);
         return nullptr;
     }
-    ifd_ctx* ctx = new (std::nothrow) ifd_ctx();
-    if (!ctx) { g_create_error = "ifd_dup_create: out of host memory"; return nullptr; }
-    ctx->device = device;
-    ctx->model = IFD_MODEL_DUP;
-    hipError_t e = hipSetDevice(device);
-    if (e == hipSuccess && weights_host) {
-        std::vector<float> img = build_punet_image(weights_host, ctx->pimg);
-        e = hipMalloc(reinterpret_cast<void**>(&ctx->d_punet), img.size() * sizeof(float));
-        if (e == hipSuccess) e = hipMemcpy(ctx->d_punet, img.data(), img.size() * sizeof(float), hipMemcpyHostToDevice);
-    }
-    if (e == hipSuccess) e = configure_prep_kernels();
-    if (e == hipSuccess) e = configure_punet_kernels();
-    if (e != hipSuccess) {
-        g_create_error = std::string("ifd_dup_create: ") + hipGetErrorString(e);
-        ifd_destroy(ctx);
-        return nullptr;
-    }
-    return ctx;
+    return create_ctx("ifd_dup_create", IFD_MODEL_DUP, device, [&](ifd_ctx* ctx) {
+        hipError_t e = weights_host ? upload(ctx->d_punet, build_punet_image(weights_host, ctx->pimg)) : hipSuccess;
+        if (e == hipSuccess) e = configure_prep_kernels();
+        if (e == hipSuccess) e = configure_punet_kernels();
+        return e;
+    });
 }
 
 int ifd_srs(ifd_ctx* ctx, const float* pc, int B, int K, int drop_num, uint64_t seed, int64_t cloud_index_base,
@@ -1471,29 +1395,17 @@ int ifd_punet_forward(ifd_ctx* ctx, const float* xyz, int B, int npoint, int up_
     IFD_ON_CTX_DEVICE(ctx);
     if (npoint != DUP_NP || up_ratio != 4)
         return fail(ctx, IFD_ERR_UNSUPPORTED, "ifd_punet_forward: only npoint = 1024, up_ratio = 4 is built");
-    if (!ctx->d_punet) return fail(ctx, IFD_ERR_ARG, "ifd_punet_forward: the context holds no PU-Net weights");
+    if (!ctx->d_punet.get()) return fail(ctx, IFD_ERR_ARG, "ifd_punet_forward: the context holds no PU-Net weights");
     if (!xyz || !out || B < 1) return fail(ctx, IFD_ERR_ARG, "ifd_punet_forward: bad argument");
     hipStream_t s = static_cast<hipStream_t>(stream);
     const int chunk = std::min(B, PUNET_CHUNK);
-    const size_t need = punet_ws_bytes(chunk);
-    if (need > ctx->ws_dup_bytes) {
-        hipError_t e = hipDeviceSynchronize();
-        if (ctx->ws_dup) { (void)hipFree(ctx->ws_dup); ctx->ws_dup = nullptr; ctx->ws_dup_bytes = 0; }
-        if (e == hipSuccess) e = hipMalloc(&ctx->ws_dup, need);
-        if (e != hipSuccess) { ctx->ws_dup = nullptr; return fail(ctx, IFD_ERR_NOMEM, "ifd_punet_forward: workspace", e); }
-        ctx->ws_dup_bytes = need;
-    }
+    hipError_t e = ctx->ws_dup.grow(punet_ws_bytes(chunk));
+    if (e != hipSuccess) return fail(ctx, IFD_ERR_NOMEM, "ifd_punet_forward: workspace", e);
     for (int c0 = 0; c0 < B; c0 += chunk) {
         const int n = std::min(chunk, B - c0);
-        char* p = static_cast<char*>(ctx->ws_dup);
-        PunetWs w;
-        w.nxyz = reinterpret_cast<float*>(p); p += (size_t)n * DUP_NS * 3 * 4;
-        w.fidx = reinterpret_cast<int32_t*>(p); p += (size_t)n * DUP_NS * 4;
-        w.bidx = reinterpret_cast<int32_t*>(p); p += (size_t)n * DUP_NS * DUP_NSAMPLE * 4;
-        w.feat = reinterpret_cast<float*>(p); p += (size_t)n * DUP_FEAT_FLOATS * 4;
-        w.kidx = reinterpret_cast<int32_t*>(p); p += (size_t)n * 3 * DUP_NP * 3 * 4;
-        w.kw = reinterpret_cast<float*>(p);
-        hipError_t e = launch_punet(ctx->d_punet, ctx->pimg, xyz + (size_t)c0 * DUP_NP * 3, n, fps_start ? fps_start + (size_t)c0 * 4 : nullptr,
+        Carve c(ctx->ws_dup.get());
+        const PunetWs w = punet_ws(c, (size_t)n);
+        e = launch_punet(ctx->d_punet.get<float>(), ctx->pimg, xyz + (size_t)c0 * DUP_NP * 3, n, fps_start ? fps_start + (size_t)c0 * 4 : nullptr,
                                     dup_draws(seed, cloud_index_base + c0), w, out + (size_t)c0 * DUP_NP * 4 * 3, s);
         if (e == hipSuccess && aux && aux->fps_idx)
             e = hipMemcpyAsync(aux->fps_idx + (size_t)c0 * DUP_NS, w.fidx, (size_t)n * DUP_NS * 4, hipMemcpyDeviceToDevice, s);
@@ -1591,10 +1503,17 @@ std::vector<float> build_cls_image(const float* w, bool ft, ClsImage& I) {
     return img;
 }
 
-size_t cls_bytes_per_cloud(int stride, bool ft) {
+// the workspace of ifd_cls_forward over n clouds: 256 bytes of which the check of the counts uses the first word, then launch_cls's scratch
+ClsWs cls_ws(Carve& c, size_t n, int stride, bool ft) {
     const size_t T = (size_t)(stride + CLS_TILE - 1) / CLS_TILE;
-    return 4096 * T + 4096 + 2048 + 1024 + 64 + (ft ? 16384 : 0);
+    c.take<int32_t>(256);
+    ClsWs w;
+    w.part = c.take<float>(n * T * CLS_FEAT * 4); w.gmax = c.take<float>(n * CLS_FEAT * 4);
+    w.f1 = c.take<float>(n * 512 * 4); w.f2 = c.take<float>(n * 256 * 4); w.trans = c.take<float>(n * 16 * 4);
+    w.tfeat = ft ? c.take<float>(n * 4096 * 4) : nullptr;
+    return w;
 }
+size_t cls_ws_bytes(int n, int stride, bool ft) { return carved_bytes([&](Carve& c) { cls_ws(c, (size_t)n, stride, ft); }); }
 
 // The backward pass's image (ifd_internal.h ClsGradImage) from the canonical vector of a model without feature_transform.
 std::vector<float> build_cls_grad_image(const float* w, const ClsImage& F, ClsGradImage& G) {
@@ -1640,9 +1559,20 @@ std::vector<float> build_cls_grad_image(const float* w, const ClsImage& F, ClsGr
     return img;
 }
 
-size_t cls_grad_bytes_per_cloud(int stride) {
+// the workspace of ifd_cls_input_grad over n clouds: 256 bytes (atk_check's two words, where nothing lies in front), then the scratch
+ClsGradWs cls_grad_ws(Carve& c, size_t n, int stride) {
     const size_t T = (size_t)(stride + CLS_TILE - 1) / CLS_TILE;
-    return 8192 * T + 2 * 4096 + 2 * 4096 + 2 * 2048 + 2 * 1024 + 64 + 160 + 256 + 1024 + 2048 + 4096 + 8;
+    c.take<int32_t>(256);
+    ClsGradWs w;
+    w.part = c.take<float>(n * T * 4096); w.part_idx = c.take<int32_t>(n * T * 4096);
+    w.gmax_stn = c.take<float>(n * 4096); w.gmax = c.take<float>(n * 4096);
+    w.win_stn = c.take<int32_t>(n * 4096); w.win = c.take<int32_t>(n * 4096);
+    w.f1_stn = c.take<float>(n * 2048); w.f1 = c.take<float>(n * 2048);
+    w.f2_stn = c.take<float>(n * 1024); w.f2 = c.take<float>(n * 1024);
+    w.trans = c.take<float>(n * 64); w.logits = c.take<float>(n * 160);
+    w.d_out = c.take<float>(n * 256); w.d2 = c.take<float>(n * 1024); w.d1 = c.take<float>(n * 2048); w.g = c.take<float>(n * 4096);
+    w.pred = c.take<int32_t>(n * 4); w.loss = c.take<float>(n * 4);
+    return w;
 }
 
 }  // namespace
@@ -1656,7 +1586,6 @@ size_t ifd_cls_weight_count(int model, int feature_transform) {
 }
 
 ifd_ctx* ifd_cls_create(const float* weights_host, size_t n_weights, int model, int feature_transform, int n_classes, int device) {
-    g_create_error.clear();
     if (model < IFD_CLS_POINTNET || model > IFD_CLS_POINTCONV) {
         g_create_error = "ifd_cls_create: unknown model id " + std::to_string(model);
         return nullptr;
@@ -1675,29 +1604,13 @@ ifd_ctx* ifd_cls_create(const float* weights_host, size_t n_weights, int model, 
                          (weights_host ? std::to_string(n_weights) : std::string("NULL"));
         return nullptr;
     }
-    ifd_ctx* ctx = new (std::nothrow) ifd_ctx();
-    if (!ctx) { g_create_error = "ifd_cls_create: out of host memory"; return nullptr; }
-    ctx->device = device;
-    ctx->model = IFD_MODEL_CLS;
-    ctx->cls_feature_transform = ft ? 1 : 0;
-    ctx->cls_classes = n_classes;
-    hipError_t e = hipSetDevice(device);
-    if (e == hipSuccess) {
-        std::vector<float> img = build_cls_image(weights_host, ft, ctx->cimg);
-        e = hipMalloc(reinterpret_cast<void**>(&ctx->d_cls), img.size() * sizeof(float));
-        if (e == hipSuccess) e = hipMemcpy(ctx->d_cls, img.data(), img.size() * sizeof(float), hipMemcpyHostToDevice);
-        if (e == hipSuccess && !ft) {
-            std::vector<float> gimg = build_cls_grad_image(weights_host, ctx->cimg, ctx->gimg);
-            e = hipMalloc(reinterpret_cast<void**>(&ctx->d_cls_grad), gimg.size() * sizeof(float));
-            if (e == hipSuccess) e = hipMemcpy(ctx->d_cls_grad, gimg.data(), gimg.size() * sizeof(float), hipMemcpyHostToDevice);
-        }
-    }
-    if (e != hipSuccess) {
-        g_create_error = std::string("ifd_cls_create: ") + hipGetErrorString(e);
-        ifd_destroy(ctx);
-        return nullptr;
-    }
-    return ctx;
+    return create_ctx("ifd_cls_create", IFD_MODEL_CLS, device, [&](ifd_ctx* ctx) {
+        ctx->cls_feature_transform = ft ? 1 : 0;
+        ctx->cls_classes = n_classes;
+        hipError_t e = upload(ctx->d_cls, build_cls_image(weights_host, ft, ctx->cimg));
+        if (e == hipSuccess && !ft) e = upload(ctx->d_cls_grad, build_cls_grad_image(weights_host, ctx->cimg, ctx->gimg));
+        return e;
+    });
 }
 
 }  // extern "C"
@@ -1709,7 +1622,7 @@ namespace {
 int cls_forward_impl(ifd_ctx* ctx, const float* pc, const int32_t* n_points, int B, int stride, float* logits, const ifd_cls_aux* aux,
                      void* stream, bool check_counts, size_t ws_off) {
     if (!ctx) return IFD_ERR_ARG;
-    if (ctx->model != IFD_MODEL_CLS || !ctx->d_cls) return fail(ctx, IFD_ERR_ARG, "ifd_cls_forward: not a classifier context");
+    if (ctx->model != IFD_MODEL_CLS || !ctx->d_cls.get()) return fail(ctx, IFD_ERR_ARG, "ifd_cls_forward: not a classifier context");
     if (!pc || !logits || B < 1 || stride < 1 || stride > IFD_CLS_MAX_POINTS)
         return fail(ctx, IFD_ERR_ARG, "ifd_cls_forward: bad argument (B >= 1, 1 <= stride <= 10000)");
     const bool ft = ctx->cls_feature_transform != 0;
@@ -1718,10 +1631,9 @@ int cls_forward_impl(ifd_ctx* ctx, const float* pc, const int32_t* n_points, int
     IFD_ON_CTX_DEVICE(ctx);
     hipStream_t s = static_cast<hipStream_t>(stream);
     const int n_chunks = (B + CLS_CHUNK - 1) / CLS_CHUNK, chunk = (B + n_chunks - 1) / n_chunks;
-    const size_t per = cls_bytes_per_cloud(stride, ft);
-    hipError_t e = ensure_ws(ctx, ws_off + 256 + per * chunk);
+    hipError_t e = ctx->ws.grow(ws_off + cls_ws_bytes(chunk, stride, ft));
     if (e != hipSuccess) return fail(ctx, IFD_ERR_NOMEM, "ifd_cls_forward: workspace", e);
-    char* base = static_cast<char*>(ctx->ws) + ws_off;
+    char* base = ctx->ws.get<char>() + ws_off;
     if (n_points && check_counts) {       // the one blocking step: the counts are device memory
         int32_t bad = 0;
         e = launch_cls_check(n_points, B, stride, reinterpret_cast<int32_t*>(base), s);
@@ -1733,18 +1645,12 @@ int cls_forward_impl(ifd_ctx* ctx, const float* pc, const int32_t* n_points, int
             return fail(ctx, IFD_ERR_ARG, msg.c_str());
         }
     }
-    const int T = (stride + CLS_TILE - 1) / CLS_TILE, nc = ctx->cls_classes;
+    const int nc = ctx->cls_classes;
     for (int c0 = 0; c0 < B; c0 += chunk) {
         const int n = std::min(chunk, B - c0);
-        char* p = base + 256;
-        ClsWs w;
-        w.part = reinterpret_cast<float*>(p); p += (size_t)n * T * CLS_FEAT * 4;
-        w.gmax = reinterpret_cast<float*>(p); p += (size_t)n * CLS_FEAT * 4;
-        w.f1 = reinterpret_cast<float*>(p); p += (size_t)n * 512 * 4;
-        w.f2 = reinterpret_cast<float*>(p); p += (size_t)n * 256 * 4;
-        w.trans = reinterpret_cast<float*>(p); p += (size_t)n * 16 * 4;
-        w.tfeat = ft ? reinterpret_cast<float*>(p) : nullptr;
-        e = launch_cls(ctx->d_cls, ctx->cimg, ft, pc + (size_t)c0 * stride * 3, n_points ? n_points + c0 : nullptr, n, stride, w,
+        Carve c(base);
+        const ClsWs w = cls_ws(c, (size_t)n, stride, ft);
+        e = launch_cls(ctx->d_cls.get<float>(), ctx->cimg, ft, pc + (size_t)c0 * stride * 3, n_points ? n_points + c0 : nullptr, n, stride, w,
                        logits + (size_t)c0 * nc, nc, aux && aux->pred ? aux->pred + c0 : nullptr, s);
         if (e == hipSuccess && aux && aux->trans)
             e = hipMemcpy2DAsync(aux->trans + (size_t)c0 * 9, 36, w.trans, 64, 36, (size_t)n, hipMemcpyDeviceToDevice, s);
@@ -1772,8 +1678,8 @@ int ifd_cls_forward(ifd_ctx* ctx, const float* pc, const int32_t* n_points, int 
 namespace {
 
 int atk_context_ok(ifd_ctx* ctx, const char* who) {
-    if (ctx->model != IFD_MODEL_CLS || !ctx->d_cls) return fail(ctx, IFD_ERR_ARG, (std::string(who) + ": not a classifier context").c_str());
-    if (ctx->cls_feature_transform || !ctx->d_cls_grad)
+    if (ctx->model != IFD_MODEL_CLS || !ctx->d_cls.get()) return fail(ctx, IFD_ERR_ARG, (std::string(who) + ": not a classifier context").c_str());
+    if (ctx->cls_feature_transform || !ctx->d_cls_grad.get())
         return fail(ctx, IFD_ERR_ARG, (std::string(who) + ": input gradients are not built for a model with feature_transform").c_str());
     return IFD_OK;
 }
@@ -1783,8 +1689,8 @@ int atk_context_ok(ifd_ctx* ctx, const char* who) {
 int atk_check(ifd_ctx* ctx, const char* who, const int32_t* n_points, const int32_t* target, int B, int lo, int hi,
               const std::string& range_text, hipStream_t s) {
     int32_t bad[2] = {0, 0};
-    hipError_t e = launch_atk_check(n_points, target, B, lo, hi, ctx->cls_classes, static_cast<int32_t*>(ctx->ws), s);
-    if (e == hipSuccess) e = hipMemcpyAsync(bad, ctx->ws, sizeof(bad), hipMemcpyDeviceToHost, s);
+    hipError_t e = launch_atk_check(n_points, target, B, lo, hi, ctx->cls_classes, ctx->ws.get<int32_t>(), s);
+    if (e == hipSuccess) e = hipMemcpyAsync(bad, ctx->ws.get(), sizeof(bad), hipMemcpyDeviceToHost, s);
     if (e == hipSuccess) e = hipStreamSynchronize(s);
     if (e != hipSuccess) return fail(ctx, IFD_ERR_HIP, (std::string(who) + ": checking n_points and target").c_str(), e);
     if (bad[0] != 0)
@@ -1805,41 +1711,21 @@ int atk_chunk(int B) {
     const int n_chunks = (B + CLS_CHUNK - 1) / CLS_CHUNK;
     return (B + n_chunks - 1) / n_chunks;
 }
-size_t atk_grad_ws_bytes(int B, int stride) { return 256 + cls_grad_bytes_per_cloud(stride) * (size_t)atk_chunk(B); }
+size_t atk_grad_ws_bytes(int B, int stride) { return carved_bytes([&](Carve& c) { cls_grad_ws(c, (size_t)atk_chunk(B), stride); }); }
 
 // ifd_cls_input_grad on workspace that is already large enough (ws_off: bytes in front that belong to the caller), unchecked
 int input_grad_impl(ifd_ctx* ctx, size_t ws_off, const float* pc, const int32_t* n_points, int B, int stride, const int32_t* target,
                     int loss_kind, float kappa, float scale, float* grad, const ifd_atk_out* out, hipStream_t s) {
-    const int chunk = atk_chunk(B), T = (stride + CLS_TILE - 1) / CLS_TILE, nc = ctx->cls_classes;
-    char* base = static_cast<char*>(ctx->ws) + ws_off + 256;
+    const int chunk = atk_chunk(B), nc = ctx->cls_classes;
     for (int c0 = 0; c0 < B; c0 += chunk) {
         const size_t n = (size_t)std::min(chunk, B - c0);
-        char* p = base;
-        auto take = [&](size_t bytes_per_cloud) { char* q = p; p += n * bytes_per_cloud; return q; };
-        ClsGradWs w;
-        w.part = reinterpret_cast<float*>(take((size_t)T * 4096));
-        w.part_idx = reinterpret_cast<int32_t*>(take((size_t)T * 4096));
-        w.gmax_stn = reinterpret_cast<float*>(take(4096));
-        w.gmax = reinterpret_cast<float*>(take(4096));
-        w.win_stn = reinterpret_cast<int32_t*>(take(4096));
-        w.win = reinterpret_cast<int32_t*>(take(4096));
-        w.f1_stn = reinterpret_cast<float*>(take(2048));
-        w.f1 = reinterpret_cast<float*>(take(2048));
-        w.f2_stn = reinterpret_cast<float*>(take(1024));
-        w.f2 = reinterpret_cast<float*>(take(1024));
-        w.trans = reinterpret_cast<float*>(take(64));
-        w.logits = reinterpret_cast<float*>(take(160));
-        w.d_out = reinterpret_cast<float*>(take(256));
-        w.d2 = reinterpret_cast<float*>(take(1024));
-        w.d1 = reinterpret_cast<float*>(take(2048));
-        w.g = reinterpret_cast<float*>(take(4096));
-        w.pred = reinterpret_cast<int32_t*>(take(4));
-        w.loss = reinterpret_cast<float*>(take(4));
+        Carve c(ctx->ws.get<char>() + ws_off);
+        const ClsGradWs w = cls_grad_ws(c, n, stride);
         const float* pcc = pc + (size_t)c0 * stride * 3;
         const int32_t* npc = n_points ? n_points + c0 : nullptr;
-        hipError_t e = launch_cls_win(ctx->d_cls, ctx->cimg, pcc, npc, (int)n, stride, w, nc, s);
+        hipError_t e = launch_cls_win(ctx->d_cls.get<float>(), ctx->cimg, pcc, npc, (int)n, stride, w, nc, s);
         if (e == hipSuccess)
-            e = launch_cls_backward(ctx->d_cls, ctx->cimg, ctx->d_cls_grad, ctx->gimg, pcc, npc, (int)n, stride, target + c0, loss_kind, kappa,
+            e = launch_cls_backward(ctx->d_cls.get<float>(), ctx->cimg, ctx->d_cls_grad.get<float>(), ctx->gimg, pcc, npc, (int)n, stride, target + c0, loss_kind, kappa,
                                     scale, w, nc, grad + (size_t)c0 * stride * 3, s);
         auto copy = [&](void* dst, size_t dst_off, const void* src, size_t bytes_per_cloud) {
             if (e == hipSuccess && dst)
@@ -1863,7 +1749,7 @@ bool atk_kind_ok(int k) { return k >= IFD_FGM_FGM && k <= IFD_FGM_PGD; }
 
 // workspace of an attack loop: its own state in front of ifd_cls_input_grad's and, with_forward, of the final forward's
 size_t atk_loop_ws_bytes(int B, int stride, size_t state_bytes, bool with_forward) {
-    const size_t fwd = with_forward ? 256 + cls_bytes_per_cloud(stride, false) * (size_t)atk_chunk(B) : 0;
+    const size_t fwd = with_forward ? cls_ws_bytes(atk_chunk(B), stride, false) : 0;
     return state_bytes + std::max(atk_grad_ws_bytes(B, stride), fwd);
 }
 
@@ -1888,17 +1774,60 @@ bool cw_state_ok(const ifd_cw_state* st, bool need_bounds) {
     return need_bounds ? st->lower && st->upper : st->m && st->v && st->o_bestscore && st->o_bestattack;
 }
 
-// the common front of the two loops' state in the workspace: the float64 weights first (alignment), then the [B] records, pred and loss
-template <class Take>
-void cw_carve_front(Take& take, int B, CwState& S, int32_t*& pred, float*& loss) {
-    S.weight = reinterpret_cast<double*>(take((size_t)B * 8));
-    S.lower = reinterpret_cast<double*>(take((size_t)B * 8));
-    S.upper = reinterpret_cast<double*>(take((size_t)B * 8));
-    S.bestdist = reinterpret_cast<float*>(take((size_t)B * 4));
-    S.bestscore = reinterpret_cast<int32_t*>(take((size_t)B * 4));
-    S.o_bestscore = reinterpret_cast<int32_t*>(take((size_t)B * 4));
-    pred = reinterpret_cast<int32_t*>(take((size_t)B * 4));
-    loss = reinterpret_cast<float*>(take((size_t)B * 4));
+// The state of an attack loop lies in front of the workspace of the calls it makes (ifd_cls_input_grad's, the final forward's),
+// rounded up to 256 bytes; B clouds of `cloud` bytes each.  Each struct carves itself; its size is carved_bytes of that.
+struct FgmLoop {
+    float *grad, *mom, *logits; int32_t* pred;
+    FgmLoop(Carve& c, size_t B, size_t cloud) {
+        grad = c.take<float>(B * cloud); mom = c.take<float>(B * cloud);
+        logits = c.take<float>(B * 160); pred = c.take<int32_t>(B * 4);
+        c.round_up(256);
+    }
+};
+// the common front of the two Carlini-Wagner loops: the float64 weights first (alignment), then the [B] records, pred and loss
+struct CwFront {
+    CwState S{}; int32_t* pred; float* loss;
+    CwFront(Carve& c, size_t B) {
+        S.weight = c.take<double>(B * 8); S.lower = c.take<double>(B * 8); S.upper = c.take<double>(B * 8);
+        S.bestdist = c.take<float>(B * 4); S.bestscore = c.take<int32_t>(B * 4); S.o_bestscore = c.take<int32_t>(B * 4);
+        pred = c.take<int32_t>(B * 4); loss = c.take<float>(B * 4);
+    }
+};
+struct CwLoop {
+    CwFront f; float *grad, *adv, *last;
+    CwLoop(Carve& c, size_t B, size_t cloud) : f(c, B) {
+        grad = c.take<float>(B * cloud); adv = c.take<float>(B * cloud);
+        f.S.m = c.take<float>(B * cloud); f.S.v = c.take<float>(B * cloud);       // side by side
+        last = c.take<float>(B * cloud);
+        c.take<char>(B * 20);                                                     // unused
+        c.round_up(256);
+    }
+};
+struct KnnLoop {
+    float *grad, *m, *v, *logits, *loss;
+    KnnLoop(Carve& c, size_t B, size_t cloud) {
+        grad = c.take<float>(B * cloud); m = c.take<float>(B * cloud); v = c.take<float>(B * cloud);       // m, v side by side
+        logits = c.take<float>(B * 160); loss = c.take<float>(B * 4);
+        c.take<char>(B * 4);                                                      // unused
+        c.round_up(256);
+    }
+};
+struct AddLoop {                          // G: points of the larger of the input and the output cloud
+    CwFront f; int32_t *n_cat, *n_ori; float *grad, *cri, *last;
+    AddLoop(Carve& c, size_t B, size_t G, size_t num_add) : f(c, B) {
+        const size_t added = B * num_add * 12;
+        n_cat = c.take<int32_t>(B * 4); n_ori = c.take<int32_t>(B * 4);
+        grad = c.take<float>(B * G * 12); cri = c.take<float>(added);
+        f.S.m = c.take<float>(added); f.S.v = c.take<float>(added); f.S.o_bestattack = c.take<float>(added);   // side by side
+        last = c.take<float>(added);
+        c.round_up(256);
+    }
+};
+// ifd_add_critical_points: the gradient alone
+float* grad_loop(Carve& c, size_t B, size_t cloud) {
+    float* grad = c.take<float>(B * cloud);
+    c.round_up(256);
+    return grad;
 }
 
 // the binary search on the weight around the Adam iterations; the callbacks return a status, the first non-zero one ends the search
@@ -1931,7 +1860,7 @@ int ifd_cls_input_grad(ifd_ctx* ctx, const float* pc, const int32_t* n_points, i
     if (!atk_loss_ok(loss_kind)) return fail(ctx, IFD_ERR_ARG, "ifd_cls_input_grad: unknown loss_kind");
     IFD_ON_CTX_DEVICE(ctx);
     hipStream_t s = static_cast<hipStream_t>(stream);
-    hipError_t e = ensure_ws(ctx, atk_grad_ws_bytes(B, stride));
+    hipError_t e = ctx->ws.grow(atk_grad_ws_bytes(B, stride));
     if (e != hipSuccess) return fail(ctx, IFD_ERR_NOMEM, "ifd_cls_input_grad: workspace", e);
     if (int rc = atk_check(ctx, "ifd_cls_input_grad", n_points, target, B, 1, stride, "[1, stride]", s)) return rc;
     return input_grad_impl(ctx, 0, pc, n_points, B, stride, target, loss_kind, kappa, scale, grad, out, s);
@@ -1964,16 +1893,14 @@ int ifd_fgm_attack(ifd_ctx* ctx, const ifd_fgm_params* params, const float* pc_i
         return fail(ctx, IFD_ERR_ARG, "ifd_fgm_attack: bad argument (pc_in, target, pc_out, success; B >= 1, 1 <= stride <= 10000)");
     IFD_ON_CTX_DEVICE(ctx);
     hipStream_t s = static_cast<hipStream_t>(stream);
-    const size_t cloud = (size_t)stride * 12, state = (((size_t)B * (2 * cloud + 160 + 4)) + 255) / 256 * 256;
-    hipError_t e = ensure_ws(ctx, atk_loop_ws_bytes(B, stride, state, true));
+    const size_t cloud = (size_t)stride * 12, state = carved_bytes([&](Carve& c) { FgmLoop(c, (size_t)B, cloud); });
+    hipError_t e = ctx->ws.grow(atk_loop_ws_bytes(B, stride, state, true));
     if (e != hipSuccess) return fail(ctx, IFD_ERR_NOMEM, "ifd_fgm_attack: workspace", e);
     if (int rc = atk_check(ctx, "ifd_fgm_attack", n_points, target, B, 1, stride, "[1, stride]", s)) return rc;
-    // the loop's own state in front of the workspace of the calls it makes
-    char* base = static_cast<char*>(ctx->ws);
-    float* grad = reinterpret_cast<float*>(base);
-    float* mom = reinterpret_cast<float*>(base + (size_t)B * cloud);
-    float* logits = reinterpret_cast<float*>(base + (size_t)B * 2 * cloud);
-    int32_t* pred = reinterpret_cast<int32_t*>(base + (size_t)B * (2 * cloud + 160));
+    Carve c(ctx->ws.get());
+    const FgmLoop L(c, (size_t)B, cloud);
+    float *grad = L.grad, *mom = L.mom, *logits = L.logits;
+    int32_t* pred = L.pred;
     e = hipMemcpyAsync(pc_out, pc_in, (size_t)B * cloud, hipMemcpyDeviceToDevice, s);
     if (e == hipSuccess && params->kind == IFD_FGM_MIFGM) e = hipMemsetAsync(mom, 0, (size_t)B * cloud, s);
     if (e != hipSuccess) return fail(ctx, IFD_ERR_HIP, "ifd_fgm_attack: start", e);
@@ -2042,22 +1969,15 @@ int ifd_cw_perturb_attack(ifd_ctx* ctx, const ifd_cw_params* params, const float
     if (clouds_overlap(pc_in, all, pc_out, all)) return fail(ctx, IFD_ERR_ARG, "ifd_cw_perturb_attack: pc_out overlaps pc_in");
     IFD_ON_CTX_DEVICE(ctx);
     hipStream_t s = static_cast<hipStream_t>(stream);
-    const size_t state = ((size_t)B * (5 * cloud + 64) + 255) / 256 * 256;
-    hipError_t e = ensure_ws(ctx, atk_loop_ws_bytes(B, stride, state, false));
+    const size_t state = carved_bytes([&](Carve& c) { CwLoop(c, (size_t)B, cloud); });
+    hipError_t e = ctx->ws.grow(atk_loop_ws_bytes(B, stride, state, false));
     if (e != hipSuccess) return fail(ctx, IFD_ERR_NOMEM, "ifd_cw_perturb_attack: workspace", e);
     if (int rc = atk_check(ctx, "ifd_cw_perturb_attack", n_points, target, B, 1, stride, "[1, stride]", s)) return rc;
-    // the loop's own state in front of the workspace of ifd_cls_input_grad: the float64 weights first (alignment)
-    char* p = static_cast<char*>(ctx->ws);
-    auto take = [&](size_t bytes) { char* q = p; p += bytes; return q; };
-    CwState S;
-    int32_t* pred;
-    float* loss;
-    cw_carve_front(take, B, S, pred, loss);
-    float* grad = reinterpret_cast<float*>(take(all));
-    float* adv = reinterpret_cast<float*>(take(all));
-    S.m = reinterpret_cast<float*>(take(all));
-    S.v = reinterpret_cast<float*>(take(all));
-    float* last = reinterpret_cast<float*>(take(all));
+    Carve c(ctx->ws.get());
+    const CwLoop L(c, (size_t)B, cloud);
+    CwState S = L.f.S;
+    int32_t* pred = L.f.pred;
+    float *loss = L.f.loss, *grad = L.grad, *adv = L.adv, *last = L.last;
     S.o_bestdist = best_dist;
     S.o_bestattack = pc_out;
     e = launch_cw_init(S, B, params->init_weight, params->max_weight, s);
@@ -2145,19 +2065,14 @@ int ifd_knn_attack(ifd_ctx* ctx, const ifd_knn_params* params, const float* pc_i
     if (clouds_overlap(pc_in, all, pc_out, all)) return fail(ctx, IFD_ERR_ARG, "ifd_knn_attack: pc_out overlaps pc_in");
     IFD_ON_CTX_DEVICE(ctx);
     hipStream_t s = static_cast<hipStream_t>(stream);
-    const size_t state = ((size_t)B * (3 * cloud + 160 + 8) + 255) / 256 * 256;
-    hipError_t e = ensure_ws(ctx, atk_loop_ws_bytes(B, stride, state, true));
+    const size_t state = carved_bytes([&](Carve& c) { KnnLoop(c, (size_t)B, cloud); });
+    hipError_t e = ctx->ws.grow(atk_loop_ws_bytes(B, stride, state, true));
     if (e != hipSuccess) return fail(ctx, IFD_ERR_NOMEM, "ifd_knn_attack: workspace", e);
     // a cloud below 6 points has no five neighbours
     if (int rc = atk_check(ctx, "ifd_knn_attack", n_points, target, B, IFD_KNN_MIN_POINTS, stride, "[6, stride]", s)) return rc;
-    // the loop's own state in front of the workspace of the calls it makes; adv is pc_out itself
-    char* p = static_cast<char*>(ctx->ws);
-    auto take = [&](size_t bytes) { char* q = p; p += bytes; return q; };
-    float* grad = reinterpret_cast<float*>(take(all));
-    float* m = reinterpret_cast<float*>(take(all));
-    float* v = reinterpret_cast<float*>(take(all));
-    float* logits = reinterpret_cast<float*>(take((size_t)B * 160));
-    float* loss = reinterpret_cast<float*>(take((size_t)B * 4));
+    Carve c(ctx->ws.get());                                             // adv is pc_out itself
+    const KnnLoop L(c, (size_t)B, cloud);
+    float *grad = L.grad, *m = L.m, *v = L.v, *logits = L.logits, *loss = L.loss;
     e = launch_cw_start(pc_in, noise, pc_out, n_points, B, stride, s);
     if (e == hipSuccess) e = hipMemsetAsync(m, 0, 2 * all, s);         // m and v lie side by side
     if (e != hipSuccess) return fail(ctx, IFD_ERR_HIP, "ifd_knn_attack: start", e);
@@ -2215,12 +2130,13 @@ int ifd_add_critical_points(ifd_ctx* ctx, const float* pc, const int32_t* n_poin
         return fail(ctx, IFD_ERR_ARG, "ifd_add_critical_points: without n_points, stride outside [num_add, 2048]");
     IFD_ON_CTX_DEVICE(ctx);
     hipStream_t s = static_cast<hipStream_t>(stream);
-    const size_t state = ((size_t)B * stride * 12 + 255) / 256 * 256;
-    hipError_t e = ensure_ws(ctx, state + atk_grad_ws_bytes(B, stride));
+    const size_t state = carved_bytes([&](Carve& c) { grad_loop(c, (size_t)B, (size_t)stride * 12); });
+    hipError_t e = ctx->ws.grow(state + atk_grad_ws_bytes(B, stride));
     if (e != hipSuccess) return fail(ctx, IFD_ERR_NOMEM, "ifd_add_critical_points: workspace", e);
     const int hi = std::min(stride, IFD_ADD_MAX_ORI);
     if (int rc = atk_check(ctx, "ifd_add_critical_points", n_points, target, B, num_add, hi, numeric_range(num_add, hi), s)) return rc;
-    float* grad = static_cast<float*>(ctx->ws);
+    Carve c(ctx->ws.get());
+    float* grad = grad_loop(c, (size_t)B, (size_t)stride * 12);
     if (int rc = input_grad_impl(ctx, state, pc, n_points, B, stride, target, IFD_ATK_LOSS_CE, 0.f, scale, grad, nullptr, s)) return rc;
     e = launch_add_select(grad, pc, n_points, B, stride, num_add, cri, idx, s);
     if (e != hipSuccess) return fail(ctx, IFD_ERR_HIP, "ifd_add_critical_points: select", e);
@@ -2277,25 +2193,15 @@ int ifd_add_attack(ifd_ctx* ctx, const ifd_add_params* params, const float* pc_i
     hipStream_t s = static_cast<hipStream_t>(stream);
     const int G = std::max(stride, out_stride);
     const size_t added = (size_t)B * num_add * 12;
-    const size_t state = ((size_t)B * (12 * (size_t)G + 60 * (size_t)num_add + 52) + 255) / 256 * 256;
-    hipError_t e = ensure_ws(ctx, atk_loop_ws_bytes(B, G, state, false));
+    const size_t state = carved_bytes([&](Carve& c) { AddLoop(c, (size_t)B, (size_t)G, (size_t)num_add); });
+    hipError_t e = ctx->ws.grow(atk_loop_ws_bytes(B, G, state, false));
     if (e != hipSuccess) return fail(ctx, IFD_ERR_NOMEM, "ifd_add_attack: workspace", e);
     if (int rc = atk_check(ctx, "ifd_add_attack", n_points, target, B, num_add, hi, numeric_range(num_add, hi), s)) return rc;
-    // the loop's own state in front of the workspace of ifd_cls_input_grad: the float64 weights first (alignment)
-    char* p = static_cast<char*>(ctx->ws);
-    auto take = [&](size_t bytes) { char* q = p; p += bytes; return q; };
-    CwState S;
-    int32_t* pred;
-    float* loss;
-    cw_carve_front(take, B, S, pred, loss);
-    int32_t* n_cat = reinterpret_cast<int32_t*>(take((size_t)B * 4));
-    int32_t* n_ori = reinterpret_cast<int32_t*>(take((size_t)B * 4));
-    float* grad = reinterpret_cast<float*>(take((size_t)B * G * 12));
-    float* cri = reinterpret_cast<float*>(take(added));
-    S.m = reinterpret_cast<float*>(take(added));
-    S.v = reinterpret_cast<float*>(take(added));
-    S.o_bestattack = reinterpret_cast<float*>(take(added));
-    float* last = reinterpret_cast<float*>(take(added));
+    Carve c(ctx->ws.get());
+    const AddLoop L(c, (size_t)B, (size_t)G, (size_t)num_add);
+    CwState S = L.f.S;
+    int32_t *pred = L.f.pred, *n_cat = L.n_cat, *n_ori = L.n_ori;
+    float *loss = L.f.loss, *grad = L.grad, *cri = L.cri, *last = L.last;
     S.o_bestdist = best_dist;
     // the critical points (Add.py:14-42): cross-entropy towards the target, whatever the loop's loss
     if (int rc = input_grad_impl(ctx, state, pc_in, n_points, B, stride, target, IFD_ATK_LOSS_CE, 0.f, params->scale, grad, nullptr, s))
