@@ -30,15 +30,8 @@ def sources():
 
 
 def _deps():
-    hdr = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h")]
-    hdr.append(os.path.join(os.path.dirname(HERE), "include", "ifd.h"))
-    hdr.append(os.path.join(os.path.dirname(HERE), "include", "ifd_dup.h"))
-    hdr.append(os.path.join(os.path.dirname(HERE), "include", "ifd_cls.h"))
-    hdr.append(os.path.join(os.path.dirname(HERE), "include", "ifd_atk.h"))
-    hdr.append(os.path.join(os.path.dirname(HERE), "include", "ifd_cw.h"))
-    hdr.append(os.path.join(os.path.dirname(HERE), "include", "ifd_knn.h"))
-    hdr.append(os.path.join(os.path.dirname(HERE), "include", "ifd_add.h"))
-    return hdr
+    return [os.path.join(d, f) for d in (CSRC, os.path.join(os.path.dirname(HERE), "include"))
+            for f in os.listdir(d) if f.endswith(".h")]
 
 
 def _stale(target: str, deps) -> bool:

@@ -101,7 +101,6 @@ struct ifd_ctx {
     std::vector<float> w;          // host copy, canonical order
     DeviceBuffer d_dec_img;        // decoder parameter image (ifd_device.h layout)
     DeviceBuffer d_dec_img_bf;     // ... and the bf16 piece image of the split-precision tiles (ifd_opt_params.precision 1 / 2)
-    DeviceBuffer d_dec_img_opt;    // ... the persistent optimiser's copy: fc_0 / fc_1 / fc_out scaled by 2^RELU_K (ifd_device.h)
     DeviceBuffer d_w;              // the whole canonical weight vector on the device (encoder kernels index it)
     EncPointOffsets eo{};
     DeviceBuffer d_unet;           // re-packed U-Net weights ([tap][Cin][Cout])
@@ -184,7 +183,7 @@ DeviceGuard::DeviceGuard(const ifd_ctx* ctx) {
     if (!ifd_device_guard_.ok) return fail(ctx, IFD_ERR_HIP, "cannot make the context's device current")
 
 // Build the LDS image of the decoder parameters.
-std::vector<float> build_dec_image(const float* w, bool relu_scaled = false) {
+std::vector<float> build_dec_image(const float* w) {
     const WeightMap& m = wmap();
     std::vector<float> img(DEC_FLOATS, 0.f);
     auto put_layer = [&](int L, size_t woff, size_t boff) {
@@ -213,13 +212,6 @@ std::vector<float> build_dec_image(const float* w, bool relu_scaled = false) {
             img[DEC_OFF_BIAS + (3 * (i - 1) + 2) * 32 + c] += img[DEC_OFF_BIAS + 3 * i * 32 + c];
             img[DEC_OFF_BIAS + 3 * i * 32 + c] = 0.f;
         }
-    }
-    if (relu_scaled && RELU_K != 0) {      // the layers fed by a ReLU (exact: a power of two; biases stay as they are)
-        const float sc = RELU_UP;
-        for (int i = 0; i < 5; ++i)
-            for (int j = 1; j <= 2; ++j)
-                for (int k = 0; k < W_LAYER; ++k) img[DEC_OFF_W + (3 * i + j) * W_LAYER + k] *= sc;
-        for (int c = 0; c < 32; ++c) img[DEC_OFF_WOUT + c] *= sc;
     }
     return img;
 }
@@ -536,7 +528,6 @@ ifd_ctx* ifd_create(const float* weights_host, size_t n_weights, const ifd_confi
         ctx->dc.uclamp = (float)(1.0 - 10e-6);
         const float* w = ctx->w.data();
         hipError_t e = upload(ctx->d_dec_img, build_dec_image(w));
-        if (e == hipSuccess) e = upload(ctx->d_dec_img_opt, build_dec_image(w, true));
         if (e == hipSuccess) e = upload(ctx->d_dec_img_bf, build_dec_image_bf(w));
         if (e == hipSuccess) e = alloc_counters(ctx);
         if (e == hipSuccess) e = upload(ctx->d_w, ctx->w);
@@ -807,11 +798,11 @@ int ifd_optimize(ifd_ctx* ctx, const float* planes, float* p, int B, int K, cons
     if (e == hipSuccess) e = launch_adam_table(ctx->adam_tab.get<float>(), a.t0, a.steps, a.lr, static_cast<hipStream_t>(stream));
     if (e != hipSuccess) return fail(ctx, IFD_ERR_HIP, "ifd_optimize memset / Adam table", e);
     if (large) {
-        e = large_optimize_in_groups(ctx, a.precision != 0 ? ctx->d_dec_img_bf.get<float>() : ctx->d_dec_img_opt.get<float>(), planes, p, m, v, loss, loss_batch_per_cloud,
+        e = large_optimize_in_groups(ctx, a.precision != 0 ? ctx->d_dec_img_bf.get<float>() : ctx->d_dec_img.get<float>(), planes, p, m, v, loss, loss_batch_per_cloud,
                                      B, K, a, static_cast<hipStream_t>(stream));
         return e == hipSuccess ? IFD_OK : fail(ctx, IFD_ERR_HIP, "ifd_optimize launch (large clouds)", e);
     }
-    e = launch_optimize(a.precision != 0 ? ctx->d_dec_img_bf.get<float>() : ctx->d_dec_img_opt.get<float>(), planes, p, m, v, loss, loss_batch_per_cloud, ctx->ws.get(), ctx->counters(),
+    e = launch_optimize(a.precision != 0 ? ctx->d_dec_img_bf.get<float>() : ctx->d_dec_img.get<float>(), planes, p, m, v, loss, loss_batch_per_cloud, ctx->ws.get(), ctx->counters(),
                         ctx->adam_tab.get<float>(), B, K, a, prm->split, ctx->n_cu, static_cast<hipStream_t>(stream));
     return e == hipSuccess ? IFD_OK : fail(ctx, IFD_ERR_HIP, "ifd_optimize launch", e);
 }

@@ -7,7 +7,7 @@
 
 namespace ifd {
 
-constexpr size_t DECODE_BF_LDS = (size_t)BF_IMG_BYTES + 8 * 256;        // the piece image + one landing strip per wave (tile_bf.h)
+constexpr size_t DECODE_BF_LDS = (size_t)BF_IMG_BYTES;                  // the piece image
 
 // workgroup (cloud, part): the cloud's 32-point tiles part * 8 + wave, + 8 * parts, ...
 template <int PREC>
@@ -16,7 +16,6 @@ __global__ __launch_bounds__(OPT_THREADS, 1) void decode3_bf_kernel(const float*
                                                                      float* __restrict__ dlogit_dp, DecConst dc) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     float* W = smem;
-    float* strips = smem + BF_IMG_BYTES / 4;
     const int cloud = blockIdx.x, tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     load_dec_image(W, dec_img, BF_IMG_BYTES / 4);
@@ -37,8 +36,7 @@ __global__ __launch_bounds__(OPT_THREADS, 1) void decode3_bf_kernel(const float*
         const float xqa = q == 0 ? xa0 : q == 1 ? xa1 : q == 2 ? xa2 : 1.f;
         const float xqb = q == 0 ? xb0 : q == 1 ? xb1 : q == 2 ? xb2 : 1.f;
         float lg[2], dx[2][3];
-        decoder_tile3_bf<MODE_SUM, PREC>(W, plr, ppa, ppb, xqa, xqb, lane, dc, 0.f, false, lg, dx, strips + 64 * wave);
-        asm volatile("s_setprio 0");
+        decoder_tile3_bf<MODE_SUM, PREC>(W, plr, ppa, ppb, xqa, xqb, lane, dc, 0.f, false, lg, dx);
         if (lane < 16) {
             if (ia < K) {
                 logits[(size_t)cloud * K + ia] = lg[0];

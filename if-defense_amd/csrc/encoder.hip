@@ -469,15 +469,11 @@ void build_enc_image(const float* w, const EncPointOffsets& eo, float* img) {
     for (int k = 0; k < 32; ++k) img[ENCI_BC + k] = w[eo.fcc_b + k];
 }
 
-// enc_img: build_enc_image's copy on the device.  -DIFD_ENC_VALU / env IFD_ENC_VALU=1: the thread-per-point kernel (validation, A/B);
+// enc_img: build_enc_image's copy on the device.  env IFD_ENC_VALU=1: the thread-per-point kernel (validation, A/B);
 // it expects zero-filled planes, the MFMA kernel fills them itself.
 hipError_t launch_encode_points(const float* w, const EncPointOffsets& eo, const float* enc_img, const float* sel,
                                 const int* t_per_cloud, int B, int Tmax, float* planes, float* c_out, DecConst dc, hipStream_t s) {
-#ifdef IFD_ENC_VALU
-    const bool valu = true;
-#else
     static const bool valu = [] { const char* e = getenv("IFD_ENC_VALU"); return e != nullptr && e[0] == '1'; }();
-#endif
     if (valu) {
         hipError_t e = hipMemsetAsync(planes, 0, (size_t)B * CLOUD_PLANE_FLOATS * sizeof(float), s);
         if (e != hipSuccess) return e;

@@ -161,15 +161,13 @@ __device__ __forceinline__ void knn_scan_ref2(const f32x4* __restrict__ X, int K
 // 16 / 48: 867 ms, 24 / 48: 865, 32 / 48: 864, 40 / 48: 866, 24 / 40: 881, 32 / 56: 857, 16 / 64: 896, 24 / 64: 855, 32 / 64: 852,
 // 40 / 64: 853, 48 / 64: 855 - longer lists mean fewer whole-cloud rebuilds (~140 k cycles per wave each) for more entries
 // evaluated per step, and the evaluation became the cheaper side once it ran on key networks.
-#ifndef IFD_LIST_F
-#define IFD_LIST_F 32
-#endif
-constexpr int LIST_F = IFD_LIST_F;               // "front": every point within rho_f at build time (evaluated every step)
-#ifndef IFD_LIST_M
-#define IFD_LIST_M 64          // <= 64: knn_build_one fills a list's unused slots one per lane
-#endif
-constexpr int LIST_B = IFD_LIST_M - IFD_LIST_F;               // "back" : the ring rho_f <= d < rho_b (evaluated only when the front fails)
-constexpr int LIST_M = LIST_F + LIST_B;  // uint16 entries per point; lists live in global memory (L2-resident)
+constexpr int LIST_F = 32;               // "front": every point within rho_f at build time (evaluated every step)
+constexpr int LIST_M = 64;               // uint16 entries per point; lists live in global memory (L2-resident).  <= 64: knn_build_one fills a list's unused slots one per lane
+constexpr int LIST_B = LIST_M - LIST_F;  // "back" : the ring rho_f <= d < rho_b (evaluated only when the front fails)
+constexpr int FILL_Q = 2;                // grow a radius while its list is less than FILL_Q / 4 full (knn_build_one)
+constexpr float FRAG_MULT = 16.f;        // a certificate whose slack rho_b - r5 is below FRAG_MULT largest moves (a few steps of life) is "fragile"
+constexpr int REBUILD_MIN = 16;          // whole-cloud rebuild only when more long-lived certificates than this are about to expire (knn_phase)
+constexpr float SOFT_SLACK = 1.f;        // soft margin of a certificate in units of the step's largest move: tuned, not derived (knn_phase)
 
 // Per-step diagnostics of the kNN phase: event counts live in LDS (one atomic by lane 0 per event - they are rare or
 // once per wave-step), not in registers that would have to survive the decoder tiles.  Summed into ifd_get_counters.
@@ -472,21 +470,15 @@ __device__ __forceinline__ void knn_refresh(const f32x4* __restrict__ X, int K, 
             kp.rho_b = sqrtf(tb);
             // carry the (possibly shrunk) radii forward as multiples of the 5-NN bound; grow slowly when sparse
             if (d4 > 0.f) { kp.al_f = tf / d4; kp.al_b = tb / d4; }
-#ifndef IFD_FILL_Q
-#define IFD_FILL_Q 2          // grow a radius while its list is less than IFD_FILL_Q / 4 full
-#endif
-            if (4 * nf < IFD_FILL_Q * LIST_F) kp.al_f *= 1.15f;
-            if (4 * (nf + nb) < IFD_FILL_Q * LIST_M) kp.al_b *= 1.15f;
+            if (4 * nf < FILL_Q * LIST_F) kp.al_f *= 1.15f;
+            if (4 * (nf + nb) < FILL_Q * LIST_M) kp.al_b *= 1.15f;
             kp.al_f = fminf(fmaxf(kp.al_f, 1.1f), 6.f);
             kp.al_b = fminf(fmaxf(kp.al_b, 1.2f), 30.f);
             kp.al_f = fminf(kp.al_f, kp.al_b);
             kp.x0 = X[half ? pb : pa];
             kp.dbase = dbase;
             // expected lifetime of the certificate ~ (rho - r5 - 6 mv) / (~2 mv per step)
-#ifndef IFD_FRAG_MULT
-#define IFD_FRAG_MULT 16.f
-#endif
-            kp.frag = kp.rho_b - sqrtf(d4) < IFD_FRAG_MULT * mv;
+            kp.frag = kp.rho_b - sqrtf(d4) < FRAG_MULT * mv;
         }
     }
 }
@@ -955,15 +947,12 @@ __device__ __forceinline__ void knn_phase(const f32x4* __restrict__ X, const Rep
     } else if (scan_every_step) {
         knn_scan2(X, K, pa, pb, ta, tb);
     } else {
-        // A whole-cloud rebuild (new epoch) only when more than IFD_REBUILD_MIN long-lived certificates are about to expire;
+        // A whole-cloud rebuild (new epoch) only when more than REBUILD_MIN long-lived certificates are about to expire;
         // fewer are refreshed individually by their own waves like the fragile ones (~250 instructions per list against
         // ~300 k cycles per wave for the rebuild).  Round 3, kernel launch of the bench workload / 512 clouds on the
         // trained-like field (ms): 0: 829.9 / 182.1, 4: 824.3 / 179.9, 16: 825.5 / 176.9, 64: 831.9 / 174.6 (whole-cloud
         // rebuilds per cloud on the trained-like field 12.8 -> 9.7 -> 8.1 -> 6.9).
-#ifndef IFD_REBUILD_MIN
-#define IFD_REBUILD_MIN 16
-#endif
-        const bool force = step == 0 || rebuild_flag[step & 1] > IFD_REBUILD_MIN;      // block-uniform
+        const bool force = step == 0 || rebuild_flag[step & 1] > REBUILD_MIN;      // block-uniform
         float dmax = 0.f, mv = 0.f;
 #pragma unroll
         for (int w = 0; w < (S > 1 ? MAX_WAVES : OWN_WAVES); ++w) {      // (split clouds: slots 8 ... hold the other members' maxima)
@@ -977,10 +966,7 @@ __device__ __forceinline__ void knn_phase(const f32x4* __restrict__ X, const Rep
         // Round 3, kernel launch of the bench workload / 512 clouds on the trained-like field (ms): 4 mv 836.6 / 186.5,
         // 3 mv 832.3, 2 mv 830.7, 1 mv 828.0 / 182.1, 0.5 mv 827.2 / 182.8, 0: 826.8 / 184.2 (certificate failures 4.6 k ->
         // 19 k -> 33 k -> 46 k per 512 clouds on the trained-like field).
-#ifndef IFD_SOFT_SLACK
-#define IFD_SOFT_SLACK 1.f
-#endif
-        const float soft_slack = IFD_SOFT_SLACK * mv;
+        const float soft_slack = SOFT_SLACK * mv;
         TRACE_STAMP(25, "s_waitcnt lgkmcnt(0)");              // flags and displacement maxima read
         PROF_T0();
         const bool need_a = pa < K && (force || ka.pend), need_b = pb < K && (force || kb.pend);
@@ -1098,12 +1084,10 @@ __device__ __forceinline__ void knn_phase(const f32x4* __restrict__ X, const Rep
         }
         ka.r5p = sqrtf(ta.d4);
         kb.r5p = sqrtf(tb.d4);
-        // a certificate about to expire: fragile ones are refreshed individually next step, the others
-        // mean the epoch is old -> whole-cloud rebuild next step
-        // (rebuild_flag counts the long-lived certificates about to expire; up to IFD_REBUILD_MIN of them are refreshed
-        // individually like the fragile ones instead of starting a new epoch for the whole cloud)
-        ka.pend = !soft_a && (ka.frag || IFD_REBUILD_MIN > 0);
-        kb.pend = !soft_b && (kb.frag || IFD_REBUILD_MIN > 0);
+        // a certificate about to expire is refreshed individually next step; the long-lived ones among them are counted in
+        // rebuild_flag, and more than REBUILD_MIN of them mean the epoch is old -> whole-cloud rebuild next step
+        ka.pend = !soft_a;
+        kb.pend = !soft_b;
         const int nbad = __popcll(__ballot(!soft_a && !ka.frag)) + __popcll(__ballot(!soft_b && !kb.frag));
         if (nbad != 0 && lane == 0) atomicAdd(const_cast<int*>(rebuild_flag) + ((step + 1) & 1), nbad);
         PROF_ACC(pc_eval);

@@ -848,21 +848,11 @@ hipError_t launch_optimize(const float* dec_img, const float* planes, float* p, 
     }
     if (split == 1 || K < 256) return IFD_PART(1, 0, B);      // (tiny clouds: nothing to share out)
     const int full = (B / n_cu) * n_cu, rest = B - full;
-#ifndef IFD_MIXED_TAIL
-#define IFD_MIXED_TAIL 0
-#endif
     // Measured per launch of n_cu / S clouds, in rounds of the unsplit kernel: S = 2 0.575, S = 4 0.365.  A rest
-    // between n_cu / 2 and 3 n_cu / 4 as n_cu / 2 clouds at S = 2 + the others at S = 4 adds up to 0.94 on paper; measured on
-    // the bench workload (2468 clouds: 9 rounds + 164) it is 820.4 ms against 812.6 with the rest as a tenth round - each
-    // launch's drain is exposed - so it is off.
-    const bool mixed = IFD_MIXED_TAIL && 2 * rest > n_cu && 4 * rest <= 3 * n_cu;
-    if (rest == 0 || (2 * rest > n_cu && !mixed)) return IFD_PART(1, 0, B);
+    // of more than n_cu / 2 clouds runs as one more unsplit round (DESIGN "Retired experiments": the mixed S = 2 + S = 4 tail).
+    if (rest == 0 || 2 * rest > n_cu) return IFD_PART(1, 0, B);
     if (full > 0) e = IFD_PART(1, 0, full);
     if (e != hipSuccess) return e;
-    if (mixed) {
-        e = IFD_PART(2, full, n_cu / 2);
-        return e != hipSuccess ? e : IFD_PART(4, full + n_cu / 2, rest - n_cu / 2);
-    }
     return 4 * rest <= n_cu ? IFD_PART(4, full, rest) : IFD_PART(2, full, rest);
 #undef IFD_PART
 }

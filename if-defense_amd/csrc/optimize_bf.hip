@@ -5,10 +5,10 @@
 
 namespace ifd {
 
-// 158,752 B (the moments are in global memory; the last 2 KB: one 256-byte landing strip per wave for the tap prefetches of tile_bf.h)
-constexpr size_t OPT_LDS_BF = (size_t)BF_IMG_BYTES + MAXK * 16 * 3 + 16 + MAXK * 12 + 128 * 4 + 8 * 256;
+// 156,704 B (the moments are in global memory)
+constexpr size_t OPT_LDS_BF = (size_t)BF_IMG_BYTES + MAXK * 16 * 3 + 16 + MAXK * 12 + 128 * 4;
 static_assert(OPT_LDS_BF <= 160 * 1024, "LDS budget");
-constexpr size_t LARGE_OCC_LDS_BF = (size_t)BF_IMG_BYTES + 8 * 256;     // large_occupancy3_kernel<1 | 2>: the piece image + the waves' landing strips
+constexpr size_t LARGE_OCC_LDS_BF = (size_t)BF_IMG_BYTES;               // large_occupancy3_kernel<1 | 2>: the piece image
 
 hipError_t configure_optimize_bf_kernels() {
     hipError_t e = hipSuccess;

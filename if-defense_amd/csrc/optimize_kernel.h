@@ -369,17 +369,7 @@ __device__ __forceinline__ void decoder_tile(const float* __restrict__ W, const 
 struct Mask8 {
     uint32_t w[2];
 };
-// v: pre-activations straight out of the MFMAs; rv: relu(v) as the compiler computed it.  The inline asm lists rv as an
-// (unused) input so that it is ordered behind the compiler's own first read of v - the compiler pads MFMA -> VALU
-// read-after-write hazards for its own instructions, not for inline asm.
-template <int BYTE>
-__device__ __forceinline__ void put_sign_byte(uint32_t& x, float v, float rv, int c31) {
-    if (BYTE == 0) asm("v_ashrrev_i32_sdwa %0, %1, %2 dst_sel:BYTE_0 dst_unused:UNUSED_PRESERVE src0_sel:DWORD src1_sel:DWORD" : "+v"(x) : "v"(c31), "v"(v), "v"(rv));
-    if (BYTE == 1) asm("v_ashrrev_i32_sdwa %0, %1, %2 dst_sel:BYTE_1 dst_unused:UNUSED_PRESERVE src0_sel:DWORD src1_sel:DWORD" : "+v"(x) : "v"(c31), "v"(v), "v"(rv));
-    if (BYTE == 2) asm("v_ashrrev_i32_sdwa %0, %1, %2 dst_sel:BYTE_2 dst_unused:UNUSED_PRESERVE src0_sel:DWORD src1_sel:DWORD" : "+v"(x) : "v"(c31), "v"(v), "v"(rv));
-    if (BYTE == 3) asm("v_ashrrev_i32_sdwa %0, %1, %2 dst_sel:BYTE_3 dst_unused:UNUSED_PRESERVE src0_sel:DWORD src1_sel:DWORD" : "+v"(x) : "v"(c31), "v"(v), "v"(rv));
-}
-__device__ __forceinline__ Mask8 mask_alive_packed(const f32x8& v, const f32x8& rv, int c31) {
+__device__ __forceinline__ Mask8 mask_alive_packed(const f32x8& v) {
     Mask8 m;
 #ifdef IFD_EXACT_REP          // the exact-arithmetic build (libifd_exact.so): torch's rule, threshold_backward passes where v > 0 -
                               // a pre-activation of exactly +0.0 is DEAD (the default build below keeps the sign bit: +0.0 alive)
@@ -391,23 +381,10 @@ __device__ __forceinline__ Mask8 mask_alive_packed(const f32x8& v, const f32x8& 
         asm volatile("" : "+v"(x));
         m.w[h] = x;
     }
-#elif defined(IFD_MASK_SDWA)          // round 2: one SDWA sign-byte shift per value (+ one s_nop between partial writes of a word) and a v_not
-#pragma unroll
-    for (int h = 0; h < 2; ++h) {
-        uint32_t x;                                  // byte 3 - r of word h: 0xff where value 4 h + r has its sign bit set
-        asm("v_ashrrev_i32_sdwa %0, %1, %2 dst_sel:BYTE_3 dst_unused:UNUSED_PAD src0_sel:DWORD src1_sel:DWORD"
-            : "=v"(x) : "v"(c31), "v"(v[4 * h + 0]), "v"(rv[4 * h + 0]));
-        put_sign_byte<2>(x, v[4 * h + 1], rv[4 * h + 1], c31);
-        put_sign_byte<1>(x, v[4 * h + 2], rv[4 * h + 2], c31);
-        put_sign_byte<0>(x, v[4 * h + 3], rv[4 * h + 3], c31);
-        x = ~x;
-        asm volatile("" : "+v"(x));
-        m.w[h] = x;
-    }
 #else
     // v_perm_b32 can replicate the sign bit of either source DWORD into a result byte (selector 11: bit 31 of src0, 9: bit 31
     // of src1; 12: 0x00), so one instruction extracts the sign bytes of TWO values; the two half-filled words have disjoint
-    // bytes, and v_xnor = ~(a ^ b) = ~(a | b) merges and inverts them in one go: 3 instructions per 4 values instead of 4
+    // bytes, and v_xnor = ~(a ^ b) = ~(a | b) merges and inverts them in one go: 3 instructions per 4 values instead of round 2's 4
     // SDWA shifts + their 3 hazard nops + a v_not (34 against ~65 SIMD cycles per 8 values, scripts/valu_rates.hip).
 #pragma unroll
     for (int h = 0; h < 2; ++h) {
@@ -421,63 +398,10 @@ __device__ __forceinline__ Mask8 mask_alive_packed(const f32x8& v, const f32x8& 
     return m;
 }
 
-// relu(v) * 2^-RELU_K for the eight values of a sub-tile and layer: four v_pk_mul_f32 ... clamp (ifd_device.h "packed ReLU").
-// The instruction is inline asm (clang folds the clamp into scalar multiplies only), and the compiler pads MFMA -> VALU
-// read-after-write hazards for its own instructions, not for inline asm: each statement therefore takes the mask word of its
-// M-tile as an (unused) input - the v_perm that made that word is the compiler's own read of the same MFMA result quad.
-__device__ __forceinline__ f32x8 relu8s(const f32x8& v, const Mask8& m, unsigned long long sc2) {
-    f32x8 o;
-#pragma unroll
-    for (int h = 0; h < 4; ++h) {
-#ifdef IFD_RELU_NOASM
-        o[2 * h] = fminf(fmaxf(v[2 * h] * RELU_DN, 0.f), 1.f);
-        o[2 * h + 1] = fminf(fmaxf(v[2 * h + 1] * RELU_DN, 0.f), 1.f);
-#else
-        const f32x2 in = {v[2 * h], v[2 * h + 1]};
-        f32x2 out;
-        asm("v_pk_mul_f32 %0, %1, %2 op_sel_hi:[1,0] clamp" : "=v"(out) : "v"(in), "s"(sc2), "v"(m.w[h >> 1]));
-        o[2 * h] = out.x;
-        o[2 * h + 1] = out.y;
-#endif
-    }
-    return o;
-}
-// (the pair of relu and mask of one sub-tile and layer, either way)
-__device__ __forceinline__ void relu_and_mask(const f32x8& v, int c31, unsigned long long sc2, f32x8& r, Mask8& m) {
-    if (RELU_K != 0) {
-        m = mask_alive_packed(v, v, c31);
-        r = relu8s(v, m, sc2);
-    } else {
-        r = relu8(v);
-        m = mask_alive_packed(v, r, c31);
-    }
-}
-// d += t * 2^-2K (RELU_K != 0: the transposed fc_1 / fc_0 products carry 2^2K) or d += t: four packed instructions either way
-__device__ __forceinline__ void add8_scaled(f32x8& d, const f32x8& t) {
-    if (RELU_K == 0) {
-#pragma unroll
-        for (int h = 0; h < 4; ++h) {
-            const f32x2 v = f32x2{d[2 * h], d[2 * h + 1]} + f32x2{t[2 * h], t[2 * h + 1]};
-            d[2 * h] = v.x; d[2 * h + 1] = v.y;
-        }
-    } else {
-        // (inline asm: left to itself the compiler turns the constant operand into eight scalar v_fma_f32; the inputs come from
-        // vector instructions - the mask application - so there is no MFMA hazard to pad here)
-        constexpr unsigned int cb = __builtin_bit_cast(unsigned int, RELU_DN2);
-        const unsigned long long c2 = ((unsigned long long)cb << 32) | cb;
-#pragma unroll
-        for (int h = 0; h < 4; ++h) {
-#ifdef IFD_RELU_NOASM
-            d[2 * h] = __builtin_fmaf(t[2 * h], RELU_DN2, d[2 * h]);
-            d[2 * h + 1] = __builtin_fmaf(t[2 * h + 1], RELU_DN2, d[2 * h + 1]);
-#else
-            f32x2 v = {d[2 * h], d[2 * h + 1]};
-            const f32x2 tt = {t[2 * h], t[2 * h + 1]};
-            asm("v_pk_fma_f32 %0, %1, %2, %0 op_sel_hi:[1,0,1]" : "+v"(v) : "v"(tt), "s"(c2));
-            d[2 * h] = v.x; d[2 * h + 1] = v.y;
-#endif
-        }
-    }
+// (the pair of relu and mask of one sub-tile and layer)
+__device__ __forceinline__ void relu_and_mask(const f32x8& v, f32x8& r, Mask8& m) {
+    r = relu8(v);
+    m = mask_alive_packed(v);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -522,18 +446,8 @@ __device__ __forceinline__ void mfma16(const WFrag& f, const f32x8& in, Acc2& ac
 // interleave pattern of one region: 4 x { 4 MFMAs, 4 NV VALU, 4 ND DS reads }, then close the region.  (An f32 MFMA and a
 // vector instruction exclude each other on the SIMD and every switch between the two kinds costs issue cycles, so they
 // alternate in groups, not one by one.)
-// -DIFD_EXTRA_VALU=<n>: n dummy vector instructions per software-pipeline region (measurement only: what ONE more vector
-// instruction next to the MFMA stream costs in the real kernel - scripts/ab_bench.sh)
-#ifndef IFD_EXTRA_VALU
-#define IFD_EXTRA_VALU 0
-#endif
 template <int NV, int ND>
 __device__ __forceinline__ void region_end() {
-    if (IFD_EXTRA_VALU > 0) {
-        int dummy = 0;
-#pragma unroll
-        for (int k = 0; k < IFD_EXTRA_VALU; ++k) asm volatile("v_add_u32 %0, 1, %0" : "+v"(dummy));
-    }
     constexpr int GROUP = 4;         // 2: 418 k, 4 / 8: 412 k, 16: 413 k cycles per step (one by one: 428 k)
 #pragma unroll
     for (int i = 0; i < 16 / GROUP; ++i) {
@@ -708,18 +622,6 @@ __device__ __forceinline__ void decoder_tile3(const float* __restrict__ W, __amd
             const SubGeo& g = geo[t];
             const float wnw = g.w0[a0] * g.w0[a1], wne = g.w1[a0] * g.w0[a1], wsw = g.w0[a0] * g.w1[a1],
                         wse = g.w1[a0] * g.w1[a1];
-#ifdef IFD_SAMPLE_SCALAR
-#pragma unroll
-            for (int mt = 0; mt < 2; ++mt)
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {      // (one fma chain over all 12 taps measured +2.6 %)
-                    float s = tap[t][0][mt][j] * wnw;
-                    s = fmaf(tap[t][1][mt][j], wne, s);
-                    s = fmaf(tap[t][2][mt][j], wsw, s);
-                    s = fmaf(tap[t][3][mt][j], wse, s);
-                    c[t][4 * mt + j] += s;
-                }
-#else
             // packed along the channels like the backward sampling: the taps arrive as aligned register pairs, the weight is
             // broadcast by op_sel - 5 v_pk instructions per channel pair instead of 10 scalar ones, same operation order
             const f32x2 wnw2 = {wnw, wnw}, wne2 = {wne, wne}, wsw2 = {wsw, wsw}, wse2 = {wse, wse};
@@ -735,7 +637,6 @@ __device__ __forceinline__ void decoder_tile3(const float* __restrict__ W, __amd
                     c[t][4 * mt + 2 * h] = cc.x;
                     c[t][4 * mt + 2 * h + 1] = cc.y;
                 }
-#endif
         }
     };
     {
@@ -788,10 +689,10 @@ __device__ __forceinline__ void decoder_tile3(const float* __restrict__ W, __amd
     Mask8 mask_a[2][NBLK], mask_h[2][NBLK];
     f32x8 wout;
     float bout = 0.f, ilb = 0.f;
-    int c31 = 31;                                  // shift count of the sign-byte extraction (an SDWA operand must be a register)
+    // (unused since the SDWA form of the ReLU masks was retired, DESIGN "Retired experiments": one v_mov whose removal moves the
+    // tile's schedule - it goes with the next change to this tile's device code)
+    int c31 = 31;
     asm volatile("" : "+v"(c31));
-    // 2^-RELU_K in both halves of an SGPR pair (the packed ReLU's second operand)
-    const unsigned long long sc2 = ((unsigned long long)__builtin_bit_cast(unsigned int, RELU_DN) << 32) | __builtin_bit_cast(unsigned int, RELU_DN);
 #pragma unroll
     for (int i = 0; i < NBLK; ++i) {
         const float* Wl = Wd + 3 * i * W_LAYER;
@@ -805,14 +706,14 @@ __device__ __forceinline__ void decoder_tile3(const float* __restrict__ W, __amd
         mfma16(A, c[1], a1);
         const f32x8 af0 = flat(a0);
         f32x8 ra0;
-        relu_and_mask(af0, c31, sc2, ra0, mask_a[0][i]);
+        relu_and_mask(af0, ra0, mask_a[0][i]);
         region_end<TV, 1>();
         T2(5 + 6 * i + 1);
         Acc2 h0 = B0;                                                          // R3
         mfma16(A0, ra0, h0);
         const f32x8 af1 = flat(a1);
         f32x8 ra1;
-        relu_and_mask(af1, c31, sc2, ra1, mask_a[1][i]);
+        relu_and_mask(af1, ra1, mask_a[1][i]);
         region_end<TV, 0>();
         T2(5 + 6 * i + 2);
         const WFrag A1 = load_wfrag<false>(Wl + 2 * W_LAYER, lo);             // R4: prefetch fc_1
@@ -821,14 +722,14 @@ __device__ __forceinline__ void decoder_tile3(const float* __restrict__ W, __amd
         mfma16(A0, ra1, h1);
         const f32x8 hf0 = flat(h0);
         f32x8 rh0;
-        relu_and_mask(hf0, c31, sc2, rh0, mask_h[0][i]);
+        relu_and_mask(hf0, rh0, mask_h[0][i]);
         region_end<TV, 1>();
         T2(5 + 6 * i + 3);
         Acc2 o0 = acc_add(B1, a0);                                             // R5
         mfma16(A1, rh0, o0);
         const f32x8 hf1 = flat(h1);
         f32x8 rh1;
-        relu_and_mask(hf1, c31, sc2, rh1, mask_h[1][i]);
+        relu_and_mask(hf1, rh1, mask_h[1][i]);
         region_end<TV, 0>();
         T2(5 + 6 * i + 4);
         if (i + 1 < NBLK) {                                                    // R6: prefetch next fc_c / first fc_1^T
@@ -859,7 +760,7 @@ __device__ __forceinline__ void decoder_tile3(const float* __restrict__ W, __amd
         const f32x8 nf = flat(net[t]);
         f32x8 rn;
         Mask8 mask_n;
-        relu_and_mask(nf, c31, sc2, rn, mask_n);
+        relu_and_mask(nf, rn, mask_n);
         float part = 0.f;
 #pragma unroll
         for (int r = 0; r < 8; ++r) part = fmaf(wout[r], rn[r], part);
@@ -869,11 +770,7 @@ __device__ __forceinline__ void decoder_tile3(const float* __restrict__ W, __amd
         if (MODE == MODE_OPT) {
             // BCE-with-logits against the threshold (opt_defense.py:213-216): d/dlogit = (sigmoid - thr) / B.  The
             // loss value itself is only reported for the last step.
-#ifdef IFD_FAST_SIGMOID_EXP
-            const float e = __expf(-fabsf(logit));
-#else
-            const float e = expf(-fabsf(logit));       // (v_exp_f32 directly: 379.2 against 380.0 k cycles per step - not taken)
-#endif
+            const float e = expf(-fabsf(logit));
             const float rc = __builtin_amdgcn_rcpf(1.f + e);
             const float sig = logit >= 0.f ? rc : e * rc;
             dl = (sig - thr) * ilb;
@@ -884,9 +781,8 @@ __device__ __forceinline__ void decoder_tile3(const float* __restrict__ W, __amd
         }
         {
             f32x8 dw;
-            const float dls = RELU_K != 0 ? dl * RELU_DN : dl;      // (fc_out sits in the image times 2^K: same products)
 #pragma unroll
-            for (int r = 0; r < 8; ++r) dw[r] = dls * wout[r];
+            for (int r = 0; r < 8; ++r) dw[r] = dl * wout[r];
             dn[t] = masked(dw, mask_n);
         }
     }
@@ -919,14 +815,14 @@ __device__ __forceinline__ void decoder_tile3(const float* __restrict__ W, __amd
         mfma16(A0, dh1, y1);
         {
             const f32x8 t = masked(y0, mask_a[0][i]);
-            add8_scaled(dn[0], t);                                             // delta a_i
+            add8_pk(dn[0], t);                                             // delta a_i
         }
         region_end<1, 1>();
         T2(36 + 6 * (NBLK - 1 - i) + 3);
         mfma16(Ac, dn[0], dcc[0]);                                             // R5: dc += fc_c^T da (sub-tile 0)
         {
             const f32x8 t = masked(y1, mask_a[1][i]);
-            add8_scaled(dn[1], t);
+            add8_pk(dn[1], t);
         }
         region_end<1, 0>();
         T2(36 + 6 * (NBLK - 1 - i) + 4);
@@ -1178,10 +1074,7 @@ __global__ __launch_bounds__(NW * 64, NW / 4) void optimize_kernel(
     __syncthreads();
 #endif
 
-#ifndef IFD_CARRY_KNNPT
-#define IFD_CARRY_KNNPT 1             // S = 1: the certificates stay in registers from the Adam phase into the next step's kNN phase
-#endif
-    constexpr bool CARRY = S == 1 && IFD_CARRY_KNNPT != 0;
+    constexpr bool CARRY = S == 1;        // the certificates stay in registers from the Adam phase into the next step's kNN phase
     KnnPt ka_c = {0, -1, 0.f, 0.f, 2.0f, 7.0f, f32x4{0.f, 0.f, 0.f, 0.f}, 0.f, 0.f, false, false}, kb_c = ka_c;
 // [pcsamp:step.head]
     for (int step = 0; step < A.steps; ++step) {
@@ -1215,7 +1108,7 @@ __global__ __launch_bounds__(NW * 64, NW / 4) void optimize_kernel(
 #endif
         // Split clouds: eight (S = 2) or four (S = 4) of a member's waves have neighbour duty, and a kNN wave beside a
         // priority-1 tile wave is starved for a whole tile (measured: 100 k cycles for its 25 k of work), so the kNN phase runs
-        // FIRST at wave priority 2 (IFD_SPLIT_KNN_PRIO).  Measured at S = 2 / 4 (53 clouds x 501 steps, one S = 1 round:
+        // FIRST at wave priority 2.  Measured at S = 2 / 4 (53 clouds x 501 steps, one S = 1 round:
         // 83.1 ms): 47.7 / 30.3 ms; without the priority 48.1 / 32.3; tiles first, kNN at the end of the step 50.6 / 34.5.
         // (S = 1, where every wave has neighbour duty: letting the upper four waves run one tile before their kNN phase, so
         // that on every SIMD one wave searches while the other feeds the MFMA pipe, measured 912 ms against 807.6 on the
@@ -1239,20 +1132,15 @@ __global__ __launch_bounds__(NW * 64, NW / 4) void optimize_kernel(
 #ifdef IFD_TRACE2
                 unsigned long long* tr2 = (cn.pc != nullptr && trace_tile == IFD_TRACE2) ? counters + TRACE2_BASE + wave * 128 : nullptr;
                 if (tr2 != nullptr && lane == 0) tr2[71] = (unsigned long long)tile;
+#else
+                constexpr unsigned long long* tr2 = nullptr;
+#endif
                 if (PREC == 0)
                     decoder_tile3<MODE_OPT>(W, plr, PIX[tpa], PIX[tpb], Xf[4 * tpa], Xf[4 * tpb], lane, dc,
                                             A.threshold, inv_lb, want_loss, bce, dx, tr2);
                 else
                     decoder_tile3_bf<MODE_OPT, PREC>(W, plr, PIX[tpa], PIX[tpb], Xf[4 * tpa], Xf[4 * tpb], lane, dc,
-                                                     A.threshold, want_loss, bce, dx, scratch + 128 + 64 * wave, tr2);
-#else
-                if (PREC == 0)
-                    decoder_tile3<MODE_OPT>(W, plr, PIX[tpa], PIX[tpb], Xf[4 * tpa], Xf[4 * tpb], lane, dc,
-                                            A.threshold, inv_lb, want_loss, bce, dx);
-                else
-                    decoder_tile3_bf<MODE_OPT, PREC>(W, plr, PIX[tpa], PIX[tpb], Xf[4 * tpa], Xf[4 * tpb], lane, dc,
-                                                     A.threshold, want_loss, bce, dx, scratch + 128 + 64 * wave);
-#endif
+                                                     A.threshold, want_loss, bce, dx, tr2);
                 if (lane < 16) {
                     if (ia < K) G[tpa] = f32x4{dx[0][0], dx[0][1], dx[0][2], bce[0]};
                     if (ib < K) G[tpb] = f32x4{dx[1][0], dx[1][1], dx[1][2], bce[1]};
@@ -1264,16 +1152,10 @@ __global__ __launch_bounds__(NW * 64, NW / 4) void optimize_kernel(
             }
         };
 // [pcsamp:step.knn_call]
-#ifndef IFD_SPLIT_KNN_PRIO
-#define IFD_SPLIT_KNN_PRIO 2          // 0: tiles first (kNN at the end of the step); 1 / 2 / 3: kNN first at that wave priority
-#endif
-        if (S > 1 && IFD_SPLIT_KNN_PRIO == 0) { PROF_T0(); run_tiles(); }
         // ---- kNN + repulsion of the points this wave owns (all waves at the same time: a VALU-only wave next to an
         //      MFMA-heavy tile wave on a SIMD is starved, f32 MFMA and VALU issue do not overlap on gfx950) -------------
         if (wave < OW && use_rep) {
-            if (S > 1 && IFD_SPLIT_KNN_PRIO == 1) asm volatile("s_setprio 1");
-            if (S > 1 && IFD_SPLIT_KNN_PRIO == 2) asm volatile("s_setprio 2");
-            if (S > 1 && IFD_SPLIT_KNN_PRIO == 3) asm volatile("s_setprio 3");
+            if (S > 1) asm volatile("s_setprio 2");
             float rep_loss_a, rep_loss_b;
             // (one workgroup per cloud: the Adam phase of the last step left the certificates in registers - no scratch round
             // trip in front of the step's first dependent work)
@@ -1304,11 +1186,11 @@ __global__ __launch_bounds__(NW * 64, NW / 4) void optimize_kernel(
                     coop_publish();
                     if (lane == 0) { *knn_done = 0; if (arrives) coop_arrive(&cv.ws->bar_knn); }
                 }
-                if (IFD_SPLIT_KNN_PRIO != 0) asm volatile("s_setprio 0");
+                asm volatile("s_setprio 0");
             }
         }
-        if (S == 1 || IFD_SPLIT_KNN_PRIO != 0) { PROF_T0(); run_tiles(); }
-        if (PREC != 0) asm volatile("s_setprio 0");          // (the split-precision tile leaves its edge priority set)
+        PROF_T0();
+        run_tiles();
         PROF_ACC(pc_tiles);
 // [pcsamp:step.adam]
         // ---- Adam: its state comes back from scratch under the barrier wait ------------------------------------------------
@@ -1479,7 +1361,6 @@ __global__ __launch_bounds__(OPT_THREADS, 1) void large_occupancy3_kernel(
     extern __shared__ __attribute__((aligned(16))) float smem[];
     constexpr int IMG_FLOATS = PREC == 0 ? DEC_FLOATS : BF_IMG_BYTES / 4;
     float* W = smem;
-    [[maybe_unused]] float* strips = smem + IMG_FLOATS;              // PREC > 0: one 256-byte landing strip per wave (tile_bf.h)
     const int cloud = blockIdx.x, tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     load_dec_image(W, dec_img, IMG_FLOATS);
@@ -1505,10 +1386,8 @@ __global__ __launch_bounds__(OPT_THREADS, 1) void large_occupancy3_kernel(
         float bce[2], dx[2][3];
         if constexpr (PREC == 0)
             decoder_tile3<MODE_OPT>(W, plr, ppa, ppb, xqa, xqb, lane, dc, thr, inv_lb, want_loss, bce, dx);
-        else {
-            decoder_tile3_bf<MODE_OPT, PREC>(W, plr, ppa, ppb, xqa, xqb, lane, dc, thr, want_loss, bce, dx, strips + 64 * wave);
-            asm volatile("s_setprio 0");
-        }
+        else
+            decoder_tile3_bf<MODE_OPT, PREC>(W, plr, ppa, ppb, xqa, xqb, lane, dc, thr, want_loss, bce, dx);
         if (lane < 16) {
             if (ia < K) G[(size_t)cloud * K + tpa] = f32x4{dx[0][0], dx[0][1], dx[0][2], bce[0]};
             if (ib < K) G[(size_t)cloud * K + tpb] = f32x4{dx[1][0], dx[1][1], dx[1][2], bce[1]};

@@ -56,17 +56,6 @@ __device__ __forceinline__ void dense_bf(const WFragBF& A, const Pieces& P, Acc2
 // wave only overlaps what is adjacent in its instruction stream; left to itself hipcc issues the twelve MFMAs first and the
 // split chain behind them with ~25 wait states between its steps).  The order is pinned with scheduling barriers.
 #define BF_SB() __builtin_amdgcn_sched_barrier(0)
-// Wave priorities (a tuning knob, off by default: measured within 2 %): the sections around the MLP at IFD_BF_PRIO_EDGE, the MLP
-// sections at IFD_BF_PRIO_MLP.
-#ifndef IFD_BF_PRIO_EDGE
-#define IFD_BF_PRIO_EDGE 0
-#endif
-#ifndef IFD_BF_PRIO_MLP
-#define IFD_BF_PRIO_MLP 0
-#endif
-#define BF_PRIO_STR2(x) #x
-#define BF_PRIO_STR(x) BF_PRIO_STR2(x)
-#define BF_PRIO(p) do { if (IFD_BF_PRIO_EDGE != IFD_BF_PRIO_MLP) asm volatile("s_setprio " BF_PRIO_STR(p)); } while (0)
 template <int PREC>
 __device__ __forceinline__ void dense_one(const WFragBF& A, const Pieces& P, Acc2& acc, int k) {        // MFMA k of the layer: term k / 2, M-tile k % 2
     constexpr int TA6[6] = {2, 0, 1, 1, 0, 0}, TP6[6] = {0, 2, 1, 0, 1, 0};
@@ -209,17 +198,12 @@ template <int MODE, int PREC>
 __device__ __forceinline__ void decoder_tile3_bf(const float* __restrict__ Wg, __amdgpu_buffer_rsrc_t planes,
                                                  const f32x4 ppa, const f32x4 ppb, float xqa, float xqb, int lane,
                                                  const DecConst dc, float thr, bool want_loss, float (&bce)[2], float (&dx)[2][3],
-                                                 [[maybe_unused]] float* pf_strip, [[maybe_unused]] unsigned long long* tr = nullptr) {
+                                                 [[maybe_unused]] unsigned long long* tr = nullptr) {
     T2(0);                                       // (-DIFD_TRACE2 stamps: decoder_tile3's slot map, scripts/tile_trace.py)
-    BF_PRIO(IFD_BF_PRIO_EDGE);
     const lds_u8* Wb = (const lds_u8*)Wg;
     const int n = lane & 15, q = lane >> 4;
     int lane_off = lane * BF_ENTRY_BYTES;
-#ifdef IFD_BF_TIMING_TR_LINEAR                   // timing experiment, WRONG results: the transposed reads without their bank conflicts
-    int lane_off_t = lane * 8;
-#else
     int lane_off_t = ((lane & 3) * 16 + 4 * q + ((lane >> 2) & 3)) * BF_ENTRY_BYTES;
-#endif
     int q4 = 4 * q;
     asm volatile("" : "+v"(lane_off), "+v"(lane_off_t), "+v"(q4));
     constexpr int AX0[3] = {0, 0, 1}, AX1[3] = {2, 1, 2};   // xz, xy, yz (common.py:243-248)
@@ -245,20 +229,8 @@ __device__ __forceinline__ void decoder_tile3_bf(const float* __restrict__ Wg, _
 #pragma unroll
         for (int r = 0; r < 8; ++r) c[t][r] = 0.f;
     const int q16 = 16 * q;
-#ifndef IFD_BF_TIMING_NOGATHER
-#define IFD_BF_TIMING_NOGATHER 0      // timing experiments with WRONG results: 1 no backward re-gather, 2 no gather at all
-#endif
     auto load_taps = [&](int P, f32x4 (&tap)[2][4][2], bool opaque) {
         const int a0 = AX0[P], a1 = AX1[P];
-        if ((IFD_BF_TIMING_NOGATHER == 1 && opaque) || IFD_BF_TIMING_NOGATHER == 2) {
-#pragma unroll
-            for (int t = 0; t < 2; ++t)
-#pragma unroll
-                for (int k = 0; k < 4; ++k)
-#pragma unroll
-                    for (int mt = 0; mt < 2; ++mt) tap[t][k][mt] = f32x4{geo[t].w0[a0], geo[t].w1[a1], 0.5f, 0.25f};
-            return;
-        }
 #pragma unroll
         for (int t = 0; t < 2; ++t) {
             int off = (geo[t].cell[a1] * RES + geo[t].cell[a0]) * (CH * 4) + (P * PLANE_FLOATS * 4 + q16);
@@ -276,41 +248,19 @@ __device__ __forceinline__ void decoder_tile3_bf(const float* __restrict__ Wg, _
             }
         }
     };
-    // L2 prefetch of the tile's 384 tap lines (3 planes x 2 rows x [32 points x 2 columns]) with six LDS-DMA loads - one dword per lane
-    // and line, no destination registers (buffer_load ... lds into this wave's 256-byte landing strip, never read): the backward
-    // pass re-gathers the taps ~15 k cycles after the forward gather fetched them, by which time they have left the XCD's L2
-    // (its 4 MB turn over in ~7 us under 32 CUs' gathers).  Lane (n, q) takes point n of sub-tile q & 1, column q >> 1.
-#ifndef IFD_BF_PREFETCH
-#define IFD_BF_PREFETCH 0      // measured: +11 % (bf16x6) / +27 % (bf16x3) - the kernel is bound by the tap TRAFFIC, not by its latency (profiles/r05_ab_bf_prefetch.txt)
-#endif
-    auto prefetch_taps = [&]() {
-        const bool t1 = (q & 1) != 0;
-#pragma unroll
-        for (int P = 0; P < 3; ++P) {
-            const int a0 = AX0[P], a1 = AX1[P];
-            const int cx = (t1 ? geo[1].cell[a0] : geo[0].cell[a0]) + (q >> 1), cy = t1 ? geo[1].cell[a1] : geo[0].cell[a1];
-#pragma unroll
-            for (int h = 0; h < 2; ++h) {
-                const int off = ((cy + h) * RES + cx) * (CH * 4) + P * PLANE_FLOATS * 4;
-                __builtin_amdgcn_raw_ptr_buffer_load_lds(planes, (__attribute__((address_space(3))) void*)pf_strip, 4, off, 0, 0, 0);
-            }
-        }
-    };
     // NO packed-f32 instruction anywhere in this tile (nor, through -fno-slp-vectorize, in the rest of this kernel): beside a wave
     // that streams bf16 MFMAs, a v_pk_mul_f32 / v_pk_fma_f32 / v_pk_add_f32 whose consumer does not follow back to back
     // occasionally delivers a wrong result on gfx950 (scripts/pk_mfma_coexec.hip, profiles/r05_pk_mfma_coexec.txt: 0 wrong of 5e9
     // beside an idle or an f32-MFMA partner, 16 ... 300 of 5e9 beside a bf16-MFMA partner - ~1 % of a launch's sub-tiles here).
     // decoder_tile3's packed sampling is therefore spelled out value by value: same operations, same order, same roundings.
-    // The sampling Jacobian (IFD_BF_JAC; default: bf16x3 only): d c[ch] / d pix along the plane's two axes, summed over the planes that share an
+    // The sampling Jacobian (JAC: bf16x3 only): d c[ch] / d pix along the plane's two axes, summed over the planes that share an
     // axis - 3 x 8 values per lane and sub-tile, parked in scratch across the MLP - replaces the backward pass's re-gather of the taps
     // (48 KB of 128-byte lines per tile and wave, the kernel's largest HBM stream: profiles/r05_ab_bf_gather.txt) by 12 KB of
     // coalesced scratch stores and loads.  J[t][a][ch]: axis 0 <- planes 0, 1; axis 1 <- planes 1, 2; axis 2 <- planes 0, 2.
     // Measured on the bench workload (profiles/r05_ab_bf_jacobian.txt): bf16x3 4068 -> 4263 clouds/s (+4.8 %, -11 % cycles per step);
     // bf16x6 3531 -> 3458 (-2 %: 2 % fewer cycles, but the ~200 extra vector instructions per tile pull the clock from 2.14 to 2.06
     // GHz - that kernel sits at the socket's power limit, profiles/r05_power_clock.txt).  So: on for bf16x3, off for bf16x6.
-#ifndef IFD_BF_JAC
-#define IFD_BF_JAC (PREC == 2)
-#endif
+    constexpr bool JAC = PREC == 2;
     [[maybe_unused]] float J[2][3][8];
     auto sample_fwd = [&](int P, const f32x4 (&tap)[2][4][2]) {
         const int a0 = AX0[P], a1 = AX1[P];
@@ -328,7 +278,7 @@ __device__ __forceinline__ void decoder_tile3_bf(const float* __restrict__ Wg, _
                     s1 = __builtin_fmaf(tap[t][2][mt][j], wsw, s1);
                     s1 = __builtin_fmaf(tap[t][3][mt][j], wse, s1);
                     c[t][4 * mt + j] = P == 0 ? s1 : c[t][4 * mt + j] + s1;
-                    if (IFD_BF_JAC && MODE == MODE_OPT) {
+                    if (JAC && MODE == MODE_OPT) {
                         const float nw = tap[t][0][mt][j], ne = tap[t][1][mt][j], sw = tap[t][2][mt][j], se = tap[t][3][mt][j];
                         const float jx = __builtin_fmaf(se - sw, g.w1[a1], (ne - nw) * g.w0[a1]);       // along a0
                         const float jy = __builtin_fmaf(se - ne, g.w1[a0], (sw - nw) * g.w0[a0]);       // along a1
@@ -369,7 +319,7 @@ __device__ __forceinline__ void decoder_tile3_bf(const float* __restrict__ Wg, _
     }
     // park the Jacobian (12 x 16 bytes per lane; a 256-byte private array indexed through an opaque zero: knn_device.h "Parking")
     [[maybe_unused]] f32x4 jpark[16];
-    if (IFD_BF_JAC && MODE == MODE_OPT) {
+    if (JAC && MODE == MODE_OPT) {
         const int z = opaque_zero();
 #pragma unroll
         for (int t = 0; t < 2; ++t)
@@ -398,15 +348,14 @@ __device__ __forceinline__ void decoder_tile3_bf(const float* __restrict__ Wg, _
     split_bf<PREC>(c[1], sel, PC[1]);
     __builtin_amdgcn_sched_barrier(0);
     T2(4);
-    BF_PRIO(IFD_BF_PRIO_MLP);
 
     // ---- forward MLP -----------------------------------------------------------------------------------------------
     Mask8 mask_a[2][NBLK], mask_h[2][NBLK];
     f32x8 wout;
     float bout = 0.f, ilb = 0.f;
+    // (unused, like decoder_tile3's: kept for the schedule)
     int c31 = 31;
     asm volatile("" : "+v"(c31));
-    const unsigned long long sc2 = 0ull;           // (packed-ReLU scale of decoder_tile3: RELU_K = 0 here)
 #pragma unroll
     for (int i = 0; i < NBLK; ++i) {
         // fc_c: a = n + fc_c(c)   (bias folded into n)
@@ -450,7 +399,6 @@ __device__ __forceinline__ void decoder_tile3_bf(const float* __restrict__ Wg, _
         T2(5 + 6 * i + 5);
     }
     // ---- logit, loss derivative, seed of the backward pass (decoder_tile3's) ---------------------------------------------
-    BF_PRIO(IFD_BF_PRIO_EDGE);
     f32x8 dn[2];
     Pieces PD[2];
 #pragma unroll
@@ -458,7 +406,7 @@ __device__ __forceinline__ void decoder_tile3_bf(const float* __restrict__ Wg, _
         const f32x8 nf = flat(net[t]);
         f32x8 rn;
         Mask8 mask_n;
-        relu_and_mask(nf, c31, sc2, rn, mask_n);
+        relu_and_mask(nf, rn, mask_n);
         float part = 0.f;
 #pragma unroll
         for (int r = 0; r < 8; ++r) part = fmaf(wout[r], rn[r], part);
@@ -483,9 +431,7 @@ __device__ __forceinline__ void decoder_tile3_bf(const float* __restrict__ Wg, _
     }
     __builtin_amdgcn_sched_barrier(0);
     T2(35);
-    BF_PRIO(IFD_BF_PRIO_MLP);
 
-    if (IFD_BF_PREFETCH & 1) prefetch_taps();      // (for the re-gather behind the backward MLP; off: see IFD_BF_PREFETCH)
     // ---- backward (A holds fc_1[4]^T) --------------------------------------------------------------------------------------
     Acc2 dcc[2] = {acc_zero(), acc_zero()};
 #pragma unroll
@@ -519,7 +465,6 @@ __device__ __forceinline__ void decoder_tile3_bf(const float* __restrict__ Wg, _
         T2(36 + 6 * (NBLK - 1 - i) + 5);
     }
     // ---- fc_p backward and d c / d u through the re-gathered taps (decoder_tile3's) -----------------------------------------
-    BF_PRIO(IFD_BF_PRIO_EDGE);
     float g[2][3];
 #pragma unroll
     for (int t = 0; t < 2; ++t) g[t][0] = g[t][1] = g[t][2] = 0.f;
@@ -534,7 +479,7 @@ __device__ __forceinline__ void decoder_tile3_bf(const float* __restrict__ Wg, _
                 g[t][0] = fmaf(wp.x, d, g[t][0]); g[t][1] = fmaf(wp.y, d, g[t][1]); g[t][2] = fmaf(wp.z, d, g[t][2]);
             }
         }
-    if (IFD_BF_JAC && MODE == MODE_OPT) {
+    if (JAC && MODE == MODE_OPT) {
         // d c / d u from the parked Jacobian: g[a] += lk[a] * sum_ch J[a][ch] dc[ch]  (even / odd channel partial sums)
         const f32x8 dcj[2] = {flat(dcc[0]), flat(dcc[1])};
         const int z = opaque_zero();

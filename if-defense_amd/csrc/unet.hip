@@ -23,9 +23,7 @@ namespace ifd {
 
 constexpr int CK = 16;               // input channels per LDS chunk
 constexpr int CKP = CK + 1;          // padded pixel stride in LDS (floats)
-#ifndef IFD_UNET_PW
-#define IFD_UNET_PW 2                 // 32-pixel sub-tiles per wave of the 3x3 layers at 16^2 ... 64^2 (A/B: -DIFD_UNET_PW=1)
-#endif
+constexpr int UNET_PW = 2;           // 32-pixel sub-tiles per wave of the 3x3 layers at 16^2 ... 64^2
 
 struct ConvArgs {
     const float* in0;      // first input  [N][H][W][C0]
@@ -255,7 +253,6 @@ static hipError_t launch_conv(const ConvArgs& a, int n_img, hipStream_t s) {
 // ---------------------------------------------------------------------------------------------
 __device__ __forceinline__ int wswz(int r) { return (r >> 2) & 2; }        // piece kq of row r sits at kq ^ wswz(r & 15)
 
-typedef unsigned int u32x4w __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ __amdgpu_buffer_rsrc_t wino_rsrc(const float* p, unsigned int bytes) {
     return __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p), 0, (int)bytes, 0x00020000);
 }
@@ -511,13 +508,8 @@ __global__ __launch_bounds__(64 * TG * CG, TG * CG == 4 ? 2 : 1) void wino_kerne
         constexpr int TRS = 36;                                            // row of the activated tile T[128 pixels][32 ch] (floats)
         // (Sending EVERY layer's tile through LDS - T[pixel][32 ch], then 16-byte stores of whole 128-byte pixel rows instead of 20
         // four-byte stores per lane from the accumulator layout - was measured: 53.3 against 50.0 ms for the U-Net, the two extra
-        // barriers per item cost more than the address unit saves; -DIFD_WINO_STORE_LDS.)
-#ifdef IFD_WINO_STORE_LDS
-        constexpr bool VIA_LDS = TG == 2 && CG == 2;
-#else
-        constexpr bool VIA_LDS = FUSE;
-#endif
-        if (VIA_LDS) __syncthreads();                                      // every wave's MFMAs have read s_v: it becomes T
+        // barriers per item cost more than the address unit saves.  Only the fused layer's tile goes through LDS.)
+        if (FUSE) __syncthreads();                                      // every wave's MFMAs have read s_v: it becomes T
 #pragma unroll
         for (int tx = 0; tx < 4; ++tx) {
             float t0[4], t1[4];
@@ -536,29 +528,13 @@ __global__ __launch_bounds__(64 * TG * CG, TG * CG == 4 ? 2 : 1) void wino_kerne
                     float v = y[ya][xb] + bias;
                     if (a.relu) v = fmaxf(v, 0.f);
                     y[ya][xb] = v;
-                    if (VIA_LDS) s_v[((2 * kq + ya) * 16 + 8 * tg + 2 * tx + xb) * TRS + cg * 16 + r] = v;
+                    if (FUSE) s_v[((2 * kq + ya) * 16 + 8 * tg + 2 * tx + xb) * TRS + cg * 16 + r] = v;
                     else __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(v), ors, st_lane, st_reg + ((ya * a.W + 2 * tx + xb) * a.Cout) * 4, 0);
                 }
             if (a.pool_out != nullptr) {
                 const float pv = fmaxf(fmaxf(y[0][0], y[0][1]), fmaxf(y[1][0], y[1][1]));
-                if (VIA_LDS) s_v[(128 + kq * 8 + 4 * tg + tx) * TRS + cg * 16 + r] = pv;
+                if (FUSE) s_v[(128 + kq * 8 + 4 * tg + tx) * TRS + cg * 16 + r] = pv;
                 else __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(pv), prs, pl_lane, pl_reg + tx * a.Cout * 4, 0);
-            }
-        }
-        if constexpr (VIA_LDS && !FUSE) {
-            __syncthreads();
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                const int idx = tid + k * 256, px = idx >> 3, pc = idx & 7;
-                const f32x4 v = *reinterpret_cast<const f32x4*>(s_v + px * TRS + 4 * pc);
-                __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4w, v), ors, (co0 + 4 * pc) * 4,
-                                                       st_reg + (((px >> 4) * a.W + (px & 15)) * a.Cout) * 4, 0);
-            }
-            if (a.pool_out != nullptr) {
-                const int px = tid >> 3, pc = tid & 7;
-                const f32x4 v = *reinterpret_cast<const f32x4*>(s_v + (128 + px) * TRS + 4 * pc);
-                __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4w, v), prs, (co0 + 4 * pc) * 4,
-                                                       pl_reg + (((px >> 3) * (a.W / 2) + (px & 7)) * a.Cout) * 4, 0);
             }
         }
         if constexpr (FUSE) {
@@ -596,20 +572,14 @@ __global__ __launch_bounds__(64 * TG * CG, TG * CG == 4 ? 2 : 1) void wino_kerne
 #endif
 }
 
-#ifndef IFD_WINO_ITEMS
-#define IFD_WINO_ITEMS 16             // (image, region) work items per block
-#endif
+constexpr int WINO_ITEMS = 16;       // (image, region) work items per block
 template <int TG, int CG, bool FUSE = false>
 static hipError_t launch_wino(const ConvArgs& a, int n_img, hipStream_t s) {
-#ifdef IFD_WINO_OCC1
-    constexpr size_t LDS = 96 * 1024;
-#else
     constexpr size_t LDS = (size_t)16 * 16 * (16 * TG + 16 * CG) * sizeof(float);
-#endif
     const int n_items = n_img * (a.H / 8) * (a.W / (8 * TG));
-    // up to IFD_WINO_ITEMS items per block, fewer where that would leave less than ~12 blocks per block slot of the chip
+    // up to WINO_ITEMS items per block, fewer where that would leave less than ~12 blocks per block slot of the chip
     const int gy = a.Cout / (16 * CG);
-    const int per = max(1, min(IFD_WINO_ITEMS, (int)((long long)n_items * gy / 6144)));
+    const int per = max(1, min(WINO_ITEMS, (int)((long long)n_items * gy / 6144)));
     const dim3 grid((n_items + per - 1) / per, gy, 1);
 #ifdef IFD_WINO_PROF
     if (FUSE) {
@@ -644,14 +614,10 @@ hipError_t configure_unet_kernels() {
     return e;
 }
 
-// -DIFD_UNET_DIRECT / env IFD_UNET_DIRECT=1: every 3x3 layer on the implicit-GEMM kernel (A/B and validation of the Winograd path)
+// env IFD_UNET_DIRECT=1: every 3x3 layer on the implicit-GEMM kernel (A/B and validation of the Winograd path)
 static bool unet_direct() {
-#ifdef IFD_UNET_DIRECT
-    return true;
-#else
     static const bool d = [] { const char* e = getenv("IFD_UNET_DIRECT"); return e != nullptr && e[0] == '1'; }();
     return d;
-#endif
 }
 
 // conv3x3 / conv1x1 / transpose-conv dispatch on the image size (64/32/16 -> 8x16 pixel tiles, 8 -> 8x8 tiles)
@@ -671,11 +637,11 @@ static hipError_t conv(const float* in0, int C0, const float* in1, int C1, const
     }
     if (fuse_w != nullptr) {
         if (HW < 16 || ks != 3 || up || Cout != 32) return hipErrorInvalidValue;
-        return launch_conv<16, 4, 1, 3, false, true, IFD_UNET_PW>(a, n_img, s);
+        return launch_conv<16, 4, 1, 3, false, true, UNET_PW>(a, n_img, s);
     }
     if (HW >= 16) {
         if (up) return launch_conv<16, 4, 1, 1, true>(a, n_img, s);
-        if (ks == 3) return launch_conv<16, 4, 1, 3, false, false, IFD_UNET_PW>(a, n_img, s);
+        if (ks == 3) return launch_conv<16, 4, 1, 3, false, false, UNET_PW>(a, n_img, s);
         return launch_conv<16, 4, 1, 1, false>(a, n_img, s);
     }
     if (up) return launch_conv<8, 2, 2, 1, true>(a, n_img, s);

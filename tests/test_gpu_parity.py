@@ -224,7 +224,7 @@ def test_certified_neighbour_lists_equal_exact_scan(restorer, golden, oracle_wei
         print("K=%d: %.1f synchronous list rebuilds per cloud over 151 steps, %d certificate failures" %
               (K, ev, c["knn_brute_scans"]))
         # lists must actually be reused across steps; wave-steps with a certificate that expired a step early are answered
-        # by the exact per-point query (the soft margin is tuned for that trade, knn_device.h IFD_SOFT_SLACK): measured
+        # by the exact per-point query (the soft margin is tuned for that trade, knn_device.h SOFT_SLACK): measured
         # 264 of 4832 wave-steps at K = 1024
         assert ev < 30 and c["knn_brute_scans"] <= 0.12 * 8 * 4 * 151, c
 
