@@ -697,7 +697,8 @@ hipError_t large_optimize_in_groups(ifd_ctx* ctx, const float* dec_img, const fl
         note(large_f_prepare(q.G, q.Bg, K, own, &q.f_ws, q.s));
         q.list_ws = large_list_ws(q.G, q.Bg, K, own);
         if (own) {                                        // own moments behind G (large_ws_bytes), zeroed
-            q.m = reinterpret_cast<float*>(q.G + (size_t)q.Bg * K * 16);
+            Carve c(q.G);
+            q.m = large_ws(c, q.Bg, K, own).moments;
             q.v = q.m + (size_t)q.Bg * K * 3;
             note(hipMemsetAsync(q.m, 0, (size_t)q.Bg * K * 3 * 4 * 2, q.s));
         } else {

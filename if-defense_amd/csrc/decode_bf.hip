@@ -7,15 +7,13 @@
 
 namespace ifd {
 
-constexpr size_t DECODE_BF_LDS = (size_t)BF_IMG_BYTES;                  // the piece image
-
 // workgroup (cloud, part): the cloud's 32-point tiles part * 8 + wave, + 8 * parts, ...
 template <int PREC>
 __global__ __launch_bounds__(OPT_THREADS, 1) void decode3_bf_kernel(const float* __restrict__ dec_img, const float* __restrict__ planes,
                                                                      const float* __restrict__ p, int K, float* __restrict__ logits,
                                                                      float* __restrict__ dlogit_dp, DecConst dc) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
-    float* W = smem;
+    float* W = LDS_AT(float, smem, DecImageLds<PREC>::W);              // the piece image
     const int cloud = blockIdx.x, tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     load_dec_image(W, dec_img, BF_IMG_BYTES / 4);
@@ -51,9 +49,7 @@ __global__ __launch_bounds__(OPT_THREADS, 1) void decode3_bf_kernel(const float*
 }
 
 hipError_t configure_decode_bf_kernels() {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(decode3_bf_kernel<1>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)DECODE_BF_LDS);
-    if (e != hipSuccess) return e;
-    return hipFuncSetAttribute(reinterpret_cast<const void*>(decode3_bf_kernel<2>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)DECODE_BF_LDS);
+    return opt_in_dynamic_lds({{decode3_bf_kernel<1>, DecImageLds<1>::BYTES}, {decode3_bf_kernel<2>, DecImageLds<2>::BYTES}});
 }
 
 hipError_t launch_decode_bf(int prec, const float* dec_img_bf, const float* planes, const float* p, int B, int K, float* logits, float* dlogit_dp,
@@ -63,9 +59,9 @@ hipError_t launch_decode_bf(int prec, const float* dec_img_bf, const float* plan
     const int want = B >= n_cu ? 1 : (n_cu + B - 1) / B, most = (ntiles + 7) / 8;
     const int parts = want < most ? want : most;                       // with few clouds a cloud's tiles are shared out over several workgroups
     if (prec == 1)
-        hipLaunchKernelGGL(decode3_bf_kernel<1>, dim3(B, parts), dim3(OPT_THREADS), DECODE_BF_LDS, s, dec_img_bf, planes, p, K, logits, dlogit_dp, dc);
+        hipLaunchKernelGGL(decode3_bf_kernel<1>, dim3(B, parts), dim3(OPT_THREADS), DecImageLds<1>::BYTES, s, dec_img_bf, planes, p, K, logits, dlogit_dp, dc);
     else
-        hipLaunchKernelGGL(decode3_bf_kernel<2>, dim3(B, parts), dim3(OPT_THREADS), DECODE_BF_LDS, s, dec_img_bf, planes, p, K, logits, dlogit_dp, dc);
+        hipLaunchKernelGGL(decode3_bf_kernel<2>, dim3(B, parts), dim3(OPT_THREADS), DecImageLds<2>::BYTES, s, dec_img_bf, planes, p, K, logits, dlogit_dp, dc);
     return hipGetLastError();
 }
 

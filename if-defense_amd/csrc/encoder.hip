@@ -15,10 +15,9 @@
 #include <cstdlib>
 #include "ifd_device.h"
 #include "ifd_internal.h"
+#include "lds_layout.h"
 
 namespace ifd {
-
-constexpr int NET_STRIDE = 33;          // LDS row stride of the [T][32] feature matrix (bank-conflict pad)
 
 // out[o] = b[o] + sum_k W[o][k] * in[k]   (W row-major [NOUT][NIN], uniform address -> s_load)
 template <int NOUT, int NIN, bool RELU_IN, bool HAS_BIAS>
@@ -44,10 +43,6 @@ __device__ __forceinline__ void resnet_block(const float* __restrict__ w, const 
     for (int o = 0; o < 32; ++o) out[o] = xs[o] + dx[o];
 }
 
-// [threads][33] features + [3][threads] cell rings; the ring construction's scratch (head table int[4096] + unordered
-// chains u16[3][threads] = 22,528 B at 1024 threads) aliases the feature matrix, which is first written after it
-constexpr size_t enc_lds(int threads) { return (size_t)threads * NET_STRIDE * 4 + 3 * (size_t)threads * 2; }   // 141,312 B @1024
-
 template <int ENC_THREADS>
 __global__ __launch_bounds__(ENC_THREADS) void encode_points_kernel(const float* __restrict__ w, EncPointOffsets eo,
                                                                      const float* __restrict__ sel,
@@ -55,9 +50,9 @@ __global__ __launch_bounds__(ENC_THREADS) void encode_points_kernel(const float*
                                                                      float* __restrict__ planes,
                                                                      float* __restrict__ c_out, DecConst dc) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
-    float* net = smem;                                                     // [ENC_THREADS][NET_STRIDE]
-    unsigned short* ring = reinterpret_cast<unsigned short*>(net + ENC_THREADS * NET_STRIDE);
-                                                                           // [3][ENC_THREADS] next point of my cell
+    constexpr EncLdsAt L = enc_lds_at(ENC_THREADS);
+    float* net = LDS_AT(float, smem, L.NET);                               // [ENC_THREADS][NET_STRIDE]
+    unsigned short* ring = LDS_AT(unsigned short, smem, L.RING);           // [3][ENC_THREADS] next point of my cell
 
     const int b = blockIdx.x, i = threadIdx.x;
     const int T = t_per_cloud ? min(t_per_cloud[b], Tmax) : Tmax;
@@ -184,7 +179,6 @@ __global__ __launch_bounds__(ENC_THREADS) void encode_points_kernel(const float*
     }
 }
 
-
 // ---------------------------------------------------------------------------------------------
 // Round 4: the same encoder with its linear layers on the matrix pipe (v_mfma_f32_16x16x4_f32).
 //
@@ -207,7 +201,6 @@ constexpr int ENCI_W0 = 0, ENCI_B0 = 2048, ENCI_W1 = 2080, ENCI_B1 = 3104, ENCI_
 constexpr int ENCI_WC = ENCI_BLK0 + 5 * ENCI_BLK;    // [32][32]
 constexpr int ENCI_BC = ENCI_WC + 1024;              // [32]
 constexpr int ENCI_FLOATS = ENCI_BC + 32;            // 27,232
-constexpr int ENC_NSTR = 36;                         // LDS row of the [points][32] feature matrix (floats): 16-byte pieces, conflict-free writes
 
 struct Acc8 { f32x4 t[2]; };                         // 8 channels of a point: t[mt][r] <-> channel 16 mt + 4 q + r
 
@@ -242,9 +235,10 @@ __global__ __launch_bounds__(NW * 64) void encode_points_mfma_kernel(const float
     constexpr int NT = NW * 64;                                            // threads = points the LDS is sized for
     constexpr int TPW = (NT / 16 + NW - 1) / NW;                           // 16-point tiles per wave: 4
     extern __shared__ __attribute__((aligned(16))) float smem[];
-    float* net = smem;                                                     // [NT][ENC_NSTR]
-    unsigned short* ring = reinterpret_cast<unsigned short*>(net + NT * ENC_NSTR);   // [3][NT] next point of my cell
-    unsigned short* cellb = ring + 3 * NT;                                 // [3][NT] cell of the point per plane
+    constexpr EncMfmaLdsAt L = enc_mfma_lds_at(NT);
+    float* net = LDS_AT(float, smem, L.NET);                               // [NT][ENC_NSTR]
+    unsigned short* ring = LDS_AT(unsigned short, smem, L.RING);           // [3][NT] next point of my cell
+    unsigned short* cellb = LDS_AT(unsigned short, smem, L.CELL);          // [3][NT] cell of the point per plane
 
     const int b = blockIdx.x, i = threadIdx.x, lane = i & 63, wave = i >> 6;
     const int T = t_per_cloud ? min(t_per_cloud[b], Tmax) : Tmax;
@@ -436,20 +430,9 @@ __global__ __launch_bounds__(NW * 64) void encode_points_mfma_kernel(const float
     }
 }
 
-constexpr size_t enc_mfma_lds(int threads) { return (size_t)threads * ENC_NSTR * 4 + 6 * (size_t)threads * 2; }   // 99,840 B @640
-
 hipError_t configure_encoder_kernels() {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(encode_points_kernel<640>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)enc_lds(640));
-    if (e != hipSuccess) return e;
-    e = hipFuncSetAttribute(reinterpret_cast<const void*>(encode_points_kernel<1024>),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)enc_lds(1024));
-    if (e != hipSuccess) return e;
-    e = hipFuncSetAttribute(reinterpret_cast<const void*>(encode_points_mfma_kernel<10>),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)enc_mfma_lds(640));
-    if (e != hipSuccess) return e;
-    return hipFuncSetAttribute(reinterpret_cast<const void*>(encode_points_mfma_kernel<16>),
-                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)enc_mfma_lds(1024));
+    return opt_in_dynamic_lds({{encode_points_kernel<640>, enc_lds_at(640).BYTES}, {encode_points_kernel<1024>, enc_lds_at(1024).BYTES},
+                               {encode_points_mfma_kernel<10>, enc_mfma_lds_at(640).BYTES}, {encode_points_mfma_kernel<16>, enc_mfma_lds_at(1024).BYTES}});
 }
 
 int enc_image_floats() { return ENCI_FLOATS; }
@@ -479,18 +462,18 @@ hipError_t launch_encode_points(const float* w, const EncPointOffsets& eo, const
         if (e != hipSuccess) return e;
         // 640 threads (10 waves, 168 VGPRs) cover the shipped pointcloud_n = 600; larger subsets use 1024 threads
         if (Tmax <= 640)
-            hipLaunchKernelGGL(encode_points_kernel<640>, dim3(B), dim3(640), enc_lds(640), s, w, eo, sel, t_per_cloud,
+            hipLaunchKernelGGL(encode_points_kernel<640>, dim3(B), dim3(640), enc_lds_at(640).BYTES, s, w, eo, sel, t_per_cloud,
                                Tmax, planes, c_out, dc);
         else
-            hipLaunchKernelGGL(encode_points_kernel<1024>, dim3(B), dim3(1024), enc_lds(1024), s, w, eo, sel,
+            hipLaunchKernelGGL(encode_points_kernel<1024>, dim3(B), dim3(1024), enc_lds_at(1024).BYTES, s, w, eo, sel,
                                t_per_cloud, Tmax, planes, c_out, dc);
         return hipGetLastError();
     }
     if (Tmax <= 640)
-        hipLaunchKernelGGL(encode_points_mfma_kernel<10>, dim3(B), dim3(640), enc_mfma_lds(640), s, enc_img, sel, t_per_cloud, Tmax,
+        hipLaunchKernelGGL(encode_points_mfma_kernel<10>, dim3(B), dim3(640), enc_mfma_lds_at(640).BYTES, s, enc_img, sel, t_per_cloud, Tmax,
                            planes, c_out, dc);
     else
-        hipLaunchKernelGGL(encode_points_mfma_kernel<16>, dim3(B), dim3(1024), enc_mfma_lds(1024), s, enc_img, sel, t_per_cloud, Tmax,
+        hipLaunchKernelGGL(encode_points_mfma_kernel<16>, dim3(B), dim3(1024), enc_mfma_lds_at(1024).BYTES, s, enc_img, sel, t_per_cloud, Tmax,
                            planes, c_out, dc);
     return hipGetLastError();
 }

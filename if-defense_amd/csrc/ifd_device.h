@@ -7,6 +7,7 @@ namespace ifd {
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
+typedef float f32x2 __attribute__((ext_vector_type(2)));
 
 constexpr int RES = 64;              // plane resolution
 constexpr int CH = 32;               // c_dim == hidden

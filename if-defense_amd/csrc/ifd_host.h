@@ -1,10 +1,12 @@
-// Host-only helpers of api.cpp: the owners of a context's HIP resources and the cursor that lays a workspace out.
-// No kernel translation unit includes this file.
+// Host-only helpers of api.cpp: the owners of a context's HIP resources.  (The cursor that lays a workspace out, Carve, is in
+// lds_layout.h, where the .hip launchers reach it too.)  No kernel translation unit includes this file.
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include <cstddef>
 #include <utility>
+
+#include "lds_layout.h"
 
 namespace ifd {
 
@@ -69,23 +71,5 @@ inline hipError_t create_event(hipEvent_t* e) { return hipEventCreateWithFlags(e
 inline hipError_t create_stream(hipStream_t* s) { return hipStreamCreateWithFlags(s, hipStreamNonBlocking); }
 using Event = Lazy<hipEvent_t, create_event, hipEventDestroy>;          // without timing
 using Stream = Lazy<hipStream_t, create_stream, hipStreamDestroy>;      // non-blocking
-
-// Cursor over a workspace.  A layout is ONE function that takes its blocks from a Carve in order; on a null base the same
-// function gets null pointers and only counts, and that count is the workspace's size: it cannot disagree with the pointers.
-class Carve {
-    char* base_;
-    size_t off_ = 0;
-
-public:
-    explicit Carve(void* base) : base_(static_cast<char*>(base)) {}
-    template <class T>
-    T* take(size_t bytes) {
-        T* r = base_ ? reinterpret_cast<T*>(base_ + off_) : nullptr;
-        off_ += bytes;
-        return r;
-    }
-    void round_up(size_t to) { off_ = (off_ + to - 1) / to * to; }
-    size_t bytes() const { return off_; }
-};
 
 }  // namespace ifd

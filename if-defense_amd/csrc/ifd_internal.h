@@ -75,6 +75,11 @@ hipError_t launch_optimize(const float* dec_img, const float* planes, float* p, 
                            const int32_t* loss_batch_per_cloud, void* ws, unsigned long long* counters,
                            const float* adam_tab, int B, int K, const OptArgs& a, int split, int n_cu, hipStream_t s);
 size_t optimize_ws_bytes(int B);
+// ... and its layout: neighbour lists of the B clouds | exchange blocks of split clouds | Adam moments of the split-precision kernels
+class Carve;
+struct CoopWs;
+struct OptWs { uint16_t* knn_lists; CoopWs* coop; f32x4* mv; };
+OptWs optimize_ws(Carve& c, int B);
 // per-step Adam bias corrections {lr / (1 - beta1^t), sqrt(1 - beta2^t)}, t = t0 + 1 ... t0 + steps -> tab[steps][2]
 hipError_t launch_adam_table(float* tab, int t0, int steps, float lr, hipStream_t s);
 // bytes of context workspace ifd_optimize needs for B clouds (certified neighbour lists)
@@ -90,10 +95,22 @@ hipError_t launch_repulsion(const float* p, int B, int K, float* loss, float* gr
 hipError_t launch_normalize(float* p, int B, int K, hipStream_t s);
 // clouds of MAXK < K <= LARGE_MAXK optimised points: two launches per Adam step (optimize.hip, "large" section)
 size_t large_ws_bytes(int B, int K, bool own_moments);
+// ... and its layout: [G: B K float4 | own moments (if the caller passes none) | global repulsion accumulators (K > LARGE_LDS_MAXK) |
+// certified neighbour lists (K <= LARGE_LDS_MAXK), 16-byte aligned]
+struct LargeWs { f32x4* G; float* moments; void *f, *lists; };
+LargeWs large_ws(Carve& c, int B, int K, bool own_moments);
 // dec_img: the image of a.precision (f32: the optimiser's copy; 1 / 2: the bf16 piece image)
 hipError_t launch_large_occupancy(int precision, const float* dec_img, const float* planes, const float* p, int B, int parts, int K,
                                   const int32_t* loss_batch_per_cloud, int loss_batch, float thr, int want_loss, void* G, DecConst dc,
                                   hipStream_t s);
+struct LargeLists {
+    uint16_t* lists;     // [B][K][LL_M]
+    f32x4* cert;         // [B][K]  {position at build time, rho}
+    f32x2* dbase;        // [B][K]  {S at build time, alpha: the point's own rho^2 / d5^2 - shrunk when its ball overflowed its list, grown when it
+                         //          was half empty, like the persistent kernel's al_f / al_b}
+    float* scal;         // [B][4]  S(now) = sum over the call's steps so far of max_j |x_j(s + 1) - x_j(s)|, -, -, -
+};
+LargeLists large_lists(Carve& c, int B, int K);
 size_t large_list_bytes(int B, int K);        // certified neighbour lists of the launch-per-step path (0 beyond LARGE_LDS_MAXK points)
 void* large_list_ws(void* ws, int B, int K, bool own_moments);                                      // ... inside ws (nullptr beyond)
 size_t large_f_bytes(int B, int K);           // global repulsion accumulators of clouds beyond LARGE_LDS_MAXK points (0 below)

@@ -874,7 +874,7 @@ __device__ __forceinline__ float wave_max(float v) {
     const u32x2_t b = __builtin_amdgcn_permlane32_swap(__float_as_uint(v), __float_as_uint(v), false, false);
     return fmaxf(__uint_as_float(b.x), __uint_as_float(b.y));
 }
-// deterministic block reductions; `scratch` holds >= NWAVES floats
+// deterministic block reductions; `scratch` holds >= NWAVES floats (each layout asserts it for its block size: lds_layout.h)
 __device__ __forceinline__ float block_sum(float v, float* scratch) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     v = wave_sum(v);
@@ -925,6 +925,23 @@ struct KnnShared {
     float* dmaxbuf;                  // [2][MAX_WAVES] per-wave max displacement from the epoch reference (next step)
     float* movebuf;                  // [2][MAX_WAVES] per-wave max single-step move
     volatile int* rebuild_flag;      // [2] by step parity: whole-cloud rebuild requested
+};
+// Slots (float indices) of the 128-float scratch block of the persistent optimisers (CloudLds::SCRATCH; optimize_kernel and
+// onet_optimize_kernel, which hand the same slots to the code below).
+struct OptScratch {
+    static constexpr int FLOATS = 128;
+    static constexpr int REDUCE = 0;                         // block_sum / block_max [OWN_WAVES]; the loss reduction: occ at [w], rep at [MAX_WAVES + w]
+    static constexpr int REDUCE_END = MAX_WAVES + OWN_WAVES;
+    static constexpr int COOP_ABORT = 27;                    // int: split clouds, a cross-CU wait of this member gave up (coop_wait)
+    static constexpr int REBUILD_FLAG = 28;                  // int [2] by step parity
+    static constexpr int TILE_CTR = 30;                      // int: next decoder tile of this step
+    static constexpr int KNN_DONE = 31;                      // int: split clouds, owner waves of this member past their kNN phase
+    static constexpr int DMAX = 32;                          // [2][MAX_WAVES] per-wave max |x - x0| (next step)
+    static constexpr int MOVE = DMAX + 2 * MAX_WAVES;        // [2][MAX_WAVES] per-wave max single-step move
+    static constexpr int CNT = MOVE + 2 * MAX_WAVES;         // unsigned [CN_COUNT] event counters
+    static_assert(OWN_WAVES <= MAX_WAVES && REDUCE_END <= COOP_ABORT && COOP_ABORT + 1 == REBUILD_FLAG && REBUILD_FLAG + 2 == TILE_CTR &&
+                  TILE_CTR + 1 == KNN_DONE && KNN_DONE + 1 == DMAX && CNT + CN_COUNT <= FLOATS, "the scratch slots neither overlap nor leave the block");
+    static_assert(DMAX == 32 && MOVE == 64 && CNT == 96, "the slots stay where they were");
 };
 
 // kNN + repulsion of the two points (pa, pb) this lane owns, for one optimiser step (all lanes of an owner wave call

@@ -1,0 +1,258 @@
+// Layouts: where the blocks of a kernel's dynamic LDS, and of a workspace in global memory, lie.
+//
+// The rule: a layout is written down ONCE.  An LDS layout is a struct of byte offsets in block order whose last
+// member, BYTES, is where the last block ends; the kernel takes every pointer from it (LDS_AT), the launch and the opt-in take the
+// size from it (BYTES, opt_in_dynamic_lds).  A layout that depends on a run-time size is a constexpr function of that size
+// returning the same kind of struct (int offsets: the kernels index LDS in 32 bits), called by the kernel and by the launcher alike.  A workspace in global memory is one function
+// that takes its blocks from a Carve; run on a null base it only counts, and that count is the workspace's size.
+//
+// Here: the cursor, the opt-in helper, the pieces several layouts share, and the layouts of the kernels that live in .hip files.
+// The persistent optimisers' layouts sit with their kernels (OptLds in optimize_kernel.h, OnetDecLds / OnetOptLds in
+// onet_kernel.h, their scratch slots - OptScratch - in knn_device.h, whose code reads them).
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <cstddef>
+#include <cstdint>
+
+#include "ifd_device.h"
+#include "ifd_internal.h"
+
+namespace ifd {
+
+constexpr size_t LDS_MAX_BYTES = 160 * 1024;         // per workgroup on gfx950
+
+// Cursor over a workspace.  A layout is ONE function that takes its blocks from a Carve in order; on a null base the same
+// function gets null pointers and only counts, and that count is the workspace's size: it cannot disagree with the pointers.
+class Carve {
+    char* base_;
+    size_t off_ = 0;
+
+public:
+    explicit Carve(void* base) : base_(static_cast<char*>(base)) {}
+    template <class T>
+    T* take(size_t bytes) {
+        T* r = base_ ? reinterpret_cast<T*>(base_ + off_) : nullptr;
+        off_ += bytes;
+        return r;
+    }
+    void round_up(size_t to) { off_ = (off_ + to - 1) / to * to; }
+    size_t bytes() const { return off_; }
+};
+
+// The block of element type T at byte offset `at` (a multiple of sizeof(T)) of a kernel's dynamic LDS.  Macros, stepping in
+// elements, because the form of the address reaches the generated code: through a function, even an inlined one, the blocks of
+// one array look like separate objects to alias analysis; byte steps, or every block taken from the array's start, changed the
+// register allocation of srs_kernel, prepare_kernel, large_repulsion_kernel<true> and the split / split-precision
+// optimize_kernel.  Those kernels step each block from the one before it (LDS_NEXT), as their hand-written carves did - the
+// steps are differences of the layout's offsets, so the layout still is the only place that states them.
+#define LDS_AT(T, smem, at) (reinterpret_cast<T*>(smem) + (int)((at) / sizeof(T)))
+// ... and the block at offset `to` stepped from the pointer `prev` of the block at offset `from`, in elements of `prev`
+#define LDS_NEXT(T, prev, from, to) reinterpret_cast<T*>((prev) + (int)(((to) - (from)) / (int)sizeof(*(prev))))
+
+// The opt-in to more than 64 KB of dynamic LDS: each configure_*_kernels() is a list of {kernel, its layout's size}.
+struct LdsOptIn {
+    const void* kernel;
+    size_t bytes;
+    template <class... A>
+    LdsOptIn(void (*k)(A...), size_t b) : kernel(reinterpret_cast<const void*>(k)), bytes(b) {}
+};
+template <size_t N>
+hipError_t opt_in_dynamic_lds(const LdsOptIn (&list)[N]) {
+    for (const LdsOptIn& k : list) {
+        const hipError_t e = hipFuncSetAttribute(k.kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)k.bytes);
+        if (e != hipSuccess) return e;               // the first error wins
+    }
+    return hipSuccess;
+}
+
+// ---- shared pieces ------------------------------------------------------------------------------------------------------------
+// the ConvONet decoder's parameter image: f32 (PREC 0) or the bf16 piece image (ifd_device.h)
+template <int PREC>
+struct DecImageLds {
+    static constexpr size_t W = 0, BYTES = PREC == 0 ? (size_t)DEC_FLOATS * 4 : (size_t)BF_IMG_BYTES;
+};
+static_assert(DecImageLds<0>::BYTES == 67856 && DecImageLds<1>::BYTES == 94736, "the decoder images");
+
+// A cloud of up to MAXK points behind `BASE` bytes of decoder state, as the persistent optimisers keep it: occupancy gradients G,
+// points X (+ the far-away dummy X[MAXK]), their sampling coordinates PIX (ConvONet only), the fixed-point repulsion sums F
+// (RepAcc, knn_device.h) and the 128-float scratch (OptScratch, knn_device.h).
+template <size_t BASE, bool HAS_PIX>
+struct CloudLds {
+    static constexpr size_t G = BASE;                                      // f32x4 [MAXK]
+    static constexpr size_t X = G + MAXK * 16;                             // f32x4 [MAXK + 1]
+    static constexpr size_t PIX = X + (MAXK + 1) * 16;                     // f32x4 [MAXK] (HAS_PIX)
+    static constexpr size_t F_XY = PIX + (HAS_PIX ? MAXK * 16 : 0);        // long long [MAXK]
+    static constexpr size_t F_Z = F_XY + MAXK * 8;                         // int [MAXK]
+    static constexpr size_t SCRATCH = F_Z + MAXK * 4;                      // float [128]
+    static constexpr size_t END = SCRATCH + 128 * 4;
+    static_assert(BASE % 16 == 0, "f32x4 blocks");
+};
+
+// ---- the stand-alone entry kernels of optimize.hip ----------------------------------------------------------------------------
+struct RepLds {                                      // repulsion_kernel
+    static constexpr size_t X = 0;                                         // f32x4 [MAXK]
+    static constexpr size_t F = X + MAXK * 16;                             // long long [3 MAXK]
+    static constexpr size_t SCRATCH = F + MAXK * 3 * 8;                    // float [16]
+    static constexpr size_t BYTES = SCRATCH + 64;
+};
+struct NrmLds {                                      // normalize_kernel
+    static constexpr size_t X = 0;                                         // f32x4 [MAXK]
+    static constexpr size_t SCRATCH = X + MAXK * 16;                       // float [16]
+    static constexpr size_t BYTES = SCRATCH + 64;
+};
+static_assert(RepLds::BYTES == 41024 && NrmLds::BYTES == 16448, "LDS of the stand-alone kernels");
+
+// ---- the launch-per-step path (optimize.hip, "large" section) -----------------------------------------------------------------
+constexpr int LARGE_THREADS = 1024;
+// large_step_kernel<GF> / large_repulsion_kernel<GF>.  GF (K > LARGE_LDS_MAXK): only the K points are in LDS, the repulsion sums
+// are in the workspace; otherwise the layout is sized for LARGE_LDS_MAXK points whatever K is.
+struct LargeLdsAt { int X, F_XY, F_Z, SCRATCH, BYTES; };
+template <bool GF>
+__host__ __device__ constexpr LargeLdsAt large_lds_at(int K) {
+    LargeLdsAt l{};
+    const int n = GF ? K : LARGE_LDS_MAXK;
+    l.X = 0;                                                               // f32x4 [n]
+    l.F_XY = l.X + n * 16;                                                 // long long [n] (not GF)
+    l.F_Z = l.F_XY + (GF ? 0 : n * 8);                                     // int [n] (not GF)
+    l.SCRATCH = l.F_Z + (GF ? 0 : n * 4);                                  // float [64]
+    l.BYTES = l.SCRATCH + 64 * 4;
+    return l;
+}
+constexpr size_t large_lds_bytes(int K) { return K <= LARGE_LDS_MAXK ? large_lds_at<false>(K).BYTES : large_lds_at<true>(K).BYTES; }
+static_assert(large_lds_bytes(LARGE_LDS_MAXK) == 114944 && large_lds_bytes(LARGE_MAXK) == 160256 && large_lds_bytes(LARGE_MAXK) <= LDS_MAX_BYTES,
+              "LDS of the brute-force step kernels");
+
+constexpr int LL_BLK = 128;                          // large_step_lists_kernel walks candidates in blocks of 128 consecutive indices, each with a bounding box
+struct LargeListsLds {                               // large_step_lists_kernel; N = LARGE_LDS_MAXK
+    static constexpr size_t N = LARGE_LDS_MAXK;
+    static constexpr size_t X = 0;                                         // f32x4 [N + 1] (the dummy entry)
+    static constexpr size_t F_XY = X + (N + 1) * 16;                       // long long [N]
+    static constexpr size_t F_Z = F_XY + N * 8;                            // int [N]
+    static constexpr size_t RL = F_Z + N * 4;                              // float [N] repulsion loss term of every point
+    static constexpr size_t SCRATCH = RL + N * 4;                          // float [64]
+    static constexpr size_t QN = SCRATCH + 64 * 4;                         // int: queue length (+ 3 pad)
+    static constexpr size_t QD5 = QN + 16;                                 // float [N] upper bound of the queued point's squared 5th distance
+    static constexpr size_t QUEUE = QD5 + N * 4;                           // uint16 [N]
+    static constexpr size_t BB = QUEUE + N * 2;                            // float [N / LL_BLK][8] bounding boxes {min xyz, -, max xyz, -}
+    static constexpr size_t BYTES = BB + (N / LL_BLK) * 8 * 4;
+};
+static_assert(LargeListsLds::BYTES == 156960 && LargeListsLds::BYTES <= LDS_MAX_BYTES, "LDS of large_step_lists_kernel");
+
+// ---- prep.hip -----------------------------------------------------------------------------------------------------------------
+constexpr int PREP_THREADS = 1024;
+// PREP_MAXK (ifd_internal.h) = 10,000: the largest input cloud these kernels accept (the LDS of prepare_kernel: 16 bytes per
+// point).  Up to SOR_NARROW_MAXK points sor_kernel keeps the cloud in LDS in double (32 bytes per point); above, in float
+// with the doubles re-made per pair (12 bytes per point) - same values, see sor_kernel.
+constexpr int SOR_NARROW_MAXK = 4096;
+constexpr int PREP_SORT_MAX = 4096;      // up to this many optimised points per cloud leave prepare_kernel in Morton order (rank by counting: O(n^2))
+// entries of prepare_kernel's key array: the K subset keys, or the n_opt Morton keys of the optimised points if there are more of
+// them (rounded so that the doubles behind the array stay 8-byte aligned: 12 K + 4 nkey bytes in front of them)
+__host__ __device__ constexpr int prep_nkey(int K, int n_opt_sorted) {
+    return n_opt_sorted > K ? n_opt_sorted + ((3 * K + n_opt_sorted) & 1) : K;
+}
+// sor_kernel<WIDE>: 32 K + 128 B up to SOR_NARROW_MAXK points (131,200 B there, 32,896 B at 1024), 12 K + 128 B above, rounded to
+// 8 (120,128 B at 10,000)
+struct SorLdsAt { int SCRATCH, X, XX, BYTES; };
+template <bool WIDE>
+__host__ __device__ constexpr SorLdsAt sor_lds_at(int K) {
+    SorLdsAt l{};
+    l.SCRATCH = 0;                                                         // double [16]
+    l.X = l.SCRATCH + 16 * 8;                                              // narrow: double [K][3]; wide: float [K][3]
+    l.XX = l.X + (WIDE ? 12 : 24) * K;                             // narrow: double [K] = |x|^2
+    l.BYTES = WIDE ? l.XX + 4 * (K & 1) : l.XX + 8 * K;
+    return l;
+}
+constexpr size_t sor_lds_bytes(int K) { return K <= SOR_NARROW_MAXK ? sor_lds_at<false>(K).BYTES : sor_lds_at<true>(K).BYTES; }
+static_assert(sor_lds_bytes(SOR_NARROW_MAXK) == 131200 && sor_lds_bytes(1024) == 32896 && sor_lds_bytes(PREP_MAXK) == 120128, "LDS of sor_kernel");
+// prepare_kernel: 16 K + 256 B (160,256 B at 10,000) unless the Morton keys of the optimised points outnumber the subset keys
+struct PrepLdsAt { int P, KEY, SCRATCH, BYTES; };
+__host__ __device__ constexpr PrepLdsAt prep_lds_at(int K, int nkey) {
+    PrepLdsAt l{};
+    l.P = 0;                                                               // float [K][3] kept points, then processed
+    l.KEY = l.P + 12 * K;                                          // uint32 [nkey] (prep_nkey)
+    l.SCRATCH = l.KEY + 4 * nkey;                                  // float [64] (8-byte aligned: holds doubles; PrepScratch)
+    l.BYTES = l.SCRATCH + 64 * 4;
+    return l;
+}
+static_assert(prep_lds_at(PREP_MAXK, PREP_MAXK).BYTES == 160256 && prep_lds_at(PREP_MAXK, PREP_MAXK).BYTES <= LDS_MAX_BYTES, "LDS of prepare_kernel");
+// slots of prepare_kernel's 64-float scratch: the block reductions' rows (doubles, ints or floats, one per wave) and the kept count
+struct PrepScratch {
+    static constexpr int REDUCE = 0, REDUCE_FLOATS = 2 * (PREP_THREADS / 64), S_N = 62, FLOATS = 64;
+    static_assert(REDUCE + REDUCE_FLOATS <= S_N && S_N < FLOATS, "prepare_kernel's scratch slots");
+};
+
+// ---- encoder.hip: LDS by the kernel's thread count (one point per thread) -------------------------------------------------------
+constexpr int NET_STRIDE = 33;          // LDS row stride of the [T][32] feature matrix (bank-conflict pad)
+constexpr int ENC_NSTR = 36;            // LDS row of the MFMA kernel's [points][32] feature matrix (floats): 16-byte pieces, conflict-free writes
+// encode_points_kernel: [threads][33] features + [3][threads] cell rings; the ring construction's scratch (head table int[4096] +
+// unordered chains u16[3][threads] = 22,528 B at 1024 threads) aliases the feature matrix, which is first written after it
+struct EncLdsAt { size_t NET, RING, BYTES; };
+__host__ __device__ constexpr EncLdsAt enc_lds_at(int threads) {
+    EncLdsAt l{};
+    l.NET = 0;                                                             // float [threads][NET_STRIDE]
+    l.RING = l.NET + (size_t)threads * NET_STRIDE * 4;                     // uint16 [3][threads] next point of my cell
+    l.BYTES = l.RING + 3 * (size_t)threads * 2;
+    return l;
+}
+struct EncMfmaLdsAt { size_t NET, RING, CELL, BYTES; };                    // encode_points_mfma_kernel
+__host__ __device__ constexpr EncMfmaLdsAt enc_mfma_lds_at(int threads) {
+    EncMfmaLdsAt l{};
+    l.NET = 0;                                                             // float [threads][ENC_NSTR]
+    l.RING = l.NET + (size_t)threads * ENC_NSTR * 4;                       // uint16 [3][threads] next point of my cell
+    l.CELL = l.RING + 3 * (size_t)threads * 2;                             // uint16 [3][threads] cell of the point per plane
+    l.BYTES = l.CELL + 3 * (size_t)threads * 2;
+    return l;
+}
+static_assert(enc_lds_at(1024).BYTES == 141312 && enc_mfma_lds_at(640).BYTES == 99840 && enc_mfma_lds_at(1024).BYTES == 159744 &&
+              enc_mfma_lds_at(1024).BYTES <= LDS_MAX_BYTES, "LDS of the encoder kernels");
+
+// ---- unet.hip: wino_kernel<TG, CG> (64 KB at TG = CG = 2, 80 KB at TG = 1, CG = 4) --------------------------------------------
+template <int TG, int CG>
+struct WinoLds {
+    static constexpr size_t V = 0;                                         // float [16 xi][16 TG tiles][16 ch]
+    static constexpr size_t U = V + (size_t)16 * (16 * TG) * 16 * 4;       // float [16 xi][16 CG couts][16 ch]
+    static constexpr size_t BYTES = U + (size_t)16 * (16 * CG) * 16 * 4;
+};
+static_assert(WinoLds<2, 2>::BYTES == 65536 && WinoLds<1, 4>::BYTES == 81920, "LDS of wino_kernel");
+
+// ---- mesh.hip: mise_fill_z_kernel, FILLZ_LINES lines of P grid values through LDS ----------------------------------------------
+constexpr int FILLZ_LINES = 64;
+struct FillzLdsAt { int VAL, KNOWN, BYTES; };
+__host__ __device__ constexpr FillzLdsAt fillz_lds_at(int P) {
+    FillzLdsAt l{};
+    l.VAL = 0;                                                             // float [FILLZ_LINES][P]
+    l.KNOWN = l.VAL + FILLZ_LINES * P * 4;                         // uint8 [FILLZ_LINES][P]
+    l.BYTES = l.KNOWN + FILLZ_LINES * P;
+    return l;
+}
+
+// ---- punet.hip: the partial shuffles of srs_kernel (K indices, m draws) and fill_kernel (kept indices, permutation, K draws) ----
+struct SrsLdsAt { int PERM, RND, BYTES; };
+__host__ __device__ constexpr SrsLdsAt srs_lds_at(int K, int m) {
+    SrsLdsAt l{};
+    l.PERM = 0;                                                            // int [K]
+    l.RND = l.PERM + K * 4;                                                // uint32 [m]
+    l.BYTES = l.RND + m * 4;
+    return l;
+}
+struct FillLdsAt { int KEPT, PERM, RND, BYTES; };
+__host__ __device__ constexpr FillLdsAt fill_lds_at(int K) {
+    FillLdsAt l{};
+    l.KEPT = 0;                                                            // int [K] kept indices, original order
+    l.PERM = l.KEPT + K * 4;                                       // int [K]
+    l.RND = l.PERM + K * 4;                                                // uint32 [K]
+    l.BYTES = l.RND + K * 4;
+    return l;
+}
+static_assert(srs_lds_at(PREP_MAXK, PREP_MAXK).BYTES == 80000 && fill_lds_at(PREP_MAXK).BYTES == 120000, "LDS of the DUP-Net sampling kernels");
+
+// ---- block_sum / block_max / block_sum_d write one value per wave into their scratch ------------------------------------------
+static_assert((RepLds::BYTES - RepLds::SCRATCH) / 4 >= OPT_THREADS / 64 && (NrmLds::BYTES - NrmLds::SCRATCH) / 4 >= OPT_THREADS / 64,
+              "8 waves: repulsion_kernel, normalize_kernel");
+static_assert((large_lds_at<false>(0).BYTES - large_lds_at<false>(0).SCRATCH) / 4 >= LARGE_THREADS / 64 &&
+              (large_lds_at<true>(0).BYTES - large_lds_at<true>(0).SCRATCH) / 4 >= LARGE_THREADS / 64 &&
+              (LargeListsLds::QN - LargeListsLds::SCRATCH) / 4 >= LARGE_THREADS / 64, "16 waves: the launch-per-step kernels");
+static_assert((sor_lds_at<false>(0).X - sor_lds_at<false>(0).SCRATCH) / 8 >= PREP_THREADS / 64, "16 waves of doubles: sor_kernel");
+
+}  // namespace ifd

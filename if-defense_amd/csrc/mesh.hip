@@ -16,6 +16,7 @@
 
 #include "ifd_device.h"
 #include "ifd_internal.h"
+#include "lds_layout.h"
 #include "mc_table_data.h"
 
 namespace ifd {
@@ -154,13 +155,12 @@ __global__ void mise_fill_kernel(MiseGrid g, int axis) {
 }
 
 // the z pass walks contiguous memory: 64 lines per block go through LDS so that global accesses stay coalesced
-constexpr int FILLZ_LINES = 64;
 __global__ __launch_bounds__(256) void mise_fill_z_kernel(MiseGrid g) {
     extern __shared__ float fz[];                                     // [FILLZ_LINES][P] values, then known bytes
     const int cloud = blockIdx.y, P = g.P;
     const int line0 = blockIdx.x * FILLZ_LINES, nlines = min(FILLZ_LINES, P * P - line0);
     if (nlines <= 0) return;
-    uint8_t* kz = reinterpret_cast<uint8_t*>(fz + FILLZ_LINES * P);
+    uint8_t* kz = LDS_AT(uint8_t, fz, fillz_lds_at(P).KNOWN);
     float* val = g.val + (size_t)cloud * g.P3 + (size_t)line0 * P;
     uint8_t* known = g.known + (size_t)cloud * g.P3 + (size_t)line0 * P;
     for (int i = threadIdx.x; i < nlines * P; i += 256) { fz[i] = val[i]; kz[i] = known[i]; }
@@ -223,7 +223,7 @@ hipError_t launch_mise_update(const MiseGrid& g, int B, hipStream_t s) {
 hipError_t launch_mise_fill(const MiseGrid& g, int B, hipStream_t s) {
     for (int axis = 0; axis < 2; ++axis)
         hipLaunchKernelGGL(mise_fill_kernel, dim3((g.P * g.P + 255) / 256, B), dim3(256), 0, s, g, axis);
-    const size_t lds = (size_t)FILLZ_LINES * g.P * 5;
+    const size_t lds = fillz_lds_at(g.P).BYTES;
     hipLaunchKernelGGL(mise_fill_z_kernel, dim3((g.P * g.P + FILLZ_LINES - 1) / FILLZ_LINES, B), dim3(256), lds, s, g);
     return hipGetLastError();
 }

@@ -21,6 +21,7 @@
 #include "ifd_device.h"
 #include "ifd_internal.h"
 #include "knn_device.h"
+#include "lds_layout.h"
 
 namespace ifd {
 
@@ -218,7 +219,7 @@ __global__ __launch_bounds__(OPT_THREADS, 2) void onet_decode_kernel(const float
 hipError_t launch_onet_grid_eval(const float* img, const float* small, const float* ab, const MiseGrid& g, int B, int n_blocks,
                                  float box, hipStream_t s) {
     hipLaunchKernelGGL(grid_plan_kernel<0>, dim3(1), dim3(64), 0, s, g, B);
-    hipLaunchKernelGGL(onet_grid_eval_kernel<0>, dim3(n_blocks), dim3(OPT_THREADS), ONET_DEC_LDS, s, img, small, ab, g, B, box);
+    hipLaunchKernelGGL(onet_grid_eval_kernel<0>, dim3(n_blocks), dim3(OPT_THREADS), OnetDecLds::BYTES, s, img, small, ab, g, B, box);
     return hipGetLastError();
 }
 
@@ -249,7 +250,9 @@ __global__ __launch_bounds__(OPT_THREADS, 2) void onet_large_occupancy_kernel(
 hipError_t launch_onet_large_optimize(const float* img, const float* small, const float* ab, float* p, float* m, float* v,
                                       float* loss, const int32_t* loss_batch_per_cloud, void* ws, unsigned long long* counters,
                                       const float* adam_tab, int B, int K, const OptArgs& a, hipStream_t s) {
-    f32x4* G = static_cast<f32x4*>(ws);
+    Carve c(ws);
+    const LargeWs w = large_ws(c, B, K, m == nullptr);
+    f32x4* G = w.G;
     void* f_ws = nullptr;                  // global repulsion accumulators beyond LARGE_LDS_MAXK points (end of ws)
     void* list_ws = large_list_ws(ws, B, K, m == nullptr);      // certified neighbour lists up to LARGE_LDS_MAXK points (optimize.hip)
     {
@@ -257,7 +260,7 @@ hipError_t launch_onet_large_optimize(const float* img, const float* small, cons
         if (e != hipSuccess) return e;
     }
     if (m == nullptr) {                    // own moments behind G (large_ws_bytes), zeroed
-        m = reinterpret_cast<float*>(G + (size_t)B * K);
+        m = w.moments;
         v = m + (size_t)B * K * 3;
         hipError_t e = hipMemsetAsync(m, 0, (size_t)B * K * 3 * 4 * 2, s);
         if (e != hipSuccess) return e;
@@ -269,7 +272,7 @@ hipError_t launch_onet_large_optimize(const float* img, const float* small, cons
         if (a.precision != 0)
             e = launch_onet_large_occupancy_bf(a.precision, img, small, ab, p, B, parts, K, loss_batch_per_cloud, a.loss_batch, a.threshold, G, s);
         else
-            hipLaunchKernelGGL(onet_large_occupancy_kernel, dim3(B, parts), dim3(OPT_THREADS), ONET_DEC_LDS, s, img, small, ab, p, K,
+            hipLaunchKernelGGL(onet_large_occupancy_kernel, dim3(B, parts), dim3(OPT_THREADS), OnetDecLds::BYTES, s, img, small, ab, p, K,
                                loss_batch_per_cloud, a.loss_batch, a.threshold, G);
         if (e != hipSuccess) return e;
         e = launch_large_step(p, m, v, G, B, K, adam_tab, step, loss_batch_per_cloud, a,
@@ -280,29 +283,21 @@ hipError_t launch_onet_large_optimize(const float* img, const float* small, cons
 }
 
 hipError_t configure_onet_kernels() {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(onet_decode_kernel),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)ONET_DEC_LDS);
-    if (e != hipSuccess) return e;
-    e = hipFuncSetAttribute(reinterpret_cast<const void*>(onet_large_occupancy_kernel),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)ONET_DEC_LDS);
-    if (e != hipSuccess) return e;
-    e = hipFuncSetAttribute(reinterpret_cast<const void*>(onet_grid_eval_kernel<0>),          // (per device: see onet_bf.hip)
-                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)ONET_DEC_LDS);
-    if (e != hipSuccess) return e;
-    return hipFuncSetAttribute(reinterpret_cast<const void*>(onet_optimize_kernel<0>),
-                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)ONET_OPT_LDS);
+    return opt_in_dynamic_lds({{onet_decode_kernel, OnetDecLds::BYTES}, {onet_large_occupancy_kernel, OnetDecLds::BYTES},
+                               {onet_grid_eval_kernel<0>, OnetDecLds::BYTES},          // (per device: see onet_bf.hip)
+                               {onet_optimize_kernel<0>, OnetOptLds::BYTES}});
 }
 
 hipError_t launch_onet_decode(const float* img, const float* small, const float* ab, const float* p, int B, int K,
                               float* logits, float* dlogit_dp, hipStream_t s) {
-    hipLaunchKernelGGL(onet_decode_kernel, dim3(B), dim3(OPT_THREADS), ONET_DEC_LDS, s, img, small, ab, p, K, logits, dlogit_dp);
+    hipLaunchKernelGGL(onet_decode_kernel, dim3(B), dim3(OPT_THREADS), OnetDecLds::BYTES, s, img, small, ab, p, K, logits, dlogit_dp);
     return hipGetLastError();
 }
 
 hipError_t launch_onet_optimize(const float* img, const float* small, const float* ab, float* p, float* m, float* v, float* loss,
                                 const int32_t* loss_batch_per_cloud, uint16_t* knn_lists, unsigned long long* counters,
                                 const float* adam_tab, int B, int K, const OptArgs& a, hipStream_t s) {
-    hipLaunchKernelGGL(onet_optimize_kernel<0>, dim3(B), dim3(OPT_THREADS), ONET_OPT_LDS, s, img, small, ab, p, m, v, loss,
+    hipLaunchKernelGGL(onet_optimize_kernel<0>, dim3(B), dim3(OPT_THREADS), OnetOptLds::BYTES, s, img, small, ab, p, m, v, loss,
                        loss_batch_per_cloud, knn_lists, counters, adam_tab, K, a);
     return hipGetLastError();
 }

@@ -6,6 +6,7 @@
 #include "ifd_device.h"
 #include "ifd_internal.h"
 #include "knn_device.h"
+#include "lds_layout.h"
 
 namespace ifd {
 
@@ -65,54 +66,39 @@ hipError_t launch_onet_large_occupancy_bf(int precision, const float* img_bf, co
                                           int parts, int K, const int32_t* loss_batch_per_cloud, int loss_batch, float thr, void* G,
                                           hipStream_t s) {
     if (precision == 1)
-        hipLaunchKernelGGL(onet_large_occupancy_bf_kernel<1>, dim3(B, parts), dim3(OPT_THREADS), ONET_DEC_LDS, s, img_bf, small, ab, p, K,
+        hipLaunchKernelGGL(onet_large_occupancy_bf_kernel<1>, dim3(B, parts), dim3(OPT_THREADS), OnetDecLds::BYTES, s, img_bf, small, ab, p, K,
                            loss_batch_per_cloud, loss_batch, thr, static_cast<f32x4*>(G));
     else
-        hipLaunchKernelGGL(onet_large_occupancy_bf_kernel<2>, dim3(B, parts), dim3(OPT_THREADS), ONET_DEC_LDS, s, img_bf, small, ab, p, K,
+        hipLaunchKernelGGL(onet_large_occupancy_bf_kernel<2>, dim3(B, parts), dim3(OPT_THREADS), OnetDecLds::BYTES, s, img_bf, small, ab, p, K,
                            loss_batch_per_cloud, loss_batch, thr, static_cast<f32x4*>(G));
     return hipGetLastError();
 }
 
+// (the grid-evaluation kernels too: the attribute is per DEVICE, and this runs under the context's device at every
+// ifd_onet_create - a process-wide "configured" flag in the launcher left a second GPU's launches unconfigured; round-5 advisor)
 hipError_t configure_onet_bf_kernels() {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(onet_optimize_kernel<1>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)ONET_OPT_LDS);
-    if (e != hipSuccess) return e;
-    e = hipFuncSetAttribute(reinterpret_cast<const void*>(onet_optimize_kernel<2>),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)ONET_OPT_LDS);
-    if (e != hipSuccess) return e;
-    // (the grid-evaluation kernels too: the attribute is per DEVICE, and this runs under the context's device at every
-    // ifd_onet_create - a process-wide "configured" flag in the launcher left a second GPU's launches unconfigured; round-5 advisor)
-    e = hipFuncSetAttribute(reinterpret_cast<const void*>(onet_large_occupancy_bf_kernel<1>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)ONET_DEC_LDS);
-    if (e != hipSuccess) return e;
-    e = hipFuncSetAttribute(reinterpret_cast<const void*>(onet_large_occupancy_bf_kernel<2>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)ONET_DEC_LDS);
-    if (e != hipSuccess) return e;
-    e = hipFuncSetAttribute(reinterpret_cast<const void*>(onet_decode_bf_kernel<1>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)ONET_DEC_LDS);
-    if (e != hipSuccess) return e;
-    e = hipFuncSetAttribute(reinterpret_cast<const void*>(onet_decode_bf_kernel<2>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)ONET_DEC_LDS);
-    if (e != hipSuccess) return e;
-    e = hipFuncSetAttribute(reinterpret_cast<const void*>(onet_grid_eval_kernel<1>),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)ONET_DEC_LDS);
-    if (e != hipSuccess) return e;
-    return hipFuncSetAttribute(reinterpret_cast<const void*>(onet_grid_eval_kernel<2>),
-                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)ONET_DEC_LDS);
+    return opt_in_dynamic_lds({{onet_optimize_kernel<1>, OnetOptLds::BYTES}, {onet_optimize_kernel<2>, OnetOptLds::BYTES},
+                               {onet_large_occupancy_bf_kernel<1>, OnetDecLds::BYTES}, {onet_large_occupancy_bf_kernel<2>, OnetDecLds::BYTES},
+                               {onet_decode_bf_kernel<1>, OnetDecLds::BYTES}, {onet_decode_bf_kernel<2>, OnetDecLds::BYTES},
+                               {onet_grid_eval_kernel<1>, OnetDecLds::BYTES}, {onet_grid_eval_kernel<2>, OnetDecLds::BYTES}});
 }
 
 hipError_t launch_onet_grid_eval_bf(int precision, const float* img_bf, const float* small, const float* ab, const MiseGrid& g, int B,
                                     int n_blocks, float box, hipStream_t s) {
     hipLaunchKernelGGL(grid_plan_kernel<1>, dim3(1), dim3(64), 0, s, g, B);
     if (precision == 1)
-        hipLaunchKernelGGL(onet_grid_eval_kernel<1>, dim3(n_blocks), dim3(OPT_THREADS), ONET_DEC_LDS, s, img_bf, small, ab, g, B, box);
+        hipLaunchKernelGGL(onet_grid_eval_kernel<1>, dim3(n_blocks), dim3(OPT_THREADS), OnetDecLds::BYTES, s, img_bf, small, ab, g, B, box);
     else
-        hipLaunchKernelGGL(onet_grid_eval_kernel<2>, dim3(n_blocks), dim3(OPT_THREADS), ONET_DEC_LDS, s, img_bf, small, ab, g, B, box);
+        hipLaunchKernelGGL(onet_grid_eval_kernel<2>, dim3(n_blocks), dim3(OPT_THREADS), OnetDecLds::BYTES, s, img_bf, small, ab, g, B, box);
     return hipGetLastError();
 }
 
 hipError_t launch_onet_decode_bf(int precision, const float* img_bf, const float* small, const float* ab, const float* p, int B, int K,
                                  float* logits, float* dlogit_dp, hipStream_t s) {
     if (precision == 1)
-        hipLaunchKernelGGL(onet_decode_bf_kernel<1>, dim3(B), dim3(OPT_THREADS), ONET_DEC_LDS, s, img_bf, small, ab, p, K, logits, dlogit_dp);
+        hipLaunchKernelGGL(onet_decode_bf_kernel<1>, dim3(B), dim3(OPT_THREADS), OnetDecLds::BYTES, s, img_bf, small, ab, p, K, logits, dlogit_dp);
     else
-        hipLaunchKernelGGL(onet_decode_bf_kernel<2>, dim3(B), dim3(OPT_THREADS), ONET_DEC_LDS, s, img_bf, small, ab, p, K, logits, dlogit_dp);
+        hipLaunchKernelGGL(onet_decode_bf_kernel<2>, dim3(B), dim3(OPT_THREADS), OnetDecLds::BYTES, s, img_bf, small, ab, p, K, logits, dlogit_dp);
     return hipGetLastError();
 }
 
@@ -120,10 +106,10 @@ hipError_t launch_onet_optimize_bf(int precision, const float* img_bf, const flo
                                    float* loss, const int32_t* loss_batch_per_cloud, uint16_t* knn_lists, unsigned long long* counters,
                                    const float* adam_tab, int B, int K, const OptArgs& a, hipStream_t s) {
     if (precision == 1)
-        hipLaunchKernelGGL(onet_optimize_kernel<1>, dim3(B), dim3(OPT_THREADS), ONET_OPT_LDS, s, img_bf, small, ab, p, m, v, loss,
+        hipLaunchKernelGGL(onet_optimize_kernel<1>, dim3(B), dim3(OPT_THREADS), OnetOptLds::BYTES, s, img_bf, small, ab, p, m, v, loss,
                            loss_batch_per_cloud, knn_lists, counters, adam_tab, K, a);
     else
-        hipLaunchKernelGGL(onet_optimize_kernel<2>, dim3(B), dim3(OPT_THREADS), ONET_OPT_LDS, s, img_bf, small, ab, p, m, v, loss,
+        hipLaunchKernelGGL(onet_optimize_kernel<2>, dim3(B), dim3(OPT_THREADS), OnetOptLds::BYTES, s, img_bf, small, ab, p, m, v, loss,
                            loss_batch_per_cloud, knn_lists, counters, adam_tab, K, a);
     return hipGetLastError();
 }

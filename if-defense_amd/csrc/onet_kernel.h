@@ -485,10 +485,10 @@ __device__ __forceinline__ void onet_prologue_bf(const float* __restrict__ img, 
     __syncthreads();
 }
 
-constexpr size_t ONET_DEC_LDS = (size_t)OL_END * 4;
-constexpr int OL_G = OL_END;                                        // optimiser state behind the decoder's
-constexpr size_t ONET_OPT_LDS = ONET_DEC_LDS + MAXK * 16 * 2 + 16 + MAXK * 12 + 128 * 4;
-static_assert(ONET_OPT_LDS <= 160 * 1024, "LDS budget");
+// LDS (lds_layout.h): the decoder's blocks (OL_*, floats) for every kernel that runs passes; the optimiser keeps its cloud behind them
+struct OnetDecLds { static constexpr size_t BYTES = (size_t)OL_END * 4; };
+struct OnetOptLds : CloudLds<OnetDecLds::BYTES, false> { static constexpr size_t BYTES = END; };
+static_assert(OnetDecLds::BYTES == 98320 && OnetOptLds::BYTES == 143904 && OnetOptLds::BYTES <= LDS_MAX_BYTES, "LDS of the ONet kernels");
 
 // Occupancy at the queued grid points of the MISE rounds (mesh.hip; generation.py:112-127 eval_points), forward only.
 // DEVICE-DRIVEN (round 5): the host does not know the queue lengths.  grid_plan_kernel turns the clouds' counts into an exclusive
@@ -574,11 +574,12 @@ __global__ __launch_bounds__(OPT_THREADS, 2) void onet_optimize_kernel(
     const int32_t* __restrict__ loss_batch_per_cloud, uint16_t* knn_lists, unsigned long long* __restrict__ counters,
     const float* __restrict__ adam_tab, int K, OptArgs A) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
-    f32x4* G = reinterpret_cast<f32x4*>(smem + OL_G);                // occupancy gradient (+ BCE term in .w)
-    f32x4* X = G + MAXK;                                             // current points; X[MAXK] = far-away dummy
-    const RepAcc F = {reinterpret_cast<long long*>(X + MAXK + 1),    // fixed-point repulsion-gradient scatter (knn_device.h)
-                      reinterpret_cast<int*>(reinterpret_cast<long long*>(X + MAXK + 1) + MAXK)};
-    float* scratch = reinterpret_cast<float*>(F.z + MAXK);           // 128 floats
+    using L = OnetOptLds;
+    f32x4* G = LDS_AT(f32x4, smem, L::G);                            // occupancy gradient (+ BCE term in .w)
+    f32x4* X = LDS_NEXT(f32x4, G, L::G, L::X);                       // current points; X[MAXK] = far-away dummy
+    const RepAcc F = {LDS_NEXT(long long, X, L::X, L::F_XY),         // fixed-point repulsion-gradient scatter (knn_device.h)
+                      LDS_NEXT(int, LDS_NEXT(long long, X, L::X, L::F_XY), L::F_XY, L::F_Z)};
+    float* scratch = LDS_NEXT(float, F.z, L::F_Z, L::SCRATCH);       // OptScratch (each block stepped from the one before: see optimize_kernel)
     const int cloud = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     float* pc = p + (size_t)cloud * K * 3;
     const int pa = tid, pb = tid + OPT_THREADS;
@@ -615,10 +616,10 @@ __global__ __launch_bounds__(OPT_THREADS, 2) void onet_optimize_kernel(
     KnnPt ka = {0, -1, 0.f, 0.f, 2.0f, 7.0f, f32x4{0.f, 0.f, 0.f, 0.f}, 0.f, 0.f, false, false};
     KnnPt kb = ka;
     uint16_t* cloud_lists = knn_lists + (size_t)cloud * MAXK * LIST_M;
-    float* dmaxbuf = scratch + 32;
-    float* movebuf = scratch + 64;
-    volatile int* rebuild_flag = reinterpret_cast<volatile int*>(scratch + 28);
-    unsigned int* lcnt = reinterpret_cast<unsigned int*>(scratch + 96);           // [CN_COUNT] event counters
+    float* dmaxbuf = scratch + OptScratch::DMAX;
+    float* movebuf = scratch + OptScratch::MOVE;
+    volatile int* rebuild_flag = reinterpret_cast<volatile int*>(scratch + OptScratch::REBUILD_FLAG);
+    unsigned int* lcnt = reinterpret_cast<unsigned int*>(scratch + OptScratch::CNT);
     KnnCounters cn{lcnt, lane};
     const KnnShared ksh = {dmaxbuf, movebuf, rebuild_flag};
     if (tid < 2) rebuild_flag[tid] = 0;

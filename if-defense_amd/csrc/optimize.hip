@@ -14,7 +14,7 @@ __global__ __launch_bounds__(OPT_THREADS, 2) void decode_kernel(const float* __r
                                                                  float* __restrict__ logits,
                                                                  float* __restrict__ dlogit_dp, DecConst dc) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
-    float* W = smem;
+    float* W = LDS_AT(float, smem, DecImageLds<0>::W);
     const int cloud = blockIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     load_dec_image(W, dec_img);
     __syncthreads();
@@ -44,9 +44,9 @@ __global__ __launch_bounds__(OPT_THREADS, 2) void repulsion_kernel(const float* 
                                                                     float* __restrict__ grad,
                                                                     int32_t* __restrict__ knn_idx, RepConst rc) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
-    f32x4* X = reinterpret_cast<f32x4*>(smem);
-    long long* F = reinterpret_cast<long long*>(X + MAXK);
-    float* scratch = reinterpret_cast<float*>(F + 3 * MAXK);
+    f32x4* X = LDS_AT(f32x4, smem, RepLds::X);
+    long long* F = LDS_AT(long long, smem, RepLds::F);
+    float* scratch = LDS_AT(float, smem, RepLds::SCRATCH);
     const int cloud = blockIdx.x, tid = threadIdx.x;
     const float* pc = p + (size_t)cloud * K * 3;
     const int pa = tid, pb = tid + OPT_THREADS;
@@ -89,8 +89,8 @@ __global__ __launch_bounds__(OPT_THREADS, 2) void repulsion_kernel(const float* 
 
 __global__ __launch_bounds__(OPT_THREADS, 2) void normalize_kernel(float* __restrict__ p, int K) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
-    f32x4* X = reinterpret_cast<f32x4*>(smem);
-    float* scratch = reinterpret_cast<float*>(X + MAXK);
+    f32x4* X = LDS_AT(f32x4, smem, NrmLds::X);
+    float* scratch = LDS_AT(float, smem, NrmLds::SCRATCH);
     float* pc = p + (size_t)blockIdx.x * K * 3;
     const int pa = threadIdx.x, pb = threadIdx.x + OPT_THREADS;
     if (pa < K) X[pa] = f32x4{pc[3 * pa], pc[3 * pa + 1], pc[3 * pa + 2], 0.f};
@@ -114,7 +114,6 @@ __global__ __launch_bounds__(OPT_THREADS, 2) void normalize_kernel(float* __rest
 // points the fixed-point repulsion accumulators sit in LDS next to the positions (28 bytes per point); above (GF = true) only
 // the positions do (16 bytes per point: 10,000 points fill the LDS) and the accumulators are integer atomics on a global
 // buffer of the workspace - the same integer sums.
-constexpr int LARGE_THREADS = 1024;
 constexpr int LARGE_PPT = (LARGE_MAXK + LARGE_THREADS - 1) / LARGE_THREADS + ((LARGE_MAXK + LARGE_THREADS - 1) / LARGE_THREADS & 1);   // points per thread: 10 (even)
 
 struct LargeLds {
@@ -125,21 +124,20 @@ struct LargeLds {
 // f_ws (GF): [B][K] packed xy sums, then [B][K] z sums (large_f_bytes); zero on entry, left zero on exit
 template <bool GF>
 __device__ __forceinline__ LargeLds large_lds(float* smem, int K, int B, int cloud, void* f_ws) {
+    const LargeLdsAt at = large_lds_at<GF>(K);
     LargeLds l;
-    l.X = reinterpret_cast<f32x4*>(smem);                                             // [LARGE_LDS_MAXK] / GF: [K]
+    l.X = LDS_AT(f32x4, smem, at.X);
     if (GF) {
         l.F.xy = static_cast<long long*>(f_ws) + (size_t)cloud * K;
         l.F.z = reinterpret_cast<int*>(static_cast<long long*>(f_ws) + (size_t)B * K) + (size_t)cloud * K;
-        l.scratch = reinterpret_cast<float*>(l.X + K);                                // [64]
+        l.scratch = LDS_NEXT(float, l.X, at.X, at.SCRATCH);
     } else {
-        l.F.xy = reinterpret_cast<long long*>(l.X + LARGE_LDS_MAXK);                  // [LARGE_LDS_MAXK]
-        l.F.z = reinterpret_cast<int*>(l.F.xy + LARGE_LDS_MAXK);                      // [LARGE_LDS_MAXK]
-        l.scratch = reinterpret_cast<float*>(l.F.z + LARGE_LDS_MAXK);                 // [64]
+        l.F.xy = LDS_AT(long long, smem, at.F_XY);
+        l.F.z = LDS_AT(int, smem, at.F_Z);
+        l.scratch = LDS_AT(float, smem, at.SCRATCH);
     }
     return l;
 }
-constexpr size_t LARGE_LDS = (size_t)LARGE_LDS_MAXK * (16 + 8 + 4) + 64 * 4;          // 114,944 B
-static size_t large_lds_bytes(int K) { return K <= LARGE_LDS_MAXK ? LARGE_LDS : (size_t)K * 16 + 64 * 4; }     // 160,256 B at 10,000
 size_t large_f_bytes(int B, int K) { return K <= LARGE_LDS_MAXK ? 0 : (size_t)B * K * 12; }
 // what a point received (GF: read past the L1 - the sums were made by atomics in the L2 - and cleared for the next step)
 template <bool GF>
@@ -272,28 +270,20 @@ constexpr unsigned int LL_IDX_MASK = 8191u;         // 13 index bits: 0 ... LARG
 constexpr int LL_DUMMY = LARGE_LDS_MAXK;            // X[LL_DUMMY]: a far-away point (unused list slots)
 constexpr float LL_ALPHA = 6.4f;                    // first rho^2 = LL_ALPHA d5^2: ~32 of the 64 entries on a surface, slack rho - r5 = 1.5 r5
 constexpr int LL_Q = LL_M / 4;                      // a renewed list is written by four lanes, a quarter each
-struct LargeLists {
-    uint16_t* lists;     // [B][K][LL_M]
-    f32x4* cert;         // [B][K]  {position at build time, rho}
-    f32x2* dbase;        // [B][K]  {S at build time, alpha: the point's own rho^2 / d5^2 - shrunk when its ball overflowed its list, grown when it
-                         //          was half empty, like the persistent kernel's al_f / al_b}
-    float* scal;         // [B][4]  S(now) = sum over the call's steps so far of max_j |x_j(s + 1) - x_j(s)|, -, -, -
-};
-size_t large_list_bytes(int B, int K) {
-    return K <= LARGE_LDS_MAXK ? (size_t)B * K * (LL_M * 2 + 16 + 8) + (size_t)B * 16 : 0;
-}
-static LargeLists large_lists_at(void* base, int B, int K) {
+// (the one layout of the lists' workspace: its count on a null base is large_list_bytes)
+LargeLists large_lists(Carve& c, int B, int K) {
     LargeLists L;
-    char* c = static_cast<char*>(base);
-    L.cert = reinterpret_cast<f32x4*>(c);                       c += (size_t)B * K * 16;
-    L.lists = reinterpret_cast<uint16_t*>(c);                   c += (size_t)B * K * LL_M * 2;
-    L.dbase = reinterpret_cast<f32x2*>(c);                      c += (size_t)B * K * 8;
-    L.scal = reinterpret_cast<float*>(c);
+    L.cert = c.take<f32x4>((size_t)B * K * 16);
+    L.lists = c.take<uint16_t>((size_t)B * K * LL_M * 2);
+    L.dbase = c.take<f32x2>((size_t)B * K * 8);
+    L.scal = c.take<float>((size_t)B * 16);
     return L;
 }
-constexpr int LL_BLK = 128;                         // candidates are walked in blocks of 128 consecutive indices, each with a bounding box
-constexpr size_t LARGE_LISTS_LDS = (size_t)(LARGE_LDS_MAXK + 1) * 16 + (size_t)LARGE_LDS_MAXK * (8 + 4 + 4 + 2 + 4) + 64 * 4 + 16 +
-                                   (LARGE_LDS_MAXK / LL_BLK) * 8 * 4;                       // 156,960 B
+size_t large_list_bytes(int B, int K) {
+    Carve c(nullptr);
+    if (K <= LARGE_LDS_MAXK) large_lists(c, B, K);
+    return c.bytes();
+}
 
 __device__ __forceinline__ float ll_dist2(const f32x4& a, const f32x4& b) {
     const float ex = a.x - b.x, ey = a.y - b.y, ez = a.z - b.z;
@@ -380,15 +370,17 @@ __global__ __launch_bounds__(LARGE_THREADS) void large_step_lists_kernel(float* 
                                                                           unsigned long long* status) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const int cloud = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    f32x4* X = reinterpret_cast<f32x4*>(smem);                                        // [LARGE_LDS_MAXK + 1]
-    long long* const fxy = reinterpret_cast<long long*>(X + LARGE_LDS_MAXK + 1);
-    const RepAcc Fz = {fxy, reinterpret_cast<int*>(fxy + LARGE_LDS_MAXK)};              // fixed-point repulsion sums (knn_device.h)
-    float* RL = reinterpret_cast<float*>(Fz.z + LARGE_LDS_MAXK);                      // [LARGE_LDS_MAXK] repulsion loss term of every point
-    float* scratch = RL + LARGE_LDS_MAXK;                                             // [64]
-    int* qn = reinterpret_cast<int*>(scratch + 64);                                   // queue length (+ 3 pad)
-    float* qd5 = reinterpret_cast<float*>(qn + 4);                                    // [LARGE_LDS_MAXK] upper bound of the queued point's squared 5th distance
-    uint16_t* queue = reinterpret_cast<uint16_t*>(qd5 + LARGE_LDS_MAXK);              // [LARGE_LDS_MAXK]
-    float* BB = reinterpret_cast<float*>(queue + LARGE_LDS_MAXK);                     // [K / LL_BLK][8] bounding boxes of the index blocks {min xyz, -, max xyz, -}
+    using Lds = LargeListsLds;
+    f32x4* X = LDS_AT(f32x4, smem, Lds::X);
+    long long* fxy = LDS_AT(long long, smem, Lds::F_XY);
+    int* fz = LDS_AT(int, smem, Lds::F_Z);
+    const RepAcc Fz = {fxy, fz};                                                      // fixed-point repulsion sums (knn_device.h)
+    float* RL = LDS_AT(float, smem, Lds::RL);
+    float* scratch = LDS_AT(float, smem, Lds::SCRATCH);
+    int* qn = LDS_AT(int, smem, Lds::QN);
+    float* qd5 = LDS_AT(float, smem, Lds::QD5);
+    uint16_t* queue = LDS_AT(uint16_t, smem, Lds::QUEUE);
+    float* BB = LDS_AT(float, smem, Lds::BB);
     const size_t cb = (size_t)cloud * K;
     float* pc = p + cb * 3;
     constexpr int PPT = LARGE_LDS_MAXK / LARGE_THREADS;                               // 4 points per thread
@@ -744,60 +736,34 @@ __global__ __launch_bounds__(LARGE_THREADS) void large_normalize_kernel(float* _
 // ---------------------------------------------------------------------------------------------
 // host launchers
 // ---------------------------------------------------------------------------------------------
-#ifdef IFD_PROF
-constexpr size_t OPT_LDS = DEC_FLOATS * 4 + MAXK * 16 * 3 + 16 + MAXK * 12 + 128 * 4 + 3 * OPT_THREADS * 16 + 8 * 8 * 8;
-#else
-constexpr size_t OPT_LDS = DEC_FLOATS * 4 + MAXK * 16 * 3 + 16 + MAXK * 12 + 128 * 4 + 3 * OPT_THREADS * 16;   // 154,400 B
-#endif
-constexpr size_t DEC_LDS = DEC_FLOATS * 4;
-constexpr size_t REP_LDS = MAXK * 16 + MAXK * 3 * 8 + 64;
-constexpr size_t NRM_LDS = MAXK * 16 + 64;
-static_assert(OPT_LDS <= 160 * 1024, "LDS budget");
 
 size_t knn_list_bytes(int B) { return (size_t)B * MAXK * LIST_M * sizeof(uint16_t); }
 // the exchange blocks of split clouds (at most one partial round of them per launch) sit behind the lists
 constexpr int COOP_MAX_CLOUDS = 512;
 // ... and behind them the Adam moments of the split-precision kernels (optimize_bf.hip: the piece image takes the moments' place in
 // LDS): 24 KB per workgroup of the largest launch
-static size_t mv_ws_bytes(int B) { return (size_t)(max(B, COOP_MAX_CLOUDS) + 32) * 3 * OPT_THREADS * sizeof(f32x4); }
-size_t optimize_ws_bytes(int B) { return knn_list_bytes(B) + COOP_MAX_CLOUDS * sizeof(CoopWs) + mv_ws_bytes(B); }
+// (optimize_ws: the one layout; its count on a null base is optimize_ws_bytes)
+OptWs optimize_ws(Carve& c, int B) {
+    OptWs w;
+    w.knn_lists = c.take<uint16_t>(knn_list_bytes(B));
+    w.coop = c.take<CoopWs>(COOP_MAX_CLOUDS * sizeof(CoopWs));
+    w.mv = c.take<f32x4>((size_t)(max(B, COOP_MAX_CLOUDS) + 32) * 3 * OPT_THREADS * sizeof(f32x4));
+    return w;
+}
+size_t optimize_ws_bytes(int B) { Carve c(nullptr); optimize_ws(c, B); return c.bytes(); }
 hipError_t configure_optimize_bf_kernels();
 hipError_t launch_part_bf(int S, int prec, const float* dec_img, const float* planes, float* p, float* m, float* v, float* loss,
                           const int32_t* lb, uint16_t* knn_lists, unsigned long long* counters, const float* adam_tab, int grid, int K,
                           const OptArgs& a, CoopWs* coop, int n, void* mv_ws, hipStream_t s);
 
 hipError_t configure_optimize_kernels() {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(optimize_kernel<8, 1>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)OPT_LDS);
-    if (e != hipSuccess) return e;
-    e = hipFuncSetAttribute(reinterpret_cast<const void*>(optimize_kernel<8, 2>),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)OPT_LDS);
-    if (e != hipSuccess) return e;
-    e = hipFuncSetAttribute(reinterpret_cast<const void*>(optimize_kernel<8, 4>),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)OPT_LDS);
-    if (e != hipSuccess) return e;
-    e = hipFuncSetAttribute(reinterpret_cast<const void*>(decode_kernel),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)DEC_LDS);
-    if (e != hipSuccess) return e;
-    e = hipFuncSetAttribute(reinterpret_cast<const void*>(large_occupancy3_kernel<0>),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)DEC_LDS);
-    if (e != hipSuccess) return e;
-    e = hipFuncSetAttribute(reinterpret_cast<const void*>(large_step_lists_kernel),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)LARGE_LISTS_LDS);
-    if (e != hipSuccess) return e;
-    e = hipFuncSetAttribute(reinterpret_cast<const void*>(large_step_kernel<false>),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)LARGE_LDS);
-    if (e != hipSuccess) return e;
-    e = hipFuncSetAttribute(reinterpret_cast<const void*>(large_step_kernel<true>),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)large_lds_bytes(LARGE_MAXK));
-    if (e != hipSuccess) return e;
-    e = hipFuncSetAttribute(reinterpret_cast<const void*>(large_repulsion_kernel<false>),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)LARGE_LDS);
-    if (e != hipSuccess) return e;
-    e = hipFuncSetAttribute(reinterpret_cast<const void*>(large_repulsion_kernel<true>),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)large_lds_bytes(LARGE_MAXK));
-    if (e != hipSuccess) return e;
-    return configure_optimize_bf_kernels();
+    const hipError_t e = opt_in_dynamic_lds({{optimize_kernel<8, 1>, OptLds<0>::BYTES}, {optimize_kernel<8, 2>, OptLds<0>::BYTES},
+                                             {optimize_kernel<8, 4>, OptLds<0>::BYTES}, {decode_kernel, DecImageLds<0>::BYTES},
+                                             {large_occupancy3_kernel<0>, DecImageLds<0>::BYTES}, {large_step_lists_kernel, LargeListsLds::BYTES},
+                                             {large_step_kernel<false>, large_lds_bytes(LARGE_LDS_MAXK)}, {large_step_kernel<true>, large_lds_bytes(LARGE_MAXK)},
+                                             {large_repulsion_kernel<false>, large_lds_bytes(LARGE_LDS_MAXK)},
+                                             {large_repulsion_kernel<true>, large_lds_bytes(LARGE_MAXK)}});
+    return e != hipSuccess ? e : configure_optimize_bf_kernels();
 }
 
 // One launch of `n` clouds starting at cloud `c0`, S workgroups per cloud.
@@ -815,7 +781,7 @@ static hipError_t launch_part(const float* dec_img, const float* planes, float* 
         return launch_part_bf(S, a.precision, dec_img, planes + (a.planes_shared ? 0 : (size_t)c0 * CLOUD_PLANE_FLOATS), p + o3,
                               m ? m + o3 : nullptr, v ? v + o3 : nullptr, loss ? loss + 2 * (size_t)c0 : nullptr, lb ? lb + c0 : nullptr,
                               knn_lists + (size_t)c0 * MAXK * LIST_M, counters, adam_tab, grid, K, a, coop, n, mv_ws, s);
-    hipLaunchKernelGGL((optimize_kernel<8, S>), dim3(grid), dim3(512), OPT_LDS, s, dec_img,
+    hipLaunchKernelGGL((optimize_kernel<8, S>), dim3(grid), dim3(512), OptLds<0>::BYTES, s, dec_img,
                        planes + (a.planes_shared ? 0 : (size_t)c0 * CLOUD_PLANE_FLOATS), p + o3, m ? m + o3 : nullptr,
                        v ? v + o3 : nullptr, loss ? loss + 2 * (size_t)c0 : nullptr, lb ? lb + c0 : nullptr,
                        knn_lists + (size_t)c0 * MAXK * LIST_M, counters, adam_tab, K, a, coop, n);
@@ -833,9 +799,11 @@ hipError_t launch_optimize(const float* dec_img, const float* planes, float* p, 
                            float* loss, const int32_t* loss_batch_per_cloud, void* ws,
                            unsigned long long* counters, const float* adam_tab, int B, int K, const OptArgs& a,
                            int split, int n_cu, hipStream_t s) {
-    uint16_t* knn_lists = static_cast<uint16_t*>(ws);
-    CoopWs* coop = reinterpret_cast<CoopWs*>(static_cast<char*>(ws) + knn_list_bytes(B));
-    void* mv_ws = static_cast<char*>(ws) + knn_list_bytes(B) + COOP_MAX_CLOUDS * sizeof(CoopWs);
+    Carve c(ws);
+    const OptWs w = optimize_ws(c, B);
+    uint16_t* knn_lists = w.knn_lists;
+    CoopWs* coop = w.coop;
+    void* mv_ws = w.mv;
     n_cu = max(8, min(n_cu, COOP_MAX_CLOUDS));
     hipError_t e = hipSuccess;
 #define IFD_PART(S_, c0_, n_) \
@@ -876,7 +844,7 @@ hipError_t launch_adam_table(float* tab, int t0, int steps, float lr, hipStream_
 
 hipError_t launch_decode(const float* dec_img, const float* planes, const float* p, int B, int K,
                          float* logits, float* dlogit_dp, DecConst dc, hipStream_t s) {
-    hipLaunchKernelGGL(decode_kernel, dim3(B), dim3(OPT_THREADS), DEC_LDS, s, dec_img, planes, p, K, logits,
+    hipLaunchKernelGGL(decode_kernel, dim3(B), dim3(OPT_THREADS), DecImageLds<0>::BYTES, s, dec_img, planes, p, K, logits,
                        dlogit_dp, dc);
     return hipGetLastError();
 }
@@ -884,25 +852,33 @@ hipError_t launch_decode(const float* dec_img, const float* planes, const float*
 hipError_t launch_repulsion(const float* p, int B, int K, float* loss, float* grad, int32_t* knn_idx,
                             float radius, float h, float eps, hipStream_t s) {
     RepConst rc = {radius, h, eps};
-    hipLaunchKernelGGL(repulsion_kernel, dim3(B), dim3(OPT_THREADS), REP_LDS, s, p, K, loss, grad, knn_idx, rc);
+    hipLaunchKernelGGL(repulsion_kernel, dim3(B), dim3(OPT_THREADS), RepLds::BYTES, s, p, K, loss, grad, knn_idx, rc);
     return hipGetLastError();
 }
 
 // workspace of the launch-per-step path: [G: B K float4 | own moments (if the caller passes none) | global repulsion accumulators
 // (K > LARGE_LDS_MAXK) | certified neighbour lists (K <= LARGE_LDS_MAXK)]
-static size_t large_ws_head(int B, int K, bool own_moments) {
-    return (((size_t)B * K * 16 + (own_moments ? (size_t)B * K * 3 * 4 * 2 : 0) + large_f_bytes(B, K)) + 15) & ~(size_t)15;
+LargeWs large_ws(Carve& c, int B, int K, bool own_moments) {
+    LargeWs w;
+    w.G = c.take<f32x4>((size_t)B * K * 16);
+    w.moments = c.take<float>(own_moments ? (size_t)B * K * 3 * 4 * 2 : 0);
+    w.f = c.take<void>(large_f_bytes(B, K));
+    c.round_up(16);
+    w.lists = c.take<void>(large_list_bytes(B, K));
+    return w;
 }
-size_t large_ws_bytes(int B, int K, bool own_moments) { return large_ws_head(B, K, own_moments) + large_list_bytes(B, K); }
+size_t large_ws_bytes(int B, int K, bool own_moments) { Carve c(nullptr); large_ws(c, B, K, own_moments); return c.bytes(); }
 void* large_list_ws(void* ws, int B, int K, bool own_moments) {
-    return K <= LARGE_LDS_MAXK ? static_cast<char*>(ws) + large_ws_head(B, K, own_moments) : nullptr;
+    Carve c(ws);
+    return K <= LARGE_LDS_MAXK ? large_ws(c, B, K, own_moments).lists : nullptr;
 }
 // the repulsion accumulators of clouds beyond LARGE_LDS_MAXK points: the LAST large_f_bytes of the workspace, zeroed here
 // (every step leaves them zero again)
 hipError_t large_f_prepare(void* ws, int B, int K, bool own_moments, void** f_ws, hipStream_t s) {
     *f_ws = nullptr;
     if (K <= LARGE_LDS_MAXK) return hipSuccess;
-    *f_ws = static_cast<char*>(ws) + (size_t)B * K * 16 + (own_moments ? (size_t)B * K * 3 * 4 * 2 : 0);
+    Carve c(ws);
+    *f_ws = large_ws(c, B, K, own_moments).f;
     return hipMemsetAsync(*f_ws, 0, large_f_bytes(B, K), s);
 }
 // a.knn_scan_every_step: 0 = certified lists where they exist (K <= LARGE_LDS_MAXK and a list workspace), 1 = the exact brute-force
@@ -911,9 +887,10 @@ static void large_step_launch(float* p, float* m, float* v, const f32x4* G, int 
                               const int32_t* lbpc, const OptArgs& a, const RepConst& rc, float* loss, void* f_ws, void* list_ws,
                               unsigned long long* status, hipStream_t s) {
     const int ref_form = a.knn_scan_every_step == 2 ? 1 : 0;
+    Carve lists_c(list_ws);
     if (K <= LARGE_LDS_MAXK && list_ws != nullptr && a.knn_scan_every_step == 0)
-        hipLaunchKernelGGL(large_step_lists_kernel, dim3(B), dim3(LARGE_THREADS), LARGE_LISTS_LDS, s, p, m, v, G, K, adam_tab, step, lbpc,
-                           a.loss_batch, a.rep_weight, rc, loss, large_lists_at(list_ws, B, K), status);
+        hipLaunchKernelGGL(large_step_lists_kernel, dim3(B), dim3(LARGE_THREADS), LargeListsLds::BYTES, s, p, m, v, G, K, adam_tab, step, lbpc,
+                           a.loss_batch, a.rep_weight, rc, loss, large_lists(lists_c, B, K), status);
     else if (K <= LARGE_LDS_MAXK)
         hipLaunchKernelGGL(large_step_kernel<false>, dim3(B), dim3(LARGE_THREADS), large_lds_bytes(K), s, p, m, v, G, K, adam_tab,
                            step, lbpc, a.loss_batch, a.rep_weight, rc, loss, f_ws, status, ref_form);
@@ -935,7 +912,7 @@ hipError_t launch_large_occupancy(int precision, const float* dec_img, const flo
     if (precision != 0)
         return launch_large_occupancy_bf(precision, dec_img, planes, p, B, parts, K, loss_batch_per_cloud, loss_batch, thr, want_loss,
                                          static_cast<f32x4*>(G), dc, s);
-    hipLaunchKernelGGL(large_occupancy3_kernel<0>, dim3(B, parts), dim3(OPT_THREADS), DEC_LDS, s, dec_img, planes, p, K,
+    hipLaunchKernelGGL(large_occupancy3_kernel<0>, dim3(B, parts), dim3(OPT_THREADS), DecImageLds<0>::BYTES, s, dec_img, planes, p, K,
                        loss_batch_per_cloud, loss_batch, thr, want_loss, static_cast<f32x4*>(G), dc);
     return hipGetLastError();
 }
@@ -973,7 +950,7 @@ hipError_t launch_large_normalize(float* p, int B, int K, hipStream_t s) {
 }
 
 hipError_t launch_normalize(float* p, int B, int K, hipStream_t s) {
-    hipLaunchKernelGGL(normalize_kernel, dim3(B), dim3(OPT_THREADS), NRM_LDS, s, p, K);
+    hipLaunchKernelGGL(normalize_kernel, dim3(B), dim3(OPT_THREADS), NrmLds::BYTES, s, p, K);
     return hipGetLastError();
 }
 

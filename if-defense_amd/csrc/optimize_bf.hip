@@ -5,34 +5,22 @@
 
 namespace ifd {
 
-// 156,704 B (the moments are in global memory)
-constexpr size_t OPT_LDS_BF = (size_t)BF_IMG_BYTES + MAXK * 16 * 3 + 16 + MAXK * 12 + 128 * 4;
-static_assert(OPT_LDS_BF <= 160 * 1024, "LDS budget");
-constexpr size_t LARGE_OCC_LDS_BF = (size_t)BF_IMG_BYTES;               // large_occupancy3_kernel<1 | 2>: the piece image
-
+// (OptLds<1 | 2>: 156,704 B - the moments are in global memory; large_occupancy3_kernel<1 | 2>: the piece image)
 hipError_t configure_optimize_bf_kernels() {
-    hipError_t e = hipSuccess;
-#define IFD_CFG(S_, P_)                                                                                                      \
-    if (e == hipSuccess)                                                                                                     \
-        e = hipFuncSetAttribute(reinterpret_cast<const void*>(optimize_kernel<8, S_, P_>), hipFuncAttributeMaxDynamicSharedMemorySize, \
-                                (int)OPT_LDS_BF);
-    IFD_CFG(1, 1) IFD_CFG(2, 1) IFD_CFG(4, 1) IFD_CFG(1, 2) IFD_CFG(2, 2) IFD_CFG(4, 2)
-#undef IFD_CFG
-    if (e == hipSuccess)
-        e = hipFuncSetAttribute(reinterpret_cast<const void*>(large_occupancy3_kernel<1>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)LARGE_OCC_LDS_BF);
-    if (e == hipSuccess)
-        e = hipFuncSetAttribute(reinterpret_cast<const void*>(large_occupancy3_kernel<2>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)LARGE_OCC_LDS_BF);
-    return e;
+    return opt_in_dynamic_lds({{optimize_kernel<8, 1, 1>, OptLds<1>::BYTES}, {optimize_kernel<8, 2, 1>, OptLds<1>::BYTES},
+                               {optimize_kernel<8, 4, 1>, OptLds<1>::BYTES}, {optimize_kernel<8, 1, 2>, OptLds<2>::BYTES},
+                               {optimize_kernel<8, 2, 2>, OptLds<2>::BYTES}, {optimize_kernel<8, 4, 2>, OptLds<2>::BYTES},
+                               {large_occupancy3_kernel<1>, DecImageLds<1>::BYTES}, {large_occupancy3_kernel<2>, DecImageLds<2>::BYTES}});
 }
 
 // the occupancy half of the launch-per-step path (clouds of more than MAXK points) on the split-precision tile
 hipError_t launch_large_occupancy_bf(int prec, const float* dec_img, const float* planes, const float* p, int B, int parts, int K,
                                      const int32_t* lbpc, int loss_batch, float thr, int want_loss, f32x4* G, DecConst dc, hipStream_t s) {
     if (prec == 1)
-        hipLaunchKernelGGL(large_occupancy3_kernel<1>, dim3(B, parts), dim3(OPT_THREADS), LARGE_OCC_LDS_BF, s, dec_img, planes, p, K, lbpc,
+        hipLaunchKernelGGL(large_occupancy3_kernel<1>, dim3(B, parts), dim3(OPT_THREADS), DecImageLds<1>::BYTES, s, dec_img, planes, p, K, lbpc,
                            loss_batch, thr, want_loss, G, dc);
     else
-        hipLaunchKernelGGL(large_occupancy3_kernel<2>, dim3(B, parts), dim3(OPT_THREADS), LARGE_OCC_LDS_BF, s, dec_img, planes, p, K, lbpc,
+        hipLaunchKernelGGL(large_occupancy3_kernel<2>, dim3(B, parts), dim3(OPT_THREADS), DecImageLds<2>::BYTES, s, dec_img, planes, p, K, lbpc,
                            loss_batch, thr, want_loss, G, dc);
     return hipGetLastError();
 }
@@ -41,7 +29,7 @@ template <int S, int PREC>
 static hipError_t launch_bf(const float* dec_img, const float* planes, float* p, float* m, float* v, float* loss, const int32_t* lb,
                             uint16_t* knn_lists, unsigned long long* counters, const float* adam_tab, int grid, int K, const OptArgs& a,
                             CoopWs* coop, int n, void* mv_ws, hipStream_t s) {
-    hipLaunchKernelGGL((optimize_kernel<8, S, PREC>), dim3(grid), dim3(512), OPT_LDS_BF, s, dec_img, planes, p, m, v, loss, lb, knn_lists,
+    hipLaunchKernelGGL((optimize_kernel<8, S, PREC>), dim3(grid), dim3(512), OptLds<PREC>::BYTES, s, dec_img, planes, p, m, v, loss, lb, knn_lists,
                        counters, adam_tab, K, a, coop, n, static_cast<f32x4*>(mv_ws));
     return hipGetLastError();
 }

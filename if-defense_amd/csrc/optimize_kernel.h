@@ -28,10 +28,10 @@
 #include "ifd_device.h"
 #include "ifd_internal.h"
 #include "knn_device.h"
+#include "lds_layout.h"
 
 namespace ifd {
 [[maybe_unused]] constexpr int IFD_TRACE_BASE = 16;      // first trace slot in the device counter buffer (= IFD_N_COUNTERS)
-typedef float f32x2 __attribute__((ext_vector_type(2)));
 
 typedef float f32x8 __attribute__((ext_vector_type(8)));
 
@@ -941,6 +941,23 @@ __device__ __forceinline__ void load_dec_image(float* __restrict__ W, const floa
 // PREC > 0: the decoder tiles on the bf16 matrix core with f32-exact operand splits (tile_bf.h; 1 = six terms, 2 = three).  The
 // parameter image is then the 94,736-byte piece image (ifd_device.h) and the Adam moments sleep in global memory (mv_ws, 24 KB per
 // workgroup, L2-resident) instead of LDS: everything else - neighbour lists, repulsion, Adam, split clouds - is the same code.
+//
+// LDS: the parameter image, the cloud's state (CloudLds, lds_layout.h), then - f32 only - the Adam moments of the owner threads;
+// -DIFD_PROF builds keep the per-wave cycle counters of the f32 kernel behind the moments.
+#ifdef IFD_PROF
+constexpr bool OPT_PROF = true;
+#else
+constexpr bool OPT_PROF = false;
+#endif
+template <int PREC, bool PROF = OPT_PROF>
+struct OptLds : CloudLds<DecImageLds<PREC>::BYTES, true> {
+    static constexpr size_t W = 0;                                                   // DecImageLds<PREC>
+    static constexpr size_t MV = OptLds::END;                                        // f32x4 [3][OPT_THREADS] (PREC 0)
+    static constexpr size_t PROF_CNT = MV + (PREC == 0 ? 3 * OPT_THREADS * 16 : 0);  // unsigned long long [OWN_WAVES][PC_COUNT] (PROF, PREC 0)
+    static constexpr size_t BYTES = PROF_CNT + (PROF && PREC == 0 ? OWN_WAVES * PC_COUNT * 8 : 0);
+    static_assert(BYTES <= LDS_MAX_BYTES, "LDS budget");
+};
+static_assert(OptLds<0, false>::BYTES == 154400 && OptLds<1, false>::BYTES == 156704 && OptLds<2>::BYTES == 156704, "LDS of optimize_kernel");
 template <int NW, int S, int PREC = 0>
 __global__ __launch_bounds__(NW * 64, NW / 4) void optimize_kernel(
     const float* __restrict__ dec_img, const float* __restrict__ planes, float* __restrict__ p,
@@ -960,17 +977,20 @@ __global__ __launch_bounds__(NW * 64, NW / 4) void optimize_kernel(
     static_assert(S * OW <= MAX_WAVES && S * OW <= MAX_COOP_WAVES, "one maxima slot per owner wave of the cloud");
     K = K < MAXK ? K : MAXK;                          // (the launcher guarantees it; spelled out so that pb < K folds to false)
     extern __shared__ __attribute__((aligned(16))) float smem[];
-    constexpr int IMG_FLOATS = PREC == 0 ? DEC_FLOATS : BF_IMG_BYTES / 4;
-    float* W = smem;                                                 // decoder parameter image
-    f32x4* G = reinterpret_cast<f32x4*>(smem + IMG_FLOATS);          // occupancy gradient (+ BCE term in .w)
-    f32x4* X = G + MAXK;                                             // current points (x, y, z, 1); X[MAXK] = far-away dummy
-    f32x4* PIX = X + MAXK + 1;                                       // their sampling coordinates (pix_encode)
-    const RepAcc F = {reinterpret_cast<long long*>(PIX + MAXK),      // fixed-point repulsion-gradient scatter (knn_device.h)
-                      reinterpret_cast<int*>(reinterpret_cast<long long*>(PIX + MAXK) + MAXK)};
-    float* scratch = reinterpret_cast<float*>(F.z + MAXK);           // 128 floats
+    using L = OptLds<PREC>;
+    static_assert(NW == OWN_WAVES, "OptLds and OptScratch are sized for eight waves");
+    constexpr int IMG_FLOATS = DecImageLds<PREC>::BYTES / 4;
+    // (each block stepped from the one before it, LDS_NEXT: this kernel's code depends on how its addresses are formed)
+    float* W = LDS_AT(float, smem, L::W);                            // decoder parameter image
+    f32x4* G = LDS_NEXT(f32x4, W, L::W, L::G);                       // occupancy gradient (+ BCE term in .w)
+    f32x4* X = LDS_NEXT(f32x4, G, L::G, L::X);                       // current points (x, y, z, 1); X[MAXK] = far-away dummy
+    f32x4* PIX = LDS_NEXT(f32x4, X, L::X, L::PIX);                   // their sampling coordinates (pix_encode)
+    const RepAcc F = {LDS_NEXT(long long, PIX, L::PIX, L::F_XY),     // fixed-point repulsion-gradient scatter (knn_device.h)
+                      LDS_NEXT(int, LDS_NEXT(long long, PIX, L::PIX, L::F_XY), L::F_XY, L::F_Z)};
+    float* scratch = LDS_NEXT(float, F.z, L::F_Z, L::SCRATCH);       // OptScratch
     // [3][OPT_THREADS] Adam moments of the owner threads: LDS, or (PREC > 0: the piece image takes their place) this workgroup's
     // block of the launch's moment workspace
-    f32x4* MV = PREC == 0 ? reinterpret_cast<f32x4*>(scratch + 128) : mv_ws + (size_t)blockIdx.x * (3 * OPT_THREADS);
+    f32x4* MV = PREC == 0 ? LDS_NEXT(f32x4, scratch, L::SCRATCH, L::MV) : mv_ws + (size_t)blockIdx.x * (3 * OPT_THREADS);
 
     // split clouds: the S members of a cloud sit 8 workgroups apart - consecutive workgroups go to the 8 XCDs in turn, so
     // the members share an L2 (an optimisation only: every exchange is agent-scope)
@@ -1051,13 +1071,13 @@ __global__ __launch_bounds__(NW * 64, NW / 4) void optimize_kernel(
     const float rep_scale = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(A.rep_weight / ((float)loss_batch * (float)K * 5.f))));
     const bool use_rep = A.rep_weight > 0.f;
     uint16_t* cloud_lists = knn_lists + (size_t)cloud * MAXK * LIST_M;   // certified neighbour lists, global (L2-resident)
-    float* dmaxbuf = scratch + 32;                                   // [2][MAX_WAVES] per-wave max |x - x0| (next step)
-    float* movebuf = scratch + 64;                                   // [2][MAX_WAVES] per-wave max single-step move
-    volatile int* rebuild_flag = reinterpret_cast<volatile int*>(scratch + 28);   // [2] by step parity
-    int* tile_ctr = reinterpret_cast<int*>(scratch + 30);            // next decoder tile of this step
-    int* knn_done = reinterpret_cast<int*>(scratch + 31);            // split clouds: owner waves of this member past their kNN phase
-    int* coop_abort = reinterpret_cast<int*>(scratch + 27);          // split clouds: a cross-CU wait of this member gave up (coop_wait)
-    unsigned int* lcnt = reinterpret_cast<unsigned int*>(scratch + 96);           // [CN_COUNT] event counters
+    float* dmaxbuf = scratch + OptScratch::DMAX;
+    float* movebuf = scratch + OptScratch::MOVE;
+    volatile int* rebuild_flag = reinterpret_cast<volatile int*>(scratch + OptScratch::REBUILD_FLAG);
+    int* tile_ctr = reinterpret_cast<int*>(scratch + OptScratch::TILE_CTR);
+    int* knn_done = reinterpret_cast<int*>(scratch + OptScratch::KNN_DONE);
+    int* coop_abort = reinterpret_cast<int*>(scratch + OptScratch::COOP_ABORT);
+    unsigned int* lcnt = reinterpret_cast<unsigned int*>(scratch + OptScratch::CNT);
     const KnnShared ksh = {dmaxbuf, movebuf, rebuild_flag};
 
     if (tid < 2) rebuild_flag[tid] = 0;
@@ -1069,7 +1089,8 @@ __global__ __launch_bounds__(NW * 64, NW / 4) void optimize_kernel(
     }
     __syncthreads();
 #ifdef IFD_PROF
-    unsigned long long* lprof = reinterpret_cast<unsigned long long*>(MV + 3 * OPT_THREADS);   // [NW][PC_COUNT] behind MV
+    // [NW][PC_COUNT] behind MV (PREC > 0: behind this workgroup's block of the moment workspace, as before)
+    unsigned long long* lprof = PREC == 0 ? LDS_NEXT(unsigned long long, MV, L::MV, L::PROF_CNT) : reinterpret_cast<unsigned long long*>(MV + 3 * OPT_THREADS);
     if (tid < NW * PC_COUNT) lprof[tid] = 0ull;
     __syncthreads();
 #endif
@@ -1359,8 +1380,8 @@ __global__ __launch_bounds__(OPT_THREADS, 1) void large_occupancy3_kernel(
     const float* __restrict__ dec_img, const float* __restrict__ planes, const float* __restrict__ p, int K,
     const int32_t* __restrict__ loss_batch_per_cloud, int loss_batch, float thr, int want_loss_i, f32x4* __restrict__ G, DecConst dc) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
-    constexpr int IMG_FLOATS = PREC == 0 ? DEC_FLOATS : BF_IMG_BYTES / 4;
-    float* W = smem;
+    constexpr int IMG_FLOATS = DecImageLds<PREC>::BYTES / 4;
+    float* W = LDS_AT(float, smem, DecImageLds<PREC>::W);
     const int cloud = blockIdx.x, tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     load_dec_image(W, dec_img, IMG_FLOATS);

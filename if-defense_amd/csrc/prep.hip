@@ -9,20 +9,11 @@
 // batched or sharded over GPUs.  For parity tests the draws can be passed in explicitly.
 #include "ifd_device.h"
 #include "ifd_internal.h"
+#include "lds_layout.h"
 
 namespace ifd {
 
-constexpr int PREP_THREADS = 1024;
-// PREP_MAXK (ifd_internal.h) = 10,000: the largest input cloud these kernels accept (the LDS of prepare_kernel: 16 bytes per
-// point).  Up to SOR_NARROW_MAXK points sor_kernel keeps the cloud in LDS in double (32 bytes per point); above, in float
-// with the doubles re-made per pair (12 bytes per point) - same values, see sor_kernel.
-constexpr int SOR_NARROW_MAXK = 4096;
-constexpr int PREP_SORT_MAX = 4096;      // up to this many optimised points per cloud leave prepare_kernel in Morton order (rank by counting: O(n^2))
-// entries of prepare_kernel's key array: the K subset keys, or the n_opt Morton keys of the optimised points if there are more of
-// them (rounded so that the doubles behind the array stay 8-byte aligned: 12 K + 4 nkey bytes in front of them)
-__host__ __device__ inline int prep_nkey(int K, int n_opt_sorted) {
-    return n_opt_sorted > K ? n_opt_sorted + ((3 * K + n_opt_sorted) & 1) : K;
-}
+// PREP_THREADS, SOR_NARROW_MAXK, PREP_SORT_MAX, prep_nkey and the kernels' LDS layouts: lds_layout.h
 
 // Philox-4x32-10 and u01: ifd_device.h
 
@@ -65,10 +56,11 @@ __global__ __launch_bounds__(PREP_THREADS) void sor_kernel(const float* __restri
                                                             uint8_t* __restrict__ keep, double* __restrict__ value_out) {
     extern __shared__ __attribute__((aligned(16))) double dsm[];
     constexpr int PPT = WIDE ? (PREP_MAXK + PREP_THREADS - 1) / PREP_THREADS : SOR_NARROW_MAXK / PREP_THREADS;     // 10 : 4
-    double* scratch = dsm;                // [16]
-    double* X = dsm + 16;                 // narrow: [K][3] doubles, then XX [K] = |x|^2 (the launch sizes the LDS by K)
-    double* XX = X + 3 * K;
-    float* Xf = reinterpret_cast<float*>(dsm + 16);       // wide: [K][3] floats
+    const SorLdsAt L = sor_lds_at<WIDE>(K);           // (the launch sizes the LDS by K)
+    double* scratch = LDS_AT(double, dsm, L.SCRATCH); // [16]
+    double* X = LDS_AT(double, dsm, L.X);             // narrow: [K][3] doubles, then XX [K] = |x|^2
+    double* XX = LDS_AT(double, dsm, L.XX);
+    float* Xf = LDS_AT(float, dsm, L.X);              // wide: [K][3] floats
     double val[PPT];                      // value of point tid + 1024 r (registers)
     const int b = blockIdx.x, tid = threadIdx.x;
     const float* p = pc + (size_t)b * K * 3;
@@ -151,11 +143,12 @@ __global__ __launch_bounds__(PREP_THREADS) void prepare_kernel(const float* __re
     // the optimised points leave in Morton order when the draws are the library's own (see the end of the kernel)
     const bool morton = init_idx == nullptr && noise == nullptr && A.n_opt <= PREP_SORT_MAX && A.no_morton == 0;
     const int nkey = prep_nkey(K, morton ? A.n_opt : 0);
-    float* P = fsm;                                                   // [K][3] kept points, then processed
-    uint32_t* KEY = reinterpret_cast<uint32_t*>(P + 3 * K);           // [K] random keys for the subset ...
+    const PrepLdsAt L = prep_lds_at(K, nkey);
+    float* P = LDS_AT(float, fsm, L.P);                               // [K][3] kept points, then processed
+    uint32_t* KEY = LDS_NEXT(uint32_t, P, L.P, L.KEY);                // [K] random keys for the subset ...
     int* POS = reinterpret_cast<int*>(KEY);                           // ... in the place of the compaction prefix (done by then)
-    float* scratch = reinterpret_cast<float*>(KEY + nkey);            // [64]  (8-byte aligned: holds doubles)
-    int* s_n = reinterpret_cast<int*>(scratch + 62);
+    float* scratch = LDS_NEXT(float, KEY, L.KEY, L.SCRATCH);          // [64]  (8-byte aligned: holds doubles)
+    int* s_n = reinterpret_cast<int*>(scratch + PrepScratch::S_N);
     const int b = blockIdx.x, tid = threadIdx.x;
     const uint32_t gcloud = (uint32_t)(A.cloud_base + b);
     const float* p = pc + (size_t)b * K * 3;
@@ -316,37 +309,23 @@ __global__ __launch_bounds__(PREP_THREADS) void prepare_kernel(const float* __re
     }
 }
 
-// LDS by the cloud size: SOR 32 K + 128 B up to 4096 points (131,200 B there, 32,896 B at 1024), 12 K + 128 B above
-// (120,128 B at 10,000); prepare 16 K + 256 B (160,256 B at 10,000)
-static size_t sor_lds(int K) { return K <= SOR_NARROW_MAXK ? ((size_t)4 * K + 16) * sizeof(double) : (size_t)12 * K + 4 * (K & 1) + 128; }
-static size_t prep_lds(int K, int n_opt = 0) {         // n_opt: the Morton keys of the optimised points share the subset keys' array
-    return (size_t)12 * K + (size_t)4 * prep_nkey(K, n_opt <= PREP_SORT_MAX ? n_opt : 0) + 64 * 4;      // (sized for the sorted case whatever the hook says)
-}
+// LDS by the cloud size (lds_layout.h).  n_opt: the Morton keys of the optimised points share the subset keys' array (sized for the
+// sorted case whatever the hook says)
+static size_t prep_lds_bytes(int K, int n_opt) { return prep_lds_at(K, prep_nkey(K, n_opt <= PREP_SORT_MAX ? n_opt : 0)).BYTES; }
 
 hipError_t configure_prep_kernels() {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(sor_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                       (int)sor_lds(SOR_NARROW_MAXK));
-    if (e != hipSuccess) return e;
-    e = hipFuncSetAttribute(reinterpret_cast<const void*>(sor_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                            (int)sor_lds(PREP_MAXK));
-    if (e != hipSuccess) return e;
-    e = hipFuncSetAttribute(reinterpret_cast<const void*>(sor_kernel<false, 3>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                            (int)sor_lds(SOR_NARROW_MAXK));
-    if (e != hipSuccess) return e;
-    e = hipFuncSetAttribute(reinterpret_cast<const void*>(sor_kernel<true, 3>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                            (int)sor_lds(PREP_MAXK));
-    if (e != hipSuccess) return e;
-    return hipFuncSetAttribute(reinterpret_cast<const void*>(prepare_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                               (int)prep_lds(PREP_MAXK));
+    return opt_in_dynamic_lds({{sor_kernel<false>, sor_lds_bytes(SOR_NARROW_MAXK)}, {sor_kernel<true>, sor_lds_bytes(PREP_MAXK)},
+                               {sor_kernel<false, 3>, sor_lds_bytes(SOR_NARROW_MAXK)}, {sor_kernel<true, 3>, sor_lds_bytes(PREP_MAXK)},
+                               {prepare_kernel, prep_lds_bytes(PREP_MAXK, 0)}});
 }
 
 hipError_t launch_sor(const float* pc, int B, int K, int k_nn, double alpha, uint8_t* keep, double* value, hipStream_t s) {
     if (K <= SOR_NARROW_MAXK) {
-        if (k_nn <= 2) hipLaunchKernelGGL((sor_kernel<false, 3>), dim3(B), dim3(PREP_THREADS), sor_lds(K), s, pc, K, k_nn, alpha, keep, value);
-        else hipLaunchKernelGGL((sor_kernel<false, 8>), dim3(B), dim3(PREP_THREADS), sor_lds(K), s, pc, K, k_nn, alpha, keep, value);
+        if (k_nn <= 2) hipLaunchKernelGGL((sor_kernel<false, 3>), dim3(B), dim3(PREP_THREADS), sor_lds_bytes(K), s, pc, K, k_nn, alpha, keep, value);
+        else hipLaunchKernelGGL((sor_kernel<false, 8>), dim3(B), dim3(PREP_THREADS), sor_lds_bytes(K), s, pc, K, k_nn, alpha, keep, value);
     } else {
-        if (k_nn <= 2) hipLaunchKernelGGL((sor_kernel<true, 3>), dim3(B), dim3(PREP_THREADS), sor_lds(K), s, pc, K, k_nn, alpha, keep, value);
-        else hipLaunchKernelGGL((sor_kernel<true, 8>), dim3(B), dim3(PREP_THREADS), sor_lds(K), s, pc, K, k_nn, alpha, keep, value);
+        if (k_nn <= 2) hipLaunchKernelGGL((sor_kernel<true, 3>), dim3(B), dim3(PREP_THREADS), sor_lds_bytes(K), s, pc, K, k_nn, alpha, keep, value);
+        else hipLaunchKernelGGL((sor_kernel<true, 8>), dim3(B), dim3(PREP_THREADS), sor_lds_bytes(K), s, pc, K, k_nn, alpha, keep, value);
     }
     return hipGetLastError();
 }
@@ -354,7 +333,7 @@ hipError_t launch_sor(const float* pc, int B, int K, int k_nn, double alpha, uin
 hipError_t launch_prepare(const float* pc, const uint8_t* keep, int B, int K, const PrepArgs& a, const int32_t* sel_idx,
                           const int32_t* init_idx, const float* noise, float* sel, int32_t* t_per_cloud, float* init,
                           int32_t* n_kept, float* proc_out, hipStream_t s) {
-    hipLaunchKernelGGL(prepare_kernel, dim3(B), dim3(PREP_THREADS), prep_lds(K, a.n_opt), s, pc, keep, K, a, sel_idx, init_idx, noise,
+    hipLaunchKernelGGL(prepare_kernel, dim3(B), dim3(PREP_THREADS), prep_lds_bytes(K, a.n_opt), s, pc, keep, K, a, sel_idx, init_idx, noise,
                        sel, t_per_cloud, init, n_kept, proc_out);
     return hipGetLastError();
 }

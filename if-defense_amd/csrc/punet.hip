@@ -23,6 +23,7 @@
 // fused multiply-add that torch's CPU matmul does use (3-term dot products: fma(z, z', fma(y, y', x x'))) is written out.
 #include "ifd_device.h"
 #include "ifd_internal.h"
+#include "lds_layout.h"
 
 #pragma clang fp contract(off)
 
@@ -98,8 +99,10 @@ __global__ __launch_bounds__(DUP_THREADS) void srs_kernel(const float* __restric
     if (idx) {
         perm = idx + (size_t)b * m;
     } else {
-        partial_shuffle(lds_i, reinterpret_cast<uint32_t*>(lds_i + K), K, m, (uint32_t)(d.cloud_base + b), DUP_STAGE_SRS, d.seed_lo, d.seed_hi);
-        perm = lds_i;
+        const SrsLdsAt at = srs_lds_at(K, m);
+        int* shuffled = LDS_AT(int, lds_i, at.PERM);
+        partial_shuffle(shuffled, LDS_AT(uint32_t, lds_i, at.RND), K, m, (uint32_t)(d.cloud_base + b), DUP_STAGE_SRS, d.seed_lo, d.seed_hi);
+        perm = shuffled;
     }
     for (int t = threadIdx.x; t < m * 3; t += blockDim.x) {
         const int j = t / 3, c = t - 3 * j;
@@ -113,9 +116,10 @@ __global__ __launch_bounds__(DUP_THREADS) void fill_kernel(const float* __restri
                                                            int32_t* __restrict__ n_kept) {
     extern __shared__ int lds_i[];
     __shared__ int part[DUP_THREADS + 1];
-    int* L = lds_i;                                   // [K] kept indices, original order
-    int* perm = lds_i + K;                            // [K]
-    uint32_t* rnd = reinterpret_cast<uint32_t*>(lds_i + 2 * K);
+    const FillLdsAt at = fill_lds_at(K);
+    int* L = LDS_AT(int, lds_i, at.KEPT);             // [K] kept indices, original order
+    int* perm = LDS_AT(int, lds_i, at.PERM);          // [K]
+    uint32_t* rnd = LDS_AT(uint32_t, lds_i, at.RND);
     const int b = blockIdx.x, tid = threadIdx.x;
     const uint8_t* M = keep + (size_t)b * K;
     const int per = (K + DUP_THREADS - 1) / DUP_THREADS, lo = min(tid * per, K), hi = min(lo + per, K);
@@ -404,23 +408,18 @@ __global__ __launch_bounds__(256) void head_kernel(const float* __restrict__ img
 }  // namespace
 
 hipError_t configure_punet_kernels() {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&srs_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                       (int)(2 * PREP_MAXK * sizeof(int)));
-    if (e == hipSuccess)
-        e = hipFuncSetAttribute(reinterpret_cast<const void*>(&fill_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                (int)(3 * PREP_MAXK * sizeof(int)));
-    return e;
+    return opt_in_dynamic_lds({{srs_kernel, srs_lds_at(PREP_MAXK, PREP_MAXK).BYTES}, {fill_kernel, fill_lds_at(PREP_MAXK).BYTES}});
 }
 
 hipError_t launch_srs(const float* pc, int B, int K, int m, const int32_t* idx, DupDraws d, float* out, hipStream_t s) {
-    const size_t lds = idx ? 0 : (size_t)(K + m) * sizeof(int);
+    const size_t lds = idx ? 0 : srs_lds_at(K, m).BYTES;
     hipLaunchKernelGGL(srs_kernel, dim3(B), dim3(DUP_THREADS), lds, s, pc, K, m, idx, d, out);
     return hipGetLastError();
 }
 
 hipError_t launch_dup_fill(const float* pc, const uint8_t* keep, int B, int K, const int32_t* draws, DupDraws d, float* out,
                            int32_t* n_kept, hipStream_t s) {
-    hipLaunchKernelGGL(fill_kernel, dim3(B), dim3(DUP_THREADS), (size_t)3 * K * sizeof(int), s, pc, keep, K, draws, d, out, n_kept);
+    hipLaunchKernelGGL(fill_kernel, dim3(B), dim3(DUP_THREADS), fill_lds_at(K).BYTES, s, pc, keep, K, draws, d, out, n_kept);
     return hipGetLastError();
 }
 

@@ -18,6 +18,7 @@
 #include <type_traits>
 #include "ifd_device.h"
 #include "ifd_internal.h"
+#include "lds_layout.h"
 
 namespace ifd {
 
@@ -269,8 +270,9 @@ __global__ __launch_bounds__(64 * TG * CG, TG * CG == 4 ? 2 : 1) void wino_kerne
     constexpr int RPT = 4 / CG;                  // xi rows per thread in the input transform: NT * 4 * (4 / RPT) = NTHR threads
     constexpr int NROW = RPT + 1;                // patch rows a thread needs for them
     extern __shared__ __attribute__((aligned(16))) float wsm[];
-    float* s_v = wsm;                            // [16 xi][NT tiles][16 ch]
-    float* s_u = wsm + 16 * NT * 16;             // [16 xi][NCO couts][16 ch]
+    using L = WinoLds<TG, CG>;
+    float* s_v = LDS_AT(float, wsm, L::V);       // [16 xi][NT tiles][16 ch]
+    float* s_u = LDS_AT(float, wsm, L::U);       // [16 xi][NCO couts][16 ch]
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int tg = wave % TG, cg = wave / TG;
@@ -575,7 +577,7 @@ __global__ __launch_bounds__(64 * TG * CG, TG * CG == 4 ? 2 : 1) void wino_kerne
 constexpr int WINO_ITEMS = 16;       // (image, region) work items per block
 template <int TG, int CG, bool FUSE = false>
 static hipError_t launch_wino(const ConvArgs& a, int n_img, hipStream_t s) {
-    constexpr size_t LDS = (size_t)16 * 16 * (16 * TG + 16 * CG) * sizeof(float);
+    constexpr size_t LDS = WinoLds<TG, CG>::BYTES;
     const int n_items = n_img * (a.H / 8) * (a.W / (8 * TG));
     // up to WINO_ITEMS items per block, fewer where that would leave less than ~12 blocks per block slot of the chip
     const int gy = a.Cout / (16 * CG);
@@ -606,12 +608,8 @@ static hipError_t launch_wino(const ConvArgs& a, int n_img, hipStream_t s) {
 }
 
 hipError_t configure_unet_kernels() {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(wino_kernel<2, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024);
-    if (e != hipSuccess) return e;
-    e = hipFuncSetAttribute(reinterpret_cast<const void*>(wino_kernel<1, 4>), hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024);
-    if (e != hipSuccess) return e;
-    e = hipFuncSetAttribute(reinterpret_cast<const void*>(wino_kernel<2, 2, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024);
-    return e;
+    return opt_in_dynamic_lds({{wino_kernel<2, 2>, WinoLds<2, 2>::BYTES}, {wino_kernel<1, 4>, WinoLds<1, 4>::BYTES},
+                               {wino_kernel<2, 2, true>, WinoLds<2, 2>::BYTES}});
 }
 
 // env IFD_UNET_DIRECT=1: every 3x3 layer on the implicit-GEMM kernel (A/B and validation of the Winograd path)

@@ -5,7 +5,15 @@
 // formula that api.cpp carried before the layouts sized themselves - copied below as the recorded side - and (b) on a real base
 // every pointer lies inside [base, base + size), the pointers come in the recorded order and each is aligned to its element.
 // The base is address space that is reserved and never touched: the largest layouts are gigabytes.
+//
+// LDS layouts (lds_layout.h, optimize_kernel.h, onet_kernel.h) and the workspaces the .hip launchers carve themselves get the same
+// treatment: every layout's size against the byte formula its launcher carried before the layouts existed, its offsets increasing
+// and aligned to their element, the run-time ones swept over the sizes at which they change shape.
 #include "../../if-defense_amd/csrc/api.cpp"
+#include "../../if-defense_amd/csrc/optimize_kernel.h"
+namespace ifd {
+#include "../../if-defense_amd/csrc/onet_kernel.h"
+}
 
 #include <sys/mman.h>
 
@@ -196,6 +204,167 @@ void mesh_layout() {
             }
 }
 
+// ---- LDS layouts --------------------------------------------------------------------------------------------------------------
+struct Off { size_t at, align; };
+// offsets strictly increasing (a block of size 0 may share its successor's), aligned, and inside the layout
+void check_offs(const char* what, const std::vector<Off>& offs, size_t bytes, bool strict = true) {
+    CHECK(bytes <= LDS_MAX_BYTES, "%s: %zu bytes of LDS", what, bytes);
+    for (size_t i = 0; i < offs.size(); ++i) {
+        CHECK(offs[i].at < bytes, "%s: block %zu starts outside the layout", what, i);
+        CHECK(i == 0 || (strict ? offs[i].at > offs[i - 1].at : offs[i].at >= offs[i - 1].at), "%s: block %zu out of order", what, i);
+        CHECK(offs[i].at % offs[i].align == 0, "%s: block %zu misaligned", what, i);
+    }
+}
+template <class L>
+std::vector<Off> cloud_offs(bool pix) {
+    std::vector<Off> o = {{L::G, 16}, {L::X, 16}};
+    if (pix) o.push_back({L::PIX, 16});
+    o.insert(o.end(), {{L::F_XY, 8}, {L::F_Z, 4}, {L::SCRATCH, 8}});
+    return o;
+}
+// the recorded formulas
+size_t rec_sor_lds(int K) { return K <= 4096 ? ((size_t)4 * K + 16) * sizeof(double) : (size_t)12 * K + 4 * (K & 1) + 128; }
+int rec_prep_nkey(int K, int n_opt_sorted) { return n_opt_sorted > K ? n_opt_sorted + ((3 * K + n_opt_sorted) & 1) : K; }
+size_t rec_prep_lds(int K, int n_opt) { return (size_t)12 * K + (size_t)4 * rec_prep_nkey(K, n_opt <= 4096 ? n_opt : 0) + 64 * 4; }
+size_t rec_large_lds(int K) { return K <= 4096 ? (size_t)4096 * (16 + 8 + 4) + 64 * 4 : (size_t)K * 16 + 64 * 4; }
+
+void lds_layouts() {
+    static_assert(MAXK == 1024 && OPT_THREADS == 512 && LARGE_LDS_MAXK == 4096 && LARGE_MAXK == 10000 && PREP_MAXK == 10000 &&
+                  SOR_NARROW_MAXK == 4096 && PREP_SORT_MAX == 4096, "the sweeps are built around these");
+    // the persistent optimisers
+    const size_t cloud3 = (size_t)MAXK * 16 * 3 + 16 + MAXK * 12 + 128 * 4;
+    CHECK((OptLds<0, false>::BYTES) == DEC_FLOATS * 4 + cloud3 + 3 * OPT_THREADS * 16, "OptLds<0>");
+    CHECK((OptLds<0, true>::BYTES) == DEC_FLOATS * 4 + cloud3 + 3 * OPT_THREADS * 16 + 8 * 8 * 8, "OptLds<0>, IFD_PROF");
+    CHECK((OptLds<1, false>::BYTES) == (size_t)BF_IMG_BYTES + cloud3 && (OptLds<2, false>::BYTES) == (size_t)BF_IMG_BYTES + cloud3, "OptLds<1 | 2>");
+    CHECK((OptLds<1, true>::BYTES) == (size_t)BF_IMG_BYTES + cloud3, "OptLds<1>, IFD_PROF: the counters are not in LDS");
+    {
+        using L = OptLds<0, true>;
+        std::vector<Off> o = cloud_offs<L>(true);
+        o.insert(o.begin(), {L::W, 16});
+        o.insert(o.end(), {{L::MV, 16}, {L::PROF_CNT, 8}});
+        check_offs("OptLds<0>", o, L::BYTES);
+        CHECK(L::G == DEC_FLOATS * 4 && L::SCRATCH + OptScratch::FLOATS * 4 == L::MV, "OptLds<0>: image, scratch");
+        using B = OptLds<1>;
+        o = cloud_offs<B>(true);
+        o.insert(o.begin(), {B::W, 16});
+        check_offs("OptLds<1>", o, B::BYTES);
+        CHECK(B::G == (size_t)BF_IMG_BYTES && B::MV == B::BYTES, "OptLds<1>: no moments in LDS");
+    }
+    CHECK(OnetDecLds::BYTES == (size_t)OL_END * 4 && OnetOptLds::BYTES == (size_t)OL_END * 4 + MAXK * 16 * 2 + 16 + MAXK * 12 + 128 * 4, "ONet");
+    check_offs("OnetOptLds", cloud_offs<OnetOptLds>(false), OnetOptLds::BYTES);
+    CHECK(OnetOptLds::G == OnetDecLds::BYTES && OnetOptLds::PIX == OnetOptLds::F_XY, "OnetOptLds: behind the decoder, no PIX");
+    // the decoder images and the stand-alone kernels
+    CHECK(DecImageLds<0>::BYTES == (size_t)DEC_FLOATS * 4 && DecImageLds<1>::BYTES == (size_t)BF_IMG_BYTES && DecImageLds<2>::BYTES == (size_t)BF_IMG_BYTES,
+          "decoder images");
+    CHECK(RepLds::BYTES == MAXK * 16 + MAXK * 3 * 8 + 64 && NrmLds::BYTES == MAXK * 16 + 64, "repulsion / normalize");
+    check_offs("RepLds", {{RepLds::X, 16}, {RepLds::F, 8}, {RepLds::SCRATCH, 4}}, RepLds::BYTES);
+    check_offs("NrmLds", {{NrmLds::X, 16}, {NrmLds::SCRATCH, 4}}, NrmLds::BYTES);
+    // the launch-per-step path
+    {
+        using L = LargeListsLds;
+        CHECK(L::BYTES == (size_t)(4096 + 1) * 16 + (size_t)4096 * (8 + 4 + 4 + 2 + 4) + 64 * 4 + 16 + (4096 / 128) * 8 * 4, "LargeListsLds");
+        check_offs("LargeListsLds", {{L::X, 16}, {L::F_XY, 8}, {L::F_Z, 4}, {L::RL, 4}, {L::SCRATCH, 4}, {L::QN, 4}, {L::QD5, 4}, {L::QUEUE, 2}, {L::BB, 4}},
+                   L::BYTES);
+    }
+    for (int K : {1025, 4096, 4097, 10000}) {
+        CHECK(large_lds_bytes(K) == rec_large_lds(K), "large_lds_bytes K %d", K);
+        if (K <= LARGE_LDS_MAXK) {
+            const LargeLdsAt l = large_lds_at<false>(K);
+            CHECK((size_t)l.BYTES == rec_large_lds(K), "large_lds_at<false> K %d", K);
+            check_offs("large_lds_at<false>", {{(size_t)l.X, 16}, {(size_t)l.F_XY, 8}, {(size_t)l.F_Z, 4}, {(size_t)l.SCRATCH, 4}}, l.BYTES);
+        } else {
+            const LargeLdsAt l = large_lds_at<true>(K);
+            CHECK((size_t)l.BYTES == rec_large_lds(K) && l.SCRATCH == 16 * K, "large_lds_at<true> K %d", K);
+            check_offs("large_lds_at<true>", {{(size_t)l.X, 16}, {(size_t)l.SCRATCH, 4}}, l.BYTES);
+        }
+    }
+    // prep.hip
+    for (int K : {6, 4096, 4097, 10000}) {
+        CHECK(sor_lds_bytes(K) == rec_sor_lds(K), "sor_lds_bytes K %d", K);
+        if (K <= SOR_NARROW_MAXK) {
+            const SorLdsAt l = sor_lds_at<false>(K);
+            check_offs("sor_lds_at<false>", {{(size_t)l.SCRATCH, 8}, {(size_t)l.X, 8}, {(size_t)l.XX, 8}}, l.BYTES);
+            CHECK((size_t)l.BYTES == rec_sor_lds(K) && l.X == 128 && l.XX == 128 + 24 * K, "sor narrow K %d", K);
+        } else {
+            const SorLdsAt l = sor_lds_at<true>(K);
+            check_offs("sor_lds_at<true>", {{(size_t)l.SCRATCH, 8}, {(size_t)l.X, 4}}, l.BYTES);
+            CHECK((size_t)l.BYTES == rec_sor_lds(K) && l.X == 128 && l.BYTES % 8 == 0, "sor wide K %d", K);
+        }
+    }
+    for (int K : {6, 4096, 4097, 10000})
+        for (int n_opt : {0, 1024, 4096, 4097}) {
+            const int nkey = prep_nkey(K, n_opt <= PREP_SORT_MAX ? n_opt : 0);
+            const PrepLdsAt l = prep_lds_at(K, nkey);
+            CHECK(nkey == rec_prep_nkey(K, n_opt <= 4096 ? n_opt : 0) && (size_t)l.BYTES == rec_prep_lds(K, n_opt), "prep K %d n_opt %d", K, n_opt);
+            check_offs("prep_lds_at", {{(size_t)l.P, 4}, {(size_t)l.KEY, 4}, {(size_t)l.SCRATCH, 8}}, l.BYTES);
+        }
+    // encoder.hip
+    for (int threads : {640, 1024}) {
+        const EncLdsAt e = enc_lds_at(threads);
+        CHECK(e.BYTES == (size_t)threads * 33 * 4 + 3 * (size_t)threads * 2, "enc_lds_at %d", threads);
+        check_offs("enc_lds_at", {{e.NET, 16}, {e.RING, 2}}, e.BYTES);
+        const EncMfmaLdsAt m = enc_mfma_lds_at(threads);
+        CHECK(m.BYTES == (size_t)threads * 36 * 4 + 6 * (size_t)threads * 2, "enc_mfma_lds_at %d", threads);
+        check_offs("enc_mfma_lds_at", {{m.NET, 16}, {m.RING, 2}, {m.CELL, 2}}, m.BYTES);
+    }
+    // unet.hip, mesh.hip, punet.hip
+    CHECK((WinoLds<2, 2>::BYTES) == (size_t)16 * 16 * (16 * 2 + 16 * 2) * 4 && (WinoLds<1, 4>::BYTES) == (size_t)16 * 16 * (16 * 1 + 16 * 4) * 4, "WinoLds");
+    check_offs("WinoLds<1, 4>", {{WinoLds<1, 4>::V, 16}, {WinoLds<1, 4>::U, 16}}, WinoLds<1, 4>::BYTES);
+    for (int P : {3, 33, 129}) {
+        const FillzLdsAt f = fillz_lds_at(P);
+        CHECK((size_t)f.BYTES == (size_t)64 * P * 5, "fillz_lds_at P %d", P);
+        check_offs("fillz_lds_at", {{(size_t)f.VAL, 4}, {(size_t)f.KNOWN, 1}}, f.BYTES);
+    }
+    for (int K : {1, 1024, 10000}) {
+        const SrsLdsAt r = srs_lds_at(K, (K + 1) / 2);
+        CHECK((size_t)r.BYTES == (size_t)(K + (K + 1) / 2) * sizeof(int), "srs_lds_at K %d", K);
+        check_offs("srs_lds_at", {{(size_t)r.PERM, 4}, {(size_t)r.RND, 4}}, r.BYTES);
+        const FillLdsAt f = fill_lds_at(K);
+        CHECK((size_t)f.BYTES == (size_t)3 * K * sizeof(int), "fill_lds_at K %d", K);
+        check_offs("fill_lds_at", {{(size_t)f.KEPT, 4}, {(size_t)f.PERM, 4}, {(size_t)f.RND, 4}}, f.BYTES);
+    }
+}
+
+// ---- the workspaces that optimize.hip's launchers carve -----------------------------------------------------------------------
+void launcher_workspaces() {
+    for (int B : {1, 3})
+        for (int K : {1025, 4096, 4097, 10000}) {
+            const size_t b = (size_t)B, k = (size_t)K;
+            const bool lists = K <= 4096;
+            const size_t rec_lists = lists ? b * k * (64 * 2 + 16 + 8) + b * 16 : 0, rec_f = lists ? 0 : b * k * 12;
+            CHECK(large_list_bytes(B, K) == rec_lists && large_f_bytes(B, K) == rec_f, "large lists / f B %d K %d", B, K);
+            if (lists) {
+                Carve c(g_base);
+                const LargeLists L = large_lists(c, B, K);
+                CHECK(c.bytes() == rec_lists, "large_lists carve B %d K %d", B, K);
+                check_ptrs("large_lists", {P(L.cert), P(L.lists), P(L.dbase), P(L.scal)}, rec_lists);
+                CHECK((const char*)L.lists == g_base + b * k * 16 && (const char*)L.dbase == g_base + b * k * (16 + 128) &&
+                      (const char*)L.scal == g_base + b * k * (16 + 128 + 8), "large_lists offsets");
+            }
+            for (bool own : {false, true}) {
+                const size_t mom = own ? b * k * 3 * 4 * 2 : 0, head = (b * k * 16 + mom + rec_f + 15) & ~(size_t)15;
+                CHECK(large_ws_bytes(B, K, own) == head + rec_lists, "large_ws_bytes B %d K %d own %d", B, K, (int)own);
+                Carve c(g_base);
+                const LargeWs w = large_ws(c, B, K, own);
+                CHECK(c.bytes() == head + rec_lists, "large_ws carve B %d K %d own %d", B, K, (int)own);
+                CHECK((const char*)w.G == g_base && (const char*)w.moments == g_base + b * k * 16 && (const char*)w.f == g_base + b * k * 16 + mom &&
+                      (const char*)w.lists == g_base + head, "large_ws offsets B %d K %d own %d", B, K, (int)own);
+                CHECK((uintptr_t)w.lists % 16 == 0 && (uintptr_t)w.f % 8 == 0, "large_ws alignment");
+                CHECK(large_list_ws(g_base, B, K, own) == (lists ? (void*)(g_base + head) : nullptr), "large_list_ws B %d K %d", B, K);
+            }
+        }
+    for (int B : {1, 512, 513}) {
+        const size_t rec_lists = (size_t)B * MAXK * LIST_M * sizeof(uint16_t), rec_coop = 512 * sizeof(CoopWs);
+        const size_t rec = rec_lists + rec_coop + (size_t)(std::max(B, 512) + 32) * 3 * OPT_THREADS * sizeof(f32x4);
+        CHECK(knn_list_bytes(B) == rec_lists && optimize_ws_bytes(B) == rec, "optimize_ws_bytes B %d", B);
+        Carve c(g_base);
+        const OptWs w = optimize_ws(c, B);
+        CHECK(c.bytes() == rec, "optimize_ws carve B %d", B);
+        check_ptrs("optimize_ws", {P(w.knn_lists), P(w.coop), P(w.mv)}, rec);
+        CHECK((const char*)w.coop == g_base + rec_lists && (const char*)w.mv == g_base + rec_lists + rec_coop, "optimize_ws offsets B %d", B);
+    }
+}
+
 // Every create function on a device ordinal no machine has: hipSetDevice fails, the half-built context is deleted, the text names
 // the function.  Three times each: a double free or a use after free on this path is the sanitizers' to find.
 void failed_creates() {
@@ -247,6 +416,8 @@ int main() {
     loop_states();
     punet_layout();
     mesh_layout();
+    lds_layouts();
+    launcher_workspaces();
     carve();
     failed_creates();
     munmap(base, BASE_BYTES);

@@ -1,6 +1,6 @@
 """CPU checks of the host half of libifd (csrc/api.cpp): the failure path of the four create functions through the C ABI, and
-the stand-alone program tests/host/ctx_selftest.cpp (workspace layouts against their recorded byte formulas, the carve cursor,
-the same failed creates) built with the host sanitizers.  Neither needs a GPU: a device ordinal that no machine has makes
+the stand-alone program tests/host/ctx_selftest.cpp (workspace layouts and the kernels' LDS layouts against their recorded byte
+formulas, the carve cursor, the same failed creates) built with the host sanitizers.  Neither needs a GPU: a device ordinal that no machine has makes
 hipSetDevice return an error, which is the first thing the common create path can fail on."""
 import ctypes as C
 import importlib.util
