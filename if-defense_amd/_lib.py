@@ -231,6 +231,27 @@ ADD_SIGNATURES = {
                                  C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
 }
 
+# include/ifd_drop.h (the saliency Drop attack on the PointNet victim), versioned on its own
+DROP_ABI_VERSION = 1
+DROP_MAX_POINTS = 2048
+
+
+class IfdDropOut(C.Structure):
+    _fields_ = [("saliency", C.c_void_p), ("center", C.c_void_p), ("dropped", C.c_void_p)]
+
+
+class IfdDropParams(C.Structure):
+    _fields_ = [("struct_size", C.c_int32), ("num_drop", C.c_int32), ("k", C.c_int32), ("alpha", C.c_float), ("scale", C.c_float)]
+
+
+DROP_SIGNATURES = {
+    "ifd_drop_abi_version": (C.c_int, []),
+    "ifd_drop_step": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_float,
+                                C.POINTER(IfdDropOut), C.c_void_p]),
+    "ifd_drop_attack": (C.c_int, [C.c_void_p, C.POINTER(IfdDropParams), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p,
+                                  C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+}
+
 _lib = None
 
 
@@ -246,7 +267,8 @@ def load() -> C.CDLL:
     import torch  # noqa: F401  (loads libamdhip64.so.7 first; libifd binds to the same runtime)
     lib = C.CDLL(LIB_PATH, mode=C.RTLD_GLOBAL)
     for name, (res, args) in list(SIGNATURES.items()) + list(DUP_SIGNATURES.items()) + list(CLS_SIGNATURES.items()) + \
-            list(ATK_SIGNATURES.items()) + list(CW_SIGNATURES.items()) + list(KNN_SIGNATURES.items()) + list(ADD_SIGNATURES.items()):
+            list(ATK_SIGNATURES.items()) + list(CW_SIGNATURES.items()) + list(KNN_SIGNATURES.items()) + list(ADD_SIGNATURES.items()) + \
+            list(DROP_SIGNATURES.items()):
         fn = getattr(lib, name)          # AttributeError if the library lacks a declared symbol
         fn.restype, fn.argtypes = res, args
     if lib.ifd_abi_version() != ABI_VERSION:
@@ -263,5 +285,7 @@ def load() -> C.CDLL:
         raise ImportError("libifd.so KNN ABI %d != binding KNN ABI %d; rebuild" % (lib.ifd_knn_abi_version(), KNN_ABI_VERSION))
     if lib.ifd_add_abi_version() != ADD_ABI_VERSION:
         raise ImportError("libifd.so ADD ABI %d != binding ADD ABI %d; rebuild" % (lib.ifd_add_abi_version(), ADD_ABI_VERSION))
+    if lib.ifd_drop_abi_version() != DROP_ABI_VERSION:
+        raise ImportError("libifd.so DROP ABI %d != binding DROP ABI %d; rebuild" % (lib.ifd_drop_abi_version(), DROP_ABI_VERSION))
     _lib = lib
     return lib

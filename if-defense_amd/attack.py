@@ -19,7 +19,9 @@ reproduce how its ``+ 1e-9`` terms weigh against the gradient's norm.  The defau
 ``CWPerturb`` is the reference's Carlini-Wagner point-perturbation attack (baselines/attack/CW/Perturb.py, include/ifd_cw.h), on the
 same two loop forms; it is not one of ``ATTACKS``, which names the FGM family for the fgm_attack CLI.  ``CWKNN`` is the reference's
 kNN attack (baselines/attack/CW/kNN.py, include/ifd_knn.h), likewise, and ``CWAdd`` its point-adding attack
-(baselines/attack/CW/Add.py, include/ifd_add.h), whose clouds come back larger than they went in.
+(baselines/attack/CW/Add.py, include/ifd_add.h), whose clouds come back larger than they went in.  ``SaliencyDrop`` is the
+reference's untargeted point-dropping attack (baselines/attack/Saliency/Drop.py, include/ifd_drop.h), whose clouds come back
+smaller; it draws no noise.
 """
 from __future__ import annotations
 
@@ -356,3 +358,62 @@ class CWAdd(_Attack):
                                                   self._scale(B), self.attack_lr, self.init_weight, self.max_weight, self.binary_step,
                                                   self.num_iter)
         return dist.cpu().numpy().astype(np.float64), adv.cpu().numpy(), self._finish(ok, B)
+
+
+class SaliencyDrop(_Attack):
+    """The saliency point-dropping attack (Saliency/Drop.py SaliencyDrop): ceil(num_drop / k) rounds, each taking the gradient of
+    cross_entropy(logits, label) and dropping the k points of highest saliency -(r ** alpha) * sum((x - centre) * grad), centre the
+    per-coordinate median of the shrinking cloud.  ``model`` is a ``runtime.Classifier`` (anything with its ``input_grad``,
+    ``drop_step``, ``drop_attack`` and ``predict``).  ``attack(data [B,K,3], target [B])`` - target the TRUE labels, the attack is
+    untargeted - returns the reference's pair (clouds [B,K - num_drop,3] as a numpy array, success_num), where success_num counts
+    the clouds the victim still classifies correctly.  ``verbose=True`` drives the rounds from the host, one ``input_grad`` and one
+    ``drop_step`` a round, with the reference's two lines every max(num_rounds // 5, 1) rounds (the reference divides by
+    num_rounds // 5 and fails below 5 rounds); ``verbose=False`` is one library call.  Both print the closing line and give the same
+    bits.  No noise is drawn, so there is no seed.
+
+    Where the reference leaves bits open the library decides (include/ifd_drop.h): among equal saliencies the lowest row is dropped
+    first, and the survivors keep their input order - the reference returns them in topk's order, which cannot be reproduced.
+    ``ref_batch``: the batch the reference's loss is a mean over (scale = 1 / ref_batch); default: the batch passed."""
+
+    def __init__(self, model, num_drop, alpha=1, k=5, ref_batch=None, verbose=True):
+        if int(num_drop) < 1 or int(k) < 1:
+            raise ValueError("num_drop and k must be at least 1")
+        if not float(alpha) > 0:
+            raise ValueError("alpha must be positive")
+        self.model, self.num_drop, self.alpha, self.k = model, int(num_drop), float(alpha), int(k)
+        self._common(0, ref_batch, verbose)
+
+    def _loop(self, data, target):
+        """Drop.py:56-95 from the host: the kernels of ifd_drop_attack on the same numbers."""
+        net = self.model
+        dev = net.device
+        B, K_ = int(data.shape[0]), int(data.shape[1])
+        cur = data.to(dev).contiguous().clone()
+        tgt = target.to(dev)
+        n = torch.full((B,), K_, device=dev, dtype=torch.int32)
+        num_rounds = -(-self.num_drop // self.k)
+        every = max(num_rounds // 5, 1)
+        for i in range(num_rounds):
+            k = min(self.k, self.num_drop - i * self.k)
+            grad, aux = net.input_grad(cur, tgt, "cross_entropy", 0., self._scale(B), n_points=n, want_aux=True)
+            if i % every == 0:
+                print('Iteration {}/{}, success {}/{}\nPoint num: {}/{}'.format(i, num_rounds, int((aux["pred"].long() == tgt).sum()), B,
+                                                                              K_ - i * self.k, K_))
+            net.drop_step(grad, cur, n, k, self.alpha)
+        out = cur[:, :K_ - self.num_drop].contiguous()
+        return out, net.predict(out).to(tgt.device) == tgt
+
+    def attack(self, data, target):
+        data, target = self._tensors(data, target)
+        if data.dim() != 3 or int(data.shape[2]) != 3:
+            raise ValueError("data must be [B,K,3]")
+        B, K_ = int(data.shape[0]), int(data.shape[1])
+        if not self.num_drop < K_ <= 2048:
+            raise ValueError("clouds must have more than num_drop and at most 2048 points")
+        if self.verbose:
+            adv, ok = self._loop(data, target)
+        else:
+            adv, ok = self.model.drop_attack(data, target, self.num_drop, self.k, self.alpha, self._scale(B))
+        success_num = int(ok.sum())
+        print('Final success: {}/{}, point num: {}/{}'.format(success_num, B, int(adv.shape[1]), K_))
+        return adv.cpu().numpy(), success_num

@@ -1,4 +1,4 @@
-"""What the attack scripts (fgm_attack, perturb_attack, knn_attack, add_attack) share: the reference's common flags, the two
+"""What the attack scripts (fgm_attack, perturb_attack, knn_attack, add_attack, drop_attack) share: the reference's common flags, the two
 refusals, the data file, the victim, the batch loop and the result file.  Each script adds its own flags between ``parser_head``
 and ``parser_tail``, so ``print(args)`` lists them in the reference's order."""
 from __future__ import annotations
@@ -12,8 +12,8 @@ import numpy as np
 from .inference import DATASETS, default_weight_path, normalize_points_np, str2bool
 
 
-def parser_head(kappa=0.):
-    """--data_root ... --kappa."""
+def parser_head(kappa=0., adv=True):
+    """--data_root ... --kappa; adv=False: up to --k (the untargeted drop script has neither --adv_func nor --kappa)."""
     parser = argparse.ArgumentParser(description='Point Cloud Recognition')
     parser.add_argument('--data_root', type=str, default='data/attack_data.npz')
     parser.add_argument('--model', type=str, default='pointnet', metavar='N', choices=['pointnet', 'pointnet2', 'dgcnn', 'pointconv'])
@@ -23,16 +23,20 @@ def parser_head(kappa=0.):
     parser.add_argument('--num_points', type=int, default=1024)
     parser.add_argument('--emb_dims', type=int, default=1024, help='unused by PointNet')
     parser.add_argument('--k', type=int, default=20, help='unused by PointNet')
-    parser.add_argument('--adv_func', type=str, default='logits', choices=['logits', 'cross_entropy'])
-    parser.add_argument('--kappa', type=float, default=kappa)
+    if adv:
+        parser.add_argument('--adv_func', type=str, default='logits', choices=['logits', 'cross_entropy'])
+        parser.add_argument('--kappa', type=float, default=kappa)
     return parser
 
 
-def parser_tail(parser, verbose=True):
-    """--local_rank ... --out_dir, and --verbose where the script has the two loop forms."""
-    parser.add_argument('--local_rank', default=-1, type=int, help='accepted; only names the output file')
+def parser_tail(parser, verbose=True, local_rank=True, seed=True):
+    """--local_rank ... --out_dir, and --verbose where the script has the two loop forms; local_rank=False, seed=False: without
+    those two (the drop script is single-process and draws no noise)."""
+    if local_rank:
+        parser.add_argument('--local_rank', default=-1, type=int, help='accepted; only names the output file')
     parser.add_argument('--model_path', type=str, default='')
-    parser.add_argument('--seed', type=int, default=1)
+    if seed:
+        parser.add_argument('--seed', type=int, default=1)
     parser.add_argument('--device', type=str, default='cuda:0')
     parser.add_argument('--out_dir', type=str, default='.')
     if verbose:

@@ -11,6 +11,7 @@
 #include "../../include/ifd_cw.h"
 #include "../../include/ifd_knn.h"
 #include "../../include/ifd_add.h"
+#include "../../include/ifd_drop.h"
 
 #include <hip/hip_runtime.h>
 
@@ -1815,6 +1816,13 @@ struct AddLoop {                          // G: points of the larger of the inpu
         c.round_up(256);
     }
 };
+struct DropLoop {
+    float *grad, *logits; int32_t* pred;
+    DropLoop(Carve& c, size_t B, size_t cloud) {
+        grad = c.take<float>(B * cloud); logits = c.take<float>(B * 160); pred = c.take<int32_t>(B * 4);
+        c.round_up(256);
+    }
+};
 // ifd_add_critical_points: the gradient alone
 float* grad_loop(Carve& c, size_t B, size_t cloud) {
     float* grad = c.take<float>(B * cloud);
@@ -2227,6 +2235,73 @@ int ifd_add_attack(ifd_ctx* ctx, const ifd_add_params* params, const float* pc_i
     e = launch_add_finish(S, last, n_cat, B, out_stride, num_add, pc_out, success, bounds, s);
     if (e != hipSuccess) return fail(ctx, IFD_ERR_HIP, "ifd_add_attack: finish", e);
     return IFD_OK;
+}
+
+}  // extern "C"
+
+// ---- the saliency Drop attack (include/ifd_drop.h) ---------------------------------------------------------------------
+static_assert(IFD_DROP_MAX_POINTS == DROP_MAX_POINTS, "ifd_drop.h and ifd_internal.h");
+
+extern "C" {
+
+int ifd_drop_abi_version(void) { return IFD_DROP_ABI_VERSION; }
+
+int ifd_drop_step(ifd_ctx* ctx, const float* grad, float* pc, int32_t* n_points, int32_t* index, int B, int stride, int k, float alpha,
+                  const ifd_drop_out* out, void* stream) {
+    if (!ctx) return IFD_ERR_ARG;
+    if (int rc = atk_context_ok(ctx, "ifd_drop_step")) return rc;
+    if (!grad || !pc || !n_points || B < 1) return fail(ctx, IFD_ERR_ARG, "ifd_drop_step: bad argument (grad, pc, n_points; B >= 1)");
+    if (stride < 1 || stride > IFD_CLS_MAX_POINTS) return fail(ctx, IFD_ERR_ARG, "ifd_drop_step: stride outside [1, 10000]");
+    if (k < 1) return fail(ctx, IFD_ERR_ARG, "ifd_drop_step: k < 1");
+    if (!(alpha > 0.f) || !std::isfinite(alpha)) return fail(ctx, IFD_ERR_ARG, "ifd_drop_step: alpha must be a finite number above 0");
+    IFD_ON_CTX_DEVICE(ctx);
+    const DropOut D = out ? DropOut{out->saliency, out->center, out->dropped} : DropOut{};
+    hipError_t e = launch_drop_step(grad, pc, n_points, index, B, stride, k, alpha, D, static_cast<hipStream_t>(stream));
+    if (e != hipSuccess) return fail(ctx, IFD_ERR_HIP, "ifd_drop_step launch", e);
+    return IFD_OK;
+}
+
+int ifd_drop_attack(ifd_ctx* ctx, const ifd_drop_params* params, const float* pc_in, const int32_t* n_points, const int32_t* label,
+                    int B, int stride, float* pc_out, int32_t* n_out, int32_t* kept, int32_t* correct, void* stream) {
+    if (!ctx) return IFD_ERR_ARG;
+    if (int rc = atk_context_ok(ctx, "ifd_drop_attack")) return rc;
+    if (!params || params->struct_size != (int32_t)sizeof(ifd_drop_params))
+        return fail(ctx, IFD_ERR_ARG, "ifd_drop_attack: params missing or of another struct_size");
+    const int num_drop = params->num_drop;
+    if (num_drop < 1) return fail(ctx, IFD_ERR_ARG, "ifd_drop_attack: num_drop < 1");
+    if (params->k < 1) return fail(ctx, IFD_ERR_ARG, "ifd_drop_attack: k < 1");
+    if (!(params->alpha > 0.f) || !std::isfinite(params->alpha))
+        return fail(ctx, IFD_ERR_ARG, "ifd_drop_attack: alpha must be a finite number above 0");
+    if (B < 1) return fail(ctx, IFD_ERR_ARG, "ifd_drop_attack: B >= 1 is needed");
+    if (stride < 1 || stride > IFD_CLS_MAX_POINTS) return fail(ctx, IFD_ERR_ARG, "ifd_drop_attack: stride outside [1, 10000]");
+    if (!pc_in || !label || !pc_out || !n_out || !correct)
+        return fail(ctx, IFD_ERR_ARG, "ifd_drop_attack: missing pointer (pc_in, label, pc_out, n_out, correct)");
+    const int hi = std::min(stride, IFD_DROP_MAX_POINTS);
+    if (!n_points && (stride <= num_drop || stride > IFD_DROP_MAX_POINTS))
+        return fail(ctx, IFD_ERR_ARG, "ifd_drop_attack: without n_points, stride outside [num_drop + 1, 2048]");
+    if (num_drop >= hi) return fail(ctx, IFD_ERR_ARG, "ifd_drop_attack: num_drop >= min(stride, 2048), no cloud can lose that many rows");
+    const size_t cloud = (size_t)stride * 12;
+    if (clouds_overlap(pc_in, (size_t)B * cloud, pc_out, (size_t)B * cloud)) return fail(ctx, IFD_ERR_ARG, "ifd_drop_attack: pc_out overlaps pc_in");
+    IFD_ON_CTX_DEVICE(ctx);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const size_t state = carved_bytes([&](Carve& c) { DropLoop(c, (size_t)B, cloud); });
+    hipError_t e = ctx->ws.grow(atk_loop_ws_bytes(B, stride, state, true));
+    if (e != hipSuccess) return fail(ctx, IFD_ERR_NOMEM, "ifd_drop_attack: workspace", e);
+    if (int rc = atk_check(ctx, "ifd_drop_attack", n_points, label, B, num_drop + 1, hi, numeric_range(num_drop + 1, hi), s)) return rc;
+    Carve c(ctx->ws.get());
+    const DropLoop L(c, (size_t)B, cloud);
+    e = hipMemcpyAsync(pc_out, pc_in, (size_t)B * cloud, hipMemcpyDeviceToDevice, s);
+    if (e == hipSuccess) e = launch_drop_begin(n_points, B, stride, n_out, kept, s);
+    if (e != hipSuccess) return fail(ctx, IFD_ERR_HIP, "ifd_drop_attack: start", e);
+    // the counts shrink on the device: every launch's grid depends on B and stride only, so nothing here waits for a round
+    const int k = std::min(params->k, num_drop);
+    for (int done = 0; done < num_drop; done += k) {
+        if (int rc = input_grad_impl(ctx, state, pc_out, n_out, B, stride, label, IFD_ATK_LOSS_CE, 0.f, params->scale, L.grad, nullptr, s))
+            return rc;
+        e = launch_drop_step(L.grad, pc_out, n_out, kept, B, stride, std::min(k, num_drop - done), params->alpha, DropOut{}, s);
+        if (e != hipSuccess) return fail(ctx, IFD_ERR_HIP, "ifd_drop_attack: step", e);
+    }
+    return atk_final_success(ctx, "ifd_drop_attack", pc_out, n_out, B, stride, L.logits, L.pred, label, correct, state, s);
 }
 
 }  // extern "C"

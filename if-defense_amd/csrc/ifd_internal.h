@@ -357,4 +357,17 @@ hipError_t launch_add_start(const float* cri, const float* noise, const int32_t*
 hipError_t launch_add_finish(const CwState& S, const float* last_input, const int32_t* n_cat, int B, int out_stride, int num_add,
                              float* pc_out, int32_t* success, double* bounds, hipStream_t s);
 
+// ---- the saliency Drop attack (pointnet_drop.hip, include/ifd_drop.h) ----
+constexpr int DROP_MAX_POINTS = 2048;           // IFD_DROP_MAX_POINTS: a cloud, its saliencies, ranks and indices in a workgroup's LDS
+struct DropOut {                                // ifd_drop_out, member for member; every pointer may be null
+    float* saliency;                            // [B][stride]
+    float* center;                              // [B][3]
+    int32_t* dropped;                           // [B][k]
+};
+// one round, a workgroup a cloud, in place; 1 <= stride, k >= 1 and alpha > 0 are the caller's to check
+hipError_t launch_drop_step(const float* grad, float* pc, int32_t* n_points, int32_t* index, int B, int stride, int k, float alpha,
+                            const DropOut& D, hipStream_t s);
+// n_out[b] = n_points[b] (stride where n_points is null); kept[b][i] = i below that count, -1 beyond (kept may be null)
+hipError_t launch_drop_begin(const int32_t* n_points, int B, int stride, int32_t* n_out, int32_t* kept, hipStream_t s);
+
 }  // namespace ifd

@@ -247,6 +247,19 @@ __host__ __device__ constexpr FillLdsAt fill_lds_at(int K) {
 }
 static_assert(srs_lds_at(PREP_MAXK, PREP_MAXK).BYTES == 80000 && fill_lds_at(PREP_MAXK).BYTES == 120000, "LDS of the DUP-Net sampling kernels");
 
+// ---- pointnet_drop.hip: drop_step_kernel, one cloud of up to DROP_MAX_POINTS points a workgroup of DROP_THREADS threads ----------
+constexpr int DROP_THREADS = 256;
+struct DropLds {
+    static constexpr size_t X = 0;                                         // float [DROP_MAX_POINTS][3] the cloud
+    static constexpr size_t S = X + (size_t)DROP_MAX_POINTS * 12;          // float [DROP_MAX_POINTS] saliencies
+    static constexpr size_t RANK = S + (size_t)DROP_MAX_POINTS * 4;        // int [DROP_MAX_POINTS] rank in the drop order
+    static constexpr size_t INDEX = RANK + (size_t)DROP_MAX_POINTS * 4;    // int [DROP_MAX_POINTS] the caller's index rows
+    static constexpr size_t SCAN = INDEX + (size_t)DROP_MAX_POINTS * 4;    // int [DROP_THREADS] prefix count of the survivors
+    static constexpr size_t CENTER = SCAN + (size_t)DROP_THREADS * 4;      // float [4]
+    static constexpr size_t BYTES = CENTER + 16;
+};
+static_assert(DropLds::BYTES == 50192 && DropLds::BYTES <= 65536 && DROP_MAX_POINTS % DROP_THREADS == 0, "LDS of drop_step_kernel");
+
 // ---- block_sum / block_max / block_sum_d write one value per wave into their scratch ------------------------------------------
 static_assert((RepLds::BYTES - RepLds::SCRATCH) / 4 >= OPT_THREADS / 64 && (NrmLds::BYTES - NrmLds::SCRATCH) / 4 >= OPT_THREADS / 64,
               "8 waves: repulsion_kernel, normalize_kernel");

@@ -1124,3 +1124,55 @@ class Classifier:
         if want_bounds:
             return out, best, success.bool(), self._bounds(bounds)
         return out, best, success.bool()
+
+    # ---- include/ifd_drop.h: the saliency Drop attack (models without feature_transform) ----
+    def drop_step(self, grad, pc, n_points, k, alpha=1., index=None, want=()):
+        """One round of the Drop attack behind ``input_grad`` (ifd_drop_step), IN PLACE on ``pc`` [B,N,3] float32, ``n_points`` [B]
+        int32 and ``index`` [B,N] int32 (or None), contiguous device tensors: every cloud with k < n <= 2048 loses its k rows of
+        highest saliency (the lowest row first among equal saliencies), the survivors move up in their order, the rows it lost
+        become zeros (-1 in ``index``) and its count n - k; any other cloud is left untouched.  grad [B,N,3] as ``input_grad``
+        returned it.  Returns the diagnostics named in ``want``: "saliency" [B,N] (the first n rows, before the drop), "center" [B,3],
+        "dropped" [B,k] int32 in drop order (NaN / -1 where the library writes nothing)."""
+        if not torch.is_tensor(pc) or pc.dim() != 3:
+            raise IfdError("pc must be a contiguous float32 [B,N,3] device tensor")
+        B, stride, k = int(pc.shape[0]), int(pc.shape[1]), int(k)
+        if grad is None:
+            raise IfdError("grad is missing")
+        ptrs = [self._cw_cloud(x, B, stride, n) for x, n in ((grad, "grad"), (pc, "pc"))]
+        for t, shape, name in ((n_points, (B,), "n_points"), (index, (B, stride), "index")):
+            if t is None and name == "index":
+                continue
+            if not (torch.is_tensor(t) and t.is_cuda and t.dtype == torch.int32 and t.is_contiguous() and tuple(t.shape) == shape):
+                raise IfdError("%s must be a contiguous int32 %s device tensor (updated in place)" % (name, list(shape)))
+        shapes = {"saliency": ((B, stride), torch.float32), "center": ((B, 3), torch.float32), "dropped": ((B, max(k, 1)), torch.int32)}
+        out = self._diag(want, shapes, "saliency | center | dropped")
+        ptr = lambda x: None if x is None else x.data_ptr()        # noqa: E731
+        diag = _lib.IfdDropOut(*[ptr(out.get(n)) for n in ("saliency", "center", "dropped")])
+        with torch.cuda.device(self.device):
+            self._check(self.lib.ifd_drop_step(self.ctx, ptrs[0], ptrs[1], n_points.data_ptr(), ptr(index), B, stride, k, float(alpha),
+                                               C.byref(diag) if out else None, self._stream()))
+        return out
+
+    def drop_attack(self, pc, label, num_drop, k=5, alpha=1., scale=1., n_points=None, want_kept: bool = False):
+        """The whole Drop attack on the device (ifd_drop_attack): ceil(num_drop / k) rounds of the gradient of scale *
+        cross_entropy(logits, label) and ``drop_step``, then a forward.  -> (clouds [B,N - num_drop,3], correct [B] bool: the
+        clouds the victim STILL classifies as ``label``) and with want_kept also kept [B,N - num_drop] int32, the surviving rows'
+        indices into ``pc``.  With n_points, cloud b is the first n_points[b] - num_drop rows of its output (zeros behind them)."""
+        pc, n_points = self._batch(pc, n_points)
+        B, stride, num_drop = int(pc.shape[0]), int(pc.shape[1]), int(num_drop)
+        if B < 1 or stride < 1:
+            raise IfdError("empty batch")
+        label = self._target(label, B)
+        out = torch.empty_like(pc)
+        n_out = torch.empty(B, device=self.device, dtype=torch.int32)
+        correct = torch.empty(B, device=self.device, dtype=torch.int32)
+        kept = torch.empty(B, stride, device=self.device, dtype=torch.int32) if want_kept else None
+        P = _lib.IfdDropParams(C.sizeof(_lib.IfdDropParams), num_drop, int(k), float(alpha), float(scale))
+        with torch.cuda.device(self.device):
+            self._check(self.lib.ifd_drop_attack(self.ctx, C.byref(P), pc.data_ptr(), None if n_points is None else n_points.data_ptr(),
+                                                 label.data_ptr(), B, stride, out.data_ptr(), n_out.data_ptr(),
+                                                 None if kept is None else kept.data_ptr(), correct.data_ptr(), self._stream()))
+        m = max(stride - num_drop, 0)
+        if want_kept:
+            return out[:, :m].contiguous(), correct.bool(), kept[:, :m].contiguous()
+        return out[:, :m].contiguous(), correct.bool()
