@@ -252,6 +252,32 @@ DROP_SIGNATURES = {
                                   C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
 }
 
+# include/ifd_cluster.h (the CW cluster-adding attack on the PointNet victim), versioned on its own
+CLUSTER_ABI_VERSION = 1
+CLUSTER_DBSCAN_MAX_POINTS = 256
+
+
+class IfdClusterDiag(C.Structure):
+    _fields_ = [("dist_grad", C.c_void_p), ("nn_ori", C.c_void_p), ("far_i", C.c_void_p), ("far_j", C.c_void_p), ("far_val", C.c_void_p)]
+
+
+class IfdClusterParams(C.Structure):
+    _fields_ = [("struct_size", C.c_int32), ("loss_kind", C.c_int32), ("binary_step", C.c_int32), ("num_iter", C.c_int32),
+                ("num_add", C.c_int32), ("cl_num_p", C.c_int32), ("kappa", C.c_float), ("scale", C.c_float), ("attack_lr", C.c_float),
+                ("init_weight", C.c_float), ("max_weight", C.c_float)]
+
+
+CLUSTER_SIGNATURES = {
+    "ifd_cluster_abi_version": (C.c_int, []),
+    "ifd_cluster_dbscan": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_int, C.c_void_p, C.c_void_p,
+                                     C.c_void_p]),
+    "ifd_cluster_step": (C.c_int, [C.c_void_p, C.POINTER(IfdCwState), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                   C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(IfdClusterDiag), C.c_int, C.c_float, C.c_float, C.c_int,
+                                   C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    "ifd_cluster_attack": (C.c_int, [C.c_void_p, C.POINTER(IfdClusterParams), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                     C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+}
+
 _lib = None
 
 
@@ -268,7 +294,7 @@ def load() -> C.CDLL:
     lib = C.CDLL(LIB_PATH, mode=C.RTLD_GLOBAL)
     for name, (res, args) in list(SIGNATURES.items()) + list(DUP_SIGNATURES.items()) + list(CLS_SIGNATURES.items()) + \
             list(ATK_SIGNATURES.items()) + list(CW_SIGNATURES.items()) + list(KNN_SIGNATURES.items()) + list(ADD_SIGNATURES.items()) + \
-            list(DROP_SIGNATURES.items()):
+            list(DROP_SIGNATURES.items()) + list(CLUSTER_SIGNATURES.items()):
         fn = getattr(lib, name)          # AttributeError if the library lacks a declared symbol
         fn.restype, fn.argtypes = res, args
     if lib.ifd_abi_version() != ABI_VERSION:
@@ -287,5 +313,7 @@ def load() -> C.CDLL:
         raise ImportError("libifd.so ADD ABI %d != binding ADD ABI %d; rebuild" % (lib.ifd_add_abi_version(), ADD_ABI_VERSION))
     if lib.ifd_drop_abi_version() != DROP_ABI_VERSION:
         raise ImportError("libifd.so DROP ABI %d != binding DROP ABI %d; rebuild" % (lib.ifd_drop_abi_version(), DROP_ABI_VERSION))
+    if lib.ifd_cluster_abi_version() != CLUSTER_ABI_VERSION:
+        raise ImportError("libifd.so CLUSTER ABI %d != binding CLUSTER ABI %d; rebuild" % (lib.ifd_cluster_abi_version(), CLUSTER_ABI_VERSION))
     _lib = lib
     return lib

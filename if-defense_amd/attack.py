@@ -21,7 +21,8 @@ same two loop forms; it is not one of ``ATTACKS``, which names the FGM family fo
 kNN attack (baselines/attack/CW/kNN.py, include/ifd_knn.h), likewise, and ``CWAdd`` its point-adding attack
 (baselines/attack/CW/Add.py, include/ifd_add.h), whose clouds come back larger than they went in.  ``SaliencyDrop`` is the
 reference's untargeted point-dropping attack (baselines/attack/Saliency/Drop.py, include/ifd_drop.h), whose clouds come back
-smaller; it draws no noise.
+smaller; it draws no noise.  ``CWAddClusters`` is the reference's cluster-adding attack (baselines/attack/CW/Add_Cluster.py,
+include/ifd_cluster.h): ``num_add`` clusters of ``cl_num_p`` points, started on DBSCAN clusters of the 128 critical points.
 """
 from __future__ import annotations
 
@@ -357,6 +358,134 @@ class CWAdd(_Attack):
             adv, dist, ok = self.model.add_attack(self.dist_func, data, target, self.num_add, noise, self.adv_func, self.kappa,
                                                   self._scale(B), self.attack_lr, self.init_weight, self.max_weight, self.binary_step,
                                                   self.num_iter)
+        return dist.cpu().numpy().astype(np.float64), adv.cpu().numpy(), self._finish(ok, B)
+
+
+def init_clusters(points, labels, num_add, cl_num_p, rng):
+    """Add_Cluster.py:103-127 on one cloud, the reference's numpy calls in its order on ``rng`` (a np.random.RandomState; the
+    reference uses the global one): points [n,3] the critical points, labels [n] their DBSCAN labels -> [num_add,cl_num_p,3].  The
+    ``num_add`` largest clusters in ascending order of their counts (a stable argsort), from each ``cl_num_p`` rows drawn with
+    replacement unless it has more; then, while clusters are missing, a random non-outlier point and its ``cl_num_p`` nearest
+    non-outlier points.  Where the reference raises: with no non-outlier point at all, every point counts as one for the fallback;
+    a fallback with fewer than ``cl_num_p`` candidates repeats their sorted list cyclically."""
+    points, result = np.asarray(points), np.asarray(labels)
+    filter_idx = result > -0.5
+    result = result[filter_idx]
+    if filter_idx.any():
+        points = points[filter_idx]
+    out = []
+    labels, counts = np.unique(result, return_counts=True)
+    for one_label in labels[np.argsort(counts, kind="stable")[-num_add:]]:
+        cluster_points = points[result == one_label]
+        replace = not (len(cluster_points) > cl_num_p)
+        out.append(cluster_points[rng.choice(len(cluster_points), cl_num_p, replace=replace)].copy())
+    while len(out) < num_add:
+        rand_point = points[rng.choice(len(points), 1)[0]]
+        dist_matrix = np.sum((points - rand_point[None, :]) ** 2, axis=1)
+        out.append(points[np.resize(np.argsort(dist_matrix)[:cl_num_p], cl_num_p)].copy())
+    return np.array(out)
+
+
+class CWAddClusters(_Attack):
+    """CW attack by adding clusters (Add_Cluster.py CWAddClusters with FarChamferDist(num_add, 'adv2ori', 0.1)): ``num_add`` clusters
+    of ``cl_num_p`` points are optimised by ``binary_step`` search steps on the weight of the distance - the farthest pair inside
+    every cluster plus 0.1 x Chamfer - ``num_iter`` Adam iterations each, while the victim sees the original cloud with the clusters
+    behind it.  ``model`` is a ``runtime.Classifier`` (anything with its ``input_grad``, ``add_critical_points``, ``cluster_dbscan``,
+    ``cw_state``, ``cluster_step``, ``cw_adjust`` and ``cluster_attack``), ``adv_func`` the loss by name ("logits":
+    LogitsAdvLoss(kappa), or "cross_entropy"), ``dist_func`` "far_chamfer" (the only one built).  ``attack(data [B,K,3], target
+    [B])``, 128 <= K <= 2048, returns the reference's triple (o_bestdist [B], clouds [B,K+num_add*cl_num_p,3]: the originals, then
+    the best added points, or the last forwarded ones where the search never succeeded; success_num) as numpy arrays.
+    ``verbose=True`` drives the loop from the host, one ``input_grad`` and one ``cluster_step`` an iteration, with the reference's
+    progress lines every num_iter // 5 iterations (the two losses are the batch means of the previous iteration, zero at iteration 0)
+    - its wall-clock lines ("total: ...") are left out; ``verbose=False`` is one library call and prints the last line only.  Both
+    give the same bits.
+
+    The start (``_init_centers``): the 128 critical points of ``add_critical_points`` towards the TARGET labels, as the reference
+    takes them, clustered on the device by ``cluster_dbscan(eps=0.2, min_samples=3)`` - include/ifd_cluster.h's definition, which is
+    sklearn's result wherever no pair lies within float32 rounding of eps - the labels copied back once per batch, then
+    ``init_clusters``: the reference's numpy calls in its order on ONE np.random.RandomState(seed) kept across ``attack`` calls, so
+    that, given equal labels, the clusters are the reference's under np.random.seed(seed), number for number.  Two cases in which
+    the reference raises are defined here: a cloud whose 128 critical points are all outliers uses all 128 as the candidate points
+    of the fallback; a fallback with fewer than ``cl_num_p`` candidate points repeats their sorted list cyclically.
+
+    Every search step starts from clusters + randn * 1e-7, drawn here once per search step from a seeded HOST torch.Generator:
+    agreement with a reference run in distribution only.  ``ref_batch``: the batch the reference's losses are a mean over (scale =
+    1 / ref_batch); the default is the batch passed to ``attack``."""
+
+    NUM_CRI, EPS, MIN_SAMPLES = 128, 0.2, 3
+
+    def __init__(self, model, adv_func="logits", dist_func="far_chamfer", attack_lr=1e-2, init_weight=5., max_weight=30., binary_step=5,
+                 num_iter=500, num_add=3, cl_num_p=32, kappa=0., seed=1, ref_batch=None, verbose=True):
+        if str(dist_func).lower() != "far_chamfer":
+            raise ValueError("only the far_chamfer distance of the reference's script is built")
+        if int(binary_step) < 1 or int(num_iter) < 1:
+            raise ValueError("binary_step and num_iter must be at least 1")
+        if int(num_add) < 1 or int(cl_num_p) < 1 or not 1 <= int(num_add) * int(cl_num_p) <= 1024:
+            raise ValueError("num_add and cl_num_p must be at least 1 and num_add * cl_num_p in [1, 1024]")
+        self.model, self.adv_func, self.kappa = model, adv_func, float(kappa)
+        self.attack_lr, self.init_weight, self.max_weight = float(attack_lr), float(init_weight), float(max_weight)
+        self.binary_step, self.num_iter, self.num_add, self.cl_num_p = int(binary_step), int(num_iter), int(num_add), int(cl_num_p)
+        self.rng = np.random.RandomState(int(seed))
+        self._common(seed, ref_batch, verbose)
+
+    def noise(self, data: torch.Tensor) -> torch.Tensor:
+        """[binary_step,B,num_add*cl_num_p,3]: the start noise, one draw per search step."""
+        shape = (int(data.shape[0]), self.num_add * self.cl_num_p, 3)
+        return torch.stack([torch.randn(shape, generator=self.generator) * 1e-7 for _ in range(self.binary_step)])
+
+    def _init_centers(self, data, target):
+        """Add_Cluster.py:83-130 -> clusters [B,num_add*cl_num_p,3] float32 (a CPU tensor)."""
+        net = self.model
+        B = int(data.shape[0])
+        cri = net.add_critical_points(data, target, self.NUM_CRI, self._scale(B))
+        labels = net.cluster_dbscan(cri, self.EPS, self.MIN_SAMPLES).cpu().numpy()
+        cri = cri.cpu().numpy()
+        out = np.stack([init_clusters(cri[b], labels[b], self.num_add, self.cl_num_p, self.rng) for b in range(B)])
+        return torch.from_numpy(out.reshape(B, self.num_add * self.cl_num_p, 3).astype(np.float32))
+
+    def _loop(self, data, target, clusters, noise):
+        """Add_Cluster.py:165-278 from the host: the kernels of ifd_cluster_attack on the same numbers."""
+        net = self.model
+        dev = net.device
+        B, K, A = int(data.shape[0]), int(data.shape[1]), self.num_add * self.cl_num_p
+        ori = data.to(dev).contiguous()
+        tgt = target.to(dev)
+        start = clusters.to(dev)
+        state = net.cw_state(B, A, self.init_weight, self.max_weight)
+        cat = torch.cat([ori, start], dim=1).contiguous()
+        last = torch.empty_like(start)
+        every = max(self.num_iter // 5, 1)
+        for step in range(self.binary_step):
+            cat[:, K:] = start + noise[step].to(dev)
+            info = None
+            for it in range(self.num_iter):
+                grad, aux = net.input_grad(cat, tgt, self.adv_func, self.kappa, self._scale(B), want_aux=True)
+                if it % every == 0:
+                    self._progress(self.STEP_LINES, step, it, aux["pred"], tgt, info, 1)
+                final = step == self.binary_step - 1 and it == self.num_iter - 1
+                info = net.cluster_step(state, grad, aux["pred"], tgt, cat, self.num_add, self.cl_num_p, it + 1, self.attack_lr,
+                                        self._scale(B), loss=aux["loss"], last_input=last if final else None,
+                                        want_info=it % every == every - 1).get("info")
+            net.cw_adjust(state, tgt)
+        ok = state["lower"] > 0
+        added = torch.where(ok[:, None, None], state["o_bestattack"], last)
+        return torch.cat([ori, added], dim=1), state["o_bestdist"], ok
+
+    def attack(self, data, target):
+        data, target = self._tensors(data, target)
+        if data.dim() != 3 or int(data.shape[2]) != 3:
+            raise ValueError("data must be [B,K,3]")
+        if not self.NUM_CRI <= int(data.shape[1]) <= 2048:
+            raise ValueError("clouds must have between 128 and 2048 points")
+        B = int(data.shape[0])
+        clusters = self._init_centers(data, target)
+        noise = self.noise(data)
+        if self.verbose:
+            adv, dist, ok = self._loop(data, target, clusters, noise)
+        else:
+            adv, dist, ok = self.model.cluster_attack(data, target, clusters, self.num_add, self.cl_num_p, noise, self.adv_func,
+                                                      self.kappa, self._scale(B), self.attack_lr, self.init_weight, self.max_weight,
+                                                      self.binary_step, self.num_iter)
         return dist.cpu().numpy().astype(np.float64), adv.cpu().numpy(), self._finish(ok, B)
 
 

@@ -12,6 +12,7 @@
 #include "../../include/ifd_knn.h"
 #include "../../include/ifd_add.h"
 #include "../../include/ifd_drop.h"
+#include "../../include/ifd_cluster.h"
 
 #include <hip/hip_runtime.h>
 
@@ -1816,6 +1817,17 @@ struct AddLoop {                          // G: points of the larger of the inpu
         c.round_up(256);
     }
 };
+struct ClusterLoop {                      // AddLoop without the critical points: the start clusters are the caller's
+    CwFront f; int32_t *n_cat, *n_ori; float *grad, *last;
+    ClusterLoop(Carve& c, size_t B, size_t G, size_t A) : f(c, B) {
+        const size_t added = B * A * 12;
+        n_cat = c.take<int32_t>(B * 4); n_ori = c.take<int32_t>(B * 4);
+        grad = c.take<float>(B * G * 12);
+        f.S.m = c.take<float>(added); f.S.v = c.take<float>(added); f.S.o_bestattack = c.take<float>(added);   // side by side
+        last = c.take<float>(added);
+        c.round_up(256);
+    }
+};
 struct DropLoop {
     float *grad, *logits; int32_t* pred;
     DropLoop(Carve& c, size_t B, size_t cloud) {
@@ -2302,6 +2314,131 @@ int ifd_drop_attack(ifd_ctx* ctx, const ifd_drop_params* params, const float* pc
         if (e != hipSuccess) return fail(ctx, IFD_ERR_HIP, "ifd_drop_attack: step", e);
     }
     return atk_final_success(ctx, "ifd_drop_attack", pc_out, n_out, B, stride, L.logits, L.pred, label, correct, state, s);
+}
+
+}  // extern "C"
+
+// ---- the CW cluster-adding attack (include/ifd_cluster.h) --------------------------------------------------------------
+static_assert(IFD_CLUSTER_DBSCAN_MAX_POINTS == ifd::CLUSTER_DBSCAN_MAX_POINTS, "the header's limit is the kernel's");
+
+namespace {
+
+// A = num_add * cl_num_p, or 0 where the pair is outside the header's limits
+int cluster_rows(int num_add, int cl_num_p) {
+    if (num_add < 1 || cl_num_p < 1 || num_add > IFD_ADD_MAX_ADD || cl_num_p > IFD_ADD_MAX_ADD) return 0;
+    const int A = num_add * cl_num_p;
+    return A <= IFD_ADD_MAX_ADD ? A : 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+int ifd_cluster_abi_version(void) { return IFD_CLUSTER_ABI_VERSION; }
+
+int ifd_cluster_dbscan(ifd_ctx* ctx, const float* pts, const int32_t* n_pts, int B, int stride, float eps, int min_samples,
+                       int32_t* labels, int32_t* n_clusters, void* stream) {
+    if (!ctx) return IFD_ERR_ARG;
+    if (int rc = atk_context_ok(ctx, "ifd_cluster_dbscan")) return rc;
+    if (!pts || !labels || B < 1) return fail(ctx, IFD_ERR_ARG, "ifd_cluster_dbscan: bad argument (pts, labels; B >= 1)");
+    if (stride < 1 || stride > IFD_CLS_MAX_POINTS) return fail(ctx, IFD_ERR_ARG, "ifd_cluster_dbscan: stride outside [1, 10000]");
+    if (!(eps > 0.f) || !std::isfinite(eps)) return fail(ctx, IFD_ERR_ARG, "ifd_cluster_dbscan: eps must be a finite number above 0");
+    if (min_samples < 1) return fail(ctx, IFD_ERR_ARG, "ifd_cluster_dbscan: min_samples < 1");
+    if (!n_pts && stride > IFD_CLUSTER_DBSCAN_MAX_POINTS)
+        return fail(ctx, IFD_ERR_ARG, "ifd_cluster_dbscan: without n_pts, stride outside [1, 256]");
+    IFD_ON_CTX_DEVICE(ctx);
+    hipError_t e = launch_cluster_dbscan(pts, n_pts, B, stride, eps, min_samples, labels, n_clusters, static_cast<hipStream_t>(stream));
+    if (e != hipSuccess) return fail(ctx, IFD_ERR_HIP, "ifd_cluster_dbscan launch", e);
+    return IFD_OK;
+}
+
+int ifd_cluster_step(ifd_ctx* ctx, const ifd_cw_state* state, const float* grad, const int32_t* pred, const float* loss,
+                     const int32_t* target, float* cat, const int32_t* n_ori, float* last_input, float* info,
+                     const ifd_cluster_diag* diag, int t, float lr, float scale, int B, int cat_stride, int num_add, int cl_num_p,
+                     void* stream) {
+    if (!ctx) return IFD_ERR_ARG;
+    if (int rc = atk_context_ok(ctx, "ifd_cluster_step")) return rc;
+    if (!cw_state_ok(state, false))
+        return fail(ctx, IFD_ERR_ARG, "ifd_cluster_step: state missing (m, v, bestdist, bestscore, o_bestdist, o_bestscore, o_bestattack, weight)");
+    if (!grad || !pred || !target || !cat || t < 1 || B < 1)
+        return fail(ctx, IFD_ERR_ARG, "ifd_cluster_step: bad argument (grad, pred, target, cat; t >= 1, B >= 1)");
+    const int A = cluster_rows(num_add, cl_num_p);
+    if (A < 1) return fail(ctx, IFD_ERR_ARG, "ifd_cluster_step: num_add < 1, cl_num_p < 1 or num_add * cl_num_p outside [1, 1024]");
+    if (cat_stride > IFD_CLS_MAX_POINTS || cat_stride < A + 1)
+        return fail(ctx, IFD_ERR_ARG, "ifd_cluster_step: cat_stride outside [num_add * cl_num_p + 1, 10000]");
+    if (!n_ori && cat_stride - A > IFD_ADD_MAX_ORI)
+        return fail(ctx, IFD_ERR_ARG, "ifd_cluster_step: without n_ori, cat_stride - num_add * cl_num_p > 2048 original rows");
+    IFD_ON_CTX_DEVICE(ctx);
+    const ClusterDiag D = diag ? ClusterDiag{diag->dist_grad, diag->nn_ori, diag->far_i, diag->far_j, diag->far_val} : ClusterDiag{};
+    hipError_t e = launch_cluster_step(cw_state(state), grad, pred, loss, target, cat, n_ori, last_input, info, D, t, lr, scale, B,
+                                       cat_stride, num_add, cl_num_p, static_cast<hipStream_t>(stream));
+    if (e != hipSuccess) return fail(ctx, IFD_ERR_HIP, "ifd_cluster_step launch", e);
+    return IFD_OK;
+}
+
+int ifd_cluster_attack(ifd_ctx* ctx, const ifd_cluster_params* params, const float* pc_in, const int32_t* n_points,
+                       const int32_t* target, const float* clusters, const float* noise, int B, int stride, int out_stride,
+                       float* pc_out, float* best_dist, int32_t* success, double* bounds, void* stream) {
+    if (!ctx) return IFD_ERR_ARG;
+    if (int rc = atk_context_ok(ctx, "ifd_cluster_attack")) return rc;
+    if (!params || params->struct_size != (int32_t)sizeof(ifd_cluster_params))
+        return fail(ctx, IFD_ERR_ARG, "ifd_cluster_attack: params missing or of another struct_size");
+    if (!atk_loss_ok(params->loss_kind)) return fail(ctx, IFD_ERR_ARG, "ifd_cluster_attack: unknown loss_kind");
+    if (params->binary_step < 1) return fail(ctx, IFD_ERR_ARG, "ifd_cluster_attack: binary_step < 1");
+    if (params->num_iter < 1) return fail(ctx, IFD_ERR_ARG, "ifd_cluster_attack: num_iter < 1");
+    const int num_add = params->num_add, cl_num_p = params->cl_num_p, A = cluster_rows(num_add, cl_num_p);
+    if (A < 1) return fail(ctx, IFD_ERR_ARG, "ifd_cluster_attack: num_add < 1, cl_num_p < 1 or num_add * cl_num_p outside [1, 1024]");
+    if (B < 1) return fail(ctx, IFD_ERR_ARG, "ifd_cluster_attack: B >= 1 is needed");
+    if (stride < 1 || stride > IFD_CLS_MAX_POINTS) return fail(ctx, IFD_ERR_ARG, "ifd_cluster_attack: stride outside [1, 10000]");
+    if (out_stride < 1 || out_stride > IFD_CLS_MAX_POINTS) return fail(ctx, IFD_ERR_ARG, "ifd_cluster_attack: out_stride outside [1, 10000]");
+    if (!pc_in || !target || !clusters || !pc_out || !best_dist || !success)
+        return fail(ctx, IFD_ERR_ARG, "ifd_cluster_attack: missing pointer (pc_in, target, clusters, pc_out, best_dist, success)");
+    const int hi = std::min(std::min(stride, IFD_ADD_MAX_ORI), out_stride - A);
+    if (!n_points && stride > hi)
+        return fail(ctx, IFD_ERR_ARG, "ifd_cluster_attack: without n_points, stride outside [1, min(2048, out_stride - num_add * cl_num_p)]");
+    if (clouds_overlap(pc_in, (size_t)B * stride * 12, pc_out, (size_t)B * out_stride * 12))
+        return fail(ctx, IFD_ERR_ARG, "ifd_cluster_attack: pc_out overlaps pc_in");
+    IFD_ON_CTX_DEVICE(ctx);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const int G = std::max(stride, out_stride);
+    const size_t added = (size_t)B * A * 12;
+    const size_t state = carved_bytes([&](Carve& c) { ClusterLoop(c, (size_t)B, (size_t)G, (size_t)A); });
+    hipError_t e = ctx->ws.grow(atk_loop_ws_bytes(B, G, state, false));
+    if (e != hipSuccess) return fail(ctx, IFD_ERR_NOMEM, "ifd_cluster_attack: workspace", e);
+    if (int rc = atk_check(ctx, "ifd_cluster_attack", n_points, target, B, 1, hi, numeric_range(1, hi), s)) return rc;
+    Carve c(ctx->ws.get());
+    const ClusterLoop L(c, (size_t)B, (size_t)G, (size_t)A);
+    CwState S = L.f.S;
+    int32_t *pred = L.f.pred, *n_cat = L.n_cat, *n_ori = L.n_ori;
+    float *loss = L.f.loss, *grad = L.grad, *last = L.last;
+    S.o_bestdist = best_dist;
+    e = launch_add_begin(pc_in, n_points, B, stride, out_stride, A, pc_out, n_ori, n_cat, s);
+    if (e == hipSuccess) e = launch_cw_init(S, B, params->init_weight, params->max_weight, s);
+    if (e == hipSuccess) e = hipMemsetAsync(S.m, 0, 3 * added, s);     // m, v and o_bestattack lie side by side
+    if (e != hipSuccess) return fail(ctx, IFD_ERR_HIP, "ifd_cluster_attack: start", e);
+    const ifd_atk_out out{nullptr, loss, pred, nullptr, nullptr, nullptr};
+    if (int rc = cw_search(
+        params->binary_step, params->num_iter,
+        [&](int step) {
+            hipError_t e = launch_add_start(clusters, noise ? noise + (size_t)step * B * A * 3 : nullptr, n_cat, B, out_stride, A, pc_out, s);
+            return e == hipSuccess ? IFD_OK : fail(ctx, IFD_ERR_HIP, "ifd_cluster_attack: search step start", e);
+        },
+        [&](int, int it, bool final_it) {
+            if (int rc = input_grad_impl(ctx, state, pc_out, n_cat, B, out_stride, target, params->loss_kind, params->kappa, params->scale,
+                                         grad, &out, s))
+                return rc;
+            hipError_t e = launch_cluster_step(S, grad, pred, loss, target, pc_out, n_ori, final_it ? last : nullptr, nullptr, ClusterDiag{},
+                                               it + 1, params->attack_lr, params->scale, B, out_stride, num_add, cl_num_p, s);
+            return e == hipSuccess ? IFD_OK : fail(ctx, IFD_ERR_HIP, "ifd_cluster_attack: step", e);
+        },
+        [&](int) {
+            hipError_t e = launch_cw_adjust(S, target, nullptr, B, A, s);
+            return e == hipSuccess ? IFD_OK : fail(ctx, IFD_ERR_HIP, "ifd_cluster_attack: adjust", e);
+        }))
+        return rc;
+    e = launch_add_finish(S, last, n_cat, B, out_stride, A, pc_out, success, bounds, s);
+    if (e != hipSuccess) return fail(ctx, IFD_ERR_HIP, "ifd_cluster_attack: finish", e);
+    return IFD_OK;
 }
 
 }  // extern "C"

@@ -357,6 +357,22 @@ hipError_t launch_add_start(const float* cri, const float* noise, const int32_t*
 hipError_t launch_add_finish(const CwState& S, const float* last_input, const int32_t* n_cat, int B, int out_stride, int num_add,
                              float* pc_out, int32_t* success, double* bounds, hipStream_t s);
 
+// ---- the CW cluster-adding attack (pointnet_cluster.hip, include/ifd_cluster.h) ----
+constexpr int CLUSTER_DBSCAN_MAX_POINTS = 256;  // IFD_CLUSTER_DBSCAN_MAX_POINTS: a point a thread, the adjacency as bits in LDS
+struct ClusterDiag {                            // ifd_cluster_diag, member for member; every pointer may be null
+    float* dist_grad;                           // [B][A][3]
+    int32_t* nn_ori;                            // [B][A]
+    int32_t *far_i, *far_j;                     // [B][num_add]
+    float* far_val;                             // [B][num_add]
+};
+// a workgroup a cloud; the limits on stride, eps, min_samples and (where n_pts is null) the counts are the caller's to check
+hipError_t launch_cluster_dbscan(const float* pts, const int32_t* n_pts, int B, int stride, float eps, int min_samples, int32_t* labels,
+                                 int32_t* n_clusters, hipStream_t s);
+// one iteration behind ifd_cls_input_grad on the concatenated cloud, a workgroup a cloud; S has stride num_add * cl_num_p
+hipError_t launch_cluster_step(const CwState& S, const float* grad, const int32_t* pred, const float* loss, const int32_t* target,
+                               float* cat, const int32_t* n_ori, float* last_input, float* info, const ClusterDiag& D, int t, float lr,
+                               float scale, int B, int cat_stride, int num_add, int cl_num_p, hipStream_t s);
+
 // ---- the saliency Drop attack (pointnet_drop.hip, include/ifd_drop.h) ----
 constexpr int DROP_MAX_POINTS = 2048;           // IFD_DROP_MAX_POINTS: a cloud, its saliencies, ranks and indices in a workgroup's LDS
 struct DropOut {                                // ifd_drop_out, member for member; every pointer may be null

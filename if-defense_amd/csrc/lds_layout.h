@@ -260,6 +260,32 @@ struct DropLds {
 };
 static_assert(DropLds::BYTES == 50192 && DropLds::BYTES <= 65536 && DROP_MAX_POINTS % DROP_THREADS == 0, "LDS of drop_step_kernel");
 
+// ---- pointnet_cluster.hip: one cloud a workgroup of CLUSTER_THREADS threads ------------------------------------------------------
+constexpr int CLUSTER_THREADS = 256;
+struct DbscanLds {                                   // cluster_dbscan_kernel: thread i owns point i
+    static constexpr size_t N = CLUSTER_DBSCAN_MAX_POINTS, WORDS = N / 32;
+    static constexpr size_t X = 0;                                         // float [N][3] the cloud
+    static constexpr size_t CORE = X + N * 12;                             // uint32 [WORDS] the core points, a bit each
+    static constexpr size_t LAB = CORE + WORDS * 4;                        // int [2][N] labels, double-buffered
+    static constexpr size_t CID = LAB + 2 * N * 4;                         // int [N] a root's cluster number
+    static constexpr size_t FLAG = CID + N * 4;                            // int [4] a label changed in this round
+    static constexpr size_t BYTES = FLAG + 16;
+};
+static_assert(DbscanLds::BYTES == 6192 &&CLUSTER_DBSCAN_MAX_POINTS == CLUSTER_THREADS, "LDS of cluster_dbscan_kernel; a point a thread");
+struct ClusterStepLds {                              // cluster_step_kernel
+    static constexpr size_t O = 0;                                         // float [ADD_MAX_ORI][3] the originals
+    static constexpr size_t A = O + (size_t)ADD_MAX_ORI * 12;              // float [ADD_MAX_ADD][3] the added rows
+    static constexpr size_t PN = A + (size_t)ADD_MAX_ADD * 12;             // float [ADD_MAX_ADD] row j: max_i n2(i, j)
+    static constexpr size_t PI = PN + (size_t)ADD_MAX_ADD * 4;             // int [ADD_MAX_ADD] row j: its arg-max i
+    static constexpr size_t CI = PI + (size_t)ADD_MAX_ADD * 4;             // int [ADD_MAX_ADD] cluster c: i*
+    static constexpr size_t CJ = CI + (size_t)ADD_MAX_ADD * 4;             // int [ADD_MAX_ADD] cluster c: j*
+    static constexpr size_t CF = CJ + (size_t)ADD_MAX_ADD * 4;             // float [ADD_MAX_ADD] cluster c: far_c
+    static constexpr size_t SH = CF + (size_t)ADD_MAX_ADD * 4;             // float [CLUSTER_THREADS] the block sum's tree
+    static constexpr size_t BYTES = SH + (size_t)CLUSTER_THREADS * 4;
+};
+static_assert(ClusterStepLds::BYTES == 58368 && ClusterStepLds::BYTES <= 65536 && ADD_MAX_ADD % CLUSTER_THREADS == 0,
+              "LDS of cluster_step_kernel");
+
 // ---- block_sum / block_max / block_sum_d write one value per wave into their scratch ------------------------------------------
 static_assert((RepLds::BYTES - RepLds::SCRATCH) / 4 >= OPT_THREADS / 64 && (NrmLds::BYTES - NrmLds::SCRATCH) / 4 >= OPT_THREADS / 64,
               "8 waves: repulsion_kernel, normalize_kernel");

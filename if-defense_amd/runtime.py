@@ -1125,6 +1125,104 @@ class Classifier:
             return out, best, success.bool(), self._bounds(bounds)
         return out, best, success.bool()
 
+    # ---- include/ifd_cluster.h: the CW cluster-adding attack (models without feature_transform) ----
+    def _cluster_rows(self, num_add, cl_num_p):
+        num_add, cl_num_p = int(num_add), int(cl_num_p)
+        if num_add < 1 or cl_num_p < 1 or not 1 <= num_add * cl_num_p <= _lib.ADD_MAX_ADD:
+            raise IfdError("num_add and cl_num_p must be at least 1 and num_add * cl_num_p in [1, %d]" % _lib.ADD_MAX_ADD)
+        return num_add, cl_num_p, num_add * cl_num_p
+
+    def cluster_dbscan(self, pts, eps=0.2, min_samples=3, n_pts=None, want_count: bool = False):
+        """DBSCAN of every cloud of ``pts`` [B,N,3] (or a ragged list) by the definition in include/ifd_cluster.h
+        (ifd_cluster_dbscan): -> labels [B,N] int32 - clusters 0, 1, ... by ascending lowest core point, -1 for outliers and in the
+        rows beyond a cloud's points - and with want_count also the number of clusters [B] int32.  1 <= n <= 256 points a cloud."""
+        pts, n_pts = self._batch(pts, n_pts)
+        B, stride = int(pts.shape[0]), int(pts.shape[1])
+        if B < 1 or stride < 1:
+            raise IfdError("empty batch")
+        labels = torch.full((B, stride), -1, device=self.device, dtype=torch.int32)
+        count = torch.zeros(B, device=self.device, dtype=torch.int32) if want_count else None
+        with torch.cuda.device(self.device):
+            self._check(self.lib.ifd_cluster_dbscan(self.ctx, pts.data_ptr(), None if n_pts is None else n_pts.data_ptr(), B, stride,
+                                                    float(eps), int(min_samples), labels.data_ptr(),
+                                                    None if count is None else count.data_ptr(), self._stream()))
+        return (labels, count) if want_count else labels
+
+    def cluster_step(self, state, grad, pred, target, cat, num_add, cl_num_p, t, lr, scale=1., loss=None, last_input=None, n_ori=None,
+                     want_info: bool = False, want=()):
+        """One iteration of the cluster-adding attack behind ``input_grad`` on the concatenated clouds (ifd_cluster_step), IN PLACE
+        on the added rows of ``cat`` [B,N,3] (cloud b: n_ori[b] originals, then A = num_add * cl_num_p added rows, cluster c the rows
+        [c * cl_num_p, (c + 1) * cl_num_p); n_ori None: N - A) and on ``state`` (``cw_state(B, A, ...)``).  grad, pred, loss, last_input
+        [B,A,3]: as ``add_step`` takes them.  Returns a dict: with want_info "info" [B,3] (adversarial loss, dist * weight, dist), and
+        the diagnostics named in ``want``: "dist_grad" [B,A,3], "nn_ori" [B,A] int32, "far_i" / "far_j" [B,num_add] int32, "far_val"
+        [B,num_add] (clouds outside the limits are left as allocated: NaN / -1)."""
+        num_add, cl_num_p, A = self._cluster_rows(num_add, cl_num_p)
+        if not torch.is_tensor(cat) or cat.dim() != 3:
+            raise IfdError("cat must be a contiguous float32 [B,N,3] device tensor")
+        B, stride = int(cat.shape[0]), int(cat.shape[1])
+        st = self._cw_struct(state, B, A)
+        ptrs = [self._cw_cloud(x, B, stride, n) for x, n in ((grad, "grad"), (cat, "cat"))]
+        if grad is None:
+            raise IfdError("grad is missing")
+        li = self._cw_cloud(last_input, B, A, "last_input")
+        pred = self._vec(pred, B, torch.int32, "pred")
+        target = self._target(target, B)
+        loss = self._vec(loss, B, torch.float32, "loss")
+        n_ori = self._counts(n_ori, B)
+        names = ("dist_grad", "nn_ori", "far_i", "far_j", "far_val")
+        shapes = {"dist_grad": ((B, A, 3), torch.float32), "nn_ori": ((B, A), torch.int32), "far_i": ((B, num_add), torch.int32),
+                  "far_j": ((B, num_add), torch.int32), "far_val": ((B, num_add), torch.float32)}
+        out = self._diag(want, shapes, " | ".join(names))
+        ptr = lambda x: None if x is None else x.data_ptr()        # noqa: E731
+        diag = _lib.IfdClusterDiag(*[ptr(out.get(k)) for k in names])
+        info = torch.empty(B, 3, device=self.device, dtype=torch.float32) if want_info else None
+        with torch.cuda.device(self.device):
+            self._check(self.lib.ifd_cluster_step(self.ctx, C.byref(st), ptrs[0], pred.data_ptr(), ptr(loss), target.data_ptr(), ptrs[1],
+                                                  ptr(n_ori), li, ptr(info), C.byref(diag) if out else None, int(t), float(lr),
+                                                  float(scale), B, stride, num_add, cl_num_p, self._stream()))
+        if want_info:
+            out["info"] = info
+        return out
+
+    def cluster_attack(self, pc, target, clusters, num_add, cl_num_p, noise=None, loss="logits", kappa=0., scale=1., attack_lr=1e-2,
+                       init_weight=5., max_weight=30., binary_step=5, num_iter=500, n_points=None, out_stride=None,
+                       want_bounds: bool = False):
+        """The whole CW cluster-adding attack on the device (ifd_cluster_attack) from the start ``clusters`` [B,A,3], A = num_add *
+        cl_num_p: -> (clouds [B,out_stride,3]: each cloud's originals bit for bit, then its A added points; best_dist [B] (1e10 where
+        no iteration reached the target); success [B] bool) and with want_bounds also {"weight", "lower", "upper"} [B] float64.
+        noise: [binary_step,B,A,3], the start noise of every search step, or None.  out_stride: rows of the output, default N + A."""
+        num_add, cl_num_p, A = self._cluster_rows(num_add, cl_num_p)
+        loss_kind = self._loss_kind(loss)
+        pc, n_points = self._batch(pc, n_points)
+        B, stride = int(pc.shape[0]), int(pc.shape[1])
+        if B < 1 or stride < 1:
+            raise IfdError("empty batch")
+        target = self._target(target, B)
+        clusters = _f32(torch.as_tensor(clusters), self.device)
+        if tuple(clusters.shape) != (B, A, 3):
+            raise IfdError("clusters must be [B,num_add*cl_num_p,3]")
+        if noise is not None:
+            noise = _f32(torch.as_tensor(noise), self.device)
+            if tuple(noise.shape) != (int(binary_step), B, A, 3):
+                raise IfdError("noise must be [binary_step,B,num_add*cl_num_p,3]")
+        out_stride = stride + A if out_stride is None else int(out_stride)
+        if out_stride < 1:
+            raise IfdError("out_stride must be positive")
+        out = torch.zeros(B, out_stride, 3, device=self.device, dtype=torch.float32)
+        best = torch.empty(B, device=self.device, dtype=torch.float32)
+        success = torch.empty(B, device=self.device, dtype=torch.int32)
+        bounds = torch.empty(3, B, device=self.device, dtype=torch.float64) if want_bounds else None
+        P = _lib.IfdClusterParams(C.sizeof(_lib.IfdClusterParams), loss_kind, int(binary_step), int(num_iter), num_add, cl_num_p,
+                                  float(kappa), float(scale), float(attack_lr), float(init_weight), float(max_weight))
+        with torch.cuda.device(self.device):
+            self._check(self.lib.ifd_cluster_attack(self.ctx, C.byref(P), pc.data_ptr(), None if n_points is None else n_points.data_ptr(),
+                                                    target.data_ptr(), clusters.data_ptr(), None if noise is None else noise.data_ptr(), B,
+                                                    stride, out_stride, out.data_ptr(), best.data_ptr(), success.data_ptr(),
+                                                    None if bounds is None else bounds.data_ptr(), self._stream()))
+        if want_bounds:
+            return out, best, success.bool(), self._bounds(bounds)
+        return out, best, success.bool()
+
     # ---- include/ifd_drop.h: the saliency Drop attack (models without feature_transform) ----
     def drop_step(self, grad, pc, n_points, k, alpha=1., index=None, want=()):
         """One round of the Drop attack behind ``input_grad`` (ifd_drop_step), IN PLACE on ``pc`` [B,N,3] float32, ``n_points`` [B]
