@@ -278,6 +278,38 @@ CLUSTER_SIGNATURES = {
                                      C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
 }
 
+# include/ifd_object.h (the CW object-adding attack on the PointNet victim), versioned on its own
+OBJECT_ABI_VERSION = 1
+
+
+class IfdObjectState(C.Structure):
+    _fields_ = [("cw", IfdCwState), ("obj", C.c_void_p), ("shift", C.c_void_p), ("angle", C.c_void_p), ("shift_m", C.c_void_p),
+                ("shift_v", C.c_void_p), ("angle_m", C.c_void_p), ("angle_v", C.c_void_p)]
+
+
+class IfdObjectDiag(C.Structure):
+    _fields_ = [("obj_grad", C.c_void_p), ("nn_ori", C.c_void_p), ("g_shift", C.c_void_p), ("g_angle", C.c_void_p), ("l2", C.c_void_p),
+                ("cd", C.c_void_p)]
+
+
+class IfdObjectParams(C.Structure):
+    _fields_ = [("struct_size", C.c_int32), ("loss_kind", C.c_int32), ("binary_step", C.c_int32), ("num_iter", C.c_int32),
+                ("num_add", C.c_int32), ("obj_num_p", C.c_int32), ("kappa", C.c_float), ("scale", C.c_float), ("attack_lr", C.c_float),
+                ("init_weight", C.c_float), ("max_weight", C.c_float)]
+
+
+OBJECT_SIGNATURES = {
+    "ifd_object_abi_version": (C.c_int, []),
+    "ifd_object_place": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int,
+                                   C.c_int, C.c_void_p]),
+    "ifd_object_step": (C.c_int, [C.c_void_p, C.POINTER(IfdObjectState), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                  C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(IfdObjectDiag), C.c_int, C.c_float, C.c_float,
+                                  C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    "ifd_object_attack": (C.c_int, [C.c_void_p, C.POINTER(IfdObjectParams), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                    C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                    C.c_void_p, C.c_void_p]),
+}
+
 _lib = None
 
 
@@ -294,7 +326,7 @@ def load() -> C.CDLL:
     lib = C.CDLL(LIB_PATH, mode=C.RTLD_GLOBAL)
     for name, (res, args) in list(SIGNATURES.items()) + list(DUP_SIGNATURES.items()) + list(CLS_SIGNATURES.items()) + \
             list(ATK_SIGNATURES.items()) + list(CW_SIGNATURES.items()) + list(KNN_SIGNATURES.items()) + list(ADD_SIGNATURES.items()) + \
-            list(DROP_SIGNATURES.items()) + list(CLUSTER_SIGNATURES.items()):
+            list(DROP_SIGNATURES.items()) + list(CLUSTER_SIGNATURES.items()) + list(OBJECT_SIGNATURES.items()):
         fn = getattr(lib, name)          # AttributeError if the library lacks a declared symbol
         fn.restype, fn.argtypes = res, args
     if lib.ifd_abi_version() != ABI_VERSION:
@@ -315,5 +347,7 @@ def load() -> C.CDLL:
         raise ImportError("libifd.so DROP ABI %d != binding DROP ABI %d; rebuild" % (lib.ifd_drop_abi_version(), DROP_ABI_VERSION))
     if lib.ifd_cluster_abi_version() != CLUSTER_ABI_VERSION:
         raise ImportError("libifd.so CLUSTER ABI %d != binding CLUSTER ABI %d; rebuild" % (lib.ifd_cluster_abi_version(), CLUSTER_ABI_VERSION))
+    if lib.ifd_object_abi_version() != OBJECT_ABI_VERSION:
+        raise ImportError("libifd.so OBJECT ABI %d != binding OBJECT ABI %d; rebuild" % (lib.ifd_object_abi_version(), OBJECT_ABI_VERSION))
     _lib = lib
     return lib

@@ -23,6 +23,8 @@ kNN attack (baselines/attack/CW/kNN.py, include/ifd_knn.h), likewise, and ``CWAd
 reference's untargeted point-dropping attack (baselines/attack/Saliency/Drop.py, include/ifd_drop.h), whose clouds come back
 smaller; it draws no noise.  ``CWAddClusters`` is the reference's cluster-adding attack (baselines/attack/CW/Add_Cluster.py,
 include/ifd_cluster.h): ``num_add`` clusters of ``cl_num_p`` points, started on DBSCAN clusters of the 128 critical points.
+``CWAddObjects`` is its object-adding attack (baselines/attack/CW/Add_Objects.py, include/ifd_object.h): ``num_add`` copies of an
+object, each placed by a shift and a rotation about the y axis that are optimised with the object's points.
 """
 from __future__ import annotations
 
@@ -486,6 +488,174 @@ class CWAddClusters(_Attack):
             adv, dist, ok = self.model.cluster_attack(data, target, clusters, self.num_add, self.cl_num_p, noise, self.adv_func,
                                                       self.kappa, self._scale(B), self.attack_lr, self.init_weight, self.max_weight,
                                                       self.binary_step, self.num_iter)
+        return dist.cpu().numpy().astype(np.float64), adv.cpu().numpy(), self._finish(ok, B)
+
+
+def prepare_objects(object_pc, scaling, num_add, obj_num_p, rng):
+    """Add_Objects.py:86-98, the reference's numpy calls in its order on ``rng`` (a np.random.RandomState; the reference uses the
+    global one): object_pc [M,3] -> [num_add,obj_num_p,3] float64.  The object is centred, scaled to the unit sphere and by
+    ``scaling`` in its own dtype (float32 for a float32 file), then shuffled in place once per object - the shuffles accumulate - and
+    the first ``obj_num_p`` rows are taken.  The caller's array is not changed.  Refused with ValueError (the reference fails on a
+    broadcast or an assert): an array that is not [M,3], fewer than ``obj_num_p`` rows, a non-finite or single-point object."""
+    pc = np.asarray(object_pc)
+    if pc.ndim != 2 or pc.shape[1] != 3:
+        raise ValueError("the object must be an [M,3] array, got %s" % (tuple(pc.shape),))
+    if len(pc) < int(obj_num_p):
+        raise ValueError("the object has %d points, fewer than obj_num_p = %d" % (len(pc), int(obj_num_p)))
+    pc = pc - np.mean(pc, axis=0)[None, :]                             # normalize_points_np
+    with np.errstate(all="ignore"):
+        pc = pc / np.max(np.sqrt(np.sum(pc ** 2, axis=1)), 0)
+    if not np.isfinite(pc).all():
+        raise ValueError("the object cannot be normalised (all points equal, or non-finite coordinates)")
+    pc = pc * scaling
+    out = np.zeros((int(num_add), int(obj_num_p), 3))
+    for i in range(int(num_add)):
+        rng.shuffle(pc)
+        out[i] = pc[:int(obj_num_p)].copy()
+    return out
+
+
+def init_centers(points, labels, num_add, rng):
+    """Add_Objects.py:116-143 on one cloud, the reference's numpy calls in its order on ``rng`` (np.random.RandomState): points [n,3]
+    the critical points, labels [n] their DBSCAN labels -> [num_add,3].  From each of the ``num_add`` largest clusters, in ascending
+    order of their counts (a stable argsort), the cluster point nearest to the cluster's mean (the lowest index among equals); then,
+    while centres are missing, one random non-outlier point.  Where the reference raises - no non-outlier point at all - every point
+    counts as one for the fallback."""
+    points, result = np.asarray(points), np.asarray(labels)
+    filter_idx = result > -0.5
+    result = result[filter_idx]
+    if filter_idx.any():
+        points = points[filter_idx]
+    out = []
+    labels, counts = np.unique(result, return_counts=True)
+    for one_label in labels[np.argsort(counts, kind="stable")[-num_add:]]:
+        cluster_points = points[result == one_label]
+        cluster_center = np.mean(cluster_points, axis=0)
+        dist = np.sum((cluster_points - cluster_center[None, :]) ** 2, axis=1)
+        out.append(cluster_points[np.argmin(dist)].copy())
+    while len(out) < num_add:
+        out.append(points[rng.choice(len(points), 1)[0]].copy())
+    return np.array(out)
+
+
+class CWAddObjects(_Attack):
+    """CW attack by adding objects (Add_Objects.py CWAddObjects with L2ChamferDist(num_add, 'adv2ori', 0.2)): ``num_add`` copies of
+    ``obj_num_p`` points of one object are placed into the cloud by a rotation about the y axis and a shift each; the object-frame
+    points, the shifts and the angles are optimised by ``binary_step`` search steps on the weight of the distance - the L2 norm of
+    the points' displacement from the object plus 0.2 x Chamfer of the placed points to the cloud - ``num_iter`` Adam iterations each.
+    ``model`` is a ``runtime.Classifier`` (anything with its ``input_grad``, ``add_critical_points``, ``cluster_dbscan``,
+    ``object_state``, ``object_place``, ``object_step``, ``cw_adjust`` and ``object_attack``), ``object_pc`` the object [M,3] (the
+    reference's data/airplane.npy), ``adv_func`` the loss by name ("logits": LogitsAdvLoss(kappa), or "cross_entropy"), ``dist_func``
+    "l2_chamfer" (the only one built).  ``attack(data [B,K,3], target [B])``, 128 <= K <= 2048, returns the reference's triple
+    (o_bestdist [B], clouds [B,K+num_add*obj_num_p,3]: the originals, then the best placed points, or the last forwarded ones where
+    the search never succeeded; success_num) as numpy arrays.  ``verbose=True`` drives the loop from the host, one ``input_grad`` and
+    one ``object_step`` an iteration, with the reference's progress lines every num_iter // 5 iterations (the two losses are the batch
+    means of the previous iteration, zero at iteration 0) - its wall-clock lines ("total: ...") are left out; ``verbose=False`` is one
+    library call and prints the last line only.  Both give the same bits.
+
+    ONE np.random.RandomState(seed) does the object's shuffles at construction (``prepare_objects``) and then the fallback draws of
+    ``init_centers``, kept across ``attack`` calls: given equal DBSCAN labels, objects and centres are the reference's under
+    np.random.seed(seed), number for number.  The centres (``_init_centers``): the 128 critical points of ``add_critical_points``
+    towards the TARGET labels, clustered on the device by ``cluster_dbscan(eps=0.2, min_samples=3)`` (include/ifd_cluster.h's
+    definition, sklearn's result wherever no pair lies within float32 rounding of eps), then ``init_centers``.  Defined where the
+    reference raises or leaves the order open: a cloud whose 128 critical points are all outliers uses all of them as fallback
+    candidates; the argsort of the cluster counts is stable; an object with fewer than ``obj_num_p`` rows, or not [M,3], is refused
+    with ValueError.
+
+    Every search step starts from objects + randn * 1e-7, centres + randn * 1e-7 and angles rand * pi, drawn here in the reference's
+    order from a seeded HOST torch.Generator: agreement with a reference run in distribution only.  The reference draws three angles
+    per object and rotates by the first alone; the other two never move and reach no output, so one angle per object is kept.
+    ``ref_batch``: the batch the reference's losses are a mean over (scale = 1 / ref_batch); the default is the batch passed to
+    ``attack``."""
+
+    NUM_CRI, EPS, MIN_SAMPLES = 128, 0.2, 3
+
+    def __init__(self, model, object_pc, adv_func="logits", dist_func="l2_chamfer", attack_lr=1e-2, init_weight=5., max_weight=40.,
+                 binary_step=5, num_iter=500, num_add=3, obj_num_p=64, scaling=0.3, kappa=0., seed=1, ref_batch=None, verbose=True):
+        if str(dist_func).lower() != "l2_chamfer":
+            raise ValueError("only the l2_chamfer distance of the reference's script is built")
+        if int(binary_step) < 1 or int(num_iter) < 1:
+            raise ValueError("binary_step and num_iter must be at least 1")
+        if int(num_add) < 1 or int(obj_num_p) < 1 or not 1 <= int(num_add) * int(obj_num_p) <= 1024:
+            raise ValueError("num_add and obj_num_p must be at least 1 and num_add * obj_num_p in [1, 1024]")
+        self.model, self.adv_func, self.kappa = model, adv_func, float(kappa)
+        self.attack_lr, self.init_weight, self.max_weight = float(attack_lr), float(init_weight), float(max_weight)
+        self.binary_step, self.num_iter, self.num_add, self.obj_num_p = int(binary_step), int(num_iter), int(num_add), int(obj_num_p)
+        self.rng = np.random.RandomState(int(seed))
+        self.object_pc = prepare_objects(object_pc, scaling, self.num_add, self.obj_num_p, self.rng)
+        self._common(seed, ref_batch, verbose)
+
+    def draws(self, data: torch.Tensor):
+        """(noise_obj [binary_step,B,A,3], noise_shift [binary_step,B,num_add,3], angles0 [binary_step,B,num_add]): per search step
+        the reference's three draws in its order (Add_Objects.py:229-240)."""
+        B, na, A = int(data.shape[0]), self.num_add, self.num_add * self.obj_num_p
+        no, ns, an = [], [], []
+        for _ in range(self.binary_step):
+            no.append(torch.randn((B, A, 3), generator=self.generator) * 1e-7)
+            ns.append(torch.randn((B, na, 3), generator=self.generator) * 1e-7)
+            an.append((torch.rand((B, na, 3), generator=self.generator) * np.pi)[..., 0].contiguous())
+        return torch.stack(no), torch.stack(ns), torch.stack(an)
+
+    def _init_centers(self, data, target):
+        """Add_Objects.py:100-146 -> centres [B,num_add,3] float32 (a CPU tensor)."""
+        net = self.model
+        B = int(data.shape[0])
+        cri = net.add_critical_points(data, target, self.NUM_CRI, self._scale(B))
+        labels = net.cluster_dbscan(cri, self.EPS, self.MIN_SAMPLES).cpu().numpy()
+        cri = cri.cpu().numpy()
+        out = np.stack([init_centers(cri[b], labels[b], self.num_add, self.rng) for b in range(B)])
+        return torch.from_numpy(out.astype(np.float32))
+
+    def _loop(self, data, target, objects, centers, noise_obj, noise_shift, angles0):
+        """Add_Objects.py:227-367 from the host: the kernels of ifd_object_attack on the same numbers."""
+        net = self.model
+        dev = net.device
+        B, K, na, P = int(data.shape[0]), int(data.shape[1]), self.num_add, self.obj_num_p
+        A = na * P
+        ori = data.to(dev).contiguous()
+        tgt = target.to(dev)
+        objects, centers = objects.to(dev), centers.to(dev)
+        state = net.object_state(B, na, P, self.init_weight, self.max_weight)
+        cat = torch.cat([ori, torch.zeros(B, A, 3, device=dev)], dim=1).contiguous()
+        last = torch.empty(B, A, 3, device=dev)
+        every = max(self.num_iter // 5, 1)
+        for step in range(self.binary_step):
+            state["obj"].copy_(objects.reshape(1, A, 3) + noise_obj[step].to(dev))
+            state["shift"].copy_(centers + noise_shift[step].to(dev))
+            state["angle"].copy_(angles0[step].to(dev))
+            for key in ("shift_m", "shift_v", "angle_m", "angle_v"):
+                state[key].zero_()
+            net.object_place(state["obj"], state["angle"], state["shift"], cat, na, P)
+            info = None
+            for it in range(self.num_iter):
+                grad, aux = net.input_grad(cat, tgt, self.adv_func, self.kappa, self._scale(B), want_aux=True)
+                if it % every == 0:
+                    self._progress(self.STEP_LINES, step, it, aux["pred"], tgt, info, 1)
+                final = step == self.binary_step - 1 and it == self.num_iter - 1
+                info = net.object_step(state, objects, grad, aux["pred"], tgt, cat, na, P, it + 1, self.attack_lr, self._scale(B),
+                                       loss=aux["loss"], last_input=last if final else None,
+                                       want_info=it % every == every - 1).get("info")
+            net.cw_adjust(state, tgt)
+        ok = state["lower"] > 0
+        added = torch.where(ok[:, None, None], state["o_bestattack"], last)
+        return torch.cat([ori, added], dim=1), state["o_bestdist"], ok
+
+    def attack(self, data, target):
+        data, target = self._tensors(data, target)
+        if data.dim() != 3 or int(data.shape[2]) != 3:
+            raise ValueError("data must be [B,K,3]")
+        if not self.NUM_CRI <= int(data.shape[1]) <= 2048:
+            raise ValueError("clouds must have between 128 and 2048 points")
+        B = int(data.shape[0])
+        objects = torch.from_numpy(self.object_pc).float()
+        centers = self._init_centers(data, target)
+        noise_obj, noise_shift, angles0 = self.draws(data)
+        if self.verbose:
+            adv, dist, ok = self._loop(data, target, objects, centers, noise_obj, noise_shift, angles0)
+        else:
+            adv, dist, ok = self.model.object_attack(data, target, objects, centers, angles0, noise_obj, noise_shift, self.adv_func,
+                                                     self.kappa, self._scale(B), self.attack_lr, self.init_weight, self.max_weight,
+                                                     self.binary_step, self.num_iter)
         return dist.cpu().numpy().astype(np.float64), adv.cpu().numpy(), self._finish(ok, B)
 
 

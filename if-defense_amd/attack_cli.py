@@ -1,4 +1,4 @@
-"""What the attack scripts (fgm_attack, perturb_attack, knn_attack, add_attack, drop_attack, cluster_attack) share: the reference's common flags, the two
+"""What the attack scripts (fgm_attack, perturb_attack, knn_attack, add_attack, drop_attack, cluster_attack, object_attack) share: the reference's common flags, the two
 refusals, the data file, the victim, the batch loop and the result file.  Each script adds its own flags between ``parser_head``
 and ``parser_tail``, so ``print(args)`` lists them in the reference's order."""
 from __future__ import annotations

@@ -13,6 +13,7 @@
 #include "../../include/ifd_add.h"
 #include "../../include/ifd_drop.h"
 #include "../../include/ifd_cluster.h"
+#include "../../include/ifd_object.h"
 
 #include <hip/hip_runtime.h>
 
@@ -1828,6 +1829,21 @@ struct ClusterLoop {                      // AddLoop without the critical points
         c.round_up(256);
     }
 };
+struct ObjectLoop {                       // ClusterLoop + the object rows and the pose (shift, angle and their moments)
+    CwFront f; int32_t *n_cat, *n_ori; float *grad, *last; ObjectState S{};
+    ObjectLoop(Carve& c, size_t B, size_t G, size_t A, size_t num_add) : f(c, B) {
+        const size_t added = B * A * 12, pose = B * num_add * 4;
+        n_cat = c.take<int32_t>(B * 4); n_ori = c.take<int32_t>(B * 4);
+        grad = c.take<float>(B * G * 12);
+        f.S.m = c.take<float>(added); f.S.v = c.take<float>(added); f.S.o_bestattack = c.take<float>(added);   // side by side
+        last = c.take<float>(added);
+        S.obj = c.take<float>(added);
+        S.shift = c.take<float>(3 * pose); S.angle = c.take<float>(pose);
+        S.shift_m = c.take<float>(3 * pose); S.shift_v = c.take<float>(3 * pose);
+        S.angle_m = c.take<float>(pose); S.angle_v = c.take<float>(pose);
+        c.round_up(256);
+    }
+};
 struct DropLoop {
     float *grad, *logits; int32_t* pred;
     DropLoop(Carve& c, size_t B, size_t cloud) {
@@ -2438,6 +2454,129 @@ int ifd_cluster_attack(ifd_ctx* ctx, const ifd_cluster_params* params, const flo
         return rc;
     e = launch_add_finish(S, last, n_cat, B, out_stride, A, pc_out, success, bounds, s);
     if (e != hipSuccess) return fail(ctx, IFD_ERR_HIP, "ifd_cluster_attack: finish", e);
+    return IFD_OK;
+}
+
+}  // extern "C"
+
+// ---- the CW object-adding attack (include/ifd_object.h) ----------------------------------------------------------------
+
+extern "C" {
+
+int ifd_object_abi_version(void) { return IFD_OBJECT_ABI_VERSION; }
+
+int ifd_object_place(ifd_ctx* ctx, const float* obj, const float* angle, const float* shift, float* cat, const int32_t* n_ori, int B,
+                     int cat_stride, int num_add, int obj_num_p, void* stream) {
+    if (!ctx) return IFD_ERR_ARG;
+    if (int rc = atk_context_ok(ctx, "ifd_object_place")) return rc;
+    if (!obj || !angle || !shift || !cat || B < 1) return fail(ctx, IFD_ERR_ARG, "ifd_object_place: bad argument (obj, angle, shift, cat; B >= 1)");
+    const int A = cluster_rows(num_add, obj_num_p);
+    if (A < 1) return fail(ctx, IFD_ERR_ARG, "ifd_object_place: num_add < 1, obj_num_p < 1 or num_add * obj_num_p outside [1, 1024]");
+    if (cat_stride > IFD_CLS_MAX_POINTS || cat_stride < A + 1)
+        return fail(ctx, IFD_ERR_ARG, "ifd_object_place: cat_stride outside [num_add * obj_num_p + 1, 10000]");
+    if (!n_ori && cat_stride - A > IFD_ADD_MAX_ORI)
+        return fail(ctx, IFD_ERR_ARG, "ifd_object_place: without n_ori, cat_stride - num_add * obj_num_p > 2048 original rows");
+    IFD_ON_CTX_DEVICE(ctx);
+    hipError_t e = launch_object_place(obj, angle, shift, cat, n_ori, B, cat_stride, num_add, obj_num_p, static_cast<hipStream_t>(stream));
+    if (e != hipSuccess) return fail(ctx, IFD_ERR_HIP, "ifd_object_place launch", e);
+    return IFD_OK;
+}
+
+int ifd_object_step(ifd_ctx* ctx, const ifd_object_state* state, const float* objects, const float* grad, const int32_t* pred,
+                    const float* loss, const int32_t* target, float* cat, const int32_t* n_ori, float* last_input, float* info,
+                    const ifd_object_diag* diag, int t, float lr, float scale, int B, int cat_stride, int num_add, int obj_num_p,
+                    void* stream) {
+    if (!ctx) return IFD_ERR_ARG;
+    if (int rc = atk_context_ok(ctx, "ifd_object_step")) return rc;
+    if (!state || !cw_state_ok(&state->cw, false) || !state->obj || !state->shift || !state->angle || !state->shift_m || !state->shift_v ||
+        !state->angle_m || !state->angle_v)
+        return fail(ctx, IFD_ERR_ARG, "ifd_object_step: state missing (cw: m, v, bestdist, bestscore, o_bestdist, o_bestscore, o_bestattack, "
+                                      "weight; obj, shift, angle, shift_m, shift_v, angle_m, angle_v)");
+    if (!objects || !grad || !pred || !target || !cat || t < 1 || B < 1)
+        return fail(ctx, IFD_ERR_ARG, "ifd_object_step: bad argument (objects, grad, pred, target, cat; t >= 1, B >= 1)");
+    const int A = cluster_rows(num_add, obj_num_p);
+    if (A < 1) return fail(ctx, IFD_ERR_ARG, "ifd_object_step: num_add < 1, obj_num_p < 1 or num_add * obj_num_p outside [1, 1024]");
+    if (cat_stride > IFD_CLS_MAX_POINTS || cat_stride < A + 1)
+        return fail(ctx, IFD_ERR_ARG, "ifd_object_step: cat_stride outside [num_add * obj_num_p + 1, 10000]");
+    if (!n_ori && cat_stride - A > IFD_ADD_MAX_ORI)
+        return fail(ctx, IFD_ERR_ARG, "ifd_object_step: without n_ori, cat_stride - num_add * obj_num_p > 2048 original rows");
+    IFD_ON_CTX_DEVICE(ctx);
+    const ObjectState S{cw_state(&state->cw), state->obj, state->shift, state->angle, state->shift_m, state->shift_v, state->angle_m,
+                        state->angle_v};
+    const ObjectDiag D = diag ? ObjectDiag{diag->obj_grad, diag->nn_ori, diag->g_shift, diag->g_angle, diag->l2, diag->cd} : ObjectDiag{};
+    hipError_t e = launch_object_step(S, objects, grad, pred, loss, target, cat, n_ori, last_input, info, D, t, lr, scale, B, cat_stride,
+                                      num_add, obj_num_p, static_cast<hipStream_t>(stream));
+    if (e != hipSuccess) return fail(ctx, IFD_ERR_HIP, "ifd_object_step launch", e);
+    return IFD_OK;
+}
+
+int ifd_object_attack(ifd_ctx* ctx, const ifd_object_params* params, const float* pc_in, const int32_t* n_points,
+                      const int32_t* target, const float* objects, const float* centers, const float* noise_obj,
+                      const float* noise_shift, const float* angles0, int B, int stride, int out_stride, float* pc_out,
+                      float* best_dist, int32_t* success, double* bounds, void* stream) {
+    if (!ctx) return IFD_ERR_ARG;
+    if (int rc = atk_context_ok(ctx, "ifd_object_attack")) return rc;
+    if (!params || params->struct_size != (int32_t)sizeof(ifd_object_params))
+        return fail(ctx, IFD_ERR_ARG, "ifd_object_attack: params missing or of another struct_size");
+    if (!atk_loss_ok(params->loss_kind)) return fail(ctx, IFD_ERR_ARG, "ifd_object_attack: unknown loss_kind");
+    if (params->binary_step < 1) return fail(ctx, IFD_ERR_ARG, "ifd_object_attack: binary_step < 1");
+    if (params->num_iter < 1) return fail(ctx, IFD_ERR_ARG, "ifd_object_attack: num_iter < 1");
+    const int num_add = params->num_add, obj_num_p = params->obj_num_p, A = cluster_rows(num_add, obj_num_p);
+    if (A < 1) return fail(ctx, IFD_ERR_ARG, "ifd_object_attack: num_add < 1, obj_num_p < 1 or num_add * obj_num_p outside [1, 1024]");
+    if (B < 1) return fail(ctx, IFD_ERR_ARG, "ifd_object_attack: B >= 1 is needed");
+    if (stride < 1 || stride > IFD_CLS_MAX_POINTS) return fail(ctx, IFD_ERR_ARG, "ifd_object_attack: stride outside [1, 10000]");
+    if (out_stride < 1 || out_stride > IFD_CLS_MAX_POINTS) return fail(ctx, IFD_ERR_ARG, "ifd_object_attack: out_stride outside [1, 10000]");
+    if (!pc_in || !target || !objects || !centers || !angles0 || !pc_out || !best_dist || !success)
+        return fail(ctx, IFD_ERR_ARG,
+                    "ifd_object_attack: missing pointer (pc_in, target, objects, centers, angles0, pc_out, best_dist, success)");
+    const int hi = std::min(std::min(stride, IFD_ADD_MAX_ORI), out_stride - A);
+    if (!n_points && stride > hi)
+        return fail(ctx, IFD_ERR_ARG, "ifd_object_attack: without n_points, stride outside [1, min(2048, out_stride - num_add * obj_num_p)]");
+    if (clouds_overlap(pc_in, (size_t)B * stride * 12, pc_out, (size_t)B * out_stride * 12))
+        return fail(ctx, IFD_ERR_ARG, "ifd_object_attack: pc_out overlaps pc_in");
+    IFD_ON_CTX_DEVICE(ctx);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const int G = std::max(stride, out_stride);
+    const size_t added = (size_t)B * A * 12, pose = (size_t)B * num_add * 4;
+    const size_t state = carved_bytes([&](Carve& c) { ObjectLoop(c, (size_t)B, (size_t)G, (size_t)A, (size_t)num_add); });
+    hipError_t e = ctx->ws.grow(atk_loop_ws_bytes(B, G, state, false));
+    if (e != hipSuccess) return fail(ctx, IFD_ERR_NOMEM, "ifd_object_attack: workspace", e);
+    if (int rc = atk_check(ctx, "ifd_object_attack", n_points, target, B, 1, hi, numeric_range(1, hi), s)) return rc;
+    Carve c(ctx->ws.get());
+    const ObjectLoop L(c, (size_t)B, (size_t)G, (size_t)A, (size_t)num_add);
+    ObjectState S = L.S;
+    S.cw = L.f.S;
+    S.cw.o_bestdist = best_dist;
+    int32_t *pred = L.f.pred, *n_cat = L.n_cat, *n_ori = L.n_ori;
+    float *loss = L.f.loss, *grad = L.grad, *last = L.last;
+    e = launch_add_begin(pc_in, n_points, B, stride, out_stride, A, pc_out, n_ori, n_cat, s);
+    if (e == hipSuccess) e = launch_cw_init(S.cw, B, params->init_weight, params->max_weight, s);
+    if (e == hipSuccess) e = hipMemsetAsync(S.cw.m, 0, 3 * added, s);  // m, v and o_bestattack lie side by side
+    if (e != hipSuccess) return fail(ctx, IFD_ERR_HIP, "ifd_object_attack: start", e);
+    const ifd_atk_out out{nullptr, loss, pred, nullptr, nullptr, nullptr};
+    if (int rc = cw_search(
+        params->binary_step, params->num_iter,
+        [&](int step) {
+            hipError_t e = launch_object_start(S, objects, centers, noise_obj ? noise_obj + (size_t)step * (added / 4) : nullptr,
+                                               noise_shift ? noise_shift + (size_t)step * pose / 4 * 3 : nullptr,
+                                               angles0 + (size_t)step * (pose / 4), n_cat, B, out_stride, num_add, obj_num_p, pc_out, s);
+            return e == hipSuccess ? IFD_OK : fail(ctx, IFD_ERR_HIP, "ifd_object_attack: search step start", e);
+        },
+        [&](int, int it, bool final_it) {
+            if (int rc = input_grad_impl(ctx, state, pc_out, n_cat, B, out_stride, target, params->loss_kind, params->kappa, params->scale,
+                                         grad, &out, s))
+                return rc;
+            hipError_t e = launch_object_step(S, objects, grad, pred, loss, target, pc_out, n_ori, final_it ? last : nullptr, nullptr,
+                                              ObjectDiag{}, it + 1, params->attack_lr, params->scale, B, out_stride, num_add, obj_num_p, s);
+            return e == hipSuccess ? IFD_OK : fail(ctx, IFD_ERR_HIP, "ifd_object_attack: step", e);
+        },
+        [&](int) {
+            hipError_t e = launch_cw_adjust(S.cw, target, nullptr, B, A, s);
+            return e == hipSuccess ? IFD_OK : fail(ctx, IFD_ERR_HIP, "ifd_object_attack: adjust", e);
+        }))
+        return rc;
+    e = launch_add_finish(S.cw, last, n_cat, B, out_stride, A, pc_out, success, bounds, s);
+    if (e != hipSuccess) return fail(ctx, IFD_ERR_HIP, "ifd_object_attack: finish", e);
     return IFD_OK;
 }
 

@@ -373,6 +373,33 @@ hipError_t launch_cluster_step(const CwState& S, const float* grad, const int32_
                                float* cat, const int32_t* n_ori, float* last_input, float* info, const ClusterDiag& D, int t, float lr,
                                float scale, int B, int cat_stride, int num_add, int cl_num_p, hipStream_t s);
 
+// ---- the CW object-adding attack (pointnet_object.hip, include/ifd_object.h) ----
+struct ObjectState {                            // ifd_object_state, member for member
+    CwState cw;                                 // stride A = num_add * obj_num_p
+    float* obj;                                 // [B][A][3]
+    float *shift, *angle;                       // [B][num_add][3], [B][num_add]
+    float *shift_m, *shift_v;                   // [B][num_add][3]
+    float *angle_m, *angle_v;                   // [B][num_add]
+};
+struct ObjectDiag {                             // ifd_object_diag, member for member; every pointer may be null
+    float* obj_grad;                            // [B][A][3]
+    int32_t* nn_ori;                            // [B][A]
+    float *g_shift, *g_angle;                   // [B][num_add][3], [B][num_add]
+    float *l2, *cd;                             // [B]
+};
+// the limits on cat_stride, num_add * obj_num_p and (where n_ori is null) the counts are the caller's to check
+hipError_t launch_object_place(const float* obj, const float* angle, const float* shift, float* cat, const int32_t* n_ori, int B,
+                               int cat_stride, int num_add, int obj_num_p, hipStream_t s);
+// one iteration behind ifd_cls_input_grad on the concatenated cloud, a workgroup a cloud
+hipError_t launch_object_step(const ObjectState& S, const float* objects, const float* grad, const int32_t* pred, const float* loss,
+                              const int32_t* target, float* cat, const int32_t* n_ori, float* last_input, float* info,
+                              const ObjectDiag& D, int t, float lr, float scale, int B, int cat_stride, int num_add, int obj_num_p,
+                              hipStream_t s);
+// the start of a search step of ifd_object_attack: obj, shift, angle from the caller's arrays, the pose moments zeroed, the placement
+hipError_t launch_object_start(const ObjectState& S, const float* objects, const float* centers, const float* noise_obj,
+                               const float* noise_shift, const float* angles0, const int32_t* n_cat, int B, int out_stride, int num_add,
+                               int obj_num_p, float* pc_out, hipStream_t s);
+
 // ---- the saliency Drop attack (pointnet_drop.hip, include/ifd_drop.h) ----
 constexpr int DROP_MAX_POINTS = 2048;           // IFD_DROP_MAX_POINTS: a cloud, its saliencies, ranks and indices in a workgroup's LDS
 struct DropOut {                                // ifd_drop_out, member for member; every pointer may be null

@@ -286,6 +286,20 @@ struct ClusterStepLds {                              // cluster_step_kernel
 static_assert(ClusterStepLds::BYTES == 58368 && ClusterStepLds::BYTES <= 65536 && ADD_MAX_ADD % CLUSTER_THREADS == 0,
               "LDS of cluster_step_kernel");
 
+// ---- pointnet_object.hip: one cloud a workgroup of OBJECT_THREADS threads --------------------------------------------------------
+constexpr int OBJECT_THREADS = 256;
+struct ObjectStepLds {                               // object_step_kernel
+    static constexpr size_t O = 0;                                         // float [ADD_MAX_ORI][3] the originals
+    static constexpr size_t W = O + (size_t)ADD_MAX_ORI * 12;              // float [ADD_MAX_ADD][3] the forwarded world rows; behind
+                                                                           //   step 5 the new shifts [num_add][3]
+    static constexpr size_t G = W + (size_t)ADD_MAX_ADD * 12;              // float [ADD_MAX_ADD][4] row p: gw_x, gw_y, gw_z, ga
+    static constexpr size_t CS = G + (size_t)ADD_MAX_ADD * 16;             // float [ADD_MAX_ADD][2] object c: cos, sin of its angle
+    static constexpr size_t SH = CS + (size_t)ADD_MAX_ADD * 8;             // float [OBJECT_THREADS] the block sum's tree
+    static constexpr size_t BYTES = SH + (size_t)OBJECT_THREADS * 4;
+};
+static_assert(ObjectStepLds::BYTES == 62464 && ObjectStepLds::BYTES <= 65536 && ADD_MAX_ADD % OBJECT_THREADS == 0,
+              "LDS of object_step_kernel");
+
 // ---- block_sum / block_max / block_sum_d write one value per wave into their scratch ------------------------------------------
 static_assert((RepLds::BYTES - RepLds::SCRATCH) / 4 >= OPT_THREADS / 64 && (NrmLds::BYTES - NrmLds::SCRATCH) / 4 >= OPT_THREADS / 64,
               "8 waves: repulsion_kernel, normalize_kernel");

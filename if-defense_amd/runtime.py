@@ -1223,6 +1223,156 @@ class Classifier:
             return out, best, success.bool(), self._bounds(bounds)
         return out, best, success.bool()
 
+    # ---- include/ifd_object.h: the CW object-adding attack (models without feature_transform) ----
+    OBJECT_POSE = (("shift", 3), ("angle", 1), ("shift_m", 3), ("shift_v", 3), ("angle_m", 1), ("angle_v", 1))
+
+    def _object_rows(self, num_add, obj_num_p):
+        num_add, obj_num_p = int(num_add), int(obj_num_p)
+        if num_add < 1 or obj_num_p < 1 or not 1 <= num_add * obj_num_p <= _lib.ADD_MAX_ADD:
+            raise IfdError("num_add and obj_num_p must be at least 1 and num_add * obj_num_p in [1, %d]" % _lib.ADD_MAX_ADD)
+        return num_add, obj_num_p, num_add * obj_num_p
+
+    def _object_template(self, objects, num_add, obj_num_p):
+        objects = _f32(torch.as_tensor(objects), self.device)
+        if tuple(objects.shape) != (num_add, obj_num_p, 3):
+            raise IfdError("objects must be [num_add,obj_num_p,3]")
+        return objects
+
+    def object_state(self, B, num_add, obj_num_p, init_weight=5., max_weight=40.):
+        """The state of a fresh attack (ifd_object_state) as a dict of device tensors: ``cw_state(B, A, ...)`` - "m" and "v" belong to
+        the object rows, "o_bestattack" holds world rows - and "obj" [B,A,3], "shift" [B,num_add,3], "angle" [B,num_add] with the pose
+        moments "shift_m", "shift_v", "angle_m", "angle_v", all zero.  ``cw_adjust`` works on it as it is; the pose moments are the
+        caller's to zero at the start of a search step."""
+        num_add, obj_num_p, A = self._object_rows(num_add, obj_num_p)
+        state = self.cw_state(B, A, init_weight, max_weight)
+        state["obj"] = torch.zeros(B, A, 3, device=self.device, dtype=torch.float32)
+        for key, width in self.OBJECT_POSE:
+            state[key] = torch.zeros((B, num_add, 3) if width == 3 else (B, num_add), device=self.device, dtype=torch.float32)
+        return state
+
+    def _object_struct(self, state, B, num_add, A):
+        ptrs = [self._cw_cloud(state.get("obj"), B, A, "object state 'obj'")]
+        if ptrs[0] is None:
+            raise IfdError("object state 'obj' is missing")
+        for key, width in self.OBJECT_POSE:
+            t = state.get(key)
+            want = (B, num_add, 3) if width == 3 else (B, num_add)
+            if t is None or not (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and tuple(t.shape) == want):
+                raise IfdError("object state %r must be a contiguous float32 device tensor of shape %s" % (key, want))
+            ptrs.append(t.data_ptr())
+        return _lib.IfdObjectState(self._cw_struct(state, B, A), *ptrs)
+
+    def object_place(self, obj, angle, shift, cat, num_add, obj_num_p, n_ori=None):
+        """world = rotate_shift(obj, angle, shift) (ifd_object_place) IN PLACE into the added rows of ``cat`` [B,N,3]: obj [B,A,3],
+        angle [B,num_add] about the y axis, shift [B,num_add,3]; cloud b has n_ori[b] originals (None: N - A) in front of its A =
+        num_add * obj_num_p added rows.  Returns ``cat``."""
+        num_add, obj_num_p, A = self._object_rows(num_add, obj_num_p)
+        if not torch.is_tensor(cat) or cat.dim() != 3:
+            raise IfdError("cat must be a contiguous float32 [B,N,3] device tensor")
+        B, stride = int(cat.shape[0]), int(cat.shape[1])
+        self._cw_cloud(cat, B, stride, "cat")
+        obj = _f32(torch.as_tensor(obj), self.device)
+        angle = _f32(torch.as_tensor(angle), self.device)
+        shift = _f32(torch.as_tensor(shift), self.device)
+        if tuple(obj.shape) != (B, A, 3) or tuple(angle.shape) != (B, num_add) or tuple(shift.shape) != (B, num_add, 3):
+            raise IfdError("obj must be [B,num_add*obj_num_p,3], angle [B,num_add] and shift [B,num_add,3]")
+        n_ori = self._counts(n_ori, B)
+        with torch.cuda.device(self.device):
+            self._check(self.lib.ifd_object_place(self.ctx, obj.data_ptr(), angle.data_ptr(), shift.data_ptr(), cat.data_ptr(),
+                                                  None if n_ori is None else n_ori.data_ptr(), B, stride, num_add, obj_num_p,
+                                                  self._stream()))
+        return cat
+
+    def object_step(self, state, objects, grad, pred, target, cat, num_add, obj_num_p, t, lr, scale=1., loss=None, last_input=None,
+                    n_ori=None, want_info: bool = False, want=()):
+        """One iteration of the object-adding attack behind ``input_grad`` on the concatenated clouds (ifd_object_step), IN PLACE on
+        ``state`` (``object_state``) and on the added rows of ``cat`` [B,N,3], which must hold the placement of the state when called
+        and hold the placement of the new state afterwards.  objects [num_add,obj_num_p,3]: the template shared by the batch.  grad,
+        pred, loss, last_input [B,A,3]: as ``add_step`` takes them.  Returns a dict: with want_info "info" [B,3] (adversarial loss,
+        dist * weight, dist), and the diagnostics named in ``want``: "obj_grad" [B,A,3], "nn_ori" [B,A] int32, "g_shift" [B,num_add,3],
+        "g_angle" [B,num_add], "l2" [B], "cd" [B] (clouds outside the limits are left as allocated: NaN / -1)."""
+        num_add, obj_num_p, A = self._object_rows(num_add, obj_num_p)
+        if not torch.is_tensor(cat) or cat.dim() != 3:
+            raise IfdError("cat must be a contiguous float32 [B,N,3] device tensor")
+        B, stride = int(cat.shape[0]), int(cat.shape[1])
+        st = self._object_struct(state, B, num_add, A)
+        objects = self._object_template(objects, num_add, obj_num_p)
+        ptrs = [self._cw_cloud(x, B, stride, n) for x, n in ((grad, "grad"), (cat, "cat"))]
+        if grad is None:
+            raise IfdError("grad is missing")
+        li = self._cw_cloud(last_input, B, A, "last_input")
+        pred = self._vec(pred, B, torch.int32, "pred")
+        target = self._target(target, B)
+        loss = self._vec(loss, B, torch.float32, "loss")
+        n_ori = self._counts(n_ori, B)
+        names = ("obj_grad", "nn_ori", "g_shift", "g_angle", "l2", "cd")
+        shapes = {"obj_grad": ((B, A, 3), torch.float32), "nn_ori": ((B, A), torch.int32), "g_shift": ((B, num_add, 3), torch.float32),
+                  "g_angle": ((B, num_add), torch.float32), "l2": ((B,), torch.float32), "cd": ((B,), torch.float32)}
+        out = self._diag(want, shapes, " | ".join(names))
+        ptr = lambda x: None if x is None else x.data_ptr()        # noqa: E731
+        diag = _lib.IfdObjectDiag(*[ptr(out.get(k)) for k in names])
+        info = torch.empty(B, 3, device=self.device, dtype=torch.float32) if want_info else None
+        with torch.cuda.device(self.device):
+            self._check(self.lib.ifd_object_step(self.ctx, C.byref(st), objects.data_ptr(), ptrs[0], pred.data_ptr(), ptr(loss),
+                                                 target.data_ptr(), ptrs[1], ptr(n_ori), li, ptr(info), C.byref(diag) if out else None,
+                                                 int(t), float(lr), float(scale), B, stride, num_add, obj_num_p, self._stream()))
+        if want_info:
+            out["info"] = info
+        return out
+
+    def object_attack(self, pc, target, objects, centers, angles0, noise_obj=None, noise_shift=None, loss="logits", kappa=0., scale=1.,
+                      attack_lr=1e-2, init_weight=5., max_weight=40., binary_step=5, num_iter=500, n_points=None, out_stride=None,
+                      want_bounds: bool = False):
+        """The whole CW object-adding attack on the device (ifd_object_attack): objects [num_add,obj_num_p,3] the template, centers
+        [B,num_add,3] the start shifts, angles0 [binary_step,B,num_add] the start angles of every search step, noise_obj
+        [binary_step,B,A,3] and noise_shift [binary_step,B,num_add,3] the start noise or None.  -> (clouds [B,out_stride,3]: each
+        cloud's originals bit for bit, then its A = num_add * obj_num_p added points; best_dist [B] (1e10 where no iteration reached
+        the target); success [B] bool) and with want_bounds also {"weight", "lower", "upper"} [B] float64.  out_stride: rows of the
+        output, default N + A."""
+        objects = _f32(torch.as_tensor(objects), self.device)
+        if objects.dim() != 3 or int(objects.shape[2]) != 3:
+            raise IfdError("objects must be [num_add,obj_num_p,3]")
+        num_add, obj_num_p, A = self._object_rows(objects.shape[0], objects.shape[1])
+        loss_kind = self._loss_kind(loss)
+        pc, n_points = self._batch(pc, n_points)
+        B, stride = int(pc.shape[0]), int(pc.shape[1])
+        if B < 1 or stride < 1:
+            raise IfdError("empty batch")
+        target = self._target(target, B)
+        steps = int(binary_step)
+
+        def arr(x, shape, what):
+            if x is None:
+                return None
+            x = _f32(torch.as_tensor(x), self.device)
+            if tuple(x.shape) != shape:
+                raise IfdError("%s must be %s" % (what, list(shape)))
+            return x
+        centers = arr(centers, (B, num_add, 3), "centers")
+        angles0 = arr(angles0, (steps, B, num_add), "angles0")
+        if centers is None or angles0 is None:
+            raise IfdError("centers and angles0 are needed")
+        noise_obj = arr(noise_obj, (steps, B, A, 3), "noise_obj")
+        noise_shift = arr(noise_shift, (steps, B, num_add, 3), "noise_shift")
+        out_stride = stride + A if out_stride is None else int(out_stride)
+        if out_stride < 1:
+            raise IfdError("out_stride must be positive")
+        out = torch.zeros(B, out_stride, 3, device=self.device, dtype=torch.float32)
+        best = torch.empty(B, device=self.device, dtype=torch.float32)
+        success = torch.empty(B, device=self.device, dtype=torch.int32)
+        bounds = torch.empty(3, B, device=self.device, dtype=torch.float64) if want_bounds else None
+        P = _lib.IfdObjectParams(C.sizeof(_lib.IfdObjectParams), loss_kind, steps, int(num_iter), num_add, obj_num_p, float(kappa),
+                                 float(scale), float(attack_lr), float(init_weight), float(max_weight))
+        ptr = lambda x: None if x is None else x.data_ptr()        # noqa: E731
+        with torch.cuda.device(self.device):
+            self._check(self.lib.ifd_object_attack(self.ctx, C.byref(P), pc.data_ptr(), ptr(n_points), target.data_ptr(),
+                                                   objects.data_ptr(), centers.data_ptr(), ptr(noise_obj), ptr(noise_shift),
+                                                   angles0.data_ptr(), B, stride, out_stride, out.data_ptr(), best.data_ptr(),
+                                                   success.data_ptr(), ptr(bounds), self._stream()))
+        if want_bounds:
+            return out, best, success.bool(), self._bounds(bounds)
+        return out, best, success.bool()
+
     # ---- include/ifd_drop.h: the saliency Drop attack (models without feature_transform) ----
     def drop_step(self, grad, pc, n_points, k, alpha=1., index=None, want=()):
         """One round of the Drop attack behind ``input_grad`` (ifd_drop_step), IN PLACE on ``pc`` [B,N,3] float32, ``n_points`` [B]
