@@ -310,6 +310,23 @@ OBJECT_SIGNATURES = {
                                     C.c_void_p, C.c_void_p]),
 }
 
+# include/ifd_dgcnn.h (the DGCNN victim classifier), versioned on its own
+DGCNN_ABI_VERSION = 1
+DGCNN_MAX_POINTS, DGCNN_MAX_K = 2048, 32
+
+
+class IfdDgcnnAux(C.Structure):
+    _fields_ = [("idx", C.c_void_p * 4), ("feat", C.c_void_p), ("global_feat", C.c_void_p), ("pred", C.c_void_p)]
+
+
+DGCNN_SIGNATURES = {
+    "ifd_dgcnn_abi_version": (C.c_int, []),
+    "ifd_dgcnn_weight_count": (C.c_size_t, []),
+    "ifd_dgcnn_create": (C.c_void_p, [C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_int]),
+    "ifd_dgcnn_forward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.POINTER(IfdDgcnnAux),
+                                    C.c_void_p]),
+}
+
 _lib = None
 
 
@@ -326,7 +343,8 @@ def load() -> C.CDLL:
     lib = C.CDLL(LIB_PATH, mode=C.RTLD_GLOBAL)
     for name, (res, args) in list(SIGNATURES.items()) + list(DUP_SIGNATURES.items()) + list(CLS_SIGNATURES.items()) + \
             list(ATK_SIGNATURES.items()) + list(CW_SIGNATURES.items()) + list(KNN_SIGNATURES.items()) + list(ADD_SIGNATURES.items()) + \
-            list(DROP_SIGNATURES.items()) + list(CLUSTER_SIGNATURES.items()) + list(OBJECT_SIGNATURES.items()):
+            list(DROP_SIGNATURES.items()) + list(CLUSTER_SIGNATURES.items()) + list(OBJECT_SIGNATURES.items()) + \
+            list(DGCNN_SIGNATURES.items()):
         fn = getattr(lib, name)          # AttributeError if the library lacks a declared symbol
         fn.restype, fn.argtypes = res, args
     if lib.ifd_abi_version() != ABI_VERSION:
@@ -349,5 +367,7 @@ def load() -> C.CDLL:
         raise ImportError("libifd.so CLUSTER ABI %d != binding CLUSTER ABI %d; rebuild" % (lib.ifd_cluster_abi_version(), CLUSTER_ABI_VERSION))
     if lib.ifd_object_abi_version() != OBJECT_ABI_VERSION:
         raise ImportError("libifd.so OBJECT ABI %d != binding OBJECT ABI %d; rebuild" % (lib.ifd_object_abi_version(), OBJECT_ABI_VERSION))
+    if lib.ifd_dgcnn_abi_version() != DGCNN_ABI_VERSION:
+        raise ImportError("libifd.so DGCNN ABI %d != binding DGCNN ABI %d; rebuild" % (lib.ifd_dgcnn_abi_version(), DGCNN_ABI_VERSION))
     _lib = lib
     return lib

@@ -14,6 +14,7 @@
 #include "../../include/ifd_drop.h"
 #include "../../include/ifd_cluster.h"
 #include "../../include/ifd_object.h"
+#include "../../include/ifd_dgcnn.h"
 
 #include <hip/hip_runtime.h>
 
@@ -149,6 +150,10 @@ struct ifd_ctx {
     // ... and the backward pass's weight image (include/ifd_atk.h; contexts without feature_transform only)
     DeviceBuffer d_cls_grad;
     ClsGradImage gimg{};
+    // DGCNN victim (ifd_dgcnn_create): the split-form weight image (dgcnn.hip); its scratch is `ws`
+    DeviceBuffer d_dgcnn;
+    DgImage dimg{};
+    int dg_k = 0;
     std::string err;
     unsigned long long* counters() const { return d_counters.get<unsigned long long>(); }
 };
@@ -1665,6 +1670,162 @@ extern "C" {
 int ifd_cls_forward(ifd_ctx* ctx, const float* pc, const int32_t* n_points, int B, int stride, float* logits,
                     const ifd_cls_aux* aux, void* stream) {
     return cls_forward_impl(ctx, pc, n_points, B, stride, logits, aux, stream, true, 0);
+}
+
+}  // extern "C"
+
+// ---- DGCNN victim classifier (include/ifd_dgcnn.h) -------------------------------------------------------------------
+namespace {
+
+constexpr int DG_CHUNK = 128;                // most clouds per chunk of ifd_dgcnn_forward
+static_assert(DG_MAX_POINTS == IFD_DGCNN_MAX_POINTS && DG_MAX_K == IFD_DGCNN_MAX_K, "ifd_dgcnn.h and ifd_internal.h");
+
+// the canonical order: conv1 .. conv5, linear1 .. linear3
+const ClsTensor DG_LAYERS[8] = {{64, 6}, {64, 128}, {128, 128}, {256, 256}, {DG_EMB, DG_FEAT}, {512, 2 * DG_EMB}, {256, 512}, {CLS_CLASSES, 256}};
+
+size_t dgcnn_count() {
+    size_t n = 0;
+    for (const ClsTensor& t : DG_LAYERS) n += (size_t)t.out * t.in + t.out;
+    return n;
+}
+
+// The device image (ifd_internal.h DgImage): the edge convolutions in split form - rows P = Wa, then Q = Wb - Wa (rounded to
+// f32 once, here) with the bias - everything else row-major as it comes.
+std::vector<float> build_dgcnn_image(const float* w, DgImage& I) {
+    std::vector<float> img;
+    size_t at[8], src = 0;
+    for (int k = 0; k < 8; ++k) { at[k] = src; src += (size_t)DG_LAYERS[k].out * DG_LAYERS[k].in + DG_LAYERS[k].out; }
+    {
+        const float* W = w + at[0];
+        I.first = (int)img.size();
+        img.resize(img.size() + 128 * 4, 0.f);
+        for (int o = 0; o < 64; ++o)
+            for (int a = 0; a < 3; ++a) {
+                img[I.first + o * 4 + a] = W[o * 6 + a];
+                img[I.first + (64 + o) * 4 + a] = W[o * 6 + 3 + a] - W[o * 6 + a];
+            }
+        for (int o = 0; o < 64; ++o) img[I.first + (64 + o) * 4 + 3] = W[64 * 6 + o];
+    }
+    for (int l = 0; l < 3; ++l) {
+        const int co = DG_LAYERS[l + 1].out, C = DG_LAYERS[l + 1].in / 2;
+        const float* W = w + at[l + 1];
+        DgLayer& L = I.pq[l];
+        L.n_out = 2 * co; L.n_in = C;
+        L.w = (int)img.size();
+        img.resize(img.size() + (size_t)2 * co * C);
+        for (int o = 0; o < co; ++o)
+            for (int c = 0; c < C; ++c) {
+                img[L.w + (size_t)o * C + c] = W[(size_t)o * 2 * C + c];
+                img[L.w + (size_t)(co + o) * C + c] = W[(size_t)o * 2 * C + C + c] - W[(size_t)o * 2 * C + c];
+            }
+        L.b = (int)img.size();
+        img.resize(img.size() + 2 * co, 0.f);
+        for (int o = 0; o < co; ++o) img[L.b + co + o] = W[(size_t)co * 2 * C + o];
+    }
+    auto plain = [&](int k) {
+        const ClsTensor& t = DG_LAYERS[k];
+        DgLayer L;
+        L.n_out = t.out; L.n_in = t.in;
+        L.w = (int)img.size();
+        img.insert(img.end(), w + at[k], w + at[k] + (size_t)t.out * t.in);
+        L.b = (int)img.size();
+        img.insert(img.end(), w + at[k] + (size_t)t.out * t.in, w + at[k] + (size_t)t.out * t.in + t.out);
+        return L;
+    };
+    I.conv5 = plain(4);
+    for (int j = 0; j < 3; ++j) I.fc[j] = plain(5 + j);
+    I.total = (int)img.size();
+    return img;
+}
+
+// the workspace of ifd_dgcnn_forward over n clouds: 1024 bytes of which the check of the counts uses the first word, then launch_dgcnn's scratch
+DgWs dgcnn_ws(Carve& c, size_t n, int stride, int k) {
+    const size_t T = (size_t)(stride + DG_TILE - 1) / DG_TILE, s = (size_t)stride;
+    c.take<int32_t>(1024);
+    DgWs w;
+    w.feat = c.take<float>(n * s * DG_FEAT * 4); w.pq = c.take<float>(n * s * DG_FEAT * 4);
+    w.nrm = c.take<float>(n * s * 4); w.idx = c.take<int32_t>(n * s * k * 4);
+    w.part_max = c.take<float>(n * T * DG_EMB * 4); w.part_sum = c.take<float>(n * T * DG_EMB * 4);
+    w.gfeat = c.take<float>(n * 2 * DG_EMB * 4); w.f1 = c.take<float>(n * 512 * 4); w.f2 = c.take<float>(n * 256 * 4);
+    return w;
+}
+size_t dgcnn_ws_bytes(int n, int stride, int k) { return carved_bytes([&](Carve& c) { dgcnn_ws(c, (size_t)n, stride, k); }); }
+
+}  // namespace
+
+extern "C" {
+
+int ifd_dgcnn_abi_version(void) { return IFD_DGCNN_ABI_VERSION; }
+
+size_t ifd_dgcnn_weight_count(void) { return dgcnn_count(); }
+
+ifd_ctx* ifd_dgcnn_create(const float* weights_host, size_t n_weights, int k, int n_classes, int device) {
+    if (k < 1 || k > IFD_DGCNN_MAX_K) {
+        g_create_error = "ifd_dgcnn_create: k must lie in [1, 32], got " + std::to_string(k);
+        return nullptr;
+    }
+    if (n_classes != CLS_CLASSES) {
+        g_create_error = "ifd_dgcnn_create: only n_classes = 40 (ModelNet40) is built, got " + std::to_string(n_classes);
+        return nullptr;
+    }
+    if (!weights_host || n_weights != dgcnn_count()) {
+        g_create_error = "ifd_dgcnn_create: expected " + std::to_string(dgcnn_count()) + " weights, got " +
+                         (weights_host ? std::to_string(n_weights) : std::string("NULL"));
+        return nullptr;
+    }
+    return create_ctx("ifd_dgcnn_create", IFD_MODEL_DGCNN, device, [&](ifd_ctx* ctx) {
+        ctx->dg_k = k;
+        ctx->cls_classes = n_classes;
+        return upload(ctx->d_dgcnn, build_dgcnn_image(weights_host, ctx->dimg));
+    });
+}
+
+int ifd_dgcnn_forward(ifd_ctx* ctx, const float* pc, const int32_t* n_points, int B, int stride, float* logits,
+                      const ifd_dgcnn_aux* aux, void* stream) {
+    if (!ctx) return IFD_ERR_ARG;
+    if (ctx->model != IFD_MODEL_DGCNN || !ctx->d_dgcnn.get()) return fail(ctx, IFD_ERR_ARG, "ifd_dgcnn_forward: not a DGCNN context");
+    const int k = ctx->dg_k;
+    if (!pc || !logits || B < 1) return fail(ctx, IFD_ERR_ARG, "ifd_dgcnn_forward: bad argument (pc, logits, B >= 1)");
+    if (stride > IFD_DGCNN_MAX_POINTS) return fail(ctx, IFD_ERR_ARG, "ifd_dgcnn_forward: stride above 2048");
+    if (stride < k) {
+        const std::string msg = "ifd_dgcnn_forward: clouds of " + std::to_string(stride) + " points, fewer than k = " + std::to_string(k);
+        return fail(ctx, IFD_ERR_ARG, msg.c_str());
+    }
+    IFD_ON_CTX_DEVICE(ctx);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const int n_chunks = (B + DG_CHUNK - 1) / DG_CHUNK, chunk = (B + n_chunks - 1) / n_chunks;
+    hipError_t e = ctx->ws.grow(dgcnn_ws_bytes(chunk, stride, k));
+    if (e != hipSuccess) return fail(ctx, IFD_ERR_NOMEM, "ifd_dgcnn_forward: workspace", e);
+    char* base = ctx->ws.get<char>();
+    if (n_points) {                       // the one blocking step: the counts are device memory
+        int32_t bad = 0;
+        e = launch_dgcnn_check(n_points, B, stride, k, reinterpret_cast<int32_t*>(base), s);
+        if (e == hipSuccess) e = hipMemcpyAsync(&bad, base, sizeof(bad), hipMemcpyDeviceToHost, s);
+        if (e == hipSuccess) e = hipStreamSynchronize(s);
+        if (e != hipSuccess) return fail(ctx, IFD_ERR_HIP, "ifd_dgcnn_forward: checking n_points", e);
+        if (bad != 0) {
+            const std::string msg = "ifd_dgcnn_forward: " + std::to_string(bad) + " cloud(s) with n_points outside [k, stride] (k = " +
+                                    std::to_string(k) + ": a cloud needs at least k points)";
+            return fail(ctx, IFD_ERR_ARG, msg.c_str());
+        }
+    }
+    const int nc = ctx->cls_classes;
+    for (int c0 = 0; c0 < B; c0 += chunk) {
+        const int n = std::min(chunk, B - c0);
+        Carve c(base);
+        const DgWs w = dgcnn_ws(c, (size_t)n, stride, k);
+        DgOut o{};
+        if (aux) {
+            for (int l = 0; l < 4; ++l) o.idx[l] = aux->idx[l] ? aux->idx[l] + (size_t)c0 * stride * k : nullptr;
+            o.feat = aux->feat ? aux->feat + (size_t)c0 * stride * DG_FEAT : nullptr;
+            o.gfeat = aux->global_feat ? aux->global_feat + (size_t)c0 * 2 * DG_EMB : nullptr;
+            o.pred = aux->pred ? aux->pred + c0 : nullptr;
+        }
+        e = launch_dgcnn(ctx->d_dgcnn.get<float>(), ctx->dimg, pc + (size_t)c0 * stride * 3, n_points ? n_points + c0 : nullptr, n, stride,
+                         k, w, o, logits + (size_t)c0 * nc, nc, s);
+        if (e != hipSuccess) return fail(ctx, IFD_ERR_HIP, "ifd_dgcnn_forward launch", e);
+    }
+    return IFD_OK;
 }
 
 }  // extern "C"

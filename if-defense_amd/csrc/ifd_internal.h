@@ -413,4 +413,44 @@ hipError_t launch_drop_step(const float* grad, float* pc, int32_t* n_points, int
 // n_out[b] = n_points[b] (stride where n_points is null); kept[b][i] = i below that count, -1 beyond (kept may be null)
 hipError_t launch_drop_begin(const int32_t* n_points, int B, int stride, int32_t* n_out, int32_t* kept, hipStream_t s);
 
+// ---- victim classifier: DGCNN (dgcnn.hip; C ABI in include/ifd_dgcnn.h) ----------------------------------------------
+constexpr int DG_MAX_POINTS = 2048;     // IFD_DGCNN_MAX_POINTS
+constexpr int DG_MAX_K = 32;
+constexpr int DG_FEAT = 512;            // x1 | x2 | x3 | x4 = 64 + 64 + 128 + 256 channels of a point
+constexpr int DG_EMB = 1024;            // conv5's width; the global feature is max | mean = 2 DG_EMB
+constexpr int DG_TILE = 64;             // points of one workgroup of the MFMA layers, and of one partial max / sum of conv5
+constexpr int DG_KNN_THREADS = 64;      // queries of one workgroup of the kNN kernel, a thread each
+constexpr int DG_KNN_PEND = 8;          // candidates a thread queues before the wave updates its lists together
+struct DgLayer { int w, b, n_out, n_in; };     // float offsets into the device image: weight row-major [n_out][n_in], bias [n_out]
+// The device image (api.cpp build_dgcnn_image).  The four edge convolutions are stored in split form: per layer the rows
+// P = Wa (no bias) then Q = Wb - Wa (the folded bias), n_out = 2 Cout, n_in = C.  first: the C = 3 layer as [128][4] rows
+// {w0, w1, w2, bias}.
+struct DgImage {
+    int first;
+    DgLayer pq[3];                      // conv2, conv3, conv4
+    DgLayer conv5, fc[3];
+    int total;
+};
+struct DgWs {                           // per-chunk scratch of launch_dgcnn (api.cpp dgcnn_ws)
+    float* feat;        // [B][stride][512]
+    float* pq;          // [B][stride][512]   P | Q of the current layer (2 Cout <= 512 columns used)
+    float* nrm;         // [B][stride]        |x_j|^2 of the current layer's input
+    int32_t* idx;       // [B][stride][k]
+    float* part_max;    // [B][T][1024], T = ceil(stride / DG_TILE)
+    float* part_sum;    // [B][T][1024]
+    float* gfeat;       // [B][2048]
+    float* f1;          // [B][512]
+    float* f2;          // [B][256]
+};
+struct DgOut {                          // where the caller wants the intermediate results; a null member stays in the scratch
+    int32_t* idx[4];
+    float* feat;
+    float* gfeat;
+    int32_t* pred;
+};
+// bad[0] = number of clouds with n_points outside [k, stride]
+hipError_t launch_dgcnn_check(const int32_t* n_points, int B, int stride, int k, int32_t* bad, hipStream_t s);
+hipError_t launch_dgcnn(const float* img, const DgImage& I, const float* pc, const int32_t* n_points, int B, int stride, int k,
+                        const DgWs& w, const DgOut& out, float* logits, int n_classes, hipStream_t s);
+
 }  // namespace ifd

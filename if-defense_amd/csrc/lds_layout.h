@@ -300,6 +300,26 @@ struct ObjectStepLds {                               // object_step_kernel
 static_assert(ObjectStepLds::BYTES == 62464 && ObjectStepLds::BYTES <= 65536 && ADD_MAX_ADD % OBJECT_THREADS == 0,
               "LDS of object_step_kernel");
 
+// ---- dgcnn.hip ----------------------------------------------------------------------------------------------------------------
+// dg_knn_kernel: every thread's list of its query's k best (score, index) pairs, entry-major so that the threads of a wave hit 64
+// consecutive words
+struct DgKnnLdsAt { int SC, IX, PS, PI, BYTES; };
+__host__ __device__ constexpr DgKnnLdsAt dg_knn_lds_at(int k) {
+    DgKnnLdsAt l{};
+    l.SC = 0;                                                              // float [k][DG_KNN_THREADS]
+    l.IX = l.SC + k * DG_KNN_THREADS * 4;                                  // int [k][DG_KNN_THREADS]
+    l.PS = l.IX + k * DG_KNN_THREADS * 4;                                  // float [DG_KNN_PEND][DG_KNN_THREADS] queued candidates
+    l.PI = l.PS + DG_KNN_PEND * DG_KNN_THREADS * 4;                        // int [DG_KNN_PEND][DG_KNN_THREADS]
+    l.BYTES = l.PI + DG_KNN_PEND * DG_KNN_THREADS * 4;
+    return l;
+}
+static_assert(dg_knn_lds_at(DG_MAX_K).BYTES == 20480, "LDS of dg_knn_kernel");
+struct DgPoolLds {                                   // dg_linear_kernel<true>: the two row halves' maxima and sums of 64 channels
+    static constexpr size_t MAX = 0;                                       // float [2][64]
+    static constexpr size_t SUM = MAX + 2 * 64 * 4;                        // float [2][64]
+    static constexpr size_t BYTES = SUM + 2 * 64 * 4;
+};
+
 // ---- block_sum / block_max / block_sum_d write one value per wave into their scratch ------------------------------------------
 static_assert((RepLds::BYTES - RepLds::SCRATCH) / 4 >= OPT_THREADS / 64 && (NrmLds::BYTES - NrmLds::SCRATCH) / 4 >= OPT_THREADS / 64,
               "8 waves: repulsion_kernel, normalize_kernel");

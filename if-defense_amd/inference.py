@@ -4,8 +4,8 @@ Same flags, rules and printed lines as the reference CLI (baselines/inference.py
 
     python -m ifdefense_amd.inference --data_root=path/to/file.npz --mode=target --model=pointnet --model_path=pointnet.pth
 
-Only the PointNet victim is built; --model pointnet2 | dgcnn | pointconv (or a path that names one of them) is refused with
-a message and a non-zero status.  --model_path: the victim checkpoint (.pth saved from nn.DataParallel, or an .npz of its
+Only the PointNet victim runs here; --model pointnet2 | dgcnn | pointconv (or a path that names one of them) is refused with
+a message and a non-zero status (DGCNN has a CLI of its own, ifdefense_amd.dgcnn_inference).  --model_path: the victim checkpoint (.pth saved from nn.DataParallel, or an .npz of its
 arrays); empty means BEST_WEIGHTS[dataset][1024][model] of baselines/config.py, relative to the working directory.
 
 Differences from the reference: the whole file runs through the classifier in one call (PointNet has no cross-cloud
@@ -116,6 +116,16 @@ def evaluate_npz(path: str, classifier, mode: str = 'normal', num_points: int = 
     return out
 
 
+def print_result(mode: str, r: dict) -> None:
+    """The reference's closing line (baselines/inference.py:198-205) for evaluate_npz's result."""
+    if mode == 'normal':
+        print('Overall accuracy: {:.4f}'.format(r["accuracy"]))
+    else:
+        print('Overall accuracy: {:.4f}, '
+              'attack success rate: {:.4f}'.
+              format(r["accuracy"], r["success_rate"]))
+
+
 def main(argv=None, make_classifier=None) -> int:
     args = build_parser().parse_args(argv)
     if not args.model:
@@ -124,8 +134,10 @@ def main(argv=None, make_classifier=None) -> int:
             print('Victim model not recognized!', file=sys.stderr)
             return 2
     if args.model.lower() != 'pointnet':
-        print("inference: the {} victim is not built here (only pointnet is); evaluate it with the reference's "
-              "baselines/inference.py".format(args.model), file=sys.stderr)
+        where = ("`python -m ifdefense_amd.dgcnn_inference`" if args.model.lower() == 'dgcnn'
+                 else "the reference's baselines/inference.py")
+        print("inference: the {} victim is not built here (only pointnet is); evaluate it with {}".format(args.model, where),
+              file=sys.stderr)
         return 2
     num_points = points_to_take(args.data_root, args.num_points)
     if make_classifier is None:
@@ -143,12 +155,7 @@ def main(argv=None, make_classifier=None) -> int:
     finally:
         if hasattr(classifier, "close"):
             classifier.close()
-    if args.mode == 'normal':
-        print('Overall accuracy: {:.4f}'.format(r["accuracy"]))
-    else:
-        print('Overall accuracy: {:.4f}, '
-              'attack success rate: {:.4f}'.
-              format(r["accuracy"], r["success_rate"]))
+    print_result(args.mode, r)
     return 0
 
 

@@ -1424,3 +1424,58 @@ class Classifier:
         if want_kept:
             return out[:, :m].contiguous(), correct.bool(), kept[:, :m].contiguous()
         return out[:, :m].contiguous(), correct.bool()
+
+
+class DgcnnClassifier(Classifier):
+    """The DGCNN victim of the reference on one GPU (include/ifd_dgcnn.h): DGCNN(emb_dims=1024, k, output_channels=40) in eval
+    mode.  ``weights``: the BN-folded canonical vector (``weights.load_checkpoint(path, "dgcnn")`` or
+    ``weights.pack_state_dict(state_dict, "dgcnn")``).  Inputs are Classifier's: [B,N,3] batches (point-major), lists and
+    object arrays of ragged clouds; every cloud needs at least k points and at most 2048.  A cloud's outputs do not depend on
+    how it is batched or padded.  The attack entry points of Classifier are PointNet's and are not offered here."""
+
+    MAX_POINTS = _lib.DGCNN_MAX_POINTS
+
+    def __init__(self, weights: np.ndarray, k: int = 20, device=None):
+        self.lib = _lib.load()
+        self.feature_transform = False
+        self.k = int(k)
+        if not 1 <= self.k <= _lib.DGCNN_MAX_K:
+            raise IfdError("k must lie in [1, %d], got %d" % (_lib.DGCNN_MAX_K, self.k))
+        w = np.ascontiguousarray(weights, dtype=np.float32)
+        want = self.lib.ifd_dgcnn_weight_count()
+        if w.size != want:
+            raise IfdError("expected %d dgcnn weights, got %d" % (want, w.size))
+        if not torch.cuda.is_available():
+            raise IfdError("no GPU visible: the classifier only runs on an MI355X (no CPU fallback)")
+        self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+        with torch.cuda.device(self.device):
+            self.ctx = self.lib.ifd_dgcnn_create(w.ctypes.data, w.size, self.k, self.N_CLASSES, self.device.index or 0)
+        if not self.ctx:
+            raise IfdError((self.lib.ifd_last_error(None) or b"ifd_dgcnn_create failed").decode())
+
+    def logits(self, pc, n_points=None, want_aux: bool = False, want_pred: bool = False):
+        """pc, n_points: as Classifier.logits.  Returns logits [B,40]; with want_aux also {"idx": four [B,N,k] int32 (the
+        neighbours each edge convolution chose; rows beyond a cloud's count are -1), "feat" [B,N,512] (x1|x2|x3|x4; zero
+        beyond a cloud's count), "global_feat" [B,2048] (max | mean of conv5), "pred" [B] int32}."""
+        pc, n_points = self._batch(pc, n_points)
+        B, stride = int(pc.shape[0]), int(pc.shape[1])
+        if B < 1 or stride < 1:
+            raise IfdError("empty batch")
+        out = torch.empty(B, self.N_CLASSES, device=self.device, dtype=torch.float32)
+        aux, st = None, None
+        if want_aux or want_pred:
+            aux = {"pred": torch.empty(B, device=self.device, dtype=torch.int32)}
+            a = _lib.IfdDgcnnAux()
+            a.pred = aux["pred"].data_ptr()
+            if want_aux:
+                aux["idx"] = [torch.full((B, stride, self.k), -1, device=self.device, dtype=torch.int32) for _ in range(4)]
+                aux["feat"] = torch.zeros(B, stride, 512, device=self.device, dtype=torch.float32)
+                aux["global_feat"] = torch.empty(B, 2048, device=self.device, dtype=torch.float32)
+                for i in range(4):
+                    a.idx[i] = aux["idx"][i].data_ptr()
+                a.feat, a.global_feat = aux["feat"].data_ptr(), aux["global_feat"].data_ptr()
+            st = C.byref(a)
+        with torch.cuda.device(self.device):
+            self._check(self.lib.ifd_dgcnn_forward(self.ctx, pc.data_ptr(), None if n_points is None else n_points.data_ptr(),
+                                                   B, stride, out.data_ptr(), st, torch.cuda.current_stream(self.device).cuda_stream))
+        return (out, aux) if aux is not None else out

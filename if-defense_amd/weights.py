@@ -172,6 +172,8 @@ def pack_pointnet(state: Dict[str, object], feature_transform=None) -> np.ndarra
 def _keys(model: str):
     if model == "pointnet":
         return pointnet_canonical_keys(False)
+    if model == "dgcnn":
+        return dgcnn_canonical_keys()
     if model == "onet":
         return onet_canonical_keys()
     if model == "punet":
@@ -185,6 +187,8 @@ def pack_state_dict(state: Dict[str, object], model: str = "convonet", feature_t
     folded on the way (pack_pointnet); feature_transform None means judged from the keys."""
     if model == "pointnet":
         return pack_pointnet(state, feature_transform)
+    if model == "dgcnn":
+        return pack_dgcnn(state)
     parts = []
     for name, shape in _keys(model):
         if name not in state:
@@ -207,6 +211,13 @@ def load_checkpoint(path: str, model: str = "convonet", feature_transform=None) 
                 return pack_pointnet({n: z[n] for n in z.files}, feature_transform)
         import torch
         return pack_pointnet(torch.load(path, map_location="cpu", weights_only=True), feature_transform)
+    if model == "dgcnn":
+        # pretrain/<dataset>/dgcnn.pth (saved from nn.DataParallel) or an .npz of its arrays
+        if path.endswith(".npz"):
+            with np.load(path, allow_pickle=False) as z:
+                return pack_dgcnn({n: z[n] for n in z.files})
+        import torch
+        return pack_dgcnn(torch.load(path, map_location="cpu", weights_only=True))
     if model == "punet":
         # pu-in_1024-up_4.pth (baselines/config.py PU_NET_WEIGHT) or an .npz of the same arrays
         if path.endswith(".npz"):
@@ -326,4 +337,91 @@ def pointnet_random_state_dict(seed: int = 0, feature_transform: bool = False) -
             w[bn + ".bias"] = rng.uniform(-0.1, 0.1, co).astype(np.float32)
             w[bn + ".running_mean"] = rng.normal(0.0, 0.1, co).astype(np.float32)
             w[bn + ".running_var"] = rng.uniform(0.5, 1.25, co).astype(np.float32)
+    return w
+
+
+# ---- the DGCNN victim (include/ifd_dgcnn.h) --------------------------------------------------------------------------
+def dgcnn_layers() -> List[Tuple[str, Tuple[str, str], Tuple[int, int], int, bool]]:
+    """The layers of DGCNN(emb_dims=1024, k, output_channels=40, use_bn=True) (baselines/model/dgcnn.py) in network order,
+    which is the canonical order of include/ifd_dgcnn.h: (layer key, the two keys its BatchNorm is registered under - the
+    module attribute first, the Sequential's member second - or None, (out, in), trailing singleton dims of the weight, has a
+    bias).  The reference builds ``self.bn1`` and then puts the same module into ``self.conv1``, so a state_dict holds every
+    BatchNorm twice: ``bn1.*`` and ``conv1.1.*``."""
+    k = []
+    for i, dims in enumerate([(64, 6), (64, 128), (128, 128), (256, 256)], 1):
+        k.append(("conv%d.0" % i, ("bn%d" % i, "conv%d.1" % i), dims, 2, False))
+    k.append(("conv5.0", ("bn5", "conv5.1"), (1024, 512), 1, False))
+    k.append(("linear1.0", ("bn6", "linear1.1"), (512, 2048), 0, False))
+    k.append(("linear2.0", ("bn7", "linear2.1"), (256, 512), 0, True))
+    k.append(("linear3", None, (40, 256), 0, True))
+    return k
+
+
+def dgcnn_canonical_keys() -> List[Tuple[str, Tuple[int, ...]]]:
+    """(name, shape) of the BN-folded tensors ifd_dgcnn_create expects, in order (include/ifd_dgcnn.h)."""
+    k: List[Tuple[str, Tuple[int, ...]]] = []
+    for lin, _, (co, ci), _, _ in dgcnn_layers():
+        k += [(lin + ".weight", (co, ci)), (lin + ".bias", (co,))]
+    return k
+
+
+def fold_dgcnn(state: Dict[str, object]) -> List[Tuple[str, np.ndarray]]:
+    """Fold every eval-mode BatchNorm into its layer in float64 (the formulas of fold_pointnet; a layer without a bias has
+    b = 0, so its folded bias is the BatchNorm's shift).  -> [(canonical name, float64 array)] in canonical order.  Each
+    BatchNorm tensor is read from ``bnN.*``, else from the Sequential's key; both present and different is a ValueError."""
+    state = strip_module_prefix(state)
+
+    def arr(name):
+        t = state[name]
+        return t.detach().cpu().numpy() if hasattr(t, "detach") else np.asarray(t)
+
+    def get(name, shape):
+        if name not in state:
+            raise KeyError("checkpoint lacks %r" % name)
+        a = arr(name)
+        if tuple(a.shape) != tuple(shape):
+            raise ValueError("%s: expected shape %s, got %s" % (name, shape, tuple(a.shape)))
+        return a.astype(np.float64)
+
+    def get_bn(names, field, shape):
+        first, second = (n + "." + field for n in names)
+        if first in state and second in state and not np.array_equal(arr(first), arr(second)):
+            raise ValueError("%s and %s name one BatchNorm tensor but differ" % (first, second))
+        return get(first if first in state or second not in state else second, shape)
+
+    out: List[Tuple[str, np.ndarray]] = []
+    for lin, bn, (co, ci), ones, has_bias in dgcnn_layers():
+        w = get(lin + ".weight", (co, ci) + (1,) * ones).reshape(co, ci)
+        b = get(lin + ".bias", (co,)) if has_bias else np.zeros(co)
+        if bn:
+            g, beta = get_bn(bn, "weight", (co,)), get_bn(bn, "bias", (co,))
+            mean, var = get_bn(bn, "running_mean", (co,)), get_bn(bn, "running_var", (co,))
+            sc = g / np.sqrt(var + BN_EPS)
+            w, b = w * sc[:, None], (b - mean) * sc + beta
+        out += [(lin + ".weight", w), (lin + ".bias", b)]
+    return out
+
+
+def pack_dgcnn(state: Dict[str, object]) -> np.ndarray:
+    """fold_dgcnn, rounded to float32 and flattened in canonical order (num_batches_tracked is ignored)."""
+    return np.concatenate([a.astype(np.float32).reshape(-1) for _, a in fold_dgcnn(state)])
+
+
+def dgcnn_random_state_dict(seed: int = 0) -> Dict[str, np.ndarray]:
+    """Seeded random un-folded DGCNN weights for smoke / benchmark runs (pretrain/mn40/dgcnn.pth is a download), under the
+    BatchNorms' module keys (``bnN.*``).  Per layer in network order: weight (and bias, where the layer has one)
+    U(+-1/sqrt(fan_in)); each BatchNorm after its layer: gamma 1 + U(+-0.2), beta U(+-0.1), running_mean N(0, 0.1),
+    running_var U(0.5, 1.25).  The recipe (and so the numbers) is that of tests/dgcnn_oracle.py make_weights."""
+    rng = np.random.default_rng(seed + 9101)
+    w: Dict[str, np.ndarray] = {}
+    for lin, bn, (co, ci), ones, has_bias in dgcnn_layers():
+        b = 1.0 / np.sqrt(ci)
+        w[lin + ".weight"] = rng.uniform(-b, b, size=(co, ci) + (1,) * ones).astype(np.float32)
+        if has_bias:
+            w[lin + ".bias"] = rng.uniform(-b, b, size=(co,)).astype(np.float32)
+        if bn:
+            w[bn[0] + ".weight"] = (1.0 + rng.uniform(-0.2, 0.2, co)).astype(np.float32)
+            w[bn[0] + ".bias"] = rng.uniform(-0.1, 0.1, co).astype(np.float32)
+            w[bn[0] + ".running_mean"] = rng.normal(0.0, 0.1, co).astype(np.float32)
+            w[bn[0] + ".running_var"] = rng.uniform(0.5, 1.25, co).astype(np.float32)
     return w
