@@ -327,6 +327,25 @@ DGCNN_SIGNATURES = {
                                     C.c_void_p]),
 }
 
+# include/ifd_pn2.h (the PointNet++ victim classifier), versioned on its own
+PN2_ABI_VERSION = 1
+PN2_MAX_POINTS = 2048
+PN2_NPOINT1, PN2_NSAMPLE1, PN2_NPOINT2, PN2_NSAMPLE2 = 512, 32, 128, 64
+
+
+class IfdPn2Aux(C.Structure):
+    _fields_ = [("fps1", C.c_void_p), ("fps2", C.c_void_p), ("ball1", C.c_void_p), ("ball2", C.c_void_p), ("l1_feat", C.c_void_p),
+                ("l2_feat", C.c_void_p), ("global_feat", C.c_void_p), ("pred", C.c_void_p)]
+
+
+PN2_SIGNATURES = {
+    "ifd_pn2_abi_version": (C.c_int, []),
+    "ifd_pn2_weight_count": (C.c_size_t, []),
+    "ifd_pn2_create": (C.c_void_p, [C.c_void_p, C.c_size_t, C.c_int, C.c_int]),
+    "ifd_pn2_forward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.POINTER(IfdPn2Aux),
+                                  C.c_void_p]),
+}
+
 _lib = None
 
 
@@ -344,7 +363,7 @@ def load() -> C.CDLL:
     for name, (res, args) in list(SIGNATURES.items()) + list(DUP_SIGNATURES.items()) + list(CLS_SIGNATURES.items()) + \
             list(ATK_SIGNATURES.items()) + list(CW_SIGNATURES.items()) + list(KNN_SIGNATURES.items()) + list(ADD_SIGNATURES.items()) + \
             list(DROP_SIGNATURES.items()) + list(CLUSTER_SIGNATURES.items()) + list(OBJECT_SIGNATURES.items()) + \
-            list(DGCNN_SIGNATURES.items()):
+            list(DGCNN_SIGNATURES.items()) + list(PN2_SIGNATURES.items()):
         fn = getattr(lib, name)          # AttributeError if the library lacks a declared symbol
         fn.restype, fn.argtypes = res, args
     if lib.ifd_abi_version() != ABI_VERSION:
@@ -369,5 +388,7 @@ def load() -> C.CDLL:
         raise ImportError("libifd.so OBJECT ABI %d != binding OBJECT ABI %d; rebuild" % (lib.ifd_object_abi_version(), OBJECT_ABI_VERSION))
     if lib.ifd_dgcnn_abi_version() != DGCNN_ABI_VERSION:
         raise ImportError("libifd.so DGCNN ABI %d != binding DGCNN ABI %d; rebuild" % (lib.ifd_dgcnn_abi_version(), DGCNN_ABI_VERSION))
+    if lib.ifd_pn2_abi_version() != PN2_ABI_VERSION:
+        raise ImportError("libifd.so PN2 ABI %d != binding PN2 ABI %d; rebuild" % (lib.ifd_pn2_abi_version(), PN2_ABI_VERSION))
     _lib = lib
     return lib

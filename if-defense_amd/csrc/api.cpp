@@ -15,6 +15,7 @@
 #include "../../include/ifd_cluster.h"
 #include "../../include/ifd_object.h"
 #include "../../include/ifd_dgcnn.h"
+#include "../../include/ifd_pn2.h"
 
 #include <hip/hip_runtime.h>
 
@@ -154,6 +155,9 @@ struct ifd_ctx {
     DeviceBuffer d_dgcnn;
     DgImage dimg{};
     int dg_k = 0;
+    // PointNet++ victim (ifd_pn2_create): the weight image (pointnet2.hip); its scratch is `ws`
+    DeviceBuffer d_pn2;
+    Pn2Image p2img{};
     std::string err;
     unsigned long long* counters() const { return d_counters.get<unsigned long long>(); }
 };
@@ -1824,6 +1828,159 @@ int ifd_dgcnn_forward(ifd_ctx* ctx, const float* pc, const int32_t* n_points, in
         e = launch_dgcnn(ctx->d_dgcnn.get<float>(), ctx->dimg, pc + (size_t)c0 * stride * 3, n_points ? n_points + c0 : nullptr, n, stride,
                          k, w, o, logits + (size_t)c0 * nc, nc, s);
         if (e != hipSuccess) return fail(ctx, IFD_ERR_HIP, "ifd_dgcnn_forward launch", e);
+    }
+    return IFD_OK;
+}
+
+}  // extern "C"
+
+// ---- PointNet++ victim classifier (include/ifd_pn2.h) ----------------------------------------------------------------
+namespace {
+
+constexpr int PN2_CHUNK = 128;               // most clouds per chunk of ifd_pn2_forward
+static_assert(PN2_MAX_POINTS == IFD_PN2_MAX_POINTS && PN2_NP1 == IFD_PN2_NPOINT1 && PN2_NS1 == IFD_PN2_NSAMPLE1 &&
+              PN2_NP2 == IFD_PN2_NPOINT2 && PN2_NS2 == IFD_PN2_NSAMPLE2, "ifd_pn2.h and ifd_internal.h");
+
+// the canonical order: sa1 x 3, sa2 x 3, sa3 x 3, fc1 .. fc3
+const ClsTensor PN2_LAYERS[12] = {{64, 3}, {64, 64}, {128, 64}, {128, 131}, {128, 128}, {256, 128}, {256, 259}, {512, 256},
+                                  {PN2_EMB, 512}, {512, PN2_EMB}, {256, 512}, {CLS_CLASSES, 256}};
+
+size_t pn2_count() {
+    size_t n = 0;
+    for (const ClsTensor& t : PN2_LAYERS) n += (size_t)t.out * t.in + t.out;
+    return n;
+}
+
+// The device image (ifd_internal.h Pn2Image): a layer whose input begins with three coordinate columns is split into those
+// columns, as [out][4] rows, and a plain layer of the feature columns; everything else row-major as it comes.
+std::vector<float> build_pn2_image(const float* w, Pn2Image& I) {
+    std::vector<float> img;
+    size_t at[12], src = 0;
+    for (int k = 0; k < 12; ++k) { at[k] = src; src += (size_t)PN2_LAYERS[k].out * PN2_LAYERS[k].in + PN2_LAYERS[k].out; }
+    // the three coordinate columns of layer k -> [out][4] = {w0, w1, w2, bias where with_bias}
+    auto coords = [&](int k, bool with_bias) {
+        const ClsTensor& t = PN2_LAYERS[k];
+        const float* W = w + at[k];
+        const int off = (int)img.size();
+        img.resize(img.size() + (size_t)t.out * 4, 0.f);
+        for (int o = 0; o < t.out; ++o) {
+            for (int a = 0; a < 3; ++a) img[off + o * 4 + a] = W[(size_t)o * t.in + a];
+            if (with_bias) img[off + o * 4 + 3] = W[(size_t)t.out * t.in + o];
+        }
+        return off;
+    };
+    // columns [skip, in) of layer k as a plain layer
+    auto plain = [&](int k, int skip) {
+        const ClsTensor& t = PN2_LAYERS[k];
+        const float* W = w + at[k];
+        Pn2Layer L;
+        L.n_out = t.out; L.n_in = t.in - skip;
+        L.w = (int)img.size();
+        for (int o = 0; o < t.out; ++o) img.insert(img.end(), W + (size_t)o * t.in + skip, W + (size_t)(o + 1) * t.in);
+        L.b = (int)img.size();
+        img.insert(img.end(), W + (size_t)t.out * t.in, W + (size_t)t.out * t.in + t.out);
+        while (img.size() % 4) img.push_back(0.f);                    // every block starts on 16 bytes
+        return L;
+    };
+    I.sa1_first = coords(0, true);
+    I.sa1[0] = plain(1, 0); I.sa1[1] = plain(2, 0);
+    I.sa2_xyz = coords(3, false);
+    I.sa2_u = plain(3, 3); I.sa2[0] = plain(4, 0); I.sa2[1] = plain(5, 0);
+    I.sa3_xyz = coords(6, false);
+    I.sa3_u = plain(6, 3); I.sa3[0] = plain(7, 0); I.sa3[1] = plain(8, 0);
+    for (int j = 0; j < 3; ++j) I.fc[j] = plain(9 + j, 0);
+    I.total = (int)img.size();
+    return img;
+}
+
+// the workspace of ifd_pn2_forward over n clouds: 1024 bytes of which the check uses the first two words, then launch_pn2's scratch
+Pn2Ws pn2_ws(Carve& c, size_t n) {
+    c.take<int32_t>(1024);
+    Pn2Ws w;
+    w.xyz1 = c.take<float>(n * PN2_NP1 * 12); w.xyz2 = c.take<float>(n * PN2_NP2 * 12);
+    w.fps1 = c.take<int32_t>(n * PN2_NP1 * 4); w.fps2 = c.take<int32_t>(n * PN2_NP2 * 4);
+    w.ball1 = c.take<int32_t>(n * PN2_NP1 * PN2_NS1 * 4); w.ball2 = c.take<int32_t>(n * PN2_NP2 * PN2_NS2 * 4);
+    w.l1_feat = c.take<float>(n * PN2_NP1 * 128 * 4); w.u2 = c.take<float>(n * PN2_NP1 * 128 * 4);
+    w.l2_feat = c.take<float>(n * PN2_NP2 * 256 * 4); w.s3a = c.take<float>(n * PN2_NP2 * 256 * 4);
+    w.s3b = c.take<float>(n * PN2_NP2 * 512 * 4); w.part_max = c.take<float>(n * (PN2_NP2 / 64) * PN2_EMB * 4);
+    w.gfeat = c.take<float>(n * PN2_EMB * 4); w.f1 = c.take<float>(n * 512 * 4); w.f2 = c.take<float>(n * 256 * 4);
+    return w;
+}
+size_t pn2_ws_bytes(int n) { return carved_bytes([&](Carve& c) { pn2_ws(c, (size_t)n); }); }
+
+}  // namespace
+
+extern "C" {
+
+int ifd_pn2_abi_version(void) { return IFD_PN2_ABI_VERSION; }
+
+size_t ifd_pn2_weight_count(void) { return pn2_count(); }
+
+ifd_ctx* ifd_pn2_create(const float* weights_host, size_t n_weights, int n_classes, int device) {
+    if (n_classes != CLS_CLASSES) {
+        g_create_error = "ifd_pn2_create: only n_classes = 40 (ModelNet40) is built, got " + std::to_string(n_classes);
+        return nullptr;
+    }
+    if (!weights_host || n_weights != pn2_count()) {
+        g_create_error = "ifd_pn2_create: expected " + std::to_string(pn2_count()) + " weights, got " +
+                         (weights_host ? std::to_string(n_weights) : std::string("NULL"));
+        return nullptr;
+    }
+    return create_ctx("ifd_pn2_create", IFD_MODEL_PN2, device, [&](ifd_ctx* ctx) {
+        ctx->cls_classes = n_classes;
+        hipError_t e = upload(ctx->d_pn2, build_pn2_image(weights_host, ctx->p2img));
+        if (e == hipSuccess) e = configure_pn2_kernels();
+        return e;
+    });
+}
+
+int ifd_pn2_forward(ifd_ctx* ctx, const float* pc, const int32_t* n_points, const int32_t* fps_start, int B, int stride, float* logits,
+                    const ifd_pn2_aux* aux, void* stream) {
+    if (!ctx) return IFD_ERR_ARG;
+    if (ctx->model != IFD_MODEL_PN2 || !ctx->d_pn2.get()) return fail(ctx, IFD_ERR_ARG, "ifd_pn2_forward: not a PointNet++ context");
+    if (!pc || !logits || B < 1 || stride < 1) return fail(ctx, IFD_ERR_ARG, "ifd_pn2_forward: bad argument (pc, logits, B >= 1, stride >= 1)");
+    if (stride > IFD_PN2_MAX_POINTS) return fail(ctx, IFD_ERR_ARG, "ifd_pn2_forward: stride above 2048");
+    IFD_ON_CTX_DEVICE(ctx);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const int n_chunks = (B + PN2_CHUNK - 1) / PN2_CHUNK, chunk = (B + n_chunks - 1) / n_chunks;
+    hipError_t e = ctx->ws.grow(pn2_ws_bytes(chunk));
+    if (e != hipSuccess) return fail(ctx, IFD_ERR_NOMEM, "ifd_pn2_forward: workspace", e);
+    char* base = ctx->ws.get<char>();
+    if (n_points || fps_start) {          // the one blocking step: counts and starts are device memory
+        int32_t bad[2] = {0, 0};
+        e = launch_pn2_check(n_points, fps_start, B, stride, reinterpret_cast<int32_t*>(base), s);
+        if (e == hipSuccess) e = hipMemcpyAsync(bad, base, sizeof(bad), hipMemcpyDeviceToHost, s);
+        if (e == hipSuccess) e = hipStreamSynchronize(s);
+        if (e != hipSuccess) return fail(ctx, IFD_ERR_HIP, "ifd_pn2_forward: checking n_points and fps_start", e);
+        if (bad[0] != 0) {
+            const std::string msg = "ifd_pn2_forward: " + std::to_string(bad[0]) + " cloud(s) with n_points outside [1, stride]";
+            return fail(ctx, IFD_ERR_ARG, msg.c_str());
+        }
+        if (bad[1] != 0) {
+            const std::string msg = "ifd_pn2_forward: " + std::to_string(bad[1]) +
+                                    " cloud(s) with fps_start outside [0, n_points) x [0, 512)";
+            return fail(ctx, IFD_ERR_ARG, msg.c_str());
+        }
+    }
+    const int nc = ctx->cls_classes;
+    for (int c0 = 0; c0 < B; c0 += chunk) {
+        const int n = std::min(chunk, B - c0);
+        Carve c(base);
+        const Pn2Ws w = pn2_ws(c, (size_t)n);
+        Pn2Out o{};
+        if (aux) {
+            o.fps1 = aux->fps1 ? aux->fps1 + (size_t)c0 * PN2_NP1 : nullptr;
+            o.fps2 = aux->fps2 ? aux->fps2 + (size_t)c0 * PN2_NP2 : nullptr;
+            o.ball1 = aux->ball1 ? aux->ball1 + (size_t)c0 * PN2_NP1 * PN2_NS1 : nullptr;
+            o.ball2 = aux->ball2 ? aux->ball2 + (size_t)c0 * PN2_NP2 * PN2_NS2 : nullptr;
+            o.l1_feat = aux->l1_feat ? aux->l1_feat + (size_t)c0 * PN2_NP1 * 128 : nullptr;
+            o.l2_feat = aux->l2_feat ? aux->l2_feat + (size_t)c0 * PN2_NP2 * 256 : nullptr;
+            o.gfeat = aux->global_feat ? aux->global_feat + (size_t)c0 * PN2_EMB : nullptr;
+            o.pred = aux->pred ? aux->pred + c0 : nullptr;
+        }
+        e = launch_pn2(ctx->d_pn2.get<float>(), ctx->p2img, pc + (size_t)c0 * stride * 3, n_points ? n_points + c0 : nullptr,
+                       fps_start ? fps_start + (size_t)c0 * 2 : nullptr, n, stride, w, o, logits + (size_t)c0 * nc, nc, s);
+        if (e != hipSuccess) return fail(ctx, IFD_ERR_HIP, "ifd_pn2_forward launch", e);
     }
     return IFD_OK;
 }

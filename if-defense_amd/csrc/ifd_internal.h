@@ -453,4 +453,54 @@ hipError_t launch_dgcnn_check(const int32_t* n_points, int B, int stride, int k,
 hipError_t launch_dgcnn(const float* img, const DgImage& I, const float* pc, const int32_t* n_points, int B, int stride, int k,
                         const DgWs& w, const DgOut& out, float* logits, int n_classes, hipStream_t s);
 
+// ---- victim classifier: PointNet++ (pointnet2.hip; C ABI in include/ifd_pn2.h) ----------------------------------------
+constexpr int PN2_MAX_POINTS = 2048;    // IFD_PN2_MAX_POINTS
+constexpr int PN2_NP1 = 512, PN2_NS1 = 32;      // sa1: centroids, samples of a ball
+constexpr int PN2_NP2 = 128, PN2_NS2 = 64;      // sa2
+constexpr int PN2_EMB = 1024;           // width of the global feature
+constexpr int PN2_FPS_THREADS = 256;    // a cloud a workgroup of the sampling kernel: thread t owns the points t + 256 k
+// radius ** 2 of the reference (a Python double), compared against the float32 distances in float32
+__host__ __device__ constexpr float pn2_radius2(int level) { return level == 0 ? (float)(0.2 * 0.2) : (float)(0.4 * 0.4); }
+struct Pn2Layer { int w, b, n_out, n_in; };    // float offsets into the device image: weight row-major [n_out][n_in], bias [n_out]
+// The device image (api.cpp build_pn2_image).  A layer whose input begins with three coordinate columns is stored as two blocks:
+// those columns as [n_out][4] rows {w0, w1, w2, bias or 0} and the feature columns as a plain layer.  sa1_first carries sa1's
+// first bias; sa2_u and sa3_u carry theirs, so sa2_xyz and sa3_xyz end in 0.
+struct Pn2Image {
+    int sa1_first;                      // [64][4]
+    Pn2Layer sa1[2];                    // 64 -> 64, 64 -> 128
+    int sa2_xyz;                        // [128][4]
+    Pn2Layer sa2_u, sa2[2];             // 128 -> 128 (the feature columns of the first layer); 128 -> 128, 128 -> 256
+    int sa3_xyz;                        // [256][4]
+    Pn2Layer sa3_u, sa3[2];             // 256 -> 256; 256 -> 512, 512 -> 1024
+    Pn2Layer fc[3];
+    int total;
+};
+struct Pn2Ws {                          // per-chunk scratch of launch_pn2 (api.cpp pn2_ws)
+    float* xyz1;        // [B][512][3]   level-1 centroids
+    float* xyz2;        // [B][128][3]
+    int32_t* fps1;      // [B][512]
+    int32_t* fps2;      // [B][128]
+    int32_t* ball1;     // [B][512][32]
+    int32_t* ball2;     // [B][128][64]
+    float* l1_feat;     // [B][512][128]
+    float* u2;          // [B][512][128]  b + W_f f of sa2's first layer
+    float* l2_feat;     // [B][128][256]
+    float* s3a;         // [B][128][256]
+    float* s3b;         // [B][128][512]
+    float* part_max;    // [B][2][1024]
+    float* gfeat;       // [B][1024]
+    float* f1;          // [B][512]
+    float* f2;          // [B][256]
+};
+struct Pn2Out {                         // where the caller wants the intermediate results; a null member stays in the scratch
+    int32_t *fps1, *fps2, *ball1, *ball2;
+    float *l1_feat, *l2_feat, *gfeat;
+    int32_t* pred;
+};
+hipError_t configure_pn2_kernels();
+// bad[0] = clouds with n_points outside [1, stride]; bad[1] = clouds (of the others) with a start outside [0, n_points) / [0, 512)
+hipError_t launch_pn2_check(const int32_t* n_points, const int32_t* fps_start, int B, int stride, int32_t* bad, hipStream_t s);
+hipError_t launch_pn2(const float* img, const Pn2Image& I, const float* pc, const int32_t* n_points, const int32_t* fps_start, int B,
+                      int stride, const Pn2Ws& w, const Pn2Out& out, float* logits, int n_classes, hipStream_t s);
+
 }  // namespace ifd

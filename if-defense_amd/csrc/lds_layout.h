@@ -320,6 +320,35 @@ struct DgPoolLds {                                   // dg_linear_kernel<true>: 
     static constexpr size_t BYTES = SUM + 2 * 64 * 4;
 };
 
+// ---- pointnet2.hip ------------------------------------------------------------------------------------------------------------
+template <int PPT>
+struct Pn2FpsLds {                                   // pn2_fps_kernel<PPT>: a cloud of up to PPT * PN2_FPS_THREADS points
+    static constexpr size_t X = 0;                                         // float [PPT * PN2_FPS_THREADS][3] the cloud
+    static constexpr size_t SLOT_V = X + (size_t)PPT * PN2_FPS_THREADS * 12;   // float [2][waves] a pick's best distance per wave,
+    static constexpr size_t SLOT_I = SLOT_V + 2 * (PN2_FPS_THREADS / 64) * 4;  // int [2][waves] ... and its index; by the pick's parity
+    static constexpr size_t BYTES = SLOT_I + 2 * (PN2_FPS_THREADS / 64) * 4;
+};
+static_assert(Pn2FpsLds<8>::BYTES == 24640 && 8 * PN2_FPS_THREADS == PN2_MAX_POINTS && 2 * PN2_FPS_THREADS == PN2_NP1,
+              "LDS of pn2_fps_kernel; the largest cloud and the 512 level-1 centroids");
+struct Pn2Sa1Lds {                                   // pn2_sa1_kernel: a 64-row tile between its layers
+    static constexpr int LD = 64 + 4;                                      // floats of a row (16-byte pieces, bank pad)
+    static constexpr size_t A = 0;                                         // float [64][LD] the first layer's output
+    static constexpr size_t B = A + (size_t)64 * LD * 4;                   // float [64][LD] the second's
+    static constexpr size_t BYTES = B + (size_t)64 * LD * 4;
+};
+struct Pn2Sa2Lds {                                   // pn2_sa2_kernel
+    static constexpr int LD = 128 + 4;
+    static constexpr size_t A = 0;                                         // float [64][LD]
+    static constexpr size_t B = A + (size_t)64 * LD * 4;                   // float [64][LD]
+    static constexpr size_t RED = B + (size_t)64 * LD * 4;                 // float [2][256] the two row halves' maxima
+    static constexpr size_t BYTES = RED + 2 * 256 * 4;
+};
+static_assert(Pn2Sa1Lds::BYTES == 34816 && Pn2Sa2Lds::BYTES == 69632 && Pn2Sa2Lds::BYTES <= LDS_MAX_BYTES, "LDS of the grouped MLPs");
+struct Pn2PoolLds {                                  // pn2_linear_kernel<true>: the two row halves' maxima of 64 channels
+    static constexpr size_t MAX = 0;                                       // float [2][64]
+    static constexpr size_t BYTES = MAX + 2 * 64 * 4;
+};
+
 // ---- block_sum / block_max / block_sum_d write one value per wave into their scratch ------------------------------------------
 static_assert((RepLds::BYTES - RepLds::SCRATCH) / 4 >= OPT_THREADS / 64 && (NrmLds::BYTES - NrmLds::SCRATCH) / 4 >= OPT_THREADS / 64,
               "8 waves: repulsion_kernel, normalize_kernel");

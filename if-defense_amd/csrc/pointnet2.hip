@@ -1,0 +1,542 @@
+// The PointNet++ victim classifier of the reference (baselines/model/pointnet2.py: PointNet2ClsSsg(num_classes=40) in eval mode).
+// Eval-mode BatchNorm is folded into the weights on the host.  The [B, C, nsample, npoint] tensor of the reference never exists:
+// a set-abstraction level gathers a tile of 64 grouped rows into LDS, runs its layers on the tile and writes only the maximum
+// of every group.
+//
+//   pn2_fps_kernel<PPT>   farthest point sampling, a workgroup of 256 threads a cloud.  Thread t keeps the points t + 256 k
+//                         (k < PPT) and their running distances in registers; a pick is a scan of its own PPT points, a
+//                         butterfly of (distance, index) pairs over the wave, ONE exchange of the four waves' pairs through LDS
+//                         and ONE barrier (the slots are double-buffered by the pick's parity).  The picked point's coordinates
+//                         come from the cloud's copy in LDS and are written as the picks are made, so that the ball query and
+//                         the grouping read centroids, not indices.
+//   pn2_ball_kernel       a wave a centroid: the cloud is walked in index order 64 candidates at a time; a ballot and the count
+//                         of the member lanes below a lane keep the order; the walk stops at nsample members.
+//   pn2_sa1_kernel        64 rows = two 32-sample groups: 3 -> 64 by plain FMAs into LDS, 64 -> 64 and 64 -> 128 on MFMA, the
+//                         maximum over each group's rows.  A wave's 32 rows are one group, so the maximum never leaves the wave.
+//   pn2_sa2_kernel        64 rows = one 64-sample group.  The first layer in split form: U_j = b + W_f f_j per level-1 point
+//                         (pn2_linear_kernel, 512 rows instead of 8192), then relu(U_j + W_xyz (xyz_j - c_i)) per row with the
+//                         difference formed first, as the reference forms it; 128 -> 128 and 128 -> 256 on MFMA, the maximum.
+//   pn2_linear_kernel     Y = act(W X + b [+ W_xyz xyz]) on v_mfma_f32_16x16x4_f32, dg_linear_kernel's tiling (dgcnn.hip): sa2's
+//                         U, the three layers of sa3 (<true>: the last, reduced to the maxima of its two 64-row tiles), the head.
+//   pn2_pool_kernel, pn2_argmax_kernel
+//
+// Columns of an MFMA never mix, and no kernel looks at another cloud: a cloud's result depends on nothing but its own rows.
+#include "ifd_device.h"
+#include "ifd_internal.h"
+#include "lds_layout.h"
+
+namespace ifd {
+
+namespace {
+
+__device__ __forceinline__ f32x4 mfma4(const f32x4 a, const f32x4 b, f32x4 c) {
+    c = __builtin_amdgcn_mfma_f32_16x16x4f32(a[0], b[0], c, 0, 0, 0);
+    c = __builtin_amdgcn_mfma_f32_16x16x4f32(a[1], b[1], c, 0, 0, 0);
+    c = __builtin_amdgcn_mfma_f32_16x16x4f32(a[2], b[2], c, 0, 0, 0);
+    c = __builtin_amdgcn_mfma_f32_16x16x4f32(a[3], b[3], c, 0, 0, 0);
+    return c;
+}
+__device__ __forceinline__ f32x4 relu4(f32x4 v) { return f32x4{fmaxf(v[0], 0.f), fmaxf(v[1], 0.f), fmaxf(v[2], 0.f), fmaxf(v[3], 0.f)}; }
+
+__device__ __forceinline__ int cloud_points(const int32_t* __restrict__ n_points, int b, int stride) {
+    const int n = n_points ? n_points[b] : stride;
+    return min(max(n, 1), stride);                                     // counts outside [1, stride] are refused by the host
+}
+
+// d = (dx dx + dy dy) + dz dz, every product and sum rounded on its own (include/ifd_pn2.h).  hipcc contracts by default, and
+// __fmul_rn / __fadd_rn are plain operators to it, so the contraction is switched off for exactly this function.
+__device__ __forceinline__ float pn2_dist(float x, float y, float z, float cx, float cy, float cz) {
+#pragma clang fp contract(off)
+    const float dx = x - cx, dy = y - cy, dz = z - cz;
+    const float xx = dx * dx, yy = dy * dy, zz = dz * dz;
+    const float xy = xx + yy;
+    return xy + zz;
+}
+
+__global__ __launch_bounds__(256) void pn2_check_kernel(const int32_t* __restrict__ n_points, const int32_t* __restrict__ fps_start, int B,
+                                                        int stride, int32_t* __restrict__ bad) {
+    const int b = blockIdx.x * 256 + threadIdx.x;
+    if (b >= B) return;
+    int n = stride;
+    if (n_points) {
+        n = n_points[b];
+        if (n < 1 || n > stride) { atomicAdd(bad, 1); return; }
+    }
+    if (fps_start) {
+        const int s1 = fps_start[2 * b], s2 = fps_start[2 * b + 1];
+        if (s1 < 0 || s1 >= n || s2 < 0 || s2 >= PN2_NP1) atomicAdd(bad + 1, 1);
+    }
+}
+
+// X: rows of 3 floats, a cloud's from X + b * xb; its first n_points[b] (n_fixed where null) rows are the cloud, n <= 256 PPT.
+// fps_start [B][2] (null: 0), column `level`.  idx [B][npoint], xyz [B][npoint][3].
+template <int PPT>
+__global__ __launch_bounds__(PN2_FPS_THREADS) void pn2_fps_kernel(const float* __restrict__ X, size_t xb, const int32_t* __restrict__ n_points,
+                                                                  int n_fixed, const int32_t* __restrict__ fps_start, int level, int npoint,
+                                                                  int32_t* __restrict__ idx, float* __restrict__ xyz) {
+    using L = Pn2FpsLds<PPT>;
+    __shared__ __attribute__((aligned(16))) unsigned char smem[L::BYTES];
+    float* sx = LDS_AT(float, smem, L::X);
+    float* sv = LDS_AT(float, smem, L::SLOT_V);
+    int* si = LDS_AT(int, smem, L::SLOT_I);
+    const int b = blockIdx.x, t = threadIdx.x, wv = t >> 6;
+    const int n = cloud_points(n_points, b, n_fixed);
+    const float* Xb = X + (size_t)b * xb;
+    float x[PPT], y[PPT], z[PPT], d[PPT];
+#pragma unroll
+    for (int k = 0; k < PPT; ++k) {
+        const int j = t + PN2_FPS_THREADS * k;
+        x[k] = y[k] = z[k] = 0.f;
+        d[k] = -1.f;                                                   // rows beyond the cloud: below every distance, never picked
+        if (j < n) {
+            x[k] = Xb[3 * j]; y[k] = Xb[3 * j + 1]; z[k] = Xb[3 * j + 2];
+            d[k] = 1e10f;
+            sx[3 * j] = x[k]; sx[3 * j + 1] = y[k]; sx[3 * j + 2] = z[k];
+        }
+    }
+    __syncthreads();
+    int far = fps_start ? fps_start[2 * b + level] : 0;
+    far = min(max(far, 0), n - 1);                                     // starts outside are refused by the host
+    int32_t* I = idx + (size_t)b * npoint;
+    float* O = xyz + (size_t)b * npoint * 3;
+    for (int i = 0; i < npoint; ++i) {
+        const float cx = sx[3 * far], cy = sx[3 * far + 1], cz = sx[3 * far + 2];
+        if (t == 0) { I[i] = far; O[3 * i] = cx; O[3 * i + 1] = cy; O[3 * i + 2] = cz; }
+        float best = -2.f;
+        int bi = 0;
+#pragma unroll
+        for (int k = 0; k < PPT; ++k) {
+            const float dist = pn2_dist(x[k], y[k], z[k], cx, cy, cz);
+            if (dist < d[k]) d[k] = dist;
+            if (d[k] > best) { best = d[k]; bi = t + PN2_FPS_THREADS * k; }      // strictly: the lowest index of a thread's equals
+        }
+#pragma unroll
+        for (int off = 32; off >= 1; off >>= 1) {
+            const float ob = __shfl_xor(best, off);
+            const int oi = __shfl_xor(bi, off);
+            if (ob > best || (ob == best && oi < bi)) { best = ob; bi = oi; }
+        }
+        const int par = (i & 1) * 4;
+        if ((t & 63) == 0) { sv[par + wv] = best; si[par + wv] = bi; }
+        __syncthreads();
+        best = sv[par]; bi = si[par];
+#pragma unroll
+        for (int w = 1; w < PN2_FPS_THREADS / 64; ++w) {
+            const float ob = sv[par + w];
+            const int oi = si[par + w];
+            if (ob > best || (ob == best && oi < bi)) { best = ob; bi = oi; }
+        }
+        far = bi;
+    }
+}
+
+// out[b][i][0 .. nsample): the first nsample j < n (ascending) with !(d(x_j, c_i) > r2), the rest filled with the first.
+__global__ __launch_bounds__(256) void pn2_ball_kernel(const float* __restrict__ X, size_t xb, const int32_t* __restrict__ n_points, int n_fixed,
+                                                       const float* __restrict__ cen, int npoint, int nsample, float r2,
+                                                       int32_t* __restrict__ out) {
+    const int b = blockIdx.y, i = blockIdx.x * 4 + (threadIdx.x >> 6), l = threadIdx.x & 63;
+    if (i >= npoint) return;                                           // the whole wave
+    const int n = cloud_points(n_points, b, n_fixed);
+    const float* Xb = X + (size_t)b * xb;
+    const float* c = cen + ((size_t)b * npoint + i) * 3;
+    const float cx = c[0], cy = c[1], cz = c[2];
+    int32_t* o = out + ((size_t)b * npoint + i) * nsample;
+    int count = 0, first = 0;
+    for (int j0 = 0; j0 < n && count < nsample; j0 += 64) {            // wave-uniform
+        const int j = j0 + l;
+        bool in = false;
+        if (j < n) in = !(pn2_dist(Xb[3 * j], Xb[3 * j + 1], Xb[3 * j + 2], cx, cy, cz) > r2);
+        const unsigned long long m = __ballot(in);
+        if (m == 0) continue;
+        if (count == 0) first = j0 + __builtin_ctzll(m);
+        const int at = count + __builtin_popcountll(m & ((1ull << l) - 1ull));
+        if (in && at < nsample) o[at] = j;
+        count += __builtin_popcountll(m);
+    }
+    for (int e = count + l; e < nsample; e += 64) o[e] = first;
+}
+
+// One layer on a 64-row tile in LDS: v[t][m] = bias + sum_c W[o][c] Xs[row][c], row = 32 (wv & 1) + 16 t + p, o = obase + 16 m +
+// 4 q + r.  The inputs go in blocks of 64: a block is four chains of 16 inputs from zero, added pairwise ((c0 + c1) + (c2 + c3)), and
+// the blocks are added to the bias in ascending order - chains of 16, not of K / 4, which is what the 512-wide layers need to stay
+// within the float32 oracle's error.  W row-major [..][K] in global memory.
+template <int K, int LDX>
+__device__ __forceinline__ void tile_layer(const float* __restrict__ Xs, const float* __restrict__ W, const float* __restrict__ bias,
+                                           int obase, int wv, int q, int p, f32x4 (&v)[2][2]) {
+    const f32x4 zero = f32x4{0.f, 0.f, 0.f, 0.f};
+    const float* xr[2];
+    const float* wr[2];
+#pragma unroll
+    for (int t = 0; t < 2; ++t) {
+        xr[t] = Xs + (32 * (wv & 1) + 16 * t + p) * LDX + 4 * q;
+        wr[t] = W + (size_t)(obase + 16 * t + p) * K + 4 * q;
+    }
+    f32x4 sum[2][2];
+#pragma unroll
+    for (int m = 0; m < 2; ++m) {
+        const f32x4 bv = *reinterpret_cast<const f32x4*>(bias + obase + 16 * m + 4 * q);
+#pragma unroll
+        for (int t = 0; t < 2; ++t) sum[t][m] = bv;
+    }
+#pragma unroll
+    for (int g = 0; g < K; g += 64) {
+        f32x4 xv[2][4], wt[2][4];
+#pragma unroll
+        for (int t = 0; t < 2; ++t)
+#pragma unroll
+            for (int c = 0; c < 4; ++c) {
+                xv[t][c] = *reinterpret_cast<const f32x4*>(xr[t] + g + 16 * c);
+                wt[t][c] = *reinterpret_cast<const f32x4*>(wr[t] + g + 16 * c);
+            }
+        f32x4 acc[2][2][4];                                            // [row tile][output tile][chain] of this 64-input block
+#pragma unroll
+        for (int c = 0; c < 4; ++c)
+#pragma unroll
+            for (int m = 0; m < 2; ++m)
+#pragma unroll
+                for (int t = 0; t < 2; ++t) acc[t][m][c] = mfma4(wt[m][c], xv[t][c], zero);
+#pragma unroll
+        for (int t = 0; t < 2; ++t)
+#pragma unroll
+            for (int m = 0; m < 2; ++m) sum[t][m] += (acc[t][m][0] + acc[t][m][1]) + (acc[t][m][2] + acc[t][m][3]);
+    }
+#pragma unroll
+    for (int t = 0; t < 2; ++t)
+#pragma unroll
+        for (int m = 0; m < 2; ++m) v[t][m] = relu4(sum[t][m]);
+}
+
+// the tile's next layer input: Ys[row][o]
+template <int LDY>
+__device__ __forceinline__ void tile_store(float* __restrict__ Ys, int obase, int wv, int q, int p, const f32x4 (&v)[2][2]) {
+#pragma unroll
+    for (int t = 0; t < 2; ++t)
+#pragma unroll
+        for (int m = 0; m < 2; ++m)
+            *reinterpret_cast<f32x4*>(Ys + (32 * (wv & 1) + 16 * t + p) * LDY + obase + 16 * m + 4 * q) = v[t][m];
+}
+
+// the maximum over the wave's 32 rows: v[0][m] of every lane = max over t and p
+__device__ __forceinline__ void tile_rowmax(f32x4 (&v)[2][2]) {
+#pragma unroll
+    for (int m = 0; m < 2; ++m)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            float x = fmaxf(v[0][m][r], v[1][m][r]);
+#pragma unroll
+            for (int d = 1; d < 16; d <<= 1) x = fmaxf(x, __shfl_xor(x, d));
+            v[0][m][r] = x;
+        }
+}
+
+// sa1.  first: [64][4] = {w0, w1, w2, bias}.  ball [B][512][32] into the cloud, cen [B][512][3].  feat [B][512][128].
+__global__ __launch_bounds__(256) void pn2_sa1_kernel(const float* __restrict__ first, const float* __restrict__ W2, const float* __restrict__ b2,
+                                                      const float* __restrict__ W3, const float* __restrict__ b3, const float* __restrict__ pc,
+                                                      const int32_t* __restrict__ n_points, int stride, const int32_t* __restrict__ ball,
+                                                      const float* __restrict__ cen, float* __restrict__ feat) {
+    __shared__ __attribute__((aligned(16))) unsigned char smem[Pn2Sa1Lds::BYTES];
+    float* A = LDS_AT(float, smem, Pn2Sa1Lds::A);
+    float* Bm = LDS_AT(float, smem, Pn2Sa1Lds::B);
+    constexpr int LD = Pn2Sa1Lds::LD;
+    const int b = blockIdx.y, tile = blockIdx.x;
+    const int wv = threadIdx.x >> 6, l = threadIdx.x & 63, q = l >> 4, p = l & 15;
+    const int n = cloud_points(n_points, b, stride);
+    {
+        const int row = threadIdx.x >> 2, o0 = (threadIdx.x & 3) * 16;
+        const int g = tile * 2 + (row >> 5);
+        const int j = min(max(ball[((size_t)b * PN2_NP1 + g) * PN2_NS1 + (row & 31)], 0), n - 1);
+        const float* x = pc + ((size_t)b * stride + j) * 3;
+        const float* c = cen + ((size_t)b * PN2_NP1 + g) * 3;
+        const float dx = x[0] - c[0], dy = x[1] - c[1], dz = x[2] - c[2];
+#pragma unroll
+        for (int e = 0; e < 16; e += 4) {
+            f32x4 v;
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const f32x4 w = *reinterpret_cast<const f32x4*>(first + (o0 + e + r) * 4);
+                v[r] = fmaxf(fmaf(w[2], dz, fmaf(w[1], dy, fmaf(w[0], dx, w[3]))), 0.f);
+            }
+            *reinterpret_cast<f32x4*>(A + row * LD + o0 + e) = v;
+        }
+    }
+    __syncthreads();
+    f32x4 v[2][2];
+    tile_layer<64, LD>(A, W2, b2, 32 * (wv >> 1), wv, q, p, v);
+    tile_store<LD>(Bm, 32 * (wv >> 1), wv, q, p, v);
+    __syncthreads();
+    const int g = tile * 2 + (wv & 1);                                 // the wave's 32 rows are this group
+    float* F = feat + ((size_t)b * PN2_NP1 + g) * 128;
+#pragma unroll
+    for (int ob = 0; ob < 128; ob += 64) {
+        const int obase = ob + 32 * (wv >> 1);
+        tile_layer<64, LD>(Bm, W3, b3, obase, wv, q, p, v);
+        tile_rowmax(v);
+        if (p == 0) {
+#pragma unroll
+            for (int m = 0; m < 2; ++m) *reinterpret_cast<f32x4*>(F + obase + 16 * m + 4 * q) = v[0][m];
+        }
+    }
+}
+
+// sa2.  U [B][512][128] = b + W_f f_j; wx: [128][4] = {w0, w1, w2, -}.  ball [B][128][64] into the 512, xyz1 [B][512][3],
+// cen [B][128][3].  feat [B][128][256].
+__global__ __launch_bounds__(256) void pn2_sa2_kernel(const float* __restrict__ U, const float* __restrict__ wx, const float* __restrict__ W2,
+                                                      const float* __restrict__ b2, const float* __restrict__ W3, const float* __restrict__ b3,
+                                                      const int32_t* __restrict__ ball, const float* __restrict__ xyz1,
+                                                      const float* __restrict__ cen, float* __restrict__ feat) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    float* A = LDS_AT(float, smem, Pn2Sa2Lds::A);
+    float* Bm = LDS_AT(float, smem, Pn2Sa2Lds::B);
+    float* red = LDS_AT(float, smem, Pn2Sa2Lds::RED);
+    constexpr int LD = Pn2Sa2Lds::LD;
+    const int b = blockIdx.y, g = blockIdx.x;
+    const int wv = threadIdx.x >> 6, l = threadIdx.x & 63, q = l >> 4, p = l & 15;
+    {
+        const int row = threadIdx.x >> 2, o0 = (threadIdx.x & 3) * 32;
+        const int j = min(max(ball[((size_t)b * PN2_NP2 + g) * PN2_NS2 + row], 0), PN2_NP1 - 1);
+        const float* x = xyz1 + ((size_t)b * PN2_NP1 + j) * 3;
+        const float* c = cen + ((size_t)b * PN2_NP2 + g) * 3;
+        const float dx = x[0] - c[0], dy = x[1] - c[1], dz = x[2] - c[2];
+        const float* u = U + ((size_t)b * PN2_NP1 + j) * 128 + o0;
+#pragma unroll
+        for (int e = 0; e < 32; e += 4) {
+            f32x4 v = *reinterpret_cast<const f32x4*>(u + e);
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const f32x4 w = *reinterpret_cast<const f32x4*>(wx + (o0 + e + r) * 4);
+                v[r] = fmaxf(fmaf(w[2], dz, fmaf(w[1], dy, fmaf(w[0], dx, v[r]))), 0.f);
+            }
+            *reinterpret_cast<f32x4*>(A + row * LD + o0 + e) = v;
+        }
+    }
+    __syncthreads();
+    f32x4 v[2][2];
+#pragma unroll
+    for (int ob = 0; ob < 128; ob += 64) {
+        const int obase = ob + 32 * (wv >> 1);
+        tile_layer<128, LD>(A, W2, b2, obase, wv, q, p, v);
+        tile_store<LD>(Bm, obase, wv, q, p, v);
+    }
+    __syncthreads();
+#pragma unroll 1
+    for (int ob = 0; ob < 256; ob += 64) {
+        const int obase = ob + 32 * (wv >> 1);
+        tile_layer<128, LD>(Bm, W3, b3, obase, wv, q, p, v);
+        tile_rowmax(v);
+        if (p == 0) {
+#pragma unroll
+            for (int m = 0; m < 2; ++m) *reinterpret_cast<f32x4*>(red + (wv & 1) * 256 + obase + 16 * m + 4 * q) = v[0][m];
+        }
+    }
+    __syncthreads();
+    feat[((size_t)b * PN2_NP2 + g) * 256 + threadIdx.x] = fmaxf(red[threadIdx.x], red[256 + threadIdx.x]);
+}
+
+// Y[row][o] = act(bias[o] + sum_c W[o][c] X[row][c] (+ wx[o] . xyz[row])), o < M (a multiple of 4), K a multiple of 64, `rows` rows
+// per cloud b = blockIdx.z: X rows of ldx floats from X + b * xb, Y rows of ldy floats from Y + b * yb, xyz rows of 3 floats from
+// xyz + b * rows * 3.  dg_linear_kernel's tiling: a workgroup = 64 rows x 64 outputs, wave w = row half (w & 1) x output half
+// (w >> 1); tile_layer's arithmetic (blocks of 64 inputs).  The xyz columns are added to that sum by three FMAs (x, then y, then z).
+// POOL (sa3's last layer; M = 1024): nothing is stored but the maximum over the workgroup's valid rows, part_max [b][T][M].
+template <bool POOL>
+__global__ __launch_bounds__(256) void pn2_linear_kernel(const float* __restrict__ W, const float* __restrict__ bias, int M, int K,
+                                                         const float* __restrict__ X, int ldx, size_t xb, int rows, float* __restrict__ Y,
+                                                         int ldy, size_t yb, int act, const float* __restrict__ wx,
+                                                         const float* __restrict__ xyz, float* __restrict__ part_max, int T) {
+    __shared__ __attribute__((aligned(16))) float red[POOL ? Pn2PoolLds::BYTES / 4 : 4];
+    const int b = blockIdx.z;
+    const int row0 = blockIdx.x * 64;
+    if (row0 >= rows) return;                                          // the whole workgroup
+    const int wv = threadIdx.x >> 6, l = threadIdx.x & 63, q = l >> 4, p = l & 15;
+    const int rbase = row0 + 32 * (wv & 1), obase = blockIdx.y * 64 + 32 * (wv >> 1);
+    const float* Xb = X + (size_t)b * xb;
+    const float* xr[2];
+    const float* wr[2];
+    bool valid[2];
+#pragma unroll
+    for (int t = 0; t < 2; ++t) {
+        const int i = rbase + 16 * t + p;
+        valid[t] = i < rows;
+        xr[t] = Xb + (size_t)min(i, rows - 1) * ldx + 4 * q;           // rows beyond compute on the last row, unused
+        wr[t] = W + (size_t)min(obase + 16 * t + p, M - 1) * K + 4 * q;
+    }
+    const f32x4 zero = f32x4{0.f, 0.f, 0.f, 0.f};
+    f32x4 sum[2][2];                                                   // [row tile][output tile]
+#pragma unroll
+    for (int m = 0; m < 2; ++m) {
+        f32x4 bv = zero;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const int o = obase + 16 * m + 4 * q + r;
+            bv[r] = o < M ? bias[o] : 0.f;
+        }
+#pragma unroll
+        for (int t = 0; t < 2; ++t) sum[t][m] = bv;
+    }
+    for (int g = 0; g < K; g += 64) {
+        f32x4 xv[2][4], wt[2][4];
+#pragma unroll
+        for (int t = 0; t < 2; ++t)
+#pragma unroll
+            for (int c = 0; c < 4; ++c) {
+                xv[t][c] = *reinterpret_cast<const f32x4*>(xr[t] + g + 16 * c);
+                wt[t][c] = *reinterpret_cast<const f32x4*>(wr[t] + g + 16 * c);
+            }
+        f32x4 acc[2][2][4];                                            // [row tile][output tile][chain] of this 64-input block
+#pragma unroll
+        for (int c = 0; c < 4; ++c)
+#pragma unroll
+            for (int m = 0; m < 2; ++m)
+#pragma unroll
+                for (int t = 0; t < 2; ++t) acc[t][m][c] = mfma4(wt[m][c], xv[t][c], zero);
+#pragma unroll
+        for (int t = 0; t < 2; ++t)
+#pragma unroll
+            for (int m = 0; m < 2; ++m) sum[t][m] += (acc[t][m][0] + acc[t][m][1]) + (acc[t][m][2] + acc[t][m][3]);
+    }
+    f32x4 v[2][2];
+#pragma unroll
+    for (int t = 0; t < 2; ++t) {
+        float px = 0.f, py = 0.f, pz = 0.f;
+        if (wx) {
+            const float* pt = xyz + ((size_t)b * rows + min(rbase + 16 * t + p, rows - 1)) * 3;
+            px = pt[0]; py = pt[1]; pz = pt[2];
+        }
+#pragma unroll
+        for (int m = 0; m < 2; ++m) {
+            v[t][m] = sum[t][m];
+            if (wx) {
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    const f32x4 w = *reinterpret_cast<const f32x4*>(wx + (size_t)min(obase + 16 * m + 4 * q + r, M - 1) * 4);
+                    v[t][m][r] = fmaf(w[2], pz, fmaf(w[1], py, fmaf(w[0], px, v[t][m][r])));
+                }
+            }
+            if (POOL || act) v[t][m] = relu4(v[t][m]);
+        }
+    }
+    if (!POOL) {
+        float* Yb = Y + (size_t)b * yb;
+#pragma unroll
+        for (int t = 0; t < 2; ++t)
+#pragma unroll
+            for (int m = 0; m < 2; ++m) {
+                const int i = rbase + 16 * t + p, o = obase + 16 * m + 4 * q;
+                if (valid[t] && o < M) *reinterpret_cast<f32x4*>(Yb + (size_t)i * ldy + o) = v[t][m];
+            }
+        return;
+    }
+    float* rmax = LDS_AT(float, red, Pn2PoolLds::MAX);
+#pragma unroll
+    for (int m = 0; m < 2; ++m) {
+        f32x4 mx = f32x4{-INFINITY, -INFINITY, -INFINITY, -INFINITY};
+#pragma unroll
+        for (int t = 0; t < 2; ++t)
+            if (valid[t]) {
+#pragma unroll
+                for (int r = 0; r < 4; ++r) mx[r] = fmaxf(mx[r], v[t][m][r]);
+            }
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            float x = mx[r];
+#pragma unroll
+            for (int d = 1; d < 16; d <<= 1) x = fmaxf(x, __shfl_xor(x, d));
+            mx[r] = x;
+        }
+        if (p == 0) *reinterpret_cast<f32x4*>(rmax + (wv & 1) * 64 + 32 * (wv >> 1) + 16 * m + 4 * q) = mx;
+    }
+    __syncthreads();
+    if (threadIdx.x < 64)
+        part_max[((size_t)b * T + blockIdx.x) * M + blockIdx.y * 64 + threadIdx.x] = fmaxf(rmax[threadIdx.x], rmax[64 + threadIdx.x]);
+}
+
+__global__ __launch_bounds__(256) void pn2_pool_kernel(const float* __restrict__ part_max, int T, float* __restrict__ gfeat) {
+    const int b = blockIdx.x, c = threadIdx.x * 4;
+    const float* P = part_max + (size_t)b * T * PN2_EMB + c;
+    f32x4 m = *reinterpret_cast<const f32x4*>(P);
+    for (int t = 1; t < T; ++t) {
+        const f32x4 v = *reinterpret_cast<const f32x4*>(P + (size_t)t * PN2_EMB);
+#pragma unroll
+        for (int r = 0; r < 4; ++r) m[r] = fmaxf(m[r], v[r]);
+    }
+    *reinterpret_cast<f32x4*>(gfeat + (size_t)b * PN2_EMB + c) = m;
+}
+
+__global__ __launch_bounds__(256) void pn2_argmax_kernel(const float* __restrict__ logits, int B, int n_classes, int32_t* __restrict__ pred) {
+    const int b = blockIdx.x * 256 + threadIdx.x;
+    if (b >= B) return;
+    const float* L = logits + (size_t)b * n_classes;
+    float bv = L[0];
+    int bi = 0;
+    for (int c = 1; c < n_classes; ++c)
+        if (L[c] > bv) { bv = L[c]; bi = c; }                          // strict: the lowest class among equals
+    pred[b] = bi;
+}
+
+// one layer on [B clouds][rows rows]
+void launch_linear(const float* img, const Pn2Layer& L, const float* X, int ldx, size_t xb, int B, int rows, float* Y, int ldy, size_t yb,
+                   int act, const float* wx, const float* xyz, hipStream_t s) {
+    hipLaunchKernelGGL((pn2_linear_kernel<false>), dim3((rows + 63) / 64, (L.n_out + 63) / 64, B), dim3(256), 0, s, img + L.w, img + L.b,
+                       L.n_out, L.n_in, X, ldx, xb, rows, Y, ldy, yb, act, wx, xyz, (float*)nullptr, 0);
+}
+
+}  // namespace
+
+hipError_t configure_pn2_kernels() { return opt_in_dynamic_lds({{pn2_sa2_kernel, Pn2Sa2Lds::BYTES}}); }
+
+hipError_t launch_pn2_check(const int32_t* n_points, const int32_t* fps_start, int B, int stride, int32_t* bad, hipStream_t s) {
+    hipError_t e = hipMemsetAsync(bad, 0, 2 * sizeof(int32_t), s);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(pn2_check_kernel, dim3((B + 255) / 256), dim3(256), 0, s, n_points, fps_start, B, stride, bad);
+    return hipGetLastError();
+}
+
+hipError_t launch_pn2(const float* img, const Pn2Image& I, const float* pc, const int32_t* n_points, const int32_t* fps_start, int B,
+                      int stride, const Pn2Ws& w, const Pn2Out& out, float* logits, int n_classes, hipStream_t s) {
+    int32_t* fps1 = out.fps1 ? out.fps1 : w.fps1;
+    int32_t* fps2 = out.fps2 ? out.fps2 : w.fps2;
+    int32_t* ball1 = out.ball1 ? out.ball1 : w.ball1;
+    int32_t* ball2 = out.ball2 ? out.ball2 : w.ball2;
+    float* l1 = out.l1_feat ? out.l1_feat : w.l1_feat;
+    float* l2 = out.l2_feat ? out.l2_feat : w.l2_feat;
+    float* gfeat = out.gfeat ? out.gfeat : w.gfeat;
+    const dim3 block(256);
+    // level 1: 512 centroids of the cloud, their balls, the grouped MLP
+    if (stride <= 512)
+        hipLaunchKernelGGL((pn2_fps_kernel<2>), dim3(B), dim3(PN2_FPS_THREADS), 0, s, pc, (size_t)stride * 3, n_points, stride, fps_start, 0,
+                           PN2_NP1, fps1, w.xyz1);
+    else if (stride <= 1024)
+        hipLaunchKernelGGL((pn2_fps_kernel<4>), dim3(B), dim3(PN2_FPS_THREADS), 0, s, pc, (size_t)stride * 3, n_points, stride, fps_start, 0,
+                           PN2_NP1, fps1, w.xyz1);
+    else
+        hipLaunchKernelGGL((pn2_fps_kernel<8>), dim3(B), dim3(PN2_FPS_THREADS), 0, s, pc, (size_t)stride * 3, n_points, stride, fps_start, 0,
+                           PN2_NP1, fps1, w.xyz1);
+    hipLaunchKernelGGL(pn2_ball_kernel, dim3(PN2_NP1 / 4, B), block, 0, s, pc, (size_t)stride * 3, n_points, stride, (const float*)w.xyz1,
+                       PN2_NP1, PN2_NS1, pn2_radius2(0), ball1);
+    hipLaunchKernelGGL(pn2_sa1_kernel, dim3(PN2_NP1 / 2, B), block, 0, s, img + I.sa1_first, img + I.sa1[0].w, img + I.sa1[0].b,
+                       img + I.sa1[1].w, img + I.sa1[1].b, pc, n_points, stride, (const int32_t*)ball1, (const float*)w.xyz1, l1);
+    // level 2: 128 centroids of the 512, their balls, U = b + W_f f per level-1 point, the grouped MLP
+    hipLaunchKernelGGL((pn2_fps_kernel<2>), dim3(B), dim3(PN2_FPS_THREADS), 0, s, (const float*)w.xyz1, (size_t)PN2_NP1 * 3,
+                       (const int32_t*)nullptr, PN2_NP1, fps_start, 1, PN2_NP2, fps2, w.xyz2);
+    hipLaunchKernelGGL(pn2_ball_kernel, dim3(PN2_NP2 / 4, B), block, 0, s, (const float*)w.xyz1, (size_t)PN2_NP1 * 3, (const int32_t*)nullptr,
+                       PN2_NP1, (const float*)w.xyz2, PN2_NP2, PN2_NS2, pn2_radius2(1), ball2);
+    launch_linear(img, I.sa2_u, l1, 128, (size_t)PN2_NP1 * 128, B, PN2_NP1, w.u2, 128, (size_t)PN2_NP1 * 128, 0, nullptr, nullptr, s);
+    hipLaunchKernelGGL(pn2_sa2_kernel, dim3(PN2_NP2, B), block, (size_t)Pn2Sa2Lds::BYTES, s, (const float*)w.u2, img + I.sa2_xyz,
+                       img + I.sa2[0].w, img + I.sa2[0].b, img + I.sa2[1].w, img + I.sa2[1].b, (const int32_t*)ball2, (const float*)w.xyz1,
+                       (const float*)w.xyz2, l2);
+    // level 3: one group of the 128 rows [xyz | 256 features]
+    launch_linear(img, I.sa3_u, l2, 256, (size_t)PN2_NP2 * 256, B, PN2_NP2, w.s3a, 256, (size_t)PN2_NP2 * 256, 1, img + I.sa3_xyz, w.xyz2, s);
+    launch_linear(img, I.sa3[0], w.s3a, 256, (size_t)PN2_NP2 * 256, B, PN2_NP2, w.s3b, 512, (size_t)PN2_NP2 * 512, 1, nullptr, nullptr, s);
+    constexpr int T = PN2_NP2 / 64;
+    hipLaunchKernelGGL((pn2_linear_kernel<true>), dim3(T, PN2_EMB / 64, B), block, 0, s, img + I.sa3[1].w, img + I.sa3[1].b, PN2_EMB, 512,
+                       (const float*)w.s3b, 512, (size_t)PN2_NP2 * 512, PN2_NP2, (float*)nullptr, 0, (size_t)0, 1, (const float*)nullptr,
+                       (const float*)nullptr, w.part_max, T);
+    hipLaunchKernelGGL(pn2_pool_kernel, dim3(B), block, 0, s, (const float*)w.part_max, T, gfeat);
+    // the head, a cloud a row
+    launch_linear(img, I.fc[0], gfeat, PN2_EMB, 0, 1, B, w.f1, 512, 0, 1, nullptr, nullptr, s);
+    launch_linear(img, I.fc[1], w.f1, 512, 0, 1, B, w.f2, 256, 0, 1, nullptr, nullptr, s);
+    launch_linear(img, I.fc[2], w.f2, 256, 0, 1, B, logits, n_classes, 0, 0, nullptr, nullptr, s);
+    if (out.pred) hipLaunchKernelGGL(pn2_argmax_kernel, dim3((B + 255) / 256), block, 0, s, (const float*)logits, B, n_classes, out.pred);
+    return hipGetLastError();
+}
+
+}  // namespace ifd

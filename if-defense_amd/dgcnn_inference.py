@@ -5,7 +5,7 @@ with --model dgcnn.
 
 The flags, the num-points rules, the evaluation and the printed lines are those of ifdefense_amd.inference (imported, not
 repeated); the model comes from --model or from the file's path, and anything but dgcnn is refused with a pointer to
-ifdefense_amd.inference.  --k is honoured (1 .. 32); --emb_dims other than 1024 is refused.  --model_path: the checkpoint
+ifdefense_amd.inference (and to ifdefense_amd.pointnet2_inference).  --k is honoured (1 .. 32); --emb_dims other than 1024 is refused.  --model_path: the checkpoint
 (.pth saved from nn.DataParallel, or an .npz of its arrays); empty means pretrain/{dataset}/dgcnn.pth.  A file that holds a
 cloud of fewer than k points is refused with a message (the reference's topk raises there), as is one of more than 2048.
 """
@@ -56,7 +56,8 @@ def main(argv=None, make_classifier=None) -> int:
             return 2
     if args.model.lower() != 'dgcnn':
         print("dgcnn_inference: only the dgcnn victim runs here, not {}; pointnet is evaluated by "
-              "`python -m ifdefense_amd.inference`".format(args.model), file=sys.stderr)
+              "`python -m ifdefense_amd.inference`, pointnet2 by `python -m ifdefense_amd.pointnet2_inference`".format(args.model),
+              file=sys.stderr)
         return 2
     if args.emb_dims != 1024:
         print("dgcnn_inference: only --emb_dims 1024 is built, got {}".format(args.emb_dims), file=sys.stderr)

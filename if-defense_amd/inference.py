@@ -5,7 +5,8 @@ Same flags, rules and printed lines as the reference CLI (baselines/inference.py
     python -m ifdefense_amd.inference --data_root=path/to/file.npz --mode=target --model=pointnet --model_path=pointnet.pth
 
 Only the PointNet victim runs here; --model pointnet2 | dgcnn | pointconv (or a path that names one of them) is refused with
-a message and a non-zero status (DGCNN has a CLI of its own, ifdefense_amd.dgcnn_inference).  --model_path: the victim checkpoint (.pth saved from nn.DataParallel, or an .npz of its
+a message and a non-zero status (DGCNN and PointNet++ have CLIs of their own, ifdefense_amd.dgcnn_inference and
+ifdefense_amd.pointnet2_inference).  --model_path: the victim checkpoint (.pth saved from nn.DataParallel, or an .npz of its
 arrays); empty means BEST_WEIGHTS[dataset][1024][model] of baselines/config.py, relative to the working directory.
 
 Differences from the reference: the whole file runs through the classifier in one call (PointNet has no cross-cloud
@@ -134,8 +135,8 @@ def main(argv=None, make_classifier=None) -> int:
             print('Victim model not recognized!', file=sys.stderr)
             return 2
     if args.model.lower() != 'pointnet':
-        where = ("`python -m ifdefense_amd.dgcnn_inference`" if args.model.lower() == 'dgcnn'
-                 else "the reference's baselines/inference.py")
+        own = {'dgcnn': "`python -m ifdefense_amd.dgcnn_inference`", 'pointnet2': "`python -m ifdefense_amd.pointnet2_inference`"}
+        where = own.get(args.model.lower(), "the reference's baselines/inference.py")
         print("inference: the {} victim is not built here (only pointnet is); evaluate it with {}".format(args.model, where),
               file=sys.stderr)
         return 2

@@ -1479,3 +1479,68 @@ class DgcnnClassifier(Classifier):
             self._check(self.lib.ifd_dgcnn_forward(self.ctx, pc.data_ptr(), None if n_points is None else n_points.data_ptr(),
                                                    B, stride, out.data_ptr(), st, torch.cuda.current_stream(self.device).cuda_stream))
         return (out, aux) if aux is not None else out
+
+
+class PointNet2Classifier(Classifier):
+    """The PointNet++ victim of the reference on one GPU (include/ifd_pn2.h): PointNet2ClsSsg(num_classes=40) in eval mode.
+    ``weights``: the BN-folded canonical vector (``weights.load_checkpoint(path, "pointnet2")`` or
+    ``weights.pack_state_dict(state_dict, "pointnet2")``).  Inputs are Classifier's: [B,N,3] batches (point-major), lists and
+    object arrays of ragged clouds of 1 to 2048 points.  ``fps_start`` [B,2] int: the first pick of the level-1 sampling (below
+    the cloud's count) and of the level-2 sampling (below 512); None means 0, 0 - the reference draws them at random, here
+    they are an input.  A cloud's outputs do not depend on how it is batched or padded.  The attack entry points of Classifier
+    are PointNet's and are not offered here."""
+
+    MAX_POINTS = _lib.PN2_MAX_POINTS
+
+    def __init__(self, weights: np.ndarray, device=None):
+        self.lib = _lib.load()
+        self.feature_transform = False
+        w = np.ascontiguousarray(weights, dtype=np.float32)
+        want = self.lib.ifd_pn2_weight_count()
+        if w.size != want:
+            raise IfdError("expected %d pointnet2 weights, got %d" % (want, w.size))
+        if not torch.cuda.is_available():
+            raise IfdError("no GPU visible: the classifier only runs on an MI355X (no CPU fallback)")
+        self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+        with torch.cuda.device(self.device):
+            self.ctx = self.lib.ifd_pn2_create(w.ctypes.data, w.size, self.N_CLASSES, self.device.index or 0)
+        if not self.ctx:
+            raise IfdError((self.lib.ifd_last_error(None) or b"ifd_pn2_create failed").decode())
+
+    def logits(self, pc, n_points=None, fps_start=None, want_aux: bool = False, want_pred: bool = False):
+        """pc, n_points: as Classifier.logits.  Returns logits [B,40]; with want_aux also {"fps1" [B,512], "fps2" [B,128],
+        "ball1" [B,512,32], "ball2" [B,128,64] (int32), "l1_feat" [B,512,128], "l2_feat" [B,128,256], "global_feat" [B,1024],
+        "pred" [B] int32}."""
+        pc, n_points = self._batch(pc, n_points)
+        B, stride = int(pc.shape[0]), int(pc.shape[1])
+        if B < 1 or stride < 1:
+            raise IfdError("empty batch")
+        if fps_start is not None:
+            fps_start = torch.as_tensor(fps_start).to(device=self.device, dtype=torch.int32).contiguous()
+            if tuple(fps_start.shape) != (B, 2):
+                raise IfdError("fps_start must be [B,2], got %s" % (tuple(fps_start.shape),))
+        out = torch.empty(B, self.N_CLASSES, device=self.device, dtype=torch.float32)
+        aux, st = None, None
+        if want_aux or want_pred:
+            aux = {"pred": torch.empty(B, device=self.device, dtype=torch.int32)}
+            a = _lib.IfdPn2Aux()
+            a.pred = aux["pred"].data_ptr()
+            if want_aux:
+                n1, s1, n2, s2 = _lib.PN2_NPOINT1, _lib.PN2_NSAMPLE1, _lib.PN2_NPOINT2, _lib.PN2_NSAMPLE2
+                i32, f32 = dict(device=self.device, dtype=torch.int32), dict(device=self.device, dtype=torch.float32)
+                aux.update(fps1=torch.empty(B, n1, **i32), fps2=torch.empty(B, n2, **i32), ball1=torch.empty(B, n1, s1, **i32),
+                           ball2=torch.empty(B, n2, s2, **i32), l1_feat=torch.empty(B, n1, 128, **f32),
+                           l2_feat=torch.empty(B, n2, 256, **f32), global_feat=torch.empty(B, 1024, **f32))
+                for name in ("fps1", "fps2", "ball1", "ball2", "l1_feat", "l2_feat", "global_feat"):
+                    setattr(a, name, aux[name].data_ptr())
+            st = C.byref(a)
+        with torch.cuda.device(self.device):
+            self._check(self.lib.ifd_pn2_forward(self.ctx, pc.data_ptr(), None if n_points is None else n_points.data_ptr(),
+                                                 None if fps_start is None else fps_start.data_ptr(), B, stride, out.data_ptr(), st,
+                                                 torch.cuda.current_stream(self.device).cuda_stream))
+        return (out, aux) if aux is not None else out
+
+    def predict(self, pc, n_points=None, fps_start=None) -> torch.Tensor:
+        """argmax of the logits, [B] int64 (the lowest class among equal logits)."""
+        _, aux = self.logits(pc, n_points, fps_start=fps_start, want_pred=True)
+        return aux["pred"].long()

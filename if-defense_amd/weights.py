@@ -174,6 +174,8 @@ def _keys(model: str):
         return pointnet_canonical_keys(False)
     if model == "dgcnn":
         return dgcnn_canonical_keys()
+    if model == "pointnet2":
+        return pointnet2_canonical_keys()
     if model == "onet":
         return onet_canonical_keys()
     if model == "punet":
@@ -189,6 +191,8 @@ def pack_state_dict(state: Dict[str, object], model: str = "convonet", feature_t
         return pack_pointnet(state, feature_transform)
     if model == "dgcnn":
         return pack_dgcnn(state)
+    if model == "pointnet2":
+        return pack_pointnet2(state)
     parts = []
     for name, shape in _keys(model):
         if name not in state:
@@ -218,6 +222,13 @@ def load_checkpoint(path: str, model: str = "convonet", feature_transform=None) 
                 return pack_dgcnn({n: z[n] for n in z.files})
         import torch
         return pack_dgcnn(torch.load(path, map_location="cpu", weights_only=True))
+    if model == "pointnet2":
+        # pretrain/<dataset>/pointnet2.pth (saved from nn.DataParallel) or an .npz of its arrays
+        if path.endswith(".npz"):
+            with np.load(path, allow_pickle=False) as z:
+                return pack_pointnet2({n: z[n] for n in z.files})
+        import torch
+        return pack_pointnet2(torch.load(path, map_location="cpu", weights_only=True))
     if model == "punet":
         # pu-in_1024-up_4.pth (baselines/config.py PU_NET_WEIGHT) or an .npz of the same arrays
         if path.endswith(".npz"):
@@ -424,4 +435,82 @@ def dgcnn_random_state_dict(seed: int = 0) -> Dict[str, np.ndarray]:
             w[bn[0] + ".bias"] = rng.uniform(-0.1, 0.1, co).astype(np.float32)
             w[bn[0] + ".running_mean"] = rng.normal(0.0, 0.1, co).astype(np.float32)
             w[bn[0] + ".running_var"] = rng.uniform(0.5, 1.25, co).astype(np.float32)
+    return w
+
+
+# ---- the PointNet++ victim (include/ifd_pn2.h) -----------------------------------------------------------------------
+def pointnet2_layers() -> List[Tuple[str, object, Tuple[int, int], int]]:
+    """The layers of PointNet2ClsSsg(num_classes=40) (baselines/model/pointnet2.py) in network order, which is the canonical
+    order of include/ifd_pn2.h: (layer key, its BatchNorm's key or None, (out, in), trailing singleton dims of the weight).
+    Every layer has a bias."""
+    k = []
+    for sa, dims in (("sa1", [(64, 3), (64, 64), (128, 64)]), ("sa2", [(128, 131), (128, 128), (256, 128)]),
+                     ("sa3", [(256, 259), (512, 256), (1024, 512)])):
+        for i, d in enumerate(dims):
+            k.append(("%s.mlp_convs.%d" % (sa, i), "%s.mlp_bns.%d" % (sa, i), d, 2))
+    k.append(("fc1", "bn1", (512, 1024), 0))
+    k.append(("fc2", "bn2", (256, 512), 0))
+    k.append(("fc3", None, (40, 256), 0))
+    return k
+
+
+def pointnet2_canonical_keys() -> List[Tuple[str, Tuple[int, ...]]]:
+    """(name, shape) of the BN-folded tensors ifd_pn2_create expects, in order (include/ifd_pn2.h)."""
+    k: List[Tuple[str, Tuple[int, ...]]] = []
+    for lin, _, (co, ci), _ in pointnet2_layers():
+        k += [(lin + ".weight", (co, ci)), (lin + ".bias", (co,))]
+    return k
+
+
+def fold_pointnet2(state: Dict[str, object]) -> List[Tuple[str, np.ndarray]]:
+    """Fold every eval-mode BatchNorm into its layer in float64 (the formulas of fold_pointnet).  -> [(canonical name, float64
+    array)] in canonical order.  A key that is there both with and without the ``module.`` prefix is a ValueError."""
+    doubled = [k for k in state if not k.startswith("module.") and ("module." + k) in state]
+    if doubled:
+        raise ValueError("checkpoint holds %r with and without the module. prefix" % doubled[0])
+    state = strip_module_prefix(state)
+
+    def get(name, shape):
+        if name not in state:
+            raise KeyError("checkpoint lacks %r" % name)
+        t = state[name]
+        a = t.detach().cpu().numpy() if hasattr(t, "detach") else np.asarray(t)
+        if tuple(a.shape) != tuple(shape):
+            raise ValueError("%s: expected shape %s, got %s" % (name, shape, tuple(a.shape)))
+        return a.astype(np.float64)
+
+    out: List[Tuple[str, np.ndarray]] = []
+    for lin, bn, (co, ci), ones in pointnet2_layers():
+        w = get(lin + ".weight", (co, ci) + (1,) * ones).reshape(co, ci)
+        b = get(lin + ".bias", (co,))
+        if bn:
+            g, beta = get(bn + ".weight", (co,)), get(bn + ".bias", (co,))
+            mean, var = get(bn + ".running_mean", (co,)), get(bn + ".running_var", (co,))
+            sc = g / np.sqrt(var + BN_EPS)
+            w, b = w * sc[:, None], (b - mean) * sc + beta
+        out += [(lin + ".weight", w), (lin + ".bias", b)]
+    return out
+
+
+def pack_pointnet2(state: Dict[str, object]) -> np.ndarray:
+    """fold_pointnet2, rounded to float32 and flattened in canonical order (num_batches_tracked is ignored)."""
+    return np.concatenate([a.astype(np.float32).reshape(-1) for _, a in fold_pointnet2(state)])
+
+
+def pointnet2_random_state_dict(seed: int = 0) -> Dict[str, np.ndarray]:
+    """Seeded random un-folded PointNet++ weights for smoke / benchmark runs (pretrain/mn40/pointnet2.pth is a download).  Per
+    layer in network order: weight and bias U(+-1/sqrt(fan_in)); each BatchNorm after its layer: gamma 1 + U(+-0.2), beta
+    U(+-0.1), running_mean N(0, 0.1), running_var U(0.5, 1.25).  The recipe (and so the numbers) is that of
+    tests/pointnet2_oracle.py make_weights."""
+    rng = np.random.default_rng(seed + 9201)
+    w: Dict[str, np.ndarray] = {}
+    for lin, bn, (co, ci), ones in pointnet2_layers():
+        b = 1.0 / np.sqrt(ci)
+        w[lin + ".weight"] = rng.uniform(-b, b, size=(co, ci) + (1,) * ones).astype(np.float32)
+        w[lin + ".bias"] = rng.uniform(-b, b, size=(co,)).astype(np.float32)
+        if bn:
+            w[bn + ".weight"] = (1.0 + rng.uniform(-0.2, 0.2, co)).astype(np.float32)
+            w[bn + ".bias"] = rng.uniform(-0.1, 0.1, co).astype(np.float32)
+            w[bn + ".running_mean"] = rng.normal(0.0, 0.1, co).astype(np.float32)
+            w[bn + ".running_var"] = rng.uniform(0.5, 1.25, co).astype(np.float32)
     return w

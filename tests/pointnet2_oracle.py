@@ -1,0 +1,226 @@
+"""PointNet2ClsSsg(num_classes=40) in eval mode restated, the test oracle of the PointNet++ victim (include/ifd_pn2.h).
+
+The two selection steps are numpy float32, exactly as the header defines them (``dist``, ``fps``, ``ball``): every difference,
+product and sum rounded on its own, strict comparisons, ties to the lowest index.  The layers follow
+baselines/model/pointnet2.py in torch (gather, subtract the centroid, cat, conv -> batch_norm -> relu with the 1 x 1 convolutions
+as linear layers on the grouped rows, max over the samples; the group-all level; the linear head), and run in float64 as the
+yardstick of the GPU's arithmetic.  A float64 run takes its index tables from outside (the float32 run's, or an
+implementation's): a different ball member moves the logits by far more than the arithmetic does.
+
+Weights: ``make_weights(seed)`` draws the un-folded state_dict from numpy's default_rng(seed + 9201), layers in network order
+(ifdefense_amd.weights.pointnet2_layers): weight and bias U(+-1/sqrt(fan_in)), then the layer's BatchNorm: gamma 1 + U(+-0.2), beta
+U(+-0.1), running_mean N(0, 0.1), running_var U(0.5, 1.25).  A dict WITHOUT BatchNorm keys (weights.fold_pointnet2's output) runs
+the same network with the BatchNorms left out.
+
+``make_calibrated_weights(seed)``: make_weights with fc3 alone replaced, by the recipe of dgcnn_oracle.make_calibrated_weights: with
+h [140,256] the float64 oracle's post-ReLU fc2 output on bench.synth_clouds(140, seed=31)[:, :128] (starts 0, 0), mu = h.mean(0),
+s = h.std(0), live = s > 1e-6 max(s):
+    fc3.weight <- fc3.weight * where(live, 1/s, 0)[None,:] * sqrt(3 * 256 / live.sum()),  fc3.bias <- -(fc3.weight @ mu),
+rounded to float32, so that the predicted class varies from cloud to cloud.  ``make_tied_weights`` copies fc3's rows 0..19 onto
+20..39: 20 exact ties in every cloud's logits."""
+import functools
+
+import numpy as np
+import torch
+import torch.nn.functional as F
+
+from ifdefense_amd.weights import BN_EPS, pointnet2_layers
+
+NP1, NS1, R1 = 512, 32, 0.2
+NP2, NS2, R2 = 128, 64, 0.4
+F32 = np.float32
+
+
+def make_weights(seed=0):
+    rng = np.random.default_rng(seed + 9201)
+    w = {}
+    for lin, bn, (co, ci), ones in pointnet2_layers():
+        b = 1.0 / np.sqrt(ci)
+        w[lin + ".weight"] = rng.uniform(-b, b, size=(co, ci) + (1,) * ones).astype(np.float32)
+        w[lin + ".bias"] = rng.uniform(-b, b, size=(co,)).astype(np.float32)
+        if bn:
+            w[bn + ".weight"] = (1.0 + rng.uniform(-0.2, 0.2, co)).astype(np.float32)
+            w[bn + ".bias"] = rng.uniform(-0.1, 0.1, co).astype(np.float32)
+            w[bn + ".running_mean"] = rng.normal(0.0, 0.1, co).astype(np.float32)
+            w[bn + ".running_var"] = rng.uniform(0.5, 1.25, co).astype(np.float32)
+    return w
+
+
+CALIBRATION_CLOUDS, CALIBRATION_SEED, CALIBRATION_POINTS = 140, 31, 128
+
+
+@functools.lru_cache(maxsize=None)
+def _calibrated_fc3(seed):
+    import bench
+    w = make_weights(seed)
+    x = bench.synth_clouds(CALIBRATION_CLOUDS, seed=CALIBRATION_SEED)[:, :CALIBRATION_POINTS]
+    h = forward(to_torch(w, torch.float64), x, dtype=torch.float64, tables=tables_of(x))["h2"].numpy()
+    mu, s = h.mean(0), h.std(0)
+    live = s > 1e-6 * s.max()
+    inv = np.where(live, 1.0 / np.where(live, s, 1.0), 0.0)
+    w3 = w["fc3.weight"].astype(np.float64) * inv[None, :] * np.sqrt(3.0 * 256 / live.sum())
+    return w3.astype(np.float32), (-(w3 @ mu)).astype(np.float32), int(live.sum())
+
+
+def make_calibrated_weights(seed=0):
+    """make_weights(seed) with fc3 rescaled so that the predicted class varies from cloud to cloud (module docstring)."""
+    w = make_weights(seed)
+    w3, b3, _ = _calibrated_fc3(int(seed))
+    w["fc3.weight"], w["fc3.bias"] = w3.copy(), b3.copy()
+    return w
+
+
+def make_tied_weights(w):
+    """A copy of ``w`` in which classes 20..39 are bit-identical twins of classes 0..19 (fc3's rows and biases copied)."""
+    w = {k: np.array(v, copy=True) for k, v in w.items()}
+    w["fc3.weight"][20:40] = w["fc3.weight"][0:20]
+    w["fc3.bias"][20:40] = w["fc3.bias"][0:20]
+    return w
+
+
+def reference_state_dict(w):
+    """make_weights' dict as nn.DataParallel saves the reference's model: torch tensors, ``module.`` prefix, num_batches_tracked."""
+    sd = {}
+    for k, v in w.items():
+        sd["module." + k] = torch.from_numpy(np.asarray(v))
+        if k.endswith(".running_var"):
+            sd["module." + k[:-len("running_var")] + "num_batches_tracked"] = torch.tensor(0, dtype=torch.long)
+    return sd
+
+
+def to_torch(w, dtype=torch.float32):
+    return {k: torch.as_tensor(np.asarray(v)).to(dtype) for k, v in w.items()}
+
+
+# ---- selection, numpy float32 (include/ifd_pn2.h) -------------------------------------------------------------------------
+def dist(x, c):
+    """x [n,3], c [3] or [m,1,3] float32 -> d = (dx dx + dy dy) + dz dz, every operation rounded to float32 on its own."""
+    x = np.asarray(x, F32)
+    d = (x - np.asarray(c, F32)).astype(F32)
+    sq = (d * d).astype(F32)
+    return ((sq[..., 0] + sq[..., 1]).astype(F32) + sq[..., 2]).astype(F32)
+
+
+def fps(x, npoint, start):
+    """x [n,3] -> [npoint] int32: the running distance starts at 1e10, is lowered where dist < running (strictly), and the next
+    pick is the largest running distance, the lowest index among equal ones."""
+    x = np.asarray(x, F32)
+    running = np.full(len(x), 1e10, F32)
+    out = np.empty(npoint, np.int32)
+    far = int(start)
+    assert 0 <= far < len(x)
+    for i in range(npoint):
+        out[i] = far
+        d = dist(x, x[far])
+        running = np.where(d < running, d, running)
+        far = int(np.argmax(running))                    # the first of equal maxima
+    return out
+
+
+def radius2(r):
+    return F32(float(r) * float(r))
+
+
+def ball(r, nsample, x, centroids):
+    """x [n,3], centroids [m,3] -> [m,nsample] int32: the first nsample j (ascending) with not (d_ij > r2), padded with the first."""
+    x, c = np.asarray(x, F32), np.asarray(centroids, F32)
+    member = ~(dist(x[None, :, :], c[:, None, :]) > radius2(r))
+    out = np.empty((len(c), nsample), np.int32)
+    for i in range(len(c)):
+        j = np.nonzero(member[i])[0][:nsample]
+        assert len(j) > 0, "a centroid outside its own ball"
+        out[i, :len(j)] = j
+        out[i, len(j):] = j[0]
+    return out
+
+
+def tables_of_cloud(x, start=(0, 0)):
+    """One cloud [n,3] -> {"fps1" [512], "fps2" [128], "ball1" [512,32], "ball2" [128,64]} int32."""
+    x = np.asarray(x, F32)
+    f1 = fps(x, NP1, start[0])
+    c1 = x[f1]
+    f2 = fps(c1, NP2, start[1])
+    return {"fps1": f1, "fps2": f2, "ball1": ball(R1, NS1, x, c1), "ball2": ball(R2, NS2, c1, c1[f2])}
+
+
+def tables_of(clouds, n_points=None, fps_start=None):
+    """A batch -> the four tables stacked over the clouds."""
+    clouds = _clouds(clouds, n_points)
+    per = [tables_of_cloud(c, (0, 0) if fps_start is None else fps_start[b]) for b, c in enumerate(clouds)]
+    return {k: np.stack([p[k] for p in per]) for k in ("fps1", "fps2", "ball1", "ball2")}
+
+
+def check_tables(x, t, start=(0, 0), what=""):
+    """The tables ``t`` of one cloud x [n,3] are the header's: every FPS pick is the lowest index of the largest running
+    distance, every ball row the first members in ascending index padded with the first.  Asserts with the first offender."""
+    x = np.asarray(x, F32)
+    want = tables_of_cloud(x, start)
+    for name in ("fps1", "fps2", "ball1", "ball2"):
+        got = np.asarray(t[name])
+        assert got.shape == want[name].shape, (what, name, got.shape)
+        bad = np.argwhere(got != want[name])
+        assert bad.size == 0, (what, name, "first difference at", tuple(bad[0]), "got", int(got[tuple(bad[0])]), "want",
+                               int(want[name][tuple(bad[0])]), "of %d" % len(bad))
+    return want
+
+
+# ---- the layers, torch -----------------------------------------------------------------------------------------------------
+def _bn(W, x, bn):
+    if bn and (bn + ".running_var") in W:
+        return F.batch_norm(x, W[bn + ".running_mean"], W[bn + ".running_var"], W[bn + ".weight"], W[bn + ".bias"], False, 0.0, BN_EPS)
+    return x
+
+
+def _sa(W, layers, new_points):
+    """new_points [B, npoint, nsample, C] -> [B, npoint, C']: the level's conv -> bn -> relu stack on every grouped row (a 1 x 1
+    convolution is a linear layer on the row) and the maximum over the samples."""
+    B, npoint, nsample, _ = new_points.shape
+    h = new_points.reshape(B * npoint * nsample, -1)
+    for lin, bn, (co, ci), _ in layers:
+        h = F.relu_(_bn(W, F.linear(h, W[lin + ".weight"].reshape(co, ci), W[lin + ".bias"]), bn))
+    return h.view(B, npoint, nsample, -1).max(2)[0]
+
+
+def _forward_batch(W, clouds, t, dtype):
+    """clouds: a list of [n_i,3] float32 arrays; t: the four tables [B,...] -> the outputs of the batch."""
+    L = pointnet2_layers()
+    B = len(clouds)
+    f1, f2 = torch.as_tensor(np.asarray(t["fps1"])).long(), torch.as_tensor(np.asarray(t["fps2"])).long()
+    b1, b2 = torch.as_tensor(np.asarray(t["ball1"])).long(), torch.as_tensor(np.asarray(t["ball2"])).long()
+    xs = [torch.from_numpy(c).to(dtype) for c in clouds]
+    c1 = torch.stack([x[f1[b]] for b, x in enumerate(xs)])                     # [B, 512, 3]
+    g1 = torch.stack([x[b1[b]] for b, x in enumerate(xs)]) - c1.view(B, NP1, 1, 3)      # [B, 512, 32, 3]
+    p1 = _sa(W, L[0:3], g1)                                                    # [B, 512, 128]
+    ar = torch.arange(B)
+    c2 = c1[ar[:, None], f2]                                                   # [B, 128, 3]
+    g2 = torch.cat([c1[ar[:, None, None], b2] - c2.view(B, NP2, 1, 3), p1[ar[:, None, None], b2]], dim=-1)
+    l2 = _sa(W, L[3:6], g2)                                                    # [B, 128, 256]
+    g3 = torch.cat([c2.view(B, 1, NP2, 3), l2.view(B, 1, NP2, -1)], dim=-1)
+    g = _sa(W, L[6:9], g3).view(B, 1024)
+    h1 = F.relu(_bn(W, F.linear(g, W["fc1.weight"], W["fc1.bias"]), "bn1"))
+    h2 = F.relu(_bn(W, F.linear(h1, W["fc2.weight"], W["fc2.bias"]), "bn2"))
+    lo = F.linear(h2, W["fc3.weight"], W["fc3.bias"])
+    return {"logits": lo, "l1_feat": p1, "l2_feat": l2, "global_feat": g, "h2": h2}
+
+
+def _clouds(x, n_points):
+    clouds = [np.asarray(c.cpu() if torch.is_tensor(c) else c, dtype=F32)[:, :3] for c in x]
+    if n_points is not None:
+        clouds = [c[:int(n)] for c, n in zip(clouds, n_points)]
+    return clouds
+
+
+def forward(W, x, n_points=None, fps_start=None, dtype=torch.float32, tables=None):
+    """x: [B,N,3] (point-major) or a list of [K_i,3]; n_points: [B] valid rows of each cloud; fps_start [B,2] (None: zeros).
+    tables: None (the oracle's own float32 selection) or {"fps1" [B,512], "fps2" [B,128], "ball1" [B,512,32], "ball2" [B,128,64]}
+    forced into the run.  -> {"logits" [B,40], "l1_feat" [B,512,128], "l2_feat" [B,128,256], "global_feat" [B,1024], "h2" [B,256]}
+    in ``dtype`` (W must be in it) and "tables", the tables used."""
+    clouds = _clouds(x, n_points)
+    if tables is None:
+        tables = tables_of(clouds, None, fps_start)
+    with torch.no_grad():
+        outs = [_forward_batch(W, clouds[a:a + 16], {k: np.asarray(v)[a:a + 16] for k, v in tables.items()}, dtype)
+                for a in range(0, len(clouds), 16)]
+    res = {k: torch.cat([o[k] for o in outs]) for k in outs[0]}
+    res["tables"] = tables
+    return res
