@@ -144,19 +144,16 @@ struct ifd_ctx {
     DeviceBuffer d_punet;
     PunetImage pimg{};
     DeviceBuffer ws_dup;
-    // victim classifier (ifd_cls_create): the PointNet weight image (pointnet.hip); its scratch is `ws`
-    DeviceBuffer d_cls;
+    // victim classifiers (ifd_cls_create, ifd_dgcnn_create, ifd_pn2_create): the weight image of the one victim a context holds -
+    // `model` says which, and so which of cimg / dimg / p2img describes it (pointnet.hip, dgcnn.hip, pointnet2.hip); the scratch is `ws`
+    DeviceBuffer d_victim;
     ClsImage cimg{};
     int cls_feature_transform = 0, cls_classes = 0;
     // ... and the backward pass's weight image (include/ifd_atk.h; contexts without feature_transform only)
     DeviceBuffer d_cls_grad;
     ClsGradImage gimg{};
-    // DGCNN victim (ifd_dgcnn_create): the split-form weight image (dgcnn.hip); its scratch is `ws`
-    DeviceBuffer d_dgcnn;
-    DgImage dimg{};
+    DgImage dimg{};                // DGCNN: the edge convolutions in split form
     int dg_k = 0;
-    // PointNet++ victim (ifd_pn2_create): the weight image (pointnet2.hip); its scratch is `ws`
-    DeviceBuffer d_pn2;
     Pn2Image p2img{};
     std::string err;
     unsigned long long* counters() const { return d_counters.get<unsigned long long>(); }
@@ -1438,10 +1435,80 @@ std::vector<ClsTensor> cls_layers(bool ft) {
     return k;
 }
 
-size_t cls_count(bool ft) {
+// ---- what the three victims' host code shares -----------------------------------------------------------------------
+// floats of a run of canonical layers (a vector or an array of ClsTensor), and where each of them begins
+template <class Layers>
+size_t layer_floats(const Layers& layers) {
     size_t n = 0;
-    for (const ClsTensor& t : cls_layers(ft)) n += (size_t)t.out * t.in + t.out;
+    for (const ClsTensor& t : layers) n += (size_t)t.out * t.in + t.out;
     return n;
+}
+template <class Layers>
+std::vector<size_t> layer_offsets(const Layers& layers) {
+    std::vector<size_t> at;
+    size_t src = 0;
+    for (const ClsTensor& t : layers) { at.push_back(src); src += (size_t)t.out * t.in + t.out; }
+    return at;
+}
+
+size_t cls_count(bool ft) { return layer_floats(cls_layers(ft)); }
+
+// the refusals every victim's create shares; false: g_create_error says why
+bool victim_create_args_ok(const char* who, const float* weights_host, size_t n_weights, size_t want, int n_classes) {
+    if (n_classes != CLS_CLASSES) {
+        g_create_error = std::string(who) + ": only n_classes = 40 (ModelNet40) is built, got " + std::to_string(n_classes);
+        return false;
+    }
+    if (!weights_host || n_weights != want) {
+        g_create_error = std::string(who) + ": expected " + std::to_string(want) + " weights, got " +
+                         (weights_host ? std::to_string(n_weights) : std::string("NULL"));
+        return false;
+    }
+    return true;
+}
+
+// Columns [skip, in) of the canonical layer t at W ([out][in], then the bias) appended to a device image row-major, then its
+// bias (DenseLayer, victim_linear.h).  pad_to_4: zeros behind it until the next block starts on 16 bytes.
+DenseLayer append_plain_layer(std::vector<float>& img, const float* W, const ClsTensor& t, int skip, bool pad_to_4) {
+    DenseLayer L;
+    L.n_out = t.out; L.n_in = t.in - skip;
+    L.w = (int)img.size();
+    for (int o = 0; o < t.out; ++o) img.insert(img.end(), W + (size_t)o * t.in + skip, W + (size_t)(o + 1) * t.in);
+    L.b = (int)img.size();
+    img.insert(img.end(), W + (size_t)t.out * t.in, W + (size_t)t.out * t.in + t.out);
+    while (pad_to_4 && img.size() % 4) img.push_back(0.f);
+    return L;
+}
+
+// The one blocking step of a call whose counts (starts, targets) are device memory: the n_words counters that a check kernel,
+// launched with result `launched`, leaves at `base` -> bad_out.  The caller words its own refusal from them.
+int read_bad_counts(ifd_ctx* ctx, const char* who, const char* what, hipError_t launched, const void* base, int n_words, int32_t* bad_out,
+                    hipStream_t s) {
+    hipError_t e = launched;
+    if (e == hipSuccess) e = hipMemcpyAsync(bad_out, base, (size_t)n_words * sizeof(int32_t), hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    if (e != hipSuccess) return fail(ctx, IFD_ERR_HIP, (std::string(who) + ": checking " + what).c_str(), e);
+    return IFD_OK;
+}
+
+// The skeleton of a victim's forward call over B clouds: chunks of at most max_chunk clouds, sized evenly; the context's workspace
+// grown to ws_off (bytes in front that belong to the caller) + ws_bytes(chunk); check(base) - the one blocking step, non-zero
+// refuses the call; then run_chunk(c0, n, carve) per chunk on a fresh Carve over the same workspace.
+template <class WsBytes, class Check, class RunChunk>
+int victim_forward(ifd_ctx* ctx, const char* who, int B, int max_chunk, size_t ws_off, WsBytes ws_bytes, Check check, RunChunk run_chunk) {
+    IFD_ON_CTX_DEVICE(ctx);
+    const int n_chunks = (B + max_chunk - 1) / max_chunk, chunk = (B + n_chunks - 1) / n_chunks;
+    hipError_t e = ctx->ws.grow(ws_off + ws_bytes(chunk));
+    if (e != hipSuccess) return fail(ctx, IFD_ERR_NOMEM, (std::string(who) + ": workspace").c_str(), e);
+    char* base = ctx->ws.get<char>() + ws_off;
+    if (int rc = check(base)) return rc;
+    for (int c0 = 0; c0 < B; c0 += chunk) {
+        const int n = std::min(chunk, B - c0);
+        Carve c(base);
+        e = run_chunk(c0, n, c);
+        if (e != hipSuccess) return fail(ctx, IFD_ERR_HIP, (std::string(who) + " launch").c_str(), e);
+    }
+    return IFD_OK;
 }
 
 // The device image: 3-input layers as [64][4] = {w0, w1, w2, bias}, every other layer as MFMA tiles (pointnet.hip header
@@ -1522,9 +1589,7 @@ size_t cls_ws_bytes(int n, int stride, bool ft) { return carved_bytes([&](Carve&
 // The backward pass's image (ifd_internal.h ClsGradImage) from the canonical vector of a model without feature_transform.
 std::vector<float> build_cls_grad_image(const float* w, const ClsImage& F, ClsGradImage& G) {
     const std::vector<ClsTensor> K = cls_layers(false);
-    std::vector<size_t> at(K.size());
-    size_t src = 0;
-    for (size_t k = 0; k < K.size(); ++k) { at[k] = src; src += (size_t)K[k].out * K[k].in + K[k].out; }
+    const std::vector<size_t> at = layer_offsets(K);
     std::vector<float> img;
     auto plain = [&](const float* p, size_t n) {
         const int o = (int)img.size();
@@ -1598,20 +1663,12 @@ ifd_ctx* ifd_cls_create(const float* weights_host, size_t n_weights, int model, 
         g_create_error = "ifd_cls_create: only PointNet (IFD_CLS_POINTNET) is built; PointNet++, DGCNN and PointConv are not";
         return nullptr;
     }
-    if (n_classes != CLS_CLASSES) {
-        g_create_error = "ifd_cls_create: only n_classes = 40 (ModelNet40) is built, got " + std::to_string(n_classes);
-        return nullptr;
-    }
     const bool ft = feature_transform != 0;
-    if (!weights_host || n_weights != cls_count(ft)) {
-        g_create_error = "ifd_cls_create: expected " + std::to_string(cls_count(ft)) + " weights, got " +
-                         (weights_host ? std::to_string(n_weights) : std::string("NULL"));
-        return nullptr;
-    }
+    if (!victim_create_args_ok("ifd_cls_create", weights_host, n_weights, cls_count(ft), n_classes)) return nullptr;
     return create_ctx("ifd_cls_create", IFD_MODEL_CLS, device, [&](ifd_ctx* ctx) {
         ctx->cls_feature_transform = ft ? 1 : 0;
         ctx->cls_classes = n_classes;
-        hipError_t e = upload(ctx->d_cls, build_cls_image(weights_host, ft, ctx->cimg));
+        hipError_t e = upload(ctx->d_victim, build_cls_image(weights_host, ft, ctx->cimg));
         if (e == hipSuccess && !ft) e = upload(ctx->d_cls_grad, build_cls_grad_image(weights_host, ctx->cimg, ctx->gimg));
         return e;
     });
@@ -1626,45 +1683,37 @@ namespace {
 int cls_forward_impl(ifd_ctx* ctx, const float* pc, const int32_t* n_points, int B, int stride, float* logits, const ifd_cls_aux* aux,
                      void* stream, bool check_counts, size_t ws_off) {
     if (!ctx) return IFD_ERR_ARG;
-    if (ctx->model != IFD_MODEL_CLS || !ctx->d_cls.get()) return fail(ctx, IFD_ERR_ARG, "ifd_cls_forward: not a classifier context");
+    if (ctx->model != IFD_MODEL_CLS || !ctx->d_victim.get()) return fail(ctx, IFD_ERR_ARG, "ifd_cls_forward: not a classifier context");
     if (!pc || !logits || B < 1 || stride < 1 || stride > IFD_CLS_MAX_POINTS)
         return fail(ctx, IFD_ERR_ARG, "ifd_cls_forward: bad argument (B >= 1, 1 <= stride <= 10000)");
     const bool ft = ctx->cls_feature_transform != 0;
     if (aux && aux->trans_feat && !ft)
         return fail(ctx, IFD_ERR_ARG, "ifd_cls_forward: trans_feat asked of a model without feature_transform");
-    IFD_ON_CTX_DEVICE(ctx);
     hipStream_t s = static_cast<hipStream_t>(stream);
-    const int n_chunks = (B + CLS_CHUNK - 1) / CLS_CHUNK, chunk = (B + n_chunks - 1) / n_chunks;
-    hipError_t e = ctx->ws.grow(ws_off + cls_ws_bytes(chunk, stride, ft));
-    if (e != hipSuccess) return fail(ctx, IFD_ERR_NOMEM, "ifd_cls_forward: workspace", e);
-    char* base = ctx->ws.get<char>() + ws_off;
-    if (n_points && check_counts) {       // the one blocking step: the counts are device memory
-        int32_t bad = 0;
-        e = launch_cls_check(n_points, B, stride, reinterpret_cast<int32_t*>(base), s);
-        if (e == hipSuccess) e = hipMemcpyAsync(&bad, base, sizeof(bad), hipMemcpyDeviceToHost, s);
-        if (e == hipSuccess) e = hipStreamSynchronize(s);
-        if (e != hipSuccess) return fail(ctx, IFD_ERR_HIP, "ifd_cls_forward: checking n_points", e);
-        if (bad != 0) {
-            const std::string msg = "ifd_cls_forward: " + std::to_string(bad) + " cloud(s) with n_points outside [1, stride]";
-            return fail(ctx, IFD_ERR_ARG, msg.c_str());
-        }
-    }
     const int nc = ctx->cls_classes;
-    for (int c0 = 0; c0 < B; c0 += chunk) {
-        const int n = std::min(chunk, B - c0);
-        Carve c(base);
-        const ClsWs w = cls_ws(c, (size_t)n, stride, ft);
-        e = launch_cls(ctx->d_cls.get<float>(), ctx->cimg, ft, pc + (size_t)c0 * stride * 3, n_points ? n_points + c0 : nullptr, n, stride, w,
-                       logits + (size_t)c0 * nc, nc, aux && aux->pred ? aux->pred + c0 : nullptr, s);
-        if (e == hipSuccess && aux && aux->trans)
-            e = hipMemcpy2DAsync(aux->trans + (size_t)c0 * 9, 36, w.trans, 64, 36, (size_t)n, hipMemcpyDeviceToDevice, s);
-        if (e == hipSuccess && aux && aux->trans_feat)
-            e = hipMemcpyAsync(aux->trans_feat + (size_t)c0 * 4096, w.tfeat, (size_t)n * 4096 * 4, hipMemcpyDeviceToDevice, s);
-        if (e == hipSuccess && aux && aux->global_feat)
-            e = hipMemcpyAsync(aux->global_feat + (size_t)c0 * CLS_FEAT, w.gmax, (size_t)n * CLS_FEAT * 4, hipMemcpyDeviceToDevice, s);
-        if (e != hipSuccess) return fail(ctx, IFD_ERR_HIP, "ifd_cls_forward launch", e);
-    }
-    return IFD_OK;
+    return victim_forward(
+        ctx, "ifd_cls_forward", B, CLS_CHUNK, ws_off, [&](int chunk) { return cls_ws_bytes(chunk, stride, ft); },
+        [&](char* base) {
+            if (!n_points || !check_counts) return (int)IFD_OK;
+            int32_t bad = 0;
+            if (int rc = read_bad_counts(ctx, "ifd_cls_forward", "n_points", launch_count_check(n_points, B, 1, stride, reinterpret_cast<int32_t*>(base), s),
+                                         base, 1, &bad, s))
+                return rc;
+            if (bad == 0) return (int)IFD_OK;
+            return fail(ctx, IFD_ERR_ARG, ("ifd_cls_forward: " + std::to_string(bad) + " cloud(s) with n_points outside [1, stride]").c_str());
+        },
+        [&](int c0, int n, Carve& c) {
+            const ClsWs w = cls_ws(c, (size_t)n, stride, ft);
+            hipError_t e = launch_cls(ctx->d_victim.get<float>(), ctx->cimg, ft, pc + (size_t)c0 * stride * 3, n_points ? n_points + c0 : nullptr, n,
+                                      stride, w, logits + (size_t)c0 * nc, nc, aux && aux->pred ? aux->pred + c0 : nullptr, s);
+            if (e == hipSuccess && aux && aux->trans)
+                e = hipMemcpy2DAsync(aux->trans + (size_t)c0 * 9, 36, w.trans, 64, 36, (size_t)n, hipMemcpyDeviceToDevice, s);
+            if (e == hipSuccess && aux && aux->trans_feat)
+                e = hipMemcpyAsync(aux->trans_feat + (size_t)c0 * 4096, w.tfeat, (size_t)n * 4096 * 4, hipMemcpyDeviceToDevice, s);
+            if (e == hipSuccess && aux && aux->global_feat)
+                e = hipMemcpyAsync(aux->global_feat + (size_t)c0 * CLS_FEAT, w.gmax, (size_t)n * CLS_FEAT * 4, hipMemcpyDeviceToDevice, s);
+            return e;
+        });
 }
 
 }  // namespace
@@ -1687,18 +1736,13 @@ static_assert(DG_MAX_POINTS == IFD_DGCNN_MAX_POINTS && DG_MAX_K == IFD_DGCNN_MAX
 // the canonical order: conv1 .. conv5, linear1 .. linear3
 const ClsTensor DG_LAYERS[8] = {{64, 6}, {64, 128}, {128, 128}, {256, 256}, {DG_EMB, DG_FEAT}, {512, 2 * DG_EMB}, {256, 512}, {CLS_CLASSES, 256}};
 
-size_t dgcnn_count() {
-    size_t n = 0;
-    for (const ClsTensor& t : DG_LAYERS) n += (size_t)t.out * t.in + t.out;
-    return n;
-}
+size_t dgcnn_count() { return layer_floats(DG_LAYERS); }
 
 // The device image (ifd_internal.h DgImage): the edge convolutions in split form - rows P = Wa, then Q = Wb - Wa (rounded to
 // f32 once, here) with the bias - everything else row-major as it comes.
 std::vector<float> build_dgcnn_image(const float* w, DgImage& I) {
     std::vector<float> img;
-    size_t at[8], src = 0;
-    for (int k = 0; k < 8; ++k) { at[k] = src; src += (size_t)DG_LAYERS[k].out * DG_LAYERS[k].in + DG_LAYERS[k].out; }
+    const std::vector<size_t> at = layer_offsets(DG_LAYERS);
     {
         const float* W = w + at[0];
         I.first = (int)img.size();
@@ -1713,7 +1757,7 @@ std::vector<float> build_dgcnn_image(const float* w, DgImage& I) {
     for (int l = 0; l < 3; ++l) {
         const int co = DG_LAYERS[l + 1].out, C = DG_LAYERS[l + 1].in / 2;
         const float* W = w + at[l + 1];
-        DgLayer& L = I.pq[l];
+        DenseLayer& L = I.pq[l];
         L.n_out = 2 * co; L.n_in = C;
         L.w = (int)img.size();
         img.resize(img.size() + (size_t)2 * co * C);
@@ -1726,16 +1770,7 @@ std::vector<float> build_dgcnn_image(const float* w, DgImage& I) {
         img.resize(img.size() + 2 * co, 0.f);
         for (int o = 0; o < co; ++o) img[L.b + co + o] = W[(size_t)co * 2 * C + o];
     }
-    auto plain = [&](int k) {
-        const ClsTensor& t = DG_LAYERS[k];
-        DgLayer L;
-        L.n_out = t.out; L.n_in = t.in;
-        L.w = (int)img.size();
-        img.insert(img.end(), w + at[k], w + at[k] + (size_t)t.out * t.in);
-        L.b = (int)img.size();
-        img.insert(img.end(), w + at[k] + (size_t)t.out * t.in, w + at[k] + (size_t)t.out * t.in + t.out);
-        return L;
-    };
+    auto plain = [&](int k) { return append_plain_layer(img, w + at[k], DG_LAYERS[k], 0, false); };
     I.conv5 = plain(4);
     for (int j = 0; j < 3; ++j) I.fc[j] = plain(5 + j);
     I.total = (int)img.size();
@@ -1768,26 +1803,18 @@ ifd_ctx* ifd_dgcnn_create(const float* weights_host, size_t n_weights, int k, in
         g_create_error = "ifd_dgcnn_create: k must lie in [1, 32], got " + std::to_string(k);
         return nullptr;
     }
-    if (n_classes != CLS_CLASSES) {
-        g_create_error = "ifd_dgcnn_create: only n_classes = 40 (ModelNet40) is built, got " + std::to_string(n_classes);
-        return nullptr;
-    }
-    if (!weights_host || n_weights != dgcnn_count()) {
-        g_create_error = "ifd_dgcnn_create: expected " + std::to_string(dgcnn_count()) + " weights, got " +
-                         (weights_host ? std::to_string(n_weights) : std::string("NULL"));
-        return nullptr;
-    }
+    if (!victim_create_args_ok("ifd_dgcnn_create", weights_host, n_weights, dgcnn_count(), n_classes)) return nullptr;
     return create_ctx("ifd_dgcnn_create", IFD_MODEL_DGCNN, device, [&](ifd_ctx* ctx) {
         ctx->dg_k = k;
         ctx->cls_classes = n_classes;
-        return upload(ctx->d_dgcnn, build_dgcnn_image(weights_host, ctx->dimg));
+        return upload(ctx->d_victim, build_dgcnn_image(weights_host, ctx->dimg));
     });
 }
 
 int ifd_dgcnn_forward(ifd_ctx* ctx, const float* pc, const int32_t* n_points, int B, int stride, float* logits,
                       const ifd_dgcnn_aux* aux, void* stream) {
     if (!ctx) return IFD_ERR_ARG;
-    if (ctx->model != IFD_MODEL_DGCNN || !ctx->d_dgcnn.get()) return fail(ctx, IFD_ERR_ARG, "ifd_dgcnn_forward: not a DGCNN context");
+    if (ctx->model != IFD_MODEL_DGCNN || !ctx->d_victim.get()) return fail(ctx, IFD_ERR_ARG, "ifd_dgcnn_forward: not a DGCNN context");
     const int k = ctx->dg_k;
     if (!pc || !logits || B < 1) return fail(ctx, IFD_ERR_ARG, "ifd_dgcnn_forward: bad argument (pc, logits, B >= 1)");
     if (stride > IFD_DGCNN_MAX_POINTS) return fail(ctx, IFD_ERR_ARG, "ifd_dgcnn_forward: stride above 2048");
@@ -1795,41 +1822,33 @@ int ifd_dgcnn_forward(ifd_ctx* ctx, const float* pc, const int32_t* n_points, in
         const std::string msg = "ifd_dgcnn_forward: clouds of " + std::to_string(stride) + " points, fewer than k = " + std::to_string(k);
         return fail(ctx, IFD_ERR_ARG, msg.c_str());
     }
-    IFD_ON_CTX_DEVICE(ctx);
     hipStream_t s = static_cast<hipStream_t>(stream);
-    const int n_chunks = (B + DG_CHUNK - 1) / DG_CHUNK, chunk = (B + n_chunks - 1) / n_chunks;
-    hipError_t e = ctx->ws.grow(dgcnn_ws_bytes(chunk, stride, k));
-    if (e != hipSuccess) return fail(ctx, IFD_ERR_NOMEM, "ifd_dgcnn_forward: workspace", e);
-    char* base = ctx->ws.get<char>();
-    if (n_points) {                       // the one blocking step: the counts are device memory
-        int32_t bad = 0;
-        e = launch_dgcnn_check(n_points, B, stride, k, reinterpret_cast<int32_t*>(base), s);
-        if (e == hipSuccess) e = hipMemcpyAsync(&bad, base, sizeof(bad), hipMemcpyDeviceToHost, s);
-        if (e == hipSuccess) e = hipStreamSynchronize(s);
-        if (e != hipSuccess) return fail(ctx, IFD_ERR_HIP, "ifd_dgcnn_forward: checking n_points", e);
-        if (bad != 0) {
+    const int nc = ctx->cls_classes;
+    return victim_forward(
+        ctx, "ifd_dgcnn_forward", B, DG_CHUNK, 0, [&](int chunk) { return dgcnn_ws_bytes(chunk, stride, k); },
+        [&](char* base) {
+            if (!n_points) return (int)IFD_OK;
+            int32_t bad = 0;
+            if (int rc = read_bad_counts(ctx, "ifd_dgcnn_forward", "n_points",
+                                         launch_count_check(n_points, B, k, stride, reinterpret_cast<int32_t*>(base), s), base, 1, &bad, s))
+                return rc;
+            if (bad == 0) return (int)IFD_OK;
             const std::string msg = "ifd_dgcnn_forward: " + std::to_string(bad) + " cloud(s) with n_points outside [k, stride] (k = " +
                                     std::to_string(k) + ": a cloud needs at least k points)";
             return fail(ctx, IFD_ERR_ARG, msg.c_str());
-        }
-    }
-    const int nc = ctx->cls_classes;
-    for (int c0 = 0; c0 < B; c0 += chunk) {
-        const int n = std::min(chunk, B - c0);
-        Carve c(base);
-        const DgWs w = dgcnn_ws(c, (size_t)n, stride, k);
-        DgOut o{};
-        if (aux) {
-            for (int l = 0; l < 4; ++l) o.idx[l] = aux->idx[l] ? aux->idx[l] + (size_t)c0 * stride * k : nullptr;
-            o.feat = aux->feat ? aux->feat + (size_t)c0 * stride * DG_FEAT : nullptr;
-            o.gfeat = aux->global_feat ? aux->global_feat + (size_t)c0 * 2 * DG_EMB : nullptr;
-            o.pred = aux->pred ? aux->pred + c0 : nullptr;
-        }
-        e = launch_dgcnn(ctx->d_dgcnn.get<float>(), ctx->dimg, pc + (size_t)c0 * stride * 3, n_points ? n_points + c0 : nullptr, n, stride,
-                         k, w, o, logits + (size_t)c0 * nc, nc, s);
-        if (e != hipSuccess) return fail(ctx, IFD_ERR_HIP, "ifd_dgcnn_forward launch", e);
-    }
-    return IFD_OK;
+        },
+        [&](int c0, int n, Carve& c) {
+            const DgWs w = dgcnn_ws(c, (size_t)n, stride, k);
+            DgOut o{};
+            if (aux) {
+                for (int l = 0; l < 4; ++l) o.idx[l] = aux->idx[l] ? aux->idx[l] + (size_t)c0 * stride * k : nullptr;
+                o.feat = aux->feat ? aux->feat + (size_t)c0 * stride * DG_FEAT : nullptr;
+                o.gfeat = aux->global_feat ? aux->global_feat + (size_t)c0 * 2 * DG_EMB : nullptr;
+                o.pred = aux->pred ? aux->pred + c0 : nullptr;
+            }
+            return launch_dgcnn(ctx->d_victim.get<float>(), ctx->dimg, pc + (size_t)c0 * stride * 3, n_points ? n_points + c0 : nullptr, n,
+                                stride, k, w, o, logits + (size_t)c0 * nc, nc, s);
+        });
 }
 
 }  // extern "C"
@@ -1845,18 +1864,13 @@ static_assert(PN2_MAX_POINTS == IFD_PN2_MAX_POINTS && PN2_NP1 == IFD_PN2_NPOINT1
 const ClsTensor PN2_LAYERS[12] = {{64, 3}, {64, 64}, {128, 64}, {128, 131}, {128, 128}, {256, 128}, {256, 259}, {512, 256},
                                   {PN2_EMB, 512}, {512, PN2_EMB}, {256, 512}, {CLS_CLASSES, 256}};
 
-size_t pn2_count() {
-    size_t n = 0;
-    for (const ClsTensor& t : PN2_LAYERS) n += (size_t)t.out * t.in + t.out;
-    return n;
-}
+size_t pn2_count() { return layer_floats(PN2_LAYERS); }
 
 // The device image (ifd_internal.h Pn2Image): a layer whose input begins with three coordinate columns is split into those
 // columns, as [out][4] rows, and a plain layer of the feature columns; everything else row-major as it comes.
 std::vector<float> build_pn2_image(const float* w, Pn2Image& I) {
     std::vector<float> img;
-    size_t at[12], src = 0;
-    for (int k = 0; k < 12; ++k) { at[k] = src; src += (size_t)PN2_LAYERS[k].out * PN2_LAYERS[k].in + PN2_LAYERS[k].out; }
+    const std::vector<size_t> at = layer_offsets(PN2_LAYERS);
     // the three coordinate columns of layer k -> [out][4] = {w0, w1, w2, bias where with_bias}
     auto coords = [&](int k, bool with_bias) {
         const ClsTensor& t = PN2_LAYERS[k];
@@ -1869,19 +1883,8 @@ std::vector<float> build_pn2_image(const float* w, Pn2Image& I) {
         }
         return off;
     };
-    // columns [skip, in) of layer k as a plain layer
-    auto plain = [&](int k, int skip) {
-        const ClsTensor& t = PN2_LAYERS[k];
-        const float* W = w + at[k];
-        Pn2Layer L;
-        L.n_out = t.out; L.n_in = t.in - skip;
-        L.w = (int)img.size();
-        for (int o = 0; o < t.out; ++o) img.insert(img.end(), W + (size_t)o * t.in + skip, W + (size_t)(o + 1) * t.in);
-        L.b = (int)img.size();
-        img.insert(img.end(), W + (size_t)t.out * t.in, W + (size_t)t.out * t.in + t.out);
-        while (img.size() % 4) img.push_back(0.f);                    // every block starts on 16 bytes
-        return L;
-    };
+    // columns [skip, in) of layer k as a plain layer; every block starts on 16 bytes
+    auto plain = [&](int k, int skip) { return append_plain_layer(img, w + at[k], PN2_LAYERS[k], skip, true); };
     I.sa1_first = coords(0, true);
     I.sa1[0] = plain(1, 0); I.sa1[1] = plain(2, 0);
     I.sa2_xyz = coords(3, false);
@@ -1917,18 +1920,10 @@ int ifd_pn2_abi_version(void) { return IFD_PN2_ABI_VERSION; }
 size_t ifd_pn2_weight_count(void) { return pn2_count(); }
 
 ifd_ctx* ifd_pn2_create(const float* weights_host, size_t n_weights, int n_classes, int device) {
-    if (n_classes != CLS_CLASSES) {
-        g_create_error = "ifd_pn2_create: only n_classes = 40 (ModelNet40) is built, got " + std::to_string(n_classes);
-        return nullptr;
-    }
-    if (!weights_host || n_weights != pn2_count()) {
-        g_create_error = "ifd_pn2_create: expected " + std::to_string(pn2_count()) + " weights, got " +
-                         (weights_host ? std::to_string(n_weights) : std::string("NULL"));
-        return nullptr;
-    }
+    if (!victim_create_args_ok("ifd_pn2_create", weights_host, n_weights, pn2_count(), n_classes)) return nullptr;
     return create_ctx("ifd_pn2_create", IFD_MODEL_PN2, device, [&](ifd_ctx* ctx) {
         ctx->cls_classes = n_classes;
-        hipError_t e = upload(ctx->d_pn2, build_pn2_image(weights_host, ctx->p2img));
+        hipError_t e = upload(ctx->d_victim, build_pn2_image(weights_host, ctx->p2img));
         if (e == hipSuccess) e = configure_pn2_kernels();
         return e;
     });
@@ -1937,52 +1932,42 @@ ifd_ctx* ifd_pn2_create(const float* weights_host, size_t n_weights, int n_class
 int ifd_pn2_forward(ifd_ctx* ctx, const float* pc, const int32_t* n_points, const int32_t* fps_start, int B, int stride, float* logits,
                     const ifd_pn2_aux* aux, void* stream) {
     if (!ctx) return IFD_ERR_ARG;
-    if (ctx->model != IFD_MODEL_PN2 || !ctx->d_pn2.get()) return fail(ctx, IFD_ERR_ARG, "ifd_pn2_forward: not a PointNet++ context");
+    if (ctx->model != IFD_MODEL_PN2 || !ctx->d_victim.get()) return fail(ctx, IFD_ERR_ARG, "ifd_pn2_forward: not a PointNet++ context");
     if (!pc || !logits || B < 1 || stride < 1) return fail(ctx, IFD_ERR_ARG, "ifd_pn2_forward: bad argument (pc, logits, B >= 1, stride >= 1)");
     if (stride > IFD_PN2_MAX_POINTS) return fail(ctx, IFD_ERR_ARG, "ifd_pn2_forward: stride above 2048");
-    IFD_ON_CTX_DEVICE(ctx);
     hipStream_t s = static_cast<hipStream_t>(stream);
-    const int n_chunks = (B + PN2_CHUNK - 1) / PN2_CHUNK, chunk = (B + n_chunks - 1) / n_chunks;
-    hipError_t e = ctx->ws.grow(pn2_ws_bytes(chunk));
-    if (e != hipSuccess) return fail(ctx, IFD_ERR_NOMEM, "ifd_pn2_forward: workspace", e);
-    char* base = ctx->ws.get<char>();
-    if (n_points || fps_start) {          // the one blocking step: counts and starts are device memory
-        int32_t bad[2] = {0, 0};
-        e = launch_pn2_check(n_points, fps_start, B, stride, reinterpret_cast<int32_t*>(base), s);
-        if (e == hipSuccess) e = hipMemcpyAsync(bad, base, sizeof(bad), hipMemcpyDeviceToHost, s);
-        if (e == hipSuccess) e = hipStreamSynchronize(s);
-        if (e != hipSuccess) return fail(ctx, IFD_ERR_HIP, "ifd_pn2_forward: checking n_points and fps_start", e);
-        if (bad[0] != 0) {
-            const std::string msg = "ifd_pn2_forward: " + std::to_string(bad[0]) + " cloud(s) with n_points outside [1, stride]";
-            return fail(ctx, IFD_ERR_ARG, msg.c_str());
-        }
-        if (bad[1] != 0) {
-            const std::string msg = "ifd_pn2_forward: " + std::to_string(bad[1]) +
-                                    " cloud(s) with fps_start outside [0, n_points) x [0, 512)";
-            return fail(ctx, IFD_ERR_ARG, msg.c_str());
-        }
-    }
     const int nc = ctx->cls_classes;
-    for (int c0 = 0; c0 < B; c0 += chunk) {
-        const int n = std::min(chunk, B - c0);
-        Carve c(base);
-        const Pn2Ws w = pn2_ws(c, (size_t)n);
-        Pn2Out o{};
-        if (aux) {
-            o.fps1 = aux->fps1 ? aux->fps1 + (size_t)c0 * PN2_NP1 : nullptr;
-            o.fps2 = aux->fps2 ? aux->fps2 + (size_t)c0 * PN2_NP2 : nullptr;
-            o.ball1 = aux->ball1 ? aux->ball1 + (size_t)c0 * PN2_NP1 * PN2_NS1 : nullptr;
-            o.ball2 = aux->ball2 ? aux->ball2 + (size_t)c0 * PN2_NP2 * PN2_NS2 : nullptr;
-            o.l1_feat = aux->l1_feat ? aux->l1_feat + (size_t)c0 * PN2_NP1 * 128 : nullptr;
-            o.l2_feat = aux->l2_feat ? aux->l2_feat + (size_t)c0 * PN2_NP2 * 256 : nullptr;
-            o.gfeat = aux->global_feat ? aux->global_feat + (size_t)c0 * PN2_EMB : nullptr;
-            o.pred = aux->pred ? aux->pred + c0 : nullptr;
-        }
-        e = launch_pn2(ctx->d_pn2.get<float>(), ctx->p2img, pc + (size_t)c0 * stride * 3, n_points ? n_points + c0 : nullptr,
-                       fps_start ? fps_start + (size_t)c0 * 2 : nullptr, n, stride, w, o, logits + (size_t)c0 * nc, nc, s);
-        if (e != hipSuccess) return fail(ctx, IFD_ERR_HIP, "ifd_pn2_forward launch", e);
-    }
-    return IFD_OK;
+    return victim_forward(
+        ctx, "ifd_pn2_forward", B, PN2_CHUNK, 0, [&](int chunk) { return pn2_ws_bytes(chunk); },
+        [&](char* base) {
+            if (!n_points && !fps_start) return (int)IFD_OK;
+            int32_t bad[2] = {0, 0};
+            if (int rc = read_bad_counts(ctx, "ifd_pn2_forward", "n_points and fps_start",
+                                         launch_pn2_check(n_points, fps_start, B, stride, reinterpret_cast<int32_t*>(base), s), base, 2, bad, s))
+                return rc;
+            if (bad[0] != 0)
+                return fail(ctx, IFD_ERR_ARG, ("ifd_pn2_forward: " + std::to_string(bad[0]) + " cloud(s) with n_points outside [1, stride]").c_str());
+            if (bad[1] != 0)
+                return fail(ctx, IFD_ERR_ARG,
+                            ("ifd_pn2_forward: " + std::to_string(bad[1]) + " cloud(s) with fps_start outside [0, n_points) x [0, 512)").c_str());
+            return (int)IFD_OK;
+        },
+        [&](int c0, int n, Carve& c) {
+            const Pn2Ws w = pn2_ws(c, (size_t)n);
+            Pn2Out o{};
+            if (aux) {
+                o.fps1 = aux->fps1 ? aux->fps1 + (size_t)c0 * PN2_NP1 : nullptr;
+                o.fps2 = aux->fps2 ? aux->fps2 + (size_t)c0 * PN2_NP2 : nullptr;
+                o.ball1 = aux->ball1 ? aux->ball1 + (size_t)c0 * PN2_NP1 * PN2_NS1 : nullptr;
+                o.ball2 = aux->ball2 ? aux->ball2 + (size_t)c0 * PN2_NP2 * PN2_NS2 : nullptr;
+                o.l1_feat = aux->l1_feat ? aux->l1_feat + (size_t)c0 * PN2_NP1 * 128 : nullptr;
+                o.l2_feat = aux->l2_feat ? aux->l2_feat + (size_t)c0 * PN2_NP2 * 256 : nullptr;
+                o.gfeat = aux->global_feat ? aux->global_feat + (size_t)c0 * PN2_EMB : nullptr;
+                o.pred = aux->pred ? aux->pred + c0 : nullptr;
+            }
+            return launch_pn2(ctx->d_victim.get<float>(), ctx->p2img, pc + (size_t)c0 * stride * 3, n_points ? n_points + c0 : nullptr,
+                              fps_start ? fps_start + (size_t)c0 * 2 : nullptr, n, stride, w, o, logits + (size_t)c0 * nc, nc, s);
+        });
 }
 
 }  // extern "C"
@@ -1991,7 +1976,7 @@ int ifd_pn2_forward(ifd_ctx* ctx, const float* pc, const int32_t* n_points, cons
 namespace {
 
 int atk_context_ok(ifd_ctx* ctx, const char* who) {
-    if (ctx->model != IFD_MODEL_CLS || !ctx->d_cls.get()) return fail(ctx, IFD_ERR_ARG, (std::string(who) + ": not a classifier context").c_str());
+    if (ctx->model != IFD_MODEL_CLS || !ctx->d_victim.get()) return fail(ctx, IFD_ERR_ARG, (std::string(who) + ": not a classifier context").c_str());
     if (ctx->cls_feature_transform || !ctx->d_cls_grad.get())
         return fail(ctx, IFD_ERR_ARG, (std::string(who) + ": input gradients are not built for a model with feature_transform").c_str());
     return IFD_OK;
@@ -2002,10 +1987,9 @@ int atk_context_ok(ifd_ctx* ctx, const char* who) {
 int atk_check(ifd_ctx* ctx, const char* who, const int32_t* n_points, const int32_t* target, int B, int lo, int hi,
               const std::string& range_text, hipStream_t s) {
     int32_t bad[2] = {0, 0};
-    hipError_t e = launch_atk_check(n_points, target, B, lo, hi, ctx->cls_classes, ctx->ws.get<int32_t>(), s);
-    if (e == hipSuccess) e = hipMemcpyAsync(bad, ctx->ws.get(), sizeof(bad), hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
-    if (e != hipSuccess) return fail(ctx, IFD_ERR_HIP, (std::string(who) + ": checking n_points and target").c_str(), e);
+    if (int rc = read_bad_counts(ctx, who, "n_points and target", launch_atk_check(n_points, target, B, lo, hi, ctx->cls_classes, ctx->ws.get<int32_t>(), s),
+                                 ctx->ws.get(), 2, bad, s))
+        return rc;
     if (bad[0] != 0)
         return fail(ctx, IFD_ERR_ARG, (std::string(who) + ": " + std::to_string(bad[0]) + " cloud(s) with n_points outside " + range_text).c_str());
     if (bad[1] != 0)
@@ -2036,9 +2020,9 @@ int input_grad_impl(ifd_ctx* ctx, size_t ws_off, const float* pc, const int32_t*
         const ClsGradWs w = cls_grad_ws(c, n, stride);
         const float* pcc = pc + (size_t)c0 * stride * 3;
         const int32_t* npc = n_points ? n_points + c0 : nullptr;
-        hipError_t e = launch_cls_win(ctx->d_cls.get<float>(), ctx->cimg, pcc, npc, (int)n, stride, w, nc, s);
+        hipError_t e = launch_cls_win(ctx->d_victim.get<float>(), ctx->cimg, pcc, npc, (int)n, stride, w, nc, s);
         if (e == hipSuccess)
-            e = launch_cls_backward(ctx->d_cls.get<float>(), ctx->cimg, ctx->d_cls_grad.get<float>(), ctx->gimg, pcc, npc, (int)n, stride, target + c0, loss_kind, kappa,
+            e = launch_cls_backward(ctx->d_victim.get<float>(), ctx->cimg, ctx->d_cls_grad.get<float>(), ctx->gimg, pcc, npc, (int)n, stride, target + c0, loss_kind, kappa,
                                     scale, w, nc, grad + (size_t)c0 * stride * 3, s);
         auto copy = [&](void* dst, size_t dst_off, const void* src, size_t bytes_per_cloud) {
             if (e == hipSuccess && dst)

@@ -16,44 +16,25 @@
 //                       a thread only queues what beats its threshold and the wave works all queues off together.  The n x n
 //                       matrix never exists.
 //   dg_first_kernel     P | Q of the C = 3 layer, plain fused multiply-adds
-//   dg_linear_kernel    Y = act(W X + b) on v_mfma_f32_16x16x4_f32, weights row-major as the canonical vector has them.  A wave
-//                       owns 32 rows (points, or clouds in the FC head) x 32 outputs; per output the bias, then four chains
-//                       over interleaved 16-input groups, added pairwise - fc_kernel's arithmetic (pointnet.hip).  <true>: conv5,
-//                       whose [points, 1024] output is reduced to the maximum and the sum of each 64-point tile at once.
+//   linear_kernel       victim_linear.h: Y = leaky(W X + b), per output the bias, then four chains across all inputs, added
+//                       pairwise.  <DgLinear>: P | Q of conv2 .. conv4 and the FC head; <DgConv5>: conv5, whose [points, 1024]
+//                       output is reduced to the maximum and the sum of each 64-point tile at once.
 //   dg_gather_kernel    out_i = leaky(max_j P_j + Q_i) over the k neighbours of idx, written into its columns of feat
 //   dg_pool_kernel      a cloud's tiles -> max | mean [2048]; the sum runs over the tiles in ascending order, and a tile's sum is
 //                       a fixed tree, so the mean depends on nothing but the cloud's own rows and count.  No atomics.
-//   dg_argmax_kernel    the lowest class among equal logits
+// The prediction is launch_argmax's (pointnet.hip): the lowest class among equal logits.
 //
 // Columns of an MFMA never mix: a point's (a cloud's) result depends on nothing but its own row, whatever shares its wave.
 #include "ifd_device.h"
 #include "ifd_internal.h"
 #include "lds_layout.h"
+#include "victim_linear.h"
 
 namespace ifd {
 
 namespace {
 
-__device__ __forceinline__ f32x4 mfma4(const f32x4 a, const f32x4 b, f32x4 c) {
-    c = __builtin_amdgcn_mfma_f32_16x16x4f32(a[0], b[0], c, 0, 0, 0);
-    c = __builtin_amdgcn_mfma_f32_16x16x4f32(a[1], b[1], c, 0, 0, 0);
-    c = __builtin_amdgcn_mfma_f32_16x16x4f32(a[2], b[2], c, 0, 0, 0);
-    c = __builtin_amdgcn_mfma_f32_16x16x4f32(a[3], b[3], c, 0, 0, 0);
-    return c;
-}
-__device__ __forceinline__ float leaky(float v) { return v > 0.f ? v : 0.2f * v; }
-__device__ __forceinline__ f32x4 leaky4(f32x4 v) { return f32x4{leaky(v[0]), leaky(v[1]), leaky(v[2]), leaky(v[3])}; }
-
-__device__ __forceinline__ int cloud_points(const int32_t* __restrict__ n_points, int b, int stride) {
-    const int n = n_points ? n_points[b] : stride;
-    return min(max(n, 1), stride);                                     // counts outside [k, stride] are refused by the host
-}
-
-__global__ __launch_bounds__(256) void dg_check_kernel(const int32_t* __restrict__ n_points, int B, int stride, int k,
-                                                       int32_t* __restrict__ bad) {
-    const int b = blockIdx.x * 256 + threadIdx.x;
-    if (b < B && (n_points[b] < k || n_points[b] > stride)) atomicAdd(bad, 1);
-}
+static_assert(DG_TILE == LINEAR_TILE, "dg_pool_kernel walks the tiles linear_kernel<DgConv5> wrote");
 
 // X: rows of ldx floats, C of them used; a cloud's rows start at X + b * xb
 template <int C>
@@ -167,119 +148,6 @@ __global__ __launch_bounds__(256) void dg_first_kernel(const float* __restrict__
     *reinterpret_cast<f32x4*>(pq + ((size_t)b * stride + i) * DG_FEAT + o) = v;
 }
 
-// Y[row][o] = act(bias[o] + sum_c W[o][c] X[row][c]), o < M (a multiple of 4), K a multiple of 64.  Rows: the first n_points[b]
-// (stride where null) of cloud b = blockIdx.z; X rows of ldx floats from X + b * xb, Y rows of ldy floats from Y + b * yb.
-// A workgroup = 64 rows x 64 outputs, wave w = row half (w & 1) x output half (w >> 1), two 16 x 16 tiles each way.
-// POOL (conv5; M = 1024, always LeakyReLU): nothing is stored but the maximum and the sum over the workgroup's valid rows,
-// part_max / part_sum [b][T][M] at tile blockIdx.x.
-template <bool POOL>
-__global__ __launch_bounds__(256) void dg_linear_kernel(const float* __restrict__ W, const float* __restrict__ bias, int M, int K,
-                                                        const float* __restrict__ X, int ldx, size_t xb,
-                                                        const int32_t* __restrict__ n_points, int stride, float* __restrict__ Y, int ldy,
-                                                        size_t yb, int act, float* __restrict__ part_max, float* __restrict__ part_sum,
-                                                        int T) {
-    __shared__ __attribute__((aligned(16))) float red[POOL ? DgPoolLds::BYTES / 4 : 4];
-    const int b = blockIdx.z;
-    const int n = cloud_points(n_points, b, stride);
-    const int row0 = blockIdx.x * DG_TILE;
-    if (row0 >= n) return;                                             // the whole workgroup
-    const int wv = threadIdx.x >> 6, l = threadIdx.x & 63, q = l >> 4, p = l & 15;
-    const int rbase = row0 + 32 * (wv & 1), obase = blockIdx.y * 64 + 32 * (wv >> 1);
-    const float* Xb = X + (size_t)b * xb;
-    const float* xr[2];
-    const float* wr[2];
-    bool valid[2];
-#pragma unroll
-    for (int t = 0; t < 2; ++t) {
-        const int i = rbase + 16 * t + p;
-        valid[t] = i < n;
-        xr[t] = Xb + (size_t)min(i, n - 1) * ldx + 4 * q;              // rows beyond the cloud compute on its last row, unused
-        wr[t] = W + (size_t)min(obase + 16 * t + p, M - 1) * K + 4 * q;
-    }
-    const f32x4 zero = f32x4{0.f, 0.f, 0.f, 0.f};
-    f32x4 acc[2][2][4];                                                // [row tile][output tile][chain]
-#pragma unroll
-    for (int m = 0; m < 2; ++m) {
-        f32x4 bv = zero;
-        if (bias) {
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const int o = obase + 16 * m + 4 * q + r;
-                bv[r] = o < M ? bias[o] : 0.f;
-            }
-        }
-#pragma unroll
-        for (int t = 0; t < 2; ++t) {
-            acc[t][m][0] = bv;
-            acc[t][m][1] = acc[t][m][2] = acc[t][m][3] = zero;
-        }
-    }
-    for (int g = 0; g < K; g += 64) {
-        f32x4 xv[2][4], wt[2][4];
-#pragma unroll
-        for (int t = 0; t < 2; ++t)
-#pragma unroll
-            for (int c = 0; c < 4; ++c) {
-                xv[t][c] = *reinterpret_cast<const f32x4*>(xr[t] + g + 16 * c);
-                wt[t][c] = *reinterpret_cast<const f32x4*>(wr[t] + g + 16 * c);
-            }
-#pragma unroll
-        for (int c = 0; c < 4; ++c)
-#pragma unroll
-            for (int m = 0; m < 2; ++m)
-#pragma unroll
-                for (int t = 0; t < 2; ++t) acc[t][m][c] = mfma4(wt[m][c], xv[t][c], acc[t][m][c]);
-    }
-    f32x4 v[2][2];
-#pragma unroll
-    for (int t = 0; t < 2; ++t)
-#pragma unroll
-        for (int m = 0; m < 2; ++m) {
-            v[t][m] = (acc[t][m][0] + acc[t][m][1]) + (acc[t][m][2] + acc[t][m][3]);
-            if (POOL || act) v[t][m] = leaky4(v[t][m]);
-        }
-    if (!POOL) {
-        float* Yb = Y + (size_t)b * yb;
-#pragma unroll
-        for (int t = 0; t < 2; ++t)
-#pragma unroll
-            for (int m = 0; m < 2; ++m) {
-                const int i = rbase + 16 * t + p, o = obase + 16 * m + 4 * q;
-                if (valid[t] && o < M) *reinterpret_cast<f32x4*>(Yb + (size_t)i * ldy + o) = v[t][m];
-            }
-        return;
-    }
-    float* rmax = LDS_AT(float, red, DgPoolLds::MAX);
-    float* rsum = LDS_AT(float, red, DgPoolLds::SUM);
-#pragma unroll
-    for (int m = 0; m < 2; ++m) {
-        f32x4 mx = f32x4{-INFINITY, -INFINITY, -INFINITY, -INFINITY}, sm = zero;
-#pragma unroll
-        for (int t = 0; t < 2; ++t)
-            if (valid[t]) {
-#pragma unroll
-                for (int r = 0; r < 4; ++r) { mx[r] = fmaxf(mx[r], v[t][m][r]); sm[r] += v[t][m][r]; }
-            }
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {                                  // over the 16 rows of the lanes: a butterfly, every lane the same tree
-            float x = mx[r], s = sm[r];
-#pragma unroll
-            for (int d = 1; d < 16; d <<= 1) { x = fmaxf(x, __shfl_xor(x, d)); s += __shfl_xor(s, d); }
-            mx[r] = x; sm[r] = s;
-        }
-        if (p == 0) {
-            *reinterpret_cast<f32x4*>(rmax + (wv & 1) * 64 + 32 * (wv >> 1) + 16 * m + 4 * q) = mx;
-            *reinterpret_cast<f32x4*>(rsum + (wv & 1) * 64 + 32 * (wv >> 1) + 16 * m + 4 * q) = sm;
-        }
-    }
-    __syncthreads();
-    if (threadIdx.x < 64) {
-        const size_t at = ((size_t)b * T + blockIdx.x) * M + blockIdx.y * 64 + threadIdx.x;
-        part_max[at] = fmaxf(rmax[threadIdx.x], rmax[64 + threadIdx.x]);
-        part_sum[at] = rsum[threadIdx.x] + rsum[64 + threadIdx.x];
-    }
-}
-
 // pq rows of DG_FEAT floats: P in [0, cout), Q in [cout, 2 cout).  feat[b][i][col + c] = leaky(max_j P[idx[i][j]][c] + Q[i][c]).
 // A thread = one point x four channels; a workgroup = 1024 / cout points.
 __global__ __launch_bounds__(256) void dg_gather_kernel(const float* __restrict__ pq, const int32_t* __restrict__ idx,
@@ -322,25 +190,6 @@ __global__ __launch_bounds__(256) void dg_pool_kernel(const float* __restrict__ 
     *reinterpret_cast<f32x4*>(gfeat + (size_t)b * 2 * DG_EMB + DG_EMB + c) = f32x4{s[0] / fn, s[1] / fn, s[2] / fn, s[3] / fn};
 }
 
-__global__ __launch_bounds__(256) void dg_argmax_kernel(const float* __restrict__ logits, int B, int n_classes, int32_t* __restrict__ pred) {
-    const int b = blockIdx.x * 256 + threadIdx.x;
-    if (b >= B) return;
-    const float* L = logits + (size_t)b * n_classes;
-    float bv = L[0];
-    int bi = 0;
-    for (int c = 1; c < n_classes; ++c)
-        if (L[c] > bv) { bv = L[c]; bi = c; }                          // strict: the lowest class among equals
-    pred[b] = bi;
-}
-
-// one layer on rows [B clouds][n_points rows]
-void launch_linear(const float* img, const DgLayer& L, const float* X, int ldx, size_t xb, const int32_t* n_points, int B, int stride,
-                   float* Y, int ldy, size_t yb, int act, hipStream_t s) {
-    hipLaunchKernelGGL((dg_linear_kernel<false>), dim3((stride + DG_TILE - 1) / DG_TILE, (L.n_out + 63) / 64, B), dim3(256), 0, s,
-                       img + L.w, img + L.b, L.n_out, L.n_in, X, ldx, xb, n_points, stride, Y, ldy, yb, act, (float*)nullptr,
-                       (float*)nullptr, 0);
-}
-
 template <int C>
 void launch_knn(const float* X, int ldx, size_t xb, const int32_t* n_points, int B, int stride, int k, float* nrm, int32_t* idx,
                 hipStream_t s) {
@@ -350,13 +199,6 @@ void launch_knn(const float* X, int ldx, size_t xb, const int32_t* n_points, int
 }
 
 }  // namespace
-
-hipError_t launch_dgcnn_check(const int32_t* n_points, int B, int stride, int k, int32_t* bad, hipStream_t s) {
-    hipError_t e = hipMemsetAsync(bad, 0, sizeof(int32_t), s);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(dg_check_kernel, dim3((B + 255) / 256), dim3(256), 0, s, n_points, B, stride, k, bad);
-    return hipGetLastError();
-}
 
 hipError_t launch_dgcnn(const float* img, const DgImage& I, const float* pc, const int32_t* n_points, int B, int stride, int k,
                         const DgWs& w, const DgOut& out, float* logits, int n_classes, hipStream_t s) {
@@ -376,22 +218,20 @@ hipError_t launch_dgcnn(const float* img, const DgImage& I, const float* pc, con
         idx = out.idx[l + 1] ? out.idx[l + 1] : w.idx;
         if (cin[l] == 64) launch_knn<64>(feat + col_in[l], DG_FEAT, fb, n_points, B, stride, k, w.nrm, idx, s);
         else launch_knn<128>(feat + col_in[l], DG_FEAT, fb, n_points, B, stride, k, w.nrm, idx, s);
-        launch_linear(img, I.pq[l], feat + col_in[l], DG_FEAT, fb, n_points, B, stride, w.pq, DG_FEAT, fb, 0, s);
+        launch_linear<DgLinear>(img, I.pq[l], feat + col_in[l], DG_FEAT, fb, n_points, B, stride, w.pq, DG_FEAT, fb, 0, s);
         const int ppb = 1024 / cout[l];
         hipLaunchKernelGGL(dg_gather_kernel, dim3((stride + ppb - 1) / ppb, B), block, 0, s, (const float*)w.pq, (const int32_t*)idx,
                            n_points, stride, k, cout[l], col_out[l], feat);
     }
     // conv5 + LeakyReLU -> max | mean over the points
     const int T = (stride + DG_TILE - 1) / DG_TILE;
-    hipLaunchKernelGGL((dg_linear_kernel<true>), dim3(T, DG_EMB / 64, B), block, 0, s, img + I.conv5.w, img + I.conv5.b, DG_EMB, DG_FEAT,
-                       (const float*)feat, DG_FEAT, fb, n_points, stride, (float*)nullptr, 0, (size_t)0, 1, w.part_max, w.part_sum, T);
+    launch_linear<DgConv5>(img, I.conv5, feat, DG_FEAT, fb, n_points, B, stride, nullptr, 0, 0, 1, s, nullptr, nullptr, w.part_max, w.part_sum);
     hipLaunchKernelGGL(dg_pool_kernel, dim3(B), block, 0, s, (const float*)w.part_max, (const float*)w.part_sum, n_points, stride, T, gfeat);
     // the head, a cloud a row
-    launch_linear(img, I.fc[0], gfeat, 2 * DG_EMB, 0, nullptr, 1, B, w.f1, 512, 0, 1, s);
-    launch_linear(img, I.fc[1], w.f1, 512, 0, nullptr, 1, B, w.f2, 256, 0, 1, s);
-    launch_linear(img, I.fc[2], w.f2, 256, 0, nullptr, 1, B, logits, n_classes, 0, 0, s);
-    if (out.pred) hipLaunchKernelGGL(dg_argmax_kernel, dim3((B + 255) / 256), block, 0, s, (const float*)logits, B, n_classes, out.pred);
-    return hipGetLastError();
+    launch_linear<DgLinear>(img, I.fc[0], gfeat, 2 * DG_EMB, 0, nullptr, 1, B, w.f1, 512, 0, 1, s);
+    launch_linear<DgLinear>(img, I.fc[1], w.f1, 512, 0, nullptr, 1, B, w.f2, 256, 0, 1, s);
+    launch_linear<DgLinear>(img, I.fc[2], w.f2, 256, 0, nullptr, 1, B, logits, n_classes, 0, 0, s);
+    return out.pred ? launch_argmax(logits, B, n_classes, out.pred, s) : hipGetLastError();
 }
 
 }  // namespace ifd

@@ -228,7 +228,11 @@ hipError_t launch_punet(const float* img, const PunetImage& I, const float* xyz,
 // ---- victim classifier: PointNet (pointnet.hip; C ABI in include/ifd_cls.h) ------------------------------------------
 constexpr int CLS_TILE = 256;           // points of one workgroup of the fused point-MLP + max kernel
 constexpr int CLS_FEAT = 1024;          // width of the max-pooled feature
-struct ClsFc { int w, b, n_out, n_in; };    // float offsets of a layer's tile image (punet.hip layout) and padded bias
+// One dense layer inside a device image, as float offsets of its weight and bias.  PointNet's FC layers (ClsFc) keep the weight
+// as an MFMA tile image (punet.hip layout) with a padded bias; DGCNN's and PointNet++'s keep it row-major [n_out][n_in] with
+// bias [n_out] (victim_linear.h).
+struct DenseLayer { int w, b, n_out, n_in; };
+using ClsFc = DenseLayer;
 // One per-point stack ending in the max over points: [3 -> 64] (plain FMAs), optionally [64 -> 64], [64 -> 128], [128 -> 1024].
 struct ClsStack { int first, mid_w, mid_b, w2, b2, w3, b3; };      // first: [64][4] = {w0, w1, w2, bias} per output channel
 struct ClsImage {
@@ -244,8 +248,10 @@ struct ClsWs {                          // per-chunk scratch of launch_cls (api.
     float* trans;    // [B][16]      (9 used)
     float* tfeat;    // [B][4096]    (feature_transform only)
 };
-// bad[0] = number of clouds with n_points outside [1, stride]
-hipError_t launch_cls_check(const int32_t* n_points, int B, int stride, int32_t* bad, hipStream_t s);
+// bad[0] = number of clouds with n_points (not null) outside [lo, hi]: [1, stride], or [k, stride] for DGCNN
+hipError_t launch_count_check(const int32_t* n_points, int B, int lo, int hi, int32_t* bad, hipStream_t s);
+// pred[b] = the lowest class among the largest logits of cloud b (torch.argmax on the CPU): the one tie rule of all victims
+hipError_t launch_argmax(const float* logits, int B, int n_classes, int32_t* pred, hipStream_t s);
 hipError_t launch_cls(const float* img, const ClsImage& I, bool feature_transform, const float* pc, const int32_t* n_points, int B,
                       int stride, const ClsWs& w, float* logits, int n_classes, int32_t* pred, hipStream_t s);
 
@@ -421,14 +427,13 @@ constexpr int DG_EMB = 1024;            // conv5's width; the global feature is 
 constexpr int DG_TILE = 64;             // points of one workgroup of the MFMA layers, and of one partial max / sum of conv5
 constexpr int DG_KNN_THREADS = 64;      // queries of one workgroup of the kNN kernel, a thread each
 constexpr int DG_KNN_PEND = 8;          // candidates a thread queues before the wave updates its lists together
-struct DgLayer { int w, b, n_out, n_in; };     // float offsets into the device image: weight row-major [n_out][n_in], bias [n_out]
 // The device image (api.cpp build_dgcnn_image).  The four edge convolutions are stored in split form: per layer the rows
 // P = Wa (no bias) then Q = Wb - Wa (the folded bias), n_out = 2 Cout, n_in = C.  first: the C = 3 layer as [128][4] rows
 // {w0, w1, w2, bias}.
 struct DgImage {
     int first;
-    DgLayer pq[3];                      // conv2, conv3, conv4
-    DgLayer conv5, fc[3];
+    DenseLayer pq[3];                   // conv2, conv3, conv4
+    DenseLayer conv5, fc[3];
     int total;
 };
 struct DgWs {                           // per-chunk scratch of launch_dgcnn (api.cpp dgcnn_ws)
@@ -448,8 +453,6 @@ struct DgOut {                          // where the caller wants the intermedia
     float* gfeat;
     int32_t* pred;
 };
-// bad[0] = number of clouds with n_points outside [k, stride]
-hipError_t launch_dgcnn_check(const int32_t* n_points, int B, int stride, int k, int32_t* bad, hipStream_t s);
 hipError_t launch_dgcnn(const float* img, const DgImage& I, const float* pc, const int32_t* n_points, int B, int stride, int k,
                         const DgWs& w, const DgOut& out, float* logits, int n_classes, hipStream_t s);
 
@@ -461,18 +464,17 @@ constexpr int PN2_EMB = 1024;           // width of the global feature
 constexpr int PN2_FPS_THREADS = 256;    // a cloud a workgroup of the sampling kernel: thread t owns the points t + 256 k
 // radius ** 2 of the reference (a Python double), compared against the float32 distances in float32
 __host__ __device__ constexpr float pn2_radius2(int level) { return level == 0 ? (float)(0.2 * 0.2) : (float)(0.4 * 0.4); }
-struct Pn2Layer { int w, b, n_out, n_in; };    // float offsets into the device image: weight row-major [n_out][n_in], bias [n_out]
 // The device image (api.cpp build_pn2_image).  A layer whose input begins with three coordinate columns is stored as two blocks:
 // those columns as [n_out][4] rows {w0, w1, w2, bias or 0} and the feature columns as a plain layer.  sa1_first carries sa1's
 // first bias; sa2_u and sa3_u carry theirs, so sa2_xyz and sa3_xyz end in 0.
 struct Pn2Image {
     int sa1_first;                      // [64][4]
-    Pn2Layer sa1[2];                    // 64 -> 64, 64 -> 128
+    DenseLayer sa1[2];                  // 64 -> 64, 64 -> 128
     int sa2_xyz;                        // [128][4]
-    Pn2Layer sa2_u, sa2[2];             // 128 -> 128 (the feature columns of the first layer); 128 -> 128, 128 -> 256
+    DenseLayer sa2_u, sa2[2];           // 128 -> 128 (the feature columns of the first layer); 128 -> 128, 128 -> 256
     int sa3_xyz;                        // [256][4]
-    Pn2Layer sa3_u, sa3[2];             // 256 -> 256; 256 -> 512, 512 -> 1024
-    Pn2Layer fc[3];
+    DenseLayer sa3_u, sa3[2];           // 256 -> 256; 256 -> 512, 512 -> 1024
+    DenseLayer fc[3];
     int total;
 };
 struct Pn2Ws {                          // per-chunk scratch of launch_pn2 (api.cpp pn2_ws)

@@ -314,11 +314,15 @@ __host__ __device__ constexpr DgKnnLdsAt dg_knn_lds_at(int k) {
     return l;
 }
 static_assert(dg_knn_lds_at(DG_MAX_K).BYTES == 20480, "LDS of dg_knn_kernel");
-struct DgPoolLds {                                   // dg_linear_kernel<true>: the two row halves' maxima and sums of 64 channels
+
+// ---- victim_linear.h ----------------------------------------------------------------------------------------------------------
+template <bool SUM_TOO>
+struct LinearPoolLds {                               // linear_kernel's pool: the two row halves' maxima (and sums) of 64 channels
     static constexpr size_t MAX = 0;                                       // float [2][64]
-    static constexpr size_t SUM = MAX + 2 * 64 * 4;                        // float [2][64]
-    static constexpr size_t BYTES = SUM + 2 * 64 * 4;
+    static constexpr size_t SUM = MAX + 2 * 64 * 4;                        // float [2][64], only with SUM_TOO
+    static constexpr size_t BYTES = SUM + (SUM_TOO ? 2 * 64 * 4 : 0);
 };
+static_assert(LinearPoolLds<true>::BYTES == 1024 && LinearPoolLds<false>::BYTES == 512, "LDS of linear_kernel's pool");
 
 // ---- pointnet2.hip ------------------------------------------------------------------------------------------------------------
 template <int PPT>
@@ -344,10 +348,6 @@ struct Pn2Sa2Lds {                                   // pn2_sa2_kernel
     static constexpr size_t BYTES = RED + 2 * 256 * 4;
 };
 static_assert(Pn2Sa1Lds::BYTES == 34816 && Pn2Sa2Lds::BYTES == 69632 && Pn2Sa2Lds::BYTES <= LDS_MAX_BYTES, "LDS of the grouped MLPs");
-struct Pn2PoolLds {                                  // pn2_linear_kernel<true>: the two row halves' maxima of 64 channels
-    static constexpr size_t MAX = 0;                                       // float [2][64]
-    static constexpr size_t BYTES = MAX + 2 * 64 * 4;
-};
 
 // ---- block_sum / block_max / block_sum_d write one value per wave into their scratch ------------------------------------------
 static_assert((RepLds::BYTES - RepLds::SCRATCH) / 4 >= OPT_THREADS / 64 && (NrmLds::BYTES - NrmLds::SCRATCH) / 4 >= OPT_THREADS / 64,

@@ -24,6 +24,7 @@
 // result depends on nothing but its own rows, whatever shares its wave.
 #include "ifd_device.h"
 #include "ifd_internal.h"
+#include "victim_device.h"
 
 namespace ifd {
 
@@ -31,16 +32,6 @@ namespace {
 
 typedef int32_t i32x4 __attribute__((ext_vector_type(4)));
 
-__device__ __forceinline__ f32x4 mfma4(const f32x4 a, const f32x4 b, f32x4 c) {
-    c = __builtin_amdgcn_mfma_f32_16x16x4f32(a[0], b[0], c, 0, 0, 0);
-    c = __builtin_amdgcn_mfma_f32_16x16x4f32(a[1], b[1], c, 0, 0, 0);
-    c = __builtin_amdgcn_mfma_f32_16x16x4f32(a[2], b[2], c, 0, 0, 0);
-    c = __builtin_amdgcn_mfma_f32_16x16x4f32(a[3], b[3], c, 0, 0, 0);
-    return c;
-}
-__device__ __forceinline__ f32x4 relu4(f32x4 v) {
-    return f32x4{fmaxf(v[0], 0.f), fmaxf(v[1], 0.f), fmaxf(v[2], 0.f), fmaxf(v[3], 0.f)};
-}
 __device__ __forceinline__ f32x4 max4(f32x4 a, f32x4 b) {
     return f32x4{fmaxf(a[0], b[0]), fmaxf(a[1], b[1]), fmaxf(a[2], b[2]), fmaxf(a[3], b[3])};
 }
@@ -322,9 +313,9 @@ __global__ __launch_bounds__(256) void argmax_kernel(const float* __restrict__ l
     pred[b] = bi;
 }
 
-__global__ __launch_bounds__(256) void check_counts_kernel(const int32_t* __restrict__ n_points, int B, int stride, int32_t* __restrict__ bad) {
+__global__ __launch_bounds__(256) void check_counts_kernel(const int32_t* __restrict__ n_points, int B, int lo, int hi, int32_t* __restrict__ bad) {
     const int b = blockIdx.x * 256 + threadIdx.x;
-    if (b < B && (n_points[b] < 1 || n_points[b] > stride)) atomicAdd(bad, 1);
+    if (b < B && (n_points[b] < lo || n_points[b] > hi)) atomicAdd(bad, 1);
 }
 
 void launch_fc(const float* img, const ClsFc& L, const float* x, int B, int relu, int eye, float* out, int ldo, hipStream_t s) {
@@ -341,10 +332,15 @@ void launch_fc_stack(const float* img, const ClsFc (&F)[3], int B, const ClsWs& 
 
 }  // namespace
 
-hipError_t launch_cls_check(const int32_t* n_points, int B, int stride, int32_t* bad, hipStream_t s) {
+hipError_t launch_count_check(const int32_t* n_points, int B, int lo, int hi, int32_t* bad, hipStream_t s) {
     hipError_t e = hipMemsetAsync(bad, 0, sizeof(int32_t), s);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(check_counts_kernel, dim3((B + 255) / 256), dim3(256), 0, s, n_points, B, stride, bad);
+    hipLaunchKernelGGL(check_counts_kernel, dim3((B + 255) / 256), dim3(256), 0, s, n_points, B, lo, hi, bad);
+    return hipGetLastError();
+}
+
+hipError_t launch_argmax(const float* logits, int B, int n_classes, int32_t* pred, hipStream_t s) {
+    hipLaunchKernelGGL(argmax_kernel, dim3((B + 255) / 256), dim3(256), 0, s, logits, B, n_classes, pred);
     return hipGetLastError();
 }
 
@@ -366,8 +362,7 @@ hipError_t launch_cls(const float* img, const ClsImage& I, bool feature_transfor
                        feature_transform ? (const float*)w.tfeat : (const float*)nullptr, w.part, T);
     hipLaunchKernelGGL(tile_max_kernel, dim3(B), block, 0, s, (const float*)w.part, n_points, stride, T, w.gmax);
     launch_fc_stack(img, I.head_fc, B, w, 0, logits, n_classes, s);
-    if (pred) hipLaunchKernelGGL(argmax_kernel, dim3((B + 255) / 256), block, 0, s, (const float*)logits, B, n_classes, pred);
-    return hipGetLastError();
+    return pred ? launch_argmax(logits, B, n_classes, pred, s) : hipGetLastError();
 }
 
 // launch_cls without feature_transform, keeping what the backward pass needs (ClsGradWs): both stacks' maxima and winners and
@@ -388,8 +383,7 @@ hipError_t launch_cls_win(const float* img, const ClsImage& I, const float* pc, 
     hipLaunchKernelGGL(tile_max_win_kernel, dim3(B), block, 0, s, (const float*)w.part, (const int32_t*)w.part_idx, n_points, stride, T,
                        w.gmax, w.win);
     launch_fc_stack(img, I.head_fc, B, h, 0, w.logits, n_classes, s);
-    hipLaunchKernelGGL(argmax_kernel, dim3((B + 255) / 256), block, 0, s, (const float*)w.logits, B, n_classes, w.pred);
-    return hipGetLastError();
+    return launch_argmax(w.logits, B, n_classes, w.pred, s);
 }
 
 }  // namespace ifd

@@ -14,34 +14,22 @@
 //   pn2_sa1_kernel        64 rows = two 32-sample groups: 3 -> 64 by plain FMAs into LDS, 64 -> 64 and 64 -> 128 on MFMA, the
 //                         maximum over each group's rows.  A wave's 32 rows are one group, so the maximum never leaves the wave.
 //   pn2_sa2_kernel        64 rows = one 64-sample group.  The first layer in split form: U_j = b + W_f f_j per level-1 point
-//                         (pn2_linear_kernel, 512 rows instead of 8192), then relu(U_j + W_xyz (xyz_j - c_i)) per row with the
+//                         (linear_kernel, 512 rows instead of 8192), then relu(U_j + W_xyz (xyz_j - c_i)) per row with the
 //                         difference formed first, as the reference forms it; 128 -> 128 and 128 -> 256 on MFMA, the maximum.
-//   pn2_linear_kernel     Y = act(W X + b [+ W_xyz xyz]) on v_mfma_f32_16x16x4_f32, dg_linear_kernel's tiling (dgcnn.hip): sa2's
-//                         U, the three layers of sa3 (<true>: the last, reduced to the maxima of its two 64-row tiles), the head.
-//   pn2_pool_kernel, pn2_argmax_kernel
+//   linear_kernel         victim_linear.h: Y = relu(W X + b [+ W_xyz xyz]) in blocks of 64 inputs.  <Pn2Linear>: sa2's U, the
+//                         first two layers of sa3, the head; <Pn2Sa3Last>: sa3's last layer, reduced to the maxima of its two
+//                         64-row tiles.  The grouped MLPs' tile_layer runs the same 64-input block (linear_block64) from LDS.
+//   pn2_pool_kernel       a cloud's two tiles -> its [1024] feature.  The prediction is launch_argmax's (pointnet.hip).
 //
 // Columns of an MFMA never mix, and no kernel looks at another cloud: a cloud's result depends on nothing but its own rows.
 #include "ifd_device.h"
 #include "ifd_internal.h"
 #include "lds_layout.h"
+#include "victim_linear.h"
 
 namespace ifd {
 
 namespace {
-
-__device__ __forceinline__ f32x4 mfma4(const f32x4 a, const f32x4 b, f32x4 c) {
-    c = __builtin_amdgcn_mfma_f32_16x16x4f32(a[0], b[0], c, 0, 0, 0);
-    c = __builtin_amdgcn_mfma_f32_16x16x4f32(a[1], b[1], c, 0, 0, 0);
-    c = __builtin_amdgcn_mfma_f32_16x16x4f32(a[2], b[2], c, 0, 0, 0);
-    c = __builtin_amdgcn_mfma_f32_16x16x4f32(a[3], b[3], c, 0, 0, 0);
-    return c;
-}
-__device__ __forceinline__ f32x4 relu4(f32x4 v) { return f32x4{fmaxf(v[0], 0.f), fmaxf(v[1], 0.f), fmaxf(v[2], 0.f), fmaxf(v[3], 0.f)}; }
-
-__device__ __forceinline__ int cloud_points(const int32_t* __restrict__ n_points, int b, int stride) {
-    const int n = n_points ? n_points[b] : stride;
-    return min(max(n, 1), stride);                                     // counts outside [1, stride] are refused by the host
-}
 
 // d = (dx dx + dy dy) + dz dz, every product and sum rounded on its own (include/ifd_pn2.h).  hipcc contracts by default, and
 // __fmul_rn / __fadd_rn are plain operators to it, so the contraction is switched off for exactly this function.
@@ -157,13 +145,11 @@ __global__ __launch_bounds__(256) void pn2_ball_kernel(const float* __restrict__
 }
 
 // One layer on a 64-row tile in LDS: v[t][m] = bias + sum_c W[o][c] Xs[row][c], row = 32 (wv & 1) + 16 t + p, o = obase + 16 m +
-// 4 q + r.  The inputs go in blocks of 64: a block is four chains of 16 inputs from zero, added pairwise ((c0 + c1) + (c2 + c3)), and
-// the blocks are added to the bias in ascending order - chains of 16, not of K / 4, which is what the 512-wide layers need to stay
-// within the float32 oracle's error.  W row-major [..][K] in global memory.
+// 4 q + r, then ReLU.  linear_kernel's CUT64 arithmetic (victim_linear.h): the blocks of 64 inputs are added to the bias in ascending
+// order.  W row-major [..][K] in global memory.
 template <int K, int LDX>
 __device__ __forceinline__ void tile_layer(const float* __restrict__ Xs, const float* __restrict__ W, const float* __restrict__ bias,
                                            int obase, int wv, int q, int p, f32x4 (&v)[2][2]) {
-    const f32x4 zero = f32x4{0.f, 0.f, 0.f, 0.f};
     const float* xr[2];
     const float* wr[2];
 #pragma unroll
@@ -179,27 +165,7 @@ __device__ __forceinline__ void tile_layer(const float* __restrict__ Xs, const f
         for (int t = 0; t < 2; ++t) sum[t][m] = bv;
     }
 #pragma unroll
-    for (int g = 0; g < K; g += 64) {
-        f32x4 xv[2][4], wt[2][4];
-#pragma unroll
-        for (int t = 0; t < 2; ++t)
-#pragma unroll
-            for (int c = 0; c < 4; ++c) {
-                xv[t][c] = *reinterpret_cast<const f32x4*>(xr[t] + g + 16 * c);
-                wt[t][c] = *reinterpret_cast<const f32x4*>(wr[t] + g + 16 * c);
-            }
-        f32x4 acc[2][2][4];                                            // [row tile][output tile][chain] of this 64-input block
-#pragma unroll
-        for (int c = 0; c < 4; ++c)
-#pragma unroll
-            for (int m = 0; m < 2; ++m)
-#pragma unroll
-                for (int t = 0; t < 2; ++t) acc[t][m][c] = mfma4(wt[m][c], xv[t][c], zero);
-#pragma unroll
-        for (int t = 0; t < 2; ++t)
-#pragma unroll
-            for (int m = 0; m < 2; ++m) sum[t][m] += (acc[t][m][0] + acc[t][m][1]) + (acc[t][m][2] + acc[t][m][3]);
-    }
+    for (int g = 0; g < K; g += 64) linear_block64(xr, wr, g, sum);
 #pragma unroll
     for (int t = 0; t < 2; ++t)
 #pragma unroll
@@ -332,123 +298,6 @@ __global__ __launch_bounds__(256) void pn2_sa2_kernel(const float* __restrict__ 
     feat[((size_t)b * PN2_NP2 + g) * 256 + threadIdx.x] = fmaxf(red[threadIdx.x], red[256 + threadIdx.x]);
 }
 
-// Y[row][o] = act(bias[o] + sum_c W[o][c] X[row][c] (+ wx[o] . xyz[row])), o < M (a multiple of 4), K a multiple of 64, `rows` rows
-// per cloud b = blockIdx.z: X rows of ldx floats from X + b * xb, Y rows of ldy floats from Y + b * yb, xyz rows of 3 floats from
-// xyz + b * rows * 3.  dg_linear_kernel's tiling: a workgroup = 64 rows x 64 outputs, wave w = row half (w & 1) x output half
-// (w >> 1); tile_layer's arithmetic (blocks of 64 inputs).  The xyz columns are added to that sum by three FMAs (x, then y, then z).
-// POOL (sa3's last layer; M = 1024): nothing is stored but the maximum over the workgroup's valid rows, part_max [b][T][M].
-template <bool POOL>
-__global__ __launch_bounds__(256) void pn2_linear_kernel(const float* __restrict__ W, const float* __restrict__ bias, int M, int K,
-                                                         const float* __restrict__ X, int ldx, size_t xb, int rows, float* __restrict__ Y,
-                                                         int ldy, size_t yb, int act, const float* __restrict__ wx,
-                                                         const float* __restrict__ xyz, float* __restrict__ part_max, int T) {
-    __shared__ __attribute__((aligned(16))) float red[POOL ? Pn2PoolLds::BYTES / 4 : 4];
-    const int b = blockIdx.z;
-    const int row0 = blockIdx.x * 64;
-    if (row0 >= rows) return;                                          // the whole workgroup
-    const int wv = threadIdx.x >> 6, l = threadIdx.x & 63, q = l >> 4, p = l & 15;
-    const int rbase = row0 + 32 * (wv & 1), obase = blockIdx.y * 64 + 32 * (wv >> 1);
-    const float* Xb = X + (size_t)b * xb;
-    const float* xr[2];
-    const float* wr[2];
-    bool valid[2];
-#pragma unroll
-    for (int t = 0; t < 2; ++t) {
-        const int i = rbase + 16 * t + p;
-        valid[t] = i < rows;
-        xr[t] = Xb + (size_t)min(i, rows - 1) * ldx + 4 * q;           // rows beyond compute on the last row, unused
-        wr[t] = W + (size_t)min(obase + 16 * t + p, M - 1) * K + 4 * q;
-    }
-    const f32x4 zero = f32x4{0.f, 0.f, 0.f, 0.f};
-    f32x4 sum[2][2];                                                   // [row tile][output tile]
-#pragma unroll
-    for (int m = 0; m < 2; ++m) {
-        f32x4 bv = zero;
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            const int o = obase + 16 * m + 4 * q + r;
-            bv[r] = o < M ? bias[o] : 0.f;
-        }
-#pragma unroll
-        for (int t = 0; t < 2; ++t) sum[t][m] = bv;
-    }
-    for (int g = 0; g < K; g += 64) {
-        f32x4 xv[2][4], wt[2][4];
-#pragma unroll
-        for (int t = 0; t < 2; ++t)
-#pragma unroll
-            for (int c = 0; c < 4; ++c) {
-                xv[t][c] = *reinterpret_cast<const f32x4*>(xr[t] + g + 16 * c);
-                wt[t][c] = *reinterpret_cast<const f32x4*>(wr[t] + g + 16 * c);
-            }
-        f32x4 acc[2][2][4];                                            // [row tile][output tile][chain] of this 64-input block
-#pragma unroll
-        for (int c = 0; c < 4; ++c)
-#pragma unroll
-            for (int m = 0; m < 2; ++m)
-#pragma unroll
-                for (int t = 0; t < 2; ++t) acc[t][m][c] = mfma4(wt[m][c], xv[t][c], zero);
-#pragma unroll
-        for (int t = 0; t < 2; ++t)
-#pragma unroll
-            for (int m = 0; m < 2; ++m) sum[t][m] += (acc[t][m][0] + acc[t][m][1]) + (acc[t][m][2] + acc[t][m][3]);
-    }
-    f32x4 v[2][2];
-#pragma unroll
-    for (int t = 0; t < 2; ++t) {
-        float px = 0.f, py = 0.f, pz = 0.f;
-        if (wx) {
-            const float* pt = xyz + ((size_t)b * rows + min(rbase + 16 * t + p, rows - 1)) * 3;
-            px = pt[0]; py = pt[1]; pz = pt[2];
-        }
-#pragma unroll
-        for (int m = 0; m < 2; ++m) {
-            v[t][m] = sum[t][m];
-            if (wx) {
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    const f32x4 w = *reinterpret_cast<const f32x4*>(wx + (size_t)min(obase + 16 * m + 4 * q + r, M - 1) * 4);
-                    v[t][m][r] = fmaf(w[2], pz, fmaf(w[1], py, fmaf(w[0], px, v[t][m][r])));
-                }
-            }
-            if (POOL || act) v[t][m] = relu4(v[t][m]);
-        }
-    }
-    if (!POOL) {
-        float* Yb = Y + (size_t)b * yb;
-#pragma unroll
-        for (int t = 0; t < 2; ++t)
-#pragma unroll
-            for (int m = 0; m < 2; ++m) {
-                const int i = rbase + 16 * t + p, o = obase + 16 * m + 4 * q;
-                if (valid[t] && o < M) *reinterpret_cast<f32x4*>(Yb + (size_t)i * ldy + o) = v[t][m];
-            }
-        return;
-    }
-    float* rmax = LDS_AT(float, red, Pn2PoolLds::MAX);
-#pragma unroll
-    for (int m = 0; m < 2; ++m) {
-        f32x4 mx = f32x4{-INFINITY, -INFINITY, -INFINITY, -INFINITY};
-#pragma unroll
-        for (int t = 0; t < 2; ++t)
-            if (valid[t]) {
-#pragma unroll
-                for (int r = 0; r < 4; ++r) mx[r] = fmaxf(mx[r], v[t][m][r]);
-            }
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            float x = mx[r];
-#pragma unroll
-            for (int d = 1; d < 16; d <<= 1) x = fmaxf(x, __shfl_xor(x, d));
-            mx[r] = x;
-        }
-        if (p == 0) *reinterpret_cast<f32x4*>(rmax + (wv & 1) * 64 + 32 * (wv >> 1) + 16 * m + 4 * q) = mx;
-    }
-    __syncthreads();
-    if (threadIdx.x < 64)
-        part_max[((size_t)b * T + blockIdx.x) * M + blockIdx.y * 64 + threadIdx.x] = fmaxf(rmax[threadIdx.x], rmax[64 + threadIdx.x]);
-}
-
 __global__ __launch_bounds__(256) void pn2_pool_kernel(const float* __restrict__ part_max, int T, float* __restrict__ gfeat) {
     const int b = blockIdx.x, c = threadIdx.x * 4;
     const float* P = part_max + (size_t)b * T * PN2_EMB + c;
@@ -459,24 +308,6 @@ __global__ __launch_bounds__(256) void pn2_pool_kernel(const float* __restrict__
         for (int r = 0; r < 4; ++r) m[r] = fmaxf(m[r], v[r]);
     }
     *reinterpret_cast<f32x4*>(gfeat + (size_t)b * PN2_EMB + c) = m;
-}
-
-__global__ __launch_bounds__(256) void pn2_argmax_kernel(const float* __restrict__ logits, int B, int n_classes, int32_t* __restrict__ pred) {
-    const int b = blockIdx.x * 256 + threadIdx.x;
-    if (b >= B) return;
-    const float* L = logits + (size_t)b * n_classes;
-    float bv = L[0];
-    int bi = 0;
-    for (int c = 1; c < n_classes; ++c)
-        if (L[c] > bv) { bv = L[c]; bi = c; }                          // strict: the lowest class among equals
-    pred[b] = bi;
-}
-
-// one layer on [B clouds][rows rows]
-void launch_linear(const float* img, const Pn2Layer& L, const float* X, int ldx, size_t xb, int B, int rows, float* Y, int ldy, size_t yb,
-                   int act, const float* wx, const float* xyz, hipStream_t s) {
-    hipLaunchKernelGGL((pn2_linear_kernel<false>), dim3((rows + 63) / 64, (L.n_out + 63) / 64, B), dim3(256), 0, s, img + L.w, img + L.b,
-                       L.n_out, L.n_in, X, ldx, xb, rows, Y, ldy, yb, act, wx, xyz, (float*)nullptr, 0);
 }
 
 }  // namespace
@@ -519,24 +350,23 @@ hipError_t launch_pn2(const float* img, const Pn2Image& I, const float* pc, cons
                        (const int32_t*)nullptr, PN2_NP1, fps_start, 1, PN2_NP2, fps2, w.xyz2);
     hipLaunchKernelGGL(pn2_ball_kernel, dim3(PN2_NP2 / 4, B), block, 0, s, (const float*)w.xyz1, (size_t)PN2_NP1 * 3, (const int32_t*)nullptr,
                        PN2_NP1, (const float*)w.xyz2, PN2_NP2, PN2_NS2, pn2_radius2(1), ball2);
-    launch_linear(img, I.sa2_u, l1, 128, (size_t)PN2_NP1 * 128, B, PN2_NP1, w.u2, 128, (size_t)PN2_NP1 * 128, 0, nullptr, nullptr, s);
+    launch_linear<Pn2Linear>(img, I.sa2_u, l1, 128, (size_t)PN2_NP1 * 128, nullptr, B, PN2_NP1, w.u2, 128, (size_t)PN2_NP1 * 128, 0, s);
     hipLaunchKernelGGL(pn2_sa2_kernel, dim3(PN2_NP2, B), block, (size_t)Pn2Sa2Lds::BYTES, s, (const float*)w.u2, img + I.sa2_xyz,
                        img + I.sa2[0].w, img + I.sa2[0].b, img + I.sa2[1].w, img + I.sa2[1].b, (const int32_t*)ball2, (const float*)w.xyz1,
                        (const float*)w.xyz2, l2);
     // level 3: one group of the 128 rows [xyz | 256 features]
-    launch_linear(img, I.sa3_u, l2, 256, (size_t)PN2_NP2 * 256, B, PN2_NP2, w.s3a, 256, (size_t)PN2_NP2 * 256, 1, img + I.sa3_xyz, w.xyz2, s);
-    launch_linear(img, I.sa3[0], w.s3a, 256, (size_t)PN2_NP2 * 256, B, PN2_NP2, w.s3b, 512, (size_t)PN2_NP2 * 512, 1, nullptr, nullptr, s);
-    constexpr int T = PN2_NP2 / 64;
-    hipLaunchKernelGGL((pn2_linear_kernel<true>), dim3(T, PN2_EMB / 64, B), block, 0, s, img + I.sa3[1].w, img + I.sa3[1].b, PN2_EMB, 512,
-                       (const float*)w.s3b, 512, (size_t)PN2_NP2 * 512, PN2_NP2, (float*)nullptr, 0, (size_t)0, 1, (const float*)nullptr,
-                       (const float*)nullptr, w.part_max, T);
+    launch_linear<Pn2Linear>(img, I.sa3_u, l2, 256, (size_t)PN2_NP2 * 256, nullptr, B, PN2_NP2, w.s3a, 256, (size_t)PN2_NP2 * 256, 1, s,
+                             img + I.sa3_xyz, w.xyz2);
+    launch_linear<Pn2Linear>(img, I.sa3[0], w.s3a, 256, (size_t)PN2_NP2 * 256, nullptr, B, PN2_NP2, w.s3b, 512, (size_t)PN2_NP2 * 512, 1, s);
+    constexpr int T = PN2_NP2 / LINEAR_TILE;                           // the tiles linear_kernel<Pn2Sa3Last> writes
+    launch_linear<Pn2Sa3Last>(img, I.sa3[1], w.s3b, 512, (size_t)PN2_NP2 * 512, nullptr, B, PN2_NP2, nullptr, 0, 0, 1, s, nullptr, nullptr,
+                              w.part_max);
     hipLaunchKernelGGL(pn2_pool_kernel, dim3(B), block, 0, s, (const float*)w.part_max, T, gfeat);
     // the head, a cloud a row
-    launch_linear(img, I.fc[0], gfeat, PN2_EMB, 0, 1, B, w.f1, 512, 0, 1, nullptr, nullptr, s);
-    launch_linear(img, I.fc[1], w.f1, 512, 0, 1, B, w.f2, 256, 0, 1, nullptr, nullptr, s);
-    launch_linear(img, I.fc[2], w.f2, 256, 0, 1, B, logits, n_classes, 0, 0, nullptr, nullptr, s);
-    if (out.pred) hipLaunchKernelGGL(pn2_argmax_kernel, dim3((B + 255) / 256), block, 0, s, (const float*)logits, B, n_classes, out.pred);
-    return hipGetLastError();
+    launch_linear<Pn2Linear>(img, I.fc[0], gfeat, PN2_EMB, 0, nullptr, 1, B, w.f1, 512, 0, 1, s);
+    launch_linear<Pn2Linear>(img, I.fc[1], w.f1, 512, 0, nullptr, 1, B, w.f2, 256, 0, 1, s);
+    launch_linear<Pn2Linear>(img, I.fc[2], w.f2, 256, 0, nullptr, 1, B, logits, n_classes, 0, 0, s);
+    return out.pred ? launch_argmax(logits, B, n_classes, out.pred, s) : hipGetLastError();
 }
 
 }  // namespace ifd

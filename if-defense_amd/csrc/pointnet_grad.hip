@@ -21,6 +21,7 @@
 // The dense work here is small beside the forward's (at most 1024 points x 3 small layers, under 4 % of its FLOPs), so the
 // stack's backward is plain FMAs; the FC transposes are MFMA (v_mfma_f32_16x16x4_f32), like the forward's.
 #include "atk_device.h"
+#include "victim_device.h"
 
 namespace ifd {
 
@@ -30,14 +31,6 @@ constexpr int ATK_MAXN = 10000;         // IFD_CLS_MAX_POINTS (api.cpp refuses a
 constexpr int ATK_PASS = 64;            // winner points of one pass of stack_backward_kernel
 constexpr int LOSS_LOGITS = 0;          // IFD_ATK_LOSS_LOGITS / _CE
 constexpr int KIND_FGM = 0, KIND_MIFGM = 2;   // IFD_FGM_FGM, _IFGM (1), _MIFGM, _PGD (3)
-
-__device__ __forceinline__ f32x4 mfma4(const f32x4 a, const f32x4 b, f32x4 c) {
-    c = __builtin_amdgcn_mfma_f32_16x16x4f32(a[0], b[0], c, 0, 0, 0);
-    c = __builtin_amdgcn_mfma_f32_16x16x4f32(a[1], b[1], c, 0, 0, 0);
-    c = __builtin_amdgcn_mfma_f32_16x16x4f32(a[2], b[2], c, 0, 0, 0);
-    c = __builtin_amdgcn_mfma_f32_16x16x4f32(a[3], b[3], c, 0, 0, 0);
-    return c;
-}
 
 __global__ __launch_bounds__(256) void atk_check_kernel(const int32_t* __restrict__ n_points, const int32_t* __restrict__ target, int B,
                                                         int lo, int hi, int n_classes, int32_t* __restrict__ bad) {

@@ -24,23 +24,13 @@
 #include "ifd_device.h"
 #include "ifd_internal.h"
 #include "lds_layout.h"
+#include "victim_device.h"
 
 #pragma clang fp contract(off)
 
 namespace ifd {
 
 namespace {
-
-__device__ __forceinline__ f32x4 mfma4(const f32x4 a, const f32x4 b, f32x4 c) {
-    c = __builtin_amdgcn_mfma_f32_16x16x4f32(a[0], b[0], c, 0, 0, 0);
-    c = __builtin_amdgcn_mfma_f32_16x16x4f32(a[1], b[1], c, 0, 0, 0);
-    c = __builtin_amdgcn_mfma_f32_16x16x4f32(a[2], b[2], c, 0, 0, 0);
-    c = __builtin_amdgcn_mfma_f32_16x16x4f32(a[3], b[3], c, 0, 0, 0);
-    return c;
-}
-__device__ __forceinline__ f32x4 relu4(f32x4 v) {
-    return f32x4{fmaxf(v[0], 0.f), fmaxf(v[1], 0.f), fmaxf(v[2], 0.f), fmaxf(v[3], 0.f)};
-}
 
 // acc[m] = bias + W X for the MT output tiles of a layer with SG input groups; in(g) yields the lane's f32x4 of group g.
 template <int SG, int MT, class In>

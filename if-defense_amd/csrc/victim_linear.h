@@ -1,0 +1,230 @@
+// The one dense layer of the DGCNN and PointNet++ victims on v_mfma_f32_16x16x4_f32: Y = act(W X + b), weights row-major
+// [n_out][n_in] as the canonical vector has them.  A workgroup owns 64 rows (points, or clouds in an FC head) x 64 outputs; wave w
+// owns the row half (w & 1) x the output half (w >> 1), two 16 x 16 tiles each way.  Columns of an MFMA never mix: a row's result
+// depends on nothing but that row, whatever shares its wave.
+//
+// What differs between the layers is a policy P of four compile-time choices and nothing else:
+//   ACT    LeakyReLU(0.2) or ReLU, applied where `act` is set (always in a pooling layer).
+//   CUT64  how the K inputs are summed.  false: the bias starts chain 0, four chains over the interleaved 16-input groups run
+//          across all of K and are added pairwise once, (c0 + c1) + (c2 + c3).  true: the inputs go in blocks of 64; a block is
+//          four chains of 16 inputs from zero, added pairwise, and the blocks are added to the bias in ascending order - chains of
+//          16, not of K / 4, which is what PointNet++'s 512-wide layers need to stay within the float32 oracle's error.
+//   XYZ    where wx is not null, wx[o] . xyz[row] is added to the sum by three FMAs (x, then y, then z) before the activation.
+//   POOL   none: Y is stored.  Otherwise nothing is stored but the maximum (and the sum) over the workgroup's valid rows,
+//          part_max / part_sum [b][T][M] at tile blockIdx.x: a butterfly d = 1, 2, 4, 8 over the 16 rows of the lanes, then the
+//          two row halves through LDS.  Every lane runs the same tree, so the sum depends on nothing but the cloud's own rows.
+// The order of the floating-point operations is part of each victim's contract with its oracle: a new policy value
+// is a new contract, not a tuning knob.  The four policies at the end of this file are the only instantiations.
+#pragma once
+#include "ifd_internal.h"
+#include "lds_layout.h"
+#include "victim_device.h"
+
+namespace ifd {
+
+constexpr int LINEAR_TILE = 64;         // rows of one workgroup of linear_kernel, and of one partial maximum / sum of its pool
+
+enum class LinearAct { LEAKY, RELU };
+enum class LinearPool { NONE, MAX, MAX_SUM };
+
+// One block of 64 inputs, columns g .. g + 63 of the rows xr[t] (a wave's two 16-row tiles) and of the weight rows wr[m] (its two
+// 16-output tiles): four chains of 16 inputs from zero, added pairwise into sum[t][m].
+__device__ __forceinline__ void linear_block64(const float* (&xr)[2], const float* (&wr)[2], int g, f32x4 (&sum)[2][2]) {
+    const f32x4 zero = f32x4{0.f, 0.f, 0.f, 0.f};
+    f32x4 xv[2][4], wt[2][4];
+#pragma unroll
+    for (int t = 0; t < 2; ++t)
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+            xv[t][c] = *reinterpret_cast<const f32x4*>(xr[t] + g + 16 * c);
+            wt[t][c] = *reinterpret_cast<const f32x4*>(wr[t] + g + 16 * c);
+        }
+    f32x4 acc[2][2][4];                                                // [row tile][output tile][chain]
+#pragma unroll
+    for (int c = 0; c < 4; ++c)
+#pragma unroll
+        for (int m = 0; m < 2; ++m)
+#pragma unroll
+            for (int t = 0; t < 2; ++t) acc[t][m][c] = mfma4(wt[m][c], xv[t][c], zero);
+#pragma unroll
+    for (int t = 0; t < 2; ++t)
+#pragma unroll
+        for (int m = 0; m < 2; ++m) sum[t][m] += (acc[t][m][0] + acc[t][m][1]) + (acc[t][m][2] + acc[t][m][3]);
+}
+
+// Y[row][o] = act(bias[o] + sum_c W[o][c] X[row][c] (+ wx[o] . xyz[row])), o < M (a multiple of 4), K a multiple of 64.  Rows: the
+// first cloud_points(n_points, b, stride) of cloud b = blockIdx.z; X rows of ldx floats from X + b * xb, Y rows of ldy floats from
+// Y + b * yb, xyz rows of 3 floats from xyz + b * stride * 3; wx [M][4] = {w0, w1, w2, -}.
+template <class P>
+__global__ __launch_bounds__(256) void linear_kernel(const float* __restrict__ W, const float* __restrict__ bias, int M, int K,
+                                                     const float* __restrict__ X, int ldx, size_t xb,
+                                                     const int32_t* __restrict__ n_points, int stride, float* __restrict__ Y, int ldy,
+                                                     size_t yb, int act, const float* __restrict__ wx, const float* __restrict__ xyz,
+                                                     float* __restrict__ part_max, float* __restrict__ part_sum, int T) {
+    constexpr bool POOL = P::POOL != LinearPool::NONE, POOL_SUM = P::POOL == LinearPool::MAX_SUM;
+    using Lds = LinearPoolLds<POOL_SUM>;
+    __shared__ __attribute__((aligned(16))) float red[POOL ? Lds::BYTES / 4 : 4];
+    const int b = blockIdx.z;
+    const int n = cloud_points(n_points, b, stride);
+    const int row0 = blockIdx.x * LINEAR_TILE;
+    if (row0 >= n) return;                                             // the whole workgroup
+    const int wv = threadIdx.x >> 6, l = threadIdx.x & 63, q = l >> 4, p = l & 15;
+    const int rbase = row0 + 32 * (wv & 1), obase = blockIdx.y * 64 + 32 * (wv >> 1);
+    const float* Xb = X + (size_t)b * xb;
+    const float* xr[2];
+    const float* wr[2];
+    bool valid[2];
+#pragma unroll
+    for (int t = 0; t < 2; ++t) {
+        const int i = rbase + 16 * t + p;
+        valid[t] = i < n;
+        xr[t] = Xb + (size_t)min(i, n - 1) * ldx + 4 * q;              // rows beyond the cloud compute on its last row, unused
+        wr[t] = W + (size_t)min(obase + 16 * t + p, M - 1) * K + 4 * q;
+    }
+    const f32x4 zero = f32x4{0.f, 0.f, 0.f, 0.f};
+    f32x4 bv[2];
+#pragma unroll
+    for (int m = 0; m < 2; ++m)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const int o = obase + 16 * m + 4 * q + r;
+            bv[m][r] = o < M ? bias[o] : 0.f;
+        }
+    f32x4 sum[2][2];                                                   // [row tile][output tile]
+    if constexpr (P::CUT64) {
+#pragma unroll
+        for (int m = 0; m < 2; ++m)
+#pragma unroll
+            for (int t = 0; t < 2; ++t) sum[t][m] = bv[m];
+        for (int g = 0; g < K; g += 64) linear_block64(xr, wr, g, sum);
+    } else {
+        f32x4 acc[2][2][4];                                            // [row tile][output tile][chain]
+#pragma unroll
+        for (int m = 0; m < 2; ++m)
+#pragma unroll
+            for (int t = 0; t < 2; ++t) {
+                acc[t][m][0] = bv[m];
+                acc[t][m][1] = acc[t][m][2] = acc[t][m][3] = zero;
+            }
+        for (int g = 0; g < K; g += 64) {
+            f32x4 xv[2][4], wt[2][4];
+#pragma unroll
+            for (int t = 0; t < 2; ++t)
+#pragma unroll
+                for (int c = 0; c < 4; ++c) {
+                    xv[t][c] = *reinterpret_cast<const f32x4*>(xr[t] + g + 16 * c);
+                    wt[t][c] = *reinterpret_cast<const f32x4*>(wr[t] + g + 16 * c);
+                }
+#pragma unroll
+            for (int c = 0; c < 4; ++c)
+#pragma unroll
+                for (int m = 0; m < 2; ++m)
+#pragma unroll
+                    for (int t = 0; t < 2; ++t) acc[t][m][c] = mfma4(wt[m][c], xv[t][c], acc[t][m][c]);
+        }
+#pragma unroll
+        for (int t = 0; t < 2; ++t)
+#pragma unroll
+            for (int m = 0; m < 2; ++m) sum[t][m] = (acc[t][m][0] + acc[t][m][1]) + (acc[t][m][2] + acc[t][m][3]);
+    }
+    f32x4 v[2][2];
+#pragma unroll
+    for (int t = 0; t < 2; ++t) {
+        float px = 0.f, py = 0.f, pz = 0.f;
+        if constexpr (P::XYZ) {
+            if (wx) {
+                const float* pt = xyz + ((size_t)b * stride + min(rbase + 16 * t + p, n - 1)) * 3;
+                px = pt[0]; py = pt[1]; pz = pt[2];
+            }
+        }
+#pragma unroll
+        for (int m = 0; m < 2; ++m) {
+            v[t][m] = sum[t][m];
+            if constexpr (P::XYZ) {
+                if (wx) {
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) {
+                        const f32x4 w = *reinterpret_cast<const f32x4*>(wx + (size_t)min(obase + 16 * m + 4 * q + r, M - 1) * 4);
+                        v[t][m][r] = fmaf(w[2], pz, fmaf(w[1], py, fmaf(w[0], px, v[t][m][r])));
+                    }
+                }
+            }
+            if (POOL || act) v[t][m] = P::ACT == LinearAct::LEAKY ? leaky4(v[t][m]) : relu4(v[t][m]);
+        }
+    }
+    if constexpr (!POOL) {
+        float* Yb = Y + (size_t)b * yb;
+#pragma unroll
+        for (int t = 0; t < 2; ++t)
+#pragma unroll
+            for (int m = 0; m < 2; ++m) {
+                const int i = rbase + 16 * t + p, o = obase + 16 * m + 4 * q;
+                if (valid[t] && o < M) *reinterpret_cast<f32x4*>(Yb + (size_t)i * ldy + o) = v[t][m];
+            }
+    } else {
+        float* rmax = LDS_AT(float, red, Lds::MAX);
+        float* rsum = LDS_AT(float, red, POOL_SUM ? Lds::SUM : Lds::MAX);  // read and written only with POOL_SUM
+        const int slot = (wv & 1) * 64 + 32 * (wv >> 1) + 4 * q;
+#pragma unroll
+        for (int m = 0; m < 2; ++m) {
+            f32x4 mx = f32x4{-INFINITY, -INFINITY, -INFINITY, -INFINITY}, sm = zero;
+#pragma unroll
+            for (int t = 0; t < 2; ++t)
+                if (valid[t]) {
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) {
+                        mx[r] = fmaxf(mx[r], v[t][m][r]);
+                        if constexpr (POOL_SUM) sm[r] += v[t][m][r];
+                    }
+                }
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {                              // over the 16 rows of the lanes: a butterfly, every lane the same tree
+                float x = mx[r], s = sm[r];
+#pragma unroll
+                for (int d = 1; d < 16; d <<= 1) {
+                    x = fmaxf(x, __shfl_xor(x, d));
+                    if constexpr (POOL_SUM) s += __shfl_xor(s, d);
+                }
+                mx[r] = x; sm[r] = s;
+            }
+            if (p == 0) {
+                *reinterpret_cast<f32x4*>(rmax + slot + 16 * m) = mx;
+                if constexpr (POOL_SUM) *reinterpret_cast<f32x4*>(rsum + slot + 16 * m) = sm;
+            }
+        }
+        __syncthreads();
+        if (threadIdx.x < 64) {
+            const size_t at = ((size_t)b * T + blockIdx.x) * M + blockIdx.y * 64 + threadIdx.x;
+            part_max[at] = fmaxf(rmax[threadIdx.x], rmax[64 + threadIdx.x]);
+            if constexpr (POOL_SUM) part_sum[at] = rsum[threadIdx.x] + rsum[64 + threadIdx.x];
+        }
+    }
+}
+
+// One layer on [B clouds][cloud_points rows].  A pooling policy writes part_max (and part_sum) [B][T][n_out], T =
+// ceil(stride / LINEAR_TILE), instead of Y.
+template <class P>
+void launch_linear(const float* img, const DenseLayer& L, const float* X, int ldx, size_t xb, const int32_t* n_points, int B, int stride,
+                   float* Y, int ldy, size_t yb, int act, hipStream_t s, const float* wx = nullptr, const float* xyz = nullptr,
+                   float* part_max = nullptr, float* part_sum = nullptr) {
+    const int T = (stride + LINEAR_TILE - 1) / LINEAR_TILE;
+    hipLaunchKernelGGL((linear_kernel<P>), dim3(T, (L.n_out + 63) / 64, B), dim3(256), 0, s, img + L.w, img + L.b, L.n_out, L.n_in, X,
+                       ldx, xb, n_points, stride, Y, ldy, yb, act, wx, xyz, part_max, part_sum, T);
+}
+
+template <LinearAct ACT_, bool CUT64_, bool XYZ_, LinearPool POOL_>
+struct LinearPolicy {
+    static constexpr LinearAct ACT = ACT_;
+    static constexpr bool CUT64 = CUT64_, XYZ = XYZ_;
+    static constexpr LinearPool POOL = POOL_;
+};
+// DGCNN: the split edge convolutions' P | Q and the head; conv5, reduced to the maximum and the sum of each 64-point tile
+using DgLinear = LinearPolicy<LinearAct::LEAKY, false, false, LinearPool::NONE>;
+using DgConv5 = LinearPolicy<LinearAct::LEAKY, false, false, LinearPool::MAX_SUM>;
+// PointNet++: sa2's U, sa3's first two layers (the first with its xyz columns) and the head; sa3's last, reduced to its tiles' maxima.
+// Both keep the run-time wx test of the kernel they replace, sa3's last too, which never passes one: without it the compiler packs the
+// block's adds differently and that layer measured 2 % slower.
+using Pn2Linear = LinearPolicy<LinearAct::RELU, true, true, LinearPool::NONE>;
+using Pn2Sa3Last = LinearPolicy<LinearAct::RELU, true, true, LinearPool::MAX>;
+
+}  // namespace ifd

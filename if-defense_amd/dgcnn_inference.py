@@ -15,7 +15,7 @@ import sys
 
 import numpy as np
 
-from .inference import build_parser, default_weight_path, evaluate_npz, get_model_name, points_to_take, print_result
+from .inference import ClosesClassifier, build_parser, default_weight_path, get_model_name, points_to_take, run_victim_cli
 
 MAX_POINTS = 2048
 
@@ -24,12 +24,13 @@ class _CloudSizeError(ValueError):
     pass
 
 
-class _SizeChecked:
+class _SizeChecked(ClosesClassifier):
     """predict() of the wrapped classifier behind the check of the clouds' sizes, so that a file the library would refuse is
     refused with the words of this CLI."""
 
     def __init__(self, classifier, k: int):
-        self.classifier, self.k = classifier, k
+        super().__init__(classifier)
+        self.k = k
 
     def predict(self, clouds):
         sizes = np.array([len(c) for c in clouds])
@@ -41,10 +42,6 @@ class _SizeChecked:
             i = int(np.argmax(sizes > MAX_POINTS))
             raise _CloudSizeError("cloud %d has %d points, more than the %d the DGCNN victim takes" % (i, int(sizes[i]), MAX_POINTS))
         return self.classifier.predict(clouds)
-
-    def close(self):
-        if hasattr(self.classifier, "close"):
-            self.classifier.close()
 
 
 def main(argv=None, make_classifier=None) -> int:
@@ -73,18 +70,7 @@ def main(argv=None, make_classifier=None) -> int:
             return DgcnnClassifier(load_checkpoint(model_path, model), k=k, device=args.device)
     model_path = args.model_path or default_weight_path(args.dataset, 'dgcnn')
     classifier = _SizeChecked(make_classifier('dgcnn', args.k, model_path), args.k)
-    try:
-        r = evaluate_npz(args.data_root, classifier, args.mode, num_points, args.normalize_pc)
-    except KeyError as e:
-        print("dgcnn_inference: {}".format(e.args[0] if e.args else e), file=sys.stderr)
-        return 2
-    except _CloudSizeError as e:
-        print("dgcnn_inference: {}: {}".format(args.data_root, e), file=sys.stderr)
-        return 2
-    finally:
-        classifier.close()
-    print_result(args.mode, r)
-    return 0
+    return run_victim_cli("dgcnn_inference", args, classifier, num_points, _CloudSizeError)
 
 
 if __name__ == '__main__':

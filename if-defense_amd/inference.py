@@ -127,6 +127,36 @@ def print_result(mode: str, r: dict) -> None:
               format(r["accuracy"], r["success_rate"]))
 
 
+class ClosesClassifier:
+    """Base of the CLIs' wrappers around a classifier's predict(): closing the wrapper closes what it wraps."""
+
+    def __init__(self, classifier):
+        self.classifier = classifier
+
+    def close(self):
+        if hasattr(self.classifier, "close"):
+            self.classifier.close()
+
+
+def run_victim_cli(prog: str, args, classifier, num_points: int, size_error=None) -> int:
+    """The tail every victim's CLI shares: evaluate args.data_root with ``classifier``, close it, print the reference's closing
+    line.  A file without the labels the mode needs, or (``size_error``: the exception the CLI's wrapper raises) with a cloud
+    the victim cannot take, is refused in ``prog``'s name with status 2."""
+    try:
+        r = evaluate_npz(args.data_root, classifier, args.mode, num_points, args.normalize_pc)
+    except KeyError as e:
+        print("{}: {}".format(prog, e.args[0] if e.args else e), file=sys.stderr)
+        return 2
+    except (size_error or ()) as e:
+        print("{}: {}: {}".format(prog, args.data_root, e), file=sys.stderr)
+        return 2
+    finally:
+        if hasattr(classifier, "close"):
+            classifier.close()
+    print_result(args.mode, r)
+    return 0
+
+
 def main(argv=None, make_classifier=None) -> int:
     args = build_parser().parse_args(argv)
     if not args.model:
@@ -147,17 +177,7 @@ def main(argv=None, make_classifier=None) -> int:
             from .weights import load_checkpoint
             return Classifier(load_checkpoint(model_path, model, feature_transform), model, feature_transform, device=args.device)
     model_path = args.model_path or default_weight_path(args.dataset, args.model)
-    classifier = make_classifier(args.model, args.feature_transform, model_path)
-    try:
-        r = evaluate_npz(args.data_root, classifier, args.mode, num_points, args.normalize_pc)
-    except KeyError as e:
-        print("inference: {}".format(e.args[0] if e.args else e), file=sys.stderr)
-        return 2
-    finally:
-        if hasattr(classifier, "close"):
-            classifier.close()
-    print_result(args.mode, r)
-    return 0
+    return run_victim_cli("inference", args, make_classifier(args.model, args.feature_transform, model_path), num_points)
 
 
 if __name__ == '__main__':

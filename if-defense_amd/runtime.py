@@ -646,20 +646,25 @@ class Classifier:
             raise IfdError("unknown victim model %r" % (model,))
         self.lib = _lib.load()
         self.feature_transform = bool(feature_transform)
-        w = np.ascontiguousarray(weights, dtype=np.float32)
         want = self.lib.ifd_cls_weight_count(self.MODELS[model], int(self.feature_transform))
         if want == 0:
             raise IfdError("victim model %r is not built (only pointnet is)" % model)
+        self._create("ifd_cls_create", want, "%s weights (feature_transform=%s)" % (model, self.feature_transform), weights, device,
+                     self.MODELS[model], int(self.feature_transform))
+
+    def _create(self, create_fn: str, want: int, label: str, weights, device, *args):
+        """The creation every victim shares: ``want`` weights of the kind ``label`` names, a GPU, the device, then
+        lib.<create_fn>(weights, count, *args, N_CLASSES, device index) -> self.ctx."""
+        w = np.ascontiguousarray(weights, dtype=np.float32)
         if w.size != want:
-            raise IfdError("expected %d %s weights (feature_transform=%s), got %d" % (want, model, self.feature_transform, w.size))
+            raise IfdError("expected %d %s, got %d" % (want, label, w.size))
         if not torch.cuda.is_available():
             raise IfdError("no GPU visible: the classifier only runs on an MI355X (no CPU fallback)")
         self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
         with torch.cuda.device(self.device):
-            self.ctx = self.lib.ifd_cls_create(w.ctypes.data, w.size, self.MODELS[model], int(self.feature_transform),
-                                               self.N_CLASSES, self.device.index or 0)
+            self.ctx = getattr(self.lib, create_fn)(w.ctypes.data, w.size, *args, self.N_CLASSES, self.device.index or 0)
         if not self.ctx:
-            raise IfdError((self.lib.ifd_last_error(None) or b"ifd_cls_create failed").decode())
+            raise IfdError((self.lib.ifd_last_error(None) or create_fn.encode() + b" failed").decode())
 
     def close(self):
         if getattr(self, "ctx", None):
@@ -703,24 +708,41 @@ class Classifier:
         """pc: [B,N,3] tensor / array, or a list (or object array) of ragged [K_i,3] clouds, which are padded into one strided
         batch.  n_points: [B] valid rows of each cloud of a [B,N,3] batch.  Returns logits [B,40]; with want_aux also
         {"trans" [B,3,3], "trans_feat" [B,64,64] (feature_transform only), "global_feat" [B,1024], "pred" [B] int32}."""
+        def aux_table(B, stride):
+            f32 = dict(device=self.device, dtype=torch.float32)
+            aux = {"trans": torch.empty(B, 3, 3, **f32), "global_feat": torch.empty(B, 1024, **f32)}
+            if self.feature_transform:
+                aux["trans_feat"] = torch.empty(B, 64, 64, **f32)
+            return aux
+        return self._forward("ifd_cls_forward", pc, n_points, _lib.IfdClsAux, aux_table, want_aux, want_pred)
+
+    def _forward(self, fn: str, pc, n_points, aux_struct, aux_table, want_aux: bool, want_pred: bool, extra=None):
+        """The forward call every victim shares: the batch, the logits, and - with want_aux or want_pred - the aux struct filled
+        with "pred" and, with want_aux, the tensors of aux_table(B, stride): a member of aux_struct per name, a list filling an
+        array member.  ``extra(B)``: the arguments lib.<fn> takes between n_points and B, as device tensors or None."""
         pc, n_points = self._batch(pc, n_points)
         B, stride = int(pc.shape[0]), int(pc.shape[1])
         if B < 1 or stride < 1:
             raise IfdError("empty batch")
+        between = extra(B) if extra else ()
         out = torch.empty(B, self.N_CLASSES, device=self.device, dtype=torch.float32)
         aux, st = None, None
         if want_aux or want_pred:
             aux = {"pred": torch.empty(B, device=self.device, dtype=torch.int32)}
             if want_aux:
-                aux["trans"] = torch.empty(B, 3, 3, device=self.device, dtype=torch.float32)
-                aux["global_feat"] = torch.empty(B, 1024, device=self.device, dtype=torch.float32)
-                if self.feature_transform:
-                    aux["trans_feat"] = torch.empty(B, 64, 64, device=self.device, dtype=torch.float32)
-            ptr = lambda k: aux[k].data_ptr() if k in aux else None        # noqa: E731
-            st = C.byref(_lib.IfdClsAux(ptr("trans"), ptr("trans_feat"), ptr("global_feat"), ptr("pred")))
+                aux.update(aux_table(B, stride))
+            a = aux_struct()
+            for name, t in aux.items():
+                if isinstance(t, list):
+                    for i, ti in enumerate(t):
+                        getattr(a, name)[i] = ti.data_ptr()
+                else:
+                    setattr(a, name, t.data_ptr())
+            st = C.byref(a)
+        ptr = lambda t: None if t is None else t.data_ptr()        # noqa: E731
         with torch.cuda.device(self.device):
-            self._check(self.lib.ifd_cls_forward(self.ctx, pc.data_ptr(), None if n_points is None else n_points.data_ptr(),
-                                                 B, stride, out.data_ptr(), st, torch.cuda.current_stream(self.device).cuda_stream))
+            self._check(getattr(self.lib, fn)(self.ctx, pc.data_ptr(), ptr(n_points), *[ptr(t) for t in between], B, stride,
+                                              out.data_ptr(), st, torch.cuda.current_stream(self.device).cuda_stream))
         return (out, aux) if aux is not None else out
 
     def predict(self, pc, n_points=None) -> torch.Tensor:
@@ -1441,44 +1463,17 @@ class DgcnnClassifier(Classifier):
         self.k = int(k)
         if not 1 <= self.k <= _lib.DGCNN_MAX_K:
             raise IfdError("k must lie in [1, %d], got %d" % (_lib.DGCNN_MAX_K, self.k))
-        w = np.ascontiguousarray(weights, dtype=np.float32)
-        want = self.lib.ifd_dgcnn_weight_count()
-        if w.size != want:
-            raise IfdError("expected %d dgcnn weights, got %d" % (want, w.size))
-        if not torch.cuda.is_available():
-            raise IfdError("no GPU visible: the classifier only runs on an MI355X (no CPU fallback)")
-        self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
-        with torch.cuda.device(self.device):
-            self.ctx = self.lib.ifd_dgcnn_create(w.ctypes.data, w.size, self.k, self.N_CLASSES, self.device.index or 0)
-        if not self.ctx:
-            raise IfdError((self.lib.ifd_last_error(None) or b"ifd_dgcnn_create failed").decode())
+        self._create("ifd_dgcnn_create", self.lib.ifd_dgcnn_weight_count(), "dgcnn weights", weights, device, self.k)
 
     def logits(self, pc, n_points=None, want_aux: bool = False, want_pred: bool = False):
         """pc, n_points: as Classifier.logits.  Returns logits [B,40]; with want_aux also {"idx": four [B,N,k] int32 (the
         neighbours each edge convolution chose; rows beyond a cloud's count are -1), "feat" [B,N,512] (x1|x2|x3|x4; zero
         beyond a cloud's count), "global_feat" [B,2048] (max | mean of conv5), "pred" [B] int32}."""
-        pc, n_points = self._batch(pc, n_points)
-        B, stride = int(pc.shape[0]), int(pc.shape[1])
-        if B < 1 or stride < 1:
-            raise IfdError("empty batch")
-        out = torch.empty(B, self.N_CLASSES, device=self.device, dtype=torch.float32)
-        aux, st = None, None
-        if want_aux or want_pred:
-            aux = {"pred": torch.empty(B, device=self.device, dtype=torch.int32)}
-            a = _lib.IfdDgcnnAux()
-            a.pred = aux["pred"].data_ptr()
-            if want_aux:
-                aux["idx"] = [torch.full((B, stride, self.k), -1, device=self.device, dtype=torch.int32) for _ in range(4)]
-                aux["feat"] = torch.zeros(B, stride, 512, device=self.device, dtype=torch.float32)
-                aux["global_feat"] = torch.empty(B, 2048, device=self.device, dtype=torch.float32)
-                for i in range(4):
-                    a.idx[i] = aux["idx"][i].data_ptr()
-                a.feat, a.global_feat = aux["feat"].data_ptr(), aux["global_feat"].data_ptr()
-            st = C.byref(a)
-        with torch.cuda.device(self.device):
-            self._check(self.lib.ifd_dgcnn_forward(self.ctx, pc.data_ptr(), None if n_points is None else n_points.data_ptr(),
-                                                   B, stride, out.data_ptr(), st, torch.cuda.current_stream(self.device).cuda_stream))
-        return (out, aux) if aux is not None else out
+        def aux_table(B, stride):
+            return {"idx": [torch.full((B, stride, self.k), -1, device=self.device, dtype=torch.int32) for _ in range(4)],
+                    "feat": torch.zeros(B, stride, 512, device=self.device, dtype=torch.float32),
+                    "global_feat": torch.empty(B, 2048, device=self.device, dtype=torch.float32)}
+        return self._forward("ifd_dgcnn_forward", pc, n_points, _lib.IfdDgcnnAux, aux_table, want_aux, want_pred)
 
 
 class PointNet2Classifier(Classifier):
@@ -1495,50 +1490,27 @@ class PointNet2Classifier(Classifier):
     def __init__(self, weights: np.ndarray, device=None):
         self.lib = _lib.load()
         self.feature_transform = False
-        w = np.ascontiguousarray(weights, dtype=np.float32)
-        want = self.lib.ifd_pn2_weight_count()
-        if w.size != want:
-            raise IfdError("expected %d pointnet2 weights, got %d" % (want, w.size))
-        if not torch.cuda.is_available():
-            raise IfdError("no GPU visible: the classifier only runs on an MI355X (no CPU fallback)")
-        self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
-        with torch.cuda.device(self.device):
-            self.ctx = self.lib.ifd_pn2_create(w.ctypes.data, w.size, self.N_CLASSES, self.device.index or 0)
-        if not self.ctx:
-            raise IfdError((self.lib.ifd_last_error(None) or b"ifd_pn2_create failed").decode())
+        self._create("ifd_pn2_create", self.lib.ifd_pn2_weight_count(), "pointnet2 weights", weights, device)
 
     def logits(self, pc, n_points=None, fps_start=None, want_aux: bool = False, want_pred: bool = False):
         """pc, n_points: as Classifier.logits.  Returns logits [B,40]; with want_aux also {"fps1" [B,512], "fps2" [B,128],
         "ball1" [B,512,32], "ball2" [B,128,64] (int32), "l1_feat" [B,512,128], "l2_feat" [B,128,256], "global_feat" [B,1024],
         "pred" [B] int32}."""
-        pc, n_points = self._batch(pc, n_points)
-        B, stride = int(pc.shape[0]), int(pc.shape[1])
-        if B < 1 or stride < 1:
-            raise IfdError("empty batch")
-        if fps_start is not None:
-            fps_start = torch.as_tensor(fps_start).to(device=self.device, dtype=torch.int32).contiguous()
-            if tuple(fps_start.shape) != (B, 2):
-                raise IfdError("fps_start must be [B,2], got %s" % (tuple(fps_start.shape),))
-        out = torch.empty(B, self.N_CLASSES, device=self.device, dtype=torch.float32)
-        aux, st = None, None
-        if want_aux or want_pred:
-            aux = {"pred": torch.empty(B, device=self.device, dtype=torch.int32)}
-            a = _lib.IfdPn2Aux()
-            a.pred = aux["pred"].data_ptr()
-            if want_aux:
-                n1, s1, n2, s2 = _lib.PN2_NPOINT1, _lib.PN2_NSAMPLE1, _lib.PN2_NPOINT2, _lib.PN2_NSAMPLE2
-                i32, f32 = dict(device=self.device, dtype=torch.int32), dict(device=self.device, dtype=torch.float32)
-                aux.update(fps1=torch.empty(B, n1, **i32), fps2=torch.empty(B, n2, **i32), ball1=torch.empty(B, n1, s1, **i32),
-                           ball2=torch.empty(B, n2, s2, **i32), l1_feat=torch.empty(B, n1, 128, **f32),
-                           l2_feat=torch.empty(B, n2, 256, **f32), global_feat=torch.empty(B, 1024, **f32))
-                for name in ("fps1", "fps2", "ball1", "ball2", "l1_feat", "l2_feat", "global_feat"):
-                    setattr(a, name, aux[name].data_ptr())
-            st = C.byref(a)
-        with torch.cuda.device(self.device):
-            self._check(self.lib.ifd_pn2_forward(self.ctx, pc.data_ptr(), None if n_points is None else n_points.data_ptr(),
-                                                 None if fps_start is None else fps_start.data_ptr(), B, stride, out.data_ptr(), st,
-                                                 torch.cuda.current_stream(self.device).cuda_stream))
-        return (out, aux) if aux is not None else out
+        def starts(B):
+            if fps_start is None:
+                return (None,)
+            t = torch.as_tensor(fps_start).to(device=self.device, dtype=torch.int32).contiguous()
+            if tuple(t.shape) != (B, 2):
+                raise IfdError("fps_start must be [B,2], got %s" % (tuple(t.shape),))
+            return (t,)
+
+        def aux_table(B, stride):
+            n1, s1, n2, s2 = _lib.PN2_NPOINT1, _lib.PN2_NSAMPLE1, _lib.PN2_NPOINT2, _lib.PN2_NSAMPLE2
+            i32, f32 = dict(device=self.device, dtype=torch.int32), dict(device=self.device, dtype=torch.float32)
+            return dict(fps1=torch.empty(B, n1, **i32), fps2=torch.empty(B, n2, **i32), ball1=torch.empty(B, n1, s1, **i32),
+                        ball2=torch.empty(B, n2, s2, **i32), l1_feat=torch.empty(B, n1, 128, **f32),
+                        l2_feat=torch.empty(B, n2, 256, **f32), global_feat=torch.empty(B, 1024, **f32))
+        return self._forward("ifd_pn2_forward", pc, n_points, _lib.IfdPn2Aux, aux_table, want_aux, want_pred, extra=starts)
 
     def predict(self, pc, n_points=None, fps_start=None) -> torch.Tensor:
         """argmax of the logits, [B] int64 (the lowest class among equal logits)."""
