@@ -18,7 +18,12 @@ with h [140,256] the float64 oracle's post-LeakyReLU linear2 output on bench.syn
 s = h.std(0), live = s > 1e-6 max(s):
     linear3.weight <- linear3.weight * where(live, 1/s, 0)[None,:] * sqrt(3 * 256 / live.sum()),  linear3.bias <- -(linear3.weight @ mu),
 rounded to float32, so that the predicted class varies from cloud to cloud.  ``make_tied_weights`` copies linear3's rows 0..19
-onto 20..39: 20 exact ties in every cloud's logits."""
+onto 20..39: 20 exact ties in every cloud's logits.
+
+The neighbour choice has two judges.  ``check_neighbours``: exact float64 scores at a derived rounding bound, whatever the order
+of summation.  ``check_neighbours_exact``: the header's own float32 arithmetic restated in numpy (``fma32``, ``header_scores``,
+``header_neighbours``), equality required.  ``wave_trace`` restates the kernel's queue discipline to certify that an input works it,
+and ``curve_cloud`` / ``in_runs`` / ``tight_cloud`` / ``translated_cloud`` make the inputs that do, or whose scores nearly tie."""
 import functools
 
 import numpy as np
@@ -218,3 +223,192 @@ def check_neighbours(x, idx, k, what=""):
     bad = np.nonzero(lo < hi - 2 * tau)[0]
     assert bad.size == 0, (what, "rows with a better candidate left out", bad[:10], (hi - lo)[bad[:10]], tau[bad[:10]])
     return worst
+
+
+# ---- the header's neighbour choice, bit for bit (include/ifd_dgcnn.h, "Neighbour choice") ------------------------------------
+_TIE_MASK, _TIE_HALF = np.int64((1 << 29) - 1), np.int64(1 << 28)      # the 29 bits float64 has below float32's last one
+
+
+def _fma32(a, b, c):
+    """fma32 on float64 arrays that hold float32 values; -> float64 holding float32 values."""
+    p = a * b                                              # exact: 24 + 24 bits
+    s = p + c
+    r = s.astype(np.float32)
+    # Rounding s once more is wrong only where s lies exactly half way between two float32 and p + c was not exact.  Such an s
+    # has 1 0...0 below float32's last bit (below 2^-126 float32's last bit lies higher: every such s is looked at).
+    near = ((s.view(np.int64) & _TIE_MASK) == _TIE_HALF) | (np.abs(s) < 2.0 ** -126)
+    if near.any():
+        at = np.nonzero(near)
+        p, c, s, r0 = np.broadcast_to(p, s.shape)[at], np.broadcast_to(c, s.shape)[at], s[at], r[at]
+        t = s - p                                          # TwoSum: p + c = s + e exactly
+        e = (p - (s - t)) + (c - t)
+        rd = r0.astype(np.float64)
+        other = np.where(s > rd, np.nextafter(r0, np.float32(np.inf)), np.nextafter(r0, np.float32(-np.inf)))
+        tie = (s != rd) & (s - rd == other.astype(np.float64) - s)
+        lo, hi = np.minimum(r0, other), np.maximum(r0, other)
+        r[at] = np.where(tie & (e > 0), hi, np.where(tie & (e < 0), lo, r0))
+    return r.astype(np.float64)
+
+
+def fma32(a, b, c):
+    """Correctly rounded float32 fused multiply-add on arrays (finite values): the product is exact in float64, the sum is
+    rounded to float64 and then to float32, and where the float64 sum lies exactly on a float32 tie while its own rounding error
+    e (TwoSum) is not zero, the result is the neighbour on e's side - the double-rounding case."""
+    a, b, c = (np.asarray(v, dtype=np.float32).astype(np.float64) for v in (a, b, c))
+    a, b, c = np.broadcast_arrays(a, b, c)
+    return _fma32(a, b, np.ascontiguousarray(c)).astype(np.float32)
+
+
+def header_scores(x, rows=None):
+    """x [n,C] float32 -> s [len(rows), n] float32, the header's score of every candidate for the queries ``rows`` (all of them
+    by default): d = fmaf(x_i[c], x_j[c], d) from 0 over c ascending, |x_j|^2 the same chain on (x_j, x_j), s = fmaf(2, d, -|x_j|^2)."""
+    x = np.asarray(x, dtype=np.float32).astype(np.float64)
+    n, C = x.shape
+    q = x if rows is None else x[np.asarray(rows, dtype=np.int64)]
+    d = np.zeros((len(q), n))
+    nrm = np.zeros(n)
+    for c in range(C):
+        d = _fma32(q[:, c:c + 1], x[None, :, c], d)
+        nrm = _fma32(x[:, c], x[:, c], nrm)
+    return _fma32(np.float64(2.0), d, np.broadcast_to(-nrm[None, :], d.shape)).astype(np.float32)
+
+
+def _best_first(S):
+    """Every row's candidates by (score descending, index ascending)."""
+    return np.argsort(-np.asarray(S), axis=1, kind="stable")
+
+
+def header_neighbours(x, k, rows=None, scores=None):
+    """-> [len(rows), k] int64: the header's choice for the queries ``rows``, every row sorted ascending.  ``scores``:
+    header_scores(x, rows) where the caller has it already."""
+    S = header_scores(x, rows) if scores is None else scores
+    return np.sort(_best_first(S)[:, :k], axis=1)
+
+
+def tied_rows(x, k, rows=None, scores=None):
+    """-> bool [len(rows)]: the k-th and the (k + 1)-th best score of the row are equal, so the lowest-index rule decides."""
+    S = header_scores(x, rows) if scores is None else scores
+    if k >= S.shape[1]:
+        return np.zeros(len(S), bool)
+    top = np.take_along_axis(S, _best_first(S)[:, k - 1:k + 1], axis=1)
+    return top[:, 0] == top[:, 1]
+
+
+def check_neighbours_exact(x, idx, k, rows=None, what="", scores=None):
+    """idx [len(rows), k]: the neighbours chosen for the queries ``rows`` (all by default) of the layer input x [n,C] float32.
+    Sorted, every row must equal header_neighbours' row.  -> the number of rows with an exact score tie at the k-th place."""
+    x = np.asarray(x, dtype=np.float32)
+    rows = np.arange(len(x)) if rows is None else np.asarray(rows, dtype=np.int64)
+    S = header_scores(x, rows) if scores is None else scores
+    got = np.sort(np.asarray(idx).astype(np.int64), axis=1)
+    assert got.shape == (len(rows), k), (what, got.shape, (len(rows), k))
+    want = header_neighbours(x, k, rows, scores=S)
+    bad = np.nonzero((got != want).any(1))[0]
+    if bad.size:
+        r = int(bad[0])
+        only_got = [j for j in got[r].tolist() if j not in set(want[r].tolist())]
+        only_want = [j for j in want[r].tolist() if j not in set(got[r].tolist())]
+
+        def bits(js):
+            return ["%d: %s" % (j, "0x%08x" % S[r, j:j + 1].view(np.uint32)[0] if 0 <= j < S.shape[1] else "out of range") for j in js]
+        raise AssertionError("%s: %d of %d rows differ from the header's choice; row %d: chosen %s, the header has %s; only chosen "
+                             "(index: score bits) %s, only in the header's %s" % (what, bad.size, len(rows), int(rows[r]), got[r].tolist(),
+                                                                                  want[r].tolist(), bits(only_got), bits(only_want)))
+    return int(tied_rows(x, k, rows, scores=S).sum())
+
+
+def wave_trace(S, k, pend=8):
+    """The queue discipline of dg_knn_kernel restated for one workgroup: S [Q <= 64, n] are the scores of its queries.  The
+    first k candidates are taken; a later one is queued where it beats the query's threshold (the worst kept score) strictly;
+    when any queue holds ``pend`` entries every queue is worked off, and once more at the end; a queued entry is applied only
+    where it still beats the threshold, replacing the worst kept entry (the lowest score, of equals the highest index).
+    -> {"queued", "applied", "stale" [Q] (stale = queued - applied), "flushes", "sets" [Q,k] sorted ascending}.
+    It certifies that an input works the mechanism; it never judges the GPU."""
+    S = np.asarray(S)
+    Q, n = S.shape
+    kk = min(k, n)
+    q = np.arange(Q)
+    sc, ix = S[:, :kk].copy(), np.tile(np.arange(kk), (Q, 1))
+    thr, tpos = np.zeros(Q, S.dtype), np.zeros(Q, np.int64)
+
+    def rescan(w):
+        m = sc[w].min(1)
+        thr[w] = m
+        tpos[w] = np.where(sc[w] == m[:, None], ix[w], -1).argmax(1)
+
+    rescan(q)
+    ps, pi = np.zeros((Q, pend), S.dtype), np.zeros((Q, pend), np.int64)
+    pending = np.zeros(Q, np.int64)
+    queued, applied = np.zeros(Q, np.int64), np.zeros(Q, np.int64)
+    flushes = 0
+
+    def flush():
+        for t in range(pend):
+            w = np.nonzero((t < pending) & (ps[:, t] > thr))[0]
+            if w.size:
+                sc[w, tpos[w]], ix[w, tpos[w]] = ps[w, t], pi[w, t]
+                applied[w] += 1
+                rescan(w)
+        pending[:] = 0
+
+    for j in range(kk, n):
+        w = np.nonzero(S[:, j] > thr)[0]
+        ps[w, pending[w]], pi[w, pending[w]] = S[w, j], j
+        pending[w] += 1
+        queued[w] += 1
+        if (pending == pend).any():
+            flush()
+            flushes += 1
+    flush()
+    flushes += 1
+    return {"queued": queued, "applied": applied, "stale": queued - applied, "flushes": flushes, "sets": np.sort(ix, axis=1)}
+
+
+# ---- inputs whose row order works the queues (tests/test_dgcnn_cpu.py certifies them, tests/test_gpu_dgcnn_exact.py runs them)
+CURVE_POINTS, CURVE_SEED = 513, 1
+STRESS_GROUP = np.arange(448, 512)                     # the workgroup whose queues the floors are about
+
+
+def curve_cloud(seed=CURVE_SEED):
+    """513 points along a curve in index order: t = linspace(-0.9, 0.9), rows (t, 0.05 sin 3t, 0.05 cos 2t) + N(0, 1e-4)."""
+    t = np.linspace(-0.9, 0.9, CURVE_POINTS)
+    c = np.stack([t, 0.05 * np.sin(3 * t), 0.05 * np.cos(2 * t)], axis=1)
+    return (c + np.random.default_rng(seed).normal(0.0, 1e-4, c.shape)).astype(np.float32)
+
+
+def in_runs(c, k, L):
+    """From row k on, every run of L consecutive rows reversed."""
+    out = c.copy()
+    for a in range(k, len(c), L):
+        out[a:a + L] = c[a:a + L][::-1]
+    return out
+
+
+# name: (k, run length or None, the counter the floor is on, the floor for every query of STRESS_GROUP)
+STRESS = {"approach, k = 20": (20, None, "queued", 0.8 * (CURVE_POINTS - 20)),
+          "runs of 8, k = 1": (1, 8, "stale", 300),
+          "runs of 8, k = 5": (5, 8, "stale", 100),
+          "runs of 32, k = 20": (20, 32, "stale", 30),
+          "approach, k = 32": (32, None, "queued", 0.5 * (CURVE_POINTS - 32)),
+          "runs of 48, k = 32": (32, 48, "queued", 0.5 * (CURVE_POINTS - 32))}
+
+
+def stress_cloud(name):
+    k, L, _, _ = STRESS[name]
+    c = curve_cloud()
+    return (c if L is None else in_runs(c, k, L)), k
+
+
+def tight_cloud(c):
+    """c / 16 + (8, -8, 8): a cloud 1/16 the size, far from the origin.  Its squared distances (1e-4) are a few float32 steps of
+    its scores (near 192, a step is 1.5e-5), and its features keep a large common part through all four layers: the k-th and
+    the (k + 1)-th score are often one step apart or equal, so a choice made with the channels summed in another order, an
+    unfused |x_j|^2 or the wrong index among equal scores differs from the header's in many rows (tests/test_dgcnn_cpu.py)."""
+    return (np.asarray(c, dtype=np.float32) * np.float32(1.0 / 16) + np.array([8, -8, 8], np.float32)).astype(np.float32)
+
+
+def translated_cloud(n=512):
+    """A bench.synth_clouds cloud moved by (+8, -8, +8): the scores cancel (|x|^2 is near 192, a neighbour's score differs from
+    it by 1e-3), so exact ties at the k-th place occur on natural data."""
+    import bench
+    return (bench.synth_clouds(4, seed=77)[2][:n] + np.array([8, -8, 8], np.float32)).astype(np.float32)

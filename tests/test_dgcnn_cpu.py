@@ -330,3 +330,240 @@ def test_cli_refusals(tmp_path, capsys):
     assert inference.main(["--data_root", "x.npz", "--model", "dgcnn"], make_classifier=never) == 2
     err = capsys.readouterr().err
     assert "not built" in err and "ifdefense_amd.dgcnn_inference" in err
+
+
+# ---------------------------------------------------------------------------------------------- the header's choice, exactly
+def _round_f32(v):
+    """A Fraction rounded to the nearest float32, ties to even, denormals included (no overflow)."""
+    from fractions import Fraction
+    if v == 0:
+        return np.float32(0.0)
+    a, e = abs(v), 0
+    while a >= 2 ** (e + 1):
+        e += 1
+    while a < Fraction(2) ** e:
+        e -= 1
+    quantum = Fraction(2) ** (max(e, -126) - 23)
+    m = a / quantum
+    n = m.numerator // m.denominator
+    rest = m - n
+    if rest > Fraction(1, 2) or (rest == Fraction(1, 2) and n % 2 == 1):
+        n += 1
+    r = float(n * quantum)                                   # exact: at most 24 bits
+    return np.float32(-r if v < 0 else r)
+
+
+def _exact_fma(a, b, c):
+    from fractions import Fraction
+    return np.array([_round_f32(Fraction(float(x)) * Fraction(float(y)) + Fraction(float(z))) for x, y, z in zip(a, b, c)], np.float32)
+
+
+def _same_bits(a, b):
+    return np.array_equal(np.asarray(a, np.float32).view(np.uint32), np.asarray(b, np.float32).view(np.uint32))
+
+
+def test_fma32_equals_rational_arithmetic_on_random_triples():
+    import dgcnn_oracle as DO
+    rng = np.random.default_rng(41)
+    n = 24000
+
+    def draw(lo=-5.0, hi=5.0):
+        return (rng.choice([-1.0, 1.0], n) * 10.0 ** rng.uniform(lo, hi, n) * rng.uniform(1, 2, n)).astype(np.float32)
+    a, b, c = draw(), draw(), draw()
+    c[:8000] = -(a[:8000] * b[:8000] * (1 + rng.normal(0, 1e-6, 8000))).astype(np.float32)        # heavy cancellation
+    c[8000:12000] = (a[8000:12000] * b[8000:12000] * rng.choice([-1, 1], 4000) * 2.0 ** rng.integers(20, 28, 4000)).astype(np.float32)
+    assert _same_bits(DO.fma32(a, b, c), _exact_fma(a, b, c))
+    # results below 2^-126, where float32's last bit lies higher
+    a, b, c = draw(-22, -19)[:4000], draw(-22, -19)[:4000], draw(-44, -38)[:4000]
+    got = DO.fma32(a, b, c)
+    assert (np.abs(got) < 2.0 ** -126).mean() > 0.3 and (got != 0).mean() > 0.9
+    assert _same_bits(got, _exact_fma(a, b, c))
+    assert DO.fma32(np.float32(3), np.float32(5), np.float32(-15)) == 0 and DO.fma32([1, 2], [3, 4], 1.0).dtype == np.float32
+
+
+def test_fma32_in_the_double_rounding_case():
+    """c with an odd (or even) last bit and a * b half an ulp of c, less or more than a term below 2^-53 relative: the float64
+    sum lies exactly on a float32 tie and its own rounding error decides."""
+    import dgcnn_oracle as DO
+    u = 2.0 ** -23
+    lo, hi = np.float32(1 - u), np.float32(1 + u)
+    A, B, Cc = [], [], []
+    for sc in (1.0, 2.0 ** -40, 2.0 ** 37):
+        for sg in (1.0, -1.0):
+            for c in (1 + u, 1 + 2 * u, 1 + 3 * u, 1.5 + u, 2 - u, 2 - 2 * u):
+                for x, y in ((hi, lo), (hi, hi), (lo, lo)):               # a b = 2^-24 (1 - 2^-46), (1 + 2^-23)^2, (1 - 2^-23)^2
+                    A.append(sg * sc * 2.0 ** -12 * x)
+                    B.append(2.0 ** -12 * y)
+                    Cc.append(sg * sc * c)
+                    A.append(-sg * sc * 2.0 ** -12 * x)                     # ... and half an ulp below c
+                    B.append(2.0 ** -12 * y)
+                    Cc.append(sg * sc * c)
+    a, b, c = (np.array(v, np.float32) for v in (A, B, Cc))
+    assert np.array_equal(a.astype(np.float64), np.array(A)) and np.array_equal(c.astype(np.float64), np.array(Cc))
+    want = _exact_fma(a, b, c)
+    assert _same_bits(DO.fma32(a, b, c), want)
+    naive = (a.astype(np.float64) * b + c).astype(np.float32)
+    wrong = int((naive.view(np.uint32) != want.view(np.uint32)).sum())
+    print("plain float32(float64(a) * b + c) is wrong on %d of %d crafted triples" % (wrong, len(a)))
+    assert wrong >= 1
+    one = DO.fma32(np.float32(2.0 ** -12) * hi, np.float32(2.0 ** -12) * lo, hi)      # the pair the contract names
+    assert one == hi and np.float32(np.float64(np.float32(2.0 ** -12) * hi) * np.float64(np.float32(2.0 ** -12) * lo) + np.float64(hi)) != hi
+
+
+def _lattice():
+    rng = np.random.default_rng(5)                                                   # test_gpu_dgcnn's lattice
+    return (rng.integers(0, 5, size=(257, 3)) * 0.25).astype(np.float32)
+
+
+def test_header_neighbours_agree_with_the_oracle(g):
+    import dgcnn_oracle as DO
+    pcs = golden_clouds(g)
+    o = DO.forward(DO.to_torch(DO.make_weights(0)), pcs)
+    cols = ((0, 64), (64, 128), (128, 256))
+    for i, c in enumerate(pcs):
+        for l in range(4):
+            x = c if l == 0 else o["feat"][i][:, cols[l - 1][0]:cols[l - 1][1]].numpy()
+            idx = DO.header_neighbours(x, 20)
+            DO.check_neighbours(x, idx, 20, "header, cloud %d layer %d" % (i, l + 1))
+            assert DO.check_neighbours_exact(x, idx[:, ::-1], 20) >= 0
+            s64 = DO.exact_scores(x)
+            tau = DO.gamma(x.shape[1] + 2) * (np.sqrt((x.astype(np.float64) ** 2).sum(1))[:, None] + np.sqrt((x.astype(np.float64) ** 2).sum(1)).max()) ** 2
+            assert (np.abs(DO.header_scores(x) - s64) <= tau).all()
+    lat = _lattice()
+    s = DO.exact_scores(lat)
+    assert np.array_equal(DO.header_scores(lat).astype(np.float64), s)                # exact in float32 there
+    got = DO.header_neighbours(lat, 20)
+    for i in range(257):
+        assert np.array_equal(got[i], np.sort(np.lexsort((np.arange(257), -s[i]))[:20])), i
+    assert DO.check_neighbours_exact(lat, got, 20) > 100                              # ties everywhere on the lattice
+    part = np.array([256, 0, 77])
+    assert np.array_equal(DO.header_neighbours(lat, 20, part), got[part]) and np.array_equal(DO.header_scores(lat, part), DO.header_scores(lat)[part])
+
+
+def test_exact_checker_refuses_planted_errors(g):
+    import dgcnn_oracle as DO
+    c = golden_clouds(g)[0]
+    k, row = 20, 7
+    S = DO.header_scores(c)
+    good = DO.header_neighbours(c, k)
+    assert DO.check_neighbours_exact(c, good, k) == int(DO.tied_rows(c, k).sum())
+    order = np.lexsort((np.arange(len(c)), -S[row]))
+    assert S[row, order[k - 1]] > S[row, order[k]]
+    bad = good.copy()
+    bad[row, np.nonzero(bad[row] == order[k - 1])[0][0]] = order[k]                    # the k-th swapped for the (k + 1)-th
+    with pytest.raises(AssertionError, match="row %d" % row):
+        DO.check_neighbours_exact(c, bad, k, what="swapped")
+    DO.check_neighbours(c, good, k)
+    dup = good.copy()
+    dup[5, 1] = dup[5, 0]
+    with pytest.raises(AssertionError, match="row 5"):
+        DO.check_neighbours_exact(c, dup, k, what="repeated")
+    with pytest.raises(AssertionError, match="row 2"):
+        DO.check_neighbours_exact(c, good[[0, 1, 3]], k, rows=[0, 1, 2], what="another row's set")
+    # a higher index among equal scores: the tolerance check cannot see it, the exact one does
+    lat = _lattice()
+    s = DO.exact_scores(lat)
+    good = DO.header_neighbours(lat, k)
+    tied = np.nonzero(DO.tied_rows(lat, k))[0]
+    row = int(tied[0])
+    order = np.lexsort((np.arange(257), -s[row]))
+    assert s[row, order[k - 1]] == s[row, order[k]] and order[k - 1] < order[k]
+    bad = good.copy()
+    bad[row, np.nonzero(bad[row] == order[k - 1])[0][0]] = order[k]
+    DO.check_neighbours(lat, bad, k)
+    with pytest.raises(AssertionError, match="row %d: " % row):
+        DO.check_neighbours_exact(lat, bad, k, what="higher index among equals")
+
+
+def test_stress_inputs_meet_their_floors_and_the_trace_is_the_header():
+    """The inputs of tests/test_gpu_dgcnn_exact.py section c, from the oracle alone: every query of the workgroup 448 .. 511
+    meets the floor on layer 1, and the restated queue discipline ends with the header's sets."""
+    import dgcnn_oracle as DO
+    assert DO.CURVE_POINTS == 513 and list(DO.STRESS_GROUP[[0, -1]]) == [448, 511]
+    for name, (k, L, counter, floor) in DO.STRESS.items():
+        c, kk = DO.stress_cloud(name)
+        assert kk == k and c.shape == (513, 3) and c.dtype == np.float32
+        S = DO.header_scores(c, DO.STRESS_GROUP)
+        tr = DO.wave_trace(S, k)
+        print("%s: queued %d .. %d (%.2f .. %.2f of n - k), stale %d .. %d, applied %d .. %d, %d flushes"
+              % (name, tr["queued"].min(), tr["queued"].max(), tr["queued"].min() / (513 - k), tr["queued"].max() / (513 - k),
+                 tr["stale"].min(), tr["stale"].max(), tr["applied"].min(), tr["applied"].max(), tr["flushes"]))
+        assert (tr[counter] >= floor).all(), (name, counter, int(tr[counter].min()), floor)
+        assert np.array_equal(tr["queued"], tr["applied"] + tr["stale"])
+        assert np.array_equal(tr["sets"], DO.header_neighbours(c, k, DO.STRESS_GROUP, scores=S)), name
+        for rows in (np.arange(0, 64), np.arange(512, 513)):                         # the first workgroup, and the last (one query)
+            S = DO.header_scores(c, rows)
+            assert np.array_equal(DO.wave_trace(S, k)["sets"], DO.header_neighbours(c, k, rows, scores=S)), (name, rows[0])
+    base = DO.curve_cloud()
+    assert np.array_equal(DO.stress_cloud("approach, k = 20")[0], base)
+    r8 = DO.stress_cloud("runs of 8, k = 5")[0]
+    assert np.array_equal(r8[:5], base[:5]) and np.array_equal(r8[5:13], base[5:13][::-1]) and np.array_equal(r8[509:], base[509:][::-1])
+    # the trace on other inputs: ties (the lattice), a cloud of exactly k points, pend = 1, random order for contrast
+    lat = _lattice()
+    for rows in (np.arange(64), np.arange(192, 256), np.arange(256, 257)):
+        S = DO.header_scores(lat, rows)
+        for pend in (1, 8):
+            assert np.array_equal(DO.wave_trace(S, 20, pend)["sets"], DO.header_neighbours(lat, 20, rows, scores=S))
+    S = DO.header_scores(base[:20])
+    tr = DO.wave_trace(S, 20)
+    assert np.array_equal(tr["sets"], np.tile(np.arange(20), (20, 1))) and tr["queued"].sum() == 0 and tr["flushes"] == 1
+    rng = np.random.default_rng(1)
+    sph = rng.normal(size=(513, 3))
+    sph = (sph / np.linalg.norm(sph, axis=1)[:, None]).astype(np.float32)
+    tr = DO.wave_trace(DO.header_scores(sph, DO.STRESS_GROUP), 20)
+    print("random sphere, k = 20: queued %.2f of n - k, stale %.1f a query, %d flushes" % (tr["queued"].mean() / 493, tr["stale"].mean(), tr["flushes"]))
+
+
+def test_translated_cloud_has_exact_ties_off_the_lattice():
+    """The input of test_gpu_dgcnn_exact's tie test, from the oracle alone: far from the origin the scores cancel and exact ties
+    at the k-th place occur on natural data."""
+    import dgcnn_oracle as DO
+    c = DO.translated_cloud()
+    ties = int(DO.tied_rows(c, 20).sum())
+    print("translated cloud: %d of %d rows tied at the 20th place in layer 1" % (ties, len(c)))
+    assert ties >= 1
+
+
+def test_tight_clouds_tell_the_header_from_its_near_misses():
+    """The tight clouds of tests/test_gpu_dgcnn_exact.py, from the oracle alone (layer 1): a choice made with the channels summed
+    in descending order, with |x_j|^2 as rounded products and sums, or with the highest index among equal scores differs from the
+    header's, at 65 points for every k the GPU test runs and on its 96 rows at 2048 points.  On the natural clouds of the same
+    sizes none of the three differs in a single row: there the exact check sees no more than the tolerance does."""
+    import bench
+    import dgcnn_oracle as DO
+    s = bench.synth_clouds(24, seed=77)
+    big = np.ascontiguousarray(np.concatenate([s[22], 0.7 * s[23] - 0.2]), dtype=np.float32)
+    rows = np.concatenate([np.arange(32), np.arange(2016, 2048), np.sort(np.random.default_rng(2048).choice(np.arange(32, 2016), 32, replace=False))])
+
+    def differing(x, k, rows):
+        x = np.asarray(x, np.float32)
+        S = DO.header_scores(x, rows)
+        want = DO.header_neighbours(x, k, rows, scores=S)
+        q = x if rows is None else x[rows]
+        nrm = np.zeros(len(x), np.float32)
+        d = np.zeros((len(q), len(x)), np.float32)
+        for c in range(x.shape[1]):
+            nrm = nrm + x[:, c] * x[:, c]
+            d = DO.fma32(q[:, c:c + 1], x[None, :, c], d)
+        unfused = np.float32(2) * d - nrm[None, :]
+        highest = S.shape[1] - 1 - np.argsort(-S[:, ::-1], axis=1, kind="stable")        # score descending, index DEscending
+        out = []
+        for got in (DO.header_neighbours(x[:, ::-1].copy(), k, rows), DO.header_neighbours(x, k, rows, scores=unfused),
+                    np.sort(highest[:, :k], axis=1)):
+            out.append(int((got != want).any(1).sum()))
+            if out[-1]:
+                with pytest.raises(AssertionError):
+                    DO.check_neighbours_exact(x, got, k, rows)
+        return out
+    total = np.zeros(3, int)
+    for k in (1, 2, 3, 4, 5, 8, 9, 20, 31, 32):
+        n = differing(DO.tight_cloud(s[9][:65]), k, None)
+        print("tight 65 points, k = %2d: rows that differ (descending channels, unfused norm, highest index): %s" % (k, n))
+        assert n[0] + n[1] >= 1, k
+        total += n
+        assert differing(s[9][:65], k, None) == [0, 0, 0]
+    assert (total >= 10).all(), total
+    n = differing(DO.tight_cloud(big), 20, rows)
+    print("tight 2048 points, 96 rows: %s" % n)
+    assert min(n) >= 32
+    assert differing(big, 20, rows) == [0, 0, 0]

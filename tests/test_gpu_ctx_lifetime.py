@@ -3,8 +3,8 @@
 Growth: every context buffer that grows on demand and has no stale-workspace test elsewhere (ws_enc, adam_tab and ws, ws_fold,
 ws_dup; the classifier, attack and MISE workspaces have theirs) sees a small call, a larger one - the buffer is freed and
 allocated again - and the small call again; both small results must equal, bit for bit, the same call on a fresh context.
-Create / close: three contexts of each of the four kinds, one after the other in one process, each making the smallest call of
-its kind; the three outputs must be equal bit for bit.  Seeded weights and inputs throughout.  Nothing here looks at the free
+Create / close: three contexts of each kind, one after the other in one process, each making the smallest call of its kind; the
+three outputs must be equal bit for bit.  The DGCNN and PointNet++ victims have both tests, on ``logits``.  Seeded weights and inputs throughout.  Nothing here looks at the free
 device memory: other processes move it."""
 import numpy as np
 import pytest
@@ -125,3 +125,45 @@ def test_create_call_close_three_times_classifier(cls_w):
     import ifdefense_amd as I
     pc = _rand(25, 1, 1, 3, scale=0.9)                  # one cloud of one point
     _three_lives(lambda: I.Classifier(cls_w, device=DEV), lambda k: k.logits(pc))
+
+
+# ---- the two later victims: DGCNN (include/ifd_dgcnn.h) and PointNet++ (include/ifd_pn2.h) -------------------------------------
+@pytest.fixture(scope="module")
+def dgcnn_w():
+    import ifdefense_amd as I
+    return I.weights.pack_state_dict(I.weights.dgcnn_random_state_dict(1), "dgcnn")
+
+
+@pytest.fixture(scope="module")
+def pn2_w():
+    import ifdefense_amd as I
+    return I.weights.pack_state_dict(I.weights.pointnet2_random_state_dict(1), "pointnet2")
+
+
+VICTIM_CALLS = (0, 1, 0)                                # 1 x 64 points, 2 x 2048, 1 x 64: a cloud's workspace grows 32-fold
+
+
+def _victim_logits(k, which):
+    return k.logits(_rand(31 + which, (1, 2)[which], (64, 2048)[which], 3, scale=0.9))
+
+
+def test_create_call_close_three_times_dgcnn(dgcnn_w):
+    import ifdefense_amd as I
+    pc = _rand(26, 1, 20, 3, scale=0.9)                 # one cloud of k points
+    _three_lives(lambda: I.DgcnnClassifier(dgcnn_w, device=DEV), lambda k: k.logits(pc))
+
+
+def test_create_call_close_three_times_pointnet2(pn2_w):
+    import ifdefense_amd as I
+    pc = _rand(27, 1, 1, 3, scale=0.9)                  # one cloud of one point
+    _three_lives(lambda: I.PointNet2Classifier(pn2_w, device=DEV), lambda k: k.logits(pc))
+
+
+def test_dgcnn_workspace_grows(dgcnn_w):
+    import ifdefense_amd as I
+    _small_large_small(lambda: I.DgcnnClassifier(dgcnn_w, device=DEV), _victim_logits, VICTIM_CALLS)
+
+
+def test_pointnet2_workspace_grows(pn2_w):
+    import ifdefense_amd as I
+    _small_large_small(lambda: I.PointNet2Classifier(pn2_w, device=DEV), _victim_logits, VICTIM_CALLS)
