@@ -346,6 +346,27 @@ PN2_SIGNATURES = {
                                   C.c_void_p]),
 }
 
+# include/ifd_pc.h (the PointConv victim classifier), versioned on its own
+PC_ABI_VERSION = 1
+PC_MAX_POINTS, PC_MIN_POINTS = 2048, 32
+PC_NPOINT1, PC_K1, PC_NPOINT2, PC_K2 = 512, 32, 128, 64
+PC_CHUNK = 32                        # IFD_PC_CHUNK: most clouds of one chunk of ifd_pc_forward
+
+
+class IfdPcAux(C.Structure):
+    _fields_ = [("fps1", C.c_void_p), ("fps2", C.c_void_p), ("knn1", C.c_void_p), ("knn2", C.c_void_p), ("dens1", C.c_void_p),
+                ("dens2", C.c_void_p), ("dens3", C.c_void_p), ("l1_feat", C.c_void_p), ("l2_feat", C.c_void_p),
+                ("global_feat", C.c_void_p), ("pred", C.c_void_p)]
+
+
+PC_SIGNATURES = {
+    "ifd_pc_abi_version": (C.c_int, []),
+    "ifd_pc_weight_count": (C.c_size_t, []),
+    "ifd_pc_create": (C.c_void_p, [C.c_void_p, C.c_size_t, C.c_int, C.c_int]),
+    "ifd_pc_forward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.POINTER(IfdPcAux),
+                                 C.c_void_p]),
+}
+
 _lib = None
 
 
@@ -363,7 +384,7 @@ def load() -> C.CDLL:
     for name, (res, args) in list(SIGNATURES.items()) + list(DUP_SIGNATURES.items()) + list(CLS_SIGNATURES.items()) + \
             list(ATK_SIGNATURES.items()) + list(CW_SIGNATURES.items()) + list(KNN_SIGNATURES.items()) + list(ADD_SIGNATURES.items()) + \
             list(DROP_SIGNATURES.items()) + list(CLUSTER_SIGNATURES.items()) + list(OBJECT_SIGNATURES.items()) + \
-            list(DGCNN_SIGNATURES.items()) + list(PN2_SIGNATURES.items()):
+            list(DGCNN_SIGNATURES.items()) + list(PN2_SIGNATURES.items()) + list(PC_SIGNATURES.items()):
         fn = getattr(lib, name)          # AttributeError if the library lacks a declared symbol
         fn.restype, fn.argtypes = res, args
     if lib.ifd_abi_version() != ABI_VERSION:
@@ -390,5 +411,7 @@ def load() -> C.CDLL:
         raise ImportError("libifd.so DGCNN ABI %d != binding DGCNN ABI %d; rebuild" % (lib.ifd_dgcnn_abi_version(), DGCNN_ABI_VERSION))
     if lib.ifd_pn2_abi_version() != PN2_ABI_VERSION:
         raise ImportError("libifd.so PN2 ABI %d != binding PN2 ABI %d; rebuild" % (lib.ifd_pn2_abi_version(), PN2_ABI_VERSION))
+    if lib.ifd_pc_abi_version() != PC_ABI_VERSION:
+        raise ImportError("libifd.so PC ABI %d != binding PC ABI %d; rebuild" % (lib.ifd_pc_abi_version(), PC_ABI_VERSION))
     _lib = lib
     return lib

@@ -15,6 +15,7 @@
 #include "../../include/ifd_cluster.h"
 #include "../../include/ifd_object.h"
 #include "../../include/ifd_dgcnn.h"
+#include "../../include/ifd_pc.h"
 #include "../../include/ifd_pn2.h"
 
 #include <hip/hip_runtime.h>
@@ -144,8 +145,8 @@ struct ifd_ctx {
     DeviceBuffer d_punet;
     PunetImage pimg{};
     DeviceBuffer ws_dup;
-    // victim classifiers (ifd_cls_create, ifd_dgcnn_create, ifd_pn2_create): the weight image of the one victim a context holds -
-    // `model` says which, and so which of cimg / dimg / p2img describes it (pointnet.hip, dgcnn.hip, pointnet2.hip); the scratch is `ws`
+    // victim classifiers (ifd_cls_create, ifd_dgcnn_create, ifd_pn2_create, ifd_pc_create): the weight image of the one victim a context holds -
+    // `model` says which, and so which of cimg / dimg / p2img / pcimg describes it (pointnet.hip, dgcnn.hip, pointnet2.hip, pointconv.hip); the scratch is `ws`
     DeviceBuffer d_victim;
     ClsImage cimg{};
     int cls_feature_transform = 0, cls_classes = 0;
@@ -155,6 +156,7 @@ struct ifd_ctx {
     DgImage dimg{};                // DGCNN: the edge convolutions in split form
     int dg_k = 0;
     Pn2Image p2img{};
+    PcImage pcimg{};               // PointConv (pointconv.hip)
     std::string err;
     unsigned long long* counters() const { return d_counters.get<unsigned long long>(); }
 };
@@ -1967,6 +1969,144 @@ int ifd_pn2_forward(ifd_ctx* ctx, const float* pc, const int32_t* n_points, cons
             }
             return launch_pn2(ctx->d_victim.get<float>(), ctx->p2img, pc + (size_t)c0 * stride * 3, n_points ? n_points + c0 : nullptr,
                               fps_start ? fps_start + (size_t)c0 * 2 : nullptr, n, stride, w, o, logits + (size_t)c0 * nc, nc, s);
+        });
+}
+
+}  // extern "C"
+
+// ---- PointConv victim classifier (include/ifd_pc.h) ------------------------------------------------------------------
+namespace {
+
+constexpr int PC_CHUNK = IFD_PC_CHUNK;       // most clouds per chunk of ifd_pc_forward: the contraction's output is 4 MB a cloud
+static_assert(PC_MAX_POINTS == IFD_PC_MAX_POINTS && PC_MIN_POINTS == IFD_PC_MIN_POINTS && PC_NP1 == IFD_PC_NPOINT1 && PC_K1 == IFD_PC_K1 &&
+              PC_NP2 == IFD_PC_NPOINT2 && PC_K2 == IFD_PC_K2 && PC_MIN_POINTS >= PC_K1, "ifd_pc.h and ifd_internal.h");
+
+// the canonical order: per level densitynet x 3, mlp x 3, weightnet x 3, linear; then fc1 .. fc3
+const ClsTensor PC_LAYERS[33] = {
+    {8, 1}, {8, 8}, {1, 8}, {64, 3}, {64, 64}, {128, 64}, {8, 3}, {8, 8}, {PC_WN, 8}, {128, 128 * PC_WN},
+    {8, 1}, {8, 8}, {1, 8}, {128, 131}, {128, 128}, {256, 128}, {8, 3}, {8, 8}, {PC_WN, 8}, {256, 256 * PC_WN},
+    {8, 1}, {8, 8}, {1, 8}, {256, 259}, {512, 256}, {PC_EMB, 512}, {8, 3}, {8, 8}, {PC_WN, 8}, {PC_EMB, PC_EMB * PC_WN},
+    {512, PC_EMB}, {256, 512}, {CLS_CLASSES, 256}};
+
+size_t pc_count() { return layer_floats(PC_LAYERS); }
+
+// The device image (ifd_internal.h PcImage): DensityNet and WeightNet as they come; an MLP's first layer split into its three
+// coordinate columns, as [out][4] rows, and a plain layer of the feature columns (sa1 has none: its rows carry the bias);
+// everything else row-major as it comes.
+std::vector<float> build_pc_image(const float* w, PcImage& I) {
+    std::vector<float> img;
+    const std::vector<size_t> at = layer_offsets(PC_LAYERS);
+    auto raw = [&](int k, int floats) {                                // three small layers in a row, from layer k on
+        const int off = (int)img.size();
+        img.insert(img.end(), w + at[k], w + at[k] + floats);
+        while (img.size() % 4) img.push_back(0.f);
+        return off;
+    };
+    auto coords = [&](int k, bool with_bias) {
+        const ClsTensor& t = PC_LAYERS[k];
+        const float* W = w + at[k];
+        const int off = (int)img.size();
+        img.resize(img.size() + (size_t)t.out * 4, 0.f);
+        for (int o = 0; o < t.out; ++o) {
+            for (int a = 0; a < 3; ++a) img[off + o * 4 + a] = W[(size_t)o * t.in + a];
+            if (with_bias) img[off + o * 4 + 3] = W[(size_t)t.out * t.in + o];
+        }
+        return off;
+    };
+    auto plain = [&](int k, int skip) { return append_plain_layer(img, w + at[k], PC_LAYERS[k], skip, true); };
+    for (int l = 0; l < 3; ++l) {
+        PcLevel& S = I.sa[l];
+        const int k = 10 * l;
+        S.dn = raw(k, PC_DN_FLOATS);
+        S.first_xyz = coords(k + 3, l == 0);
+        S.u = l == 0 ? DenseLayer{} : plain(k + 3, 3);
+        S.mlp[0] = plain(k + 4, 0); S.mlp[1] = plain(k + 5, 0);
+        S.wn = raw(k + 6, PC_WN_FLOATS);
+        S.lin = plain(k + 9, 0);
+    }
+    for (int j = 0; j < 3; ++j) I.fc[j] = plain(30 + j, 0);
+    I.total = (int)img.size();
+    return img;
+}
+
+// the workspace of ifd_pc_forward over n clouds: 1024 bytes of which the check uses the first two words, then launch_pc's scratch
+PcWs pc_ws(Carve& c, size_t n) {
+    c.take<int32_t>(1024);
+    PcWs w;
+    w.xyz1 = c.take<float>(n * PC_NP1 * 12); w.xyz2 = c.take<float>(n * PC_NP2 * 12); w.xyz3 = c.take<float>(n * PC_NP2 * 12);
+    w.fps1 = c.take<int32_t>(n * PC_NP1 * 4); w.fps2 = c.take<int32_t>(n * PC_NP2 * 4);
+    w.knn1 = c.take<int32_t>(n * PC_NP1 * PC_K1 * 4); w.knn2 = c.take<int32_t>(n * PC_NP2 * PC_K2 * 4);
+    w.dens1 = c.take<float>(n * PC_MAX_POINTS * 4); w.dens2 = c.take<float>(n * PC_NP1 * 4); w.dens3 = c.take<float>(n * PC_NP2 * 4);
+    w.g = c.take<float>(n * PC_NP1 * 128 * PC_WN * 4);
+    w.l1_feat = c.take<float>(n * PC_NP1 * 128 * 4); w.u2 = c.take<float>(n * PC_NP1 * 128 * 4);
+    w.l2_feat = c.take<float>(n * PC_NP2 * 256 * 4); w.s3a = c.take<float>(n * PC_NP2 * 256 * 4);
+    w.s3b = c.take<float>(n * PC_NP2 * 512 * 4); w.s3c = c.take<float>(n * PC_NP2 * PC_EMB * 4);
+    w.wn3 = c.take<float>(n * PC_NP2 * PC_WN * 4);
+    w.gfeat = c.take<float>(n * PC_EMB * 4); w.f1 = c.take<float>(n * 512 * 4); w.f2 = c.take<float>(n * 256 * 4);
+    return w;
+}
+size_t pc_ws_bytes(int n) { return carved_bytes([&](Carve& c) { pc_ws(c, (size_t)n); }); }
+
+}  // namespace
+
+extern "C" {
+
+int ifd_pc_abi_version(void) { return IFD_PC_ABI_VERSION; }
+
+size_t ifd_pc_weight_count(void) { return pc_count(); }
+
+ifd_ctx* ifd_pc_create(const float* weights_host, size_t n_weights, int n_classes, int device) {
+    if (!victim_create_args_ok("ifd_pc_create", weights_host, n_weights, pc_count(), n_classes)) return nullptr;
+    return create_ctx("ifd_pc_create", IFD_MODEL_PC, device, [&](ifd_ctx* ctx) {
+        ctx->cls_classes = n_classes;
+        hipError_t e = upload(ctx->d_victim, build_pc_image(weights_host, ctx->pcimg));
+        if (e == hipSuccess) e = configure_pc_kernels();
+        return e;
+    });
+}
+
+int ifd_pc_forward(ifd_ctx* ctx, const float* pc, const int32_t* n_points, const int32_t* fps_start, int B, int stride, float* logits,
+                   const ifd_pc_aux* aux, void* stream) {
+    if (!ctx) return IFD_ERR_ARG;
+    if (ctx->model != IFD_MODEL_PC || !ctx->d_victim.get()) return fail(ctx, IFD_ERR_ARG, "ifd_pc_forward: not a PointConv context");
+    if (!pc || !logits || B < 1) return fail(ctx, IFD_ERR_ARG, "ifd_pc_forward: bad argument (pc, logits, B >= 1)");
+    if (stride < IFD_PC_MIN_POINTS) return fail(ctx, IFD_ERR_ARG, "ifd_pc_forward: stride below 32 (a cloud needs at least 32 points)");
+    if (stride > IFD_PC_MAX_POINTS) return fail(ctx, IFD_ERR_ARG, "ifd_pc_forward: stride above 2048");
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const int nc = ctx->cls_classes;
+    return victim_forward(
+        ctx, "ifd_pc_forward", B, PC_CHUNK, 0, [&](int chunk) { return pc_ws_bytes(chunk); },
+        [&](char* base) {
+            if (!n_points && !fps_start) return (int)IFD_OK;
+            int32_t bad[2] = {0, 0};
+            if (int rc = read_bad_counts(ctx, "ifd_pc_forward", "n_points and fps_start",
+                                         launch_pc_check(n_points, fps_start, B, stride, reinterpret_cast<int32_t*>(base), s), base, 2, bad, s))
+                return rc;
+            if (bad[0] != 0)
+                return fail(ctx, IFD_ERR_ARG, ("ifd_pc_forward: " + std::to_string(bad[0]) + " cloud(s) with n_points outside [32, stride]").c_str());
+            if (bad[1] != 0)
+                return fail(ctx, IFD_ERR_ARG,
+                            ("ifd_pc_forward: " + std::to_string(bad[1]) + " cloud(s) with fps_start outside [0, n_points) x [0, 512)").c_str());
+            return (int)IFD_OK;
+        },
+        [&](int c0, int n, Carve& c) {
+            const PcWs w = pc_ws(c, (size_t)n);
+            PcOut o{};
+            if (aux) {
+                o.fps1 = aux->fps1 ? aux->fps1 + (size_t)c0 * PC_NP1 : nullptr;
+                o.fps2 = aux->fps2 ? aux->fps2 + (size_t)c0 * PC_NP2 : nullptr;
+                o.knn1 = aux->knn1 ? aux->knn1 + (size_t)c0 * PC_NP1 * PC_K1 : nullptr;
+                o.knn2 = aux->knn2 ? aux->knn2 + (size_t)c0 * PC_NP2 * PC_K2 : nullptr;
+                o.dens1 = aux->dens1 ? aux->dens1 + (size_t)c0 * stride : nullptr;
+                o.dens2 = aux->dens2 ? aux->dens2 + (size_t)c0 * PC_NP1 : nullptr;
+                o.dens3 = aux->dens3 ? aux->dens3 + (size_t)c0 * PC_NP2 : nullptr;
+                o.l1_feat = aux->l1_feat ? aux->l1_feat + (size_t)c0 * PC_NP1 * 128 : nullptr;
+                o.l2_feat = aux->l2_feat ? aux->l2_feat + (size_t)c0 * PC_NP2 * 256 : nullptr;
+                o.gfeat = aux->global_feat ? aux->global_feat + (size_t)c0 * PC_EMB : nullptr;
+                o.pred = aux->pred ? aux->pred + c0 : nullptr;
+            }
+            return launch_pc(ctx->d_victim.get<float>(), ctx->pcimg, pc + (size_t)c0 * stride * 3, n_points ? n_points + c0 : nullptr,
+                             fps_start ? fps_start + (size_t)c0 * 2 : nullptr, n, stride, w, o, logits + (size_t)c0 * nc, nc, s);
         });
 }
 

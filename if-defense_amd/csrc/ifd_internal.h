@@ -505,4 +505,67 @@ hipError_t launch_pn2_check(const int32_t* n_points, const int32_t* fps_start, i
 hipError_t launch_pn2(const float* img, const Pn2Image& I, const float* pc, const int32_t* n_points, const int32_t* fps_start, int B,
                       int stride, const Pn2Ws& w, const Pn2Out& out, float* logits, int n_classes, hipStream_t s);
 
+// ---- victim classifier: PointConv (pointconv.hip; C ABI in include/ifd_pc.h) ------------------------------------------
+constexpr int PC_MAX_POINTS = 2048, PC_MIN_POINTS = 32;   // IFD_PC_MAX_POINTS, IFD_PC_MIN_POINTS
+constexpr int PC_NP1 = 512, PC_K1 = 32;         // sa1: centroids, nearest neighbours of each
+constexpr int PC_NP2 = 128, PC_K2 = 64;         // sa2; sa3 is one group of the 128
+constexpr int PC_WN = 16;                       // WeightNet's outputs
+constexpr int PC_EMB = 1024;                    // width of the global feature
+constexpr int PC_DN_FLOATS = 97, PC_WN_FLOATS = 248;      // a DensityNet (1 -> 8 -> 8 -> 1) and a WeightNet (3 -> 8 -> 8 -> 16), biases included
+// The Gaussian density's two divisors at level 0, 1, 2 (bandwidth 0.1, 0.2, 0.4): the reference's Python doubles, rounded to
+// float where they meet the float tensors
+__host__ __device__ constexpr float pc_two_bw2(int level) {
+    return level == 0 ? (float)(2.0 * 0.1 * 0.1) : (level == 1 ? (float)(2.0 * 0.2 * 0.2) : (float)(2.0 * 0.4 * 0.4));
+}
+__host__ __device__ constexpr float pc_norm(int level) {
+    return level == 0 ? (float)(2.5 * 0.1) : (level == 1 ? (float)(2.5 * 0.2) : (float)(2.5 * 0.4));
+}
+// One level inside the device image (api.cpp build_pc_image).  dn and wn: the three small layers as they come in the canonical
+// vector ({weight [out][in], bias [out]} x 3).  The MLP's first layer as Pn2Image stores it: sa1's as [64][4] rows {w0, w1, w2,
+// bias} (first_xyz, u unused); sa2's and sa3's as the coordinate columns [out][4] = {w0, w1, w2, 0} and the feature columns u
+// with the bias.  lin: the 16 C -> C linear behind the contraction.
+struct PcLevel {
+    int dn, wn, first_xyz;
+    DenseLayer u, mlp[2], lin;
+};
+struct PcImage {
+    PcLevel sa[3];
+    DenseLayer fc[3];
+    int total;
+};
+struct PcWs {                           // per-chunk scratch of launch_pc (api.cpp pc_ws)
+    float* xyz1;        // [B][512][3]   level-1 centroids
+    float* xyz2;        // [B][128][3]
+    float* xyz3;        // [B][128][3]   xyz2 minus its mean
+    int32_t* fps1;      // [B][512]
+    int32_t* fps2;      // [B][128]
+    int32_t* knn1;      // [B][512][32]
+    int32_t* knn2;      // [B][128][64]
+    float* dens1;       // [B][stride]   DensityNet's output per point of the level's input
+    float* dens2;       // [B][512]
+    float* dens3;       // [B][128]
+    float* g;           // [B][512][2048]  the contraction's output of the level at work: sa1's, then sa2's [128][4096], then sa3's [16384]
+    float* l1_feat;     // [B][512][128]
+    float* u2;          // [B][512][128]  b + W_f f of sa2's first layer
+    float* l2_feat;     // [B][128][256]
+    float* s3a;         // [B][128][256]
+    float* s3b;         // [B][128][512]
+    float* s3c;         // [B][128][1024]
+    float* wn3;         // [B][128][16]   WeightNet of sa3's members
+    float* gfeat;       // [B][1024]
+    float* f1;          // [B][512]
+    float* f2;          // [B][256]
+};
+struct PcOut {                          // where the caller wants the intermediate results; a null member stays in the scratch
+    int32_t *fps1, *fps2, *knn1, *knn2;
+    float *dens1, *dens2, *dens3;
+    float *l1_feat, *l2_feat, *gfeat;
+    int32_t* pred;
+};
+hipError_t configure_pc_kernels();
+// bad[0] = clouds with n_points outside [32, stride]; bad[1] = clouds (of the others) with a start outside [0, n_points) / [0, 512)
+hipError_t launch_pc_check(const int32_t* n_points, const int32_t* fps_start, int B, int stride, int32_t* bad, hipStream_t s);
+hipError_t launch_pc(const float* img, const PcImage& I, const float* pc, const int32_t* n_points, const int32_t* fps_start, int B,
+                     int stride, const PcWs& w, const PcOut& out, float* logits, int n_classes, hipStream_t s);
+
 }  // namespace ifd

@@ -349,6 +349,29 @@ struct Pn2Sa2Lds {                                   // pn2_sa2_kernel
 };
 static_assert(Pn2Sa1Lds::BYTES == 34816 && Pn2Sa2Lds::BYTES == 69632 && Pn2Sa2Lds::BYTES <= LDS_MAX_BYTES, "LDS of the grouped MLPs");
 
+// ---- pointconv.hip ------------------------------------------------------------------------------------------------------------
+struct PcDensityLds {                                // pc_density_kernel: the level's whole input cloud
+    static constexpr size_t X = 0;                                         // float [PC_MAX_POINTS][3]
+    static constexpr size_t BYTES = X + (size_t)PC_MAX_POINTS * 12;
+};
+template <int LD_>
+struct PcSaLds {                                     // pc_sa1_kernel (LD 68), pc_sa2_kernel (LD 132): a 64-row tile between its layers
+    static constexpr int LD = LD_;                                         // floats of a row (16-byte pieces, bank pad)
+    static constexpr size_t A = 0;                                         // float [64][LD] the first layer's output; later 64 scaled channels of the last
+    static constexpr size_t B = A + (size_t)64 * LD * 4;                   // float [64][LD] the second's
+    static constexpr size_t WN = B + (size_t)64 * LD * 4;                  // float [64][PC_WN] WeightNet of the rows
+    static constexpr size_t S = WN + (size_t)64 * PC_WN * 4;               // float [64] the rows' density scales
+    static constexpr size_t BYTES = S + 64 * 4;
+};
+struct PcCentreLds {                                 // pc_centre_kernel
+    static constexpr size_t MEAN = 0;                                      // float [3] the mean of the 128 centroids (padded to 16 bytes)
+    static constexpr size_t BYTES = MEAN + 16;
+};
+using PcSa1Lds = PcSaLds<64 + 4>;
+using PcSa2Lds = PcSaLds<128 + 4>;
+static_assert(PcDensityLds::BYTES == 24576 && PcSa1Lds::BYTES == 39168 && PcSa2Lds::BYTES == 71936 && PcSa2Lds::BYTES <= LDS_MAX_BYTES,
+              "LDS of the PointConv kernels");
+
 // ---- block_sum / block_max / block_sum_d write one value per wave into their scratch ------------------------------------------
 static_assert((RepLds::BYTES - RepLds::SCRATCH) / 4 >= OPT_THREADS / 64 && (NrmLds::BYTES - NrmLds::SCRATCH) / 4 >= OPT_THREADS / 64,
               "8 waves: repulsion_kernel, normalize_kernel");

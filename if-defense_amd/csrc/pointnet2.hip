@@ -3,12 +3,7 @@
 // a set-abstraction level gathers a tile of 64 grouped rows into LDS, runs its layers on the tile and writes only the maximum
 // of every group.
 //
-//   pn2_fps_kernel<PPT>   farthest point sampling, a workgroup of 256 threads a cloud.  Thread t keeps the points t + 256 k
-//                         (k < PPT) and their running distances in registers; a pick is a scan of its own PPT points, a
-//                         butterfly of (distance, index) pairs over the wave, ONE exchange of the four waves' pairs through LDS
-//                         and ONE barrier (the slots are double-buffered by the pick's parity).  The picked point's coordinates
-//                         come from the cloud's copy in LDS and are written as the picks are made, so that the ball query and
-//                         the grouping read centroids, not indices.
+//   pn2_fps_kernel<PPT>   farthest point sampling (victim_fps.h, shared with the PointConv victim), with the distance both use.
 //   pn2_ball_kernel       a wave a centroid: the cloud is walked in index order 64 candidates at a time; a ballot and the count
 //                         of the member lanes below a lane keep the order; the walk stops at nsample members.
 //   pn2_sa1_kernel        64 rows = two 32-sample groups: 3 -> 64 by plain FMAs into LDS, 64 -> 64 and 64 -> 128 on MFMA, the
@@ -25,21 +20,12 @@
 #include "ifd_device.h"
 #include "ifd_internal.h"
 #include "lds_layout.h"
+#include "victim_fps.h"
 #include "victim_linear.h"
 
 namespace ifd {
 
 namespace {
-
-// d = (dx dx + dy dy) + dz dz, every product and sum rounded on its own (include/ifd_pn2.h).  hipcc contracts by default, and
-// __fmul_rn / __fadd_rn are plain operators to it, so the contraction is switched off for exactly this function.
-__device__ __forceinline__ float pn2_dist(float x, float y, float z, float cx, float cy, float cz) {
-#pragma clang fp contract(off)
-    const float dx = x - cx, dy = y - cy, dz = z - cz;
-    const float xx = dx * dx, yy = dy * dy, zz = dz * dz;
-    const float xy = xx + yy;
-    return xy + zz;
-}
 
 __global__ __launch_bounds__(256) void pn2_check_kernel(const int32_t* __restrict__ n_points, const int32_t* __restrict__ fps_start, int B,
                                                         int stride, int32_t* __restrict__ bad) {
@@ -53,68 +39,6 @@ __global__ __launch_bounds__(256) void pn2_check_kernel(const int32_t* __restric
     if (fps_start) {
         const int s1 = fps_start[2 * b], s2 = fps_start[2 * b + 1];
         if (s1 < 0 || s1 >= n || s2 < 0 || s2 >= PN2_NP1) atomicAdd(bad + 1, 1);
-    }
-}
-
-// X: rows of 3 floats, a cloud's from X + b * xb; its first n_points[b] (n_fixed where null) rows are the cloud, n <= 256 PPT.
-// fps_start [B][2] (null: 0), column `level`.  idx [B][npoint], xyz [B][npoint][3].
-template <int PPT>
-__global__ __launch_bounds__(PN2_FPS_THREADS) void pn2_fps_kernel(const float* __restrict__ X, size_t xb, const int32_t* __restrict__ n_points,
-                                                                  int n_fixed, const int32_t* __restrict__ fps_start, int level, int npoint,
-                                                                  int32_t* __restrict__ idx, float* __restrict__ xyz) {
-    using L = Pn2FpsLds<PPT>;
-    __shared__ __attribute__((aligned(16))) unsigned char smem[L::BYTES];
-    float* sx = LDS_AT(float, smem, L::X);
-    float* sv = LDS_AT(float, smem, L::SLOT_V);
-    int* si = LDS_AT(int, smem, L::SLOT_I);
-    const int b = blockIdx.x, t = threadIdx.x, wv = t >> 6;
-    const int n = cloud_points(n_points, b, n_fixed);
-    const float* Xb = X + (size_t)b * xb;
-    float x[PPT], y[PPT], z[PPT], d[PPT];
-#pragma unroll
-    for (int k = 0; k < PPT; ++k) {
-        const int j = t + PN2_FPS_THREADS * k;
-        x[k] = y[k] = z[k] = 0.f;
-        d[k] = -1.f;                                                   // rows beyond the cloud: below every distance, never picked
-        if (j < n) {
-            x[k] = Xb[3 * j]; y[k] = Xb[3 * j + 1]; z[k] = Xb[3 * j + 2];
-            d[k] = 1e10f;
-            sx[3 * j] = x[k]; sx[3 * j + 1] = y[k]; sx[3 * j + 2] = z[k];
-        }
-    }
-    __syncthreads();
-    int far = fps_start ? fps_start[2 * b + level] : 0;
-    far = min(max(far, 0), n - 1);                                     // starts outside are refused by the host
-    int32_t* I = idx + (size_t)b * npoint;
-    float* O = xyz + (size_t)b * npoint * 3;
-    for (int i = 0; i < npoint; ++i) {
-        const float cx = sx[3 * far], cy = sx[3 * far + 1], cz = sx[3 * far + 2];
-        if (t == 0) { I[i] = far; O[3 * i] = cx; O[3 * i + 1] = cy; O[3 * i + 2] = cz; }
-        float best = -2.f;
-        int bi = 0;
-#pragma unroll
-        for (int k = 0; k < PPT; ++k) {
-            const float dist = pn2_dist(x[k], y[k], z[k], cx, cy, cz);
-            if (dist < d[k]) d[k] = dist;
-            if (d[k] > best) { best = d[k]; bi = t + PN2_FPS_THREADS * k; }      // strictly: the lowest index of a thread's equals
-        }
-#pragma unroll
-        for (int off = 32; off >= 1; off >>= 1) {
-            const float ob = __shfl_xor(best, off);
-            const int oi = __shfl_xor(bi, off);
-            if (ob > best || (ob == best && oi < bi)) { best = ob; bi = oi; }
-        }
-        const int par = (i & 1) * 4;
-        if ((t & 63) == 0) { sv[par + wv] = best; si[par + wv] = bi; }
-        __syncthreads();
-        best = sv[par]; bi = si[par];
-#pragma unroll
-        for (int w = 1; w < PN2_FPS_THREADS / 64; ++w) {
-            const float ob = sv[par + w];
-            const int oi = si[par + w];
-            if (ob > best || (ob == best && oi < bi)) { best = ob; bi = oi; }
-        }
-        far = bi;
     }
 }
 
@@ -142,44 +66,6 @@ __global__ __launch_bounds__(256) void pn2_ball_kernel(const float* __restrict__
         count += __builtin_popcountll(m);
     }
     for (int e = count + l; e < nsample; e += 64) o[e] = first;
-}
-
-// One layer on a 64-row tile in LDS: v[t][m] = bias + sum_c W[o][c] Xs[row][c], row = 32 (wv & 1) + 16 t + p, o = obase + 16 m +
-// 4 q + r, then ReLU.  linear_kernel's CUT64 arithmetic (victim_linear.h): the blocks of 64 inputs are added to the bias in ascending
-// order.  W row-major [..][K] in global memory.
-template <int K, int LDX>
-__device__ __forceinline__ void tile_layer(const float* __restrict__ Xs, const float* __restrict__ W, const float* __restrict__ bias,
-                                           int obase, int wv, int q, int p, f32x4 (&v)[2][2]) {
-    const float* xr[2];
-    const float* wr[2];
-#pragma unroll
-    for (int t = 0; t < 2; ++t) {
-        xr[t] = Xs + (32 * (wv & 1) + 16 * t + p) * LDX + 4 * q;
-        wr[t] = W + (size_t)(obase + 16 * t + p) * K + 4 * q;
-    }
-    f32x4 sum[2][2];
-#pragma unroll
-    for (int m = 0; m < 2; ++m) {
-        const f32x4 bv = *reinterpret_cast<const f32x4*>(bias + obase + 16 * m + 4 * q);
-#pragma unroll
-        for (int t = 0; t < 2; ++t) sum[t][m] = bv;
-    }
-#pragma unroll
-    for (int g = 0; g < K; g += 64) linear_block64(xr, wr, g, sum);
-#pragma unroll
-    for (int t = 0; t < 2; ++t)
-#pragma unroll
-        for (int m = 0; m < 2; ++m) v[t][m] = relu4(sum[t][m]);
-}
-
-// the tile's next layer input: Ys[row][o]
-template <int LDY>
-__device__ __forceinline__ void tile_store(float* __restrict__ Ys, int obase, int wv, int q, int p, const f32x4 (&v)[2][2]) {
-#pragma unroll
-    for (int t = 0; t < 2; ++t)
-#pragma unroll
-        for (int m = 0; m < 2; ++m)
-            *reinterpret_cast<f32x4*>(Ys + (32 * (wv & 1) + 16 * t + p) * LDY + obase + 16 * m + 4 * q) = v[t][m];
 }
 
 // the maximum over the wave's 32 rows: v[0][m] of every lane = max over t and p
@@ -332,22 +218,13 @@ hipError_t launch_pn2(const float* img, const Pn2Image& I, const float* pc, cons
     float* gfeat = out.gfeat ? out.gfeat : w.gfeat;
     const dim3 block(256);
     // level 1: 512 centroids of the cloud, their balls, the grouped MLP
-    if (stride <= 512)
-        hipLaunchKernelGGL((pn2_fps_kernel<2>), dim3(B), dim3(PN2_FPS_THREADS), 0, s, pc, (size_t)stride * 3, n_points, stride, fps_start, 0,
-                           PN2_NP1, fps1, w.xyz1);
-    else if (stride <= 1024)
-        hipLaunchKernelGGL((pn2_fps_kernel<4>), dim3(B), dim3(PN2_FPS_THREADS), 0, s, pc, (size_t)stride * 3, n_points, stride, fps_start, 0,
-                           PN2_NP1, fps1, w.xyz1);
-    else
-        hipLaunchKernelGGL((pn2_fps_kernel<8>), dim3(B), dim3(PN2_FPS_THREADS), 0, s, pc, (size_t)stride * 3, n_points, stride, fps_start, 0,
-                           PN2_NP1, fps1, w.xyz1);
+    launch_fps(pc, stride, n_points, fps_start, 0, PN2_NP1, B, fps1, w.xyz1, s);
     hipLaunchKernelGGL(pn2_ball_kernel, dim3(PN2_NP1 / 4, B), block, 0, s, pc, (size_t)stride * 3, n_points, stride, (const float*)w.xyz1,
                        PN2_NP1, PN2_NS1, pn2_radius2(0), ball1);
     hipLaunchKernelGGL(pn2_sa1_kernel, dim3(PN2_NP1 / 2, B), block, 0, s, img + I.sa1_first, img + I.sa1[0].w, img + I.sa1[0].b,
                        img + I.sa1[1].w, img + I.sa1[1].b, pc, n_points, stride, (const int32_t*)ball1, (const float*)w.xyz1, l1);
     // level 2: 128 centroids of the 512, their balls, U = b + W_f f per level-1 point, the grouped MLP
-    hipLaunchKernelGGL((pn2_fps_kernel<2>), dim3(B), dim3(PN2_FPS_THREADS), 0, s, (const float*)w.xyz1, (size_t)PN2_NP1 * 3,
-                       (const int32_t*)nullptr, PN2_NP1, fps_start, 1, PN2_NP2, fps2, w.xyz2);
+    launch_fps(w.xyz1, PN2_NP1, nullptr, fps_start, 1, PN2_NP2, B, fps2, w.xyz2, s);
     hipLaunchKernelGGL(pn2_ball_kernel, dim3(PN2_NP2 / 4, B), block, 0, s, (const float*)w.xyz1, (size_t)PN2_NP1 * 3, (const int32_t*)nullptr,
                        PN2_NP1, (const float*)w.xyz2, PN2_NP2, PN2_NS2, pn2_radius2(1), ball2);
     launch_linear<Pn2Linear>(img, I.sa2_u, l1, 128, (size_t)PN2_NP1 * 128, nullptr, B, PN2_NP1, w.u2, 128, (size_t)PN2_NP1 * 128, 0, s);

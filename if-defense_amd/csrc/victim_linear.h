@@ -52,6 +52,44 @@ __device__ __forceinline__ void linear_block64(const float* (&xr)[2], const floa
         for (int m = 0; m < 2; ++m) sum[t][m] += (acc[t][m][0] + acc[t][m][1]) + (acc[t][m][2] + acc[t][m][3]);
 }
 
+// One layer of a grouped MLP (pointnet2.hip, pointconv.hip) on a 64-row tile in LDS: v[t][m] = bias + sum_c W[o][c] Xs[row][c], row = 32 (wv & 1) + 16 t + p, o = obase + 16 m +
+// 4 q + r, then ReLU.  linear_kernel's CUT64 arithmetic (victim_linear.h): the blocks of 64 inputs are added to the bias in ascending
+// order.  W row-major [..][K] in global memory.
+template <int K, int LDX>
+__device__ __forceinline__ void tile_layer(const float* __restrict__ Xs, const float* __restrict__ W, const float* __restrict__ bias,
+                                           int obase, int wv, int q, int p, f32x4 (&v)[2][2]) {
+    const float* xr[2];
+    const float* wr[2];
+#pragma unroll
+    for (int t = 0; t < 2; ++t) {
+        xr[t] = Xs + (32 * (wv & 1) + 16 * t + p) * LDX + 4 * q;
+        wr[t] = W + (size_t)(obase + 16 * t + p) * K + 4 * q;
+    }
+    f32x4 sum[2][2];
+#pragma unroll
+    for (int m = 0; m < 2; ++m) {
+        const f32x4 bv = *reinterpret_cast<const f32x4*>(bias + obase + 16 * m + 4 * q);
+#pragma unroll
+        for (int t = 0; t < 2; ++t) sum[t][m] = bv;
+    }
+#pragma unroll
+    for (int g = 0; g < K; g += 64) linear_block64(xr, wr, g, sum);
+#pragma unroll
+    for (int t = 0; t < 2; ++t)
+#pragma unroll
+        for (int m = 0; m < 2; ++m) v[t][m] = relu4(sum[t][m]);
+}
+
+// the tile's next layer input: Ys[row][o]
+template <int LDY>
+__device__ __forceinline__ void tile_store(float* __restrict__ Ys, int obase, int wv, int q, int p, const f32x4 (&v)[2][2]) {
+#pragma unroll
+    for (int t = 0; t < 2; ++t)
+#pragma unroll
+        for (int m = 0; m < 2; ++m)
+            *reinterpret_cast<f32x4*>(Ys + (32 * (wv & 1) + 16 * t + p) * LDY + obase + 16 * m + 4 * q) = v[t][m];
+}
+
 // Y[row][o] = act(bias[o] + sum_c W[o][c] X[row][c] (+ wx[o] . xyz[row])), o < M (a multiple of 4), K a multiple of 64.  Rows: the
 // first cloud_points(n_points, b, stride) of cloud b = blockIdx.z; X rows of ldx floats from X + b * xb, Y rows of ldy floats from
 // Y + b * yb, xyz rows of 3 floats from xyz + b * stride * 3; wx [M][4] = {w0, w1, w2, -}.

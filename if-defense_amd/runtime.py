@@ -1516,3 +1516,48 @@ class PointNet2Classifier(Classifier):
         """argmax of the logits, [B] int64 (the lowest class among equal logits)."""
         _, aux = self.logits(pc, n_points, fps_start=fps_start, want_pred=True)
         return aux["pred"].long()
+
+
+class PointConvClassifier(Classifier):
+    """The PointConv victim of the reference on one GPU (include/ifd_pc.h): PointConvDensityClsSsg(num_classes=40) in eval mode.
+    ``weights``: the BN-folded canonical vector (``weights.load_checkpoint(path, "pointconv")`` or
+    ``weights.pack_state_dict(state_dict, "pointconv")``).  Inputs are Classifier's: [B,N,3] batches (point-major), lists and
+    object arrays of ragged clouds of 32 to 2048 points.  ``fps_start`` [B,2] int: the first pick of the level-1 sampling (below
+    the cloud's count) and of the level-2 sampling (below 512); None means 0, 0 - the reference draws them at random, here
+    they are an input.  A cloud's outputs do not depend on how it is batched or padded.  The attack entry points of Classifier
+    are PointNet's and are not offered here."""
+
+    MAX_POINTS = _lib.PC_MAX_POINTS
+    MIN_POINTS = _lib.PC_MIN_POINTS
+    CHUNK = _lib.PC_CHUNK
+
+    def __init__(self, weights: np.ndarray, device=None):
+        self.lib = _lib.load()
+        self.feature_transform = False
+        self._create("ifd_pc_create", self.lib.ifd_pc_weight_count(), "pointconv weights", weights, device)
+
+    def logits(self, pc, n_points=None, fps_start=None, want_aux: bool = False, want_pred: bool = False):
+        """pc, n_points: as Classifier.logits.  Returns logits [B,40]; with want_aux also {"fps1" [B,512], "fps2" [B,128],
+        "knn1" [B,512,32], "knn2" [B,128,64] (int32), "dens1" [B,N] (zero beyond a cloud's count), "dens2" [B,512], "dens3"
+        [B,128] (DensityNet's outputs), "l1_feat" [B,512,128], "l2_feat" [B,128,256], "global_feat" [B,1024], "pred" [B] int32}."""
+        def starts(B):
+            if fps_start is None:
+                return (None,)
+            t = torch.as_tensor(fps_start).to(device=self.device, dtype=torch.int32).contiguous()
+            if tuple(t.shape) != (B, 2):
+                raise IfdError("fps_start must be [B,2], got %s" % (tuple(t.shape),))
+            return (t,)
+
+        def aux_table(B, stride):
+            n1, k1, n2, k2 = _lib.PC_NPOINT1, _lib.PC_K1, _lib.PC_NPOINT2, _lib.PC_K2
+            i32, f32 = dict(device=self.device, dtype=torch.int32), dict(device=self.device, dtype=torch.float32)
+            return dict(fps1=torch.empty(B, n1, **i32), fps2=torch.empty(B, n2, **i32), knn1=torch.empty(B, n1, k1, **i32),
+                        knn2=torch.empty(B, n2, k2, **i32), dens1=torch.zeros(B, stride, **f32), dens2=torch.empty(B, n1, **f32),
+                        dens3=torch.empty(B, n2, **f32), l1_feat=torch.empty(B, n1, 128, **f32),
+                        l2_feat=torch.empty(B, n2, 256, **f32), global_feat=torch.empty(B, 1024, **f32))
+        return self._forward("ifd_pc_forward", pc, n_points, _lib.IfdPcAux, aux_table, want_aux, want_pred, extra=starts)
+
+    def predict(self, pc, n_points=None, fps_start=None) -> torch.Tensor:
+        """argmax of the logits, [B] int64 (the lowest class among equal logits)."""
+        _, aux = self.logits(pc, n_points, fps_start=fps_start, want_pred=True)
+        return aux["pred"].long()

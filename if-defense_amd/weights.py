@@ -176,6 +176,8 @@ def _keys(model: str):
         return dgcnn_canonical_keys()
     if model == "pointnet2":
         return pointnet2_canonical_keys()
+    if model == "pointconv":
+        return pointconv_canonical_keys()
     if model == "onet":
         return onet_canonical_keys()
     if model == "punet":
@@ -193,6 +195,8 @@ def pack_state_dict(state: Dict[str, object], model: str = "convonet", feature_t
         return pack_dgcnn(state)
     if model == "pointnet2":
         return pack_pointnet2(state)
+    if model == "pointconv":
+        return pack_pointconv(state)
     parts = []
     for name, shape in _keys(model):
         if name not in state:
@@ -229,6 +233,13 @@ def load_checkpoint(path: str, model: str = "convonet", feature_transform=None) 
                 return pack_pointnet2({n: z[n] for n in z.files})
         import torch
         return pack_pointnet2(torch.load(path, map_location="cpu", weights_only=True))
+    if model == "pointconv":
+        # pretrain/<dataset>/pointconv.pth (saved from nn.DataParallel) or an .npz of its arrays
+        if path.endswith(".npz"):
+            with np.load(path, allow_pickle=False) as z:
+                return pack_pointconv({n: z[n] for n in z.files})
+        import torch
+        return pack_pointconv(torch.load(path, map_location="cpu", weights_only=True))
     if model == "punet":
         # pu-in_1024-up_4.pth (baselines/config.py PU_NET_WEIGHT) or an .npz of the same arrays
         if path.endswith(".npz"):
@@ -513,4 +524,98 @@ def pointnet2_random_state_dict(seed: int = 0) -> Dict[str, np.ndarray]:
             w[bn + ".bias"] = rng.uniform(-0.1, 0.1, co).astype(np.float32)
             w[bn + ".running_mean"] = rng.normal(0.0, 0.1, co).astype(np.float32)
             w[bn + ".running_var"] = rng.uniform(0.5, 1.25, co).astype(np.float32)
+    return w
+
+
+# ---- the PointConv victim (include/ifd_pc.h) -------------------------------------------------------------------------
+def pointconv_layers() -> List[Tuple[str, object, Tuple[int, int], int]]:
+    """The layers of PointConvDensityClsSsg(num_classes=40) (baselines/model/pointconv.py) in the canonical order of
+    include/ifd_pc.h - per level densitynet x 3 (Conv1d), mlp x 3 (Conv2d), weightnet x 3 (Conv2d), linear (Linear); then the
+    head: (layer key, its BatchNorm's key or None, (out, in), trailing singleton dims of the weight).  Every layer has a bias."""
+    k = []
+    for sa, cin, mlp in (("sa1", 3, (64, 64, 128)), ("sa2", 131, (128, 128, 256)), ("sa3", 259, (256, 512, 1024))):
+        for i, d in enumerate([(8, 1), (8, 8), (1, 8)]):
+            k.append(("%s.densitynet.mlp_convs.%d" % (sa, i), "%s.densitynet.mlp_bns.%d" % (sa, i), d, 1))
+        last = cin
+        for i, co in enumerate(mlp):
+            k.append(("%s.mlp_convs.%d" % (sa, i), "%s.mlp_bns.%d" % (sa, i), (co, last), 2))
+            last = co
+        for i, d in enumerate([(8, 3), (8, 8), (16, 8)]):
+            k.append(("%s.weightnet.mlp_convs.%d" % (sa, i), "%s.weightnet.mlp_bns.%d" % (sa, i), d, 2))
+        k.append((sa + ".linear", sa + ".bn_linear", (last, 16 * last), 0))
+    k.append(("fc1", "bn1", (512, 1024), 0))
+    k.append(("fc2", "bn2", (256, 512), 0))
+    k.append(("fc3", None, (40, 256), 0))
+    return k
+
+
+def pointconv_canonical_keys() -> List[Tuple[str, Tuple[int, ...]]]:
+    """(name, shape) of the BN-folded tensors ifd_pc_create expects, in order (include/ifd_pc.h): 19,559,411 floats."""
+    k: List[Tuple[str, Tuple[int, ...]]] = []
+    for lin, _, (co, ci), _ in pointconv_layers():
+        k += [(lin + ".weight", (co, ci)), (lin + ".bias", (co,))]
+    return k
+
+
+def pointconv_weight_count() -> int:
+    return sum(int(np.prod(shape)) for _, shape in pointconv_canonical_keys())
+
+
+def fold_pointconv(state: Dict[str, object]) -> List[Tuple[str, np.ndarray]]:
+    """Fold every eval-mode BatchNorm into its layer in float64 (the formulas of fold_pointnet).  -> [(canonical name, float64
+    array)] in canonical order.  A key that is there both with and without the ``module.`` prefix is a ValueError."""
+    doubled = [k for k in state if not k.startswith("module.") and ("module." + k) in state]
+    if doubled:
+        raise ValueError("checkpoint holds %r with and without the module. prefix" % doubled[0])
+    state = strip_module_prefix(state)
+
+    def get(name, shape):
+        if name not in state:
+            raise KeyError("checkpoint lacks %r" % name)
+        t = state[name]
+        a = t.detach().cpu().numpy() if hasattr(t, "detach") else np.asarray(t)
+        if tuple(a.shape) != tuple(shape):
+            raise ValueError("%s: expected shape %s, got %s" % (name, shape, tuple(a.shape)))
+        return a.astype(np.float64)
+
+    out: List[Tuple[str, np.ndarray]] = []
+    for lin, bn, (co, ci), ones in pointconv_layers():
+        w = get(lin + ".weight", (co, ci) + (1,) * ones).reshape(co, ci)
+        b = get(lin + ".bias", (co,))
+        if bn:
+            g, beta = get(bn + ".weight", (co,)), get(bn + ".bias", (co,))
+            mean, var = get(bn + ".running_mean", (co,)), get(bn + ".running_var", (co,))
+            sc = g / np.sqrt(var + BN_EPS)
+            w, b = w * sc[:, None], (b - mean) * sc + beta
+        out += [(lin + ".weight", w), (lin + ".bias", b)]
+    return out
+
+
+def pack_pointconv(state: Dict[str, object]) -> np.ndarray:
+    """fold_pointconv, rounded to float32 and flattened in canonical order (num_batches_tracked is ignored)."""
+    return np.concatenate([a.astype(np.float32).reshape(-1) for _, a in fold_pointconv(state)])
+
+
+def pointconv_random_state_dict(seed: int = 0) -> Dict[str, np.ndarray]:
+    """Seeded random un-folded PointConv weights for smoke / benchmark runs (pretrain/mn40/pointconv.pth is a download).  Per
+    layer in canonical order: weight and bias U(+-1/sqrt(fan_in)); each BatchNorm after its layer: gamma 1 + U(+-0.2), beta
+    U(+-0.1), running_mean N(0, 0.1), running_var U(0.5, 1.25).  A DensityNet ends in a ReLU and a net of fan-in 1 and 8 drawn
+    this way is dead as often as not, so the DensityNets' tensors are then made positive: weights and biases by their absolute
+    values, running_mean by minus its absolute value - every density scale s_j is positive.  The recipe (and so the numbers) is
+    that of tests/pointconv_oracle.py make_weights."""
+    rng = np.random.default_rng(seed + 9301)
+    w: Dict[str, np.ndarray] = {}
+    for lin, bn, (co, ci), ones in pointconv_layers():
+        b = 1.0 / np.sqrt(ci)
+        w[lin + ".weight"] = rng.uniform(-b, b, size=(co, ci) + (1,) * ones).astype(np.float32)
+        w[lin + ".bias"] = rng.uniform(-b, b, size=(co,)).astype(np.float32)
+        if bn:
+            w[bn + ".weight"] = (1.0 + rng.uniform(-0.2, 0.2, co)).astype(np.float32)
+            w[bn + ".bias"] = rng.uniform(-0.1, 0.1, co).astype(np.float32)
+            w[bn + ".running_mean"] = rng.normal(0.0, 0.1, co).astype(np.float32)
+            w[bn + ".running_var"] = rng.uniform(0.5, 1.25, co).astype(np.float32)
+        if ".densitynet." in lin:
+            for key in (lin + ".weight", lin + ".bias", bn + ".bias"):
+                w[key] = np.abs(w[key])
+            w[bn + ".running_mean"] = -np.abs(w[bn + ".running_mean"])
     return w

@@ -5,7 +5,8 @@
  * except where noted), and the contexts made here are destroyed with ifd_destroy and report through ifd_last_error.
  *
  * Built: PointNetCls(k=40, feature_transform=False|True, use_bn=True) in eval() (baselines/model/pointnet.py).  The other
- * victims of the reference (PointNet++, DGCNN, PointConv) have model ids reserved below and are refused.
+ * victims of the reference (PointNet++, DGCNN, PointConv) have model ids reserved below and are refused here: each has an ABI
+ * of its own (ifd_pn2.h, ifd_dgcnn.h, ifd_pc.h).
  */
 #ifndef IFD_CLS_H
 #define IFD_CLS_H

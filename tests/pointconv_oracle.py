@@ -1,0 +1,196 @@
+"""PointConvDensityClsSsg(num_classes=40) in eval mode restated, the test oracle of the PointConv victim (include/ifd_pc.h).
+
+The two selection steps are numpy float32, exactly as the header defines them: ``dist`` and ``fps`` are pointnet2_oracle's
+(imported), ``knn`` takes the K points of smallest distance, the lower index first among equal distances, in ascending (d, index)
+order.  The arithmetic follows baselines/model/pointconv.py in torch (density -> DensityNet with ReLU after all three layers;
+gather, subtract the centroid, cat; conv -> batch_norm -> relu with the 1 x 1 convolutions as linear layers on the grouped rows;
+WeightNet on the differences; features times the density scale; matmul over the members; the level's linear; the head), and runs
+in float64 as the yardstick of the GPU's arithmetic.  The density is the reference's own formulation, squared distances in the
+matrix form |a|^2 + |b|^2 - 2 <a, b>: the float32 run's error e_32 is then the error of the reference's arithmetic in float32,
+cancellation included, which is what the reference's recorded densities carry (on level-2 inputs with many repeated centroids it
+reaches 9 ulp of s; the header's difference form, exact on copies, stays near 1 ulp and is held to 4 e_32 all the same).  A
+float64 run takes its index tables from outside (the float32 run's, or an implementation's): a different neighbour moves the
+logits by far more than the arithmetic does.
+
+Weights: ``make_weights(seed)`` draws the un-folded state_dict from numpy's default_rng(seed + 9301), layers in canonical order
+(ifdefense_amd.weights.pointconv_layers): weight and bias U(+-1/sqrt(fan_in)), then the layer's BatchNorm: gamma 1 + U(+-0.2), beta
+U(+-0.1), running_mean N(0, 0.1), running_var U(0.5, 1.25).  A DensityNet ends in a ReLU and multiplies every feature, and a net of
+fan-in 1 and 8 drawn this way is dead as often as not; so each DensityNet layer's weight, bias and BatchNorm beta are replaced by
+their absolute values and its running_mean by minus its absolute value: every s_j is positive and grows with the density.  A dict
+WITHOUT BatchNorm keys (weights.fold_pointconv's output) runs the same network with the BatchNorms left out.
+
+``make_calibrated_weights(seed)``: make_weights with fc3 alone replaced, by the recipe of pointnet2_oracle: with h [140,256] the
+float64 oracle's post-ReLU fc2 output on bench.synth_clouds(140, seed=31)[:, :128] (starts 0, 0), mu = h.mean(0), s = h.std(0),
+live = s > 1e-6 max(s):
+    fc3.weight <- fc3.weight * where(live, 1/s, 0)[None,:] * sqrt(3 * 256 / live.sum()),  fc3.bias <- -(fc3.weight @ mu),
+rounded to float32, so that the predicted class varies from cloud to cloud.  ``make_tied_weights`` copies fc3's rows 0..19 onto
+20..39: 20 exact ties in every cloud's logits."""
+import functools
+
+import numpy as np
+import torch
+import torch.nn.functional as F
+
+from ifdefense_amd.weights import BN_EPS, pointconv_layers
+from pointnet2_oracle import _clouds, dist, fps, make_tied_weights, reference_state_dict, to_torch  # noqa: F401
+
+NP1, K1, BW1 = 512, 32, 0.1
+NP2, K2, BW2 = 128, 64, 0.2
+BW3 = 0.4
+TABLES = ("fps1", "fps2", "knn1", "knn2")
+F32 = np.float32
+
+
+def make_weights(seed=0):
+    rng = np.random.default_rng(seed + 9301)
+    w = {}
+    for lin, bn, (co, ci), ones in pointconv_layers():
+        b = 1.0 / np.sqrt(ci)
+        w[lin + ".weight"] = rng.uniform(-b, b, size=(co, ci) + (1,) * ones).astype(np.float32)
+        w[lin + ".bias"] = rng.uniform(-b, b, size=(co,)).astype(np.float32)
+        if bn:
+            w[bn + ".weight"] = (1.0 + rng.uniform(-0.2, 0.2, co)).astype(np.float32)
+            w[bn + ".bias"] = rng.uniform(-0.1, 0.1, co).astype(np.float32)
+            w[bn + ".running_mean"] = rng.normal(0.0, 0.1, co).astype(np.float32)
+            w[bn + ".running_var"] = rng.uniform(0.5, 1.25, co).astype(np.float32)
+        if ".densitynet." in lin:
+            for key in (lin + ".weight", lin + ".bias", bn + ".bias"):
+                w[key] = np.abs(w[key])
+            w[bn + ".running_mean"] = -np.abs(w[bn + ".running_mean"])
+    return w
+
+
+CALIBRATION_CLOUDS, CALIBRATION_SEED, CALIBRATION_POINTS = 140, 31, 128
+
+
+@functools.lru_cache(maxsize=None)
+def _calibrated_fc3(seed):
+    import bench
+    w = make_weights(seed)
+    x = bench.synth_clouds(CALIBRATION_CLOUDS, seed=CALIBRATION_SEED)[:, :CALIBRATION_POINTS]
+    h = forward(to_torch(w, torch.float64), x, dtype=torch.float64, tables=tables_of(x))["h2"].numpy()
+    mu, s = h.mean(0), h.std(0)
+    live = s > 1e-6 * s.max()
+    inv = np.where(live, 1.0 / np.where(live, s, 1.0), 0.0)
+    w3 = w["fc3.weight"].astype(np.float64) * inv[None, :] * np.sqrt(3.0 * 256 / live.sum())
+    return w3.astype(np.float32), (-(w3 @ mu)).astype(np.float32), int(live.sum())
+
+
+def make_calibrated_weights(seed=0):
+    """make_weights(seed) with fc3 rescaled so that the predicted class varies from cloud to cloud (module docstring)."""
+    w = make_weights(seed)
+    w3, b3, _ = _calibrated_fc3(int(seed))
+    w["fc3.weight"], w["fc3.bias"] = w3.copy(), b3.copy()
+    return w
+
+
+# ---- selection, numpy float32 (include/ifd_pc.h) --------------------------------------------------------------------------
+def knn(k, x, centroids):
+    """x [n,3], centroids [m,3] -> [m,k] int32: the k points of smallest dist, the lower index first among equal distances, in
+    ascending (d, index) order."""
+    x, c = np.asarray(x, F32), np.asarray(centroids, F32)
+    assert len(x) >= k
+    d = dist(x[None, :, :], c[:, None, :])
+    return np.argsort(d, axis=1, kind="stable")[:, :k].astype(np.int32)
+
+
+def tables_of_cloud(x, start=(0, 0)):
+    """One cloud [n,3] -> {"fps1" [512], "fps2" [128], "knn1" [512,32], "knn2" [128,64]} int32."""
+    x = np.asarray(x, F32)
+    f1 = fps(x, NP1, start[0])
+    c1 = x[f1]
+    f2 = fps(c1, NP2, start[1])
+    return {"fps1": f1, "fps2": f2, "knn1": knn(K1, x, c1), "knn2": knn(K2, c1, c1[f2])}
+
+
+def tables_of(clouds, n_points=None, fps_start=None):
+    """A batch -> the four tables stacked over the clouds."""
+    clouds = _clouds(clouds, n_points)
+    per = [tables_of_cloud(c, (0, 0) if fps_start is None else fps_start[b]) for b, c in enumerate(clouds)]
+    return {k: np.stack([p[k] for p in per]) for k in TABLES}
+
+
+def check_tables(x, t, start=(0, 0), what=""):
+    """The tables ``t`` of one cloud x [n,3] are the header's: every FPS pick is the lowest index of the largest running
+    distance, every kNN row the K nearest in ascending (d, index) order.  Asserts with the first offender."""
+    x = np.asarray(x, F32)
+    want = tables_of_cloud(x, start)
+    for name in TABLES:
+        got = np.asarray(t[name])
+        assert got.shape == want[name].shape, (what, name, got.shape)
+        bad = np.argwhere(got != want[name])
+        assert bad.size == 0, (what, name, "first difference at", tuple(bad[0]), "got", int(got[tuple(bad[0])]), "want",
+                               int(want[name][tuple(bad[0])]), "of %d" % len(bad))
+    return want
+
+
+# ---- the layers, torch -----------------------------------------------------------------------------------------------------
+def _bn(W, x, bn):
+    if bn and (bn + ".running_var") in W:
+        return F.batch_norm(x, W[bn + ".running_mean"], W[bn + ".running_var"], W[bn + ".weight"], W[bn + ".bias"], False, 0.0, BN_EPS)
+    return x
+
+
+def _stack(W, layers, h):
+    """conv -> bn -> relu of every layer on the rows h [rows, C]."""
+    for lin, bn, (co, ci), _ in layers:
+        h = F.relu(_bn(W, F.linear(h, W[lin + ".weight"].reshape(co, ci), W[lin + ".bias"]), bn))
+    return h
+
+
+def density_scale(W, layers, xyz, bw):
+    """xyz [n,3] -> (rho [n], s [n]): compute_density on matrix-form distances, then DensityNet (ReLU after all three)."""
+    sq = (xyz * xyz).sum(-1)
+    d = (sq[:, None] + sq[None, :]) - 2.0 * (xyz @ xyz.t())
+    rho = (torch.exp(-d / (2.0 * bw * bw)) / (2.5 * bw)).mean(-1)
+    return rho, _stack(W, layers, rho[:, None])[:, 0]
+
+
+def _level(W, L, grouped_xyz, feats, scale):
+    """grouped_xyz [S,K,3] (minus the centroid), feats [S,K,D] or None, scale [S,K] -> [S,C]."""
+    S, K, _ = grouped_xyz.shape
+    rows = grouped_xyz if feats is None else torch.cat([grouped_xyz, feats], dim=-1)
+    h = _stack(W, L[3:6], rows.reshape(S * K, -1)).view(S, K, -1)
+    wn = _stack(W, L[6:9], grouped_xyz.reshape(S * K, 3)).view(S, K, 16)
+    h = h * scale[:, :, None]
+    g = torch.matmul(h.permute(0, 2, 1), wn).reshape(S, -1)                    # [S, C, 16] -> c * 16 + w
+    return _stack(W, L[9:10], g)
+
+
+def _forward_cloud(W, x, t, dtype):
+    L = pointconv_layers()
+    x = torch.from_numpy(x).to(dtype)
+    f1, f2 = torch.as_tensor(np.asarray(t["fps1"])).long(), torch.as_tensor(np.asarray(t["fps2"])).long()
+    k1, k2 = torch.as_tensor(np.asarray(t["knn1"])).long(), torch.as_tensor(np.asarray(t["knn2"])).long()
+    _, s1 = density_scale(W, L[0:3], x, BW1)
+    c1 = x[f1]
+    p1 = _level(W, L[0:10], x[k1] - c1[:, None, :], None, s1[k1])              # [512, 128]
+    _, s2 = density_scale(W, L[10:13], c1, BW2)
+    c2 = c1[f2]
+    l2 = _level(W, L[10:20], c1[k2] - c2[:, None, :], p1[k2], s2[k2])          # [128, 256]
+    _, s3 = density_scale(W, L[20:23], c2, BW3)
+    centred = c2 - c2.mean(dim=0, keepdim=True)
+    g = _level(W, L[20:30], centred[None], l2[None], s3[None])[0]              # [1024]
+    h1 = F.relu(_bn(W, F.linear(g[None], W["fc1.weight"], W["fc1.bias"]), "bn1"))
+    h2 = F.relu(_bn(W, F.linear(h1, W["fc2.weight"], W["fc2.bias"]), "bn2"))
+    lo = F.linear(h2, W["fc3.weight"], W["fc3.bias"])
+    return {"logits": lo[0], "dens1": s1, "dens2": s2, "dens3": s3, "l1_feat": p1, "l2_feat": l2, "global_feat": g, "h2": h2[0]}
+
+
+def forward(W, x, n_points=None, fps_start=None, dtype=torch.float32, tables=None):
+    """x: [B,N,3] (point-major) or a list of [K_i,3]; n_points: [B] valid rows of each cloud; fps_start [B,2] (None: zeros).
+    tables: None (the oracle's own float32 selection) or {"fps1" [B,512], "fps2" [B,128], "knn1" [B,512,32], "knn2" [B,128,64]}
+    forced into the run.  -> {"logits" [B,40], "dens1" [B,max n] (zero beyond a cloud's count), "dens2" [B,512], "dens3" [B,128],
+    "l1_feat" [B,512,128], "l2_feat" [B,128,256], "global_feat" [B,1024], "h2" [B,256]} in ``dtype`` (W must be in it) and
+    "tables", the tables used."""
+    clouds = _clouds(x, n_points)
+    if tables is None:
+        tables = tables_of(clouds, None, fps_start)
+    with torch.no_grad():
+        outs = [_forward_cloud(W, c, {k: np.asarray(v)[b] for k, v in tables.items()}, dtype) for b, c in enumerate(clouds)]
+    res = {k: torch.stack([o[k] for o in outs]) for k in outs[0] if k != "dens1"}
+    res["dens1"] = torch.zeros(len(clouds), max(len(c) for c in clouds), dtype=dtype)
+    for b, o in enumerate(outs):
+        res["dens1"][b, :len(clouds[b])] = o["dens1"]
+    res["tables"] = tables
+    return res

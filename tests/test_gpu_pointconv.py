@@ -1,0 +1,347 @@
+"""GPU tests of the PointConv victim (include/ifd_pc.h) against tests/pointconv_oracle.py.
+
+The two selection steps (farthest point sampling, K nearest neighbours) are held to the header's definitions bit for bit: the numpy
+float32 oracle's tables must equal the GPU's.  The arithmetic is judged with the GPU's tables forced into the float32 and the
+float64 oracle, every bar relative to e_32 = max |float32 oracle - float64 oracle| of the tensor in question, computed here.
+
+Measured on an MI355X (worst e_gpu / e_32 over test_arithmetic_against_f64's cases): DESIGN 7p."""
+import os
+
+import numpy as np
+import pytest
+import torch
+
+pytestmark = pytest.mark.gpu
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+IFD_ERR_ARG = -1
+CHUNK = 32                                                # clouds per chunk of ifd_pc_forward (include/ifd_pc.h IFD_PC_CHUNK)
+TABLES = ("fps1", "fps2", "knn1", "knn2")
+TENSORS = ("dens1", "dens2", "dens3", "l1_feat", "l2_feat", "global_feat")
+SIZES = (32, 33, 63, 64, 65, 100, 511, 512, 513, 1024, 2048)
+
+
+def make_net(sd):
+    import ifdefense_amd as I
+    return I.PointConvClassifier(I.weights.pack_state_dict(sd, "pointconv"), device="cuda:0")
+
+
+@pytest.fixture(scope="module")
+def sd():
+    import pointconv_oracle as PO
+    return PO.make_weights(0)
+
+
+@pytest.fixture(scope="module")
+def net(sd):
+    with make_net(sd) as c:
+        assert c.CHUNK == CHUNK
+        yield c
+
+
+@pytest.fixture(scope="module")
+def pool():
+    """Source clouds: 24 x 1024 points, and two of 2048 (two shapes side by side)."""
+    import bench
+    s = bench.synth_clouds(24, seed=77)
+    big = [np.concatenate([s[20], 0.8 * s[21] + 0.1]), np.concatenate([s[22], 0.7 * s[23] - 0.2])]
+    return s, [np.ascontiguousarray(b, dtype=np.float32) for b in big]
+
+
+def cloud(pool, i, n):
+    s, big = pool
+    return np.ascontiguousarray(s[i % 24][:n] if n <= 1024 else big[i % 2][:n], dtype=np.float32)
+
+
+def to_cpu(lo, aux):
+    torch.cuda.synchronize()
+    return lo.cpu(), {k: v.cpu() for k, v in aux.items()}
+
+
+def run(net, clouds, fps_start=None, n_points=None):
+    """-> logits [B,40], aux (everything on the CPU), for a list of clouds or a [B,N,3] array."""
+    return to_cpu(*net.logits(clouds, n_points=n_points, fps_start=fps_start, want_aux=True))
+
+
+def assert_tables(clouds, starts, aux, what):
+    """The GPU's four tables of every cloud equal the numpy oracle's."""
+    import pointconv_oracle as PO
+    for b, c in enumerate(clouds):
+        PO.check_tables(c, {k: aux[k][b].numpy() for k in TABLES}, (0, 0) if starts is None else starts[b], "%s, cloud %d (n = %d)" % (what, b, len(c)))
+
+
+# ---- 1. selection, bit for bit ------------------------------------------------------------------------------------------------
+@pytest.fixture(scope="module")
+def sized(net, pool):
+    """One cloud of every size of SIZES, each alone in its call (stride = its size), with starts in the middle: shared by the
+    selection and the arithmetic test."""
+    rng = np.random.default_rng(3)
+    out = []
+    for i, n in enumerate(SIZES):
+        c = cloud(pool, i, n)
+        st = np.array([[rng.integers(0, n), rng.integers(0, 512)]], np.int32)
+        lo, aux = run(net, c[None], fps_start=st)
+        out.append((c, st, lo, aux))
+    return out
+
+
+def test_selection_equals_the_oracle_at_every_size(sized):
+    for c, st, lo, aux in sized:
+        assert_tables([c], st, aux, "alone")
+        assert aux["fps1"][0, 0] == st[0, 0] and aux["fps2"][0, 0] == st[0, 1]
+        if len(c) == 32:                                                       # every row is all 32 points
+            assert np.array_equal(np.sort(aux["knn1"][0].numpy(), axis=1), np.tile(np.arange(32), (512, 1)))
+
+
+@pytest.mark.parametrize("n", [100, 513, 2048])
+def test_selection_under_several_starts(net, pool, n):
+    c = cloud(pool, 5, n)
+    starts = np.array([[0, 0], [n - 1, 511], [n // 2, 255], [n - 1, 0]], np.int32)
+    lo, aux = run(net, np.stack([c] * 4), fps_start=starts)
+    assert_tables([c] * 4, starts, aux, "starts")
+    assert not torch.equal(aux["fps1"][0], aux["fps1"][1])
+
+
+def test_selection_in_a_ragged_batch_with_nan_rows(net, pool):
+    sizes = (32, 33, 100, 513, 700, 64)
+    clouds = [cloud(pool, 7 + i, n) for i, n in enumerate(sizes)]
+    pad = np.full((len(sizes), 777, 3), np.nan, np.float32)
+    for b, c in enumerate(clouds):
+        pad[b, :len(c)] = c
+    starts = np.array([[0, 5], [32, 511], [99, 0], [512, 17], [3, 300], [63, 63]], np.int32)
+    lo, aux = run(net, pad, fps_start=starts, n_points=np.array(sizes, np.int32))
+    assert_tables(clouds, starts, aux, "ragged, NaN beyond the counts")
+    assert bool(torch.isfinite(lo).all())
+    lo_l, aux_l = run(net, clouds, fps_start=starts)                           # the same clouds as a list, zero padding
+    assert torch.equal(lo, lo_l)
+    for k in aux:
+        if k == "dens1":                                                       # [B, stride]: 777 columns there, 700 here
+            assert torch.equal(aux[k][:, :700], aux_l[k]) and not aux[k][:, 700:].any()
+        else:
+            assert torch.equal(aux[k], aux_l[k]), k
+
+
+# ---- 2. ties ------------------------------------------------------------------------------------------------------------------
+def lattice_fps(q, npoint, start):
+    """FPS on integer coordinates in exact integer arithmetic: the lowest index of the largest running distance."""
+    q = np.asarray(q, np.int64)
+    running = np.full(len(q), np.iinfo(np.int64).max)
+    out, far = [], start
+    for _ in range(npoint):
+        out.append(far)
+        running = np.minimum(running, ((q - q[far]) ** 2).sum(1))
+        far = int(np.flatnonzero(running == running.max())[0])
+    return np.array(out)
+
+
+def lattice_knn(q, centres, k):
+    """kNN on integer coordinates in exact integer arithmetic: ascending (d, index)."""
+    q, c = np.asarray(q, np.int64), np.asarray(centres, np.int64)
+    d = ((q[None, :, :] - c[:, None, :]) ** 2).sum(-1)
+    return np.argsort(d, axis=1, kind="stable")[:, :k]
+
+
+def test_ties_go_to_the_lowest_index(net):
+    rng = np.random.default_rng(5)
+    q = rng.integers(0, 6, size=(700, 3))                                      # a 6^3 lattice: 216 places for 700 points
+    lattice = (q * 0.25).astype(np.float32)                                    # every distance is exact in f32
+    half = rng.normal(0, 0.3, (150, 3)).astype(np.float32)
+    twins = np.concatenate([half, half])                                       # point i + 150 is point i again
+    inter = np.repeat(half, 2, axis=0)                                         # point 2 i + 1 is point 2 i again
+    starts = np.array([[699, 0], [299, 3], [1, 2]], np.int32)
+    lo, aux = run(net, [lattice, twins, inter], fps_start=starts)
+    assert_tables([lattice, twins, inter], starts, aux, "ties")
+    f1 = aux["fps1"][0].numpy()
+    assert np.array_equal(f1, lattice_fps(q, 512, 699))
+    f2 = aux["fps2"][0].numpy()
+    assert np.array_equal(f2, lattice_fps(q[f1], 128, 0))
+    k1 = aux["knn1"][0].numpy()
+    assert np.array_equal(k1, lattice_knn(q, q[f1], 32))                       # many equal distances at the 32nd place
+    assert np.array_equal(aux["knn2"][0].numpy(), lattice_knn(q[f1], q[f1][f2], 64))
+    t = aux["fps1"][1].numpy()
+    assert t[0] == 299 and (t[1:150] < 150).all() and (t[150:] == 0).all()     # after the start only first copies, then exhausted
+    k = aux["knn1"][1].numpy()                                                 # a point and its twin: d = 0 twice, the lower index first
+    first = np.where(t < 150, t, t - 150)
+    assert np.array_equal(k[:, 0], first) and np.array_equal(k[:, 1], first + 150)
+    t = aux["fps1"][2].numpy()
+    assert t[0] == 1 and (t[1:150] % 2 == 0).all() and (t[150:] == 0).all()
+    k = aux["knn1"][2].numpy()
+    assert np.array_equal(k[:, 0], t - t % 2) and np.array_equal(k[:, 1], t - t % 2 + 1)
+    assert (k[:, 0::2] % 2 == 0).all() and np.array_equal(k[:, 1::2], k[:, 0::2] + 1)     # the copies stay in pairs down the row
+
+
+# ---- 3. arithmetic against float64, the GPU's tables forced -------------------------------------------------------------------
+def check_arithmetic(sd, clouds, lo, aux, what):
+    import pointconv_oracle as PO
+    t = {k: aux[k].numpy() for k in TABLES}
+    r32 = PO.forward(PO.to_torch(sd), clouds, tables=t)
+    r64 = PO.forward(PO.to_torch(sd, torch.float64), clouds, dtype=torch.float64, tables=t)
+    bad, ratio = [], {}
+    for name, got in [(k, aux[k]) for k in TENSORS] + [("logits", lo)]:
+        e32 = float((r32[name].double() - r64[name]).abs().max())
+        egpu = float((got.double() - r64[name]).abs().max())
+        assert e32 > 0, (what, name)
+        ratio[name] = egpu / e32
+        if egpu > 4 * e32:
+            bad.append((name, egpu, e32))
+    print("%s: e_gpu / e_32: %s" % (what, ", ".join("%s %.2f" % kv for kv in ratio.items())))
+    assert not bad, (what, bad)
+    return ratio
+
+
+def test_arithmetic_against_f64(sd, sized):
+    worst = {}
+    for c, st, lo, aux in sized:
+        for k, v in check_arithmetic(sd, [c], lo, aux, "n = %d" % len(c)).items():
+            worst[k] = max(worst.get(k, 0.0), v)
+    print("worst e_gpu / e_32: %s" % ", ".join("%s %.2f" % kv for kv in worst.items()))
+
+
+def test_arithmetic_against_f64_ragged(net, sd, pool):
+    clouds = [cloud(pool, 11 + i, n) for i, n in enumerate((40, 300, 65, 257))]
+    lo, aux = run(net, clouds)
+    assert_tables(clouds, None, aux, "ragged")
+    check_arithmetic(sd, clouds, lo, aux, "ragged 40 / 300 / 65 / 257")
+
+
+# ---- 4. predictions ----------------------------------------------------------------------------------------------------------
+@pytest.fixture(scope="module")
+def varied():
+    import bench
+    import pointconv_oracle as PO
+    sd = PO.make_calibrated_weights(0)
+    x = np.ascontiguousarray(bench.synth_clouds(256, seed=23)[:, :128])
+    with make_net(sd) as c:
+        lo, aux = run(c, x)
+    return sd, x, lo, aux
+
+
+def test_predictions_against_f64(varied):
+    import cls_checks
+    import pointconv_oracle as PO
+    sd, x, lo, aux = varied
+    t = {k: aux[k].numpy() for k in TABLES}
+    lo32 = PO.forward(PO.to_torch(sd), x, tables=t)["logits"]
+    lo64 = PO.forward(PO.to_torch(sd, torch.float64), x, dtype=torch.float64, tables=t)["logits"]
+    e_32 = cls_checks.e32_of(lo32, lo64)
+    assert e_32 > 0
+    e_gpu = float((lo.double() - lo64).abs().max())
+    print("calibrated head: e_gpu %.3e, e_32 %.3e, ratio %.2f" % (e_gpu, e_32, e_gpu / e_32))
+    assert e_gpu <= 4 * e_32
+    cls_checks.check_pred_against_f64(aux["pred"].numpy(), lo64, e_32, "pointconv, calibrated head, 256 x 128 points")
+    for b in (0, 100, 255):
+        PO.check_tables(x[b], {k: t[k][b] for k in TABLES}, (0, 0), "calibrated, cloud %d" % b)
+
+
+def test_pred_is_the_argmax_of_its_own_logits(varied):
+    import cls_checks
+    import pointconv_oracle as PO
+    sd, x, lo, aux = varied
+    cls_checks.check_pred_is_argmax(aux["pred"].numpy(), lo, "calibrated head")
+    with make_net(PO.make_tied_weights(sd)) as c:
+        lo_t, aux_t = run(c, x[:64])
+    cls_checks.check_ties(lo_t, aux_t["pred"].numpy(), "tied head")
+    assert torch.equal(lo_t[:, :20], lo[:64, :20])
+
+
+# ---- 5. bitwise independence -------------------------------------------------------------------------------------------------
+def same_cloud(a_lo, a_aux, ia, b_lo, b_aux, ib, n=200):
+    assert torch.equal(a_lo[ia], b_lo[ib])
+    for k in a_aux:
+        if k == "dens1":                                                       # [B, stride]: compare the cloud's own rows
+            assert torch.equal(a_aux[k][ia][:n], b_aux[k][ib][:n]), k
+        else:
+            assert torch.equal(a_aux[k][ia], b_aux[k][ib]), k
+
+
+def test_a_cloud_does_not_depend_on_its_batch(net, pool):
+    rng = np.random.default_rng(12)
+    B = CHUNK + 1
+    x = np.stack([cloud(pool, i, 200) + np.float32(0.001 * i) for i in range(B)])
+    starts = np.stack([rng.integers(0, 200, B), rng.integers(0, 512, B)], 1).astype(np.int32)
+    lo_all, aux_all = run(net, x, fps_start=starts)                            # 33 clouds: chunks of 17 and 16
+    for n in (1, 2, CHUNK):                                                    # ... one chunk of 1, of 2, of exactly 32
+        lo, aux = run(net, x[:n], fps_start=starts[:n])
+        for b in (range(n) if n <= 2 else (0, 16, 17, CHUNK - 1)):
+            same_cloud(lo, aux, b, lo_all, aux_all, b)
+    lo_r, aux_r = run(net, np.roll(x[:17], 5, axis=0), fps_start=np.roll(starts[:17], 5, axis=0))
+    for b in range(17):
+        same_cloud(lo_r, aux_r, (b + 5) % 17, lo_all, aux_all, b)
+    # a larger stride, NaN beyond n_points
+    pad = np.full((17, 333, 3), np.nan, np.float32)
+    pad[:, :200] = x[:17]
+    lo_p, aux_p = run(net, pad, fps_start=starts[:17], n_points=np.full(17, 200, np.int32))
+    for b in range(17):
+        same_cloud(lo_p, aux_p, b, lo_all, aux_all, b)
+    # ... and one that changes the sampling and the neighbour kernels' points per thread (above 512 and above 1024 rows)
+    for stride in (600, 1100):
+        pad = np.zeros((3, stride, 3), np.float32)
+        pad[:, :200] = x[:3]
+        lo_p, aux_p = run(net, pad, fps_start=starts[:3], n_points=np.full(3, 200, np.int32))
+        for b in range(3):
+            same_cloud(lo_p, aux_p, b, lo_all, aux_all, b)
+
+
+def test_stale_workspace(net, pool):
+    sizes = (40, 64, 32, 33, 300)
+    clouds = [cloud(pool, b, n) for b, n in enumerate(sizes)]
+    lo, aux = run(net, clouds)
+    run(net, np.stack([cloud(pool, i, 2048) for i in range(CHUNK + 8)]))       # a larger call in between
+    for b, c in enumerate(clouds):                                             # ... then every cloud alone
+        lo1, aux1 = run(net, [c])
+        same_cloud(lo1, aux1, 0, lo, aux, b, n=sizes[b])
+
+
+# ---- 6. refusals -------------------------------------------------------------------------------------------------------------
+def test_runtime_refusals_leave_the_context_usable(net, pool):
+    import ifdefense_amd as I
+    x = np.stack([cloud(pool, 0, 64), cloud(pool, 1, 64)])
+    want = net.logits(x).cpu()
+    ok = [[0, 0], [63, 511]]
+    for bad_x, counts, starts, words in ((x, [64, 31], None, "n_points outside"), (x, [65, 64], None, "n_points outside"),
+                                         (np.zeros((1, 2049, 3), np.float32), None, None, "stride above 2048"),
+                                         (np.zeros((1, 31, 3), np.float32), None, None, "stride below 32"),
+                                         (x, None, [[0, 0], [64, 0]], "fps_start outside"), (x, [64, 40], [[0, 0], [40, 0]], "fps_start outside"),
+                                         (x, None, [[0, 0], [0, 512]], "fps_start outside"), (x, None, [[-1, 0], [0, 0]], "fps_start outside")):
+        with pytest.raises(I.IfdError, match="libifd error %d: .*%s" % (IFD_ERR_ARG, words)):
+            net.logits(bad_x, n_points=counts, fps_start=starts)
+        assert torch.equal(net.logits(x).cpu(), want)
+    assert torch.equal(net.logits(x, fps_start=[[0, 0], [0, 0]]).cpu(), want)  # NULL starts mean 0, 0
+    assert bool(torch.isfinite(net.logits(x, fps_start=ok)).all())             # the last valid starts are taken
+
+
+# ---- 7. the CLI --------------------------------------------------------------------------------------------------------------
+def test_cli_end_to_end(varied, tmp_path, capsys):
+    import pointconv_oracle as PO
+    from ifdefense_amd import pointconv_inference as Inf
+    sd, x, lo, aux = varied
+    wpath = str(tmp_path / "pointconv.npz")
+    np.savez(wpath, **sd)
+    n = 48
+    starts = Inf.fps_starts(1, [128] * n)
+    t = PO.tables_of(x[:n], fps_start=starts)
+    pred = PO.forward(PO.to_torch(sd, torch.float64), x[:n], dtype=torch.float64, tables=t)["logits"].argmax(1).numpy()
+    with make_net(sd) as c:
+        got = c.predict(x[:n], fps_start=starts).cpu().numpy()
+    assert np.array_equal(got, pred)
+    label = pred.copy()
+    label[::4] = (label[::4] + 1) % 40
+    target = (pred + (np.arange(n) % 3 == 0)) % 40
+    same = str(tmp_path / "kNN-pointconv-same.npz")
+    np.savez(same, test_pc=x[:n], test_label=label, target_label=target)
+    assert Inf.main(["--data_root", same, "--mode", "target", "--model_path", wpath, "--num_points", "128"]) == 0
+    out = capsys.readouterr().out
+    assert out == "Overall accuracy: %.4f, attack success rate: %.4f\n" % ((pred == label).mean(), (pred == target).mean())
+    sizes = [128, 100, 64, 32, 77, 128]
+    rag = np.empty(len(sizes), dtype=object)
+    for i, m in enumerate(sizes):
+        rag[i] = x[100 + i, :m]
+    st = Inf.fps_starts(7, sizes)
+    with make_net(sd) as c:
+        pr = c.predict([rag[i] for i in range(len(sizes))], fps_start=st).cpu().numpy()
+    lab = pr.copy()
+    lab[1] = (lab[1] + 3) % 40
+    ragged = str(tmp_path / "sor-ragged.npz")
+    np.savez(ragged, test_pc=rag, test_label=lab)
+    assert Inf.main(["--data_root", ragged, "--model", "pointconv", "--model_path", wpath, "--fps_seed", "7"]) == 0
+    assert capsys.readouterr().out == "Overall accuracy: %.4f\n" % (5 / 6)
