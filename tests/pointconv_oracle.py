@@ -12,6 +12,9 @@ reaches 9 ulp of s; the header's difference form, exact on copies, stays near 1 
 float64 run takes its index tables from outside (the float32 run's, or an implementation's): a different neighbour moves the
 logits by far more than the arithmetic does.
 
+``density_header`` is the header's own density (difference form, its sum order) in numpy float32, the yardstick of rho itself:
+``make_identity_density_weights`` turns every DensityNet into the identity, so that an implementation's dens outputs are rho.
+
 Weights: ``make_weights(seed)`` draws the un-folded state_dict from numpy's default_rng(seed + 9301), layers in canonical order
 (ifdefense_amd.weights.pointconv_layers): weight and bias U(+-1/sqrt(fan_in)), then the layer's BatchNorm: gamma 1 + U(+-0.2), beta
 U(+-0.1), running_mean N(0, 0.1), running_var U(0.5, 1.25).  A DensityNet ends in a ReLU and multiplies every feature, and a net of
@@ -32,7 +35,9 @@ import torch
 import torch.nn.functional as F
 
 from ifdefense_amd.weights import BN_EPS, pointconv_layers
-from pointnet2_oracle import _clouds, dist, fps, make_tied_weights, reference_state_dict, to_torch  # noqa: F401
+from pointnet2_oracle import (DIST_MUTANTS, LATTICE_FAMILY, RULE_FPS, RULE_KNN, _clouds, certify, check_family, dist,  # noqa: F401
+                              dyadic_cloud, family_cloud, fps, fps_highest, fps_refusals, group_refusals, lattice_cloud,
+                              make_tied_weights, reference_state_dict, rows_differing, stride_class, to_torch)
 
 NP1, K1, BW1 = 512, 32, 0.1
 NP2, K2, BW2 = 128, 64, 0.2
@@ -76,6 +81,24 @@ def _calibrated_fc3(seed):
     return w3.astype(np.float32), (-(w3 @ mu)).astype(np.float32), int(live.sum())
 
 
+def make_identity_density_weights(sd):
+    """A copy of ``sd`` in which every DensityNet is the identity on its unit 0: weights 1 on the path unit 0 -> unit 0 -> unit 0
+    and 0 elsewhere, biases 0, BatchNorm gamma 1, beta 0, mean 0 and running_var 1 - BN_EPS, so that the fold's scale
+    gamma / sqrt(var + eps) rounds to exactly 1.  Every chain of the GPU's DensityNet is then fma(1, rho, 0) and exact zeros, rho >= 0
+    passes the ReLUs untouched: dens1, dens2 and dens3 are rho itself."""
+    sd = {k: np.array(v, copy=True) for k, v in sd.items()}
+    for lin, bn, _, _ in pointconv_layers():
+        if ".densitynet." not in lin:
+            continue
+        w = np.zeros_like(sd[lin + ".weight"])
+        w[0, 0] = 1
+        sd[lin + ".weight"], sd[lin + ".bias"] = w, np.zeros_like(sd[lin + ".bias"])
+        co = w.shape[0]
+        sd[bn + ".weight"], sd[bn + ".bias"] = np.ones(co, F32), np.zeros(co, F32)
+        sd[bn + ".running_mean"], sd[bn + ".running_var"] = np.zeros(co, F32), np.full(co, 1.0 - BN_EPS, F32)
+    return sd
+
+
 def make_calibrated_weights(seed=0):
     """make_weights(seed) with fc3 rescaled so that the predicted class varies from cloud to cloud (module docstring)."""
     w = make_weights(seed)
@@ -85,13 +108,72 @@ def make_calibrated_weights(seed=0):
 
 
 # ---- selection, numpy float32 (include/ifd_pc.h) --------------------------------------------------------------------------
-def knn(k, x, centroids):
+def knn(k, x, centroids, dist=dist, higher_first=False):
     """x [n,3], centroids [m,3] -> [m,k] int32: the k points of smallest dist, the lower index first among equal distances, in
-    ascending (d, index) order."""
+    ascending (d, index) order.  ``dist``: another distance of dist's signature (pointnet2_oracle.DIST_MUTANTS);
+    ``higher_first``: the rule mutant that puts the HIGHER index first among equal distances."""
     x, c = np.asarray(x, F32), np.asarray(centroids, F32)
     assert len(x) >= k
     d = dist(x[None, :, :], c[:, None, :])
+    if higher_first:
+        return (len(x) - 1 - np.argsort(d[:, ::-1], axis=1, kind="stable")[:, :k]).astype(np.int32)
     return np.argsort(d, axis=1, kind="stable")[:, :k].astype(np.int32)
+
+
+def knn_higher_first(k, x, centroids):
+    """The rule mutant of knn: ascending (d, -index) order."""
+    return knn(k, x, centroids, higher_first=True)
+
+
+def _knn_group(level, src, cen, dist=dist, rule=False):
+    return knn((K1, K2)[level], src, cen, dist=dist, higher_first=rule)
+
+
+def knn_refusals(i):
+    """pointnet2_oracle's fps_refusals and group_refusals of cloud i with the kNN as the grouping, in one dict."""
+    out = {k: dict(v) for k, v in fps_refusals(i).items()}
+    for k, v in group_refusals(i, _knn_group, ("knn1", "knn2"), RULE_KNN).items():
+        out.setdefault(k, {}).update(v)
+    return out
+
+
+# ---- the density as the header states it, numpy float32 --------------------------------------------------------------------
+def density_header(x, bw):
+    """x [n,3] -> rho [n] float32, include/ifd_pc.h's density word for word: d = dist (the difference form, every operation rounded),
+    e_i = expf(-(d_ij / c1)) with c1 = (float)(2 bw bw), 64 partial sums (partial l over i = l, l + 64, ... in ascending order
+    from 0), the butterfly l ^ 1, l ^ 2, ..., l ^ 32, then / (float)n, then / c2 with c2 = (float)(2.5 bw).  expf here is the
+    float64 exponential rounded to float32, the correctly rounded one; a C library's expf may differ from it in the last place,
+    except where the argument is -0 (e = 1) or below -104 (e = 0), where every expf agrees."""
+    x = np.asarray(x, F32)
+    n = len(x)
+    c1, c2 = F32(2.0 * bw * bw), F32(2.5 * bw)
+    arg = -((dist(x[None, :, :], x[:, None, :]) / c1).astype(F32))            # [j, i]
+    e = np.zeros((n, -(-n // 64) * 64), F32)
+    e[:, :n] = np.exp(arg.astype(np.float64)).astype(F32)
+    e = e.reshape(n, -1, 64)
+    acc = np.zeros((n, 64), F32)
+    for k in range(e.shape[1]):                                              # an index beyond n adds nothing (+0 to a sum >= +0)
+        acc = (acc + e[:, k, :]).astype(F32)
+    lane = np.arange(64)
+    for off in (1, 2, 4, 8, 16, 32):
+        acc = (acc + acc[:, lane ^ off]).astype(F32)
+    assert (acc == acc[:, :1]).all()                                         # all 64 ends are the same number
+    return ((acc[:, 0] / F32(n)).astype(F32) / c2).astype(F32)
+
+
+def density_f64(x, bw):
+    """x [n,3] float32 -> rho [n] float64: the same density on the same float32 coordinates in float64, the difference form."""
+    x = np.asarray(x, F32).astype(np.float64)
+    d = ((x[None, :, :] - x[:, None, :]) ** 2).sum(-1)
+    return np.exp(-d / (2.0 * bw * bw)).mean(-1) / (2.5 * bw)
+
+
+def level_inputs(x, fps1, fps2):
+    """The three clouds whose densities a forward pass takes, with their bandwidths: the cloud, its 512 level-1 centroids, their
+    128 level-2 centroids (repeats included).  -> [("dens1", x, 0.1), ("dens2", x[fps1], 0.2), ("dens3", x[fps1][fps2], 0.4)]."""
+    x = np.asarray(x, F32)
+    c1 = x[np.asarray(fps1)]
+    return [("dens1", x, BW1), ("dens2", c1, BW2), ("dens3", c1[np.asarray(fps2)], BW3)]
 
 
 def tables_of_cloud(x, start=(0, 0)):
@@ -110,11 +192,11 @@ def tables_of(clouds, n_points=None, fps_start=None):
     return {k: np.stack([p[k] for p in per]) for k in TABLES}
 
 
-def check_tables(x, t, start=(0, 0), what=""):
+def check_tables(x, t, start=(0, 0), what="", want=None):
     """The tables ``t`` of one cloud x [n,3] are the header's: every FPS pick is the lowest index of the largest running
     distance, every kNN row the K nearest in ascending (d, index) order.  Asserts with the first offender."""
     x = np.asarray(x, F32)
-    want = tables_of_cloud(x, start)
+    want = tables_of_cloud(x, start) if want is None else want      # want: tables_of_cloud(x, start) computed before
     for name in TABLES:
         got = np.asarray(t[name])
         assert got.shape == want[name].shape, (what, name, got.shape)
@@ -144,6 +226,11 @@ def density_scale(W, layers, xyz, bw):
     d = (sq[:, None] + sq[None, :]) - 2.0 * (xyz @ xyz.t())
     rho = (torch.exp(-d / (2.0 * bw * bw)) / (2.5 * bw)).mean(-1)
     return rho, _stack(W, layers, rho[:, None])[:, 0]
+
+
+def density_net(W, level, rho):
+    """DensityNet of level 0, 1, 2 on given densities rho [n] (a tensor of W's dtype) -> s [n]."""
+    return _stack(W, pointconv_layers()[10 * level:10 * level + 3], rho[:, None])[:, 0]
 
 
 def _level(W, L, grouped_xyz, feats, scale):

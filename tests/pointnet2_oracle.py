@@ -7,6 +7,11 @@ as linear layers on the grouped rows, max over the samples; the group-all level;
 yardstick of the GPU's arithmetic.  A float64 run takes its index tables from outside (the float32 run's, or an
 implementation's): a different ball member moves the logits by far more than the arithmetic does.
 
+What "exactly as the header defines them" rests on: ``DIST_MUTANTS`` (a contracted, a re-associated, a matrix-form and a doubly
+precise distance) and the rule mutants (``fps(highest=True)``, ``ball(open_edge=True)``, pointconv_oracle's ``knn(higher_first=True)``)
+are the wrong definitions an implementation could compute instead, and ``LATTICE_FAMILY`` the clouds certified to give other
+tables under every one of them (``certify``); ``check_family`` holds an implementation's tables to the oracle's on those clouds.
+
 Weights: ``make_weights(seed)`` draws the un-folded state_dict from numpy's default_rng(seed + 9201), layers in network order
 (ifdefense_amd.weights.pointnet2_layers): weight and bias U(+-1/sqrt(fan_in)), then the layer's BatchNorm: gamma 1 + U(+-0.2), beta
 U(+-0.1), running_mean N(0, 0.1), running_var U(0.5, 1.25).  A dict WITHOUT BatchNorm keys (weights.fold_pointnet2's output) runs
@@ -101,9 +106,52 @@ def dist(x, c):
     return ((sq[..., 0] + sq[..., 1]).astype(F32) + sq[..., 2]).astype(F32)
 
 
-def fps(x, npoint, start):
+def _diffs(x, c):
+    d = (np.asarray(x, F32) - np.asarray(c, F32)).astype(F32)
+    return d[..., 0], d[..., 1], d[..., 2]
+
+
+# Wrong distances of dist's signature: what a compiler or a refactor could make of the header's three lines.  The certification
+# tests (test_pointnet2_cpu.py, test_pointconv_cpu.py) show that LATTICE_FAMILY's tables refuse every one of them.
+def dist_contracted(x, c):
+    """fma(dz, dz, fma(dy, dy, dx dx)): the differences and the first product rounded, the two sums fused with their products
+    (what hipcc makes of the expression without the pragma), in correctly rounded float32 fmas (dgcnn_oracle.fma32)."""
+    from dgcnn_oracle import fma32
+    dx, dy, dz = _diffs(x, c)
+    return fma32(dz, dz, fma32(dy, dy, (dx * dx).astype(F32)))
+
+
+def dist_reassociated(x, c):
+    """dx dx + (dy dy + dz dz), every operation rounded on its own: the header's operations in another order."""
+    dx, dy, dz = _diffs(x, c)
+    return ((dx * dx).astype(F32) + ((dy * dy).astype(F32) + (dz * dz).astype(F32)).astype(F32)).astype(F32)
+
+
+def dist_matrix(x, c):
+    """The reference's matrix form (|a|^2 + |c|^2) - 2 <a, c> in float32: squares and products added in x, y, z order, every
+    operation rounded on its own."""
+    x, c = np.asarray(x, F32), np.asarray(c, F32)
+
+    def dot(a, b):
+        p = (a * b).astype(F32)
+        return ((p[..., 0] + p[..., 1]).astype(F32) + p[..., 2]).astype(F32)
+    return ((dot(x, x) + dot(c, c)).astype(F32) - (F32(2) * dot(x, c)).astype(F32)).astype(F32)
+
+
+def dist_float64(x, c):
+    """The difference form on the float32 coordinates in float64, rounded to float32 once."""
+    d = np.asarray(x, F32).astype(np.float64) - np.asarray(c, F32).astype(np.float64)
+    sq = d * d
+    return ((sq[..., 0] + sq[..., 1]) + sq[..., 2]).astype(F32)
+
+
+DIST_MUTANTS = {"contracted": dist_contracted, "re-associated": dist_reassociated, "matrix": dist_matrix, "float64": dist_float64}
+
+
+def fps(x, npoint, start, dist=dist, highest=False):
     """x [n,3] -> [npoint] int32: the running distance starts at 1e10, is lowered where dist < running (strictly), and the next
-    pick is the largest running distance, the lowest index among equal ones."""
+    pick is the largest running distance, the lowest index among equal ones.  ``dist``: another distance of dist's signature;
+    ``highest``: the rule mutant that takes the HIGHEST index among equal ones."""
     x = np.asarray(x, F32)
     running = np.full(len(x), 1e10, F32)
     out = np.empty(npoint, np.int32)
@@ -113,18 +161,25 @@ def fps(x, npoint, start):
         out[i] = far
         d = dist(x, x[far])
         running = np.where(d < running, d, running)
-        far = int(np.argmax(running))                    # the first of equal maxima
+        far = len(x) - 1 - int(np.argmax(running[::-1])) if highest else int(np.argmax(running))   # the first of equal maxima
     return out
+
+
+def fps_highest(x, npoint, start):
+    """The rule mutant of fps: the highest index among equal running distances."""
+    return fps(x, npoint, start, highest=True)
 
 
 def radius2(r):
     return F32(float(r) * float(r))
 
 
-def ball(r, nsample, x, centroids):
-    """x [n,3], centroids [m,3] -> [m,nsample] int32: the first nsample j (ascending) with not (d_ij > r2), padded with the first."""
+def ball(r, nsample, x, centroids, dist=dist, open_edge=False):
+    """x [n,3], centroids [m,3] -> [m,nsample] int32: the first nsample j (ascending) with not (d_ij > r2), padded with the first.
+    ``dist``: another distance of dist's signature; ``open_edge``: the rule mutant that leaves d == r2 outside."""
     x, c = np.asarray(x, F32), np.asarray(centroids, F32)
-    member = ~(dist(x[None, :, :], c[:, None, :]) > radius2(r))
+    d = dist(x[None, :, :], c[:, None, :])
+    member = d < radius2(r) if open_edge else ~(d > radius2(r))
     out = np.empty((len(c), nsample), np.int32)
     for i in range(len(c)):
         j = np.nonzero(member[i])[0][:nsample]
@@ -150,11 +205,11 @@ def tables_of(clouds, n_points=None, fps_start=None):
     return {k: np.stack([p[k] for p in per]) for k in ("fps1", "fps2", "ball1", "ball2")}
 
 
-def check_tables(x, t, start=(0, 0), what=""):
+def check_tables(x, t, start=(0, 0), what="", want=None):
     """The tables ``t`` of one cloud x [n,3] are the header's: every FPS pick is the lowest index of the largest running
     distance, every ball row the first members in ascending index padded with the first.  Asserts with the first offender."""
     x = np.asarray(x, F32)
-    want = tables_of_cloud(x, start)
+    want = tables_of_cloud(x, start) if want is None else want      # want: tables_of_cloud(x, start) computed before
     for name in ("fps1", "fps2", "ball1", "ball2"):
         got = np.asarray(t[name])
         assert got.shape == want[name].shape, (what, name, got.shape)
@@ -162,6 +217,153 @@ def check_tables(x, t, start=(0, 0), what=""):
         assert bad.size == 0, (what, name, "first difference at", tuple(bad[0]), "got", int(got[tuple(bad[0])]), "want",
                                int(want[name][tuple(bad[0])]), "of %d" % len(bad))
     return want
+
+
+# ---- clouds on which rounding decides the selection ------------------------------------------------------------------------
+def lattice_cloud(seed, m, n, s, o):
+    """n distinct places q of the m^3 integer lattice in the order default_rng(seed) draws them -> float32(q s + o) [n,3].  With a
+    spacing s that is no power of two, distances that tie over the integers become float32 near-ties, ordered by the rounding of
+    every single operation: natural clouds, dyadic lattices and twins accept a contracted, a re-associated or a doubly precise
+    distance, these clouds refuse them."""
+    assert n <= m ** 3
+    q = np.stack(np.unravel_index(np.random.default_rng(seed).permutation(m ** 3)[:n], (m, m, m)), 1)
+    return np.ascontiguousarray((q * float(s) + float(o)).astype(F32))
+
+
+# (seed, m, n, s, o).  The sizes are the edges of every points-per-thread variant of the sampling and the neighbour kernels (stride
+# <= 512, <= 1024, above); the spacings put mixed offsets on both radii: (2, 2, 1) s and (4, 4, 2) s at s = 0.2 / 3, (3, 4, 0) s
+# and (6, 8, 0) s at s = 0.04.  n = 20 lies below PointConv's 32 points and is PointNet++'s alone.
+_S3 = 0.2 / 3
+LATTICE_FAMILY = ((14, 4, 20, _S3, -0.4), (11, 8, 33, _S3, -0.4), (14, 12, 100, 0.04, -0.37), (14, 16, 300, _S3, -0.4),
+                  (11, 16, 512, _S3, -0.4), (11, 16, 513, _S3, -0.4), (14, 20, 1024, 0.04, -0.37), (11, 16, 1025, _S3, -0.4),
+                  (14, 20, 2048, 0.04, -0.37))
+STRIDE_CLASSES = ("<= 512", "<= 1024", "> 1024")
+RULE_FPS, RULE_BALL, RULE_KNN = "fps: highest index", "ball: d == r2 outside", "knn: higher index first"
+
+
+def stride_class(n):
+    """Which points-per-thread variant of the sampling and the neighbour kernels a cloud of n rows runs on (stride = n)."""
+    return 0 if n <= 512 else 1 if n <= 1024 else 2
+
+
+def dyadic_cloud(n=700):
+    """The tie lattice of the GPU tests: n points on 6^3 places at spacing 0.25, every distance exact in float32, many of them
+    equal and most places taken more than once.  -> (x [n,3] float32, q [n,3] integer places)."""
+    q = np.random.default_rng(5).integers(0, 6, size=(n, 3))
+    return (q * 0.25).astype(F32), q
+
+
+def _frozen(a):
+    a.setflags(write=False)
+    return a
+
+
+@functools.lru_cache(maxsize=None)
+def family_cloud(i):
+    """Cloud i of LATTICE_FAMILY, or the dyadic lattice for i = "dyadic", with the header's sampling of it from the starts 0, 0:
+    (x, fps1, fps2), computed once."""
+    x = dyadic_cloud()[0] if i == "dyadic" else lattice_cloud(*LATTICE_FAMILY[i])
+    f1 = fps(x, NP1, 0)
+    return _frozen(x), _frozen(f1), _frozen(fps(x[f1], NP2, 0))
+
+
+def rows_differing(a, b):
+    """Picks (1-D tables) or rows (2-D tables) in which two tables differ."""
+    ne = np.asarray(a) != np.asarray(b)
+    return int((ne if ne.ndim == 1 else ne.any(axis=1)).sum())
+
+
+@functools.lru_cache(maxsize=None)
+def fps_refusals(i):
+    """How many picks of the header's two samplings of family_cloud(i) change under every wrong distance and under the rule
+    mutant, level 2 on the header's level-1 centroids: {mutant: {"fps1": picks, "fps2": picks}}."""
+    x, f1, f2 = family_cloud(i)
+    c1 = x[f1]
+    out = {name: {"fps1": rows_differing(fps(x, NP1, 0, dist=d), f1), "fps2": rows_differing(fps(c1, NP2, 0, dist=d), f2)}
+           for name, d in DIST_MUTANTS.items()}
+    out[RULE_FPS] = {"fps1": rows_differing(fps_highest(x, NP1, 0), f1), "fps2": rows_differing(fps_highest(c1, NP2, 0), f2)}
+    return out
+
+
+def group_refusals(i, group, names, rule_name):
+    """How many rows of the header's two grouping tables of family_cloud(i) change under every wrong distance and under the
+    grouping's rule mutant, the centroids forced to the header's.  group(level, src, centroids, **kw) is the victim's grouping
+    (ball query or kNN) with dist = ... or rule = True.  -> {mutant: {names[0]: rows, names[1]: rows}}."""
+    x, f1, f2 = family_cloud(i)
+    c1 = x[f1]
+    levels = ((x, c1), (c1, c1[f2]))
+    want = [group(lv, src, cen) for lv, (src, cen) in enumerate(levels)]
+    out = {name: {names[lv]: rows_differing(group(lv, src, cen, dist=d), want[lv]) for lv, (src, cen) in enumerate(levels)}
+           for name, d in DIST_MUTANTS.items()}
+    out[rule_name] = {names[lv]: rows_differing(group(lv, src, cen, rule=True), want[lv]) for lv, (src, cen) in enumerate(levels)}
+    return out
+
+
+def certify(clouds, refusals_of, tables):
+    """The condition the GPU's selection tests rest on: refusals_of(i) -> {mutant: {table: differing rows}} for every cloud i of
+    ``clouds`` (indices into LATTICE_FAMILY); every mutant must change every one of its tables on at least one cloud of every
+    stride class.  Prints the counts, asserts with the empty cells."""
+    cells, lines = {}, []
+    for i in clouds:
+        seed, m, n, s, o = LATTICE_FAMILY[i]
+        for mutant, per in refusals_of(i).items():
+            for t in tables:
+                if t in per:
+                    cells.setdefault((mutant, t), [0, 0, 0])[stride_class(n)] += per[t] > 0
+            lines.append("%-26s %-40s %s" % (mutant, "n = %d (seed %d, m %d, s %.4g, o %.4g)" % (n, seed, m, s, o),
+                                             "  ".join("%s %d" % (t, per[t]) for t in tables if t in per)))
+    print("\n".join(sorted(lines, key=lambda l: l[:26])))
+    empty = [(m, t, STRIDE_CLASSES[c]) for (m, t), per in cells.items() for c in range(3) if per[c] == 0]
+    assert not empty, ("accepted by every cloud of a stride class", empty)
+    return cells
+
+
+def check_family(cls, victim, call, min_points=1):
+    """An implementation's tables on the clouds of LATTICE_FAMILY of stride class ``cls`` (of at least min_points points) against
+    ``victim``'s oracle (this module or pointconv_oracle: tables_of_cloud, check_tables), each cloud's oracle tables computed once
+    per start pair.  call(x [B,stride,3], fps_start [B,2] int32 or None, n_points [B] int32 or None) -> {table: [B,...] array}.
+    Every cloud alone at its own stride from the starts 0, 0 and from a mid-cloud pair; all of them once more in one batch at the
+    class's largest stride with NaN beyond the counts, the starts alternating; and the 300-point cloud at strides 600 and 1100,
+    because the stride, not the count, picks the kernel variant."""
+    clouds = [np.array(family_cloud(i)[0]) for i, f in enumerate(LATTICE_FAMILY) if stride_class(f[2]) == cls and f[2] >= min_points]
+    assert clouds
+    mid = [(len(c) // 2, 255) for c in clouds]
+    want = [{st: victim.tables_of_cloud(c, st) for st in ((0, 0), m)} for c, m in zip(clouds, mid)]
+
+    def check(t, row, b, start, what):
+        victim.check_tables(clouds[b], {k: v[row] for k, v in t.items()}, start, "%s (n = %d)" % (what, len(clouds[b])), want=want[b][start])
+
+    def padded(rows, stride):
+        pad = np.full((len(rows), stride, 3), np.nan, F32)
+        for r, b in enumerate(rows):
+            pad[r, :len(clouds[b])] = clouds[b]
+        return pad, np.array([len(clouds[b]) for b in rows], np.int32)
+    for b, c in enumerate(clouds):
+        check(call(c[None], None, None), 0, b, (0, 0), "alone")
+        check(call(c[None], np.array([mid[b]], np.int32), None), 0, b, mid[b], "alone, mid-cloud starts")
+    stride = max(len(c) for c in clouds)
+    starts = [mid[b] if b % 2 == 0 else (0, 0) for b in range(len(clouds))]
+    pad, counts = padded(range(len(clouds)), stride)
+    t = call(pad, np.array(starts, np.int32), counts)
+    for b in range(len(clouds)):
+        check(t, b, b, starts[b], "ragged batch at stride %d, NaN beyond the counts" % stride)
+    for b, c in enumerate(clouds):
+        if len(c) == 300:
+            for stride in (600, 1100):
+                pad, counts = padded([b], stride)
+                check(call(pad, np.array([mid[b]], np.int32), counts), 0, b, mid[b], "stride %d" % stride)
+
+
+def _ball_group(level, src, cen, dist=dist, rule=False):
+    return ball((R1, R2)[level], (NS1, NS2)[level], src, cen, dist=dist, open_edge=rule)
+
+
+def ball_refusals(i):
+    """fps_refusals and group_refusals of cloud i with the ball query as the grouping, in one dict."""
+    out = {k: dict(v) for k, v in fps_refusals(i).items()}
+    for k, v in group_refusals(i, _ball_group, ("ball1", "ball2"), RULE_BALL).items():
+        out.setdefault(k, {}).update(v)
+    return out
 
 
 # ---- the layers, torch -----------------------------------------------------------------------------------------------------

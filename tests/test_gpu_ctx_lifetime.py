@@ -4,7 +4,7 @@ Growth: every context buffer that grows on demand and has no stale-workspace tes
 ws_dup; the classifier, attack and MISE workspaces have theirs) sees a small call, a larger one - the buffer is freed and
 allocated again - and the small call again; both small results must equal, bit for bit, the same call on a fresh context.
 Create / close: three contexts of each kind, one after the other in one process, each making the smallest call of its kind; the
-three outputs must be equal bit for bit.  The DGCNN and PointNet++ victims have both tests, on ``logits``.  Seeded weights and inputs throughout.  Nothing here looks at the free
+three outputs must be equal bit for bit.  The DGCNN, PointNet++ and PointConv victims have both tests, on ``logits``.  Seeded weights and inputs throughout.  Nothing here looks at the free
 device memory: other processes move it."""
 import numpy as np
 import pytest
@@ -167,3 +167,25 @@ def test_dgcnn_workspace_grows(dgcnn_w):
 def test_pointnet2_workspace_grows(pn2_w):
     import ifdefense_amd as I
     _small_large_small(lambda: I.PointNet2Classifier(pn2_w, device=DEV), _victim_logits, VICTIM_CALLS)
+
+
+# ---- PointConv (include/ifd_pc.h): the largest workspace of the victims, 5.9 MB a cloud, chunks of 32 ------------------------------
+@pytest.fixture(scope="module")
+def pc_w():
+    import ifdefense_amd as I
+    return I.weights.pack_state_dict(I.weights.pointconv_random_state_dict(1), "pointconv")
+
+
+def _pointconv_logits(k, which):                        # 1 x 32 points (the smallest cloud PointConv takes), 2 x 2048, 1 x 32
+    return k.logits(_rand(41 + which, (1, 2)[which], (32, 2048)[which], 3, scale=0.9))
+
+
+def test_create_call_close_three_times_pointconv(pc_w):
+    import ifdefense_amd as I
+    pc = _rand(28, 1, 32, 3, scale=0.9)                 # one cloud of 32 points
+    _three_lives(lambda: I.PointConvClassifier(pc_w, device=DEV), lambda k: k.logits(pc))
+
+
+def test_pointconv_workspace_grows(pc_w):
+    import ifdefense_amd as I
+    _small_large_small(lambda: I.PointConvClassifier(pc_w, device=DEV), _pointconv_logits, VICTIM_CALLS)

@@ -3,6 +3,8 @@
 The two selection steps (farthest point sampling, K nearest neighbours) are held to the header's definitions bit for bit: the numpy
 float32 oracle's tables must equal the GPU's.  The arithmetic is judged with the GPU's tables forced into the float32 and the
 float64 oracle, every bar relative to e_32 = max |float32 oracle - float64 oracle| of the tensor in question, computed here.
+Section 1b runs the clouds on which rounding decides the selection (certified in test_pointconv_cpu.py); section 3b holds the
+density itself to the header's sum: bit for bit where expf drops out, per element relative to float64 elsewhere.
 
 Measured on an MI355X (worst e_gpu / e_32 over test_arithmetic_against_f64's cases): DESIGN 7p."""
 import os
@@ -121,6 +123,23 @@ def test_selection_in_a_ragged_batch_with_nan_rows(net, pool):
             assert torch.equal(aux[k], aux_l[k]), k
 
 
+# ---- 1b. selection where rounding decides --------------------------------------------------------------------------------------
+@pytest.mark.parametrize("cls", [0, 1, 2])
+def test_lattice_family_equals_the_oracle(net, cls):
+    """The clouds of pointnet2_oracle.LATTICE_FAMILY from 33 points on, on which test_pointconv_cpu.py certifies that a contracted,
+    a re-associated, a matrix-form or a doubly precise distance, and each tie rule turned round, changes every table in every
+    stride class: equal tables here mean the header's distance and rules, which bench.synth_clouds, the tie lattice and twins
+    cannot tell.  The settings (alone, mid-cloud starts, a ragged NaN-padded batch, 300 points at strides 600 and 1100):
+    pointnet2_oracle.check_family."""
+    import pointconv_oracle as PO
+
+    def call(x, fps_start, n_points):
+        lo, aux = run(net, x, fps_start=fps_start, n_points=n_points)
+        assert bool(torch.isfinite(lo).all())
+        return {k: aux[k].numpy() for k in TABLES}
+    PO.check_family(cls, PO, call, min_points=PO.K1)
+
+
 # ---- 2. ties ------------------------------------------------------------------------------------------------------------------
 def lattice_fps(q, npoint, start):
     """FPS on integer coordinates in exact integer arithmetic: the lowest index of the largest running distance."""
@@ -202,6 +221,166 @@ def test_arithmetic_against_f64_ragged(net, sd, pool):
     lo, aux = run(net, clouds)
     assert_tables(clouds, None, aux, "ragged")
     check_arithmetic(sd, clouds, lo, aux, "ragged 40 / 300 / 65 / 257")
+
+
+# ---- 3b. the density itself, held to the header -------------------------------------------------------------------------------
+# Section 3's yardstick computes the density in the reference's matrix form and looks at DensityNet's output by max |.|: on natural
+# clouds DensityNet's own rounding hides rho, away from the origin the matrix form's cancellation makes the bar 1000 times looser
+# than the kernel.  Here every DensityNet is the identity (pointconv_oracle.make_identity_density_weights), so that dens1, dens2
+# and dens3 ARE rho, and rho is held to pointconv_oracle.density_header, the header's sum order in numpy float32.
+DENSITY_SIZES = (32, 33, 63, 64, 65, 100, 513, 2048)
+DENSITY_STRIDES = (333, 600, 1100)                        # ... and 200 points at these strides: n, not the stride, divides the sum
+
+
+@pytest.fixture(scope="module")
+def ident_net(sd):
+    import pointconv_oracle as PO
+    with make_net(PO.make_identity_density_weights(sd)) as c:
+        yield c
+
+
+def padded(clouds, stride):
+    pad = np.full((len(clouds), stride, 3), np.nan, np.float32)
+    for b, c in enumerate(clouds):
+        pad[b, :len(c)] = c
+    return pad, np.array([len(c) for c in clouds], np.int32)
+
+
+def density_calls(net, clouds_of):
+    """clouds_of(n) -> {name: cloud [n,3]}.  Yields (what, cloud, aux, row) for every size of DENSITY_SIZES, a size's clouds in one
+    call at stride n, and for 200 points at every stride of DENSITY_STRIDES, NaN beyond the count."""
+    for n in DENSITY_SIZES:
+        cs = clouds_of(n)
+        lo, aux = run(net, np.stack(list(cs.values())))
+        for b, (name, c) in enumerate(cs.items()):
+            yield "%s, n = %d" % (name, n), c, aux, b
+    cs = clouds_of(200)
+    for stride in DENSITY_STRIDES:
+        pad, counts = padded(list(cs.values()), stride)
+        lo, aux = run(net, pad, n_points=counts)
+        for b, (name, c) in enumerate(cs.items()):
+            assert not aux["dens1"][b, 200:].any()
+            yield "%s, n = 200 at stride %d" % (name, stride), c, aux, b
+
+
+def gpu_levels(c, aux, b):
+    """-> [(name, the GPU's [n], the level's input cloud [n,3], bandwidth)] of a cloud, the level inputs by the GPU's own sampling."""
+    import pointconv_oracle as PO
+    return [(name, aux[name][b].numpy()[:len(xyz)], xyz, bw)
+            for name, xyz, bw in PO.level_inputs(c, aux["fps1"][b].numpy(), aux["fps2"][b].numpy())]
+
+
+def zero_one_clouds(n):
+    """Clouds on which every e_i = expf(-(d / c1)) is exactly 1 (d = 0) or exactly 0 (d >= 64: the argument is below -200 at every
+    bandwidth, far below the -104 at which float32's exponential ends), so that no expf implementation matters and every partial
+    sum is a small integer: rho is (count / n) / c2 in float32, bit for bit."""
+    import pointconv_oracle as PO
+    rng = np.random.default_rng(n)
+    apart = PO.lattice_cloud(n, 13, n, 8.0, -48.0)                             # distinct integer places, at least 8 apart
+    p, q = np.array([0.3, -0.7, 0.45], np.float32), np.array([9.5, 8.25, -10.0], np.float32)
+    a = n // 3 + 1                                                             # unequal counts
+    two = np.where((rng.permutation(n) < a)[:, None], p, q).astype(np.float32)
+    return {"far apart": apart, "copies": np.tile(p, (n, 1)), "two clusters": two}
+
+
+def test_density_bit_for_bit_where_expf_drops_out(ident_net):
+    import pointconv_oracle as PO
+    for what, c, aux, b in density_calls(ident_net, zero_one_clouds):
+        n = len(c)
+        for name, got, xyz, bw in gpu_levels(c, aux, b):
+            want = PO.density_header(xyz, bw)
+            bad = np.flatnonzero(got != want)
+            assert bad.size == 0, (what, name, "first difference at", int(bad[0]), float(got[bad[0]]), float(want[bad[0]]), "of %d" % bad.size)
+        c2 = np.float32(2.5 * PO.BW1)
+        d1 = aux["dens1"][b].numpy()[:n]
+        if what.startswith("far apart"):                                       # level 1 in closed form: one e_i = 1 of n
+            assert (d1 == np.float32(np.float32(1) / np.float32(n)) / c2).all(), what
+            counts = np.bincount(aux["fps1"][b].numpy(), minlength=n)          # level 2: a centroid's copies among the 512
+            want2 = (counts[aux["fps1"][b].numpy()].astype(np.float32) / np.float32(512)) / np.float32(2.5 * PO.BW2)
+            assert np.array_equal(aux["dens2"][b].numpy(), want2), what
+            if n < 512:
+                assert counts.max() > 1                                        # repeats: the counts differ from point to point
+        if what.startswith("copies"):
+            for lv, bw in enumerate((PO.BW1, PO.BW2, PO.BW3)):
+                assert (aux["dens%d" % (lv + 1)][b].numpy()[:n if lv == 0 else None] == np.float32(1) / np.float32(2.5 * bw)).all(), (what, lv)
+        if what.startswith("two clusters"):
+            a = n // 3 + 1
+            assert sorted(set(d1.tolist())) == sorted({float((np.float32(k) / np.float32(n)) / c2) for k in (a, n - a)}), what
+
+
+def density_ratios(got_levels):
+    """[(name, got [n], xyz, bw)] -> {name: (e_gpu, e_header)}: the largest error of an element relative to its float64 value, of
+    the GPU and of density_header."""
+    import pointconv_oracle as PO
+    out = {}
+    for name, got, xyz, bw in got_levels:
+        r64 = PO.density_f64(xyz, bw)
+        out[name] = (float((np.abs(got - r64) / r64).max()), float((np.abs(PO.density_header(xyz, bw) - r64) / r64).max()))
+    return out
+
+
+def check_density_against_f64(ident_net, clouds_of):
+    bad, worst = [], {}
+    for what, c, aux, b in density_calls(ident_net, clouds_of):
+        r = density_ratios(gpu_levels(c, aux, b))
+        print("%s: e_gpu / e_header (relative to float64, per element): %s" % (what, ", ".join("%s %.2f (%.2e / %.2e)" % (k, g / h, g, h)
+                                                                                              for k, (g, h) in r.items())))
+        for k, (g, h) in r.items():
+            assert h > 0, (what, k)
+            worst[k] = max(worst.get(k, 0.0), g / h)
+            if g > 4 * h:
+                bad.append((what, k, g, h))
+    print("worst e_gpu / e_header: %s" % ", ".join("%s %.2f" % kv for kv in worst.items()))
+    assert not bad, bad
+
+
+def natural_clouds(pool):
+    def clouds_of(n):
+        c = cloud(pool, n, n)
+        return {"natural": c, "natural + 4": (c + np.float32(4)).astype(np.float32), "natural + 16": (c + np.float32(16)).astype(np.float32)}
+    return clouds_of
+
+
+def test_density_against_f64_per_element(ident_net, pool):
+    """rho of natural clouds, at the origin and shifted by 4 and by 16: every element within 4 times density_header's own largest
+    relative error against the float64 density of the same float32 coordinates."""
+    check_density_against_f64(ident_net, natural_clouds(pool))
+
+
+def test_density_against_f64_per_element_on_the_lattice_family(ident_net):
+    import pointconv_oracle as PO
+    bad = []
+    for i, f in enumerate(PO.LATTICE_FAMILY):
+        if f[2] < PO.K1:
+            continue
+        c = np.array(PO.family_cloud(i)[0])
+        lo, aux = run(ident_net, c[None])
+        r = density_ratios(gpu_levels(c, aux, 0))
+        print("lattice n = %d: e_gpu / e_header: %s" % (len(c), ", ".join("%s %.2f (%.2e / %.2e)" % (k, g / h, g, h) for k, (g, h) in r.items())))
+        bad += [(len(c), k, g, h) for k, (g, h) in r.items() if not (h > 0 and g <= 4 * h)]
+    assert not bad, bad
+
+
+def test_density_scale_of_shifted_clouds_against_the_header_form(net, sd, pool):
+    """The seeded DensityNets on clouds away from the origin: e_gpu <= 4 e_32h on dens1, dens2 and dens3, e_32h the error of
+    density_header pushed through the float32 torch DensityNet, both against the float64 density through the float64 DensityNet.
+    (Section 3's bar, the matrix form's, is three orders of magnitude wider there.)"""
+    import pointconv_oracle as PO
+    W32, W64 = PO.to_torch(sd), PO.to_torch(sd, torch.float64)
+    bad = []
+    for what, c, aux, b in density_calls(net, natural_clouds(pool)):
+        if what.startswith("natural,"):
+            continue
+        line = []
+        for lv, (name, got, xyz, bw) in enumerate(gpu_levels(c, aux, b)):
+            s64 = PO.density_net(W64, lv, torch.from_numpy(PO.density_f64(xyz, bw))).numpy()
+            s32h = PO.density_net(W32, lv, torch.from_numpy(PO.density_header(xyz, bw))).numpy()
+            e_32h, e_gpu = float(np.abs(s32h - s64).max()), float(np.abs(got - s64).max())
+            line.append("%s %.2f (%.2e / %.2e)" % (name, e_gpu / e_32h, e_gpu, e_32h))
+            if not (e_32h > 0 and e_gpu <= 4 * e_32h):
+                bad.append((what, name, e_gpu, e_32h))
+        print("%s: e_gpu / e_32h: %s" % (what, ", ".join(line)))
+    assert not bad, bad
 
 
 # ---- 4. predictions ----------------------------------------------------------------------------------------------------------

@@ -3,6 +3,7 @@
 The two selection steps (farthest point sampling, ball query) are held to the header's definitions bit for bit: the numpy float32
 oracle's tables must equal the GPU's.  The arithmetic is judged with the GPU's tables forced into the float32 and the float64
 oracle, every bar relative to e_32 = max |float32 oracle - float64 oracle| of the tensor in question, computed here.
+Section 1b runs the clouds on which rounding decides the selection (certified in test_pointnet2_cpu.py).
 
 Measured on an MI355X (worst e_gpu / e_32 over test_arithmetic_against_f64's cases): DESIGN 7n."""
 import os
@@ -113,6 +114,22 @@ def test_selection_in_a_ragged_batch_with_nan_rows(net, pool):
     assert bool(torch.isfinite(lo).all())
     lo_l, aux_l = run(net, clouds, fps_start=starts)                           # the same clouds as a list, zero padding
     assert torch.equal(lo, lo_l) and all(torch.equal(aux[k], aux_l[k]) for k in aux)
+
+
+# ---- 1b. selection where rounding decides --------------------------------------------------------------------------------------
+@pytest.mark.parametrize("cls", [0, 1, 2])
+def test_lattice_family_equals_the_oracle(net, cls):
+    """The clouds of pointnet2_oracle.LATTICE_FAMILY, on which test_pointnet2_cpu.py certifies that a contracted, a re-associated,
+    a matrix-form or a doubly precise distance, and each tie or edge rule turned round, changes every table in every stride class:
+    equal tables here mean the header's distance and rules, which bench.synth_clouds, the tie lattice and twins cannot tell.  The
+    settings (alone, mid-cloud starts, a ragged NaN-padded batch, 300 points at strides 600 and 1100): check_family."""
+    import pointnet2_oracle as PO
+
+    def call(x, fps_start, n_points):
+        lo, aux = run(net, x, fps_start=fps_start, n_points=n_points)
+        assert bool(torch.isfinite(lo).all())
+        return {k: aux[k].numpy() for k in TABLES}
+    PO.check_family(cls, PO, call)
 
 
 # ---- 2. ties of the sampling --------------------------------------------------------------------------------------------------

@@ -323,6 +323,85 @@ def test_table_checker_accepts_the_oracle_and_catches_planted_errors(g):
     assert k[0, 0] == 10 and k[0, 1] == 60
 
 
+def test_lattice_family_refuses_every_wrong_definition():
+    """The condition the GPU's selection tests rest on (test_gpu_pointconv.py, section 1b), as in test_pointnet2_cpu.py with the kNN
+    as the grouping: every wrong distance changes fps1, fps2, knn1 and knn2, and every rule mutant its own tables, on at least
+    one cloud of the family (from 33 points on) in each stride class.  The tie lattice refuses both rule mutants too."""
+    import pointconv_oracle as PO
+    clouds = [i for i, f in enumerate(PO.LATTICE_FAMILY) if f[2] >= PO.K1]
+    assert [PO.LATTICE_FAMILY[i][2] for i in clouds] == [33, 100, 300, 512, 513, 1024, 1025, 2048]
+    cells = PO.certify(clouds, PO.knn_refusals, TABLES)
+    assert set(cells) == {(m, t) for m in PO.DIST_MUTANTS for t in TABLES} | {(PO.RULE_FPS, "fps1"), (PO.RULE_FPS, "fps2"),
+                                                                             (PO.RULE_KNN, "knn1"), (PO.RULE_KNN, "knn2")}
+    tie = PO.knn_refusals("dyadic")
+    print("tie lattice:", tie)
+    assert all(tie[PO.RULE_FPS][t] > 0 for t in ("fps1", "fps2")) and all(tie[PO.RULE_KNN][t] > 0 for t in ("knn1", "knn2"))
+    t = np.array([[0, 0, 0], [1, 0, 0], [0, 1, 0], [0, 0, 1]], np.float32)
+    assert PO.knn(3, t, t[:1]).tolist() == [[0, 1, 2]] and PO.knn_higher_first(3, t, t[:1]).tolist() == [[0, 3, 2]]
+
+
+def test_density_header_and_identity_density_weights(g, runs):
+    """density_header is the header's density in numpy float32; make_identity_density_weights turns every DensityNet into the
+    identity, in the packed image exactly, so that the GPU's dens outputs are rho itself (test_gpu_pointconv.py, section 3b)."""
+    import pointconv_oracle as PO
+    from ifdefense_amd import weights
+    w, o32, o64 = runs
+    ident = PO.make_identity_density_weights(w)
+    assert all(np.array_equal(ident[k], w[k]) for k in w if ".densitynet." not in k) and ident.keys() == w.keys()
+    # the packed image: 97 floats in front of every level, {[8][1], [8], [8][8], [8], [1][8], [1]}
+    img = weights.pack_state_dict(ident, "pointconv")
+    want = np.zeros(97, np.float32)
+    want[[0, 16, 88]] = 1
+    for at in (0, 275353, 275353 + 1115609):
+        assert np.array_equal(img[at:at + 97], want), at
+    other = np.ones(img.size, bool)
+    for at in (0, 275353, 275353 + 1115609):
+        other[at:at + 97] = False
+    assert np.array_equal(img[other], weights.pack_state_dict(w, "pointconv")[other])
+    # the torch oracle returns rho as s: in float32 bit for bit, in float64 up to running_var's rounding
+    pcs, t = golden_clouds(g), golden_tables(g)
+    W32, W64 = PO.to_torch(ident), PO.to_torch(ident, torch.float64)
+    L = weights.pointconv_layers()
+    for b in (0, 2, 4):
+        for lv, (name, xyz, bw) in enumerate(PO.level_inputs(pcs[b], t["fps1"][b], t["fps2"][b])):
+            rho, s = PO.density_scale(W32, L[10 * lv:10 * lv + 3], torch.from_numpy(xyz), bw)
+            assert torch.equal(rho, s) and float(rho.min()) > 0, (b, name)
+            rho, s = PO.density_scale(W64, L[10 * lv:10 * lv + 3], torch.from_numpy(xyz).double(), bw)
+            assert float(((s - rho).abs() / rho).max()) <= 1e-7, (b, name)
+            h = torch.from_numpy(PO.density_header(xyz, bw))
+            assert torch.equal(PO.density_net(W32, lv, h), h), (b, name)
+    # density_header against float64, per element and relative, beside the reference's matrix form in float32
+    W = PO.to_torch(w)
+    worst = 0.0
+    for b in range(len(pcs)):
+        for lv, (name, xyz, bw) in enumerate(PO.level_inputs(pcs[b], t["fps1"][b], t["fps2"][b])):
+            r64 = PO.density_f64(xyz, bw)
+            rel_h = np.abs(PO.density_header(xyz, bw) - r64) / r64
+            e_h = float(rel_h.max())
+            e_m = float((np.abs(PO.density_scale(W, L[0:3], torch.from_numpy(xyz), bw)[0].numpy() - r64) / r64).max())
+            print("cloud %d (n = %d) %s: relative error of rho: header form %.2e, matrix form %.2e" % (b, len(pcs[b]), name, e_h, e_m))
+            worst = max(worst, e_h)
+            # To first order, in units of u = 2^-24: the argument carries 7 u (two differences 2 u, the product, two sums, the
+            # division, c1), which moves rho_j by 7 u A_j with A_j the e-weighted mean of |arg| over i; expf 1 u; the sum of
+            # positive terms ceil(n / 64) + 6 additions; the two divisions and c2 3 u.
+            xd = xyz.astype(np.float64)
+            arg = ((xd[None] - xd[:, None]) ** 2).sum(-1) / (2.0 * bw * bw)
+            A = (arg * np.exp(-arg)).sum(-1) / np.exp(-arg).sum(-1)
+            assert (rel_h <= (7 * A + -(-len(xyz) // 64) + 6 + 4) * 2.0 ** -24).all(), (b, name, e_h)
+    print("worst relative error of density_header: %.2e" % worst)
+    # ... and against the reference's recorded densities, at the bar of test_oracle_outputs_against_the_reference
+    for lv in range(3):
+        name = "dens%d" % (lv + 1)
+        e32 = float((o32[name].double() - o64[name]).abs().max())
+        d = 0.0
+        for b in range(len(pcs)):
+            xyz, bw = PO.level_inputs(pcs[b], t["fps1"][b], t["fps2"][b])[lv][1:]
+            s = PO.density_net(W, lv, torch.from_numpy(PO.density_header(xyz, bw))).numpy()
+            d = max(d, float(np.abs(s - g["%s_%d" % (name, b)]).max()))
+        print("%s: density_header through DensityNet vs reference %.3e, e_32 %.3e, ratio %.2f" % (name, d, e32, d / e32))
+        assert d <= 4 * e32
+
+
 def test_calibrated_weights_give_varied_predictions():
     """The calibrated head alone (no GPU): on bench.synth_clouds(64, seed=23)[:, :128] the float64 oracle predicts at least 10
     classes; fc3 alone differs from make_weights."""

@@ -253,6 +253,62 @@ def test_distance_definition():
     assert PO.radius2(0.2).dtype == np.float32
 
 
+def test_wrong_distances_round_differently():
+    """The four wrong distances are what their names say: each stays within a few float32 steps of dist (the matrix form within
+    its cancellation error) and differs from it somewhere on a non-dyadic lattice, and each is 0 on a copy but for the matrix
+    form's bound; the contracted chain is the correctly rounded fma chain."""
+    import pointnet2_oracle as PO
+    from dgcnn_oracle import fma32
+    x = PO.lattice_cloud(3, 12, 400, 0.2 / 3, -0.4)
+    c = x[17]
+    d = PO.dist(x, c)
+    exact = ((x.astype(np.float64) - c.astype(np.float64)) ** 2).sum(1)
+    ulp = np.spacing(np.maximum(d, np.float32(1e-30)))
+    for name, f in PO.DIST_MUTANTS.items():
+        got = f(x, c)
+        assert got.dtype == np.float32 and got.shape == d.shape, name
+        assert np.array_equal(f(x[None, :, :], x[:5, None, :])[3], f(x, x[3])), name      # the grouping's broadcast
+        n_diff = int((got != d).sum())
+        print("%s: %d of %d distances differ from the header's" % (name, n_diff, len(d)))
+        assert n_diff > 0, name
+        if name == "matrix":
+            bound = 2.0 ** -21 * ((x.astype(np.float64) ** 2).sum(1) + float((c.astype(np.float64) ** 2).sum()))
+            assert (np.abs(got - exact) <= bound).all()
+        else:
+            assert (np.abs(got.astype(np.float64) - d) <= 8 * ulp).all(), name        # a sanity bound, not a sharp one
+            assert got[17] == 0
+    dx, dy, dz = (x - c).T
+    assert np.array_equal(PO.dist_contracted(x, c), fma32(dz, dz, fma32(dy, dy, (dx * dx).astype(np.float32))))
+    assert np.array_equal(PO.dist_float64(x, c), exact.astype(np.float32))
+    # the rule mutants on three points at equal distance from the first
+    t = np.array([[0, 0, 0], [1, 0, 0], [0, 1, 0], [0, 0, 1]], np.float32)
+    assert PO.fps(t, 2, 0).tolist() == [0, 1] and PO.fps_highest(t, 2, 0).tolist() == [0, 3]
+    edge = np.array([[0, 0, 0], [np.sqrt(PO.radius2(0.5)), 0, 0]], np.float32)               # 0.5 exactly: d == r2
+    assert PO.ball(0.5, 2, edge, edge[:1]).tolist() == [[0, 1]] and PO.ball(0.5, 2, edge, edge[:1], open_edge=True).tolist() == [[0, 0]]
+
+
+def test_lattice_family_refuses_every_wrong_definition():
+    """The condition the GPU's selection tests rest on (test_gpu_pointnet2.py, section 1b).  With every earlier stage forced to the
+    header's result, every wrong distance changes fps1, fps2, ball1 and ball2, and every rule mutant its own tables, on at least
+    one cloud of LATTICE_FAMILY in each stride class: a GPU that equals the header oracle on the family computes the header's
+    distance and rules, not one of these.  The tie lattice refuses the sampling's rule mutant too; it has no point at d == r2."""
+    import pointnet2_oracle as PO
+    fam = PO.LATTICE_FAMILY
+    assert [f[2] for f in fam] == [20, 33, 100, 300, 512, 513, 1024, 1025, 2048]
+    assert {0.04, 0.2 / 3} <= {f[3] for f in fam}
+    for i, f in enumerate(fam):
+        x = PO.family_cloud(i)[0]
+        assert x.shape == (f[2], 3) and x.dtype == np.float32 and len(np.unique(x, axis=0)) == f[2]      # distinct places
+    tables = ("fps1", "fps2", "ball1", "ball2")
+    cells = PO.certify(range(len(fam)), PO.ball_refusals, tables)
+    want = {(m, t) for m in PO.DIST_MUTANTS for t in tables} | {(PO.RULE_FPS, "fps1"), (PO.RULE_FPS, "fps2"),
+                                                               (PO.RULE_BALL, "ball1"), (PO.RULE_BALL, "ball2")}
+    assert set(cells) == want
+    tie = PO.ball_refusals("dyadic")
+    print("tie lattice:", tie)
+    assert tie[PO.RULE_FPS]["fps1"] > 0 and tie[PO.RULE_FPS]["fps2"] > 0
+
+
 def test_calibrated_weights_give_varied_predictions():
     """The calibrated head alone (no GPU): on bench.synth_clouds(64, seed=23)[:, :128] the float64 oracle predicts at least 10
     classes; fc3 alone differs from make_weights."""
