@@ -327,6 +327,25 @@ DGCNN_SIGNATURES = {
                                     C.c_void_p]),
 }
 
+# include/ifd_dgcnn_atk.h (input gradients of the DGCNN victim and the FGM family on it), versioned on its own
+DGCNN_ATK_ABI_VERSION = 1
+
+
+class IfdDgcnnGradOut(C.Structure):
+    _fields_ = [("logits", C.c_void_p), ("loss", C.c_void_p), ("pred", C.c_void_p), ("idx", C.c_void_p * 4), ("feat", C.c_void_p),
+                ("global_feat", C.c_void_p), ("win_pool", C.c_void_p), ("win_edge", C.c_void_p * 4), ("act5", C.c_void_p)]
+
+
+DGCNN_ATK_SIGNATURES = {
+    "ifd_dgcnn_atk_abi_version": (C.c_int, []),
+    "ifd_dgcnn_input_grad": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_float, C.c_float,
+                                       C.c_void_p, C.POINTER(IfdDgcnnGradOut), C.c_void_p]),
+    "ifd_dgcnn_fgm_update": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_float,
+                                       C.c_float, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
+    "ifd_dgcnn_fgm_attack": (C.c_int, [C.c_void_p, C.POINTER(IfdFgmParams), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int,
+                                       C.c_void_p, C.c_void_p, C.c_void_p]),
+}
+
 # include/ifd_pn2.h (the PointNet++ victim classifier), versioned on its own
 PN2_ABI_VERSION = 1
 PN2_MAX_POINTS = 2048
@@ -384,7 +403,8 @@ def load() -> C.CDLL:
     for name, (res, args) in list(SIGNATURES.items()) + list(DUP_SIGNATURES.items()) + list(CLS_SIGNATURES.items()) + \
             list(ATK_SIGNATURES.items()) + list(CW_SIGNATURES.items()) + list(KNN_SIGNATURES.items()) + list(ADD_SIGNATURES.items()) + \
             list(DROP_SIGNATURES.items()) + list(CLUSTER_SIGNATURES.items()) + list(OBJECT_SIGNATURES.items()) + \
-            list(DGCNN_SIGNATURES.items()) + list(PN2_SIGNATURES.items()) + list(PC_SIGNATURES.items()):
+            list(DGCNN_SIGNATURES.items()) + list(DGCNN_ATK_SIGNATURES.items()) + list(PN2_SIGNATURES.items()) + \
+            list(PC_SIGNATURES.items()):
         fn = getattr(lib, name)          # AttributeError if the library lacks a declared symbol
         fn.restype, fn.argtypes = res, args
     if lib.ifd_abi_version() != ABI_VERSION:
@@ -409,6 +429,9 @@ def load() -> C.CDLL:
         raise ImportError("libifd.so OBJECT ABI %d != binding OBJECT ABI %d; rebuild" % (lib.ifd_object_abi_version(), OBJECT_ABI_VERSION))
     if lib.ifd_dgcnn_abi_version() != DGCNN_ABI_VERSION:
         raise ImportError("libifd.so DGCNN ABI %d != binding DGCNN ABI %d; rebuild" % (lib.ifd_dgcnn_abi_version(), DGCNN_ABI_VERSION))
+    if lib.ifd_dgcnn_atk_abi_version() != DGCNN_ATK_ABI_VERSION:
+        raise ImportError("libifd.so DGCNN ATK ABI %d != binding DGCNN ATK ABI %d; rebuild" %
+                          (lib.ifd_dgcnn_atk_abi_version(), DGCNN_ATK_ABI_VERSION))
     if lib.ifd_pn2_abi_version() != PN2_ABI_VERSION:
         raise ImportError("libifd.so PN2 ABI %d != binding PN2 ABI %d; rebuild" % (lib.ifd_pn2_abi_version(), PN2_ABI_VERSION))
     if lib.ifd_pc_abi_version() != PC_ABI_VERSION:

@@ -15,6 +15,7 @@
 #include "../../include/ifd_cluster.h"
 #include "../../include/ifd_object.h"
 #include "../../include/ifd_dgcnn.h"
+#include "../../include/ifd_dgcnn_atk.h"
 #include "../../include/ifd_pc.h"
 #include "../../include/ifd_pn2.h"
 
@@ -154,6 +155,7 @@ struct ifd_ctx {
     DeviceBuffer d_cls_grad;
     ClsGradImage gimg{};
     DgImage dimg{};                // DGCNN: the edge convolutions in split form
+    DgGradImage dgimg{};           // ... and its backward pass's image, in d_cls_grad (include/ifd_dgcnn_atk.h)
     int dg_k = 0;
     Pn2Image p2img{};
     PcImage pcimg{};               // PointConv (pointconv.hip)
@@ -1792,29 +1794,45 @@ DgWs dgcnn_ws(Carve& c, size_t n, int stride, int k) {
 }
 size_t dgcnn_ws_bytes(int n, int stride, int k) { return carved_bytes([&](Carve& c) { dgcnn_ws(c, (size_t)n, stride, k); }); }
 
-}  // namespace
-
-extern "C" {
-
-int ifd_dgcnn_abi_version(void) { return IFD_DGCNN_ABI_VERSION; }
-
-size_t ifd_dgcnn_weight_count(void) { return dgcnn_count(); }
-
-ifd_ctx* ifd_dgcnn_create(const float* weights_host, size_t n_weights, int k, int n_classes, int device) {
-    if (k < 1 || k > IFD_DGCNN_MAX_K) {
-        g_create_error = "ifd_dgcnn_create: k must lie in [1, 32], got " + std::to_string(k);
-        return nullptr;
-    }
-    if (!victim_create_args_ok("ifd_dgcnn_create", weights_host, n_weights, dgcnn_count(), n_classes)) return nullptr;
-    return create_ctx("ifd_dgcnn_create", IFD_MODEL_DGCNN, device, [&](ifd_ctx* ctx) {
-        ctx->dg_k = k;
-        ctx->cls_classes = n_classes;
-        return upload(ctx->d_victim, build_dgcnn_image(weights_host, ctx->dimg));
-    });
+// The backward pass's image (ifd_internal.h DgGradImage) from the forward's: every layer transposed, one block of zeros as the bias of all.
+std::vector<float> build_dgcnn_grad_image(const std::vector<float>& f, const DgImage& I, DgGradImage& G) {
+    std::vector<float> img(2 * DG_EMB, 0.f);                           // the zero bias
+    // rows [n_in of L][n_out of L, padded with zeros to pad_out]
+    auto transposed = [&](const DenseLayer& L, int pad_out) {
+        DenseLayer T;
+        T.n_out = L.n_in; T.n_in = pad_out; T.b = 0;
+        T.w = (int)img.size();
+        img.resize(img.size() + (size_t)L.n_in * pad_out, 0.f);
+        for (int o = 0; o < L.n_out; ++o)
+            for (int c = 0; c < L.n_in; ++c) img[T.w + (size_t)c * pad_out + o] = f[L.w + (size_t)o * L.n_in + c];
+        return T;
+    };
+    for (int j = 0; j < 3; ++j) G.fct[j] = transposed(I.fc[j], (I.fc[j].n_out + 63) / 64 * 64);
+    for (int l = 0; l < 3; ++l) G.pqt[l] = transposed(I.pq[l], I.pq[l].n_out);
+    G.w5t = transposed(I.conv5, I.conv5.n_out).w;
+    G.total = (int)img.size();
+    return img;
 }
 
-int ifd_dgcnn_forward(ifd_ctx* ctx, const float* pc, const int32_t* n_points, int B, int stride, float* logits,
-                      const ifd_dgcnn_aux* aux, void* stream) {
+// the workspace of ifd_dgcnn_input_grad over n clouds: ifd_dgcnn_forward's (whose first 1024 bytes the check uses), then the backward's
+DgGradWs dgcnn_grad_ws(Carve& c, size_t n, int stride, int k) {
+    const size_t s = (size_t)stride;
+    DgGradWs w;
+    w.f = dgcnn_ws(c, n, stride, k);
+    c.round_up(256);
+    w.dfeat = c.take<float>(n * s * DG_FEAT * 4); w.dx = c.take<float>(n * s * 128 * 4); w.win = c.take<int32_t>(n * s * 256 * 4);
+    w.logits = c.take<float>(n * 160); w.d_out = c.take<float>(n * 256); w.d2 = c.take<float>(n * 1024); w.d1 = c.take<float>(n * 2048);
+    w.g = c.take<float>(n * 2 * DG_EMB * 4);
+    w.wtile = c.take<int32_t>(n * DG_EMB * 4); w.win_pool = c.take<int32_t>(n * DG_EMB * 4);
+    for (int l = 0; l < 4; ++l) w.idx[l] = c.take<int32_t>(n * s * k * 4);
+    w.pred = c.take<int32_t>(n * 4); w.loss = c.take<float>(n * 4);
+    return w;
+}
+
+// ifd_dgcnn_forward; check_counts = false skips the blocking check (the caller has made it), ws_off: bytes at the front of the
+// workspace that belong to the caller (ifd_dgcnn_fgm_attack's loop state)
+int dgcnn_forward_impl(ifd_ctx* ctx, const float* pc, const int32_t* n_points, int B, int stride, float* logits,
+                       const ifd_dgcnn_aux* aux, void* stream, bool check_counts, size_t ws_off) {
     if (!ctx) return IFD_ERR_ARG;
     if (ctx->model != IFD_MODEL_DGCNN || !ctx->d_victim.get()) return fail(ctx, IFD_ERR_ARG, "ifd_dgcnn_forward: not a DGCNN context");
     const int k = ctx->dg_k;
@@ -1827,9 +1845,9 @@ int ifd_dgcnn_forward(ifd_ctx* ctx, const float* pc, const int32_t* n_points, in
     hipStream_t s = static_cast<hipStream_t>(stream);
     const int nc = ctx->cls_classes;
     return victim_forward(
-        ctx, "ifd_dgcnn_forward", B, DG_CHUNK, 0, [&](int chunk) { return dgcnn_ws_bytes(chunk, stride, k); },
+        ctx, "ifd_dgcnn_forward", B, DG_CHUNK, ws_off, [&](int chunk) { return dgcnn_ws_bytes(chunk, stride, k); },
         [&](char* base) {
-            if (!n_points) return (int)IFD_OK;
+            if (!n_points || !check_counts) return (int)IFD_OK;
             int32_t bad = 0;
             if (int rc = read_bad_counts(ctx, "ifd_dgcnn_forward", "n_points",
                                          launch_count_check(n_points, B, k, stride, reinterpret_cast<int32_t*>(base), s), base, 1, &bad, s))
@@ -1851,6 +1869,35 @@ int ifd_dgcnn_forward(ifd_ctx* ctx, const float* pc, const int32_t* n_points, in
             return launch_dgcnn(ctx->d_victim.get<float>(), ctx->dimg, pc + (size_t)c0 * stride * 3, n_points ? n_points + c0 : nullptr, n,
                                 stride, k, w, o, logits + (size_t)c0 * nc, nc, s);
         });
+}
+
+}  // namespace
+
+extern "C" {
+
+int ifd_dgcnn_abi_version(void) { return IFD_DGCNN_ABI_VERSION; }
+
+size_t ifd_dgcnn_weight_count(void) { return dgcnn_count(); }
+
+ifd_ctx* ifd_dgcnn_create(const float* weights_host, size_t n_weights, int k, int n_classes, int device) {
+    if (k < 1 || k > IFD_DGCNN_MAX_K) {
+        g_create_error = "ifd_dgcnn_create: k must lie in [1, 32], got " + std::to_string(k);
+        return nullptr;
+    }
+    if (!victim_create_args_ok("ifd_dgcnn_create", weights_host, n_weights, dgcnn_count(), n_classes)) return nullptr;
+    return create_ctx("ifd_dgcnn_create", IFD_MODEL_DGCNN, device, [&](ifd_ctx* ctx) {
+        ctx->dg_k = k;
+        ctx->cls_classes = n_classes;
+        const std::vector<float> img = build_dgcnn_image(weights_host, ctx->dimg);
+        hipError_t e = upload(ctx->d_victim, img);
+        if (e == hipSuccess) e = upload(ctx->d_cls_grad, build_dgcnn_grad_image(img, ctx->dimg, ctx->dgimg));
+        return e;
+    });
+}
+
+int ifd_dgcnn_forward(ifd_ctx* ctx, const float* pc, const int32_t* n_points, int B, int stride, float* logits,
+                      const ifd_dgcnn_aux* aux, void* stream) {
+    return dgcnn_forward_impl(ctx, pc, n_points, B, stride, logits, aux, stream, true, 0);
 }
 
 }  // extern "C"
@@ -2383,6 +2430,149 @@ int ifd_fgm_attack(ifd_ctx* ctx, const ifd_fgm_params* params, const float* pc_i
         if (e != hipSuccess) return fail(ctx, IFD_ERR_HIP, "ifd_fgm_attack: update", e);
     }
     return atk_final_success(ctx, "ifd_fgm_attack", pc_out, n_points, B, stride, logits, pred, target, success, state, s);
+}
+
+}  // extern "C"
+
+// ---- attacks on the DGCNN victim (include/ifd_dgcnn_atk.h) -------------------------------------------------------------
+namespace {
+
+constexpr int DG_ATK_CHUNK = DG_CHUNK;       // most clouds per chunk of ifd_dgcnn_input_grad: the forward's (two chunks of 64 cost its kNN kernels 1.5 x one of 128)
+
+int dg_atk_context_ok(ifd_ctx* ctx, const char* who) {
+    if (ctx->model != IFD_MODEL_DGCNN || !ctx->d_victim.get() || !ctx->d_cls_grad.get())
+        return fail(ctx, IFD_ERR_ARG, (std::string(who) + ": not a DGCNN context").c_str());
+    return IFD_OK;
+}
+// the strides a DGCNN call takes: k <= stride <= 2048
+int dg_atk_stride_ok(ifd_ctx* ctx, const char* who, int stride) {
+    if (stride >= ctx->dg_k && stride <= IFD_DGCNN_MAX_POINTS) return IFD_OK;
+    return fail(ctx, IFD_ERR_ARG, (std::string(who) + ": stride " + std::to_string(stride) + " outside [k, 2048] (k = " +
+                                   std::to_string(ctx->dg_k) + ")").c_str());
+}
+
+int dg_atk_chunk(int B) {
+    const int n_chunks = (B + DG_ATK_CHUNK - 1) / DG_ATK_CHUNK;
+    return (B + n_chunks - 1) / n_chunks;
+}
+size_t dg_grad_ws_bytes(int B, int stride, int k) {
+    return carved_bytes([&](Carve& c) { dgcnn_grad_ws(c, (size_t)dg_atk_chunk(B), stride, k); });
+}
+// workspace of ifd_dgcnn_fgm_attack: its state in front of the gradient's and the final forward's
+size_t dg_loop_ws_bytes(int B, int stride, int k, size_t state_bytes) {
+    const int fwd_chunks = (B + DG_CHUNK - 1) / DG_CHUNK;
+    return state_bytes + std::max(dg_grad_ws_bytes(B, stride, k), dgcnn_ws_bytes((B + fwd_chunks - 1) / fwd_chunks, stride, k));
+}
+
+// ifd_dgcnn_input_grad on workspace that is already large enough (ws_off: bytes in front that belong to the caller), unchecked
+int dg_input_grad_impl(ifd_ctx* ctx, size_t ws_off, const float* pc, const int32_t* n_points, int B, int stride, const int32_t* target,
+                       int loss_kind, float kappa, float scale, float* grad, const ifd_dgcnn_grad_out* out, hipStream_t s) {
+    const int chunk = dg_atk_chunk(B), nc = ctx->cls_classes, k = ctx->dg_k;
+    static const int cout[4] = {64, 64, 128, 256};
+    for (int c0 = 0; c0 < B; c0 += chunk) {
+        const size_t n = (size_t)std::min(chunk, B - c0), st = (size_t)stride;
+        Carve c(ctx->ws.get<char>() + ws_off);
+        const DgGradWs w = dgcnn_grad_ws(c, n, stride, k);
+        DgGradOut o{};
+        if (out) {
+            for (int l = 0; l < 4; ++l) {
+                o.idx[l] = out->idx[l] ? out->idx[l] + (size_t)c0 * st * k : nullptr;
+                o.win_edge[l] = out->win_edge[l] ? out->win_edge[l] + (size_t)c0 * st * cout[l] : nullptr;
+            }
+            o.feat = out->feat ? out->feat + (size_t)c0 * st * DG_FEAT : nullptr;
+            o.act5 = out->act5 ? out->act5 + (size_t)c0 * st * (DG_EMB / 32) : nullptr;
+        }
+        hipError_t e = launch_dgcnn_grad(ctx->d_victim.get<float>(), ctx->dimg, ctx->d_cls_grad.get<float>(), ctx->dgimg, pc + (size_t)c0 * st * 3,
+                                         n_points ? n_points + c0 : nullptr, (int)n, stride, k, target + c0, loss_kind, kappa, scale, w, o, nc,
+                                         grad + (size_t)c0 * st * 3, s);
+        auto copy = [&](void* dst, const void* src, size_t bytes_per_cloud) {
+            if (e == hipSuccess && dst)
+                e = hipMemcpyAsync(static_cast<char*>(dst) + (size_t)c0 * bytes_per_cloud, src, n * bytes_per_cloud, hipMemcpyDeviceToDevice, s);
+        };
+        if (out) {
+            copy(out->logits, w.logits, 160);
+            copy(out->loss, w.loss, 4);
+            copy(out->pred, w.pred, 4);
+            copy(out->global_feat, w.f.gfeat, 2 * DG_EMB * 4);
+            copy(out->win_pool, w.win_pool, DG_EMB * 4);
+        }
+        if (e != hipSuccess) return fail(ctx, IFD_ERR_HIP, "ifd_dgcnn_input_grad launch", e);
+    }
+    return IFD_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int ifd_dgcnn_atk_abi_version(void) { return IFD_DGCNN_ATK_ABI_VERSION; }
+
+int ifd_dgcnn_input_grad(ifd_ctx* ctx, const float* pc, const int32_t* n_points, int B, int stride, const int32_t* target, int loss_kind,
+                         float kappa, float scale, float* grad, const ifd_dgcnn_grad_out* out, void* stream) {
+    if (!ctx) return IFD_ERR_ARG;
+    if (int rc = dg_atk_context_ok(ctx, "ifd_dgcnn_input_grad")) return rc;
+    if (!pc || !target || !grad || B < 1) return fail(ctx, IFD_ERR_ARG, "ifd_dgcnn_input_grad: bad argument (pc, target, grad; B >= 1)");
+    if (int rc = dg_atk_stride_ok(ctx, "ifd_dgcnn_input_grad", stride)) return rc;
+    if (!atk_loss_ok(loss_kind)) return fail(ctx, IFD_ERR_ARG, "ifd_dgcnn_input_grad: unknown loss_kind");
+    IFD_ON_CTX_DEVICE(ctx);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    hipError_t e = ctx->ws.grow(dg_grad_ws_bytes(B, stride, ctx->dg_k));
+    if (e != hipSuccess) return fail(ctx, IFD_ERR_NOMEM, "ifd_dgcnn_input_grad: workspace", e);
+    if (int rc = atk_check(ctx, "ifd_dgcnn_input_grad", n_points, target, B, ctx->dg_k, stride, "[k, stride]", s)) return rc;
+    return dg_input_grad_impl(ctx, 0, pc, n_points, B, stride, target, loss_kind, kappa, scale, grad, out, s);
+}
+
+int ifd_dgcnn_fgm_update(ifd_ctx* ctx, int kind, const float* grad, float* pc, const float* ori_pc, float* momentum, float step_size,
+                         float budget, float mu, const int32_t* n_points, int B, int stride, void* stream) {
+    if (!ctx) return IFD_ERR_ARG;
+    if (int rc = dg_atk_context_ok(ctx, "ifd_dgcnn_fgm_update")) return rc;
+    if (!atk_kind_ok(kind)) return fail(ctx, IFD_ERR_ARG, "ifd_dgcnn_fgm_update: unknown kind");
+    if (!grad || !pc || B < 1 || stride < 1 || stride > IFD_DGCNN_MAX_POINTS || (kind != IFD_FGM_FGM && !ori_pc) ||
+        (kind == IFD_FGM_MIFGM && !momentum))
+        return fail(ctx, IFD_ERR_ARG, "ifd_dgcnn_fgm_update: bad argument (grad, pc; ori_pc unless FGM; momentum for MIFGM; 1 <= stride <= 2048)");
+    IFD_ON_CTX_DEVICE(ctx);
+    hipError_t e = launch_fgm_update(kind, grad, pc, ori_pc, momentum, step_size, budget, mu, n_points, B, stride,
+                                     static_cast<hipStream_t>(stream));
+    if (e != hipSuccess) return fail(ctx, IFD_ERR_HIP, "ifd_dgcnn_fgm_update launch", e);
+    return IFD_OK;
+}
+
+int ifd_dgcnn_fgm_attack(ifd_ctx* ctx, const ifd_fgm_params* params, const float* pc_in, const int32_t* n_points, const int32_t* target,
+                         int B, int stride, float* pc_out, int32_t* success, void* stream) {
+    if (!ctx) return IFD_ERR_ARG;
+    if (int rc = dg_atk_context_ok(ctx, "ifd_dgcnn_fgm_attack")) return rc;
+    if (!params || params->struct_size != (int32_t)sizeof(ifd_fgm_params))
+        return fail(ctx, IFD_ERR_ARG, "ifd_dgcnn_fgm_attack: params missing or of another struct_size");
+    if (!atk_kind_ok(params->kind) || !atk_loss_ok(params->loss_kind) || params->num_iter < 1)
+        return fail(ctx, IFD_ERR_ARG, "ifd_dgcnn_fgm_attack: unknown kind or loss_kind, or num_iter < 1");
+    if (!pc_in || !target || !pc_out || !success || pc_in == pc_out || B < 1)
+        return fail(ctx, IFD_ERR_ARG, "ifd_dgcnn_fgm_attack: bad argument (pc_in, target, pc_out, success; B >= 1)");
+    if (int rc = dg_atk_stride_ok(ctx, "ifd_dgcnn_fgm_attack", stride)) return rc;
+    IFD_ON_CTX_DEVICE(ctx);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const size_t cloud = (size_t)stride * 12, state = carved_bytes([&](Carve& c) { FgmLoop(c, (size_t)B, cloud); });
+    hipError_t e = ctx->ws.grow(dg_loop_ws_bytes(B, stride, ctx->dg_k, state));
+    if (e != hipSuccess) return fail(ctx, IFD_ERR_NOMEM, "ifd_dgcnn_fgm_attack: workspace", e);
+    if (int rc = atk_check(ctx, "ifd_dgcnn_fgm_attack", n_points, target, B, ctx->dg_k, stride, "[k, stride]", s)) return rc;
+    Carve c(ctx->ws.get());
+    const FgmLoop L(c, (size_t)B, cloud);
+    e = hipMemcpyAsync(pc_out, pc_in, (size_t)B * cloud, hipMemcpyDeviceToDevice, s);
+    if (e == hipSuccess && params->kind == IFD_FGM_MIFGM) e = hipMemsetAsync(L.mom, 0, (size_t)B * cloud, s);
+    if (e != hipSuccess) return fail(ctx, IFD_ERR_HIP, "ifd_dgcnn_fgm_attack: start", e);
+    const int iters = params->kind == IFD_FGM_FGM ? 1 : params->num_iter;
+    for (int it = 0; it < iters; ++it) {
+        if (int rc = dg_input_grad_impl(ctx, state, pc_out, n_points, B, stride, target, params->loss_kind, params->kappa, params->scale,
+                                        L.grad, nullptr, s))
+            return rc;
+        e = launch_fgm_update(params->kind, L.grad, pc_out, pc_in, L.mom, params->step_size, params->budget, params->mu, n_points, B, stride, s);
+        if (e != hipSuccess) return fail(ctx, IFD_ERR_HIP, "ifd_dgcnn_fgm_attack: update", e);
+    }
+    ifd_dgcnn_aux aux{};
+    aux.pred = L.pred;
+    if (int rc = dgcnn_forward_impl(ctx, pc_out, n_points, B, stride, L.logits, &aux, stream, false, state)) return rc;
+    e = launch_atk_success(L.pred, target, B, success, s);
+    if (e != hipSuccess) return fail(ctx, IFD_ERR_HIP, "ifd_dgcnn_fgm_attack: success", e);
+    return IFD_OK;
 }
 
 }  // extern "C"

@@ -200,6 +200,15 @@ void launch_knn(const float* X, int ldx, size_t xb, const int32_t* n_points, int
 
 }  // namespace
 
+hipError_t launch_dg_pq(const float* img, const DgImage& I, int l, const float* pc, const float* feat, const int32_t* n_points, int B,
+                        int stride, float* pq, hipStream_t s) {
+    const size_t fb = (size_t)stride * DG_FEAT;
+    const int col_in[4] = {0, 0, 64, 128};
+    if (l == 0) hipLaunchKernelGGL(dg_first_kernel, dim3((stride + 7) / 8, B), dim3(256), 0, s, img + I.first, pc, n_points, stride, pq);
+    else launch_linear<DgLinear>(img, I.pq[l - 1], feat + col_in[l], DG_FEAT, fb, n_points, B, stride, pq, DG_FEAT, fb, 0, s);
+    return hipGetLastError();
+}
+
 hipError_t launch_dgcnn(const float* img, const DgImage& I, const float* pc, const int32_t* n_points, int B, int stride, int k,
                         const DgWs& w, const DgOut& out, float* logits, int n_classes, hipStream_t s) {
     float* feat = out.feat ? out.feat : w.feat;

@@ -456,6 +456,49 @@ struct DgOut {                          // where the caller wants the intermedia
 hipError_t launch_dgcnn(const float* img, const DgImage& I, const float* pc, const int32_t* n_points, int B, int stride, int k,
                         const DgWs& w, const DgOut& out, float* logits, int n_classes, hipStream_t s);
 
+// P | Q of edge convolution l + 1 (l = 0 .. 3) recomputed into w.pq from pc (l = 0) or from feat's columns, by the forward's kernels
+hipError_t launch_dg_pq(const float* img, const DgImage& I, int l, const float* pc, const float* feat, const int32_t* n_points, int B,
+                        int stride, float* pq, hipStream_t s);
+
+// ---- DGCNN input gradients (dgcnn_grad.hip; C ABI in include/ifd_dgcnn_atk.h) ------------------------------------------
+// The backward pass's weight image (api.cpp build_dgcnn_grad_image): every layer transposed, row-major [n_in of the forward][n_out
+// of the forward], as a DenseLayer of linear_kernel whose bias is a shared block of zeros.  fct[2] (linear3) has its 40 inputs
+// padded to 64 with zero columns.
+struct DgGradImage {
+    DenseLayer fct[3];                  // linear1^T [2048][512], linear2^T [512][256], linear3^T [256][64]
+    DenseLayer pqt[3];                  // conv2 .. conv4: [P ; Q]^T, [C][2 Cout]
+    int w5t;                            // conv5^T [512][1024]
+    int total;
+};
+struct DgGradWs {                       // per-chunk scratch of launch_dgcnn_grad (api.cpp dgcnn_grad_ws)
+    DgWs f;                             // the forward's
+    int32_t* idx[4];    // [B][stride][k] each
+    float* logits;      // [B][40]
+    int32_t* pred;      // [B]
+    float* loss;        // [B]
+    float* d_out;       // [B][64]
+    float* d2;          // [B][256]
+    float* d1;          // [B][512]
+    float* g;           // [B][2048]      d loss / d (max | mean)
+    int32_t* wtile;     // [B][1024]      the first tile whose maximum is the cloud's
+    int32_t* win_pool;  // [B][1024]
+    float* dfeat;       // [B][stride][512]
+    float* dx;          // [B][stride][128]
+    int32_t* win;       // [B][stride][256]
+};
+struct DgGradOut {                      // ifd_dgcnn_grad_out's members that the kernels write themselves, so that rows beyond a
+    int32_t* idx[4];                    // cloud stay as they were; null: not wanted (idx and feat then stay in the scratch)
+    float* feat;
+    int32_t* win_edge[4];
+    uint32_t* act5;
+};
+hipError_t launch_dgcnn_grad(const float* img, const DgImage& I, const float* gimg, const DgGradImage& G, const float* pc,
+                             const int32_t* n_points, int B, int stride, int k, const int32_t* target, int loss_kind, float kappa,
+                             float scale, const DgGradWs& w, const DgGradOut& out, int n_classes, float* grad, hipStream_t s);
+// loss [B] and d_out [B][64] = scale * d loss / d logits (zeros behind the classes), the losses of include/ifd_atk.h (pointnet_grad.hip)
+hipError_t launch_loss_grad(const float* logits, const int32_t* target, int B, int n_classes, int loss_kind, float kappa, float scale,
+                            float* loss, float* d_out, hipStream_t s);
+
 // ---- victim classifier: PointNet++ (pointnet2.hip; C ABI in include/ifd_pn2.h) ----------------------------------------
 constexpr int PN2_MAX_POINTS = 2048;    // IFD_PN2_MAX_POINTS
 constexpr int PN2_NP1 = 512, PN2_NS1 = 32;      // sa1: centroids, samples of a ball

@@ -336,6 +336,13 @@ hipError_t launch_cls_backward(const float* img, const ClsImage& I, const float*
     return hipGetLastError();
 }
 
+hipError_t launch_loss_grad(const float* logits, const int32_t* target, int B, int n_classes, int loss_kind, float kappa, float scale,
+                            float* loss, float* d_out, hipStream_t s) {
+    hipLaunchKernelGGL(loss_grad_kernel, dim3((B + 255) / 256), dim3(256), 0, s, logits, target, B, n_classes, loss_kind, kappa, scale, loss,
+                       d_out);
+    return hipGetLastError();
+}
+
 hipError_t launch_fgm_update(int kind, const float* grad, float* pc, const float* ori_pc, float* momentum, float step_size, float budget,
                              float mu, const int32_t* n_points, int B, int stride, hipStream_t s) {
     hipLaunchKernelGGL(fgm_update_kernel, dim3(B), dim3(256), 0, s, kind, grad, pc, ori_pc, momentum, step_size, budget, mu, n_points,

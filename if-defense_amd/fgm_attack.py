@@ -44,14 +44,14 @@ def save_path(out_dir, dataset, num_points, model, attack_type, delta, num_iter,
     return d, name
 
 
-def main(argv=None, make_classifier=None) -> int:
+def attack_file(prog, args, open_classifier, check_data=None) -> int:
+    """The script behind its refusals, shared with dgcnn_fgm_attack: the settings, the data file, the victim that
+    ``open_classifier()`` makes, the batches and the result file.  ``check_data(data)``: a message where the clouds [N,K,3]
+    cannot be attacked (status 2, before the victim is made), else None."""
     from .attack import ATTACKS
-    args = build_parser().parse_args(argv)
-    if C.refuse_unbuilt('fgm_attack', args):
-        return 2
     kind = args.attack_type.lower()
     if kind not in ATTACKS:
-        print("fgm_attack: unknown --attack_type {} (fgm | ifgm | mifgm | pgd)".format(args.attack_type), file=sys.stderr)
+        print("{}: unknown --attack_type {} (fgm | ifgm | mifgm | pgd)".format(prog, args.attack_type), file=sys.stderr)
         return 2
     print(args)
     delta = args.budget
@@ -60,7 +60,11 @@ def main(argv=None, make_classifier=None) -> int:
     npz = np.load(args.data_root)
     data = C.load_points(npz, args.num_points)
     label, target = C.load_labels(npz)
-    classifier = C.open_classifier(args, make_classifier)
+    why = check_data(data) if check_data else None
+    if why:
+        print("{}: {}".format(prog, why), file=sys.stderr)
+        return 2
+    classifier = open_classifier()
     try:
         kw = dict(kappa=args.kappa, seed=args.seed)
         if kind == 'fgm':
@@ -76,6 +80,13 @@ def main(argv=None, make_classifier=None) -> int:
     d, name = save_path(args.out_dir, args.dataset, args.num_points, args.model, kind, delta, num_iter, rate, args.local_rank)
     C.save_npz(d, name, adv, label, target)
     return 0
+
+
+def main(argv=None, make_classifier=None) -> int:
+    args = build_parser().parse_args(argv)
+    if C.refuse_unbuilt('fgm_attack', args):
+        return 2
+    return attack_file('fgm_attack', args, lambda: C.open_classifier(args, make_classifier))
 
 
 if __name__ == '__main__':

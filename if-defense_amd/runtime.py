@@ -800,6 +800,18 @@ class Classifier:
     def _stream(self):
         return torch.cuda.current_stream(self.device).cuda_stream
 
+    # the library calls behind input_grad, fgm_update and fgm_attack; a victim with its own (DgcnnClassifier) names them here
+    ATK_FNS = {"input_grad": "ifd_cls_input_grad", "fgm_update": "ifd_fgm_update", "fgm_attack": "ifd_fgm_attack"}
+
+    def _grad_aux(self, B, stride):
+        """-> (the diagnostics of input_grad as a dict of device tensors, the library's struct pointing at them)."""
+        f, i = torch.float32, torch.int32
+        aux = {"logits": torch.empty(B, self.N_CLASSES, device=self.device, dtype=f), "loss": torch.empty(B, device=self.device, dtype=f),
+               "pred": torch.empty(B, device=self.device, dtype=i), "win_feat": torch.empty(B, 1024, device=self.device, dtype=i),
+               "win_stn": torch.empty(B, 1024, device=self.device, dtype=i),
+               "global_feat": torch.empty(B, 1024, device=self.device, dtype=f)}
+        return aux, _lib.IfdAtkOut(*[aux[k].data_ptr() for k in ("logits", "loss", "pred", "win_feat", "win_stn", "global_feat")])
+
     def input_grad(self, pc, target, loss="logits", kappa=0., scale=1., n_points=None, want_aux: bool = False):
         """scale * d loss_b / d pc[b] of an adversarial loss on the logits (FGM.get_gradient without its normalisation):
         grad [B,N,3], zeros in the rows beyond a cloud's points.  pc: as ``logits`` takes it, ragged lists included; target [B].
@@ -814,16 +826,12 @@ class Classifier:
         grad = torch.empty(B, stride, 3, device=self.device, dtype=torch.float32)
         aux, st = None, None
         if want_aux:
-            f, i = torch.float32, torch.int32
-            aux = {"logits": torch.empty(B, self.N_CLASSES, device=self.device, dtype=f), "loss": torch.empty(B, device=self.device, dtype=f),
-                   "pred": torch.empty(B, device=self.device, dtype=i), "win_feat": torch.empty(B, 1024, device=self.device, dtype=i),
-                   "win_stn": torch.empty(B, 1024, device=self.device, dtype=i),
-                   "global_feat": torch.empty(B, 1024, device=self.device, dtype=f)}
-            st = C.byref(_lib.IfdAtkOut(*[aux[k].data_ptr() for k in ("logits", "loss", "pred", "win_feat", "win_stn", "global_feat")]))
+            aux, struct = self._grad_aux(B, stride)
+            st = C.byref(struct)
         with torch.cuda.device(self.device):
-            self._check(self.lib.ifd_cls_input_grad(self.ctx, pc.data_ptr(), None if n_points is None else n_points.data_ptr(), B, stride,
-                                                    target.data_ptr(), kind, float(kappa), float(scale), grad.data_ptr(), st,
-                                                    self._stream()))
+            self._check(getattr(self.lib, self.ATK_FNS["input_grad"])(
+                self.ctx, pc.data_ptr(), None if n_points is None else n_points.data_ptr(), B, stride, target.data_ptr(), kind,
+                float(kappa), float(scale), grad.data_ptr(), st, self._stream()))
         return (grad, aux) if want_aux else grad
 
     def fgm_update(self, kind, grad, pc, ori_pc=None, momentum=None, step_size=0., budget=0., mu=1., n_points=None):
@@ -837,8 +845,9 @@ class Classifier:
         n_points = self._counts(n_points, B)
         ptr = lambda t: None if t is None else t.data_ptr()        # noqa: E731
         with torch.cuda.device(self.device):
-            self._check(self.lib.ifd_fgm_update(self.ctx, self.FGM_KINDS[kind], ptr(grad), ptr(pc), ptr(ori_pc), ptr(momentum),
-                                                float(step_size), float(budget), float(mu), ptr(n_points), B, stride, self._stream()))
+            self._check(getattr(self.lib, self.ATK_FNS["fgm_update"])(
+                self.ctx, self.FGM_KINDS[kind], ptr(grad), ptr(pc), ptr(ori_pc), ptr(momentum), float(step_size), float(budget), float(mu),
+                ptr(n_points), B, stride, self._stream()))
         return pc
 
     def fgm_attack(self, kind, pc, target, budget, step_size, num_iter=1, mu=1., loss="logits", kappa=0., scale=1., n_points=None):
@@ -857,8 +866,9 @@ class Classifier:
         P = _lib.IfdFgmParams(C.sizeof(_lib.IfdFgmParams), self.FGM_KINDS[kind], loss_kind, int(num_iter), float(kappa), float(scale),
                               float(step_size), float(budget), float(mu))
         with torch.cuda.device(self.device):
-            self._check(self.lib.ifd_fgm_attack(self.ctx, C.byref(P), pc.data_ptr(), None if n_points is None else n_points.data_ptr(),
-                                                target.data_ptr(), B, stride, out.data_ptr(), success.data_ptr(), self._stream()))
+            self._check(getattr(self.lib, self.ATK_FNS["fgm_attack"])(
+                self.ctx, C.byref(P), pc.data_ptr(), None if n_points is None else n_points.data_ptr(), target.data_ptr(), B, stride,
+                out.data_ptr(), success.data_ptr(), self._stream()))
         return out, success.bool()
 
     # ---- include/ifd_cw.h: the CW point-perturbation attack (models without feature_transform) ----
@@ -1453,9 +1463,16 @@ class DgcnnClassifier(Classifier):
     mode.  ``weights``: the BN-folded canonical vector (``weights.load_checkpoint(path, "dgcnn")`` or
     ``weights.pack_state_dict(state_dict, "dgcnn")``).  Inputs are Classifier's: [B,N,3] batches (point-major), lists and
     object arrays of ragged clouds; every cloud needs at least k points and at most 2048.  A cloud's outputs do not depend on
-    how it is batched or padded.  The attack entry points of Classifier are PointNet's and are not offered here."""
+    how it is batched or padded.
+
+    Of the attack entry points, ``input_grad``, ``fgm_update`` and ``fgm_attack`` run on this victim (include/ifd_dgcnn_atk.h),
+    with Classifier's signatures and return shapes, so attack.FGM / IFGM / MIFGM / PGD work on it unchanged; the gradient is
+    the one of the network with its neighbour tables held fixed.  The other attack methods are PointNet's, and the library
+    refuses them on a DGCNN context."""
 
     MAX_POINTS = _lib.DGCNN_MAX_POINTS
+    ATK_FNS = {"input_grad": "ifd_dgcnn_input_grad", "fgm_update": "ifd_dgcnn_fgm_update", "fgm_attack": "ifd_dgcnn_fgm_attack"}
+    EDGE_WIDTHS = (64, 64, 128, 256)
 
     def __init__(self, weights: np.ndarray, k: int = 20, device=None):
         self.lib = _lib.load()
@@ -1474,6 +1491,28 @@ class DgcnnClassifier(Classifier):
                     "feat": torch.zeros(B, stride, 512, device=self.device, dtype=torch.float32),
                     "global_feat": torch.empty(B, 2048, device=self.device, dtype=torch.float32)}
         return self._forward("ifd_dgcnn_forward", pc, n_points, _lib.IfdDgcnnAux, aux_table, want_aux, want_pred)
+
+    def _grad_aux(self, B, stride):
+        """input_grad's diagnostics on this victim: {"logits" [B,40], "loss" [B], "pred" [B], "idx": four [B,N,k] int32, "feat"
+        [B,N,512], "global_feat" [B,2048], "win_pool" [B,1024] int32 (the point of each conv5 max-pool channel), "win_edge": four
+        [B,N,Cout] int32 (the neighbour holding each channel's maximum), "act5" [B,N,32] int32 (bit c % 32 of word c // 32: conv5's
+        pre-activation of channel c is > 0)}.  Rows beyond a cloud's count: -1 in idx and win_edge, zero in feat and act5."""
+        dev, f, i = self.device, torch.float32, torch.int32
+        aux = {"logits": torch.empty(B, self.N_CLASSES, device=dev, dtype=f), "loss": torch.empty(B, device=dev, dtype=f),
+               "pred": torch.empty(B, device=dev, dtype=i),
+               "idx": [torch.full((B, stride, self.k), -1, device=dev, dtype=i) for _ in range(4)],
+               "feat": torch.zeros(B, stride, 512, device=dev, dtype=f), "global_feat": torch.empty(B, 2048, device=dev, dtype=f),
+               "win_pool": torch.empty(B, 1024, device=dev, dtype=i),
+               "win_edge": [torch.full((B, stride, c), -1, device=dev, dtype=i) for c in self.EDGE_WIDTHS],
+               "act5": torch.zeros(B, stride, 32, device=dev, dtype=i)}
+        st = _lib.IfdDgcnnGradOut()
+        for name, t in aux.items():
+            if isinstance(t, list):
+                for j, tj in enumerate(t):
+                    getattr(st, name)[j] = tj.data_ptr()
+            else:
+                setattr(st, name, t.data_ptr())
+        return aux, st
 
 
 class PointNet2Classifier(Classifier):
