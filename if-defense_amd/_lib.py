@@ -365,6 +365,27 @@ PN2_SIGNATURES = {
                                   C.c_void_p]),
 }
 
+# include/ifd_pn2_atk.h (input gradients of the PointNet++ victim and the FGM family on it), versioned on its own
+PN2_ATK_ABI_VERSION = 1
+
+
+class IfdPn2GradOut(C.Structure):
+    _fields_ = [("logits", C.c_void_p), ("loss", C.c_void_p), ("pred", C.c_void_p), ("fps1", C.c_void_p), ("fps2", C.c_void_p),
+                ("ball1", C.c_void_p), ("ball2", C.c_void_p), ("l1_feat", C.c_void_p), ("l2_feat", C.c_void_p),
+                ("global_feat", C.c_void_p), ("win1", C.c_void_p), ("win2", C.c_void_p), ("win3", C.c_void_p), ("act1", C.c_void_p),
+                ("act2", C.c_void_p), ("act3", C.c_void_p)]
+
+
+PN2_ATK_SIGNATURES = {
+    "ifd_pn2_atk_abi_version": (C.c_int, []),
+    "ifd_pn2_input_grad": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_float,
+                                     C.c_float, C.c_void_p, C.POINTER(IfdPn2GradOut), C.c_void_p]),
+    "ifd_pn2_fgm_update": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_float,
+                                     C.c_float, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
+    "ifd_pn2_fgm_attack": (C.c_int, [C.c_void_p, C.POINTER(IfdFgmParams), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
+                                     C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+}
+
 # include/ifd_pc.h (the PointConv victim classifier), versioned on its own
 PC_ABI_VERSION = 1
 PC_MAX_POINTS, PC_MIN_POINTS = 2048, 32
@@ -404,7 +425,7 @@ def load() -> C.CDLL:
             list(ATK_SIGNATURES.items()) + list(CW_SIGNATURES.items()) + list(KNN_SIGNATURES.items()) + list(ADD_SIGNATURES.items()) + \
             list(DROP_SIGNATURES.items()) + list(CLUSTER_SIGNATURES.items()) + list(OBJECT_SIGNATURES.items()) + \
             list(DGCNN_SIGNATURES.items()) + list(DGCNN_ATK_SIGNATURES.items()) + list(PN2_SIGNATURES.items()) + \
-            list(PC_SIGNATURES.items()):
+            list(PN2_ATK_SIGNATURES.items()) + list(PC_SIGNATURES.items()):
         fn = getattr(lib, name)          # AttributeError if the library lacks a declared symbol
         fn.restype, fn.argtypes = res, args
     if lib.ifd_abi_version() != ABI_VERSION:
@@ -434,6 +455,9 @@ def load() -> C.CDLL:
                           (lib.ifd_dgcnn_atk_abi_version(), DGCNN_ATK_ABI_VERSION))
     if lib.ifd_pn2_abi_version() != PN2_ABI_VERSION:
         raise ImportError("libifd.so PN2 ABI %d != binding PN2 ABI %d; rebuild" % (lib.ifd_pn2_abi_version(), PN2_ABI_VERSION))
+    if lib.ifd_pn2_atk_abi_version() != PN2_ATK_ABI_VERSION:
+        raise ImportError("libifd.so PN2 ATK ABI %d != binding PN2 ATK ABI %d; rebuild" %
+                          (lib.ifd_pn2_atk_abi_version(), PN2_ATK_ABI_VERSION))
     if lib.ifd_pc_abi_version() != PC_ABI_VERSION:
         raise ImportError("libifd.so PC ABI %d != binding PC ABI %d; rebuild" % (lib.ifd_pc_abi_version(), PC_ABI_VERSION))
     _lib = lib

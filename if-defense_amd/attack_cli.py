@@ -81,11 +81,14 @@ def close_classifier(classifier):
         classifier.close()
 
 
-def run_batches(attacker, data, target, batch_size):
-    """-> (adversarial clouds of the whole file, successes): attack() returns (..., clouds, success_num)."""
+def run_batches(attacker, data, target, batch_size, on_batch=None):
+    """-> (adversarial clouds of the whole file, successes): attack() returns (..., clouds, success_num).  ``on_batch(a, n)``,
+    where given, is told the offset and the size of every batch before it is attacked."""
     bs = len(data) if batch_size < 1 else batch_size
     adv, num = [], 0
     for a in range(0, len(data), bs):
+        if on_batch is not None:
+            on_batch(a, len(data[a:a + bs]))
         *_, pc, n_ok = attacker.attack(data[a:a + bs], target[a:a + bs].astype(np.int64))
         adv.append(pc)
         num += n_ok

@@ -18,6 +18,7 @@
 #include "../../include/ifd_dgcnn_atk.h"
 #include "../../include/ifd_pc.h"
 #include "../../include/ifd_pn2.h"
+#include "../../include/ifd_pn2_atk.h"
 
 #include <hip/hip_runtime.h>
 
@@ -158,6 +159,7 @@ struct ifd_ctx {
     DgGradImage dgimg{};           // ... and its backward pass's image, in d_cls_grad (include/ifd_dgcnn_atk.h)
     int dg_k = 0;
     Pn2Image p2img{};
+    Pn2GradImage p2gimg{};         // ... and its backward pass's image, in d_cls_grad (include/ifd_pn2_atk.h)
     PcImage pcimg{};               // PointConv (pointconv.hip)
     std::string err;
     unsigned long long* counters() const { return d_counters.get<unsigned long long>(); }
@@ -1794,19 +1796,22 @@ DgWs dgcnn_ws(Carve& c, size_t n, int stride, int k) {
 }
 size_t dgcnn_ws_bytes(int n, int stride, int k) { return carved_bytes([&](Carve& c) { dgcnn_ws(c, (size_t)n, stride, k); }); }
 
+// L of the forward's image f, transposed, appended to a backward image whose zero bias lies at its start: rows [n_in of L][n_out of
+// L, padded with zeros to pad_out]
+DenseLayer append_transposed_layer(std::vector<float>& img, const std::vector<float>& f, const DenseLayer& L, int pad_out) {
+    DenseLayer T;
+    T.n_out = L.n_in; T.n_in = pad_out; T.b = 0;
+    T.w = (int)img.size();
+    img.resize(img.size() + (size_t)L.n_in * pad_out, 0.f);
+    for (int o = 0; o < L.n_out; ++o)
+        for (int c = 0; c < L.n_in; ++c) img[T.w + (size_t)c * pad_out + o] = f[L.w + (size_t)o * L.n_in + c];
+    return T;
+}
+
 // The backward pass's image (ifd_internal.h DgGradImage) from the forward's: every layer transposed, one block of zeros as the bias of all.
 std::vector<float> build_dgcnn_grad_image(const std::vector<float>& f, const DgImage& I, DgGradImage& G) {
     std::vector<float> img(2 * DG_EMB, 0.f);                           // the zero bias
-    // rows [n_in of L][n_out of L, padded with zeros to pad_out]
-    auto transposed = [&](const DenseLayer& L, int pad_out) {
-        DenseLayer T;
-        T.n_out = L.n_in; T.n_in = pad_out; T.b = 0;
-        T.w = (int)img.size();
-        img.resize(img.size() + (size_t)L.n_in * pad_out, 0.f);
-        for (int o = 0; o < L.n_out; ++o)
-            for (int c = 0; c < L.n_in; ++c) img[T.w + (size_t)c * pad_out + o] = f[L.w + (size_t)o * L.n_in + c];
-        return T;
-    };
+    auto transposed = [&](const DenseLayer& L, int pad_out) { return append_transposed_layer(img, f, L, pad_out); };
     for (int j = 0; j < 3; ++j) G.fct[j] = transposed(I.fc[j], (I.fc[j].n_out + 63) / 64 * 64);
     for (int l = 0; l < 3; ++l) G.pqt[l] = transposed(I.pq[l], I.pq[l].n_out);
     G.w5t = transposed(I.conv5, I.conv5.n_out).w;
@@ -1960,26 +1965,42 @@ Pn2Ws pn2_ws(Carve& c, size_t n) {
 }
 size_t pn2_ws_bytes(int n) { return carved_bytes([&](Carve& c) { pn2_ws(c, (size_t)n); }); }
 
-}  // namespace
-
-extern "C" {
-
-int ifd_pn2_abi_version(void) { return IFD_PN2_ABI_VERSION; }
-
-size_t ifd_pn2_weight_count(void) { return pn2_count(); }
-
-ifd_ctx* ifd_pn2_create(const float* weights_host, size_t n_weights, int n_classes, int device) {
-    if (!victim_create_args_ok("ifd_pn2_create", weights_host, n_weights, pn2_count(), n_classes)) return nullptr;
-    return create_ctx("ifd_pn2_create", IFD_MODEL_PN2, device, [&](ifd_ctx* ctx) {
-        ctx->cls_classes = n_classes;
-        hipError_t e = upload(ctx->d_victim, build_pn2_image(weights_host, ctx->p2img));
-        if (e == hipSuccess) e = configure_pn2_kernels();
-        return e;
-    });
+// The backward pass's image (ifd_internal.h Pn2GradImage) from the forward's: the layers that run dense, transposed, on one block of
+// zeros as the bias of all.
+std::vector<float> build_pn2_grad_image(const std::vector<float>& f, const Pn2Image& I, Pn2GradImage& G) {
+    std::vector<float> img(PN2_EMB, 0.f);                              // the zero bias
+    auto transposed = [&](const DenseLayer& L, int pad_out) { return append_transposed_layer(img, f, L, pad_out); };
+    for (int j = 0; j < 3; ++j) G.fct[j] = transposed(I.fc[j], (I.fc[j].n_out + 63) / 64 * 64);
+    G.s3t = transposed(I.sa3[0], I.sa3[0].n_out);
+    G.s3ut = transposed(I.sa3_u, I.sa3_u.n_out);
+    G.s3xt = transposed(DenseLayer{I.sa3_xyz, 0, I.sa3_u.n_out, 4}, I.sa3_u.n_out);    // the [256][4] rows {w0, w1, w2, 0}
+    G.s2t = transposed(I.sa2[0], I.sa2[0].n_out);
+    G.s2ut = transposed(I.sa2_u, I.sa2_u.n_out);
+    G.s1t = transposed(I.sa1[0], I.sa1[0].n_out);
+    G.total = (int)img.size();
+    return img;
 }
 
-int ifd_pn2_forward(ifd_ctx* ctx, const float* pc, const int32_t* n_points, const int32_t* fps_start, int B, int stride, float* logits,
-                    const ifd_pn2_aux* aux, void* stream) {
+// the workspace of ifd_pn2_input_grad over n clouds: ifd_pn2_forward's (whose first 1024 bytes the check uses), then the backward's
+Pn2GradWs pn2_grad_ws(Carve& c, size_t n) {
+    Pn2GradWs w;
+    w.f = pn2_ws(c, n);
+    c.round_up(256);
+    w.logits = c.take<float>(n * 160); w.d_out = c.take<float>(n * 256); w.d2 = c.take<float>(n * 1024); w.d1 = c.take<float>(n * 2048);
+    w.dg = c.take<float>(n * PN2_EMB * 4); w.win3 = c.take<int32_t>(n * PN2_EMB * 4);
+    w.ds3b = c.take<float>(n * PN2_NP2 * 512 * 4); w.ds3a = c.take<float>(n * PN2_NP2 * 256 * 4); w.dl2 = c.take<float>(n * PN2_NP2 * 256 * 4);
+    w.dx2a = c.take<float>(n * PN2_NP2 * 16); w.dx2 = c.take<float>(n * PN2_NP2 * 16);
+    w.dh = c.take<float>(n * PN2_NP2 * PN2_NS2 * 128 * 4); w.de = c.take<float>(n * PN2_NP2 * PN2_NS2 * 16);
+    w.du = c.take<float>(n * PN2_NP1 * 128 * 4); w.dx1a = c.take<float>(n * PN2_NP1 * 16); w.dl1 = c.take<float>(n * PN2_NP1 * 128 * 4);
+    w.dd = c.take<float>(n * PN2_NP1 * PN2_NS1 * 16); w.dx1 = c.take<float>(n * PN2_NP1 * 16);
+    w.pred = c.take<int32_t>(n * 4); w.loss = c.take<float>(n * 4);
+    return w;
+}
+
+// ifd_pn2_forward; check = false skips the blocking check (the caller has made it), ws_off: bytes at the front of the workspace that
+// belong to the caller (ifd_pn2_fgm_attack's loop state)
+int pn2_forward_impl(ifd_ctx* ctx, const float* pc, const int32_t* n_points, const int32_t* fps_start, int B, int stride, float* logits,
+                     const ifd_pn2_aux* aux, void* stream, bool check, size_t ws_off) {
     if (!ctx) return IFD_ERR_ARG;
     if (ctx->model != IFD_MODEL_PN2 || !ctx->d_victim.get()) return fail(ctx, IFD_ERR_ARG, "ifd_pn2_forward: not a PointNet++ context");
     if (!pc || !logits || B < 1 || stride < 1) return fail(ctx, IFD_ERR_ARG, "ifd_pn2_forward: bad argument (pc, logits, B >= 1, stride >= 1)");
@@ -1987,9 +2008,9 @@ int ifd_pn2_forward(ifd_ctx* ctx, const float* pc, const int32_t* n_points, cons
     hipStream_t s = static_cast<hipStream_t>(stream);
     const int nc = ctx->cls_classes;
     return victim_forward(
-        ctx, "ifd_pn2_forward", B, PN2_CHUNK, 0, [&](int chunk) { return pn2_ws_bytes(chunk); },
+        ctx, "ifd_pn2_forward", B, PN2_CHUNK, ws_off, [&](int chunk) { return pn2_ws_bytes(chunk); },
         [&](char* base) {
-            if (!n_points && !fps_start) return (int)IFD_OK;
+            if (!check || (!n_points && !fps_start)) return (int)IFD_OK;
             int32_t bad[2] = {0, 0};
             if (int rc = read_bad_counts(ctx, "ifd_pn2_forward", "n_points and fps_start",
                                          launch_pn2_check(n_points, fps_start, B, stride, reinterpret_cast<int32_t*>(base), s), base, 2, bad, s))
@@ -2017,6 +2038,32 @@ int ifd_pn2_forward(ifd_ctx* ctx, const float* pc, const int32_t* n_points, cons
             return launch_pn2(ctx->d_victim.get<float>(), ctx->p2img, pc + (size_t)c0 * stride * 3, n_points ? n_points + c0 : nullptr,
                               fps_start ? fps_start + (size_t)c0 * 2 : nullptr, n, stride, w, o, logits + (size_t)c0 * nc, nc, s);
         });
+}
+
+}  // namespace
+
+extern "C" {
+
+int ifd_pn2_abi_version(void) { return IFD_PN2_ABI_VERSION; }
+
+size_t ifd_pn2_weight_count(void) { return pn2_count(); }
+
+ifd_ctx* ifd_pn2_create(const float* weights_host, size_t n_weights, int n_classes, int device) {
+    if (!victim_create_args_ok("ifd_pn2_create", weights_host, n_weights, pn2_count(), n_classes)) return nullptr;
+    return create_ctx("ifd_pn2_create", IFD_MODEL_PN2, device, [&](ifd_ctx* ctx) {
+        ctx->cls_classes = n_classes;
+        const std::vector<float> img = build_pn2_image(weights_host, ctx->p2img);
+        hipError_t e = upload(ctx->d_victim, img);
+        if (e == hipSuccess) e = upload(ctx->d_cls_grad, build_pn2_grad_image(img, ctx->p2img, ctx->p2gimg));
+        if (e == hipSuccess) e = configure_pn2_kernels();
+        if (e == hipSuccess) e = configure_pn2_grad_kernels();
+        return e;
+    });
+}
+
+int ifd_pn2_forward(ifd_ctx* ctx, const float* pc, const int32_t* n_points, const int32_t* fps_start, int B, int stride, float* logits,
+                    const ifd_pn2_aux* aux, void* stream) {
+    return pn2_forward_impl(ctx, pc, n_points, fps_start, B, stride, logits, aux, stream, true, 0);
 }
 
 }  // extern "C"
@@ -2572,6 +2619,163 @@ int ifd_dgcnn_fgm_attack(ifd_ctx* ctx, const ifd_fgm_params* params, const float
     if (int rc = dgcnn_forward_impl(ctx, pc_out, n_points, B, stride, L.logits, &aux, stream, false, state)) return rc;
     e = launch_atk_success(L.pred, target, B, success, s);
     if (e != hipSuccess) return fail(ctx, IFD_ERR_HIP, "ifd_dgcnn_fgm_attack: success", e);
+    return IFD_OK;
+}
+
+}  // extern "C"
+
+// ---- attacks on the PointNet++ victim (include/ifd_pn2_atk.h) ----------------------------------------------------------
+namespace {
+
+int pn2_atk_context_ok(ifd_ctx* ctx, const char* who) {
+    if (ctx->model != IFD_MODEL_PN2 || !ctx->d_victim.get() || !ctx->d_cls_grad.get())
+        return fail(ctx, IFD_ERR_ARG, (std::string(who) + ": not a PointNet++ context").c_str());
+    return IFD_OK;
+}
+int pn2_atk_stride_ok(ifd_ctx* ctx, const char* who, int stride) {
+    if (stride >= 1 && stride <= IFD_PN2_MAX_POINTS) return IFD_OK;
+    return fail(ctx, IFD_ERR_ARG, (std::string(who) + ": stride " + std::to_string(stride) + " outside [1, 2048]").c_str());
+}
+
+int pn2_atk_chunk(int B) {                   // the forward's chunks
+    const int n_chunks = (B + PN2_CHUNK - 1) / PN2_CHUNK;
+    return (B + n_chunks - 1) / n_chunks;
+}
+size_t pn2_grad_ws_bytes(int B) { return carved_bytes([&](Carve& c) { pn2_grad_ws(c, (size_t)pn2_atk_chunk(B)); }); }
+
+// the one blocking step of the PointNet++ attack calls: counts and starts (launch_pn2_check) and targets (launch_atk_check), four
+// counters at the start of the workspace, read together
+int pn2_atk_check(ifd_ctx* ctx, const char* who, const int32_t* n_points, const int32_t* fps_start, const int32_t* target, int B,
+                  int stride, hipStream_t s) {
+    int32_t* d_bad = ctx->ws.get<int32_t>();
+    hipError_t e = launch_pn2_check(n_points, fps_start, B, stride, d_bad, s);
+    if (e == hipSuccess) e = launch_atk_check(nullptr, target, B, 1, stride, ctx->cls_classes, d_bad + 2, s);
+    int32_t bad[4] = {0, 0, 0, 0};
+    if (int rc = read_bad_counts(ctx, who, "n_points, fps_start and target", e, d_bad, 4, bad, s)) return rc;
+    if (bad[0] != 0)
+        return fail(ctx, IFD_ERR_ARG, (std::string(who) + ": " + std::to_string(bad[0]) + " cloud(s) with n_points outside [1, stride]").c_str());
+    if (bad[1] != 0)
+        return fail(ctx, IFD_ERR_ARG,
+                    (std::string(who) + ": " + std::to_string(bad[1]) + " cloud(s) with fps_start outside [0, n_points) x [0, 512)").c_str());
+    if (bad[3] != 0)
+        return fail(ctx, IFD_ERR_ARG, (std::string(who) + ": " + std::to_string(bad[3]) + " target(s) outside [0, 40)").c_str());
+    return IFD_OK;
+}
+
+// ifd_pn2_input_grad on workspace that is already large enough (ws_off: bytes in front that belong to the caller), unchecked
+int pn2_input_grad_impl(ifd_ctx* ctx, size_t ws_off, const float* pc, const int32_t* n_points, const int32_t* fps_start, int B, int stride,
+                        const int32_t* target, int loss_kind, float kappa, float scale, float* grad, const ifd_pn2_grad_out* out,
+                        hipStream_t s) {
+    const int chunk = pn2_atk_chunk(B), nc = ctx->cls_classes;
+    for (int c0 = 0; c0 < B; c0 += chunk) {
+        const size_t n = (size_t)std::min(chunk, B - c0), st = (size_t)stride, at = (size_t)c0;
+        Carve c(ctx->ws.get<char>() + ws_off);
+        const Pn2GradWs w = pn2_grad_ws(c, n);
+        Pn2GradOut o{};
+        if (out) {
+            o.fps1 = out->fps1 ? out->fps1 + at * PN2_NP1 : nullptr;
+            o.fps2 = out->fps2 ? out->fps2 + at * PN2_NP2 : nullptr;
+            o.ball1 = out->ball1 ? out->ball1 + at * PN2_NP1 * PN2_NS1 : nullptr;
+            o.ball2 = out->ball2 ? out->ball2 + at * PN2_NP2 * PN2_NS2 : nullptr;
+            o.l1_feat = out->l1_feat ? out->l1_feat + at * PN2_NP1 * 128 : nullptr;
+            o.l2_feat = out->l2_feat ? out->l2_feat + at * PN2_NP2 * 256 : nullptr;
+            o.gfeat = out->global_feat ? out->global_feat + at * PN2_EMB : nullptr;
+            o.win1 = out->win1 ? out->win1 + at * PN2_NP1 * 128 : nullptr;
+            o.win2 = out->win2 ? out->win2 + at * PN2_NP2 * 256 : nullptr;
+            o.act1 = out->act1 ? out->act1 + at * PN2_NP1 * PN2_NS1 * 4 : nullptr;
+            o.act2 = out->act2 ? out->act2 + at * PN2_NP2 * PN2_NS2 * 8 : nullptr;
+            o.act3 = out->act3 ? out->act3 + at * PN2_NP2 * 24 : nullptr;
+        }
+        hipError_t e = launch_pn2_grad(ctx->d_victim.get<float>(), ctx->p2img, ctx->d_cls_grad.get<float>(), ctx->p2gimg, pc + at * st * 3,
+                                       n_points ? n_points + c0 : nullptr, fps_start ? fps_start + at * 2 : nullptr, (int)n, stride,
+                                       target + c0, loss_kind, kappa, scale, w, o, nc, grad + at * st * 3, s);
+        auto copy = [&](void* dst, const void* src, size_t bytes_per_cloud) {
+            if (e == hipSuccess && dst)
+                e = hipMemcpyAsync(static_cast<char*>(dst) + at * bytes_per_cloud, src, n * bytes_per_cloud, hipMemcpyDeviceToDevice, s);
+        };
+        if (out) {
+            copy(out->logits, w.logits, 160);
+            copy(out->loss, w.loss, 4);
+            copy(out->pred, w.pred, 4);
+            copy(out->win3, w.win3, PN2_EMB * 4);
+        }
+        if (e != hipSuccess) return fail(ctx, IFD_ERR_HIP, "ifd_pn2_input_grad launch", e);
+    }
+    return IFD_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int ifd_pn2_atk_abi_version(void) { return IFD_PN2_ATK_ABI_VERSION; }
+
+int ifd_pn2_input_grad(ifd_ctx* ctx, const float* pc, const int32_t* n_points, const int32_t* fps_start, int B, int stride,
+                       const int32_t* target, int loss_kind, float kappa, float scale, float* grad, const ifd_pn2_grad_out* out,
+                       void* stream) {
+    if (!ctx) return IFD_ERR_ARG;
+    if (int rc = pn2_atk_context_ok(ctx, "ifd_pn2_input_grad")) return rc;
+    if (!pc || !target || !grad || B < 1) return fail(ctx, IFD_ERR_ARG, "ifd_pn2_input_grad: bad argument (pc, target, grad; B >= 1)");
+    if (int rc = pn2_atk_stride_ok(ctx, "ifd_pn2_input_grad", stride)) return rc;
+    if (!atk_loss_ok(loss_kind)) return fail(ctx, IFD_ERR_ARG, "ifd_pn2_input_grad: unknown loss_kind");
+    IFD_ON_CTX_DEVICE(ctx);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    hipError_t e = ctx->ws.grow(pn2_grad_ws_bytes(B));
+    if (e != hipSuccess) return fail(ctx, IFD_ERR_NOMEM, "ifd_pn2_input_grad: workspace", e);
+    if (int rc = pn2_atk_check(ctx, "ifd_pn2_input_grad", n_points, fps_start, target, B, stride, s)) return rc;
+    return pn2_input_grad_impl(ctx, 0, pc, n_points, fps_start, B, stride, target, loss_kind, kappa, scale, grad, out, s);
+}
+
+int ifd_pn2_fgm_update(ifd_ctx* ctx, int kind, const float* grad, float* pc, const float* ori_pc, float* momentum, float step_size,
+                       float budget, float mu, const int32_t* n_points, int B, int stride, void* stream) {
+    if (!ctx) return IFD_ERR_ARG;
+    if (int rc = pn2_atk_context_ok(ctx, "ifd_pn2_fgm_update")) return rc;
+    if (!atk_kind_ok(kind)) return fail(ctx, IFD_ERR_ARG, "ifd_pn2_fgm_update: unknown kind");
+    if (!grad || !pc || B < 1 || stride < 1 || stride > IFD_PN2_MAX_POINTS || (kind != IFD_FGM_FGM && !ori_pc) ||
+        (kind == IFD_FGM_MIFGM && !momentum))
+        return fail(ctx, IFD_ERR_ARG, "ifd_pn2_fgm_update: bad argument (grad, pc; ori_pc unless FGM; momentum for MIFGM; 1 <= stride <= 2048)");
+    IFD_ON_CTX_DEVICE(ctx);
+    hipError_t e = launch_fgm_update(kind, grad, pc, ori_pc, momentum, step_size, budget, mu, n_points, B, stride,
+                                     static_cast<hipStream_t>(stream));
+    if (e != hipSuccess) return fail(ctx, IFD_ERR_HIP, "ifd_pn2_fgm_update launch", e);
+    return IFD_OK;
+}
+
+int ifd_pn2_fgm_attack(ifd_ctx* ctx, const ifd_fgm_params* params, const float* pc_in, const int32_t* n_points, const int32_t* fps_start,
+                       const int32_t* target, int B, int stride, float* pc_out, int32_t* success, void* stream) {
+    if (!ctx) return IFD_ERR_ARG;
+    if (int rc = pn2_atk_context_ok(ctx, "ifd_pn2_fgm_attack")) return rc;
+    if (!params || params->struct_size != (int32_t)sizeof(ifd_fgm_params))
+        return fail(ctx, IFD_ERR_ARG, "ifd_pn2_fgm_attack: params missing or of another struct_size");
+    if (!atk_kind_ok(params->kind) || !atk_loss_ok(params->loss_kind) || params->num_iter < 1)
+        return fail(ctx, IFD_ERR_ARG, "ifd_pn2_fgm_attack: unknown kind or loss_kind, or num_iter < 1");
+    if (!pc_in || !target || !pc_out || !success || pc_in == pc_out || B < 1)
+        return fail(ctx, IFD_ERR_ARG, "ifd_pn2_fgm_attack: bad argument (pc_in, target, pc_out, success; B >= 1)");
+    if (int rc = pn2_atk_stride_ok(ctx, "ifd_pn2_fgm_attack", stride)) return rc;
+    IFD_ON_CTX_DEVICE(ctx);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const size_t cloud = (size_t)stride * 12, state = carved_bytes([&](Carve& c) { FgmLoop(c, (size_t)B, cloud); });
+    hipError_t e = ctx->ws.grow(state + pn2_grad_ws_bytes(B));         // the final forward's workspace is the front of the gradient's
+    if (e != hipSuccess) return fail(ctx, IFD_ERR_NOMEM, "ifd_pn2_fgm_attack: workspace", e);
+    if (int rc = pn2_atk_check(ctx, "ifd_pn2_fgm_attack", n_points, fps_start, target, B, stride, s)) return rc;
+    Carve c(ctx->ws.get());
+    const FgmLoop L(c, (size_t)B, cloud);
+    e = hipMemcpyAsync(pc_out, pc_in, (size_t)B * cloud, hipMemcpyDeviceToDevice, s);
+    if (e == hipSuccess && params->kind == IFD_FGM_MIFGM) e = hipMemsetAsync(L.mom, 0, (size_t)B * cloud, s);
+    if (e != hipSuccess) return fail(ctx, IFD_ERR_HIP, "ifd_pn2_fgm_attack: start", e);
+    const int iters = params->kind == IFD_FGM_FGM ? 1 : params->num_iter;
+    for (int it = 0; it < iters; ++it) {
+        if (int rc = pn2_input_grad_impl(ctx, state, pc_out, n_points, fps_start, B, stride, target, params->loss_kind, params->kappa,
+                                         params->scale, L.grad, nullptr, s))
+            return rc;
+        e = launch_fgm_update(params->kind, L.grad, pc_out, pc_in, L.mom, params->step_size, params->budget, params->mu, n_points, B, stride, s);
+        if (e != hipSuccess) return fail(ctx, IFD_ERR_HIP, "ifd_pn2_fgm_attack: update", e);
+    }
+    ifd_pn2_aux aux{};
+    aux.pred = L.pred;
+    if (int rc = pn2_forward_impl(ctx, pc_out, n_points, fps_start, B, stride, L.logits, &aux, stream, false, state)) return rc;
+    e = launch_atk_success(L.pred, target, B, success, s);
+    if (e != hipSuccess) return fail(ctx, IFD_ERR_HIP, "ifd_pn2_fgm_attack: success", e);
     return IFD_OK;
 }
 

@@ -548,6 +548,51 @@ hipError_t launch_pn2_check(const int32_t* n_points, const int32_t* fps_start, i
 hipError_t launch_pn2(const float* img, const Pn2Image& I, const float* pc, const int32_t* n_points, const int32_t* fps_start, int B,
                       int stride, const Pn2Ws& w, const Pn2Out& out, float* logits, int n_classes, hipStream_t s);
 
+// ---- PointNet++ input gradients (pointnet2_grad.hip; C ABI in include/ifd_pn2_atk.h) -----------------------------------
+// The backward pass's weight image (api.cpp build_pn2_grad_image): the layers that run dense in the backward pass, transposed as
+// DgGradImage's are, all on one block of zeros as their bias.  The sparse last layers read the forward's image.
+struct Pn2GradImage {
+    DenseLayer fct[3];                  // fc1^T [1024][512], fc2^T [512][256], fc3^T [256][64] (40 inputs padded with zero columns)
+    DenseLayer s3t;                     // sa3's middle layer^T [256][512]
+    DenseLayer s3ut, s3xt;              // sa3's first layer^T: the feature columns [256][256], the coordinates [4][256] (row 3 zero)
+    DenseLayer s2t, s2ut;               // sa2's middle layer^T [128][128], its first layer's feature columns^T [128][128]
+    DenseLayer s1t;                     // sa1's middle layer^T [64][64]
+    int total;
+};
+struct Pn2GradWs {                      // per-chunk scratch of launch_pn2_grad (api.cpp pn2_grad_ws)
+    Pn2Ws f;                            // the forward's
+    float* logits;      // [B][40]
+    int32_t* pred;      // [B]
+    float* loss;        // [B]
+    float* d_out;       // [B][64]
+    float* d2;          // [B][256]
+    float* d1;          // [B][512]
+    float* dg;          // [B][1024]          d loss / d global_feat
+    int32_t* win3;      // [B][1024]
+    float* ds3b;        // [B][128][512]
+    float* ds3a;        // [B][128][256]
+    float* dl2;         // [B][128][256]
+    float* dx2a;        // [B][128][4]        sa3's coordinate columns transposed
+    float* dx2;         // [B][128][4]        d xyz2
+    float* dh;          // [B][128][64][128]  sa2's first-layer gradient per row
+    float* de;          // [B][128][64][4]    d (xyz1_j - xyz2_g) per row
+    float* du;          // [B][512][128]
+    float* dx1a;        // [B][512][4]        d xyz1 but for sa1's own term
+    float* dl1;         // [B][512][128]
+    float* dd;          // [B][512][32][4]    d (x_j - xyz1_i) per row
+    float* dx1;         // [B][512][4]        d xyz1
+};
+struct Pn2GradOut {                     // ifd_pn2_grad_out's members that the kernels write themselves; null: not wanted
+    int32_t *fps1, *fps2, *ball1, *ball2;
+    float *l1_feat, *l2_feat, *gfeat;
+    int32_t *win1, *win2;
+    uint32_t *act1, *act2, *act3;
+};
+hipError_t configure_pn2_grad_kernels();
+hipError_t launch_pn2_grad(const float* img, const Pn2Image& I, const float* gimg, const Pn2GradImage& G, const float* pc,
+                           const int32_t* n_points, const int32_t* fps_start, int B, int stride, const int32_t* target, int loss_kind,
+                           float kappa, float scale, const Pn2GradWs& w, const Pn2GradOut& out, int n_classes, float* grad, hipStream_t s);
+
 // ---- victim classifier: PointConv (pointconv.hip; C ABI in include/ifd_pc.h) ------------------------------------------
 constexpr int PC_MAX_POINTS = 2048, PC_MIN_POINTS = 32;   // IFD_PC_MAX_POINTS, IFD_PC_MIN_POINTS
 constexpr int PC_NP1 = 512, PC_K1 = 32;         // sa1: centroids, nearest neighbours of each

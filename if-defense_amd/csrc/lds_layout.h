@@ -349,6 +349,43 @@ struct Pn2Sa2Lds {                                   // pn2_sa2_kernel
 };
 static_assert(Pn2Sa1Lds::BYTES == 34816 && Pn2Sa2Lds::BYTES == 69632 && Pn2Sa2Lds::BYTES <= LDS_MAX_BYTES, "LDS of the grouped MLPs");
 
+// ---- pointnet2_grad.hip -------------------------------------------------------------------------------------------------------
+struct Pn2Sa1BwdLds {                                // pn2_sa1_bwd_kernel: the forward's tile, then the gradients in its place
+    static constexpr int LD = Pn2Sa1Lds::LD;
+    static constexpr size_t A = 0;                                         // float [64][LD] h1; then d h2
+    static constexpr size_t B = A + (size_t)64 * LD * 4;                   // float [64][LD] h2; then d h1 before its gate
+    static constexpr size_t WIN = B + (size_t)64 * LD * 4;                 // int [2][128] a group's winner row per channel, -1: none
+    static constexpr size_t DG = WIN + 2 * 128 * 4;                        // float [2][128] d l1_feat under the last layer's gate
+    static constexpr size_t DD = DG + 2 * 128 * 4;                         // float [64][4] d (x_j - c_i) of the rows
+    static constexpr size_t BYTES = DD + 64 * 16;
+};
+struct Pn2Sa2BwdLds {                                // pn2_sa2_bwd_kernel
+    static constexpr int LD = Pn2Sa2Lds::LD;
+    static constexpr size_t A = 0;                                         // float [64][LD] a1; then d a2
+    static constexpr size_t B = A + (size_t)64 * LD * 4;                   // float [64][LD] a2; then d a1 before its gate
+    static constexpr size_t WROW = B + (size_t)64 * LD * 4;                // int [2][256] the two row halves' lowest winner rows
+    static constexpr size_t WIN = WROW + 2 * 256 * 4;                      // int [256] the group's winner row per channel, -1: none
+    static constexpr size_t DG = WIN + 256 * 4;                            // float [256] d l2_feat under the last layer's gate
+    static constexpr size_t DE = DG + 256 * 4;                             // float [64][4] d (xyz1_j - c_g) of the rows
+    static constexpr size_t BYTES = DE + 64 * 16;
+};
+struct Pn2Sa3WinLds {                                // pn2_sa3_win_kernel
+    static constexpr size_t WROW = 0;                                      // int [2 tiles][2 row halves][64] lowest winner rows
+    static constexpr size_t BYTES = WROW + 4 * 64 * 4;
+};
+struct Pn2Sa3SparseLds {                             // pn2_sa3_sparse_kernel
+    static constexpr size_t WIN = 0;                                       // int [1024]
+    static constexpr size_t DG = WIN + (size_t)PN2_EMB * 4;                // float [1024] d global_feat under the last layer's gate
+    static constexpr size_t BYTES = DG + (size_t)PN2_EMB * 4;
+};
+struct Pn2GatherLds {                                // pn2_l1_gather_kernel (8192 rows), pn2_point_gather_kernel (16384 rows)
+    static constexpr size_t FPS = 0;                                       // uint16 [512] the centroid table (128 used at level 2)
+    static constexpr size_t TAB = FPS + (size_t)PN2_NP1 * 2;               // uint16 [rows] the ball table of the cloud
+    static constexpr size_t BYTES = TAB + (size_t)PN2_NP1 * PN2_NS1 * 2;
+};
+static_assert(Pn2Sa1BwdLds::BYTES == 37888 && Pn2Sa2BwdLds::BYTES == 72704 && Pn2Sa2BwdLds::BYTES <= LDS_MAX_BYTES &&
+              Pn2GatherLds::BYTES == 33792 && PN2_NP1 * PN2_NS1 >= PN2_NP2 * PN2_NS2, "LDS of the PointNet++ backward kernels");
+
 // ---- pointconv.hip ------------------------------------------------------------------------------------------------------------
 struct PcDensityLds {                                // pc_density_kernel: the level's whole input cloud
     static constexpr size_t X = 0;                                         // float [PC_MAX_POINTS][3]

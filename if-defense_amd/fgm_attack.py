@@ -44,10 +44,14 @@ def save_path(out_dir, dataset, num_points, model, attack_type, delta, num_iter,
     return d, name
 
 
-def attack_file(prog, args, open_classifier, check_data=None) -> int:
-    """The script behind its refusals, shared with dgcnn_fgm_attack: the settings, the data file, the victim that
-    ``open_classifier()`` makes, the batches and the result file.  ``check_data(data)``: a message where the clouds [N,K,3]
-    cannot be attacked (status 2, before the victim is made), else None."""
+def attack_file(prog, args, open_classifier, check_data=None, on_batch=None, by_file=False) -> int:
+    """The script behind its refusals, shared with dgcnn_fgm_attack and pointnet2_fgm_attack: the settings, the data file, the
+    victim that ``open_classifier()`` makes, the batches and the result file.  ``check_data(data)``: a message where the clouds
+    [N,K,3] cannot be attacked (status 2, before the victim is made), else None.  ``on_batch(classifier, a, n)``, where given, is
+    told the offset in the file and the size of every batch before it is attacked.  ``by_file``: what the batches of a file share
+    is taken from the file, as --batch_size -1 takes it - the loss is a mean over the whole file (scale = 1 / N in every batch)
+    and the start noise is ONE draw of the file's shape - so that --batch_size only says how many clouds go through the library at
+    once and the clouds written do not depend on it.  Without it every batch has its own mean and its own draw, as before."""
     from .attack import ATTACKS
     kind = args.attack_type.lower()
     if kind not in ATTACKS:
@@ -67,13 +71,20 @@ def attack_file(prog, args, open_classifier, check_data=None) -> int:
     classifier = open_classifier()
     try:
         kw = dict(kappa=args.kappa, seed=args.seed)
+        if by_file:
+            kw['ref_batch'] = len(data)
         if kind == 'fgm':
             attacker = ATTACKS[kind](classifier, args.adv_func, budget, **kw)
         elif kind == 'mifgm':
             attacker = ATTACKS[kind](classifier, args.adv_func, None, budget, step_size, num_iter, args.mu, **kw)
         else:
             attacker = ATTACKS[kind](classifier, args.adv_func, None, budget, step_size, num_iter, **kw)
-        adv, num = C.run_batches(attacker, data, target, args.batch_size)
+        if by_file:                                                    # the file's start clouds, then loops that add nothing
+            import torch
+            data = attacker.start(torch.from_numpy(np.ascontiguousarray(data, dtype=np.float32))).numpy()
+            attacker.start = lambda d: d
+        hook = None if on_batch is None else (lambda a, n: on_batch(classifier, a, n))
+        adv, num = C.run_batches(attacker, data, target, args.batch_size, hook)
     finally:
         C.close_classifier(classifier)
     rate = float(num) / float(len(data))

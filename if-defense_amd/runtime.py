@@ -817,12 +817,18 @@ class Classifier:
         grad [B,N,3], zeros in the rows beyond a cloud's points.  pc: as ``logits`` takes it, ragged lists included; target [B].
         loss: "logits" (LogitsAdvLoss(kappa)) or "cross_entropy".  With want_aux also {"logits" [B,40], "loss" [B], "pred" [B],
         "win_feat" / "win_stn" [B,1024] int32 (the point each max-pool channel came from), "global_feat" [B,1024]}."""
+        return self._input_grad(pc, target, loss, kappa, scale, n_points, want_aux)
+
+    def _input_grad(self, pc, target, loss, kappa, scale, n_points, want_aux, extra=None):
+        """input_grad's call; ``extra(B)``: the arguments the library call takes between n_points and B, device tensors or None."""
         kind = self._loss_kind(loss)
         pc, n_points = self._batch(pc, n_points)
         B, stride = int(pc.shape[0]), int(pc.shape[1])
         if B < 1 or stride < 1:
             raise IfdError("empty batch")
         target = self._target(target, B)
+        held = extra(B) if extra else ()                               # the tensors stay alive until the call has been made
+        between = [None if t is None else t.data_ptr() for t in held]
         grad = torch.empty(B, stride, 3, device=self.device, dtype=torch.float32)
         aux, st = None, None
         if want_aux:
@@ -830,7 +836,7 @@ class Classifier:
             st = C.byref(struct)
         with torch.cuda.device(self.device):
             self._check(getattr(self.lib, self.ATK_FNS["input_grad"])(
-                self.ctx, pc.data_ptr(), None if n_points is None else n_points.data_ptr(), B, stride, target.data_ptr(), kind,
+                self.ctx, pc.data_ptr(), None if n_points is None else n_points.data_ptr(), *between, B, stride, target.data_ptr(), kind,
                 float(kappa), float(scale), grad.data_ptr(), st, self._stream()))
         return (grad, aux) if want_aux else grad
 
@@ -853,6 +859,10 @@ class Classifier:
     def fgm_attack(self, kind, pc, target, budget, step_size, num_iter=1, mu=1., loss="logits", kappa=0., scale=1., n_points=None):
         """The whole loop on the device (ifd_fgm_attack): -> (adversarial clouds [B,N,3], success [B] bool).  ``pc`` is the
         start AND the centre of the clip: pass it with the start noise already added."""
+        return self._fgm_attack(kind, pc, target, budget, step_size, num_iter, mu, loss, kappa, scale, n_points)
+
+    def _fgm_attack(self, kind, pc, target, budget, step_size, num_iter, mu, loss, kappa, scale, n_points, extra=None):
+        """fgm_attack's call; ``extra(B)``: the arguments the library call takes between n_points and target."""
         if kind not in self.FGM_KINDS:
             raise IfdError("unknown attack %r (fgm | ifgm | mifgm | pgd)" % (kind,))
         loss_kind = self._loss_kind(loss)
@@ -861,13 +871,15 @@ class Classifier:
         if B < 1 or stride < 1:
             raise IfdError("empty batch")
         target = self._target(target, B)
+        held = extra(B) if extra else ()                               # the tensors stay alive until the call has been made
+        between = [None if t is None else t.data_ptr() for t in held]
         out = torch.empty_like(pc)
         success = torch.empty(B, device=self.device, dtype=torch.int32)
         P = _lib.IfdFgmParams(C.sizeof(_lib.IfdFgmParams), self.FGM_KINDS[kind], loss_kind, int(num_iter), float(kappa), float(scale),
                               float(step_size), float(budget), float(mu))
         with torch.cuda.device(self.device):
             self._check(getattr(self.lib, self.ATK_FNS["fgm_attack"])(
-                self.ctx, C.byref(P), pc.data_ptr(), None if n_points is None else n_points.data_ptr(), target.data_ptr(), B, stride,
+                self.ctx, C.byref(P), pc.data_ptr(), None if n_points is None else n_points.data_ptr(), *between, target.data_ptr(), B, stride,
                 out.data_ptr(), success.data_ptr(), self._stream()))
         return out, success.bool()
 
@@ -1521,20 +1533,23 @@ class PointNet2Classifier(Classifier):
     ``weights.pack_state_dict(state_dict, "pointnet2")``).  Inputs are Classifier's: [B,N,3] batches (point-major), lists and
     object arrays of ragged clouds of 1 to 2048 points.  ``fps_start`` [B,2] int: the first pick of the level-1 sampling (below
     the cloud's count) and of the level-2 sampling (below 512); None means 0, 0 - the reference draws them at random, here
-    they are an input.  A cloud's outputs do not depend on how it is batched or padded.  The attack entry points of Classifier
-    are PointNet's and are not offered here."""
+    they are an input.  A cloud's outputs do not depend on how it is batched or padded.
+
+    Of the attack entry points, ``input_grad``, ``fgm_update`` and ``fgm_attack`` run on this victim (include/ifd_pn2_atk.h),
+    with Classifier's signatures and return shapes plus ``fps_start=None``, so attack.FGM / IFGM / MIFGM / PGD work on it
+    unchanged; the gradient is the one of the network with its four index tables held fixed, the tables being the forward's on
+    the current cloud.  The other attack methods are PointNet's, and the library refuses them on a PointNet++ context."""
 
     MAX_POINTS = _lib.PN2_MAX_POINTS
+    ATK_FNS = {"input_grad": "ifd_pn2_input_grad", "fgm_update": "ifd_pn2_fgm_update", "fgm_attack": "ifd_pn2_fgm_attack"}
 
     def __init__(self, weights: np.ndarray, device=None):
         self.lib = _lib.load()
         self.feature_transform = False
         self._create("ifd_pn2_create", self.lib.ifd_pn2_weight_count(), "pointnet2 weights", weights, device)
 
-    def logits(self, pc, n_points=None, fps_start=None, want_aux: bool = False, want_pred: bool = False):
-        """pc, n_points: as Classifier.logits.  Returns logits [B,40]; with want_aux also {"fps1" [B,512], "fps2" [B,128],
-        "ball1" [B,512,32], "ball2" [B,128,64] (int32), "l1_feat" [B,512,128], "l2_feat" [B,128,256], "global_feat" [B,1024],
-        "pred" [B] int32}."""
+    def _starts(self, fps_start):
+        """-> extra(B) of _forward / _input_grad / _fgm_attack: fps_start as [B,2] int32 on the device, or None."""
         def starts(B):
             if fps_start is None:
                 return (None,)
@@ -1542,6 +1557,45 @@ class PointNet2Classifier(Classifier):
             if tuple(t.shape) != (B, 2):
                 raise IfdError("fps_start must be [B,2], got %s" % (tuple(t.shape),))
             return (t,)
+        return starts
+
+    def _grad_aux(self, B, stride):
+        """input_grad's diagnostics on this victim: {"logits" [B,40], "loss" [B], "pred" [B], the tables and features of
+        ``logits``' aux, "win1" [B,512,128], "win2" [B,128,256], "win3" [B,1024] int32 (the sample position, resp. row, holding each
+        group maximum), "act1" [B,512,32,4], "act2" [B,128,64,8], "act3" [B,128,24] int32 (gate bits of the hidden layers: bit c % 32
+        of a layer's word c // 32 is set where its pre-activation of channel c is > 0)}."""
+        n1, s1, n2, s2 = _lib.PN2_NPOINT1, _lib.PN2_NSAMPLE1, _lib.PN2_NPOINT2, _lib.PN2_NSAMPLE2
+        i32, f32 = dict(device=self.device, dtype=torch.int32), dict(device=self.device, dtype=torch.float32)
+        aux = dict(logits=torch.empty(B, self.N_CLASSES, **f32), loss=torch.empty(B, **f32), pred=torch.empty(B, **i32),
+                   fps1=torch.empty(B, n1, **i32), fps2=torch.empty(B, n2, **i32), ball1=torch.empty(B, n1, s1, **i32),
+                   ball2=torch.empty(B, n2, s2, **i32), l1_feat=torch.empty(B, n1, 128, **f32), l2_feat=torch.empty(B, n2, 256, **f32),
+                   global_feat=torch.empty(B, 1024, **f32), win1=torch.empty(B, n1, 128, **i32), win2=torch.empty(B, n2, 256, **i32),
+                   win3=torch.empty(B, 1024, **i32), act1=torch.empty(B, n1, s1, 4, **i32), act2=torch.empty(B, n2, s2, 8, **i32),
+                   act3=torch.empty(B, n2, 24, **i32))
+        st = _lib.IfdPn2GradOut()
+        for name, t in aux.items():
+            setattr(st, name, t.data_ptr())
+        return aux, st
+
+    def input_grad(self, pc, target, loss="logits", kappa=0., scale=1., n_points=None, want_aux: bool = False, fps_start=None):
+        """Classifier.input_grad on this victim (ifd_pn2_input_grad); fps_start as ``logits`` takes it; want_aux: see _grad_aux."""
+        return self._input_grad(pc, target, loss, kappa, scale, n_points, want_aux, extra=self._starts(fps_start))
+
+    def fgm_attack(self, kind, pc, target, budget, step_size, num_iter=1, mu=1., loss="logits", kappa=0., scale=1., n_points=None,
+                   fps_start=None):
+        """Classifier.fgm_attack on this victim (ifd_pn2_fgm_attack): the same fps_start in every iteration and in the last forward."""
+        return self._fgm_attack(kind, pc, target, budget, step_size, num_iter, mu, loss, kappa, scale, n_points,
+                                extra=self._starts(fps_start))
+
+    def fgm_update(self, kind, grad, pc, ori_pc=None, momentum=None, step_size=0., budget=0., mu=1., n_points=None, fps_start=None):
+        """Classifier.fgm_update on this victim (ifd_pn2_fgm_update); the update does not sample, fps_start is accepted and unused."""
+        return super().fgm_update(kind, grad, pc, ori_pc, momentum, step_size, budget, mu, n_points)
+
+    def logits(self, pc, n_points=None, fps_start=None, want_aux: bool = False, want_pred: bool = False):
+        """pc, n_points: as Classifier.logits.  Returns logits [B,40]; with want_aux also {"fps1" [B,512], "fps2" [B,128],
+        "ball1" [B,512,32], "ball2" [B,128,64] (int32), "l1_feat" [B,512,128], "l2_feat" [B,128,256], "global_feat" [B,1024],
+        "pred" [B] int32}."""
+        starts = self._starts(fps_start)
 
         def aux_table(B, stride):
             n1, s1, n2, s2 = _lib.PN2_NPOINT1, _lib.PN2_NSAMPLE1, _lib.PN2_NPOINT2, _lib.PN2_NSAMPLE2
