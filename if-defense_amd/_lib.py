@@ -407,6 +407,26 @@ PC_SIGNATURES = {
                                  C.c_void_p]),
 }
 
+# include/ifd_pc_atk.h (input gradients of the PointConv victim and the FGM family on it), versioned on its own
+PC_ATK_ABI_VERSION = 1
+
+
+class IfdPcGradOut(C.Structure):
+    _fields_ = [(name, C.c_void_p) for name in (
+        "logits", "loss", "pred", "fps1", "fps2", "knn1", "knn2", "dens1", "dens2", "dens3", "l1_feat", "l2_feat", "global_feat",
+        "dgate1", "dgate2", "dgate3", "wgate1", "wgate2", "wgate3", "mgate1", "mgate2", "mgate3")]
+
+
+PC_ATK_SIGNATURES = {
+    "ifd_pc_atk_abi_version": (C.c_int, []),
+    "ifd_pc_input_grad": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_float,
+                                    C.c_float, C.c_void_p, C.POINTER(IfdPcGradOut), C.c_void_p]),
+    "ifd_pc_fgm_update": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_float,
+                                    C.c_float, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
+    "ifd_pc_fgm_attack": (C.c_int, [C.c_void_p, C.POINTER(IfdFgmParams), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
+                                    C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+}
+
 _lib = None
 
 
@@ -425,7 +445,7 @@ def load() -> C.CDLL:
             list(ATK_SIGNATURES.items()) + list(CW_SIGNATURES.items()) + list(KNN_SIGNATURES.items()) + list(ADD_SIGNATURES.items()) + \
             list(DROP_SIGNATURES.items()) + list(CLUSTER_SIGNATURES.items()) + list(OBJECT_SIGNATURES.items()) + \
             list(DGCNN_SIGNATURES.items()) + list(DGCNN_ATK_SIGNATURES.items()) + list(PN2_SIGNATURES.items()) + \
-            list(PN2_ATK_SIGNATURES.items()) + list(PC_SIGNATURES.items()):
+            list(PN2_ATK_SIGNATURES.items()) + list(PC_SIGNATURES.items()) + list(PC_ATK_SIGNATURES.items()):
         fn = getattr(lib, name)          # AttributeError if the library lacks a declared symbol
         fn.restype, fn.argtypes = res, args
     if lib.ifd_abi_version() != ABI_VERSION:
@@ -460,5 +480,8 @@ def load() -> C.CDLL:
                           (lib.ifd_pn2_atk_abi_version(), PN2_ATK_ABI_VERSION))
     if lib.ifd_pc_abi_version() != PC_ABI_VERSION:
         raise ImportError("libifd.so PC ABI %d != binding PC ABI %d; rebuild" % (lib.ifd_pc_abi_version(), PC_ABI_VERSION))
+    if lib.ifd_pc_atk_abi_version() != PC_ATK_ABI_VERSION:
+        raise ImportError("libifd.so PC ATK ABI %d != binding PC ATK ABI %d; rebuild" %
+                          (lib.ifd_pc_atk_abi_version(), PC_ATK_ABI_VERSION))
     _lib = lib
     return lib

@@ -19,6 +19,7 @@
 #include "../../include/ifd_pc.h"
 #include "../../include/ifd_pn2.h"
 #include "../../include/ifd_pn2_atk.h"
+#include "../../include/ifd_pc_atk.h"
 
 #include <hip/hip_runtime.h>
 
@@ -161,6 +162,7 @@ struct ifd_ctx {
     Pn2Image p2img{};
     Pn2GradImage p2gimg{};         // ... and its backward pass's image, in d_cls_grad (include/ifd_pn2_atk.h)
     PcImage pcimg{};               // PointConv (pointconv.hip)
+    PcGradImage pcgimg{};          // ... and its backward pass's image, in d_cls_grad (include/ifd_pc_atk.h)
     std::string err;
     unsigned long long* counters() const { return d_counters.get<unsigned long long>(); }
 };
@@ -2141,26 +2143,50 @@ PcWs pc_ws(Carve& c, size_t n) {
 }
 size_t pc_ws_bytes(int n) { return carved_bytes([&](Carve& c) { pc_ws(c, (size_t)n); }); }
 
-}  // namespace
-
-extern "C" {
-
-int ifd_pc_abi_version(void) { return IFD_PC_ABI_VERSION; }
-
-size_t ifd_pc_weight_count(void) { return pc_count(); }
-
-ifd_ctx* ifd_pc_create(const float* weights_host, size_t n_weights, int n_classes, int device) {
-    if (!victim_create_args_ok("ifd_pc_create", weights_host, n_weights, pc_count(), n_classes)) return nullptr;
-    return create_ctx("ifd_pc_create", IFD_MODEL_PC, device, [&](ifd_ctx* ctx) {
-        ctx->cls_classes = n_classes;
-        hipError_t e = upload(ctx->d_victim, build_pc_image(weights_host, ctx->pcimg));
-        if (e == hipSuccess) e = configure_pc_kernels();
-        return e;
-    });
+// The backward pass's image (ifd_internal.h PcGradImage) from the forward's: every dense layer transposed, on one block of zeros as
+// the bias of all.
+std::vector<float> build_pc_grad_image(const std::vector<float>& f, const PcImage& I, PcGradImage& G) {
+    std::vector<float> img((size_t)PC_EMB * PC_WN, 0.f);               // the zero bias
+    auto transposed = [&](const DenseLayer& L, int pad_out) { return append_transposed_layer(img, f, L, pad_out); };
+    for (int j = 0; j < 3; ++j) G.fct[j] = transposed(I.fc[j], (I.fc[j].n_out + 63) / 64 * 64);
+    for (int l = 0; l < 3; ++l) {
+        const PcLevel& S = I.sa[l];
+        PcGradLevel& T = G.sa[l];
+        T.lint = transposed(S.lin, S.lin.n_out);
+        T.w3t = transposed(S.mlp[1], S.mlp[1].n_out);
+        T.w2t = transposed(S.mlp[0], S.mlp[0].n_out);
+        T.ut = l == 0 ? DenseLayer{} : transposed(S.u, S.u.n_out);
+        T.xt = l == 2 ? transposed(DenseLayer{S.first_xyz, 0, S.u.n_out, 4}, S.u.n_out) : DenseLayer{};   // the [256][4] rows {w0, w1, w2, 0}
+    }
+    G.total = (int)img.size();
+    return img;
 }
 
-int ifd_pc_forward(ifd_ctx* ctx, const float* pc, const int32_t* n_points, const int32_t* fps_start, int B, int stride, float* logits,
-                   const ifd_pc_aux* aux, void* stream) {
+// the workspace of ifd_pc_input_grad over n clouds: ifd_pc_forward's (whose first 1024 bytes the check uses), then the backward's
+PcGradWs pc_grad_ws(Carve& c, size_t n) {
+    PcGradWs w;
+    w.f = pc_ws(c, n);
+    c.round_up(256);
+    w.logits = c.take<float>(n * 160); w.d_out = c.take<float>(n * 256); w.d2 = c.take<float>(n * 1024); w.d1 = c.take<float>(n * 2048);
+    w.dg = c.take<float>(n * PC_EMB * 4);
+    w.ds3c = c.take<float>(n * PC_NP2 * PC_EMB * 4); w.ds3b = c.take<float>(n * PC_NP2 * 512 * 4); w.ds3a = c.take<float>(n * PC_NP2 * 256 * 4);
+    w.dl2 = c.take<float>(n * PC_NP2 * 256 * 4);
+    w.dx3m = c.take<float>(n * PC_NP2 * 16); w.dwn3 = c.take<float>(n * PC_NP2 * 16); w.ds3 = c.take<float>(n * PC_NP2 * 4);
+    w.aj = c.take<float>(n * PC_MAX_POINTS * 4);
+    w.dx2a = c.take<float>(n * PC_NP2 * 16); w.dx2 = c.take<float>(n * PC_NP2 * 16);
+    w.dh = c.take<float>(n * PC_NP2 * PC_K2 * 128 * 4); w.de = c.take<float>(n * PC_NP2 * PC_K2 * 16);
+    w.du = c.take<float>(n * PC_NP1 * 128 * 4); w.dx1a = c.take<float>(n * PC_NP1 * 16); w.ds2 = c.take<float>(n * PC_NP1 * 4);
+    w.dl1 = c.take<float>(n * PC_NP1 * 128 * 4);
+    w.dd = c.take<float>(n * PC_NP1 * PC_K1 * 16); w.dx1 = c.take<float>(n * PC_NP1 * 16);
+    w.gpre = c.take<float>(n * PC_MAX_POINTS * 16); w.ds1 = c.take<float>(n * PC_MAX_POINTS * 4);
+    w.pred = c.take<int32_t>(n * 4); w.loss = c.take<float>(n * 4);
+    return w;
+}
+
+// ifd_pc_forward; check = false skips the blocking check (the caller has made it), ws_off: bytes at the front of the workspace that
+// belong to the caller (ifd_pc_fgm_attack's loop state)
+int pc_forward_impl(ifd_ctx* ctx, const float* pc, const int32_t* n_points, const int32_t* fps_start, int B, int stride, float* logits,
+                    const ifd_pc_aux* aux, void* stream, bool check, size_t ws_off) {
     if (!ctx) return IFD_ERR_ARG;
     if (ctx->model != IFD_MODEL_PC || !ctx->d_victim.get()) return fail(ctx, IFD_ERR_ARG, "ifd_pc_forward: not a PointConv context");
     if (!pc || !logits || B < 1) return fail(ctx, IFD_ERR_ARG, "ifd_pc_forward: bad argument (pc, logits, B >= 1)");
@@ -2169,9 +2195,9 @@ int ifd_pc_forward(ifd_ctx* ctx, const float* pc, const int32_t* n_points, const
     hipStream_t s = static_cast<hipStream_t>(stream);
     const int nc = ctx->cls_classes;
     return victim_forward(
-        ctx, "ifd_pc_forward", B, PC_CHUNK, 0, [&](int chunk) { return pc_ws_bytes(chunk); },
+        ctx, "ifd_pc_forward", B, PC_CHUNK, ws_off, [&](int chunk) { return pc_ws_bytes(chunk); },
         [&](char* base) {
-            if (!n_points && !fps_start) return (int)IFD_OK;
+            if (!check || (!n_points && !fps_start)) return (int)IFD_OK;
             int32_t bad[2] = {0, 0};
             if (int rc = read_bad_counts(ctx, "ifd_pc_forward", "n_points and fps_start",
                                          launch_pc_check(n_points, fps_start, B, stride, reinterpret_cast<int32_t*>(base), s), base, 2, bad, s))
@@ -2202,6 +2228,32 @@ int ifd_pc_forward(ifd_ctx* ctx, const float* pc, const int32_t* n_points, const
             return launch_pc(ctx->d_victim.get<float>(), ctx->pcimg, pc + (size_t)c0 * stride * 3, n_points ? n_points + c0 : nullptr,
                              fps_start ? fps_start + (size_t)c0 * 2 : nullptr, n, stride, w, o, logits + (size_t)c0 * nc, nc, s);
         });
+}
+
+}  // namespace
+
+extern "C" {
+
+int ifd_pc_abi_version(void) { return IFD_PC_ABI_VERSION; }
+
+size_t ifd_pc_weight_count(void) { return pc_count(); }
+
+ifd_ctx* ifd_pc_create(const float* weights_host, size_t n_weights, int n_classes, int device) {
+    if (!victim_create_args_ok("ifd_pc_create", weights_host, n_weights, pc_count(), n_classes)) return nullptr;
+    return create_ctx("ifd_pc_create", IFD_MODEL_PC, device, [&](ifd_ctx* ctx) {
+        ctx->cls_classes = n_classes;
+        const std::vector<float> img = build_pc_image(weights_host, ctx->pcimg);
+        hipError_t e = upload(ctx->d_victim, img);
+        if (e == hipSuccess) e = upload(ctx->d_cls_grad, build_pc_grad_image(img, ctx->pcimg, ctx->pcgimg));
+        if (e == hipSuccess) e = configure_pc_kernels();
+        if (e == hipSuccess) e = configure_pc_grad_kernels();
+        return e;
+    });
+}
+
+int ifd_pc_forward(ifd_ctx* ctx, const float* pc, const int32_t* n_points, const int32_t* fps_start, int B, int stride, float* logits,
+                   const ifd_pc_aux* aux, void* stream) {
+    return pc_forward_impl(ctx, pc, n_points, fps_start, B, stride, logits, aux, stream, true, 0);
 }
 
 }  // extern "C"
@@ -2776,6 +2828,158 @@ int ifd_pn2_fgm_attack(ifd_ctx* ctx, const ifd_fgm_params* params, const float* 
     if (int rc = pn2_forward_impl(ctx, pc_out, n_points, fps_start, B, stride, L.logits, &aux, stream, false, state)) return rc;
     e = launch_atk_success(L.pred, target, B, success, s);
     if (e != hipSuccess) return fail(ctx, IFD_ERR_HIP, "ifd_pn2_fgm_attack: success", e);
+    return IFD_OK;
+}
+
+}  // extern "C"
+
+// ---- attacks on the PointConv victim (include/ifd_pc_atk.h) -----------------------------------------------------------
+namespace {
+
+int pc_atk_context_ok(ifd_ctx* ctx, const char* who) {
+    if (ctx->model != IFD_MODEL_PC || !ctx->d_victim.get() || !ctx->d_cls_grad.get())
+        return fail(ctx, IFD_ERR_ARG, (std::string(who) + ": not a PointConv context").c_str());
+    return IFD_OK;
+}
+int pc_atk_stride_ok(ifd_ctx* ctx, const char* who, int stride) {
+    if (stride >= IFD_PC_MIN_POINTS && stride <= IFD_PC_MAX_POINTS) return IFD_OK;
+    return fail(ctx, IFD_ERR_ARG, (std::string(who) + ": stride " + std::to_string(stride) + " outside [32, 2048]").c_str());
+}
+
+int pc_atk_chunk(int B) {                    // the forward's chunks
+    const int n_chunks = (B + PC_CHUNK - 1) / PC_CHUNK;
+    return (B + n_chunks - 1) / n_chunks;
+}
+size_t pc_grad_ws_bytes(int B) { return carved_bytes([&](Carve& c) { pc_grad_ws(c, (size_t)pc_atk_chunk(B)); }); }
+
+// the one blocking step of the PointConv attack calls: counts and starts (launch_pc_check) and targets (launch_atk_check), four
+// counters at the start of the workspace, read together
+int pc_atk_check(ifd_ctx* ctx, const char* who, const int32_t* n_points, const int32_t* fps_start, const int32_t* target, int B, int stride,
+                 hipStream_t s) {
+    int32_t* d_bad = ctx->ws.get<int32_t>();
+    hipError_t e = launch_pc_check(n_points, fps_start, B, stride, d_bad, s);
+    if (e == hipSuccess) e = launch_atk_check(nullptr, target, B, 1, stride, ctx->cls_classes, d_bad + 2, s);
+    int32_t bad[4] = {0, 0, 0, 0};
+    if (int rc = read_bad_counts(ctx, who, "n_points, fps_start and target", e, d_bad, 4, bad, s)) return rc;
+    if (bad[0] != 0)
+        return fail(ctx, IFD_ERR_ARG, (std::string(who) + ": " + std::to_string(bad[0]) + " cloud(s) with n_points outside [32, stride]").c_str());
+    if (bad[1] != 0)
+        return fail(ctx, IFD_ERR_ARG,
+                    (std::string(who) + ": " + std::to_string(bad[1]) + " cloud(s) with fps_start outside [0, n_points) x [0, 512)").c_str());
+    if (bad[3] != 0)
+        return fail(ctx, IFD_ERR_ARG, (std::string(who) + ": " + std::to_string(bad[3]) + " target(s) outside [0, 40)").c_str());
+    return IFD_OK;
+}
+
+// ifd_pc_input_grad on workspace that is already large enough (ws_off: bytes in front that belong to the caller), unchecked
+int pc_input_grad_impl(ifd_ctx* ctx, size_t ws_off, const float* pc, const int32_t* n_points, const int32_t* fps_start, int B, int stride,
+                       const int32_t* target, int loss_kind, float kappa, float scale, float* grad, const ifd_pc_grad_out* out, hipStream_t s) {
+    const int chunk = pc_atk_chunk(B), nc = ctx->cls_classes;
+    for (int c0 = 0; c0 < B; c0 += chunk) {
+        const size_t n = (size_t)std::min(chunk, B - c0), st = (size_t)stride, at = (size_t)c0;
+        Carve c(ctx->ws.get<char>() + ws_off);
+        const PcGradWs w = pc_grad_ws(c, n);
+        PcGradOut o{};
+        if (out) {
+            auto off = [&](auto* p, size_t per_cloud) { return p ? p + at * per_cloud : nullptr; };
+            o.f.fps1 = off(out->fps1, PC_NP1); o.f.fps2 = off(out->fps2, PC_NP2);
+            o.f.knn1 = off(out->knn1, PC_NP1 * PC_K1); o.f.knn2 = off(out->knn2, PC_NP2 * PC_K2);
+            o.f.dens1 = off(out->dens1, st); o.f.dens2 = off(out->dens2, PC_NP1); o.f.dens3 = off(out->dens3, PC_NP2);
+            o.f.l1_feat = off(out->l1_feat, PC_NP1 * 128); o.f.l2_feat = off(out->l2_feat, PC_NP2 * 256);
+            o.f.gfeat = off(out->global_feat, PC_EMB);
+            o.dgate1 = off(out->dgate1, st); o.dgate2 = off(out->dgate2, PC_NP1); o.dgate3 = off(out->dgate3, PC_NP2);
+            o.wgate1 = off(out->wgate1, PC_NP1 * PC_K1); o.wgate2 = off(out->wgate2, PC_NP2 * PC_K2); o.wgate3 = off(out->wgate3, PC_NP2);
+            o.mgate1 = off(out->mgate1, PC_NP1 * PC_K1 * 8); o.mgate2 = off(out->mgate2, PC_NP2 * PC_K2 * 16);
+            o.mgate3 = off(out->mgate3, PC_NP2 * 56);
+        }
+        hipError_t e = launch_pc_grad(ctx->d_victim.get<float>(), ctx->pcimg, ctx->d_cls_grad.get<float>(), ctx->pcgimg, pc + at * st * 3,
+                                      n_points ? n_points + c0 : nullptr, fps_start ? fps_start + at * 2 : nullptr, (int)n, stride,
+                                      target + c0, loss_kind, kappa, scale, w, o, nc, grad + at * st * 3, s);
+        auto copy = [&](void* dst, const void* src, size_t bytes_per_cloud) {
+            if (e == hipSuccess && dst)
+                e = hipMemcpyAsync(static_cast<char*>(dst) + at * bytes_per_cloud, src, n * bytes_per_cloud, hipMemcpyDeviceToDevice, s);
+        };
+        if (out) {
+            copy(out->logits, w.logits, 160);
+            copy(out->loss, w.loss, 4);
+            copy(out->pred, w.pred, 4);
+        }
+        if (e != hipSuccess) return fail(ctx, IFD_ERR_HIP, "ifd_pc_input_grad launch", e);
+    }
+    return IFD_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int ifd_pc_atk_abi_version(void) { return IFD_PC_ATK_ABI_VERSION; }
+
+int ifd_pc_input_grad(ifd_ctx* ctx, const float* pc, const int32_t* n_points, const int32_t* fps_start, int B, int stride,
+                      const int32_t* target, int loss_kind, float kappa, float scale, float* grad, const ifd_pc_grad_out* out, void* stream) {
+    if (!ctx) return IFD_ERR_ARG;
+    if (int rc = pc_atk_context_ok(ctx, "ifd_pc_input_grad")) return rc;
+    if (!pc || !target || !grad || B < 1) return fail(ctx, IFD_ERR_ARG, "ifd_pc_input_grad: bad argument (pc, target, grad; B >= 1)");
+    if (int rc = pc_atk_stride_ok(ctx, "ifd_pc_input_grad", stride)) return rc;
+    if (!atk_loss_ok(loss_kind)) return fail(ctx, IFD_ERR_ARG, "ifd_pc_input_grad: unknown loss_kind");
+    IFD_ON_CTX_DEVICE(ctx);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    hipError_t e = ctx->ws.grow(pc_grad_ws_bytes(B));
+    if (e != hipSuccess) return fail(ctx, IFD_ERR_NOMEM, "ifd_pc_input_grad: workspace", e);
+    if (int rc = pc_atk_check(ctx, "ifd_pc_input_grad", n_points, fps_start, target, B, stride, s)) return rc;
+    return pc_input_grad_impl(ctx, 0, pc, n_points, fps_start, B, stride, target, loss_kind, kappa, scale, grad, out, s);
+}
+
+int ifd_pc_fgm_update(ifd_ctx* ctx, int kind, const float* grad, float* pc, const float* ori_pc, float* momentum, float step_size,
+                      float budget, float mu, const int32_t* n_points, int B, int stride, void* stream) {
+    if (!ctx) return IFD_ERR_ARG;
+    if (int rc = pc_atk_context_ok(ctx, "ifd_pc_fgm_update")) return rc;
+    if (!atk_kind_ok(kind)) return fail(ctx, IFD_ERR_ARG, "ifd_pc_fgm_update: unknown kind");
+    if (!grad || !pc || B < 1 || stride < IFD_PC_MIN_POINTS || stride > IFD_PC_MAX_POINTS || (kind != IFD_FGM_FGM && !ori_pc) ||
+        (kind == IFD_FGM_MIFGM && !momentum))
+        return fail(ctx, IFD_ERR_ARG, "ifd_pc_fgm_update: bad argument (grad, pc; ori_pc unless FGM; momentum for MIFGM; 32 <= stride <= 2048)");
+    IFD_ON_CTX_DEVICE(ctx);
+    hipError_t e = launch_fgm_update(kind, grad, pc, ori_pc, momentum, step_size, budget, mu, n_points, B, stride,
+                                     static_cast<hipStream_t>(stream));
+    if (e != hipSuccess) return fail(ctx, IFD_ERR_HIP, "ifd_pc_fgm_update launch", e);
+    return IFD_OK;
+}
+
+int ifd_pc_fgm_attack(ifd_ctx* ctx, const ifd_fgm_params* params, const float* pc_in, const int32_t* n_points, const int32_t* fps_start,
+                      const int32_t* target, int B, int stride, float* pc_out, int32_t* success, void* stream) {
+    if (!ctx) return IFD_ERR_ARG;
+    if (int rc = pc_atk_context_ok(ctx, "ifd_pc_fgm_attack")) return rc;
+    if (!params || params->struct_size != (int32_t)sizeof(ifd_fgm_params))
+        return fail(ctx, IFD_ERR_ARG, "ifd_pc_fgm_attack: params missing or of another struct_size");
+    if (!atk_kind_ok(params->kind) || !atk_loss_ok(params->loss_kind) || params->num_iter < 1)
+        return fail(ctx, IFD_ERR_ARG, "ifd_pc_fgm_attack: unknown kind or loss_kind, or num_iter < 1");
+    if (!pc_in || !target || !pc_out || !success || pc_in == pc_out || B < 1)
+        return fail(ctx, IFD_ERR_ARG, "ifd_pc_fgm_attack: bad argument (pc_in, target, pc_out, success; B >= 1)");
+    if (int rc = pc_atk_stride_ok(ctx, "ifd_pc_fgm_attack", stride)) return rc;
+    IFD_ON_CTX_DEVICE(ctx);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const size_t cloud = (size_t)stride * 12, state = carved_bytes([&](Carve& c) { FgmLoop(c, (size_t)B, cloud); });
+    hipError_t e = ctx->ws.grow(state + pc_grad_ws_bytes(B));          // the final forward's workspace is the front of the gradient's
+    if (e != hipSuccess) return fail(ctx, IFD_ERR_NOMEM, "ifd_pc_fgm_attack: workspace", e);
+    if (int rc = pc_atk_check(ctx, "ifd_pc_fgm_attack", n_points, fps_start, target, B, stride, s)) return rc;
+    Carve c(ctx->ws.get());
+    const FgmLoop L(c, (size_t)B, cloud);
+    e = hipMemcpyAsync(pc_out, pc_in, (size_t)B * cloud, hipMemcpyDeviceToDevice, s);
+    if (e == hipSuccess && params->kind == IFD_FGM_MIFGM) e = hipMemsetAsync(L.mom, 0, (size_t)B * cloud, s);
+    if (e != hipSuccess) return fail(ctx, IFD_ERR_HIP, "ifd_pc_fgm_attack: start", e);
+    const int iters = params->kind == IFD_FGM_FGM ? 1 : params->num_iter;
+    for (int it = 0; it < iters; ++it) {
+        if (int rc = pc_input_grad_impl(ctx, state, pc_out, n_points, fps_start, B, stride, target, params->loss_kind, params->kappa,
+                                        params->scale, L.grad, nullptr, s))
+            return rc;
+        e = launch_fgm_update(params->kind, L.grad, pc_out, pc_in, L.mom, params->step_size, params->budget, params->mu, n_points, B, stride, s);
+        if (e != hipSuccess) return fail(ctx, IFD_ERR_HIP, "ifd_pc_fgm_attack: update", e);
+    }
+    ifd_pc_aux aux{};
+    aux.pred = L.pred;
+    if (int rc = pc_forward_impl(ctx, pc_out, n_points, fps_start, B, stride, L.logits, &aux, stream, false, state)) return rc;
+    e = launch_atk_success(L.pred, target, B, success, s);
+    if (e != hipSuccess) return fail(ctx, IFD_ERR_HIP, "ifd_pc_fgm_attack: success", e);
     return IFD_OK;
 }
 

@@ -656,4 +656,57 @@ hipError_t launch_pc_check(const int32_t* n_points, const int32_t* fps_start, in
 hipError_t launch_pc(const float* img, const PcImage& I, const float* pc, const int32_t* n_points, const int32_t* fps_start, int B,
                      int stride, const PcWs& w, const PcOut& out, float* logits, int n_classes, hipStream_t s);
 
+
+// ---- PointConv input gradients (pointconv_grad.hip; C ABI in include/ifd_pc_atk.h) --------------------------------------
+// The backward pass's weight image (api.cpp build_pc_grad_image): every dense layer transposed as Pn2GradImage's are, all on one
+// block of zeros as their bias.
+struct PcGradLevel {
+    DenseLayer lint;                    // the wide linear^T [16 C][C]
+    DenseLayer w3t, w2t;                // the MLP's last and middle layers^T
+    DenseLayer ut, xt;                  // sa2, sa3: the first layer's feature columns^T; sa3: its coordinate columns^T [4][256] (row 3 zero)
+};
+struct PcGradImage {
+    DenseLayer fct[3];                  // fc1^T [1024][512], fc2^T [512][256], fc3^T [256][64] (40 inputs padded with zero columns)
+    PcGradLevel sa[3];
+    int total;
+};
+struct PcGradWs {                       // per-chunk scratch of launch_pc_grad (api.cpp pc_grad_ws)
+    PcWs f;                             // the forward's; f.g holds d G of the level at work
+    float* logits;      // [B][40]
+    int32_t* pred;      // [B]
+    float* loss;        // [B]
+    float* d_out;       // [B][64]
+    float* d2;          // [B][256]
+    float* d1;          // [B][512]
+    float* dg;          // [B][1024]          d loss / d global_feat
+    float* ds3c;        // [B][128][1024]     d F of sa3 under its gate
+    float* ds3b;        // [B][128][512]
+    float* ds3a;        // [B][128][256]
+    float* dl2;         // [B][128][256]
+    float* dx3m;        // [B][128][4]        sa3's coordinate columns transposed
+    float* dwn3;        // [B][128][4]        sa3's WeightNet term of d (xyz2 - mean)
+    float* ds3;         // [B][128]           d s of the level-2 centroids
+    float* aj;          // [B][2048]          a_j of the density at work
+    float* dx2a;        // [B][128][4]        d xyz2 but for sa2's own term
+    float* dx2;         // [B][128][4]        d xyz2
+    float* dh;          // [B][128][64][128]  sa2's first-layer gradient per row
+    float* de;          // [B][128][64][4]    per row of sa2: d (xyz1_j - xyz2_g), and d s_j in the fourth place
+    float* du;          // [B][512][128]
+    float* dx1a;        // [B][512][4]        d xyz1 but for sa1's own term
+    float* ds2;         // [B][512]           d s of the level-1 centroids
+    float* dl1;         // [B][512][128]
+    float* dd;          // [B][512][32][4]    per row of sa1: d (x_j - xyz1_i), and d s_j in the fourth place
+    float* dx1;         // [B][512][4]        d xyz1
+    float* gpre;        // [B][2048][4]       the gradient but for the level-1 density's term
+    float* ds1;         // [B][2048]          d s of the cloud's points
+};
+struct PcGradOut {                      // ifd_pc_grad_out's members that the kernels write themselves; null: not wanted
+    PcOut f;
+    uint32_t *dgate1, *dgate2, *dgate3, *wgate1, *wgate2, *wgate3, *mgate1, *mgate2, *mgate3;
+};
+hipError_t configure_pc_grad_kernels();
+hipError_t launch_pc_grad(const float* img, const PcImage& I, const float* gimg, const PcGradImage& G, const float* pc,
+                          const int32_t* n_points, const int32_t* fps_start, int B, int stride, const int32_t* target, int loss_kind,
+                          float kappa, float scale, const PcGradWs& w, const PcGradOut& out, int n_classes, float* grad, hipStream_t s);
+
 }  // namespace ifd

@@ -409,6 +409,39 @@ using PcSa2Lds = PcSaLds<128 + 4>;
 static_assert(PcDensityLds::BYTES == 24576 && PcSa1Lds::BYTES == 39168 && PcSa2Lds::BYTES == 71936 && PcSa2Lds::BYTES <= LDS_MAX_BYTES,
               "LDS of the PointConv kernels");
 
+// ---- pointconv_grad.hip ------------------------------------------------------------------------------------------------------
+template <int LD_, int C_>
+struct PcSaBwdLds {                                  // pc_sa1_bwd_kernel (LD 68, 2 x 128 channels), pc_sa2_bwd_kernel (LD 132, 256 channels)
+    static constexpr int LD = LD_, XLD = 64 + 4;
+    static constexpr size_t A = 0;                                         // float [64][LD] the first layer; then [64][XLD] 64 channels of F, then of
+                                                                           // d F; at the end d a2 [64][LD]
+    static constexpr size_t B = A + (size_t)64 * LD * 4;                   // float [64][LD] the second layer; then d a1 before its gate
+    static constexpr size_t DG = B + (size_t)64 * LD * 4;                  // float [C][PC_WN] d G of the tile's group(s)
+    static constexpr size_t WN = DG + (size_t)C_ * PC_WN * 4;              // float [64][PC_WN] WeightNet of the rows
+    static constexpr size_t S = WN + (size_t)64 * PC_WN * 4;               // float [64] the rows' density scales
+    static constexpr size_t DD = S + 64 * 4;                               // float [64][4] d (x_j - c_i) of the rows
+    static constexpr size_t BYTES = DD + 64 * 16;
+};
+using PcSa1BwdLds = PcSaBwdLds<64 + 4, 2 * 128>;
+using PcSa2BwdLds = PcSaBwdLds<128 + 4, 256>;
+struct PcSa3BwdLds {                                 // pc_sa3_bwd_kernel
+    static constexpr size_t RED = 0;                                       // float [4 waves][PC_WN + 1] the waves' sums of d Wn and d s
+    static constexpr size_t BYTES = RED + 4 * (PC_WN + 1) * 4;
+};
+struct PcDensityBwdLds {                             // pc_density_a_kernel, pc_density_nbody_kernel: the level's input cloud and its a_j
+    static constexpr size_t X = 0;                                         // float [PC_MAX_POINTS][3]
+    static constexpr size_t AJ = X + (size_t)PC_MAX_POINTS * 12;           // float [PC_MAX_POINTS]
+    static constexpr size_t BYTES = AJ + (size_t)PC_MAX_POINTS * 4;
+};
+struct PcGatherLds {                                 // pc_l1_gather_kernel (8192 rows), pc_point_gather_kernel (16384 rows)
+    static constexpr size_t FPS = 0;                                       // uint16 [512] the centroid table (128 used at level 2)
+    static constexpr size_t TAB = FPS + (size_t)PC_NP1 * 2;                // uint16 [rows] the neighbour table of the cloud
+    static constexpr size_t BYTES = TAB + (size_t)PC_NP1 * PC_K1 * 2;
+};
+static_assert(PcSa1BwdLds::BYTES == 56576 && PcSa2BwdLds::BYTES == 89344 && PcSa2BwdLds::BYTES <= LDS_MAX_BYTES &&
+              PcDensityBwdLds::BYTES == 32768 && PcGatherLds::BYTES == 33792 && PC_NP1 * PC_K1 >= PC_NP2 * PC_K2,
+              "LDS of the PointConv backward kernels");
+
 // ---- block_sum / block_max / block_sum_d write one value per wave into their scratch ------------------------------------------
 static_assert((RepLds::BYTES - RepLds::SCRATCH) / 4 >= OPT_THREADS / 64 && (NrmLds::BYTES - NrmLds::SCRATCH) / 4 >= OPT_THREADS / 64,
               "8 waves: repulsion_kernel, normalize_kernel");

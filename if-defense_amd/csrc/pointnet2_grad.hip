@@ -147,29 +147,6 @@ __device__ __forceinline__ int tile_winner(const f32x4 (&v)[2][2], int m, int r,
     return cand;
 }
 
-// Ys[row][obase + ..] = sum_c WT[o][c] Xs[row][c], no bias, no activation: a transposed layer on the tile, tile_layer's block
-// arithmetic (the 64-input blocks from zero, added in ascending order).
-template <int K, int LD>
-__device__ __forceinline__ void tile_layer_t(const float* __restrict__ Xs, const float* __restrict__ WT, float* __restrict__ Ys, int obase,
-                                             int wv, int q, int p) {
-    const float* xr[2];
-    const float* wr[2];
-#pragma unroll
-    for (int t = 0; t < 2; ++t) {
-        xr[t] = Xs + (32 * (wv & 1) + 16 * t + p) * LD + 4 * q;
-        wr[t] = WT + (size_t)(obase + 16 * t + p) * K + 4 * q;
-    }
-    const f32x4 zero = f32x4{0.f, 0.f, 0.f, 0.f};
-    f32x4 sum[2][2];
-#pragma unroll
-    for (int m = 0; m < 2; ++m)
-#pragma unroll
-        for (int t = 0; t < 2; ++t) sum[t][m] = zero;
-#pragma unroll
-    for (int g = 0; g < K; g += 64) linear_block64(xr, wr, g, sum);
-    tile_store<LD>(Ys, obase, wv, q, p, sum);
-}
-
 // sa2 backward.  The forward's arguments (pn2_sa2_kernel), W2T [128][128] the middle layer transposed, l2 the saved l2_feat,
 // dl2 its gradient, dx2a [B][128][4] sa3's term of d xyz2.  Out: dh [B][128][64][128], de [B][128][64][4], dx2 [B][128][4];
 // win2 [B][128][256] and act2 [B][128][64][8] where wanted.

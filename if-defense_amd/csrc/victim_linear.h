@@ -90,6 +90,29 @@ __device__ __forceinline__ void tile_store(float* __restrict__ Ys, int obase, in
             *reinterpret_cast<f32x4*>(Ys + (32 * (wv & 1) + 16 * t + p) * LDY + obase + 16 * m + 4 * q) = v[t][m];
 }
 
+// Ys[row][obase + ..] = sum_c WT[o][c] Xs[row][c], no bias, no activation: a transposed layer on the tile, tile_layer's block
+// arithmetic (the 64-input blocks from zero, added in ascending order).
+template <int K, int LD>
+__device__ __forceinline__ void tile_layer_t(const float* __restrict__ Xs, const float* __restrict__ WT, float* __restrict__ Ys, int obase,
+                                             int wv, int q, int p) {
+    const float* xr[2];
+    const float* wr[2];
+#pragma unroll
+    for (int t = 0; t < 2; ++t) {
+        xr[t] = Xs + (32 * (wv & 1) + 16 * t + p) * LD + 4 * q;
+        wr[t] = WT + (size_t)(obase + 16 * t + p) * K + 4 * q;
+    }
+    const f32x4 zero = f32x4{0.f, 0.f, 0.f, 0.f};
+    f32x4 sum[2][2];
+#pragma unroll
+    for (int m = 0; m < 2; ++m)
+#pragma unroll
+        for (int t = 0; t < 2; ++t) sum[t][m] = zero;
+#pragma unroll
+    for (int g = 0; g < K; g += 64) linear_block64(xr, wr, g, sum);
+    tile_store<LD>(Ys, obase, wv, q, p, sum);
+}
+
 // Y[row][o] = act(bias[o] + sum_c W[o][c] X[row][c] (+ wx[o] . xyz[row])), o < M (a multiple of 4), K a multiple of 64.  Rows: the
 // first cloud_points(n_points, b, stride) of cloud b = blockIdx.z; X rows of ldx floats from X + b * xb, Y rows of ldy floats from
 // Y + b * yb, xyz rows of 3 floats from xyz + b * stride * 3; wx [M][4] = {w0, w1, w2, -}.

@@ -32,7 +32,8 @@ from .inference import default_weight_path
 from .pointnet2_inference import MAX_POINTS, fps_starts
 
 PROG = 'pointnet2_fgm_attack'
-OTHER_CLI = {'pointnet': "`python -m ifdefense_amd.fgm_attack`", 'dgcnn': "`python -m ifdefense_amd.dgcnn_fgm_attack`"}
+OTHER_CLI = {'pointnet': "`python -m ifdefense_amd.fgm_attack`", 'dgcnn': "`python -m ifdefense_amd.dgcnn_fgm_attack`",
+             'pointconv': "`python -m ifdefense_amd.pointconv_fgm_attack`"}
 
 
 class BoundStarts:

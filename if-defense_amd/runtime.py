@@ -1527,7 +1527,22 @@ class DgcnnClassifier(Classifier):
         return aux, st
 
 
-class PointNet2Classifier(Classifier):
+class _SampledVictim(Classifier):
+    """What the two victims that sample share (PointNet++, PointConv): how ``fps_start`` reaches the library."""
+
+    def _starts(self, fps_start):
+        """-> extra(B) of _forward / _input_grad / _fgm_attack: fps_start as [B,2] int32 on the device, or None."""
+        def starts(B):
+            if fps_start is None:
+                return (None,)
+            t = torch.as_tensor(fps_start).to(device=self.device, dtype=torch.int32).contiguous()
+            if tuple(t.shape) != (B, 2):
+                raise IfdError("fps_start must be [B,2], got %s" % (tuple(t.shape),))
+            return (t,)
+        return starts
+
+
+class PointNet2Classifier(_SampledVictim):
     """The PointNet++ victim of the reference on one GPU (include/ifd_pn2.h): PointNet2ClsSsg(num_classes=40) in eval mode.
     ``weights``: the BN-folded canonical vector (``weights.load_checkpoint(path, "pointnet2")`` or
     ``weights.pack_state_dict(state_dict, "pointnet2")``).  Inputs are Classifier's: [B,N,3] batches (point-major), lists and
@@ -1547,17 +1562,6 @@ class PointNet2Classifier(Classifier):
         self.lib = _lib.load()
         self.feature_transform = False
         self._create("ifd_pn2_create", self.lib.ifd_pn2_weight_count(), "pointnet2 weights", weights, device)
-
-    def _starts(self, fps_start):
-        """-> extra(B) of _forward / _input_grad / _fgm_attack: fps_start as [B,2] int32 on the device, or None."""
-        def starts(B):
-            if fps_start is None:
-                return (None,)
-            t = torch.as_tensor(fps_start).to(device=self.device, dtype=torch.int32).contiguous()
-            if tuple(t.shape) != (B, 2):
-                raise IfdError("fps_start must be [B,2], got %s" % (tuple(t.shape),))
-            return (t,)
-        return starts
 
     def _grad_aux(self, B, stride):
         """input_grad's diagnostics on this victim: {"logits" [B,40], "loss" [B], "pred" [B], the tables and features of
@@ -1611,44 +1615,74 @@ class PointNet2Classifier(Classifier):
         return aux["pred"].long()
 
 
-class PointConvClassifier(Classifier):
+class PointConvClassifier(_SampledVictim):
     """The PointConv victim of the reference on one GPU (include/ifd_pc.h): PointConvDensityClsSsg(num_classes=40) in eval mode.
     ``weights``: the BN-folded canonical vector (``weights.load_checkpoint(path, "pointconv")`` or
     ``weights.pack_state_dict(state_dict, "pointconv")``).  Inputs are Classifier's: [B,N,3] batches (point-major), lists and
     object arrays of ragged clouds of 32 to 2048 points.  ``fps_start`` [B,2] int: the first pick of the level-1 sampling (below
     the cloud's count) and of the level-2 sampling (below 512); None means 0, 0 - the reference draws them at random, here
-    they are an input.  A cloud's outputs do not depend on how it is batched or padded.  The attack entry points of Classifier
-    are PointNet's and are not offered here."""
+    they are an input.  A cloud's outputs do not depend on how it is batched or padded.
+
+    Of the attack entry points, ``input_grad``, ``fgm_update`` and ``fgm_attack`` run on this victim (include/ifd_pc_atk.h),
+    with Classifier's signatures and return shapes plus ``fps_start=None``, so attack.FGM / IFGM / MIFGM / PGD work on it
+    unchanged; the gradient is the one of the network with its four index tables held fixed, the tables being the forward's on
+    the current cloud.  The other attack methods are PointNet's, and the library refuses them on a PointConv context."""
 
     MAX_POINTS = _lib.PC_MAX_POINTS
     MIN_POINTS = _lib.PC_MIN_POINTS
     CHUNK = _lib.PC_CHUNK
+    ATK_FNS = {"input_grad": "ifd_pc_input_grad", "fgm_update": "ifd_pc_fgm_update", "fgm_attack": "ifd_pc_fgm_attack"}
 
     def __init__(self, weights: np.ndarray, device=None):
         self.lib = _lib.load()
         self.feature_transform = False
         self._create("ifd_pc_create", self.lib.ifd_pc_weight_count(), "pointconv weights", weights, device)
 
+    def _aux_table(self, B, stride):
+        n1, k1, n2, k2 = _lib.PC_NPOINT1, _lib.PC_K1, _lib.PC_NPOINT2, _lib.PC_K2
+        i32, f32 = dict(device=self.device, dtype=torch.int32), dict(device=self.device, dtype=torch.float32)
+        return dict(fps1=torch.empty(B, n1, **i32), fps2=torch.empty(B, n2, **i32), knn1=torch.empty(B, n1, k1, **i32),
+                    knn2=torch.empty(B, n2, k2, **i32), dens1=torch.zeros(B, stride, **f32), dens2=torch.empty(B, n1, **f32),
+                    dens3=torch.empty(B, n2, **f32), l1_feat=torch.empty(B, n1, 128, **f32),
+                    l2_feat=torch.empty(B, n2, 256, **f32), global_feat=torch.empty(B, 1024, **f32))
+
+    def _grad_aux(self, B, stride):
+        """input_grad's diagnostics on this victim: {"logits" [B,40], "loss" [B], "pred" [B], the tables, densities and features of
+        ``logits``' aux, and the gate bits of the backward pass as int32 words (include/ifd_pc_atk.h): "dgate1" [B,N] (zero beyond a
+        cloud's count), "dgate2" [B,512], "dgate3" [B,128] (DensityNet), "wgate1" [B,512,32], "wgate2" [B,128,64], "wgate3" [B,128]
+        (WeightNet), "mgate1" [B,512,32,8], "mgate2" [B,128,64,16], "mgate3" [B,128,56] (the MLPs)}."""
+        n1, k1, n2, k2 = _lib.PC_NPOINT1, _lib.PC_K1, _lib.PC_NPOINT2, _lib.PC_K2
+        i32, f32 = dict(device=self.device, dtype=torch.int32), dict(device=self.device, dtype=torch.float32)
+        aux = dict(logits=torch.empty(B, self.N_CLASSES, **f32), loss=torch.empty(B, **f32), pred=torch.empty(B, **i32),
+                   **self._aux_table(B, stride),
+                   dgate1=torch.zeros(B, stride, **i32), dgate2=torch.empty(B, n1, **i32), dgate3=torch.empty(B, n2, **i32),
+                   wgate1=torch.empty(B, n1, k1, **i32), wgate2=torch.empty(B, n2, k2, **i32), wgate3=torch.empty(B, n2, **i32),
+                   mgate1=torch.empty(B, n1, k1, 8, **i32), mgate2=torch.empty(B, n2, k2, 16, **i32), mgate3=torch.empty(B, n2, 56, **i32))
+        st = _lib.IfdPcGradOut()
+        for name, t in aux.items():
+            setattr(st, name, t.data_ptr())
+        return aux, st
+
+    def input_grad(self, pc, target, loss="logits", kappa=0., scale=1., n_points=None, want_aux: bool = False, fps_start=None):
+        """Classifier.input_grad on this victim (ifd_pc_input_grad); fps_start as ``logits`` takes it; want_aux: see _grad_aux."""
+        return self._input_grad(pc, target, loss, kappa, scale, n_points, want_aux, extra=self._starts(fps_start))
+
+    def fgm_attack(self, kind, pc, target, budget, step_size, num_iter=1, mu=1., loss="logits", kappa=0., scale=1., n_points=None,
+                   fps_start=None):
+        """Classifier.fgm_attack on this victim (ifd_pc_fgm_attack): the same fps_start in every iteration and in the last forward."""
+        return self._fgm_attack(kind, pc, target, budget, step_size, num_iter, mu, loss, kappa, scale, n_points,
+                                extra=self._starts(fps_start))
+
+    def fgm_update(self, kind, grad, pc, ori_pc=None, momentum=None, step_size=0., budget=0., mu=1., n_points=None, fps_start=None):
+        """Classifier.fgm_update on this victim (ifd_pc_fgm_update); the update does not sample, fps_start is accepted and unused."""
+        return super().fgm_update(kind, grad, pc, ori_pc, momentum, step_size, budget, mu, n_points)
+
     def logits(self, pc, n_points=None, fps_start=None, want_aux: bool = False, want_pred: bool = False):
         """pc, n_points: as Classifier.logits.  Returns logits [B,40]; with want_aux also {"fps1" [B,512], "fps2" [B,128],
         "knn1" [B,512,32], "knn2" [B,128,64] (int32), "dens1" [B,N] (zero beyond a cloud's count), "dens2" [B,512], "dens3"
         [B,128] (DensityNet's outputs), "l1_feat" [B,512,128], "l2_feat" [B,128,256], "global_feat" [B,1024], "pred" [B] int32}."""
-        def starts(B):
-            if fps_start is None:
-                return (None,)
-            t = torch.as_tensor(fps_start).to(device=self.device, dtype=torch.int32).contiguous()
-            if tuple(t.shape) != (B, 2):
-                raise IfdError("fps_start must be [B,2], got %s" % (tuple(t.shape),))
-            return (t,)
-
-        def aux_table(B, stride):
-            n1, k1, n2, k2 = _lib.PC_NPOINT1, _lib.PC_K1, _lib.PC_NPOINT2, _lib.PC_K2
-            i32, f32 = dict(device=self.device, dtype=torch.int32), dict(device=self.device, dtype=torch.float32)
-            return dict(fps1=torch.empty(B, n1, **i32), fps2=torch.empty(B, n2, **i32), knn1=torch.empty(B, n1, k1, **i32),
-                        knn2=torch.empty(B, n2, k2, **i32), dens1=torch.zeros(B, stride, **f32), dens2=torch.empty(B, n1, **f32),
-                        dens3=torch.empty(B, n2, **f32), l1_feat=torch.empty(B, n1, 128, **f32),
-                        l2_feat=torch.empty(B, n2, 256, **f32), global_feat=torch.empty(B, 1024, **f32))
-        return self._forward("ifd_pc_forward", pc, n_points, _lib.IfdPcAux, aux_table, want_aux, want_pred, extra=starts)
+        return self._forward("ifd_pc_forward", pc, n_points, _lib.IfdPcAux, self._aux_table, want_aux, want_pred,
+                             extra=self._starts(fps_start))
 
     def predict(self, pc, n_points=None, fps_start=None) -> torch.Tensor:
         """argmax of the logits, [B] int64 (the lowest class among equal logits)."""
