@@ -1499,24 +1499,35 @@ int read_bad_counts(ifd_ctx* ctx, const char* who, const char* what, hipError_t 
     return IFD_OK;
 }
 
+// clouds of a chunk when B clouds go in chunks of at most max_chunk, sized evenly
+int even_chunk(int B, int max_chunk) {
+    const int n_chunks = (B + max_chunk - 1) / max_chunk;
+    return (B + n_chunks - 1) / n_chunks;
+}
+
+// run_chunk(c0, n, carve) per chunk of B clouds, each on a fresh Carve over the same workspace at `base`
+template <class RunChunk>
+int run_chunks(ifd_ctx* ctx, const char* who, int B, int chunk, char* base, RunChunk run_chunk) {
+    for (int c0 = 0; c0 < B; c0 += chunk) {
+        Carve c(base);
+        const hipError_t e = run_chunk(c0, std::min(chunk, B - c0), c);
+        if (e != hipSuccess) return fail(ctx, IFD_ERR_HIP, (std::string(who) + " launch").c_str(), e);
+    }
+    return IFD_OK;
+}
+
 // The skeleton of a victim's forward call over B clouds: chunks of at most max_chunk clouds, sized evenly; the context's workspace
 // grown to ws_off (bytes in front that belong to the caller) + ws_bytes(chunk); check(base) - the one blocking step, non-zero
-// refuses the call; then run_chunk(c0, n, carve) per chunk on a fresh Carve over the same workspace.
+// refuses the call; then the chunks (run_chunks).  The gradient calls' skeleton is victim_grad, below.
 template <class WsBytes, class Check, class RunChunk>
 int victim_forward(ifd_ctx* ctx, const char* who, int B, int max_chunk, size_t ws_off, WsBytes ws_bytes, Check check, RunChunk run_chunk) {
     IFD_ON_CTX_DEVICE(ctx);
-    const int n_chunks = (B + max_chunk - 1) / max_chunk, chunk = (B + n_chunks - 1) / n_chunks;
+    const int chunk = even_chunk(B, max_chunk);
     hipError_t e = ctx->ws.grow(ws_off + ws_bytes(chunk));
     if (e != hipSuccess) return fail(ctx, IFD_ERR_NOMEM, (std::string(who) + ": workspace").c_str(), e);
     char* base = ctx->ws.get<char>() + ws_off;
     if (int rc = check(base)) return rc;
-    for (int c0 = 0; c0 < B; c0 += chunk) {
-        const int n = std::min(chunk, B - c0);
-        Carve c(base);
-        e = run_chunk(c0, n, c);
-        if (e != hipSuccess) return fail(ctx, IFD_ERR_HIP, (std::string(who) + " launch").c_str(), e);
-    }
-    return IFD_OK;
+    return run_chunks(ctx, who, B, chunk, base, run_chunk);
 }
 
 // The device image: 3-input layers as [64][4] = {w0, w1, w2, bias}, every other layer as MFMA tiles (pointnet.hip header
@@ -2258,15 +2269,10 @@ int ifd_pc_forward(ifd_ctx* ctx, const float* pc, const int32_t* n_points, const
 
 }  // extern "C"
 
-// ---- attacks on the victim classifier (include/ifd_atk.h) ------------------------------------------------------------
+// ---- attacks on the victims (include/ifd_atk.h, ifd_dgcnn_atk.h, ifd_pn2_atk.h, ifd_pc_atk.h) -------------------------
 namespace {
 
-int atk_context_ok(ifd_ctx* ctx, const char* who) {
-    if (ctx->model != IFD_MODEL_CLS || !ctx->d_victim.get()) return fail(ctx, IFD_ERR_ARG, (std::string(who) + ": not a classifier context").c_str());
-    if (ctx->cls_feature_transform || !ctx->d_cls_grad.get())
-        return fail(ctx, IFD_ERR_ARG, (std::string(who) + ": input gradients are not built for a model with feature_transform").c_str());
-    return IFD_OK;
-}
+int refuse(ifd_ctx* ctx, const char* who, const std::string& why) { return fail(ctx, IFD_ERR_ARG, (who + why).c_str()); }
 
 // the one blocking step of the attack calls: counts (n_points in [lo, hi], range_text in the message) and targets live on the
 // device.  Uses the first 8 bytes of the workspace.
@@ -2290,61 +2296,8 @@ bool clouds_overlap(const void* a, size_t bytes_a, const void* b, size_t bytes_b
     return p < q + bytes_b && q < p + bytes_a;
 }
 
-int atk_chunk(int B) {
-    const int n_chunks = (B + CLS_CHUNK - 1) / CLS_CHUNK;
-    return (B + n_chunks - 1) / n_chunks;
-}
-size_t atk_grad_ws_bytes(int B, int stride) { return carved_bytes([&](Carve& c) { cls_grad_ws(c, (size_t)atk_chunk(B), stride); }); }
-
-// ifd_cls_input_grad on workspace that is already large enough (ws_off: bytes in front that belong to the caller), unchecked
-int input_grad_impl(ifd_ctx* ctx, size_t ws_off, const float* pc, const int32_t* n_points, int B, int stride, const int32_t* target,
-                    int loss_kind, float kappa, float scale, float* grad, const ifd_atk_out* out, hipStream_t s) {
-    const int chunk = atk_chunk(B), nc = ctx->cls_classes;
-    for (int c0 = 0; c0 < B; c0 += chunk) {
-        const size_t n = (size_t)std::min(chunk, B - c0);
-        Carve c(ctx->ws.get<char>() + ws_off);
-        const ClsGradWs w = cls_grad_ws(c, n, stride);
-        const float* pcc = pc + (size_t)c0 * stride * 3;
-        const int32_t* npc = n_points ? n_points + c0 : nullptr;
-        hipError_t e = launch_cls_win(ctx->d_victim.get<float>(), ctx->cimg, pcc, npc, (int)n, stride, w, nc, s);
-        if (e == hipSuccess)
-            e = launch_cls_backward(ctx->d_victim.get<float>(), ctx->cimg, ctx->d_cls_grad.get<float>(), ctx->gimg, pcc, npc, (int)n, stride, target + c0, loss_kind, kappa,
-                                    scale, w, nc, grad + (size_t)c0 * stride * 3, s);
-        auto copy = [&](void* dst, size_t dst_off, const void* src, size_t bytes_per_cloud) {
-            if (e == hipSuccess && dst)
-                e = hipMemcpyAsync(static_cast<char*>(dst) + dst_off * bytes_per_cloud, src, n * bytes_per_cloud, hipMemcpyDeviceToDevice, s);
-        };
-        if (out) {
-            copy(out->logits, c0, w.logits, 160);
-            copy(out->loss, c0, w.loss, 4);
-            copy(out->pred, c0, w.pred, 4);
-            copy(out->win_feat, c0, w.win, 4096);
-            copy(out->win_stn, c0, w.win_stn, 4096);
-            copy(out->global_feat, c0, w.gmax, 4096);
-        }
-        if (e != hipSuccess) return fail(ctx, IFD_ERR_HIP, "ifd_cls_input_grad launch", e);
-    }
-    return IFD_OK;
-}
-
 bool atk_loss_ok(int k) { return k == IFD_ATK_LOSS_LOGITS || k == IFD_ATK_LOSS_CE; }
 bool atk_kind_ok(int k) { return k >= IFD_FGM_FGM && k <= IFD_FGM_PGD; }
-
-// workspace of an attack loop: its own state in front of ifd_cls_input_grad's and, with_forward, of the final forward's
-size_t atk_loop_ws_bytes(int B, int stride, size_t state_bytes, bool with_forward) {
-    const size_t fwd = with_forward ? cls_ws_bytes(atk_chunk(B), stride, false) : 0;
-    return state_bytes + std::max(atk_grad_ws_bytes(B, stride), fwd);
-}
-
-// the final forward behind the loop's state (the counts were checked before the loop, so it does not block), success = pred == target
-int atk_final_success(ifd_ctx* ctx, const char* who, const float* pc_out, const int32_t* n_points, int B, int stride, float* logits,
-                      int32_t* pred, const int32_t* target, int32_t* success, size_t state_bytes, hipStream_t s) {
-    ifd_cls_aux aux{nullptr, nullptr, nullptr, pred};
-    if (int rc = cls_forward_impl(ctx, pc_out, n_points, B, stride, logits, &aux, s, false, state_bytes)) return rc;
-    hipError_t e = launch_atk_success(pred, target, B, success, s);
-    if (e != hipSuccess) return fail(ctx, IFD_ERR_HIP, (std::string(who) + ": success").c_str(), e);
-    return IFD_OK;
-}
 
 // ---- shared by the two Carlini-Wagner searches (ifd_cw_perturb_attack, ifd_add_attack) ----
 CwState cw_state(const ifd_cw_state* st) {
@@ -2461,526 +2414,387 @@ int cw_search(int binary_step, int num_iter, Start start, Iterate iterate, Adjus
     return IFD_OK;
 }
 
+// ---- a victim that can be attacked --------------------------------------------------------------------------------------
+// One gradient call's arguments.  fps_start is null for the victims that do not sample (PointNet, DGCNN).
+struct GradCall {
+    const float* pc; const int32_t *n_points, *fps_start, *target; int B, stride, loss_kind; float kappa, scale; float* grad; hipStream_t s;
+};
+
+// The clouds [c0, c0 + n) of a call: the caller's tensors from cloud c0 on, and copies of the chunk's scratch into them.  e: the
+// first error of the chunk; nothing is enqueued behind it.
+struct ChunkRows {
+    size_t c0, n; hipStream_t s; hipError_t e;
+    template <class T>
+    T* at(T* p, size_t per_cloud) const { return p ? p + c0 * per_cloud : nullptr; }
+    void copy(void* dst, const void* src, size_t bytes_per_cloud) {
+        if (e == hipSuccess && dst)
+            e = hipMemcpyAsync(static_cast<char*>(dst) + c0 * bytes_per_cloud, src, n * bytes_per_cloud, hipMemcpyDeviceToDevice, s);
+    }
+};
+
+// A victim's description, what differs between the four and nothing else:
+//   MODEL, NAME     the context's model and what a wrong context is told it is not
+//   GRAD_WHO        the gradient call's name in a launch failure
+//   CHUNK           most clouds of a chunk: the forward's
+//   MIN_POINTS, MAX_POINTS, COUNTS   the strides a call takes (DGCNN: the context's k on top) and how a refused n_points reads
+//   SAMPLE_CHECK    the check of counts and starts of a victim that samples, else null
+//   Out, Ws, grad_ws   the caller's diagnostic tensors; the gradient's workspace over n clouds and its carve
+//   fwd_ws_bytes    bytes of the final forward's workspace over n clouds
+//   grad_chunk      the gradient of one chunk on w: g and r are the chunk's; leaves its error in r.e and copies the diagnostics
+//                   that are the victim's own (logits, loss and pred are victim_grad's)
+//   forward         the forward call behind ws_off bytes, unchecked, with pred
+using SampleCheck = hipError_t (*)(const int32_t*, const int32_t*, int, int, int32_t*, hipStream_t);
+
+struct ClsVictim {
+    using Out = ifd_atk_out;
+    using Ws = ClsGradWs;
+    static constexpr int MODEL = IFD_MODEL_CLS, CHUNK = CLS_CHUNK, MIN_POINTS = 1, MAX_POINTS = IFD_CLS_MAX_POINTS;
+    static constexpr const char *NAME = "classifier", *GRAD_WHO = "ifd_cls_input_grad", *COUNTS = "[1, stride]";
+    static constexpr SampleCheck SAMPLE_CHECK = nullptr;
+    static Ws grad_ws(ifd_ctx*, Carve& c, size_t n, int stride) { return cls_grad_ws(c, n, stride); }
+    static size_t fwd_ws_bytes(ifd_ctx*, int n, int stride) { return cls_ws_bytes(n, stride, false); }
+    static void grad_chunk(ifd_ctx* ctx, const Ws& w, const GradCall& g, const Out* out, ChunkRows& r) {
+        const float* img = ctx->d_victim.get<float>();
+        r.e = launch_cls_win(img, ctx->cimg, g.pc, g.n_points, g.B, g.stride, w, ctx->cls_classes, g.s);
+        if (r.e == hipSuccess)
+            r.e = launch_cls_backward(img, ctx->cimg, ctx->d_cls_grad.get<float>(), ctx->gimg, g.pc, g.n_points, g.B, g.stride, g.target,
+                                      g.loss_kind, g.kappa, g.scale, w, ctx->cls_classes, g.grad, g.s);
+        if (!out) return;
+        r.copy(out->win_feat, w.win, 4096);
+        r.copy(out->win_stn, w.win_stn, 4096);
+        r.copy(out->global_feat, w.gmax, 4096);
+    }
+    static int forward(ifd_ctx* ctx, const float* pc, const int32_t* n_points, const int32_t*, int B, int stride, float* logits,
+                       int32_t* pred, void* stream, size_t ws_off) {
+        ifd_cls_aux aux{nullptr, nullptr, nullptr, pred};
+        return cls_forward_impl(ctx, pc, n_points, B, stride, logits, &aux, stream, false, ws_off);
+    }
+};
+
+struct DgVictim {
+    using Out = ifd_dgcnn_grad_out;
+    using Ws = DgGradWs;
+    // the forward's chunks: two chunks of 64 cost its kNN kernels 1.5 x one of 128
+    static constexpr int MODEL = IFD_MODEL_DGCNN, CHUNK = DG_CHUNK, MIN_POINTS = 1, MAX_POINTS = IFD_DGCNN_MAX_POINTS;
+    static constexpr const char *NAME = "DGCNN", *GRAD_WHO = "ifd_dgcnn_input_grad", *COUNTS = "[k, stride]";
+    static constexpr SampleCheck SAMPLE_CHECK = nullptr;
+    static Ws grad_ws(ifd_ctx* ctx, Carve& c, size_t n, int stride) { return dgcnn_grad_ws(c, n, stride, ctx->dg_k); }
+    static size_t fwd_ws_bytes(ifd_ctx* ctx, int n, int stride) { return dgcnn_ws_bytes(n, stride, ctx->dg_k); }
+    static void grad_chunk(ifd_ctx* ctx, const Ws& w, const GradCall& g, const Out* out, ChunkRows& r) {
+        static const int cout[4] = {64, 64, 128, 256};
+        const size_t st = (size_t)g.stride;
+        const int k = ctx->dg_k;
+        DgGradOut o{};
+        if (out) {
+            for (int l = 0; l < 4; ++l) { o.idx[l] = r.at(out->idx[l], st * k); o.win_edge[l] = r.at(out->win_edge[l], st * cout[l]); }
+            o.feat = r.at(out->feat, st * DG_FEAT);
+            o.act5 = r.at(out->act5, st * (DG_EMB / 32));
+        }
+        r.e = launch_dgcnn_grad(ctx->d_victim.get<float>(), ctx->dimg, ctx->d_cls_grad.get<float>(), ctx->dgimg, g.pc, g.n_points, g.B, g.stride, k,
+                                g.target, g.loss_kind, g.kappa, g.scale, w, o, ctx->cls_classes, g.grad, g.s);
+        if (!out) return;
+        r.copy(out->global_feat, w.f.gfeat, 2 * DG_EMB * 4);
+        r.copy(out->win_pool, w.win_pool, DG_EMB * 4);
+    }
+    static int forward(ifd_ctx* ctx, const float* pc, const int32_t* n_points, const int32_t*, int B, int stride, float* logits,
+                       int32_t* pred, void* stream, size_t ws_off) {
+        ifd_dgcnn_aux aux{};
+        aux.pred = pred;
+        return dgcnn_forward_impl(ctx, pc, n_points, B, stride, logits, &aux, stream, false, ws_off);
+    }
+};
+
+struct Pn2Victim {
+    using Out = ifd_pn2_grad_out;
+    using Ws = Pn2GradWs;
+    static constexpr int MODEL = IFD_MODEL_PN2, CHUNK = PN2_CHUNK, MIN_POINTS = 1, MAX_POINTS = IFD_PN2_MAX_POINTS;
+    static constexpr const char *NAME = "PointNet++", *GRAD_WHO = "ifd_pn2_input_grad", *COUNTS = "[1, stride]";
+    static constexpr SampleCheck SAMPLE_CHECK = launch_pn2_check;
+    static Ws grad_ws(ifd_ctx*, Carve& c, size_t n, int) { return pn2_grad_ws(c, n); }
+    static size_t fwd_ws_bytes(ifd_ctx*, int n, int) { return pn2_ws_bytes(n); }          // the front of the gradient's
+    static void grad_chunk(ifd_ctx* ctx, const Ws& w, const GradCall& g, const Out* out, ChunkRows& r) {
+        Pn2GradOut o{};
+        if (out) {
+            o.fps1 = r.at(out->fps1, PN2_NP1); o.fps2 = r.at(out->fps2, PN2_NP2);
+            o.ball1 = r.at(out->ball1, PN2_NP1 * PN2_NS1); o.ball2 = r.at(out->ball2, PN2_NP2 * PN2_NS2);
+            o.l1_feat = r.at(out->l1_feat, PN2_NP1 * 128); o.l2_feat = r.at(out->l2_feat, PN2_NP2 * 256);
+            o.gfeat = r.at(out->global_feat, PN2_EMB);
+            o.win1 = r.at(out->win1, PN2_NP1 * 128); o.win2 = r.at(out->win2, PN2_NP2 * 256);
+            o.act1 = r.at(out->act1, PN2_NP1 * PN2_NS1 * 4); o.act2 = r.at(out->act2, PN2_NP2 * PN2_NS2 * 8);
+            o.act3 = r.at(out->act3, PN2_NP2 * 24);
+        }
+        r.e = launch_pn2_grad(ctx->d_victim.get<float>(), ctx->p2img, ctx->d_cls_grad.get<float>(), ctx->p2gimg, g.pc, g.n_points, g.fps_start, g.B,
+                              g.stride, g.target, g.loss_kind, g.kappa, g.scale, w, o, ctx->cls_classes, g.grad, g.s);
+        if (out) r.copy(out->win3, w.win3, PN2_EMB * 4);
+    }
+    static int forward(ifd_ctx* ctx, const float* pc, const int32_t* n_points, const int32_t* fps_start, int B, int stride, float* logits,
+                       int32_t* pred, void* stream, size_t ws_off) {
+        ifd_pn2_aux aux{};
+        aux.pred = pred;
+        return pn2_forward_impl(ctx, pc, n_points, fps_start, B, stride, logits, &aux, stream, false, ws_off);
+    }
+};
+
+struct PcVictim {
+    using Out = ifd_pc_grad_out;
+    using Ws = PcGradWs;
+    static constexpr int MODEL = IFD_MODEL_PC, CHUNK = PC_CHUNK, MIN_POINTS = IFD_PC_MIN_POINTS, MAX_POINTS = IFD_PC_MAX_POINTS;
+    static constexpr const char *NAME = "PointConv", *GRAD_WHO = "ifd_pc_input_grad", *COUNTS = "[32, stride]";
+    static constexpr SampleCheck SAMPLE_CHECK = launch_pc_check;
+    static Ws grad_ws(ifd_ctx*, Carve& c, size_t n, int) { return pc_grad_ws(c, n); }
+    static size_t fwd_ws_bytes(ifd_ctx*, int n, int) { return pc_ws_bytes(n); }           // the front of the gradient's
+    static void grad_chunk(ifd_ctx* ctx, const Ws& w, const GradCall& g, const Out* out, ChunkRows& r) {
+        const size_t st = (size_t)g.stride;
+        PcGradOut o{};
+        if (out) {
+            o.f.fps1 = r.at(out->fps1, PC_NP1); o.f.fps2 = r.at(out->fps2, PC_NP2);
+            o.f.knn1 = r.at(out->knn1, PC_NP1 * PC_K1); o.f.knn2 = r.at(out->knn2, PC_NP2 * PC_K2);
+            o.f.dens1 = r.at(out->dens1, st); o.f.dens2 = r.at(out->dens2, PC_NP1); o.f.dens3 = r.at(out->dens3, PC_NP2);
+            o.f.l1_feat = r.at(out->l1_feat, PC_NP1 * 128); o.f.l2_feat = r.at(out->l2_feat, PC_NP2 * 256);
+            o.f.gfeat = r.at(out->global_feat, PC_EMB);
+            o.dgate1 = r.at(out->dgate1, st); o.dgate2 = r.at(out->dgate2, PC_NP1); o.dgate3 = r.at(out->dgate3, PC_NP2);
+            o.wgate1 = r.at(out->wgate1, PC_NP1 * PC_K1); o.wgate2 = r.at(out->wgate2, PC_NP2 * PC_K2); o.wgate3 = r.at(out->wgate3, PC_NP2);
+            o.mgate1 = r.at(out->mgate1, PC_NP1 * PC_K1 * 8); o.mgate2 = r.at(out->mgate2, PC_NP2 * PC_K2 * 16);
+            o.mgate3 = r.at(out->mgate3, PC_NP2 * 56);
+        }
+        r.e = launch_pc_grad(ctx->d_victim.get<float>(), ctx->pcimg, ctx->d_cls_grad.get<float>(), ctx->pcgimg, g.pc, g.n_points, g.fps_start, g.B,
+                             g.stride, g.target, g.loss_kind, g.kappa, g.scale, w, o, ctx->cls_classes, g.grad, g.s);
+    }
+    static int forward(ifd_ctx* ctx, const float* pc, const int32_t* n_points, const int32_t* fps_start, int B, int stride, float* logits,
+                       int32_t* pred, void* stream, size_t ws_off) {
+        ifd_pc_aux aux{};
+        aux.pred = pred;
+        return pc_forward_impl(ctx, pc, n_points, fps_start, B, stride, logits, &aux, stream, false, ws_off);
+    }
+};
+
+// ---- what every attack on a victim V shares -------------------------------------------------------------------------
+// PointNet keeps a refusal of its own: a model with feature_transform has no backward image
+template <class V>
+int victim_context_ok(ifd_ctx* ctx, const char* who) {
+    const bool has_grad = ctx->d_cls_grad.get() && !ctx->cls_feature_transform;
+    if (ctx->model != V::MODEL || !ctx->d_victim.get() || (!has_grad && V::MODEL != IFD_MODEL_CLS))
+        return refuse(ctx, who, std::string(": not a ") + V::NAME + " context");
+    if (!has_grad) return refuse(ctx, who, ": input gradients are not built for a model with feature_transform");
+    return IFD_OK;
+}
+int atk_context_ok(ifd_ctx* ctx, const char* who) { return victim_context_ok<ClsVictim>(ctx, who); }
+
+// the fewest points of a cloud: a DGCNN context's k, which is 0 in every other context
+template <class V>
+int victim_min_points(ifd_ctx* ctx) { return std::max(V::MIN_POINTS, ctx->dg_k); }
+
+template <class V>
+int victim_stride_ok(ifd_ctx* ctx, const char* who, int stride) {
+    const int lo = victim_min_points<V>(ctx);
+    if (stride >= lo && stride <= V::MAX_POINTS) return IFD_OK;
+    return refuse(ctx, who, ": stride " + std::to_string(stride) + " outside " + numeric_range(lo, V::MAX_POINTS));
+}
+
+// the one blocking step of an attack call on a victim that samples: counts and starts (`sampled`: launch_pn2_check, launch_pc_check)
+// and targets (launch_atk_check), four counters at the start of the workspace, read together
+int sampled_atk_check(ifd_ctx* ctx, const char* who, SampleCheck sampled, const char* counts, const GradCall& g) {
+    int32_t* d_bad = ctx->ws.get<int32_t>();
+    hipError_t e = sampled(g.n_points, g.fps_start, g.B, g.stride, d_bad, g.s);
+    if (e == hipSuccess) e = launch_atk_check(nullptr, g.target, g.B, 1, g.stride, ctx->cls_classes, d_bad + 2, g.s);
+    int32_t bad[4] = {0, 0, 0, 0};
+    if (int rc = read_bad_counts(ctx, who, "n_points, fps_start and target", e, d_bad, 4, bad, g.s)) return rc;
+    if (bad[0] != 0) return refuse(ctx, who, ": " + std::to_string(bad[0]) + " cloud(s) with n_points outside " + counts);
+    if (bad[1] != 0) return refuse(ctx, who, ": " + std::to_string(bad[1]) + " cloud(s) with fps_start outside [0, n_points) x [0, 512)");
+    if (bad[3] != 0) return refuse(ctx, who, ": " + std::to_string(bad[3]) + " target(s) outside [0, 40)");
+    return IFD_OK;
+}
+template <class V>
+int victim_atk_check(ifd_ctx* ctx, const char* who, const GradCall& g) {
+    if constexpr (V::SAMPLE_CHECK != nullptr) return sampled_atk_check(ctx, who, V::SAMPLE_CHECK, V::COUNTS, g);
+    else return atk_check(ctx, who, g.n_points, g.target, g.B, victim_min_points<V>(ctx), g.stride, V::COUNTS, g.s);
+}
+
+// workspace of the gradient of B clouds, and of an attack loop: its own state in front of the gradient's and, with_forward, of the
+// final forward's (which in DGCNN, PointNet++ and PointConv is the front of the gradient's)
+template <class V>
+size_t grad_ws_bytes(ifd_ctx* ctx, int B, int stride) {
+    return carved_bytes([&](Carve& c) { V::grad_ws(ctx, c, (size_t)even_chunk(B, V::CHUNK), stride); });
+}
+template <class V>
+size_t loop_ws_bytes(ifd_ctx* ctx, int B, int stride, size_t state_bytes, bool with_forward) {
+    const size_t fwd = with_forward ? V::fwd_ws_bytes(ctx, even_chunk(B, V::CHUNK), stride) : 0;
+    return state_bytes + std::max(grad_ws_bytes<V>(ctx, B, stride), fwd);
+}
+int atk_chunk(int B) { return even_chunk(B, CLS_CHUNK); }
+size_t atk_grad_ws_bytes(int B, int stride) { return grad_ws_bytes<ClsVictim>(nullptr, B, stride); }
+size_t atk_loop_ws_bytes(int B, int stride, size_t state_bytes, bool with_forward) {
+    return loop_ws_bytes<ClsVictim>(nullptr, B, stride, state_bytes, with_forward);
+}
+
+// The skeleton of a victim's gradient call, victim_forward's sibling: on workspace that is already large enough (ws_off: bytes in
+// front that belong to the caller), unchecked.  This is what an attack loop calls per iteration.
+template <class V>
+int victim_grad(ifd_ctx* ctx, size_t ws_off, const GradCall& g, const typename V::Out* out) {
+    return run_chunks(ctx, V::GRAD_WHO, g.B, even_chunk(g.B, V::CHUNK), ctx->ws.get<char>() + ws_off, [&](int c0, int n, Carve& c) {
+        const typename V::Ws w = V::grad_ws(ctx, c, (size_t)n, g.stride);
+        ChunkRows r{(size_t)c0, (size_t)n, g.s, hipSuccess};
+        GradCall h = g;
+        h.B = n;
+        h.pc = r.at(g.pc, (size_t)g.stride * 3); h.grad = r.at(g.grad, (size_t)g.stride * 3);
+        h.n_points = r.at(g.n_points, 1); h.fps_start = r.at(g.fps_start, 2); h.target = r.at(g.target, 1);
+        V::grad_chunk(ctx, w, h, out, r);
+        if (out) {
+            r.copy(out->logits, w.logits, 160);
+            r.copy(out->loss, w.loss, 4);
+            r.copy(out->pred, w.pred, 4);
+        }
+        return r.e;
+    });
+}
+int input_grad_impl(ifd_ctx* ctx, size_t ws_off, const float* pc, const int32_t* n_points, int B, int stride, const int32_t* target,
+                    int loss_kind, float kappa, float scale, float* grad, const ifd_atk_out* out, hipStream_t s) {
+    return victim_grad<ClsVictim>(ctx, ws_off, {pc, n_points, nullptr, target, B, stride, loss_kind, kappa, scale, grad, s}, out);
+}
+
+// the final forward behind the loop's state (the counts were checked before the loop, so it does not block), success = pred == target
+template <class V>
+int victim_final_success(ifd_ctx* ctx, const char* who, const float* pc_out, const int32_t* n_points, const int32_t* fps_start, int B,
+                         int stride, float* logits, int32_t* pred, const int32_t* target, int32_t* success, size_t state_bytes, hipStream_t s) {
+    if (int rc = V::forward(ctx, pc_out, n_points, fps_start, B, stride, logits, pred, s, state_bytes)) return rc;
+    hipError_t e = launch_atk_success(pred, target, B, success, s);
+    if (e != hipSuccess) return fail(ctx, IFD_ERR_HIP, (std::string(who) + ": success").c_str(), e);
+    return IFD_OK;
+}
+int atk_final_success(ifd_ctx* ctx, const char* who, const float* pc_out, const int32_t* n_points, int B, int stride, float* logits,
+                      int32_t* pred, const int32_t* target, int32_t* success, size_t state_bytes, hipStream_t s) {
+    return victim_final_success<ClsVictim>(ctx, who, pc_out, n_points, nullptr, B, stride, logits, pred, target, success, state_bytes, s);
+}
+
+// ifd_*_input_grad
+template <class V>
+int victim_input_grad(ifd_ctx* ctx, const char* who, const GradCall& g, const typename V::Out* out) {
+    if (!ctx) return IFD_ERR_ARG;
+    if (int rc = victim_context_ok<V>(ctx, who)) return rc;
+    if (!g.pc || !g.target || !g.grad || g.B < 1) return refuse(ctx, who, ": bad argument (pc, target, grad; B >= 1)");
+    if (int rc = victim_stride_ok<V>(ctx, who, g.stride)) return rc;
+    if (!atk_loss_ok(g.loss_kind)) return refuse(ctx, who, ": unknown loss_kind");
+    IFD_ON_CTX_DEVICE(ctx);
+    hipError_t e = ctx->ws.grow(grad_ws_bytes<V>(ctx, g.B, g.stride));
+    if (e != hipSuccess) return fail(ctx, IFD_ERR_NOMEM, (std::string(who) + ": workspace").c_str(), e);
+    if (int rc = victim_atk_check<V>(ctx, who, g)) return rc;
+    return victim_grad<V>(ctx, 0, g, out);
+}
+
+// ifd_*_fgm_update: the one kernel on any victim's context; the strides are the victim's, not a DGCNN context's k
+template <class V>
+int victim_fgm_update(ifd_ctx* ctx, const char* who, int kind, const float* grad, float* pc, const float* ori_pc, float* momentum,
+                      float step_size, float budget, float mu, const int32_t* n_points, int B, int stride, void* stream) {
+    if (!ctx) return IFD_ERR_ARG;
+    if (int rc = victim_context_ok<V>(ctx, who)) return rc;
+    if (!atk_kind_ok(kind)) return refuse(ctx, who, ": unknown kind");
+    if (!grad || !pc || B < 1 || stride < V::MIN_POINTS || stride > V::MAX_POINTS || (kind != IFD_FGM_FGM && !ori_pc) ||
+        (kind == IFD_FGM_MIFGM && !momentum))
+        return refuse(ctx, who, ": bad argument (grad, pc; ori_pc unless FGM; momentum for MIFGM; " + std::to_string(V::MIN_POINTS) +
+                                    " <= stride <= " + std::to_string(V::MAX_POINTS) + ")");
+    IFD_ON_CTX_DEVICE(ctx);
+    hipError_t e = launch_fgm_update(kind, grad, pc, ori_pc, momentum, step_size, budget, mu, n_points, B, stride, static_cast<hipStream_t>(stream));
+    if (e != hipSuccess) return fail(ctx, IFD_ERR_HIP, (std::string(who) + " launch").c_str(), e);
+    return IFD_OK;
+}
+
+// ifd_*_fgm_attack
+template <class V>
+int victim_fgm_attack(ifd_ctx* ctx, const char* who, const ifd_fgm_params* params, const float* pc_in, const int32_t* n_points,
+                      const int32_t* fps_start, const int32_t* target, int B, int stride, float* pc_out, int32_t* success, void* stream) {
+    if (!ctx) return IFD_ERR_ARG;
+    if (int rc = victim_context_ok<V>(ctx, who)) return rc;
+    if (!params || params->struct_size != (int32_t)sizeof(ifd_fgm_params)) return refuse(ctx, who, ": params missing or of another struct_size");
+    if (!atk_kind_ok(params->kind) || !atk_loss_ok(params->loss_kind) || params->num_iter < 1)
+        return refuse(ctx, who, ": unknown kind or loss_kind, or num_iter < 1");
+    if (!pc_in || !target || !pc_out || !success || pc_in == pc_out || B < 1)
+        return refuse(ctx, who, ": bad argument (pc_in, target, pc_out, success; B >= 1)");
+    if (int rc = victim_stride_ok<V>(ctx, who, stride)) return rc;
+    IFD_ON_CTX_DEVICE(ctx);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const size_t cloud = (size_t)stride * 12, state = carved_bytes([&](Carve& c) { FgmLoop(c, (size_t)B, cloud); });
+    hipError_t e = ctx->ws.grow(loop_ws_bytes<V>(ctx, B, stride, state, true));
+    if (e != hipSuccess) return fail(ctx, IFD_ERR_NOMEM, (std::string(who) + ": workspace").c_str(), e);
+    GradCall g{pc_out, n_points, fps_start, target, B, stride, params->loss_kind, params->kappa, params->scale, nullptr, s};
+    if (int rc = victim_atk_check<V>(ctx, who, g)) return rc;
+    Carve c(ctx->ws.get());
+    const FgmLoop L(c, (size_t)B, cloud);
+    g.grad = L.grad;
+    e = hipMemcpyAsync(pc_out, pc_in, (size_t)B * cloud, hipMemcpyDeviceToDevice, s);
+    if (e == hipSuccess && params->kind == IFD_FGM_MIFGM) e = hipMemsetAsync(L.mom, 0, (size_t)B * cloud, s);
+    if (e != hipSuccess) return fail(ctx, IFD_ERR_HIP, (std::string(who) + ": start").c_str(), e);
+    const int iters = params->kind == IFD_FGM_FGM ? 1 : params->num_iter;
+    for (int it = 0; it < iters; ++it) {
+        if (int rc = victim_grad<V>(ctx, state, g, nullptr)) return rc;
+        e = launch_fgm_update(params->kind, L.grad, pc_out, pc_in, L.mom, params->step_size, params->budget, params->mu, n_points, B, stride, s);
+        if (e != hipSuccess) return fail(ctx, IFD_ERR_HIP, (std::string(who) + ": update").c_str(), e);
+    }
+    return victim_final_success<V>(ctx, who, pc_out, n_points, fps_start, B, stride, L.logits, L.pred, target, success, state, s);
+}
+
 }  // namespace
 
 extern "C" {
 
 int ifd_atk_abi_version(void) { return IFD_ATK_ABI_VERSION; }
+int ifd_dgcnn_atk_abi_version(void) { return IFD_DGCNN_ATK_ABI_VERSION; }
+int ifd_pn2_atk_abi_version(void) { return IFD_PN2_ATK_ABI_VERSION; }
+int ifd_pc_atk_abi_version(void) { return IFD_PC_ATK_ABI_VERSION; }
 
 int ifd_cls_input_grad(ifd_ctx* ctx, const float* pc, const int32_t* n_points, int B, int stride, const int32_t* target, int loss_kind,
                        float kappa, float scale, float* grad, const ifd_atk_out* out, void* stream) {
-    if (!ctx) return IFD_ERR_ARG;
-    if (int rc = atk_context_ok(ctx, "ifd_cls_input_grad")) return rc;
-    if (!pc || !target || !grad || B < 1 || stride < 1 || stride > IFD_CLS_MAX_POINTS)
-        return fail(ctx, IFD_ERR_ARG, "ifd_cls_input_grad: bad argument (pc, target, grad; B >= 1, 1 <= stride <= 10000)");
-    if (!atk_loss_ok(loss_kind)) return fail(ctx, IFD_ERR_ARG, "ifd_cls_input_grad: unknown loss_kind");
-    IFD_ON_CTX_DEVICE(ctx);
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    hipError_t e = ctx->ws.grow(atk_grad_ws_bytes(B, stride));
-    if (e != hipSuccess) return fail(ctx, IFD_ERR_NOMEM, "ifd_cls_input_grad: workspace", e);
-    if (int rc = atk_check(ctx, "ifd_cls_input_grad", n_points, target, B, 1, stride, "[1, stride]", s)) return rc;
-    return input_grad_impl(ctx, 0, pc, n_points, B, stride, target, loss_kind, kappa, scale, grad, out, s);
+    return victim_input_grad<ClsVictim>(ctx, "ifd_cls_input_grad", {pc, n_points, nullptr, target, B, stride, loss_kind, kappa, scale, grad,
+                                                                     static_cast<hipStream_t>(stream)}, out);
+}
+int ifd_dgcnn_input_grad(ifd_ctx* ctx, const float* pc, const int32_t* n_points, int B, int stride, const int32_t* target, int loss_kind,
+                         float kappa, float scale, float* grad, const ifd_dgcnn_grad_out* out, void* stream) {
+    return victim_input_grad<DgVictim>(ctx, "ifd_dgcnn_input_grad", {pc, n_points, nullptr, target, B, stride, loss_kind, kappa, scale, grad,
+                                                                      static_cast<hipStream_t>(stream)}, out);
+}
+int ifd_pn2_input_grad(ifd_ctx* ctx, const float* pc, const int32_t* n_points, const int32_t* fps_start, int B, int stride,
+                       const int32_t* target, int loss_kind, float kappa, float scale, float* grad, const ifd_pn2_grad_out* out,
+                       void* stream) {
+    return victim_input_grad<Pn2Victim>(ctx, "ifd_pn2_input_grad", {pc, n_points, fps_start, target, B, stride, loss_kind, kappa, scale, grad,
+                                                                     static_cast<hipStream_t>(stream)}, out);
+}
+int ifd_pc_input_grad(ifd_ctx* ctx, const float* pc, const int32_t* n_points, const int32_t* fps_start, int B, int stride,
+                      const int32_t* target, int loss_kind, float kappa, float scale, float* grad, const ifd_pc_grad_out* out, void* stream) {
+    return victim_input_grad<PcVictim>(ctx, "ifd_pc_input_grad", {pc, n_points, fps_start, target, B, stride, loss_kind, kappa, scale, grad,
+                                                                   static_cast<hipStream_t>(stream)}, out);
 }
 
 int ifd_fgm_update(ifd_ctx* ctx, int kind, const float* grad, float* pc, const float* ori_pc, float* momentum, float step_size,
                    float budget, float mu, const int32_t* n_points, int B, int stride, void* stream) {
-    if (!ctx) return IFD_ERR_ARG;
-    if (int rc = atk_context_ok(ctx, "ifd_fgm_update")) return rc;
-    if (!atk_kind_ok(kind)) return fail(ctx, IFD_ERR_ARG, "ifd_fgm_update: unknown kind");
-    if (!grad || !pc || B < 1 || stride < 1 || stride > IFD_CLS_MAX_POINTS || (kind != IFD_FGM_FGM && !ori_pc) ||
-        (kind == IFD_FGM_MIFGM && !momentum))
-        return fail(ctx, IFD_ERR_ARG, "ifd_fgm_update: bad argument (grad, pc; ori_pc unless FGM; momentum for MIFGM; 1 <= stride <= 10000)");
-    IFD_ON_CTX_DEVICE(ctx);
-    hipError_t e = launch_fgm_update(kind, grad, pc, ori_pc, momentum, step_size, budget, mu, n_points, B, stride,
-                                     static_cast<hipStream_t>(stream));
-    if (e != hipSuccess) return fail(ctx, IFD_ERR_HIP, "ifd_fgm_update launch", e);
-    return IFD_OK;
+    return victim_fgm_update<ClsVictim>(ctx, "ifd_fgm_update", kind, grad, pc, ori_pc, momentum, step_size, budget, mu, n_points, B, stride, stream);
+}
+int ifd_dgcnn_fgm_update(ifd_ctx* ctx, int kind, const float* grad, float* pc, const float* ori_pc, float* momentum, float step_size,
+                         float budget, float mu, const int32_t* n_points, int B, int stride, void* stream) {
+    return victim_fgm_update<DgVictim>(ctx, "ifd_dgcnn_fgm_update", kind, grad, pc, ori_pc, momentum, step_size, budget, mu, n_points, B, stride, stream);
+}
+int ifd_pn2_fgm_update(ifd_ctx* ctx, int kind, const float* grad, float* pc, const float* ori_pc, float* momentum, float step_size,
+                       float budget, float mu, const int32_t* n_points, int B, int stride, void* stream) {
+    return victim_fgm_update<Pn2Victim>(ctx, "ifd_pn2_fgm_update", kind, grad, pc, ori_pc, momentum, step_size, budget, mu, n_points, B, stride, stream);
+}
+int ifd_pc_fgm_update(ifd_ctx* ctx, int kind, const float* grad, float* pc, const float* ori_pc, float* momentum, float step_size,
+                      float budget, float mu, const int32_t* n_points, int B, int stride, void* stream) {
+    return victim_fgm_update<PcVictim>(ctx, "ifd_pc_fgm_update", kind, grad, pc, ori_pc, momentum, step_size, budget, mu, n_points, B, stride, stream);
 }
 
 int ifd_fgm_attack(ifd_ctx* ctx, const ifd_fgm_params* params, const float* pc_in, const int32_t* n_points, const int32_t* target, int B,
                    int stride, float* pc_out, int32_t* success, void* stream) {
-    if (!ctx) return IFD_ERR_ARG;
-    if (int rc = atk_context_ok(ctx, "ifd_fgm_attack")) return rc;
-    if (!params || params->struct_size != (int32_t)sizeof(ifd_fgm_params))
-        return fail(ctx, IFD_ERR_ARG, "ifd_fgm_attack: params missing or of another struct_size");
-    if (!atk_kind_ok(params->kind) || !atk_loss_ok(params->loss_kind) || params->num_iter < 1)
-        return fail(ctx, IFD_ERR_ARG, "ifd_fgm_attack: unknown kind or loss_kind, or num_iter < 1");
-    if (!pc_in || !target || !pc_out || !success || pc_in == pc_out || B < 1 || stride < 1 || stride > IFD_CLS_MAX_POINTS)
-        return fail(ctx, IFD_ERR_ARG, "ifd_fgm_attack: bad argument (pc_in, target, pc_out, success; B >= 1, 1 <= stride <= 10000)");
-    IFD_ON_CTX_DEVICE(ctx);
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    const size_t cloud = (size_t)stride * 12, state = carved_bytes([&](Carve& c) { FgmLoop(c, (size_t)B, cloud); });
-    hipError_t e = ctx->ws.grow(atk_loop_ws_bytes(B, stride, state, true));
-    if (e != hipSuccess) return fail(ctx, IFD_ERR_NOMEM, "ifd_fgm_attack: workspace", e);
-    if (int rc = atk_check(ctx, "ifd_fgm_attack", n_points, target, B, 1, stride, "[1, stride]", s)) return rc;
-    Carve c(ctx->ws.get());
-    const FgmLoop L(c, (size_t)B, cloud);
-    float *grad = L.grad, *mom = L.mom, *logits = L.logits;
-    int32_t* pred = L.pred;
-    e = hipMemcpyAsync(pc_out, pc_in, (size_t)B * cloud, hipMemcpyDeviceToDevice, s);
-    if (e == hipSuccess && params->kind == IFD_FGM_MIFGM) e = hipMemsetAsync(mom, 0, (size_t)B * cloud, s);
-    if (e != hipSuccess) return fail(ctx, IFD_ERR_HIP, "ifd_fgm_attack: start", e);
-    const int iters = params->kind == IFD_FGM_FGM ? 1 : params->num_iter;
-    for (int it = 0; it < iters; ++it) {
-        if (int rc = input_grad_impl(ctx, state, pc_out, n_points, B, stride, target, params->loss_kind, params->kappa, params->scale, grad,
-                                     nullptr, s))
-            return rc;
-        e = launch_fgm_update(params->kind, grad, pc_out, pc_in, mom, params->step_size, params->budget, params->mu, n_points, B, stride, s);
-        if (e != hipSuccess) return fail(ctx, IFD_ERR_HIP, "ifd_fgm_attack: update", e);
-    }
-    return atk_final_success(ctx, "ifd_fgm_attack", pc_out, n_points, B, stride, logits, pred, target, success, state, s);
+    return victim_fgm_attack<ClsVictim>(ctx, "ifd_fgm_attack", params, pc_in, n_points, nullptr, target, B, stride, pc_out, success, stream);
 }
-
-}  // extern "C"
-
-// ---- attacks on the DGCNN victim (include/ifd_dgcnn_atk.h) -------------------------------------------------------------
-namespace {
-
-constexpr int DG_ATK_CHUNK = DG_CHUNK;       // most clouds per chunk of ifd_dgcnn_input_grad: the forward's (two chunks of 64 cost its kNN kernels 1.5 x one of 128)
-
-int dg_atk_context_ok(ifd_ctx* ctx, const char* who) {
-    if (ctx->model != IFD_MODEL_DGCNN || !ctx->d_victim.get() || !ctx->d_cls_grad.get())
-        return fail(ctx, IFD_ERR_ARG, (std::string(who) + ": not a DGCNN context").c_str());
-    return IFD_OK;
-}
-// the strides a DGCNN call takes: k <= stride <= 2048
-int dg_atk_stride_ok(ifd_ctx* ctx, const char* who, int stride) {
-    if (stride >= ctx->dg_k && stride <= IFD_DGCNN_MAX_POINTS) return IFD_OK;
-    return fail(ctx, IFD_ERR_ARG, (std::string(who) + ": stride " + std::to_string(stride) + " outside [k, 2048] (k = " +
-                                   std::to_string(ctx->dg_k) + ")").c_str());
-}
-
-int dg_atk_chunk(int B) {
-    const int n_chunks = (B + DG_ATK_CHUNK - 1) / DG_ATK_CHUNK;
-    return (B + n_chunks - 1) / n_chunks;
-}
-size_t dg_grad_ws_bytes(int B, int stride, int k) {
-    return carved_bytes([&](Carve& c) { dgcnn_grad_ws(c, (size_t)dg_atk_chunk(B), stride, k); });
-}
-// workspace of ifd_dgcnn_fgm_attack: its state in front of the gradient's and the final forward's
-size_t dg_loop_ws_bytes(int B, int stride, int k, size_t state_bytes) {
-    const int fwd_chunks = (B + DG_CHUNK - 1) / DG_CHUNK;
-    return state_bytes + std::max(dg_grad_ws_bytes(B, stride, k), dgcnn_ws_bytes((B + fwd_chunks - 1) / fwd_chunks, stride, k));
-}
-
-// ifd_dgcnn_input_grad on workspace that is already large enough (ws_off: bytes in front that belong to the caller), unchecked
-int dg_input_grad_impl(ifd_ctx* ctx, size_t ws_off, const float* pc, const int32_t* n_points, int B, int stride, const int32_t* target,
-                       int loss_kind, float kappa, float scale, float* grad, const ifd_dgcnn_grad_out* out, hipStream_t s) {
-    const int chunk = dg_atk_chunk(B), nc = ctx->cls_classes, k = ctx->dg_k;
-    static const int cout[4] = {64, 64, 128, 256};
-    for (int c0 = 0; c0 < B; c0 += chunk) {
-        const size_t n = (size_t)std::min(chunk, B - c0), st = (size_t)stride;
-        Carve c(ctx->ws.get<char>() + ws_off);
-        const DgGradWs w = dgcnn_grad_ws(c, n, stride, k);
-        DgGradOut o{};
-        if (out) {
-            for (int l = 0; l < 4; ++l) {
-                o.idx[l] = out->idx[l] ? out->idx[l] + (size_t)c0 * st * k : nullptr;
-                o.win_edge[l] = out->win_edge[l] ? out->win_edge[l] + (size_t)c0 * st * cout[l] : nullptr;
-            }
-            o.feat = out->feat ? out->feat + (size_t)c0 * st * DG_FEAT : nullptr;
-            o.act5 = out->act5 ? out->act5 + (size_t)c0 * st * (DG_EMB / 32) : nullptr;
-        }
-        hipError_t e = launch_dgcnn_grad(ctx->d_victim.get<float>(), ctx->dimg, ctx->d_cls_grad.get<float>(), ctx->dgimg, pc + (size_t)c0 * st * 3,
-                                         n_points ? n_points + c0 : nullptr, (int)n, stride, k, target + c0, loss_kind, kappa, scale, w, o, nc,
-                                         grad + (size_t)c0 * st * 3, s);
-        auto copy = [&](void* dst, const void* src, size_t bytes_per_cloud) {
-            if (e == hipSuccess && dst)
-                e = hipMemcpyAsync(static_cast<char*>(dst) + (size_t)c0 * bytes_per_cloud, src, n * bytes_per_cloud, hipMemcpyDeviceToDevice, s);
-        };
-        if (out) {
-            copy(out->logits, w.logits, 160);
-            copy(out->loss, w.loss, 4);
-            copy(out->pred, w.pred, 4);
-            copy(out->global_feat, w.f.gfeat, 2 * DG_EMB * 4);
-            copy(out->win_pool, w.win_pool, DG_EMB * 4);
-        }
-        if (e != hipSuccess) return fail(ctx, IFD_ERR_HIP, "ifd_dgcnn_input_grad launch", e);
-    }
-    return IFD_OK;
-}
-
-}  // namespace
-
-extern "C" {
-
-int ifd_dgcnn_atk_abi_version(void) { return IFD_DGCNN_ATK_ABI_VERSION; }
-
-int ifd_dgcnn_input_grad(ifd_ctx* ctx, const float* pc, const int32_t* n_points, int B, int stride, const int32_t* target, int loss_kind,
-                         float kappa, float scale, float* grad, const ifd_dgcnn_grad_out* out, void* stream) {
-    if (!ctx) return IFD_ERR_ARG;
-    if (int rc = dg_atk_context_ok(ctx, "ifd_dgcnn_input_grad")) return rc;
-    if (!pc || !target || !grad || B < 1) return fail(ctx, IFD_ERR_ARG, "ifd_dgcnn_input_grad: bad argument (pc, target, grad; B >= 1)");
-    if (int rc = dg_atk_stride_ok(ctx, "ifd_dgcnn_input_grad", stride)) return rc;
-    if (!atk_loss_ok(loss_kind)) return fail(ctx, IFD_ERR_ARG, "ifd_dgcnn_input_grad: unknown loss_kind");
-    IFD_ON_CTX_DEVICE(ctx);
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    hipError_t e = ctx->ws.grow(dg_grad_ws_bytes(B, stride, ctx->dg_k));
-    if (e != hipSuccess) return fail(ctx, IFD_ERR_NOMEM, "ifd_dgcnn_input_grad: workspace", e);
-    if (int rc = atk_check(ctx, "ifd_dgcnn_input_grad", n_points, target, B, ctx->dg_k, stride, "[k, stride]", s)) return rc;
-    return dg_input_grad_impl(ctx, 0, pc, n_points, B, stride, target, loss_kind, kappa, scale, grad, out, s);
-}
-
-int ifd_dgcnn_fgm_update(ifd_ctx* ctx, int kind, const float* grad, float* pc, const float* ori_pc, float* momentum, float step_size,
-                         float budget, float mu, const int32_t* n_points, int B, int stride, void* stream) {
-    if (!ctx) return IFD_ERR_ARG;
-    if (int rc = dg_atk_context_ok(ctx, "ifd_dgcnn_fgm_update")) return rc;
-    if (!atk_kind_ok(kind)) return fail(ctx, IFD_ERR_ARG, "ifd_dgcnn_fgm_update: unknown kind");
-    if (!grad || !pc || B < 1 || stride < 1 || stride > IFD_DGCNN_MAX_POINTS || (kind != IFD_FGM_FGM && !ori_pc) ||
-        (kind == IFD_FGM_MIFGM && !momentum))
-        return fail(ctx, IFD_ERR_ARG, "ifd_dgcnn_fgm_update: bad argument (grad, pc; ori_pc unless FGM; momentum for MIFGM; 1 <= stride <= 2048)");
-    IFD_ON_CTX_DEVICE(ctx);
-    hipError_t e = launch_fgm_update(kind, grad, pc, ori_pc, momentum, step_size, budget, mu, n_points, B, stride,
-                                     static_cast<hipStream_t>(stream));
-    if (e != hipSuccess) return fail(ctx, IFD_ERR_HIP, "ifd_dgcnn_fgm_update launch", e);
-    return IFD_OK;
-}
-
 int ifd_dgcnn_fgm_attack(ifd_ctx* ctx, const ifd_fgm_params* params, const float* pc_in, const int32_t* n_points, const int32_t* target,
                          int B, int stride, float* pc_out, int32_t* success, void* stream) {
-    if (!ctx) return IFD_ERR_ARG;
-    if (int rc = dg_atk_context_ok(ctx, "ifd_dgcnn_fgm_attack")) return rc;
-    if (!params || params->struct_size != (int32_t)sizeof(ifd_fgm_params))
-        return fail(ctx, IFD_ERR_ARG, "ifd_dgcnn_fgm_attack: params missing or of another struct_size");
-    if (!atk_kind_ok(params->kind) || !atk_loss_ok(params->loss_kind) || params->num_iter < 1)
-        return fail(ctx, IFD_ERR_ARG, "ifd_dgcnn_fgm_attack: unknown kind or loss_kind, or num_iter < 1");
-    if (!pc_in || !target || !pc_out || !success || pc_in == pc_out || B < 1)
-        return fail(ctx, IFD_ERR_ARG, "ifd_dgcnn_fgm_attack: bad argument (pc_in, target, pc_out, success; B >= 1)");
-    if (int rc = dg_atk_stride_ok(ctx, "ifd_dgcnn_fgm_attack", stride)) return rc;
-    IFD_ON_CTX_DEVICE(ctx);
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    const size_t cloud = (size_t)stride * 12, state = carved_bytes([&](Carve& c) { FgmLoop(c, (size_t)B, cloud); });
-    hipError_t e = ctx->ws.grow(dg_loop_ws_bytes(B, stride, ctx->dg_k, state));
-    if (e != hipSuccess) return fail(ctx, IFD_ERR_NOMEM, "ifd_dgcnn_fgm_attack: workspace", e);
-    if (int rc = atk_check(ctx, "ifd_dgcnn_fgm_attack", n_points, target, B, ctx->dg_k, stride, "[k, stride]", s)) return rc;
-    Carve c(ctx->ws.get());
-    const FgmLoop L(c, (size_t)B, cloud);
-    e = hipMemcpyAsync(pc_out, pc_in, (size_t)B * cloud, hipMemcpyDeviceToDevice, s);
-    if (e == hipSuccess && params->kind == IFD_FGM_MIFGM) e = hipMemsetAsync(L.mom, 0, (size_t)B * cloud, s);
-    if (e != hipSuccess) return fail(ctx, IFD_ERR_HIP, "ifd_dgcnn_fgm_attack: start", e);
-    const int iters = params->kind == IFD_FGM_FGM ? 1 : params->num_iter;
-    for (int it = 0; it < iters; ++it) {
-        if (int rc = dg_input_grad_impl(ctx, state, pc_out, n_points, B, stride, target, params->loss_kind, params->kappa, params->scale,
-                                        L.grad, nullptr, s))
-            return rc;
-        e = launch_fgm_update(params->kind, L.grad, pc_out, pc_in, L.mom, params->step_size, params->budget, params->mu, n_points, B, stride, s);
-        if (e != hipSuccess) return fail(ctx, IFD_ERR_HIP, "ifd_dgcnn_fgm_attack: update", e);
-    }
-    ifd_dgcnn_aux aux{};
-    aux.pred = L.pred;
-    if (int rc = dgcnn_forward_impl(ctx, pc_out, n_points, B, stride, L.logits, &aux, stream, false, state)) return rc;
-    e = launch_atk_success(L.pred, target, B, success, s);
-    if (e != hipSuccess) return fail(ctx, IFD_ERR_HIP, "ifd_dgcnn_fgm_attack: success", e);
-    return IFD_OK;
+    return victim_fgm_attack<DgVictim>(ctx, "ifd_dgcnn_fgm_attack", params, pc_in, n_points, nullptr, target, B, stride, pc_out, success, stream);
 }
-
-}  // extern "C"
-
-// ---- attacks on the PointNet++ victim (include/ifd_pn2_atk.h) ----------------------------------------------------------
-namespace {
-
-int pn2_atk_context_ok(ifd_ctx* ctx, const char* who) {
-    if (ctx->model != IFD_MODEL_PN2 || !ctx->d_victim.get() || !ctx->d_cls_grad.get())
-        return fail(ctx, IFD_ERR_ARG, (std::string(who) + ": not a PointNet++ context").c_str());
-    return IFD_OK;
-}
-int pn2_atk_stride_ok(ifd_ctx* ctx, const char* who, int stride) {
-    if (stride >= 1 && stride <= IFD_PN2_MAX_POINTS) return IFD_OK;
-    return fail(ctx, IFD_ERR_ARG, (std::string(who) + ": stride " + std::to_string(stride) + " outside [1, 2048]").c_str());
-}
-
-int pn2_atk_chunk(int B) {                   // the forward's chunks
-    const int n_chunks = (B + PN2_CHUNK - 1) / PN2_CHUNK;
-    return (B + n_chunks - 1) / n_chunks;
-}
-size_t pn2_grad_ws_bytes(int B) { return carved_bytes([&](Carve& c) { pn2_grad_ws(c, (size_t)pn2_atk_chunk(B)); }); }
-
-// the one blocking step of the PointNet++ attack calls: counts and starts (launch_pn2_check) and targets (launch_atk_check), four
-// counters at the start of the workspace, read together
-int pn2_atk_check(ifd_ctx* ctx, const char* who, const int32_t* n_points, const int32_t* fps_start, const int32_t* target, int B,
-                  int stride, hipStream_t s) {
-    int32_t* d_bad = ctx->ws.get<int32_t>();
-    hipError_t e = launch_pn2_check(n_points, fps_start, B, stride, d_bad, s);
-    if (e == hipSuccess) e = launch_atk_check(nullptr, target, B, 1, stride, ctx->cls_classes, d_bad + 2, s);
-    int32_t bad[4] = {0, 0, 0, 0};
-    if (int rc = read_bad_counts(ctx, who, "n_points, fps_start and target", e, d_bad, 4, bad, s)) return rc;
-    if (bad[0] != 0)
-        return fail(ctx, IFD_ERR_ARG, (std::string(who) + ": " + std::to_string(bad[0]) + " cloud(s) with n_points outside [1, stride]").c_str());
-    if (bad[1] != 0)
-        return fail(ctx, IFD_ERR_ARG,
-                    (std::string(who) + ": " + std::to_string(bad[1]) + " cloud(s) with fps_start outside [0, n_points) x [0, 512)").c_str());
-    if (bad[3] != 0)
-        return fail(ctx, IFD_ERR_ARG, (std::string(who) + ": " + std::to_string(bad[3]) + " target(s) outside [0, 40)").c_str());
-    return IFD_OK;
-}
-
-// ifd_pn2_input_grad on workspace that is already large enough (ws_off: bytes in front that belong to the caller), unchecked
-int pn2_input_grad_impl(ifd_ctx* ctx, size_t ws_off, const float* pc, const int32_t* n_points, const int32_t* fps_start, int B, int stride,
-                        const int32_t* target, int loss_kind, float kappa, float scale, float* grad, const ifd_pn2_grad_out* out,
-                        hipStream_t s) {
-    const int chunk = pn2_atk_chunk(B), nc = ctx->cls_classes;
-    for (int c0 = 0; c0 < B; c0 += chunk) {
-        const size_t n = (size_t)std::min(chunk, B - c0), st = (size_t)stride, at = (size_t)c0;
-        Carve c(ctx->ws.get<char>() + ws_off);
-        const Pn2GradWs w = pn2_grad_ws(c, n);
-        Pn2GradOut o{};
-        if (out) {
-            o.fps1 = out->fps1 ? out->fps1 + at * PN2_NP1 : nullptr;
-            o.fps2 = out->fps2 ? out->fps2 + at * PN2_NP2 : nullptr;
-            o.ball1 = out->ball1 ? out->ball1 + at * PN2_NP1 * PN2_NS1 : nullptr;
-            o.ball2 = out->ball2 ? out->ball2 + at * PN2_NP2 * PN2_NS2 : nullptr;
-            o.l1_feat = out->l1_feat ? out->l1_feat + at * PN2_NP1 * 128 : nullptr;
-            o.l2_feat = out->l2_feat ? out->l2_feat + at * PN2_NP2 * 256 : nullptr;
-            o.gfeat = out->global_feat ? out->global_feat + at * PN2_EMB : nullptr;
-            o.win1 = out->win1 ? out->win1 + at * PN2_NP1 * 128 : nullptr;
-            o.win2 = out->win2 ? out->win2 + at * PN2_NP2 * 256 : nullptr;
-            o.act1 = out->act1 ? out->act1 + at * PN2_NP1 * PN2_NS1 * 4 : nullptr;
-            o.act2 = out->act2 ? out->act2 + at * PN2_NP2 * PN2_NS2 * 8 : nullptr;
-            o.act3 = out->act3 ? out->act3 + at * PN2_NP2 * 24 : nullptr;
-        }
-        hipError_t e = launch_pn2_grad(ctx->d_victim.get<float>(), ctx->p2img, ctx->d_cls_grad.get<float>(), ctx->p2gimg, pc + at * st * 3,
-                                       n_points ? n_points + c0 : nullptr, fps_start ? fps_start + at * 2 : nullptr, (int)n, stride,
-                                       target + c0, loss_kind, kappa, scale, w, o, nc, grad + at * st * 3, s);
-        auto copy = [&](void* dst, const void* src, size_t bytes_per_cloud) {
-            if (e == hipSuccess && dst)
-                e = hipMemcpyAsync(static_cast<char*>(dst) + at * bytes_per_cloud, src, n * bytes_per_cloud, hipMemcpyDeviceToDevice, s);
-        };
-        if (out) {
-            copy(out->logits, w.logits, 160);
-            copy(out->loss, w.loss, 4);
-            copy(out->pred, w.pred, 4);
-            copy(out->win3, w.win3, PN2_EMB * 4);
-        }
-        if (e != hipSuccess) return fail(ctx, IFD_ERR_HIP, "ifd_pn2_input_grad launch", e);
-    }
-    return IFD_OK;
-}
-
-}  // namespace
-
-extern "C" {
-
-int ifd_pn2_atk_abi_version(void) { return IFD_PN2_ATK_ABI_VERSION; }
-
-int ifd_pn2_input_grad(ifd_ctx* ctx, const float* pc, const int32_t* n_points, const int32_t* fps_start, int B, int stride,
-                       const int32_t* target, int loss_kind, float kappa, float scale, float* grad, const ifd_pn2_grad_out* out,
-                       void* stream) {
-    if (!ctx) return IFD_ERR_ARG;
-    if (int rc = pn2_atk_context_ok(ctx, "ifd_pn2_input_grad")) return rc;
-    if (!pc || !target || !grad || B < 1) return fail(ctx, IFD_ERR_ARG, "ifd_pn2_input_grad: bad argument (pc, target, grad; B >= 1)");
-    if (int rc = pn2_atk_stride_ok(ctx, "ifd_pn2_input_grad", stride)) return rc;
-    if (!atk_loss_ok(loss_kind)) return fail(ctx, IFD_ERR_ARG, "ifd_pn2_input_grad: unknown loss_kind");
-    IFD_ON_CTX_DEVICE(ctx);
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    hipError_t e = ctx->ws.grow(pn2_grad_ws_bytes(B));
-    if (e != hipSuccess) return fail(ctx, IFD_ERR_NOMEM, "ifd_pn2_input_grad: workspace", e);
-    if (int rc = pn2_atk_check(ctx, "ifd_pn2_input_grad", n_points, fps_start, target, B, stride, s)) return rc;
-    return pn2_input_grad_impl(ctx, 0, pc, n_points, fps_start, B, stride, target, loss_kind, kappa, scale, grad, out, s);
-}
-
-int ifd_pn2_fgm_update(ifd_ctx* ctx, int kind, const float* grad, float* pc, const float* ori_pc, float* momentum, float step_size,
-                       float budget, float mu, const int32_t* n_points, int B, int stride, void* stream) {
-    if (!ctx) return IFD_ERR_ARG;
-    if (int rc = pn2_atk_context_ok(ctx, "ifd_pn2_fgm_update")) return rc;
-    if (!atk_kind_ok(kind)) return fail(ctx, IFD_ERR_ARG, "ifd_pn2_fgm_update: unknown kind");
-    if (!grad || !pc || B < 1 || stride < 1 || stride > IFD_PN2_MAX_POINTS || (kind != IFD_FGM_FGM && !ori_pc) ||
-        (kind == IFD_FGM_MIFGM && !momentum))
-        return fail(ctx, IFD_ERR_ARG, "ifd_pn2_fgm_update: bad argument (grad, pc; ori_pc unless FGM; momentum for MIFGM; 1 <= stride <= 2048)");
-    IFD_ON_CTX_DEVICE(ctx);
-    hipError_t e = launch_fgm_update(kind, grad, pc, ori_pc, momentum, step_size, budget, mu, n_points, B, stride,
-                                     static_cast<hipStream_t>(stream));
-    if (e != hipSuccess) return fail(ctx, IFD_ERR_HIP, "ifd_pn2_fgm_update launch", e);
-    return IFD_OK;
-}
-
 int ifd_pn2_fgm_attack(ifd_ctx* ctx, const ifd_fgm_params* params, const float* pc_in, const int32_t* n_points, const int32_t* fps_start,
                        const int32_t* target, int B, int stride, float* pc_out, int32_t* success, void* stream) {
-    if (!ctx) return IFD_ERR_ARG;
-    if (int rc = pn2_atk_context_ok(ctx, "ifd_pn2_fgm_attack")) return rc;
-    if (!params || params->struct_size != (int32_t)sizeof(ifd_fgm_params))
-        return fail(ctx, IFD_ERR_ARG, "ifd_pn2_fgm_attack: params missing or of another struct_size");
-    if (!atk_kind_ok(params->kind) || !atk_loss_ok(params->loss_kind) || params->num_iter < 1)
-        return fail(ctx, IFD_ERR_ARG, "ifd_pn2_fgm_attack: unknown kind or loss_kind, or num_iter < 1");
-    if (!pc_in || !target || !pc_out || !success || pc_in == pc_out || B < 1)
-        return fail(ctx, IFD_ERR_ARG, "ifd_pn2_fgm_attack: bad argument (pc_in, target, pc_out, success; B >= 1)");
-    if (int rc = pn2_atk_stride_ok(ctx, "ifd_pn2_fgm_attack", stride)) return rc;
-    IFD_ON_CTX_DEVICE(ctx);
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    const size_t cloud = (size_t)stride * 12, state = carved_bytes([&](Carve& c) { FgmLoop(c, (size_t)B, cloud); });
-    hipError_t e = ctx->ws.grow(state + pn2_grad_ws_bytes(B));         // the final forward's workspace is the front of the gradient's
-    if (e != hipSuccess) return fail(ctx, IFD_ERR_NOMEM, "ifd_pn2_fgm_attack: workspace", e);
-    if (int rc = pn2_atk_check(ctx, "ifd_pn2_fgm_attack", n_points, fps_start, target, B, stride, s)) return rc;
-    Carve c(ctx->ws.get());
-    const FgmLoop L(c, (size_t)B, cloud);
-    e = hipMemcpyAsync(pc_out, pc_in, (size_t)B * cloud, hipMemcpyDeviceToDevice, s);
-    if (e == hipSuccess && params->kind == IFD_FGM_MIFGM) e = hipMemsetAsync(L.mom, 0, (size_t)B * cloud, s);
-    if (e != hipSuccess) return fail(ctx, IFD_ERR_HIP, "ifd_pn2_fgm_attack: start", e);
-    const int iters = params->kind == IFD_FGM_FGM ? 1 : params->num_iter;
-    for (int it = 0; it < iters; ++it) {
-        if (int rc = pn2_input_grad_impl(ctx, state, pc_out, n_points, fps_start, B, stride, target, params->loss_kind, params->kappa,
-                                         params->scale, L.grad, nullptr, s))
-            return rc;
-        e = launch_fgm_update(params->kind, L.grad, pc_out, pc_in, L.mom, params->step_size, params->budget, params->mu, n_points, B, stride, s);
-        if (e != hipSuccess) return fail(ctx, IFD_ERR_HIP, "ifd_pn2_fgm_attack: update", e);
-    }
-    ifd_pn2_aux aux{};
-    aux.pred = L.pred;
-    if (int rc = pn2_forward_impl(ctx, pc_out, n_points, fps_start, B, stride, L.logits, &aux, stream, false, state)) return rc;
-    e = launch_atk_success(L.pred, target, B, success, s);
-    if (e != hipSuccess) return fail(ctx, IFD_ERR_HIP, "ifd_pn2_fgm_attack: success", e);
-    return IFD_OK;
+    return victim_fgm_attack<Pn2Victim>(ctx, "ifd_pn2_fgm_attack", params, pc_in, n_points, fps_start, target, B, stride, pc_out, success, stream);
 }
-
-}  // extern "C"
-
-// ---- attacks on the PointConv victim (include/ifd_pc_atk.h) -----------------------------------------------------------
-namespace {
-
-int pc_atk_context_ok(ifd_ctx* ctx, const char* who) {
-    if (ctx->model != IFD_MODEL_PC || !ctx->d_victim.get() || !ctx->d_cls_grad.get())
-        return fail(ctx, IFD_ERR_ARG, (std::string(who) + ": not a PointConv context").c_str());
-    return IFD_OK;
-}
-int pc_atk_stride_ok(ifd_ctx* ctx, const char* who, int stride) {
-    if (stride >= IFD_PC_MIN_POINTS && stride <= IFD_PC_MAX_POINTS) return IFD_OK;
-    return fail(ctx, IFD_ERR_ARG, (std::string(who) + ": stride " + std::to_string(stride) + " outside [32, 2048]").c_str());
-}
-
-int pc_atk_chunk(int B) {                    // the forward's chunks
-    const int n_chunks = (B + PC_CHUNK - 1) / PC_CHUNK;
-    return (B + n_chunks - 1) / n_chunks;
-}
-size_t pc_grad_ws_bytes(int B) { return carved_bytes([&](Carve& c) { pc_grad_ws(c, (size_t)pc_atk_chunk(B)); }); }
-
-// the one blocking step of the PointConv attack calls: counts and starts (launch_pc_check) and targets (launch_atk_check), four
-// counters at the start of the workspace, read together
-int pc_atk_check(ifd_ctx* ctx, const char* who, const int32_t* n_points, const int32_t* fps_start, const int32_t* target, int B, int stride,
-                 hipStream_t s) {
-    int32_t* d_bad = ctx->ws.get<int32_t>();
-    hipError_t e = launch_pc_check(n_points, fps_start, B, stride, d_bad, s);
-    if (e == hipSuccess) e = launch_atk_check(nullptr, target, B, 1, stride, ctx->cls_classes, d_bad + 2, s);
-    int32_t bad[4] = {0, 0, 0, 0};
-    if (int rc = read_bad_counts(ctx, who, "n_points, fps_start and target", e, d_bad, 4, bad, s)) return rc;
-    if (bad[0] != 0)
-        return fail(ctx, IFD_ERR_ARG, (std::string(who) + ": " + std::to_string(bad[0]) + " cloud(s) with n_points outside [32, stride]").c_str());
-    if (bad[1] != 0)
-        return fail(ctx, IFD_ERR_ARG,
-                    (std::string(who) + ": " + std::to_string(bad[1]) + " cloud(s) with fps_start outside [0, n_points) x [0, 512)").c_str());
-    if (bad[3] != 0)
-        return fail(ctx, IFD_ERR_ARG, (std::string(who) + ": " + std::to_string(bad[3]) + " target(s) outside [0, 40)").c_str());
-    return IFD_OK;
-}
-
-// ifd_pc_input_grad on workspace that is already large enough (ws_off: bytes in front that belong to the caller), unchecked
-int pc_input_grad_impl(ifd_ctx* ctx, size_t ws_off, const float* pc, const int32_t* n_points, const int32_t* fps_start, int B, int stride,
-                       const int32_t* target, int loss_kind, float kappa, float scale, float* grad, const ifd_pc_grad_out* out, hipStream_t s) {
-    const int chunk = pc_atk_chunk(B), nc = ctx->cls_classes;
-    for (int c0 = 0; c0 < B; c0 += chunk) {
-        const size_t n = (size_t)std::min(chunk, B - c0), st = (size_t)stride, at = (size_t)c0;
-        Carve c(ctx->ws.get<char>() + ws_off);
-        const PcGradWs w = pc_grad_ws(c, n);
-        PcGradOut o{};
-        if (out) {
-            auto off = [&](auto* p, size_t per_cloud) { return p ? p + at * per_cloud : nullptr; };
-            o.f.fps1 = off(out->fps1, PC_NP1); o.f.fps2 = off(out->fps2, PC_NP2);
-            o.f.knn1 = off(out->knn1, PC_NP1 * PC_K1); o.f.knn2 = off(out->knn2, PC_NP2 * PC_K2);
-            o.f.dens1 = off(out->dens1, st); o.f.dens2 = off(out->dens2, PC_NP1); o.f.dens3 = off(out->dens3, PC_NP2);
-            o.f.l1_feat = off(out->l1_feat, PC_NP1 * 128); o.f.l2_feat = off(out->l2_feat, PC_NP2 * 256);
-            o.f.gfeat = off(out->global_feat, PC_EMB);
-            o.dgate1 = off(out->dgate1, st); o.dgate2 = off(out->dgate2, PC_NP1); o.dgate3 = off(out->dgate3, PC_NP2);
-            o.wgate1 = off(out->wgate1, PC_NP1 * PC_K1); o.wgate2 = off(out->wgate2, PC_NP2 * PC_K2); o.wgate3 = off(out->wgate3, PC_NP2);
-            o.mgate1 = off(out->mgate1, PC_NP1 * PC_K1 * 8); o.mgate2 = off(out->mgate2, PC_NP2 * PC_K2 * 16);
-            o.mgate3 = off(out->mgate3, PC_NP2 * 56);
-        }
-        hipError_t e = launch_pc_grad(ctx->d_victim.get<float>(), ctx->pcimg, ctx->d_cls_grad.get<float>(), ctx->pcgimg, pc + at * st * 3,
-                                      n_points ? n_points + c0 : nullptr, fps_start ? fps_start + at * 2 : nullptr, (int)n, stride,
-                                      target + c0, loss_kind, kappa, scale, w, o, nc, grad + at * st * 3, s);
-        auto copy = [&](void* dst, const void* src, size_t bytes_per_cloud) {
-            if (e == hipSuccess && dst)
-                e = hipMemcpyAsync(static_cast<char*>(dst) + at * bytes_per_cloud, src, n * bytes_per_cloud, hipMemcpyDeviceToDevice, s);
-        };
-        if (out) {
-            copy(out->logits, w.logits, 160);
-            copy(out->loss, w.loss, 4);
-            copy(out->pred, w.pred, 4);
-        }
-        if (e != hipSuccess) return fail(ctx, IFD_ERR_HIP, "ifd_pc_input_grad launch", e);
-    }
-    return IFD_OK;
-}
-
-}  // namespace
-
-extern "C" {
-
-int ifd_pc_atk_abi_version(void) { return IFD_PC_ATK_ABI_VERSION; }
-
-int ifd_pc_input_grad(ifd_ctx* ctx, const float* pc, const int32_t* n_points, const int32_t* fps_start, int B, int stride,
-                      const int32_t* target, int loss_kind, float kappa, float scale, float* grad, const ifd_pc_grad_out* out, void* stream) {
-    if (!ctx) return IFD_ERR_ARG;
-    if (int rc = pc_atk_context_ok(ctx, "ifd_pc_input_grad")) return rc;
-    if (!pc || !target || !grad || B < 1) return fail(ctx, IFD_ERR_ARG, "ifd_pc_input_grad: bad argument (pc, target, grad; B >= 1)");
-    if (int rc = pc_atk_stride_ok(ctx, "ifd_pc_input_grad", stride)) return rc;
-    if (!atk_loss_ok(loss_kind)) return fail(ctx, IFD_ERR_ARG, "ifd_pc_input_grad: unknown loss_kind");
-    IFD_ON_CTX_DEVICE(ctx);
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    hipError_t e = ctx->ws.grow(pc_grad_ws_bytes(B));
-    if (e != hipSuccess) return fail(ctx, IFD_ERR_NOMEM, "ifd_pc_input_grad: workspace", e);
-    if (int rc = pc_atk_check(ctx, "ifd_pc_input_grad", n_points, fps_start, target, B, stride, s)) return rc;
-    return pc_input_grad_impl(ctx, 0, pc, n_points, fps_start, B, stride, target, loss_kind, kappa, scale, grad, out, s);
-}
-
-int ifd_pc_fgm_update(ifd_ctx* ctx, int kind, const float* grad, float* pc, const float* ori_pc, float* momentum, float step_size,
-                      float budget, float mu, const int32_t* n_points, int B, int stride, void* stream) {
-    if (!ctx) return IFD_ERR_ARG;
-    if (int rc = pc_atk_context_ok(ctx, "ifd_pc_fgm_update")) return rc;
-    if (!atk_kind_ok(kind)) return fail(ctx, IFD_ERR_ARG, "ifd_pc_fgm_update: unknown kind");
-    if (!grad || !pc || B < 1 || stride < IFD_PC_MIN_POINTS || stride > IFD_PC_MAX_POINTS || (kind != IFD_FGM_FGM && !ori_pc) ||
-        (kind == IFD_FGM_MIFGM && !momentum))
-        return fail(ctx, IFD_ERR_ARG, "ifd_pc_fgm_update: bad argument (grad, pc; ori_pc unless FGM; momentum for MIFGM; 32 <= stride <= 2048)");
-    IFD_ON_CTX_DEVICE(ctx);
-    hipError_t e = launch_fgm_update(kind, grad, pc, ori_pc, momentum, step_size, budget, mu, n_points, B, stride,
-                                     static_cast<hipStream_t>(stream));
-    if (e != hipSuccess) return fail(ctx, IFD_ERR_HIP, "ifd_pc_fgm_update launch", e);
-    return IFD_OK;
-}
-
 int ifd_pc_fgm_attack(ifd_ctx* ctx, const ifd_fgm_params* params, const float* pc_in, const int32_t* n_points, const int32_t* fps_start,
                       const int32_t* target, int B, int stride, float* pc_out, int32_t* success, void* stream) {
-    if (!ctx) return IFD_ERR_ARG;
-    if (int rc = pc_atk_context_ok(ctx, "ifd_pc_fgm_attack")) return rc;
-    if (!params || params->struct_size != (int32_t)sizeof(ifd_fgm_params))
-        return fail(ctx, IFD_ERR_ARG, "ifd_pc_fgm_attack: params missing or of another struct_size");
-    if (!atk_kind_ok(params->kind) || !atk_loss_ok(params->loss_kind) || params->num_iter < 1)
-        return fail(ctx, IFD_ERR_ARG, "ifd_pc_fgm_attack: unknown kind or loss_kind, or num_iter < 1");
-    if (!pc_in || !target || !pc_out || !success || pc_in == pc_out || B < 1)
-        return fail(ctx, IFD_ERR_ARG, "ifd_pc_fgm_attack: bad argument (pc_in, target, pc_out, success; B >= 1)");
-    if (int rc = pc_atk_stride_ok(ctx, "ifd_pc_fgm_attack", stride)) return rc;
-    IFD_ON_CTX_DEVICE(ctx);
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    const size_t cloud = (size_t)stride * 12, state = carved_bytes([&](Carve& c) { FgmLoop(c, (size_t)B, cloud); });
-    hipError_t e = ctx->ws.grow(state + pc_grad_ws_bytes(B));          // the final forward's workspace is the front of the gradient's
-    if (e != hipSuccess) return fail(ctx, IFD_ERR_NOMEM, "ifd_pc_fgm_attack: workspace", e);
-    if (int rc = pc_atk_check(ctx, "ifd_pc_fgm_attack", n_points, fps_start, target, B, stride, s)) return rc;
-    Carve c(ctx->ws.get());
-    const FgmLoop L(c, (size_t)B, cloud);
-    e = hipMemcpyAsync(pc_out, pc_in, (size_t)B * cloud, hipMemcpyDeviceToDevice, s);
-    if (e == hipSuccess && params->kind == IFD_FGM_MIFGM) e = hipMemsetAsync(L.mom, 0, (size_t)B * cloud, s);
-    if (e != hipSuccess) return fail(ctx, IFD_ERR_HIP, "ifd_pc_fgm_attack: start", e);
-    const int iters = params->kind == IFD_FGM_FGM ? 1 : params->num_iter;
-    for (int it = 0; it < iters; ++it) {
-        if (int rc = pc_input_grad_impl(ctx, state, pc_out, n_points, fps_start, B, stride, target, params->loss_kind, params->kappa,
-                                        params->scale, L.grad, nullptr, s))
-            return rc;
-        e = launch_fgm_update(params->kind, L.grad, pc_out, pc_in, L.mom, params->step_size, params->budget, params->mu, n_points, B, stride, s);
-        if (e != hipSuccess) return fail(ctx, IFD_ERR_HIP, "ifd_pc_fgm_attack: update", e);
-    }
-    ifd_pc_aux aux{};
-    aux.pred = L.pred;
-    if (int rc = pc_forward_impl(ctx, pc_out, n_points, fps_start, B, stride, L.logits, &aux, stream, false, state)) return rc;
-    e = launch_atk_success(L.pred, target, B, success, s);
-    if (e != hipSuccess) return fail(ctx, IFD_ERR_HIP, "ifd_pc_fgm_attack: success", e);
-    return IFD_OK;
+    return victim_fgm_attack<PcVictim>(ctx, "ifd_pc_fgm_attack", params, pc_in, n_points, fps_start, target, B, stride, pc_out, success, stream);
 }
 
 }  // extern "C"

@@ -3,9 +3,9 @@
 // The forward half is launch_dgcnn itself (dgcnn.hip), so logits, pred, feat, the global feature and the tables are its bits;
 // it leaves feat, the four tables, the tiles' maxima, f1 and f2 behind.  The backward half, in launch order:
 //
-//   loss_grad_kernel         (pointnet_grad.hip) logits, target -> loss, scale * d loss / d logits
-//   linear_kernel<DgLinear>  the three FC layers transposed (DgGradImage.fct, zero bias, no activation), a cloud a row;
-//   dg_slope_kernel          times LeakyReLU's derivative at the saved activation: 1 where it is > 0, else 0.2
+//   launch_head_backward     (victim_linear.h) loss_grad_kernel: logits, target -> loss, scale * d loss / d logits; the three FC
+//                            layers transposed (DgGradImage.fct, zero bias, no activation), a cloud a row; act_gate_kernel between
+//                            them: times LeakyReLU's derivative at the saved activation, 1 where it is > 0, else 0.2
 //   dg_pool_wtile_kernel     per channel the first 64-point tile whose maximum is the cloud's
 //   dg_conv5_bwd_kernel      the hot kernel, a workgroup a 64-point tile.  conv5's [points, 1024] output is never stored: per chunk
 //                            of 64 channels, ascending, the tile's pre-activations are recomputed by linear_kernel<DgConv5>'s own
@@ -37,11 +37,6 @@ namespace {
 constexpr int DGB_LD = 68;              // floats of a row of the dY chunk in LDS: 64 channels + 4, so a quarter wave's b128 reads spread over all banks
 constexpr int DGB_NONE = 0x7fffffff;
 static_assert(DG_TILE == 64 && DG_FEAT == 512 && DG_EMB == 1024, "dg_conv5_bwd_kernel's tiling");
-
-__global__ __launch_bounds__(256) void dg_slope_kernel(float* __restrict__ d, const float* __restrict__ act, int n) {
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    if (i < n) d[i] = act[i] > 0.f ? d[i] : 0.2f * d[i];
-}
 
 __global__ __launch_bounds__(256) void dg_pool_wtile_kernel(const float* __restrict__ part_max, const float* __restrict__ gfeat,
                                                             const int32_t* __restrict__ n_points, int stride, int T,
@@ -325,14 +320,8 @@ hipError_t launch_dgcnn_grad(const float* img, const DgImage& I, const float* gi
     o.pred = w.pred;
     hipError_t e = launch_dgcnn(img, I, pc, n_points, B, stride, k, w.f, o, w.logits, n_classes, s);
     if (e != hipSuccess) return e;
-    e = launch_loss_grad(w.logits, target, B, n_classes, loss_kind, kappa, scale, w.loss, w.d_out, s);
+    e = launch_head_backward<DgLinear>(gimg, G.fct, w, target, B, n_classes, loss_kind, kappa, scale, w.g, 2 * DG_EMB, s);
     if (e != hipSuccess) return e;
-    // the head, a cloud a row
-    launch_linear<DgLinear>(gimg, G.fct[2], w.d_out, 64, 0, nullptr, 1, B, w.d2, 256, 0, 0, s);
-    hipLaunchKernelGGL(dg_slope_kernel, dim3((B * 256 + 255) / 256), block, 0, s, w.d2, (const float*)w.f.f2, B * 256);
-    launch_linear<DgLinear>(gimg, G.fct[1], w.d2, 256, 0, nullptr, 1, B, w.d1, 512, 0, 0, s);
-    hipLaunchKernelGGL(dg_slope_kernel, dim3((B * 512 + 255) / 256), block, 0, s, w.d1, (const float*)w.f.f1, B * 512);
-    launch_linear<DgLinear>(gimg, G.fct[0], w.d1, 512, 0, nullptr, 1, B, w.g, 2 * DG_EMB, 0, 0, s);
     // the pool and conv5
     const int T = (stride + DG_TILE - 1) / DG_TILE;
     hipLaunchKernelGGL(dg_pool_wtile_kernel, dim3(B), block, 0, s, (const float*)w.f.part_max, (const float*)w.f.gfeat, n_points, stride, T,

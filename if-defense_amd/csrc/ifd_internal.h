@@ -256,7 +256,19 @@ hipError_t launch_cls(const float* img, const ClsImage& I, bool feature_transfor
                       int stride, const ClsWs& w, float* logits, int n_classes, int32_t* pred, hipStream_t s);
 
 
-// ---- PointNet input gradients and the FGM updates (pointnet_grad.hip; C ABI in include/ifd_atk.h) -------------------
+// ---- shared by the victims' attacks (pointnet_grad.hip; C ABI in include/ifd_atk.h) ----------------------------------
+// the one check of every attack call: bad[0] = clouds with n_points outside [lo, hi] (n_points may be null), bad[1] = targets
+// outside [0, n_classes)
+hipError_t launch_atk_check(const int32_t* n_points, const int32_t* target, int B, int lo, int hi, int n_classes, int32_t* bad,
+                            hipStream_t s);
+// loss [B] and d_out [B][64] = scale * d loss / d logits (zeros behind the classes), the losses of include/ifd_atk.h
+hipError_t launch_loss_grad(const float* logits, const int32_t* target, int B, int n_classes, int loss_kind, float kappa, float scale,
+                            float* loss, float* d_out, hipStream_t s);
+hipError_t launch_fgm_update(int kind, const float* grad, float* pc, const float* ori_pc, float* momentum, float step_size, float budget,
+                             float mu, const int32_t* n_points, int B, int stride, hipStream_t s);
+hipError_t launch_atk_success(const int32_t* pred, const int32_t* target, int B, int32_t* success, hipStream_t s);
+
+// ---- PointNet input gradients (pointnet_grad.hip; C ABI in include/ifd_atk.h) ------------------------------------------
 // The backward pass's own weight image (api.cpp build_cls_grad_image): the FC layers transposed in the MFMA tile layout
 // (a layer [out][in] becomes the layer [in][out padded to 64], zero bias), the point stacks' layers row-major.
 struct ClsGradStack { int w1, w2, b2, w3; };     // w1: the forward's [64][4] = {w0, w1, w2, bias}; w2 [128][64]; b2 [128]; w3 [1024][128]
@@ -265,7 +277,7 @@ struct ClsGradImage {
     ClsFc stn_fct[3], head_fct[3];              // fc1^T, fc2^T, fc3^T
     int total;
 };
-struct ClsGradWs {                              // per-chunk scratch of ifd_cls_input_grad (api.cpp cls_grad_bytes_per_cloud)
+struct ClsGradWs {                              // per-chunk scratch of ifd_cls_input_grad (api.cpp cls_grad_ws)
     float* part;        // [B][T][1024]
     int32_t* part_idx;  // [B][T][1024]
     float *gmax_stn, *gmax;          // [B][1024]
@@ -283,17 +295,10 @@ struct ClsGradWs {                              // per-chunk scratch of ifd_cls_
 };
 hipError_t launch_cls_win(const float* img, const ClsImage& I, const float* pc, const int32_t* n_points, int B, int stride,
                           const ClsGradWs& w, int n_classes, hipStream_t s);
-// the one check of every attack call: bad[0] = clouds with n_points outside [lo, hi] (n_points may be null), bad[1] = targets
-// outside [0, n_classes)
-hipError_t launch_atk_check(const int32_t* n_points, const int32_t* target, int B, int lo, int hi, int n_classes, int32_t* bad,
-                            hipStream_t s);
 // after launch_cls_win: loss, its gradient through the head, the trunk, the STN head and the STN stack -> grad [B][stride][3]
 hipError_t launch_cls_backward(const float* img, const ClsImage& I, const float* gimg, const ClsGradImage& G, const float* pc,
                                const int32_t* n_points, int B, int stride, const int32_t* target, int loss_kind, float kappa, float scale,
                                const ClsGradWs& w, int n_classes, float* grad, hipStream_t s);
-hipError_t launch_fgm_update(int kind, const float* grad, float* pc, const float* ori_pc, float* momentum, float step_size, float budget,
-                             float mu, const int32_t* n_points, int B, int stride, hipStream_t s);
-hipError_t launch_atk_success(const int32_t* pred, const int32_t* target, int B, int32_t* success, hipStream_t s);
 
 // torch.optim.Adam's scalars of step t for the attacks' step kernels (atk_device.h atk_adam): step_size = lr / (1 - b1^t),
 // bc2 = sqrt(1 - b2^t), omb1 = 1 - b1, omb2 = 1 - b2.  torch/optim/adam.py: Python doubles, rounded to float where they meet the
@@ -495,9 +500,6 @@ struct DgGradOut {                      // ifd_dgcnn_grad_out's members that the
 hipError_t launch_dgcnn_grad(const float* img, const DgImage& I, const float* gimg, const DgGradImage& G, const float* pc,
                              const int32_t* n_points, int B, int stride, int k, const int32_t* target, int loss_kind, float kappa,
                              float scale, const DgGradWs& w, const DgGradOut& out, int n_classes, float* grad, hipStream_t s);
-// loss [B] and d_out [B][64] = scale * d loss / d logits (zeros behind the classes), the losses of include/ifd_atk.h (pointnet_grad.hip)
-hipError_t launch_loss_grad(const float* logits, const int32_t* target, int B, int n_classes, int loss_kind, float kappa, float scale,
-                            float* loss, float* d_out, hipStream_t s);
 
 // ---- victim classifier: PointNet++ (pointnet2.hip; C ABI in include/ifd_pn2.h) ----------------------------------------
 constexpr int PN2_MAX_POINTS = 2048;    // IFD_PN2_MAX_POINTS

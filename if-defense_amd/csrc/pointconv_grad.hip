@@ -5,9 +5,9 @@
 // it leaves xyz1 .. xyz3, the tables, dens1 .. dens3, l1_feat, u2, l2_feat, s3a, s3b, s3c, wn3, gfeat, f1 and f2 behind, and its
 // contraction buffer g, dead by then, takes d G of one level after the other.  The backward half, in launch order:
 //
-//   loss_grad_kernel          (pointnet_grad.hip) logits, target -> loss, scale * d loss / d logits
+//   launch_head_backward      (victim_linear.h) loss_grad_kernel: logits, target -> loss, scale * d loss / d logits; the head's layers
 //   linear_kernel<Pn2Linear>  every dense layer transposed (PcGradImage, zero bias, no activation): the head, the three wide linears
-//                             (d G = W_l^T d Y), sa3's MLP, sa2's U; pc_gate_kernel applies ReLU's derivative at the saved activation
+//                             (d G = W_l^T d Y), sa3's MLP, sa2's U; act_gate_kernel applies ReLU's derivative at the saved activation
 //   pc_sa3_bwd_kernel         a workgroup a row k of sa3: d t, d Wn, d s and d F from d G; WeightNet backward
 //   pc_density_a_kernel       the forward's density again (a wave a point), DensityNet forward and backward: a_j = d rho_j / (n c2)
 //   pc_centre_bwd_kernel      sa3's centre: d xyz2[g] = d delta[g] - mean of all d delta
@@ -35,11 +35,6 @@ constexpr int PC_PG_THREADS = 128;                                      // point
 constexpr size_t PC_GB = (size_t)PC_NP1 * 128 * PC_WN;                 // floats of a cloud's contraction buffer
 static_assert(PC_NP1 == 512 && PC_K1 == 32 && PC_NP2 == 128 && PC_K2 == 64 && PC_EMB == 1024 && PC_WN == 16 && LINEAR_TILE == 64,
               "the tilings of the backward kernels");
-
-__global__ __launch_bounds__(256) void pc_gate_kernel(float* __restrict__ d, const float* __restrict__ act, int n) {
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    if (i < n) d[i] = act[i] > 0.f ? d[i] : 0.f;
-}
 
 // mgate3 [B][128][56]: words 0 .. 7 of a row s3a's 256 channels, 8 .. 23 s3b's 512, 24 .. 55 s3c's 1024
 __global__ __launch_bounds__(256) void pc_act3_kernel(const float* __restrict__ s3a, const float* __restrict__ s3b, const float* __restrict__ s3c,
@@ -622,11 +617,9 @@ hipError_t launch_pc_grad(const float* img, const PcImage& I, const float* gimg,
     const float* gfeat = o.gfeat ? o.gfeat : w.f.gfeat;
     const PcLevel &S1 = I.sa[0], &S2 = I.sa[1], &S3 = I.sa[2];
     const PcGradLevel &T1 = G.sa[0], &T2 = G.sa[1], &T3 = G.sa[2];
-    e = launch_loss_grad(w.logits, target, B, n_classes, loss_kind, kappa, scale, w.loss, w.d_out, s);
+    e = launch_head_backward<Pn2Linear>(gimg, G.fct, w, target, B, n_classes, loss_kind, kappa, scale, w.dg, PC_EMB, s);
     if (e != hipSuccess) return e;
-    auto gate = [&](float* d, const float* act, int n) {
-        hipLaunchKernelGGL(pc_gate_kernel, dim3((n + 255) / 256), block, 0, s, d, act, n);
-    };
+    auto gate = [&](float* d, const float* act, int n) { launch_act_gate<Pn2Linear>(d, act, n, s); };
     // a level's density: a_j from d s, then the N-body term added to `base`
     auto density = [&](int level, const float* X, int xs, const int32_t* np, const float* ds, int lds, uint32_t* dgate, int ldg,
                        const float* base, int sb, float* dst, int so, int ldo, int zero_beyond) {
@@ -636,12 +629,7 @@ hipError_t launch_pc_grad(const float* img, const PcImage& I, const float* gimg,
         hipLaunchKernelGGL(pc_density_nbody_kernel, grid, block, 0, s, X, (size_t)xs * 3, np, xs, pc_two_bw2(level), (const float*)w.aj, base,
                            sb, dst, so, ldo, zero_beyond);
     };
-    // the head, a cloud a row, and sa3's wide linear
-    launch_linear<Pn2Linear>(gimg, G.fct[2], w.d_out, 64, 0, nullptr, 1, B, w.d2, 256, 0, 0, s);
-    gate(w.d2, w.f.f2, B * 256);
-    launch_linear<Pn2Linear>(gimg, G.fct[1], w.d2, 256, 0, nullptr, 1, B, w.d1, 512, 0, 0, s);
-    gate(w.d1, w.f.f1, B * 512);
-    launch_linear<Pn2Linear>(gimg, G.fct[0], w.d1, 512, 0, nullptr, 1, B, w.dg, PC_EMB, 0, 0, s);
+    // sa3's wide linear
     gate(w.dg, gfeat, B * PC_EMB);
     launch_linear<Pn2Linear>(gimg, T3.lint, w.dg, PC_EMB, 0, nullptr, 1, B, w.f.g, (int)PC_GB, 0, 0, s);
     // sa3

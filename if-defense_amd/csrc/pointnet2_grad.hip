@@ -4,14 +4,14 @@
 // The forward half is launch_pn2 itself (pointnet2.hip), so logits, pred, the tables and the features are its bits; it leaves
 // xyz1, xyz2, the tables, l1_feat, u2, l2_feat, s3a, s3b, the tiles' maxima, gfeat, f1 and f2 behind.  The backward half, in launch order:
 //
-//   loss_grad_kernel          (pointnet_grad.hip) logits, target -> loss, scale * d loss / d logits
-//   linear_kernel<Pn2Linear>  the three FC layers transposed (Pn2GradImage.fct, zero bias, no activation), a cloud a row;
-//   pn2_gate_kernel           times ReLU's derivative at the saved activation: 1 where it is > 0, else 0
+//   launch_head_backward      (victim_linear.h) loss_grad_kernel: logits, target -> loss, scale * d loss / d logits; the three FC
+//                             layers transposed (Pn2GradImage.fct, zero bias, no activation), a cloud a row; act_gate_kernel between
+//                             them: times ReLU's derivative at the saved activation, 1 where it is > 0, else 0
 //   pn2_sa3_win_kernel        sa3's last layer again per 64-row tile, by linear_kernel<Pn2Sa3Last>'s own instruction sequence: per
 //                             channel the lowest row whose activation equals the saved global feature
 //   pn2_sa3_sparse_kernel     the last layer transposed in its sparse form: a workgroup a row g, one chain over the channels c it
 //                             won, ascending: d s3b[g][k] += d gfeat[c] W[c][k], then the gate s3b > 0
-//   linear_kernel<Pn2Linear>  512 -> 256 transposed, pn2_gate_kernel (s3a), 256 -> 256 transposed (d l2_feat) and 256 -> 3 (xyz2's
+//   linear_kernel<Pn2Linear>  512 -> 256 transposed, act_gate_kernel (s3a), 256 -> 256 transposed (d l2_feat) and 256 -> 3 (xyz2's
 //                             columns of sa3's first layer)
 //   pn2_sa2_bwd_kernel        a workgroup a group of 64 rows: the forward's tile again (same instruction sequence), winners of the
 //                             256 channels, the last layer transposed in its sparse form (one row per channel), the 128 x 128 middle
@@ -38,11 +38,6 @@ constexpr int P2G_NONE = 0x7fffffff;
 constexpr int PN2_ROWS1 = PN2_NP1 * PN2_NS1, PN2_ROWS2 = PN2_NP2 * PN2_NS2;
 static_assert(PN2_NP1 == 512 && PN2_NS1 == 32 && PN2_NP2 == 128 && PN2_NS2 == 64 && PN2_EMB == 1024 && LINEAR_TILE == 64,
               "the tilings of the backward kernels");
-
-__global__ __launch_bounds__(256) void pn2_gate_kernel(float* __restrict__ d, const float* __restrict__ act, int n) {
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    if (i < n) d[i] = act[i] > 0.f ? d[i] : 0.f;
-}
 
 // act3 [B][128][24]: word w < 8 of a row: s3a's channels 32 w .. 32 w + 31; w >= 8: s3b's channels 32 (w - 8) ..
 __global__ __launch_bounds__(256) void pn2_act3_kernel(const float* __restrict__ s3a, const float* __restrict__ s3b, int B,
@@ -536,24 +531,15 @@ hipError_t launch_pn2_grad(const float* img, const Pn2Image& I, const float* gim
     const float* l1 = out.l1_feat ? out.l1_feat : w.f.l1_feat;
     const float* l2 = out.l2_feat ? out.l2_feat : w.f.l2_feat;
     const float* gfeat = out.gfeat ? out.gfeat : w.f.gfeat;
-    e = launch_loss_grad(w.logits, target, B, n_classes, loss_kind, kappa, scale, w.loss, w.d_out, s);
+    e = launch_head_backward<Pn2Linear>(gimg, G.fct, w, target, B, n_classes, loss_kind, kappa, scale, w.dg, PN2_EMB, s);
     if (e != hipSuccess) return e;
-    auto gate = [&](float* d, const float* act, int n) {
-        hipLaunchKernelGGL(pn2_gate_kernel, dim3((n + 255) / 256), block, 0, s, d, act, n);
-    };
-    // the head, a cloud a row
-    launch_linear<Pn2Linear>(gimg, G.fct[2], w.d_out, 64, 0, nullptr, 1, B, w.d2, 256, 0, 0, s);
-    gate(w.d2, w.f.f2, B * 256);
-    launch_linear<Pn2Linear>(gimg, G.fct[1], w.d2, 256, 0, nullptr, 1, B, w.d1, 512, 0, 0, s);
-    gate(w.d1, w.f.f1, B * 512);
-    launch_linear<Pn2Linear>(gimg, G.fct[0], w.d1, 512, 0, nullptr, 1, B, w.dg, PN2_EMB, 0, 0, s);
     // sa3
     hipLaunchKernelGGL(pn2_sa3_win_kernel, dim3(PN2_EMB / 64, B), block, 0, s, img + I.sa3[1].w, img + I.sa3[1].b, (const float*)w.f.s3b, gfeat,
                        w.win3);
     hipLaunchKernelGGL(pn2_sa3_sparse_kernel, dim3(PN2_NP2, B), block, 0, s, img + I.sa3[1].w, (const int32_t*)w.win3, gfeat,
                        (const float*)w.dg, (const float*)w.f.s3b, w.ds3b);
     launch_linear<Pn2Linear>(gimg, G.s3t, w.ds3b, 512, (size_t)PN2_NP2 * 512, nullptr, B, PN2_NP2, w.ds3a, 256, (size_t)PN2_NP2 * 256, 0, s);
-    gate(w.ds3a, w.f.s3a, B * PN2_NP2 * 256);
+    launch_act_gate<Pn2Linear>(w.ds3a, w.f.s3a, B * PN2_NP2 * 256, s);
     launch_linear<Pn2Linear>(gimg, G.s3ut, w.ds3a, 256, (size_t)PN2_NP2 * 256, nullptr, B, PN2_NP2, w.dl2, 256, (size_t)PN2_NP2 * 256, 0, s);
     launch_linear<Pn2Linear>(gimg, G.s3xt, w.ds3a, 256, (size_t)PN2_NP2 * 256, nullptr, B, PN2_NP2, w.dx2a, 4, (size_t)PN2_NP2 * 4, 0, s);
     if (out.act3)

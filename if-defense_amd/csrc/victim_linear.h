@@ -288,4 +288,34 @@ using DgConv5 = LinearPolicy<LinearAct::LEAKY, false, false, LinearPool::MAX_SUM
 using Pn2Linear = LinearPolicy<LinearAct::RELU, true, true, LinearPool::NONE>;
 using Pn2Sa3Last = LinearPolicy<LinearAct::RELU, true, true, LinearPool::MAX>;
 
+// d times the activation's derivative at the saved activation: 1 where it is > 0, else LeakyReLU's 0.2, or ReLU's 0 written as such
+// (0 * d would keep d's sign, and a non-finite d)
+template <LinearAct ACT>
+__global__ __launch_bounds__(256) void act_gate_kernel(float* __restrict__ d, const float* __restrict__ act, int n) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    if constexpr (ACT == LinearAct::LEAKY) d[i] = act[i] > 0.f ? d[i] : 0.2f * d[i];
+    else d[i] = act[i] > 0.f ? d[i] : 0.f;
+}
+template <class P>
+void launch_act_gate(float* d, const float* act, int n, hipStream_t s) {
+    hipLaunchKernelGGL((act_gate_kernel<P::ACT>), dim3((n + 255) / 256), dim3(256), 0, s, d, act, n);
+}
+
+// The classifier head's backward pass, a cloud a row: loss and d_out from the logits (launch_loss_grad), then the three FC layers
+// transposed (fct: fc1^T, fc2^T, fc3^T on a zero bias) with the gates of the saved f2 and f1 between them -> dg [B][emb].
+// w: the victim's *GradWs (logits, loss, d_out, d2, d1, and the forward's f.f1, f.f2).
+template <class P, class Ws>
+hipError_t launch_head_backward(const float* gimg, const DenseLayer (&fct)[3], const Ws& w, const int32_t* target, int B, int n_classes,
+                                int loss_kind, float kappa, float scale, float* dg, int emb, hipStream_t s) {
+    hipError_t e = launch_loss_grad(w.logits, target, B, n_classes, loss_kind, kappa, scale, w.loss, w.d_out, s);
+    if (e != hipSuccess) return e;
+    launch_linear<P>(gimg, fct[2], w.d_out, 64, 0, nullptr, 1, B, w.d2, 256, 0, 0, s);
+    launch_act_gate<P>(w.d2, w.f.f2, B * 256, s);
+    launch_linear<P>(gimg, fct[1], w.d2, 256, 0, nullptr, 1, B, w.d1, 512, 0, 0, s);
+    launch_act_gate<P>(w.d1, w.f.f1, B * 512, s);
+    launch_linear<P>(gimg, fct[0], w.d1, 512, 0, nullptr, 1, B, dg, emb, 0, 0, s);
+    return hipSuccess;
+}
+
 }  // namespace ifd

@@ -22,11 +22,8 @@ from __future__ import annotations
 
 import sys
 
-from .fgm_attack import attack_file, build_parser
-from .inference import default_weight_path
 from .pointconv_inference import MAX_POINTS, MIN_POINTS
-from .pointnet2_fgm_attack import BoundStarts
-from .pointnet2_inference import fps_starts
+from .pointnet2_fgm_attack import BoundStarts, sampled_main  # noqa: F401  (BoundStarts: the tests and callers reach it here too)
 
 PROG = 'pointconv_fgm_attack'
 OTHER_CLI = {'pointnet': "`python -m ifdefense_amd.fgm_attack`", 'dgcnn': "`python -m ifdefense_amd.dgcnn_fgm_attack`",
@@ -34,40 +31,7 @@ OTHER_CLI = {'pointnet': "`python -m ifdefense_amd.fgm_attack`", 'dgcnn': "`pyth
 
 
 def main(argv=None, make_classifier=None) -> int:
-    parser = build_parser()
-    parser.set_defaults(model='pointconv')
-    parser.add_argument('--fps_seed', type=int, default=1, help='seed of the start indices of the farthest point samplings')
-    args = parser.parse_args(argv)
-    if args.model.lower() != 'pointconv':
-        print("{}: only the pointconv victim is attacked here, not {}; attack it with {}".format(
-            PROG, args.model, OTHER_CLI.get(args.model.lower(), "the reference's targeted_fgm_attack.py")), file=sys.stderr)
-        return 2
-    if args.feature_transform:
-        print("{}: --feature_transform belongs to pointnet".format(PROG), file=sys.stderr)
-        return 2
-    sizes = []
-
-    def check_data(data):
-        n = data.shape[1]
-        if n > MAX_POINTS:
-            return "clouds of {} points, more than the {} the PointConv victim takes".format(n, MAX_POINTS)
-        if n < MIN_POINTS:
-            return "clouds of {} points, fewer than the {} the PointConv victim needs".format(n, MIN_POINTS)
-        sizes[:] = [n] * len(data)
-        return None
-
-    def open_classifier():
-        make = make_classifier
-        if make is None:
-            def make(model, model_path):
-                from .runtime import PointConvClassifier
-                from .weights import load_checkpoint
-                return PointConvClassifier(load_checkpoint(model_path, model), device=args.device)
-        model_path = args.model_path or default_weight_path(args.dataset, 'pointconv')
-        print('Loading weight {}'.format(model_path))
-        return BoundStarts(make('pointconv', model_path), fps_starts(args.fps_seed, sizes))
-
-    return attack_file(PROG, args, open_classifier, check_data, on_batch=lambda classifier, a, n: classifier.at(a, n), by_file=True)
+    return sampled_main(PROG, OTHER_CLI, 'pointconv', 'PointConv', 'PointConvClassifier', MIN_POINTS, MAX_POINTS, argv, make_classifier)
 
 
 if __name__ == '__main__':

@@ -71,26 +71,29 @@ class BoundStarts:
             self.classifier.close()
 
 
-def main(argv=None, make_classifier=None) -> int:
+def sampled_main(prog, other_cli, model, label, classifier_name, min_points, max_points, argv, make_classifier) -> int:
+    """main() of the CLI ``prog`` of a victim that samples: ``model`` its --model, ``label`` its name in messages,
+    ``classifier_name`` its class in ifdefense_amd.runtime, [min_points, max_points] the clouds it takes."""
     parser = build_parser()
-    parser.set_defaults(model='pointnet2')
+    parser.set_defaults(model=model)
     parser.add_argument('--fps_seed', type=int, default=1, help='seed of the start indices of the farthest point samplings')
     args = parser.parse_args(argv)
-    if args.model.lower() != 'pointnet2':
-        print("{}: only the pointnet2 victim is attacked here, not {}; attack it with {}".format(
-            PROG, args.model, OTHER_CLI.get(args.model.lower(), "the reference's targeted_fgm_attack.py")), file=sys.stderr)
+    if args.model.lower() != model:
+        print("{}: only the {} victim is attacked here, not {}; attack it with {}".format(
+            prog, model, args.model, other_cli.get(args.model.lower(), "the reference's targeted_fgm_attack.py")), file=sys.stderr)
         return 2
     if args.feature_transform:
-        print("{}: --feature_transform belongs to pointnet".format(PROG), file=sys.stderr)
+        print("{}: --feature_transform belongs to pointnet".format(prog), file=sys.stderr)
         return 2
     sizes = []
 
     def check_data(data):
         n = data.shape[1]
-        if n > MAX_POINTS:
-            return "clouds of {} points, more than the {} the PointNet++ victim takes".format(n, MAX_POINTS)
-        if n < 1:
-            return "empty clouds"
+        if n > max_points:
+            return "clouds of {} points, more than the {} the {} victim takes".format(n, max_points, label)
+        if n < min_points:
+            return "empty clouds" if min_points == 1 else "clouds of {} points, fewer than the {} the {} victim needs".format(
+                n, min_points, label)
         sizes[:] = [n] * len(data)
         return None
 
@@ -98,14 +101,18 @@ def main(argv=None, make_classifier=None) -> int:
         make = make_classifier
         if make is None:
             def make(model, model_path):
-                from .runtime import PointNet2Classifier
+                from . import runtime
                 from .weights import load_checkpoint
-                return PointNet2Classifier(load_checkpoint(model_path, model), device=args.device)
-        model_path = args.model_path or default_weight_path(args.dataset, 'pointnet2')
+                return getattr(runtime, classifier_name)(load_checkpoint(model_path, model), device=args.device)
+        model_path = args.model_path or default_weight_path(args.dataset, model)
         print('Loading weight {}'.format(model_path))
-        return BoundStarts(make('pointnet2', model_path), fps_starts(args.fps_seed, sizes))
+        return BoundStarts(make(model, model_path), fps_starts(args.fps_seed, sizes))
 
-    return attack_file(PROG, args, open_classifier, check_data, on_batch=lambda classifier, a, n: classifier.at(a, n), by_file=True)
+    return attack_file(prog, args, open_classifier, check_data, on_batch=lambda classifier, a, n: classifier.at(a, n), by_file=True)
+
+
+def main(argv=None, make_classifier=None) -> int:
+    return sampled_main(PROG, OTHER_CLI, 'pointnet2', 'PointNet++', 'PointNet2Classifier', 1, MAX_POINTS, argv, make_classifier)
 
 
 if __name__ == '__main__':
