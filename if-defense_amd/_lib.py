@@ -427,6 +427,24 @@ PC_ATK_SIGNATURES = {
                                     C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
 }
 
+# include/ifd_victim_atk.h (Perturb, kNN and Drop on any of the four victims), versioned on its own
+VICTIM_ATK_ABI_VERSION = 1
+
+_P = C.c_void_p
+VICTIM_ATK_SIGNATURES = {
+    "ifd_victim_atk_abi_version": (C.c_int, []),
+    # the step calls: the signatures of ifd_cw_step, ifd_cw_adjust, ifd_knn_step, ifd_knn_project_clip, ifd_drop_step
+    "ifd_victim_cw_step": CW_SIGNATURES["ifd_cw_step"],
+    "ifd_victim_cw_adjust": CW_SIGNATURES["ifd_cw_adjust"],
+    "ifd_victim_knn_step": KNN_SIGNATURES["ifd_knn_step"],
+    "ifd_victim_knn_project_clip": KNN_SIGNATURES["ifd_knn_project_clip"],
+    "ifd_victim_drop_step": DROP_SIGNATURES["ifd_drop_step"],
+    # the loops: fps_start behind n_points
+    "ifd_victim_cw_perturb_attack": (C.c_int, [_P, C.POINTER(IfdCwParams), _P, _P, _P, _P, _P, C.c_int, C.c_int, _P, _P, _P, _P, _P]),
+    "ifd_victim_knn_attack": (C.c_int, [_P, C.POINTER(IfdKnnParams), _P, _P, _P, _P, _P, _P, C.c_int, C.c_int, _P, _P, _P, _P]),
+    "ifd_victim_drop_attack": (C.c_int, [_P, C.POINTER(IfdDropParams), _P, _P, _P, _P, C.c_int, C.c_int, _P, _P, _P, _P, _P]),
+}
+
 _lib = None
 
 
@@ -445,7 +463,8 @@ def load() -> C.CDLL:
             list(ATK_SIGNATURES.items()) + list(CW_SIGNATURES.items()) + list(KNN_SIGNATURES.items()) + list(ADD_SIGNATURES.items()) + \
             list(DROP_SIGNATURES.items()) + list(CLUSTER_SIGNATURES.items()) + list(OBJECT_SIGNATURES.items()) + \
             list(DGCNN_SIGNATURES.items()) + list(DGCNN_ATK_SIGNATURES.items()) + list(PN2_SIGNATURES.items()) + \
-            list(PN2_ATK_SIGNATURES.items()) + list(PC_SIGNATURES.items()) + list(PC_ATK_SIGNATURES.items()):
+            list(PN2_ATK_SIGNATURES.items()) + list(PC_SIGNATURES.items()) + list(PC_ATK_SIGNATURES.items()) + \
+            list(VICTIM_ATK_SIGNATURES.items()):
         fn = getattr(lib, name)          # AttributeError if the library lacks a declared symbol
         fn.restype, fn.argtypes = res, args
     if lib.ifd_abi_version() != ABI_VERSION:
@@ -483,5 +502,8 @@ def load() -> C.CDLL:
     if lib.ifd_pc_atk_abi_version() != PC_ATK_ABI_VERSION:
         raise ImportError("libifd.so PC ATK ABI %d != binding PC ATK ABI %d; rebuild" %
                           (lib.ifd_pc_atk_abi_version(), PC_ATK_ABI_VERSION))
+    if lib.ifd_victim_atk_abi_version() != VICTIM_ATK_ABI_VERSION:
+        raise ImportError("libifd.so VICTIM ATK ABI %d != binding VICTIM ATK ABI %d; rebuild" %
+                          (lib.ifd_victim_atk_abi_version(), VICTIM_ATK_ABI_VERSION))
     _lib = lib
     return lib

@@ -25,6 +25,10 @@ smaller; it draws no noise.  ``CWAddClusters`` is the reference's cluster-adding
 include/ifd_cluster.h): ``num_add`` clusters of ``cl_num_p`` points, started on DBSCAN clusters of the 128 critical points.
 ``CWAddObjects`` is its object-adding attack (baselines/attack/CW/Add_Objects.py, include/ifd_object.h): ``num_add`` copies of an
 object, each placed by a shift and a rotation about the y axis that are optimised with the object's points.
+
+``CWPerturb``, ``CWKNN`` and ``SaliencyDrop`` also run on ``runtime.DgcnnClassifier`` and, through ``victim_atk_cli.BoundLoopStarts``,
+on ``PointNet2Classifier`` and ``PointConvClassifier`` (include/ifd_victim_atk.h).  The host-driven loops ask ``input_grad`` for the
+diagnostics they read only (``want_aux=("pred", "loss")``).
 """
 from __future__ import annotations
 
@@ -90,7 +94,7 @@ class FGM(_Attack):
         tgt = target.to(dev)
         mom = torch.zeros_like(cur) if self.KIND == "mifgm" else None
         for it in range(self.num_iter):
-            grad, aux = self.model.input_grad(cur, tgt, self.adv_func, self.kappa, self._scale(B), want_aux=True)
+            grad, aux = self.model.input_grad(cur, tgt, self.adv_func, self.kappa, self._scale(B), want_aux=("pred",))
             if it % max(self.num_iter // 5, 1) == 0:
                 print('iter {}/{}, success: {}/{}'.format(it, self.num_iter, int((aux["pred"].long() == tgt).sum()), B))
             self.model.fgm_update(self.KIND, grad, cur, ori, mom, self.step_size, self.budget, self.mu)
@@ -185,7 +189,7 @@ class CWPerturb(_Attack):
             adv = ori + noise[step].to(dev)
             info = None
             for it in range(self.num_iter):
-                grad, aux = net.input_grad(adv, tgt, self.adv_func, self.kappa, self._scale(B), want_aux=True)
+                grad, aux = net.input_grad(adv, tgt, self.adv_func, self.kappa, self._scale(B), want_aux=("pred", "loss"))
                 if it % every == 0:
                     self._progress(self.STEP_LINES, step, it, aux["pred"], tgt, info, 1)
                 final = step == self.binary_step - 1 and it == self.num_iter - 1
@@ -257,7 +261,7 @@ class CWKNN(_Attack):
         every = max(self.num_iter // 5, 1)
         info = None
         for it in range(self.num_iter):
-            grad, aux = net.input_grad(adv, tgt, self.adv_func, self.kappa, self._scale(B), want_aux=True)
+            grad, aux = net.input_grad(adv, tgt, self.adv_func, self.kappa, self._scale(B), want_aux=("pred", "loss"))
             if it % every == 0:
                 self._progress('Iteration {}/{}, success {}/{}\nadv_loss: {:.4f}, dist_loss: {:.4f}', it, self.num_iter, aux["pred"], tgt,
                                info, 3)
@@ -694,7 +698,7 @@ class SaliencyDrop(_Attack):
         every = max(num_rounds // 5, 1)
         for i in range(num_rounds):
             k = min(self.k, self.num_drop - i * self.k)
-            grad, aux = net.input_grad(cur, tgt, "cross_entropy", 0., self._scale(B), n_points=n, want_aux=True)
+            grad, aux = net.input_grad(cur, tgt, "cross_entropy", 0., self._scale(B), n_points=n, want_aux=("pred",))
             if i % every == 0:
                 print('Iteration {}/{}, success {}/{}\nPoint num: {}/{}'.format(i, num_rounds, int((aux["pred"].long() == tgt).sum()), B,
                                                                               K_ - i * self.k, K_))

@@ -20,6 +20,7 @@
 #include "../../include/ifd_pn2.h"
 #include "../../include/ifd_pn2_atk.h"
 #include "../../include/ifd_pc_atk.h"
+#include "../../include/ifd_victim_atk.h"
 
 #include <hip/hip_runtime.h>
 
@@ -2507,7 +2508,7 @@ struct DgVictim {
 struct Pn2Victim {
     using Out = ifd_pn2_grad_out;
     using Ws = Pn2GradWs;
-    static constexpr int MODEL = IFD_MODEL_PN2, CHUNK = PN2_CHUNK, MIN_POINTS = 1, MAX_POINTS = IFD_PN2_MAX_POINTS;
+    static constexpr int MODEL = IFD_MODEL_PN2, CHUNK = PN2_CHUNK, MIN_POINTS = 1, MAX_POINTS = IFD_PN2_MAX_POINTS, NP1 = PN2_NP1;
     static constexpr const char *NAME = "PointNet++", *GRAD_WHO = "ifd_pn2_input_grad", *COUNTS = "[1, stride]";
     static constexpr SampleCheck SAMPLE_CHECK = launch_pn2_check;
     static Ws grad_ws(ifd_ctx*, Carve& c, size_t n, int) { return pn2_grad_ws(c, n); }
@@ -2538,7 +2539,7 @@ struct Pn2Victim {
 struct PcVictim {
     using Out = ifd_pc_grad_out;
     using Ws = PcGradWs;
-    static constexpr int MODEL = IFD_MODEL_PC, CHUNK = PC_CHUNK, MIN_POINTS = IFD_PC_MIN_POINTS, MAX_POINTS = IFD_PC_MAX_POINTS;
+    static constexpr int MODEL = IFD_MODEL_PC, CHUNK = PC_CHUNK, MIN_POINTS = IFD_PC_MIN_POINTS, MAX_POINTS = IFD_PC_MAX_POINTS, NP1 = PC_NP1;
     static constexpr const char *NAME = "PointConv", *GRAD_WHO = "ifd_pc_input_grad", *COUNTS = "[32, stride]";
     static constexpr SampleCheck SAMPLE_CHECK = launch_pc_check;
     static Ws grad_ws(ifd_ctx*, Carve& c, size_t n, int) { return pc_grad_ws(c, n); }
@@ -2800,61 +2801,96 @@ int ifd_pc_fgm_attack(ifd_ctx* ctx, const ifd_fgm_params* params, const float* p
 }  // extern "C"
 
 // ---- the CW point-perturbation attack (include/ifd_cw.h) --------------------------------------------------------------
-extern "C" {
+// Every loop below is written once over the victim V (include/ifd_victim_atk.h); the calls of ifd_cw.h, ifd_knn.h and ifd_drop.h
+// are its ClsVictim instance.  `who` names the call in every message.
+namespace {
 
-int ifd_cw_abi_version(void) { return IFD_CW_ABI_VERSION; }
+int hip_fail(ifd_ctx* ctx, const char* who, const char* what, hipError_t e, int code = IFD_ERR_HIP) {
+    return fail(ctx, code, (std::string(who) + what).c_str(), e);
+}
 
-int ifd_cw_step(ifd_ctx* ctx, const ifd_cw_state* state, const float* grad, const int32_t* pred, const float* loss, const int32_t* target,
-                float* adv, const float* ori, float* last_input, float* info, int t, float lr, float scale, const int32_t* n_points, int B,
-                int stride, void* stream) {
-    if (!ctx) return IFD_ERR_ARG;
-    if (int rc = atk_context_ok(ctx, "ifd_cw_step")) return rc;
+// a victim that does not sample takes no starts
+template <class V>
+int starts_ok(ifd_ctx* ctx, const char* who, const int32_t* fps_start) {
+    if (V::SAMPLE_CHECK == nullptr && fps_start) return refuse(ctx, who, std::string(": fps_start must be NULL on a ") + V::NAME + " context");
+    return IFD_OK;
+}
+
+// The one blocking step of a loop on V: counts in [lo, hi] (range_text in the message), targets, and on a victim that samples the
+// starts, which must still name a row after the cloud has lost `shrink` rows.  Uses the first 16 bytes of the workspace.
+template <class V>
+int loop_check(ifd_ctx* ctx, const char* who, const GradCall& g, int lo, int hi, int shrink, const std::string& range_text) {
+    if constexpr (V::SAMPLE_CHECK == nullptr) {
+        return atk_check(ctx, who, g.n_points, g.target, g.B, lo, hi, range_text, g.s);
+    } else {
+        int32_t* d_bad = ctx->ws.get<int32_t>();
+        hipError_t e = launch_victim_sample_check(g.n_points, g.fps_start, g.B, lo, hi, shrink, V::NP1, d_bad, g.s);
+        if (e == hipSuccess) e = launch_atk_check(nullptr, g.target, g.B, 1, g.stride, ctx->cls_classes, d_bad + 2, g.s);
+        int32_t bad[4] = {0, 0, 0, 0};
+        if (int rc = read_bad_counts(ctx, who, "n_points, fps_start and target", e, d_bad, 4, bad, g.s)) return rc;
+        if (bad[0] != 0) return refuse(ctx, who, ": " + std::to_string(bad[0]) + " cloud(s) with n_points outside " + range_text);
+        if (bad[1] != 0)
+            return refuse(ctx, who, ": " + std::to_string(bad[1]) + " cloud(s) with fps_start outside [0, n_points" +
+                                        (shrink ? " - " + std::to_string(shrink) : std::string()) + ") x [0, " + std::to_string(V::NP1) + ")");
+        if (bad[3] != 0) return refuse(ctx, who, ": " + std::to_string(bad[3]) + " target(s) outside [0, 40)");
+        return IFD_OK;
+    }
+}
+
+// the step calls take any victim's context; their strides are the step kernel's own
+template <class V>
+int cw_step_impl(ifd_ctx* ctx, const char* who, const ifd_cw_state* state, const float* grad, const int32_t* pred, const float* loss,
+                 const int32_t* target, float* adv, const float* ori, float* last_input, float* info, int t, float lr, float scale,
+                 const int32_t* n_points, int B, int stride, void* stream) {
+    if (int rc = victim_context_ok<V>(ctx, who)) return rc;
     if (!cw_state_ok(state, false))
-        return fail(ctx, IFD_ERR_ARG, "ifd_cw_step: state missing (m, v, bestdist, bestscore, o_bestdist, o_bestscore, o_bestattack, weight)");
+        return refuse(ctx, who, ": state missing (m, v, bestdist, bestscore, o_bestdist, o_bestscore, o_bestattack, weight)");
     if (!grad || !pred || !target || !adv || !ori || t < 1 || B < 1 || stride < 1 || stride > IFD_CLS_MAX_POINTS)
-        return fail(ctx, IFD_ERR_ARG, "ifd_cw_step: bad argument (grad, pred, target, adv, ori; t >= 1, B >= 1, 1 <= stride <= 10000)");
+        return refuse(ctx, who, ": bad argument (grad, pred, target, adv, ori; t >= 1, B >= 1, 1 <= stride <= 10000)");
     IFD_ON_CTX_DEVICE(ctx);
     hipError_t e = launch_cw_step(cw_state(state), grad, pred, loss, target, adv, ori, last_input, info, t, lr, scale, n_points, B, stride,
                                   static_cast<hipStream_t>(stream));
-    if (e != hipSuccess) return fail(ctx, IFD_ERR_HIP, "ifd_cw_step launch", e);
+    if (e != hipSuccess) return hip_fail(ctx, who, " launch", e);
     return IFD_OK;
 }
 
-int ifd_cw_adjust(ifd_ctx* ctx, const ifd_cw_state* state, const int32_t* target, const int32_t* n_points, int B, int stride, void* stream) {
-    if (!ctx) return IFD_ERR_ARG;
-    if (int rc = atk_context_ok(ctx, "ifd_cw_adjust")) return rc;
-    if (!cw_state_ok(state, true))
-        return fail(ctx, IFD_ERR_ARG, "ifd_cw_adjust: state missing (bestdist, bestscore, o_bestdist, weight, lower, upper)");
+template <class V>
+int cw_adjust_impl(ifd_ctx* ctx, const char* who, const ifd_cw_state* state, const int32_t* target, const int32_t* n_points, int B,
+                   int stride, void* stream) {
+    if (int rc = victim_context_ok<V>(ctx, who)) return rc;
+    if (!cw_state_ok(state, true)) return refuse(ctx, who, ": state missing (bestdist, bestscore, o_bestdist, weight, lower, upper)");
     if (!target || B < 1 || stride < 1 || stride > IFD_CLS_MAX_POINTS)
-        return fail(ctx, IFD_ERR_ARG, "ifd_cw_adjust: bad argument (target; B >= 1, 1 <= stride <= 10000)");
+        return refuse(ctx, who, ": bad argument (target; B >= 1, 1 <= stride <= 10000)");
     IFD_ON_CTX_DEVICE(ctx);
     hipError_t e = launch_cw_adjust(cw_state(state), target, n_points, B, stride, static_cast<hipStream_t>(stream));
-    if (e != hipSuccess) return fail(ctx, IFD_ERR_HIP, "ifd_cw_adjust launch", e);
+    if (e != hipSuccess) return hip_fail(ctx, who, " launch", e);
     return IFD_OK;
 }
 
-int ifd_cw_perturb_attack(ifd_ctx* ctx, const ifd_cw_params* params, const float* pc_in, const int32_t* n_points, const int32_t* target,
-                          const float* noise, int B, int stride, float* pc_out, float* best_dist, int32_t* success, double* bounds,
-                          void* stream) {
-    if (!ctx) return IFD_ERR_ARG;
-    if (int rc = atk_context_ok(ctx, "ifd_cw_perturb_attack")) return rc;
-    if (!params || params->struct_size != (int32_t)sizeof(ifd_cw_params))
-        return fail(ctx, IFD_ERR_ARG, "ifd_cw_perturb_attack: params missing or of another struct_size");
-    if (params->binary_step < 1) return fail(ctx, IFD_ERR_ARG, "ifd_cw_perturb_attack: binary_step < 1");
-    if (params->num_iter < 1) return fail(ctx, IFD_ERR_ARG, "ifd_cw_perturb_attack: num_iter < 1");
-    if (!atk_loss_ok(params->loss_kind)) return fail(ctx, IFD_ERR_ARG, "ifd_cw_perturb_attack: unknown loss_kind");
-    if (B < 1) return fail(ctx, IFD_ERR_ARG, "ifd_cw_perturb_attack: B >= 1 is needed");
-    if (stride < 1 || stride > IFD_CLS_MAX_POINTS) return fail(ctx, IFD_ERR_ARG, "ifd_cw_perturb_attack: stride outside [1, 10000]");
+template <class V>
+int cw_perturb_impl(ifd_ctx* ctx, const char* who, const ifd_cw_params* params, const float* pc_in, const int32_t* n_points,
+                    const int32_t* fps_start, const int32_t* target, const float* noise, int B, int stride, float* pc_out,
+                    float* best_dist, int32_t* success, double* bounds, void* stream) {
+    if (int rc = victim_context_ok<V>(ctx, who)) return rc;
+    if (!params || params->struct_size != (int32_t)sizeof(ifd_cw_params)) return refuse(ctx, who, ": params missing or of another struct_size");
+    if (params->binary_step < 1) return refuse(ctx, who, ": binary_step < 1");
+    if (params->num_iter < 1) return refuse(ctx, who, ": num_iter < 1");
+    if (!atk_loss_ok(params->loss_kind)) return refuse(ctx, who, ": unknown loss_kind");
+    if (B < 1) return refuse(ctx, who, ": B >= 1 is needed");
+    const int lo = victim_min_points<V>(ctx);
+    if (stride < lo || stride > V::MAX_POINTS) return refuse(ctx, who, ": stride outside " + numeric_range(lo, V::MAX_POINTS));
     if (!pc_in || !target || !pc_out || !best_dist || !success)
-        return fail(ctx, IFD_ERR_ARG, "ifd_cw_perturb_attack: missing pointer (pc_in, target, pc_out, best_dist, success)");
+        return refuse(ctx, who, ": missing pointer (pc_in, target, pc_out, best_dist, success)");
+    if (int rc = starts_ok<V>(ctx, who, fps_start)) return rc;
     const size_t cloud = (size_t)stride * 12, all = (size_t)B * cloud;
-    if (clouds_overlap(pc_in, all, pc_out, all)) return fail(ctx, IFD_ERR_ARG, "ifd_cw_perturb_attack: pc_out overlaps pc_in");
+    if (clouds_overlap(pc_in, all, pc_out, all)) return refuse(ctx, who, ": pc_out overlaps pc_in");
     IFD_ON_CTX_DEVICE(ctx);
     hipStream_t s = static_cast<hipStream_t>(stream);
     const size_t state = carved_bytes([&](Carve& c) { CwLoop(c, (size_t)B, cloud); });
-    hipError_t e = ctx->ws.grow(atk_loop_ws_bytes(B, stride, state, false));
-    if (e != hipSuccess) return fail(ctx, IFD_ERR_NOMEM, "ifd_cw_perturb_attack: workspace", e);
-    if (int rc = atk_check(ctx, "ifd_cw_perturb_attack", n_points, target, B, 1, stride, "[1, stride]", s)) return rc;
+    hipError_t e = ctx->ws.grow(loop_ws_bytes<V>(ctx, B, stride, state, false));
+    if (e != hipSuccess) return hip_fail(ctx, who, ": workspace", e, IFD_ERR_NOMEM);
+    GradCall g{nullptr, n_points, fps_start, target, B, stride, params->loss_kind, params->kappa, params->scale, nullptr, s};
+    if (int rc = loop_check<V>(ctx, who, g, lo, stride, 0, V::COUNTS)) return rc;
     Carve c(ctx->ws.get());
     const CwLoop L(c, (size_t)B, cloud);
     CwState S = L.f.S;
@@ -2864,36 +2900,140 @@ int ifd_cw_perturb_attack(ifd_ctx* ctx, const ifd_cw_params* params, const float
     S.o_bestattack = pc_out;
     e = launch_cw_init(S, B, params->init_weight, params->max_weight, s);
     if (e == hipSuccess) e = hipMemsetAsync(S.m, 0, 2 * all, s);       // m and v lie side by side
-    if (e != hipSuccess) return fail(ctx, IFD_ERR_HIP, "ifd_cw_perturb_attack: start", e);
-    const ifd_atk_out out{nullptr, loss, pred, nullptr, nullptr, nullptr};
+    if (e != hipSuccess) return hip_fail(ctx, who, ": start", e);
+    typename V::Out out{};
+    out.loss = loss;
+    out.pred = pred;
+    g.pc = adv;
+    g.grad = grad;
     if (int rc = cw_search(
         params->binary_step, params->num_iter,
         [&](int step) {
             hipError_t e = launch_cw_start(pc_in, noise ? noise + (size_t)step * B * stride * 3 : nullptr, adv, n_points, B, stride, s);
-            return e == hipSuccess ? IFD_OK : fail(ctx, IFD_ERR_HIP, "ifd_cw_perturb_attack: search step start", e);
+            return e == hipSuccess ? IFD_OK : hip_fail(ctx, who, ": search step start", e);
         },
         [&](int, int it, bool final_it) {
-            if (int rc = input_grad_impl(ctx, state, adv, n_points, B, stride, target, params->loss_kind, params->kappa, params->scale, grad,
-                                         &out, s))
-                return rc;
+            if (int rc = victim_grad<V>(ctx, state, g, &out)) return rc;
             hipError_t e = launch_cw_step(S, grad, pred, loss, target, adv, pc_in, final_it ? last : nullptr, nullptr, it + 1,
                                           params->attack_lr, params->scale, n_points, B, stride, s);
-            return e == hipSuccess ? IFD_OK : fail(ctx, IFD_ERR_HIP, "ifd_cw_perturb_attack: step", e);
+            return e == hipSuccess ? IFD_OK : hip_fail(ctx, who, ": step", e);
         },
         [&](int) {
             hipError_t e = launch_cw_adjust(S, target, n_points, B, stride, s);
-            return e == hipSuccess ? IFD_OK : fail(ctx, IFD_ERR_HIP, "ifd_cw_perturb_attack: adjust", e);
+            return e == hipSuccess ? IFD_OK : hip_fail(ctx, who, ": adjust", e);
         }))
         return rc;
     e = launch_cw_finish(S, last, pc_out, success, bounds, n_points, B, stride, s);
-    if (e != hipSuccess) return fail(ctx, IFD_ERR_HIP, "ifd_cw_perturb_attack: finish", e);
+    if (e != hipSuccess) return hip_fail(ctx, who, ": finish", e);
     return IFD_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int ifd_cw_abi_version(void) { return IFD_CW_ABI_VERSION; }
+
+int ifd_cw_step(ifd_ctx* ctx, const ifd_cw_state* state, const float* grad, const int32_t* pred, const float* loss, const int32_t* target,
+                float* adv, const float* ori, float* last_input, float* info, int t, float lr, float scale, const int32_t* n_points, int B,
+                int stride, void* stream) {
+    if (!ctx) return IFD_ERR_ARG;
+    return cw_step_impl<ClsVictim>(ctx, "ifd_cw_step", state, grad, pred, loss, target, adv, ori, last_input, info, t, lr, scale, n_points, B,
+                                   stride, stream);
+}
+
+int ifd_cw_adjust(ifd_ctx* ctx, const ifd_cw_state* state, const int32_t* target, const int32_t* n_points, int B, int stride, void* stream) {
+    if (!ctx) return IFD_ERR_ARG;
+    return cw_adjust_impl<ClsVictim>(ctx, "ifd_cw_adjust", state, target, n_points, B, stride, stream);
+}
+
+int ifd_cw_perturb_attack(ifd_ctx* ctx, const ifd_cw_params* params, const float* pc_in, const int32_t* n_points, const int32_t* target,
+                          const float* noise, int B, int stride, float* pc_out, float* best_dist, int32_t* success, double* bounds,
+                          void* stream) {
+    if (!ctx) return IFD_ERR_ARG;
+    return cw_perturb_impl<ClsVictim>(ctx, "ifd_cw_perturb_attack", params, pc_in, n_points, nullptr, target, noise, B, stride, pc_out,
+                                      best_dist, success, bounds, stream);
 }
 
 }  // extern "C"
 
 // ---- the kNN attack (include/ifd_knn.h) ----------------------------------------------------------------------------------
 static_assert(IFD_KNN_MAX_POINTS == ifd::KNN_MAX_POINTS, "the header's limit is the kernel's");
+
+namespace {
+
+template <class V>
+int knn_step_impl(ifd_ctx* ctx, const char* who, const ifd_knn_params* params, const float* grad, const float* loss, float* adv,
+                  const float* ori, const float* normal, float* m, float* v, int t, float lr, float scale, const ifd_knn_diag* diag,
+                  const int32_t* n_points, int B, int stride, void* stream) {
+    if (int rc = victim_context_ok<V>(ctx, who)) return rc;
+    if (!params || params->struct_size != (int32_t)sizeof(ifd_knn_params)) return refuse(ctx, who, ": params missing or of another struct_size");
+    if (B < 1) return refuse(ctx, who, ": B >= 1 is needed");
+    if (stride < IFD_KNN_MIN_POINTS || stride > IFD_KNN_MAX_POINTS) return refuse(ctx, who, ": stride outside [6, 2048]");
+    if (!grad || !adv || !ori || !m || !v || t < 1) return refuse(ctx, who, ": missing pointer (grad, adv, ori, m, v) or t < 1");
+    IFD_ON_CTX_DEVICE(ctx);
+    const KnnDiag D = diag ? KnnDiag{diag->info, diag->dist_grad, diag->nn_ori, diag->nn5, diag->mask} : KnnDiag{};
+    hipError_t e = launch_knn_step(grad, loss, adv, ori, normal, m, v, D, params->chamfer_weight, params->knn_weight, params->alpha,
+                                   params->budget, t, lr, scale, n_points, B, stride, static_cast<hipStream_t>(stream));
+    if (e != hipSuccess) return hip_fail(ctx, who, " launch", e);
+    return IFD_OK;
+}
+
+template <class V>
+int knn_clip_impl(ifd_ctx* ctx, const char* who, float* adv, const float* ori, const float* normal, float budget, const int32_t* n_points,
+                  int B, int stride, void* stream) {
+    if (int rc = victim_context_ok<V>(ctx, who)) return rc;
+    if (B < 1) return refuse(ctx, who, ": B >= 1 is needed");
+    if (stride < 1 || stride > IFD_CLS_MAX_POINTS) return refuse(ctx, who, ": stride outside [1, 10000]");
+    if (!adv || !ori) return refuse(ctx, who, ": missing pointer (adv, ori)");
+    IFD_ON_CTX_DEVICE(ctx);
+    hipError_t e = launch_knn_clip(adv, ori, normal, budget, n_points, B, stride, static_cast<hipStream_t>(stream));
+    if (e != hipSuccess) return hip_fail(ctx, who, " launch", e);
+    return IFD_OK;
+}
+
+template <class V>
+int knn_attack_impl(ifd_ctx* ctx, const char* who, const ifd_knn_params* params, const float* pc_in, const float* normal,
+                    const int32_t* n_points, const int32_t* fps_start, const int32_t* target, const float* noise, int B, int stride,
+                    float* pc_out, int32_t* pred, int32_t* success, void* stream) {
+    if (int rc = victim_context_ok<V>(ctx, who)) return rc;
+    if (!params || params->struct_size != (int32_t)sizeof(ifd_knn_params)) return refuse(ctx, who, ": params missing or of another struct_size");
+    if (params->num_iter < 1) return refuse(ctx, who, ": num_iter < 1");
+    if (!atk_loss_ok(params->loss_kind)) return refuse(ctx, who, ": unknown loss_kind");
+    if (B < 1) return refuse(ctx, who, ": B >= 1 is needed");
+    // a cloud below 6 points has no five neighbours
+    const int lo = std::max((int)IFD_KNN_MIN_POINTS, victim_min_points<V>(ctx)), hi = std::min((int)IFD_KNN_MAX_POINTS, V::MAX_POINTS);
+    if (stride < lo || stride > hi) return refuse(ctx, who, ": stride outside " + numeric_range(lo, hi));
+    if (!pc_in || !target || !pc_out || !pred || !success) return refuse(ctx, who, ": missing pointer (pc_in, target, pc_out, pred, success)");
+    if (int rc = starts_ok<V>(ctx, who, fps_start)) return rc;
+    const size_t cloud = (size_t)stride * 12, all = (size_t)B * cloud;
+    if (clouds_overlap(pc_in, all, pc_out, all)) return refuse(ctx, who, ": pc_out overlaps pc_in");
+    IFD_ON_CTX_DEVICE(ctx);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const size_t state = carved_bytes([&](Carve& c) { KnnLoop(c, (size_t)B, cloud); });
+    hipError_t e = ctx->ws.grow(loop_ws_bytes<V>(ctx, B, stride, state, true));
+    if (e != hipSuccess) return hip_fail(ctx, who, ": workspace", e, IFD_ERR_NOMEM);
+    GradCall g{pc_out, n_points, fps_start, target, B, stride, params->loss_kind, params->kappa, params->scale, nullptr, s};
+    if (int rc = loop_check<V>(ctx, who, g, lo, stride, 0, "[" + std::to_string(lo) + ", stride]")) return rc;
+    Carve c(ctx->ws.get());                                             // adv is pc_out itself
+    const KnnLoop L(c, (size_t)B, cloud);
+    float *grad = L.grad, *m = L.m, *v = L.v, *logits = L.logits, *loss = L.loss;
+    e = launch_cw_start(pc_in, noise, pc_out, n_points, B, stride, s);
+    if (e == hipSuccess) e = hipMemsetAsync(m, 0, 2 * all, s);         // m and v lie side by side
+    if (e != hipSuccess) return hip_fail(ctx, who, ": start", e);
+    typename V::Out out{};
+    out.loss = loss;
+    g.grad = grad;
+    for (int it = 0; it < params->num_iter; ++it) {
+        if (int rc = victim_grad<V>(ctx, state, g, &out)) return rc;
+        e = launch_knn_step(grad, loss, pc_out, pc_in, normal, m, v, KnnDiag{}, params->chamfer_weight, params->knn_weight, params->alpha,
+                            params->budget, it + 1, params->attack_lr, params->scale, n_points, B, stride, s);
+        if (e != hipSuccess) return hip_fail(ctx, who, ": step", e);
+    }
+    return victim_final_success<V>(ctx, who, pc_out, n_points, fps_start, B, stride, logits, pred, target, success, state, s);
+}
+
+}  // namespace
 
 extern "C" {
 
@@ -2903,71 +3043,22 @@ int ifd_knn_step(ifd_ctx* ctx, const ifd_knn_params* params, const float* grad, 
                  const float* normal, float* m, float* v, int t, float lr, float scale, const ifd_knn_diag* diag, const int32_t* n_points,
                  int B, int stride, void* stream) {
     if (!ctx) return IFD_ERR_ARG;
-    if (int rc = atk_context_ok(ctx, "ifd_knn_step")) return rc;
-    if (!params || params->struct_size != (int32_t)sizeof(ifd_knn_params))
-        return fail(ctx, IFD_ERR_ARG, "ifd_knn_step: params missing or of another struct_size");
-    if (B < 1) return fail(ctx, IFD_ERR_ARG, "ifd_knn_step: B >= 1 is needed");
-    if (stride < IFD_KNN_MIN_POINTS || stride > IFD_KNN_MAX_POINTS) return fail(ctx, IFD_ERR_ARG, "ifd_knn_step: stride outside [6, 2048]");
-    if (!grad || !adv || !ori || !m || !v || t < 1) return fail(ctx, IFD_ERR_ARG, "ifd_knn_step: missing pointer (grad, adv, ori, m, v) or t < 1");
-    IFD_ON_CTX_DEVICE(ctx);
-    const KnnDiag D = diag ? KnnDiag{diag->info, diag->dist_grad, diag->nn_ori, diag->nn5, diag->mask} : KnnDiag{};
-    hipError_t e = launch_knn_step(grad, loss, adv, ori, normal, m, v, D, params->chamfer_weight, params->knn_weight, params->alpha,
-                                   params->budget, t, lr, scale, n_points, B, stride, static_cast<hipStream_t>(stream));
-    if (e != hipSuccess) return fail(ctx, IFD_ERR_HIP, "ifd_knn_step launch", e);
-    return IFD_OK;
+    return knn_step_impl<ClsVictim>(ctx, "ifd_knn_step", params, grad, loss, adv, ori, normal, m, v, t, lr, scale, diag, n_points, B, stride,
+                                    stream);
 }
 
 int ifd_knn_project_clip(ifd_ctx* ctx, float* adv, const float* ori, const float* normal, float budget, const int32_t* n_points, int B,
                          int stride, void* stream) {
     if (!ctx) return IFD_ERR_ARG;
-    if (int rc = atk_context_ok(ctx, "ifd_knn_project_clip")) return rc;
-    if (B < 1) return fail(ctx, IFD_ERR_ARG, "ifd_knn_project_clip: B >= 1 is needed");
-    if (stride < 1 || stride > IFD_CLS_MAX_POINTS) return fail(ctx, IFD_ERR_ARG, "ifd_knn_project_clip: stride outside [1, 10000]");
-    if (!adv || !ori) return fail(ctx, IFD_ERR_ARG, "ifd_knn_project_clip: missing pointer (adv, ori)");
-    IFD_ON_CTX_DEVICE(ctx);
-    hipError_t e = launch_knn_clip(adv, ori, normal, budget, n_points, B, stride, static_cast<hipStream_t>(stream));
-    if (e != hipSuccess) return fail(ctx, IFD_ERR_HIP, "ifd_knn_project_clip launch", e);
-    return IFD_OK;
+    return knn_clip_impl<ClsVictim>(ctx, "ifd_knn_project_clip", adv, ori, normal, budget, n_points, B, stride, stream);
 }
 
 int ifd_knn_attack(ifd_ctx* ctx, const ifd_knn_params* params, const float* pc_in, const float* normal, const int32_t* n_points,
                    const int32_t* target, const float* noise, int B, int stride, float* pc_out, int32_t* pred, int32_t* success,
                    void* stream) {
     if (!ctx) return IFD_ERR_ARG;
-    if (int rc = atk_context_ok(ctx, "ifd_knn_attack")) return rc;
-    if (!params || params->struct_size != (int32_t)sizeof(ifd_knn_params))
-        return fail(ctx, IFD_ERR_ARG, "ifd_knn_attack: params missing or of another struct_size");
-    if (params->num_iter < 1) return fail(ctx, IFD_ERR_ARG, "ifd_knn_attack: num_iter < 1");
-    if (!atk_loss_ok(params->loss_kind)) return fail(ctx, IFD_ERR_ARG, "ifd_knn_attack: unknown loss_kind");
-    if (B < 1) return fail(ctx, IFD_ERR_ARG, "ifd_knn_attack: B >= 1 is needed");
-    if (stride < IFD_KNN_MIN_POINTS || stride > IFD_KNN_MAX_POINTS) return fail(ctx, IFD_ERR_ARG, "ifd_knn_attack: stride outside [6, 2048]");
-    if (!pc_in || !target || !pc_out || !pred || !success)
-        return fail(ctx, IFD_ERR_ARG, "ifd_knn_attack: missing pointer (pc_in, target, pc_out, pred, success)");
-    const size_t cloud = (size_t)stride * 12, all = (size_t)B * cloud;
-    if (clouds_overlap(pc_in, all, pc_out, all)) return fail(ctx, IFD_ERR_ARG, "ifd_knn_attack: pc_out overlaps pc_in");
-    IFD_ON_CTX_DEVICE(ctx);
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    const size_t state = carved_bytes([&](Carve& c) { KnnLoop(c, (size_t)B, cloud); });
-    hipError_t e = ctx->ws.grow(atk_loop_ws_bytes(B, stride, state, true));
-    if (e != hipSuccess) return fail(ctx, IFD_ERR_NOMEM, "ifd_knn_attack: workspace", e);
-    // a cloud below 6 points has no five neighbours
-    if (int rc = atk_check(ctx, "ifd_knn_attack", n_points, target, B, IFD_KNN_MIN_POINTS, stride, "[6, stride]", s)) return rc;
-    Carve c(ctx->ws.get());                                             // adv is pc_out itself
-    const KnnLoop L(c, (size_t)B, cloud);
-    float *grad = L.grad, *m = L.m, *v = L.v, *logits = L.logits, *loss = L.loss;
-    e = launch_cw_start(pc_in, noise, pc_out, n_points, B, stride, s);
-    if (e == hipSuccess) e = hipMemsetAsync(m, 0, 2 * all, s);         // m and v lie side by side
-    if (e != hipSuccess) return fail(ctx, IFD_ERR_HIP, "ifd_knn_attack: start", e);
-    const ifd_atk_out out{nullptr, loss, nullptr, nullptr, nullptr, nullptr};
-    for (int it = 0; it < params->num_iter; ++it) {
-        if (int rc = input_grad_impl(ctx, state, pc_out, n_points, B, stride, target, params->loss_kind, params->kappa, params->scale, grad,
-                                     &out, s))
-            return rc;
-        e = launch_knn_step(grad, loss, pc_out, pc_in, normal, m, v, KnnDiag{}, params->chamfer_weight, params->knn_weight, params->alpha,
-                            params->budget, it + 1, params->attack_lr, params->scale, n_points, B, stride, s);
-        if (e != hipSuccess) return fail(ctx, IFD_ERR_HIP, "ifd_knn_attack: step", e);
-    }
-    return atk_final_success(ctx, "ifd_knn_attack", pc_out, n_points, B, stride, logits, pred, target, success, state, s);
+    return knn_attack_impl<ClsVictim>(ctx, "ifd_knn_attack", params, pc_in, normal, n_points, nullptr, target, noise, B, stride, pc_out, pred,
+                                      success, stream);
 }
 
 }  // extern "C"
@@ -3124,6 +3215,74 @@ int ifd_add_attack(ifd_ctx* ctx, const ifd_add_params* params, const float* pc_i
 // ---- the saliency Drop attack (include/ifd_drop.h) ---------------------------------------------------------------------
 static_assert(IFD_DROP_MAX_POINTS == DROP_MAX_POINTS, "ifd_drop.h and ifd_internal.h");
 
+namespace {
+
+template <class V>
+int drop_step_impl(ifd_ctx* ctx, const char* who, const float* grad, float* pc, int32_t* n_points, int32_t* index, int B, int stride, int k,
+                   float alpha, const ifd_drop_out* out, void* stream) {
+    if (int rc = victim_context_ok<V>(ctx, who)) return rc;
+    if (!grad || !pc || !n_points || B < 1) return refuse(ctx, who, ": bad argument (grad, pc, n_points; B >= 1)");
+    if (stride < 1 || stride > IFD_CLS_MAX_POINTS) return refuse(ctx, who, ": stride outside [1, 10000]");
+    if (k < 1) return refuse(ctx, who, ": k < 1");
+    if (!(alpha > 0.f) || !std::isfinite(alpha)) return refuse(ctx, who, ": alpha must be a finite number above 0");
+    IFD_ON_CTX_DEVICE(ctx);
+    const DropOut D = out ? DropOut{out->saliency, out->center, out->dropped} : DropOut{};
+    hipError_t e = launch_drop_step(grad, pc, n_points, index, B, stride, k, alpha, D, static_cast<hipStream_t>(stream));
+    if (e != hipSuccess) return hip_fail(ctx, who, " launch", e);
+    return IFD_OK;
+}
+
+// keep: the fewest rows that the victim takes, which every cloud must still have when it is written
+template <class V>
+int drop_attack_impl(ifd_ctx* ctx, const char* who, const ifd_drop_params* params, const float* pc_in, const int32_t* n_points,
+                     const int32_t* fps_start, const int32_t* label, int B, int stride, float* pc_out, int32_t* n_out, int32_t* kept,
+                     int32_t* correct, void* stream) {
+    if (int rc = victim_context_ok<V>(ctx, who)) return rc;
+    if (!params || params->struct_size != (int32_t)sizeof(ifd_drop_params)) return refuse(ctx, who, ": params missing or of another struct_size");
+    const int num_drop = params->num_drop;
+    if (num_drop < 1) return refuse(ctx, who, ": num_drop < 1");
+    if (params->k < 1) return refuse(ctx, who, ": k < 1");
+    if (!(params->alpha > 0.f) || !std::isfinite(params->alpha)) return refuse(ctx, who, ": alpha must be a finite number above 0");
+    if (B < 1) return refuse(ctx, who, ": B >= 1 is needed");
+    const int keep = victim_min_points<V>(ctx);
+    if (stride < keep || stride > V::MAX_POINTS) return refuse(ctx, who, ": stride outside " + numeric_range(keep, V::MAX_POINTS));
+    if (!pc_in || !label || !pc_out || !n_out || !correct) return refuse(ctx, who, ": missing pointer (pc_in, label, pc_out, n_out, correct)");
+    if (int rc = starts_ok<V>(ctx, who, fps_start)) return rc;
+    const int hi = std::min(stride, IFD_DROP_MAX_POINTS);
+    const std::string lo_text = "num_drop + " + std::to_string(keep);
+    if (!n_points && (stride - keep < num_drop || stride > IFD_DROP_MAX_POINTS))
+        return refuse(ctx, who, ": without n_points, stride outside [" + lo_text + ", 2048]");
+    if (num_drop > hi - keep)
+        return refuse(ctx, who, keep == 1 ? std::string(": num_drop >= min(stride, 2048), no cloud can lose that many rows")
+                                          : ": " + lo_text + " > min(stride, 2048), no cloud can lose that many rows and keep the victim's fewest");
+    const size_t cloud = (size_t)stride * 12;
+    if (clouds_overlap(pc_in, (size_t)B * cloud, pc_out, (size_t)B * cloud)) return refuse(ctx, who, ": pc_out overlaps pc_in");
+    IFD_ON_CTX_DEVICE(ctx);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const size_t state = carved_bytes([&](Carve& c) { DropLoop(c, (size_t)B, cloud); });
+    hipError_t e = ctx->ws.grow(loop_ws_bytes<V>(ctx, B, stride, state, true));
+    if (e != hipSuccess) return hip_fail(ctx, who, ": workspace", e, IFD_ERR_NOMEM);
+    Carve c(ctx->ws.get());
+    const DropLoop L(c, (size_t)B, cloud);
+    // the gradients read the shrinking counts; the starts stay, so they are checked against the counts that are written
+    GradCall g{pc_out, n_points, fps_start, label, B, stride, IFD_ATK_LOSS_CE, 0.f, params->scale, L.grad, s};
+    if (int rc = loop_check<V>(ctx, who, g, num_drop + keep, hi, num_drop, numeric_range(num_drop + keep, hi))) return rc;
+    g.n_points = n_out;
+    e = hipMemcpyAsync(pc_out, pc_in, (size_t)B * cloud, hipMemcpyDeviceToDevice, s);
+    if (e == hipSuccess) e = launch_drop_begin(n_points, B, stride, n_out, kept, s);
+    if (e != hipSuccess) return hip_fail(ctx, who, ": start", e);
+    // the counts shrink on the device: every launch's grid depends on B and stride only, so nothing here waits for a round
+    const int k = std::min(params->k, num_drop);
+    for (int done = 0; done < num_drop; done += k) {
+        if (int rc = victim_grad<V>(ctx, state, g, nullptr)) return rc;
+        e = launch_drop_step(L.grad, pc_out, n_out, kept, B, stride, std::min(k, num_drop - done), params->alpha, DropOut{}, s);
+        if (e != hipSuccess) return hip_fail(ctx, who, ": step", e);
+    }
+    return victim_final_success<V>(ctx, who, pc_out, n_out, fps_start, B, stride, L.logits, L.pred, label, correct, state, s);
+}
+
+}  // namespace
+
 extern "C" {
 
 int ifd_drop_abi_version(void) { return IFD_DROP_ABI_VERSION; }
@@ -3131,59 +3290,98 @@ int ifd_drop_abi_version(void) { return IFD_DROP_ABI_VERSION; }
 int ifd_drop_step(ifd_ctx* ctx, const float* grad, float* pc, int32_t* n_points, int32_t* index, int B, int stride, int k, float alpha,
                   const ifd_drop_out* out, void* stream) {
     if (!ctx) return IFD_ERR_ARG;
-    if (int rc = atk_context_ok(ctx, "ifd_drop_step")) return rc;
-    if (!grad || !pc || !n_points || B < 1) return fail(ctx, IFD_ERR_ARG, "ifd_drop_step: bad argument (grad, pc, n_points; B >= 1)");
-    if (stride < 1 || stride > IFD_CLS_MAX_POINTS) return fail(ctx, IFD_ERR_ARG, "ifd_drop_step: stride outside [1, 10000]");
-    if (k < 1) return fail(ctx, IFD_ERR_ARG, "ifd_drop_step: k < 1");
-    if (!(alpha > 0.f) || !std::isfinite(alpha)) return fail(ctx, IFD_ERR_ARG, "ifd_drop_step: alpha must be a finite number above 0");
-    IFD_ON_CTX_DEVICE(ctx);
-    const DropOut D = out ? DropOut{out->saliency, out->center, out->dropped} : DropOut{};
-    hipError_t e = launch_drop_step(grad, pc, n_points, index, B, stride, k, alpha, D, static_cast<hipStream_t>(stream));
-    if (e != hipSuccess) return fail(ctx, IFD_ERR_HIP, "ifd_drop_step launch", e);
-    return IFD_OK;
+    return drop_step_impl<ClsVictim>(ctx, "ifd_drop_step", grad, pc, n_points, index, B, stride, k, alpha, out, stream);
 }
 
 int ifd_drop_attack(ifd_ctx* ctx, const ifd_drop_params* params, const float* pc_in, const int32_t* n_points, const int32_t* label,
                     int B, int stride, float* pc_out, int32_t* n_out, int32_t* kept, int32_t* correct, void* stream) {
     if (!ctx) return IFD_ERR_ARG;
-    if (int rc = atk_context_ok(ctx, "ifd_drop_attack")) return rc;
-    if (!params || params->struct_size != (int32_t)sizeof(ifd_drop_params))
-        return fail(ctx, IFD_ERR_ARG, "ifd_drop_attack: params missing or of another struct_size");
-    const int num_drop = params->num_drop;
-    if (num_drop < 1) return fail(ctx, IFD_ERR_ARG, "ifd_drop_attack: num_drop < 1");
-    if (params->k < 1) return fail(ctx, IFD_ERR_ARG, "ifd_drop_attack: k < 1");
-    if (!(params->alpha > 0.f) || !std::isfinite(params->alpha))
-        return fail(ctx, IFD_ERR_ARG, "ifd_drop_attack: alpha must be a finite number above 0");
-    if (B < 1) return fail(ctx, IFD_ERR_ARG, "ifd_drop_attack: B >= 1 is needed");
-    if (stride < 1 || stride > IFD_CLS_MAX_POINTS) return fail(ctx, IFD_ERR_ARG, "ifd_drop_attack: stride outside [1, 10000]");
-    if (!pc_in || !label || !pc_out || !n_out || !correct)
-        return fail(ctx, IFD_ERR_ARG, "ifd_drop_attack: missing pointer (pc_in, label, pc_out, n_out, correct)");
-    const int hi = std::min(stride, IFD_DROP_MAX_POINTS);
-    if (!n_points && (stride <= num_drop || stride > IFD_DROP_MAX_POINTS))
-        return fail(ctx, IFD_ERR_ARG, "ifd_drop_attack: without n_points, stride outside [num_drop + 1, 2048]");
-    if (num_drop >= hi) return fail(ctx, IFD_ERR_ARG, "ifd_drop_attack: num_drop >= min(stride, 2048), no cloud can lose that many rows");
-    const size_t cloud = (size_t)stride * 12;
-    if (clouds_overlap(pc_in, (size_t)B * cloud, pc_out, (size_t)B * cloud)) return fail(ctx, IFD_ERR_ARG, "ifd_drop_attack: pc_out overlaps pc_in");
-    IFD_ON_CTX_DEVICE(ctx);
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    const size_t state = carved_bytes([&](Carve& c) { DropLoop(c, (size_t)B, cloud); });
-    hipError_t e = ctx->ws.grow(atk_loop_ws_bytes(B, stride, state, true));
-    if (e != hipSuccess) return fail(ctx, IFD_ERR_NOMEM, "ifd_drop_attack: workspace", e);
-    if (int rc = atk_check(ctx, "ifd_drop_attack", n_points, label, B, num_drop + 1, hi, numeric_range(num_drop + 1, hi), s)) return rc;
-    Carve c(ctx->ws.get());
-    const DropLoop L(c, (size_t)B, cloud);
-    e = hipMemcpyAsync(pc_out, pc_in, (size_t)B * cloud, hipMemcpyDeviceToDevice, s);
-    if (e == hipSuccess) e = launch_drop_begin(n_points, B, stride, n_out, kept, s);
-    if (e != hipSuccess) return fail(ctx, IFD_ERR_HIP, "ifd_drop_attack: start", e);
-    // the counts shrink on the device: every launch's grid depends on B and stride only, so nothing here waits for a round
-    const int k = std::min(params->k, num_drop);
-    for (int done = 0; done < num_drop; done += k) {
-        if (int rc = input_grad_impl(ctx, state, pc_out, n_out, B, stride, label, IFD_ATK_LOSS_CE, 0.f, params->scale, L.grad, nullptr, s))
-            return rc;
-        e = launch_drop_step(L.grad, pc_out, n_out, kept, B, stride, std::min(k, num_drop - done), params->alpha, DropOut{}, s);
-        if (e != hipSuccess) return fail(ctx, IFD_ERR_HIP, "ifd_drop_attack: step", e);
+    return drop_attack_impl<ClsVictim>(ctx, "ifd_drop_attack", params, pc_in, n_points, nullptr, label, B, stride, pc_out, n_out, kept, correct,
+                                       stream);
+}
+
+}  // extern "C"
+
+// ---- Perturb, kNN and Drop on any victim (include/ifd_victim_atk.h) ------------------------------------------------------
+namespace {
+
+// f(V{}) for the victim V of the context's model
+template <class F>
+int by_victim(ifd_ctx* ctx, const char* who, F f) {
+    if (!ctx) return IFD_ERR_ARG;
+    switch (ctx->model) {
+        case IFD_MODEL_CLS: return f(ClsVictim{});
+        case IFD_MODEL_DGCNN: return f(DgVictim{});
+        case IFD_MODEL_PN2: return f(Pn2Victim{});
+        case IFD_MODEL_PC: return f(PcVictim{});
     }
-    return atk_final_success(ctx, "ifd_drop_attack", pc_out, n_out, B, stride, L.logits, L.pred, label, correct, state, s);
+    return refuse(ctx, who, ": not a victim's context (PointNet, DGCNN, PointNet++, PointConv)");
+}
+
+}  // namespace
+
+extern "C" {
+
+int ifd_victim_atk_abi_version(void) { return IFD_VICTIM_ATK_ABI_VERSION; }
+
+int ifd_victim_cw_step(ifd_ctx* ctx, const ifd_cw_state* state, const float* grad, const int32_t* pred, const float* loss,
+                       const int32_t* target, float* adv, const float* ori, float* last_input, float* info, int t, float lr, float scale,
+                       const int32_t* n_points, int B, int stride, void* stream) {
+    const char* who = "ifd_victim_cw_step";
+    return by_victim(ctx, who, [&](auto v) {
+        return cw_step_impl<decltype(v)>(ctx, who, state, grad, pred, loss, target, adv, ori, last_input, info, t, lr, scale, n_points, B, stride,
+                                         stream);
+    });
+}
+int ifd_victim_cw_adjust(ifd_ctx* ctx, const ifd_cw_state* state, const int32_t* target, const int32_t* n_points, int B, int stride,
+                         void* stream) {
+    const char* who = "ifd_victim_cw_adjust";
+    return by_victim(ctx, who, [&](auto v) { return cw_adjust_impl<decltype(v)>(ctx, who, state, target, n_points, B, stride, stream); });
+}
+int ifd_victim_knn_step(ifd_ctx* ctx, const ifd_knn_params* params, const float* grad, const float* loss, float* adv, const float* ori,
+                        const float* normal, float* m, float* v, int t, float lr, float scale, const ifd_knn_diag* diag,
+                        const int32_t* n_points, int B, int stride, void* stream) {
+    const char* who = "ifd_victim_knn_step";
+    return by_victim(ctx, who, [&](auto vic) {
+        return knn_step_impl<decltype(vic)>(ctx, who, params, grad, loss, adv, ori, normal, m, v, t, lr, scale, diag, n_points, B, stride, stream);
+    });
+}
+int ifd_victim_knn_project_clip(ifd_ctx* ctx, float* adv, const float* ori, const float* normal, float budget, const int32_t* n_points,
+                                int B, int stride, void* stream) {
+    const char* who = "ifd_victim_knn_project_clip";
+    return by_victim(ctx, who, [&](auto v) { return knn_clip_impl<decltype(v)>(ctx, who, adv, ori, normal, budget, n_points, B, stride, stream); });
+}
+int ifd_victim_drop_step(ifd_ctx* ctx, const float* grad, float* pc, int32_t* n_points, int32_t* index, int B, int stride, int k,
+                         float alpha, const ifd_drop_out* out, void* stream) {
+    const char* who = "ifd_victim_drop_step";
+    return by_victim(ctx, who, [&](auto v) { return drop_step_impl<decltype(v)>(ctx, who, grad, pc, n_points, index, B, stride, k, alpha, out, stream); });
+}
+
+int ifd_victim_cw_perturb_attack(ifd_ctx* ctx, const ifd_cw_params* params, const float* pc_in, const int32_t* n_points,
+                                 const int32_t* fps_start, const int32_t* target, const float* noise, int B, int stride, float* pc_out,
+                                 float* best_dist, int32_t* success, double* bounds, void* stream) {
+    const char* who = "ifd_victim_cw_perturb_attack";
+    return by_victim(ctx, who, [&](auto v) {
+        return cw_perturb_impl<decltype(v)>(ctx, who, params, pc_in, n_points, fps_start, target, noise, B, stride, pc_out, best_dist, success,
+                                            bounds, stream);
+    });
+}
+int ifd_victim_knn_attack(ifd_ctx* ctx, const ifd_knn_params* params, const float* pc_in, const float* normal, const int32_t* n_points,
+                          const int32_t* fps_start, const int32_t* target, const float* noise, int B, int stride, float* pc_out,
+                          int32_t* pred, int32_t* success, void* stream) {
+    const char* who = "ifd_victim_knn_attack";
+    return by_victim(ctx, who, [&](auto v) {
+        return knn_attack_impl<decltype(v)>(ctx, who, params, pc_in, normal, n_points, fps_start, target, noise, B, stride, pc_out, pred, success,
+                                            stream);
+    });
+}
+int ifd_victim_drop_attack(ifd_ctx* ctx, const ifd_drop_params* params, const float* pc_in, const int32_t* n_points,
+                           const int32_t* fps_start, const int32_t* label, int B, int stride, float* pc_out, int32_t* n_out,
+                           int32_t* kept, int32_t* correct, void* stream) {
+    const char* who = "ifd_victim_drop_attack";
+    return by_victim(ctx, who, [&](auto v) {
+        return drop_attack_impl<decltype(v)>(ctx, who, params, pc_in, n_points, fps_start, label, B, stride, pc_out, n_out, kept, correct, stream);
+    });
 }
 
 }  // extern "C"

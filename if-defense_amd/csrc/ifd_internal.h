@@ -267,6 +267,10 @@ hipError_t launch_loss_grad(const float* logits, const int32_t* target, int B, i
 hipError_t launch_fgm_update(int kind, const float* grad, float* pc, const float* ori_pc, float* momentum, float step_size, float budget,
                              float mu, const int32_t* n_points, int B, int stride, hipStream_t s);
 hipError_t launch_atk_success(const int32_t* pred, const int32_t* target, int B, int32_t* success, hipStream_t s);
+// the counts and starts of an attack loop on a victim that samples (victim_atk.hip): bad[0] = clouds with n_points (may be null:
+// hi) outside [lo, hi], bad[1] = clouds with fps_start (may be null) outside [0, n - shrink) x [0, np1)
+hipError_t launch_victim_sample_check(const int32_t* n_points, const int32_t* fps_start, int B, int lo, int hi, int shrink, int np1,
+                                      int32_t* bad, hipStream_t s);
 
 // ---- PointNet input gradients (pointnet_grad.hip; C ABI in include/ifd_atk.h) ------------------------------------------
 // The backward pass's own weight image (api.cpp build_cls_grad_image): the FC layers transposed in the MFMA tile layout

@@ -802,21 +802,66 @@ class Classifier:
 
     # the library calls behind input_grad, fgm_update and fgm_attack; a victim with its own (DgcnnClassifier) names them here
     ATK_FNS = {"input_grad": "ifd_cls_input_grad", "fgm_update": "ifd_fgm_update", "fgm_attack": "ifd_fgm_attack"}
+    # and behind the Perturb, kNN and Drop calls: PointNet's own entry points here, include/ifd_victim_atk.h's on the other victims
+    LOOP_FNS = {"cw_step": "ifd_cw_step", "cw_adjust": "ifd_cw_adjust", "cw_perturb_attack": "ifd_cw_perturb_attack",
+                "knn_step": "ifd_knn_step", "knn_project_clip": "ifd_knn_project_clip", "knn_attack": "ifd_knn_attack",
+                "drop_step": "ifd_drop_step", "drop_attack": "ifd_drop_attack"}
+    VICTIM_LOOP_FNS = {"cw_step": "ifd_victim_cw_step", "cw_adjust": "ifd_victim_cw_adjust",
+                      "cw_perturb_attack": "ifd_victim_cw_perturb_attack", "knn_step": "ifd_victim_knn_step",
+                      "knn_project_clip": "ifd_victim_knn_project_clip", "knn_attack": "ifd_victim_knn_attack",
+                      "drop_step": "ifd_victim_drop_step", "drop_attack": "ifd_victim_drop_attack"}
 
-    def _grad_aux(self, B, stride):
-        """-> (the diagnostics of input_grad as a dict of device tensors, the library's struct pointing at them)."""
+    def _fn(self, name):
+        return getattr(self.lib, self.LOOP_FNS[name])
+
+    def _loop_starts(self, fps_start, B):
+        """The fps_start argument of a whole-loop call as a list of device tensors (or None) that the call takes behind n_points:
+        PointNet's own calls have none."""
+        if fps_start is not None:
+            raise IfdError("this victim does not sample: it takes no fps_start")
+        return []
+
+    GRAD_OUT = _lib.IfdAtkOut            # the library's struct of input_grad's diagnostics: a member per name of _grad_spec
+
+    def _grad_spec(self, B, stride):
+        """input_grad's diagnostics: name -> (shape, dtype, fill), or a list of those for an array member; fill None: the library
+        writes every element."""
         f, i = torch.float32, torch.int32
-        aux = {"logits": torch.empty(B, self.N_CLASSES, device=self.device, dtype=f), "loss": torch.empty(B, device=self.device, dtype=f),
-               "pred": torch.empty(B, device=self.device, dtype=i), "win_feat": torch.empty(B, 1024, device=self.device, dtype=i),
-               "win_stn": torch.empty(B, 1024, device=self.device, dtype=i),
-               "global_feat": torch.empty(B, 1024, device=self.device, dtype=f)}
-        return aux, _lib.IfdAtkOut(*[aux[k].data_ptr() for k in ("logits", "loss", "pred", "win_feat", "win_stn", "global_feat")])
+        return {"logits": ((B, self.N_CLASSES), f, None), "loss": ((B,), f, None), "pred": ((B,), i, None),
+                "win_feat": ((B, 1024), i, None), "win_stn": ((B, 1024), i, None), "global_feat": ((B, 1024), f, None)}
+
+    def _make(self, entry):
+        """The device tensor(s) of one entry of a spec."""
+        if isinstance(entry, list):
+            return [self._make(e) for e in entry]
+        shape, dt, fill = entry
+        return torch.empty(shape, device=self.device, dtype=dt) if fill is None else torch.full(shape, fill, device=self.device, dtype=dt)
+
+    def _grad_aux(self, B, stride, names=None):
+        """-> (the diagnostics of input_grad as a dict of device tensors, the library's struct pointing at them).  names: only
+        those are allocated and filled; None: all of them."""
+        spec = self._grad_spec(B, stride)
+        if names is not None:
+            for n in names:
+                if n not in spec:
+                    raise IfdError("unknown diagnostic %r of input_grad (%s)" % (n, " | ".join(spec)))
+            spec = {n: e for n, e in spec.items() if n in names}
+        aux = {n: self._make(e) for n, e in spec.items()}
+        st = self.GRAD_OUT()
+        for name, t in aux.items():
+            if isinstance(t, list):
+                for j, tj in enumerate(t):
+                    getattr(st, name)[j] = tj.data_ptr()
+            else:
+                setattr(st, name, t.data_ptr())
+        return aux, st
 
     def input_grad(self, pc, target, loss="logits", kappa=0., scale=1., n_points=None, want_aux: bool = False):
         """scale * d loss_b / d pc[b] of an adversarial loss on the logits (FGM.get_gradient without its normalisation):
         grad [B,N,3], zeros in the rows beyond a cloud's points.  pc: as ``logits`` takes it, ragged lists included; target [B].
         loss: "logits" (LogitsAdvLoss(kappa)) or "cross_entropy".  With want_aux also {"logits" [B,40], "loss" [B], "pred" [B],
-        "win_feat" / "win_stn" [B,1024] int32 (the point each max-pool channel came from), "global_feat" [B,1024]}."""
+        "win_feat" / "win_stn" [B,1024] int32 (the point each max-pool channel came from), "global_feat" [B,1024]}.  want_aux may
+        also be a tuple of those names, e.g. ("pred", "loss"): then only they are allocated, filled and returned."""
         return self._input_grad(pc, target, loss, kappa, scale, n_points, want_aux)
 
     def _input_grad(self, pc, target, loss, kappa, scale, n_points, want_aux, extra=None):
@@ -832,7 +877,7 @@ class Classifier:
         grad = torch.empty(B, stride, 3, device=self.device, dtype=torch.float32)
         aux, st = None, None
         if want_aux:
-            aux, struct = self._grad_aux(B, stride)
+            aux, struct = self._grad_aux(B, stride, tuple(want_aux) if isinstance(want_aux, (tuple, list)) else None)
             st = C.byref(struct)
         with torch.cuda.device(self.device):
             self._check(getattr(self.lib, self.ATK_FNS["input_grad"])(
@@ -927,7 +972,7 @@ class Classifier:
         info = torch.empty(B, 3, device=self.device, dtype=torch.float32) if want_info else None
         ptr = lambda x: None if x is None else x.data_ptr()        # noqa: E731
         with torch.cuda.device(self.device):
-            self._check(self.lib.ifd_cw_step(self.ctx, C.byref(st), ptrs[0], pred.data_ptr(), ptr(loss), target.data_ptr(), ptrs[1], ptrs[2],
+            self._check(self._fn("cw_step")(self.ctx, C.byref(st), ptrs[0], pred.data_ptr(), ptr(loss), target.data_ptr(), ptrs[1], ptrs[2],
                                              ptrs[3], ptr(info), int(t), float(lr), float(scale), ptr(n_points), B, stride, self._stream()))
         return info
 
@@ -939,12 +984,12 @@ class Classifier:
         target = self._target(target, B)
         n_points = self._counts(n_points, B)
         with torch.cuda.device(self.device):
-            self._check(self.lib.ifd_cw_adjust(self.ctx, C.byref(st), target.data_ptr(), None if n_points is None else n_points.data_ptr(),
+            self._check(self._fn("cw_adjust")(self.ctx, C.byref(st), target.data_ptr(), None if n_points is None else n_points.data_ptr(),
                                                B, stride, self._stream()))
         return state
 
     def cw_perturb_attack(self, pc, target, noise=None, loss="logits", kappa=0., scale=1., attack_lr=1e-2, init_weight=10.,
-                          max_weight=80., binary_step=10, num_iter=500, n_points=None, want_bounds: bool = False):
+                          max_weight=80., binary_step=10, num_iter=500, n_points=None, want_bounds: bool = False, fps_start=None):
         """The whole CW point-perturbation attack on the device (ifd_cw_perturb_attack): -> (adversarial clouds [B,N,3],
         best_dist [B] (1e10 where no iteration reached the target), success [B] bool) and with want_bounds also
         {"weight", "lower", "upper"} [B] float64.  noise: [binary_step,B,N,3], the start noise of every search step, or None."""
@@ -954,6 +999,7 @@ class Classifier:
         if B < 1 or stride < 1:
             raise IfdError("empty batch")
         target = self._target(target, B)
+        starts = self._loop_starts(fps_start, B)
         if noise is not None:
             noise = _f32(torch.as_tensor(noise), self.device)
             if tuple(noise.shape) != (int(binary_step), B, stride, 3):
@@ -965,7 +1011,9 @@ class Classifier:
         P = _lib.IfdCwParams(C.sizeof(_lib.IfdCwParams), loss_kind, int(binary_step), int(num_iter), float(kappa), float(scale),
                              float(attack_lr), float(init_weight), float(max_weight))
         with torch.cuda.device(self.device):
-            self._check(self.lib.ifd_cw_perturb_attack(self.ctx, C.byref(P), pc.data_ptr(), None if n_points is None else n_points.data_ptr(),
+            self._check(self._fn("cw_perturb_attack")(self.ctx, C.byref(P), pc.data_ptr(),
+                                                       None if n_points is None else n_points.data_ptr(),
+                                                       *[None if t is None else t.data_ptr() for t in starts],
                                                        target.data_ptr(), None if noise is None else noise.data_ptr(), B, stride,
                                                        out.data_ptr(), best.data_ptr(), success.data_ptr(),
                                                        None if bounds is None else bounds.data_ptr(), self._stream()))
@@ -1003,7 +1051,7 @@ class Classifier:
         diag = _lib.IfdKnnDiag(*[ptr(out.get(k)) for k in ("info", "dist_grad", "nn_ori", "nn5", "mask")])
         P = self._knn_params(chamfer_weight=chamfer_weight, knn_weight=knn_weight, alpha=alpha, budget=budget)
         with torch.cuda.device(self.device):
-            self._check(self.lib.ifd_knn_step(self.ctx, C.byref(P), ptrs["grad"], ptr(loss), ptrs["adv"], ptrs["ori"], ptrs["normal"],
+            self._check(self._fn("knn_step")(self.ctx, C.byref(P), ptrs["grad"], ptr(loss), ptrs["adv"], ptrs["ori"], ptrs["normal"],
                                               ptrs["m"], ptrs["v"], int(t), float(lr), float(scale), C.byref(diag) if out else None,
                                               ptr(n_points), B, stride, self._stream()))
         return out
@@ -1019,12 +1067,12 @@ class Classifier:
         ptrs = [self._cw_cloud(x, B, stride, name) for name, x in (("adv", adv), ("ori", ori), ("normal", normal))]
         n_points = self._counts(n_points, B)
         with torch.cuda.device(self.device):
-            self._check(self.lib.ifd_knn_project_clip(self.ctx, ptrs[0], ptrs[1], ptrs[2], float(budget),
+            self._check(self._fn("knn_project_clip")(self.ctx, ptrs[0], ptrs[1], ptrs[2], float(budget),
                                                       None if n_points is None else n_points.data_ptr(), B, stride, self._stream()))
         return adv
 
     def knn_attack(self, pc, target, normal=None, noise=None, loss="logits", kappa=15., scale=1., attack_lr=1e-3, num_iter=2500,
-                   n_points=None, chamfer_weight=5., knn_weight=3., alpha=1.05, budget=0.1):
+                   n_points=None, chamfer_weight=5., knn_weight=3., alpha=1.05, budget=0.1, fps_start=None):
         """The whole kNN attack on the device (ifd_knn_attack): -> (adversarial clouds [B,N,3], pred [B] int64, success [B] bool).
         pc [B,N,3]; normal [B,N,3] or None (the clip alone); noise [B,N,3], the start noise, or None."""
         loss_kind = self._loss_kind(loss)
@@ -1033,6 +1081,7 @@ class Classifier:
         if B < 1 or stride < 1:
             raise IfdError("empty batch")
         target = self._target(target, B)
+        starts = self._loop_starts(fps_start, B)
         extra = {}
         for name, x in (("normal", normal), ("noise", noise)):
             if x is not None:
@@ -1046,7 +1095,8 @@ class Classifier:
         P = self._knn_params(loss_kind, num_iter, kappa, scale, attack_lr, chamfer_weight, knn_weight, alpha, budget)
         ptr = lambda x: None if x is None else x.data_ptr()        # noqa: E731
         with torch.cuda.device(self.device):
-            self._check(self.lib.ifd_knn_attack(self.ctx, C.byref(P), pc.data_ptr(), ptr(extra["normal"]), ptr(n_points), target.data_ptr(),
+            self._check(self._fn("knn_attack")(self.ctx, C.byref(P), pc.data_ptr(), ptr(extra["normal"]), ptr(n_points),
+                                            *[ptr(t) for t in starts], target.data_ptr(),
                                                 ptr(extra["noise"]), B, stride, out.data_ptr(), pred.data_ptr(), success.data_ptr(),
                                                 self._stream()))
         return out, pred.long(), success.bool()
@@ -1441,11 +1491,11 @@ class Classifier:
         ptr = lambda x: None if x is None else x.data_ptr()        # noqa: E731
         diag = _lib.IfdDropOut(*[ptr(out.get(n)) for n in ("saliency", "center", "dropped")])
         with torch.cuda.device(self.device):
-            self._check(self.lib.ifd_drop_step(self.ctx, ptrs[0], ptrs[1], n_points.data_ptr(), ptr(index), B, stride, k, float(alpha),
+            self._check(self._fn("drop_step")(self.ctx, ptrs[0], ptrs[1], n_points.data_ptr(), ptr(index), B, stride, k, float(alpha),
                                                C.byref(diag) if out else None, self._stream()))
         return out
 
-    def drop_attack(self, pc, label, num_drop, k=5, alpha=1., scale=1., n_points=None, want_kept: bool = False):
+    def drop_attack(self, pc, label, num_drop, k=5, alpha=1., scale=1., n_points=None, want_kept: bool = False, fps_start=None):
         """The whole Drop attack on the device (ifd_drop_attack): ceil(num_drop / k) rounds of the gradient of scale *
         cross_entropy(logits, label) and ``drop_step``, then a forward.  -> (clouds [B,N - num_drop,3], correct [B] bool: the
         clouds the victim STILL classifies as ``label``) and with want_kept also kept [B,N - num_drop] int32, the surviving rows'
@@ -1455,15 +1505,17 @@ class Classifier:
         if B < 1 or stride < 1:
             raise IfdError("empty batch")
         label = self._target(label, B)
+        starts = self._loop_starts(fps_start, B)
         out = torch.empty_like(pc)
         n_out = torch.empty(B, device=self.device, dtype=torch.int32)
         correct = torch.empty(B, device=self.device, dtype=torch.int32)
         kept = torch.empty(B, stride, device=self.device, dtype=torch.int32) if want_kept else None
         P = _lib.IfdDropParams(C.sizeof(_lib.IfdDropParams), num_drop, int(k), float(alpha), float(scale))
         with torch.cuda.device(self.device):
-            self._check(self.lib.ifd_drop_attack(self.ctx, C.byref(P), pc.data_ptr(), None if n_points is None else n_points.data_ptr(),
-                                                 label.data_ptr(), B, stride, out.data_ptr(), n_out.data_ptr(),
-                                                 None if kept is None else kept.data_ptr(), correct.data_ptr(), self._stream()))
+            self._check(self._fn("drop_attack")(self.ctx, C.byref(P), pc.data_ptr(), None if n_points is None else n_points.data_ptr(),
+                                                *[None if t is None else t.data_ptr() for t in starts], label.data_ptr(), B, stride,
+                                                out.data_ptr(), n_out.data_ptr(), None if kept is None else kept.data_ptr(),
+                                                correct.data_ptr(), self._stream()))
         m = max(stride - num_drop, 0)
         if want_kept:
             return out[:, :m].contiguous(), correct.bool(), kept[:, :m].contiguous()
@@ -1479,11 +1531,14 @@ class DgcnnClassifier(Classifier):
 
     Of the attack entry points, ``input_grad``, ``fgm_update`` and ``fgm_attack`` run on this victim (include/ifd_dgcnn_atk.h),
     with Classifier's signatures and return shapes, so attack.FGM / IFGM / MIFGM / PGD work on it unchanged; the gradient is
-    the one of the network with its neighbour tables held fixed.  The other attack methods are PointNet's, and the library
-    refuses them on a DGCNN context."""
+    the one of the network with its neighbour tables held fixed.  ``cw_state``, ``cw_step``, ``cw_adjust``, ``cw_perturb_attack``,
+    ``knn_step``, ``knn_project_clip``, ``knn_attack``, ``drop_step`` and ``drop_attack`` run on it too (include/ifd_victim_atk.h),
+    so attack.CWPerturb / CWKNN / SaliencyDrop work on it unchanged.  The point-adding attacks (add_*, cluster_*, object_*) are
+    PointNet's, and the library refuses them on a DGCNN context."""
 
     MAX_POINTS = _lib.DGCNN_MAX_POINTS
     ATK_FNS = {"input_grad": "ifd_dgcnn_input_grad", "fgm_update": "ifd_dgcnn_fgm_update", "fgm_attack": "ifd_dgcnn_fgm_attack"}
+    LOOP_FNS = Classifier.VICTIM_LOOP_FNS
     EDGE_WIDTHS = (64, 64, 128, 256)
 
     def __init__(self, weights: np.ndarray, k: int = 20, device=None):
@@ -1504,27 +1559,21 @@ class DgcnnClassifier(Classifier):
                     "global_feat": torch.empty(B, 2048, device=self.device, dtype=torch.float32)}
         return self._forward("ifd_dgcnn_forward", pc, n_points, _lib.IfdDgcnnAux, aux_table, want_aux, want_pred)
 
-    def _grad_aux(self, B, stride):
+    GRAD_OUT = _lib.IfdDgcnnGradOut
+
+    def _loop_starts(self, fps_start, B):
+        return super()._loop_starts(fps_start, B) + [None]             # the ifd_victim_* loops take a (NULL) fps_start
+
+    def _grad_spec(self, B, stride):
         """input_grad's diagnostics on this victim: {"logits" [B,40], "loss" [B], "pred" [B], "idx": four [B,N,k] int32, "feat"
         [B,N,512], "global_feat" [B,2048], "win_pool" [B,1024] int32 (the point of each conv5 max-pool channel), "win_edge": four
         [B,N,Cout] int32 (the neighbour holding each channel's maximum), "act5" [B,N,32] int32 (bit c % 32 of word c // 32: conv5's
         pre-activation of channel c is > 0)}.  Rows beyond a cloud's count: -1 in idx and win_edge, zero in feat and act5."""
-        dev, f, i = self.device, torch.float32, torch.int32
-        aux = {"logits": torch.empty(B, self.N_CLASSES, device=dev, dtype=f), "loss": torch.empty(B, device=dev, dtype=f),
-               "pred": torch.empty(B, device=dev, dtype=i),
-               "idx": [torch.full((B, stride, self.k), -1, device=dev, dtype=i) for _ in range(4)],
-               "feat": torch.zeros(B, stride, 512, device=dev, dtype=f), "global_feat": torch.empty(B, 2048, device=dev, dtype=f),
-               "win_pool": torch.empty(B, 1024, device=dev, dtype=i),
-               "win_edge": [torch.full((B, stride, c), -1, device=dev, dtype=i) for c in self.EDGE_WIDTHS],
-               "act5": torch.zeros(B, stride, 32, device=dev, dtype=i)}
-        st = _lib.IfdDgcnnGradOut()
-        for name, t in aux.items():
-            if isinstance(t, list):
-                for j, tj in enumerate(t):
-                    getattr(st, name)[j] = tj.data_ptr()
-            else:
-                setattr(st, name, t.data_ptr())
-        return aux, st
+        f, i = torch.float32, torch.int32
+        return {"logits": ((B, self.N_CLASSES), f, None), "loss": ((B,), f, None), "pred": ((B,), i, None),
+                "idx": [((B, stride, self.k), i, -1) for _ in range(4)],
+                "feat": ((B, stride, 512), f, 0.), "global_feat": ((B, 2048), f, None), "win_pool": ((B, 1024), i, None),
+                "win_edge": [((B, stride, c), i, -1) for c in self.EDGE_WIDTHS], "act5": ((B, stride, 32), i, 0)}
 
 
 class _SampledVictim(Classifier):
@@ -1541,6 +1590,9 @@ class _SampledVictim(Classifier):
             return (t,)
         return starts
 
+    def _loop_starts(self, fps_start, B):
+        return list(self._starts(fps_start)(B))
+
 
 class PointNet2Classifier(_SampledVictim):
     """The PointNet++ victim of the reference on one GPU (include/ifd_pn2.h): PointNet2ClsSsg(num_classes=40) in eval mode.
@@ -1553,33 +1605,35 @@ class PointNet2Classifier(_SampledVictim):
     Of the attack entry points, ``input_grad``, ``fgm_update`` and ``fgm_attack`` run on this victim (include/ifd_pn2_atk.h),
     with Classifier's signatures and return shapes plus ``fps_start=None``, so attack.FGM / IFGM / MIFGM / PGD work on it
     unchanged; the gradient is the one of the network with its four index tables held fixed, the tables being the forward's on
-    the current cloud.  The other attack methods are PointNet's, and the library refuses them on a PointNet++ context."""
+    the current cloud.  ``cw_state``, ``cw_step``, ``cw_adjust``, ``cw_perturb_attack``, ``knn_step``, ``knn_project_clip``,
+    ``knn_attack``, ``drop_step`` and ``drop_attack`` run on it too (include/ifd_victim_atk.h); the three whole loops take
+    ``fps_start=None`` and use the same starts in every gradient and in the closing forward - for ``drop_attack`` they must be valid
+    for the clouds that are written, fps_start[b][0] < n_points[b] - num_drop.  The point-adding attacks (add_*, cluster_*,
+    object_*) are PointNet's, and the library refuses them on a PointNet++ context."""
 
     MAX_POINTS = _lib.PN2_MAX_POINTS
     ATK_FNS = {"input_grad": "ifd_pn2_input_grad", "fgm_update": "ifd_pn2_fgm_update", "fgm_attack": "ifd_pn2_fgm_attack"}
+    LOOP_FNS = Classifier.VICTIM_LOOP_FNS
 
     def __init__(self, weights: np.ndarray, device=None):
         self.lib = _lib.load()
         self.feature_transform = False
         self._create("ifd_pn2_create", self.lib.ifd_pn2_weight_count(), "pointnet2 weights", weights, device)
 
-    def _grad_aux(self, B, stride):
+    GRAD_OUT = _lib.IfdPn2GradOut
+
+    def _grad_spec(self, B, stride):
         """input_grad's diagnostics on this victim: {"logits" [B,40], "loss" [B], "pred" [B], the tables and features of
         ``logits``' aux, "win1" [B,512,128], "win2" [B,128,256], "win3" [B,1024] int32 (the sample position, resp. row, holding each
         group maximum), "act1" [B,512,32,4], "act2" [B,128,64,8], "act3" [B,128,24] int32 (gate bits of the hidden layers: bit c % 32
         of a layer's word c // 32 is set where its pre-activation of channel c is > 0)}."""
         n1, s1, n2, s2 = _lib.PN2_NPOINT1, _lib.PN2_NSAMPLE1, _lib.PN2_NPOINT2, _lib.PN2_NSAMPLE2
-        i32, f32 = dict(device=self.device, dtype=torch.int32), dict(device=self.device, dtype=torch.float32)
-        aux = dict(logits=torch.empty(B, self.N_CLASSES, **f32), loss=torch.empty(B, **f32), pred=torch.empty(B, **i32),
-                   fps1=torch.empty(B, n1, **i32), fps2=torch.empty(B, n2, **i32), ball1=torch.empty(B, n1, s1, **i32),
-                   ball2=torch.empty(B, n2, s2, **i32), l1_feat=torch.empty(B, n1, 128, **f32), l2_feat=torch.empty(B, n2, 256, **f32),
-                   global_feat=torch.empty(B, 1024, **f32), win1=torch.empty(B, n1, 128, **i32), win2=torch.empty(B, n2, 256, **i32),
-                   win3=torch.empty(B, 1024, **i32), act1=torch.empty(B, n1, s1, 4, **i32), act2=torch.empty(B, n2, s2, 8, **i32),
-                   act3=torch.empty(B, n2, 24, **i32))
-        st = _lib.IfdPn2GradOut()
-        for name, t in aux.items():
-            setattr(st, name, t.data_ptr())
-        return aux, st
+        f, i = torch.float32, torch.int32
+        shapes = dict(logits=((B, self.N_CLASSES), f), loss=((B,), f), pred=((B,), i), fps1=((B, n1), i), fps2=((B, n2), i),
+                      ball1=((B, n1, s1), i), ball2=((B, n2, s2), i), l1_feat=((B, n1, 128), f), l2_feat=((B, n2, 256), f),
+                      global_feat=((B, 1024), f), win1=((B, n1, 128), i), win2=((B, n2, 256), i), win3=((B, 1024), i),
+                      act1=((B, n1, s1, 4), i), act2=((B, n2, s2, 8), i), act3=((B, n2, 24), i))
+        return {n: (shape, dt, None) for n, (shape, dt) in shapes.items()}
 
     def input_grad(self, pc, target, loss="logits", kappa=0., scale=1., n_points=None, want_aux: bool = False, fps_start=None):
         """Classifier.input_grad on this victim (ifd_pn2_input_grad); fps_start as ``logits`` takes it; want_aux: see _grad_aux."""
@@ -1626,42 +1680,46 @@ class PointConvClassifier(_SampledVictim):
     Of the attack entry points, ``input_grad``, ``fgm_update`` and ``fgm_attack`` run on this victim (include/ifd_pc_atk.h),
     with Classifier's signatures and return shapes plus ``fps_start=None``, so attack.FGM / IFGM / MIFGM / PGD work on it
     unchanged; the gradient is the one of the network with its four index tables held fixed, the tables being the forward's on
-    the current cloud.  The other attack methods are PointNet's, and the library refuses them on a PointConv context."""
+    the current cloud.  ``cw_state``, ``cw_step``, ``cw_adjust``, ``cw_perturb_attack``, ``knn_step``, ``knn_project_clip``,
+    ``knn_attack``, ``drop_step`` and ``drop_attack`` run on it too (include/ifd_victim_atk.h); the three whole loops take
+    ``fps_start=None`` and use the same starts in every gradient and in the closing forward - for ``drop_attack`` they must be valid
+    for the clouds that are written, fps_start[b][0] < n_points[b] - num_drop.  The point-adding attacks (add_*, cluster_*,
+    object_*) are PointNet's, and the library refuses them on a PointConv context."""
 
     MAX_POINTS = _lib.PC_MAX_POINTS
     MIN_POINTS = _lib.PC_MIN_POINTS
     CHUNK = _lib.PC_CHUNK
     ATK_FNS = {"input_grad": "ifd_pc_input_grad", "fgm_update": "ifd_pc_fgm_update", "fgm_attack": "ifd_pc_fgm_attack"}
+    LOOP_FNS = Classifier.VICTIM_LOOP_FNS
 
     def __init__(self, weights: np.ndarray, device=None):
         self.lib = _lib.load()
         self.feature_transform = False
         self._create("ifd_pc_create", self.lib.ifd_pc_weight_count(), "pointconv weights", weights, device)
 
-    def _aux_table(self, B, stride):
-        n1, k1, n2, k2 = _lib.PC_NPOINT1, _lib.PC_K1, _lib.PC_NPOINT2, _lib.PC_K2
-        i32, f32 = dict(device=self.device, dtype=torch.int32), dict(device=self.device, dtype=torch.float32)
-        return dict(fps1=torch.empty(B, n1, **i32), fps2=torch.empty(B, n2, **i32), knn1=torch.empty(B, n1, k1, **i32),
-                    knn2=torch.empty(B, n2, k2, **i32), dens1=torch.zeros(B, stride, **f32), dens2=torch.empty(B, n1, **f32),
-                    dens3=torch.empty(B, n2, **f32), l1_feat=torch.empty(B, n1, 128, **f32),
-                    l2_feat=torch.empty(B, n2, 256, **f32), global_feat=torch.empty(B, 1024, **f32))
+    GRAD_OUT = _lib.IfdPcGradOut
 
-    def _grad_aux(self, B, stride):
+    def _aux_spec(self, B, stride):
+        n1, k1, n2, k2 = _lib.PC_NPOINT1, _lib.PC_K1, _lib.PC_NPOINT2, _lib.PC_K2
+        f, i = torch.float32, torch.int32
+        return dict(fps1=((B, n1), i, None), fps2=((B, n2), i, None), knn1=((B, n1, k1), i, None), knn2=((B, n2, k2), i, None),
+                    dens1=((B, stride), f, 0.), dens2=((B, n1), f, None), dens3=((B, n2), f, None), l1_feat=((B, n1, 128), f, None),
+                    l2_feat=((B, n2, 256), f, None), global_feat=((B, 1024), f, None))
+
+    def _aux_table(self, B, stride):
+        return {n: self._make(e) for n, e in self._aux_spec(B, stride).items()}
+
+    def _grad_spec(self, B, stride):
         """input_grad's diagnostics on this victim: {"logits" [B,40], "loss" [B], "pred" [B], the tables, densities and features of
         ``logits``' aux, and the gate bits of the backward pass as int32 words (include/ifd_pc_atk.h): "dgate1" [B,N] (zero beyond a
         cloud's count), "dgate2" [B,512], "dgate3" [B,128] (DensityNet), "wgate1" [B,512,32], "wgate2" [B,128,64], "wgate3" [B,128]
         (WeightNet), "mgate1" [B,512,32,8], "mgate2" [B,128,64,16], "mgate3" [B,128,56] (the MLPs)}."""
         n1, k1, n2, k2 = _lib.PC_NPOINT1, _lib.PC_K1, _lib.PC_NPOINT2, _lib.PC_K2
-        i32, f32 = dict(device=self.device, dtype=torch.int32), dict(device=self.device, dtype=torch.float32)
-        aux = dict(logits=torch.empty(B, self.N_CLASSES, **f32), loss=torch.empty(B, **f32), pred=torch.empty(B, **i32),
-                   **self._aux_table(B, stride),
-                   dgate1=torch.zeros(B, stride, **i32), dgate2=torch.empty(B, n1, **i32), dgate3=torch.empty(B, n2, **i32),
-                   wgate1=torch.empty(B, n1, k1, **i32), wgate2=torch.empty(B, n2, k2, **i32), wgate3=torch.empty(B, n2, **i32),
-                   mgate1=torch.empty(B, n1, k1, 8, **i32), mgate2=torch.empty(B, n2, k2, 16, **i32), mgate3=torch.empty(B, n2, 56, **i32))
-        st = _lib.IfdPcGradOut()
-        for name, t in aux.items():
-            setattr(st, name, t.data_ptr())
-        return aux, st
+        f, i = torch.float32, torch.int32
+        return dict(logits=((B, self.N_CLASSES), f, None), loss=((B,), f, None), pred=((B,), i, None), **self._aux_spec(B, stride),
+                    dgate1=((B, stride), i, 0), dgate2=((B, n1), i, None), dgate3=((B, n2), i, None),
+                    wgate1=((B, n1, k1), i, None), wgate2=((B, n2, k2), i, None), wgate3=((B, n2), i, None),
+                    mgate1=((B, n1, k1, 8), i, None), mgate2=((B, n2, k2, 16), i, None), mgate3=((B, n2, 56), i, None))
 
     def input_grad(self, pc, target, loss="logits", kappa=0., scale=1., n_points=None, want_aux: bool = False, fps_start=None):
         """Classifier.input_grad on this victim (ifd_pc_input_grad); fps_start as ``logits`` takes it; want_aux: see _grad_aux."""
