@@ -22,8 +22,6 @@ from __future__ import annotations
 import os
 import sys
 
-import numpy as np
-
 from . import attack_cli as C
 
 
@@ -59,24 +57,14 @@ def main(argv=None, make_classifier=None) -> int:
     if not 1 <= args.num_add <= 1024 or not args.num_add <= args.num_points <= 2048:
         print("add_attack: 1 <= --num_add <= 1024 and --num_add <= --num_points <= 2048 are needed", file=sys.stderr)
         return 2
-    print(args)
-    npz = np.load(args.data_root)
-    data = C.load_points(npz, args.num_points)
-    label, target = C.load_labels(npz)
-    classifier = C.open_classifier(args, make_classifier)
-    try:
-        init_w, upper_w = WEIGHTS[args.dist_func]
-        attacker = CWAdd(classifier, args.adv_func, args.dist_func, attack_lr=args.attack_lr, init_weight=init_w, max_weight=upper_w,
-                         binary_step=args.binary_step, num_iter=args.num_iter, num_add=args.num_add, kappa=args.kappa, seed=args.seed,
-                         verbose=args.verbose)
-        adv, num = C.run_batches(attacker, data, target, args.batch_size)
-    finally:
-        C.close_classifier(classifier)
-    rate = float(num) / float(len(data))
-    d, name = save_path(args.out_dir, args.dataset, args.num_points, args.dist_func, args.model, args.adv_func, args.kappa, rate,
-                        0 if args.local_rank < 0 else args.local_rank)
-    C.save_npz(d, name, adv, label, target)
-    return 0
+    init_w, upper_w = WEIGHTS[args.dist_func]
+    return C.run_attack(
+        args, make_classifier,
+        lambda classifier: CWAdd(classifier, args.adv_func, args.dist_func, attack_lr=args.attack_lr, init_weight=init_w, max_weight=upper_w,
+                                 binary_step=args.binary_step, num_iter=args.num_iter, num_add=args.num_add, kappa=args.kappa,
+                                 seed=args.seed, verbose=args.verbose),
+        lambda rate, rank: save_path(args.out_dir, args.dataset, args.num_points, args.dist_func, args.model, args.adv_func, args.kappa,
+                                     rate, rank))
 
 
 if __name__ == '__main__':

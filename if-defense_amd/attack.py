@@ -69,6 +69,28 @@ class _Attack:
         print(fmt.format(success_num, B))
         return success_num
 
+    def _search(self, tgt, state, last, want_aux, start, step):
+        """The Carlini-Wagner search from the host, shared by CWPerturb and the adding attacks: ``binary_step`` search steps of
+        ``num_iter`` iterations - one ``input_grad`` (with ``want_aux``) and one step call each, the reference's lines every
+        num_iter // 5 iterations - and ``cw_adjust`` behind each.  start(search_step) -> the cloud the victim sees in that step;
+        step(cloud, grad, aux, t, last_input, want_info) -> the step call's info or None, last_input being ``last`` in the very last
+        iteration.  -> (o_bestattack, or ``last`` where the search never succeeded; o_bestdist; success)."""
+        net = self.model
+        B = int(tgt.shape[0])
+        every = max(self.num_iter // 5, 1)
+        for s in range(self.binary_step):
+            cloud = start(s)
+            info = None
+            for it in range(self.num_iter):
+                grad, aux = net.input_grad(cloud, tgt, self.adv_func, self.kappa, self._scale(B), want_aux=want_aux)
+                if it % every == 0:
+                    self._progress(self.STEP_LINES, s, it, aux["pred"], tgt, info, 1)
+                final = s == self.binary_step - 1 and it == self.num_iter - 1
+                info = step(cloud, grad, aux, it + 1, last if final else None, it % every == every - 1)
+            net.cw_adjust(state, tgt)
+        ok = state["lower"] > 0
+        return torch.where(ok[:, None, None], state["o_bestattack"], last), state["o_bestdist"], ok
+
 
 class FGM(_Attack):
     KIND = "fgm"
@@ -183,22 +205,11 @@ class CWPerturb(_Attack):
         ori = data.to(dev).contiguous()
         tgt = target.to(dev)
         state = net.cw_state(B, K, self.init_weight, self.max_weight)
-        last = torch.empty_like(ori)
-        every = max(self.num_iter // 5, 1)
-        for step in range(self.binary_step):
-            adv = ori + noise[step].to(dev)
-            info = None
-            for it in range(self.num_iter):
-                grad, aux = net.input_grad(adv, tgt, self.adv_func, self.kappa, self._scale(B), want_aux=("pred", "loss"))
-                if it % every == 0:
-                    self._progress(self.STEP_LINES, step, it, aux["pred"], tgt, info, 1)
-                final = step == self.binary_step - 1 and it == self.num_iter - 1
-                info = net.cw_step(state, grad, aux["pred"], tgt, adv, ori, it + 1, self.attack_lr, self._scale(B), loss=aux["loss"],
-                                   last_input=last if final else None, want_info=it % every == every - 1)
-            net.cw_adjust(state, tgt)
-        ok = state["lower"] > 0
-        out = torch.where(ok[:, None, None], state["o_bestattack"], last)
-        return out, state["o_bestdist"], ok
+
+        def step(adv, grad, aux, t, last_input, want_info):
+            return net.cw_step(state, grad, aux["pred"], tgt, adv, ori, t, self.attack_lr, self._scale(B), loss=aux["loss"],
+                               last_input=last_input, want_info=want_info)
+        return self._search(tgt, state, torch.empty_like(ori), ("pred", "loss"), lambda s: ori + noise[s].to(dev), step)
 
     def attack(self, data, target):
         data, target = self._tensors(data, target)
@@ -286,7 +297,34 @@ class CWKNN(_Attack):
         return adv.cpu().numpy(), self._finish(ok, B)
 
 
-class CWAdd(_Attack):
+class _CWAdding(_Attack):
+    """What CWAdd, CWAddClusters and CWAddObjects share: the checks and the end of ``attack`` and, around their own step calls, the
+    host-driven loop.  A subclass has ``_run(data, target)`` -> (clouds, o_bestdist, success), on either loop form."""
+
+    NUM_CRI, EPS, MIN_SAMPLES = 128, 0.2, 3        # clusters and objects start from DBSCAN on 128 critical points
+    FEWEST = "128"                                 # the fewest points of a cloud, as the refusal names them
+
+    def _fewest(self):
+        return self.NUM_CRI
+
+    def _host_loop(self, ori, tgt, state, cat, start, step):
+        """``_search`` on ``cat``, the originals ``ori`` with the added rows behind them -> (ori with the rows the search ends on,
+        o_bestdist, success)."""
+        last = torch.empty(int(cat.shape[0]), int(cat.shape[1]) - int(ori.shape[1]), 3, device=cat.device, dtype=torch.float32)
+        added, dist, ok = self._search(tgt, state, last, True, start, step)
+        return torch.cat([ori, added], dim=1), dist, ok
+
+    def attack(self, data, target):
+        data, target = self._tensors(data, target)
+        if data.dim() != 3 or int(data.shape[2]) != 3:
+            raise ValueError("data must be [B,K,3]")
+        if not self._fewest() <= int(data.shape[1]) <= 2048:
+            raise ValueError("clouds must have between %s and 2048 points" % self.FEWEST)
+        adv, dist, ok = self._run(data, target)
+        return dist.cpu().numpy().astype(np.float64), adv.cpu().numpy(), self._finish(ok, int(data.shape[0]))
+
+
+class CWAdd(_CWAdding):
     """CW attack by adding points (Add.py CWAdd): ``num_add`` points start on the cloud's critical points - the rows with the largest
     gradient of cross_entropy(logits, target) - and are optimised by ``binary_step`` search steps on the weight of the set distance,
     ``num_iter`` Adam iterations each, while the victim sees the original cloud with the added points behind it.  ``model`` is a
@@ -318,6 +356,11 @@ class CWAdd(_Attack):
         self.binary_step, self.num_iter, self.num_add = int(binary_step), int(num_iter), int(num_add)
         self._common(seed, ref_batch, verbose)
 
+    FEWEST = "num_add"                             # the critical points are rows of the cloud
+
+    def _fewest(self):
+        return self.num_add
+
     def noise(self, data: torch.Tensor) -> torch.Tensor:
         """[binary_step,B,num_add,3]: the start noise, one draw per search step."""
         shape = (int(data.shape[0]), self.num_add, 3)
@@ -333,38 +376,23 @@ class CWAdd(_Attack):
         cri = net.add_critical_points(ori, tgt, A, self._scale(B))
         state = net.cw_state(B, A, self.init_weight, self.max_weight)
         cat = torch.cat([ori, cri], dim=1).contiguous()
-        last = torch.empty_like(cri)
-        every = max(self.num_iter // 5, 1)
-        for step in range(self.binary_step):
-            cat[:, K:] = cri + noise[step].to(dev)
-            info = None
-            for it in range(self.num_iter):
-                grad, aux = net.input_grad(cat, tgt, self.adv_func, self.kappa, self._scale(B), want_aux=True)
-                if it % every == 0:
-                    self._progress(self.STEP_LINES, step, it, aux["pred"], tgt, info, 1)
-                final = step == self.binary_step - 1 and it == self.num_iter - 1
-                info = net.add_step(self.dist_func, state, grad, aux["pred"], tgt, cat, A, it + 1, self.attack_lr, self._scale(B),
-                                    loss=aux["loss"], last_input=last if final else None, want_info=it % every == every - 1).get("info")
-            net.cw_adjust(state, tgt)
-        ok = state["lower"] > 0
-        added = torch.where(ok[:, None, None], state["o_bestattack"], last)
-        return torch.cat([ori, added], dim=1), state["o_bestdist"], ok
 
-    def attack(self, data, target):
-        data, target = self._tensors(data, target)
-        if data.dim() != 3 or int(data.shape[2]) != 3:
-            raise ValueError("data must be [B,K,3]")
-        if not self.num_add <= int(data.shape[1]) <= 2048:
-            raise ValueError("clouds must have between num_add and 2048 points")
-        B = int(data.shape[0])
+        def start(s):
+            cat[:, K:] = cri + noise[s].to(dev)
+            return cat
+
+        def step(cat, grad, aux, t, last_input, want_info):
+            return net.add_step(self.dist_func, state, grad, aux["pred"], tgt, cat, A, t, self.attack_lr, self._scale(B), loss=aux["loss"],
+                                last_input=last_input, want_info=want_info).get("info")
+        return self._host_loop(ori, tgt, state, cat, start, step)
+
+    def _run(self, data, target):
         noise = self.noise(data)
         if self.verbose:
-            adv, dist, ok = self._loop(data, target, noise)
-        else:
-            adv, dist, ok = self.model.add_attack(self.dist_func, data, target, self.num_add, noise, self.adv_func, self.kappa,
-                                                  self._scale(B), self.attack_lr, self.init_weight, self.max_weight, self.binary_step,
-                                                  self.num_iter)
-        return dist.cpu().numpy().astype(np.float64), adv.cpu().numpy(), self._finish(ok, B)
+            return self._loop(data, target, noise)
+        return self.model.add_attack(self.dist_func, data, target, self.num_add, noise, self.adv_func, self.kappa,
+                                     self._scale(int(data.shape[0])), self.attack_lr, self.init_weight, self.max_weight, self.binary_step,
+                                     self.num_iter)
 
 
 def init_clusters(points, labels, num_add, cl_num_p, rng):
@@ -392,7 +420,7 @@ def init_clusters(points, labels, num_add, cl_num_p, rng):
     return np.array(out)
 
 
-class CWAddClusters(_Attack):
+class CWAddClusters(_CWAdding):
     """CW attack by adding clusters (Add_Cluster.py CWAddClusters with FarChamferDist(num_add, 'adv2ori', 0.1)): ``num_add`` clusters
     of ``cl_num_p`` points are optimised by ``binary_step`` search steps on the weight of the distance - the farthest pair inside
     every cluster plus 0.1 x Chamfer - ``num_iter`` Adam iterations each, while the victim sees the original cloud with the clusters
@@ -417,8 +445,6 @@ class CWAddClusters(_Attack):
     Every search step starts from clusters + randn * 1e-7, drawn here once per search step from a seeded HOST torch.Generator:
     agreement with a reference run in distribution only.  ``ref_batch``: the batch the reference's losses are a mean over (scale =
     1 / ref_batch); the default is the batch passed to ``attack``."""
-
-    NUM_CRI, EPS, MIN_SAMPLES = 128, 0.2, 3
 
     def __init__(self, model, adv_func="logits", dist_func="far_chamfer", attack_lr=1e-2, init_weight=5., max_weight=30., binary_step=5,
                  num_iter=500, num_add=3, cl_num_p=32, kappa=0., seed=1, ref_batch=None, verbose=True):
@@ -453,46 +479,30 @@ class CWAddClusters(_Attack):
         """Add_Cluster.py:165-278 from the host: the kernels of ifd_cluster_attack on the same numbers."""
         net = self.model
         dev = net.device
-        B, K, A = int(data.shape[0]), int(data.shape[1]), self.num_add * self.cl_num_p
+        B, K = int(data.shape[0]), int(data.shape[1])
         ori = data.to(dev).contiguous()
         tgt = target.to(dev)
         start = clusters.to(dev)
-        state = net.cw_state(B, A, self.init_weight, self.max_weight)
+        state = net.cw_state(B, self.num_add * self.cl_num_p, self.init_weight, self.max_weight)
         cat = torch.cat([ori, start], dim=1).contiguous()
-        last = torch.empty_like(start)
-        every = max(self.num_iter // 5, 1)
-        for step in range(self.binary_step):
-            cat[:, K:] = start + noise[step].to(dev)
-            info = None
-            for it in range(self.num_iter):
-                grad, aux = net.input_grad(cat, tgt, self.adv_func, self.kappa, self._scale(B), want_aux=True)
-                if it % every == 0:
-                    self._progress(self.STEP_LINES, step, it, aux["pred"], tgt, info, 1)
-                final = step == self.binary_step - 1 and it == self.num_iter - 1
-                info = net.cluster_step(state, grad, aux["pred"], tgt, cat, self.num_add, self.cl_num_p, it + 1, self.attack_lr,
-                                        self._scale(B), loss=aux["loss"], last_input=last if final else None,
-                                        want_info=it % every == every - 1).get("info")
-            net.cw_adjust(state, tgt)
-        ok = state["lower"] > 0
-        added = torch.where(ok[:, None, None], state["o_bestattack"], last)
-        return torch.cat([ori, added], dim=1), state["o_bestdist"], ok
 
-    def attack(self, data, target):
-        data, target = self._tensors(data, target)
-        if data.dim() != 3 or int(data.shape[2]) != 3:
-            raise ValueError("data must be [B,K,3]")
-        if not self.NUM_CRI <= int(data.shape[1]) <= 2048:
-            raise ValueError("clouds must have between 128 and 2048 points")
-        B = int(data.shape[0])
+        def begin(s):
+            cat[:, K:] = start + noise[s].to(dev)
+            return cat
+
+        def step(cat, grad, aux, t, last_input, want_info):
+            return net.cluster_step(state, grad, aux["pred"], tgt, cat, self.num_add, self.cl_num_p, t, self.attack_lr, self._scale(B),
+                                    loss=aux["loss"], last_input=last_input, want_info=want_info).get("info")
+        return self._host_loop(ori, tgt, state, cat, begin, step)
+
+    def _run(self, data, target):
         clusters = self._init_centers(data, target)
         noise = self.noise(data)
         if self.verbose:
-            adv, dist, ok = self._loop(data, target, clusters, noise)
-        else:
-            adv, dist, ok = self.model.cluster_attack(data, target, clusters, self.num_add, self.cl_num_p, noise, self.adv_func,
-                                                      self.kappa, self._scale(B), self.attack_lr, self.init_weight, self.max_weight,
-                                                      self.binary_step, self.num_iter)
-        return dist.cpu().numpy().astype(np.float64), adv.cpu().numpy(), self._finish(ok, B)
+            return self._loop(data, target, clusters, noise)
+        return self.model.cluster_attack(data, target, clusters, self.num_add, self.cl_num_p, noise, self.adv_func, self.kappa,
+                                         self._scale(int(data.shape[0])), self.attack_lr, self.init_weight, self.max_weight,
+                                         self.binary_step, self.num_iter)
 
 
 def prepare_objects(object_pc, scaling, num_add, obj_num_p, rng):
@@ -542,7 +552,7 @@ def init_centers(points, labels, num_add, rng):
     return np.array(out)
 
 
-class CWAddObjects(_Attack):
+class CWAddObjects(_CWAdding):
     """CW attack by adding objects (Add_Objects.py CWAddObjects with L2ChamferDist(num_add, 'adv2ori', 0.2)): ``num_add`` copies of
     ``obj_num_p`` points of one object are placed into the cloud by a rotation about the y axis and a shift each; the object-frame
     points, the shifts and the angles are optimised by ``binary_step`` search steps on the weight of the distance - the L2 norm of
@@ -571,8 +581,6 @@ class CWAddObjects(_Attack):
     per object and rotates by the first alone; the other two never move and reach no output, so one angle per object is kept.
     ``ref_batch``: the batch the reference's losses are a mean over (scale = 1 / ref_batch); the default is the batch passed to
     ``attack``."""
-
-    NUM_CRI, EPS, MIN_SAMPLES = 128, 0.2, 3
 
     def __init__(self, model, object_pc, adv_func="logits", dist_func="l2_chamfer", attack_lr=1e-2, init_weight=5., max_weight=40.,
                  binary_step=5, num_iter=500, num_add=3, obj_num_p=64, scaling=0.3, kappa=0., seed=1, ref_batch=None, verbose=True):
@@ -621,46 +629,30 @@ class CWAddObjects(_Attack):
         objects, centers = objects.to(dev), centers.to(dev)
         state = net.object_state(B, na, P, self.init_weight, self.max_weight)
         cat = torch.cat([ori, torch.zeros(B, A, 3, device=dev)], dim=1).contiguous()
-        last = torch.empty(B, A, 3, device=dev)
-        every = max(self.num_iter // 5, 1)
-        for step in range(self.binary_step):
-            state["obj"].copy_(objects.reshape(1, A, 3) + noise_obj[step].to(dev))
-            state["shift"].copy_(centers + noise_shift[step].to(dev))
-            state["angle"].copy_(angles0[step].to(dev))
+
+        def start(s):
+            state["obj"].copy_(objects.reshape(1, A, 3) + noise_obj[s].to(dev))
+            state["shift"].copy_(centers + noise_shift[s].to(dev))
+            state["angle"].copy_(angles0[s].to(dev))
             for key in ("shift_m", "shift_v", "angle_m", "angle_v"):
                 state[key].zero_()
             net.object_place(state["obj"], state["angle"], state["shift"], cat, na, P)
-            info = None
-            for it in range(self.num_iter):
-                grad, aux = net.input_grad(cat, tgt, self.adv_func, self.kappa, self._scale(B), want_aux=True)
-                if it % every == 0:
-                    self._progress(self.STEP_LINES, step, it, aux["pred"], tgt, info, 1)
-                final = step == self.binary_step - 1 and it == self.num_iter - 1
-                info = net.object_step(state, objects, grad, aux["pred"], tgt, cat, na, P, it + 1, self.attack_lr, self._scale(B),
-                                       loss=aux["loss"], last_input=last if final else None,
-                                       want_info=it % every == every - 1).get("info")
-            net.cw_adjust(state, tgt)
-        ok = state["lower"] > 0
-        added = torch.where(ok[:, None, None], state["o_bestattack"], last)
-        return torch.cat([ori, added], dim=1), state["o_bestdist"], ok
+            return cat
 
-    def attack(self, data, target):
-        data, target = self._tensors(data, target)
-        if data.dim() != 3 or int(data.shape[2]) != 3:
-            raise ValueError("data must be [B,K,3]")
-        if not self.NUM_CRI <= int(data.shape[1]) <= 2048:
-            raise ValueError("clouds must have between 128 and 2048 points")
-        B = int(data.shape[0])
+        def step(cat, grad, aux, t, last_input, want_info):
+            return net.object_step(state, objects, grad, aux["pred"], tgt, cat, na, P, t, self.attack_lr, self._scale(B), loss=aux["loss"],
+                                   last_input=last_input, want_info=want_info).get("info")
+        return self._host_loop(ori, tgt, state, cat, start, step)
+
+    def _run(self, data, target):
         objects = torch.from_numpy(self.object_pc).float()
         centers = self._init_centers(data, target)
         noise_obj, noise_shift, angles0 = self.draws(data)
         if self.verbose:
-            adv, dist, ok = self._loop(data, target, objects, centers, noise_obj, noise_shift, angles0)
-        else:
-            adv, dist, ok = self.model.object_attack(data, target, objects, centers, angles0, noise_obj, noise_shift, self.adv_func,
-                                                     self.kappa, self._scale(B), self.attack_lr, self.init_weight, self.max_weight,
-                                                     self.binary_step, self.num_iter)
-        return dist.cpu().numpy().astype(np.float64), adv.cpu().numpy(), self._finish(ok, B)
+            return self._loop(data, target, objects, centers, noise_obj, noise_shift, angles0)
+        return self.model.object_attack(data, target, objects, centers, angles0, noise_obj, noise_shift, self.adv_func, self.kappa,
+                                        self._scale(int(data.shape[0])), self.attack_lr, self.init_weight, self.max_weight,
+                                        self.binary_step, self.num_iter)
 
 
 class SaliencyDrop(_Attack):

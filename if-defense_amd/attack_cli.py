@@ -98,3 +98,24 @@ def run_batches(attacker, data, target, batch_size, on_batch=None):
 def save_npz(d, name, adv, label, target):
     os.makedirs(d, exist_ok=True)
     np.savez(os.path.join(d, name), test_pc=adv.astype(np.float32), test_label=label.astype(np.uint8), target_label=target.astype(np.uint8))
+
+
+def run_attack(args, make_classifier, make_attacker, name_file) -> int:
+    """A script's main behind its own refusals (add_attack, cluster_attack, object_attack): print(args), the data, the victim, the
+    batches, the result file.  make_attacker(classifier) -> the attacker, or None behind a message of its own (status 2);
+    name_file(success_rate, rank) -> (directory, file name)."""
+    print(args)
+    npz = np.load(args.data_root)
+    data = load_points(npz, args.num_points)
+    label, target = load_labels(npz)
+    classifier = open_classifier(args, make_classifier)
+    try:
+        attacker = make_attacker(classifier)
+        if attacker is None:
+            return 2
+        adv, num = run_batches(attacker, data, target, args.batch_size)
+    finally:
+        close_classifier(classifier)
+    d, name = name_file(float(num) / float(len(data)), 0 if args.local_rank < 0 else args.local_rank)
+    save_npz(d, name, adv, label, target)
+    return 0

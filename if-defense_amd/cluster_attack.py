@@ -23,8 +23,6 @@ from __future__ import annotations
 import os
 import sys
 
-import numpy as np
-
 from . import attack_cli as C
 
 
@@ -63,23 +61,13 @@ def main(argv=None, make_classifier=None) -> int:
     if not 128 <= args.num_points <= 2048:
         print("cluster_attack: 128 <= --num_points <= 2048 is needed", file=sys.stderr)
         return 2
-    print(args)
-    npz = np.load(args.data_root)
-    data = C.load_points(npz, args.num_points)
-    label, target = C.load_labels(npz)
-    classifier = C.open_classifier(args, make_classifier)
-    try:
-        attacker = CWAddClusters(classifier, args.adv_func, "far_chamfer", attack_lr=args.attack_lr, init_weight=INIT_WEIGHT,
-                                 max_weight=MAX_WEIGHT, binary_step=args.binary_step, num_iter=args.num_iter, num_add=args.num_add,
-                                 cl_num_p=args.cl_num_p, kappa=args.kappa, seed=args.seed, verbose=args.verbose)
-        adv, num = C.run_batches(attacker, data, target, args.batch_size)
-    finally:
-        C.close_classifier(classifier)
-    rate = float(num) / float(len(data))
-    d, name = save_path(args.out_dir, args.dataset, args.num_points, args.num_add, args.cl_num_p, args.model, args.adv_func, args.kappa,
-                        rate, 0 if args.local_rank < 0 else args.local_rank)
-    C.save_npz(d, name, adv, label, target)
-    return 0
+    return C.run_attack(
+        args, make_classifier,
+        lambda classifier: CWAddClusters(classifier, args.adv_func, "far_chamfer", attack_lr=args.attack_lr, init_weight=INIT_WEIGHT,
+                                         max_weight=MAX_WEIGHT, binary_step=args.binary_step, num_iter=args.num_iter, num_add=args.num_add,
+                                         cl_num_p=args.cl_num_p, kappa=args.kappa, seed=args.seed, verbose=args.verbose),
+        lambda rate, rank: save_path(args.out_dir, args.dataset, args.num_points, args.num_add, args.cl_num_p, args.model, args.adv_func,
+                                     args.kappa, rate, rank))
 
 
 if __name__ == '__main__':

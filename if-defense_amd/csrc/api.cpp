@@ -2349,37 +2349,21 @@ struct KnnLoop {
         c.round_up(256);
     }
 };
-struct AddLoop {                          // G: points of the larger of the input and the output cloud
-    CwFront f; int32_t *n_cat, *n_ori; float *grad, *cri, *last;
-    AddLoop(Carve& c, size_t B, size_t G, size_t num_add) : f(c, B) {
-        const size_t added = B * num_add * 12;
+// The state of the three point-adding loops (Add, Add-Cluster, Add-Objects), one layout: G points of the larger of the input and
+// the output cloud, A added rows a cloud; cri_rows: Add's critical points, pose_rows: Objects' poses (shift, angle and their moments)
+// behind its object rows - 0 in the other loops, where those blocks take no bytes (Carve::take adds no padding).
+struct AddingLoop {
+    ObjectState S{};                      // S.cw: every loop's search state; the rest: Objects' alone
+    int32_t *pred, *n_cat, *n_ori; float *loss, *grad, *cri, *last;
+    AddingLoop(Carve& c, size_t B, size_t G, size_t A, size_t cri_rows, size_t pose_rows) {
+        const CwFront f(c, B);
+        const size_t added = B * A * 12, pose = B * pose_rows * 4;
+        S.cw = f.S; pred = f.pred; loss = f.loss;
         n_cat = c.take<int32_t>(B * 4); n_ori = c.take<int32_t>(B * 4);
-        grad = c.take<float>(B * G * 12); cri = c.take<float>(added);
-        f.S.m = c.take<float>(added); f.S.v = c.take<float>(added); f.S.o_bestattack = c.take<float>(added);   // side by side
+        grad = c.take<float>(B * G * 12); cri = c.take<float>(B * cri_rows * 12);
+        S.cw.m = c.take<float>(added); S.cw.v = c.take<float>(added); S.cw.o_bestattack = c.take<float>(added);   // side by side
         last = c.take<float>(added);
-        c.round_up(256);
-    }
-};
-struct ClusterLoop {                      // AddLoop without the critical points: the start clusters are the caller's
-    CwFront f; int32_t *n_cat, *n_ori; float *grad, *last;
-    ClusterLoop(Carve& c, size_t B, size_t G, size_t A) : f(c, B) {
-        const size_t added = B * A * 12;
-        n_cat = c.take<int32_t>(B * 4); n_ori = c.take<int32_t>(B * 4);
-        grad = c.take<float>(B * G * 12);
-        f.S.m = c.take<float>(added); f.S.v = c.take<float>(added); f.S.o_bestattack = c.take<float>(added);   // side by side
-        last = c.take<float>(added);
-        c.round_up(256);
-    }
-};
-struct ObjectLoop {                       // ClusterLoop + the object rows and the pose (shift, angle and their moments)
-    CwFront f; int32_t *n_cat, *n_ori; float *grad, *last; ObjectState S{};
-    ObjectLoop(Carve& c, size_t B, size_t G, size_t A, size_t num_add) : f(c, B) {
-        const size_t added = B * A * 12, pose = B * num_add * 4;
-        n_cat = c.take<int32_t>(B * 4); n_ori = c.take<int32_t>(B * 4);
-        grad = c.take<float>(B * G * 12);
-        f.S.m = c.take<float>(added); f.S.v = c.take<float>(added); f.S.o_bestattack = c.take<float>(added);   // side by side
-        last = c.take<float>(added);
-        S.obj = c.take<float>(added);
+        S.obj = c.take<float>(pose_rows ? added : 0);
         S.shift = c.take<float>(3 * pose); S.angle = c.take<float>(pose);
         S.shift_m = c.take<float>(3 * pose); S.shift_v = c.take<float>(3 * pose);
         S.angle_m = c.take<float>(pose); S.angle_v = c.take<float>(pose);
@@ -2579,7 +2563,6 @@ int victim_context_ok(ifd_ctx* ctx, const char* who) {
     if (!has_grad) return refuse(ctx, who, ": input gradients are not built for a model with feature_transform");
     return IFD_OK;
 }
-int atk_context_ok(ifd_ctx* ctx, const char* who) { return victim_context_ok<ClsVictim>(ctx, who); }
 
 // the fewest points of a cloud: a DGCNN context's k, which is 0 in every other context
 template <class V>
@@ -2622,11 +2605,6 @@ size_t loop_ws_bytes(ifd_ctx* ctx, int B, int stride, size_t state_bytes, bool w
     const size_t fwd = with_forward ? V::fwd_ws_bytes(ctx, even_chunk(B, V::CHUNK), stride) : 0;
     return state_bytes + std::max(grad_ws_bytes<V>(ctx, B, stride), fwd);
 }
-int atk_chunk(int B) { return even_chunk(B, CLS_CHUNK); }
-size_t atk_grad_ws_bytes(int B, int stride) { return grad_ws_bytes<ClsVictim>(nullptr, B, stride); }
-size_t atk_loop_ws_bytes(int B, int stride, size_t state_bytes, bool with_forward) {
-    return loop_ws_bytes<ClsVictim>(nullptr, B, stride, state_bytes, with_forward);
-}
 
 // The skeleton of a victim's gradient call, victim_forward's sibling: on workspace that is already large enough (ws_off: bytes in
 // front that belong to the caller), unchecked.  This is what an attack loop calls per iteration.
@@ -2648,10 +2626,6 @@ int victim_grad(ifd_ctx* ctx, size_t ws_off, const GradCall& g, const typename V
         return r.e;
     });
 }
-int input_grad_impl(ifd_ctx* ctx, size_t ws_off, const float* pc, const int32_t* n_points, int B, int stride, const int32_t* target,
-                    int loss_kind, float kappa, float scale, float* grad, const ifd_atk_out* out, hipStream_t s) {
-    return victim_grad<ClsVictim>(ctx, ws_off, {pc, n_points, nullptr, target, B, stride, loss_kind, kappa, scale, grad, s}, out);
-}
 
 // the final forward behind the loop's state (the counts were checked before the loop, so it does not block), success = pred == target
 template <class V>
@@ -2661,10 +2635,6 @@ int victim_final_success(ifd_ctx* ctx, const char* who, const float* pc_out, con
     hipError_t e = launch_atk_success(pred, target, B, success, s);
     if (e != hipSuccess) return fail(ctx, IFD_ERR_HIP, (std::string(who) + ": success").c_str(), e);
     return IFD_OK;
-}
-int atk_final_success(ifd_ctx* ctx, const char* who, const float* pc_out, const int32_t* n_points, int B, int stride, float* logits,
-                      int32_t* pred, const int32_t* target, int32_t* success, size_t state_bytes, hipStream_t s) {
-    return victim_final_success<ClsVictim>(ctx, who, pc_out, n_points, nullptr, B, stride, logits, pred, target, success, state_bytes, s);
 }
 
 // ifd_*_input_grad
@@ -3063,13 +3033,125 @@ int ifd_knn_attack(ifd_ctx* ctx, const ifd_knn_params* params, const float* pc_i
 
 }  // extern "C"
 
-// ---- the CW point-adding attack (include/ifd_add.h) --------------------------------------------------------------------
+// ---- the CW point-adding attacks (include/ifd_add.h, ifd_cluster.h, ifd_object.h) ---------------------------------------
+// Add, Add-Cluster and Add-Objects are one loop over the victim V, adding_attack_impl; the entry points below are its ClsVictim
+// instance.  What a call adds to a cloud is A rows: num_add (Add), or num_add groups of `per` rows - `per` is the name of that
+// factor in the messages, "cl_num_p" or "obj_num_p", and "" in Add.
 static_assert(IFD_ADD_MAX_ADD == ifd::ADD_MAX_ADD && IFD_ADD_MAX_ORI == ifd::ADD_MAX_ORI, "the header's limits are the kernel's");
 static_assert(IFD_ADD_CHAMFER == ifd::ADD_CHAMFER && IFD_ADD_HAUSDORFF == ifd::ADD_HAUSDORFF, "the header's kinds are the kernel's");
 
 namespace {
 
 bool add_kind_ok(int k) { return k == IFD_ADD_CHAMFER || k == IFD_ADD_HAUSDORFF; }
+
+// A = num_add * per_group, or 0 where the pair is outside the headers' limits
+int added_rows(int num_add, int per_group) {
+    if (num_add < 1 || per_group < 1 || num_add > IFD_ADD_MAX_ADD || per_group > IFD_ADD_MAX_ADD) return 0;
+    const int A = num_add * per_group;
+    return A <= IFD_ADD_MAX_ADD ? A : 0;
+}
+// how A reads in a message, and the refusal of an A of 0
+std::string rows_name(const std::string& per) { return per.empty() ? "num_add" : "num_add * " + per; }
+std::string rows_refusal(const std::string& per) {
+    return per.empty() ? ": num_add outside [1, 1024]" : ": num_add < 1, " + per + " < 1 or " + rows_name(per) + " outside [1, 1024]";
+}
+
+// the row checks of the step and place calls on a concatenated cloud: A, cat_stride in [lo, 10000], and the originals without n_ori
+int cat_rows_ok(ifd_ctx* ctx, const char* who, int A, const std::string& per, int cat_stride, int lo, const int32_t* n_ori) {
+    if (A < 1) return refuse(ctx, who, rows_refusal(per));
+    if (cat_stride > IFD_CLS_MAX_POINTS || cat_stride < lo)
+        return refuse(ctx, who, ": cat_stride outside [" + (per.empty() ? "2 num_add" : rows_name(per) + " + 1") + ", 10000]");
+    if (!n_ori && cat_stride - A > IFD_ADD_MAX_ORI)
+        return refuse(ctx, who, ": without n_ori, cat_stride - " + rows_name(per) + " > 2048 original rows");
+    return IFD_OK;
+}
+// ... and of the two selection calls on the original cloud
+int select_rows_ok(ifd_ctx* ctx, const char* who, int num_add, int stride, const int32_t* n_points) {
+    if (num_add < 1 || num_add > IFD_ADD_MAX_ADD) return refuse(ctx, who, rows_refusal(""));
+    if (stride < 1 || stride > IFD_CLS_MAX_POINTS) return refuse(ctx, who, ": stride outside [1, 10000]");
+    if (!n_points && (stride < num_add || stride > IFD_ADD_MAX_ORI)) return refuse(ctx, who, ": without n_points, stride outside [num_add, 2048]");
+    return IFD_OK;
+}
+
+// What is an adding attack's own, beside its two kernels: its rows, and the pointers it takes between target and B
+struct AddingRows {
+    int A; const char* per;
+    bool critical;                         // Add: the rows start on the cloud's critical points, so a cloud needs A originals
+    int pose_rows;                         // Objects: num_add poses a cloud, else 0
+    bool pointers; const char* pointers_text;   // its own pointers are all there; the list in the refusal of a missing one
+};
+// ... and the tensors every one of them takes
+struct AddingIo {
+    const float* pc_in; const int32_t *n_points, *target; int B, stride, out_stride; float *pc_out, *best_dist; int32_t* success;
+    double* bounds; hipStream_t s;
+};
+
+// The loop of ifd_add_attack, ifd_cluster_attack and ifd_object_attack, whose params P share every member read here; the caller has
+// checked the context, P's struct_size and what only it has.  start(L, step): the launch that opens a search step;
+// step(L, t, last_input): the step kernel behind the gradient.
+template <class V, class P, class Start, class Step>
+int adding_attack_impl(ifd_ctx* ctx, const char* who, const P& prm, const AddingRows& r, const AddingIo& io, Start start, Step step) {
+    static_assert(V::SAMPLE_CHECK == nullptr, "a victim that samples needs its starts and its own count check here");
+    const int B = io.B, stride = io.stride, out_stride = io.out_stride, A = r.A;
+    if (!atk_loss_ok(prm.loss_kind)) return refuse(ctx, who, ": unknown loss_kind");
+    if (prm.binary_step < 1) return refuse(ctx, who, ": binary_step < 1");
+    if (prm.num_iter < 1) return refuse(ctx, who, ": num_iter < 1");
+    if (A < 1) return refuse(ctx, who, rows_refusal(r.per));
+    if (B < 1) return refuse(ctx, who, ": B >= 1 is needed");
+    if (stride < 1 || stride > IFD_CLS_MAX_POINTS) return refuse(ctx, who, ": stride outside [1, 10000]");
+    if (out_stride < 1 || out_stride > IFD_CLS_MAX_POINTS) return refuse(ctx, who, ": out_stride outside [1, 10000]");
+    if (!io.pc_in || !io.target || !r.pointers || !io.pc_out || !io.best_dist || !io.success)
+        return refuse(ctx, who, std::string(": missing pointer (") + r.pointers_text + ")");
+    const int lo = r.critical ? A : 1, hi = std::min(std::min(stride, IFD_ADD_MAX_ORI), out_stride - A);
+    if (!io.n_points && (stride < lo || stride > hi))
+        return refuse(ctx, who, std::string(": without n_points, stride outside [") + (r.critical ? "num_add" : "1") +
+                                    ", min(2048, out_stride - " + rows_name(r.per) + ")]");
+    if (clouds_overlap(io.pc_in, (size_t)B * stride * 12, io.pc_out, (size_t)B * out_stride * 12)) return refuse(ctx, who, ": pc_out overlaps pc_in");
+    IFD_ON_CTX_DEVICE(ctx);
+    hipStream_t s = io.s;
+    const int G = std::max(stride, out_stride);
+    auto carve = [&](Carve& c) { return AddingLoop(c, (size_t)B, (size_t)G, (size_t)A, r.critical ? (size_t)A : 0, (size_t)r.pose_rows); };
+    const size_t state = carved_bytes(carve);
+    hipError_t e = ctx->ws.grow(loop_ws_bytes<V>(ctx, B, G, state, false));
+    if (e != hipSuccess) return hip_fail(ctx, who, ": workspace", e, IFD_ERR_NOMEM);
+    if (int rc = atk_check(ctx, who, io.n_points, io.target, B, lo, hi, numeric_range(lo, hi), s)) return rc;
+    Carve c(ctx->ws.get());
+    AddingLoop L = carve(c);
+    L.S.cw.o_bestdist = io.best_dist;
+    const CwState& S = L.S.cw;
+    GradCall g{io.pc_in, io.n_points, nullptr, io.target, B, stride, IFD_ATK_LOSS_CE, 0.f, prm.scale, L.grad, s};
+    if (r.critical) {     // the critical points (Add.py:14-42): cross-entropy towards the target, whatever the loop's loss
+        if (int rc = victim_grad<V>(ctx, state, g, nullptr)) return rc;
+        e = launch_add_select(L.grad, io.pc_in, io.n_points, B, stride, A, L.cri, nullptr, s);
+    }
+    if (e == hipSuccess) e = launch_add_begin(io.pc_in, io.n_points, B, stride, out_stride, A, io.pc_out, L.n_ori, L.n_cat, s);
+    if (e == hipSuccess) e = launch_cw_init(S, B, prm.init_weight, prm.max_weight, s);
+    if (e == hipSuccess) e = hipMemsetAsync(S.m, 0, 3 * (size_t)B * A * 12, s);       // m, v and o_bestattack lie side by side
+    if (e != hipSuccess) return hip_fail(ctx, who, ": start", e);
+    typename V::Out out{};
+    out.loss = L.loss;
+    out.pred = L.pred;
+    g = GradCall{io.pc_out, L.n_cat, nullptr, io.target, B, out_stride, prm.loss_kind, prm.kappa, prm.scale, L.grad, s};
+    if (int rc = cw_search(
+        prm.binary_step, prm.num_iter,
+        [&](int search_step) {
+            hipError_t e = start(L, search_step);
+            return e == hipSuccess ? IFD_OK : hip_fail(ctx, who, ": search step start", e);
+        },
+        [&](int, int it, bool final_it) {
+            if (int rc = victim_grad<V>(ctx, state, g, &out)) return rc;
+            hipError_t e = step(L, it + 1, final_it ? L.last : nullptr);
+            return e == hipSuccess ? IFD_OK : hip_fail(ctx, who, ": step", e);
+        },
+        [&](int) {
+            hipError_t e = launch_cw_adjust(S, io.target, nullptr, B, A, s);
+            return e == hipSuccess ? IFD_OK : hip_fail(ctx, who, ": adjust", e);
+        }))
+        return rc;
+    e = launch_add_finish(S, L.last, L.n_cat, B, out_stride, A, io.pc_out, io.success, io.bounds, s);
+    if (e != hipSuccess) return hip_fail(ctx, who, ": finish", e);
+    return IFD_OK;
+}
 
 }  // namespace
 
@@ -3080,12 +3162,9 @@ int ifd_add_abi_version(void) { return IFD_ADD_ABI_VERSION; }
 int ifd_add_select(ifd_ctx* ctx, const float* grad, const float* pc, const int32_t* n_points, int B, int stride, int num_add, float* cri,
                    int32_t* idx, void* stream) {
     if (!ctx) return IFD_ERR_ARG;
-    if (int rc = atk_context_ok(ctx, "ifd_add_select")) return rc;
+    if (int rc = victim_context_ok<ClsVictim>(ctx, "ifd_add_select")) return rc;
     if (!grad || !pc || !cri || B < 1) return fail(ctx, IFD_ERR_ARG, "ifd_add_select: bad argument (grad, pc, cri; B >= 1)");
-    if (num_add < 1 || num_add > IFD_ADD_MAX_ADD) return fail(ctx, IFD_ERR_ARG, "ifd_add_select: num_add outside [1, 1024]");
-    if (stride < 1 || stride > IFD_CLS_MAX_POINTS) return fail(ctx, IFD_ERR_ARG, "ifd_add_select: stride outside [1, 10000]");
-    if (!n_points && (stride < num_add || stride > IFD_ADD_MAX_ORI))
-        return fail(ctx, IFD_ERR_ARG, "ifd_add_select: without n_points, stride outside [num_add, 2048]");
+    if (int rc = select_rows_ok(ctx, "ifd_add_select", num_add, stride, n_points)) return rc;
     IFD_ON_CTX_DEVICE(ctx);
     hipError_t e = launch_add_select(grad, pc, n_points, B, stride, num_add, cri, idx, static_cast<hipStream_t>(stream));
     if (e != hipSuccess) return fail(ctx, IFD_ERR_HIP, "ifd_add_select launch", e);
@@ -3095,22 +3174,20 @@ int ifd_add_select(ifd_ctx* ctx, const float* grad, const float* pc, const int32
 int ifd_add_critical_points(ifd_ctx* ctx, const float* pc, const int32_t* n_points, const int32_t* target, int B, int stride, int num_add,
                             float scale, float* cri, int32_t* idx, void* stream) {
     if (!ctx) return IFD_ERR_ARG;
-    if (int rc = atk_context_ok(ctx, "ifd_add_critical_points")) return rc;
+    if (int rc = victim_context_ok<ClsVictim>(ctx, "ifd_add_critical_points")) return rc;
     if (!pc || !target || !cri || B < 1) return fail(ctx, IFD_ERR_ARG, "ifd_add_critical_points: bad argument (pc, target, cri; B >= 1)");
-    if (num_add < 1 || num_add > IFD_ADD_MAX_ADD) return fail(ctx, IFD_ERR_ARG, "ifd_add_critical_points: num_add outside [1, 1024]");
-    if (stride < 1 || stride > IFD_CLS_MAX_POINTS) return fail(ctx, IFD_ERR_ARG, "ifd_add_critical_points: stride outside [1, 10000]");
-    if (!n_points && (stride < num_add || stride > IFD_ADD_MAX_ORI))
-        return fail(ctx, IFD_ERR_ARG, "ifd_add_critical_points: without n_points, stride outside [num_add, 2048]");
+    if (int rc = select_rows_ok(ctx, "ifd_add_critical_points", num_add, stride, n_points)) return rc;
     IFD_ON_CTX_DEVICE(ctx);
     hipStream_t s = static_cast<hipStream_t>(stream);
     const size_t state = carved_bytes([&](Carve& c) { grad_loop(c, (size_t)B, (size_t)stride * 12); });
-    hipError_t e = ctx->ws.grow(state + atk_grad_ws_bytes(B, stride));
+    hipError_t e = ctx->ws.grow(state + grad_ws_bytes<ClsVictim>(ctx, B, stride));
     if (e != hipSuccess) return fail(ctx, IFD_ERR_NOMEM, "ifd_add_critical_points: workspace", e);
     const int hi = std::min(stride, IFD_ADD_MAX_ORI);
     if (int rc = atk_check(ctx, "ifd_add_critical_points", n_points, target, B, num_add, hi, numeric_range(num_add, hi), s)) return rc;
     Carve c(ctx->ws.get());
     float* grad = grad_loop(c, (size_t)B, (size_t)stride * 12);
-    if (int rc = input_grad_impl(ctx, state, pc, n_points, B, stride, target, IFD_ATK_LOSS_CE, 0.f, scale, grad, nullptr, s)) return rc;
+    if (int rc = victim_grad<ClsVictim>(ctx, state, {pc, n_points, nullptr, target, B, stride, IFD_ATK_LOSS_CE, 0.f, scale, grad, s}, nullptr))
+        return rc;
     e = launch_add_select(grad, pc, n_points, B, stride, num_add, cri, idx, s);
     if (e != hipSuccess) return fail(ctx, IFD_ERR_HIP, "ifd_add_critical_points: select", e);
     return IFD_OK;
@@ -3120,17 +3197,13 @@ int ifd_add_step(ifd_ctx* ctx, int kind, const ifd_cw_state* state, const float*
                  const int32_t* target, float* cat, const int32_t* n_ori, float* last_input, float* info, const ifd_add_diag* diag, int t,
                  float lr, float scale, int B, int cat_stride, int num_add, void* stream) {
     if (!ctx) return IFD_ERR_ARG;
-    if (int rc = atk_context_ok(ctx, "ifd_add_step")) return rc;
+    if (int rc = victim_context_ok<ClsVictim>(ctx, "ifd_add_step")) return rc;
     if (!add_kind_ok(kind)) return fail(ctx, IFD_ERR_ARG, "ifd_add_step: unknown kind");
     if (!cw_state_ok(state, false))
         return fail(ctx, IFD_ERR_ARG, "ifd_add_step: state missing (m, v, bestdist, bestscore, o_bestdist, o_bestscore, o_bestattack, weight)");
     if (!grad || !pred || !target || !cat || t < 1 || B < 1)
         return fail(ctx, IFD_ERR_ARG, "ifd_add_step: bad argument (grad, pred, target, cat; t >= 1, B >= 1)");
-    if (num_add < 1 || num_add > IFD_ADD_MAX_ADD) return fail(ctx, IFD_ERR_ARG, "ifd_add_step: num_add outside [1, 1024]");
-    if (cat_stride > IFD_CLS_MAX_POINTS || cat_stride < 2 * num_add)
-        return fail(ctx, IFD_ERR_ARG, "ifd_add_step: cat_stride outside [2 num_add, 10000]");
-    if (!n_ori && cat_stride - num_add > IFD_ADD_MAX_ORI)
-        return fail(ctx, IFD_ERR_ARG, "ifd_add_step: without n_ori, cat_stride - num_add > 2048 original rows");
+    if (int rc = cat_rows_ok(ctx, "ifd_add_step", added_rows(num_add, 1), "", cat_stride, 2 * num_add, n_ori)) return rc;
     IFD_ON_CTX_DEVICE(ctx);
     const AddDiag D = diag ? AddDiag{diag->dist_grad, diag->nn_ori, diag->far} : AddDiag{};
     hipError_t e = launch_add_step(kind, cw_state(state), grad, pred, loss, target, cat, n_ori, last_input, info, D, t, lr, scale, B,
@@ -3143,71 +3216,22 @@ int ifd_add_attack(ifd_ctx* ctx, const ifd_add_params* params, const float* pc_i
                    const float* noise, int B, int stride, int out_stride, float* pc_out, float* best_dist, int32_t* success,
                    double* bounds, void* stream) {
     if (!ctx) return IFD_ERR_ARG;
-    if (int rc = atk_context_ok(ctx, "ifd_add_attack")) return rc;
+    if (int rc = victim_context_ok<ClsVictim>(ctx, "ifd_add_attack")) return rc;
     if (!params || params->struct_size != (int32_t)sizeof(ifd_add_params))
         return fail(ctx, IFD_ERR_ARG, "ifd_add_attack: params missing or of another struct_size");
     if (!add_kind_ok(params->kind)) return fail(ctx, IFD_ERR_ARG, "ifd_add_attack: unknown kind");
-    if (!atk_loss_ok(params->loss_kind)) return fail(ctx, IFD_ERR_ARG, "ifd_add_attack: unknown loss_kind");
-    if (params->binary_step < 1) return fail(ctx, IFD_ERR_ARG, "ifd_add_attack: binary_step < 1");
-    if (params->num_iter < 1) return fail(ctx, IFD_ERR_ARG, "ifd_add_attack: num_iter < 1");
-    const int num_add = params->num_add;
-    if (num_add < 1 || num_add > IFD_ADD_MAX_ADD) return fail(ctx, IFD_ERR_ARG, "ifd_add_attack: num_add outside [1, 1024]");
-    if (B < 1) return fail(ctx, IFD_ERR_ARG, "ifd_add_attack: B >= 1 is needed");
-    if (stride < 1 || stride > IFD_CLS_MAX_POINTS) return fail(ctx, IFD_ERR_ARG, "ifd_add_attack: stride outside [1, 10000]");
-    if (out_stride < 1 || out_stride > IFD_CLS_MAX_POINTS) return fail(ctx, IFD_ERR_ARG, "ifd_add_attack: out_stride outside [1, 10000]");
-    if (!pc_in || !target || !pc_out || !best_dist || !success)
-        return fail(ctx, IFD_ERR_ARG, "ifd_add_attack: missing pointer (pc_in, target, pc_out, best_dist, success)");
-    const int hi = std::min(std::min(stride, IFD_ADD_MAX_ORI), out_stride - num_add);
-    if (!n_points && (stride < num_add || stride > hi))
-        return fail(ctx, IFD_ERR_ARG, "ifd_add_attack: without n_points, stride outside [num_add, min(2048, out_stride - num_add)]");
-    if (clouds_overlap(pc_in, (size_t)B * stride * 12, pc_out, (size_t)B * out_stride * 12))
-        return fail(ctx, IFD_ERR_ARG, "ifd_add_attack: pc_out overlaps pc_in");
-    IFD_ON_CTX_DEVICE(ctx);
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    const int G = std::max(stride, out_stride);
-    const size_t added = (size_t)B * num_add * 12;
-    const size_t state = carved_bytes([&](Carve& c) { AddLoop(c, (size_t)B, (size_t)G, (size_t)num_add); });
-    hipError_t e = ctx->ws.grow(atk_loop_ws_bytes(B, G, state, false));
-    if (e != hipSuccess) return fail(ctx, IFD_ERR_NOMEM, "ifd_add_attack: workspace", e);
-    if (int rc = atk_check(ctx, "ifd_add_attack", n_points, target, B, num_add, hi, numeric_range(num_add, hi), s)) return rc;
-    Carve c(ctx->ws.get());
-    const AddLoop L(c, (size_t)B, (size_t)G, (size_t)num_add);
-    CwState S = L.f.S;
-    int32_t *pred = L.f.pred, *n_cat = L.n_cat, *n_ori = L.n_ori;
-    float *loss = L.f.loss, *grad = L.grad, *cri = L.cri, *last = L.last;
-    S.o_bestdist = best_dist;
-    // the critical points (Add.py:14-42): cross-entropy towards the target, whatever the loop's loss
-    if (int rc = input_grad_impl(ctx, state, pc_in, n_points, B, stride, target, IFD_ATK_LOSS_CE, 0.f, params->scale, grad, nullptr, s))
-        return rc;
-    e = launch_add_select(grad, pc_in, n_points, B, stride, num_add, cri, nullptr, s);
-    if (e == hipSuccess) e = launch_add_begin(pc_in, n_points, B, stride, out_stride, num_add, pc_out, n_ori, n_cat, s);
-    if (e == hipSuccess) e = launch_cw_init(S, B, params->init_weight, params->max_weight, s);
-    if (e == hipSuccess) e = hipMemsetAsync(S.m, 0, 3 * added, s);     // m, v and o_bestattack lie side by side
-    if (e != hipSuccess) return fail(ctx, IFD_ERR_HIP, "ifd_add_attack: start", e);
-    const ifd_atk_out out{nullptr, loss, pred, nullptr, nullptr, nullptr};
-    if (int rc = cw_search(
-        params->binary_step, params->num_iter,
-        [&](int step) {
-            hipError_t e = launch_add_start(cri, noise ? noise + (size_t)step * B * num_add * 3 : nullptr, n_cat, B, out_stride, num_add,
-                                            pc_out, s);
-            return e == hipSuccess ? IFD_OK : fail(ctx, IFD_ERR_HIP, "ifd_add_attack: search step start", e);
+    const int num_add = added_rows(params->num_add, 1);
+    const AddingRows rows{num_add, "", true, 0, true, "pc_in, target, pc_out, best_dist, success"};
+    const AddingIo io{pc_in, n_points, target, B, stride, out_stride, pc_out, best_dist, success, bounds, static_cast<hipStream_t>(stream)};
+    return adding_attack_impl<ClsVictim>(
+        ctx, "ifd_add_attack", *params, rows, io,
+        [&](const AddingLoop& L, int step) {
+            return launch_add_start(L.cri, noise ? noise + (size_t)step * B * num_add * 3 : nullptr, L.n_cat, B, out_stride, num_add, pc_out, io.s);
         },
-        [&](int, int it, bool final_it) {
-            if (int rc = input_grad_impl(ctx, state, pc_out, n_cat, B, out_stride, target, params->loss_kind, params->kappa, params->scale,
-                                         grad, &out, s))
-                return rc;
-            hipError_t e = launch_add_step(params->kind, S, grad, pred, loss, target, pc_out, n_ori, final_it ? last : nullptr, nullptr,
-                                           AddDiag{}, it + 1, params->attack_lr, params->scale, B, out_stride, num_add, s);
-            return e == hipSuccess ? IFD_OK : fail(ctx, IFD_ERR_HIP, "ifd_add_attack: step", e);
-        },
-        [&](int) {
-            hipError_t e = launch_cw_adjust(S, target, nullptr, B, num_add, s);
-            return e == hipSuccess ? IFD_OK : fail(ctx, IFD_ERR_HIP, "ifd_add_attack: adjust", e);
-        }))
-        return rc;
-    e = launch_add_finish(S, last, n_cat, B, out_stride, num_add, pc_out, success, bounds, s);
-    if (e != hipSuccess) return fail(ctx, IFD_ERR_HIP, "ifd_add_attack: finish", e);
-    return IFD_OK;
+        [&](const AddingLoop& L, int t, float* last_input) {
+            return launch_add_step(params->kind, L.S.cw, L.grad, L.pred, L.loss, target, pc_out, L.n_ori, last_input, nullptr, AddDiag{}, t,
+                                   params->attack_lr, params->scale, B, out_stride, num_add, io.s);
+        });
 }
 
 }  // extern "C"
@@ -3389,17 +3413,6 @@ int ifd_victim_drop_attack(ifd_ctx* ctx, const ifd_drop_params* params, const fl
 // ---- the CW cluster-adding attack (include/ifd_cluster.h) --------------------------------------------------------------
 static_assert(IFD_CLUSTER_DBSCAN_MAX_POINTS == ifd::CLUSTER_DBSCAN_MAX_POINTS, "the header's limit is the kernel's");
 
-namespace {
-
-// A = num_add * cl_num_p, or 0 where the pair is outside the header's limits
-int cluster_rows(int num_add, int cl_num_p) {
-    if (num_add < 1 || cl_num_p < 1 || num_add > IFD_ADD_MAX_ADD || cl_num_p > IFD_ADD_MAX_ADD) return 0;
-    const int A = num_add * cl_num_p;
-    return A <= IFD_ADD_MAX_ADD ? A : 0;
-}
-
-}  // namespace
-
 extern "C" {
 
 int ifd_cluster_abi_version(void) { return IFD_CLUSTER_ABI_VERSION; }
@@ -3407,7 +3420,7 @@ int ifd_cluster_abi_version(void) { return IFD_CLUSTER_ABI_VERSION; }
 int ifd_cluster_dbscan(ifd_ctx* ctx, const float* pts, const int32_t* n_pts, int B, int stride, float eps, int min_samples,
                        int32_t* labels, int32_t* n_clusters, void* stream) {
     if (!ctx) return IFD_ERR_ARG;
-    if (int rc = atk_context_ok(ctx, "ifd_cluster_dbscan")) return rc;
+    if (int rc = victim_context_ok<ClsVictim>(ctx, "ifd_cluster_dbscan")) return rc;
     if (!pts || !labels || B < 1) return fail(ctx, IFD_ERR_ARG, "ifd_cluster_dbscan: bad argument (pts, labels; B >= 1)");
     if (stride < 1 || stride > IFD_CLS_MAX_POINTS) return fail(ctx, IFD_ERR_ARG, "ifd_cluster_dbscan: stride outside [1, 10000]");
     if (!(eps > 0.f) || !std::isfinite(eps)) return fail(ctx, IFD_ERR_ARG, "ifd_cluster_dbscan: eps must be a finite number above 0");
@@ -3425,17 +3438,13 @@ int ifd_cluster_step(ifd_ctx* ctx, const ifd_cw_state* state, const float* grad,
                      const ifd_cluster_diag* diag, int t, float lr, float scale, int B, int cat_stride, int num_add, int cl_num_p,
                      void* stream) {
     if (!ctx) return IFD_ERR_ARG;
-    if (int rc = atk_context_ok(ctx, "ifd_cluster_step")) return rc;
+    if (int rc = victim_context_ok<ClsVictim>(ctx, "ifd_cluster_step")) return rc;
     if (!cw_state_ok(state, false))
         return fail(ctx, IFD_ERR_ARG, "ifd_cluster_step: state missing (m, v, bestdist, bestscore, o_bestdist, o_bestscore, o_bestattack, weight)");
     if (!grad || !pred || !target || !cat || t < 1 || B < 1)
         return fail(ctx, IFD_ERR_ARG, "ifd_cluster_step: bad argument (grad, pred, target, cat; t >= 1, B >= 1)");
-    const int A = cluster_rows(num_add, cl_num_p);
-    if (A < 1) return fail(ctx, IFD_ERR_ARG, "ifd_cluster_step: num_add < 1, cl_num_p < 1 or num_add * cl_num_p outside [1, 1024]");
-    if (cat_stride > IFD_CLS_MAX_POINTS || cat_stride < A + 1)
-        return fail(ctx, IFD_ERR_ARG, "ifd_cluster_step: cat_stride outside [num_add * cl_num_p + 1, 10000]");
-    if (!n_ori && cat_stride - A > IFD_ADD_MAX_ORI)
-        return fail(ctx, IFD_ERR_ARG, "ifd_cluster_step: without n_ori, cat_stride - num_add * cl_num_p > 2048 original rows");
+    const int A = added_rows(num_add, cl_num_p);
+    if (int rc = cat_rows_ok(ctx, "ifd_cluster_step", A, "cl_num_p", cat_stride, A + 1, n_ori)) return rc;
     IFD_ON_CTX_DEVICE(ctx);
     const ClusterDiag D = diag ? ClusterDiag{diag->dist_grad, diag->nn_ori, diag->far_i, diag->far_j, diag->far_val} : ClusterDiag{};
     hipError_t e = launch_cluster_step(cw_state(state), grad, pred, loss, target, cat, n_ori, last_input, info, D, t, lr, scale, B,
@@ -3448,65 +3457,21 @@ int ifd_cluster_attack(ifd_ctx* ctx, const ifd_cluster_params* params, const flo
                        const int32_t* target, const float* clusters, const float* noise, int B, int stride, int out_stride,
                        float* pc_out, float* best_dist, int32_t* success, double* bounds, void* stream) {
     if (!ctx) return IFD_ERR_ARG;
-    if (int rc = atk_context_ok(ctx, "ifd_cluster_attack")) return rc;
+    if (int rc = victim_context_ok<ClsVictim>(ctx, "ifd_cluster_attack")) return rc;
     if (!params || params->struct_size != (int32_t)sizeof(ifd_cluster_params))
         return fail(ctx, IFD_ERR_ARG, "ifd_cluster_attack: params missing or of another struct_size");
-    if (!atk_loss_ok(params->loss_kind)) return fail(ctx, IFD_ERR_ARG, "ifd_cluster_attack: unknown loss_kind");
-    if (params->binary_step < 1) return fail(ctx, IFD_ERR_ARG, "ifd_cluster_attack: binary_step < 1");
-    if (params->num_iter < 1) return fail(ctx, IFD_ERR_ARG, "ifd_cluster_attack: num_iter < 1");
-    const int num_add = params->num_add, cl_num_p = params->cl_num_p, A = cluster_rows(num_add, cl_num_p);
-    if (A < 1) return fail(ctx, IFD_ERR_ARG, "ifd_cluster_attack: num_add < 1, cl_num_p < 1 or num_add * cl_num_p outside [1, 1024]");
-    if (B < 1) return fail(ctx, IFD_ERR_ARG, "ifd_cluster_attack: B >= 1 is needed");
-    if (stride < 1 || stride > IFD_CLS_MAX_POINTS) return fail(ctx, IFD_ERR_ARG, "ifd_cluster_attack: stride outside [1, 10000]");
-    if (out_stride < 1 || out_stride > IFD_CLS_MAX_POINTS) return fail(ctx, IFD_ERR_ARG, "ifd_cluster_attack: out_stride outside [1, 10000]");
-    if (!pc_in || !target || !clusters || !pc_out || !best_dist || !success)
-        return fail(ctx, IFD_ERR_ARG, "ifd_cluster_attack: missing pointer (pc_in, target, clusters, pc_out, best_dist, success)");
-    const int hi = std::min(std::min(stride, IFD_ADD_MAX_ORI), out_stride - A);
-    if (!n_points && stride > hi)
-        return fail(ctx, IFD_ERR_ARG, "ifd_cluster_attack: without n_points, stride outside [1, min(2048, out_stride - num_add * cl_num_p)]");
-    if (clouds_overlap(pc_in, (size_t)B * stride * 12, pc_out, (size_t)B * out_stride * 12))
-        return fail(ctx, IFD_ERR_ARG, "ifd_cluster_attack: pc_out overlaps pc_in");
-    IFD_ON_CTX_DEVICE(ctx);
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    const int G = std::max(stride, out_stride);
-    const size_t added = (size_t)B * A * 12;
-    const size_t state = carved_bytes([&](Carve& c) { ClusterLoop(c, (size_t)B, (size_t)G, (size_t)A); });
-    hipError_t e = ctx->ws.grow(atk_loop_ws_bytes(B, G, state, false));
-    if (e != hipSuccess) return fail(ctx, IFD_ERR_NOMEM, "ifd_cluster_attack: workspace", e);
-    if (int rc = atk_check(ctx, "ifd_cluster_attack", n_points, target, B, 1, hi, numeric_range(1, hi), s)) return rc;
-    Carve c(ctx->ws.get());
-    const ClusterLoop L(c, (size_t)B, (size_t)G, (size_t)A);
-    CwState S = L.f.S;
-    int32_t *pred = L.f.pred, *n_cat = L.n_cat, *n_ori = L.n_ori;
-    float *loss = L.f.loss, *grad = L.grad, *last = L.last;
-    S.o_bestdist = best_dist;
-    e = launch_add_begin(pc_in, n_points, B, stride, out_stride, A, pc_out, n_ori, n_cat, s);
-    if (e == hipSuccess) e = launch_cw_init(S, B, params->init_weight, params->max_weight, s);
-    if (e == hipSuccess) e = hipMemsetAsync(S.m, 0, 3 * added, s);     // m, v and o_bestattack lie side by side
-    if (e != hipSuccess) return fail(ctx, IFD_ERR_HIP, "ifd_cluster_attack: start", e);
-    const ifd_atk_out out{nullptr, loss, pred, nullptr, nullptr, nullptr};
-    if (int rc = cw_search(
-        params->binary_step, params->num_iter,
-        [&](int step) {
-            hipError_t e = launch_add_start(clusters, noise ? noise + (size_t)step * B * A * 3 : nullptr, n_cat, B, out_stride, A, pc_out, s);
-            return e == hipSuccess ? IFD_OK : fail(ctx, IFD_ERR_HIP, "ifd_cluster_attack: search step start", e);
+    const int num_add = params->num_add, cl_num_p = params->cl_num_p, A = added_rows(num_add, cl_num_p);
+    const AddingRows rows{A, "cl_num_p", false, 0, clusters != nullptr, "pc_in, target, clusters, pc_out, best_dist, success"};
+    const AddingIo io{pc_in, n_points, target, B, stride, out_stride, pc_out, best_dist, success, bounds, static_cast<hipStream_t>(stream)};
+    return adding_attack_impl<ClsVictim>(
+        ctx, "ifd_cluster_attack", *params, rows, io,
+        [&](const AddingLoop& L, int step) {
+            return launch_add_start(clusters, noise ? noise + (size_t)step * B * A * 3 : nullptr, L.n_cat, B, out_stride, A, pc_out, io.s);
         },
-        [&](int, int it, bool final_it) {
-            if (int rc = input_grad_impl(ctx, state, pc_out, n_cat, B, out_stride, target, params->loss_kind, params->kappa, params->scale,
-                                         grad, &out, s))
-                return rc;
-            hipError_t e = launch_cluster_step(S, grad, pred, loss, target, pc_out, n_ori, final_it ? last : nullptr, nullptr, ClusterDiag{},
-                                               it + 1, params->attack_lr, params->scale, B, out_stride, num_add, cl_num_p, s);
-            return e == hipSuccess ? IFD_OK : fail(ctx, IFD_ERR_HIP, "ifd_cluster_attack: step", e);
-        },
-        [&](int) {
-            hipError_t e = launch_cw_adjust(S, target, nullptr, B, A, s);
-            return e == hipSuccess ? IFD_OK : fail(ctx, IFD_ERR_HIP, "ifd_cluster_attack: adjust", e);
-        }))
-        return rc;
-    e = launch_add_finish(S, last, n_cat, B, out_stride, A, pc_out, success, bounds, s);
-    if (e != hipSuccess) return fail(ctx, IFD_ERR_HIP, "ifd_cluster_attack: finish", e);
-    return IFD_OK;
+        [&](const AddingLoop& L, int t, float* last_input) {
+            return launch_cluster_step(L.S.cw, L.grad, L.pred, L.loss, target, pc_out, L.n_ori, last_input, nullptr, ClusterDiag{}, t,
+                                       params->attack_lr, params->scale, B, out_stride, num_add, cl_num_p, io.s);
+        });
 }
 
 }  // extern "C"
@@ -3520,14 +3485,10 @@ int ifd_object_abi_version(void) { return IFD_OBJECT_ABI_VERSION; }
 int ifd_object_place(ifd_ctx* ctx, const float* obj, const float* angle, const float* shift, float* cat, const int32_t* n_ori, int B,
                      int cat_stride, int num_add, int obj_num_p, void* stream) {
     if (!ctx) return IFD_ERR_ARG;
-    if (int rc = atk_context_ok(ctx, "ifd_object_place")) return rc;
+    if (int rc = victim_context_ok<ClsVictim>(ctx, "ifd_object_place")) return rc;
     if (!obj || !angle || !shift || !cat || B < 1) return fail(ctx, IFD_ERR_ARG, "ifd_object_place: bad argument (obj, angle, shift, cat; B >= 1)");
-    const int A = cluster_rows(num_add, obj_num_p);
-    if (A < 1) return fail(ctx, IFD_ERR_ARG, "ifd_object_place: num_add < 1, obj_num_p < 1 or num_add * obj_num_p outside [1, 1024]");
-    if (cat_stride > IFD_CLS_MAX_POINTS || cat_stride < A + 1)
-        return fail(ctx, IFD_ERR_ARG, "ifd_object_place: cat_stride outside [num_add * obj_num_p + 1, 10000]");
-    if (!n_ori && cat_stride - A > IFD_ADD_MAX_ORI)
-        return fail(ctx, IFD_ERR_ARG, "ifd_object_place: without n_ori, cat_stride - num_add * obj_num_p > 2048 original rows");
+    const int A = added_rows(num_add, obj_num_p);
+    if (int rc = cat_rows_ok(ctx, "ifd_object_place", A, "obj_num_p", cat_stride, A + 1, n_ori)) return rc;
     IFD_ON_CTX_DEVICE(ctx);
     hipError_t e = launch_object_place(obj, angle, shift, cat, n_ori, B, cat_stride, num_add, obj_num_p, static_cast<hipStream_t>(stream));
     if (e != hipSuccess) return fail(ctx, IFD_ERR_HIP, "ifd_object_place launch", e);
@@ -3539,19 +3500,15 @@ int ifd_object_step(ifd_ctx* ctx, const ifd_object_state* state, const float* ob
                     const ifd_object_diag* diag, int t, float lr, float scale, int B, int cat_stride, int num_add, int obj_num_p,
                     void* stream) {
     if (!ctx) return IFD_ERR_ARG;
-    if (int rc = atk_context_ok(ctx, "ifd_object_step")) return rc;
+    if (int rc = victim_context_ok<ClsVictim>(ctx, "ifd_object_step")) return rc;
     if (!state || !cw_state_ok(&state->cw, false) || !state->obj || !state->shift || !state->angle || !state->shift_m || !state->shift_v ||
         !state->angle_m || !state->angle_v)
         return fail(ctx, IFD_ERR_ARG, "ifd_object_step: state missing (cw: m, v, bestdist, bestscore, o_bestdist, o_bestscore, o_bestattack, "
                                       "weight; obj, shift, angle, shift_m, shift_v, angle_m, angle_v)");
     if (!objects || !grad || !pred || !target || !cat || t < 1 || B < 1)
         return fail(ctx, IFD_ERR_ARG, "ifd_object_step: bad argument (objects, grad, pred, target, cat; t >= 1, B >= 1)");
-    const int A = cluster_rows(num_add, obj_num_p);
-    if (A < 1) return fail(ctx, IFD_ERR_ARG, "ifd_object_step: num_add < 1, obj_num_p < 1 or num_add * obj_num_p outside [1, 1024]");
-    if (cat_stride > IFD_CLS_MAX_POINTS || cat_stride < A + 1)
-        return fail(ctx, IFD_ERR_ARG, "ifd_object_step: cat_stride outside [num_add * obj_num_p + 1, 10000]");
-    if (!n_ori && cat_stride - A > IFD_ADD_MAX_ORI)
-        return fail(ctx, IFD_ERR_ARG, "ifd_object_step: without n_ori, cat_stride - num_add * obj_num_p > 2048 original rows");
+    const int A = added_rows(num_add, obj_num_p);
+    if (int rc = cat_rows_ok(ctx, "ifd_object_step", A, "obj_num_p", cat_stride, A + 1, n_ori)) return rc;
     IFD_ON_CTX_DEVICE(ctx);
     const ObjectState S{cw_state(&state->cw), state->obj, state->shift, state->angle, state->shift_m, state->shift_v, state->angle_m,
                         state->angle_v};
@@ -3567,69 +3524,25 @@ int ifd_object_attack(ifd_ctx* ctx, const ifd_object_params* params, const float
                       const float* noise_shift, const float* angles0, int B, int stride, int out_stride, float* pc_out,
                       float* best_dist, int32_t* success, double* bounds, void* stream) {
     if (!ctx) return IFD_ERR_ARG;
-    if (int rc = atk_context_ok(ctx, "ifd_object_attack")) return rc;
+    if (int rc = victim_context_ok<ClsVictim>(ctx, "ifd_object_attack")) return rc;
     if (!params || params->struct_size != (int32_t)sizeof(ifd_object_params))
         return fail(ctx, IFD_ERR_ARG, "ifd_object_attack: params missing or of another struct_size");
-    if (!atk_loss_ok(params->loss_kind)) return fail(ctx, IFD_ERR_ARG, "ifd_object_attack: unknown loss_kind");
-    if (params->binary_step < 1) return fail(ctx, IFD_ERR_ARG, "ifd_object_attack: binary_step < 1");
-    if (params->num_iter < 1) return fail(ctx, IFD_ERR_ARG, "ifd_object_attack: num_iter < 1");
-    const int num_add = params->num_add, obj_num_p = params->obj_num_p, A = cluster_rows(num_add, obj_num_p);
-    if (A < 1) return fail(ctx, IFD_ERR_ARG, "ifd_object_attack: num_add < 1, obj_num_p < 1 or num_add * obj_num_p outside [1, 1024]");
-    if (B < 1) return fail(ctx, IFD_ERR_ARG, "ifd_object_attack: B >= 1 is needed");
-    if (stride < 1 || stride > IFD_CLS_MAX_POINTS) return fail(ctx, IFD_ERR_ARG, "ifd_object_attack: stride outside [1, 10000]");
-    if (out_stride < 1 || out_stride > IFD_CLS_MAX_POINTS) return fail(ctx, IFD_ERR_ARG, "ifd_object_attack: out_stride outside [1, 10000]");
-    if (!pc_in || !target || !objects || !centers || !angles0 || !pc_out || !best_dist || !success)
-        return fail(ctx, IFD_ERR_ARG,
-                    "ifd_object_attack: missing pointer (pc_in, target, objects, centers, angles0, pc_out, best_dist, success)");
-    const int hi = std::min(std::min(stride, IFD_ADD_MAX_ORI), out_stride - A);
-    if (!n_points && stride > hi)
-        return fail(ctx, IFD_ERR_ARG, "ifd_object_attack: without n_points, stride outside [1, min(2048, out_stride - num_add * obj_num_p)]");
-    if (clouds_overlap(pc_in, (size_t)B * stride * 12, pc_out, (size_t)B * out_stride * 12))
-        return fail(ctx, IFD_ERR_ARG, "ifd_object_attack: pc_out overlaps pc_in");
-    IFD_ON_CTX_DEVICE(ctx);
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    const int G = std::max(stride, out_stride);
-    const size_t added = (size_t)B * A * 12, pose = (size_t)B * num_add * 4;
-    const size_t state = carved_bytes([&](Carve& c) { ObjectLoop(c, (size_t)B, (size_t)G, (size_t)A, (size_t)num_add); });
-    hipError_t e = ctx->ws.grow(atk_loop_ws_bytes(B, G, state, false));
-    if (e != hipSuccess) return fail(ctx, IFD_ERR_NOMEM, "ifd_object_attack: workspace", e);
-    if (int rc = atk_check(ctx, "ifd_object_attack", n_points, target, B, 1, hi, numeric_range(1, hi), s)) return rc;
-    Carve c(ctx->ws.get());
-    const ObjectLoop L(c, (size_t)B, (size_t)G, (size_t)A, (size_t)num_add);
-    ObjectState S = L.S;
-    S.cw = L.f.S;
-    S.cw.o_bestdist = best_dist;
-    int32_t *pred = L.f.pred, *n_cat = L.n_cat, *n_ori = L.n_ori;
-    float *loss = L.f.loss, *grad = L.grad, *last = L.last;
-    e = launch_add_begin(pc_in, n_points, B, stride, out_stride, A, pc_out, n_ori, n_cat, s);
-    if (e == hipSuccess) e = launch_cw_init(S.cw, B, params->init_weight, params->max_weight, s);
-    if (e == hipSuccess) e = hipMemsetAsync(S.cw.m, 0, 3 * added, s);  // m, v and o_bestattack lie side by side
-    if (e != hipSuccess) return fail(ctx, IFD_ERR_HIP, "ifd_object_attack: start", e);
-    const ifd_atk_out out{nullptr, loss, pred, nullptr, nullptr, nullptr};
-    if (int rc = cw_search(
-        params->binary_step, params->num_iter,
-        [&](int step) {
-            hipError_t e = launch_object_start(S, objects, centers, noise_obj ? noise_obj + (size_t)step * (added / 4) : nullptr,
-                                               noise_shift ? noise_shift + (size_t)step * pose / 4 * 3 : nullptr,
-                                               angles0 + (size_t)step * (pose / 4), n_cat, B, out_stride, num_add, obj_num_p, pc_out, s);
-            return e == hipSuccess ? IFD_OK : fail(ctx, IFD_ERR_HIP, "ifd_object_attack: search step start", e);
+    const int num_add = params->num_add, obj_num_p = params->obj_num_p, A = added_rows(num_add, obj_num_p);
+    const AddingRows rows{A, "obj_num_p", false, num_add, objects && centers && angles0,
+                          "pc_in, target, objects, centers, angles0, pc_out, best_dist, success"};
+    const AddingIo io{pc_in, n_points, target, B, stride, out_stride, pc_out, best_dist, success, bounds, static_cast<hipStream_t>(stream)};
+    const size_t added = (size_t)B * A * 3, pose = (size_t)B * num_add;        // floats a search step
+    return adding_attack_impl<ClsVictim>(
+        ctx, "ifd_object_attack", *params, rows, io,
+        [&](const AddingLoop& L, int step) {
+            return launch_object_start(L.S, objects, centers, noise_obj ? noise_obj + step * added : nullptr,
+                                       noise_shift ? noise_shift + step * pose * 3 : nullptr, angles0 + step * pose, L.n_cat, B, out_stride,
+                                       num_add, obj_num_p, pc_out, io.s);
         },
-        [&](int, int it, bool final_it) {
-            if (int rc = input_grad_impl(ctx, state, pc_out, n_cat, B, out_stride, target, params->loss_kind, params->kappa, params->scale,
-                                         grad, &out, s))
-                return rc;
-            hipError_t e = launch_object_step(S, objects, grad, pred, loss, target, pc_out, n_ori, final_it ? last : nullptr, nullptr,
-                                              ObjectDiag{}, it + 1, params->attack_lr, params->scale, B, out_stride, num_add, obj_num_p, s);
-            return e == hipSuccess ? IFD_OK : fail(ctx, IFD_ERR_HIP, "ifd_object_attack: step", e);
-        },
-        [&](int) {
-            hipError_t e = launch_cw_adjust(S.cw, target, nullptr, B, A, s);
-            return e == hipSuccess ? IFD_OK : fail(ctx, IFD_ERR_HIP, "ifd_object_attack: adjust", e);
-        }))
-        return rc;
-    e = launch_add_finish(S.cw, last, n_cat, B, out_stride, A, pc_out, success, bounds, s);
-    if (e != hipSuccess) return fail(ctx, IFD_ERR_HIP, "ifd_object_attack: finish", e);
-    return IFD_OK;
+        [&](const AddingLoop& L, int t, float* last_input) {
+            return launch_object_step(L.S, objects, L.grad, L.pred, L.loss, target, pc_out, L.n_ori, last_input, nullptr, ObjectDiag{}, t,
+                                      params->attack_lr, params->scale, B, out_stride, num_add, obj_num_p, io.s);
+        });
 }
 
 }  // extern "C"

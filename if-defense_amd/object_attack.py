@@ -82,27 +82,18 @@ def main(argv=None, make_classifier=None) -> int:
     object_pc = load_object(args.obj_root, args.obj_num_p)
     if object_pc is None:
         return 2
-    print(args)
-    npz = np.load(args.data_root)
-    data = C.load_points(npz, args.num_points)
-    label, target = C.load_labels(npz)
-    classifier = C.open_classifier(args, make_classifier)
-    try:
+
+    def make_attacker(classifier):
         try:
-            attacker = CWAddObjects(classifier, object_pc, args.adv_func, "l2_chamfer", attack_lr=args.attack_lr, init_weight=INIT_WEIGHT,
-                                    max_weight=MAX_WEIGHT, binary_step=args.binary_step, num_iter=args.num_iter, num_add=args.num_add,
-                                    obj_num_p=args.obj_num_p, scaling=SCALING, kappa=args.kappa, seed=args.seed, verbose=args.verbose)
+            return CWAddObjects(classifier, object_pc, args.adv_func, "l2_chamfer", attack_lr=args.attack_lr, init_weight=INIT_WEIGHT,
+                                max_weight=MAX_WEIGHT, binary_step=args.binary_step, num_iter=args.num_iter, num_add=args.num_add,
+                                obj_num_p=args.obj_num_p, scaling=SCALING, kappa=args.kappa, seed=args.seed, verbose=args.verbose)
         except ValueError as e:
             print("object_attack: {}".format(e), file=sys.stderr)
-            return 2
-        adv, num = C.run_batches(attacker, data, target, args.batch_size)
-    finally:
-        C.close_classifier(classifier)
-    rate = float(num) / float(len(data))
-    d, name = save_path(args.out_dir, args.dataset, args.num_points, args.num_add, args.obj_num_p, args.model, args.adv_func, args.kappa,
-                        rate, 0 if args.local_rank < 0 else args.local_rank)
-    C.save_npz(d, name, adv, label, target)
-    return 0
+            return None
+    return C.run_attack(args, make_classifier, make_attacker,
+                        lambda rate, rank: save_path(args.out_dir, args.dataset, args.num_points, args.num_add, args.obj_num_p, args.model,
+                                                     args.adv_func, args.kappa, rate, rank))
 
 
 if __name__ == '__main__':

@@ -1115,6 +1115,82 @@ class Classifier:
             raise IfdError("num_add must be in [1, %d]" % _lib.ADD_MAX_ADD)
         return num_add
 
+    # what add_*, cluster_* and object_* share (include/ifd_add.h, ifd_cluster.h, ifd_object.h)
+    def _group_rows(self, num_add, per, word):
+        """-> (num_add, per, A = num_add * per) of clusters or objects of ``per`` points; word: how ``per`` reads in the refusal."""
+        num_add, per = int(num_add), int(per)
+        if num_add < 1 or per < 1 or not 1 <= num_add * per <= _lib.ADD_MAX_ADD:
+            raise IfdError("num_add and %s must be at least 1 and num_add * %s in [1, %d]" % (word, word, _lib.ADD_MAX_ADD))
+        return num_add, per, num_add * per
+
+    @staticmethod
+    def _cat_dims(cat):
+        if not torch.is_tensor(cat) or cat.dim() != 3:
+            raise IfdError("cat must be a contiguous float32 [B,N,3] device tensor")
+        return int(cat.shape[0]), int(cat.shape[1])
+
+    def _shaped(self, x, shape, message):
+        """x as a float32 device tensor of that shape, or None."""
+        if x is None:
+            return None
+        x = _f32(torch.as_tensor(x), self.device)
+        if tuple(x.shape) != tuple(shape):
+            raise IfdError(message)
+        return x
+
+    def _adding_step(self, fn, lead, counts, A, shapes, diag_type, grad, pred, target, cat, t, lr, scale, loss, last_input, n_ori,
+                     want_info, want):
+        """The body of add_step, cluster_step and object_step.  lead: the library call's arguments in front of grad (the kind, the
+        state struct, the object template), counts: those behind the stride (num_add, the points per group); A: added rows a cloud;
+        shapes: the diagnostics {name: (shape, dtype)} in the order of diag_type's members."""
+        B, stride = self._cat_dims(cat)
+        ptrs = [self._cw_cloud(x, B, stride, n) for x, n in ((grad, "grad"), (cat, "cat"))]
+        if grad is None:
+            raise IfdError("grad is missing")
+        li = self._cw_cloud(last_input, B, A, "last_input")
+        pred = self._vec(pred, B, torch.int32, "pred")
+        target = self._target(target, B)
+        loss = self._vec(loss, B, torch.float32, "loss")
+        n_ori = self._counts(n_ori, B)
+        out = self._diag(want, shapes, " | ".join(shapes))
+        ptr = lambda x: None if x is None else x.data_ptr()        # noqa: E731
+        diag = diag_type(*[ptr(out.get(k)) for k in shapes])
+        info = torch.empty(B, 3, device=self.device, dtype=torch.float32) if want_info else None
+        with torch.cuda.device(self.device):
+            self._check(fn(self.ctx, *lead, ptrs[0], pred.data_ptr(), ptr(loss), target.data_ptr(), ptrs[1], ptr(n_ori), li, ptr(info),
+                           C.byref(diag) if out else None, int(t), float(lr), float(scale), B, stride, *counts, self._stream()))
+        if want_info:
+            out["info"] = info
+        return out
+
+    def _adding_inputs(self, loss, pc, n_points, target):
+        """The front of add_attack, cluster_attack and object_attack -> (loss_kind, pc, n_points, B, stride, target)."""
+        loss_kind = self._loss_kind(loss)
+        pc, n_points = self._batch(pc, n_points)
+        B, stride = int(pc.shape[0]), int(pc.shape[1])
+        if B < 1 or stride < 1:
+            raise IfdError("empty batch")
+        return loss_kind, pc, n_points, B, stride, self._target(target, B)
+
+    def _adding_attack(self, fn, params, pc, n_points, target, between, A, out_stride, want_bounds):
+        """... and their end: the outputs of A added rows a cloud and the library call.  params: the call's struct; between: its
+        tensors (or None) between target and B."""
+        B, stride = int(pc.shape[0]), int(pc.shape[1])
+        out_stride = stride + A if out_stride is None else int(out_stride)
+        if out_stride < 1:
+            raise IfdError("out_stride must be positive")
+        out = torch.zeros(B, out_stride, 3, device=self.device, dtype=torch.float32)
+        best = torch.empty(B, device=self.device, dtype=torch.float32)
+        success = torch.empty(B, device=self.device, dtype=torch.int32)
+        bounds = torch.empty(3, B, device=self.device, dtype=torch.float64) if want_bounds else None
+        ptr = lambda x: None if x is None else x.data_ptr()        # noqa: E731
+        with torch.cuda.device(self.device):
+            self._check(fn(self.ctx, C.byref(params), pc.data_ptr(), ptr(n_points), target.data_ptr(), *[ptr(x) for x in between], B, stride,
+                           out_stride, out.data_ptr(), best.data_ptr(), success.data_ptr(), ptr(bounds), self._stream()))
+        if want_bounds:
+            return out, best, success.bool(), self._bounds(bounds)
+        return out, best, success.bool()
+
     def add_select(self, grad, pc, num_add, n_points=None, want_idx: bool = False):
         """The num_add rows of ``pc`` [B,N,3] with the largest gradient norm (ifd_add_select), in descending order of the score
         (gx*gx + gy*gy) + gz*gz, the lowest index first among equal scores: -> cri [B,num_add,3], with want_idx also idx
@@ -1158,30 +1234,11 @@ class Classifier:
         int32 (clouds outside the limits are left as allocated: NaN / -1)."""
         kind = self._add_kind(kind)
         num_add = self._add_num(num_add)
-        if not torch.is_tensor(cat) or cat.dim() != 3:
-            raise IfdError("cat must be a contiguous float32 [B,N,3] device tensor")
-        B, stride = int(cat.shape[0]), int(cat.shape[1])
+        B, _ = self._cat_dims(cat)
         st = self._cw_struct(state, B, num_add)
-        ptrs = [self._cw_cloud(x, B, stride, n) for x, n in ((grad, "grad"), (cat, "cat"))]
-        if grad is None:
-            raise IfdError("grad is missing")
-        li = self._cw_cloud(last_input, B, num_add, "last_input")
-        pred = self._vec(pred, B, torch.int32, "pred")
-        target = self._target(target, B)
-        loss = self._vec(loss, B, torch.float32, "loss")
-        n_ori = self._counts(n_ori, B)
         shapes = {"dist_grad": ((B, num_add, 3), torch.float32), "nn_ori": ((B, num_add), torch.int32), "far": ((B,), torch.int32)}
-        out = self._diag(want, shapes, "dist_grad | nn_ori | far")
-        ptr = lambda x: None if x is None else x.data_ptr()        # noqa: E731
-        diag = _lib.IfdAddDiag(*[ptr(out.get(k)) for k in ("dist_grad", "nn_ori", "far")])
-        info = torch.empty(B, 3, device=self.device, dtype=torch.float32) if want_info else None
-        with torch.cuda.device(self.device):
-            self._check(self.lib.ifd_add_step(self.ctx, kind, C.byref(st), ptrs[0], pred.data_ptr(), ptr(loss), target.data_ptr(), ptrs[1],
-                                              ptr(n_ori), li, ptr(info), C.byref(diag) if out else None, int(t), float(lr), float(scale),
-                                              B, stride, num_add, self._stream()))
-        if want_info:
-            out["info"] = info
-        return out
+        return self._adding_step(self.lib.ifd_add_step, [kind, C.byref(st)], [num_add], num_add, shapes, _lib.IfdAddDiag, grad, pred, target,
+                                 cat, t, lr, scale, loss, last_input, n_ori, want_info, want)
 
     def add_attack(self, kind, pc, target, num_add, noise=None, loss="logits", kappa=0., scale=1., attack_lr=1e-2, init_weight=5e3,
                    max_weight=4e4, binary_step=10, num_iter=500, n_points=None, out_stride=None, want_bounds: bool = False):
@@ -1191,41 +1248,13 @@ class Classifier:
         search step, or None.  out_stride: rows of the output, default N + num_add (rows beyond a cloud's n + num_add are zero)."""
         kind = self._add_kind(kind)
         num_add = self._add_num(num_add)
-        loss_kind = self._loss_kind(loss)
-        pc, n_points = self._batch(pc, n_points)
-        B, stride = int(pc.shape[0]), int(pc.shape[1])
-        if B < 1 or stride < 1:
-            raise IfdError("empty batch")
-        target = self._target(target, B)
-        if noise is not None:
-            noise = _f32(torch.as_tensor(noise), self.device)
-            if tuple(noise.shape) != (int(binary_step), B, num_add, 3):
-                raise IfdError("noise must be [binary_step,B,num_add,3]")
-        out_stride = stride + num_add if out_stride is None else int(out_stride)
-        if out_stride < 1:
-            raise IfdError("out_stride must be positive")
-        out = torch.zeros(B, out_stride, 3, device=self.device, dtype=torch.float32)
-        best = torch.empty(B, device=self.device, dtype=torch.float32)
-        success = torch.empty(B, device=self.device, dtype=torch.int32)
-        bounds = torch.empty(3, B, device=self.device, dtype=torch.float64) if want_bounds else None
+        loss_kind, pc, n_points, B, stride, target = self._adding_inputs(loss, pc, n_points, target)
+        noise = self._shaped(noise, (int(binary_step), B, num_add, 3), "noise must be [binary_step,B,num_add,3]")
         P = _lib.IfdAddParams(C.sizeof(_lib.IfdAddParams), kind, loss_kind, int(binary_step), int(num_iter), num_add, float(kappa),
                               float(scale), float(attack_lr), float(init_weight), float(max_weight))
-        with torch.cuda.device(self.device):
-            self._check(self.lib.ifd_add_attack(self.ctx, C.byref(P), pc.data_ptr(), None if n_points is None else n_points.data_ptr(),
-                                                target.data_ptr(), None if noise is None else noise.data_ptr(), B, stride, out_stride,
-                                                out.data_ptr(), best.data_ptr(), success.data_ptr(),
-                                                None if bounds is None else bounds.data_ptr(), self._stream()))
-        if want_bounds:
-            return out, best, success.bool(), self._bounds(bounds)
-        return out, best, success.bool()
+        return self._adding_attack(self.lib.ifd_add_attack, P, pc, n_points, target, [noise], num_add, out_stride, want_bounds)
 
     # ---- include/ifd_cluster.h: the CW cluster-adding attack (models without feature_transform) ----
-    def _cluster_rows(self, num_add, cl_num_p):
-        num_add, cl_num_p = int(num_add), int(cl_num_p)
-        if num_add < 1 or cl_num_p < 1 or not 1 <= num_add * cl_num_p <= _lib.ADD_MAX_ADD:
-            raise IfdError("num_add and cl_num_p must be at least 1 and num_add * cl_num_p in [1, %d]" % _lib.ADD_MAX_ADD)
-        return num_add, cl_num_p, num_add * cl_num_p
-
     def cluster_dbscan(self, pts, eps=0.2, min_samples=3, n_pts=None, want_count: bool = False):
         """DBSCAN of every cloud of ``pts`` [B,N,3] (or a ragged list) by the definition in include/ifd_cluster.h
         (ifd_cluster_dbscan): -> labels [B,N] int32 - clusters 0, 1, ... by ascending lowest core point, -1 for outliers and in the
@@ -1250,33 +1279,13 @@ class Classifier:
         [B,A,3]: as ``add_step`` takes them.  Returns a dict: with want_info "info" [B,3] (adversarial loss, dist * weight, dist), and
         the diagnostics named in ``want``: "dist_grad" [B,A,3], "nn_ori" [B,A] int32, "far_i" / "far_j" [B,num_add] int32, "far_val"
         [B,num_add] (clouds outside the limits are left as allocated: NaN / -1)."""
-        num_add, cl_num_p, A = self._cluster_rows(num_add, cl_num_p)
-        if not torch.is_tensor(cat) or cat.dim() != 3:
-            raise IfdError("cat must be a contiguous float32 [B,N,3] device tensor")
-        B, stride = int(cat.shape[0]), int(cat.shape[1])
+        num_add, cl_num_p, A = self._group_rows(num_add, cl_num_p, "cl_num_p")
+        B, _ = self._cat_dims(cat)
         st = self._cw_struct(state, B, A)
-        ptrs = [self._cw_cloud(x, B, stride, n) for x, n in ((grad, "grad"), (cat, "cat"))]
-        if grad is None:
-            raise IfdError("grad is missing")
-        li = self._cw_cloud(last_input, B, A, "last_input")
-        pred = self._vec(pred, B, torch.int32, "pred")
-        target = self._target(target, B)
-        loss = self._vec(loss, B, torch.float32, "loss")
-        n_ori = self._counts(n_ori, B)
-        names = ("dist_grad", "nn_ori", "far_i", "far_j", "far_val")
         shapes = {"dist_grad": ((B, A, 3), torch.float32), "nn_ori": ((B, A), torch.int32), "far_i": ((B, num_add), torch.int32),
                   "far_j": ((B, num_add), torch.int32), "far_val": ((B, num_add), torch.float32)}
-        out = self._diag(want, shapes, " | ".join(names))
-        ptr = lambda x: None if x is None else x.data_ptr()        # noqa: E731
-        diag = _lib.IfdClusterDiag(*[ptr(out.get(k)) for k in names])
-        info = torch.empty(B, 3, device=self.device, dtype=torch.float32) if want_info else None
-        with torch.cuda.device(self.device):
-            self._check(self.lib.ifd_cluster_step(self.ctx, C.byref(st), ptrs[0], pred.data_ptr(), ptr(loss), target.data_ptr(), ptrs[1],
-                                                  ptr(n_ori), li, ptr(info), C.byref(diag) if out else None, int(t), float(lr),
-                                                  float(scale), B, stride, num_add, cl_num_p, self._stream()))
-        if want_info:
-            out["info"] = info
-        return out
+        return self._adding_step(self.lib.ifd_cluster_step, [C.byref(st)], [num_add, cl_num_p], A, shapes, _lib.IfdClusterDiag, grad, pred,
+                                 target, cat, t, lr, scale, loss, last_input, n_ori, want_info, want)
 
     def cluster_attack(self, pc, target, clusters, num_add, cl_num_p, noise=None, loss="logits", kappa=0., scale=1., attack_lr=1e-2,
                        init_weight=5., max_weight=30., binary_step=5, num_iter=500, n_points=None, out_stride=None,
@@ -1285,46 +1294,16 @@ class Classifier:
         cl_num_p: -> (clouds [B,out_stride,3]: each cloud's originals bit for bit, then its A added points; best_dist [B] (1e10 where
         no iteration reached the target); success [B] bool) and with want_bounds also {"weight", "lower", "upper"} [B] float64.
         noise: [binary_step,B,A,3], the start noise of every search step, or None.  out_stride: rows of the output, default N + A."""
-        num_add, cl_num_p, A = self._cluster_rows(num_add, cl_num_p)
-        loss_kind = self._loss_kind(loss)
-        pc, n_points = self._batch(pc, n_points)
-        B, stride = int(pc.shape[0]), int(pc.shape[1])
-        if B < 1 or stride < 1:
-            raise IfdError("empty batch")
-        target = self._target(target, B)
-        clusters = _f32(torch.as_tensor(clusters), self.device)
-        if tuple(clusters.shape) != (B, A, 3):
-            raise IfdError("clusters must be [B,num_add*cl_num_p,3]")
-        if noise is not None:
-            noise = _f32(torch.as_tensor(noise), self.device)
-            if tuple(noise.shape) != (int(binary_step), B, A, 3):
-                raise IfdError("noise must be [binary_step,B,num_add*cl_num_p,3]")
-        out_stride = stride + A if out_stride is None else int(out_stride)
-        if out_stride < 1:
-            raise IfdError("out_stride must be positive")
-        out = torch.zeros(B, out_stride, 3, device=self.device, dtype=torch.float32)
-        best = torch.empty(B, device=self.device, dtype=torch.float32)
-        success = torch.empty(B, device=self.device, dtype=torch.int32)
-        bounds = torch.empty(3, B, device=self.device, dtype=torch.float64) if want_bounds else None
+        num_add, cl_num_p, A = self._group_rows(num_add, cl_num_p, "cl_num_p")
+        loss_kind, pc, n_points, B, stride, target = self._adding_inputs(loss, pc, n_points, target)
+        clusters = self._shaped(torch.as_tensor(clusters), (B, A, 3), "clusters must be [B,num_add*cl_num_p,3]")
+        noise = self._shaped(noise, (int(binary_step), B, A, 3), "noise must be [binary_step,B,num_add*cl_num_p,3]")
         P = _lib.IfdClusterParams(C.sizeof(_lib.IfdClusterParams), loss_kind, int(binary_step), int(num_iter), num_add, cl_num_p,
                                   float(kappa), float(scale), float(attack_lr), float(init_weight), float(max_weight))
-        with torch.cuda.device(self.device):
-            self._check(self.lib.ifd_cluster_attack(self.ctx, C.byref(P), pc.data_ptr(), None if n_points is None else n_points.data_ptr(),
-                                                    target.data_ptr(), clusters.data_ptr(), None if noise is None else noise.data_ptr(), B,
-                                                    stride, out_stride, out.data_ptr(), best.data_ptr(), success.data_ptr(),
-                                                    None if bounds is None else bounds.data_ptr(), self._stream()))
-        if want_bounds:
-            return out, best, success.bool(), self._bounds(bounds)
-        return out, best, success.bool()
+        return self._adding_attack(self.lib.ifd_cluster_attack, P, pc, n_points, target, [clusters, noise], A, out_stride, want_bounds)
 
     # ---- include/ifd_object.h: the CW object-adding attack (models without feature_transform) ----
     OBJECT_POSE = (("shift", 3), ("angle", 1), ("shift_m", 3), ("shift_v", 3), ("angle_m", 1), ("angle_v", 1))
-
-    def _object_rows(self, num_add, obj_num_p):
-        num_add, obj_num_p = int(num_add), int(obj_num_p)
-        if num_add < 1 or obj_num_p < 1 or not 1 <= num_add * obj_num_p <= _lib.ADD_MAX_ADD:
-            raise IfdError("num_add and obj_num_p must be at least 1 and num_add * obj_num_p in [1, %d]" % _lib.ADD_MAX_ADD)
-        return num_add, obj_num_p, num_add * obj_num_p
 
     def _object_template(self, objects, num_add, obj_num_p):
         objects = _f32(torch.as_tensor(objects), self.device)
@@ -1337,7 +1316,7 @@ class Classifier:
         the object rows, "o_bestattack" holds world rows - and "obj" [B,A,3], "shift" [B,num_add,3], "angle" [B,num_add] with the pose
         moments "shift_m", "shift_v", "angle_m", "angle_v", all zero.  ``cw_adjust`` works on it as it is; the pose moments are the
         caller's to zero at the start of a search step."""
-        num_add, obj_num_p, A = self._object_rows(num_add, obj_num_p)
+        num_add, obj_num_p, A = self._group_rows(num_add, obj_num_p, "obj_num_p")
         state = self.cw_state(B, A, init_weight, max_weight)
         state["obj"] = torch.zeros(B, A, 3, device=self.device, dtype=torch.float32)
         for key, width in self.OBJECT_POSE:
@@ -1360,10 +1339,8 @@ class Classifier:
         """world = rotate_shift(obj, angle, shift) (ifd_object_place) IN PLACE into the added rows of ``cat`` [B,N,3]: obj [B,A,3],
         angle [B,num_add] about the y axis, shift [B,num_add,3]; cloud b has n_ori[b] originals (None: N - A) in front of its A =
         num_add * obj_num_p added rows.  Returns ``cat``."""
-        num_add, obj_num_p, A = self._object_rows(num_add, obj_num_p)
-        if not torch.is_tensor(cat) or cat.dim() != 3:
-            raise IfdError("cat must be a contiguous float32 [B,N,3] device tensor")
-        B, stride = int(cat.shape[0]), int(cat.shape[1])
+        num_add, obj_num_p, A = self._group_rows(num_add, obj_num_p, "obj_num_p")
+        B, stride = self._cat_dims(cat)
         self._cw_cloud(cat, B, stride, "cat")
         obj = _f32(torch.as_tensor(obj), self.device)
         angle = _f32(torch.as_tensor(angle), self.device)
@@ -1385,34 +1362,14 @@ class Classifier:
         pred, loss, last_input [B,A,3]: as ``add_step`` takes them.  Returns a dict: with want_info "info" [B,3] (adversarial loss,
         dist * weight, dist), and the diagnostics named in ``want``: "obj_grad" [B,A,3], "nn_ori" [B,A] int32, "g_shift" [B,num_add,3],
         "g_angle" [B,num_add], "l2" [B], "cd" [B] (clouds outside the limits are left as allocated: NaN / -1)."""
-        num_add, obj_num_p, A = self._object_rows(num_add, obj_num_p)
-        if not torch.is_tensor(cat) or cat.dim() != 3:
-            raise IfdError("cat must be a contiguous float32 [B,N,3] device tensor")
-        B, stride = int(cat.shape[0]), int(cat.shape[1])
+        num_add, obj_num_p, A = self._group_rows(num_add, obj_num_p, "obj_num_p")
+        B, _ = self._cat_dims(cat)
         st = self._object_struct(state, B, num_add, A)
         objects = self._object_template(objects, num_add, obj_num_p)
-        ptrs = [self._cw_cloud(x, B, stride, n) for x, n in ((grad, "grad"), (cat, "cat"))]
-        if grad is None:
-            raise IfdError("grad is missing")
-        li = self._cw_cloud(last_input, B, A, "last_input")
-        pred = self._vec(pred, B, torch.int32, "pred")
-        target = self._target(target, B)
-        loss = self._vec(loss, B, torch.float32, "loss")
-        n_ori = self._counts(n_ori, B)
-        names = ("obj_grad", "nn_ori", "g_shift", "g_angle", "l2", "cd")
         shapes = {"obj_grad": ((B, A, 3), torch.float32), "nn_ori": ((B, A), torch.int32), "g_shift": ((B, num_add, 3), torch.float32),
                   "g_angle": ((B, num_add), torch.float32), "l2": ((B,), torch.float32), "cd": ((B,), torch.float32)}
-        out = self._diag(want, shapes, " | ".join(names))
-        ptr = lambda x: None if x is None else x.data_ptr()        # noqa: E731
-        diag = _lib.IfdObjectDiag(*[ptr(out.get(k)) for k in names])
-        info = torch.empty(B, 3, device=self.device, dtype=torch.float32) if want_info else None
-        with torch.cuda.device(self.device):
-            self._check(self.lib.ifd_object_step(self.ctx, C.byref(st), objects.data_ptr(), ptrs[0], pred.data_ptr(), ptr(loss),
-                                                 target.data_ptr(), ptrs[1], ptr(n_ori), li, ptr(info), C.byref(diag) if out else None,
-                                                 int(t), float(lr), float(scale), B, stride, num_add, obj_num_p, self._stream()))
-        if want_info:
-            out["info"] = info
-        return out
+        return self._adding_step(self.lib.ifd_object_step, [C.byref(st), objects.data_ptr()], [num_add, obj_num_p], A, shapes,
+                                 _lib.IfdObjectDiag, grad, pred, target, cat, t, lr, scale, loss, last_input, n_ori, want_info, want)
 
     def object_attack(self, pc, target, objects, centers, angles0, noise_obj=None, noise_shift=None, loss="logits", kappa=0., scale=1.,
                       attack_lr=1e-2, init_weight=5., max_weight=40., binary_step=5, num_iter=500, n_points=None, out_stride=None,
@@ -1426,46 +1383,20 @@ class Classifier:
         objects = _f32(torch.as_tensor(objects), self.device)
         if objects.dim() != 3 or int(objects.shape[2]) != 3:
             raise IfdError("objects must be [num_add,obj_num_p,3]")
-        num_add, obj_num_p, A = self._object_rows(objects.shape[0], objects.shape[1])
-        loss_kind = self._loss_kind(loss)
-        pc, n_points = self._batch(pc, n_points)
-        B, stride = int(pc.shape[0]), int(pc.shape[1])
-        if B < 1 or stride < 1:
-            raise IfdError("empty batch")
-        target = self._target(target, B)
+        num_add, obj_num_p, A = self._group_rows(objects.shape[0], objects.shape[1], "obj_num_p")
+        loss_kind, pc, n_points, B, stride, target = self._adding_inputs(loss, pc, n_points, target)
         steps = int(binary_step)
-
-        def arr(x, shape, what):
-            if x is None:
-                return None
-            x = _f32(torch.as_tensor(x), self.device)
-            if tuple(x.shape) != shape:
-                raise IfdError("%s must be %s" % (what, list(shape)))
-            return x
+        arr = lambda x, shape, what: self._shaped(x, shape, "%s must be %s" % (what, list(shape)))       # noqa: E731
         centers = arr(centers, (B, num_add, 3), "centers")
         angles0 = arr(angles0, (steps, B, num_add), "angles0")
         if centers is None or angles0 is None:
             raise IfdError("centers and angles0 are needed")
         noise_obj = arr(noise_obj, (steps, B, A, 3), "noise_obj")
         noise_shift = arr(noise_shift, (steps, B, num_add, 3), "noise_shift")
-        out_stride = stride + A if out_stride is None else int(out_stride)
-        if out_stride < 1:
-            raise IfdError("out_stride must be positive")
-        out = torch.zeros(B, out_stride, 3, device=self.device, dtype=torch.float32)
-        best = torch.empty(B, device=self.device, dtype=torch.float32)
-        success = torch.empty(B, device=self.device, dtype=torch.int32)
-        bounds = torch.empty(3, B, device=self.device, dtype=torch.float64) if want_bounds else None
         P = _lib.IfdObjectParams(C.sizeof(_lib.IfdObjectParams), loss_kind, steps, int(num_iter), num_add, obj_num_p, float(kappa),
                                  float(scale), float(attack_lr), float(init_weight), float(max_weight))
-        ptr = lambda x: None if x is None else x.data_ptr()        # noqa: E731
-        with torch.cuda.device(self.device):
-            self._check(self.lib.ifd_object_attack(self.ctx, C.byref(P), pc.data_ptr(), ptr(n_points), target.data_ptr(),
-                                                   objects.data_ptr(), centers.data_ptr(), ptr(noise_obj), ptr(noise_shift),
-                                                   angles0.data_ptr(), B, stride, out_stride, out.data_ptr(), best.data_ptr(),
-                                                   success.data_ptr(), ptr(bounds), self._stream()))
-        if want_bounds:
-            return out, best, success.bool(), self._bounds(bounds)
-        return out, best, success.bool()
+        return self._adding_attack(self.lib.ifd_object_attack, P, pc, n_points, target, [objects, centers, noise_obj, noise_shift, angles0],
+                                   A, out_stride, want_bounds)
 
     # ---- include/ifd_drop.h: the saliency Drop attack (models without feature_transform) ----
     def drop_step(self, grad, pc, n_points, k, alpha=1., index=None, want=()):

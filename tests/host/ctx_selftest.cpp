@@ -73,7 +73,7 @@ void classifier_layouts() {
     for (int B : BS)
         for (int stride : STRIDES) {
             const int chunk = rec_chunk(B);
-            CHECK(atk_chunk(B) == chunk, "B %d", B);
+            CHECK(even_chunk(B, ClsVictim::CHUNK) == chunk, "B %d", B);
             for (bool ft : {false, true}) {
                 const size_t want = 256 + rec_cls_per_cloud(stride, ft) * (size_t)chunk;
                 CHECK(cls_ws_bytes(chunk, stride, ft) == want, "cls B %d stride %d ft %d", B, stride, (int)ft);
@@ -86,7 +86,7 @@ void classifier_layouts() {
                 check_ptrs("cls", ptrs, want);
             }
             const size_t want = 256 + rec_grad_per_cloud(stride) * (size_t)chunk;
-            CHECK(atk_grad_ws_bytes(B, stride) == want, "grad B %d stride %d", B, stride);
+            CHECK(grad_ws_bytes<ClsVictim>(nullptr, B, stride) == want, "grad B %d stride %d", B, stride);
             Carve c(g_base);
             const ClsGradWs w = cls_grad_ws(c, (size_t)chunk, stride);
             CHECK(c.bytes() == want && (const char*)w.part == g_base + 256, "grad carve B %d stride %d", B, stride);
@@ -94,8 +94,8 @@ void classifier_layouts() {
                                 P(w.f2), P(w.trans), P(w.logits), P(w.d_out), P(w.d2), P(w.d1), P(w.g), P(w.pred), P(w.loss)}, want);
             // the loops' workspaces: state + the larger of the two calls behind it
             const size_t fwd = 256 + rec_cls_per_cloud(stride, false) * (size_t)chunk;
-            CHECK(atk_loop_ws_bytes(B, stride, 512, true) == 512 + std::max(want, fwd), "loop ws B %d stride %d", B, stride);
-            CHECK(atk_loop_ws_bytes(B, stride, 512, false) == 512 + want, "loop ws B %d stride %d", B, stride);
+            CHECK(loop_ws_bytes<ClsVictim>(nullptr, B, stride, 512, true) == 512 + std::max(want, fwd), "loop ws B %d stride %d", B, stride);
+            CHECK(loop_ws_bytes<ClsVictim>(nullptr, B, stride, 512, false) == 512 + want, "loop ws B %d stride %d", B, stride);
         }
 }
 
@@ -137,14 +137,29 @@ void loop_states() {
             for (int num_add : {1, 1024}) {
                 const size_t G = (size_t)stride, na = (size_t)num_add, added = b * na * 12;
                 const size_t want = up256(b * (12 * G + 60 * na + 52));
-                CHECK(carved_bytes([&](Carve& c) { AddLoop(c, b, G, na); }) == want, "add B %d G %d num_add %d", B, stride, num_add);
+                CHECK(carved_bytes([&](Carve& c) { AddingLoop(c, b, G, na, na, 0); }) == want, "add B %d G %d num_add %d", B, stride, num_add);
                 Carve c(g_base);
-                const AddLoop L(c, b, G, na);
-                const CwState& S = L.f.S;
-                check_ptrs("add", {P(S.weight), P(S.lower), P(S.upper), P(S.bestdist), P(S.bestscore), P(S.o_bestscore), P(L.f.pred), P(L.f.loss),
+                const AddingLoop L(c, b, G, na, na, 0);
+                const CwState& S = L.S.cw;
+                check_ptrs("add", {P(S.weight), P(S.lower), P(S.upper), P(S.bestdist), P(S.bestscore), P(S.o_bestscore), P(L.pred), P(L.loss),
                                    P(L.n_cat), P(L.n_ori), P(L.grad), P(L.cri), P(S.m), P(S.v), P(S.o_bestattack), P(L.last)}, want);
                 CHECK((const char*)S.v == (const char*)S.m + added && (const char*)S.o_bestattack == (const char*)S.v + added,
                       "add: m, v and o_bestattack side by side");
+                // the same loop without critical points (Add-Cluster: A = num_add rows), and with `pose` poses behind it (Add-Objects)
+                CHECK(carved_bytes([&](Carve& c) { AddingLoop(c, b, G, na, 0, 0); }) == up256(b * (12 * G + 48 * na + 52)),
+                      "cluster B %d G %d A %d", B, stride, num_add);
+                for (size_t pose : {(size_t)1, na}) {
+                    const size_t want_o = up256(b * (12 * G + 60 * na + 52 + 48 * pose));
+                    CHECK(carved_bytes([&](Carve& c) { AddingLoop(c, b, G, na, 0, pose); }) == want_o, "object B %d G %d A %d", B, stride, num_add);
+                    Carve co(g_base);
+                    const AddingLoop O(co, b, G, na, 0, pose);
+                    const ObjectState& T = O.S;
+                    check_ptrs("object", {P(T.cw.weight), P(T.cw.lower), P(T.cw.upper), P(T.cw.bestdist), P(T.cw.bestscore), P(T.cw.o_bestscore),
+                                          P(O.pred), P(O.loss), P(O.n_cat), P(O.n_ori), P(O.grad), P(T.cw.m), P(T.cw.v), P(T.cw.o_bestattack),
+                                          P(O.last), P(T.obj), P(T.shift), P(T.angle), P(T.shift_m), P(T.shift_v), P(T.angle_m), P(T.angle_v)},
+                               want_o);
+                    CHECK((const char*)T.obj == (const char*)O.last + added, "object: the object rows lie behind last");
+                }
             }
         }
 }

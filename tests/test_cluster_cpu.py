@@ -266,7 +266,7 @@ def test_cluster_header_symbols_exported_and_bound(lib):
     assert len(declared_symbols(os.path.join(ROOT, "include", "ifd_cw.h"))) == 4 and lib.ifd_cw_abi_version() == 1
     for k in ("cluster_dbscan", "cluster_step", "cluster_attack"):
         assert callable(getattr(I.Classifier, k))
-    src = open(os.path.join(ROOT, "if-defense_amd", "attack.py")).read() + open(os.path.join(ROOT, "if-defense_amd", "cluster_attack.py")).read()
+    src = "".join(open(os.path.join(ROOT, "if-defense_amd", f)).read() for f in ("attack.py", "cluster_attack.py", "attack_cli.py"))
     assert "sklearn" not in src.replace("sklearn's", "")              # named in the docstring only, never imported
 
 

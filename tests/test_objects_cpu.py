@@ -205,7 +205,7 @@ def test_object_header_symbols_exported_and_bound(lib):
     assert len(declared_symbols(os.path.join(ROOT, "include", "ifd_cluster.h"))) == 4 and lib.ifd_cluster_abi_version() == 1
     for k in ("object_state", "object_place", "object_step", "object_attack"):
         assert callable(getattr(I.Classifier, k))
-    src = open(os.path.join(ROOT, "if-defense_amd", "attack.py")).read() + open(os.path.join(ROOT, "if-defense_amd", "object_attack.py")).read()
+    src = "".join(open(os.path.join(ROOT, "if-defense_amd", f)).read() for f in ("attack.py", "object_attack.py", "attack_cli.py"))
     assert "sklearn" not in src.replace("sklearn's", "")              # named in the docstrings only, never imported
 
 
